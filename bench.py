@@ -43,8 +43,8 @@ from benchlib import multigpu  # noqa: E402
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --config 5: 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; --config 5: 1)")
     ap.add_argument("--beams", type=int, default=64)
     ap.add_argument("--azimuths", type=int, default=1024)
     ap.add_argument("--high-resolution", type=float, default=0.10)
@@ -66,6 +66,8 @@ def parse():
                     help="skips the config-5 line (N = 1: two submaps, four grids, three steps; N > 1: the sharded one)")
     ap.add_argument("--no-rccl-check", action="store_true",
                     help="N = 1: skips the one-rank run of the library's RCCL entry point")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="writes what the last timed step computed to DIR/<name>.npy (benchlib/outputs.py)")
     # internal: scene + 3 matches, no timing
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -73,8 +75,12 @@ def parse():
         a.beams, a.azimuths, a.high_resolution = 128, 2048, 0.05
         a.map_scans = min(a.map_scans, 3)
         a.distinct_scans = min(a.distinct_scans, 2)
-        if a.steps == 20 and a.warmup == 3:  # the defaults: a config-5 step takes ~0.4 s
+        if a.steps is None and a.warmup is None:  # a config-5 step takes ~0.4 s
             a.steps, a.warmup = 5, 1
+    a.steps = 20 if a.steps is None else a.steps
+    a.warmup = 3 if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup not negative")
     return a
 
 
@@ -182,6 +188,7 @@ def main():
                             coll_clock.wrap(lambda v: sharded.all_reduce_max_int(v, dist, dev)))
     stage = {"rtcsm": 0.0, "ceres": 0.0, "insert": 0.0}
     evals = []
+    last = {}  # what the last timed step computed (--dump-outputs)
     use_shards = [sharded_mode]  # flipped for the second (config 4) line of an N > 1 replica run
 
     def step(i, timed):
@@ -189,9 +196,9 @@ def main():
         a = time.perf_counter()
         if use_shards[0]:
             # dliom_rtcsm3d_match_sharded: own rotations, own exact winner, ONE 8-byte max all-reduce (RCCL)
-            _, p1 = sharded_rtcsm(shard, sc, g_hi)
+            s1, p1 = sharded_rtcsm(shard, sc, g_hi)
         else:
-            _, p1 = rt.Match(sc["init"], sc["cloud"], g_hi)
+            s1, p1 = rt.Match(sc["init"], sc["cloud"], g_hi)
         b = time.perf_counter()
         p2, summ = cs.Match(sc["init"][:3], p1, [(sc["cloud"], g_hi), (sc["cloud"], g_lo)])
         c = time.perf_counter()
@@ -207,6 +214,7 @@ def main():
             stage["ceres"] += c - b
             stage["insert"] += d - c
             evals.append(summ["num_residual_evaluations"])
+            last.update(rtcsm_score=s1, rtcsm_pose=p1, ceres_pose=p2, ceres_summary=summ)
         return p2
 
     def fence():
@@ -243,6 +251,12 @@ def main():
         elapsed = float(t.item())
 
     gc.enable()
+    # the grids as the last timed step left them: every later leg inserts into them again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        from benchlib import outputs
+        dumped = outputs.dump(args.dump_outputs, last, [("hi", g_hi), ("lo", g_lo)] +
+                              list(zip(("second_hi", "second_lo"), SECOND_SUBMAP)))
     score_ms, score_n = ctx.kernel_time(dl.KERNEL_RTCSM_SCORE)
     ctx.set_profiling(0)
     # N > 1 replica run: the same scans once more with the search window SHARDED over the ranks (BASELINE config 4).
@@ -393,6 +407,8 @@ def main():
             "kernel_ms_per_scan": breakdown,
             "roofline": roofline_block(args, pairs, k_ms, int(score_n), alg_bytes, int(st.score_kernel)),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if rccl_one_rank is not None:
             out["sharded_rccl_one_rank"] = rccl_one_rank
         if sharded_line is not None:

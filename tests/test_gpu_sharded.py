@@ -1,11 +1,17 @@
-"""BASELINE config 4 through the C entry points: dliom_rtcsm3d_match_sharded with a gloo collective between two and
-between EIGHT processes (all on GPU 0 -- the collective is the caller's, so a one-GPU box can run the N-rank protocol,
+"""BASELINE config 4 through the C entry points: dliom_rtcsm3d_match_sharded with a collective between two and
+between EIGHT ranks (all on GPU 0 -- the collective is the caller's, so a one-GPU box can run the N-rank protocol,
 including the rank that fails before the exchange), and
-dliom_rtcsm3d_match_sharded_rccl on a one-rank RCCL communicator (ncclAllReduce really runs)."""
+dliom_rtcsm3d_match_sharded_rccl on a one-rank RCCL communicator (ncclAllReduce really runs).
+
+At most MAX_RANK_PROCESSES processes open the GPU besides the pytest process (a shared GPU admits only a few processes
+at a time): eight ranks run as two threads in each of four processes (calls on different contexts are concurrency-safe,
+include/dliom.h).  A rank's MAX all-reduce meets its process's other ranks at a barrier and goes between the processes
+as one gloo all-reduce."""
 import ctypes as C
 import os
 import socket
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -33,13 +39,111 @@ def _scene(dl, ctx):
     return orc, og, to_device_grid(dl, ctx, og), pts, init, DEFAULT_RTCSM
 
 
-def _worker(rank, world, port, ret):
+MAX_RANK_PROCESSES = 4
+
+
+class _ProcessRanks:
+    """The ranks of one process, one thread each: the MAX all-reduce meets at a barrier here, and the barrier's action
+    runs the gloo all-reduce between the processes (one gloo rank per process)."""
+
+    def __init__(self, num_local):
+        import threading
+        self.values = [0] * num_local
+        self.barrier = threading.Barrier(num_local, action=self._reduce)
+        self.result = None
+
+    def _reduce(self):
+        import torch
+        import torch.distributed as dist
+        t = torch.tensor([max(self.values)], dtype=torch.int64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        self.result = int(t.item())
+
+    def exchange(self, local, value):
+        self.values[local] = value
+        self.barrier.wait(timeout=300)
+        return self.result
+
+
+class _RankDist:
+    """What dliom.sharded uses of torch.distributed, for one rank of a _ProcessRanks."""
+
+    def __init__(self, ranks, local, world):
+        import torch.distributed as dist
+        self.ReduceOp = dist.ReduceOp
+        self.ranks, self.local, self.world = ranks, local, world
+
+    def is_initialized(self):
+        return True
+
+    def get_world_size(self):
+        return self.world
+
+    def all_reduce(self, t, op):
+        assert op == self.ReduceOp.MAX and t.numel() == 1
+        t.fill_(self.ranks.exchange(self.local, int(t.item())))
+
+
+def _rank_groups(world):
+    per = -(-world // MAX_RANK_PROCESSES)
+    return [list(range(r, min(r + per, world))) for r in range(0, world, per)]
+
+
+def _process(body, index, groups, world, port, ret):
+    """One process: gloo rank `index` among len(groups) processes, the world ranks groups[index] on threads."""
+    import threading
     for p in (ROOT, os.path.join(ROOT, "d-liom_amd"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", rank=index, world_size=len(groups))
+    import dliom as dl
+    from oracle import oracle as orc
+    dl.load_library()
+    orc.lib()
+    ranks = _ProcessRanks(len(groups[index]))
+
+    def run(local, rank):
+        try:
+            ret[rank] = body(rank, world, _RankDist(ranks, local, world))
+        except Exception as e:
+            ret[rank] = "%s: %s" % (type(e).__name__, e)
+            ranks.barrier.abort()
+
+    threads = [threading.Thread(target=run, args=(i, r)) for i, r in enumerate(groups[index])]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _run_world(body, world, timeout):
+    import torch.multiprocessing as mp
+    mpc = mp.get_context("spawn")
+    ret = mpc.Manager().dict()
+    port = _free_port()
+    groups = _rank_groups(world)
+    assert len(groups) <= MAX_RANK_PROCESSES
+    procs = [mpc.Process(target=_process, args=(body, i, groups, world, port, ret)) for i in range(len(groups))]
+    deadline = time.monotonic() + timeout
+    try:
+        for p in procs:
+            p.start()
+        for p in procs:
+            p.join(max(0.0, deadline - time.monotonic()))
+            assert p.exitcode == 0, "a rank process hung or crashed: %s" % dict(ret)
+    finally:
+        for p in procs:  # the others wait in the collective for a rank that is gone
+            if p.is_alive():
+                p.kill()
+                p.join()
+    return dict(ret)
+
+
+def _worker(rank, world, dist):
     import dliom as dl
     from dliom import sharded
     ctx = dl.Context(0)
@@ -48,37 +152,24 @@ def _worker(rank, world, port, ret):
     shard = dl.RtcsmShard(ctx, opts, rank, world)
     score, pose = sharded.sharded_match(shard, init, cloud, dg, dist=dist)  # -> dliom_rtcsm3d_match_sharded
     ref = orc.rtcsm3d_match(opts, init, pts, og)
-    ret[rank] = bool(np.float32(score) == np.float32(ref["score"]) and np.array_equal(pose, ref["pose"]))
-    dist.barrier()
-    dist.destroy_process_group()
+    ok = bool(np.float32(score) == np.float32(ref["score"]) and np.array_equal(pose, ref["pose"]))
+    cloud.close()
+    dg.close()
+    ctx.close()
+    return ok
 
 
 @pytest.mark.parametrize("world", [2, 8])
 def test_ranks_one_collective_through_the_c_entry_point(world):
     """world = 8 is the control flow of the driver's 8-GPU run (eight shards of the rotations, one exchange) with every
     rank on GPU 0: the collective is the caller's, so a one-GPU box can run it."""
-    import torch.multiprocessing as mp
-    mpc = mp.get_context("spawn")
-    ret = mpc.Manager().dict()
-    port = _free_port()
-    procs = [mpc.Process(target=_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(600)
-        assert p.exitcode == 0
-    assert all(ret.get(r) is True for r in range(world)), dict(ret)
+    ret = _run_world(_worker, world, 600)
+    assert all(ret.get(r) is True for r in range(world)), ret
 
 
-def _failing_worker(rank, world, port, ret):
+def _failing_worker(rank, world, dist):
     """The last rank hands in an empty cloud (DLIOM_ERR_EMPTY_CLOUD before any kernel): it must still join the collective,
     and every other rank must come back with DLIOM_ERR_PEER_FAILED instead of hanging in the all-reduce."""
-    for p in (ROOT, os.path.join(ROOT, "d-liom_amd"), os.path.join(ROOT, "tests")):
-        sys.path.insert(0, p)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     import dliom as dl
     from dliom import sharded
     ctx = dl.Context(0)
@@ -87,27 +178,20 @@ def _failing_worker(rank, world, port, ret):
     shard = dl.RtcsmShard(ctx, opts, rank, world)
     try:
         sharded.sharded_match(shard, init, cloud, dg, dist=dist)
-        ret[rank] = "no error"
+        status = "no error"
     except dl.DliomError as e:
-        ret[rank] = e.status
-    dist.barrier()
-    dist.destroy_process_group()
+        status = e.status
+    cloud.close()
+    dg.close()
+    ctx.close()
+    return status
 
 
 @pytest.mark.parametrize("world", [2, 8])
 def test_a_failing_rank_still_joins_the_collective(world):
-    import torch.multiprocessing as mp
     import dliom as dl
-    mpc = mp.get_context("spawn")
-    ret = mpc.Manager().dict()
-    port = _free_port()
-    procs = [mpc.Process(target=_failing_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(300)
-        assert p.exitcode == 0, "a rank hung or crashed"
-    assert all(ret.get(r) == dl.ERR_PEER_FAILED for r in range(world - 1)) and ret.get(world - 1) == dl.ERR_EMPTY_CLOUD, dict(ret)
+    ret = _run_world(_failing_worker, world, 300)
+    assert all(ret.get(r) == dl.ERR_PEER_FAILED for r in range(world - 1)) and ret.get(world - 1) == dl.ERR_EMPTY_CLOUD, ret
 
 
 def _rccl_one_rank_main():
