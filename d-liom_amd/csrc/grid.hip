@@ -10,8 +10,6 @@
 // (hybrid_grid.h:143-409) into one dependent load while keeping its 1 KiB
 // leaves, its index range [-32<<bits, 32<<bits) and its growth rule.
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -1247,19 +1245,6 @@ int dliom_inserter_insert_cloud_multi(const dliom_inserter* ins, int num_targets
   if (n == 0) return DLIOM_OK;
   if (n > (int64_t{1} << 30)) return DLIOM_ERR_INVALID_ARGUMENT;
   dliom_ctx* ctx = grids[0]->ctx;
-#ifdef DLIOM_EXPERIMENTS
-  static const int timing = tuning_int("DLIOM_TIMING", 0);
-  const auto t_begin = std::chrono::steady_clock::now();
-  struct TimingGuard {
-    std::chrono::steady_clock::time_point t0;
-    int on;
-    const char* path = "scan";
-    ~TimingGuard() {
-      if (on) std::fprintf(stderr, "TIMING insert (%s): %.1f us on the host\n", path,
-                           std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-    }
-  } timing_guard{t_begin, timing};
-#endif
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   MultiInsertArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1316,9 +1301,6 @@ int dliom_inserter_insert_cloud_multi(const dliom_inserter* ins, int num_targets
     hipLaunchKernelGGL(multi_insert_kernel<4>, grid_dim, block, 0, ctx->stream, a);
     ctx->end_span(span);
     DLIOM_HIP_TRY(hipGetLastError());
-#ifdef DLIOM_EXPERIMENTS
-    timing_guard.path = "proven";
-#endif
     return DLIOM_OK;
   }
   DLIOM_TRY(ctx->misc.reserve(256));

@@ -7,18 +7,25 @@
 //   host   window sizes, the (2A+1)^3 candidate rotations normalized(q_init * q_r) and the
 //          (2L+1)^3 candidate translations q_init * t_j + t_init, in the reference's float
 //          arithmetic (candidate c = j * R + r in generation order z,y,x,rz,ry,rx)
-//   GPU A  score volume: exact integer sum_i max(v_i & 0x7fff, 1) per candidate
-//          (rtcsm_score_dense_kernel over the grid's bricked dense mirror; the two leaf-table
-//          kernels above it are the fallbacks for grids whose mirror would not fit)
+//   GPU A  score volume: exact integer sum_i max(v_i & 0x7fff, 1) per candidate.  run_score_volume
+//          starts from the mapping DLIOM_TUNE_SCORE_KERNEL asks for (3 by default) and falls back:
+//            3  LDS-box kernel over the grid's dense mirror (score_box.h), when the search suits it:
+//               >= 8 translations, >= 2^24 candidate-point pairs, bits <= 7, no refusal of its own
+//            2  rotation per lane over the dense mirror (rtcsm_score_dense_kernel): searches the box
+//               kernel refuses (W-ref's small ones), and the redo of a match the box kernel flagged
+//            1  rotation per lane over the leaf table (rtcsm_score_rot_kernel): grids whose mirror is
+//               windowed (bits >= 5) or was not built
+//            0  point per lane over the leaf table (rtcsm_score_kernel): bits = 8, whose leaf table
+//               needs 64-bit indices
 //   GPU B  rigorous float-score interval per candidate from that sum; candidates whose upper
 //          bound reaches the best lower bound survive
 //   GPU C  survivors only: the reference's SEQUENTIAL float sum in point order, bit-identical,
-//          evaluated in parallel (chunk functions + binade-wise scan; element scan and serial
-//          replay kept as cross-checks)
+//          evaluated in parallel by chunk functions + binade-wise scan (method 2); clouds of at most
+//          1 024 points replay the loop in one lane instead (method 0).  The element scan (method 1)
+//          runs only when dliom_rtcsm3d_sequential_sums asks for it
 //   host   score = sum / N * exp(-(|t| wt + angle wr)^2) as the reference computes it; first
 //          strictly greater score in generation order wins.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -50,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void rtcsm_score_kernel(
     GridView g, const float* __restrict__ px, const float* __restrict__ py,
     const float* __restrict__ pz, const float4* __restrict__ rot, int R, int r_first, int r_last,
     const float* __restrict__ trans, int T, int rots_per_block,
-    unsigned long long* __restrict__ sums, int debug_no_atomic) {
+    unsigned long long* __restrict__ sums) {
   // Clouds are padded to a multiple of 4096 points with far-away points (kPadCoordinate): those
   // fall outside every grid, read 0 and add exactly 1 each -- the host subtracts the pad count.
   extern __shared__ unsigned block_sum[];  // T entries
@@ -113,10 +120,8 @@ __global__ __launch_bounds__(kBlock) void rtcsm_score_kernel(
       if (lane == 63) atomicAdd(&block_sum[j], total);
     }
     __syncthreads();
-    if (!debug_no_atomic) {
-      for (int j = threadIdx.x; j < T; j += kBlock)
-        atomicAdd(&sums[static_cast<size_t>(j) * R + r], static_cast<unsigned long long>(block_sum[j]));
-    }
+    for (int j = threadIdx.x; j < T; j += kBlock)
+      atomicAdd(&sums[static_cast<size_t>(j) * R + r], static_cast<unsigned long long>(block_sum[j]));
   }
 }
 
@@ -240,16 +245,13 @@ struct DenseDomain {
   float pad[3];
 };
 
-// DEBUG != 0 are TIMING-ONLY variants (wrong sums) that isolate one pipe each (DLIOM_SCORE_DEBUG,
-// profiles/r2_score_pipe_experiment.json): 1 = all index math and LDS table reads, the gather replaced
-// by a register value; 2 = the gather with the index math done once per point instead of once per
-// (point, translation); 3 = index math only (no LDS table reads, no gather).
-template <int P, bool CLAMP, int DEBUG = 0>
+template <bool CLAMP>
 __global__ __launch_bounds__(kDenseMaxBlock) void rtcsm_score_dense_kernel(
     GridView g, DenseDomain dom, const float* __restrict__ px, const float* __restrict__ py,
     const float* __restrict__ pz, int points_per_chunk, int point_chunks,
     int rot_groups, const float4* __restrict__ rot, int R, int r_first, int r_last,
     const float4* __restrict__ trans4, int T, int t_chunk, unsigned long long* __restrict__ sums) {
+  constexpr int P = 8;  // points per iteration (wave-uniform, scalar loads); the host's point chunks are multiples of 8
   // XCD-aware block -> (point chunk, rotation group) map.  Workgroup b lands on XCD b % 8 (observed,
   // used for speed only): the rotation groups of one point chunk run back to back on ONE XCD and
   // share its L2 lines; chunks are dealt to the XCDs round-robin -- giving every XCD one contiguous
@@ -309,26 +311,6 @@ __global__ __launch_bounds__(kDenseMaxBlock) void rtcsm_score_dense_kernel(
         rotate_point(q, real ? px[i + k] : dom.pad[0], real ? py[i + k] : dom.pad[1], real ? pz[i + k] : dom.pad[2],
                      rx[k], ry[k], rz[k]);
       }
-      if (DEBUG == 2) {
-        unsigned o[P];
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-          const float4 t = lds_trans[jc];
-          o[k] = lds_off[cvt_flr(__builtin_fmaf(rx[k] + t.x, inv, K))] +
-                 lds_off[TS + cvt_flr(__builtin_fmaf(ry[k] + t.y, inv, K))] +
-                 lds_off[2 * TS + cvt_flr(__builtin_fmaf(rz[k] + t.z, inv, K))];
-        }
-#pragma unroll 1
-        for (int jj = 0; jj < tc; ++jj) {
-          const unsigned d = (jj % 3) * 2u + ((jj / 3) % 3) * 8u + ((jj / 9) % 3) * 32u;  // uniform, stays inside a brick or the next
-          unsigned a = 0;
-#pragma unroll
-          for (int k = 0; k < P; ++k)
-            a += *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(g.dense) + (o[k] + d));
-          atomicAdd(&lds_acc[jj * bs + threadIdx.x], a);
-        }
-        continue;
-      }
 #pragma unroll 1
       for (int jj = 0; jj < tc; ++jj) {
         const float4 t = lds_trans[jc + jj];  // same address in every lane: LDS broadcast
@@ -348,10 +330,6 @@ __global__ __launch_bounds__(kDenseMaxBlock) void rtcsm_score_dense_kernel(
             ox[k] = lds_off[cvt_flr(__builtin_amdgcn_fmed3f(zx, 0.f, lim))];
             oy[k] = lds_off[TS + cvt_flr(__builtin_amdgcn_fmed3f(zy, 0.f, lim))];
             oz[k] = lds_off[2 * TS + cvt_flr(__builtin_amdgcn_fmed3f(zz, 0.f, lim))];
-          } else if (DEBUG == 3) {
-            ox[k] = cvt_flr(zx);
-            oy[k] = cvt_flr(zy) << 3;
-            oz[k] = cvt_flr(zz) << 6;
           } else {
             ox[k] = lds_off[cvt_flr(zx)];
             oy[k] = lds_off[TS + cvt_flr(zy)];
@@ -379,10 +357,7 @@ __global__ __launch_bounds__(kDenseMaxBlock) void rtcsm_score_dense_kernel(
         unsigned v[P];
 #pragma unroll
         for (int k = 0; k < P; ++k)
-          v[k] = DEBUG == 1 || DEBUG == 3
-                     ? ((ox[k] + oy[k] + oz[k]) & 0x7fffu)
-                     : *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(g.dense) +
-                                                                (ox[k] + oy[k] + oz[k]));
+          v[k] = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(g.dense) + (ox[k] + oy[k] + oz[k]));
         unsigned a = 0;
 #pragma unroll
         for (int k = 0; k < P; ++k) a += v[k];  // the mirror stores max(value, 1) already
@@ -1318,7 +1293,6 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   // at 54); on config 2's narrow kernel they cost 1-3 % (0.70-0.72 against 0.69 ms)
   static const int forced_chunk = env_int("DLIOM_BOX_CHUNK", 0);
   const int chunk_pts = forced_chunk > 0 ? forced_chunk : (variant == 0 ? kCostChunk : kCostChunkBig);
-  static const int target_waves = env_int("DLIOM_BOX_WAVES", 0);
   const double res = static_cast<double>(g.resolution);
   const int passes = (T + TC - 1) / TC;
   // ---- error budget (score_box.h): E / u = 1 + (2 qmax + rmax + taumax) / 256
@@ -1568,7 +1542,7 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   }
   ctx->last_box_variant = variant;
   // workgroups: one round of residents (every wave walks an equal share of the point chunks, so a second,
-  // partly filled round would only idle); `target_waves` overrides
+  // partly filled round would only idle)
   static thread_local size_t resident_lds = 0;
   static thread_local int resident = 0, resident_nw = 0, resident_variant = -1;
   if (resident_lds != lds || resident_nw != nw || resident_variant != variant) {
@@ -1577,8 +1551,7 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
     DLIOM_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, reinterpret_cast<const void*>(kernel), 64 * nw, lds));
     resident_lds = lds;
   }
-  const int num_cus = ctx->num_cus;
-  const int want_blocks = target_waves > 0 ? target_waves / nw : std::max(1, resident) * num_cus;
+  const int want_blocks = std::max(1, resident) * ctx->num_cus;
   int slot_quads = std::max(1, want_blocks / std::max(1, rot_blocks * passes));
   slot_quads = std::min(slot_quads, p.point_chunks);
   // (32-bit register accumulators: the kernel adds them to the 64-bit volume every box::kFlushPoints points)
@@ -1615,8 +1588,145 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   return DLIOM_OK;
 }
 
-// Launches the score-volume kernel; *pad_processed = padding points visited (each adds 1 to
-// every sum).
+// The fallback score kernels below: point chunks are halved until a launch has at least this many workgroups.
+constexpr int kScoreTargetBlocks = 8192;
+
+// Mapping 2: rotation per lane over the dense mirror (rtcsm_score_dense_kernel).  *processed = points visited, padding
+// included.
+static int launch_score_dense(dliom_ctx* ctx, const dliom_cloud& cloud, const GridView& g, const Candidates& c,
+                              const DeviceCandidates& d, int r_first, int r_last, unsigned long long* d_sums,
+                              int64_t* processed) {
+  const int R = static_cast<int>(c.w.num_rotations), T = static_cast<int>(c.w.num_translations);
+  const int n = static_cast<int>(cloud.n);
+  const int Rs = r_last - r_first;  // rotations of this shard
+  const size_t trans_lds = static_cast<size_t>(T) * 16;
+  if (trans_lds > 100 * 1024) return DLIOM_ERR_INVALID_ARGUMENT;
+  // block size: whole wavefronts, the fewest idle lanes in the last rotation group
+  int bs = kDenseMaxBlock;
+  for (int cand = kDenseMaxBlock; cand >= 64; cand -= 64)
+    if ((Rs + cand - 1) / cand * cand < (Rs + bs - 1) / bs * bs) bs = cand;
+  // small searches (a few hundred points after the adaptive voxel filter) would fill a handful
+  // of workgroups: go down to one wavefront per group and 8-point chunks to spread them
+  if (static_cast<int64_t>((Rs + bs - 1) / bs) * ((n + 63) / 64) < 256) bs = 64;
+  const int rot_groups = (Rs + bs - 1) / bs;
+  int chunk = 4096;
+  while (chunk > 8 && static_cast<int64_t>(rot_groups) * ((n + chunk - 1) / chunk) < kScoreTargetBlocks) chunk >>= 1;
+  const int point_chunks = (n + chunk - 1) / chunk;
+  *processed = static_cast<int64_t>(point_chunks) * chunk;
+  // Table domain: all real lookups lie within max ||p|| + max |translation component| of the origin.
+  DenseDomain dom;
+  dom.lo = 0;
+  dom.size = g.dense_stride;
+  dom.n_real = n;
+  dom.pad[0] = dom.pad[1] = dom.pad[2] = kPadCoordinate;
+  bool clamp = true;
+  {
+    float tmax = 0.f, t_init = norm3(c.init.t);
+    for (const F3& t : c.trans) tmax = std::max(tmax, std::max(std::fabs(t.x), std::max(std::fabs(t.y), std::fabs(t.z))));
+    const float res = g.resolution;
+    const double reach = (static_cast<double>(cloud.max_norm) + tmax) / res + 3.0;  // cells from the origin
+    // padding point: W = ((half + m) res, 0, 0) in the grid frame, mapped back through the initial
+    // pose; under a candidate it moves by at most theta_max |W - t_init| + (L + 1) res sqrt(3)
+    const double theta_max = 1.7321 * (c.w.angular_window_size + 1) * c.w.angular_step_size * 1.01 + 1e-4;
+    const double rho = (g.half + 64) * static_cast<double>(res) + t_init;
+    const double m_cells = 8.0 + std::ceil((theta_max * rho + (c.w.linear_window_size + 1) * res * 1.7321) / res);
+    // the padding point itself may be carried up to (m - 8) cells outward as well
+    const double hi_cell = std::max(reach, g.half + 2.0 * m_cells);
+    const int lo_i = std::min(0, g.half + 1 - static_cast<int>(std::ceil(hi_cell)));
+    const int hi_i = std::max(g.dense_stride, g.half + 1 + static_cast<int>(std::ceil(hi_cell)) + 1);
+    if (m_cells <= 64.0 && hi_i - lo_i <= 1024 && std::isfinite(reach)) {
+      clamp = false;
+      dom.lo = lo_i;
+      dom.size = hi_i - lo_i;
+      const F3 w{static_cast<float>((g.half + m_cells) * res) - c.init.t.x, -c.init.t.y, -c.init.t.z};
+      const QF qi{c.init.q.w, -c.init.q.x, -c.init.q.y, -c.init.q.z};
+      const F3 p = qrot(qi, w);
+      dom.pad[0] = p.x;
+      dom.pad[1] = p.y;
+      dom.pad[2] = p.z;
+    }
+  }
+  // translations per pass over the points: up to 27, as many as keep >= 4 workgroups per CU in LDS (160 KB);
+  // large windows / big grids trade a few extra point rotations for occupancy
+  const size_t fixed_lds = trans_lds + static_cast<size_t>(dom.size) * 12;
+  const size_t acc_budget = fixed_lds < 34 * 1024 ? 36 * 1024 - fixed_lds : 2 * 1024;
+  int t_chunk = std::max(4, std::min(std::min(T, 27), static_cast<int>(acc_budget / (static_cast<size_t>(bs) * 4))));
+  const int chunks_per_xcd = (point_chunks + 7) / 8;
+  // small searches (the reference's ~170 filtered points): translation slices over gridDim.y until ~4 workgroups per CU
+  int t_slices = 1;
+  const int base_blocks = 8 * chunks_per_xcd * rot_groups;
+  if (base_blocks < 512 && T > 1) {
+    const int want = std::min(T, (1024 + base_blocks - 1) / base_blocks);
+    t_chunk = std::min(t_chunk, (T + want - 1) / want);
+    t_slices = (T + t_chunk - 1) / t_chunk;
+  }
+  const size_t lds = fixed_lds + static_cast<size_t>(t_chunk) * bs * 4;
+  const auto kernel = clamp ? &rtcsm_score_dense_kernel<true> : &rtcsm_score_dense_kernel<false>;
+  const int span = ctx->begin_span(DLIOM_KERNEL_RTCSM_SCORE);
+  hipLaunchKernelGGL(kernel, dim3(base_blocks, t_slices), dim3(bs), lds, ctx->stream, g, dom, cloud.d_xs, cloud.d_ys,
+                     cloud.d_zs, chunk, point_chunks, rot_groups, d.rot, R, r_first, r_last, d.trans4, T, t_chunk, d_sums);
+  ctx->end_span(span);
+  return DLIOM_OK;
+}
+
+// Mapping 1: rotation per lane over the leaf table (rtcsm_score_rot_kernel).  *processed as above.
+static int launch_score_rot(dliom_ctx* ctx, const dliom_cloud& cloud, const GridView& g, const Candidates& c,
+                            const DeviceCandidates& d, int r_first, int r_last, unsigned long long* d_sums,
+                            int64_t* processed) {
+  const int R = static_cast<int>(c.w.num_rotations), T = static_cast<int>(c.w.num_translations);
+  const int n = static_cast<int>(cloud.n);
+  const size_t lds = static_cast<size_t>(T) * 16;
+  if (lds > 100 * 1024) return DLIOM_ERR_INVALID_ARGUMENT;
+  const int rot_groups = (r_last - r_first + kBlock - 1) / kBlock;
+  // points per chunk: a power of two dividing the 4096-point padding
+  int chunk = 4096;
+  while (chunk > 64 && static_cast<int64_t>(rot_groups) * ((n + chunk - 1) / chunk) < kScoreTargetBlocks) chunk >>= 1;
+  const int point_chunks = (n + chunk - 1) / chunk;
+  *processed = static_cast<int64_t>(point_chunks) * chunk;
+  const auto kernel = T == 1 ? &rtcsm_score_rot_kernel<1, 4> : &rtcsm_score_rot_kernel<27, 8>;
+  const int span = ctx->begin_span(DLIOM_KERNEL_RTCSM_SCORE);
+  hipLaunchKernelGGL(kernel, dim3(rot_groups, point_chunks), dim3(kBlock), lds, ctx->stream, g, cloud.d_xs, cloud.d_ys,
+                     cloud.d_zs, chunk, d.rot, R, r_first, r_last, d.trans4, T, d_sums);
+  ctx->end_span(span);
+  return DLIOM_OK;
+}
+
+// Mapping 0: point per lane over the leaf table (rtcsm_score_kernel).  *processed as above.
+static int launch_score_point(dliom_ctx* ctx, const dliom_cloud& cloud, const GridView& g, const Candidates& c,
+                              const DeviceCandidates& d, int r_first, int r_last, unsigned long long* d_sums,
+                              int64_t* processed) {
+  const int R = static_cast<int>(c.w.num_rotations), T = static_cast<int>(c.w.num_translations);
+  const int n = static_cast<int>(cloud.n);
+  const int Rs = r_last - r_first;  // rotations of this shard
+  int ppt = n >= 32 * 1024 ? 8 : (n >= 8 * 1024 ? 4 : (n >= 2048 ? 2 : 1));
+  while (ppt > 1 && (cloud.n_padded % (static_cast<int64_t>(kBlock) * ppt)) != 0) ppt >>= 1;
+  const int point_tiles = (n + kBlock * ppt - 1) / (kBlock * ppt);
+  int rot_tiles = std::max(1, std::min(Rs, (kScoreTargetBlocks + point_tiles - 1) / point_tiles));
+  const int rots_per_block = (Rs + rot_tiles - 1) / rot_tiles;
+  rot_tiles = (Rs + rots_per_block - 1) / rots_per_block;
+  const size_t lds = static_cast<size_t>(T) * sizeof(unsigned);
+  if (lds > 150 * 1024) return DLIOM_ERR_INVALID_ARGUMENT;  // (2L+1)^3 translations must fit LDS
+  // bits = 8 (2^33 leaf-table entries): the 64-bit-index kernel is built for 1 and 4 points per lane, on the rotation
+  // tiles sized above
+  const bool wide = g.log2_leaves > 10;
+  const int lane_pts = wide ? (ppt >= 4 ? 4 : 1) : ppt;
+  const int tile = kBlock * lane_pts;
+  const int tiles = (n + tile - 1) / tile;
+  *processed = static_cast<int64_t>(tiles) * tile;
+  auto kernel = &rtcsm_score_kernel<1>;
+  if (wide) kernel = lane_pts == 4 ? &rtcsm_score_kernel<4, true> : &rtcsm_score_kernel<1, true>;
+  else if (lane_pts == 8) kernel = &rtcsm_score_kernel<8>;
+  else if (lane_pts == 4) kernel = &rtcsm_score_kernel<4>;
+  else if (lane_pts == 2) kernel = &rtcsm_score_kernel<2>;
+  const int span = ctx->begin_span(DLIOM_KERNEL_RTCSM_SCORE);
+  hipLaunchKernelGGL(kernel, dim3(tiles, rot_tiles), dim3(kBlock), lds, ctx->stream, g, cloud.d_xs, cloud.d_ys, cloud.d_zs,
+                     d.rot, R, r_first, r_last, d.trans, T, rots_per_block, d_sums);
+  ctx->end_span(span);
+  return DLIOM_OK;
+}
+
+// Chooses the score kernel (mapping) and launches it; *pad_processed = padding points visited (each adds 1 to every
+// sum).  Records the choice in ctx->last_score_mapping / last_box_refusal / last_score_used_box.
 static int run_score_volume(dliom_ctx* ctx, const dliom_cloud& cloud, const dliom_grid* grid,
                             const Candidates& c, int r_first, int r_last, DeviceCandidates* d,
                             unsigned long long** d_sums, int64_t* pad_processed, const FillJob* also_fill = nullptr) {
@@ -1635,7 +1745,7 @@ static int run_score_volume(dliom_ctx* ctx, const dliom_cloud& cloud, const dlio
     for (int k = 0; k < nf; ++k)
       if (!prep_add(&prep, fills[k].p, nullptr, fills[k].bytes, fills[k].value)) DLIOM_TRY(fill_multi(ctx, &fills[k], 1));
   }
-  const int R = static_cast<int>(c.w.num_rotations), T = static_cast<int>(c.w.num_translations);
+  const int T = static_cast<int>(c.w.num_translations);
   const int n = static_cast<int>(cloud.n);
   // 3: LDS-box kernel over the dense mirror (score_box.h; default when the search suits it),
   // 2: rotation per lane over the dense mirror, 1: rotation per lane over the leaf table,
@@ -1671,11 +1781,10 @@ static int run_score_volume(dliom_ctx* ctx, const dliom_cloud& cloud, const dlio
     mapping = 0;
   }
   if (mapping == 3) {
-    static const int box_min_pairs_log2 = env_int("DLIOM_BOX_MIN_LOG2", 24);  // small searches: launch-bound anyway
     const double pairs = static_cast<double>(C) * static_cast<double>(n);
     int s3 = DLIOM_ERR_CAPACITY;
     ctx->last_box_refusal = DLIOM_BOX_REFUSED_SMALL;  // unless the launch below is reached
-    if (T >= 8 && pairs >= std::ldexp(1.0, box_min_pairs_log2)) {
+    if (T >= 8 && pairs >= std::ldexp(1.0, 24)) {  // small searches: launch-bound anyway
       ctx->last_box_refusal = DLIOM_BOX_RAN;
 #ifdef DLIOM_EXPERIMENTS
       constexpr size_t kBoxErrorBytes = 256 + 4096 * 32;  // + per-workgroup time stamps (Params::debug & 256)
@@ -1699,171 +1808,14 @@ static int run_score_volume(dliom_ctx* ctx, const dliom_cloud& cloud, const dlio
     mapping = windowed ? 1 : 2;
   }
   DLIOM_TRY(prep_flush(ctx, &prep));  // the kernels below read the device copies
-  static const int forced_ppt = env_int("DLIOM_SCORE_PPT", 0);   // tuning knobs
-  static const int target_blocks = env_int("DLIOM_SCORE_BLOCKS", 8192);
-  const int Rs = r_last - r_first;  // rotations of this shard
-  int span = -1;
-  int64_t processed = 0;
   ctx->last_score_mapping = mapping;
-  if (mapping >= 1) {
-    static const int forced_chunk = env_int("DLIOM_SCORE_CHUNK", 0);
-    const int rot_groups = (Rs + kBlock - 1) / kBlock;
-    // points per chunk: a multiple of 4 dividing the 4096-point padding; aim at >= target blocks
-    int chunk = 4096;
-    while (chunk > 64 && static_cast<int64_t>(rot_groups) * ((n + chunk - 1) / chunk) < target_blocks) chunk >>= 1;
-    if (forced_chunk > 0) chunk = forced_chunk;
-    const int point_chunks = (n + chunk - 1) / chunk;
-    processed = static_cast<int64_t>(point_chunks) * chunk;
-    const dim3 grid_dim(rot_groups, point_chunks), block(kBlock);
-    span = ctx->begin_span(DLIOM_KERNEL_RTCSM_SCORE);
-    static const int pts_per_iter = env_int("DLIOM_SCORE_P", 8);
-    const size_t lds = static_cast<size_t>(T) * 16;
-    if (lds > 100 * 1024) return DLIOM_ERR_INVALID_ARGUMENT;
-    if (mapping == 2) {
-
-      // block size: whole wavefronts, the fewest idle lanes in the last rotation group
-      static const int forced_bs = env_int("DLIOM_SCORE_BLOCK", 0);
-      static const int max_bs = env_int("DLIOM_SCORE_MAX_BLOCK", kDenseMaxBlock);
-      int bs = max_bs;
-      for (int cand = max_bs; cand >= 64; cand -= 64)
-        if ((Rs + cand - 1) / cand * cand < (Rs + bs - 1) / bs * bs) bs = cand;
-      if (forced_bs >= 64 && forced_bs <= kDenseMaxBlock && forced_bs % 64 == 0) bs = forced_bs;
-      // small searches (a few hundred points after the adaptive voxel filter) would fill a handful
-      // of workgroups: go down to one wavefront per group and 8-point chunks to spread them
-      if (forced_bs == 0 && static_cast<int64_t>((Rs + bs - 1) / bs) * ((n + 63) / 64) < 256) bs = 64;
-      const int rot_groups = (Rs + bs - 1) / bs;
-      int chunk = 4096;
-      while (chunk > 8 && static_cast<int64_t>(rot_groups) * ((n + chunk - 1) / chunk) < target_blocks) chunk >>= 1;
-      if (forced_chunk > 0) chunk = forced_chunk;
-      const int point_chunks = (n + chunk - 1) / chunk;
-      processed = static_cast<int64_t>(point_chunks) * chunk;
-      const dim3 block(bs);
-      // Table domain: all real lookups lie within max ||p|| + max |translation component| of the origin.
-      DenseDomain dom;
-      dom.lo = 0;
-      dom.size = g.dense_stride;
-      dom.n_real = n;
-      dom.pad[0] = dom.pad[1] = dom.pad[2] = kPadCoordinate;
-      bool clamp = true;
-      {
-        float tmax = 0.f, t_init = norm3(c.init.t);
-        for (const F3& t : c.trans) tmax = std::max(tmax, std::max(std::fabs(t.x), std::max(std::fabs(t.y), std::fabs(t.z))));
-        const float res = g.resolution;
-        const double reach = (static_cast<double>(cloud.max_norm) + tmax) / res + 3.0;  // cells from the origin
-        // padding point: W = ((half + m) res, 0, 0) in the grid frame, mapped back through the initial
-        // pose; under a candidate it moves by at most theta_max |W - t_init| + (L + 1) res sqrt(3)
-        const double theta_max = 1.7321 * (c.w.angular_window_size + 1) * c.w.angular_step_size * 1.01 + 1e-4;
-        const double rho = (g.half + 64) * static_cast<double>(res) + t_init;
-        const double m_cells = 8.0 + std::ceil((theta_max * rho + (c.w.linear_window_size + 1) * res * 1.7321) / res);
-        // the padding point itself may be carried up to (m - 8) cells outward as well
-        const double hi_cell = std::max(reach, g.half + 2.0 * m_cells);
-        const int lo_i = std::min(0, g.half + 1 - static_cast<int>(std::ceil(hi_cell)));
-        const int hi_i = std::max(g.dense_stride, g.half + 1 + static_cast<int>(std::ceil(hi_cell)) + 1);
-        static const int no_clamp = env_int("DLIOM_SCORE_NO_CLAMP", 1);
-        if (no_clamp && m_cells <= 64.0 && hi_i - lo_i <= 1024 && std::isfinite(reach)) {
-          clamp = false;
-          dom.lo = lo_i;
-          dom.size = hi_i - lo_i;
-          const F3 w{static_cast<float>((g.half + m_cells) * res) - c.init.t.x, -c.init.t.y, -c.init.t.z};
-          const QF qi{c.init.q.w, -c.init.q.x, -c.init.q.y, -c.init.q.z};
-          const F3 p = qrot(qi, w);
-          dom.pad[0] = p.x;
-          dom.pad[1] = p.y;
-          dom.pad[2] = p.z;
-        }
-      }
-      // translations per pass over the points: as many as keep >= 4 workgroups per CU in LDS (160 KB);
-      // large windows / big grids trade a few extra point rotations for occupancy
-      static const int t_chunk_max = env_int("DLIOM_SCORE_TCHUNK", 27);
-      const size_t fixed_lds = lds + static_cast<size_t>(dom.size) * 12;
-      const size_t acc_budget = fixed_lds < 34 * 1024 ? 36 * 1024 - fixed_lds : 2 * 1024;
-      int t_chunk = std::max(4, std::min(std::min(T, t_chunk_max), static_cast<int>(acc_budget / (static_cast<size_t>(bs) * 4))));
-      const int chunks_per_xcd = (point_chunks + 7) / 8;
-      // small searches (the reference's ~170 filtered points): translation slices over gridDim.y until ~4 workgroups per CU
-      static const int small_slices = env_int("DLIOM_SCORE_SLICES", 1);
-      int t_slices = 1;
-      const int base_blocks = 8 * chunks_per_xcd * rot_groups;
-      if (small_slices != 0 && base_blocks < 512 && T > 1) {
-        const int want = std::min(T, (1024 + base_blocks - 1) / base_blocks);
-        t_chunk = std::min(t_chunk, (T + want - 1) / want);
-        t_slices = (T + t_chunk - 1) / t_chunk;
-      }
-      const size_t lds2 = fixed_lds + static_cast<size_t>(t_chunk) * bs * 4;
-      const dim3 dense_grid(base_blocks, t_slices);
-#define DLIOM_LAUNCH_DENSE(PP, CL)                                                                                    \
-  hipLaunchKernelGGL((rtcsm_score_dense_kernel<PP, CL>), dense_grid, block, lds2, ctx->stream, g, dom, cloud.d_xs,     \
-                     cloud.d_ys, cloud.d_zs, chunk, point_chunks, rot_groups, d->rot, R, r_first, r_last, d->trans4, T, \
-                     t_chunk, *d_sums)
-      static const int score_debug = env_int("DLIOM_SCORE_DEBUG", 0);  // timing-only pipe isolation
-      if (score_debug >= 1 && score_debug <= 3 && !clamp) {
-#define DLIOM_LAUNCH_DEBUG(DBG)                                                                                       \
-  hipLaunchKernelGGL((rtcsm_score_dense_kernel<8, false, DBG>), dense_grid, block, lds2, ctx->stream, g, dom,         \
-                     cloud.d_xs, cloud.d_ys, cloud.d_zs, chunk, point_chunks, rot_groups, d->rot, R, r_first, r_last, \
-                     d->trans4, T, t_chunk, *d_sums)
-        if (score_debug == 1) DLIOM_LAUNCH_DEBUG(1);
-        else if (score_debug == 2) DLIOM_LAUNCH_DEBUG(2);
-        else DLIOM_LAUNCH_DEBUG(3);
-#undef DLIOM_LAUNCH_DEBUG
-      } else if (pts_per_iter == 2) {
-        if (clamp) DLIOM_LAUNCH_DENSE(2, true); else DLIOM_LAUNCH_DENSE(2, false);
-      } else if (pts_per_iter == 4) {
-        if (clamp) DLIOM_LAUNCH_DENSE(4, true); else DLIOM_LAUNCH_DENSE(4, false);
-      } else {
-        if (clamp) DLIOM_LAUNCH_DENSE(8, true); else DLIOM_LAUNCH_DENSE(8, false);
-      }
-#undef DLIOM_LAUNCH_DENSE
-    } else if (T == 1) {
-      hipLaunchKernelGGL((rtcsm_score_rot_kernel<1, 4>), grid_dim, block, lds, ctx->stream, g, cloud.d_xs,
-                         cloud.d_ys, cloud.d_zs, chunk, d->rot, R, r_first, r_last, d->trans4, T, *d_sums);
-    } else if (pts_per_iter == 2) {
-      hipLaunchKernelGGL((rtcsm_score_rot_kernel<27, 2>), grid_dim, block, lds, ctx->stream, g, cloud.d_xs,
-                         cloud.d_ys, cloud.d_zs, chunk, d->rot, R, r_first, r_last, d->trans4, T, *d_sums);
-    } else if (pts_per_iter == 8) {
-      hipLaunchKernelGGL((rtcsm_score_rot_kernel<27, 8>), grid_dim, block, lds, ctx->stream, g, cloud.d_xs,
-                         cloud.d_ys, cloud.d_zs, chunk, d->rot, R, r_first, r_last, d->trans4, T, *d_sums);
-    } else {
-      hipLaunchKernelGGL((rtcsm_score_rot_kernel<27, 4>), grid_dim, block, lds, ctx->stream, g, cloud.d_xs,
-                         cloud.d_ys, cloud.d_zs, chunk, d->rot, R, r_first, r_last, d->trans4, T, *d_sums);
-    }
-  } else {
-    static const int debug_no_atomic = env_int("DLIOM_DEBUG_NO_ATOMIC", 0);
-    int ppt = forced_ppt > 0 ? forced_ppt : (n >= 32 * 1024 ? 8 : (n >= 8 * 1024 ? 4 : (n >= 2048 ? 2 : 1)));
-    while (ppt > 1 && (cloud.n_padded % (static_cast<int64_t>(kBlock) * ppt)) != 0) ppt >>= 1;
-    const int tile = kBlock * ppt;
-    const int point_tiles = (n + tile - 1) / tile;
-    processed = static_cast<int64_t>(point_tiles) * tile;
-    int rot_tiles = std::max(1, std::min(Rs, (target_blocks + point_tiles - 1) / point_tiles));
-    const int rots_per_block = (Rs + rot_tiles - 1) / rot_tiles;
-    rot_tiles = (Rs + rots_per_block - 1) / rots_per_block;
-    const dim3 grid_dim(point_tiles, rot_tiles), block(kBlock);
-    const size_t lds = static_cast<size_t>(T) * sizeof(unsigned);
-    if (lds > 150 * 1024) return DLIOM_ERR_INVALID_ARGUMENT;  // (2L+1)^3 translations must fit LDS
-    span = ctx->begin_span(DLIOM_KERNEL_RTCSM_SCORE);
-#define DLIOM_LAUNCH_SCORE(PP)                                                                    \
-  hipLaunchKernelGGL((rtcsm_score_kernel<PP>), grid_dim, block, lds, ctx->stream, g, cloud.d_xs,  \
-                     cloud.d_ys, cloud.d_zs, d->rot, R, r_first, r_last, d->trans, T,             \
-                     rots_per_block, *d_sums, debug_no_atomic)
-    if (g.log2_leaves > 10) {  // bits = 8: the leaf table has 2^33 entries
-      if (ppt >= 4)
-        hipLaunchKernelGGL((rtcsm_score_kernel<4, true>), dim3((n + 4 * kBlock - 1) / (4 * kBlock), rot_tiles), block, lds, ctx->stream,
-                           g, cloud.d_xs, cloud.d_ys, cloud.d_zs, d->rot, R, r_first, r_last, d->trans, T, rots_per_block, *d_sums,
-                           debug_no_atomic);
-      else
-        hipLaunchKernelGGL((rtcsm_score_kernel<1, true>), dim3((n + kBlock - 1) / kBlock, rot_tiles), block, lds, ctx->stream, g,
-                           cloud.d_xs, cloud.d_ys, cloud.d_zs, d->rot, R, r_first, r_last, d->trans, T, rots_per_block, *d_sums,
-                           debug_no_atomic);
-      processed = static_cast<int64_t>((n + (ppt >= 4 ? 4 : 1) * kBlock - 1) / ((ppt >= 4 ? 4 : 1) * kBlock)) * (ppt >= 4 ? 4 : 1) * kBlock;
-    } else
-    switch (ppt) {
-      case 16: DLIOM_LAUNCH_SCORE(16); break;
-      case 8: DLIOM_LAUNCH_SCORE(8); break;
-      case 4: DLIOM_LAUNCH_SCORE(4); break;
-      case 2: DLIOM_LAUNCH_SCORE(2); break;
-      default: DLIOM_LAUNCH_SCORE(1); break;
-    }
-#undef DLIOM_LAUNCH_SCORE
-  }
-  ctx->end_span(span);
+  int64_t processed = 0;
+  if (mapping == 2)
+    DLIOM_TRY(launch_score_dense(ctx, cloud, g, c, *d, r_first, r_last, *d_sums, &processed));
+  else if (mapping == 1)
+    DLIOM_TRY(launch_score_rot(ctx, cloud, g, c, *d, r_first, r_last, *d_sums, &processed));
+  else
+    DLIOM_TRY(launch_score_point(ctx, cloud, g, c, *d, r_first, r_last, *d_sums, &processed));
   DLIOM_HIP_TRY(hipGetLastError());
   *pad_processed = processed - n;
   return DLIOM_OK;
@@ -1894,22 +1846,17 @@ static const LutModel& lut_model() {
   return m;
 }
 
-// State of a (possibly sharded) match between its phases; lives in dliom_ctx::rtcsm_state.
+// The library's rescoring method (the chunk scan), and the cloud size up to which a match replays the sum serially
+// instead: for small clouds (the reference's ~170 filtered points) the serial replay is one launch of ~5 us, the chunk
+// scan three.  All methods return identical bits (test_sequential_sum_kernels_bit_exact).
+constexpr int kRescoreMethod = 2;
+constexpr int64_t kRescoreSerialMaxPoints = 1024;
+
 // Launches the exact sequential-sum kernels for `count` candidates whose indices are in d_list
 // (c -> translation c / R, rotation c % R): method 0 = one lane replays the loop, 1 = element scan,
-// 2 = chunk scan (default).  Methods 1 and 2 need the 15-bit values of a candidate in LDS
+// 2 = chunk scan.  Methods 1 and 2 need the 15-bit values of a candidate in LDS
 // (n <= 65536) and fall back to method 0 beyond.  `scratch` receives values / chunk sums / chunk
 // functions; d_count != nullptr: the kernels read the live candidate count on the device.
-static int rescore_method_default() {
-  static const int m = env_int("DLIOM_RESCORE", 2);
-  return m;
-}
-// Small clouds (the reference's ~170 filtered points): the serial replay is one launch of ~5 us, the chunk scan three;
-// all methods return identical bits (test_sequential_sum_kernels_bit_exact).
-static int rescore_method_for(int64_t n) {
-  static const int small_n = env_int("DLIOM_RESCORE_SERIAL_BELOW", 1024);
-  return n <= small_n ? 0 : rescore_method_default();
-}
 static int launch_sequential_sums(dliom_ctx* ctx, int method, const GridView& gv, const dliom_cloud& cloud,
                                   const float4* d_rot, int R, const float* d_trans, const unsigned* d_list,
                                   const unsigned* d_count, unsigned count, DevBuf* scratch, float* d_ksums) {
@@ -1948,6 +1895,7 @@ static int launch_sequential_sums(dliom_ctx* ctx, int method, const GridView& gv
   return DLIOM_OK;
 }
 
+// State of a (possibly sharded) match between its phases; lives in dliom_ctx::rtcsm_state.
 struct RtcsmState {
   dliom_rtcsm_options o;
   Candidates c;
@@ -2111,7 +2059,7 @@ static int match_finish(dliom_ctx* ctx, const unsigned* global_best_lo_bits, uin
     auto rescore = [&](unsigned count, const unsigned* d_count, size_t list_offset) -> int {
       DLIOM_TRY(ctx->rescore.reserve((static_cast<size_t>(count) * 4 + 255) & ~static_cast<size_t>(255)));
       const int span = ctx->begin_span(DLIOM_KERNEL_RTCSM_RESCORE);
-      const int s = launch_sequential_sums(ctx, rescore_method_for(cloud.n), st->grid->view(), cloud, st->d.rot, R, st->d.trans,
+      const int s = launch_sequential_sums(ctx, cloud.n <= kRescoreSerialMaxPoints ? 0 : kRescoreMethod, st->grid->view(), cloud, st->d.rot, R, st->d.trans,
                                            st->d_list + list_offset, d_count, count, &ctx->misc, ctx->rescore.as<float>());
       ctx->end_span(span);
       return s;
@@ -2219,29 +2167,10 @@ static int match_decode(dliom_ctx* ctx, uint64_t best_packed, double out7[7], fl
 static int match_impl(dliom_ctx* ctx, const dliom_rtcsm_options* o, const double init7[7],
                       const dliom_cloud& cloud, const dliom_grid* grid, double out7[7],
                       float* out_score) {
-#ifdef DLIOM_EXPERIMENTS
-  static const int timing = env_int("DLIOM_TIMING", 0);
-  const auto t0 = std::chrono::steady_clock::now();
-#endif
   DLIOM_TRY(match_begin(ctx, o, init7, cloud, grid, 0, 1, nullptr));
-#ifdef DLIOM_EXPERIMENTS
-  const auto t1 = std::chrono::steady_clock::now();
-#endif
   uint64_t packed = 0;
   DLIOM_TRY(match_finish(ctx, nullptr, &packed));
-#ifdef DLIOM_EXPERIMENTS
-  const auto t2 = std::chrono::steady_clock::now();
-#endif
-  const int s = match_decode(ctx, packed, out7, out_score);
-#ifdef DLIOM_EXPERIMENTS
-  if (timing) {
-    const auto t3 = std::chrono::steady_clock::now();
-    auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    std::fprintf(stderr, "TIMING match: begin (host prep + enqueue) %.1f us, finish (enqueue + wait) %.1f us, decode %.1f us\n", us(t0, t1),
-                 us(t1, t2), us(t2, t3));
-  }
-#endif
-  return s;
+  return match_decode(ctx, packed, out7, out_score);
 }
 
 }  // namespace dliom
@@ -2283,7 +2212,7 @@ int sequential_probability_sums(dliom_ctx* ctx, const dliom_cloud& cloud, const 
   const unsigned* d_list = reinterpret_cast<const unsigned*>(base + rot_bytes + trans_bytes);
   DLIOM_TRY(ctx->rescore.reserve(list_bytes));
   float* d_ksums = ctx->rescore.as<float>();
-  DLIOM_TRY(launch_sequential_sums(ctx, rescore_method_default(), grid->view(), cloud, d_rot, k, d_trans, d_list, nullptr,
+  DLIOM_TRY(launch_sequential_sums(ctx, kRescoreMethod, grid->view(), cloud, d_rot, k, d_trans, d_list, nullptr,
                                    static_cast<unsigned>(k), &ctx->misc, d_ksums));
   if (K <= 1024) {  // a few sums (the loop-closure matcher asks for one at a time): packed by a kernel, polled
     const GatherJob job{d_ksums, static_cast<unsigned>(K)};
