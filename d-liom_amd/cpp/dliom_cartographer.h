@@ -364,6 +364,42 @@ class CeresScanMatcher3D {
           "CeresScanMatcher3D::Match");
     *pose_estimate = transform::Rigid3d::FromArray(out);
   }
+  // Match for a list of problems in one call (dliom_csm3d_match_batch): every pose and summary equals Match's.
+  struct Problem {
+    transform::Vector3d target_translation;
+    transform::Rigid3d initial_pose_estimate;
+    std::vector<PointCloudAndHybridGridPointers> point_clouds_and_hybrid_grids;
+  };
+  void MatchBatch(const std::vector<Problem>& problems, std::vector<transform::Rigid3d>* pose_estimates,
+                  std::vector<Summary>* summaries, dliom_batch_stats* stats = nullptr) const {
+    const int count = static_cast<int>(problems.size());
+    std::vector<dliom_csm_problem> p(count);
+    for (int i = 0; i < count; ++i) {
+      dliom_csm_problem& q = p[i];
+      q = dliom_csm_problem{};
+      for (int a = 0; a < 3; ++a) q.target_translation[a] = problems[i].target_translation.v[a];
+      const std::array<double, 7> init = problems[i].initial_pose_estimate.ToArray();
+      for (int a = 0; a < 7; ++a) q.initial_pose_estimate[a] = init[a];
+      const auto& pairs = problems[i].point_clouds_and_hybrid_grids;
+      q.num_clouds = static_cast<int>(pairs.size());
+      for (size_t j = 0; j < pairs.size() && j < DLIOM_MAX_CLOUDS; ++j) {
+        const sensor::PointCloud& c = *pairs[j].first;
+        q.points_xyz[j] = c.empty() ? nullptr : &c[0].x;
+        q.n[j] = static_cast<int64_t>(c.size());
+        q.grids[j] = pairs[j].second->get();
+      }
+    }
+    std::vector<double> out(7 * static_cast<size_t>(count));
+    std::vector<int> statuses(count);
+    summaries->resize(count);
+    Check(dliom_csm3d_match_batch(context_->get(), &options_, count, p.data(), out.data(), summaries->data(), statuses.data(), stats),
+          "CeresScanMatcher3D::MatchBatch");
+    pose_estimates->resize(count);
+    for (int i = 0; i < count; ++i) {
+      Check(statuses[i], "CeresScanMatcher3D::MatchBatch");
+      (*pose_estimates)[i] = transform::Rigid3d::FromArray(&out[7 * static_cast<size_t>(i)]);
+    }
+  }
 
  private:
   Context* context_;
@@ -444,6 +480,55 @@ class FastCorrelativeScanMatcher3D {
     return Store(r, result);
   }
 
+  // One search of a batch: the matcher (submap) it runs on, its kind and that kind's pose arguments.
+  enum class Kind { kMatch = DLIOM_FAST_CSM_MATCH, kMatchFullSubmap = DLIOM_FAST_CSM_MATCH_FULL_SUBMAP,
+                    kMatchWith3DofInitial = DLIOM_FAST_CSM_MATCH_WITH_3DOF_INITIAL };
+  struct Query {
+    const FastCorrelativeScanMatcher3D* matcher;
+    Kind kind;
+    transform::Rigid3d pose;         // Match: global_node_pose; MatchFullSubmap: its rotation; 3-DoF: the guess
+    transform::Rigid3d submap_pose;  // Match: global_submap_pose; MatchFullSubmap: its rotation
+    const TrajectoryNodeData* constant_data;
+    float min_score;
+  };
+  // All queries in one call (dliom_fast_csm_match_batch) on the calling thread's context.  found[i] / results[i] =
+  // what the single call for queries[i] returns.
+  static void MatchBatch(const std::vector<Query>& queries, std::vector<bool>* found, std::vector<Result>* results,
+                         dliom_batch_stats* stats = nullptr) {
+    const int count = static_cast<int>(queries.size());
+    std::vector<dliom_fast_csm_query> q(count);
+    int device = 0;
+    for (int i = 0; i < count; ++i) {
+      const Query& in = queries[i];
+      device = in.matcher->device_;
+      dliom_fast_csm_query& a = q[i];
+      a = dliom_fast_csm_query{};
+      a.kind = static_cast<int>(in.kind);
+      a.matcher = in.matcher->matcher_;
+      const std::array<double, 7> p = in.pose.ToArray(), sp = in.submap_pose.ToArray();
+      if (in.kind == Kind::kMatchFullSubmap) {
+        for (int k = 0; k < 4; ++k) a.pose[k] = p[3 + k];
+        for (int k = 0; k < 4; ++k) a.submap_pose[k] = sp[3 + k];
+      } else {
+        for (int k = 0; k < 7; ++k) a.pose[k] = p[k];
+        for (int k = 0; k < 7; ++k) a.submap_pose[k] = sp[k];
+      }
+      a.node_data = in.matcher->Data(*in.constant_data);
+      a.histogram_size = in.matcher->histogram_size_;
+      a.min_score = in.min_score;
+    }
+    std::vector<dliom_fast_csm_result> r(count);
+    std::vector<int> statuses(count);
+    Check(dliom_fast_csm_match_batch(Context::ForThisThread(device)->get(), q.data(), count, r.data(), statuses.data(), stats),
+          "FastCorrelativeScanMatcher3D::MatchBatch");
+    found->assign(count, false);
+    results->resize(count);
+    for (int i = 0; i < count; ++i) {
+      Check(statuses[i], "FastCorrelativeScanMatcher3D::MatchBatch");
+      (*found)[i] = Store(r[i], &(*results)[i]);
+    }
+  }
+
  private:
   dliom_fast_csm_node_data Data(const TrajectoryNodeData& c) const {
     if (static_cast<int>(c.rotational_scan_matcher_histogram.size()) != histogram_size_)
@@ -469,6 +554,51 @@ class FastCorrelativeScanMatcher3D {
   int histogram_size_ = 0;
   int device_ = 0;
 };
+
+// ConstraintBuilder3D::ComputeConstraint's three stages (mapping/internal/constraints/constraint_builder_3d.cc:202-334)
+// for a whole list of (submap B, node) pairs: 1. the fast estimate, 2. no constraint when it finds nothing ("prune"),
+// 3. CeresScanMatcher3D::Match with target = the match's translation, initial = the match's pose and the clouds
+// {node high resolution, B's high resolution grid}, {node low resolution, B's low resolution grid}.  Two calls into
+// the library for the whole list.  The policy lives here so that callers do not restate it.
+struct ConstraintQuery {
+  FastCorrelativeScanMatcher3D::Query search;  // search.matcher is B's matcher
+  const HybridGrid* high_resolution_grid;      // B's grids
+  const HybridGrid* low_resolution_grid;
+};
+struct ComputedConstraint {
+  bool found = false;                          // false: no constraint (the reference's early return)
+  FastCorrelativeScanMatcher3D::Result match;  // score, rotational and low-resolution score (the metrics at :296-302)
+  transform::Rigid3d pose;                     // the refined constraint transform (submap B <- node)
+};
+inline std::vector<ComputedConstraint> ComputeConstraints(const CeresScanMatcher3D& ceres_scan_matcher,
+                                                          const std::vector<ConstraintQuery>& queries,
+                                                          dliom_batch_stats* fast_stats = nullptr,
+                                                          dliom_batch_stats* ceres_stats = nullptr) {
+  std::vector<FastCorrelativeScanMatcher3D::Query> searches;
+  for (const ConstraintQuery& q : queries) searches.push_back(q.search);
+  std::vector<bool> found;
+  std::vector<FastCorrelativeScanMatcher3D::Result> matches;
+  FastCorrelativeScanMatcher3D::MatchBatch(searches, &found, &matches, fast_stats);
+  std::vector<ComputedConstraint> out(queries.size());
+  std::vector<CeresScanMatcher3D::Problem> problems;
+  std::vector<size_t> index;
+  for (size_t i = 0; i < queries.size(); ++i) {
+    if (!found[i]) continue;
+    out[i].found = true;
+    out[i].match = matches[i];
+    const TrajectoryNodeData& d = *queries[i].search.constant_data;
+    problems.push_back(CeresScanMatcher3D::Problem{
+        matches[i].pose_estimate.translation(), matches[i].pose_estimate,
+        {{&d.high_resolution_point_cloud, queries[i].high_resolution_grid},
+         {&d.low_resolution_point_cloud, queries[i].low_resolution_grid}}});
+    index.push_back(i);
+  }
+  std::vector<transform::Rigid3d> poses;
+  std::vector<Summary> unused_summaries;
+  ceres_scan_matcher.MatchBatch(problems, &poses, &unused_summaries, ceres_stats);
+  for (size_t k = 0; k < index.size(); ++k) out[index[k]].pose = poses[k];
+  return out;
+}
 
 }  // namespace scan_matching
 

@@ -627,6 +627,20 @@ size_t staged_cloud_bytes(int64_t n) { return cloud_bytes(n); }
 
 using namespace dliom;
 
+int dliom_ctx::reserve_batch_pinned(size_t bytes) {
+  if (bytes <= batch_pinned_bytes) return DLIOM_OK;
+  const size_t want = (std::max(bytes, batch_pinned_bytes + batch_pinned_bytes / 2) + 4095) & ~static_cast<size_t>(4095);
+  if (batch_pinned != nullptr) {
+    DLIOM_HIP_TRY(hipStreamSynchronize(stream));  // the device may still read or write the old block
+    (void)hipHostFree(batch_pinned);
+    batch_pinned = nullptr;
+    batch_pinned_bytes = 0;
+  }
+  DLIOM_HIP_TRY(hipHostMalloc(&batch_pinned, want, hipHostMallocCoherent | hipHostMallocMapped));
+  batch_pinned_bytes = want;
+  return DLIOM_OK;
+}
+
 int dliom_ctx::begin_span(int id) {
   if (!profiling || ((profiling_mask >> id) & 1u) == 0u) return -1;
   hipEvent_t ev[2];
@@ -769,6 +783,8 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
   ctx->box_counters.release();
   ctx->box_extents.release();
   ctx->csm_arrivals.release();
+  ctx->batch.release();
+  if (ctx->batch_pinned != nullptr) (void)hipHostFree(ctx->batch_pinned);
   ctx->aux_scratch.release();
   if (ctx->aux_pinned != nullptr) (void)hipHostFree(ctx->aux_pinned);
   if (ctx->aux_fork != nullptr) (void)hipEventDestroy(ctx->aux_fork);
@@ -784,6 +800,12 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
 }
 
 int dliom_ctx_device(const dliom_ctx* ctx) { return ctx == nullptr ? -1 : ctx->device; }
+
+int dliom_ctx_synchronizations(const dliom_ctx* ctx, int64_t* count) {
+  if (ctx == nullptr || count == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *count = ctx->host_syncs;
+  return DLIOM_OK;
+}
 
 int dliom_ctx_synchronize(dliom_ctx* ctx) {
   if (ctx == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
@@ -969,6 +991,7 @@ int dliom_cloud_create(dliom_ctx* ctx, const float* points_xyz, int64_t n, dliom
   c->base_bytes = bytes;
   // the host buffer may be reused by the caller as soon as we return
   if (s == DLIOM_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) s = DLIOM_ERR_HIP;
+  ++ctx->host_syncs;
   if (s != DLIOM_OK) {
     pool_free(ctx->device, base, bytes);
     delete c;

@@ -972,6 +972,20 @@ struct DeviceEval {
   }
 };
 
+// The thread's points of the two-cloud fast path (DeviceEval::pts), loaded once before the first evaluation.
+__device__ __forceinline__ void load_pair_points(const CsmArgs& a, double pts[6]) {
+  const int n0 = a.cloud[0].n, n1 = a.cloud[1].n;
+  const bool pair = a.num_clouds == 2 && n0 > 0 && n1 > 0 && n0 <= kCsmBlock && n1 <= kCsmBlock;
+  const int t = threadIdx.x;
+  const int i0 = pair ? (t < n0 ? t : n0 - 1) : 0, i1 = pair ? (t < n1 ? t : n1 - 1) : 0;
+  pts[0] = pair ? static_cast<double>(a.cloud[0].x[i0]) : 0.0;
+  pts[1] = pair ? static_cast<double>(a.cloud[0].y[i0]) : 0.0;
+  pts[2] = pair ? static_cast<double>(a.cloud[0].z[i0]) : 0.0;
+  pts[3] = pair ? static_cast<double>(a.cloud[1].x[i1]) : 0.0;
+  pts[4] = pair ? static_cast<double>(a.cloud[1].y[i1]) : 0.0;
+  pts[5] = pair ? static_cast<double>(a.cloud[1].z[i1]) : 0.0;
+}
+
 template <int NLOC>
 __global__ __launch_bounds__(kCsmBlock) void csm_lm_kernel(CsmArgs a, LmKernelParams prm, LmKernelOut* out) {
   __shared__ double part[2 * (kCsmBlock / 64) * 32];
@@ -979,18 +993,7 @@ __global__ __launch_bounds__(kCsmBlock) void csm_lm_kernel(CsmArgs a, LmKernelPa
   ev.a = &a;
   ev.prm = &prm;
   ev.part = part;
-  {
-    const int n0 = a.cloud[0].n, n1 = a.cloud[1].n;
-    const bool pair = a.num_clouds == 2 && n0 > 0 && n1 > 0 && n0 <= kCsmBlock && n1 <= kCsmBlock;
-    const int t = threadIdx.x;
-    const int i0 = pair ? (t < n0 ? t : n0 - 1) : 0, i1 = pair ? (t < n1 ? t : n1 - 1) : 0;
-    ev.pts[0] = pair ? static_cast<double>(a.cloud[0].x[i0]) : 0.0;
-    ev.pts[1] = pair ? static_cast<double>(a.cloud[0].y[i0]) : 0.0;
-    ev.pts[2] = pair ? static_cast<double>(a.cloud[0].z[i0]) : 0.0;
-    ev.pts[3] = pair ? static_cast<double>(a.cloud[1].x[i1]) : 0.0;
-    ev.pts[4] = pair ? static_cast<double>(a.cloud[1].y[i1]) : 0.0;
-    ev.pts[5] = pair ? static_cast<double>(a.cloud[1].z[i1]) : 0.0;
-  }
+  load_pair_points(a, ev.pts);
   double x[7];
   for (int i = 0; i < 7; ++i) x[i] = prm.x0[i];
   dliom_csm_summary sum;
@@ -1008,6 +1011,39 @@ __global__ __launch_bounds__(kCsmBlock) void csm_lm_kernel(CsmArgs a, LmKernelPa
     if (prm.done_word != nullptr) {
       __threadfence_system();
       *reinterpret_cast<volatile unsigned*>(prm.done_word) = prm.done_seq;
+    }
+  }
+}
+
+// A batch of problems (dliom_csm3d_match_batch): one workgroup per problem, the same minimize<> over the same
+// DeviceEval as csm_lm_kernel -- only the arguments come from device arrays.  Every workgroup releases its result
+// system-wide and counts itself in `arrivals` (zero before the launch); the last one writes the completion word.
+template <int NLOC>
+__global__ __launch_bounds__(kCsmBlock) void csm_lm_batch_kernel(const CsmArgs* __restrict__ args,
+                                                                 const LmKernelParams* __restrict__ prms,
+                                                                 LmKernelOut* out, unsigned* arrivals, unsigned* done_word,
+                                                                 unsigned done_seq) {
+  __shared__ double part[2 * (kCsmBlock / 64) * 32];
+  const CsmArgs& a = args[blockIdx.x];
+  const LmKernelParams& prm = prms[blockIdx.x];
+  DeviceEval<NLOC> ev;
+  ev.a = &a;
+  ev.prm = &prm;
+  ev.part = part;
+  load_pair_points(a, ev.pts);
+  double x[7];
+  for (int i = 0; i < 7; ++i) x[i] = prm.x0[i];
+  dliom_csm_summary sum;
+  const int status = minimize<NLOC>(ev, prm.cfg, x, &sum);
+  if (threadIdx.x == 0) {
+    LmKernelOut& o = out[blockIdx.x];
+    for (int i = 0; i < 7; ++i) o.x[i] = x[i];
+    o.summary = sum;
+    o.status = status;
+    __threadfence_system();
+    if (atomicAdd(arrivals, 1u) == gridDim.x - 1) {
+      __threadfence_system();
+      *reinterpret_cast<volatile unsigned*>(done_word) = done_seq;
     }
   }
 }
@@ -1186,6 +1222,24 @@ static int setup_problem(dliom_ctx* ctx, const dliom_csm_options* o, const doubl
   return DLIOM_OK;
 }
 
+// The one-launch loop's parameters of a set-up problem started at x0.
+static LmKernelParams lm_params(const dliom_csm_options* o, const CsmProblem& p, const LmConfig& cfg, const double x0[7]) {
+  LmKernelParams prm;
+  prm.cfg = cfg;
+  prm.translation_weight = o->translation_weight;
+  prm.rotation_weight = o->rotation_weight;
+  for (int i = 0; i < 3; ++i) prm.target_t[i] = p.target_t[i];
+  for (int i = 0; i < 4; ++i) prm.init_q[i] = p.init_q[i];
+  for (int i = 0; i < 7; ++i) prm.x0[i] = x0[i];
+  const float kMin = 0.1f, kMax = 1.f - 0.1f;
+  prm.k_scale = (kMax - kMin) / 32766.f;
+  prm.k_offset = kMin - prm.k_scale;
+  prm.k_unknown = kMin;
+  prm.done_word = nullptr;
+  prm.done_seq = 0u;
+  return prm;
+}
+
 static int stage_clouds(dliom_ctx* ctx, int k, const float* const* pts, const int64_t* n,
                         std::vector<dliom_cloud>* staged, std::vector<const dliom_cloud*>* ptrs) {
   size_t total = 0;
@@ -1229,17 +1283,7 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* o, const do
   // total points up to which the one-launch loop is used (0 = never)
   const int persistent_max = ctx->tuning[DLIOM_TUNE_CSM_ONE_LAUNCH_MAX];
   if (p.args.total_points <= persistent_max) {
-    LmKernelParams prm;
-    prm.cfg = cfg;
-    prm.translation_weight = o->translation_weight;
-    prm.rotation_weight = o->rotation_weight;
-    for (int i = 0; i < 3; ++i) prm.target_t[i] = p.target_t[i];
-    for (int i = 0; i < 4; ++i) prm.init_q[i] = p.init_q[i];
-    for (int i = 0; i < 7; ++i) prm.x0[i] = x[i];
-    const float kMin = 0.1f, kMax = 1.f - 0.1f;
-    prm.k_scale = (kMax - kMin) / 32766.f;
-    prm.k_offset = kMin - prm.k_scale;
-    prm.k_unknown = kMin;
+    LmKernelParams prm = lm_params(o, p, cfg, x);
     LmKernelOut* host = reinterpret_cast<LmKernelOut*>(static_cast<char*>(ctx->pinned) + 1024);  // device-visible
     prm.done_word = ctx->done_word;
     prm.done_seq = ctx->done_word != nullptr ? (++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq) : 0u;
@@ -1250,10 +1294,12 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* o, const do
       hipLaunchKernelGGL(csm_lm_kernel<1>, dim3(1), dim3(kCsmBlock), 0, ctx->stream, p.args, prm, host);
     ctx->end_span(span);
     DLIOM_HIP_TRY(hipGetLastError());
-    if (prm.done_word != nullptr)
+    if (prm.done_word != nullptr) {
       DLIOM_TRY(wait_done(ctx, ctx->stream, prm.done_word, prm.done_seq));
-    else
+    } else {
       DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+      ++ctx->host_syncs;
+    }
     std::memcpy(out7, host->x, sizeof(x));
     *sum = host->summary;
     return host->status;
@@ -1309,6 +1355,136 @@ int dliom_csm3d_match(dliom_ctx* ctx, const dliom_csm_options* o, const double t
   std::vector<const dliom_cloud*> ptrs;
   DLIOM_TRY(stage_clouds(ctx, k, pts, n, &staged, &ptrs));
   return dliom_csm3d_match_cloud(ctx, o, target_t, init7, k, ptrs.data(), grids, out7, summary);
+}
+
+int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* o, int count, const dliom_csm_problem* problems,
+                            double* poses, dliom_csm_summary* summaries, int* statuses, dliom_batch_stats* stats) {
+  if (ctx == nullptr || o == nullptr || count < 0 || (count > 0 && (problems == nullptr || poses == nullptr || statuses == nullptr)))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < count; ++i) {
+    const dliom_csm_problem& q = problems[i];
+    for (int j = 0; j < std::min(std::max(q.num_clouds, 0), DLIOM_MAX_CLOUDS); ++j)
+      if (q.grids[j] == nullptr || (q.clouds[j] == nullptr && (q.n[j] < 0 || (q.n[j] > 0 && q.points_xyz[j] == nullptr))))
+        return DLIOM_ERR_INVALID_ARGUMENT;
+  }
+  dliom_batch_stats st;
+  std::memset(&st, 0, sizeof(st));
+  const int64_t read_backs0 = ctx->read_backs, syncs0 = ctx->host_syncs;
+  if (count > 0) DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  const int persistent_max = ctx->tuning[DLIOM_TUNE_CSM_ONE_LAUNCH_MAX];
+  const int nloc = o->only_optimize_yaw ? 1 : 3;
+  const LmConfig cfg{o->max_num_iterations, o->use_nonmonotonic_steps, nloc};
+  constexpr int kChunk = 256;  // problems per launch; bounds the host clouds staged at once
+  for (int at = 0; at < count; at += kChunk) {
+    const int B = std::min(kChunk, count - at);
+    // host clouds: staged for the whole chunk with one reservation (stage_clouds' layout, problem after problem)
+    size_t total = 0;
+    std::vector<size_t> off(static_cast<size_t>(B) * DLIOM_MAX_CLOUDS, 0);
+    for (int b = 0; b < B; ++b) {
+      const dliom_csm_problem& q = problems[at + b];
+      for (int j = 0; j < std::min(std::max(q.num_clouds, 0), DLIOM_MAX_CLOUDS); ++j)
+        if (q.clouds[j] == nullptr && q.n[j] > 0) {
+          off[b * DLIOM_MAX_CLOUDS + j] = total;
+          total += (staged_cloud_bytes(q.n[j]) + 255) & ~static_cast<size_t>(255);
+        }
+    }
+    DLIOM_TRY(ctx->points.reserve(total));
+    std::vector<dliom_cloud> staged(static_cast<size_t>(B) * DLIOM_MAX_CLOUDS);
+    std::vector<CsmProblem> prob(B);
+    std::vector<int> batched, single;
+    for (int b = 0; b < B; ++b) {
+      const int i = at + b;
+      const dliom_csm_problem& q = problems[i];
+      std::memset(&poses[7 * static_cast<size_t>(i)], 0, 7 * sizeof(double));
+      if (summaries != nullptr) std::memset(&summaries[i], 0, sizeof(dliom_csm_summary));
+      // dliom_csm3d_match's refusals, in its order
+      int status = q.num_clouds <= 0 || q.num_clouds > DLIOM_MAX_CLOUDS ? DLIOM_ERR_WEIGHTS : DLIOM_OK;
+      const dliom_cloud* clouds[DLIOM_MAX_CLOUDS] = {};
+      for (int j = 0; status == DLIOM_OK && j < q.num_clouds; ++j) {
+        if (q.clouds[j] != nullptr) {
+          clouds[j] = q.clouds[j];
+        } else if (q.n[j] == 0) {
+          status = DLIOM_ERR_EMPTY_CLOUD;
+        } else {
+          status = stage_cloud(ctx, q.points_xyz[j], q.n[j], &staged[b * DLIOM_MAX_CLOUDS + j], off[b * DLIOM_MAX_CLOUDS + j]);
+          clouds[j] = &staged[b * DLIOM_MAX_CLOUDS + j];
+        }
+      }
+      if (status == DLIOM_OK)
+        status = setup_problem(ctx, o, q.target_translation, q.initial_pose_estimate, q.num_clouds, clouds, q.grids, &prob[b]);
+      if (status == DLIOM_ERR_HIP) return status;
+      statuses[i] = status;
+      if (status != DLIOM_OK) {
+        ++st.without_search;
+      } else if (prob[b].args.total_points <= persistent_max) {
+        batched.push_back(b);
+      } else {
+        single.push_back(b);
+      }
+    }
+    if (!batched.empty()) {
+      const int n = static_cast<int>(batched.size());
+      const size_t args_bytes = (n * sizeof(CsmArgs) + 255) & ~static_cast<size_t>(255);
+      const size_t prm_bytes = (n * sizeof(LmKernelParams) + 255) & ~static_cast<size_t>(255);
+      const size_t upload = args_bytes + prm_bytes + 256;  // + the arrival counter (uploaded as zero)
+      DLIOM_TRY(ctx->batch.reserve(upload));
+      DLIOM_TRY(ctx->reserve_batch_pinned(upload + n * sizeof(LmKernelOut)));
+      char* h = static_cast<char*>(ctx->batch_pinned);
+      char* d = static_cast<char*>(ctx->batch.p);
+      CsmArgs* h_args = reinterpret_cast<CsmArgs*>(h);
+      LmKernelParams* h_prm = reinterpret_cast<LmKernelParams*>(h + args_bytes);
+      std::memset(h + args_bytes + prm_bytes, 0, 256);
+      LmKernelOut* h_out = reinterpret_cast<LmKernelOut*>(h + upload);
+      for (int k = 0; k < n; ++k) {
+        const CsmProblem& p = prob[batched[k]];
+        std::memcpy(&h_args[k], &p.args, sizeof(CsmArgs));
+        h_prm[k] = lm_params(o, p, cfg, problems[at + batched[k]].initial_pose_estimate);
+      }
+      DLIOM_HIP_TRY(hipMemcpyAsync(d, h, upload, hipMemcpyHostToDevice, ctx->stream));
+      unsigned* arrivals = reinterpret_cast<unsigned*>(d + args_bytes + prm_bytes);
+      unsigned* done_word = ctx->done_word != nullptr ? ctx->done_word : reinterpret_cast<unsigned*>(h + args_bytes + prm_bytes);
+      const unsigned seq = ++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq;
+      if (nloc == 3)
+        hipLaunchKernelGGL(csm_lm_batch_kernel<3>, dim3(n), dim3(kCsmBlock), 0, ctx->stream, reinterpret_cast<const CsmArgs*>(d),
+                           reinterpret_cast<const LmKernelParams*>(d + args_bytes), h_out, arrivals, done_word, seq);
+      else
+        hipLaunchKernelGGL(csm_lm_batch_kernel<1>, dim3(n), dim3(kCsmBlock), 0, ctx->stream, reinterpret_cast<const CsmArgs*>(d),
+                           reinterpret_cast<const LmKernelParams*>(d + args_bytes), h_out, arrivals, done_word, seq);
+      DLIOM_HIP_TRY(hipGetLastError());
+      if (ctx->done_word != nullptr) {
+        DLIOM_TRY(wait_done(ctx, ctx->stream, done_word, seq));
+      } else {
+        DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ++ctx->host_syncs;
+      }
+      ++st.lm_launches;
+      ++st.chunks;
+      st.batched += n;
+      for (int k = 0; k < n; ++k) {
+        const int i = at + batched[k];
+        std::memcpy(&poses[7 * static_cast<size_t>(i)], h_out[k].x, 7 * sizeof(double));
+        if (summaries != nullptr) summaries[i] = h_out[k].summary;
+        statuses[i] = h_out[k].status;
+      }
+    }
+    for (int b : single) {  // above the one-launch limit: the single call's own path on the staged clouds
+      const int i = at + b;
+      const dliom_csm_problem& q = problems[i];
+      const dliom_cloud* clouds[DLIOM_MAX_CLOUDS] = {};
+      for (int j = 0; j < q.num_clouds; ++j) clouds[j] = q.clouds[j] != nullptr ? q.clouds[j] : &staged[b * DLIOM_MAX_CLOUDS + j];
+      dliom_csm_summary local;
+      const int status = dliom_csm3d_match_cloud(ctx, o, q.target_translation, q.initial_pose_estimate, q.num_clouds, clouds, q.grids,
+                                                 &poses[7 * static_cast<size_t>(i)], summaries != nullptr ? &summaries[i] : &local);
+      if (status == DLIOM_ERR_HIP) return status;
+      statuses[i] = status;
+      ++st.per_query;
+      ++st.per_query_one_launch;
+    }
+  }
+  st.synchronizations = ctx->host_syncs - syncs0;
+  st.read_backs = ctx->read_backs - read_backs0;
+  if (stats != nullptr) *stats = st;
+  return DLIOM_OK;
 }
 
 int dliom_csm3d_evaluate(dliom_ctx* ctx, const dliom_csm_options* o, const double target_t[3],

@@ -24,6 +24,7 @@
 #include <functional>
 #include <limits>
 #include <memory>
+#include <unordered_map>
 #include <vector>
 
 #include "device_common.h"
@@ -95,20 +96,37 @@ __global__ void precompute_level_kernel(LevelView src, uint8_t* __restrict__ dst
 }
 
 // DiscretizeScan: cell index of pose_s * p for every discrete scan s and point p.
+__device__ __forceinline__ void discretize_point(const float* pose7, float px, float py, float pz, float resolution, int* cx,
+                                                 int* cy, int* cz) {
+  const Quat4 q{pose7[3], pose7[4], pose7[5], pose7[6]};
+  float rx, ry, rz;
+  rotate_point(q, px, py, pz, rx, ry, rz);
+  *cx = cell_of(rx + pose7[0], resolution);
+  *cy = cell_of(ry + pose7[1], resolution);
+  *cz = cell_of(rz + pose7[2], resolution);
+}
 __global__ void discretize_kernel(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz,
                                   int n, const float* __restrict__ poses7, float resolution, int* __restrict__ cx,
                                   int* __restrict__ cy, int* __restrict__ cz) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int s = blockIdx.y;
-  const float* p = poses7 + 7 * s;
-  const Quat4 q{p[3], p[4], p[5], p[6]};
-  float rx, ry, rz;
-  rotate_point(q, px[i], py[i], pz[i], rx, ry, rz);
   const size_t o = static_cast<size_t>(s) * n + i;
-  cx[o] = cell_of(rx + p[0], resolution);
-  cy[o] = cell_of(ry + p[1], resolution);
-  cz[o] = cell_of(rz + p[2], resolution);
+  discretize_point(poses7 + 7 * s, px[i], py[i], pz[i], resolution, &cx[o], &cy[o], &cz[o]);
+}
+// The discrete scans of a whole batch (dliom_fast_csm_match_batch): blockIdx.y = scan across every query of the batch.
+struct DiscreteScanArg {
+  const float* pts;  // the query's high-resolution cloud, packed xyz
+  int *cx, *cy, *cz; // this scan's row of the query's [scan][point] cells
+  int n;
+  float resolution;
+  float pose[7];
+};
+__global__ __launch_bounds__(256) void discretize_batch_kernel(const DiscreteScanArg* __restrict__ scans) {
+  const DiscreteScanArg& a = scans[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  discretize_point(a.pose, a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2], a.resolution, &a.cx[i], &a.cy[i], &a.cz[i]);
 }
 
 struct ScoreArgs {
@@ -164,9 +182,12 @@ __global__ __launch_bounds__(256) void score_candidates_kernel(ScoreArgs a, cons
 // anything missing (a first leaf refused by the low-resolution matcher, a list that hit its capacity) is fetched
 // on demand as before.  Exactness is untouched: scores are functions of exact integer sums.
 constexpr int kMaxLevels = 16;
+constexpr int kCountWords = 64;  // per search: [kMaxLevels] records per list, [kMaxLevels] overflow flag, [kMaxLevels + 1] theta
 struct FrontierRec {
   int scan, ox, oy, oz, sum;
 };
+// One search of a chain.  The chain serves any number of searches (the single calls: one); their arguments live in a
+// device array, each with its own level views, window, depth, record pool, counts and output region.
 struct FrontierArgs {
   LevelView level[kMaxLevels];
   const int *cx, *cy, *cz;  // [scan][point] full-resolution cells
@@ -174,9 +195,12 @@ struct FrontierArgs {
   int max_depth, full_resolution_depth;
   int linear_xy, linear_z;
   FrontierRec* pool;        // (max_depth + 1) lists of `cap` records, list d at pool + d * cap
-  int* counts;              // [kMaxLevels] records per list, [kMaxLevels] overflow flag, [kMaxLevels + 1] theta bits
+  int* counts;              // kCountWords
   int cap;
   float min_score;
+  int top_begin, top_count; // this search's lowest-resolution candidates in the chain's flat list
+  int* out;                 // page-locked: [counts | overflow | theta | records of list max_depth, ..., 0]
+  int out_records;
 };
 
 __device__ __forceinline__ float frontier_probability(int sum, int n) {  // ScoreCandidates' float (:407-411)
@@ -205,20 +229,30 @@ __device__ __forceinline__ int frontier_wave_sum(const FrontierArgs& a, int dept
   return __builtin_amdgcn_readlane(static_cast<int>(wave_sum_lane63(sum)), 63);
 }
 
-// 1. sums of the uploaded lowest-resolution list (list max_depth), one wavefront per candidate
-__global__ __launch_bounds__(256) void frontier_top_kernel(FrontierArgs a, int count) {
-  const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (w >= count) return;
-  FrontierRec* r = a.pool + static_cast<size_t>(a.max_depth) * a.cap + w;
-  const int sum = frontier_wave_sum(a, a.max_depth, r->scan, r->ox, r->oy, r->oz, lane);
-  if (lane == 0) r->sum = sum;
+// 1. sums of the flat list of every search's lowest-resolution candidates, one wavefront per candidate; each record
+//    goes to list max_depth of its search
+__global__ __launch_bounds__(256) void frontier_top_kernel(const FrontierArgs* __restrict__ args, int num_searches,
+                                                           const FrontierRec* __restrict__ flat, int total) {
+  const int w = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (w >= total) return;
+  int lo = 0, hi = num_searches - 1;  // the search whose range holds w
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (args[mid].top_begin <= w) lo = mid; else hi = mid - 1;
+  }
+  const FrontierArgs& a = args[lo];
+  FrontierRec r = flat[w];
+  r.sum = frontier_wave_sum(a, a.max_depth, r.scan, r.ox, r.oy, r.oz, lane);
+  if (lane == 0) a.pool[static_cast<size_t>(a.max_depth) * a.cap + (w - a.top_begin)] = r;
 }
 
-// 2. the branch the recursion walks first; writes theta
-__global__ __launch_bounds__(512) void frontier_greedy_kernel(FrontierArgs a, int top_count) {
+// 2. the branch the recursion walks first; writes theta.  One workgroup per search.
+__global__ __launch_bounds__(512) void frontier_greedy_kernel(const FrontierArgs* __restrict__ args) {
   __shared__ unsigned long long best_key[8];
   __shared__ int child_sum[8];
   __shared__ int cur[4];
+  const FrontierArgs& a = args[blockIdx.x];
+  const int top_count = a.top_count;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const FrontierRec* top = a.pool + static_cast<size_t>(a.max_depth) * a.cap;
   unsigned long long key = 0ull;
@@ -265,8 +299,11 @@ __global__ __launch_bounds__(512) void frontier_greedy_kernel(FrontierArgs a, in
   }
 }
 
-// 3. list `depth` -> list depth - 1: the children of every node with score >= theta, one wavefront per child
-__global__ __launch_bounds__(256) void frontier_level_kernel(FrontierArgs a, int depth) {
+// 3. list `depth` -> list depth - 1: the children of every node with score >= theta, one wavefront per child.
+//    blockIdx.y = search; a search whose pyramid is shallower than `depth` has nothing to do in this launch.
+__global__ __launch_bounds__(256) void frontier_level_kernel(const FrontierArgs* __restrict__ args, int depth) {
+  const FrontierArgs& a = args[blockIdx.y];
+  if (depth > a.max_depth) return;
   const int lane = threadIdx.x & 63;
   const int waves = (gridDim.x * blockDim.x) >> 6;
   const int parents = min(a.counts[depth], a.cap);
@@ -291,8 +328,11 @@ __global__ __launch_bounds__(256) void frontier_level_kernel(FrontierArgs a, int
   }
 }
 
-// 4. [counts | overflow | theta | records of list max_depth, ..., 0] -> pinned host memory
-__global__ __launch_bounds__(256) void frontier_pack_kernel(FrontierArgs a, int* __restrict__ out, int out_records) {
+// 4. [counts | overflow | theta | records of list max_depth, ..., 0] -> the search's page-locked region (blockIdx.y)
+__global__ __launch_bounds__(256) void frontier_pack_kernel(const FrontierArgs* __restrict__ args) {
+  const FrontierArgs& a = args[blockIdx.y];
+  int* out = a.out;
+  const int out_records = a.out_records;
   const int tid = blockIdx.x * blockDim.x + threadIdx.x, nthreads = gridDim.x * blockDim.x;
   if (tid < kMaxLevels + 2) out[tid] = a.counts[tid];
   int first = 0;
@@ -381,6 +421,10 @@ struct Search {
   const std::vector<Candidate>* top = nullptr;  // the sorted lowest-resolution candidates
   float initial_min_score = 0.f;
   float frontier_threshold = std::numeric_limits<float>::infinity();  // last wavefront prefetch ran with this
+  long long syncs = 0;         // stream synchronisations of this search's on-demand fetches
+  long long cache_misses = 0;  // scores fetched on demand
+  // low-resolution sums of leaves a batch scored ahead (key(0, scan, offset) -> sequential float sum); empty otherwise
+  std::unordered_map<uint64_t, float> low_sums;
   // score cache: (depth, scan, offset) -> integer sum.  Open addressing, linear probing (a match looks up and inserts
   // ~1e4 keys: std::unordered_map's node allocations were a third of the host time of a whole-submap match)
   struct ScoreCache {
@@ -483,6 +527,9 @@ int device_sums(Search& s, int depth, const std::vector<Candidate>& list, std::v
   int* host_sums = host + 4 * k;
   DLIOM_HIP_TRY(hipMemcpyAsync(host_sums, d_sums, k * 4, hipMemcpyDeviceToHost, ctx->stream));
   DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ++ctx->host_syncs;
+  ++s.syncs;
+  s.cache_misses += static_cast<long long>(k);
   std::memcpy(sums->data(), host_sums, k * 4);
   s.scored += static_cast<long long>(k);
   ++s.launches;
@@ -581,36 +628,39 @@ int prefetch_frontier(Search& s, float threshold) {
   return DLIOM_OK;
 }
 
-// The device frontier (kernels above): one chain of launches and one synchronisation that puts the lowest-resolution
-// candidates and everything the recursion can reach below them into the cache.  Does nothing (DLIOM_OK) for searches
-// it is not made for; the recursion then fetches scores on demand.
-int device_frontier(Search& s, const std::vector<Candidate>& lowest, float min_score) {
+// The device frontier (kernels above): one chain of launches that puts the lowest-resolution candidates and
+// everything the recursion can reach below them into a page-locked region per search.  `h` (page-locked) and `d`
+// (device) hold the same upload: the array of num_searches FrontierArgs, at frontier_counts_at() num_searches x
+// kCountWords counts, then the flat list of `total` lowest-resolution records.  Enqueued only: the caller synchronises.
+size_t frontier_counts_at(int num_searches) {
+  return (num_searches * sizeof(FrontierArgs) + 255) & ~static_cast<size_t>(255);
+}
+size_t frontier_flat_at(int num_searches) { return frontier_counts_at(num_searches) + num_searches * kCountWords * 4; }
+size_t frontier_upload_bytes(int num_searches, size_t total) {
+  return frontier_flat_at(num_searches) + total * sizeof(FrontierRec);
+}
+int enqueue_frontier_chain(dliom_ctx* ctx, int num_searches, int total, int deepest, const char* d) {
+  const FrontierArgs* args = reinterpret_cast<const FrontierArgs*>(d);
+  const FrontierRec* flat = reinterpret_cast<const FrontierRec*>(d + frontier_flat_at(num_searches));
+  hipLaunchKernelGGL(frontier_top_kernel, dim3(static_cast<unsigned>((total + 3) / 4)), dim3(256), 0, ctx->stream, args,
+                     num_searches, flat, total);
+  hipLaunchKernelGGL(frontier_greedy_kernel, dim3(static_cast<unsigned>(num_searches)), dim3(512), 0, ctx->stream, args);
+  // 256 workgroups over the whole chain (the single search's grid), at least two per search
+  const unsigned per_search = static_cast<unsigned>(std::max(2, 256 / num_searches));
+  for (int depth = deepest; depth >= 1; --depth)
+    hipLaunchKernelGGL(frontier_level_kernel, dim3(per_search, static_cast<unsigned>(num_searches)), dim3(256), 0, ctx->stream,
+                       args, depth);
+  hipLaunchKernelGGL(frontier_pack_kernel, dim3(static_cast<unsigned>(std::max(1, 64 / num_searches)), static_cast<unsigned>(num_searches)),
+                     dim3(256), 0, ctx->stream, args);
+  DLIOM_HIP_TRY(hipGetLastError());
+  return DLIOM_OK;
+}
+
+// The search's FrontierArgs, except where its pool, counts, upload range and output live.
+FrontierArgs frontier_args(const Search& s, float min_score) {
   const dliom_fast_csm* m = s.m;
-  dliom_ctx* ctx = s.ctx;
-  const int max_depth = m->max_depth();
-  constexpr int kCap = 8192;
-  constexpr size_t kHead = 256, kUpload = 256 * 1024;
-  const size_t k = lowest.size();
-  // one wavefront per candidate: made for the clouds the reference matches (adaptive voxel filter, ~150-200 points);
-  // with every return of a scan (65 536 points) the single workgroup of step 2 alone takes 7 ms -- those searches keep
-  // the on-demand batches, whose block-per-chunk scoring kernel fills the chip
-  constexpr int kMaxPoints = 8192;
-  if (k == 0 || k > static_cast<size_t>(kCap) || max_depth + 1 > kMaxLevels || max_depth < 1 || ctx->pinned_bytes < (1u << 20) ||
-      s.n_hi > kMaxPoints)
-    return DLIOM_OK;
-  const size_t pool_bytes = static_cast<size_t>(max_depth + 1) * kCap * sizeof(FrontierRec);
-  DLIOM_TRY(ctx->cand.reserve(kHead + pool_bytes));
-  int* d_counts = ctx->cand.as<int>();
-  FrontierRec* d_pool = reinterpret_cast<FrontierRec*>(static_cast<char*>(ctx->cand.p) + kHead);
-  int* h = static_cast<int*>(ctx->pinned);
-  std::memset(h, 0, kHead);
-  h[max_depth] = static_cast<int>(k);
-  FrontierRec* h_top = reinterpret_cast<FrontierRec*>(static_cast<char*>(ctx->pinned) + kHead);
-  for (size_t i = 0; i < k; ++i) h_top[i] = FrontierRec{lowest[i].scan_index, lowest[i].offset[0], lowest[i].offset[1], lowest[i].offset[2], 0};
-  DLIOM_HIP_TRY(hipMemcpyAsync(d_counts, h, kHead, hipMemcpyHostToDevice, ctx->stream));
-  DLIOM_HIP_TRY(hipMemcpyAsync(d_pool + static_cast<size_t>(max_depth) * kCap, h_top, k * sizeof(FrontierRec), hipMemcpyHostToDevice,
-                               ctx->stream));
   FrontierArgs a;
+  const int max_depth = m->max_depth();
   for (int d = 0; d < kMaxLevels; ++d) a.level[d] = d <= max_depth ? m->levels[d].view() : LevelView{nullptr, {0, 0, 0}, {0, 0, 0}};
   a.cx = s.d_cx;
   a.cy = s.d_cy;
@@ -620,23 +670,17 @@ int device_frontier(Search& s, const std::vector<Candidate>& lowest, float min_s
   a.full_resolution_depth = m->options.full_resolution_depth;
   a.linear_xy = s.linear_xy;
   a.linear_z = s.linear_z;
-  a.pool = d_pool;
-  a.counts = d_counts;
-  a.cap = kCap;
   a.min_score = min_score;
-  hipLaunchKernelGGL(frontier_top_kernel, dim3(static_cast<unsigned>((k + 3) / 4)), dim3(256), 0, ctx->stream, a, static_cast<int>(k));
-  hipLaunchKernelGGL(frontier_greedy_kernel, dim3(1), dim3(512), 0, ctx->stream, a, static_cast<int>(k));
-  for (int depth = max_depth; depth >= 1; --depth)
-    hipLaunchKernelGGL(frontier_level_kernel, dim3(256), dim3(256), 0, ctx->stream, a, depth);
-  int* out = reinterpret_cast<int*>(static_cast<char*>(ctx->pinned) + kUpload);
-  const int out_records = static_cast<int>((ctx->pinned_bytes - kUpload - 8192 - (kMaxLevels + 2) * 4) / sizeof(FrontierRec));
-  hipLaunchKernelGGL(frontier_pack_kernel, dim3(64), dim3(256), 0, ctx->stream, a, out, out_records);
-  DLIOM_HIP_TRY(hipGetLastError());
-  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return a;
+}
+
+// A search's packed chain output -> its score cache; returns theta.
+float take_frontier(Search& s, const int* out, int out_records, int cap) {
+  const int max_depth = s.m->max_depth();
   const FrontierRec* rec = reinterpret_cast<const FrontierRec*>(out + kMaxLevels + 2);
   int at = 0;
   for (int depth = max_depth; depth >= 0 && at < out_records; --depth) {
-    const int cnt = std::min(std::min(out[depth], kCap), out_records - at);
+    const int cnt = std::min(std::min(out[depth], cap), out_records - at);
     for (int i = 0; i < cnt; ++i) {
       const FrontierRec& r = rec[at + i];
       const int o[3] = {r.ox, r.oy, r.oz};
@@ -649,6 +693,54 @@ int device_frontier(Search& s, const std::vector<Candidate>& lowest, float min_s
   float theta;
   std::memcpy(&theta, &out[kMaxLevels + 1], 4);
   s.frontier_threshold = theta;
+  return theta;
+}
+
+// one wavefront per candidate: made for the clouds the reference matches (adaptive voxel filter, ~150-200 points);
+// with every return of a scan (65 536 points) the single workgroup of step 2 alone takes 7 ms -- those searches keep
+// the on-demand batches, whose block-per-chunk scoring kernel fills the chip
+constexpr int kFrontierMaxPoints = 8192;
+bool frontier_suits(const Search& s, size_t lowest, int cap) {
+  const int max_depth = s.m->max_depth();
+  return lowest > 0 && lowest <= static_cast<size_t>(cap) && max_depth + 1 <= kMaxLevels && max_depth >= 1 &&
+         s.n_hi <= kFrontierMaxPoints;
+}
+
+// The single call's frontier: the chain with one search.  Does nothing (DLIOM_OK) for searches it is not made for;
+// the recursion then fetches scores on demand.
+int device_frontier(Search& s, const std::vector<Candidate>& lowest, float min_score) {
+  dliom_ctx* ctx = s.ctx;
+  const int max_depth = s.m->max_depth();
+  constexpr int kCap = 8192;
+  constexpr size_t kUpload = 256 * 1024;
+  const size_t k = lowest.size();
+  if (!frontier_suits(s, k, kCap) || ctx->pinned_bytes < (1u << 20)) return DLIOM_OK;
+  const size_t up = (frontier_upload_bytes(1, k) + 255) & ~static_cast<size_t>(255);
+  const size_t pool_bytes = static_cast<size_t>(max_depth + 1) * kCap * sizeof(FrontierRec);
+  DLIOM_TRY(ctx->cand.reserve(up + pool_bytes));
+  char* d = static_cast<char*>(ctx->cand.p);
+  char* h = static_cast<char*>(ctx->pinned);
+  int* out = reinterpret_cast<int*>(h + kUpload);
+  const int out_records = static_cast<int>((ctx->pinned_bytes - kUpload - 8192 - (kMaxLevels + 2) * 4) / sizeof(FrontierRec));
+  FrontierArgs a = frontier_args(s, min_score);
+  a.pool = reinterpret_cast<FrontierRec*>(d + up);
+  a.counts = reinterpret_cast<int*>(d + frontier_counts_at(1));
+  a.cap = kCap;
+  a.top_begin = 0;
+  a.top_count = static_cast<int>(k);
+  a.out = out;
+  a.out_records = out_records;
+  std::memcpy(h, &a, sizeof(a));
+  int* counts = reinterpret_cast<int*>(h + frontier_counts_at(1));
+  std::memset(counts, 0, kCountWords * 4);
+  counts[max_depth] = static_cast<int>(k);
+  FrontierRec* flat = reinterpret_cast<FrontierRec*>(h + frontier_flat_at(1));
+  for (size_t i = 0; i < k; ++i) flat[i] = FrontierRec{lowest[i].scan_index, lowest[i].offset[0], lowest[i].offset[1], lowest[i].offset[2], 0};
+  DLIOM_HIP_TRY(hipMemcpyAsync(d, h, frontier_upload_bytes(1, k), hipMemcpyHostToDevice, ctx->stream));
+  DLIOM_TRY(enqueue_frontier_chain(ctx, 1, static_cast<int>(k), max_depth, d));
+  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ++ctx->host_syncs;
+  take_frontier(s, out, out_records, kCap);
   return DLIOM_OK;
 }
 
@@ -659,10 +751,16 @@ PoseF pose_from_candidate(const Search& s, const Candidate& c) {  // :431-437
   return pose_mul_f(t, s.scan_poses[c.scan_index]);
 }
 
-int low_resolution_score(Search& s, const PoseF& pose, float* score) {  // low_resolution_matcher.cc:23-36
-  const float p7[7] = {pose.t.x, pose.t.y, pose.t.z, pose.q.w, pose.q.x, pose.q.y, pose.q.z};
+int low_resolution_score(Search& s, const Candidate& c, float* score) {  // low_resolution_matcher.cc:23-36
   float sum = 0.f;
-  DLIOM_TRY(sequential_probability_sums(s.ctx, *s.lo_cloud, s.m->lo_grid, p7, 1, &sum));
+  const auto ahead = s.low_sums.find(Search::key(0, c.scan_index, c.offset));
+  if (ahead != s.low_sums.end()) {
+    sum = ahead->second;  // scored by the batch's chain: the same kernels on the same pose
+  } else {
+    const PoseF pose = pose_from_candidate(s, c);
+    const float p7[7] = {pose.t.x, pose.t.y, pose.t.z, pose.q.w, pose.q.x, pose.q.y, pose.q.z};
+    DLIOM_TRY(sequential_probability_sums(s.ctx, *s.lo_cloud, s.m->lo_grid, p7, 1, &sum));
+  }
   *score = sum / static_cast<float>(s.lo_cloud->n);
   return DLIOM_OK;
 }
@@ -678,7 +776,7 @@ Candidate branch_and_bound(Search& s, const std::vector<Candidate>& candidates, 
     for (const Candidate& c : candidates) {
       if (c.score <= min_score) return unsuccessful;
       float low = 0.f;
-      *status = low_resolution_score(s, pose_from_candidate(s, c), &low);
+      *status = low_resolution_score(s, c, &low);
       if (*status != DLIOM_OK) return unsuccessful;
       if (low >= s.m->options.min_low_resolution_score) {
         Candidate best = c;
@@ -711,6 +809,55 @@ Candidate branch_and_bound(Search& s, const std::vector<Candidate>& candidates, 
     if (*status != DLIOM_OK) return unsuccessful;
   }
   return best;
+}
+
+// Lowest-resolution candidates (:358-392, 419-429), or DLIOM_ERR_CAPACITY for searches that cannot fit.
+int lowest_candidates(const Search& s, std::vector<Candidate>* lowest) {
+  const int num_scans = static_cast<int>(s.scan_poses.size());
+  const int step = 1 << s.m->max_depth();
+  {
+    // the reference would allocate them all as well; refuse searches that cannot fit instead of
+    // exhausting host memory (a whole-submap window with a shallow pyramid is ~1e8 per scan)
+    const double per_axis_xy = std::floor((2.0 * s.linear_xy + step) / step), per_axis_z = std::floor((2.0 * s.linear_z + step) / step);
+    if (per_axis_xy * per_axis_xy * per_axis_z * num_scans > 3.0e7) return DLIOM_ERR_CAPACITY;
+    // the score cache packs (depth, scan, offsets) into 64 bits: 14-bit offsets, 16-bit scan index (Search::key)
+    if (s.linear_xy > 8191 || s.linear_z > 8191 || num_scans > 65535) return DLIOM_ERR_CAPACITY;
+  }
+  lowest->clear();
+  for (int scan = 0; scan != num_scans; ++scan)
+    for (int z = -s.linear_z; z <= s.linear_z; z += step)
+      for (int y = -s.linear_xy; y <= s.linear_xy; y += step)
+        for (int x = -s.linear_xy; x <= s.linear_xy; x += step) {
+          Candidate c;
+          c.scan_index = scan;
+          c.offset[0] = x;
+          c.offset[1] = y;
+          c.offset[2] = z;
+          lowest->push_back(c);
+        }
+  return DLIOM_OK;
+}
+
+// The recursion over a search whose discrete scans are on the device and whose cache holds what was fetched ahead.
+int finish_search(Search& s, std::vector<Candidate>* lowest, float min_score, dliom_fast_csm_result* r) {
+  DLIOM_TRY(score_candidates(s, s.m->max_depth(), lowest));
+  s.top = lowest;
+  s.initial_min_score = min_score;
+  int status = DLIOM_OK;
+  const Candidate best = branch_and_bound(s, *lowest, s.m->max_depth(), min_score, &status);
+  DLIOM_TRY(status);
+  r->num_scored_candidates = s.scored;
+  r->num_score_launches = s.launches;
+  if (best.score > min_score) {
+    r->found = 1;
+    r->score = best.score;
+    const PoseF p = pose_from_candidate(s, best);
+    const double out[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
+    std::memcpy(r->pose_estimate, out, sizeof(out));
+    r->rotational_score = s.rotational_scores[best.scan_index];
+    r->low_resolution_score = best.low_resolution_score;
+  }
+  return DLIOM_OK;
 }
 
 int run_search(Search& s, const dliom_cloud& hi_cloud, float min_score, dliom_fast_csm_result* r) {
@@ -748,49 +895,14 @@ int run_search(Search& s, const dliom_cloud& hi_cloud, float min_score, dliom_fa
   hipLaunchKernelGGL(discretize_kernel, dim3((s.n_hi + 255) / 256, num_scans), dim3(256), 0, ctx->stream, hi_cloud.d_x,
                      hi_cloud.d_y, hi_cloud.d_z, s.n_hi, d_poses, m->resolution, s.d_cx, s.d_cy, s.d_cz);
   DLIOM_HIP_TRY(hipGetLastError());
-  if (!poses_pinned) DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // pageable source
-
-  // lowest-resolution candidates (:358-392, 419-429)
-  const int step = 1 << m->max_depth();
-  {
-    // the reference would allocate them all as well; refuse searches that cannot fit instead of
-    // exhausting host memory (a whole-submap window with a shallow pyramid is ~1e8 per scan)
-    const double per_axis_xy = std::floor((2.0 * s.linear_xy + step) / step), per_axis_z = std::floor((2.0 * s.linear_z + step) / step);
-    if (per_axis_xy * per_axis_xy * per_axis_z * num_scans > 3.0e7) return DLIOM_ERR_CAPACITY;
-    // the score cache packs (depth, scan, offsets) into 64 bits: 14-bit offsets, 16-bit scan index (Search::key)
-    if (s.linear_xy > 8191 || s.linear_z > 8191 || num_scans > 65535) return DLIOM_ERR_CAPACITY;
+  if (!poses_pinned) {  // pageable source
+    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ++ctx->host_syncs;
   }
   std::vector<Candidate> lowest;
-  for (int scan = 0; scan != num_scans; ++scan)
-    for (int z = -s.linear_z; z <= s.linear_z; z += step)
-      for (int y = -s.linear_xy; y <= s.linear_xy; y += step)
-        for (int x = -s.linear_xy; x <= s.linear_xy; x += step) {
-          Candidate c;
-          c.scan_index = scan;
-          c.offset[0] = x;
-          c.offset[1] = y;
-          c.offset[2] = z;
-          lowest.push_back(c);
-        }
+  DLIOM_TRY(lowest_candidates(s, &lowest));
   DLIOM_TRY(device_frontier(s, lowest, min_score));
-  DLIOM_TRY(score_candidates(s, m->max_depth(), &lowest));
-  s.top = &lowest;
-  s.initial_min_score = min_score;
-  int status = DLIOM_OK;
-  const Candidate best = branch_and_bound(s, lowest, m->max_depth(), min_score, &status);
-  DLIOM_TRY(status);
-  r->num_scored_candidates = s.scored;
-  r->num_score_launches = s.launches;
-  if (best.score > min_score) {
-    r->found = 1;
-    r->score = best.score;
-    const PoseF p = pose_from_candidate(s, best);
-    const double out[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
-    std::memcpy(r->pose_estimate, out, sizeof(out));
-    r->rotational_score = s.rotational_scores[best.scan_index];
-    r->low_resolution_score = best.low_resolution_score;
-  }
-  return DLIOM_OK;
+  return finish_search(s, &lowest, min_score, r);
 }
 
 // GenerateDiscreteScans (:306-356): poses and rotational scores of the scans worth discretising.
@@ -839,14 +951,302 @@ struct StagedClouds {
   }
 };
 
+bool valid_node_data(const dliom_fast_csm_node_data* data) {
+  return !(data == nullptr || data->num_high_resolution_points < 0 || data->num_low_resolution_points <= 0 ||
+           data->rotational_scan_matcher_histogram == nullptr ||
+           (data->num_high_resolution_points > 0 && data->high_resolution_points == nullptr) ||
+           data->low_resolution_points == nullptr);
+}
+
 int stage(dliom_ctx* ctx, const dliom_fast_csm_node_data* data, StagedClouds* c) {
-  if (data == nullptr || data->num_high_resolution_points < 0 || data->num_low_resolution_points <= 0 ||
-      data->rotational_scan_matcher_histogram == nullptr ||
-      (data->num_high_resolution_points > 0 && data->high_resolution_points == nullptr) ||
-      data->low_resolution_points == nullptr)
-    return DLIOM_ERR_INVALID_ARGUMENT;
+  if (!valid_node_data(data)) return DLIOM_ERR_INVALID_ARGUMENT;
   DLIOM_TRY(dliom_cloud_create(ctx, data->high_resolution_points, data->num_high_resolution_points, &c->hi));
   DLIOM_TRY(dliom_cloud_create(ctx, data->low_resolution_points, data->num_low_resolution_points, &c->lo));
+  return DLIOM_OK;
+}
+
+// The search of one call: window, discrete scans and their rotational scores.  Match (:147-165), MatchFullSubmap
+// (:204-232; `pose` / `submap_pose` hold the rotations), MatchWith3DofInitial (:168-201).
+void setup_search(Search* s, dliom_ctx* ctx, const dliom_fast_csm* m, int kind, const double* pose, const double* submap_pose,
+                  const dliom_fast_csm_node_data& data, float max_norm) {
+  s->m = m;
+  s->ctx = ctx;
+  if (kind == DLIOM_FAST_CSM_MATCH_FULL_SUBMAP) {
+    const int w = (m->width_in_voxels + 1) / 2 + static_cast<int>(std::lround(max_norm / m->resolution + 0.5f));  // :209-216
+    s->linear_xy = w;
+    s->linear_z = w;
+    s->angular_window = M_PI;
+    const double node[7] = {0, 0, 0, pose[0], pose[1], pose[2], pose[3]};
+    const double submap[7] = {0, 0, 0, submap_pose[0], submap_pose[1], submap_pose[2], submap_pose[3]};
+    generate_discrete_scans(*s, data, max_norm, to_pose_f(node), to_pose_f(submap));
+    return;
+  }
+  s->linear_xy = static_cast<int>(std::lround(m->options.linear_xy_search_window / m->resolution));  // :154-156
+  s->linear_z = static_cast<int>(std::lround(m->options.linear_z_search_window / m->resolution));
+  s->angular_window = m->options.angular_search_window;
+  if (kind == DLIOM_FAST_CSM_MATCH) {
+    generate_discrete_scans(*s, data, max_norm, to_pose_f(pose), to_pose_f(submap_pose));
+  } else {
+    s->scan_poses.push_back(to_pose_f(pose));  // :181-184
+    s->rotational_scores.push_back(static_cast<float>(m->options.min_rotational_score + 0.01));
+  }
+}
+
+// ---- the batch (dliom_fast_csm_match_batch) -------------------------------------------------------------------
+constexpr int kBatchCap = 4096;          // records per list of a batched search (the single call's: 8 192)
+constexpr int kBatchOutRecords = 4096;   // records a batched search packs into its page-locked region
+constexpr int kBatchLeavesAhead = 256;   // leaves per search whose low-resolution score the chain computes ahead
+constexpr int kChunkSearches = 128;      // searches per chunk, and what bounds one chunk's scratch:
+constexpr size_t kChunkTop = 1u << 18;   //   lowest-resolution candidates
+constexpr size_t kChunkCellBytes = 256u << 20;  // discrete-scan cells
+constexpr int kChunkScans = 65535;       //   discrete scans (discretize_batch_kernel's grid)
+
+inline size_t up256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
+inline size_t pad64(int64_t n) { return (static_cast<size_t>(n) + 63) & ~static_cast<size_t>(63); }
+
+// One chunk: discretisation + frontier chain (one synchronisation), the low-resolution scores of the leaves at or
+// above each search's theta (one more), then each search's recursion in query order.
+int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const int* ids, int S,
+                   std::vector<std::unique_ptr<Search>>& searches, std::vector<std::vector<Candidate>>& lowest,
+                   dliom_fast_csm_result* results, dliom_batch_stats* st) {
+  // ---- layout: upload [frontier args | counts | flat top][scan args][hi clouds xyz][lo clouds SoA], then device-only
+  // pools and cells; page-locked: the upload's mirror, the output regions, the leaves' poses and their sums
+  size_t total_top = 0, total_scans = 0, hi_bytes = 0, lo_bytes = 0, pool_bytes = 0, cell_bytes = 0;
+  int deepest = 0, widest = 0;
+  for (int j = 0; j < S; ++j) {
+    const Search& s = *searches[ids[j]];
+    const dliom_fast_csm_node_data& d = queries[ids[j]].node_data;
+    total_top += lowest[ids[j]].size();
+    total_scans += s.scan_poses.size();
+    hi_bytes += up256(static_cast<size_t>(d.num_high_resolution_points) * 12);
+    lo_bytes += 3 * pad64(d.num_low_resolution_points) * 4;
+    pool_bytes += static_cast<size_t>(s.m->max_depth() + 1) * kBatchCap * sizeof(FrontierRec);
+    cell_bytes += up256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
+    deepest = std::max(deepest, s.m->max_depth());
+    widest = std::max(widest, s.n_hi);
+  }
+  const size_t front_bytes = up256(frontier_upload_bytes(S, total_top));
+  const size_t scan_at = front_bytes, hi_at = scan_at + up256(total_scans * sizeof(DiscreteScanArg)), lo_at = hi_at + hi_bytes;
+  const size_t upload_bytes = lo_at + lo_bytes;
+  const size_t pool_at = up256(upload_bytes), cells_at = pool_at + pool_bytes;
+  const size_t leaves = static_cast<size_t>(S) * kBatchLeavesAhead;
+  const size_t rot_at = cells_at + cell_bytes, trans_at = rot_at + up256(leaves * 16), list_at = trans_at + up256(leaves * 12),
+               lsum_at = list_at + up256(leaves * 4);
+  DLIOM_TRY(ctx->batch.reserve(lsum_at + up256(leaves * 4)));
+  const size_t out_stride = up256((kMaxLevels + 2) * 4 + static_cast<size_t>(kBatchOutRecords) * sizeof(FrontierRec));
+  const size_t h_out_at = up256(upload_bytes), h_leaf_at = h_out_at + S * out_stride;
+  const size_t h_lsum_at = h_leaf_at + (lsum_at - rot_at);
+  DLIOM_TRY(ctx->reserve_batch_pinned(h_lsum_at + up256(leaves * 4)));
+  char* d = static_cast<char*>(ctx->batch.p);
+  char* h = static_cast<char*>(ctx->batch_pinned);
+
+  // ---- fill the upload
+  FrontierArgs* h_args = reinterpret_cast<FrontierArgs*>(h);
+  int* h_counts = reinterpret_cast<int*>(h + frontier_counts_at(S));
+  FrontierRec* h_flat = reinterpret_cast<FrontierRec*>(h + frontier_flat_at(S));
+  DiscreteScanArg* h_scans = reinterpret_cast<DiscreteScanArg*>(h + scan_at);
+  std::memset(h_counts, 0, static_cast<size_t>(S) * kCountWords * 4);
+  std::vector<dliom_cloud> lo(S);
+  size_t top = 0, scan = 0, hi_off = 0, lo_off = 0, pool_off = 0, cell_off = 0;
+  for (int j = 0; j < S; ++j) {
+    Search& s = *searches[ids[j]];
+    const dliom_fast_csm_node_data& nd = queries[ids[j]].node_data;
+    const std::vector<Candidate>& low = lowest[ids[j]];
+    const int num_scans = static_cast<int>(s.scan_poses.size());
+    const size_t cells = static_cast<size_t>(num_scans) * s.n_hi;
+    s.d_cx = reinterpret_cast<int*>(d + cells_at + cell_off);
+    s.d_cy = s.d_cx + cells;
+    s.d_cz = s.d_cy + cells;
+    std::memcpy(h + hi_at + hi_off, nd.high_resolution_points, static_cast<size_t>(s.n_hi) * 12);
+    const float* d_pts = reinterpret_cast<const float*>(d + hi_at + hi_off);
+    for (int k = 0; k < num_scans; ++k, ++scan) {
+      DiscreteScanArg& a = h_scans[scan];
+      const PoseF& p = s.scan_poses[k];
+      a.pts = d_pts;
+      a.cx = s.d_cx + static_cast<size_t>(k) * s.n_hi;
+      a.cy = s.d_cy + static_cast<size_t>(k) * s.n_hi;
+      a.cz = s.d_cz + static_cast<size_t>(k) * s.n_hi;
+      a.n = s.n_hi;
+      a.resolution = s.m->resolution;
+      const float v[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
+      std::memcpy(a.pose, v, sizeof(v));
+    }
+    // the low-resolution cloud, SoA, zero padded (what sequential_probability_sums reads of a dliom_cloud)
+    const int64_t n_lo = nd.num_low_resolution_points;
+    const size_t pl = pad64(n_lo);
+    float* hx = reinterpret_cast<float*>(h + lo_at + lo_off);
+    std::memset(hx, 0, 3 * pl * 4);
+    for (int64_t i = 0; i < n_lo; ++i) {
+      hx[i] = nd.low_resolution_points[3 * i];
+      hx[pl + i] = nd.low_resolution_points[3 * i + 1];
+      hx[2 * pl + i] = nd.low_resolution_points[3 * i + 2];
+    }
+    dliom_cloud& c = lo[j];
+    c.ctx = ctx;
+    c.device = ctx->device;
+    c.n = n_lo;
+    c.n_padded = static_cast<int64_t>(pl);
+    c.d_x = reinterpret_cast<float*>(d + lo_at + lo_off);
+    c.d_y = c.d_x + pl;
+    c.d_z = c.d_y + pl;
+    c.max_norm = cloud_max_norm(nd.low_resolution_points, n_lo);
+    c.owned_by_ctx_scratch = true;
+    s.lo_cloud = &c;
+    // the frontier
+    FrontierArgs a = frontier_args(s, queries[ids[j]].min_score);
+    a.pool = reinterpret_cast<FrontierRec*>(d + pool_at + pool_off);
+    a.counts = reinterpret_cast<int*>(d + frontier_counts_at(S)) + static_cast<size_t>(j) * kCountWords;
+    a.cap = kBatchCap;
+    a.top_begin = static_cast<int>(top);
+    a.top_count = static_cast<int>(low.size());
+    a.out = reinterpret_cast<int*>(h + h_out_at + j * out_stride);
+    a.out_records = kBatchOutRecords;
+    std::memcpy(&h_args[j], &a, sizeof(a));
+    h_counts[static_cast<size_t>(j) * kCountWords + a.max_depth] = a.top_count;
+    for (const Candidate& cd : low) h_flat[top++] = FrontierRec{cd.scan_index, cd.offset[0], cd.offset[1], cd.offset[2], 0};
+    hi_off += up256(static_cast<size_t>(s.n_hi) * 12);
+    lo_off += 3 * pl * 4;
+    pool_off += static_cast<size_t>(s.m->max_depth() + 1) * kBatchCap * sizeof(FrontierRec);
+    cell_off += up256(3 * cells * 4);
+  }
+
+  // ---- one upload, the discrete scans, the chain, one synchronisation
+  DLIOM_HIP_TRY(hipMemcpyAsync(d, h, upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(discretize_batch_kernel, dim3(static_cast<unsigned>((widest + 255) / 256), static_cast<unsigned>(total_scans)),
+                     dim3(256), 0, ctx->stream, reinterpret_cast<const DiscreteScanArg*>(d + scan_at));
+  DLIOM_TRY(enqueue_frontier_chain(ctx, S, static_cast<int>(total_top), deepest, d));
+  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ++ctx->host_syncs;
+  ++st->chunks;
+  ++st->frontier_chains;
+
+  // ---- the leaves at or above theta: their low-resolution sums, ahead of the recursion (one more synchronisation)
+  float4* h_rot = reinterpret_cast<float4*>(h + h_leaf_at);
+  float* h_trans = reinterpret_cast<float*>(h + h_leaf_at + (trans_at - rot_at));
+  unsigned* h_list = reinterpret_cast<unsigned*>(h + h_leaf_at + (list_at - rot_at));
+  std::vector<SequentialSumJob> jobs;
+  std::vector<std::vector<uint64_t>> leaf_keys(S);
+  int first = 0;
+  for (int j = 0; j < S; ++j) {
+    Search& s = *searches[ids[j]];
+    const int* out = reinterpret_cast<const int*>(h + h_out_at + j * out_stride);
+    const float theta = take_frontier(s, out, kBatchOutRecords, kBatchCap);
+    const float min_score = queries[ids[j]].min_score;
+    int at = 0;  // the depth-0 records come last
+    for (int depth = s.m->max_depth(); depth >= 1; --depth) at += std::min(out[depth], kBatchCap);
+    const int end = std::min(at + std::min(out[0], kBatchCap), kBatchOutRecords);
+    const FrontierRec* rec = reinterpret_cast<const FrontierRec*>(out + kMaxLevels + 2);
+    int k = 0;
+    for (int i = at; i < end && k < kBatchLeavesAhead; ++i) {
+      Candidate c;
+      c.scan_index = rec[i].scan;
+      c.offset[0] = rec[i].ox;
+      c.offset[1] = rec[i].oy;
+      c.offset[2] = rec[i].oz;
+      const float score = to_probability(rec[i].sum / static_cast<float>(s.n_hi));
+      if (!(score >= theta && score > min_score)) continue;
+      const PoseF p = pose_from_candidate(s, c);
+      h_rot[first + k] = make_float4(p.q.w, p.q.x, p.q.y, p.q.z);
+      h_trans[3 * (first + k)] = p.t.x;
+      h_trans[3 * (first + k) + 1] = p.t.y;
+      h_trans[3 * (first + k) + 2] = p.t.z;
+      leaf_keys[j].push_back(Search::key(0, c.scan_index, c.offset));
+      ++k;
+    }
+    for (int i = 0; i < k; ++i) h_list[first + i] = static_cast<unsigned>(i * k + i);
+    if (k > 0) jobs.push_back(SequentialSumJob{s.lo_cloud, s.m->lo_grid, first, k});
+    first += k;
+  }
+  if (first > 0) {
+    DLIOM_HIP_TRY(hipMemcpyAsync(d + rot_at, h + h_leaf_at, lsum_at - rot_at, hipMemcpyHostToDevice, ctx->stream));
+    float* d_lsum = reinterpret_cast<float*>(d + lsum_at);
+    DLIOM_TRY(sequential_probability_sums_enqueue(ctx, jobs.data(), static_cast<int>(jobs.size()),
+                                                  reinterpret_cast<const float4*>(d + rot_at),
+                                                  reinterpret_cast<const float*>(d + trans_at),
+                                                  reinterpret_cast<const unsigned*>(d + list_at), d_lsum));
+    float* h_lsum = reinterpret_cast<float*>(h + h_lsum_at);
+    DLIOM_HIP_TRY(hipMemcpyAsync(h_lsum, d_lsum, static_cast<size_t>(first) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ++ctx->host_syncs;
+    int at = 0;
+    for (int j = 0; j < S; ++j)
+      for (uint64_t key : leaf_keys[j]) searches[ids[j]]->low_sums[key] = h_lsum[at++];
+  }
+
+  // ---- the recursions, in query order
+  for (int j = 0; j < S; ++j) {
+    Search& s = *searches[ids[j]];
+    DLIOM_TRY(finish_search(s, &lowest[ids[j]], queries[ids[j]].min_score, &results[ids[j]]));
+    st->cache_misses += s.cache_misses;
+    s.lo_cloud = nullptr;  // lo[] ends with this chunk
+  }
+  st->batched += S;
+  return DLIOM_OK;
+}
+
+int fast_csm_batch(dliom_ctx* ctx, const dliom_fast_csm_query* queries, int count, dliom_fast_csm_result* results,
+                   int* statuses, dliom_batch_stats* st) {
+  std::vector<std::unique_ptr<Search>> searches(count);
+  std::vector<std::vector<Candidate>> lowest(count);
+  std::vector<int> batched;
+  for (int i = 0; i < count; ++i) {  // host preparation; the single calls for what the chain is not made for
+    const dliom_fast_csm_query& q = queries[i];
+    const dliom_fast_csm_node_data& nd = q.node_data;
+    dliom_fast_csm_result* r = &results[i];
+    std::memset(r, 0, sizeof(*r));
+    statuses[i] = DLIOM_OK;
+    std::unique_ptr<Search> s(new Search);
+    setup_search(s.get(), ctx, q.matcher, q.kind, q.pose, q.submap_pose, nd,
+                 cloud_max_norm(nd.high_resolution_points, nd.num_high_resolution_points));
+    r->num_discrete_scans = static_cast<int>(s->scan_poses.size());
+    if (s->scan_poses.empty() || nd.num_high_resolution_points == 0) {  // no candidates: nullptr in the reference
+      ++st->without_search;
+      continue;
+    }
+    s->n_hi = static_cast<int>(nd.num_high_resolution_points);
+    statuses[i] = lowest_candidates(*s, &lowest[i]);
+    if (statuses[i] != DLIOM_OK) {
+      ++st->without_search;
+      continue;
+    }
+    if (!frontier_suits(*s, lowest[i].size(), kBatchCap)) {
+      int status;
+      if (q.kind == DLIOM_FAST_CSM_MATCH)
+        status = dliom_fast_csm_match(ctx, q.matcher, q.pose, q.submap_pose, &nd, q.min_score, r);
+      else if (q.kind == DLIOM_FAST_CSM_MATCH_FULL_SUBMAP)
+        status = dliom_fast_csm_match_full_submap(ctx, q.matcher, q.pose, q.submap_pose, &nd, q.min_score, r);
+      else
+        status = dliom_fast_csm_match_with_3dof_initial(ctx, q.matcher, q.pose, &nd, q.min_score, r);
+      if (status != DLIOM_OK && status != DLIOM_ERR_CAPACITY) return status;
+      statuses[i] = status;
+      lowest[i].clear();
+      ++st->per_query;
+      ++st->per_query_frontier;
+      continue;
+    }
+    searches[i] = std::move(s);
+    batched.push_back(i);
+  }
+  for (size_t at = 0; at < batched.size();) {
+    size_t end = at, top = 0, cells = 0;
+    int scans = 0;
+    while (end < batched.size() && end - at < static_cast<size_t>(kChunkSearches)) {
+      const Search& s = *searches[batched[end]];
+      const size_t k = lowest[batched[end]].size(), c = up256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
+      const int ns = static_cast<int>(s.scan_poses.size());
+      if (end > at && (top + k > kChunkTop || cells + c > kChunkCellBytes || scans + ns > kChunkScans)) break;
+      top += k;
+      cells += c;
+      scans += ns;
+      ++end;
+    }
+    DLIOM_TRY(fast_csm_chunk(ctx, queries, &batched[at], static_cast<int>(end - at), searches, lowest, results, st));
+    for (size_t j = at; j < end; ++j) {  // done: free the host side early
+      searches[batched[j]].reset();
+      std::vector<Candidate>().swap(lowest[batched[j]]);
+    }
+    at = end;
+  }
   return DLIOM_OK;
 }
 
@@ -971,13 +1371,8 @@ int dliom_fast_csm_match(dliom_ctx* ctx, const dliom_fast_csm* m, const double g
   StagedClouds c;
   DLIOM_TRY(stage(ctx, data, &c));
   Search s;
-  s.m = m;
-  s.ctx = ctx;
-  s.linear_xy = static_cast<int>(std::lround(m->options.linear_xy_search_window / m->resolution));  // :154-156
-  s.linear_z = static_cast<int>(std::lround(m->options.linear_z_search_window / m->resolution));
-  s.angular_window = m->options.angular_search_window;
+  setup_search(&s, ctx, m, DLIOM_FAST_CSM_MATCH, global_node_pose, global_submap_pose, *data, c.hi->max_norm);
   s.lo_cloud = c.lo;
-  generate_discrete_scans(s, *data, c.hi->max_norm, to_pose_f(global_node_pose), to_pose_f(global_submap_pose));
   return run_search(s, *c.hi, min_score, result);
 }
 
@@ -991,19 +1386,8 @@ int dliom_fast_csm_match_full_submap(dliom_ctx* ctx, const dliom_fast_csm* m, co
   StagedClouds c;
   DLIOM_TRY(stage(ctx, data, &c));
   Search s;
-  s.m = m;
-  s.ctx = ctx;
-  // :209-216
-  const int w = (m->width_in_voxels + 1) / 2 + static_cast<int>(std::lround(c.hi->max_norm / m->resolution + 0.5f));
-  s.linear_xy = w;
-  s.linear_z = w;
-  s.angular_window = M_PI;
+  setup_search(&s, ctx, m, DLIOM_FAST_CSM_MATCH_FULL_SUBMAP, global_node_rotation, global_submap_rotation, *data, c.hi->max_norm);
   s.lo_cloud = c.lo;
-  const double node[7] = {0, 0, 0, global_node_rotation[0], global_node_rotation[1], global_node_rotation[2],
-                          global_node_rotation[3]};
-  const double submap[7] = {0, 0, 0, global_submap_rotation[0], global_submap_rotation[1], global_submap_rotation[2],
-                            global_submap_rotation[3]};
-  generate_discrete_scans(s, *data, c.hi->max_norm, to_pose_f(node), to_pose_f(submap));
   return run_search(s, *c.hi, min_score, result);
 }
 
@@ -1016,15 +1400,33 @@ int dliom_fast_csm_match_with_3dof_initial(dliom_ctx* ctx, const dliom_fast_csm*
   StagedClouds c;
   DLIOM_TRY(stage(ctx, data, &c));
   Search s;
-  s.m = m;
-  s.ctx = ctx;
-  s.linear_xy = static_cast<int>(std::lround(m->options.linear_xy_search_window / m->resolution));
-  s.linear_z = static_cast<int>(std::lround(m->options.linear_z_search_window / m->resolution));
-  s.angular_window = m->options.angular_search_window;
+  setup_search(&s, ctx, m, DLIOM_FAST_CSM_MATCH_WITH_3DOF_INITIAL, pose_in_submap_guess, nullptr, *data, c.hi->max_norm);
   s.lo_cloud = c.lo;
-  s.scan_poses.push_back(to_pose_f(pose_in_submap_guess));  // :181-184
-  s.rotational_scores.push_back(static_cast<float>(m->options.min_rotational_score + 0.01));
   return run_search(s, *c.hi, min_score, result);
+}
+
+int dliom_fast_csm_match_batch(dliom_ctx* ctx, const dliom_fast_csm_query* queries, int count, dliom_fast_csm_result* results,
+                               int* statuses, dliom_batch_stats* stats) {
+  if (ctx == nullptr || count < 0 || (count > 0 && (queries == nullptr || results == nullptr || statuses == nullptr)))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < count; ++i) {
+    const dliom_fast_csm_query& q = queries[i];
+    if (q.matcher == nullptr || q.kind < DLIOM_FAST_CSM_MATCH || q.kind > DLIOM_FAST_CSM_MATCH_WITH_3DOF_INITIAL ||
+        q.matcher->ctx->device != ctx->device || q.histogram_size != static_cast<int>(q.matcher->submap_histogram.size()) ||
+        !valid_node_data(&q.node_data))
+      return DLIOM_ERR_INVALID_ARGUMENT;
+  }
+  dliom_batch_stats st;
+  std::memset(&st, 0, sizeof(st));
+  const int64_t read_backs0 = ctx->read_backs, syncs0 = ctx->host_syncs;
+  if (count > 0) {
+    DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+    DLIOM_TRY(fast_csm_batch(ctx, queries, count, results, statuses, &st));
+  }
+  st.synchronizations = ctx->host_syncs - syncs0;
+  st.read_backs = ctx->read_backs - read_backs0;
+  if (stats != nullptr) *stats = st;
+  return DLIOM_OK;
 }
 
 }  // extern "C"

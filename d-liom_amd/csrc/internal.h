@@ -122,6 +122,13 @@ struct dliom_ctx {
   int64_t voxel_unpacked_reruns = 0;  // voxel filter launches repeated with 21-bit keys (dliom_ctx_voxel_filter_reruns)
   int64_t read_backs = 0;         // wait_done() calls: polled host round trips on this context (dliom_ctx_read_backs)
   int64_t poll_fallbacks = 0;     // wait_done() calls that ran out of their polling time (dliom_ctx_poll_fallbacks)
+  int64_t host_syncs = 0;         // stream synchronisations of the loop-closure paths (dliom_ctx_synchronizations)
+  // the batched loop-closure calls (dliom_fast_csm_match_batch, dliom_csm3d_match_batch): device scratch and a
+  // page-locked block of their own, reserved by the first batch that needs them (contexts that never batch hold neither)
+  dliom::DevBuf batch;
+  void* batch_pinned = nullptr;
+  size_t batch_pinned_bytes = 0;
+  int reserve_batch_pinned(size_t bytes);  // grow-only, contents not preserved; synchronises the stream on growth
   int num_cus = 256;              // of ctx->device (set at creation)
   unsigned func_attr_set = 0;     // kFuncAttr* bits: hipFuncSetAttribute done for this context's device
   // auxiliary stream (dliom_cloud_rotational_histogram_begin / _finish): work that only reads what is already on the
@@ -309,6 +316,16 @@ int zero_words(dliom_ctx* ctx, unsigned** out);
 // rtcsm3d.hip: exact sequential float sums of LUT probabilities under explicit float poses
 int sequential_probability_sums(dliom_ctx* ctx, const dliom_cloud& cloud, const dliom_grid* grid, const float* poses7,
                                 int k, float* sums);
+// The same sums for several (cloud, grid) pairs, only enqueued on ctx->stream: job j scores the poses [first, first + k)
+// of d_rot (w, x, y, z) / d_trans (x, y, z), whose list words d_list[first + i] are i * k + i, into d_sums[first + i].
+// Same kernels and method as sequential_probability_sums, hence the same bits.
+struct SequentialSumJob {
+  const dliom_cloud* cloud;
+  const dliom_grid* grid;
+  int first, k;
+};
+int sequential_probability_sums_enqueue(dliom_ctx* ctx, const SequentialSumJob* jobs, int num_jobs, const float4* d_rot,
+                                        const float* d_trans, const unsigned* d_list, float* d_sums);
 }  // namespace dliom
 
 #endif  // DLIOM_CSRC_INTERNAL_H_

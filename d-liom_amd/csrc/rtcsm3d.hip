@@ -2223,6 +2223,28 @@ int sequential_probability_sums(dliom_ctx* ctx, const dliom_cloud& cloud, const 
   }
   DLIOM_HIP_TRY(hipMemcpyAsync(sums, d_ksums, K * 4, hipMemcpyDeviceToHost, ctx->stream));
   DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // also keeps `host` alive long enough
+  ++ctx->host_syncs;
+  return DLIOM_OK;
+}
+
+int sequential_probability_sums_enqueue(dliom_ctx* ctx, const SequentialSumJob* jobs, int num_jobs, const float4* d_rot,
+                                        const float* d_trans, const unsigned* d_list, float* d_sums) {
+  // launch_sequential_sums' scratch, reserved once for the largest job: growing it between the launches would free
+  // memory the launches before still use
+  size_t most = 0;
+  for (int j = 0; j < num_jobs; ++j) {
+    if (jobs[j].k <= 0 || jobs[j].k > 65535 || jobs[j].cloud->n <= 0) return DLIOM_ERR_INVALID_ARGUMENT;
+    const int n = static_cast<int>(jobs[j].cloud->n), n_stride = (n + 7) & ~7, chunks = (n + kChunk - 1) / kChunk;
+    const size_t count = static_cast<size_t>(jobs[j].k);
+    most = std::max(most, ((count * n_stride * 2 + 255) & ~static_cast<size_t>(255)) +
+                              ((count * chunks * 8 + 255) & ~static_cast<size_t>(255)) + count * chunks * sizeof(ChunkFns));
+  }
+  DLIOM_TRY(ctx->misc.reserve(most));
+  for (int j = 0; j < num_jobs; ++j) {
+    const SequentialSumJob& b = jobs[j];
+    DLIOM_TRY(launch_sequential_sums(ctx, kRescoreMethod, b.grid->view(), *b.cloud, d_rot + b.first, b.k, d_trans + 3 * b.first,
+                                     d_list + b.first, nullptr, static_cast<unsigned>(b.k), &ctx->misc, d_sums + b.first));
+  }
   return DLIOM_OK;
 }
 }  // namespace dliom

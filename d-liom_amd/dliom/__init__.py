@@ -132,6 +132,28 @@ class FastCsmResult(C.Structure):
                 ("num_scored_candidates", C.c_int64), ("num_score_launches", C.c_int64)]
 
 
+class BatchStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("batched", "per_query", "per_query_frontier", "per_query_one_launch",
+                                         "without_search", "chunks", "frontier_chains", "lm_launches", "cache_misses",
+                                         "synchronizations", "read_backs")]
+
+
+FAST_CSM_MATCH, FAST_CSM_MATCH_FULL_SUBMAP, FAST_CSM_MATCH_WITH_3DOF_INITIAL = 0, 1, 2
+_FAST_CSM_KINDS = {"Match": FAST_CSM_MATCH, "MatchFullSubmap": FAST_CSM_MATCH_FULL_SUBMAP,
+                   "MatchWith3DofInitial": FAST_CSM_MATCH_WITH_3DOF_INITIAL}
+
+
+class FastCsmQuery(C.Structure):
+    _fields_ = [("kind", C.c_int), ("matcher", _vp), ("pose", C.c_double * 7), ("submap_pose", C.c_double * 7),
+                ("node_data", FastCsmNodeData), ("histogram_size", C.c_int), ("min_score", C.c_float)]
+
+
+class CsmProblem(C.Structure):
+    _fields_ = [("target_translation", C.c_double * 3), ("initial_pose_estimate", C.c_double * 7),
+                ("num_clouds", C.c_int), ("points_xyz", _f32p * MAX_CLOUDS), ("n", C.c_int64 * MAX_CLOUDS),
+                ("clouds", _vp * MAX_CLOUDS), ("grids", _vp * MAX_CLOUDS)]
+
+
 class ImuNoise(C.Structure):
     _fields_ = [("acc_n", C.c_double), ("gyr_n", C.c_double), ("acc_w", C.c_double), ("gyr_w", C.c_double)]
 
@@ -274,6 +296,11 @@ SYMBOLS = [
     ("dliom_fast_csm_match_with_3dof_initial", C.c_int, [_vp, _vp, _f64p, C.POINTER(FastCsmNodeData), C.c_float,
                                                          C.POINTER(FastCsmResult)]),
     ("dliom_fast_csm_level", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(C.c_uint8), C.c_int64]),
+    ("dliom_fast_csm_match_batch", C.c_int, [_vp, C.POINTER(FastCsmQuery), C.c_int, C.POINTER(FastCsmResult),
+                                             C.POINTER(C.c_int), C.POINTER(BatchStats)]),
+    ("dliom_csm3d_match_batch", C.c_int, [_vp, C.POINTER(CsmOptions), C.c_int, C.POINTER(CsmProblem), _f64p,
+                                          C.POINTER(CsmSummary), C.POINTER(C.c_int), C.POINTER(BatchStats)]),
+    ("dliom_ctx_synchronizations", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("dliom_range_accumulator_create", C.c_int, [_vp, C.POINTER(_vp)]),
     ("dliom_range_accumulator_destroy", C.c_int, [_vp]),
     ("dliom_range_accumulator_add", C.c_int, [_vp, _f64p, _f64p, C.c_double, _f32p, _f32p, C.c_int64, _f32p, C.c_int,
@@ -440,6 +467,12 @@ class Context:
 
     def host_unregister(self, array):
         _check(self._L.dliom_host_unregister(self.h, C.c_void_p(array.ctypes.data)), "host_unregister")
+
+    def synchronizations(self):
+        """dliom_ctx_synchronizations: stream synchronisations of the loop-closure paths on this context so far."""
+        n = C.c_int64()
+        _check(self._L.dliom_ctx_synchronizations(self.h, C.byref(n)), "synchronizations")
+        return n.value
 
     def read_backs(self):
         """dliom_ctx_read_backs: polled host round trips on this context so far."""
@@ -903,6 +936,36 @@ class CeresScanMatcher3D:
         _check(s, "dliom_csm3d_match")
         return out, {f: getattr(summ, f) for f, _ in CsmSummary._fields_}
 
+    def match_batch(self, problems):
+        """dliom_csm3d_match_batch.  problems: (target_translation, initial_pose_estimate, [(cloud, grid), ...]) with
+        clouds as PointCloud or (n, 3) arrays.  Returns (poses[n, 7], summaries, statuses, stats); every pose and summary
+        equals Match() of the same problem."""
+        n = len(problems)
+        arr = (CsmProblem * max(n, 1))()
+        keep = []
+        for i, (tgt, init, pairs) in enumerate(problems):
+            q = arr[i]
+            q.target_translation[:] = [float(v) for v in tgt]
+            q.initial_pose_estimate[:] = [float(v) for v in init]
+            q.num_clouds = len(pairs)
+            for j, (c, g) in enumerate(pairs[:MAX_CLOUDS]):
+                q.grids[j] = g.h
+                if isinstance(c, PointCloud):
+                    q.clouds[j] = c.h
+                else:
+                    a = _f32(c).reshape(-1, 3)
+                    keep.append(a)
+                    q.points_xyz[j] = _p(a, _f32p)
+                    q.n[j] = len(a)
+        poses = np.zeros((max(n, 1), 7))
+        summ = (CsmSummary * max(n, 1))()
+        st = (C.c_int * max(n, 1))()
+        stats = BatchStats()
+        _check(self._L.dliom_csm3d_match_batch(self.ctx.h, C.byref(self.options), n, arr, _p(poses, _f64p), summ, st,
+                                               C.byref(stats)), "dliom_csm3d_match_batch")
+        return (poses[:n], [{f: getattr(summ[i], f) for f, _ in CsmSummary._fields_} for i in range(n)],
+                [st[i] for i in range(n)], {f: getattr(stats, f) for f, _ in BatchStats._fields_})
+
     def evaluate(self, target_translation, initial_pose_estimate, pose, point_clouds_and_hybrid_grids):
         k = len(point_clouds_and_hybrid_grids)
         arrs = [_f32(c).reshape(-1, 3) for c, _ in point_clouds_and_hybrid_grids]
@@ -1313,6 +1376,67 @@ class FastCorrelativeScanMatcher3D:
                                                               C.c_float(min_score), C.byref(r)),
                "dliom_fast_csm_match_with_3dof_initial")
         return self._result(r)
+
+
+def fast_csm_match_batch(ctx, queries):
+    """dliom_fast_csm_match_batch.  queries: dicts with kind ("Match", "MatchFullSubmap", "MatchWith3DofInitial"),
+    matcher (FastCorrelativeScanMatcher3D), the kind's pose arguments (global_node_pose + global_submap_pose,
+    global_node_rotation + global_submap_rotation, or pose_in_submap_guess), data (as for Match) and min_score.
+    Returns (results, statuses, stats); results[i] is what the single call returns (its dict)."""
+    L = ctx._L
+    n = len(queries)
+    arr = (FastCsmQuery * max(n, 1))()
+    keep = []
+    for i, q in enumerate(queries):
+        m = q["matcher"]
+        kind = _FAST_CSM_KINDS[q["kind"]]
+        d = m._data(q["data"])
+        keep.append((m._hi, m._lo, m._hist))
+        a = arr[i]
+        a.kind = kind
+        a.matcher = m.h
+        if kind == FAST_CSM_MATCH:
+            a.pose[:] = [float(v) for v in q["global_node_pose"]]
+            a.submap_pose[:] = [float(v) for v in q["global_submap_pose"]]
+        elif kind == FAST_CSM_MATCH_FULL_SUBMAP:
+            a.pose[:4] = [float(v) for v in q["global_node_rotation"]]
+            a.submap_pose[:4] = [float(v) for v in q["global_submap_rotation"]]
+        else:
+            a.pose[:] = [float(v) for v in q["pose_in_submap_guess"]]
+        a.node_data = d
+        a.histogram_size = m.hist_size
+        a.min_score = float(q["min_score"])
+    res = (FastCsmResult * max(n, 1))()
+    st = (C.c_int * max(n, 1))()
+    stats = BatchStats()
+    _check(L.dliom_fast_csm_match_batch(ctx.h, arr, n, res, st, C.byref(stats)), "dliom_fast_csm_match_batch")
+    return ([FastCorrelativeScanMatcher3D._result(res[i]) for i in range(n)], [st[i] for i in range(n)],
+            {f: getattr(stats, f) for f, _ in BatchStats._fields_})
+
+
+def compute_constraints(ctx, queries, ceres_scan_matcher):
+    """ConstraintBuilder3D::ComputeConstraint's three stages (constraint_builder_3d.cc:202-334) for a list of queries
+    (fast_csm_match_batch's dicts): the fast estimate, the prune when it finds nothing, and CeresScanMatcher3D::Match
+    with target = the match's translation, initial = the match's pose and the clouds {high resolution, B's high
+    resolution grid}, {low resolution, B's low resolution grid}.  Returns per query None (no constraint) or a dict with
+    the fast search's result under "match" and the refined pose under "pose"; and the two calls' stats."""
+    results, statuses, fast_stats = fast_csm_match_batch(ctx, queries)
+    for s in statuses:
+        _check(s, "dliom_fast_csm_match_batch")
+    found = [i for i, r in enumerate(results) if r["found"]]
+    problems = []
+    for i in found:
+        q, r = queries[i], results[i]
+        hi_grid, lo_grid = q["matcher"].grids
+        problems.append((r["pose"][:3], r["pose"], [(q["data"]["high_resolution_point_cloud"], hi_grid),
+                                                   (q["data"]["low_resolution_point_cloud"], lo_grid)]))
+    poses, _, csm_statuses, csm_stats = ceres_scan_matcher.match_batch(problems)
+    for s in csm_statuses:
+        _check(s, "dliom_csm3d_match_batch")
+    out = [None] * len(queries)
+    for k, i in enumerate(found):
+        out[i] = dict(match=results[i], pose=poses[k])
+    return out, fast_stats, csm_stats
 
 
 def cloud_rotational_histogram(ctx, cloud, histogram_size, rotation_wxyz=None):

@@ -336,6 +336,25 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* options,
                             const double initial_pose_estimate[7], int num_clouds,
                             const dliom_cloud* const* clouds, const dliom_grid* const* grids,
                             double pose_estimate[7], dliom_csm_summary* summary);
+/* One CeresScanMatcher3D::Match of a batch (dliom_csm3d_match_batch): cloud j is clouds[j] when that is not NULL, else
+ * the host points points_xyz[j] (n[j] of them). */
+typedef struct dliom_batch_stats dliom_batch_stats;  /* below, with the batched loop-closure search */
+typedef struct dliom_csm_problem {
+  double target_translation[3];
+  double initial_pose_estimate[7];
+  int num_clouds;
+  const float* points_xyz[DLIOM_MAX_CLOUDS];
+  int64_t n[DLIOM_MAX_CLOUDS];
+  const dliom_cloud* clouds[DLIOM_MAX_CLOUDS];
+  const dliom_grid* grids[DLIOM_MAX_CLOUDS];
+} dliom_csm_problem;
+/* The refinement stage of a batch of loop-closure constraints (constraint_builder_3d.cc:311-320: one option set for
+ * the batch).  poses[7 * i], summaries[i] (may be NULL) and statuses[i] = what dliom_csm3d_match of problems[i] gives,
+ * bit for bit.  Problems up to DLIOM_TUNE_CSM_ONE_LAUNCH_MAX points run in ONE launch of csm_lm_batch_kernel (one
+ * workgroup each, one completion word for all); larger ones take the single call's path.  NULL pointers (a grid, host
+ * points with n > 0) or count < 0 fail the whole call with DLIOM_ERR_INVALID_ARGUMENT before anything runs. */
+int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* options, int count, const dliom_csm_problem* problems,
+                            double* poses, dliom_csm_summary* summaries, int* statuses, dliom_batch_stats* stats);
 
 /* ---- scan-to-submap front end --------------------------------------------------------------
  * LocalTrajectoryBuilder3D::AddAccumulatedRangeData + InsertIntoSubmap
@@ -562,6 +581,50 @@ int dliom_fast_csm_match_with_3dof_initial(dliom_ctx* ctx, const dliom_fast_csm*
  * (0,0,0) is cell lo[]; everything outside is 0.  values may be NULL to query the box only. */
 int dliom_fast_csm_level(const dliom_fast_csm* matcher, int depth, int32_t lo[3], int32_t dims[3], uint8_t* values,
                          int64_t capacity);
+
+/* ---- Batched loop-closure constraints ------------------------------------------------------------
+ * ConstraintBuilder3D::ComputeConstraintsBetweenSubmaps (mapping/internal/constraints/constraint_builder_3d.cc:162-200)
+ * schedules one ComputeConstraint task (:202-334) per (node, matched submap) pair: a fast search
+ * (MatchWith3DofInitial, or Match / MatchFullSubmap), a prune when it finds nothing, and CeresScanMatcher3D::Match of
+ * the node's two clouds against the submap's two grids.  The two calls below take the whole list at once.  Every result
+ * equals the single call's, bit for bit; queries may name different matchers (submaps).
+ *
+ * Statistics of one batch call (both calls fill it when it is not NULL). */
+struct dliom_batch_stats {
+  int64_t batched;             /* queries / problems served by the batched device path */
+  int64_t per_query;           /* ... served by the single call's own path, for the reasons below: */
+  int64_t per_query_frontier;  /*   fast search outside the device frontier's limits (> 8 192 points, > 4 096
+                                    lowest-resolution candidates, depth 1 or > 16 levels) */
+  int64_t per_query_one_launch;/*   Ceres problem above DLIOM_TUNE_CSM_ONE_LAUNCH_MAX points */
+  int64_t without_search;      /* fast search with no candidate (empty cloud, no discrete scan) or refused with
+                                  DLIOM_ERR_CAPACITY; Ceres problem refused with its single call's status */
+  int64_t chunks;              /* device passes the batch was cut into (scratch and page-locked memory) */
+  int64_t frontier_chains;     /* fast search: discretisation + frontier chains (one per chunk) */
+  int64_t lm_launches;         /* Ceres: csm_lm_batch_kernel launches (one per chunk) */
+  int64_t cache_misses;        /* fast search: scores the recursion fetched on demand after the chain */
+  int64_t synchronizations;    /* host round trips of the call: stream synchronisations (dliom_ctx_synchronizations) */
+  int64_t read_backs;          /*   ... and polled read-backs (dliom_ctx_read_backs) */
+};
+
+enum { DLIOM_FAST_CSM_MATCH = 0, DLIOM_FAST_CSM_MATCH_FULL_SUBMAP = 1, DLIOM_FAST_CSM_MATCH_WITH_3DOF_INITIAL = 2 };
+typedef struct dliom_fast_csm_query {
+  int kind;                         /* DLIOM_FAST_CSM_* */
+  const dliom_fast_csm* matcher;    /* created on the context's device */
+  double pose[7];                   /* Match: global_node_pose; MatchFullSubmap: global_node_rotation (w, x, y, z in
+                                       [0..3]); MatchWith3DofInitial: pose_in_submap_guess */
+  double submap_pose[7];            /* Match: global_submap_pose; MatchFullSubmap: global_submap_rotation in [0..3] */
+  dliom_fast_csm_node_data node_data;
+  int histogram_size;               /* floats of node_data's histogram: must equal the matcher's */
+  float min_score;
+} dliom_fast_csm_query;
+/* results[i] / statuses[i] = what the single call for queries[i] returns (DLIOM_ERR_CAPACITY where run_search refuses).
+ * Malformed input (NULL pointers, count < 0, an unknown kind, a matcher on another device, a histogram size that
+ * differs from the matcher's, node data the single call refuses) fails the whole call with DLIOM_ERR_INVALID_ARGUMENT
+ * before anything runs.  The discrete scans of all queries are made in one launch and their branch-and-bound frontiers
+ * in one chain, followed by the low-resolution scores of the leaves the recursions are expected to test; the host
+ * recursion then runs once per query, in query order.  Large batches are cut into chunks (results do not depend on it). */
+int dliom_fast_csm_match_batch(dliom_ctx* ctx, const dliom_fast_csm_query* queries, int count,
+                               dliom_fast_csm_result* results, int* statuses, dliom_batch_stats* stats);
 
 /* RotationalScanMatcher::ComputeHistogram (rotational_scan_matcher.cc:159-170; called per inserted
  * scan, local_trajectory_builder_3d.cc:605-610) on the host: histogram_size floats.  Clouds of 8192 points and more
@@ -819,6 +882,9 @@ int dliom_ctx_poll_fallbacks(const dliom_ctx* ctx, int64_t* count);
 /* *count = polled read-backs on this context so far: the host round trips a caller's chain costs (a W-ref scan of the
  * front end: 8, profiles/r5_wref_full.json `read_backs_per_scan`). */
 int dliom_ctx_read_backs(const dliom_ctx* ctx, int64_t* count);
+/* *count = stream synchronisations the loop-closure paths made on this context so far (fast search, CeresScanMatcher3D,
+ * dliom_cloud_create): with dliom_ctx_read_backs, the host round trips of a chain of such calls. */
+int dliom_ctx_synchronizations(const dliom_ctx* ctx, int64_t* count);
 /* The device voxel filter (sensor/internal/voxel_filter.cc:81-131) keeps "voxel -> first point" in a hash table whose
  * entries pack the voxel index (13 bits per axis) and the point index (24 bits) into one word, so that a voxel costs
  * one atomic.  A cloud with a point farther than 4095 voxel edges from the origin (61 m at 1.5 cm) does not fit: the
