@@ -745,6 +745,46 @@ struct LocalTrajectoryBuilderOptions3D {
   int rotational_histogram_size = 120;   // trajectory_builder_3d.lua: rotational_histogram_size
 };
 
+// proto::SubmapQuery::Response (mapping/proto/submap_visualization.proto) as plain structs.  `cells` is the texture's
+// UNCOMPRESSED (value, alpha) bytes: the caller applies common::FastGzipString before it sets the proto field.
+struct SubmapTexture {
+  std::string cells;
+  int width = 0;
+  int height = 0;
+  double resolution = 0.;
+  transform::Rigid3d slice_pose;
+};
+struct SubmapQueryResponse {
+  int submap_version = 0;
+  std::vector<SubmapTexture> textures;  // high resolution, then low resolution
+};
+
+// AddToTextureProto (mapping/3d/submap_3d.cc:53-177) for one grid, without the gzip step (dliom_grid_xray_texture).
+inline SubmapTexture XrayTexture(const dliom_grid* grid, const transform::Rigid3d& global_submap_pose) {
+  const std::array<double, 7> pose = global_submap_pose.ToArray();
+  SubmapTexture t;
+  int32_t w = 0, h = 0;
+  double slice[7];
+  Check(dliom_grid_xray_texture(grid, pose.data(), nullptr, 0, &w, &h, &t.resolution, slice), "dliom_grid_xray_texture");
+  t.cells.resize(static_cast<size_t>(w) * h * 2);
+  if (!t.cells.empty())
+    Check(dliom_grid_xray_texture(grid, pose.data(), reinterpret_cast<uint8_t*>(&t.cells[0]), static_cast<int64_t>(t.cells.size()),
+                                  &w, &h, &t.resolution, slice), "dliom_grid_xray_texture");
+  t.width = w;
+  t.height = h;
+  t.slice_pose = transform::Rigid3d::FromArray(slice);
+  return t;
+}
+
+// ProjectToCvMat's image (D-LIOM mapping/3d/submap_3d.cc:381-443) without OpenCV: `data` is rows x cols CV_8UC1,
+// row-major -- cv::Mat(rows, cols, CV_8UC1, data.data()) wraps it.  Pixel values are the reference's, reduced modulo 256
+// (empty pixels 224); an empty projection is 0 x 0.
+struct ProjectedImage {
+  int rows = 0;
+  int cols = 0;
+  std::vector<uint8_t> data;
+};
+
 // A submap of the active pair; the grids stay owned by the front end (borrowed handles).
 class Submap3D {
  public:
@@ -783,6 +823,15 @@ class Submap3D {
                                   reinterpret_cast<uint8_t*>(&out[0]), n, &n), "dliom_submap3d_to_proto");
     return out;
   }
+  // Submap3D::ToResponseProto (submap_3d.cc:253-262): submap_version = num_range_data, then one X-ray texture per grid,
+  // computed on the device.  The textures' cells are uncompressed (see SubmapTexture).
+  SubmapQueryResponse ToResponseProto(const transform::Rigid3d& global_submap_pose) const {
+    SubmapQueryResponse r;
+    r.submap_version = num_range_data_;
+    r.textures.push_back(XrayTexture(hi_, global_submap_pose));
+    r.textures.push_back(XrayTexture(lo_, global_submap_pose));
+    return r;
+  }
 
  private:
   transform::Rigid3d local_pose_;
@@ -791,6 +840,24 @@ class Submap3D {
   dliom_grid* hi_;
   dliom_grid* lo_;
 };
+
+// ProjectToCvMat(hybrid_grid, transform, ox, oy, resolution) (submap_3d.cc:381-443) on the device
+// (dliom_grid_project_to_image); the caller wraps the result in a cv::Mat, see ProjectedImage.
+inline ProjectedImage ProjectToCvMat(const dliom_grid* hybrid_grid, const transform::Rigid3d& transform, double& ox,
+                                     double& oy, double& resolution) {
+  const std::array<double, 7> pose = transform.ToArray();
+  ProjectedImage img;
+  int32_t w = 0, h = 0;
+  Check(dliom_grid_project_to_image(hybrid_grid, pose.data(), nullptr, 0, &w, &h, &ox, &oy, &resolution),
+        "dliom_grid_project_to_image");
+  img.data.resize(static_cast<size_t>(w) * h);
+  if (!img.data.empty())
+    Check(dliom_grid_project_to_image(hybrid_grid, pose.data(), img.data.data(), static_cast<int64_t>(img.data.size()), &w, &h,
+                                      &ox, &oy, &resolution), "dliom_grid_project_to_image");
+  img.rows = h;
+  img.cols = w;
+  return img;
+}
 
 // ActiveSubmaps3D (mapping/3d/submap_3d.h:95-122) over the front end's submap pair.
 class ActiveSubmaps3D {

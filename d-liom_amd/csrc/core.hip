@@ -784,6 +784,8 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
   ctx->box_extents.release();
   ctx->csm_arrivals.release();
   ctx->batch.release();
+  ctx->xray_leaves.release();
+  ctx->xray_cells.release();
   if (ctx->batch_pinned != nullptr) (void)hipHostFree(ctx->batch_pinned);
   ctx->aux_scratch.release();
   if (ctx->aux_pinned != nullptr) (void)hipHostFree(ctx->aux_pinned);
@@ -825,7 +827,8 @@ int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out) {
   out->mirrors_refused = l.mirrors_refused;
   const dliom::DevBuf* bufs[] = {&ctx->points, &ctx->cand, &ctx->sums, &ctx->bounds, &ctx->rescore, &ctx->partials, &ctx->misc,
                                  &ctx->sort_tmp, &ctx->voxel, &ctx->box_tables, &ctx->box_counters, &ctx->box_extents,
-                                 &ctx->csm_arrivals, &ctx->box_error, &ctx->deskew_flags, &ctx->zero_words, &ctx->aux_scratch};
+                                 &ctx->csm_arrivals, &ctx->box_error, &ctx->deskew_flags, &ctx->zero_words, &ctx->aux_scratch,
+                                 &ctx->xray_leaves, &ctx->xray_cells};
   for (const dliom::DevBuf* b : bufs) out->scratch_bytes += static_cast<int64_t>(b->cap);
   return DLIOM_OK;
 }

@@ -126,6 +126,8 @@ struct dliom_ctx {
   // the batched loop-closure calls (dliom_fast_csm_match_batch, dliom_csm3d_match_batch): device scratch and a
   // page-locked block of their own, reserved by the first batch that needs them (contexts that never batch hold neither)
   dliom::DevBuf batch;
+  // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
+  dliom::DevBuf xray_leaves, xray_cells;
   void* batch_pinned = nullptr;
   size_t batch_pinned_bytes = 0;
   int reserve_batch_pinned(size_t bytes);  // grow-only, contents not preserved; synchronises the stream on growth

@@ -227,6 +227,10 @@ SYMBOLS = [
     ("dliom_grid_num_blocks", C.c_int, [_vp, _i64p]),
     ("dliom_grid_download_blocks", C.c_int, [_vp, _i32p, _u16p, C.c_int64, _i64p]),
     ("dliom_grid_get_values", C.c_int, [_vp, _i32p, C.c_int64, _u16p]),
+    ("dliom_grid_xray_texture", C.c_int, [_vp, _f64p, C.POINTER(C.c_uint8), C.c_int64, _i32p, _i32p, _f64p, _f64p]),
+    ("dliom_grid_project_to_image", C.c_int, [_vp, _f64p, C.POINTER(C.c_uint8), C.c_int64, _i32p, _i32p, _f64p, _f64p,
+                                              _f64p]),
+    ("dliom_probability_to_log_odds_integer", C.c_uint8, [C.c_float]),
     ("dliom_grid_to_proto", C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_int64, _i64p]),
     ("dliom_grid_from_proto", C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(_vp)]),
     ("dliom_submap3d_to_proto", C.c_int, [_f64p, C.c_int32, C.c_int, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_uint8),
@@ -1014,6 +1018,55 @@ def submap3d_from_proto(data, wrapped=False):
     hi = None if hs.value < 0 else bytes(data[ho.value:ho.value + hs.value])
     low = None if ls.value < 0 else bytes(data[lo.value:lo.value + ls.value])
     return pose, n.value, bool(fin.value), hi, low
+
+
+XRAY_MAX_PIXELS = 1 << 26  # DLIOM_XRAY_MAX_PIXELS
+
+
+def _pose7(pose):
+    p = _f64(pose).reshape(-1)
+    if p.shape != (7,):
+        raise ValueError("pose must be (tx, ty, tz, qw, qx, qy, qz)")
+    return p
+
+
+def grid_xray_texture(grid, pose):
+    """Submap3D::ToResponseProto's texture of one grid (submap_3d.cc:53-177) at `global_submap_pose`, on the device:
+    (width, height, resolution, slice_pose7, cells) with cells the uncompressed (height, width, 2) uint8 array of
+    (value, alpha).  An empty projection is 0 x 0."""
+    p = _pose7(pose)
+    w, h, res = C.c_int32(), C.c_int32(), C.c_double()
+    slice_pose = np.zeros(7, dtype=np.float64)
+    L = grid._L
+    _check(L.dliom_grid_xray_texture(grid.h, _p(p, _f64p), None, 0, C.byref(w), C.byref(h), C.byref(res),
+                                     _p(slice_pose, _f64p)), "dliom_grid_xray_texture")
+    cells = np.zeros((h.value, w.value, 2), dtype=np.uint8)
+    if cells.size:
+        _check(L.dliom_grid_xray_texture(grid.h, _p(p, _f64p), _p(cells, C.POINTER(C.c_uint8)), cells.size, C.byref(w),
+                                         C.byref(h), C.byref(res), _p(slice_pose, _f64p)), "dliom_grid_xray_texture")
+    return w.value, h.value, res.value, slice_pose, cells
+
+
+def grid_project_to_image(grid, pose):
+    """D-LIOM's ProjectToCvMat (submap_3d.cc:381-443) on the device: (image, ox, oy, resolution) with image the
+    (height, width) uint8 array the reference wraps in a CV_8UC1 cv::Mat (values reduced modulo 256, empty pixels
+    224).  An empty projection is 0 x 0."""
+    p = _pose7(pose)
+    w, h, ox, oy, res = C.c_int32(), C.c_int32(), C.c_double(), C.c_double(), C.c_double()
+    L = grid._L
+    _check(L.dliom_grid_project_to_image(grid.h, _p(p, _f64p), None, 0, C.byref(w), C.byref(h), C.byref(ox), C.byref(oy),
+                                         C.byref(res)), "dliom_grid_project_to_image")
+    image = np.zeros((h.value, w.value), dtype=np.uint8)
+    if image.size:
+        _check(L.dliom_grid_project_to_image(grid.h, _p(p, _f64p), _p(image, C.POINTER(C.c_uint8)), image.size, C.byref(w),
+                                             C.byref(h), C.byref(ox), C.byref(oy), C.byref(res)),
+               "dliom_grid_project_to_image")
+    return image, ox.value, oy.value, res.value
+
+
+def probability_to_log_odds_integer(probability):
+    """ProbabilityToLogOddsInteger (mapping/submaps.h:37-52) from the library's step table (host)."""
+    return int(load_library().dliom_probability_to_log_odds_integer(C.c_float(probability)))
 
 
 def voxel_filter(size, points):

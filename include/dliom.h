@@ -141,6 +141,42 @@ int dliom_submap3d_to_proto(const double local_pose7[7], int32_t num_range_data,
 int dliom_submap3d_from_proto(const uint8_t* buffer, int64_t size, int wrapped_in_submap, double local_pose7[7],
                               int32_t* num_range_data, int* finished, int64_t* high_offset, int64_t* high_size,
                               int64_t* low_offset, int64_t* low_size);
+/* ---- X-ray projections of a grid (mapping/3d/submap_3d.cc), computed on the device from the leaf pool ----
+ * Both reproduce the reference's float arithmetic byte for byte: the cells with ValueToProbability(v) >= 0.501 in
+ * HybridGrid::Iterator order, each cell centre index * resolution transformed in float and rounded with
+ * RoundToInt(c * resolution_inverse), a per-pixel float probability sum added in iterator order.
+ * Sizes follow dliom_grid_to_proto: buffer == NULL is a size query (DLIOM_OK, sizes filled); a buffer smaller than
+ * the image fills the sizes and returns DLIOM_ERR_CAPACITY; a NULL grid, pose or size pointer returns
+ * DLIOM_ERR_INVALID_ARGUMENT.  A projection of more than DLIOM_XRAY_MAX_PIXELS pixels fills the sizes and returns
+ * DLIOM_ERR_CAPACITY whatever the buffer.
+ * Empty projection: when no cell reaches 0.501 the reference's bounding box stays at (INT_MAX, INT_MIN) and its size
+ * computation overflows (undefined).  Here that is DLIOM_OK with width = height = 0 and nothing written.
+ * Runs on the grid's context stream and synchronises it; one small read-back (the bounding box) sizes the image. */
+#define DLIOM_XRAY_MAX_PIXELS (INT64_C(1) << 26)
+/* Submap3D::ToResponseProto's AddToTextureProto (submap_3d.cc:53-177, 253-262) without the gzip step.
+ *   cells        height * width (value, alpha) byte pairs, row (max_x - px), column (max_y - py): the texture's
+ *                uncompressed `cells` (the caller applies common::FastGzipString); capacity in bytes
+ *   width        max_y - min_y + 1, height max_x - min_x + 1 of the rounded xy indices
+ *   resolution   the grid's (float) resolution
+ *   slice_pose7  global_submap_pose.inverse() * Translation(max_x * res, max_y * res, global_submap_pose.z), the
+ *                products in float widened to double (for an empty projection max_x = max_y = 0)
+ * Poses are (tx, ty, tz, qw, qx, qy, qz); the cell transform is global_submap_pose.cast<float>(). */
+int dliom_grid_xray_texture(const dliom_grid* grid, const double global_submap_pose7[7], uint8_t* cells, int64_t capacity,
+                            int32_t* width, int32_t* height, double* resolution, double slice_pose7[7]);
+/* D-LIOM's ProjectToCvMat (submap_3d.cc:381-443): the gravity-aligned, yaw-free top-down CV_8UC1 image for loop
+ * detection.  The cells are rotated by Embed3D(Rigid2d::Rotation(-GetYaw(T))).cast<float>() *
+ * Rigid3d::Rotation(T.rotation()).cast<float>() (no translation; transform.h:43-52, 110-115).
+ *   image        height * width bytes, row-major: pixel (py - min_y) * width + (px - min_x); capacity in bytes
+ *   width        max_x - min_x + 1, height max_y - min_y + 1; ox = min_x * resolution, oy = min_y * resolution (double)
+ * Every pixel, empty ones included, is RoundToInt((probability_sum - 0.1f) * (255.f / 0.8f)) stored into a uchar,
+ * i.e. reduced modulo 256, as the reference stores it before cv::threshold: an empty pixel is 224 and a column whose
+ * sum exceeds ~0.9 wraps past 255.  This is the reference's behaviour, kept on purpose. */
+int dliom_grid_project_to_image(const dliom_grid* grid, const double transform7[7], uint8_t* image, int64_t capacity,
+                                int32_t* width, int32_t* height, double* ox, double* oy, double* resolution);
+/* ProbabilityToLogOddsInteger (mapping/submaps.h:37-52, glibc logf) for probability in [0.1, 0.9], as the texture
+ * kernel evaluates it: from a table of the 254 floats where the result steps up, built on the host when the
+ * library loads (1 below 0.1, 255 above 0.9). */
+uint8_t dliom_probability_to_log_odds_integer(float probability);
 /* HybridGrid::value() for n cell indices (0 outside / unallocated). */
 int dliom_grid_get_values(const dliom_grid* grid, const int32_t* cell_xyz, int64_t n,
                           uint16_t* values);
