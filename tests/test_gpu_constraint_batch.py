@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import DEFAULT_CSM, build_oracle_submap, to_device_grid
+from helpers import DEFAULT_CSM, build_oracle_submap, pose_distance, to_device_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -228,6 +228,8 @@ def test_csm_batch_equals_single_and_oracle(dl, ctx, orc, scene):
             assert np.array_equal(p, p1) and s == s1
             ro = orc.csm3d_match(copts, tgt, init, [(cg[0][0], oh), (cg[1][0], ol)])
             assert np.linalg.norm(p[:3] - ro["pose"][:3]) <= 1e-6
+            dt, dr = pose_distance(p, ro["pose"])
+            assert dt <= 1e-6 and dr <= 1e-6
             assert s["num_iterations"] == ro["num_iterations"]
 
 
@@ -256,6 +258,8 @@ def test_compute_constraints_equals_oracle_chain(dl, ctx, orc, scene):
         rc = orc.csm3d_match(copts, ro["pose"][:3], ro["pose"], [(q["data"]["high_resolution_point_cloud"], b.og_hi),
                                                                 (q["data"]["low_resolution_point_cloud"], b.og_lo)])
         assert np.linalg.norm(c["pose"][:3] - rc["pose"][:3]) <= 1e-6
+        dt, dr = pose_distance(c["pose"], rc["pose"])
+        assert dt <= 1e-6 and dr <= 1e-6
     assert found > 0 and pruned > 0
 
 

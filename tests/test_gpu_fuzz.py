@@ -54,3 +54,11 @@ def test_fuzz_box_variants_slice(capsys):
     (tools/fuzz_box_variants.py): every integer sum, winner index, score bits, pose."""
     out = _run("fuzz_box_variants", ["--cases", "40", "--seed", "96000", "--seconds", "60"], capsys)
     assert "box variant fuzz ok" in out
+
+
+def test_fuzz_constraint_batch_slice(capsys):
+    """dliom_fast_csm_match_batch and CeresScanMatcher3D.match_batch on random batches over 1-4 random matchers (cube and
+    yard scenes, depths 1-7, all three query kinds, duplicates, cloud sizes on the kernels' chunk and padding edges)
+    against the single calls and the oracle (tools/fuzz_constraint_batch.py)."""
+    out = _run("fuzz_constraint_batch", ["--cases", "300", "--seed", "97000", "--seconds", "58"], capsys)
+    assert "constraint batch fuzz ok" in out
