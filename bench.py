@@ -15,10 +15,15 @@ region starts.
 N > 1: one process per GPU, every rank runs its own independent scan stream against its own
 submap (weak scaling, no data-path collective; SURVEY.md 8e "replicas").  `python bench.py --gpus N`
 without a launcher starts the N ranks itself (re-executes under torch.distributed.run); the printed
-`n_gpus` is the communicator's size.  Rank 0 prints ONE JSON line; for N > 1 it also carries `sharded`
-(config 4: the same stream with the search window sharded over the ranks) and `sharded_config5` (the
-128 x 2048 @ 5 cm search, 98 % score volume, sharded the same way).  The CPU oracle is used ONLY for the
-`cpu_baseline` / `parity` legs (rank 0, N == 1), after the timed region.
+`n_gpus` is the communicator's size.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line: nothing else
+runs.  --full adds everything else the benchmark measures or checks, after the timed region: the per-kernel
+breakdown (`kernel_ms_per_scan`, extra untimed steps), `roofline` (rocprofv3 --pmc child runs), the one-rank
+RCCL check, `wref`, `config5`, `parity` and `cpu_baseline` (N == 1; the only legs that use the CPU oracle), and
+for N > 1 `sharded` (config 4: the same stream with the search window sharded over the ranks) and
+`sharded_config5` (the 128 x 2048 @ 5 cm search, 98 % score volume, sharded the same way).  The --no-* options
+trim a --full run.
 """
 import argparse
 import json
@@ -54,6 +59,9 @@ def parse():
     ap.add_argument("--shard-candidates", action="store_true",
                     help="config 4: ONE scan stream; the RTCSM search window is sharded over the ranks "
                          "(two 8-byte RCCL max all-reduces per scan), Ceres + insertion replicated")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: per-kernel breakdown, roofline counters, RCCL check, "
+                         "W-ref, config 5, parity, CPU baseline; N > 1: the sharded lines")
     ap.add_argument("--no-cpu-baseline", action="store_true",
                     help="skips the CPU oracle leg (cpu_baseline AND the post-timing parity check)")
     ap.add_argument("--no-wref", action="store_true", help="skips the W-ref (reference-faithful filter chain) line")
@@ -159,9 +167,11 @@ def main():
     # ---------------------------------------------------------------- scene (per rank: own time offset)
     # the sharded lines go through the library's own RCCL entry point (dliom_rtcsm3d_match_sharded_rccl, an ncclComm_t of
     # this process) when the backend is nccl -- also on ONE rank (--gpus 1 --shard-candidates: a one-rank communicator,
-    # same winner as the unsharded line); DLIOM_BENCH_BACKEND=gloo keeps the callback entry point over host collectives
+    # same winner as the unsharded line); DLIOM_BENCH_BACKEND=gloo keeps the callback entry point over host collectives.
+    # A plain N > 1 replica run has no sharded line, so it sets up no shard
+    uses_shards = args.shard_candidates or (world > 1 and args.full)
     rccl_comm = None
-    if backend == "nccl" and (world > 1 or args.shard_candidates):
+    if backend == "nccl" and uses_shards:
         from dliom import sharded as _sh
         rccl_comm = _sh.RcclCommunicator(rank, world, dist)
         assert rccl_comm.ranks_seen == world, (rccl_comm.ranks_seen, world)
@@ -175,7 +185,7 @@ def main():
 
     rt = dl.RealTimeCorrelativeScanMatcher3D(ctx, RTCSM_OPTS)
     cs = dl.CeresScanMatcher3D(ctx, CSM_OPTS)
-    shard = dl.RtcsmShard(ctx, RTCSM_OPTS, rank, world) if (world > 1 or rccl_comm is not None) else None
+    shard = dl.RtcsmShard(ctx, RTCSM_OPTS, rank, world) if uses_shards and (world > 1 or rccl_comm is not None) else None
     from dliom import sharded
     dev = coll_device
 
@@ -227,7 +237,7 @@ def main():
     for i in range(args.warmup):
         step(i, False)
     # HIP events around the dominant kernel only inside the timed region (roofline.achieved); the
-    # per-kernel breakdown comes from a few extra, untimed steps with every kernel timed
+    # per-kernel breakdown (--full) comes from a few extra, untimed steps with every kernel timed
     ctx.set_profiling(2)
     ctx.reset_profiling()
     # The harness, not the product: with torch imported a full (generation 2) collection of CPython's cyclic garbage
@@ -251,6 +261,9 @@ def main():
         elapsed = float(t.item())
 
     gc.enable()
+    st = rt.last_stats()  # the last timed step's match
+    n_pts = int(st.num_points)
+    C = int(st.window.num_candidates)
     # the grids as the last timed step left them: every later leg inserts into them again
     dumped = None
     if args.dump_outputs and rank == 0:
@@ -262,7 +275,7 @@ def main():
     # N > 1 replica run: the same scans once more with the search window SHARDED over the ranks (BASELINE config 4).
     # Replicas hold identical submaps, so every rank can take its share of the rotations of ONE stream: strong scaling.
     sharded_line = None
-    if world > 1 and not sharded_mode:
+    if args.full and world > 1 and not sharded_mode:
         use_shards[0] = True
         for i in range(args.warmup):
             step(args.warmup + args.steps + i, False)
@@ -313,29 +326,28 @@ def main():
     # ... and the search where sharding pays: config 5 (128 x 2048 returns, 5 cm voxels, ~3e6 candidates), whose step
     # is 98 % score volume -- every rank builds the same small submap and takes its share of the rotations
     config5_sharded = None
-    if world > 1 and not sharded_mode and args.config == 2 and not args.no_config5:
+    if args.full and world > 1 and not sharded_mode and args.config == 2 and not args.no_config5:
         config5_sharded = config5_sharded_line(args, dl, synth, ctx, rank, world, dist, coll_device, torch, sharded,
                                                rccl_comm)
 
-    extra = max(1, min(5, args.steps))
-    ctx.set_profiling(1)
-    ctx.reset_profiling()
-    for i in range(extra):
-        step(args.warmup + args.steps + i, False)
-    fence()
-    breakdown = {name: ctx.kernel_time(kid)[0] / extra for name, kid in (
-        ("rtcsm_score", dl.KERNEL_RTCSM_SCORE), ("rtcsm_select", dl.KERNEL_RTCSM_SELECT),
-        ("rtcsm_rescore", dl.KERNEL_RTCSM_RESCORE), ("csm_eval", dl.KERNEL_CSM_EVAL),
-        ("insert", dl.KERNEL_INSERT))}
-    ctx.set_profiling(0)
-    st = rt.last_stats()
-    n_pts = int(st.num_points)
-    C = int(st.window.num_candidates)
+    breakdown = None
+    if args.full:
+        extra = max(1, min(5, args.steps))
+        ctx.set_profiling(1)
+        ctx.reset_profiling()
+        for i in range(extra):
+            step(args.warmup + args.steps + i, False)
+        fence()
+        breakdown = {name: ctx.kernel_time(kid)[0] / extra for name, kid in (
+            ("rtcsm_score", dl.KERNEL_RTCSM_SCORE), ("rtcsm_select", dl.KERNEL_RTCSM_SELECT),
+            ("rtcsm_rescore", dl.KERNEL_RTCSM_RESCORE), ("csm_eval", dl.KERNEL_CSM_EVAL),
+            ("insert", dl.KERNEL_INSERT))}
+        ctx.set_profiling(0)
 
-    # N = 1: the library's RCCL entry point on a one-rank communicator (ncclAllReduce really runs), so that every driver
+    # N = 1: the library's RCCL entry point on a one-rank communicator (ncclAllReduce really runs), so that every --full
     # line shows it alive: same winner as the unsharded match, and what the collective costs when there is nobody to wait for
     rccl_one_rank = None
-    if world == 1 and backend == "nccl" and not args.no_rccl_check and not sharded_mode:
+    if args.full and world == 1 and backend == "nccl" and not args.no_rccl_check and not sharded_mode:
         try:
             comm1 = sharded.RcclCommunicator(0, 1)
             sh1 = dl.RtcsmShard(ctx, RTCSM_OPTS, 0, 1)
@@ -404,9 +416,10 @@ def main():
             "stage_ms_per_scan": {k: 1e3 * v / args.steps for k, v in stage.items()},
             # the part of a step that does not shard (config 4's Amdahl ceiling): the step minus this rank's score kernel
             "serial_remainder_ms_per_step": 1e3 * elapsed / args.steps - k_ms,
-            "kernel_ms_per_scan": breakdown,
-            "roofline": roofline_block(args, pairs, k_ms, int(score_n), alg_bytes, int(st.score_kernel)),
         }
+        if args.full:
+            out["kernel_ms_per_scan"] = breakdown
+            out["roofline"] = roofline_block(args, pairs, k_ms, int(score_n), alg_bytes, int(st.score_kernel))
         if dumped is not None:
             out["dump_outputs"] = dumped
         if rccl_one_rank is not None:
@@ -415,14 +428,14 @@ def main():
             out["sharded"] = sharded_line
         if config5_sharded is not None:
             out["sharded_config5"] = config5_sharded
-        if world == 1 and not args.no_wref and args.config == 2:
+        if args.full and world == 1 and not args.no_wref and args.config == 2:
             out["wref"] = wref_line(dl, ctx, cpu=not args.no_cpu_baseline)
-        if world == 1 and args.config == 2 and not args.no_config5:
-            try:  # BASELINE config 5 in the driver's record: two active submaps, four grids, C = 2 352 637, three steps
+        if args.full and world == 1 and args.config == 2 and not args.no_config5:
+            try:  # BASELINE config 5 in the --full line: two active submaps, four grids, C = 2 352 637, three steps
                 out["config5"] = config5_line(dl, synth, ctx, steps=3, with_oracle=not args.no_cpu_baseline)
             except Exception as e:
                 out["config5"] = {"error": ("%s: %s" % (type(e).__name__, e))[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from benchlib.cpu_legs import cpu_baseline, parity_check  # the only importer of oracle/
             # the oracle leg: checker first (one more step, compared end to end), then the CPU baseline
             parity = parity_check(dl, ctx, scans[1 % len(scans)], g_hi, g_lo, ins, rt, cs)

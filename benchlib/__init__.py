@@ -1,7 +1,7 @@
 """bench.py's pieces outside the timed region (the timed loop is bench.py and nothing else).
 
   benchlib/__init__.py  constants, the scene (submap + scans), insertion targets
-  benchlib/config5.py   BASELINE config 5: the line the driver times at N = 1, the sharded line at N > 1
+  benchlib/config5.py   BASELINE config 5: the --full line's `config5` at N = 1, the sharded line at N > 1
   benchlib/roofline.py  the `roofline` object: live rocprofv3 --pmc child runs of the same invocation
   benchlib/wref.py      the W-ref lines (tools/wref_full.py)
   benchlib/cpu_legs.py  the ONLY importer of oracle/: the post-timing parity check and the cpu_baseline leg

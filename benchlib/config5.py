@@ -109,7 +109,7 @@ def device_grid_to_oracle(orc, dg, resolution):
 
 def config5_line(dl, synth, ctx, steps=3, with_oracle=True):
     """BASELINE config 5 as BASELINE.json words it -- "128-beam x 2048 dense cloud, 5 cm voxels, multi-submap insertion +
-    scan match" -- short enough for the default N = 1 line, so that the DRIVER times it: the scan matched against the older
+    scan match" -- short enough for the N = 1 --full line, so that every full run times it: the scan matched against the older
     submap's 5 cm grid (RTCSM3D over C = 343 x 19^3 candidates + CeresScanMatcher3D hi + lo) and inserted into all four
     grids by the fused insertion (config5_scene).  Parity in this line: sampled candidates (the full loop is 6e11 lookups,
     minutes on every core of the box); the SAME scene's full loop -- every candidate's integer sum and reference score, the

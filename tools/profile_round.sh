@@ -4,7 +4,7 @@
 #   trace     kernel trace + stats of bench.py (same command as the bench line, no CPU legs)
 #   pmc       PMC passes over the score kernel (separate passes, never combined with tracing: gpurun refuses that)
 #   wreftrace the W-ref chains under the kernel trace (launches per scan, GPU time per scan), both scenes
-#   bench     the full bench line (what the driver runs)
+#   bench     the full bench line (bench.py --full)
 #   config5   config 5 as its own run
 #   gloo2     the N = 2 control run over gloo
 #   wref      W-ref chains, stages, streaming config 3
@@ -54,11 +54,11 @@ fi
 cd $R
 if want bench; then
   SECONDS=0
-  timeout 600 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+  timeout 600 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
   echo "bench rc=$? in $SECONDS s"
 fi
-if want config5; then timeout 500 python bench.py --config 5 --no-wref > $OUT/config5_bench.json 2> $OUT/config5_bench.err; echo "config5 rc=$?"; fi
-if want gloo2; then DLIOM_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 10 --no-wref 2> $OUT/bench_gloo2.err | grep '^{' > $OUT/bench_gloo2.json; echo "gloo2 rc=$?"; fi
+if want config5; then timeout 500 python bench.py --config 5 --full --no-wref > $OUT/config5_bench.json 2> $OUT/config5_bench.err; echo "config5 rc=$?"; fi
+if want gloo2; then DLIOM_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 10 --full --no-wref 2> $OUT/bench_gloo2.err | grep '^{' > $OUT/bench_gloo2.json; echo "gloo2 rc=$?"; fi
 if want wref; then
   timeout 300 python tools/wref_full.py > $OUT/wref_full.json 2> $OUT/wref.err
   timeout 200 python tools/wref.py > $OUT/wref.json 2>> $OUT/wref.err
