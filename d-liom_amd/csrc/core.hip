@@ -730,8 +730,7 @@ static int ctx_create_common(int device_id, hipStream_t stream, bool owns, dliom
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) ctx->num_cus = prop.multiProcessorCount;
   }
-  ctx->pinned_bytes = 1 << 20;
-  hipError_t e = hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocCoherent | hipHostMallocMapped);
+  hipError_t e = hipHostMalloc(&ctx->pinned, kPinnedBytes, hipHostMallocCoherent | hipHostMallocMapped);
   if (e != hipSuccess) {
     set_last_error("hipHostMalloc", e, __FILE__, __LINE__);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);

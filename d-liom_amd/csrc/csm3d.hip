@@ -569,7 +569,7 @@ static int evaluate(CsmProblem* p, const double x[7], Normal* out) {
   const float k_offset = kMin - k_scale;
   const int span = ctx->begin_span(DLIOM_KERNEL_CSM_EVAL);
   // the 28 results go straight into pinned host memory (device-visible): no copy command
-  double* host = static_cast<double*>(ctx->pinned);
+  double* host = pinned_at<double>(ctx, kPinCsmSums);
   // ... and a completion word behind them, which the host polls: ten evaluations a match, 5 us of synchronise each
   unsigned* done = p->d_arrivals != nullptr ? ctx->done_word : nullptr;
   const unsigned seq = done != nullptr ? (++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq) : 0u;
@@ -1284,7 +1284,7 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* o, const do
   const int persistent_max = ctx->tuning[DLIOM_TUNE_CSM_ONE_LAUNCH_MAX];
   if (p.args.total_points <= persistent_max) {
     LmKernelParams prm = lm_params(o, p, cfg, x);
-    LmKernelOut* host = reinterpret_cast<LmKernelOut*>(static_cast<char*>(ctx->pinned) + 1024);  // device-visible
+    LmKernelOut* host = pinned_at<LmKernelOut>(ctx, kPinLmResult);  // device-visible
     prm.done_word = ctx->done_word;
     prm.done_seq = ctx->done_word != nullptr ? (++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq) : 0u;
     const int span = ctx->begin_span(DLIOM_KERNEL_CSM_EVAL);
@@ -1326,7 +1326,7 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* o, const do
     double* partials = ctx->partials.as<double>();
     unsigned* counter = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->partials.p) + part_bytes);
     DLIOM_HIP_TRY(hipMemsetAsync(counter, 0, 4, ctx->stream));
-    LmKernelOut* host = reinterpret_cast<LmKernelOut*>(static_cast<char*>(ctx->pinned) + 1024);  // device-visible
+    LmKernelOut* host = pinned_at<LmKernelOut>(ctx, kPinLmResult);  // device-visible
     const int span = ctx->begin_span(DLIOM_KERNEL_CSM_EVAL);
     if (p.nloc == 3)
       hipLaunchKernelGGL(csm_lm_grid_kernel<3>, dim3(p.num_blocks), dim3(kCsmBlock), 0, ctx->stream, p.args, prm, partials, counter, host);

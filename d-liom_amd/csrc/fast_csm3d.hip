@@ -493,9 +493,9 @@ int device_sums(Search& s, int depth, const std::vector<Candidate>& list, std::v
   const size_t cbytes = (k * 16 + 255) & ~static_cast<size_t>(255);
   DLIOM_TRY(ctx->cand.reserve(cbytes + k * 4));
   // candidate list and sums travel through the pinned block when they fit (no staging copies)
-  const bool pinned = cbytes + k * 4 <= ctx->pinned_bytes - 8192;
+  const bool pinned = cbytes + k * 4 <= kPinFastCsmScores.bytes;
   std::vector<int> pageable;
-  int* host = static_cast<int*>(ctx->pinned);
+  int* host = pinned_at<int>(ctx, kPinFastCsmScores);
   if (!pinned) {
     pageable.resize(4 * k + k);
     host = pageable.data();
@@ -632,11 +632,11 @@ int prefetch_frontier(Search& s, float threshold) {
 // everything the recursion can reach below them into a page-locked region per search.  `h` (page-locked) and `d`
 // (device) hold the same upload: the array of num_searches FrontierArgs, at frontier_counts_at() num_searches x
 // kCountWords counts, then the flat list of `total` lowest-resolution records.  Enqueued only: the caller synchronises.
-size_t frontier_counts_at(int num_searches) {
+constexpr size_t frontier_counts_at(int num_searches) {
   return (num_searches * sizeof(FrontierArgs) + 255) & ~static_cast<size_t>(255);
 }
-size_t frontier_flat_at(int num_searches) { return frontier_counts_at(num_searches) + num_searches * kCountWords * 4; }
-size_t frontier_upload_bytes(int num_searches, size_t total) {
+constexpr size_t frontier_flat_at(int num_searches) { return frontier_counts_at(num_searches) + num_searches * kCountWords * 4; }
+constexpr size_t frontier_upload_bytes(int num_searches, size_t total) {
   return frontier_flat_at(num_searches) + total * sizeof(FrontierRec);
 }
 int enqueue_frontier_chain(dliom_ctx* ctx, int num_searches, int total, int deepest, const char* d) {
@@ -712,16 +712,16 @@ int device_frontier(Search& s, const std::vector<Candidate>& lowest, float min_s
   dliom_ctx* ctx = s.ctx;
   const int max_depth = s.m->max_depth();
   constexpr int kCap = 8192;
-  constexpr size_t kUpload = 256 * 1024;
+  static_assert(frontier_upload_bytes(1, kCap) <= kPinFrontierUpload.bytes, "the largest upload fits its region");
   const size_t k = lowest.size();
-  if (!frontier_suits(s, k, kCap) || ctx->pinned_bytes < (1u << 20)) return DLIOM_OK;
+  if (!frontier_suits(s, k, kCap)) return DLIOM_OK;
   const size_t up = (frontier_upload_bytes(1, k) + 255) & ~static_cast<size_t>(255);
   const size_t pool_bytes = static_cast<size_t>(max_depth + 1) * kCap * sizeof(FrontierRec);
   DLIOM_TRY(ctx->cand.reserve(up + pool_bytes));
   char* d = static_cast<char*>(ctx->cand.p);
-  char* h = static_cast<char*>(ctx->pinned);
-  int* out = reinterpret_cast<int*>(h + kUpload);
-  const int out_records = static_cast<int>((ctx->pinned_bytes - kUpload - 8192 - (kMaxLevels + 2) * 4) / sizeof(FrontierRec));
+  char* h = pinned_at<char>(ctx, kPinFrontierUpload);
+  int* out = pinned_at<int>(ctx, kPinFrontierOut);
+  const int out_records = static_cast<int>((kPinFrontierOut.bytes - (kMaxLevels + 2) * 4) / sizeof(FrontierRec));
   FrontierArgs a = frontier_args(s, min_score);
   a.pool = reinterpret_cast<FrontierRec*>(d + up);
   a.counts = reinterpret_cast<int*>(d + frontier_counts_at(1));
@@ -882,14 +882,13 @@ int run_search(Search& s, const dliom_cloud& hi_cloud, float min_score, dliom_fa
     const float v[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
     std::memcpy(&poses[7 * i], v, sizeof(v));
   }
-  // through the pinned block when they fit (its first 208 KB belong to device_frontier's upload): no synchronisation
-  // here, the stream orders the kernels behind the copy
-  constexpr size_t kPosesAt = 208 * 1024, kPosesMax = 48 * 1024;
-  const bool poses_pinned = poses.size() * 4 <= kPosesMax && ctx->pinned_bytes >= (1u << 20);
+  // through the pinned block when they fit: no synchronisation here, the stream orders the kernels behind the copy
+  const bool poses_pinned = poses.size() * 4 <= kPinPoses.bytes;
   const float* poses_src = poses.data();
   if (poses_pinned) {
-    std::memcpy(static_cast<char*>(ctx->pinned) + kPosesAt, poses.data(), poses.size() * 4);
-    poses_src = reinterpret_cast<const float*>(static_cast<char*>(ctx->pinned) + kPosesAt);
+    float* staged = pinned_at<float>(ctx, kPinPoses);
+    std::memcpy(staged, poses.data(), poses.size() * 4);
+    poses_src = staged;
   }
   DLIOM_HIP_TRY(hipMemcpyAsync(d_poses, poses_src, poses.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(discretize_kernel, dim3((s.n_hi + 255) / 256, num_scans), dim3(256), 0, ctx->stream, hi_cloud.d_x,

@@ -1306,7 +1306,7 @@ int dliom_inserter_insert_cloud_multi(const dliom_inserter* ins, int num_targets
   DLIOM_TRY(ctx->misc.reserve(256));
   a.status = ctx->misc.as<int>();
   DLIOM_HIP_TRY(hipMemsetAsync(a.status, 0, 8 * kMaxInsertTargets, ctx->stream));
-  a.host_status = static_cast<int*>(ctx->pinned);  // device-visible; written by pass 1 only
+  a.host_status = pinned_at<int>(ctx, kPinReadback);  // device-visible; written by pass 1 only
   // The host needs pass 0's verdict, not the end of the update passes: everything that follows on this context is
   // ordered behind them by the stream.  Pass 1 ends its copy of the verdict with a completion word; the call returns
   // when that arrives (the update passes may still be running -- 50 us the caller's next step no longer waits for).

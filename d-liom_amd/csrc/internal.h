@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/dliom.h"
+#include "pinned_layout.h"
 
 namespace dliom {
 
@@ -115,8 +116,7 @@ struct dliom_ctx {
   int last_score_mapping = -1;     // 3 box, 2 dense mirror, 1 / 0 leaf table kernels
   int last_box_refusal = 0;        // DLIOM_BOX_* of the last score volume (dliom_rtcsm_stats.box_kernel_status)
   int last_box_variant = -1;       // which instantiation of the box kernel ran last (dliom_rtcsm_stats.box_kernel_variant)
-  void* pinned = nullptr;   // small pinned host staging block
-  size_t pinned_bytes = 0;
+  void* pinned = nullptr;   // page-locked staging block of kPinnedBytes: regions and ownership in pinned_layout.h
   unsigned* done_word = nullptr;  // pinned, own allocation: completion word of the main stream's read-back kernels
   unsigned done_seq = 0;
   int64_t voxel_unpacked_reruns = 0;  // voxel filter launches repeated with 21-bit keys (dliom_ctx_voxel_filter_reruns)
@@ -138,9 +138,9 @@ struct dliom_ctx {
   hipStream_t aux_stream = nullptr;
   hipEvent_t aux_fork = nullptr;
   dliom::DevBuf aux_scratch;
-  void* aux_pinned = nullptr;  // 4 KB
+  void* aux_pinned = nullptr;  // kAuxPinnedBytes (pinned_layout.h)
   int aux_histogram_size = 0;  // > 0: a histogram is pending on aux_stream
-  unsigned aux_seq = 0;        // its completion word is the one at aux_pinned + 4032
+  unsigned aux_seq = 0;        // its completion word is kAuxDoneWord
   bool aux_enqueued = false;   // false: the pending histogram is the empty cloud's (nothing on the stream)
   const dliom_cloud* aux_cloud = nullptr;  // the pending histogram's input, should _finish have to run it again
   float aux_rotation[4] = {1.f, 0.f, 0.f, 0.f};

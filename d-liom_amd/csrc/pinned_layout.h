@@ -1,0 +1,99 @@
+// Layout of a context's page-locked, device-visible staging block (dliom_ctx::pinned, kPinnedBytes, allocated with the
+// context) and of the histogram's auxiliary block (dliom_ctx::aux_pinned, kAuxPinnedBytes, made on first use).
+//
+// Ownership: the block belongs to the entry point that is running.  Every entry point that writes it waits for the
+// device before it returns, so the next call finds it free.  Within one call, regions that are live at the same time do
+// not overlap: each such group is checked by a static_assert at the end of this file.
+//
+// Regions that overlap only across time:
+//  * the small read-backs at offset 0 (kPinReadback, kPinCsmSums), kPinLmResult and kPinHistogram are each waited for
+//    and copied out by the call that issued them, before that call stages anything else;
+//  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
+//    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
+//    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
+//    discrete scans' pose upload (kPinPoses) is not waited for when the search skips the frontier; the list that
+//    device_sums writes there (16 bytes a candidate from offset 0) reaches into it only beyond 13 312 candidates.
+#ifndef DLIOM_CSRC_PINNED_LAYOUT_H_
+#define DLIOM_CSRC_PINNED_LAYOUT_H_
+
+#include <cstddef>
+#include <initializer_list>
+
+namespace dliom {
+
+constexpr size_t kPinnedBytes = size_t{1} << 20;
+
+struct PinRegion {
+  size_t at, bytes;
+};
+
+// small read-backs (counts, flags, maxima) of gather_and_wait and the like; the largest, the de-skew stage's, is
+// 3 + 976 words
+constexpr PinRegion kPinReadback{0, 4096};
+// Ceres evaluation (csm3d.hip evaluate): the 28 double sums of one evaluation
+constexpr PinRegion kPinCsmSums{0, 1024};
+// Ceres in one launch (csm3d.hip): LmKernelOut
+constexpr PinRegion kPinLmResult{1024, 1024};
+// dliom_cloud_rotational_histogram on the main stream: histogram_size (<= 255) floats and two flag words
+constexpr PinRegion kPinHistogram{2048, 2048};
+// dliom_cloud_download[_transformed]: packed xyz, in pieces of kPinDownload.bytes / 12 points
+constexpr PinRegion kPinDownload{0, kPinnedBytes - 8192};
+
+// an RTCSM match (rtcsm3d.hip)
+constexpr PinRegion kPinRtcsmCandidates{0, kPinnedBytes - 81920};  // candidate tables (pageable above this)
+constexpr PinRegion kPinBoxTables{kPinnedBytes - 81920, 65536};    // the LDS-box kernel's tables (pageable above this)
+constexpr PinRegion kPinSequentialSums{kPinnedBytes - 8192, 4096};  // sequential_probability_sums: up to 1024 floats
+constexpr PinRegion kPinMatchReadback{kPinnedBytes - 4096, 2048};  // [count pair | list | sums | box overflow word]
+constexpr PinRegion kPinBoxErrorWord{kPinnedBytes - 2048, 4};      // a shard's box overflow word
+constexpr PinRegion kPinRcclWord{kPinnedBytes - 1024, 8};          // the RCCL exchange's 64-bit word
+
+// a single fast-CSM search (fast_csm3d.hip); it also reads kPinSequentialSums back
+constexpr PinRegion kPinFastCsmScores{0, kPinnedBytes - 8192};        // device_sums: candidate list, then its sums
+constexpr PinRegion kPinFrontierUpload{0, 208 * 1024};                // device_frontier's upload
+constexpr PinRegion kPinPoses{208 * 1024, 48 * 1024};                 // the discrete scans' poses (pageable above this)
+constexpr PinRegion kPinFrontierOut{256 * 1024, kPinnedBytes - 256 * 1024 - 8192};  // device_frontier's output
+
+// the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
+constexpr size_t kAuxPinnedBytes = 4096;
+constexpr PinRegion kAuxHistogram{0, 4032};
+constexpr PinRegion kAuxDoneWord{4032, 4};
+
+// A region's first byte as a T*, in the context's block or in its auxiliary block (Ctx: dliom_ctx).
+template <class T = void, class Ctx>
+inline T* pinned_at(Ctx* ctx, PinRegion r) {
+  return static_cast<T*>(static_cast<void*>(static_cast<char*>(ctx->pinned) + r.at));
+}
+template <class T = void, class Ctx>
+inline T* aux_pinned_at(Ctx* ctx, PinRegion r) {
+  return static_cast<T*>(static_cast<void*>(static_cast<char*>(ctx->aux_pinned) + r.at));
+}
+
+constexpr bool pins_inside(std::initializer_list<PinRegion> rs, size_t block) {
+  for (const PinRegion& r : rs)
+    if (r.at > block || r.bytes > block - r.at) return false;
+  return true;
+}
+constexpr bool pins_disjoint(std::initializer_list<PinRegion> rs) {
+  for (const PinRegion* a = rs.begin(); a != rs.end(); ++a)
+    for (const PinRegion* b = rs.begin(); b != a; ++b)
+      if (a->at < b->at + b->bytes && b->at < a->at + a->bytes) return false;
+  return true;
+}
+
+static_assert(pins_inside({kPinReadback, kPinCsmSums, kPinLmResult, kPinHistogram, kPinDownload, kPinRtcsmCandidates,
+                           kPinBoxTables, kPinSequentialSums, kPinMatchReadback, kPinBoxErrorWord, kPinRcclWord,
+                           kPinFastCsmScores, kPinFrontierUpload, kPinPoses, kPinFrontierOut},
+                          kPinnedBytes) &&
+                  pins_inside({kAuxHistogram, kAuxDoneWord}, kAuxPinnedBytes),
+              "every region lies inside its block");
+static_assert(pins_disjoint({kPinRtcsmCandidates, kPinBoxTables, kPinSequentialSums, kPinMatchReadback, kPinBoxErrorWord,
+                             kPinRcclWord}),
+              "an RTCSM match's regions");
+static_assert(pins_disjoint({kPinFrontierUpload, kPinPoses, kPinFrontierOut, kPinSequentialSums}),
+              "a single fast-CSM search's regions");
+static_assert(pins_disjoint({kPinCsmSums, kPinLmResult}), "Ceres' regions");
+static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
+
+}  // namespace dliom
+
+#endif  // DLIOM_CSRC_PINNED_LAYOUT_H_

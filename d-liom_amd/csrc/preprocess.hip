@@ -549,7 +549,7 @@ static int add_range_data_stage_a(dliom_ctx* ctx, const double prev_pose[7], con
                          d + 2 * nn, 1, kind, d_flags, 0, d_hits);
       DLIOM_HIP_TRY(hipGetLastError());
       DLIOM_TRY(compact_equal_arrays_enqueue(ctx, Soa{d, d + nn, d + 2 * nn, nullptr, n}, kind, 1, e, e + nn, e + 2 * nn, d_hits, &d_returns));
-      unsigned* host = static_cast<unsigned*>(ctx->pinned);
+      unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
       const GatherJob jobs[4] = {{d_hits, 1}, {d_unpackable, 1}, {d_returns, 1}, {d_flags, static_cast<unsigned>(kDeskewFlagWords)}};
       DLIOM_TRY(gather_and_wait(ctx, jobs, 4, host));
       if (host[1] == 0u) {
@@ -622,7 +622,7 @@ static int add_range_data_stage_b(dliom_ctx* ctx, const float* rx, const float* 
   origin_in_tracking[1] = o.y;
   origin_in_tracking[2] = o.z;
   const int threads = 256;
-  float* host = static_cast<float*>(ctx->pinned);
+  float* host = pinned_at<float>(ctx, kPinReadback);
   float max_norm = 0.f, abs_max[3] = {0.f, 0.f, 0.f};
   int64_t n3 = -1;
   // Round 5: ONE read-back for the stage.  The filter is only enqueued (its survivor count stays on the device), the

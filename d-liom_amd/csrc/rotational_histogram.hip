@@ -1547,8 +1547,7 @@ extern "C" int dliom_cloud_rotational_histogram(dliom_ctx* ctx, const dliom_clou
     return DLIOM_OK;
   }
   if (cloud->n > (int64_t{1} << 26)) return DLIOM_ERR_CAPACITY;
-  void* h = static_cast<char*>(ctx->pinned) + 2048;
-  return run_histogram(ctx, ctx->stream, ctx->misc, h, ctx->done_word, &ctx->done_seq, cloud, rotation_wxyz, histogram_size, histogram);
+  return run_histogram(ctx, ctx->stream, ctx->misc, pinned_at(ctx, kPinHistogram), ctx->done_word, &ctx->done_seq, cloud, rotation_wxyz, histogram_size, histogram);
 }
 
 // Test hook: the (bucket, value) pairs the histogram is summed from, in the order of the additions (slice order, then the
@@ -1601,20 +1600,20 @@ extern "C" int dliom_cloud_rotational_histogram_begin(dliom_ctx* ctx, const dlio
     void* pin = nullptr;
     const bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess &&
-                    hipHostMalloc(&pin, 4096, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
+                    hipHostMalloc(&pin, kAuxPinnedBytes, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
     if (!ok) {
       if (pin != nullptr) (void)hipHostFree(pin);
       if (ev != nullptr) (void)hipEventDestroy(ev);
       if (st != nullptr) (void)hipStreamDestroy(st);
       return DLIOM_ERR_HIP;
     }
-    std::memset(pin, 0, 4096);
+    std::memset(pin, 0, kAuxPinnedBytes);
     ctx->aux_stream = st;
     ctx->aux_fork = ev;
     ctx->aux_pinned = pin;
   }
   if (cloud->n == 0) {
-    std::memset(ctx->aux_pinned, 0, 4032);
+    std::memset(aux_pinned_at(ctx, kAuxHistogram), 0, kAuxHistogram.bytes);
     ctx->aux_histogram_size = histogram_size;
     ctx->aux_enqueued = false;
     return DLIOM_OK;
@@ -1623,8 +1622,8 @@ extern "C" int dliom_cloud_rotational_histogram_begin(dliom_ctx* ctx, const dlio
   DLIOM_HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
   ctx->aux_seq = ++ctx->aux_seq == 0u ? 1u : ctx->aux_seq;
   ctx->hist_enqueued_at = std::chrono::steady_clock::now();
-  DLIOM_TRY(enqueue_histogram(ctx, ctx->aux_stream, ctx->aux_scratch, ctx->aux_pinned, cloud, rotation_wxyz, histogram_size,
-                              ctx->hist_expect_big, reinterpret_cast<unsigned*>(static_cast<char*>(ctx->aux_pinned) + 4032), ctx->aux_seq));
+  DLIOM_TRY(enqueue_histogram(ctx, ctx->aux_stream, ctx->aux_scratch, aux_pinned_at(ctx, kAuxHistogram), cloud, rotation_wxyz,
+                              histogram_size, ctx->hist_expect_big, aux_pinned_at<unsigned>(ctx, kAuxDoneWord), ctx->aux_seq));
   ctx->aux_histogram_size = histogram_size;
   ctx->aux_enqueued = true;
   ctx->aux_cloud = cloud;
@@ -1638,13 +1637,14 @@ extern "C" int dliom_cloud_rotational_histogram_finish(dliom_ctx* ctx, float* hi
   const int size = ctx->aux_histogram_size;
   ctx->aux_histogram_size = 0;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  unsigned* word = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->aux_pinned) + 4032);
+  void* h = aux_pinned_at(ctx, kAuxHistogram);
+  unsigned* word = aux_pinned_at<unsigned>(ctx, kAuxDoneWord);
   if (ctx->aux_enqueued) DLIOM_TRY(wait_histogram(ctx, ctx->aux_stream, word, ctx->aux_seq));
   bool had_big = false;
-  const int status = read_histogram(ctx->aux_pinned, size, histogram, &had_big);
+  const int status = read_histogram(h, size, histogram, &had_big);
   if (ctx->aux_enqueued) ctx->hist_expect_big = had_big;
   if (status != kRetryWithBigPath) return status;
   ctx->hist_expect_big = true;  // the first cloud with a floor after clouds without one: once more, with the big path
-  return run_histogram(ctx, ctx->aux_stream, ctx->aux_scratch, ctx->aux_pinned, word, &ctx->aux_seq, ctx->aux_cloud,
+  return run_histogram(ctx, ctx->aux_stream, ctx->aux_scratch, h, word, &ctx->aux_seq, ctx->aux_cloud,
                        ctx->aux_has_rotation ? ctx->aux_rotation : nullptr, size, histogram);
 }

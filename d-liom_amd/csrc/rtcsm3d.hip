@@ -1241,14 +1241,14 @@ static int upload_candidates(dliom_ctx* ctx, const Candidates& c, DeviceCandidat
   }
   char* base = static_cast<char*>(ctx->cand.p);
   d->rot_src = reinterpret_cast<const float4*>(base);
-  if (total + 81920 <= ctx->pinned_bytes) {  // the last 80 KB stage the box-kernel tables and the readbacks
-    // Pinned staging: truly asynchronous.  Every entry point that gets here synchronises the
-    // stream before it returns, so the block is free again at the next call.
-    std::memcpy(ctx->pinned, host.data(), total);
-    if (prep_add(prep, base, ctx->pinned, total, 0u))
-      d->rot_src = static_cast<const float4*>(ctx->pinned);
+  if (total <= kPinRtcsmCandidates.bytes) {  // (the match's other regions: pinned_layout.h)
+    // Pinned staging: truly asynchronous.
+    void* staged = pinned_at(ctx, kPinRtcsmCandidates);
+    std::memcpy(staged, host.data(), total);
+    if (prep_add(prep, base, staged, total, 0u))
+      d->rot_src = static_cast<const float4*>(staged);
     else
-      DLIOM_HIP_TRY(hipMemcpyAsync(base, ctx->pinned, total, hipMemcpyHostToDevice, ctx->stream));
+      DLIOM_HIP_TRY(hipMemcpyAsync(base, staged, total, hipMemcpyHostToDevice, ctx->stream));
   } else {
     DLIOM_HIP_TRY(hipMemcpyAsync(base, host.data(), total, hipMemcpyHostToDevice, ctx->stream));
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `host` dies at scope exit
@@ -1478,8 +1478,8 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   char* base = static_cast<char*>(ctx->box_tables.p);
   const Group* group_src = reinterpret_cast<const Group*>(base + tau_bytes + pass_only_bytes);  // for the pre-pass (below)
   // small (a few KB): staged through the pinned block when it fits, else a synchronous copy
-  if (tau_bytes + pass_bytes <= 65536 && ctx->pinned_bytes >= 81920) {
-    char* h = static_cast<char*>(ctx->pinned) + ctx->pinned_bytes - 81920;
+  if (tau_bytes + pass_bytes <= kPinBoxTables.bytes) {
+    char* h = pinned_at<char>(ctx, kPinBoxTables);
     std::memcpy(h, tau.data(), tau.size() * 4);
     std::memcpy(h + tau_bytes, pass.data(), pass.size() * sizeof(Pass));
     std::memcpy(h + tau_bytes + pass_only_bytes, groups.data(), groups.size() * sizeof(Group));
@@ -1999,7 +1999,7 @@ static int match_begin(dliom_ctx* ctx, const dliom_rtcsm_options* o, const doubl
     DLIOM_HIP_TRY(hipGetLastError());
   }
   if (local_best_lo_bits != nullptr) {
-    unsigned* h_err = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->pinned) + ctx->pinned_bytes - 4096 + 2048);
+    unsigned* h_err = pinned_at<unsigned>(ctx, kPinBoxErrorWord);
     *h_err = 0u;
     DLIOM_HIP_TRY(hipMemcpyAsync(local_best_lo_bits, st->d_ctrs, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (st->used_box)
@@ -2052,8 +2052,9 @@ static int match_finish(dliom_ctx* ctx, const unsigned* global_best_lo_bits, uin
   std::vector<unsigned> list;
   std::vector<float> ksums;
   if (st->r_last > st->r_first) {
-    // readback block at the end of the pinned staging area: [count pair | list | sums]
-    unsigned* h_ctrs = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->pinned) + ctx->pinned_bytes - 4096);
+    // readback block: [count pair | list | sums | box overflow word]
+    static_assert((2 + 2 * kSpecK + 1) * 4 <= kPinMatchReadback.bytes, "the read-back fits its region");
+    unsigned* h_ctrs = pinned_at<unsigned>(ctx, kPinMatchReadback);
     unsigned* h_list = h_ctrs + 2;
     float* h_sums = reinterpret_cast<float*>(h_ctrs + 2 + kSpecK);
     auto rescore = [&](unsigned count, const unsigned* d_count, size_t list_offset) -> int {
@@ -2216,7 +2217,8 @@ int sequential_probability_sums(dliom_ctx* ctx, const dliom_cloud& cloud, const 
                                    static_cast<unsigned>(k), &ctx->misc, d_ksums));
   if (K <= 1024) {  // a few sums (the loop-closure matcher asks for one at a time): packed by a kernel, polled
     const GatherJob job{d_ksums, static_cast<unsigned>(K)};
-    float* h = reinterpret_cast<float*>(static_cast<char*>(ctx->pinned) + ctx->pinned_bytes - 8192);
+    static_assert(1024 * 4 <= kPinSequentialSums.bytes, "the sums fit their region");
+    float* h = pinned_at<float>(ctx, kPinSequentialSums);
     DLIOM_TRY(gather_and_wait(ctx, &job, 1, h));  // also keeps `host` alive long enough: the upload is in front of it
     std::memcpy(sums, h, K * 4);
     return DLIOM_OK;
@@ -2373,7 +2375,7 @@ int rccl_exchange(uint64_t* value, void* user) {
   dliom_ctx* ctx = x->ctx;
   if (ctx->misc.reserve(256) != DLIOM_OK) return 1;
   uint64_t* d = ctx->misc.as<uint64_t>();
-  uint64_t* h = reinterpret_cast<uint64_t*>(static_cast<char*>(ctx->pinned) + ctx->pinned_bytes - 4096 + 3072);
+  uint64_t* h = pinned_at<uint64_t>(ctx, kPinRcclWord);
   *h = *value;
   const int span = ctx->begin_span(DLIOM_KERNEL_ALLREDUCE);  // (profiling on: HIP events around the collective)
   bool ok = hipMemcpyAsync(d, h, 8, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&

@@ -330,7 +330,7 @@ static int run_insert(dliom_ctx* ctx, const Soa& in, const std::vector<float>& s
     lengths.max_range[k] = ranges[k];
   }
   const unsigned n = static_cast<unsigned>(in.n);
-  unsigned* host = static_cast<unsigned*>(ctx->pinned);
+  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
   // packed words first (one atomic per voxel); a point outside their 13 bits per axis: once more with the 21-bit keys
   for (int packed = in.n <= (int64_t{1} << kPackedIndexBits) ? 1 : 0; packed >= 0; --packed) {
     t->packed = packed;
@@ -462,8 +462,9 @@ int compact_equal_arrays(dliom_ctx* ctx, const Soa& in, const unsigned char* kin
   if (in.n == 0) {
     if (also_src != nullptr && also_words > 0) {
       const GatherJob job{also_src, also_words};
-      DLIOM_TRY(gather_and_wait(ctx, &job, 1, ctx->pinned));
-      std::memcpy(also_dst, ctx->pinned, static_cast<size_t>(also_words) * 4);
+      void* host = pinned_at(ctx, kPinReadback);
+      DLIOM_TRY(gather_and_wait(ctx, &job, 1, host));
+      std::memcpy(also_dst, host, static_cast<size_t>(also_words) * 4);
     }
     return DLIOM_OK;
   }
@@ -478,7 +479,7 @@ int compact_equal_arrays(dliom_ctx* ctx, const Soa& in, const unsigned char* kin
                      static_cast<const float*>(nullptr), n, s.flags, s.block_counts, ox, oy, oz,
                      static_cast<float*>(nullptr), static_cast<unsigned*>(nullptr), static_cast<unsigned*>(nullptr), s.max_sq);
   DLIOM_HIP_TRY(hipGetLastError());
-  unsigned* host = static_cast<unsigned*>(ctx->pinned);
+  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
   const GatherJob jobs[2] = {{s.max_sq, 1}, {also_src, also_words}};
   DLIOM_TRY(gather_and_wait(ctx, jobs, also_src != nullptr && also_words > 0 ? 2 : 1, host));
   *n_out = host[0];
@@ -504,7 +505,7 @@ int compact_equal_arrays_enqueue(dliom_ctx* ctx, const Soa& in, const unsigned c
 }
 
 int read_max_norm(dliom_ctx* ctx, const unsigned* d_max_sq, float* max_norm) {
-  unsigned* host = static_cast<unsigned*>(ctx->pinned);
+  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
   const GatherJob job{d_max_sq, 1};
   DLIOM_TRY(gather_and_wait(ctx, &job, 1, host));
   float sq;
@@ -723,7 +724,7 @@ int adaptive_voxel_filter_clouds(dliom_ctx* ctx, const dliom_cloud& in, const dl
   }
   float max_sq[kMaxFilters] = {0.f, 0.f};
   if (any) {
-    unsigned* host = static_cast<unsigned*>(ctx->pinned);
+    unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
     int st = DLIOM_OK;
     const GatherJob job{s.max_sq, static_cast<unsigned>(num_filters)};
     st = gather_and_wait(ctx, &job, 1, host);
@@ -814,7 +815,7 @@ static int download_packed(const dliom_cloud* cloud, const float* pose7, float* 
   if (n == 0) return DLIOM_OK;
   dliom_ctx* ctx = cloud->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  const size_t room = (ctx->pinned_bytes - 8192) / 12;  // (the block's last 4 KB hold other calls' words)
+  const size_t room = kPinDownload.bytes / 12;  // points a piece (pinned_layout.h)
   DownloadPose dp;
   dp.apply = pose7 != nullptr ? 1 : 0;
   if (pose7 != nullptr) {
@@ -826,7 +827,7 @@ static int download_packed(const dliom_cloud* cloud, const float* pose7, float* 
     dp.q = Quat4{1.f, 0.f, 0.f, 0.f};
     dp.t[0] = dp.t[1] = dp.t[2] = 0.f;
   }
-  float* staged = static_cast<float*>(ctx->pinned);
+  float* staged = pinned_at<float>(ctx, kPinDownload);
   for (size_t first = 0; first < n; first += room) {
     const size_t m = std::min(room, n - first);
     hipLaunchKernelGGL(download_packed_kernel, dim3(static_cast<unsigned>((m + 255) / 256)), dim3(256), 0, ctx->stream, cloud->d_x + first,

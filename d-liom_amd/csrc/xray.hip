@@ -334,7 +334,7 @@ int run_xray(const dliom_grid* g, const XrayTransform& T, bool texture, uint8_t*
   DLIOM_HIP_TRY(hipGetLastError());
   DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(b1 + off_tmp, scan_bytes, counts, incl, static_cast<int>(S), st));
   const GatherJob back[2] = {{incl + (S - 1), 1}, {box, 4}};
-  int* host = static_cast<int*>(ctx->pinned);
+  int* host = pinned_at<int>(ctx, kPinReadback);
   DLIOM_TRY(gather_and_wait(ctx, back, 2, host));
   const int64_t n = static_cast<uint32_t>(host[0]);
   if (n == 0) return DLIOM_OK;  // nothing at or above 0.501: 0 x 0 (the reference's box would overflow)
