@@ -12,6 +12,9 @@
 //   dliom::mapping::ActiveSubmaps3D / Submap3D                mapping/3d/submap_3d.h:43-130
 //   dliom::mapping::RangeDataSynchronizer                     mapping/internal/3d/range_data_synchronizer.h
 //   dliom::mapping::LocalTrajectoryBuilder3D                  mapping/internal/3d/local_trajectory_builder_3d.h:83-111
+//   dliom::io::PointsBatch / PointsProcessor                  io/points_batch.h:36-73, io/points_processor.h:29-52
+//   dliom::io::MinMaxRangeFiteringPointsProcessor             io/min_max_range_filtering_points_processor.h:30-53
+//   dliom::io::OutlierRemovingPointsProcessor                 io/outlier_removing_points_processor.h:29-82
 //
 // The value types below are layout-compatible stand-ins for Eigen::Vector3f / transform::Rigid3d
 // so that this header builds without Eigen; inside cartographer the same adapters are
@@ -1236,6 +1239,154 @@ class LocalTrajectoryBuilder3D {
 };
 
 }  // namespace mapping
+
+// The points-processor pipeline's stages with compute in them (cartographer/io), on the device.  A batch's points go to
+// the device once per stage and phase; intensities and colors stay on the host and are filtered with the survivors'
+// indices, as RemovePoints does (io/points_batch.cc:22-49).
+namespace io {
+
+using FloatColor = std::array<float, 3>;  // io/color.h:30
+
+struct PointsBatch {  // io/points_batch.h:36-73: the fields the stages here touch
+  sensor::Vector3f origin{0.f, 0.f, 0.f};
+  std::vector<sensor::Vector3f> points;  // in the map frame
+  std::vector<float> intensities;        // optional
+  std::vector<FloatColor> colors;        // optional
+};
+
+class PointsProcessor {  // io/points_processor.h:29-52
+ public:
+  enum class FlushResult { kRestartStream, kFinished };
+  PointsProcessor() {}
+  virtual ~PointsProcessor() {}
+  PointsProcessor(const PointsProcessor&) = delete;
+  PointsProcessor& operator=(const PointsProcessor&) = delete;
+  virtual void Process(std::unique_ptr<PointsBatch> points_batch) = 0;
+  virtual FlushResult Flush() = 0;
+};
+
+namespace internal {
+struct DeviceCloud {
+  DeviceCloud(Context* context, const std::vector<sensor::Vector3f>& points) {
+    Check(dliom_cloud_create(context->get(), points.empty() ? nullptr : &points[0].x, static_cast<int64_t>(points.size()), &cloud),
+          "dliom_cloud_create");
+  }
+  ~DeviceCloud() { dliom_cloud_destroy(cloud); }
+  DeviceCloud(const DeviceCloud&) = delete;
+  DeviceCloud& operator=(const DeviceCloud&) = delete;
+  dliom_cloud* cloud = nullptr;
+};
+// RemovePoints with the complement: the batch keeps the points of `kept` (a device cloud of kept_index.size() points)
+inline void KeepPoints(dliom_cloud* kept, const std::vector<int32_t>& kept_index, PointsBatch* batch) {
+  std::vector<sensor::Vector3f> points(kept_index.size());
+  if (!points.empty()) Check(dliom_cloud_download(kept, &points[0].x), "dliom_cloud_download");
+  std::vector<float> intensities;
+  std::vector<FloatColor> colors;
+  if (!batch->intensities.empty())
+    for (const int32_t i : kept_index) intensities.push_back(batch->intensities[i]);
+  if (!batch->colors.empty())
+    for (const int32_t i : kept_index) colors.push_back(batch->colors[i]);
+  batch->points = std::move(points);
+  batch->intensities = std::move(intensities);
+  batch->colors = std::move(colors);
+}
+}  // namespace internal
+
+// io/min_max_range_filtering_points_processor.{h,cc}
+class MinMaxRangeFiteringPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "min_max_range_filter";
+  MinMaxRangeFiteringPointsProcessor(double min_range, double max_range, PointsProcessor* next, Context* context = nullptr)
+      : min_range_(min_range), max_range_(max_range), next_(next), context_(context != nullptr ? context : Context::ForThisThread()) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {
+    internal::DeviceCloud in(context_, batch->points);
+    std::vector<int32_t> kept_index(batch->points.size());
+    dliom_cloud* kept = nullptr;
+    int64_t num_kept = 0;
+    const float origin[3] = {batch->origin.x, batch->origin.y, batch->origin.z};
+    Check(dliom_cloud_min_max_range_filter(context_->get(), in.cloud, origin, min_range_, max_range_, &kept, kept_index.data(),
+                                           static_cast<int64_t>(kept_index.size()), &num_kept),
+          "dliom_cloud_min_max_range_filter");
+    kept_index.resize(static_cast<size_t>(num_kept));
+    internal::KeepPoints(kept, kept_index, batch.get());
+    dliom_cloud_destroy(kept);
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override { return next_->Flush(); }
+
+ private:
+  const double min_range_, max_range_;
+  PointsProcessor* const next_;
+  Context* const context_;
+};
+
+// io/outlier_removing_points_processor.{h,cc}: "voxel_filter_and_remove_moving_objects"
+class OutlierRemovingPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "voxel_filter_and_remove_moving_objects";
+  OutlierRemovingPointsProcessor(double voxel_size, PointsProcessor* next, Context* context = nullptr)
+      : next_(next), context_(context != nullptr ? context : Context::ForThisThread()) {
+    Check(dliom_outlier_remover_create(context_->get(), voxel_size, &remover_), "dliom_outlier_remover_create");
+  }
+  ~OutlierRemovingPointsProcessor() override { dliom_outlier_remover_destroy(remover_); }
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:45-61
+    internal::DeviceCloud in(context_, batch->points);
+    const float origin[3] = {batch->origin.x, batch->origin.y, batch->origin.z};
+    switch (state_) {
+      case State::kPhase1:
+        Check(dliom_outlier_remover_mark_hits(remover_, in.cloud), "dliom_outlier_remover_mark_hits");
+        break;
+      case State::kPhase2:
+        Check(dliom_outlier_remover_count_rays(remover_, origin, in.cloud), "dliom_outlier_remover_count_rays");
+        break;
+      case State::kPhase3: {
+        std::vector<int32_t> kept_index(batch->points.size());
+        dliom_cloud* kept = nullptr;
+        int64_t num_kept = 0;
+        Check(dliom_outlier_remover_filter(remover_, in.cloud, &kept, kept_index.data(), static_cast<int64_t>(kept_index.size()),
+                                           &num_kept),
+              "dliom_outlier_remover_filter");
+        kept_index.resize(static_cast<size_t>(num_kept));
+        internal::KeepPoints(kept, kept_index, batch.get());
+        dliom_cloud_destroy(kept);
+        next_->Process(std::move(batch));
+        break;
+      }
+    }
+  }
+
+  FlushResult Flush() override {  // .cc:63-82
+    switch (state_) {
+      case State::kPhase1:
+        state_ = State::kPhase2;
+        return FlushResult::kRestartStream;
+      case State::kPhase2:
+        state_ = State::kPhase3;
+        return FlushResult::kRestartStream;
+      case State::kPhase3:
+        if (next_->Flush() != FlushResult::kFinished) {
+          std::fprintf(stderr, "Check failed: Voxel filtering and outlier removal must be configured to occur after any "
+                               "stages that require multiple passes.\n");
+          std::abort();
+        }
+        return FlushResult::kFinished;
+    }
+    std::abort();
+  }
+
+  const dliom_outlier_remover* remover() const { return remover_; }
+
+ private:
+  enum class State { kPhase1, kPhase2, kPhase3 };
+  PointsProcessor* const next_;
+  Context* const context_;
+  State state_ = State::kPhase1;
+  dliom_outlier_remover* remover_ = nullptr;
+};
+
+}  // namespace io
 }  // namespace dliom
 
 #endif  // DLIOM_CPP_DLIOM_CARTOGRAPHER_H_

@@ -785,6 +785,7 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
   ctx->batch.release();
   ctx->xray_leaves.release();
   ctx->xray_cells.release();
+  ctx->outlier.release();
   if (ctx->batch_pinned != nullptr) (void)hipHostFree(ctx->batch_pinned);
   ctx->aux_scratch.release();
   if (ctx->aux_pinned != nullptr) (void)hipHostFree(ctx->aux_pinned);
@@ -824,10 +825,11 @@ int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out) {
   out->mirror_bytes = l.mirror_bytes;
   out->mirror_budget_bytes = l.mirror_budget;
   out->mirrors_refused = l.mirrors_refused;
+  out->outlier_table_bytes = l.outlier_table_bytes;
   const dliom::DevBuf* bufs[] = {&ctx->points, &ctx->cand, &ctx->sums, &ctx->bounds, &ctx->rescore, &ctx->partials, &ctx->misc,
                                  &ctx->sort_tmp, &ctx->voxel, &ctx->box_tables, &ctx->box_counters, &ctx->box_extents,
                                  &ctx->csm_arrivals, &ctx->box_error, &ctx->deskew_flags, &ctx->zero_words, &ctx->aux_scratch,
-                                 &ctx->xray_leaves, &ctx->xray_cells};
+                                 &ctx->xray_leaves, &ctx->xray_cells, &ctx->outlier};
   for (const dliom::DevBuf* b : bufs) out->scratch_bytes += static_cast<int64_t>(b->cap);
   return DLIOM_OK;
 }

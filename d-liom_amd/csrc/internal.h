@@ -78,6 +78,7 @@ struct GridView {
 struct MemoryLedger {
   int64_t grids = 0, leaf_table_bytes = 0, leaf_pool_bytes = 0, mirror_bytes = 0;
   int64_t mirror_budget = 0;   // 0: no cap.  A mirror that would take mirror_bytes above it is not built: the correlative
+  int64_t outlier_table_bytes = 0;  // the voxel tables of the context's outlier removers (outlier.hip)
   int64_t mirrors_refused = 0; // matcher then runs its leaf-table kernel on that grid (same results, slower)
 };
 
@@ -128,6 +129,8 @@ struct dliom_ctx {
   dliom::DevBuf batch;
   // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
   dliom::DevBuf xray_leaves, xray_cells;
+  // the export stages (outlier.hip): keep flags, their scan and the survivors' indices; the voxel list of a table dump
+  dliom::DevBuf outlier;
   void* batch_pinned = nullptr;
   size_t batch_pinned_bytes = 0;
   int reserve_batch_pinned(size_t bytes);  // grow-only, contents not preserved; synchronises the stream on growth

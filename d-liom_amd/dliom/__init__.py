@@ -188,7 +188,15 @@ class MatchResult(C.Structure):
 class MemoryStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("grids", "leaf_table_bytes", "leaf_pool_bytes", "mirror_bytes", "mirror_budget_bytes",
                                          "mirrors_refused", "scratch_bytes", "leaf_capacity", "leaf_slots_upper_bound")] + [
-                                             ("mirror_windowed", C.c_int)]
+                                             ("mirror_windowed", C.c_int), ("outlier_table_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class OutlierStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("voxels", "leaves", "leaf_capacity", "table_capacity", "table_bytes", "growths",
+                                         "samples_walked", "probes")] + [("phase", C.c_int)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -253,6 +261,15 @@ SYMBOLS = [
                                                          C.POINTER(AdaptiveVoxelFilterOptions), C.POINTER(_vp), C.POINTER(_vp)]),
     ("dliom_cloud_download", C.c_int, [_vp, _f32p]),
     ("dliom_cloud_download_transformed", C.c_int, [_vp, _f32p, _f32p]),
+    ("dliom_outlier_remover_create", C.c_int, [_vp, C.c_double, C.POINTER(_vp)]),
+    ("dliom_outlier_remover_destroy", C.c_int, [_vp]),
+    ("dliom_outlier_remover_mark_hits", C.c_int, [_vp, _vp]),
+    ("dliom_outlier_remover_count_rays", C.c_int, [_vp, _f32p, _vp]),
+    ("dliom_outlier_remover_filter", C.c_int, [_vp, _vp, C.POINTER(_vp), _i32p, C.c_int64, _i64p]),
+    ("dliom_outlier_remover_voxels", C.c_int, [_vp, _i32p, _i32p, _i32p, C.c_int64, _i64p]),
+    ("dliom_outlier_remover_stats", C.c_int, [_vp, C.POINTER(OutlierStats)]),
+    ("dliom_cloud_min_max_range_filter", C.c_int, [_vp, _vp, _f32p, C.c_double, C.c_double, C.POINTER(_vp), _i32p, C.c_int64,
+                                                   _i64p]),
     ("dliom_rtcsm3d_match", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _f32p, C.c_int64, _vp, _f64p, _f32p]),
     ("dliom_rtcsm3d_match_cloud", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _vp, _vp, _f64p, _f32p]),
     ("dliom_rtcsm3d_shard_begin", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _vp, _vp, C.c_int, C.c_int,
@@ -570,6 +587,15 @@ class PointCloud:
                                                               C.byref(hb)), "dliom_cloud_adaptive_voxel_filter_pair")
         return PointCloud(self.ctx, _handle=ha), PointCloud(self.ctx, _handle=hb)
 
+    def min_max_range_filter(self, origin, min_range, max_range):
+        """io::MinMaxRangeFiteringPointsProcessor on the device -> (PointCloud, int32 input indices of the survivors)."""
+        h, kept = _vp(), C.c_int64()
+        index = np.zeros(max(self.n, 1), dtype=np.int32)
+        _check(self._L.dliom_cloud_min_max_range_filter(self.ctx.h, self.h, _p(_f32(origin), _f32p), float(min_range),
+                                                        float(max_range), C.byref(h), _p(index, _i32p), self.n,
+                                                        C.byref(kept)), "dliom_cloud_min_max_range_filter")
+        return PointCloud(self.ctx, _handle=h), index[:kept.value].copy()
+
     def download(self, pose7=None):
         """The points, packed xyz; pose7 (float [t, q]): sensor::TransformPointCloud(cloud, pose) applied on the device."""
         out = np.zeros((self.n, 3), dtype=np.float32)
@@ -583,6 +609,60 @@ class PointCloud:
     def close(self):
         if getattr(self, "h", None):
             self._L.dliom_cloud_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OutlierRemover:
+    """io::OutlierRemovingPointsProcessor's voxel table on the device (dliom_outlier_remover): mark_hits over every
+    batch, then count_rays over every batch, then filter every batch."""
+
+    def __init__(self, ctx, voxel_size):
+        self._L = ctx._L
+        self.ctx = ctx
+        h = _vp()
+        _check(self._L.dliom_outlier_remover_create(ctx.h, float(voxel_size), C.byref(h)), "dliom_outlier_remover_create")
+        self.h = h
+
+    def mark_hits(self, cloud):
+        _check(self._L.dliom_outlier_remover_mark_hits(self.h, cloud.h), "dliom_outlier_remover_mark_hits")
+
+    def count_rays(self, origin, cloud):
+        _check(self._L.dliom_outlier_remover_count_rays(self.h, _p(_f32(origin), _f32p), cloud.h),
+               "dliom_outlier_remover_count_rays")
+
+    def filter(self, cloud):
+        """-> (PointCloud of the points kept, int32 input indices of them)."""
+        h, kept = _vp(), C.c_int64()
+        index = np.zeros(max(cloud.n, 1), dtype=np.int32)
+        _check(self._L.dliom_outlier_remover_filter(self.h, cloud.h, C.byref(h), _p(index, _i32p), cloud.n, C.byref(kept)),
+               "dliom_outlier_remover_filter")
+        return PointCloud(self.ctx, _handle=h), index[:kept.value].copy()
+
+    def voxels(self):
+        """Every voxel with hits > 0, sorted by (z, y, x) -> (xyz int32 (n, 3), hits int32, rays int32)."""
+        n = C.c_int64()
+        _check(self._L.dliom_outlier_remover_voxels(self.h, None, None, None, 0, C.byref(n)), "dliom_outlier_remover_voxels")
+        xyz = np.zeros((n.value, 3), dtype=np.int32)
+        hits, rays = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        if n.value > 0:
+            _check(self._L.dliom_outlier_remover_voxels(self.h, _p(xyz, _i32p), _p(hits, _i32p), _p(rays, _i32p), n.value,
+                                                        C.byref(n)), "dliom_outlier_remover_voxels")
+        return xyz, hits, rays
+
+    def stats(self):
+        s = OutlierStats()
+        _check(self._L.dliom_outlier_remover_stats(self.h, C.byref(s)), "dliom_outlier_remover_stats")
+        return s.as_dict()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_outlier_remover_destroy(self.h)
             self.h = None
 
     def __del__(self):

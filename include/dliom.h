@@ -104,6 +104,7 @@ typedef struct dliom_memory_stats {
   int64_t leaf_capacity;           /* grid only: slots of the pool */
   int64_t leaf_slots_upper_bound;  /* grid only: >= slots in use (exact after dliom_grid_num_blocks) */
   int mirror_windowed;             /* grid only */
+  int64_t outlier_table_bytes;     /* context only: the voxel tables of its dliom_outlier_remover objects */
 } dliom_memory_stats;
 int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out);
 int dliom_ctx_set_mirror_budget(dliom_ctx* ctx, int64_t bytes);
@@ -508,6 +509,67 @@ int dliom_cloud_download(const dliom_cloud* cloud, float* points_xyz);
  * filtered_range_data_in_local = TransformRangeData(filtered_range_data_in_tracking, opt_pose.cast<float>())
  * (local_trajectory_builder_3d.cc:556-559) without a host loop over the returns. */
 int dliom_cloud_download_transformed(const dliom_cloud* cloud, const float pose[7], float* points_xyz);
+
+/* ---- Point-cloud export: the points-processor stages with compute in them (cartographer/io) ----
+ * io::OutlierRemovingPointsProcessor (io/outlier_removing_points_processor.{h,cc}, the pipeline action
+ * "voxel_filter_and_remove_moving_objects") streams every batch of a trajectory three times over a
+ * HybridGridBase<VoxelData {int hits; int rays;}> (.h:55-58, 81): mark hits, count the rays through voxels that have
+ * hits, drop the points of voxels with rays >= 3 * hits.  A dliom_outlier_remover is that grid as a sparse voxel table
+ * in HBM; every count equals the reference's (integers only: no result depends on the order of the device's atomics).
+ * Clouds hold map-frame points, like io::PointsBatch::points; the caller supplies the batch origin.
+ *
+ * Where the reference aborts, hangs or is undefined, a call returns an error and leaves the table as it was:
+ *   DLIOM_ERR_GRID_EXTENT       mark_hits: a hit whose cell index leaves [-8192, 8191] on an axis (Grow()'s
+ *                               CHECK_LE(new_bits, 8), hybrid_grid.h:389)
+ *   DLIOM_ERR_INVALID_ARGUMENT  a non-finite coordinate or origin (lround of it is undefined); a call out of phase order
+ *   DLIOM_ERR_RAY_TOO_LONG      count_rays: a ray of voxel_size * 2^24 or more (`x += voxel_size_` stops advancing in
+ *                               float and the reference's loop does not end, .cc:98)
+ * A pass-2 sample or a pass-3 point outside the extent reads ValueType() as in the reference (value(),
+ * hybrid_grid.h:266-271): nothing is counted, and pass 3 removes the point (!(0 < 0)).
+ * Phases are one-way like the reference's State (.h:59-63): mark_hits after the first successful count_rays, or
+ * count_rays after the first successful filter, is refused.
+ * NULL pointers, a voxel_size that is not finite and positive (as double and as float) and a negative capacity are
+ * refused with DLIOM_ERR_INVALID_ARGUMENT before anything touches a device.
+ * Every call runs on the context's stream and has finished with its inputs when it returns: mark_hits and count_rays
+ * read back only their error flag (mark_hits with it the number of leaves, which sizes the pool), filter the survivor
+ * count.  The table grows between launches, never inside a kernel. */
+typedef struct dliom_outlier_remover dliom_outlier_remover;
+typedef struct dliom_outlier_stats {
+  int64_t voxels;          /* voxels with hits > 0 */
+  int64_t leaves;          /* 8x8x8 blocks of voxels in use (4 KiB each) */
+  int64_t leaf_capacity, table_capacity; /* allocated leaves; entries of the leaf hash table */
+  int64_t table_bytes;     /* HBM held: hash table, leaf pool, counters */
+  int64_t growths;         /* reallocations of the hash table or the pool since creation */
+  int64_t samples_walked;  /* pass-2 samples so far (iterations of the loop at .cc:98) */
+  int64_t probes;          /* hash-table entries read by pass 2 so far */
+  int phase;               /* 1, 2, 3 */
+} dliom_outlier_stats;
+/* OutlierRemovingPointsProcessor(voxel_size, next) (.cc:36-43): the grid's resolution is float(voxel_size), the ray step
+ * stays double. */
+int dliom_outlier_remover_create(dliom_ctx* ctx, double voxel_size, dliom_outlier_remover** out);
+int dliom_outlier_remover_destroy(dliom_outlier_remover* remover);
+/* ProcessInPhaseOne (.cc:84-90): ++hits in the voxel of every point. */
+int dliom_outlier_remover_mark_hits(dliom_outlier_remover* remover, const dliom_cloud* points);
+/* ProcessInPhaseTwo (.cc:92-108): for every point, for (float x = 0; x < length; x += voxel_size), ++rays in the voxel
+ * of origin + (x / length) * delta if it has hits.  Two samples of a ray in one voxel count twice. */
+int dliom_outlier_remover_count_rays(dliom_outlier_remover* remover, const float origin[3], const dliom_cloud* points);
+/* ProcessInPhaseThree (.cc:110-124) with RemovePoints (points_batch.cc:22-49): *kept = the points whose voxel has
+ * rays < 3 * hits, in input order (a new cloud, the caller destroys it); kept_index (may be NULL; capacity entries)
+ * receives their input indices, for the caller's intensities and colors.  *num_kept is always filled; a kept_index
+ * too small for it returns DLIOM_ERR_CAPACITY and no cloud. */
+int dliom_outlier_remover_filter(dliom_outlier_remover* remover, const dliom_cloud* points, dliom_cloud** kept,
+                                 int32_t* kept_index, int64_t capacity, int64_t* num_kept);
+/* The table (the reference's voxels_, .h:81): every voxel with hits > 0, sorted by (z, y, x); xyz 3 * capacity ints,
+ * hits and rays capacity ints.  All three NULL: *count only.  Too small a capacity: *count and DLIOM_ERR_CAPACITY. */
+int dliom_outlier_remover_voxels(const dliom_outlier_remover* remover, int32_t* xyz, int32_t* hits, int32_t* rays,
+                                 int64_t capacity, int64_t* count);
+int dliom_outlier_remover_stats(const dliom_outlier_remover* remover, dliom_outlier_stats* out);
+/* MinMaxRangeFiteringPointsProcessor::Process (io/min_max_range_filtering_points_processor.cc:40-51): keeps the points
+ * with min_range <= range && range <= max_range, range = (p - origin).norm() in float, the bounds in double; order kept.
+ * kept_index, capacity, num_kept as in dliom_outlier_remover_filter.  NaN bounds are refused. */
+int dliom_cloud_min_max_range_filter(dliom_ctx* ctx, const dliom_cloud* in, const float origin[3], double min_range,
+                                     double max_range, dliom_cloud** out, int32_t* kept_index, int64_t capacity,
+                                     int64_t* num_kept);
 /* The same filters on host buffers (the reference's own placement): out_xyz has room for n points;
  * *num_out receives the survivors (first point per voxel). */
 int dliom_voxel_filter(float size, const float* points_xyz, int64_t n, float* out_xyz, int64_t* num_out);
