@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <set>
@@ -1247,11 +1248,17 @@ namespace io {
 
 using FloatColor = std::array<float, 3>;  // io/color.h:30
 
+namespace internal {
+struct DeviceCloud;
+}
 struct PointsBatch {  // io/points_batch.h:36-73: the fields the stages here touch
   sensor::Vector3f origin{0.f, 0.f, 0.f};
   std::vector<sensor::Vector3f> points;  // in the map frame
   std::vector<float> intensities;        // optional
   std::vector<FloatColor> colors;        // optional
+  // Not in the reference: `points` as a stage left them on the device (the range filter and the outlier remover set it),
+  // so that the next device stage does not upload them again.  Whoever changes `points` resets it (KeepPoints does).
+  std::shared_ptr<internal::DeviceCloud> device_points;
 };
 
 class PointsProcessor {  // io/points_processor.h:29-52
@@ -1267,13 +1274,15 @@ class PointsProcessor {  // io/points_processor.h:29-52
 
 namespace internal {
 struct DeviceCloud {
-  DeviceCloud(Context* context, const std::vector<sensor::Vector3f>& points) {
+  DeviceCloud(Context* context, const std::vector<sensor::Vector3f>& points) : context(context) {
     Check(dliom_cloud_create(context->get(), points.empty() ? nullptr : &points[0].x, static_cast<int64_t>(points.size()), &cloud),
           "dliom_cloud_create");
   }
+  DeviceCloud(Context* context, dliom_cloud* owned) : context(context), cloud(owned) {}  // takes a cloud a filter made
   ~DeviceCloud() { dliom_cloud_destroy(cloud); }
   DeviceCloud(const DeviceCloud&) = delete;
   DeviceCloud& operator=(const DeviceCloud&) = delete;
+  Context* const context;  // the context the cloud lives on
   dliom_cloud* cloud = nullptr;
 };
 // RemovePoints with the complement: the batch keeps the points of `kept` (a device cloud of kept_index.size() points)
@@ -1289,6 +1298,17 @@ inline void KeepPoints(dliom_cloud* kept, const std::vector<int32_t>& kept_index
   batch->points = std::move(points);
   batch->intensities = std::move(intensities);
   batch->colors = std::move(colors);
+  batch->device_points.reset();
+}
+// The batch's points on the device: what the stage before left there -- on this context, and of the batch's size --, else
+// one upload.  (A stage that rewrites `points` in place without changing their number must reset device_points itself.)
+inline std::shared_ptr<DeviceCloud> PointsOnDevice(Context* context, const PointsBatch& batch) {
+  int64_t n = -1;
+  if (batch.device_points != nullptr && batch.device_points->context == context &&
+      dliom_cloud_size(batch.device_points->cloud, &n) == DLIOM_OK &&
+      n == static_cast<int64_t>(batch.points.size()))
+    return batch.device_points;
+  return std::make_shared<DeviceCloud>(context, batch.points);
 }
 }  // namespace internal
 
@@ -1310,7 +1330,7 @@ class MinMaxRangeFiteringPointsProcessor : public PointsProcessor {
           "dliom_cloud_min_max_range_filter");
     kept_index.resize(static_cast<size_t>(num_kept));
     internal::KeepPoints(kept, kept_index, batch.get());
-    dliom_cloud_destroy(kept);
+    batch->device_points = std::make_shared<internal::DeviceCloud>(context_, kept);  // the next device stage reads them there
     next_->Process(std::move(batch));
   }
   FlushResult Flush() override { return next_->Flush(); }
@@ -1350,7 +1370,7 @@ class OutlierRemovingPointsProcessor : public PointsProcessor {
               "dliom_outlier_remover_filter");
         kept_index.resize(static_cast<size_t>(num_kept));
         internal::KeepPoints(kept, kept_index, batch.get());
-        dliom_cloud_destroy(kept);
+        batch->device_points = std::make_shared<internal::DeviceCloud>(context_, kept);
         next_->Process(std::move(batch));
         break;
       }
@@ -1384,6 +1404,167 @@ class OutlierRemovingPointsProcessor : public PointsProcessor {
   Context* const context_;
   State state_ = State::kPhase1;
   dliom_outlier_remover* remover_ = nullptr;
+};
+
+// io/file_writer.h:31-50, the part the map writers use
+class FileWriter {
+ public:
+  FileWriter() {}
+  virtual ~FileWriter() {}
+  FileWriter(const FileWriter&) = delete;
+  FileWriter& operator=(const FileWriter&) = delete;
+  virtual bool Write(const char* data, size_t len) = 0;
+  virtual bool Close() = 0;
+  virtual std::string GetFilename() = 0;
+};
+using FileWriterFactory = std::function<std::unique_ptr<FileWriter>(const std::string& filename)>;
+
+struct ProbabilityGridRangeDataInserterOptions2D {  // proto/2d/probability_grid_range_data_inserter_options_2d.proto
+  double hit_probability = 0.55;
+  double miss_probability = 0.49;
+  bool insert_free_space = true;
+};
+
+namespace internal {
+// What both map stages hold: CreateProbabilityGrid(resolution) (io/probability_grid_points_processor.cc:150-158) and a
+// ProbabilityGridRangeDataInserter2D, on the device.
+class ProbabilityGridOnDevice {
+ public:
+  ProbabilityGridOnDevice(double resolution, const ProbabilityGridRangeDataInserterOptions2D& options, Context* context)
+      : context_(context) {
+    Check(dliom_probability_grid_create(context_->get(), resolution, 0, &grid_), "dliom_probability_grid_create");
+    Check(dliom_inserter2d_create(context_->get(), options.hit_probability, options.miss_probability,
+                                  options.insert_free_space ? 1 : 0, &inserter_),
+          "dliom_inserter2d_create");
+  }
+  ~ProbabilityGridOnDevice() {
+    dliom_inserter2d_destroy(inserter_);
+    dliom_probability_grid_destroy(grid_);
+  }
+  ProbabilityGridOnDevice(const ProbabilityGridOnDevice&) = delete;
+  ProbabilityGridOnDevice& operator=(const ProbabilityGridOnDevice&) = delete;
+
+  // range_data_inserter_.Insert({batch->origin, batch->points, {}}, &probability_grid_)
+  void Insert(const PointsBatch& batch) {
+    const std::shared_ptr<DeviceCloud> points = PointsOnDevice(context_, batch);
+    const float origin[3] = {batch.origin.x, batch.origin.y, batch.origin.z};
+    Check(dliom_inserter2d_insert_cloud(inserter_, grid_, origin, points->cloud), "dliom_inserter2d_insert_cloud");
+  }
+  // DrawProbabilityGrid (:127-148), rotated by Image::Rotate90DegreesClockwise if asked: the gray bytes, row-major
+  std::vector<uint8_t> Draw(bool rotate_cw, int32_t offset[2], int32_t size[2]) const {
+    Check(dliom_probability_grid_draw(grid_, nullptr, 0, offset, size, rotate_cw ? 1 : 0), "dliom_probability_grid_draw");
+    std::vector<uint8_t> gray(static_cast<size_t>(size[0]) * static_cast<size_t>(size[1]));
+    Check(dliom_probability_grid_draw(grid_, gray.data(), static_cast<int64_t>(gray.size()), offset, size, rotate_cw ? 1 : 0),
+          "dliom_probability_grid_draw");
+    return gray;
+  }
+  const dliom_probability_grid* grid() const { return grid_; }
+
+ private:
+  Context* const context_;
+  dliom_probability_grid* grid_ = nullptr;
+  dliom_inserter2d* inserter_ = nullptr;
+};
+
+inline PointsProcessor::FlushResult FlushLastStage(PointsProcessor* next, const char* message) {
+  switch (next->Flush()) {
+    case PointsProcessor::FlushResult::kRestartStream:
+      std::fprintf(stderr, "Check failed: %s\n", message);  // LOG(FATAL)
+      std::abort();
+    case PointsProcessor::FlushResult::kFinished:
+      return PointsProcessor::FlushResult::kFinished;
+  }
+  std::abort();
+}
+}  // namespace internal
+
+// io/probability_grid_points_processor.{h,cc}: "write_probability_grid".  Flush hands the gray image of
+// DrawProbabilityGrid to `sink` (row-major, one byte a pixel, with its width, height and the offset of its first pixel in
+// the grid); PNG encoding and cairo's trajectory drawing stay with the caller (DrawTrajectories::kNo).
+class ProbabilityGridPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "write_probability_grid";
+  using ImageSink = std::function<void(const std::vector<uint8_t>& gray, int width, int height, const int32_t offset[2])>;
+  ProbabilityGridPointsProcessor(double resolution, const ProbabilityGridRangeDataInserterOptions2D& options, ImageSink sink,
+                                 PointsProcessor* next, Context* context = nullptr)
+      : sink_(std::move(sink)), next_(next), grid_(resolution, options, context != nullptr ? context : Context::ForThisThread()) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:92-97
+    grid_.Insert(*batch);
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override {  // .cc:99-125
+    int32_t offset[2], size[2];
+    const std::vector<uint8_t> gray = grid_.Draw(false, offset, size);
+    sink_(gray, size[0], size[1], offset);
+    return internal::FlushLastStage(next_, "ProbabilityGrid generation must be configured to occur after any stages that "
+                                           "require multiple passes.");
+  }
+  const dliom_probability_grid* grid() const { return grid_.grid(); }
+
+ private:
+  ImageSink sink_;
+  PointsProcessor* const next_;
+  internal::ProbabilityGridOnDevice grid_;
+};
+
+// cartographer_ros/ros_map_writing_points_processor.{h,cc} with ros_map.cc: "write_ros_map"
+class RosMapWritingPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "write_ros_map";
+  RosMapWritingPointsProcessor(double resolution, const ProbabilityGridRangeDataInserterOptions2D& options,
+                               FileWriterFactory file_writer_factory, const std::string& filestem, PointsProcessor* next,
+                               Context* context = nullptr)
+      : filestem_(filestem),
+        next_(next),
+        file_writer_factory_(std::move(file_writer_factory)),
+        grid_(resolution, options, context != nullptr ? context : Context::ForThisThread()) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:52-57
+    grid_.Insert(*batch);
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override {  // .cc:59-94
+    int32_t offset[2], size[2];
+    const std::vector<uint8_t> gray = grid_.Draw(true, offset, size);  // image->Rotate90DegreesClockwise()
+    double resolution, max_xy[2];
+    int32_t num_cells[2];
+    Check(dliom_probability_grid_limits(grid_.grid(), &resolution, max_xy, num_cells), "dliom_probability_grid_limits");
+    std::unique_ptr<FileWriter> pgm_writer = file_writer_factory_(filestem_ + ".pgm");
+    const std::string pgm_filename = pgm_writer->GetFilename();
+    Write(pgm_writer.get(), [&](char* buffer, int64_t capacity, int64_t* length) {  // WritePgm (ros_map.cc:21-34)
+      return dliom_ros_map_pgm_header(resolution, size[0], size[1], buffer, capacity, length);
+    });
+    if (!pgm_writer->Write(reinterpret_cast<const char*>(gray.data()), gray.size()) || !pgm_writer->Close()) Fail("pgm");
+    double origin[2];
+    Check(dliom_ros_map_yaml_origin(resolution, max_xy, offset, size[0], size[1], origin), "dliom_ros_map_yaml_origin");
+    std::unique_ptr<FileWriter> yaml_writer = file_writer_factory_(filestem_ + ".yaml");
+    Write(yaml_writer.get(), [&](char* buffer, int64_t capacity, int64_t* length) {  // WriteYaml (ros_map.cc:36-47)
+      return dliom_ros_map_yaml(resolution, origin, pgm_filename.c_str(), buffer, capacity, length);
+    });
+    if (!yaml_writer->Close()) Fail("yaml");
+    return internal::FlushLastStage(next_, "ROS map writing must be configured to occur after any stages that require "
+                                           "multiple passes.");
+  }
+  const dliom_probability_grid* grid() const { return grid_.grid(); }
+
+ private:
+  static void Fail(const char* what) {
+    std::fprintf(stderr, "Check failed: writing the %s file\n", what);  // CHECK(writer->Close())
+    std::abort();
+  }
+  template <typename Text>
+  static void Write(FileWriter* writer, Text text) {
+    int64_t length = 0;
+    text(nullptr, 0, &length);  // the size
+    std::string buffer(static_cast<size_t>(length), '\0');
+    Check(text(&buffer[0], length, &length), "ros map text");
+    if (!writer->Write(buffer.data(), buffer.size())) Fail("map");
+  }
+  const std::string filestem_;
+  PointsProcessor* const next_;
+  FileWriterFactory file_writer_factory_;
+  internal::ProbabilityGridOnDevice grid_;
 };
 
 }  // namespace io

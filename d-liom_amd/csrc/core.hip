@@ -692,6 +692,7 @@ const char* dliom_status_string(int status) {
     case DLIOM_ERR_EMPTY_CLOUD: return "empty point cloud";
     case DLIOM_ERR_CAPACITY: return "output buffer too small";
     case DLIOM_ERR_SOLVER: return "solver failure";
+    case DLIOM_ERR_INTERNAL: return "a device consistency word is set (2D ray casting)";
     case DLIOM_ERR_DIVERGED: return "IMU window diverged (velocity or bias beyond the FailureDetection limits)";
     case DLIOM_ERR_PEER_FAILED: return "sharded match: another rank failed before the exchange";
     default: return "unknown status";
@@ -826,6 +827,7 @@ int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out) {
   out->mirror_budget_bytes = l.mirror_budget;
   out->mirrors_refused = l.mirrors_refused;
   out->outlier_table_bytes = l.outlier_table_bytes;
+  out->probability_grid_bytes = l.probability_grid_bytes;
   const dliom::DevBuf* bufs[] = {&ctx->points, &ctx->cand, &ctx->sums, &ctx->bounds, &ctx->rescore, &ctx->partials, &ctx->misc,
                                  &ctx->sort_tmp, &ctx->voxel, &ctx->box_tables, &ctx->box_counters, &ctx->box_extents,
                                  &ctx->csm_arrivals, &ctx->box_error, &ctx->deskew_flags, &ctx->zero_words, &ctx->aux_scratch,

@@ -188,7 +188,8 @@ class MatchResult(C.Structure):
 class MemoryStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("grids", "leaf_table_bytes", "leaf_pool_bytes", "mirror_bytes", "mirror_budget_bytes",
                                          "mirrors_refused", "scratch_bytes", "leaf_capacity", "leaf_slots_upper_bound")] + [
-                                             ("mirror_windowed", C.c_int), ("outlier_table_bytes", C.c_int64)]
+                                             ("mirror_windowed", C.c_int), ("outlier_table_bytes", C.c_int64),
+                                             ("probability_grid_bytes", C.c_int64)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -200,6 +201,11 @@ class OutlierStats(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class ProbabilityGridStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("bytes", "growths", "inserts", "cells_visited")] + [("known_box", C.c_int32 * 4),
+                                                                                             ("error_word", C.c_int32)]
 
 
 class InsertionResult(C.Structure):
@@ -368,6 +374,28 @@ SYMBOLS = [
                                                 C.c_int64, C.c_int, _f32p]),
     ("dliom_csm3d_evaluate", C.c_int, [_vp, C.POINTER(CsmOptions), _f64p, _f64p, _f64p, C.c_int, C.POINTER(_f32p),
                                        _i64p, C.POINTER(_vp), _f64p, _f64p, _f64p]),
+    ("dliom_probability_grid_create", C.c_int, [_vp, C.c_double, C.c_int64, C.POINTER(_vp)]),
+    ("dliom_probability_grid_create_with_limits", C.c_int, [_vp, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                                            C.c_int64, C.POINTER(_vp)]),
+    ("dliom_probability_grid_destroy", C.c_int, [_vp]),
+    ("dliom_probability_grid_limits", C.c_int, [_vp, _f64p, _f64p, _i32p]),
+    ("dliom_probability_grid_memory_stats", C.c_int, [_vp, C.POINTER(MemoryStats)]),
+    ("dliom_probability_grid_get_stats", C.c_int, [_vp, C.POINTER(ProbabilityGridStats)]),
+    ("dliom_probability_grid_grow_limits", C.c_int, [C.c_double, _f64p, _i32p, C.c_float, C.c_float, C.c_int64, _i32p,
+                                                     C.POINTER(C.c_int32)]),
+    ("dliom_compute_lookup_table_to_apply_correspondence_cost_odds", C.c_int, [C.c_float, _u16p]),
+    ("dliom_inserter2d_create", C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(_vp)]),
+    ("dliom_inserter2d_destroy", C.c_int, [_vp]),
+    ("dliom_inserter2d_tables", C.c_int, [_vp, _u16p, _u16p]),
+    ("dliom_inserter2d_insert_cloud", C.c_int, [_vp, _vp, _f32p, _vp]),
+    ("dliom_inserter2d_insert", C.c_int, [_vp, _vp, _f32p, _f32p, C.c_int64]),
+    ("dliom_probability_grid_cells", C.c_int, [_vp, _u16p, C.c_int64, _i32p, _i32p, C.c_int]),
+    ("dliom_probability_grid_get_probabilities", C.c_int, [_vp, _i32p, C.c_int64, _f32p, C.POINTER(C.c_uint8)]),
+    ("dliom_probability_grid_draw", C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_int64, _i32p, _i32p, C.c_int]),
+    ("dliom_probability_grid_color_table", C.c_int, [C.POINTER(C.c_uint8)]),
+    ("dliom_ros_map_yaml_origin", C.c_int, [C.c_double, _f64p, _i32p, C.c_int32, C.c_int32, _f64p]),
+    ("dliom_ros_map_pgm_header", C.c_int, [C.c_double, C.c_int32, C.c_int32, C.c_char_p, C.c_int64, _i64p]),
+    ("dliom_ros_map_yaml", C.c_int, [C.c_double, _f64p, C.c_char_p, C.c_char_p, C.c_int64, _i64p]),
     ("dliom_ctx_set_tuning", C.c_int, [_vp, C.c_int, C.c_int]),
     ("dliom_ctx_poll_fallbacks", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("dliom_ctx_read_backs", C.c_int, [_vp, C.POINTER(C.c_int64)]),
@@ -663,6 +691,174 @@ class OutlierRemover:
     def close(self):
         if getattr(self, "h", None):
             self._L.dliom_outlier_remover_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+KERNEL_PG_HITS, KERNEL_PG_RAYS, KERNEL_PG_CLEAR = 6, 7, 8
+ERR_INTERNAL = -13
+_u8p = C.POINTER(C.c_uint8)
+
+
+def lookup_table_to_apply_correspondence_cost_odds(odds):
+    """mapping/probability_values.cc:85-101"""
+    out = np.zeros(32768, dtype=np.uint16)
+    _check(load_library().dliom_compute_lookup_table_to_apply_correspondence_cost_odds(C.c_float(odds), _p(out, _u16p)),
+           "correspondence cost lookup table")
+    return out
+
+
+def probability_grid_color_table():
+    """The gray value of every cell value: 128 unknown, else ProbabilityToColor (probability_grid_points_processor.cc:49-54)."""
+    out = np.zeros(32768, dtype=np.uint8)
+    _check(load_library().dliom_probability_grid_color_table(_p(out, _u8p)), "color table")
+    return out
+
+
+def probability_grid_grow_limits(resolution, max_xy, num_cells, point_xy, budget_bytes=0):
+    """Grid2D::GrowLimits on the limits alone -> (max_xy, num_cells, offset of the old cell (0, 0), doublings)."""
+    mx, nc, off, turns = _f64(max_xy).copy(), np.array(num_cells, dtype=np.int32), np.zeros(2, dtype=np.int32), C.c_int32()
+    _check(load_library().dliom_probability_grid_grow_limits(float(resolution), _p(mx, _f64p), _p(nc, _i32p), C.c_float(point_xy[0]),
+                                                            C.c_float(point_xy[1]), int(budget_bytes), _p(off, _i32p),
+                                                            C.byref(turns)), "dliom_probability_grid_grow_limits")
+    return mx, nc, off, turns.value
+
+
+def ros_map_yaml_origin(resolution, max_xy, offset, width, height):
+    """ros_map_writing_points_processor.cc:73-76; width / height of the rotated image."""
+    out = np.zeros(2)
+    _check(load_library().dliom_ros_map_yaml_origin(float(resolution), _p(_f64(max_xy), _f64p),
+                                                   _p(np.ascontiguousarray(offset, dtype=np.int32), _i32p), int(width), int(height),
+                                                   _p(out, _f64p)), "dliom_ros_map_yaml_origin")
+    return out
+
+
+def _text(call):
+    buf, n = C.create_string_buffer(1024), C.c_int64()
+    _check(call(buf, 1024, C.byref(n)), "ros map text")
+    return buf.raw[:n.value]
+
+
+def ros_map_pgm_header(resolution, width, height):
+    """WritePgm's header (ros_map.cc:23-26) -> bytes."""
+    return _text(lambda b, c, n: load_library().dliom_ros_map_pgm_header(float(resolution), int(width), int(height), b, c, n))
+
+
+def ros_map_yaml(resolution, origin, pgm_filename):
+    """WriteYaml's text (ros_map.cc:41-45) -> bytes."""
+    o = _f64(origin)
+    return _text(lambda b, c, n: load_library().dliom_ros_map_yaml(float(resolution), _p(o, _f64p), pgm_filename.encode(), b, c, n))
+
+
+class ProbabilityGrid2D:
+    """mapping::ProbabilityGrid of the export pipeline in HBM (dliom_probability_grid).  limits=None:
+    io::CreateProbabilityGrid(resolution); else (max_x, max_y, num_x_cells, num_y_cells)."""
+
+    def __init__(self, ctx, resolution, limits=None, budget_bytes=0):
+        self._L = ctx._L
+        self.ctx = ctx
+        h = _vp()
+        if limits is None:
+            _check(self._L.dliom_probability_grid_create(ctx.h, float(resolution), int(budget_bytes), C.byref(h)),
+                   "dliom_probability_grid_create")
+        else:
+            _check(self._L.dliom_probability_grid_create_with_limits(ctx.h, float(resolution), float(limits[0]), float(limits[1]),
+                                                                     int(limits[2]), int(limits[3]), int(budget_bytes),
+                                                                     C.byref(h)), "dliom_probability_grid_create_with_limits")
+        self.h = h
+
+    def limits(self):
+        """-> (resolution, (max_x, max_y), (num_x_cells, num_y_cells))"""
+        r, mx, nc = C.c_double(), np.zeros(2), np.zeros(2, dtype=np.int32)
+        _check(self._L.dliom_probability_grid_limits(self.h, C.byref(r), _p(mx, _f64p), _p(nc, _i32p)), "dliom_probability_grid_limits")
+        return r.value, (float(mx[0]), float(mx[1])), (int(nc[0]), int(nc[1]))
+
+    def cells(self, cropped=False):
+        """-> (uint16 [num_y, num_x], offset (x, y)): the whole grid, or ComputeCroppedLimits' box."""
+        off, num = np.zeros(2, dtype=np.int32), np.zeros(2, dtype=np.int32)
+        _check(self._L.dliom_probability_grid_cells(self.h, None, 0, _p(off, _i32p), _p(num, _i32p), int(cropped)),
+               "dliom_probability_grid_cells")
+        out = np.zeros((int(num[1]), int(num[0])), dtype=np.uint16)
+        _check(self._L.dliom_probability_grid_cells(self.h, _p(out, _u16p), out.size, _p(off, _i32p), _p(num, _i32p), int(cropped)),
+               "dliom_probability_grid_cells")
+        return out, (int(off[0]), int(off[1]))
+
+    def get_probabilities(self, cell_xy):
+        """GetProbability / IsKnown of cells (x, y) -> (float32, bool)."""
+        xy = np.ascontiguousarray(cell_xy, dtype=np.int32).reshape(-1, 2)
+        p, k = np.zeros(len(xy), dtype=np.float32), np.zeros(len(xy), dtype=np.uint8)
+        _check(self._L.dliom_probability_grid_get_probabilities(self.h, _p(xy, _i32p), len(xy), _p(p, _f32p), _p(k, _u8p)),
+               "dliom_probability_grid_get_probabilities")
+        return p, k.astype(bool)
+
+    def draw(self, rotate_cw=False):
+        """DrawProbabilityGrid -> (uint8 [height, width], offset (x, y)); a fresh grid draws one unknown pixel."""
+        off, size = np.zeros(2, dtype=np.int32), np.zeros(2, dtype=np.int32)
+        _check(self._L.dliom_probability_grid_draw(self.h, None, 0, _p(off, _i32p), _p(size, _i32p), int(rotate_cw)),
+               "dliom_probability_grid_draw")
+        out = np.zeros((int(size[1]), int(size[0])), dtype=np.uint8)
+        _check(self._L.dliom_probability_grid_draw(self.h, _p(out, _u8p), out.size, _p(off, _i32p), _p(size, _i32p), int(rotate_cw)),
+               "dliom_probability_grid_draw")
+        return out, (int(off[0]), int(off[1]))
+
+    def stats(self):
+        s = ProbabilityGridStats()
+        _check(self._L.dliom_probability_grid_get_stats(self.h, C.byref(s)), "dliom_probability_grid_get_stats")
+        d = {n: int(getattr(s, n)) for n in ("bytes", "growths", "inserts", "cells_visited", "error_word")}
+        d["known_box"] = tuple(int(v) for v in s.known_box)
+        return d
+
+    def memory_stats(self):
+        m = MemoryStats()
+        _check(self._L.dliom_probability_grid_memory_stats(self.h, C.byref(m)), "dliom_probability_grid_memory_stats")
+        return m.as_dict()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_probability_grid_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Inserter2D:
+    """mapping::ProbabilityGridRangeDataInserter2D (dliom_inserter2d): insert(grid, origin, points) is one Insert with the
+    points as returns and no misses, as the export pipeline calls it."""
+
+    def __init__(self, ctx, hit_probability, miss_probability, insert_free_space=True):
+        self._L = ctx._L
+        self.ctx = ctx
+        h = _vp()
+        _check(self._L.dliom_inserter2d_create(ctx.h, float(hit_probability), float(miss_probability), int(insert_free_space),
+                                               C.byref(h)), "dliom_inserter2d_create")
+        self.h = h
+
+    def tables(self):
+        hit, miss = np.zeros(32768, dtype=np.uint16), np.zeros(32768, dtype=np.uint16)
+        _check(self._L.dliom_inserter2d_tables(self.h, _p(hit, _u16p), _p(miss, _u16p)), "dliom_inserter2d_tables")
+        return hit, miss
+
+    def insert(self, grid, origin, points):
+        """points: a PointCloud on the device, or an array (n, 3)."""
+        o = _f32(origin)
+        if isinstance(points, PointCloud):
+            _check(self._L.dliom_inserter2d_insert_cloud(self.h, grid.h, _p(o, _f32p), points.h), "dliom_inserter2d_insert_cloud")
+        else:
+            pts = _f32(points).reshape(-1, 3)
+            _check(self._L.dliom_inserter2d_insert(self.h, grid.h, _p(o, _f32p), _p(pts, _f32p), len(pts)), "dliom_inserter2d_insert")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_inserter2d_destroy(self.h)
             self.h = None
 
     def __del__(self):

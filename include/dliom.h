@@ -44,6 +44,7 @@ extern "C" {
 #define DLIOM_ERR_EMPTY_CLOUD (-8)      /* division by size()==0 in ScoreCandidate / sqrt(N) scaling */
 #define DLIOM_ERR_CAPACITY (-9)         /* caller-provided output buffer too small */
 #define DLIOM_ERR_SOLVER (-10)          /* Ceres would report FAILURE (evaluation or invalid steps) */
+#define DLIOM_ERR_INTERNAL (-13)        /* a device 'cannot happen' word is set (2D ray casting: CHECK_NE / CHECK_EQ ray_casting.cc:114-115,144-145) */
 #define DLIOM_ERR_PEER_FAILED (-12)     /* sharded match: another rank failed before the exchange (it still took part) */
 
 typedef struct dliom_ctx dliom_ctx;
@@ -105,6 +106,7 @@ typedef struct dliom_memory_stats {
   int64_t leaf_slots_upper_bound;  /* grid only: >= slots in use (exact after dliom_grid_num_blocks) */
   int mirror_windowed;             /* grid only */
   int64_t outlier_table_bytes;     /* context only: the voxel tables of its dliom_outlier_remover objects */
+  int64_t probability_grid_bytes;  /* the dense cells, tables and words of dliom_probability_grid objects (2D) */
 } dliom_memory_stats;
 int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out);
 int dliom_ctx_set_mirror_budget(dliom_ctx* ctx, int64_t bytes);
@@ -576,6 +578,105 @@ int dliom_voxel_filter(float size, const float* points_xyz, int64_t n, float* ou
 int dliom_adaptive_voxel_filter(const dliom_adaptive_voxel_filter_options* options, const float* points_xyz,
                                 int64_t n, float* out_xyz, int64_t* num_out);
 
+/* ---- 2D probability grid of the export pipeline (the actions "write_probability_grid" and "write_ros_map") ----
+ * io::ProbabilityGridPointsProcessor (io/probability_grid_points_processor.{h,cc}) and
+ * cartographer_ros::RosMapWritingPointsProcessor (ros_map_writing_points_processor.cc:52-94, ros_map.cc:21-47) insert
+ * every batch into a mapping::ProbabilityGrid with ProbabilityGridRangeDataInserter2D
+ * (probability_grid_range_data_inserter_2d.cc:48-64) and draw it at the end.  A dliom_probability_grid is that grid in
+ * HBM: dense uint16 correspondence-cost cells, row-major num_x_cells * y + x (grid_2d.cc:168-171); MapLimits and the
+ * known-cells box live on the host.  Every cell, limit and pixel equals the reference's bit for bit (DESIGN.md
+ * section 3.11): the arithmetic is double up to the cell index (map_limits.h:69-76) and integer from there on.
+ *
+ * Refusals leave the grid exactly as it was:
+ *   DLIOM_ERR_INVALID_ARGUMENT  NULL or wrong-context arguments, negative n (before anything touches a device); a
+ *                               non-finite x or y of the origin or of a point (lround of it is undefined; z is
+ *                               never read, as in the reference: head<2>())
+ *   DLIOM_ERR_GRID_EXTENT       growth that would need num_cells * 1000 beyond int (the superscaled CellLimits of
+ *                               ray_casting.cc:175-178 overflows), a cell index that the reference's long -> int
+ *                               narrowing would wrap (map_limits.h:73-75), a superscaled index outside the grid
+ *                               (CHECK_GE ray_casting.cc:38-40, CHECK(Contains) grid_2d.cc:169), or more bytes of
+ *                               cells than the grid's budget
+ *   DLIOM_ERR_INTERNAL          the device error word is set (never expected; the passes have written: the grid is NOT
+ *                               restored, the known-cells box is extended and the insert counted like any other)
+ * An insert reads back twice: the batch's float bounding box with the non-finite flag (GrowAsNeeded runs on the
+ * host, between launches), and after the last pass the error words -- so a call has finished with its inputs
+ * when it returns. */
+typedef struct dliom_probability_grid dliom_probability_grid;
+typedef struct dliom_inserter2d dliom_inserter2d;
+#define DLIOM_PROBABILITY_GRID_DEFAULT_BUDGET_BYTES (INT64_C(1) << 30) /* of cells: 23170 x 23170 */
+typedef struct dliom_probability_grid_stats {
+  int64_t bytes;          /* HBM held: cells, colour table, words */
+  int64_t growths;        /* doublings since creation (grid_2d.cc:118) */
+  int64_t inserts;        /* successful inserts */
+  int64_t cells_visited;  /* ApplyLookupTable calls of the ray passes so far (ray_casting.cc:49,89-142) */
+  int32_t known_box[4];   /* min x, min y, max x, max y (grid_2d.h known_cells_box_); min > max: empty */
+  int32_t error_word;     /* the device error word as last read */
+} dliom_probability_grid_stats;
+/* io::CreateProbabilityGrid (probability_grid_points_processor.cc:150-158): 100 x 100 cells, max = 0.5 * 100 *
+ * resolution on both axes.  budget_bytes <= 0: DLIOM_PROBABILITY_GRID_DEFAULT_BUDGET_BYTES. */
+int dliom_probability_grid_create(dliom_ctx* ctx, double resolution, int64_t budget_bytes, dliom_probability_grid** out);
+/* ProbabilityGrid(MapLimits(resolution, (max_x, max_y), CellLimits(num_x_cells, num_y_cells))), e.g. the fixture of
+ * range_data_inserter_2d_test.cc:35. */
+int dliom_probability_grid_create_with_limits(dliom_ctx* ctx, double resolution, double max_x, double max_y,
+                                              int32_t num_x_cells, int32_t num_y_cells, int64_t budget_bytes,
+                                              dliom_probability_grid** out);
+int dliom_probability_grid_destroy(dliom_probability_grid* grid);
+/* limits(): resolution, max (x, y), cell limits (x, y) (map_limits.h:44-58) */
+int dliom_probability_grid_limits(const dliom_probability_grid* grid, double* resolution, double max_xy[2],
+                                  int32_t num_cells[2]);
+/* probability_grid_bytes alone; `grids` counts HybridGrids and stays 0. */
+int dliom_probability_grid_memory_stats(const dliom_probability_grid* grid, dliom_memory_stats* out);
+int dliom_probability_grid_get_stats(const dliom_probability_grid* grid, dliom_probability_grid_stats* out);
+/* Grid2D::GrowLimits on the limits alone (grid_2d.cc:116-145; host only, no device): grows max_xy / num_cells until
+ * they contain (px, py); offset accumulates where the old cell (0, 0) lands, *doublings counts the loop's turns.
+ * DLIOM_ERR_GRID_EXTENT (limits untouched) as above, with budget_bytes (<= 0: the default) on 2 bytes a cell. */
+int dliom_probability_grid_grow_limits(double resolution, double max_xy[2], int32_t num_cells[2], float px, float py,
+                                       int64_t budget_bytes, int32_t offset[2], int32_t* doublings);
+/* ComputeLookupTableToApplyCorrespondenceCostOdds (probability_values.cc:85-101): 32768 entries. */
+int dliom_compute_lookup_table_to_apply_correspondence_cost_odds(float odds, uint16_t* table);
+/* ProbabilityGridRangeDataInserter2D (probability_grid_range_data_inserter_2d.cc:36-46): the two tables of
+ * Odds(hit_probability), Odds(miss_probability), uploaded once.  hit_probability <= 0.5 or miss_probability >= 0.5 is
+ * refused (:43-44 of the options' CHECKs). */
+int dliom_inserter2d_create(dliom_ctx* ctx, double hit_probability, double miss_probability, int insert_free_space,
+                            dliom_inserter2d** out);
+int dliom_inserter2d_destroy(dliom_inserter2d* inserter);
+/* hit_table / miss_table: 32768 entries each, read back from the device. */
+int dliom_inserter2d_tables(const dliom_inserter2d* inserter, uint16_t* hit_table, uint16_t* miss_table);
+/* One Insert({origin, points, {}}, grid) (:48-64 -> CastRays, ray_casting.cc:166-203): GrowAsNeeded, the hit table on
+ * every end pixel, one CastRay(begin, end) per point if insert_free_space, FinishUpdate.  Map-frame points. */
+int dliom_inserter2d_insert_cloud(dliom_inserter2d* inserter, dliom_probability_grid* grid, const float origin[3],
+                                  const dliom_cloud* points);
+int dliom_inserter2d_insert(dliom_inserter2d* inserter, dliom_probability_grid* grid, const float origin[3],
+                            const float* points_xyz, int64_t n);
+/* The cells: cropped = 0 the whole grid (offset 0, num_cells = the limits'), else ComputeCroppedLimits
+ * (grid_2d.cc:101-111; empty box: offset 0, 1 x 1).  offset / num_cells are always filled; cells may be NULL (sizes
+ * only), a capacity (in cells) below num_cells[0] * num_cells[1] returns DLIOM_ERR_CAPACITY. */
+int dliom_probability_grid_cells(const dliom_probability_grid* grid, uint16_t* cells, int64_t capacity, int32_t offset[2],
+                                 int32_t num_cells[2], int cropped);
+/* GetProbability / IsKnown (probability_grid.cc:69-73, grid_2d.cc:93-97) of n cells (x, y); outside the limits:
+ * kMinProbability, unknown.  known may be NULL. */
+int dliom_probability_grid_get_probabilities(const dliom_probability_grid* grid, const int32_t* cell_xy, int64_t n,
+                                             float* probabilities, uint8_t* known);
+/* DrawProbabilityGrid (probability_grid_points_processor.cc:127-148) on the device: one gray byte a pixel of the
+ * cropped box, 128 unknown, else ProbabilityToColor (:49-54).  rotate_cw = 1 also applies
+ * Image::Rotate90DegreesClockwise (io/image.cc:67-76): size = {height, width} of the unrotated image.  offset / size
+ * are filled; gray may be NULL (sizes only); too small a capacity returns DLIOM_ERR_CAPACITY.  There is always an image:
+ * DrawProbabilityGrid returns nullptr only for cropped limits with a zero side (:131-134), and ComputeCroppedLimits
+ * gives 1 x 1 for an empty box (grid_2d.cc:103-107), so a fresh grid draws one unknown pixel, as in the reference. */
+int dliom_probability_grid_draw(const dliom_probability_grid* grid, uint8_t* gray, int64_t capacity, int32_t offset[2],
+                                int32_t size[2], int rotate_cw);
+/* The 32768 gray values draw uses (host only). */
+int dliom_probability_grid_color_table(uint8_t* table);
+/* The YAML origin of ros_map_writing_points_processor.cc:73-76 with the ROTATED image's width / height (host only). */
+int dliom_ros_map_yaml_origin(double resolution, const double max_xy[2], const int32_t offset[2], int32_t width,
+                              int32_t height, double origin[2]);
+/* WritePgm's header (ros_map.cc:23-26) and WriteYaml's text (:41-45) into buffer (capacity bytes, no terminator);
+ * *length is always filled, DLIOM_ERR_CAPACITY if it does not fit (host only). */
+int dliom_ros_map_pgm_header(double resolution, int32_t width, int32_t height, char* buffer, int64_t capacity,
+                             int64_t* length);
+int dliom_ros_map_yaml(double resolution, const double origin[2], const char* pgm_filename, char* buffer,
+                       int64_t capacity, int64_t* length);
+
 /* ---- per-hit de-skew of LocalTrajectoryBuilder3D::AddRangeData -------------------------------
  * (mapping/internal/3d/local_trajectory_builder_3d.cc:421-472, InterpolatePose :869-877).
  * hits_xyzt: n x (x, y, z, t) in the tracking frame, t <= 0 seconds relative to the scan end (the
@@ -1006,7 +1107,10 @@ enum {
   DLIOM_KERNEL_INSERT = 4,
   DLIOM_KERNEL_ALLREDUCE = 5,   /* dliom_rtcsm3d_match_sharded_rccl: copy in, ncclAllReduce(max, u64), copy out -- the
                                    collective's own time on this rank's stream, the wait for the slowest peer included */
-  DLIOM_KERNEL_COUNT = 6
+  DLIOM_KERNEL_PG_HITS = 6,     /* 2D probability grid insertion: end pixels + hit table (the bounds pass included) */
+  DLIOM_KERNEL_PG_RAYS = 7,     /* ... the supercover rays (the hot path) */
+  DLIOM_KERNEL_PG_CLEAR = 8,    /* ... FinishUpdate over the batch's pixel box */
+  DLIOM_KERNEL_COUNT = 9
 };
 /* enabled: 0 off, 1 every kernel id, otherwise a mask with bit (id + 1) per timed kernel id
  * (2 = the score kernel only: what bench.py's timed region uses; 2 | 64 = score kernel and the sharded match's
