@@ -12,6 +12,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "internal.h"
+#include "probability_values.h"
 
 namespace dliom {
 
@@ -33,7 +34,7 @@ void set_last_error(const char* what, hipError_t e, const char* file, int line) 
 int DevBuf::reserve(size_t bytes) {
   if (bytes <= cap) return DLIOM_OK;
   size_t want = std::max(bytes, cap + cap / 2);
-  want = (want + 255) & ~static_cast<size_t>(255);
+  want = align256(want);
   if (p != nullptr) {
     DLIOM_HIP_TRY(hipFree(p));
     p = nullptr;
@@ -216,7 +217,7 @@ static CloudLayout layout_cloud(char* base, int64_t n) {
   const int64_t np = pad_points(n);
   CloudLayout l;
   l.aos = reinterpret_cast<float*>(base);
-  const size_t soa_off = (static_cast<size_t>(n) * 12 + 255) & ~static_cast<size_t>(255);
+  const size_t soa_off = align256(static_cast<size_t>(n) * 12);
   l.x = reinterpret_cast<float*>(base + soa_off);
   l.y = l.x + np;
   l.z = l.y + np;
@@ -314,7 +315,7 @@ int ensure_morton(dliom_ctx* ctx, const dliom_cloud* cloud) {
         // need more than 27 translations, a search that small on a small cloud never reaches the box kernel.
         const int chunks64 = static_cast<int>((n + kCostChunkBig - 1) / kCostChunkBig);
         if (n >= 16384) {
-          unsigned char* cls64 = cls + ((static_cast<size_t>(chunks) + 255) & ~static_cast<size_t>(255));
+          unsigned char* cls64 = cls + align256(static_cast<size_t>(chunks));
           unsigned* order64 = l.keys_in + ((static_cast<size_t>(chunks) + 63) & ~static_cast<size_t>(63));
           hipLaunchKernelGGL(chunk_cost_kernel<kCostChunkBig>, dim3((chunks64 + 3) / 4), dim3(256), 0, ctx->stream, l.xs, l.ys, l.zs, n,
                              chunks64, cls64);
@@ -941,34 +942,18 @@ int dliom_ctx_kernel_time(dliom_ctx* ctx, int kernel_id, double* total_ms, int64
   return DLIOM_OK;
 }
 
-// ---- probability value tables (host, float arithmetic as in the reference) -------
-// mapping/probability_values.h:32-44,48-54 and probability_values.cc:27-36,73-83.
-static inline float clampf(float v, float lo, float hi) { return v > hi ? hi : (v < lo ? lo : v); }
-static const float kMinP = 0.1f;
-static const float kMaxP = 1.f - 0.1f;
-
-static inline uint16_t probability_to_value(float p) {
-  const int v =
-      static_cast<int>(std::lround((clampf(p, kMinP, kMaxP) - kMinP) * (32766.f / (kMaxP - kMinP)))) + 1;
-  return static_cast<uint16_t>(v);
-}
-static inline float value_to_probability(int v) {
-  if (v == 0) return kMinP;
-  const float kScale = (kMaxP - kMinP) / 32766.f;
-  return v * kScale + (kMinP - kScale);
-}
-
-float dliom_odds(float probability) { return probability / (1.f - probability); }
+// ---- probability value tables (host, float arithmetic as in the reference: probability_values.h) -------
+// ComputeLookupTableToApplyOdds: probability_values.cc:73-83.
+float dliom_odds(float probability) { return odds_of(probability); }
 
 uint16_t dliom_probability_to_value(float probability) { return probability_to_value(probability); }
 
 int dliom_compute_lookup_table_to_apply_odds(float odds, uint16_t* t) {
   if (t == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
-  t[0] = static_cast<uint16_t>(probability_to_value(odds / (odds + 1.f)) + 32768u);
+  t[0] = static_cast<uint16_t>(probability_to_value(probability_from_odds(odds)) + 32768u);
   for (int cell = 1; cell != 32768; ++cell) {
-    const float p = value_to_probability(cell);
-    const float o = odds * (p / (1.f - p));
-    t[cell] = static_cast<uint16_t>(probability_to_value(o / (o + 1.f)) + 32768u);
+    t[cell] = static_cast<uint16_t>(
+        probability_to_value(probability_from_odds(odds * odds_of(value_to_probability(cell)))) + 32768u);
   }
   return DLIOM_OK;
 }

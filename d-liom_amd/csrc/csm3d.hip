@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_common.h"
+#include "probability_values.h"
 
 namespace dliom {
 
@@ -564,17 +565,14 @@ static int evaluate(CsmProblem* p, const double x[7], Normal* out) {
   for (int i = 0; i < 4; ++i) a.pose.q[i] = x[3 + i];
   a.pose.nloc = p->nloc;
   plus_jacobian(x + 3, p->nloc, a.pose.plus);
-  const float kMin = 0.1f, kMax = 1.f - 0.1f;
-  const float k_scale = (kMax - kMin) / 32766.f;
-  const float k_offset = kMin - k_scale;
   const int span = ctx->begin_span(DLIOM_KERNEL_CSM_EVAL);
   // the 28 results go straight into pinned host memory (device-visible): no copy command
   double* host = pinned_at<double>(ctx, kPinCsmSums);
   // ... and a completion word behind them, which the host polls: ten evaluations a match, 5 us of synchronise each
   unsigned* done = p->d_arrivals != nullptr ? ctx->done_word : nullptr;
   const unsigned seq = done != nullptr ? (++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq) : 0u;
-  hipLaunchKernelGGL(csm_eval_kernel, dim3(p->num_blocks), dim3(kCsmBlock), 0, ctx->stream, a, k_scale,
-                     k_offset, kMin, p->d_partials, host, done, seq);
+  hipLaunchKernelGGL(csm_eval_kernel, dim3(p->num_blocks), dim3(kCsmBlock), 0, ctx->stream, a, kValueToProbabilityScale,
+                     kValueToProbabilityOffset, kUnknownProbability, p->d_partials, host, done, seq);
   if (p->num_blocks > 1)
     hipLaunchKernelGGL(csm_final_reduce_kernel, dim3(kAcc), dim3(64), 0, ctx->stream, p->d_partials,
                        p->num_blocks, host, p->d_arrivals, done, seq);
@@ -1193,9 +1191,7 @@ static int setup_problem(dliom_ctx* ctx, const dliom_csm_options* o, const doubl
     c.g = grids[i]->view();
     {
       // the mirror stands in for the leaf table only if "unknown" (0) and the mirror's 1 mean the same probability
-      const float kMin = 0.1f, kMax = 1.f - 0.1f;
-      const float k_scale = (kMax - kMin) / 32766.f, k_offset = kMin - k_scale;
-      if (!(1.f * k_scale + k_offset == kMin)) c.g.dense = nullptr;
+      if (!(1.f * kValueToProbabilityScale + kValueToProbabilityOffset == kUnknownProbability)) c.g.dense = nullptr;
     }
     DLIOM_TRY(ensure_morton(ctx, clouds[i]));
     c.x = clouds[i]->d_xs;  // Morton order: neighbouring lanes read neighbouring voxels; the
@@ -1231,10 +1227,9 @@ static LmKernelParams lm_params(const dliom_csm_options* o, const CsmProblem& p,
   for (int i = 0; i < 3; ++i) prm.target_t[i] = p.target_t[i];
   for (int i = 0; i < 4; ++i) prm.init_q[i] = p.init_q[i];
   for (int i = 0; i < 7; ++i) prm.x0[i] = x0[i];
-  const float kMin = 0.1f, kMax = 1.f - 0.1f;
-  prm.k_scale = (kMax - kMin) / 32766.f;
-  prm.k_offset = kMin - prm.k_scale;
-  prm.k_unknown = kMin;
+  prm.k_scale = kValueToProbabilityScale;
+  prm.k_offset = kValueToProbabilityOffset;
+  prm.k_unknown = kUnknownProbability;
   prm.done_word = nullptr;
   prm.done_seq = 0u;
   return prm;
@@ -1248,7 +1243,7 @@ static int stage_clouds(dliom_ctx* ctx, int k, const float* const* pts, const in
     if (n[i] < 0 || (n[i] > 0 && pts[i] == nullptr)) return DLIOM_ERR_INVALID_ARGUMENT;
     if (n[i] == 0) return DLIOM_ERR_EMPTY_CLOUD;
     off[i] = total;
-    total += (staged_cloud_bytes(n[i]) + 255) & ~static_cast<size_t>(255);
+    total += align256(staged_cloud_bytes(n[i]));
   }
   DLIOM_TRY(ctx->points.reserve(total));
   staged->resize(k);
@@ -1315,13 +1310,12 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* o, const do
     for (int i = 0; i < 3; ++i) prm.target_t[i] = p.target_t[i];
     for (int i = 0; i < 4; ++i) prm.init_q[i] = p.init_q[i];
     for (int i = 0; i < 7; ++i) prm.x0[i] = x[i];
-    const float kMin = 0.1f, kMax = 1.f - 0.1f;
-    prm.k_scale = (kMax - kMin) / 32766.f;
-    prm.k_offset = kMin - prm.k_scale;
-    prm.k_unknown = kMin;
+    prm.k_scale = kValueToProbabilityScale;
+    prm.k_offset = kValueToProbabilityOffset;
+    prm.k_unknown = kUnknownProbability;
     prm.done_word = nullptr;
     prm.done_seq = 0u;
-    const size_t part_bytes = (2 * static_cast<size_t>(p.num_blocks) * kAcc * sizeof(double) + 255) & ~static_cast<size_t>(255);
+    const size_t part_bytes = align256(2 * static_cast<size_t>(p.num_blocks) * kAcc * sizeof(double));
     DLIOM_TRY(ctx->partials.reserve(part_bytes + 256));
     double* partials = ctx->partials.as<double>();
     unsigned* counter = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->partials.p) + part_bytes);
@@ -1385,7 +1379,7 @@ int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* o, int coun
       for (int j = 0; j < std::min(std::max(q.num_clouds, 0), DLIOM_MAX_CLOUDS); ++j)
         if (q.clouds[j] == nullptr && q.n[j] > 0) {
           off[b * DLIOM_MAX_CLOUDS + j] = total;
-          total += (staged_cloud_bytes(q.n[j]) + 255) & ~static_cast<size_t>(255);
+          total += align256(staged_cloud_bytes(q.n[j]));
         }
     }
     DLIOM_TRY(ctx->points.reserve(total));
@@ -1424,8 +1418,8 @@ int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* o, int coun
     }
     if (!batched.empty()) {
       const int n = static_cast<int>(batched.size());
-      const size_t args_bytes = (n * sizeof(CsmArgs) + 255) & ~static_cast<size_t>(255);
-      const size_t prm_bytes = (n * sizeof(LmKernelParams) + 255) & ~static_cast<size_t>(255);
+      const size_t args_bytes = align256(n * sizeof(CsmArgs));
+      const size_t prm_bytes = align256(n * sizeof(LmKernelParams));
       const size_t upload = args_bytes + prm_bytes + 256;  // + the arrival counter (uploaded as zero)
       DLIOM_TRY(ctx->batch.reserve(upload));
       DLIOM_TRY(ctx->reserve_batch_pinned(upload + n * sizeof(LmKernelOut)));

@@ -10,7 +10,7 @@
 //                                                    fills in batches
 //   mapping/internal/3d/scan_matching/rotational_scan_matcher.cc:125-194 histogram matching (host)
 //   mapping/internal/3d/scan_matching/low_resolution_matcher.cc:23-36   -> the exact sequential
-//                                                    float sum kernels of rtcsm3d.hip
+//                                                    float sum kernels of sequential_sums.hip
 //
 // Exactness: a candidate's score is ToProbability(sum / float(N)) of an INTEGER sum, so any
 // summation order on the device gives the reference's float; the traversal (which candidates are
@@ -30,6 +30,7 @@
 #include "device_common.h"
 #include "host_math.h"
 #include "internal.h"
+#include "probability_values.h"
 #include "rotational.h"
 
 namespace dliom {
@@ -204,8 +205,7 @@ struct FrontierArgs {
 };
 
 __device__ __forceinline__ float frontier_probability(int sum, int n) {  // ScoreCandidates' float (:407-411)
-  const float kMin = 0.1f, kMax = 1.f - 0.1f;
-  return kMin + (static_cast<float>(sum) / static_cast<float>(n)) * ((kMax - kMin) / 255.f);
+  return kMinProbability + (static_cast<float>(sum) / static_cast<float>(n)) * ((kMaxProbability - kMinProbability) / 255.f);
 }
 
 // Integer sum of one candidate at `depth`, by one wavefront (every lane returns it).
@@ -490,7 +490,7 @@ int device_sums(Search& s, int depth, const std::vector<Candidate>& list, std::v
   const size_t k = list.size();
   sums->assign(k, 0);
   if (k == 0) return DLIOM_OK;
-  const size_t cbytes = (k * 16 + 255) & ~static_cast<size_t>(255);
+  const size_t cbytes = align256(k * 16);
   DLIOM_TRY(ctx->cand.reserve(cbytes + k * 4));
   // candidate list and sums travel through the pinned block when they fit (no staging copies)
   const bool pinned = cbytes + k * 4 <= kPinFastCsmScores.bytes;
@@ -537,8 +537,7 @@ int device_sums(Search& s, int depth, const std::vector<Candidate>& list, std::v
 }
 
 inline float to_probability(float value) {  // precomputation_grid_3d.h:31-34
-  const float kMin = 0.1f, kMax = 1.f - 0.1f;
-  return kMin + value * ((kMax - kMin) / 255.f);
+  return kMinProbability + value * ((kMaxProbability - kMinProbability) / 255.f);
 }
 
 // ScoreCandidates (:394-417) with the sums served from the cache (filled here when missing).
@@ -633,7 +632,7 @@ int prefetch_frontier(Search& s, float threshold) {
 // (device) hold the same upload: the array of num_searches FrontierArgs, at frontier_counts_at() num_searches x
 // kCountWords counts, then the flat list of `total` lowest-resolution records.  Enqueued only: the caller synchronises.
 constexpr size_t frontier_counts_at(int num_searches) {
-  return (num_searches * sizeof(FrontierArgs) + 255) & ~static_cast<size_t>(255);
+  return align256(num_searches * sizeof(FrontierArgs));
 }
 constexpr size_t frontier_flat_at(int num_searches) { return frontier_counts_at(num_searches) + num_searches * kCountWords * 4; }
 constexpr size_t frontier_upload_bytes(int num_searches, size_t total) {
@@ -715,7 +714,7 @@ int device_frontier(Search& s, const std::vector<Candidate>& lowest, float min_s
   static_assert(frontier_upload_bytes(1, kCap) <= kPinFrontierUpload.bytes, "the largest upload fits its region");
   const size_t k = lowest.size();
   if (!frontier_suits(s, k, kCap)) return DLIOM_OK;
-  const size_t up = (frontier_upload_bytes(1, k) + 255) & ~static_cast<size_t>(255);
+  const size_t up = align256(frontier_upload_bytes(1, k));
   const size_t pool_bytes = static_cast<size_t>(max_depth + 1) * kCap * sizeof(FrontierRec);
   DLIOM_TRY(ctx->cand.reserve(up + pool_bytes));
   char* d = static_cast<char*>(ctx->cand.p);
@@ -870,7 +869,7 @@ int run_search(Search& s, const dliom_cloud& hi_cloud, float min_score, dliom_fa
   s.n_hi = static_cast<int>(hi_cloud.n);
   // discrete scans on the device
   const size_t cells = static_cast<size_t>(num_scans) * s.n_hi;
-  const size_t pose_bytes = (static_cast<size_t>(num_scans) * 28 + 255) & ~static_cast<size_t>(255);
+  const size_t pose_bytes = align256(static_cast<size_t>(num_scans) * 28);
   DLIOM_TRY(ctx->sums.reserve(pose_bytes + 3 * cells * 4));
   float* d_poses = ctx->sums.as<float>();
   s.d_cx = reinterpret_cast<int*>(static_cast<char*>(ctx->sums.p) + pose_bytes);
@@ -1000,7 +999,6 @@ constexpr size_t kChunkTop = 1u << 18;   //   lowest-resolution candidates
 constexpr size_t kChunkCellBytes = 256u << 20;  // discrete-scan cells
 constexpr int kChunkScans = 65535;       //   discrete scans (discretize_batch_kernel's grid)
 
-inline size_t up256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 inline size_t pad64(int64_t n) { return (static_cast<size_t>(n) + 63) & ~static_cast<size_t>(63); }
 
 // One chunk: discretisation + frontier chain (one synchronisation), the low-resolution scores of the leaves at or
@@ -1017,25 +1015,25 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
     const dliom_fast_csm_node_data& d = queries[ids[j]].node_data;
     total_top += lowest[ids[j]].size();
     total_scans += s.scan_poses.size();
-    hi_bytes += up256(static_cast<size_t>(d.num_high_resolution_points) * 12);
+    hi_bytes += align256(static_cast<size_t>(d.num_high_resolution_points) * 12);
     lo_bytes += 3 * pad64(d.num_low_resolution_points) * 4;
     pool_bytes += static_cast<size_t>(s.m->max_depth() + 1) * kBatchCap * sizeof(FrontierRec);
-    cell_bytes += up256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
+    cell_bytes += align256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
     deepest = std::max(deepest, s.m->max_depth());
     widest = std::max(widest, s.n_hi);
   }
-  const size_t front_bytes = up256(frontier_upload_bytes(S, total_top));
-  const size_t scan_at = front_bytes, hi_at = scan_at + up256(total_scans * sizeof(DiscreteScanArg)), lo_at = hi_at + hi_bytes;
+  const size_t front_bytes = align256(frontier_upload_bytes(S, total_top));
+  const size_t scan_at = front_bytes, hi_at = scan_at + align256(total_scans * sizeof(DiscreteScanArg)), lo_at = hi_at + hi_bytes;
   const size_t upload_bytes = lo_at + lo_bytes;
-  const size_t pool_at = up256(upload_bytes), cells_at = pool_at + pool_bytes;
+  const size_t pool_at = align256(upload_bytes), cells_at = pool_at + pool_bytes;
   const size_t leaves = static_cast<size_t>(S) * kBatchLeavesAhead;
-  const size_t rot_at = cells_at + cell_bytes, trans_at = rot_at + up256(leaves * 16), list_at = trans_at + up256(leaves * 12),
-               lsum_at = list_at + up256(leaves * 4);
-  DLIOM_TRY(ctx->batch.reserve(lsum_at + up256(leaves * 4)));
-  const size_t out_stride = up256((kMaxLevels + 2) * 4 + static_cast<size_t>(kBatchOutRecords) * sizeof(FrontierRec));
-  const size_t h_out_at = up256(upload_bytes), h_leaf_at = h_out_at + S * out_stride;
+  const size_t rot_at = cells_at + cell_bytes, trans_at = rot_at + align256(leaves * 16), list_at = trans_at + align256(leaves * 12),
+               lsum_at = list_at + align256(leaves * 4);
+  DLIOM_TRY(ctx->batch.reserve(lsum_at + align256(leaves * 4)));
+  const size_t out_stride = align256((kMaxLevels + 2) * 4 + static_cast<size_t>(kBatchOutRecords) * sizeof(FrontierRec));
+  const size_t h_out_at = align256(upload_bytes), h_leaf_at = h_out_at + S * out_stride;
   const size_t h_lsum_at = h_leaf_at + (lsum_at - rot_at);
-  DLIOM_TRY(ctx->reserve_batch_pinned(h_lsum_at + up256(leaves * 4)));
+  DLIOM_TRY(ctx->reserve_batch_pinned(h_lsum_at + align256(leaves * 4)));
   char* d = static_cast<char*>(ctx->batch.p);
   char* h = static_cast<char*>(ctx->batch_pinned);
 
@@ -1103,10 +1101,10 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
     std::memcpy(&h_args[j], &a, sizeof(a));
     h_counts[static_cast<size_t>(j) * kCountWords + a.max_depth] = a.top_count;
     for (const Candidate& cd : low) h_flat[top++] = FrontierRec{cd.scan_index, cd.offset[0], cd.offset[1], cd.offset[2], 0};
-    hi_off += up256(static_cast<size_t>(s.n_hi) * 12);
+    hi_off += align256(static_cast<size_t>(s.n_hi) * 12);
     lo_off += 3 * pl * 4;
     pool_off += static_cast<size_t>(s.m->max_depth() + 1) * kBatchCap * sizeof(FrontierRec);
-    cell_off += up256(3 * cells * 4);
+    cell_off += align256(3 * cells * 4);
   }
 
   // ---- one upload, the discrete scans, the chain, one synchronisation
@@ -1231,7 +1229,7 @@ int fast_csm_batch(dliom_ctx* ctx, const dliom_fast_csm_query* queries, int coun
     int scans = 0;
     while (end < batched.size() && end - at < static_cast<size_t>(kChunkSearches)) {
       const Search& s = *searches[batched[end]];
-      const size_t k = lowest[batched[end]].size(), c = up256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
+      const size_t k = lowest[batched[end]].size(), c = align256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
       const int ns = static_cast<int>(s.scan_poses.size());
       if (end > at && (top + k > kChunkTop || cells + c > kChunkCellBytes || scans + ns > kChunkScans)) break;
       top += k;
@@ -1293,11 +1291,8 @@ int dliom_fast_csm_create(dliom_ctx* ctx, const dliom_grid* hi, const dliom_grid
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     // ConvertToPrecomputationGrid's value map (:53-57), host float arithmetic like the reference
     std::vector<uint8_t> lut(32768, 0);
-    const float kMin = 0.1f, kMax = 1.f - 0.1f;
     for (int v = 1; v < 32768; ++v) {
-      const float kScale = (kMax - kMin) / 32766.f;
-      const float p = v * kScale + (kMin - kScale);
-      const long cell = std::lround((p - kMin) * (255.f / (kMax - kMin)));
+      const long cell = std::lround((value_to_probability(v) - kMinProbability) * (255.f / (kMaxProbability - kMinProbability)));
       lut[v] = static_cast<uint8_t>(std::min(255l, std::max(0l, cell)));
     }
     uint8_t* d_lut = static_cast<uint8_t*>(ctx->misc.p);

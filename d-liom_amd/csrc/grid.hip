@@ -492,10 +492,6 @@ __global__ void multi_insert_kernel(MultiInsertArgs a) {
   }
 }
 
-static inline unsigned blocks_for(int64_t n, int threads) {
-  return static_cast<unsigned>((n + threads - 1) / threads);
-}
-
 }  // namespace dliom
 
 using namespace dliom;
@@ -558,7 +554,7 @@ int dliom_grid::ensure_bits(int needed_bits) {
   int64_t count = 0;
   DLIOM_TRY(refresh_count(&count));
   if (count > 1) {
-    hipLaunchKernelGGL(rebuild_table_kernel, dim3(blocks_for(count - 1, 256)), dim3(256), 0,
+    hipLaunchKernelGGL(rebuild_table_kernel, dim3(blocks_of(count - 1, 256)), dim3(256), 0,
                        ctx->stream, d_slot_coord, static_cast<uint32_t>(count), new_table,
                        4 << needed_bits, 8u << needed_bits);
     DLIOM_HIP_TRY(hipGetLastError());
@@ -583,7 +579,7 @@ void dliom_grid::drop_dense() {
 
 // Dense mirror of the grid for the correlative matcher: (grid_size + 2)^3 uint16 in 4x4x4 bricks
 // (dense_index), one guard cell per side, holding what the matcher SUMS: max(value & 0x7fff, 1) -- unknown cells,
-// guard cells and everything outside read 1 (= kMinProbability's value, rtcsm3d.hip), known cells
+// guard cells and everything outside read 1 (= kMinProbability's value, probability_values.h), known cells
 // their marker-free value (always >= 1 once a lookup table was applied).  Spends HBM capacity (258 MiB at
 // bits = 3, 2.0 GiB at bits = 4) to make a voxel lookup ONE load at a linear address instead of
 // leaf-table load + leaf load; kept in sync by the insertion kernels (write-through) and rebuilt
@@ -880,11 +876,11 @@ int dliom_grid_upload_blocks(dliom_grid* g, const int32_t* origins, const uint16
   DLIOM_TRY(ctx->misc.reserve(obytes + 256 + vbytes));
   int32_t* d_orig = ctx->misc.as<int32_t>();
   uint16_t* d_vals = reinterpret_cast<uint16_t*>(static_cast<char*>(ctx->misc.p) +
-                                                  ((obytes + 255) & ~static_cast<size_t>(255)));
+                                                  align256(obytes));
   DLIOM_HIP_TRY(hipMemcpyAsync(d_orig, origins, obytes, hipMemcpyHostToDevice, ctx->stream));
   DLIOM_HIP_TRY(hipMemcpyAsync(d_vals, values512, vbytes, hipMemcpyHostToDevice, ctx->stream));
   const GridView v = g->view();
-  hipLaunchKernelGGL(upload_alloc_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_orig,
+  hipLaunchKernelGGL(upload_alloc_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, d_orig,
                      n, g->d_table, g->d_slot_coord, g->d_count, v.half, v.grid_size,
                      static_cast<unsigned>(v.leaves_per_axis));
   DLIOM_HIP_TRY(hipGetLastError());
@@ -939,17 +935,17 @@ int dliom_grid_set_values(dliom_grid* g, const int32_t* cells, const uint16_t* v
   }
   DLIOM_TRY(g->ensure_bits(needed_bits_for_cell_range(lo, hi)));
   DLIOM_TRY(g->ensure_capacity(n));
-  const size_t cbytes = (static_cast<size_t>(n) * 12 + 255) & ~static_cast<size_t>(255);
+  const size_t cbytes = align256(static_cast<size_t>(n) * 12);
   DLIOM_TRY(ctx->misc.reserve(cbytes + static_cast<size_t>(n) * 2));
   int32_t* d_cells = ctx->misc.as<int32_t>();
   uint16_t* d_vals = reinterpret_cast<uint16_t*>(static_cast<char*>(ctx->misc.p) + cbytes);
   DLIOM_HIP_TRY(hipMemcpyAsync(d_cells, cells, static_cast<size_t>(n) * 12, hipMemcpyHostToDevice, ctx->stream));
   DLIOM_HIP_TRY(hipMemcpyAsync(d_vals, values, static_cast<size_t>(n) * 2, hipMemcpyHostToDevice, ctx->stream));
   const GridView v = g->view();
-  hipLaunchKernelGGL(set_alloc_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_cells, n,
+  hipLaunchKernelGGL(set_alloc_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, d_cells, n,
                      g->d_table, g->d_slot_coord, g->d_count, v.half, v.grid_size,
                      static_cast<unsigned>(v.leaves_per_axis));
-  hipLaunchKernelGGL(set_values_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_cells, d_vals,
+  hipLaunchKernelGGL(set_values_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, d_cells, d_vals,
                      n, g->d_table, g->d_pool, v.half, v.grid_size, static_cast<unsigned>(v.leaves_per_axis));
   DLIOM_HIP_TRY(hipGetLastError());
   g->used_upper += n;
@@ -965,12 +961,12 @@ int dliom_grid_get_values(const dliom_grid* g, const int32_t* cells, int64_t n, 
   dliom_ctx* ctx = g->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   const size_t cbytes = static_cast<size_t>(n) * 12;
-  const size_t off = (cbytes + 255) & ~static_cast<size_t>(255);
+  const size_t off = align256(cbytes);
   DLIOM_TRY(ctx->misc.reserve(off + static_cast<size_t>(n) * 2));
   int32_t* d_cells = ctx->misc.as<int32_t>();
   uint16_t* d_out = reinterpret_cast<uint16_t*>(static_cast<char*>(ctx->misc.p) + off);
   DLIOM_HIP_TRY(hipMemcpyAsync(d_cells, cells, cbytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(get_values_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, g->view(),
+  hipLaunchKernelGGL(get_values_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, g->view(),
                      d_cells, n, d_out);
   DLIOM_HIP_TRY(hipGetLastError());
   DLIOM_HIP_TRY(hipMemcpyAsync(values, d_out, static_cast<size_t>(n) * 2, hipMemcpyDeviceToHost,
@@ -1001,7 +997,7 @@ static int insert_device(dliom_grid* g, const float origin[3], const float* d_re
   a.L = 0;
   a.dense = nullptr;
   a.dense_stride = 0;
-  const dim3 grid(blocks_for(n, 256)), block(256);
+  const dim3 grid(blocks_of(n, 256)), block(256);
   hipLaunchKernelGGL(insert_scan_kernel, grid, block, 0, ctx->stream, a, d_scan);
   DLIOM_HIP_TRY(hipGetLastError());
   int scan[2] = {0, 0};
@@ -1042,7 +1038,7 @@ int dliom_grid_insert(dliom_grid* g, const float origin[3], const float* returns
   dliom_ctx* ctx = g->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   // scratch: [returns | hit lut | miss lut | scan out]
-  const size_t pbytes = (static_cast<size_t>(n) * 12 + 255) & ~static_cast<size_t>(255);
+  const size_t pbytes = align256(static_cast<size_t>(n) * 12);
   DLIOM_TRY(ctx->misc.reserve(pbytes + 65536 * 2 + 256));
   char* base = static_cast<char*>(ctx->misc.p);
   float* d_returns = reinterpret_cast<float*>(base);
@@ -1114,7 +1110,7 @@ int dliom_inserter_insert(const dliom_inserter* ins, dliom_grid* g, const float 
   if (n == 0) return DLIOM_OK;
   dliom_ctx* ctx = g->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  const size_t pbytes = (static_cast<size_t>(n) * 12 + 255) & ~static_cast<size_t>(255);
+  const size_t pbytes = align256(static_cast<size_t>(n) * 12);
   DLIOM_TRY(ctx->misc.reserve(pbytes + 256));
   char* base = static_cast<char*>(ctx->misc.p);
   float* d_returns = reinterpret_cast<float*>(base);
@@ -1279,7 +1275,7 @@ int dliom_inserter_insert_cloud_multi(const dliom_inserter* ins, int num_targets
   a.hit = ins->d_tables;
   a.miss = ins->d_tables + 32768;
   a.run_mask = (1u << num_targets) - 1u;
-  const dim3 grid_dim(blocks_for(n, 256), num_targets), block(256);
+  const dim3 grid_dim(blocks_of(n, 256), num_targets), block(256);
   // Steady state (round 5): the scan's range is known on the host (max ||p|| travels with the cloud), so "no target
   // needs more bits, no ray is too long" is usually PROVEN before anything is launched -- then there is no extent scan,
   // no status fill and, above all, no verdict to wait for: the four update passes are enqueued and the call returns

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/dliom.h"
+#include "probability_values.h"
 
 namespace {
 
@@ -45,18 +46,10 @@ bool get_varint(const uint8_t*& p, const uint8_t* end, uint64_t* v) {
   return false;
 }
 
-// probability_values.{h,cc}: the round trip the proto constructor applies to every value
-inline float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// probability_values.h: the round trip the proto constructor applies to every value, SetProbability(index,
+// ValueToProbability(uint16(value))).  The probability comes out of the table, so it is never a NaN, whatever the bytes.
 uint16_t set_probability_of_value(int32_t proto_value) {
-  const float kMin = 0.1f, kMax = 1.f - 0.1f;
-  const uint16_t v16 = static_cast<uint16_t>(proto_value);  // ValueToProbability(uint16)
-  const int v = v16 & 0x7FFF;                               // the table repeats above the update marker
-  float p = kMin;
-  if (v != 0) {
-    const float kScale = (kMax - kMin) / 32766.f;
-    p = v * kScale + (kMin - kScale);
-  }
-  return static_cast<uint16_t>(static_cast<int>(std::lround((clampf(p, kMin, kMax) - kMin) * (32766.f / (kMax - kMin)))) + 1);
+  return dliom::probability_to_value(dliom::value_to_probability(static_cast<uint16_t>(proto_value)));
 }
 
 }  // namespace

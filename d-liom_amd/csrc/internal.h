@@ -289,6 +289,10 @@ int compact_equal_arrays(dliom_ctx* ctx, const Soa& in, const unsigned char* kin
 int compact_equal_arrays_enqueue(dliom_ctx* ctx, const Soa& in, const unsigned char* kinds, unsigned char want, float* ox,
                                  float* oy, float* oz, const unsigned* n_dev, const unsigned** d_total);
 int needed_bits_for_cell_range(int min_index, int max_index);
+// sizes and offsets inside the scratch buffers are multiples of 256 bytes
+constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
+// workgroups of `threads` that cover n items
+constexpr unsigned blocks_of(int64_t n, int threads) { return static_cast<unsigned>((n + threads - 1) / threads); }
 // core.hip: several small device fills / read-backs in ONE dispatch each (a hipMemsetAsync or hipMemcpyAsync is a
 // dispatch of its own: ~3 us of GPU time plus the gap to its neighbours, and the filtered-cloud chain issued ~25 per scan)
 struct FillJob {
@@ -319,7 +323,17 @@ int wait_done(dliom_ctx* ctx, hipStream_t stream, const unsigned* done_word, uns
 int gather_and_wait(dliom_ctx* ctx, const GatherJob* jobs, int num_jobs, void* pinned_dst);
 // 64 device words that are zero and that nobody writes (zeroed on ctx->stream at first use)
 int zero_words(dliom_ctx* ctx, unsigned** out);
-// rtcsm3d.hip: exact sequential float sums of LUT probabilities under explicit float poses
+// sequential_sums.hip: the reference's sequential `score += probability` float sums, bit-identical.
+// Launches the kernels for `count` candidates whose indices are in d_list (c -> translation c / R, rotation c % R):
+// method 0 = one lane replays the loop, 1 = element scan, 2 = chunk scan.  Methods 1 and 2 need the 15-bit values of a
+// candidate in LDS (n <= 65536) and fall back to method 0 beyond.  `scratch` receives values / chunk sums / chunk
+// functions; d_count != nullptr: the kernels read the live candidate count on the device.
+int launch_sequential_sums(dliom_ctx* ctx, int method, const GridView& gv, const dliom_cloud& cloud, const float4* d_rot,
+                           int R, const float* d_trans, const unsigned* d_list, const unsigned* d_count, unsigned count,
+                           DevBuf* scratch, float* d_ksums);
+// The method the library itself uses for a cloud of num_points: the serial replay up to 1 024 points, else the chunk scan
+int sequential_sum_method(int64_t num_points);
+// The sums under k explicit float poses (x, y, z, qw, qx, qy, qz), read back into `sums`
 int sequential_probability_sums(dliom_ctx* ctx, const dliom_cloud& cloud, const dliom_grid* grid, const float* poses7,
                                 int k, float* sums);
 // The same sums for several (cloud, grid) pairs, only enqueued on ctx->stream: job j scores the poses [first, first + k)

@@ -316,8 +316,7 @@ __global__ __launch_bounds__(kBlock) void outlier_emit_voxels_kernel(const int* 
   out[at] = VoxelRecord{(vz << 28) | (vy << 14) | vx, pool[2 * c], pool[2 * c + 1]};
 }
 
-inline unsigned blocks_of(int64_t n) { return static_cast<unsigned>((n + kBlock - 1) / kBlock); }
-inline size_t align256(size_t b) { return (b + 255) & ~size_t{255}; }
+inline unsigned blocks_of(int64_t n) { return dliom::blocks_of(n, kBlock); }
 
 // Compacts `in` by the flags a kernel has just written to scratch: one read-back (count, max squared norm, `flag_word`).
 struct CompactScratch {

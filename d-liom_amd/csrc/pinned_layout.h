@@ -42,7 +42,7 @@ constexpr PinRegion kPinDownload{0, kPinnedBytes - 8192};
 // an RTCSM match (rtcsm3d.hip)
 constexpr PinRegion kPinRtcsmCandidates{0, kPinnedBytes - 81920};  // candidate tables (pageable above this)
 constexpr PinRegion kPinBoxTables{kPinnedBytes - 81920, 65536};    // the LDS-box kernel's tables (pageable above this)
-constexpr PinRegion kPinSequentialSums{kPinnedBytes - 8192, 4096};  // sequential_probability_sums: up to 1024 floats
+constexpr PinRegion kPinSequentialSums{kPinnedBytes - 8192, 4096};  // sequential_probability_sums (sequential_sums.hip): up to 1024 floats
 constexpr PinRegion kPinMatchReadback{kPinnedBytes - 4096, 2048};  // [count pair | list | sums | box overflow word]
 constexpr PinRegion kPinBoxErrorWord{kPinnedBytes - 2048, 4};      // a shard's box overflow word
 constexpr PinRegion kPinRcclWord{kPinnedBytes - 1024, 8};          // the RCCL exchange's 64-bit word

@@ -502,12 +502,11 @@ static int add_range_data_stage_a(dliom_ctx* ctx, const double prev_pose[7], con
                                   size_t* stride, int64_t* num_returns) {
   if (n >= (int64_t{1} << 27)) return DLIOM_ERR_INVALID_ARGUMENT;  // (hit indices share a word with the records' launch tag)
   const size_t nn = static_cast<size_t>(n);
-  auto al = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   // scratch: raw AoS | raw SoA (4) | filtered hits SoA (4) | de-skewed SoA (3) + kind | returns (3) | origin index in
   // | origin index filtered | pose
-  const size_t off_raw = 0, off_b = al(16 * nn), off_c = off_b + al(16 * nn), off_d = off_c + al(16 * nn),
-               off_kind = off_d + al(12 * nn), off_e = off_kind + al(nn), off_oi = off_e + al(12 * nn),
-               off_of = off_oi + al(4 * nn), off_pose = off_of + al(4 * nn), total = off_pose + 256;
+  const size_t off_raw = 0, off_b = align256(16 * nn), off_c = off_b + align256(16 * nn), off_d = off_c + align256(16 * nn),
+               off_kind = off_d + align256(12 * nn), off_e = off_kind + align256(nn), off_oi = off_e + align256(12 * nn),
+               off_of = off_oi + align256(4 * nn), off_pose = off_of + align256(4 * nn), total = off_pose + 256;
   DLIOM_TRY(ctx->misc.reserve(total));
   char* base = static_cast<char*>(ctx->misc.p);
   float* b = reinterpret_cast<float*>(base + off_b);
@@ -606,13 +605,12 @@ static int add_range_data_stage_b(dliom_ctx* ctx, const float* rx, const float* 
                                   float voxel_filter_size, const float current_pose[7], dliom_cloud** returns_in_tracking,
                                   float origin_in_tracking[3]) {
   const size_t nn = static_cast<size_t>(std::max<int64_t>(n2, 1));
-  auto al = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   // filtered returns | per-workgroup maxima | transformed returns (misc holds the inputs)
-  DLIOM_TRY(ctx->rescore.reserve(6 * al(4 * nn) + 16 * kTransformBlocks));
+  DLIOM_TRY(ctx->rescore.reserve(6 * align256(4 * nn) + 16 * kTransformBlocks));
   float* f = ctx->rescore.as<float>();
-  float* d_partial_max = reinterpret_cast<float*>(static_cast<char*>(ctx->rescore.p) + 3 * al(4 * nn));
-  float* t = reinterpret_cast<float*>(static_cast<char*>(ctx->rescore.p) + 3 * al(4 * nn) + 16 * kTransformBlocks);
-  const size_t fs = al(4 * nn) / 4;
+  float* d_partial_max = reinterpret_cast<float*>(static_cast<char*>(ctx->rescore.p) + 3 * align256(4 * nn));
+  float* t = reinterpret_cast<float*>(static_cast<char*>(ctx->rescore.p) + 3 * align256(4 * nn) + 16 * kTransformBlocks);
+  const size_t fs = align256(4 * nn) / 4;
   // current_pose.inverse() in float (rigid_transform.h:167-171)
   const QF qc{current_pose[3], -current_pose[4], -current_pose[5], -current_pose[6]};
   const F3 rt = qrot(qc, F3{current_pose[0], current_pose[1], current_pose[2]});
@@ -824,9 +822,9 @@ extern "C" int dliom_deskew(dliom_ctx* ctx, const double prev_pose[7], const dou
   DLIOM_TRY(make_deskew_args(prev_pose, predicted_pose, scan_period, origin, min_range, max_range, hits_xyzt[3], &a));
   deskew_test_hook(ctx, &a);
   const size_t in_bytes = static_cast<size_t>(n) * 16;
-  const size_t xyz_off = (in_bytes + 255) & ~static_cast<size_t>(255);
-  const size_t kind_off = xyz_off + ((static_cast<size_t>(n) * 12 + 255) & ~static_cast<size_t>(255));
-  const size_t pose_off = kind_off + ((static_cast<size_t>(n) + 255) & ~static_cast<size_t>(255));
+  const size_t xyz_off = align256(in_bytes);
+  const size_t kind_off = xyz_off + align256(static_cast<size_t>(n) * 12);
+  const size_t pose_off = kind_off + align256(static_cast<size_t>(n));
   DLIOM_TRY(ctx->misc.reserve(pose_off + 64));
   char* base = static_cast<char*>(ctx->misc.p);
   unsigned* d_flags = nullptr;

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "device_common.h"
+#include "probability_values.h"
 
 namespace dliom {
 namespace {
@@ -296,33 +297,10 @@ __global__ __launch_bounds__(kBlock) void pg_gather_cells_kernel(Cells g, const 
   out[i] = inside ? g.cells[static_cast<size_t>(g.nx) * static_cast<size_t>(y) + static_cast<size_t>(x)] : 0xFFFFFFFFu;
 }
 
-inline unsigned blocks_of(int64_t n) { return static_cast<unsigned>((n + kBlock - 1) / kBlock); }
+inline unsigned blocks_of(int64_t n) { return dliom::blocks_of(n, kBlock); }
 inline dim3 grid_2d(int w, int h) { return dim3(blocks_of(w), static_cast<unsigned>(std::min(h, 32768))); }
 
-// ---- probability values (host, the reference's float expressions; probability_values.{h,cc}) ---------------------------
-const float kMinProbability = 0.1f;
-const float kMaxProbability = 1.f - kMinProbability;
-const float kMinCorrespondenceCost = 1.f - kMaxProbability;
-const float kMaxCorrespondenceCost = 1.f - kMinProbability;
-
-inline float clampf(float v, float lo, float hi) { return v > hi ? hi : (v < lo ? lo : v); }
-// CorrespondenceCostToValue = BoundedFloatToValue (probability_values.h:32-44)
-inline uint16_t correspondence_cost_to_value(float c) {
-  const int v = static_cast<int>(std::lround((clampf(c, kMinCorrespondenceCost, kMaxCorrespondenceCost) - kMinCorrespondenceCost) *
-                                             (32766.f / (kMaxCorrespondenceCost - kMinCorrespondenceCost)))) +
-                1;
-  return static_cast<uint16_t>(v);
-}
-// SlowValueToBoundedFloat (probability_values.cc:27-36)
-inline float value_to_correspondence_cost(unsigned v) {
-  v &= 32767u;  // the table's upper half repeats the lower (:38-51)
-  if (v == 0u) return kMaxCorrespondenceCost;
-  const float kScale = (kMaxCorrespondenceCost - kMinCorrespondenceCost) / 32766.f;
-  return v * kScale + (kMinCorrespondenceCost - kScale);
-}
-inline float probability_from_odds(float odds) { return odds / (odds + 1.f); }
-inline float odds_of(float p) { return p / (1.f - p); }
-
+// ---- the tables of a 2D inserter and of the drawing (host, the reference's float expressions: probability_values.h) ----
 void correspondence_cost_odds_table(float odds, uint16_t* t) {
   t[0] = static_cast<uint16_t>(correspondence_cost_to_value(1.f - probability_from_odds(odds)) + kUpdateMarker);
   for (unsigned cell = 1; cell != 32768u; ++cell) {

@@ -1242,7 +1242,7 @@ size_t carve_big_arrays(char* base, size_t entries, dliom::rothist::BigArrays* A
   size_t at = 0;
   auto take = [&](size_t bytes) {
     char* p = base == nullptr ? nullptr : base + at;
-    at += (bytes + 255) & ~static_cast<size_t>(255);
+    at += align256(bytes);
     return p;
   };
   const size_t e = entries + 64;
@@ -1277,9 +1277,9 @@ extern "C" int dliom_diag_std_sort_order(dliom_ctx* ctx, const float* keys, int 
     const size_t big_bytes = carve_big_arrays(nullptr, entries, &A);
     size_t temp_bytes = 0;
     DLIOM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, A.key_in, A.key_out, A.val_in, A.val_out, n, 0, 32, ctx->stream));
-    const size_t keys_at = (big_bytes + 255) & ~static_cast<size_t>(255);
-    const size_t order_at = keys_at + ((static_cast<size_t>(n) * 4 + 255) & ~static_cast<size_t>(255));
-    const size_t temp_at = order_at + ((static_cast<size_t>(n) * 4 + 256 + 255) & ~static_cast<size_t>(255));
+    const size_t keys_at = align256(big_bytes);
+    const size_t order_at = keys_at + align256(static_cast<size_t>(n) * 4);
+    const size_t temp_at = order_at + align256(static_cast<size_t>(n) * 4 + 256);
     DLIOM_TRY(ctx->misc.reserve(temp_at + temp_bytes + 256));
     char* base = static_cast<char*>(ctx->misc.p);
     carve_big_arrays(base, entries, &A);
@@ -1346,7 +1346,7 @@ extern "C" int dliom_diag_sequential_sums(dliom_ctx* ctx, const float* values, i
       static_cast<int64_t>(k) * n > (int64_t{1} << 28))
     return DLIOM_ERR_INVALID_ARGUMENT;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  const size_t v_bytes = (static_cast<size_t>(k) * n * 4 + 255) & ~static_cast<size_t>(255);
+  const size_t v_bytes = align256(static_cast<size_t>(k) * n * 4);
   DLIOM_TRY(ctx->misc.reserve(v_bytes + static_cast<size_t>(k) * 8 + 256));
   float* d_v = ctx->misc.as<float>();
   float* d_a = reinterpret_cast<float*>(static_cast<char*>(ctx->misc.p) + v_bytes);

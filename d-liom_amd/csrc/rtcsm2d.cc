@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/dliom.h"
+#include "probability_values.h"
 
 namespace {
 
@@ -28,12 +29,8 @@ struct Limits {
 struct CostTable {
   std::vector<float> probability;  // 1 - cost, indexed by the 16-bit cell value
   CostTable() : probability(65536) {
-    const float lo = 1.f - (1.f - 0.1f);  // kMinCorrespondenceCost
-    const float hi = 1.f - 0.1f;          // kMaxCorrespondenceCost
-    const float scale = (hi - lo) / 32766.f;
     for (int v = 0; v < 32768; ++v) {
-      const float cost = v == 0 ? hi : v * scale + (lo - scale);
-      probability[v] = 1.f - cost;
+      probability[v] = 1.f - dliom::value_to_correspondence_cost(v);
       probability[v + 32768] = probability[v];
     }
   }
@@ -101,7 +98,7 @@ extern "C" int dliom_rtcsm2d_match(const dliom_rtcsm_options* o, const double in
         float sum = 0.f;
         for (int64_t i = 0; i < n; ++i) {
           const int x = cx[i] + xo, y = cy[i] + yo;
-          sum += lim.Contains(x, y) ? table.probability[cells[static_cast<size_t>(num_x_cells) * y + x]] : 0.1f;
+          sum += lim.Contains(x, y) ? table.probability[cells[static_cast<size_t>(num_x_cells) * y + x]] : dliom::kMinProbability;
         }
         float sc = sum / static_cast<float>(n);
         const double px = -yo * resolution, py = -xo * resolution;

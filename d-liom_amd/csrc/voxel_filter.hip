@@ -283,7 +283,6 @@ struct VfScratch {
   int max_lengths;
 };
 
-static size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 // `lengths`: the most edge lengths one insert launch of this call will carry.
 static int carve_scratch(dliom_ctx* ctx, int64_t n, int lengths, VfScratch* s) {

@@ -24,21 +24,13 @@
 
 #include "device_common.h"
 #include "host_math.h"
+#include "probability_values.h"
 
 namespace dliom {
 namespace {
 
-// probability_values.h:32-44: kMinProbability, kMaxProbability; probability_values.cc:27-36 ValueToProbability
-constexpr float kMinProbability = 0.1f;
-constexpr float kMaxProbability = 1.f - kMinProbability;
 constexpr float kObstructedLimit = 0.501f;  // kXrayObstructedCellProbabilityLimit, submap_3d.cc:88, 405
 constexpr int kNumLogOddsSteps = 254;       // ProbabilityToLogOddsInteger steps up 254 times from 1 to 255
-
-inline float host_value_to_probability(int v) {  // core.hip value_to_probability (the reference's table entries)
-  if (v == 0) return kMinProbability;
-  const float kScale = (kMaxProbability - kMinProbability) / 32766.f;
-  return v * kScale + (kMinProbability - kScale);
-}
 
 // mapping/submaps.h:37-52 with glibc's logf, evaluated at run time (std::log(float) -> logf).
 float host_logit(float p) { return std::log(p / (1.f - p)); }
@@ -279,12 +271,10 @@ __global__ void xray_image_kernel(PixelArgs a, float gain) {
   a.out[p] = static_cast<uint8_t>(static_cast<unsigned>(lround_away((sum - kMinProbability) * gain)));
 }
 
-inline unsigned blocks_of(int64_t n, int threads) { return static_cast<unsigned>((n + threads - 1) / threads); }
-inline size_t align256(size_t b) { return (b + 255) & ~size_t{255}; }
 
 unsigned obstructed_threshold() {
   for (int v = 1; v < 32768; ++v)
-    if (!(host_value_to_probability(v) < kObstructedLimit)) return static_cast<unsigned>(v);
+    if (!(dliom::value_to_probability(v) < kObstructedLimit)) return static_cast<unsigned>(v);
   return 32768u;
 }
 
@@ -375,8 +365,7 @@ int run_xray(const dliom_grid* g, const XrayTransform& T, bool texture, uint8_t*
   DLIOM_HIP_TRY(hipGetLastError());
   DLIOM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(b2 + o_tmp, sort2_bytes, pk, pk_out, pay, pay_out, static_cast<int>(n), 0,
                                                    end_bit, st));
-  const float scale = (kMaxProbability - kMinProbability) / 32766.f;
-  PixelArgs a{pk_out, pay_out, static_cast<int>(n), pixels, scale, kMinProbability - scale, steps, img};
+  PixelArgs a{pk_out, pay_out, static_cast<int>(n), pixels, kValueToProbabilityScale, kValueToProbabilityOffset, steps, img};
   if (texture) {
     hipLaunchKernelGGL(xray_texture_kernel, dim3(blocks_of(pixels, 256)), dim3(256), 0, st, a);
   } else {
