@@ -25,10 +25,12 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <chrono>
 #include <deque>
 #include <functional>
@@ -170,6 +172,18 @@ class Rigid3d {
  private:
   Vector3d t_;
   Quaterniond q_;
+};
+// transform::Rigid3f, the part the X-ray stage uses: [tx, ty, tz] and (w, x, y, z)
+struct Rigid3f {
+  float t[3] = {0.f, 0.f, 0.f};
+  float wxyz[4] = {1.f, 0.f, 0.f, 0.f};
+  Rigid3f() {}
+  Rigid3f(float tx, float ty, float tz, float w, float x, float y, float z) : t{tx, ty, tz}, wxyz{w, x, y, z} {}
+  explicit Rigid3f(const Rigid3d& d)  // Rigid3d::cast<float>()
+      : t{static_cast<float>(d.translation().v[0]), static_cast<float>(d.translation().v[1]), static_cast<float>(d.translation().v[2])},
+        wxyz{static_cast<float>(d.rotation().wxyz[0]), static_cast<float>(d.rotation().wxyz[1]),
+             static_cast<float>(d.rotation().wxyz[2]), static_cast<float>(d.rotation().wxyz[3])} {}
+  std::array<float, 7> ToArray() const { return {{t[0], t[1], t[2], wxyz[0], wxyz[1], wxyz[2], wxyz[3]}}; }
 };
 }  // namespace transform
 
@@ -1241,6 +1255,16 @@ class LocalTrajectoryBuilder3D {
 
 }  // namespace mapping
 
+namespace mapping {
+struct Timespan {  // mapping/detect_floors.h:27-30, common::Time as ticks
+  int64_t start = 0, end = 0;
+};
+struct Floor {  // mapping/detect_floors.h:32-40
+  std::vector<Timespan> timespans;
+  double z = 0.0;
+};
+}  // namespace mapping
+
 // The points-processor pipeline's stages with compute in them (cartographer/io), on the device.  A batch's points go to
 // the device once per stage and phase; intensities and colors stay on the host and are filtered with the survivors'
 // indices, as RemovePoints does (io/points_batch.cc:22-49).
@@ -1256,6 +1280,8 @@ struct PointsBatch {  // io/points_batch.h:36-73: the fields the stages here tou
   std::vector<sensor::Vector3f> points;  // in the map frame
   std::vector<float> intensities;        // optional
   std::vector<FloatColor> colors;        // optional
+  int64_t start_time = 0;                // common::Time (ticks) of the batch's first point (:41)
+  std::string frame_id;                  // the sensor's frame, or empty (:49)
   // Not in the reference: `points` as a stage left them on the device (the range filter and the outlier remover set it),
   // so that the next device stage does not upload them again.  Whoever changes `points` resets it (KeepPoints does).
   std::shared_ptr<internal::DeviceCloud> device_points;
@@ -1274,7 +1300,13 @@ class PointsProcessor {  // io/points_processor.h:29-52
 
 namespace internal {
 struct DeviceCloud {
+  // clouds this process has uploaded from host points so far (a stage that reuses device_points adds nothing)
+  static std::atomic<int64_t>& Uploads() {
+    static std::atomic<int64_t> uploads{0};
+    return uploads;
+  }
   DeviceCloud(Context* context, const std::vector<sensor::Vector3f>& points) : context(context) {
+    ++Uploads();
     Check(dliom_cloud_create(context->get(), points.empty() ? nullptr : &points[0].x, static_cast<int64_t>(points.size()), &cloud),
           "dliom_cloud_create");
   }
@@ -1565,6 +1597,186 @@ class RosMapWritingPointsProcessor : public PointsProcessor {
   PointsProcessor* const next_;
   FileWriterFactory file_writer_factory_;
   internal::ProbabilityGridOnDevice grid_;
+};
+
+// io/coloring_points_processor.{h,cc}: "color_points".  Host code: it writes batch->colors and leaves the points alone,
+// so what a stage before left on the device stays valid.
+class ColoringPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "color_points";
+  ColoringPointsProcessor(const FloatColor& color, const std::string& frame_id, PointsProcessor* next)
+      : color_(color), frame_id_(frame_id), next_(next) {}
+  // FromDictionary's ToFloatColor(Uint8Color) (io/color.h:40,46-49): c / 255.f
+  static FloatColor FromUint8(uint8_t r, uint8_t g, uint8_t b) { return FloatColor{{r / 255.f, g / 255.f, b / 255.f}}; }
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:48-56
+    if (batch->frame_id == frame_id_) batch->colors.assign(batch->points.size(), color_);
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override { return next_->Flush(); }
+
+ private:
+  const FloatColor color_;
+  const std::string frame_id_;
+  PointsProcessor* const next_;
+};
+
+// io/intensity_to_color_points_processor.{h,cc}: "intensity_to_color"
+class IntensityToColorPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "intensity_to_color";
+  IntensityToColorPointsProcessor(float min_intensity, float max_intensity, const std::string& frame_id, PointsProcessor* next)
+      : min_intensity_(min_intensity), max_intensity_(max_intensity), frame_id_(frame_id), next_(next) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:47-60
+    if (!batch->intensities.empty() && (frame_id_.empty() || batch->frame_id == frame_id_)) {
+      batch->colors.clear();
+      for (const float intensity : batch->intensities) {
+        const float scaled = (intensity - min_intensity_) / (max_intensity_ - min_intensity_);
+        const float gray = scaled > 1.f ? 1.f : (scaled < 0.f ? 0.f : scaled);  // common::Clamp(value, 0.f, 1.f)
+        batch->colors.push_back(FloatColor{{gray, gray, gray}});
+      }
+    }
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override { return next_->Flush(); }
+
+ private:
+  const float min_intensity_, max_intensity_;
+  const std::string frame_id_;
+  PointsProcessor* const next_;
+};
+
+// io/xray_points_processor.{h,cc}: "write_xray_image".  One device aggregator per floor (one without floors) and the
+// reference's single bounding box over all of them.  Flush hands every image to `sink` as io::Image's pixels
+// (0xFF000000 | r << 16 | g << 8 | b, row-major) under the reference's file name; PNG encoding, cairo's trajectory
+// drawing (DrawTrajectories::kNo here; VoxelIndexToPixel is what a caller's DrawTrajectory needs) and DetectFloors stay
+// with the caller.
+class XRayPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "write_xray_image";
+  struct XRayImage {
+    std::string filename;
+    int width = 0, height = 0;
+    std::vector<uint32_t> pixels;
+  };
+  using ImageSink = std::function<void(const XRayImage& image)>;
+  XRayPointsProcessor(double voxel_size, const transform::Rigid3f& transform, const std::vector<mapping::Floor>& floors,
+                      const std::string& output_filename, ImageSink sink, PointsProcessor* next, Context* context = nullptr)
+      : next_(next),
+        context_(context != nullptr ? context : Context::ForThisThread()),
+        floors_(floors),
+        output_filename_(output_filename),
+        sink_(std::move(sink)) {
+    const std::array<float, 7> t = transform.ToArray();
+    aggregations_.resize(floors_.empty() ? 1 : floors_.size(), nullptr);  // .cc:112-115
+    for (dliom_points_xray*& a : aggregations_)
+      Check(dliom_points_xray_create(context_->get(), voxel_size, t.data(), &a), "dliom_points_xray_create");
+  }
+  ~XRayPointsProcessor() override {
+    for (dliom_points_xray* a : aggregations_)
+      if (a != nullptr) dliom_points_xray_destroy(a);
+  }
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:215-228
+    if (floors_.empty()) {
+      Insert(*batch, aggregations_[0]);
+    } else {
+      for (size_t i = 0; i < floors_.size(); ++i) {
+        if (!ContainedIn(batch->start_time, floors_[i].timespans)) continue;
+        Insert(*batch, aggregations_[i]);
+      }
+    }
+    next_->Process(std::move(batch));
+  }
+
+  FlushResult Flush() override {  // .cc:230-253
+    if (floors_.empty()) {
+      WriteVoxels(aggregations_[0], output_filename_ + ".png");
+    } else {
+      for (size_t i = 0; i < floors_.size(); ++i) WriteVoxels(aggregations_[i], output_filename_ + std::to_string(i) + ".png");
+    }
+    return internal::FlushLastStage(next_, "X-Ray generation must be configured to occur after any stages that require "
+                                           "multiple passes.");
+  }
+
+  // bounding_box_ over every aggregation; false while it is empty
+  bool BoundingBox(int32_t box_min[3], int32_t box_max[3]) const {
+    bool any = false;
+    for (const dliom_points_xray* a : aggregations_) {
+      int32_t lo[3], hi[3];
+      int empty = 1;
+      Check(dliom_points_xray_bounding_box(a, lo, hi, &empty), "dliom_points_xray_bounding_box");
+      if (empty) continue;
+      for (int k = 0; k < 3; ++k) {
+        box_min[k] = any ? std::min(box_min[k], lo[k]) : lo[k];
+        box_max[k] = any ? std::max(box_max[k], hi[k]) : hi[k];
+      }
+      any = true;
+    }
+    return any;
+  }
+  // voxel_index_to_pixel (.cc:152-157) of a cell index in the current bounding box; false while the box is empty
+  bool VoxelIndexToPixel(const int32_t index[3], int32_t pixel[2]) const {
+    int32_t lo[3], hi[3];
+    if (!BoundingBox(lo, hi)) return false;
+    pixel[0] = hi[1] - index[1];
+    pixel[1] = hi[2] - index[2];
+    return true;
+  }
+  const std::vector<dliom_points_xray*>& aggregations() const { return aggregations_; }
+
+ private:
+  static bool ContainedIn(int64_t time, const std::vector<mapping::Timespan>& timespans) {  // .cc:86-94
+    for (const mapping::Timespan& timespan : timespans)
+      if (timespan.start <= time && time <= timespan.end) return true;
+    return false;
+  }
+  void Insert(const PointsBatch& batch, dliom_points_xray* aggregation) {  // .cc:195-213
+    if (!batch.colors.empty() && batch.colors.size() < batch.points.size()) {
+      std::fprintf(stderr, "Check failed: batch.colors.at(i)\n");  // std::out_of_range in the reference
+      std::abort();
+    }
+    const std::shared_ptr<internal::DeviceCloud> points = internal::PointsOnDevice(context_, batch);
+    // colours beyond the last point are never read (.cc:206-207)
+    int64_t num_colors = static_cast<int64_t>(std::min(batch.colors.size(), batch.points.size()));
+    // one colour for the whole batch (what ColoringPointsProcessor leaves) needs no per-point colours on the device
+    if (num_colors > 1 && std::all_of(batch.colors.begin(), batch.colors.begin() + num_colors,
+                                      [&](const FloatColor& c) { return SameBits(c, batch.colors[0]); }))
+      num_colors = 1;
+    Check(dliom_points_xray_insert(aggregation, points->cloud, num_colors > 0 ? batch.colors[0].data() : nullptr, num_colors),
+          "dliom_points_xray_insert");
+  }
+  static bool SameBits(const FloatColor& a, const FloatColor& b) {
+    uint32_t x[3], y[3];
+    std::memcpy(x, a.data(), 12);
+    std::memcpy(y, b.data(), 12);
+    return x[0] == y[0] && x[1] == y[1] && x[2] == y[2];
+  }
+  void WriteVoxels(const dliom_points_xray* aggregation, const std::string& filename) {  // .cc:144-193
+    int32_t lo[3], hi[3];
+    if (!BoundingBox(lo, hi)) {
+      std::fprintf(stderr, "Not writing output: bounding box is empty.\n");  // LOG(WARNING)
+      return;
+    }
+    XRayImage image;
+    image.filename = filename;
+    int32_t w = 0, h = 0;
+    Check(dliom_points_xray_draw(aggregation, lo, hi, nullptr, 0, &w, &h), "dliom_points_xray_draw");
+    image.pixels.resize(static_cast<size_t>(w) * static_cast<size_t>(h));
+    Check(dliom_points_xray_draw(aggregation, lo, hi, image.pixels.data(), static_cast<int64_t>(image.pixels.size()), &w, &h),
+          "dliom_points_xray_draw");
+    image.width = w;
+    image.height = h;
+    sink_(image);
+  }
+
+  PointsProcessor* const next_;
+  Context* const context_;
+  const std::vector<mapping::Floor> floors_;
+  const std::string output_filename_;
+  ImageSink sink_;
+  std::vector<dliom_points_xray*> aggregations_;
 };
 
 }  // namespace io

@@ -829,6 +829,7 @@ int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out) {
   out->mirrors_refused = l.mirrors_refused;
   out->outlier_table_bytes = l.outlier_table_bytes;
   out->probability_grid_bytes = l.probability_grid_bytes;
+  out->points_xray_bytes = l.points_xray_bytes;
   const dliom::DevBuf* bufs[] = {&ctx->points, &ctx->cand, &ctx->sums, &ctx->bounds, &ctx->rescore, &ctx->partials, &ctx->misc,
                                  &ctx->sort_tmp, &ctx->voxel, &ctx->box_tables, &ctx->box_counters, &ctx->box_extents,
                                  &ctx->csm_arrivals, &ctx->box_error, &ctx->deskew_flags, &ctx->zero_words, &ctx->aux_scratch,

@@ -80,6 +80,7 @@ struct MemoryLedger {
   int64_t mirror_budget = 0;   // 0: no cap.  A mirror that would take mirror_bytes above it is not built: the correlative
   int64_t outlier_table_bytes = 0;  // the voxel tables of the context's outlier removers (outlier.hip)
   int64_t probability_grid_bytes = 0;  // the 2D probability grids and 2D inserters of the context (probability_grid.hip)
+  int64_t points_xray_bytes = 0;  // the tables and scratch of the context's X-ray aggregators (points_xray.hip)
   int64_t mirrors_refused = 0; // matcher then runs its leaf-table kernel on that grid (same results, slower)
 };
 

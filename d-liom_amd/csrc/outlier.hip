@@ -20,7 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "device_common.h"
+#include "voxel_hash.h"
 
 // Leaf edge 2^kLeafBits voxels.  3: the layout that ships.  0 turns the table into a flat hash of single voxels (an
 // experiment build: tools/outlier_bench.py --lib, DESIGN.md section 3.10 for the comparison).
@@ -35,10 +35,6 @@ constexpr int kLeafBits = DLIOM_OUTLIER_LEAF_BITS;
 constexpr int kLeafCells = 1 << (3 * kLeafBits);
 constexpr int kLeafInts = 2 * kLeafCells;  // {hits, rays} per cell
 constexpr int kLeafMask = (1 << kLeafBits) - 1;
-// CHECK_LE(new_bits, 8) (hybrid_grid.h:389): 64 << 8 voxels per axis, indices [-8192, 8191] (hybrid_grid.h:263-268)
-constexpr int kMinIndex = -8192, kMaxIndex = 8191;
-constexpr uint64_t kEmptyKey = ~uint64_t{0};
-constexpr unsigned kNoSlot = 0xFFFFFFFFu;
 constexpr unsigned kFlagNonFinite = 1u, kFlagExtent = 2u, kFlagRayTooLong = 4u;
 constexpr int kBlock = 256;
 
@@ -53,25 +49,6 @@ struct TableView {
   float resolution;  // float(voxel_size): HybridGridBase(const float resolution)
 };
 
-__host__ __device__ inline unsigned hash_key(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return static_cast<unsigned>(k);
-}
-
-// GetCellIndex of one coordinate (hybrid_grid.h:430-434) where the result is a voxel the grid can hold; false
-// otherwise (and for NaN).  |q| < 16384 keeps the conversion to int defined.
-__device__ __forceinline__ bool cell_in_extent(float p, float resolution, int* cell) {
-  const float q = p / resolution;
-  if (!(fabsf(q) < 16384.f)) return false;
-  const int c = lround_away(q);
-  *cell = c;
-  return c >= kMinIndex && c <= kMaxIndex;
-}
-
 __device__ __forceinline__ uint64_t leaf_key(int cx, int cy, int cz) {
   const int bias = 8192 >> kLeafBits;
   return (static_cast<uint64_t>((cz >> kLeafBits) + bias) << 28) | (static_cast<uint64_t>((cy >> kLeafBits) + bias) << 14) |
@@ -83,18 +60,7 @@ __device__ __forceinline__ int cell_in_leaf(int cx, int cy, int cz) {
 
 // slot of the leaf `key`, kNoSlot if the table has none; *probes += entries read
 __device__ __forceinline__ unsigned find_leaf(const TableView& t, uint64_t key, unsigned* probes) {
-  unsigned h = hash_key(key) & t.mask;
-  for (;;) {  // ends: the table is at most half full
-    const uint64_t k = t.keys[h];
-    ++*probes;
-    if (k == key) return t.slots[h];
-    if (k == kEmptyKey) return kNoSlot;
-    h = (h + 1u) & t.mask;
-  }
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  return fabsf(x) <= 3.4028234e38f && fabsf(y) <= 3.4028234e38f && fabsf(z) <= 3.4028234e38f;  // false for NaN
+  return hash_find(t.keys, t.slots, t.mask, key, probes);
 }
 
 // ---- pass 1 -----------------------------------------------------------------------------------------------------
@@ -123,23 +89,7 @@ __global__ __launch_bounds__(kBlock) void outlier_insert_leaves_kernel(const flo
   int cx, cy, cz;
   if (!cell_in_extent(x[i], t.resolution, &cx) || !cell_in_extent(y[i], t.resolution, &cy) || !cell_in_extent(z[i], t.resolution, &cz))
     return;  // (flagged by the check kernel)
-  const uint64_t key = leaf_key(cx, cy, cz);
-  unsigned h = hash_key(key) & t.mask;
-  for (;;) {
-    uint64_t k = t.keys[h];
-    if (k == kEmptyKey) {
-      k = atomicCAS(reinterpret_cast<unsigned long long*>(&t.keys[h]), static_cast<unsigned long long>(kEmptyKey),
-                    static_cast<unsigned long long>(key));
-      if (k == kEmptyKey) {
-        const unsigned slot = atomicAdd(&words[kWordLeaves], 1u);
-        t.slots[h] = slot;
-        slot_key[slot] = key;
-        return;
-      }
-    }
-    if (k == key) return;
-    h = (h + 1u) & t.mask;
-  }
+  hash_claim(t.keys, t.slots, t.mask, leaf_key(cx, cy, cz), &words[kWordLeaves], slot_key);
 }
 
 __global__ __launch_bounds__(kBlock) void outlier_mark_hits_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -159,17 +109,7 @@ __global__ __launch_bounds__(kBlock) void outlier_mark_hits_kernel(const float* 
 __global__ __launch_bounds__(kBlock) void outlier_rehash_kernel(const uint64_t* __restrict__ slot_key, unsigned leaves, TableView t) {
   const unsigned s = blockIdx.x * kBlock + threadIdx.x;
   if (s >= leaves) return;
-  const uint64_t key = slot_key[s];
-  unsigned h = hash_key(key) & t.mask;
-  for (;;) {
-    if (t.keys[h] == kEmptyKey &&
-        atomicCAS(reinterpret_cast<unsigned long long*>(&t.keys[h]), static_cast<unsigned long long>(kEmptyKey),
-                  static_cast<unsigned long long>(key)) == static_cast<unsigned long long>(kEmptyKey)) {
-      t.slots[h] = s;
-      return;
-    }
-    h = (h + 1u) & t.mask;
-  }
+  hash_place(t.keys, t.slots, t.mask, slot_key[s], s);
 }
 
 // ---- pass 2 -----------------------------------------------------------------------------------------------------

@@ -50,6 +50,7 @@ _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u16p = C.POINTER(C.c_uint16)
+_u32p = C.POINTER(C.c_uint32)
 _u64p = C.POINTER(C.c_uint64)
 _vp = C.c_void_p
 
@@ -189,7 +190,7 @@ class MemoryStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("grids", "leaf_table_bytes", "leaf_pool_bytes", "mirror_bytes", "mirror_budget_bytes",
                                          "mirrors_refused", "scratch_bytes", "leaf_capacity", "leaf_slots_upper_bound")] + [
                                              ("mirror_windowed", C.c_int), ("outlier_table_bytes", C.c_int64),
-                                             ("probability_grid_bytes", C.c_int64)]
+                                             ("probability_grid_bytes", C.c_int64), ("points_xray_bytes", C.c_int64)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -198,6 +199,14 @@ class MemoryStats(C.Structure):
 class OutlierStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("voxels", "leaves", "leaf_capacity", "table_capacity", "table_bytes", "growths",
                                          "samples_walked", "probes")] + [("phase", C.c_int)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class PointsXrayStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("voxels", "columns", "leaves", "table_bytes", "probes", "longest_segment", "growths",
+                                         "inserts", "points")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -274,6 +283,15 @@ SYMBOLS = [
     ("dliom_outlier_remover_filter", C.c_int, [_vp, _vp, C.POINTER(_vp), _i32p, C.c_int64, _i64p]),
     ("dliom_outlier_remover_voxels", C.c_int, [_vp, _i32p, _i32p, _i32p, C.c_int64, _i64p]),
     ("dliom_outlier_remover_stats", C.c_int, [_vp, C.POINTER(OutlierStats)]),
+    ("dliom_points_xray_create", C.c_int, [_vp, C.c_double, _f32p, C.POINTER(_vp)]),
+    ("dliom_points_xray_destroy", C.c_int, [_vp]),
+    ("dliom_points_xray_insert", C.c_int, [_vp, _vp, _f32p, C.c_int64]),
+    ("dliom_points_xray_bounding_box", C.c_int, [_vp, _i32p, _i32p, C.POINTER(C.c_int)]),
+    ("dliom_points_xray_columns", C.c_int, [_vp, _i32p, _f32p, _u32p, _u32p, C.c_int64, _i64p]),
+    ("dliom_points_xray_voxels", C.c_int, [_vp, _i32p, C.c_int64, _i64p]),
+    ("dliom_points_xray_draw", C.c_int, [_vp, _i32p, _i32p, _u32p, C.c_int64, _i32p, _i32p]),
+    ("dliom_points_xray_stats", C.c_int, [_vp, C.POINTER(PointsXrayStats)]),
+    ("dliom_points_xray_pixel", C.c_int, [C.c_uint32, C.c_uint32, _f32p, _u32p]),
     ("dliom_cloud_min_max_range_filter", C.c_int, [_vp, _vp, _f32p, C.c_double, C.c_double, C.POINTER(_vp), _i32p, C.c_int64,
                                                    _i64p]),
     ("dliom_rtcsm3d_match", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _f32p, C.c_int64, _vp, _f64p, _f32p]),
@@ -691,6 +709,93 @@ class OutlierRemover:
     def close(self):
         if getattr(self, "h", None):
             self._L.dliom_outlier_remover_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def points_xray_pixel(occupied, max_occupied, mean_rgb):
+    """dliom_points_xray_pixel: one pixel of IntoImage on the host's libm (io::Image's 0xFFrrggbb)."""
+    out = C.c_uint32()
+    _check(load_library().dliom_points_xray_pixel(int(occupied), int(max_occupied), _p(_f32(mean_rgb), _f32p), C.byref(out)),
+           "dliom_points_xray_pixel")
+    return int(out.value)
+
+
+class PointsXray:
+    """One Aggregation of io::XRayPointsProcessor on the device (dliom_points_xray): occupied voxels and per-column colour
+    sums, equal to the reference's bit for bit.  transform7 = [tx, ty, tz, qw, qx, qy, qz] (a Rigid3f)."""
+
+    def __init__(self, ctx, voxel_size, transform7=(0, 0, 0, 1, 0, 0, 0)):
+        self._L = ctx._L
+        self.ctx = ctx
+        h = _vp()
+        _check(self._L.dliom_points_xray_create(ctx.h, float(voxel_size), _p(_f32(transform7), _f32p), C.byref(h)),
+               "dliom_points_xray_create")
+        self.h = h
+
+    def insert(self, cloud, colors=None):
+        """colors: None (the reference's default black), one (r, g, b) for the batch, or float32 (n, 3) per point."""
+        if colors is None:
+            _check(self._L.dliom_points_xray_insert(self.h, cloud.h, None, 0), "dliom_points_xray_insert")
+            return
+        c = _f32(colors).reshape(-1, 3)
+        _check(self._L.dliom_points_xray_insert(self.h, cloud.h, _p(c, _f32p), len(c)), "dliom_points_xray_insert")
+
+    def bounding_box(self):
+        """-> (min int32[3], max int32[3]) of the cell indices inserted, or None while empty."""
+        lo, hi, empty = np.zeros(3, dtype=np.int32), np.zeros(3, dtype=np.int32), C.c_int()
+        _check(self._L.dliom_points_xray_bounding_box(self.h, _p(lo, _i32p), _p(hi, _i32p), C.byref(empty)),
+               "dliom_points_xray_bounding_box")
+        return None if empty.value else (lo, hi)
+
+    def columns(self):
+        """column_data sorted by (y, z) -> (yz int32 (n, 2), sums float32 (n, 3), counts uint32, occupied voxels uint32)."""
+        n = C.c_int64()
+        _check(self._L.dliom_points_xray_columns(self.h, None, None, None, None, 0, C.byref(n)), "dliom_points_xray_columns")
+        yz, sums = np.zeros((n.value, 2), dtype=np.int32), np.zeros((n.value, 3), dtype=np.float32)
+        counts, occupied = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        if n.value > 0:
+            _check(self._L.dliom_points_xray_columns(self.h, _p(yz, _i32p), _p(sums, _f32p), _p(counts, _u32p), _p(occupied, _u32p),
+                                                     n.value, C.byref(n)), "dliom_points_xray_columns")
+        return yz, sums, counts, occupied
+
+    def voxels(self):
+        """The occupied voxels sorted by (z, y, x) -> int32 (n, 3)."""
+        n = C.c_int64()
+        _check(self._L.dliom_points_xray_voxels(self.h, None, 0, C.byref(n)), "dliom_points_xray_voxels")
+        xyz = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value > 0:
+            _check(self._L.dliom_points_xray_voxels(self.h, _p(xyz, _i32p), n.value, C.byref(n)), "dliom_points_xray_voxels")
+        return xyz
+
+    def draw(self, box=None):
+        """IntoImage in `box` ((min, max) of cell indices; None: the aggregator's own) -> uint32 (height, width) 0xFFrrggbb;
+        (0, 0) for an empty box."""
+        lo = hi = None
+        if box is not None:
+            lo, hi = np.ascontiguousarray(box[0], dtype=np.int32), np.ascontiguousarray(box[1], dtype=np.int32)
+        args = (None, None) if box is None else (_p(lo, _i32p), _p(hi, _i32p))
+        w, h = C.c_int32(), C.c_int32()
+        _check(self._L.dliom_points_xray_draw(self.h, args[0], args[1], None, 0, C.byref(w), C.byref(h)), "dliom_points_xray_draw")
+        image = np.zeros((h.value, w.value), dtype=np.uint32)
+        if image.size > 0:
+            _check(self._L.dliom_points_xray_draw(self.h, args[0], args[1], _p(image, _u32p), image.size, C.byref(w), C.byref(h)),
+                   "dliom_points_xray_draw")
+        return image
+
+    def stats(self):
+        s = PointsXrayStats()
+        _check(self._L.dliom_points_xray_stats(self.h, C.byref(s)), "dliom_points_xray_stats")
+        return s.as_dict()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_points_xray_destroy(self.h)
             self.h = None
 
     def __del__(self):

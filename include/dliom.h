@@ -107,6 +107,7 @@ typedef struct dliom_memory_stats {
   int mirror_windowed;             /* grid only */
   int64_t outlier_table_bytes;     /* context only: the voxel tables of its dliom_outlier_remover objects */
   int64_t probability_grid_bytes;  /* the dense cells, tables and words of dliom_probability_grid objects (2D) */
+  int64_t points_xray_bytes;       /* context only: tables and scratch of its dliom_points_xray objects */
 } dliom_memory_stats;
 int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out);
 int dliom_ctx_set_mirror_budget(dliom_ctx* ctx, int64_t bytes);
@@ -577,6 +578,65 @@ int dliom_cloud_min_max_range_filter(dliom_ctx* ctx, const dliom_cloud* in, cons
 int dliom_voxel_filter(float size, const float* points_xyz, int64_t n, float* out_xyz, int64_t* num_out);
 int dliom_adaptive_voxel_filter(const dliom_adaptive_voxel_filter_options* options, const float* points_xyz,
                                 int64_t n, float* out_xyz, int64_t* num_out);
+
+/* ---- X-ray images of point clouds (the pipeline action "write_xray_image") ----
+ * io::XRayPointsProcessor (io/xray_points_processor.{h,cc}) projects every batch through a Rigid3f into a
+ * HybridGridBase<bool> of occupied voxels and a std::map<(y, z), ColumnData {float sum_r, sum_g, sum_b; uint32 count}>
+ * (.h:61-71), and at Flush paints one pixel per column (y, z): its mean colour, saturated by the logarithm of the
+ * number of occupied voxels in the column.  A dliom_points_xray is one such Aggregation in HBM.  Voxels, counts and the
+ * bounding box are integers; the colour sums are the reference's sequential float sums in point order, batch after
+ * batch, bit for bit -- so the tables and the image equal the reference's exactly.
+ *
+ * Where the reference aborts or is undefined, insert returns an error and leaves the aggregator as it was:
+ *   DLIOM_ERR_GRID_EXTENT       a transformed point whose cell index leaves [-8192, 8191] (hybrid_grid.h:389)
+ *   DLIOM_ERR_INVALID_ARGUMENT  a transformed point that is not finite (lround of it is undefined)
+ * NULL pointers, a voxel_size that is not finite and positive (as double and as float), a non-finite transform, a
+ * colour count other than 0, 1 or the number of points and a negative capacity are refused with
+ * DLIOM_ERR_INVALID_ARGUMENT before anything touches a device.  Colours are not checked: non-finite colours give
+ * unspecified pixels, as they do in the reference.
+ * The pixels are io::Image's (image.h): 0xFF000000 | r << 16 | g << 8 | b, row-major.  PNG encoding, cairo and
+ * DrawTrajectory stay with the caller. */
+typedef struct dliom_points_xray dliom_points_xray;
+typedef struct dliom_points_xray_statistics {
+  int64_t voxels;           /* occupied voxels */
+  int64_t columns;          /* slots of the column table (entries of column_data, see dliom_points_xray_columns) */
+  int64_t leaves;           /* 8x8x8 blocks of voxels in use (64 bytes each) */
+  int64_t table_bytes;      /* HBM held: both hash tables, leaf masks, column arrays, counters, scratch */
+  int64_t probes;           /* hash-table entries read by the inserts so far */
+  int64_t longest_segment;  /* most points of one batch in one column so far: the length of the longest ordered sum */
+  int64_t growths;          /* reallocations of a table or a pool since creation */
+  int64_t inserts, points;  /* successful non-empty inserts and their points */
+} dliom_points_xray_statistics;
+/* XRayPointsProcessor(voxel_size, transform, ...) (.cc:98-116), one Aggregation: HybridGridBase<bool>(voxel_size) takes
+ * float(voxel_size); transform7 = [tx, ty, tz, qw, qx, qy, qz] of transform_. */
+int dliom_points_xray_create(dliom_ctx* ctx, double voxel_size, const float transform7[7], dliom_points_xray** out);
+int dliom_points_xray_destroy(dliom_points_xray* xray);
+/* Insert (.cc:195-213).  num_colors 0: batch.colors is empty, kDefaultColor black; 1: colors_rgb[0..2] for every point
+ * (what ColoringPointsProcessor produces); points' size: colors_rgb holds r, g, b per point.  colors_rgb is a host
+ * pointer (page-locked memory of dliom_host_register is copied from without staging) and is free when the call returns. */
+int dliom_points_xray_insert(dliom_points_xray* xray, const dliom_cloud* points, const float* colors_rgb, int64_t num_colors);
+/* bounding_box_ (.cc:203) of this aggregator's inserts: cell indices; *empty as AlignedBox3i::isEmpty (min, max then
+ * hold INT32_MAX, INT32_MIN).  The reference keeps one box for all floors: the caller merges. */
+int dliom_points_xray_bounding_box(const dliom_points_xray* xray, int32_t box_min[3], int32_t box_max[3], int* empty);
+/* column_data, sorted by (y, z) like the std::map: yz 2 * capacity ints, sums_rgb 3 * capacity floats, counts and
+ * occupied (the number of occupied voxels of the column, .cc:174) capacity each.  All four NULL: *count only.  Too small
+ * a capacity: *count and DLIOM_ERR_CAPACITY.  (An insert that fails with DLIOM_ERR_HIP while its pools grow -- out of
+ * memory -- inserts none of its points; the column keys it had claimed hold no points and are not listed.) */
+int dliom_points_xray_columns(const dliom_points_xray* xray, int32_t* yz, float* sums_rgb, uint32_t* counts, uint32_t* occupied,
+                              int64_t capacity, int64_t* count);
+/* The occupied voxels (aggregation.voxels, .cc:164), sorted by (z, y, x); xyz 3 * capacity ints, NULL: *count only. */
+int dliom_points_xray_voxels(const dliom_points_xray* xray, int32_t* xyz, int64_t capacity, int64_t* count);
+/* WriteVoxels + IntoImage (.cc:46-84, 144-175) in the box [box_min, box_max] of cell indices (both NULL: the
+ * aggregator's own): width = sizes[1] + 1, height = sizes[2] + 1, pixel (box_max[1] - y, box_max[2] - z).  *width and
+ * *height are always filled; argb NULL: sizes only; capacity (pixels) too small: DLIOM_ERR_CAPACITY.  An empty box gives
+ * DLIOM_OK and width = height = 0 ("Not writing output", .cc:146-149).  A box that does not hold every voxel of the
+ * aggregator is refused (the reference would write outside its matrix). */
+int dliom_points_xray_draw(const dliom_points_xray* xray, const int32_t box_min[3], const int32_t box_max[3], uint32_t* argb,
+                           int64_t capacity, int32_t* width, int32_t* height);
+int dliom_points_xray_stats(const dliom_points_xray* xray, dliom_points_xray_statistics* out);
+/* One pixel of IntoImage on the host (.cc:64-81, io/color.h:35-38): a column of `occupied` voxels in an image whose
+ * fullest column has max_occupied, with the column's mean colour.  occupied == 0: white.  What the device paints. */
+int dliom_points_xray_pixel(uint32_t occupied, uint32_t max_occupied, const float mean_rgb[3], uint32_t* argb);
 
 /* ---- 2D probability grid of the export pipeline (the actions "write_probability_grid" and "write_ros_map") ----
  * io::ProbabilityGridPointsProcessor (io/probability_grid_points_processor.{h,cc}) and
