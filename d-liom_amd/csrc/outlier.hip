@@ -35,7 +35,7 @@ constexpr int kLeafBits = DLIOM_OUTLIER_LEAF_BITS;
 constexpr int kLeafCells = 1 << (3 * kLeafBits);
 constexpr int kLeafInts = 2 * kLeafCells;  // {hits, rays} per cell
 constexpr int kLeafMask = (1 << kLeafBits) - 1;
-constexpr unsigned kFlagNonFinite = 1u, kFlagExtent = 2u, kFlagRayTooLong = 4u;
+constexpr unsigned kFlagRayTooLong = 4u;  // beside kFlagNonFinite and kFlagExtent
 constexpr int kBlock = 256;
 
 // device words of a remover
@@ -49,14 +49,8 @@ struct TableView {
   float resolution;  // float(voxel_size): HybridGridBase(const float resolution)
 };
 
-__device__ __forceinline__ uint64_t leaf_key(int cx, int cy, int cz) {
-  const int bias = 8192 >> kLeafBits;
-  return (static_cast<uint64_t>((cz >> kLeafBits) + bias) << 28) | (static_cast<uint64_t>((cy >> kLeafBits) + bias) << 14) |
-         static_cast<uint64_t>((cx >> kLeafBits) + bias);
-}
-__device__ __forceinline__ int cell_in_leaf(int cx, int cy, int cz) {
-  return ((cz & kLeafMask) << (2 * kLeafBits)) | ((cy & kLeafMask) << kLeafBits) | (cx & kLeafMask);
-}
+__device__ __forceinline__ uint64_t leaf_key(int cx, int cy, int cz) { return dliom::leaf_key(cx, cy, cz, kLeafBits); }
+__device__ __forceinline__ int cell_in_leaf(int cx, int cy, int cz) { return dliom::cell_in_leaf(cx, cy, cz, kLeafBits); }
 
 // slot of the leaf `key`, kNoSlot if the table has none; *probes += entries read
 __device__ __forceinline__ unsigned find_leaf(const TableView& t, uint64_t key, unsigned* probes) {
@@ -103,13 +97,6 @@ __global__ __launch_bounds__(kBlock) void outlier_mark_hits_kernel(const float* 
   const unsigned slot = find_leaf(t, leaf_key(cx, cy, cz), &probes);
   if (slot == kNoSlot) return;  // (cannot happen: inserted by the launch before)
   atomicAdd(&t.pool[static_cast<size_t>(slot) * kLeafInts + 2 * cell_in_leaf(cx, cy, cz)], 1);  // ++hits (.cc:88)
-}
-
-// the old table's leaves into a larger one
-__global__ __launch_bounds__(kBlock) void outlier_rehash_kernel(const uint64_t* __restrict__ slot_key, unsigned leaves, TableView t) {
-  const unsigned s = blockIdx.x * kBlock + threadIdx.x;
-  if (s >= leaves) return;
-  hash_place(t.keys, t.slots, t.mask, slot_key[s], s);
 }
 
 // ---- pass 2 -----------------------------------------------------------------------------------------------------
@@ -250,9 +237,9 @@ __global__ __launch_bounds__(kBlock) void outlier_emit_voxels_kernel(const int* 
   if (at >= capacity) return;
   const uint64_t lk = slot_key[c / kLeafCells];
   const unsigned in = static_cast<unsigned>(c % kLeafCells);
-  const uint64_t vx = ((lk & 0x3FFFu) << kLeafBits) | (in & kLeafMask);
-  const uint64_t vy = (((lk >> 14) & 0x3FFFu) << kLeafBits) | ((in >> kLeafBits) & kLeafMask);
-  const uint64_t vz = (((lk >> 28) & 0x3FFFu) << kLeafBits) | ((in >> (2 * kLeafBits)) & kLeafMask);
+  const uint64_t vx = ((lk & kKeyMask) << kLeafBits) | (in & kLeafMask);
+  const uint64_t vy = (((lk >> 14) & kKeyMask) << kLeafBits) | ((in >> kLeafBits) & kLeafMask);
+  const uint64_t vz = (((lk >> 28) & kKeyMask) << kLeafBits) | ((in >> (2 * kLeafBits)) & kLeafMask);
   out[at] = VoxelRecord{(vz << 28) | (vy << 14) | vx, pool[2 * c], pool[2 * c + 1]};
 }
 
@@ -327,11 +314,9 @@ int compact_kept(dliom_ctx* ctx, const dliom_cloud* in, const CompactScratch& s,
   return st;
 }
 
-int status_of_flag(unsigned flag) {
-  if (flag & kFlagNonFinite) return DLIOM_ERR_INVALID_ARGUMENT;
-  if (flag & kFlagExtent) return DLIOM_ERR_GRID_EXTENT;
-  if (flag & kFlagRayTooLong) return DLIOM_ERR_RAY_TOO_LONG;
-  return DLIOM_OK;
+int status_of_ray_flag(unsigned flag) {  // the shared bits first
+  const int st = status_of_flag(flag);
+  return st == DLIOM_OK && (flag & kFlagRayTooLong) ? DLIOM_ERR_RAY_TOO_LONG : st;
 }
 
 bool finite_origin(const float o[3]) { return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]); }
@@ -347,67 +332,30 @@ struct dliom_outlier_remover {
   double voxel_size = 0.0;  // voxel_size_ stays double (.h:79)
   float resolution = 0.f;   // voxels_(voxel_size_): HybridGridBase(const float)
   int phase = 1;            // State (.h:59-63)
-  uint64_t* d_keys = nullptr;
-  unsigned* d_slots = nullptr;
-  uint64_t* d_slot_key = nullptr;  // table_capacity / 2 entries: the leaf of a slot
-  int64_t table_capacity = 0;      // entries, a power of two, at least twice the leaves
-  int* d_pool = nullptr;           // leaf_capacity leaves; those past `leaves` are zero
+  KeyTable table;         // leaf key -> slot
+  int* d_pool = nullptr;  // leaf_capacity leaves; those past `leaves` are zero
   int64_t leaf_capacity = 0;
-  int64_t leaves = 0;              // exact: read back by every mark_hits
+  int64_t leaves = 0;  // exact: read back by every mark_hits
   unsigned* d_words = nullptr;
   int64_t growths = 0, booked = 0;
 
-  TableView view() const { return TableView{d_keys, d_slots, static_cast<unsigned>(table_capacity - 1), d_pool, resolution}; }
-  int64_t bytes() const { return table_capacity * 12 + table_capacity / 2 * 8 + leaf_capacity * kLeafInts * 4 + kNumWords * 4; }
+  TableView view() const {
+    const HashView t = table.view();
+    return TableView{t.keys, t.slots, t.mask, d_pool, resolution};
+  }
+  int64_t bytes() const { return table.bytes() + leaf_capacity * kLeafInts * 4 + kNumWords * 4; }
   void book() {
     if (ledger) ledger->outlier_table_bytes += bytes() - booked;
     booked = bytes();
   }
-  int grow_table(int64_t want_leaves);
   int grow_pool(int64_t want_leaves);
 };
-
-// room for `want_leaves` leaves at a load of at most one half; the stream is idle or may be waited for (between launches)
-int dliom_outlier_remover::grow_table(int64_t want_leaves) {
-  if (2 * want_leaves <= table_capacity) return DLIOM_OK;
-  int64_t cap = std::max<int64_t>(table_capacity, 1024);
-  while (cap < 2 * want_leaves) cap <<= 1;
-  if (cap > (int64_t{1} << 31)) return DLIOM_ERR_CAPACITY;
-  uint64_t *keys = nullptr, *slot_key = nullptr;
-  unsigned* slots = nullptr;
-  DLIOM_HIP_TRY(hipMalloc(&keys, cap * 8));
-  DLIOM_HIP_TRY(hipMalloc(&slots, cap * 4));
-  DLIOM_HIP_TRY(hipMalloc(&slot_key, cap / 2 * 8));
-  DLIOM_HIP_TRY(hipMemsetAsync(keys, 0xFF, cap * 8, ctx->stream));
-  if (leaves > 0) {
-    DLIOM_HIP_TRY(hipMemcpyAsync(slot_key, d_slot_key, leaves * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    TableView t{keys, slots, static_cast<unsigned>(cap - 1), d_pool, resolution};
-    hipLaunchKernelGGL(outlier_rehash_kernel, dim3(blocks_of(leaves)), dim3(kBlock), 0, ctx->stream, slot_key,
-                       static_cast<unsigned>(leaves), t);
-    DLIOM_HIP_TRY(hipGetLastError());
-  }
-  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (d_keys) (void)hipFree(d_keys);
-  if (d_slots) (void)hipFree(d_slots);
-  if (d_slot_key) (void)hipFree(d_slot_key);
-  d_keys = keys;
-  d_slots = slots;
-  d_slot_key = slot_key;
-  if (table_capacity > 0) ++growths;
-  table_capacity = cap;
-  book();
-  return DLIOM_OK;
-}
 
 int dliom_outlier_remover::grow_pool(int64_t want_leaves) {
   if (want_leaves <= leaf_capacity) return DLIOM_OK;
   const int64_t cap = std::max<int64_t>(want_leaves, leaf_capacity + leaf_capacity / 2);
   int* pool = nullptr;
-  const size_t leaf_bytes = static_cast<size_t>(kLeafInts) * 4;
-  DLIOM_HIP_TRY(hipMalloc(&pool, cap * leaf_bytes));
-  if (leaves > 0) DLIOM_HIP_TRY(hipMemcpyAsync(pool, d_pool, leaves * leaf_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  DLIOM_HIP_TRY(hipMemsetAsync(reinterpret_cast<char*>(pool) + leaves * leaf_bytes, 0, (cap - leaves) * leaf_bytes, ctx->stream));
-  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  DLIOM_TRY(grown_copy(ctx, d_pool, leaves * kLeafInts, cap * kLeafInts, &pool));
   if (d_pool) (void)hipFree(d_pool);
   d_pool = pool;
   if (leaf_capacity > 0) ++growths;
@@ -431,7 +379,7 @@ int dliom_outlier_remover_create(dliom_ctx* ctx, double voxel_size, dliom_outlie
   r->resolution = static_cast<float>(voxel_size);
   int st = hipMalloc(&r->d_words, kNumWords * 4) == hipSuccess ? DLIOM_OK : DLIOM_ERR_HIP;
   if (st == DLIOM_OK && hipMemsetAsync(r->d_words, 0, kNumWords * 4, ctx->stream) != hipSuccess) st = DLIOM_ERR_HIP;
-  if (st == DLIOM_OK) st = r->grow_table(512);
+  if (st == DLIOM_OK) st = r->table.grow(ctx, 512, 0, &r->growths);
   if (st == DLIOM_OK) st = r->grow_pool(64);
   if (st != DLIOM_OK) {
     dliom_outlier_remover_destroy(r);
@@ -445,9 +393,7 @@ int dliom_outlier_remover_destroy(dliom_outlier_remover* r) {
   if (r == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
   (void)hipSetDevice(r->ctx->device);
   (void)hipStreamSynchronize(r->ctx->stream);
-  if (r->d_keys) (void)hipFree(r->d_keys);
-  if (r->d_slots) (void)hipFree(r->d_slots);
-  if (r->d_slot_key) (void)hipFree(r->d_slot_key);
+  r->table.release();
   if (r->d_pool) (void)hipFree(r->d_pool);
   if (r->d_words) (void)hipFree(r->d_words);
   if (r->ledger) r->ledger->outlier_table_bytes -= r->booked;
@@ -461,17 +407,18 @@ int dliom_outlier_remover_mark_hits(dliom_outlier_remover* r, const dliom_cloud*
   dliom_ctx* ctx = r->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   const unsigned n = static_cast<unsigned>(points->n);
-  DLIOM_TRY(r->grow_table(r->leaves + points->n));  // every hit in a leaf of its own: the bound the call knows
+  // every hit in a leaf of its own: the bound the call knows
+  DLIOM_TRY(r->table.grow(ctx, r->leaves + points->n, r->leaves, &r->growths));
+  r->book();
   const FillJob fill{r->d_words + kWordFlag, 4, 0u};
   DLIOM_TRY(fill_multi(ctx, &fill, 1));
   hipLaunchKernelGGL(outlier_check_hits_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, points->d_x, points->d_y,
                      points->d_z, n, r->resolution, r->d_words);
   hipLaunchKernelGGL(outlier_insert_leaves_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, points->d_x, points->d_y,
-                     points->d_z, n, r->view(), r->d_slot_key, r->d_words);
+                     points->d_z, n, r->view(), r->table.slot_key, r->d_words);
   DLIOM_HIP_TRY(hipGetLastError());
-  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
-  const GatherJob back{r->d_words, 2};  // leaves, flag
-  DLIOM_TRY(gather_and_wait(ctx, &back, 1, host));
+  unsigned host[2];
+  DLIOM_TRY(read_words(ctx, r->d_words, 0, 2, host));  // leaves, flag
   if (host[kWordFlag] != 0u) return status_of_flag(host[kWordFlag]);  // nothing was inserted
   const int64_t leaves = host[kWordLeaves];
   DLIOM_TRY(r->grow_pool(leaves));  // copies the `r->leaves` leaves in use; the new ones are zero
@@ -499,10 +446,9 @@ int dliom_outlier_remover_count_rays(dliom_outlier_remover* r, const float origi
   hipLaunchKernelGGL(outlier_count_rays_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, points->d_x, points->d_y,
                      points->d_z, n, origin[0], origin[1], origin[2], r->voxel_size, r->view(), r->d_words);
   DLIOM_HIP_TRY(hipGetLastError());
-  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
-  const GatherJob back{r->d_words + kWordFlag, 1};
-  DLIOM_TRY(gather_and_wait(ctx, &back, 1, host));
-  if (host[0] != 0u) return status_of_flag(host[0]);  // no ray was walked
+  unsigned flag;
+  DLIOM_TRY(read_words(ctx, r->d_words, kWordFlag, 1, &flag));
+  if (flag != 0u) return status_of_ray_flag(flag);  // no ray was walked
   r->phase = 2;
   return DLIOM_OK;
 }
@@ -529,7 +475,7 @@ int dliom_outlier_remover_filter(dliom_outlier_remover* r, const dliom_cloud* po
   DLIOM_HIP_TRY(hipGetLastError());
   unsigned flag = 0;
   DLIOM_TRY(compact_kept(ctx, points, s, r->d_words + kWordFlag, &flag, kept, kept_index, capacity, num_kept));
-  if (flag != 0u) return status_of_flag(flag);
+  if (flag != 0u) return status_of_flag(flag);  // (non-finite: the only one this pass raises)
   r->phase = 3;
   return DLIOM_OK;
 }
@@ -547,10 +493,9 @@ int dliom_outlier_remover_voxels(const dliom_outlier_remover* r, int32_t* xyz, i
   DLIOM_TRY(fill_multi(ctx, &fill, 1));
   hipLaunchKernelGGL(outlier_count_voxels_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, r->d_pool, cells, r->d_words);
   DLIOM_HIP_TRY(hipGetLastError());
-  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
-  const GatherJob back{r->d_words + kWordCursor, 2};
-  DLIOM_TRY(gather_and_wait(ctx, &back, 1, host));
-  const int64_t total = static_cast<int64_t>(host[0]) | (static_cast<int64_t>(host[1]) << 32);
+  unsigned host[2];
+  DLIOM_TRY(read_words(ctx, r->d_words, kWordCursor, 2, host));
+  const int64_t total = words64(host, 0);
   *count = total;
   if (xyz == nullptr && hits == nullptr && rays == nullptr) return DLIOM_OK;  // size query
   if (xyz == nullptr || hits == nullptr || rays == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
@@ -559,7 +504,7 @@ int dliom_outlier_remover_voxels(const dliom_outlier_remover* r, int32_t* xyz, i
   DLIOM_TRY(ctx->outlier.reserve(static_cast<size_t>(total) * sizeof(VoxelRecord)));
   VoxelRecord* d_records = ctx->outlier.as<VoxelRecord>();
   DLIOM_TRY(fill_multi(ctx, &fill, 1));
-  hipLaunchKernelGGL(outlier_emit_voxels_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, r->d_pool, r->d_slot_key, cells,
+  hipLaunchKernelGGL(outlier_emit_voxels_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, r->d_pool, r->table.slot_key, cells,
                      static_cast<unsigned long long>(total), d_records, r->d_words);
   DLIOM_HIP_TRY(hipGetLastError());
   std::vector<VoxelRecord> records(static_cast<size_t>(total));
@@ -568,10 +513,7 @@ int dliom_outlier_remover_voxels(const dliom_outlier_remover* r, int32_t* xyz, i
   ++ctx->host_syncs;
   std::sort(records.begin(), records.end(), [](const VoxelRecord& a, const VoxelRecord& b) { return a.key < b.key; });
   for (int64_t i = 0; i < total; ++i) {
-    const uint64_t k = records[i].key;
-    xyz[3 * i] = static_cast<int32_t>(k & 0x3FFFu) - 8192;
-    xyz[3 * i + 1] = static_cast<int32_t>((k >> 14) & 0x3FFFu) - 8192;
-    xyz[3 * i + 2] = static_cast<int32_t>((k >> 28) & 0x3FFFu) - 8192;
+    key_xyz(records[i].key, &xyz[3 * i]);
     hits[i] = records[i].hits;
     rays[i] = records[i].rays;
   }
@@ -583,16 +525,15 @@ int dliom_outlier_remover_stats(const dliom_outlier_remover* r, dliom_outlier_st
   std::memset(out, 0, sizeof *out);
   dliom_ctx* ctx = r->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
-  const GatherJob back{r->d_words, kNumWords};
-  DLIOM_TRY(gather_and_wait(ctx, &back, 1, host));
+  unsigned host[kNumWords];
+  DLIOM_TRY(read_words(ctx, r->d_words, 0, kNumWords, host));
   out->leaves = r->leaves;
   out->leaf_capacity = r->leaf_capacity;
-  out->table_capacity = r->table_capacity;
+  out->table_capacity = r->table.capacity;
   out->table_bytes = r->bytes();
   out->growths = r->growths;
-  out->samples_walked = static_cast<int64_t>(host[kWordSamples]) | (static_cast<int64_t>(host[kWordSamples + 1]) << 32);
-  out->probes = static_cast<int64_t>(host[kWordProbes]) | (static_cast<int64_t>(host[kWordProbes + 1]) << 32);
+  out->samples_walked = words64(host, kWordSamples);
+  out->probes = words64(host, kWordProbes);
   out->phase = r->phase;
   int64_t voxels = 0;
   DLIOM_TRY(dliom_outlier_remover_voxels(r, nullptr, nullptr, nullptr, 0, &voxels));

@@ -26,8 +26,8 @@ namespace dliom {
 namespace {
 
 constexpr int kBlock = 256;
+constexpr int kLeafBits = 3;
 constexpr int kLeafWords = 16;  // 512 voxels, one bit each
-constexpr unsigned kFlagNonFinite = 1u, kFlagExtent = 2u;
 // a column with more points than this in one batch is summed by a wavefront (xray_long_columns_kernel), not by one lane
 constexpr unsigned kShortSegment = 64;
 
@@ -66,13 +66,10 @@ struct XrayView {
   float tx, ty, tz;
 };
 
-__device__ __forceinline__ uint64_t leaf_key(int cx, int cy, int cz) {
-  return (static_cast<uint64_t>((cz >> 3) + 1024) << 28) | (static_cast<uint64_t>((cy >> 3) + 1024) << 14) |
-         static_cast<uint64_t>((cx >> 3) + 1024);
-}
-__device__ __forceinline__ int cell_in_leaf(int cx, int cy, int cz) { return ((cz & 7) << 6) | ((cy & 7) << 3) | (cx & 7); }
+__device__ __forceinline__ uint64_t leaf_key(int cx, int cy, int cz) { return dliom::leaf_key(cx, cy, cz, kLeafBits); }
+__device__ __forceinline__ int cell_in_leaf(int cx, int cy, int cz) { return dliom::cell_in_leaf(cx, cy, cz, kLeafBits); }
 __host__ __device__ inline uint64_t column_key(int cy, int cz) {  // ascending keys: the std::map's order of (y, z)
-  return (static_cast<uint64_t>(cy + 8192) << 14) | static_cast<uint64_t>(cz + 8192);
+  return key_field(cy, kKeyBias, 1) | key_field(cz, kKeyBias, 0);
 }
 
 // camera_point = transform_ * batch.points[i] (.cc:199): rotation * p + translation
@@ -293,13 +290,6 @@ __global__ __launch_bounds__(kBlock) void xray_long_columns_kernel(const unsigne
   }
 }
 
-__global__ __launch_bounds__(kBlock) void xray_rehash_kernel(const uint64_t* __restrict__ slot_key, unsigned used, uint64_t* keys,
-                                                             unsigned* slots, unsigned mask) {
-  const unsigned s = blockIdx.x * kBlock + threadIdx.x;
-  if (s >= used) return;
-  hash_place(keys, slots, mask, slot_key[s], s);
-}
-
 // ---- the tables' contents ---------------------------------------------------------------------------------------------
 // every occupied voxel as (z, y, x) biased by 8192, z most significant
 __global__ __launch_bounds__(kBlock) void xray_emit_voxels_kernel(const unsigned* __restrict__ masks,
@@ -316,9 +306,9 @@ __global__ __launch_bounds__(kBlock) void xray_emit_voxels_kernel(const unsigned
   while (m != 0u) {
     const unsigned cell = first + static_cast<unsigned>(__ffs(static_cast<int>(m)) - 1);
     m &= m - 1u;
-    const uint64_t vx = ((lk & 0x3FFFu) << 3) | (cell & 7u);
-    const uint64_t vy = (((lk >> 14) & 0x3FFFu) << 3) | ((cell >> 3) & 7u);
-    const uint64_t vz = (((lk >> 28) & 0x3FFFu) << 3) | ((cell >> 6) & 7u);
+    const uint64_t vx = ((lk & kKeyMask) << 3) | (cell & 7u);
+    const uint64_t vy = (((lk >> 14) & kKeyMask) << 3) | ((cell >> 3) & 7u);
+    const uint64_t vz = (((lk >> 28) & kKeyMask) << 3) | ((cell >> 6) & 7u);
     if (at < capacity) out[at] = (vz << 28) | (vy << 14) | vx;
     ++at;
   }
@@ -372,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void xray_paint_kernel(const uint64_t* __re
   const unsigned n = occupied[c];
   if (n == 0u || n >= table_size) return;
   const uint64_t key = col_of_slot[c];
-  const int cy = static_cast<int>((key >> 14) & 0x3FFFu) - 8192, cz = static_cast<int>(key & 0x3FFFu) - 8192;
+  const int cy = key_coord(key, 1), cz = key_coord(key, 0);
   const int px = box_max_y - cy, py = box_max_z - cz;  // voxel_index_to_pixel: the y axis flipped
   if (px < 0 || px >= width || py < 0 || py >= height) return;
   const ColumnData d = data[c];
@@ -382,77 +372,6 @@ __global__ __launch_bounds__(kBlock) void xray_paint_kernel(const uint64_t* __re
 }
 
 inline unsigned blocks_of(int64_t n) { return dliom::blocks_of(n, kBlock); }
-
-int status_of_flag(unsigned flag) {
-  if (flag & kFlagNonFinite) return DLIOM_ERR_INVALID_ARGUMENT;
-  if (flag & kFlagExtent) return DLIOM_ERR_GRID_EXTENT;
-  return DLIOM_OK;
-}
-
-// "key -> slot" with the key of every slot; grown on the host while the stream is idle
-struct KeyTable {
-  uint64_t* keys = nullptr;
-  unsigned* slots = nullptr;
-  uint64_t* slot_key = nullptr;  // capacity / 2 entries
-  int64_t capacity = 0;          // entries, a power of two, at least twice the slots in use
-  int64_t bytes() const { return capacity * 12 + capacity / 2 * 8; }
-  void release() {
-    if (keys) (void)hipFree(keys);
-    if (slots) (void)hipFree(slots);
-    if (slot_key) (void)hipFree(slot_key);
-    keys = slot_key = nullptr;
-    slots = nullptr;
-  }
-  // room for `want` slots at a load of at most one half
-  int grow(dliom_ctx* ctx, int64_t want, int64_t used, int64_t* growths) {
-    if (2 * want <= capacity) return DLIOM_OK;
-    int64_t cap = std::max<int64_t>(capacity, 1024);
-    while (cap < 2 * want) cap <<= 1;
-    if (cap > (int64_t{1} << 31)) return DLIOM_ERR_CAPACITY;
-    KeyTable t;
-    t.capacity = cap;
-    int st = DLIOM_OK;
-    if (hipMalloc(&t.keys, cap * 8) != hipSuccess || hipMalloc(&t.slots, cap * 4) != hipSuccess ||
-        hipMalloc(&t.slot_key, cap / 2 * 8) != hipSuccess || hipMemsetAsync(t.keys, 0xFF, cap * 8, ctx->stream) != hipSuccess)
-      st = DLIOM_ERR_HIP;
-    if (st == DLIOM_OK && used > 0) {
-      if (hipMemcpyAsync(t.slot_key, slot_key, used * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) st = DLIOM_ERR_HIP;
-      hipLaunchKernelGGL(xray_rehash_kernel, dim3(blocks_of(used)), dim3(kBlock), 0, ctx->stream, t.slot_key,
-                         static_cast<unsigned>(used), t.keys, t.slots, static_cast<unsigned>(cap - 1));
-      if (hipGetLastError() != hipSuccess) st = DLIOM_ERR_HIP;
-    }
-    if (st == DLIOM_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = DLIOM_ERR_HIP;
-    if (st != DLIOM_OK) {
-      (void)hipStreamSynchronize(ctx->stream);
-      t.release();
-      return st;
-    }
-    release();
-    if (capacity > 0) ++*growths;
-    *this = t;
-    return DLIOM_OK;
-  }
-};
-
-// `used` elements of *p into a zeroed allocation of `cap` elements
-template <typename T>
-int regrow(dliom_ctx* ctx, T** p, int64_t used, int64_t cap) {
-  T* q = nullptr;
-  DLIOM_HIP_TRY(hipMalloc(&q, cap * sizeof(T)));
-  hipError_t e = hipSuccess;
-  if (used > 0) e = hipMemcpyAsync(q, *p, used * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(q + used, 0, (cap - used) * sizeof(T), ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    (void)hipFree(q);
-    DLIOM_HIP_TRY(e);
-  }
-  if (*p) (void)hipFree(*p);
-  *p = q;
-  return DLIOM_OK;
-}
-
-int64_t words64(const unsigned* host, int at) { return static_cast<int64_t>(host[at]) | (static_cast<int64_t>(host[at + 1]) << 32); }
 
 }  // namespace
 }  // namespace dliom
@@ -477,8 +396,8 @@ struct dliom_points_xray {
   int64_t growths = 0, inserts = 0, points = 0, booked = 0;
 
   XrayView view() const {
-    return XrayView{leaf_table.keys, leaf_table.slots, static_cast<unsigned>(leaf_table.capacity - 1), d_masks, column_table.keys,
-                    column_table.slots, static_cast<unsigned>(column_table.capacity - 1), resolution, q, t[0], t[1], t[2]};
+    const HashView l = leaf_table.view(), c = column_table.view();
+    return XrayView{l.keys, l.slots, l.mask, d_masks, c.keys, c.slots, c.mask, resolution, q, t[0], t[1], t[2]};
   }
   int64_t bytes() const {
     return leaf_table.bytes() + column_table.bytes() + leaf_capacity * kLeafWords * 4 + column_capacity * (16 + 4 + 4) + kNumWords * 4 +
@@ -498,8 +417,9 @@ struct dliom_points_xray {
   int grow_leaves(int64_t want) {
     if (want <= leaf_capacity) return DLIOM_OK;
     const int64_t cap = std::max<int64_t>(want, leaf_capacity + leaf_capacity / 2);
-    unsigned* masks = d_masks;
-    DLIOM_TRY(regrow(ctx, &masks, leaf_capacity * kLeafWords, cap * kLeafWords));
+    unsigned* masks = nullptr;
+    DLIOM_TRY(grown_copy(ctx, d_masks, leaf_capacity * kLeafWords, cap * kLeafWords, &masks));
+    if (d_masks) (void)hipFree(d_masks);
     d_masks = masks;
     if (leaf_capacity > 0) ++growths;
     leaf_capacity = cap;
@@ -510,14 +430,14 @@ struct dliom_points_xray {
     if (want <= column_capacity) return DLIOM_OK;
     const int64_t cap = std::max<int64_t>(want, column_capacity + column_capacity / 2);
     // three new arrays first, the old ones freed after all three exist: a failure leaves the pools as they were
-    ColumnData* data = d_data;
-    unsigned *occ = d_occupied, *pend = nullptr;
-    int st = regrow_keep(&data, column_capacity, cap);
-    if (st == DLIOM_OK) st = regrow_keep(&occ, column_capacity, cap);
-    if (st == DLIOM_OK) st = regrow_keep(&pend, 0, cap);  // zero between inserts
+    ColumnData* data = nullptr;
+    unsigned *occ = nullptr, *pend = nullptr;
+    int st = grown_copy(ctx, d_data, column_capacity, cap, &data);
+    if (st == DLIOM_OK) st = grown_copy(ctx, d_occupied, column_capacity, cap, &occ);
+    if (st == DLIOM_OK) st = grown_copy(ctx, d_pending, 0, cap, &pend);  // zero between inserts
     if (st != DLIOM_OK) {
-      if (data != d_data) (void)hipFree(data);
-      if (occ != d_occupied) (void)hipFree(occ);
+      if (data) (void)hipFree(data);
+      if (occ) (void)hipFree(occ);
       return st;
     }
     if (d_data) (void)hipFree(d_data);
@@ -531,36 +451,12 @@ struct dliom_points_xray {
     book();
     return DLIOM_OK;
   }
-  // *p := a zeroed allocation of `cap` elements that starts with `used` elements of the old *p, which stays allocated
-  template <typename T>
-  int regrow_keep(T** p, int64_t used, int64_t cap) {
-    T* q = nullptr;
-    DLIOM_HIP_TRY(hipMalloc(&q, cap * sizeof(T)));
-    hipError_t e = hipSuccess;
-    if (used > 0) e = hipMemcpyAsync(q, *p, used * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(q + used, 0, (cap - used) * sizeof(T), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-      (void)hipFree(q);
-      DLIOM_HIP_TRY(e);
-    }
-    *p = q;
-    return DLIOM_OK;
-  }
   // Every slot the tables name has its place in the pools.  Always so, except after an insert whose pool growth failed
   // (out of memory): its keys are in the tables -- the counts were taken over, so a later rehash keeps them -- but its
   // points were not inserted.  The next call that needs the pools grows them here, or fails in the same way.
   int pools_ready() {
     DLIOM_TRY(grow_leaves(leaves));
     return grow_columns(columns);
-  }
-  // the device words [first, first + count) on the host
-  int read_words(int first, int count, unsigned* host) const {
-    unsigned* pinned = pinned_at<unsigned>(ctx, kPinReadback);
-    const GatherJob back{d_words + first, static_cast<unsigned>(count)};
-    DLIOM_TRY(gather_and_wait(ctx, &back, 1, pinned));
-    std::memcpy(host, pinned, static_cast<size_t>(count) * 4);
-    return DLIOM_OK;
   }
 };
 
@@ -643,7 +539,7 @@ int dliom_points_xray_insert(dliom_points_xray* x, const dliom_cloud* points, co
                      x->view(), x->leaf_table.slot_key, x->column_table.slot_key, x->d_words);
   DLIOM_HIP_TRY(hipGetLastError());
   unsigned host[3];
-  DLIOM_TRY(x->read_words(0, 3, host));  // leaves, columns, flag
+  DLIOM_TRY(read_words(x->ctx, x->d_words, 0, 3, host));  // leaves, columns, flag
   if (host[kWordFlag] != 0u) return status_of_flag(host[kWordFlag]);  // nothing was claimed or written
   // The keys are in the tables now: the counts are taken over first, so that a rehash always moves every key, and the
   // pools grow to them.  Should that fail, nothing of the batch is inserted: its new columns stay at count 0, which
@@ -711,7 +607,7 @@ int dliom_points_xray_bounding_box(const dliom_points_xray* x, int32_t box_min[3
   if (x == nullptr || box_min == nullptr || box_max == nullptr || empty == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
   DLIOM_HIP_TRY(hipSetDevice(x->ctx->device));
   unsigned host[6];
-  DLIOM_TRY(x->read_words(kWordBoxMin, 6, host));
+  DLIOM_TRY(read_words(x->ctx, x->d_words, kWordBoxMin, 6, host));
   for (int k = 0; k < 3; ++k) {
     box_min[k] = static_cast<int32_t>(host[k]);
     box_max[k] = static_cast<int32_t>(host[3 + k]);
@@ -752,8 +648,8 @@ int dliom_points_xray_columns(const dliom_points_xray* cx, int32_t* yz, float* s
   std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) { return keys[a] < keys[b]; });
   for (size_t i = 0; i < order.size(); ++i) {
     const unsigned s = order[i];
-    yz[2 * i] = static_cast<int32_t>((keys[s] >> 14) & 0x3FFFu) - 8192;
-    yz[2 * i + 1] = static_cast<int32_t>(keys[s] & 0x3FFFu) - 8192;
+    yz[2 * i] = key_coord(keys[s], 1);
+    yz[2 * i + 1] = key_coord(keys[s], 0);
     sums_rgb[3 * i] = data[s].sum_r;
     sums_rgb[3 * i + 1] = data[s].sum_g;
     sums_rgb[3 * i + 2] = data[s].sum_b;
@@ -770,7 +666,7 @@ int dliom_points_xray_voxels(const dliom_points_xray* cx, int32_t* xyz, int64_t 
   dliom_ctx* ctx = x->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   unsigned host[2];
-  DLIOM_TRY(x->read_words(kWordVoxels, 2, host));
+  DLIOM_TRY(read_words(x->ctx, x->d_words, kWordVoxels, 2, host));
   const int64_t total = words64(host, 0);
   *count = total;
   if (xyz == nullptr) return DLIOM_OK;  // size query
@@ -791,12 +687,7 @@ int dliom_points_xray_voxels(const dliom_points_xray* cx, int32_t* xyz, int64_t 
   DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   ++ctx->host_syncs;
   std::sort(keys.begin(), keys.end());
-  for (int64_t i = 0; i < total; ++i) {
-    const uint64_t k = keys[static_cast<size_t>(i)];
-    xyz[3 * i] = static_cast<int32_t>(k & 0x3FFFu) - 8192;
-    xyz[3 * i + 1] = static_cast<int32_t>((k >> 14) & 0x3FFFu) - 8192;
-    xyz[3 * i + 2] = static_cast<int32_t>((k >> 28) & 0x3FFFu) - 8192;
-  }
+  for (int64_t i = 0; i < total; ++i) key_xyz(keys[static_cast<size_t>(i)], &xyz[3 * i]);
   return DLIOM_OK;
 }
 
@@ -817,7 +708,7 @@ int dliom_points_xray_draw(const dliom_points_xray* cx, const int32_t box_min[3]
     DLIOM_HIP_TRY(hipGetLastError());
   }
   unsigned host[7];
-  DLIOM_TRY(x->read_words(kWordMaxOccupied, 7, host));
+  DLIOM_TRY(read_words(x->ctx, x->d_words, kWordMaxOccupied, 7, host));
   const uint32_t max_occupied = host[0];
   int own_min[3], own_max[3], lo[3], hi[3];
   for (int k = 0; k < 3; ++k) {
@@ -867,7 +758,7 @@ int dliom_points_xray_stats(const dliom_points_xray* x, dliom_points_xray_statis
   std::memset(out, 0, sizeof *out);
   DLIOM_HIP_TRY(hipSetDevice(x->ctx->device));
   unsigned host[kNumWords];
-  DLIOM_TRY(x->read_words(0, kNumWords, host));
+  DLIOM_TRY(read_words(x->ctx, x->d_words, 0, kNumWords, host));
   out->voxels = words64(host, kWordVoxels);
   out->columns = x->columns;
   out->leaves = x->leaves;

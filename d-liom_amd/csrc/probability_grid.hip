@@ -24,6 +24,7 @@
 
 #include "device_common.h"
 #include "probability_values.h"
+#include "voxel_hash.h"  // read_words, words64
 
 namespace dliom {
 namespace {
@@ -713,19 +714,19 @@ int dliom_inserter2d_insert_cloud(dliom_inserter2d* ins, dliom_probability_grid*
     restore();
     return DLIOM_ERR_HIP;
   }
-  const GatherJob back{g->d_words, 4};  // flag, error, visits (u64)
-  const int st = gather_and_wait(ctx, &back, 1, host);
+  unsigned back[4];  // flag, error, visits (u64)
+  const int st = read_words(ctx, g->d_words, 0, 4, back);
   if (st != DLIOM_OK) {
     restore();
     return st;
   }
-  if (host[0] != 0u) {  // a superscaled end outside the grid: no pass wrote anything
+  if (back[0] != 0u) {  // a superscaled end outside the grid: no pass wrote anything
     restore();
     return DLIOM_ERR_GRID_EXTENT;
   }
   commit_growth();
-  g->error_word = host[1];
-  g->visits = static_cast<int64_t>(host[2]) | (static_cast<int64_t>(host[3]) << 32);
+  g->error_word = back[1];
+  g->visits = words64(back, 2);
   // mutable_known_cells_box()->extend of every cell touched (probability_grid.cc:62); also when the error word is set: the
   // passes have written, and the box must go on agreeing with the cells
   if (g->box_empty()) {
