@@ -1265,6 +1265,85 @@ struct Floor {  // mapping/detect_floors.h:32-40
 };
 }  // namespace mapping
 
+namespace transform {
+// transform/transform_interpolation_buffer.{h,cc}, common::Time as ticks: the class surface of the reference.  Has and
+// the time getters read the pushed times; Lookup goes through a host-only dliom_trajectory, so that a buffer that is only
+// asked on the host opens no device context.  io::AssemblePointsBatch reads trajectory(), the same nodes on the buffer's
+// context (the calling thread's, unless one was given), created on first use.  Both are immutable arrays that a Push
+// drops and the next use makes again -- with acos / sin per interval, O(n) each time: push the trajectory first, then
+// look up or assemble, as the assets writer does; interleaving Push with Lookup costs O(n^2).
+class TransformInterpolationBuffer {
+ public:
+  explicit TransformInterpolationBuffer(Context* context = nullptr) : context_(context) {}
+  ~TransformInterpolationBuffer() { Drop(); }
+  TransformInterpolationBuffer(const TransformInterpolationBuffer&) = delete;
+  TransformInterpolationBuffer& operator=(const TransformInterpolationBuffer&) = delete;
+
+  void Push(int64_t time, const Rigid3d& transform) {
+    if (!times_.empty() && time < times_.back()) {
+      std::fprintf(stderr, "Check failed: time >= latest_time() New transform is older than latest.\n");
+      std::abort();
+    }
+    times_.push_back(time);
+    const std::array<double, 7> pose = transform.ToArray();
+    poses_.insert(poses_.end(), pose.begin(), pose.end());
+    Drop();
+  }
+  bool Has(int64_t time) const { return !times_.empty() && times_.front() <= time && time <= times_.back(); }
+  Rigid3d Lookup(int64_t time) const {
+    int has = 0;
+    double pose[7];
+    if (host_ == nullptr) Create(nullptr, &host_);
+    Check(dliom_trajectory_lookup(host_, time, &has, pose), "dliom_trajectory_lookup");
+    if (has == 0) {
+      std::fprintf(stderr, "Check failed: Has(time) Missing transform for: %lld\n", static_cast<long long>(time));
+      std::abort();
+    }
+    return Rigid3d::FromArray(pose);
+  }
+  int64_t earliest_time() const {
+    CheckNotEmpty();
+    return times_.front();
+  }
+  int64_t latest_time() const {
+    CheckNotEmpty();
+    return times_.back();
+  }
+  bool empty() const { return times_.empty(); }
+
+  Context* context() const {
+    if (context_ == nullptr) context_ = Context::ForThisThread();
+    return context_;
+  }
+  // the nodes pushed so far as a dliom_trajectory of context() (valid until the next Push)
+  dliom_trajectory* trajectory() const {
+    if (device_ == nullptr) Create(context()->get(), &device_);
+    return device_;
+  }
+
+ private:
+  void Create(dliom_ctx* ctx, dliom_trajectory** out) const {
+    Check(dliom_trajectory_create(ctx, times_.data(), poses_.data(), static_cast<int64_t>(times_.size()), out),
+          "dliom_trajectory_create");
+  }
+  void CheckNotEmpty() const {
+    if (!times_.empty()) return;
+    std::fprintf(stderr, "Check failed: !empty() Empty buffer.\n");
+    std::abort();
+  }
+  void Drop() {
+    if (host_ != nullptr) dliom_trajectory_destroy(host_);
+    if (device_ != nullptr) dliom_trajectory_destroy(device_);
+    host_ = device_ = nullptr;
+  }
+  mutable Context* context_;
+  std::vector<int64_t> times_;
+  std::vector<double> poses_;
+  mutable dliom_trajectory* host_ = nullptr;
+  mutable dliom_trajectory* device_ = nullptr;
+};
+}  // namespace transform
+
 // The points-processor pipeline's stages with compute in them (cartographer/io), on the device.  A batch's points go to
 // the device once per stage and phase; intensities and colors stay on the host and are filtered with the survivors'
 // indices, as RemovePoints does (io/points_batch.cc:22-49).
@@ -1352,12 +1431,12 @@ class MinMaxRangeFiteringPointsProcessor : public PointsProcessor {
       : min_range_(min_range), max_range_(max_range), next_(next), context_(context != nullptr ? context : Context::ForThisThread()) {}
 
   void Process(std::unique_ptr<PointsBatch> batch) override {
-    internal::DeviceCloud in(context_, batch->points);
+    const std::shared_ptr<internal::DeviceCloud> in = internal::PointsOnDevice(context_, *batch);
     std::vector<int32_t> kept_index(batch->points.size());
     dliom_cloud* kept = nullptr;
     int64_t num_kept = 0;
     const float origin[3] = {batch->origin.x, batch->origin.y, batch->origin.z};
-    Check(dliom_cloud_min_max_range_filter(context_->get(), in.cloud, origin, min_range_, max_range_, &kept, kept_index.data(),
+    Check(dliom_cloud_min_max_range_filter(context_->get(), in->cloud, origin, min_range_, max_range_, &kept, kept_index.data(),
                                            static_cast<int64_t>(kept_index.size()), &num_kept),
           "dliom_cloud_min_max_range_filter");
     kept_index.resize(static_cast<size_t>(num_kept));
@@ -1373,6 +1452,42 @@ class MinMaxRangeFiteringPointsProcessor : public PointsProcessor {
   Context* const context_;
 };
 
+// HandleMessage (cartographer_ros/assets_writer.cc:119-160) behind the message decoding: the batch of one message from its
+// points in the sensor frame (x, y, z, time relative to cloud_time), assembled on the device.  Null when no point's time
+// lies on the trajectory, as in the reference.  `points` are downloaded once; the assembled cloud stays in device_points,
+// so that the device stages behind upload nothing.  sensor_to_tracking: one transform for the message (the reference asks
+// a tf buffer per point, which holds the URDF's static transforms only).
+inline std::unique_ptr<PointsBatch> AssemblePointsBatch(const transform::TransformInterpolationBuffer& buffer, int64_t cloud_time,
+                                                        const sensor::TimedPointCloud& points_xyzt,
+                                                        const std::vector<float>& intensities,
+                                                        const transform::Rigid3d& sensor_to_tracking, const std::string& frame_id,
+                                                        Context* context = nullptr) {
+  if (context == nullptr) context = buffer.context();
+  if (!intensities.empty() && intensities.size() != points_xyzt.size())
+    Check(DLIOM_ERR_INVALID_ARGUMENT, "AssemblePointsBatch: CHECK_EQ(intensities.size(), points.size())");
+  std::vector<int32_t> kept_index(points_xyzt.size());
+  dliom_cloud* cloud = nullptr;
+  int64_t num_kept = 0;
+  float origin[3] = {0.f, 0.f, 0.f};
+  const std::array<double, 7> mount = sensor_to_tracking.ToArray();
+  Check(dliom_cloud_from_sensor_points(context->get(), buffer.trajectory(), cloud_time,
+                                       points_xyzt.empty() ? nullptr : &points_xyzt[0].x, static_cast<int64_t>(points_xyzt.size()),
+                                       mount.data(), &cloud, origin, kept_index.data(), static_cast<int64_t>(kept_index.size()),
+                                       &num_kept),
+        "dliom_cloud_from_sensor_points");
+  if (cloud == nullptr) return nullptr;
+  std::unique_ptr<PointsBatch> batch(new PointsBatch);
+  batch->start_time = cloud_time;
+  batch->frame_id = frame_id;
+  batch->origin = sensor::Vector3f(origin[0], origin[1], origin[2]);
+  batch->points.resize(static_cast<size_t>(num_kept));
+  Check(dliom_cloud_download(cloud, &batch->points[0].x), "dliom_cloud_download");
+  if (!intensities.empty())
+    for (int64_t i = 0; i < num_kept; ++i) batch->intensities.push_back(intensities[kept_index[static_cast<size_t>(i)]]);
+  batch->device_points = std::make_shared<internal::DeviceCloud>(context, cloud);
+  return batch;
+}
+
 // io/outlier_removing_points_processor.{h,cc}: "voxel_filter_and_remove_moving_objects"
 class OutlierRemovingPointsProcessor : public PointsProcessor {
  public:
@@ -1384,7 +1499,8 @@ class OutlierRemovingPointsProcessor : public PointsProcessor {
   ~OutlierRemovingPointsProcessor() override { dliom_outlier_remover_destroy(remover_); }
 
   void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:45-61
-    internal::DeviceCloud in(context_, batch->points);
+    const std::shared_ptr<internal::DeviceCloud> points = internal::PointsOnDevice(context_, *batch);
+    const internal::DeviceCloud& in = *points;
     const float origin[3] = {batch->origin.x, batch->origin.y, batch->origin.z};
     switch (state_) {
       case State::kPhase1:

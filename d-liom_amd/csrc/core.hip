@@ -898,7 +898,8 @@ int dliom_ctx_set_tuning(dliom_ctx* ctx, int knob, int value) {
       break;
     case DLIOM_TUNE_RESERVED_TEST_HOOK:
 #ifdef DLIOM_TEST_HOOKS  // libdliom_hooks.so (make hooks): 1 injects the box kernel's inconsistency word once; 2 / 3 make
-      if (value < 0 || value > 3) return DLIOM_ERR_INVALID_ARGUMENT;  // the de-skew record every hit / also "fix" every record
+      if (value < 0 || value > 5) return DLIOM_ERR_INVALID_ARGUMENT;  // the de-skew record every hit / also "fix" every record;
+      // 4 / 5 make the batch assembler (assemble.hip) record every point / also perturb the device's rotation
       break;
 #else
       return DLIOM_ERR_INVALID_ARGUMENT;  // the shipped library has no fault injection

@@ -110,6 +110,7 @@ struct dliom_ctx {
   unsigned deskew_flag_total = 0;   // its monotonic record counter as last read
   unsigned deskew_launch_id = 0;    // tags the records of a launch (DeskewArgs::launch_tag)
   int64_t deskew_records_checked = 0, deskew_overflows = 0, deskew_fixed_hits = 0;  // dliom_deskew_check_stats
+  int64_t assemble_recorded = 0, assemble_recomputed = 0, assemble_fixed = 0, assemble_overflows = 0;  // dliom_assemble_check_stats (assemble.hip)
   dliom::DevBuf zero_words; // 256 bytes that stay zero (zeroed once): status words of kernels whose checking pass was
   bool zero_words_ready = false;  // proven unnecessary on the host (grid.hip: insertion without the extent scan)
   bool box_error_zeroed = false;

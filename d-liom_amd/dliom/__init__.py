@@ -292,6 +292,13 @@ SYMBOLS = [
     ("dliom_points_xray_draw", C.c_int, [_vp, _i32p, _i32p, _u32p, C.c_int64, _i32p, _i32p]),
     ("dliom_points_xray_stats", C.c_int, [_vp, C.POINTER(PointsXrayStats)]),
     ("dliom_points_xray_pixel", C.c_int, [C.c_uint32, C.c_uint32, _f32p, _u32p]),
+    ("dliom_trajectory_create", C.c_int, [_vp, _i64p, _f64p, C.c_int64, C.POINTER(_vp)]),
+    ("dliom_trajectory_destroy", C.c_int, [_vp]),
+    ("dliom_trajectory_size", C.c_int, [_vp, _i64p]),
+    ("dliom_trajectory_lookup", C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int), _f64p]),
+    ("dliom_cloud_from_sensor_points", C.c_int, [_vp, _vp, C.c_int64, _f32p, C.c_int64, _f64p, C.POINTER(_vp), _f32p, _i32p,
+                                                 C.c_int64, _i64p]),
+    ("dliom_assemble_check_stats", C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p]),
     ("dliom_cloud_min_max_range_filter", C.c_int, [_vp, _vp, _f32p, C.c_double, C.c_double, C.POINTER(_vp), _i32p, C.c_int64,
                                                    _i64p]),
     ("dliom_rtcsm3d_match", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _f32p, C.c_int64, _vp, _f64p, _f32p]),
@@ -564,6 +571,13 @@ class Context:
         _check(self._L.dliom_deskew_check_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "deskew_check_stats")
         return int(a.value), int(b.value), int(c.value)
 
+    def assemble_check_stats(self):
+        """dliom_assemble_check_stats: (points recorded by the batch assembler, records recomputed with glibc on the host,
+        points whose device cast differed and were redone, calls whose records outgrew the ring)."""
+        v = [C.c_int64() for _ in range(4)]
+        _check(self._L.dliom_assemble_check_stats(self.h, *[C.byref(x) for x in v]), "assemble_check_stats")
+        return tuple(int(x.value) for x in v)
+
     def get_tuning(self, knob):
         v = C.c_int(0)
         _check(self._L.dliom_ctx_get_tuning(self.h, int(knob), C.byref(v)), "get_tuning")
@@ -655,6 +669,63 @@ class PointCloud:
     def close(self):
         if getattr(self, "h", None):
             self._L.dliom_cloud_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Trajectory:
+    """transform::TransformInterpolationBuffer as an immutable array of nodes (dliom_trajectory): times in common::Time
+    ticks (100 ns), poses [tx,ty,tz,qw,qx,qy,qz].  ctx None: a host-only buffer (has / lookup)."""
+
+    def __init__(self, ctx, times, poses7):
+        self._L = ctx._L if ctx is not None else load_library()
+        self.ctx = ctx
+        t = np.ascontiguousarray(times, dtype=np.int64).reshape(-1)
+        p = _f64(poses7).reshape(-1, 7)
+        if len(t) != len(p):
+            raise ValueError("one pose per time")
+        h = _vp()
+        _check(self._L.dliom_trajectory_create(ctx.h if ctx is not None else None, _p(t, _i64p), _p(p, _f64p), len(t), C.byref(h)),
+               "dliom_trajectory_create")
+        self.h = h
+        self.n = len(t)
+
+    def __len__(self):
+        return self.n
+
+    def has(self, time):
+        has = C.c_int()
+        _check(self._L.dliom_trajectory_lookup(self.h, int(time), C.byref(has), None), "dliom_trajectory_lookup")
+        return bool(has.value)
+
+    def lookup(self, time):
+        """Lookup(time) as float64[7], or None where not Has(time)."""
+        has, pose = C.c_int(), np.zeros(7, dtype=np.float64)
+        _check(self._L.dliom_trajectory_lookup(self.h, int(time), C.byref(has), _p(pose, _f64p)), "dliom_trajectory_lookup")
+        return pose if has.value else None
+
+    def assemble(self, cloud_time, points_xyzt, sensor_to_tracking, capacity=None):
+        """HandleMessage's loop on the device (dliom_cloud_from_sensor_points) -> (PointCloud or None, float32 origin[3],
+        int32 input indices of the kept points)."""
+        pts = _f32(points_xyzt).reshape(-1, 4)
+        h, kept, origin = _vp(), C.c_int64(), np.zeros(3, dtype=np.float32)
+        cap = len(pts) if capacity is None else int(capacity)
+        index = np.zeros(max(cap, 1), dtype=np.int32)
+        _check(self._L.dliom_cloud_from_sensor_points(self.ctx.h, self.h, int(cloud_time), _p(pts, _f32p), len(pts),
+                                                      _p(_f64(sensor_to_tracking), _f64p), C.byref(h), _p(origin, _f32p),
+                                                      _p(index, _i32p), cap, C.byref(kept)), "dliom_cloud_from_sensor_points")
+        if not h:
+            return None, origin, index[:0].copy()
+        return PointCloud(self.ctx, _handle=h), origin, index[:kept.value].copy()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_trajectory_destroy(self.h)
             self.h = None
 
     def __del__(self):

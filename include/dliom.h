@@ -573,6 +573,35 @@ int dliom_outlier_remover_stats(const dliom_outlier_remover* remover, dliom_outl
 int dliom_cloud_min_max_range_filter(dliom_ctx* ctx, const dliom_cloud* in, const float origin[3], double min_range,
                                      double max_range, dliom_cloud** out, int32_t* kept_index, int64_t capacity,
                                      int64_t* num_kept);
+/* ---- The head of the export: batches assembled from sensor-frame points (cartographer_ros/assets_writer.cc:119-160) ----
+ * transform::TransformInterpolationBuffer (transform/transform_interpolation_buffer.{h,cc}) as an immutable array of
+ * nodes: times in common::Time ticks (100 ns), poses [tx,ty,tz,qw,qx,qy,qz] of tracking in map.  Decreasing times are
+ * refused with DLIOM_ERR_INVALID_ARGUMENT (Push's CHECK_GE); equal neighbours are allowed; n = 0 is the empty buffer.
+ * ctx may be NULL: a host-only buffer for dliom_trajectory_lookup (dliom_cloud_from_sensor_points refuses it).  The nodes
+ * reach the device with the first call that needs them there.  A trajectory may be destroyed after its context (it then
+ * only frees its own device memory); it may not be used after it. */
+typedef struct dliom_trajectory dliom_trajectory;
+int dliom_trajectory_create(dliom_ctx* ctx, const int64_t* times, const double* poses7, int64_t n, dliom_trajectory** out);
+int dliom_trajectory_destroy(dliom_trajectory* trajectory);
+int dliom_trajectory_size(const dliom_trajectory* trajectory, int64_t* n);
+/* Has(time) and, where it holds and pose7 is not NULL, Lookup(time) (host only): the node's own transform when
+ * lower_bound's node has that time, else Interpolate(prev, node) (transform/timestamped_transform.cc:22-37: translations
+ * blended in double, Eigen's slerp with its 1 - epsilon threshold and sign flip, not renormalised). */
+int dliom_trajectory_lookup(const dliom_trajectory* trajectory, int64_t time, int* has, double pose7[7]);
+/* HandleMessage's loop over the n points (x, y, z, relative time [s]) of one message in the sensor frame.  Point i has
+ * time = cloud_time + int64(double(t_i) * 1e7) (common::FromSeconds); it is dropped unless the trajectory Has(time), else
+ * transformed in float by (Lookup(time) * sensor_to_tracking).cast<float>().  *out: the kept points in input order (a new
+ * cloud, the caller destroys it), NULL with status OK when none is kept (the reference returns nullptr).  origin: the
+ * translation of the last kept point's transform.  kept_index, capacity, num_kept as in dliom_outlier_remover_filter.
+ * The floats are the reference's, proven per call (dliom_assemble_check_stats).  DLIOM_ERR_INVALID_ARGUMENT, before
+ * anything is written: a t_i that is not finite or has |t_i * 1e7| >= 2^63, NULL arguments, a trajectory of another
+ * context, negative n.  Coordinates are not checked: non-finite ones are passed through, as the reference does. */
+int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* trajectory, int64_t cloud_time, const float* points_xyzt,
+                                   int64_t n, const double sensor_to_tracking[7], dliom_cloud** out, float origin[3],
+                                   int32_t* kept_index, int64_t capacity, int64_t* num_kept);
+/* The check behind it: points whose casts to float the device could not prove equal to glibc's (recorded), records the
+ * host recomputed with glibc, points it had to redo, and calls whose records outgrew the words read back anyway. */
+int dliom_assemble_check_stats(const dliom_ctx* ctx, int64_t* recorded, int64_t* recomputed, int64_t* fixed, int64_t* ring_overflows);
 /* The same filters on host buffers (the reference's own placement): out_xyz has room for n points;
  * *num_out receives the survivors (first point per voxel). */
 int dliom_voxel_filter(float size, const float* points_xyz, int64_t n, float* out_xyz, int64_t* num_out);
@@ -1123,7 +1152,8 @@ enum {
                                          libdliom_hooks.so, loaded by one GPU test) accepts it: the next match then
                                          treats the box kernel's consistency word as set and takes the "redo on the
                                          dense kernel" path once; 2 / 3 force the de-skew check's overflow and fix
-                                         paths.  The shipped library contains no fault injection. */
+                                         paths, 4 / 5 the batch assembler's (every point recorded / the device's
+                                         rotation also perturbed).  The shipped library contains no fault injection. */
   DLIOM_TUNE_CSM_GRID_SYNC = 3,       /* CeresScanMatcher3D on large clouds: 1 = the whole loop in one launch with grid
                                          barriers, 0 = one launch per evaluation (default: measured 0.27 ms against
                                          0.35 ms per 131 072-point match -- the barrier, the final reduction and the
