@@ -1344,15 +1344,18 @@ class TransformInterpolationBuffer {
 };
 }  // namespace transform
 
-// The points-processor pipeline's stages with compute in them (cartographer/io), on the device.  A batch's points go to
-// the device once per stage and phase; intensities and colors stay on the host and are filtered with the survivors'
-// indices, as RemovePoints does (io/points_batch.cc:22-49).
+// The points-processor pipeline's stages with compute in them (cartographer/io), on the device.  A batch that arrives as
+// host vectors goes to the device once per stage and phase, its intensities and colors stay on the host and are filtered
+// with the survivors' indices, as RemovePoints does (io/points_batch.cc:22-49).  A batch that carries a device_batch
+// (AssemblePointsBatch(kOnDevice, ...), or any stage that made one) lives in HBM with its attributes: the stages rewrite it
+// there and pass it on; the host vectors are refreshed only by internal::SyncToHost.
 namespace io {
 
 using FloatColor = std::array<float, 3>;  // io/color.h:30
 
 namespace internal {
 struct DeviceCloud;
+struct DeviceBatch;
 }
 struct PointsBatch {  // io/points_batch.h:36-73: the fields the stages here touch
   sensor::Vector3f origin{0.f, 0.f, 0.f};
@@ -1364,6 +1367,10 @@ struct PointsBatch {  // io/points_batch.h:36-73: the fields the stages here tou
   // Not in the reference: `points` as a stage left them on the device (the range filter and the outlier remover set it),
   // so that the next device stage does not upload them again.  Whoever changes `points` resets it (KeepPoints does).
   std::shared_ptr<internal::DeviceCloud> device_points;
+  // Not in the reference: the whole batch (points, intensities, colors) in HBM.  While its host_stale is set it alone is
+  // the batch and the three vectors above are out of date (internal::SyncToHost brings them back); otherwise it mirrors
+  // them and is valid like device_points: same context, same size.  A stage that rewrites a host vector resets it.
+  std::shared_ptr<internal::DeviceBatch> device_batch;
 };
 
 class PointsProcessor {  // io/points_processor.h:29-52
@@ -1396,6 +1403,79 @@ struct DeviceCloud {
   Context* const context;  // the context the cloud lives on
   dliom_cloud* cloud = nullptr;
 };
+struct DeviceBatch {
+  // bytes of batch contents brought back to the host so far: SyncToHost's vectors and the writers' packed records
+  static std::atomic<int64_t>& DownloadedBytes() {
+    static std::atomic<int64_t> bytes{0};
+    return bytes;
+  }
+  DeviceBatch(Context* context, dliom_points_batch* owned, bool host_stale) : context(context), batch(owned), host_stale(host_stale) {}
+  ~DeviceBatch() { dliom_points_batch_destroy(batch); }
+  DeviceBatch(const DeviceBatch&) = delete;
+  DeviceBatch& operator=(const DeviceBatch&) = delete;
+  int64_t size() const {
+    int64_t n = 0;
+    Check(dliom_points_batch_size(batch, &n), "dliom_points_batch_size");
+    return n;
+  }
+  const dliom_cloud* cloud() const {
+    const dliom_cloud* c = nullptr;
+    Check(dliom_points_batch_cloud(batch, &c), "dliom_points_batch_cloud");
+    return c;
+  }
+  Context* const context;
+  dliom_points_batch* batch = nullptr;
+  bool host_stale;  // the PointsBatch's vectors do not hold what the device batch holds
+};
+// The batch's device_batch if a stage on `context` may use it, else null
+inline DeviceBatch* BatchOnDevice(Context* context, const PointsBatch& batch) {
+  DeviceBatch* d = batch.device_batch.get();
+  if (d == nullptr || d->context != context) return nullptr;
+  if (!d->host_stale && d->size() != static_cast<int64_t>(batch.points.size())) return nullptr;
+  return d;
+}
+// points, intensities and colors := the device batch's (one download each); a no-op unless they are stale
+inline void SyncToHost(PointsBatch* batch) {
+  DeviceBatch* d = batch->device_batch.get();
+  if (d == nullptr || !d->host_stale) return;
+  const size_t n = static_cast<size_t>(d->size());
+  int has_intensities = 0, has_colors = 0;
+  Check(dliom_points_batch_has_intensities(d->batch, &has_intensities), "dliom_points_batch_has_intensities");
+  Check(dliom_points_batch_has_colors(d->batch, &has_colors), "dliom_points_batch_has_colors");
+  batch->points.assign(n, sensor::Vector3f(0.f, 0.f, 0.f));
+  batch->intensities.assign(has_intensities ? n : 0, 0.f);
+  batch->colors.assign(has_colors ? n : 0, FloatColor{{0.f, 0.f, 0.f}});
+  if (n > 0)
+    Check(dliom_points_batch_download(d->batch, &batch->points[0].x, has_intensities ? batch->intensities.data() : nullptr,
+                                      has_colors ? batch->colors[0].data() : nullptr),
+          "dliom_points_batch_download");
+  DeviceBatch::DownloadedBytes() += static_cast<int64_t>(n * (12 + (has_intensities ? 4 : 0) + (has_colors ? 12 : 0)));
+  batch->device_points.reset();
+  d->host_stale = false;
+}
+// What a stage that works on the host vectors calls first: they are brought up to date and the device batch is dropped
+inline void UseHostVectors(PointsBatch* batch) {
+  SyncToHost(batch);
+  batch->device_batch.reset();
+}
+// The batch in HBM on `context`: what it carries, else made from the host vectors (one upload of each)
+inline DeviceBatch* EnsureOnDevice(Context* context, PointsBatch* batch) {
+  if (DeviceBatch* d = BatchOnDevice(context, *batch)) return d;
+  UseHostVectors(batch);
+  if ((!batch->intensities.empty() && batch->intensities.size() != batch->points.size()) ||
+      (!batch->colors.empty() && batch->colors.size() != batch->points.size()))
+    Check(DLIOM_ERR_INVALID_ARGUMENT, "PointsBatch: an attribute vector that is neither empty nor of the points' size");
+  const float origin[3] = {batch->origin.x, batch->origin.y, batch->origin.z};
+  dliom_points_batch* made = nullptr;
+  Check(dliom_points_batch_create(context->get(), batch->points.empty() ? nullptr : &batch->points[0].x,
+                                  static_cast<int64_t>(batch->points.size()), origin,
+                                  batch->intensities.empty() ? nullptr : batch->intensities.data(),
+                                  batch->colors.empty() ? nullptr : batch->colors[0].data(), static_cast<int64_t>(batch->colors.size()),
+                                  &made),
+        "dliom_points_batch_create");
+  batch->device_batch = std::make_shared<DeviceBatch>(context, made, false);
+  return batch->device_batch.get();
+}
 // RemovePoints with the complement: the batch keeps the points of `kept` (a device cloud of kept_index.size() points)
 inline void KeepPoints(dliom_cloud* kept, const std::vector<int32_t>& kept_index, PointsBatch* batch) {
   std::vector<sensor::Vector3f> points(kept_index.size());
@@ -1410,6 +1490,7 @@ inline void KeepPoints(dliom_cloud* kept, const std::vector<int32_t>& kept_index
   batch->intensities = std::move(intensities);
   batch->colors = std::move(colors);
   batch->device_points.reset();
+  batch->device_batch.reset();
 }
 // The batch's points on the device: what the stage before left there -- on this context, and of the batch's size --, else
 // one upload.  (A stage that rewrites `points` in place without changing their number must reset device_points itself.)
@@ -1431,6 +1512,13 @@ class MinMaxRangeFiteringPointsProcessor : public PointsProcessor {
       : min_range_(min_range), max_range_(max_range), next_(next), context_(context != nullptr ? context : Context::ForThisThread()) {}
 
   void Process(std::unique_ptr<PointsBatch> batch) override {
+    if (internal::DeviceBatch* d = internal::BatchOnDevice(context_, *batch)) {  // compacted where it is: one count comes back
+      Check(dliom_points_batch_min_max_range_filter(d->batch, min_range_, max_range_), "dliom_points_batch_min_max_range_filter");
+      d->host_stale = true;
+      next_->Process(std::move(batch));
+      return;
+    }
+    internal::UseHostVectors(batch.get());
     const std::shared_ptr<internal::DeviceCloud> in = internal::PointsOnDevice(context_, *batch);
     std::vector<int32_t> kept_index(batch->points.size());
     dliom_cloud* kept = nullptr;
@@ -1488,6 +1576,73 @@ inline std::unique_ptr<PointsBatch> AssemblePointsBatch(const transform::Transfo
   return batch;
 }
 
+// The same batch left in HBM: points and intensities never visit the host (batch->points stays empty until
+// internal::SyncToHost; batch->device_batch is the batch).  The message's intensities are uploaded once.
+struct OnDevice {};
+constexpr OnDevice kOnDevice{};
+inline std::unique_ptr<PointsBatch> AssemblePointsBatch(OnDevice, const transform::TransformInterpolationBuffer& buffer,
+                                                        int64_t cloud_time, const sensor::TimedPointCloud& points_xyzt,
+                                                        const std::vector<float>& intensities,
+                                                        const transform::Rigid3d& sensor_to_tracking, const std::string& frame_id,
+                                                        Context* context = nullptr) {
+  if (context == nullptr) context = buffer.context();
+  if (!intensities.empty() && intensities.size() != points_xyzt.size())
+    Check(DLIOM_ERR_INVALID_ARGUMENT, "AssemblePointsBatch: CHECK_EQ(intensities.size(), points.size())");
+  const std::array<double, 7> mount = sensor_to_tracking.ToArray();
+  dliom_points_batch* made = nullptr;
+  Check(dliom_points_batch_from_sensor_points(context->get(), buffer.trajectory(), cloud_time,
+                                              points_xyzt.empty() ? nullptr : &points_xyzt[0].x,
+                                              intensities.empty() ? nullptr : intensities.data(),
+                                              static_cast<int64_t>(points_xyzt.size()), mount.data(), &made),
+        "dliom_points_batch_from_sensor_points");
+  if (made == nullptr) return nullptr;
+  std::unique_ptr<PointsBatch> batch(new PointsBatch);
+  batch->start_time = cloud_time;
+  batch->frame_id = frame_id;
+  float origin[3];
+  Check(dliom_points_batch_origin(made, origin), "dliom_points_batch_origin");
+  batch->origin = sensor::Vector3f(origin[0], origin[1], origin[2]);
+  batch->device_batch = std::make_shared<internal::DeviceBatch>(context, made, true);
+  return batch;
+}
+
+// io/fixed_ratio_sampling_points_processor.{h,cc} over common::FixedRatioSampler: "fixed_ratio_sampler".  One sampler
+// state whichever way a batch arrives: host vectors go to the device for the call and come back.
+class FixedRatioSamplingPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "fixed_ratio_sampler";
+  FixedRatioSamplingPointsProcessor(double sampling_ratio, PointsProcessor* next, Context* context = nullptr)
+      : next_(next), context_(context != nullptr ? context : Context::ForThisThread()) {
+    Check(dliom_fixed_ratio_sampler_create(sampling_ratio, &sampler_), "dliom_fixed_ratio_sampler_create");
+  }
+  ~FixedRatioSamplingPointsProcessor() override { dliom_fixed_ratio_sampler_destroy(sampler_); }
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:43-53
+    const bool arrived_on_host = internal::BatchOnDevice(context_, *batch) == nullptr || !batch->device_batch->host_stale;
+    internal::DeviceBatch* d = internal::EnsureOnDevice(context_, batch.get());
+    Check(dliom_points_batch_fixed_ratio_sample(sampler_, d->batch), "dliom_points_batch_fixed_ratio_sample");
+    d->host_stale = true;
+    if (arrived_on_host) internal::SyncToHost(batch.get());  // a host-vector caller finds its vectors sampled
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override {  // .cc:55-66
+    switch (next_->Flush()) {
+      case FlushResult::kFinished:
+        return FlushResult::kFinished;
+      case FlushResult::kRestartStream:
+        Check(dliom_fixed_ratio_sampler_reset(sampler_), "dliom_fixed_ratio_sampler_reset");  // a new FixedRatioSampler
+        return FlushResult::kRestartStream;
+    }
+    std::abort();
+  }
+  const dliom_fixed_ratio_sampler* sampler() const { return sampler_; }
+
+ private:
+  PointsProcessor* const next_;
+  Context* const context_;
+  dliom_fixed_ratio_sampler* sampler_ = nullptr;
+};
+
 // io/outlier_removing_points_processor.{h,cc}: "voxel_filter_and_remove_moving_objects"
 class OutlierRemovingPointsProcessor : public PointsProcessor {
  public:
@@ -1499,9 +1654,26 @@ class OutlierRemovingPointsProcessor : public PointsProcessor {
   ~OutlierRemovingPointsProcessor() override { dliom_outlier_remover_destroy(remover_); }
 
   void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:45-61
+    const float origin[3] = {batch->origin.x, batch->origin.y, batch->origin.z};
+    if (internal::DeviceBatch* d = internal::BatchOnDevice(context_, *batch)) {
+      switch (state_) {
+        case State::kPhase1:
+          Check(dliom_outlier_remover_mark_hits(remover_, d->cloud()), "dliom_outlier_remover_mark_hits");
+          break;
+        case State::kPhase2:
+          Check(dliom_outlier_remover_count_rays(remover_, origin, d->cloud()), "dliom_outlier_remover_count_rays");
+          break;
+        case State::kPhase3:
+          Check(dliom_outlier_remover_filter_batch(remover_, d->batch), "dliom_outlier_remover_filter_batch");
+          d->host_stale = true;
+          next_->Process(std::move(batch));
+          break;
+      }
+      return;
+    }
+    internal::UseHostVectors(batch.get());
     const std::shared_ptr<internal::DeviceCloud> points = internal::PointsOnDevice(context_, *batch);
     const internal::DeviceCloud& in = *points;
-    const float origin[3] = {batch->origin.x, batch->origin.y, batch->origin.z};
     switch (state_) {
       case State::kPhase1:
         Check(dliom_outlier_remover_mark_hits(remover_, in.cloud), "dliom_outlier_remover_mark_hits");
@@ -1562,6 +1734,9 @@ class FileWriter {
   FileWriter(const FileWriter&) = delete;
   FileWriter& operator=(const FileWriter&) = delete;
   virtual bool Write(const char* data, size_t len) = 0;
+  // Overwrites the start of the file (io/file_writer.h:43: the PLY / PCD writers' placeholder header and its final form).
+  // Not pure, unlike the reference's: the map writers' FileWriters never needed it.
+  virtual bool WriteHeader(const char* /*data*/, size_t /*len*/) { return false; }
   virtual bool Close() = 0;
   virtual std::string GetFilename() = 0;
 };
@@ -1594,8 +1769,20 @@ class ProbabilityGridOnDevice {
 
   // range_data_inserter_.Insert({batch->origin, batch->points, {}}, &probability_grid_)
   void Insert(const PointsBatch& batch) {
-    const std::shared_ptr<DeviceCloud> points = PointsOnDevice(context_, batch);
     const float origin[3] = {batch.origin.x, batch.origin.y, batch.origin.z};
+    if (const DeviceBatch* d = BatchOnDevice(context_, batch)) {
+      Check(dliom_inserter2d_insert_cloud(inserter_, grid_, origin, d->cloud()), "dliom_inserter2d_insert_cloud");
+      return;
+    }
+    PointsBatch synced;  // (a device batch of another context: its points by way of the host)
+    const PointsBatch* host = &batch;
+    if (batch.device_batch != nullptr && batch.device_batch->host_stale) {
+      synced.device_batch = batch.device_batch;
+      SyncToHost(&synced);
+      synced.device_batch.reset();
+      host = &synced;
+    }
+    const std::shared_ptr<DeviceCloud> points = PointsOnDevice(context_, *host);
     Check(dliom_inserter2d_insert_cloud(inserter_, grid_, origin, points->cloud), "dliom_inserter2d_insert_cloud");
   }
   // DrawProbabilityGrid (:127-148), rotated by Image::Rotate90DegreesClockwise if asked: the gray bytes, row-major
@@ -1715,8 +1902,140 @@ class RosMapWritingPointsProcessor : public PointsProcessor {
   internal::ProbabilityGridOnDevice grid_;
 };
 
-// io/coloring_points_processor.{h,cc}: "color_points".  Host code: it writes batch->colors and leaves the points alone,
-// so what a stage before left on the device stays valid.
+namespace internal {
+// What the PLY and the PCD writer share: the header rewritten in place, one Write of packed records a batch.
+class RecordWriter {
+ public:
+  RecordWriter(std::unique_ptr<FileWriter> file, Context* context) : context_(context), file_(std::move(file)) {}
+  template <typename Header>
+  void WriteHeader(Header header) {
+    int64_t length = 0;
+    header(nullptr, 0, &length);  // the size
+    std::string text(static_cast<size_t>(length), '\0');
+    Check(header(&text[0], length, &length), "points file header");
+    if (!file_->WriteHeader(text.data(), text.size())) Fail("WriteHeader");
+  }
+  // the batch's records, packed on the device and downloaded in one copy -> its number of points
+  int64_t WriteRecords(PointsBatch* batch, int format, bool with_colors, bool with_intensities) {
+    DeviceBatch* d = EnsureOnDevice(context_, batch);
+    int64_t bytes = 0;
+    Check(dliom_points_batch_pack(d->batch, format, with_colors ? 1 : 0, with_intensities ? 1 : 0, nullptr, 0, &bytes),
+          "dliom_points_batch_pack: the first PointsBatch had an attribute that this one lacks");
+    records_.resize(static_cast<size_t>(bytes));
+    Check(dliom_points_batch_pack(d->batch, format, with_colors ? 1 : 0, with_intensities ? 1 : 0, records_.data(), bytes, &bytes),
+          "dliom_points_batch_pack");
+    DeviceBatch::DownloadedBytes() += bytes;
+    if (!file_->Write(reinterpret_cast<const char*>(records_.data()), records_.size())) Fail("Write");
+    return d->size();
+  }
+  void Close() {
+    if (!file_->Close()) Fail("Close");
+  }
+  Context* context() const { return context_; }
+
+ private:
+  static void Fail(const char* what) {
+    std::fprintf(stderr, "Check failed: file_writer->%s\n", what);
+    std::abort();
+  }
+  Context* const context_;
+  std::unique_ptr<FileWriter> file_;
+  std::vector<uint8_t> records_;
+};
+inline int64_t BatchSize(Context* context, const PointsBatch& batch) {
+  const DeviceBatch* d = BatchOnDevice(context, batch);
+  return d != nullptr ? d->size() : static_cast<int64_t>(batch.points.size());
+}
+inline void BatchAttributes(Context* context, PointsBatch* batch, bool* has_colors, bool* has_intensities) {
+  const DeviceBatch* d = EnsureOnDevice(context, batch);
+  int colors = 0, intensities = 0;
+  Check(dliom_points_batch_has_colors(d->batch, &colors), "dliom_points_batch_has_colors");
+  Check(dliom_points_batch_has_intensities(d->batch, &intensities), "dliom_points_batch_has_intensities");
+  *has_colors = colors != 0;
+  *has_intensities = intensities != 0;
+}
+}  // namespace internal
+
+// io/ply_writing_points_processor.{h,cc}: "write_ply"
+class PlyWritingPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "write_ply";
+  PlyWritingPointsProcessor(std::unique_ptr<FileWriter> file_writer, PointsProcessor* next, Context* context = nullptr)
+      : next_(next), writer_(std::move(file_writer), context != nullptr ? context : Context::ForThisThread()) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:106-150
+    if (internal::BatchSize(writer_.context(), *batch) == 0) {
+      next_->Process(std::move(batch));
+      return;
+    }
+    if (num_points_ == 0) {
+      internal::BatchAttributes(writer_.context(), batch.get(), &has_colors_, &has_intensities_);
+      Header(0);
+    }
+    num_points_ += writer_.WriteRecords(batch.get(), DLIOM_PACK_PLY, has_colors_, has_intensities_);
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override {  // .cc:91-104
+    Header(num_points_);
+    writer_.Close();
+    return internal::FlushLastStage(next_, "PLY generation must be configured to occur after any stages that require multiple "
+                                           "passes.");
+  }
+
+ private:
+  void Header(int64_t num_points) {
+    writer_.WriteHeader([&](char* buffer, int64_t capacity, int64_t* length) {
+      return dliom_ply_header(has_colors_ ? 1 : 0, has_intensities_ ? 1 : 0, num_points, buffer, capacity, length);
+    });
+  }
+  PointsProcessor* const next_;
+  internal::RecordWriter writer_;
+  int64_t num_points_ = 0;
+  bool has_colors_ = false, has_intensities_ = false;
+};
+
+// io/pcd_writing_points_processor.{h,cc}: "write_pcd".  The header's colour field is the first non-empty batch's; a later
+// batch whose colours differ from it is refused (the reference would write records the header does not describe).
+class PcdWritingPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "write_pcd";
+  PcdWritingPointsProcessor(std::unique_ptr<FileWriter> file_writer, PointsProcessor* next, Context* context = nullptr)
+      : next_(next), writer_(std::move(file_writer), context != nullptr ? context : Context::ForThisThread()) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:93-131
+    if (internal::BatchSize(writer_.context(), *batch) == 0) {
+      next_->Process(std::move(batch));
+      return;
+    }
+    if (num_points_ == 0) {
+      bool unused = false;
+      internal::BatchAttributes(writer_.context(), batch.get(), &has_colors_, &unused);
+      Header(0);
+    }
+    num_points_ += writer_.WriteRecords(batch.get(), DLIOM_PACK_PCD, has_colors_, false);
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override {  // .cc:78-91
+    Header(num_points_);
+    writer_.Close();
+    return internal::FlushLastStage(next_, "PCD generation must be configured to occur after any stages that require multiple "
+                                           "passes.");
+  }
+
+ private:
+  void Header(int64_t num_points) {
+    writer_.WriteHeader([&](char* buffer, int64_t capacity, int64_t* length) {
+      return dliom_pcd_header(has_colors_ ? 1 : 0, num_points, buffer, capacity, length);
+    });
+  }
+  PointsProcessor* const next_;
+  internal::RecordWriter writer_;
+  int64_t num_points_ = 0;
+  bool has_colors_ = false;
+};
+
+// io/coloring_points_processor.{h,cc}: "color_points".  On a batch in HBM the colour is set there; on host vectors it
+// writes batch->colors and leaves the points alone, so what a stage before left in device_points stays valid.
 class ColoringPointsProcessor : public PointsProcessor {
  public:
   constexpr static const char* kConfigurationFileActionName = "color_points";
@@ -1726,7 +2045,15 @@ class ColoringPointsProcessor : public PointsProcessor {
   static FloatColor FromUint8(uint8_t r, uint8_t g, uint8_t b) { return FloatColor{{r / 255.f, g / 255.f, b / 255.f}}; }
 
   void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:48-56
-    if (batch->frame_id == frame_id_) batch->colors.assign(batch->points.size(), color_);
+    if (batch->frame_id == frame_id_) {
+      internal::DeviceBatch* d = batch->device_batch.get();
+      if (d != nullptr && d->host_stale) {
+        Check(dliom_points_batch_color(d->batch, color_.data()), "dliom_points_batch_color");
+      } else {
+        batch->device_batch.reset();
+        batch->colors.assign(batch->points.size(), color_);
+      }
+    }
     next_->Process(std::move(batch));
   }
   FlushResult Flush() override { return next_->Flush(); }
@@ -1745,7 +2072,15 @@ class IntensityToColorPointsProcessor : public PointsProcessor {
       : min_intensity_(min_intensity), max_intensity_(max_intensity), frame_id_(frame_id), next_(next) {}
 
   void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:47-60
+    internal::DeviceBatch* d = batch->device_batch.get();
+    if (d != nullptr && d->host_stale) {  // (a batch without intensities is left alone by the call itself)
+      if (frame_id_.empty() || batch->frame_id == frame_id_)
+        Check(dliom_points_batch_intensity_to_color(d->batch, min_intensity_, max_intensity_), "dliom_points_batch_intensity_to_color");
+      next_->Process(std::move(batch));
+      return;
+    }
     if (!batch->intensities.empty() && (frame_id_.empty() || batch->frame_id == frame_id_)) {
+      batch->device_batch.reset();
       batch->colors.clear();
       for (const float intensity : batch->intensities) {
         const float scaled = (intensity - min_intensity_) / (max_intensity_ - min_intensity_);
@@ -1848,7 +2183,22 @@ class XRayPointsProcessor : public PointsProcessor {
       if (timespan.start <= time && time <= timespan.end) return true;
     return false;
   }
-  void Insert(const PointsBatch& batch, dliom_points_xray* aggregation) {  // .cc:195-213
+  void Insert(const PointsBatch& batch_in, dliom_points_xray* aggregation) {  // .cc:195-213
+    if (const internal::DeviceBatch* d = internal::BatchOnDevice(context_, batch_in)) {
+      if (d->host_stale) {  // the colours are read where they are
+        Check(dliom_points_xray_insert_batch(aggregation, d->batch), "dliom_points_xray_insert_batch");
+        return;
+      }
+    }
+    PointsBatch synced;  // (a device batch of another context: by way of the host)
+    const PointsBatch* host = &batch_in;
+    if (batch_in.device_batch != nullptr && batch_in.device_batch->host_stale) {
+      synced.device_batch = batch_in.device_batch;
+      internal::SyncToHost(&synced);
+      synced.device_batch.reset();
+      host = &synced;
+    }
+    const PointsBatch& batch = *host;
     if (!batch.colors.empty() && batch.colors.size() < batch.points.size()) {
       std::fprintf(stderr, "Check failed: batch.colors.at(i)\n");  // std::out_of_range in the reference
       std::abort();

@@ -479,9 +479,14 @@ int dliom_trajectory_lookup(const dliom_trajectory* t, int64_t time, int* has, d
   return DLIOM_OK;
 }
 
-int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt, int64_t n,
-                                   const double sensor_to_tracking[7], dliom_cloud** out, float origin[3], int32_t* kept_index,
-                                   int64_t capacity, int64_t* num_kept) {
+}  // extern "C"
+
+// intensities (host, n floats, may be null): uploaded once beside the points; the kept ones are gathered by the indices the
+// scatter leaves in scratch into *kept_intensities (an empty block of the caller's; left empty when nothing is kept).
+int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt,
+                                       int64_t n, const double sensor_to_tracking[7], dliom_cloud** out, float origin[3],
+                                       int32_t* kept_index, int64_t capacity, int64_t* num_kept, const float* intensities,
+                                       AttrBlock* kept_intensities) {
   if (ctx == nullptr || traj == nullptr || traj->ctx != ctx || sensor_to_tracking == nullptr || out == nullptr || origin == nullptr ||
       num_kept == nullptr || n < 0 || n > INT32_MAX || capacity < 0 || (n > 0 && points_xyzt == nullptr) ||
       !pose_is_finite(sensor_to_tracking))
@@ -508,7 +513,7 @@ int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64
   DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, static_cast<const unsigned*>(nullptr), static_cast<unsigned*>(nullptr),
                                                  static_cast<int>(n), ctx->stream));
   const size_t per = align256(4 * static_cast<size_t>(n)), raw = align256(16 * static_cast<size_t>(n));
-  DLIOM_TRY(ctx->outlier.reserve(raw + 6 * per + align256(4 * kWords) + align256(tmp_bytes)));
+  DLIOM_TRY(ctx->outlier.reserve(raw + 6 * per + align256(4 * kWords) + align256(tmp_bytes) + (intensities != nullptr ? per : 0)));
   char* base = static_cast<char*>(ctx->outlier.p);
   const float4* d_points = reinterpret_cast<const float4*>(base);
   float* x = reinterpret_cast<float*>(base + raw);
@@ -519,9 +524,12 @@ int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64
   int* index = reinterpret_cast<int*>(base + raw + 5 * per);
   unsigned* words = reinterpret_cast<unsigned*>(base + raw + 6 * per);
   void* tmp = base + raw + 6 * per + align256(4 * kWords);
+  float* d_intensities = reinterpret_cast<float*>(base + raw + 6 * per + align256(4 * kWords) + align256(tmp_bytes));
   const FillJob fill{words, 4 * kHeadWords, 0u};
   DLIOM_TRY(fill_multi(ctx, &fill, 1));
   DLIOM_HIP_TRY(hipMemcpyAsync(base, points_xyzt, 16 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+  if (intensities != nullptr)
+    DLIOM_HIP_TRY(hipMemcpyAsync(d_intensities, intensities, 4 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, a, d_points, un, x, y, z, keep, words, 0);
   DLIOM_HIP_TRY(hipGetLastError());
   DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, keep, inclusive, static_cast<int>(n), ctx->stream));
@@ -596,6 +604,10 @@ int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64
                      index);
   int st = hipGetLastError() == hipSuccess ? DLIOM_OK : DLIOM_ERR_HIP;
   if (st == DLIOM_OK) st = finish_device_cloud(ctx, *out, std::sqrt(max_sq));  // sqrt is monotone: the max of the norms
+  if (st == DLIOM_OK && intensities != nullptr) {
+    st = kept_intensities->alloc(ctx, static_cast<size_t>(kept));
+    if (st == DLIOM_OK) st = gather_batch_attributes(ctx, index, kept, d_intensities, nullptr, kept_intensities->p, nullptr);
+  }
   if (st == DLIOM_OK && kept_index != nullptr) {
     if (hipMemcpyAsync(kept_index, index, static_cast<size_t>(kept) * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess)
@@ -605,9 +617,40 @@ int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64
   if (st != DLIOM_OK) {
     dliom_cloud_destroy(*out);
     *out = nullptr;
+    if (kept_intensities != nullptr) kept_intensities->release(ctx);
     return st;
   }
   std::memcpy(origin, &head[kWordOrigin], 12);
+  return DLIOM_OK;
+}
+
+extern "C" {
+
+int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt, int64_t n,
+                                   const double sensor_to_tracking[7], dliom_cloud** out, float origin[3], int32_t* kept_index,
+                                   int64_t capacity, int64_t* num_kept) {
+  return assemble_from_sensor_points(ctx, traj, cloud_time, points_xyzt, n, sensor_to_tracking, out, origin, kept_index, capacity,
+                                     num_kept, nullptr, nullptr);
+}
+
+int dliom_points_batch_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt,
+                                          const float* intensities, int64_t n, const double sensor_to_tracking[7],
+                                          dliom_points_batch** out) {
+  if (out == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  dliom_cloud* cloud = nullptr;
+  float origin[3] = {0.f, 0.f, 0.f};
+  int64_t kept = 0;
+  AttrBlock kept_intensities;
+  DLIOM_TRY(assemble_from_sensor_points(ctx, traj, cloud_time, points_xyzt, n, sensor_to_tracking, &cloud, origin, nullptr, 0, &kept,
+                                        intensities, &kept_intensities));
+  if (cloud == nullptr) return DLIOM_OK;  // nothing kept: the reference returns nullptr
+  dliom_points_batch* b = new dliom_points_batch;
+  b->ctx = ctx;
+  b->cloud = cloud;
+  std::memcpy(b->origin, origin, 12);
+  b->intensities = kept_intensities;
+  *out = b;
   return DLIOM_OK;
 }
 

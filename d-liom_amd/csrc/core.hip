@@ -624,6 +624,9 @@ int finish_device_cloud(dliom_ctx* ctx, dliom_cloud* c, float max_norm) {
 
 size_t staged_cloud_bytes(int64_t n) { return cloud_bytes(n); }
 
+int device_block_alloc(int device, size_t need, void** p, size_t* bytes) { return pool_alloc(device, need, p, bytes); }
+void device_block_free(int device, void* p, size_t bytes) { pool_free(device, p, bytes); }
+
 }  // namespace dliom
 
 using namespace dliom;

@@ -245,6 +245,32 @@ struct dliom_inserter {
   uint16_t* d_tables = nullptr;                 // [hit 32768 | miss 32768] in HBM
 };
 
+
+// `count` floats in a block of the cloud pool (power-of-two size classes; handed back after a device synchronise)
+namespace dliom {
+struct AttrBlock {
+  void* base = nullptr;
+  size_t bytes = 0;
+  float* p = nullptr;
+  int alloc(dliom_ctx* ctx, size_t count);  // (this block must be empty)
+  void release(dliom_ctx* ctx);
+};
+}  // namespace dliom
+
+// The points-processor batch in HBM (points_batch.hip): io::PointsBatch's points, origin, intensities and colors.
+// has_* mean "one a point": an empty batch has neither attribute, like the reference's empty vectors.
+struct dliom_points_batch {
+  dliom_ctx* ctx = nullptr;
+  dliom_cloud* cloud = nullptr;  // owned
+  float origin[3] = {0.f, 0.f, 0.f};
+  dliom::AttrBlock intensities;  // n floats, or empty
+  dliom::AttrBlock colors;       // 3 n floats (r g b a point), or empty
+  bool single_color = false;     // every point has `rgb` (what color_points leaves); `colors` is empty then
+  float rgb[3] = {0.f, 0.f, 0.f};
+  bool has_intensities() const { return intensities.p != nullptr && cloud->n > 0; }
+  bool has_colors() const { return (colors.p != nullptr || single_color) && cloud->n > 0; }
+};
+
 namespace dliom {
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remembered per context, not per thread or process
 enum : unsigned { kFuncAttrScoreBox = 1u, kFuncAttrHistogram = 2u, kFuncAttrStdSortDiag = 4u, kFuncAttrHistogramBig = 8u,
@@ -325,6 +351,31 @@ int wait_done(dliom_ctx* ctx, hipStream_t stream, const unsigned* done_word, uns
 int gather_and_wait(dliom_ctx* ctx, const GatherJob* jobs, int num_jobs, void* pinned_dst);
 // 64 device words that are zero and that nobody writes (zeroed on ctx->stream at first use)
 int zero_words(dliom_ctx* ctx, unsigned** out);
+int device_block_alloc(int device, size_t need, void** p, size_t* bytes);  // the cloud pool (core.hip)
+void device_block_free(int device, void* p, size_t bytes);
+// ---- outlier.hip: keep flags -> order-preserving compaction, shared by the export stages
+// Scratch of one compaction in ctx->outlier: a stage's kernel writes keep[i] in {0, 1} and the largest squared norm of the
+// kept points (as bits) to *max_sq, then calls compact_kept / compact_batch.  `extra_bytes` more are carved behind, at *extra.
+struct CompactScratch {
+  unsigned *keep, *inclusive, *max_sq;
+  int* index;
+  void* tmp;
+  size_t tmp_bytes;
+  void* extra;
+};
+int carve_compact(dliom_ctx* ctx, int64_t n, CompactScratch* s, size_t extra_bytes = 0);
+// dst[j] = src[index[j]] for the kept points, on ctx->stream (either source may be null)
+int gather_batch_attributes(dliom_ctx* ctx, const int* d_index, int64_t kept, const float* src_intensities, const float* src_colors,
+                            float* dst_intensities, float* dst_colors);
+// Compacts the batch in place by the flags in `s`: points and attributes, one read-back (count, max squared norm,
+// *flag_word if given).  A non-zero flag leaves the batch alone and returns DLIOM_OK: the caller decides.  Any failure
+// leaves the batch as it was.
+int compact_batch(dliom_points_batch* batch, const CompactScratch& s, const unsigned* flag_word, unsigned* flag, int64_t* num_kept);
+// assemble.hip: dliom_cloud_from_sensor_points with the kept points' intensities (host, n floats, may be null) gathered on
+// the device into *kept_intensities (left empty when there are none or nothing is kept)
+int assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt, int64_t n,
+                                const double sensor_to_tracking[7], dliom_cloud** out, float origin[3], int32_t* kept_index,
+                                int64_t capacity, int64_t* num_kept, const float* intensities, AttrBlock* kept_intensities);
 // sequential_sums.hip: the reference's sequential `score += probability` float sums, bit-identical.
 // Launches the kernels for `count` candidates whose indices are in d_list (c -> translation c / R, rotation c % R):
 // method 0 = one lane replays the loop, 1 = element scan, 2 = chunk scan.  Methods 1 and 2 need the 15-bit values of a

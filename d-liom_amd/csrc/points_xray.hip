@@ -517,10 +517,12 @@ int dliom_points_xray_destroy(dliom_points_xray* x) {
   return DLIOM_OK;
 }
 
-int dliom_points_xray_insert(dliom_points_xray* x, const dliom_cloud* points, const float* colors_rgb, int64_t num_colors) {
-  if (x == nullptr || points == nullptr || points->n > INT32_MAX) return DLIOM_ERR_INVALID_ARGUMENT;
-  if (num_colors != 0 && num_colors != 1 && num_colors != points->n) return DLIOM_ERR_INVALID_ARGUMENT;
-  if (num_colors != 0 && colors_rgb == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+}  // extern "C"
+
+// Insert with the colours where they are.  num_colors 0 or 1: `rgb` is the batch's colour (host, 3 floats; unread for 0).
+// One a point: d_colors (device, r g b a point) is read in place; when it is null, h_colors (host) is uploaded first.
+static int xray_insert(dliom_points_xray* x, const dliom_cloud* points, int64_t num_colors, const float* rgb, const float* d_colors,
+                       const float* h_colors) {
   if (points->n == 0) return DLIOM_OK;
   dliom_ctx* ctx = x->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
@@ -571,24 +573,24 @@ int dliom_points_xray_insert(dliom_points_xray* x, const dliom_cloud* points, co
   float* colors = reinterpret_cast<float*>(b + 5 * per + align256(16 * static_cast<size_t>(n)));
   void* sort_tmp = b + 5 * per + align256(16 * static_cast<size_t>(n)) + align256(12 * static_cast<size_t>(n));
 
-  if (per_point) {
+  if (per_point && d_colors == nullptr) {
     // The caller's buffer is free when the call returns, page-locked or not; everything before the copy has finished.
-    DLIOM_HIP_TRY(hipMemcpyAsync(colors, colors_rgb, 12 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+    DLIOM_HIP_TRY(hipMemcpyAsync(colors, h_colors, 12 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     ++ctx->host_syncs;
+    d_colors = colors;
   }
   hipLaunchKernelGGL(xray_mark_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, points->d_x, points->d_y, points->d_z, n,
                      x->view(), x->d_occupied, per_point ? nullptr : x->d_pending, point_column, per_point ? point_index : nullptr,
                      static_cast<unsigned>(columns), x->d_words);
   if (!per_point) {
-    const float r = num_colors == 1 ? colors_rgb[0] : 0.f, g = num_colors == 1 ? colors_rgb[1] : 0.f,
-                bl = num_colors == 1 ? colors_rgb[2] : 0.f;
+    const float r = num_colors == 1 ? rgb[0] : 0.f, g = num_colors == 1 ? rgb[1] : 0.f, bl = num_colors == 1 ? rgb[2] : 0.f;
     hipLaunchKernelGGL(xray_settle_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, point_column, n,
                        static_cast<unsigned>(columns), x->d_pending, x->d_data, r, g, bl, num_colors == 1 ? 1 : 0, x->d_words);
   } else {
     DLIOM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, point_column, sorted_column, point_index, sorted_index,
                                                      static_cast<int>(n), 0, end_bit, ctx->stream));
-    hipLaunchKernelGGL(xray_gather_colors_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, sorted_index, colors, n, sorted_rgb);
+    hipLaunchKernelGGL(xray_gather_colors_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, sorted_index, d_colors, n, sorted_rgb);
     hipLaunchKernelGGL(xray_short_columns_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, sorted_column, sorted_rgb, n,
                        static_cast<unsigned>(columns), x->d_data, long_list, x->d_words);
     // a wavefront per list entry; the list has at most n / (kShortSegment + 1) of them
@@ -601,6 +603,31 @@ int dliom_points_xray_insert(dliom_points_xray* x, const dliom_cloud* points, co
   ++x->inserts;
   x->points += points->n;
   return DLIOM_OK;
+}
+
+extern "C" {
+
+int dliom_points_xray_insert(dliom_points_xray* x, const dliom_cloud* points, const float* colors_rgb, int64_t num_colors) {
+  if (x == nullptr || points == nullptr || points->n > INT32_MAX) return DLIOM_ERR_INVALID_ARGUMENT;
+  if (num_colors != 0 && num_colors != 1 && num_colors != points->n) return DLIOM_ERR_INVALID_ARGUMENT;
+  if (num_colors != 0 && colors_rgb == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  return xray_insert(x, points, num_colors, colors_rgb, nullptr, colors_rgb);
+}
+
+int dliom_points_xray_insert_batch(dliom_points_xray* x, const dliom_points_batch* batch) {
+  if (x == nullptr || batch == nullptr || batch->ctx != x->ctx || batch->cloud->n > INT32_MAX) return DLIOM_ERR_INVALID_ARGUMENT;
+  const dliom_cloud* points = batch->cloud;
+  if (!batch->has_colors()) return xray_insert(x, points, 0, nullptr, nullptr, nullptr);
+  if (batch->single_color) return xray_insert(x, points, 1, batch->rgb, nullptr, nullptr);
+  if (points->n == 1) {  // one point, one colour: the single-colour path reads it from the host, as the host entry does
+    float rgb[3];
+    DLIOM_HIP_TRY(hipSetDevice(x->ctx->device));
+    DLIOM_HIP_TRY(hipMemcpyAsync(rgb, batch->colors.p, 12, hipMemcpyDeviceToHost, x->ctx->stream));
+    DLIOM_HIP_TRY(hipStreamSynchronize(x->ctx->stream));
+    ++x->ctx->host_syncs;
+    return xray_insert(x, points, 1, rgb, nullptr, nullptr);
+  }
+  return xray_insert(x, points, points->n, nullptr, batch->colors.p, nullptr);
 }
 
 int dliom_points_xray_bounding_box(const dliom_points_xray* x, int32_t box_min[3], int32_t box_max[3], int* empty) {

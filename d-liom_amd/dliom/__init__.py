@@ -212,6 +212,13 @@ class PointsXrayStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class FixedRatioSamplerStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("chunks", "repaired_chunks", "repair_passes")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class ProbabilityGridStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("bytes", "growths", "inserts", "cells_visited")] + [("known_box", C.c_int32 * 4),
                                                                                              ("error_word", C.c_int32)]
@@ -301,6 +308,29 @@ SYMBOLS = [
     ("dliom_assemble_check_stats", C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p]),
     ("dliom_cloud_min_max_range_filter", C.c_int, [_vp, _vp, _f32p, C.c_double, C.c_double, C.POINTER(_vp), _i32p, C.c_int64,
                                                    _i64p]),
+    ("dliom_points_batch_create", C.c_int, [_vp, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64, C.POINTER(_vp)]),
+    ("dliom_points_batch_destroy", C.c_int, [_vp]),
+    ("dliom_points_batch_size", C.c_int, [_vp, _i64p]),
+    ("dliom_points_batch_has_intensities", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("dliom_points_batch_has_colors", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("dliom_points_batch_cloud", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("dliom_points_batch_origin", C.c_int, [_vp, _f32p]),
+    ("dliom_points_batch_download", C.c_int, [_vp, _f32p, _f32p, _f32p]),
+    ("dliom_points_batch_from_sensor_points", C.c_int, [_vp, _vp, C.c_int64, _f32p, _f32p, C.c_int64, _f64p, C.POINTER(_vp)]),
+    ("dliom_points_batch_min_max_range_filter", C.c_int, [_vp, C.c_double, C.c_double]),
+    ("dliom_outlier_remover_filter_batch", C.c_int, [_vp, _vp]),
+    ("dliom_points_batch_color", C.c_int, [_vp, _f32p]),
+    ("dliom_points_batch_intensity_to_color", C.c_int, [_vp, C.c_float, C.c_float]),
+    ("dliom_points_xray_insert_batch", C.c_int, [_vp, _vp]),
+    ("dliom_fixed_ratio_sampler_create", C.c_int, [C.c_double, C.POINTER(_vp)]),
+    ("dliom_fixed_ratio_sampler_destroy", C.c_int, [_vp]),
+    ("dliom_fixed_ratio_sampler_reset", C.c_int, [_vp]),
+    ("dliom_fixed_ratio_sampler_state", C.c_int, [_vp, _i64p, _i64p]),
+    ("dliom_fixed_ratio_sampler_stats", C.c_int, [_vp, C.POINTER(FixedRatioSamplerStats)]),
+    ("dliom_points_batch_fixed_ratio_sample", C.c_int, [_vp, _vp]),
+    ("dliom_points_batch_pack", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int64, _i64p]),
+    ("dliom_ply_header", C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_char_p, C.c_int64, _i64p]),
+    ("dliom_pcd_header", C.c_int, [C.c_int, C.c_int64, C.c_char_p, C.c_int64, _i64p]),
     ("dliom_rtcsm3d_match", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _f32p, C.c_int64, _vp, _f64p, _f32p]),
     ("dliom_rtcsm3d_match_cloud", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _vp, _vp, _f64p, _f32p]),
     ("dliom_rtcsm3d_shard_begin", C.c_int, [_vp, C.POINTER(RtcsmOptions), _f64p, _vp, _vp, C.c_int, C.c_int,
@@ -874,6 +904,187 @@ class PointsXray:
             self.close()
         except Exception:
             pass
+
+
+PACK_PLY, PACK_PCD = 0, 1
+
+
+class _BorrowedCloud:
+    """The points of a PointsBatch as the stages that take a dliom_cloud see them (not owned: no close)."""
+
+    def __init__(self, handle, n):
+        self.h, self.n = handle, n
+
+    def __len__(self):
+        return self.n
+
+
+class PointsBatch:
+    """io::PointsBatch in HBM (dliom_points_batch): map-frame points, the origin, and optionally one intensity and one
+    colour a point.  The stages below rewrite it in place; nothing but counts comes back until download() or pack()."""
+
+    def __init__(self, ctx, points=None, origin=(0, 0, 0), intensities=None, colors=None, _handle=None):
+        self._L = ctx._L
+        self.ctx = ctx
+        if _handle is not None:
+            self.h = _handle
+            return
+        pts = _f32(points).reshape(-1, 3)
+        it = None if intensities is None else _f32(intensities).reshape(-1)
+        col = None if colors is None else _f32(colors).reshape(-1, 3)
+        if it is not None and len(it) != len(pts):
+            raise DliomError(ERR_INVALID_ARGUMENT, "one intensity a point")
+        h = _vp()
+        _check(self._L.dliom_points_batch_create(ctx.h, _p(pts, _f32p), len(pts), _p(_f32(origin), _f32p),
+                                                 None if it is None else _p(it, _f32p), None if col is None else _p(col, _f32p),
+                                                 0 if col is None else len(col), C.byref(h)), "dliom_points_batch_create")
+        self.h = h
+
+    @classmethod
+    def from_sensor_points(cls, trajectory, cloud_time, points_xyzt, sensor_to_tracking, intensities=None):
+        """dliom_points_batch_from_sensor_points -> PointsBatch, or None when no point is kept."""
+        pts = _f32(points_xyzt).reshape(-1, 4)
+        it = None if intensities is None else _f32(intensities).reshape(-1)
+        if it is not None and len(it) != len(pts):
+            raise DliomError(ERR_INVALID_ARGUMENT, "one intensity a point")
+        h = _vp()
+        _check(trajectory._L.dliom_points_batch_from_sensor_points(
+            trajectory.ctx.h, trajectory.h, int(cloud_time), _p(pts, _f32p), None if it is None else _p(it, _f32p), len(pts),
+            _p(_f64(sensor_to_tracking), _f64p), C.byref(h)), "dliom_points_batch_from_sensor_points")
+        return cls(trajectory.ctx, _handle=h) if h else None
+
+    def __len__(self):
+        n = C.c_int64()
+        _check(self._L.dliom_points_batch_size(self.h, C.byref(n)), "dliom_points_batch_size")
+        return int(n.value)
+
+    @property
+    def has_intensities(self):
+        v = C.c_int()
+        _check(self._L.dliom_points_batch_has_intensities(self.h, C.byref(v)), "dliom_points_batch_has_intensities")
+        return bool(v.value)
+
+    @property
+    def has_colors(self):
+        v = C.c_int()
+        _check(self._L.dliom_points_batch_has_colors(self.h, C.byref(v)), "dliom_points_batch_has_colors")
+        return bool(v.value)
+
+    @property
+    def origin(self):
+        o = np.zeros(3, dtype=np.float32)
+        _check(self._L.dliom_points_batch_origin(self.h, _p(o, _f32p)), "dliom_points_batch_origin")
+        return o
+
+    def cloud(self):
+        """The points, borrowed, for OutlierRemover.mark_hits / count_rays and the inserters: valid until the next
+        compacting call on this batch."""
+        h = _vp()
+        _check(self._L.dliom_points_batch_cloud(self.h, C.byref(h)), "dliom_points_batch_cloud")
+        return _BorrowedCloud(h, len(self))
+
+    def download(self):
+        """-> (points float32 (n, 3), intensities float32 (n,) or None, colors float32 (n, 3) or None)"""
+        n = len(self)
+        pts = np.zeros((n, 3), dtype=np.float32)
+        it = np.zeros(n, dtype=np.float32) if self.has_intensities else None
+        col = np.zeros((n, 3), dtype=np.float32) if self.has_colors else None
+        _check(self._L.dliom_points_batch_download(self.h, _p(pts, _f32p), None if it is None else _p(it, _f32p),
+                                                   None if col is None else _p(col, _f32p)), "dliom_points_batch_download")
+        return pts, it, col
+
+    def min_max_range_filter(self, min_range, max_range):
+        _check(self._L.dliom_points_batch_min_max_range_filter(self.h, float(min_range), float(max_range)),
+               "dliom_points_batch_min_max_range_filter")
+
+    def remove_outliers(self, remover):
+        """Phase three of an OutlierRemover, in place."""
+        _check(self._L.dliom_outlier_remover_filter_batch(remover.h, self.h), "dliom_outlier_remover_filter_batch")
+
+    def fixed_ratio_sample(self, sampler):
+        _check(self._L.dliom_points_batch_fixed_ratio_sample(sampler.h, self.h), "dliom_points_batch_fixed_ratio_sample")
+
+    def color(self, rgb):
+        _check(self._L.dliom_points_batch_color(self.h, _p(_f32(rgb), _f32p)), "dliom_points_batch_color")
+
+    def intensity_to_color(self, min_intensity, max_intensity):
+        _check(self._L.dliom_points_batch_intensity_to_color(self.h, C.c_float(min_intensity), C.c_float(max_intensity)),
+               "dliom_points_batch_intensity_to_color")
+
+    def xray_insert(self, xray):
+        _check(self._L.dliom_points_xray_insert_batch(xray.h, self.h), "dliom_points_xray_insert_batch")
+
+    def pack_size(self, fmt, with_colors, with_intensities=False):
+        n = C.c_int64()
+        _check(self._L.dliom_points_batch_pack(self.h, int(fmt), int(with_colors), int(with_intensities), None, 0, C.byref(n)),
+               "dliom_points_batch_pack")
+        return int(n.value)
+
+    def pack(self, fmt, with_colors, with_intensities=False, capacity=None, fill=0):
+        """The writers' records -> uint8 array of `capacity` bytes (default: exactly the size) pre-filled with `fill`, and
+        the number of bytes written."""
+        size = self.pack_size(fmt, with_colors, with_intensities)
+        out = np.full(size if capacity is None else int(capacity), fill, dtype=np.uint8)
+        n = C.c_int64()
+        _check(self._L.dliom_points_batch_pack(self.h, int(fmt), int(with_colors), int(with_intensities),
+                                               _p(out, C.POINTER(C.c_uint8)), len(out), C.byref(n)), "dliom_points_batch_pack")
+        return out, int(n.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_points_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FixedRatioSampler:
+    """common::FixedRatioSampler whose Pulse() loop over a batch runs on the device (dliom_fixed_ratio_sampler)."""
+
+    def __init__(self, ratio):
+        self._L = load_library()
+        h = _vp()
+        _check(self._L.dliom_fixed_ratio_sampler_create(float(ratio), C.byref(h)), "dliom_fixed_ratio_sampler_create")
+        self.h = h
+
+    def reset(self):
+        _check(self._L.dliom_fixed_ratio_sampler_reset(self.h), "dliom_fixed_ratio_sampler_reset")
+
+    def state(self):
+        """-> (num_pulses, num_samples)"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self._L.dliom_fixed_ratio_sampler_state(self.h, C.byref(a), C.byref(b)), "dliom_fixed_ratio_sampler_state")
+        return int(a.value), int(b.value)
+
+    def stats(self):
+        s = FixedRatioSamplerStats()
+        _check(self._L.dliom_fixed_ratio_sampler_stats(self.h, C.byref(s)), "dliom_fixed_ratio_sampler_stats")
+        return s.as_dict()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_fixed_ratio_sampler_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ply_header(with_colors, with_intensities, num_points):
+    """WriteBinaryPlyHeader (io/ply_writing_points_processor.cc:35-56) -> bytes."""
+    return _text(lambda b, c, n: load_library().dliom_ply_header(int(with_colors), int(with_intensities), int(num_points), b, c, n))
+
+
+def pcd_header(with_colors, num_points):
+    """WriteBinaryPcdHeader (io/pcd_writing_points_processor.cc:35-57) -> bytes."""
+    return _text(lambda b, c, n: load_library().dliom_pcd_header(int(with_colors), int(num_points), b, c, n))
 
 
 KERNEL_PG_HITS, KERNEL_PG_RAYS, KERNEL_PG_CLEAR = 6, 7, 8

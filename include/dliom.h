@@ -667,6 +667,99 @@ int dliom_points_xray_stats(const dliom_points_xray* xray, dliom_points_xray_sta
  * fullest column has max_occupied, with the column's mean colour.  occupied == 0: white.  What the device paints. */
 int dliom_points_xray_pixel(uint32_t occupied, uint32_t max_occupied, const float mean_rgb[3], uint32_t* argb);
 
+/* ---- Export batches in HBM: io::PointsBatch with its intensities and colours on the device (cartographer/io) ----
+ * A dliom_points_batch owns one dliom_cloud of map-frame points, the origin (host), and optionally one intensity and one
+ * colour (r, g, b) a point, all in HBM.  The stages below read and rewrite it where it is: every compacting stage is
+ * RemovePoints (io/points_batch.cc:22-49) on the three vectors at once, and reads back the kept count and nothing else.
+ * Attribute counts are 0 or the number of points, as RemovePoints assumes (:40-45 index past the end otherwise); an
+ * empty batch has neither attribute, like the reference's empty vectors.
+ *
+ * NULL pointers, a count that is negative or neither 0 nor n, NaN bounds and an object of another context are refused
+ * with DLIOM_ERR_INVALID_ARGUMENT before anything touches a device.  A failed call leaves the batch as it was.
+ * Blocks go back to the cloud pool like a cloud's, each after a whole-device synchronise (not counted by
+ * dliom_ctx_synchronizations): a compacting call gives back up to three (cloud, intensities, colours), dliom_points_batch_color
+ * one when the batch held a colour a point. */
+typedef struct dliom_points_batch dliom_points_batch;
+/* points_xyz: n points; origin: 3 floats; intensities: n floats or NULL; colors_rgb: num_colors * 3 floats, num_colors 0
+ * (colors_rgb may be NULL) or n.  Host pointers, free when the call returns. */
+int dliom_points_batch_create(dliom_ctx* ctx, const float* points_xyz, int64_t n, const float origin[3], const float* intensities,
+                              const float* colors_rgb, int64_t num_colors, dliom_points_batch** out);
+int dliom_points_batch_destroy(dliom_points_batch* batch);
+int dliom_points_batch_size(const dliom_points_batch* batch, int64_t* n);
+int dliom_points_batch_has_intensities(const dliom_points_batch* batch, int* has);
+int dliom_points_batch_has_colors(const dliom_points_batch* batch, int* has);
+/* The batch's points, borrowed: valid until the next call that compacts or destroys the batch.  What
+ * dliom_outlier_remover_mark_hits / _count_rays, dliom_inserter2d_insert_cloud and dliom_inserter_insert_cloud take. */
+int dliom_points_batch_cloud(const dliom_points_batch* batch, const dliom_cloud** cloud);
+int dliom_points_batch_origin(const dliom_points_batch* batch, float origin[3]);
+/* points_xyz 3 n floats, intensities n, colors_rgb 3 n; any of them may be NULL.  A requested attribute the batch does
+ * not have is refused. */
+int dliom_points_batch_download(const dliom_points_batch* batch, float* points_xyz, float* intensities, float* colors_rgb);
+/* dliom_cloud_from_sensor_points with the kept points' intensities (n floats or NULL) gathered on the device in the same
+ * call: the message's intensities are uploaded once and never come back.  *out is NULL with DLIOM_OK when nothing is
+ * kept.  Refusals and the per-call exactness check are dliom_cloud_from_sensor_points' own. */
+int dliom_points_batch_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* trajectory, int64_t cloud_time, const float* points_xyzt,
+                                          const float* intensities, int64_t n, const double sensor_to_tracking[7],
+                                          dliom_points_batch** out);
+/* dliom_cloud_min_max_range_filter about the batch's origin, in place. */
+int dliom_points_batch_min_max_range_filter(dliom_points_batch* batch, double min_range, double max_range);
+/* dliom_outlier_remover_filter (phase three), in place. */
+int dliom_outlier_remover_filter_batch(dliom_outlier_remover* remover, dliom_points_batch* batch);
+/* ColoringPointsProcessor::Process (io/coloring_points_processor.cc:45-53): every point gets rgb.  (The frame_id
+ * comparison is the caller's.) */
+int dliom_points_batch_color(dliom_points_batch* batch, const float rgb[3]);
+/* IntensityToColorPointsProcessor::Process (io/intensity_to_color_points_processor.cc:47-58): gray =
+ * Clamp((intensity - min) / (max - min), 0.f, 1.f) in float with IEEE division; common::Clamp (common/math.h:32-40) lets
+ * NaN through, and max == min gives the host's infinities and NaNs.  A batch without intensities is left alone. */
+int dliom_points_batch_intensity_to_color(dliom_points_batch* batch, float min_intensity, float max_intensity);
+/* dliom_points_xray_insert with the batch's colours read where they are (none: black; one for the batch; one a point).
+ * A batch of ONE point with a per-point colour reads those 12 bytes back first (one stream synchronise): the insert's
+ * single-colour path takes its colour from the host, as it does for the host entry. */
+int dliom_points_xray_insert_batch(dliom_points_xray* xray, const dliom_points_batch* batch);
+
+/* common::FixedRatioSampler (common/fixed_ratio_sampler.cc:32-39) behind io::FixedRatioSamplingPointsProcessor
+ * (io/fixed_ratio_sampling_points_processor.cc:43-53): per point, ++num_pulses; kept iff
+ * double(num_samples) / num_pulses < ratio, then ++num_samples.  Both counters are int64 and run on from batch to batch.
+ * The device runs chunks of consecutive pulses from guessed starting counts, proves every chunk's start against its
+ * predecessor's end, and re-runs the chunks whose start was wrong until none is: the result is the sequential loop's,
+ * whatever the guess.  A ratio outside [0, 1] or NaN is refused (CHECK_GE / CHECK_LE). */
+typedef struct dliom_fixed_ratio_sampler dliom_fixed_ratio_sampler;
+typedef struct dliom_fixed_ratio_sampler_statistics {
+  int64_t chunks;          /* chunks run so far, first passes only */
+  int64_t repaired_chunks; /* chunks re-run because their guessed start was wrong */
+  int64_t repair_passes;   /* passes after the first, over all calls */
+} dliom_fixed_ratio_sampler_statistics;
+int dliom_fixed_ratio_sampler_create(double ratio, dliom_fixed_ratio_sampler** out);
+int dliom_fixed_ratio_sampler_destroy(dliom_fixed_ratio_sampler* sampler);
+/* (0, 0) again: what Flush does when the stream restarts. */
+int dliom_fixed_ratio_sampler_reset(dliom_fixed_ratio_sampler* sampler);
+int dliom_fixed_ratio_sampler_state(const dliom_fixed_ratio_sampler* sampler, int64_t* num_pulses, int64_t* num_samples);
+int dliom_fixed_ratio_sampler_stats(const dliom_fixed_ratio_sampler* sampler, dliom_fixed_ratio_sampler_statistics* out);
+/* One Pulse() a point, in order; the batch is compacted in place and the state advances by its size.  One read-back a
+ * pass (kept count and the number of wrong starts together). */
+int dliom_points_batch_fixed_ratio_sample(dliom_fixed_ratio_sampler* sampler, dliom_points_batch* batch);
+
+/* The writers' per-point loops (io/ply_writing_points_processor.cc:138-147, io/pcd_writing_points_processor.cc:121-128)
+ * as packed records, built on the device and downloaded in one copy.
+ *   PLY: x y z (little-endian floats) [r g b bytes: ToUint8Color] [intensity float]       12, 15, 16 or 19 bytes
+ *   PCD: x y z [b g r 0 bytes]                                                         12 or 16 bytes
+ * ToUint8Color (io/color.h:35-45) is uint8(lround(Clamp(c, 0.f, 1.f) * 255)): a float product rounded half away from
+ * zero; infinite components clamp; a NaN component gives an unspecified byte, as lround does in the reference.
+ * with_colors / with_intensities are the FILE's layout, decided by the writer at its first non-empty batch; a non-empty
+ * batch that lacks an attribute the file has is refused (the reference's CHECK_EQ).  PCD never writes intensities
+ * (with_intensities must be 0) and takes its colours from the batch: with_colors must equal the batch's own.
+ * *num_bytes is always filled; bytes NULL: the size only; capacity < *num_bytes: DLIOM_ERR_CAPACITY.  Exactly *num_bytes
+ * bytes are written. */
+#define DLIOM_PACK_PLY 0
+#define DLIOM_PACK_PCD 1
+int dliom_points_batch_pack(const dliom_points_batch* batch, int format, int with_colors, int with_intensities, uint8_t* bytes,
+                            int64_t capacity, int64_t* num_bytes);
+/* WriteBinaryPlyHeader (.cc:35-56) and WriteBinaryPcdHeader (.cc:35-57), byte for byte (host only): the count is
+ * zero-padded to 15 digits, so the placeholder written with count 0 and the final header have one length.  buffer,
+ * capacity, *length as dliom_ros_map_pgm_header.  A negative count is refused. */
+int dliom_ply_header(int with_colors, int with_intensities, int64_t num_points, char* buffer, int64_t capacity, int64_t* length);
+int dliom_pcd_header(int with_colors, int64_t num_points, char* buffer, int64_t capacity, int64_t* length);
+
 /* ---- 2D probability grid of the export pipeline (the actions "write_probability_grid" and "write_ros_map") ----
  * io::ProbabilityGridPointsProcessor (io/probability_grid_points_processor.{h,cc}) and
  * cartographer_ros::RosMapWritingPointsProcessor (ros_map_writing_points_processor.cc:52-94, ros_map.cc:21-47) insert
