@@ -14,8 +14,6 @@
 // the device (OCML) and the reference's host (glibc) can differ.  Every point whose seven casts to float could land on
 // another float under the documented bounds of the two libraries is recorded, recomputed on the host with glibc and
 // redone if it differs (assemble_pose is ONE source for both sides): equality is proven per call, not sampled.
-#include <hipcub/hipcub.hpp>
-
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -27,9 +25,10 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kRing = 120;                     // records a launch keeps in the words that are read back anyway
-enum { kWordBadTime = 0, kWordRecords = 1, kWordMaxSq = 2, kWordOrigin = 3 /* 3 floats */, kWordLast = 6, kHeadWords = 8 };
+enum { kWordBadTime = 0, kWordRecords = 1, /* 2, 7: free */ kWordOrigin = 3 /* 3 floats */, kWordLast = 6, kHeadWords = 8 };
 constexpr int kRecordWords = 8;                // point index, bits of the seven floats (tx ty tz qw qx qy qz)
-constexpr int kWords = kHeadWords + kRecordWords * kRing;  // 968: one job of gather_to_pinned beside the count
+constexpr int kWords = kHeadWords + kRecordWords * kRing;  // 968: one job of read_kept beside the count and the maximum
+static_assert(4 * (2 + kWords) <= kPinReadback.bytes && kWords <= 1024, "the call's one read-back: count, maximum, words");
 constexpr double kTicksPerSecond = 1e7;        // common::Time: 100 ns
 
 struct AssembleArgs {
@@ -195,21 +194,7 @@ __device__ __forceinline__ void transform_point(const float f[7], float px, floa
   *z = rz + f[2];
 }
 
-// The squared norm of a kept point as the word that the maximum is taken of: cloud_max_norm's order; bit patterns of
-// non-negative floats keep their order; 0 for a NaN (and for a point that is not kept).
-__device__ __forceinline__ unsigned norm_word(float x, float y, float z) {
-  const float sq = x * x + (y * y + z * z);
-  return sq == sq ? __float_as_uint(sq) : 0u;
-}
-// Called by every lane of a wavefront: the wavefront's maximum by six shuffles, then one atomic a wavefront instead of
-// one a point on the same word.
-__device__ __forceinline__ void note_kept(unsigned word, unsigned* max_sq) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) word = max(word, static_cast<unsigned>(__shfl_xor(static_cast<int>(word), off, 64)));
-  if ((threadIdx.x & 63u) == 0u && word != 0u) atomicMax(max_sq, word);
-}
-
-// Point i: keep[i] = Has(time_i); the transformed point goes to x/y/z[i] (compacted by the scatter below).  Returns the
+// Point i: keep[i] = Has(time_i); the transformed point goes to x/y/z[i] (compacted by compact.hip's scatter).  Returns the
 // norm word of a kept point, else 0.
 __device__ __forceinline__ unsigned assemble_point(const AssembleArgs& a, const float4* __restrict__ points, unsigned i,
                                                    float* __restrict__ x, float* __restrict__ y, float* __restrict__ z,
@@ -258,15 +243,15 @@ __device__ __forceinline__ unsigned assemble_point(const AssembleArgs& a, const 
   return norm_word(ox, oy, oz);
 }
 
-// One point a thread.  words: the call's device words (kWords of them, layout above).  only_records: nothing but the
-// records is written, into `words` = [count | records] with room for every point (the pass after a ring that overflowed).
+// One point a thread.  words: the call's device words (kWords of them, layout above); max_sq: the compaction's.  only_records:
+// nothing but the records is written, into `words` = [count | records] with room for every point (after a ring overflowed).
 __global__ __launch_bounds__(kBlock) void assemble_kernel(AssembleArgs a, const float4* __restrict__ points, unsigned n,
                                                           float* __restrict__ x, float* __restrict__ y, float* __restrict__ z,
                                                           unsigned* __restrict__ keep, unsigned* __restrict__ words,
-                                                          int only_records) {
+                                                          unsigned* __restrict__ max_sq, int only_records) {
   const unsigned i = blockIdx.x * kBlock + threadIdx.x;
   const unsigned word = i < n ? assemble_point(a, points, i, x, y, z, keep, words, only_records) : 0u;
-  if (!only_records) note_kept(word, &words[kWordMaxSq]);
+  if (!only_records) note_kept(word, max_sq);
 }
 
 // "We use the last transform for the origin": sensor_to_map * Zero of the last kept point, found in the scan of the keep
@@ -316,30 +301,6 @@ __global__ void assemble_fix_kernel(const float4* __restrict__ points, unsigned 
     words[kWordOrigin + 1] = __float_as_uint(oy);
     words[kWordOrigin + 2] = __float_as_uint(oz);
   }
-}
-
-// the largest squared norm of the kept points once more (after a fix moved some of them)
-__global__ __launch_bounds__(kBlock) void assemble_max_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                              const float* __restrict__ z, const unsigned* __restrict__ keep,
-                                                              unsigned n, unsigned* __restrict__ words) {
-  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-  note_kept(i < n && keep[i] != 0u ? norm_word(x[i], y[i], z[i]) : 0u, &words[kWordMaxSq]);
-}
-
-// RemovePoints' order (outlier.hip's scatter): the survivors in input order, and their input indices
-__global__ __launch_bounds__(kBlock) void assemble_scatter_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                                  const float* __restrict__ z, unsigned n,
-                                                                  const unsigned* __restrict__ keep,
-                                                                  const unsigned* __restrict__ inclusive, float* __restrict__ ox,
-                                                                  float* __restrict__ oy, float* __restrict__ oz,
-                                                                  int* __restrict__ index) {
-  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n || keep[i] == 0u) return;
-  const unsigned at = inclusive[i] - 1u;
-  ox[at] = x[i];
-  oy[at] = y[i];
-  oz[at] = z[i];
-  index[at] = static_cast<int>(i);
 }
 
 // Every record once more on the HOST -- assemble_pose with glibc's sin, the reference's own -- against the floats the
@@ -507,39 +468,31 @@ int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, i
   if (ctx->tuning[DLIOM_TUNE_RESERVED_TEST_HOOK] >= 4) a.wide = 1;
   if (ctx->tuning[DLIOM_TUNE_RESERVED_TEST_HOOK] == 5) a.perturb = 1;
 #endif
-  // scratch: raw points | x | y | z | keep | inclusive | index | words | the scan's temporary storage
+  // behind the compaction's scratch: words | raw points | x | y | z | intensities
   const unsigned un = static_cast<unsigned>(n);
-  size_t tmp_bytes = 0;
-  DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, static_cast<const unsigned*>(nullptr), static_cast<unsigned*>(nullptr),
-                                                 static_cast<int>(n), ctx->stream));
-  const size_t per = align256(4 * static_cast<size_t>(n)), raw = align256(16 * static_cast<size_t>(n));
-  DLIOM_TRY(ctx->outlier.reserve(raw + 6 * per + align256(4 * kWords) + align256(tmp_bytes) + (intensities != nullptr ? per : 0)));
-  char* base = static_cast<char*>(ctx->outlier.p);
-  const float4* d_points = reinterpret_cast<const float4*>(base);
-  float* x = reinterpret_cast<float*>(base + raw);
-  float* y = reinterpret_cast<float*>(base + raw + per);
-  float* z = reinterpret_cast<float*>(base + raw + 2 * per);
-  unsigned* keep = reinterpret_cast<unsigned*>(base + raw + 3 * per);
-  unsigned* inclusive = reinterpret_cast<unsigned*>(base + raw + 4 * per);
-  int* index = reinterpret_cast<int*>(base + raw + 5 * per);
-  unsigned* words = reinterpret_cast<unsigned*>(base + raw + 6 * per);
-  void* tmp = base + raw + 6 * per + align256(4 * kWords);
-  float* d_intensities = reinterpret_cast<float*>(base + raw + 6 * per + align256(4 * kWords) + align256(tmp_bytes));
-  const FillJob fill{words, 4 * kHeadWords, 0u};
-  DLIOM_TRY(fill_multi(ctx, &fill, 1));
-  DLIOM_HIP_TRY(hipMemcpyAsync(base, points_xyzt, 16 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+  const size_t per = align256(4 * static_cast<size_t>(n)), raw = align256(16 * static_cast<size_t>(n)), wb = align256(4 * kWords);
+  CompactScratch s;
+  DLIOM_TRY(carve_compact(ctx, n, &s, wb + raw + 3 * per + (intensities != nullptr ? per : 0), 4 * kHeadWords));
+  char* base = static_cast<char*>(s.extra);
+  unsigned* words = reinterpret_cast<unsigned*>(base);
+  const float4* d_points = reinterpret_cast<const float4*>(base + wb);
+  float* x = reinterpret_cast<float*>(base + wb + raw);
+  float* y = reinterpret_cast<float*>(base + wb + raw + per);
+  float* z = reinterpret_cast<float*>(base + wb + raw + 2 * per);
+  float* d_intensities = reinterpret_cast<float*>(base + wb + raw + 3 * per);
+  DLIOM_HIP_TRY(hipMemcpyAsync(base + wb, points_xyzt, 16 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
   if (intensities != nullptr)
     DLIOM_HIP_TRY(hipMemcpyAsync(d_intensities, intensities, 4 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, a, d_points, un, x, y, z, keep, words, 0);
+  hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, a, d_points, un, x, y, z, s.keep, words, s.max_sq, 0);
   DLIOM_HIP_TRY(hipGetLastError());
-  DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, keep, inclusive, static_cast<int>(n), ctx->stream));
-  hipLaunchKernelGGL(assemble_origin_kernel, dim3(1), dim3(64), 0, ctx->stream, a, d_points, un, inclusive, words);
+  DLIOM_TRY(scan_kept(ctx, n, s));
+  hipLaunchKernelGGL(assemble_origin_kernel, dim3(1), dim3(64), 0, ctx->stream, a, d_points, un, s.inclusive, words);
   DLIOM_HIP_TRY(hipGetLastError());
-  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
-  const GatherJob jobs[2] = {{inclusive + (un - 1), 1}, {words, static_cast<unsigned>(kWords)}};
-  DLIOM_TRY(gather_and_wait(ctx, jobs, 2, host));
-  const int64_t kept = host[0];
-  std::vector<unsigned> head(host + 1, host + 1 + kWords);  // (the pinned block is reused by the calls below)
+  const GatherJob words_job{words, static_cast<unsigned>(kWords)};
+  int64_t kept;
+  float max_sq;
+  std::vector<unsigned> head(kWords);  // (a copy: the pinned block is reused by the calls below)
+  DLIOM_TRY(read_kept(ctx, n, s, &words_job, &kept, &max_sq, head.data()));
   if (head[kWordBadTime] != 0u) return DLIOM_ERR_INVALID_ARGUMENT;  // nothing was written
   *num_kept = kept;
   if (kept_index != nullptr && capacity < kept) return DLIOM_ERR_CAPACITY;
@@ -564,7 +517,7 @@ int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, i
       DLIOM_TRY(ctx->sort_tmp.reserve(4 * list_words));
       unsigned* d_list = ctx->sort_tmp.as<unsigned>();
       DLIOM_HIP_TRY(hipMemsetAsync(d_list, 0, 4, ctx->stream));
-      hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, a, d_points, un, x, y, z, keep, d_list, 1);
+      hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, a, d_points, un, x, y, z, s.keep, d_list, s.max_sq, 1);
       DLIOM_HIP_TRY(hipGetLastError());
       unsigned count = 0;
       DLIOM_HIP_TRY(hipMemcpyAsync(&count, d_list, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -586,39 +539,26 @@ int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, i
       hipLaunchKernelGGL(assemble_fix_kernel, dim3(dliom::blocks_of(nf, 64)), dim3(64), 0, ctx->stream, d_points, un, x, y, z,
                          ctx->sort_tmp.as<unsigned>(), nf, head[kWordLast], words);
       DLIOM_HIP_TRY(hipGetLastError());
-      const FillJob zero_max{words + kWordMaxSq, 4, 0u};
+      const FillJob zero_max{s.max_sq, 4, 0u};
       DLIOM_TRY(fill_multi(ctx, &zero_max, 1));
-      hipLaunchKernelGGL(assemble_max_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, x, y, z, keep, un, words);
-      DLIOM_HIP_TRY(hipGetLastError());
+      DLIOM_TRY(max_of_kept(ctx, x, y, z, n, s));
       DLIOM_HIP_TRY(hipMemcpyAsync(head.data(), words, 4 * kHeadWords, hipMemcpyDeviceToHost, ctx->stream));
+      DLIOM_HIP_TRY(hipMemcpyAsync(&max_sq, s.max_sq, 4, hipMemcpyDeviceToHost, ctx->stream));
       DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `fixes` dies with this scope
       ++ctx->host_syncs;
     }
   }
-  float max_sq;
-  std::memcpy(&max_sq, &head[kWordMaxSq], 4);
-  // ---- the cloud: the kept points in input order
-  float *ox, *oy, *oz;
-  DLIOM_TRY(alloc_device_cloud(ctx, kept, out, &ox, &oy, &oz));
-  hipLaunchKernelGGL(assemble_scatter_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, x, y, z, un, keep, inclusive, ox, oy, oz,
-                     index);
-  int st = hipGetLastError() == hipSuccess ? DLIOM_OK : DLIOM_ERR_HIP;
-  if (st == DLIOM_OK) st = finish_device_cloud(ctx, *out, std::sqrt(max_sq));  // sqrt is monotone: the max of the norms
-  if (st == DLIOM_OK && intensities != nullptr) {
-    st = kept_intensities->alloc(ctx, static_cast<size_t>(kept));
-    if (st == DLIOM_OK) st = gather_batch_attributes(ctx, index, kept, d_intensities, nullptr, kept_intensities->p, nullptr);
-  }
-  if (st == DLIOM_OK && kept_index != nullptr) {
-    if (hipMemcpyAsync(kept_index, index, static_cast<size_t>(kept) * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
-      st = DLIOM_ERR_HIP;
-    ++ctx->host_syncs;
-  }
-  if (st != DLIOM_OK) {
-    dliom_cloud_destroy(*out);
-    *out = nullptr;
-    if (kept_intensities != nullptr) kept_intensities->release(ctx);
-    return st;
+  // ---- the cloud: the kept points in input order, and their intensities by the indices the scatter leaves in scratch
+  DLIOM_TRY(emit_kept(ctx, x, y, z, n, s, kept, max_sq, out, kept_index));
+  if (intensities != nullptr) {
+    int st = kept_intensities->alloc(ctx, static_cast<size_t>(kept));
+    if (st == DLIOM_OK) st = gather_batch_attributes(ctx, s.index, kept, d_intensities, nullptr, kept_intensities->p, nullptr);
+    if (st != DLIOM_OK) {
+      dliom_cloud_destroy(*out);
+      *out = nullptr;
+      kept_intensities->release(ctx);
+      return st;
+    }
   }
   std::memcpy(origin, &head[kWordOrigin], 12);
   return DLIOM_OK;

@@ -112,6 +112,20 @@ __device__ __forceinline__ unsigned wave_sum_lane63(unsigned v) {
   return v;
 }
 
+// The squared norm of a kept point as the word that the maximum is taken of: cloud_max_norm's order; bit patterns of
+// non-negative floats keep their order; 0 for a NaN (and for a point that is not kept).
+__device__ __forceinline__ unsigned norm_word(float x, float y, float z) {
+  const float sq = x * x + (y * y + z * z);
+  return sq == sq ? __float_as_uint(sq) : 0u;
+}
+// Called by every lane of a wavefront: the wavefront's maximum by six shuffles, then one atomic a wavefront instead of
+// one a point on the same word.
+__device__ __forceinline__ void note_kept(unsigned word, unsigned* max_sq) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) word = max(word, static_cast<unsigned>(__shfl_xor(static_cast<int>(word), off, 64)));
+  if ((threadIdx.x & 63u) == 0u && word != 0u) atomicMax(max_sq, word);
+}
+
 // ---- small copies and fills that ride along in another kernel's launch (round 5) ------------------------------------
 // A Match used to put six operations on the stream before its score kernel could start -- candidate tables H2D, fill of
 // the score volume, box tables H2D, counter memset, extent pre-pass, score kernel -- each a packet of its own with ~5 us

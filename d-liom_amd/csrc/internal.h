@@ -132,7 +132,7 @@ struct dliom_ctx {
   dliom::DevBuf batch;
   // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
   dliom::DevBuf xray_leaves, xray_cells;
-  // the export stages (outlier.hip): keep flags, their scan and the survivors' indices; the voxel list of a table dump
+  // the export stages (compact.hip): keep flags, their scan and the survivors' indices; the voxel list of a table dump
   dliom::DevBuf outlier;
   void* batch_pinned = nullptr;
   size_t batch_pinned_bytes = 0;
@@ -353,9 +353,10 @@ int gather_and_wait(dliom_ctx* ctx, const GatherJob* jobs, int num_jobs, void* p
 int zero_words(dliom_ctx* ctx, unsigned** out);
 int device_block_alloc(int device, size_t need, void** p, size_t* bytes);  // the cloud pool (core.hip)
 void device_block_free(int device, void* p, size_t bytes);
-// ---- outlier.hip: keep flags -> order-preserving compaction, shared by the export stages
+// ---- compact.hip: keep flags -> order-preserving compaction, shared by the export stages
 // Scratch of one compaction in ctx->outlier: a stage's kernel writes keep[i] in {0, 1} and the largest squared norm of the
-// kept points (as bits) to *max_sq, then calls compact_kept / compact_batch.  `extra_bytes` more are carved behind, at *extra.
+// kept points (as bits) to *max_sq, which carve_compact zeroes.  `extra_bytes` more are carved behind, at *extra, the first
+// `zeroed_extra_bytes` of them zeroed in the same dispatch.
 struct CompactScratch {
   unsigned *keep, *inclusive, *max_sq;
   int* index;
@@ -363,13 +364,27 @@ struct CompactScratch {
   size_t tmp_bytes;
   void* extra;
 };
-int carve_compact(dliom_ctx* ctx, int64_t n, CompactScratch* s, size_t extra_bytes = 0);
+int carve_compact(dliom_ctx* ctx, int64_t n, CompactScratch* s, size_t extra_bytes = 0, size_t zeroed_extra_bytes = 0);
+int empty_cloud(dliom_ctx* ctx, dliom_cloud** out);
+// *s.max_sq (zero on entry) for a stage whose flag kernel does not take it: over the points of x/y/z whose flag is set
+int max_of_kept(dliom_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const CompactScratch& s);
+// The steps.  scan_kept: the inclusive sum of s.keep into s.inclusive, enqueued.  read_kept: the call's ONE polled read-back
+// -- the kept count, *s.max_sq and the words of `more` (null: none), copied out of the page-locked block to more_host.
+// emit_kept (kept > 0): the survivors of x/y/z in input order as a finished cloud bounded by sqrt(max_sq), their input
+// indices in s.index and, if asked for, in kept_index (one stream synchronisation); a failure leaves *out null.
+int scan_kept(dliom_ctx* ctx, int64_t n, const CompactScratch& s);
+int read_kept(dliom_ctx* ctx, int64_t n, const CompactScratch& s, const GatherJob* more, int64_t* kept, float* max_sq,
+              unsigned* more_host);
+int emit_kept(dliom_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const CompactScratch& s, int64_t kept,
+              float max_sq, dliom_cloud** out, int32_t* kept_index);
+// The three in a row on a cloud, an empty cloud if nothing is kept.  *flag_word (device, null: none) rides in the read-back
+// into *flag; a non-zero flag leaves *out null and returns DLIOM_OK: the caller refuses.
+int compact_kept(dliom_ctx* ctx, const dliom_cloud* in, const CompactScratch& s, const unsigned* flag_word, unsigned* flag,
+                 dliom_cloud** out, int32_t* kept_index, int64_t capacity, int64_t* num_kept);
 // dst[j] = src[index[j]] for the kept points, on ctx->stream (either source may be null)
 int gather_batch_attributes(dliom_ctx* ctx, const int* d_index, int64_t kept, const float* src_intensities, const float* src_colors,
                             float* dst_intensities, float* dst_colors);
-// Compacts the batch in place by the flags in `s`: points and attributes, one read-back (count, max squared norm,
-// *flag_word if given).  A non-zero flag leaves the batch alone and returns DLIOM_OK: the caller decides.  Any failure
-// leaves the batch as it was.
+// compact_kept on a batch in place, points and attributes.  A non-zero flag or any failure leaves the batch as it was.
 int compact_batch(dliom_points_batch* batch, const CompactScratch& s, const unsigned* flag_word, unsigned* flag, int64_t* num_kept);
 // assemble.hip: dliom_cloud_from_sensor_points with the kept points' intensities (host, n floats, may be null) gathered on
 // the device into *kept_intensities (left empty when there are none or nothing is kept)

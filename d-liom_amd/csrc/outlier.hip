@@ -13,8 +13,6 @@
 // Only pass 1 inserts, and the table and the pool grow between launches.  Passes 2 and 3 look up and add to `rays`.
 // Everything accumulated is a 32-bit integer, so no result depends on the order of the atomics; everything that decides
 // a voxel is float arithmetic in the reference's order, without contraction, with IEEE division and square root.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -154,7 +152,9 @@ __global__ __launch_bounds__(kBlock) void outlier_count_rays_kernel(const float*
   }
 }
 
-// ---- pass 3 and the range filter: a keep flag per point, then an order-preserving compaction ---------------------------
+// ---- pass 3 and the range filter: a keep flag per point, then compact.hip's order-preserving compaction ------------------
+// One atomic a kept point, not device_common.h's norm_word and wavefront fold: the two kernels here leave early for
+// i >= n, and on norm_word (a select, then a test for zero) they are no longer the instructions that were measured.
 __device__ __forceinline__ void note_kept(float x, float y, float z, unsigned* max_sq) {
   const float sq = x * x + (y * y + z * z);  // cloud_max_norm's order; bit patterns of non-negative floats keep their order
   if (sq == sq) atomicMax(max_sq, __float_as_uint(sq));
@@ -198,36 +198,6 @@ __global__ __launch_bounds__(kBlock) void range_keep_flags_kernel(const float* _
   if (k) note_kept(x[i], y[i], z[i], max_sq);
 }
 
-// RemovePoints (points_batch.cc:22-49): the survivors in input order, and their input indices
-__global__ __launch_bounds__(kBlock) void scatter_kept_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                              const float* __restrict__ z, unsigned n,
-                                                              const unsigned* __restrict__ keep, const unsigned* __restrict__ inclusive,
-                                                              float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz,
-                                                              int* __restrict__ index) {
-  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n || keep[i] == 0u) return;
-  const unsigned at = inclusive[i] - 1u;
-  ox[at] = x[i];
-  oy[at] = y[i];
-  oz[at] = z[i];
-  index[at] = static_cast<int>(i);
-}
-
-// The survivors' intensities and colours, by the input indices the scatter has just left in scratch
-__global__ __launch_bounds__(kBlock) void gather_attributes_kernel(const int* __restrict__ index, unsigned kept,
-                                                                   const float* __restrict__ src_i, const float* __restrict__ src_c,
-                                                                   float* __restrict__ dst_i, float* __restrict__ dst_c) {
-  const unsigned j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= kept) return;
-  const size_t i = static_cast<size_t>(index[j]);
-  if (src_i != nullptr) dst_i[j] = src_i[i];
-  if (src_c != nullptr) {
-    dst_c[3 * static_cast<size_t>(j)] = src_c[3 * i];
-    dst_c[3 * static_cast<size_t>(j) + 1] = src_c[3 * i + 1];
-    dst_c[3 * static_cast<size_t>(j) + 2] = src_c[3 * i + 2];
-  }
-}
-
 // ---- the table's contents (tests, statistics) -----------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void outlier_count_voxels_kernel(const int* __restrict__ pool, unsigned long long cells,
                                                                       unsigned* __restrict__ words) {
@@ -260,51 +230,6 @@ __global__ __launch_bounds__(kBlock) void outlier_emit_voxels_kernel(const int* 
 
 inline unsigned blocks_of(int64_t n) { return dliom::blocks_of(n, kBlock); }
 
-int empty_cloud(dliom_ctx* ctx, dliom_cloud** out) {
-  float *x, *y, *z;
-  DLIOM_TRY(alloc_device_cloud(ctx, 0, out, &x, &y, &z));
-  return finish_device_cloud(ctx, *out, 0.f);
-}
-
-// Compacts `in` by the flags a kernel has just written to scratch: one read-back (count, max squared norm, `flag_word`).
-// flag_word: a device word read back with the count (null: none); *flag receives it
-int compact_kept(dliom_ctx* ctx, const dliom_cloud* in, const CompactScratch& s, const unsigned* flag_word, unsigned* flag,
-                 dliom_cloud** out, int32_t* kept_index, int64_t capacity, int64_t* num_kept) {
-  const unsigned n = static_cast<unsigned>(in->n);
-  size_t tmp = s.tmp_bytes;
-  DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(s.tmp, tmp, s.keep, s.inclusive, static_cast<int>(n), ctx->stream));
-  unsigned* host = pinned_at<unsigned>(ctx, kPinReadback);
-  const GatherJob jobs[3] = {{s.inclusive + (n - 1), 1}, {s.max_sq, 1}, {flag_word, 1}};
-  DLIOM_TRY(gather_and_wait(ctx, jobs, flag_word != nullptr ? 3 : 2, host));
-  const int64_t kept = host[0];
-  float max_sq;
-  std::memcpy(&max_sq, &host[1], 4);
-  if (flag_word != nullptr) {
-    *flag = host[2];
-    if (*flag != 0u) return DLIOM_OK;  // the caller refuses
-  }
-  *num_kept = kept;
-  if (kept_index != nullptr && capacity < kept) return DLIOM_ERR_CAPACITY;
-  if (kept == 0) return empty_cloud(ctx, out);
-  float *ox, *oy, *oz;
-  DLIOM_TRY(alloc_device_cloud(ctx, kept, out, &ox, &oy, &oz));
-  hipLaunchKernelGGL(scatter_kept_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, in->d_x, in->d_y, in->d_z, n, s.keep,
-                     s.inclusive, ox, oy, oz, s.index);
-  int st = hipGetLastError() == hipSuccess ? DLIOM_OK : DLIOM_ERR_HIP;
-  if (st == DLIOM_OK) st = finish_device_cloud(ctx, *out, std::sqrt(max_sq));  // sqrt is monotone: the max of the norms
-  if (st == DLIOM_OK && kept_index != nullptr) {
-    if (hipMemcpyAsync(kept_index, s.index, static_cast<size_t>(kept) * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
-      st = DLIOM_ERR_HIP;
-    ++ctx->host_syncs;
-  }
-  if (st != DLIOM_OK) {
-    dliom_cloud_destroy(*out);
-    *out = nullptr;
-  }
-  return st;
-}
-
 int status_of_ray_flag(unsigned flag) {  // the shared bits first
   const int st = status_of_flag(flag);
   return st == DLIOM_OK && (flag & kFlagRayTooLong) ? DLIOM_ERR_RAY_TOO_LONG : st;
@@ -313,78 +238,6 @@ int status_of_ray_flag(unsigned flag) {  // the shared bits first
 bool finite_origin(const float o[3]) { return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]); }
 
 }  // namespace
-
-int AttrBlock::alloc(dliom_ctx* ctx, size_t count) {
-  if (count == 0) return DLIOM_OK;
-  DLIOM_TRY(device_block_alloc(ctx->device, 4 * count, &base, &bytes));
-  p = static_cast<float*>(base);
-  return DLIOM_OK;
-}
-void AttrBlock::release(dliom_ctx* ctx) {
-  if (base != nullptr) device_block_free(ctx->device, base, bytes);
-  base = nullptr;
-  bytes = 0;
-  p = nullptr;
-}
-
-int gather_batch_attributes(dliom_ctx* ctx, const int* d_index, int64_t kept, const float* src_intensities, const float* src_colors,
-                            float* dst_intensities, float* dst_colors) {
-  if (kept <= 0 || (src_intensities == nullptr && src_colors == nullptr)) return DLIOM_OK;
-  hipLaunchKernelGGL(gather_attributes_kernel, dim3(blocks_of(kept)), dim3(kBlock), 0, ctx->stream, d_index, static_cast<unsigned>(kept),
-                     src_intensities, src_colors, dst_intensities, dst_colors);
-  DLIOM_HIP_TRY(hipGetLastError());
-  return DLIOM_OK;
-}
-
-int compact_batch(dliom_points_batch* b, const CompactScratch& s, const unsigned* flag_word, unsigned* flag, int64_t* num_kept) {
-  dliom_ctx* ctx = b->ctx;
-  dliom_cloud* kept_cloud = nullptr;
-  int64_t kept = 0;
-  if (flag != nullptr) *flag = 0u;
-  DLIOM_TRY(compact_kept(ctx, b->cloud, s, flag_word, flag, &kept_cloud, nullptr, 0, &kept));
-  if (kept_cloud == nullptr) return DLIOM_OK;  // the flag is set: nothing was compacted
-  // s.index holds the survivors' input indices until the next stage carves the scratch
-  AttrBlock ki, kc;
-  int st = DLIOM_OK;
-  if (b->intensities.p != nullptr) st = ki.alloc(ctx, static_cast<size_t>(kept));
-  if (st == DLIOM_OK && b->colors.p != nullptr) st = kc.alloc(ctx, 3 * static_cast<size_t>(kept));
-  if (st == DLIOM_OK) st = gather_batch_attributes(ctx, s.index, kept, ki.p != nullptr ? b->intensities.p : nullptr,
-                                                   kc.p != nullptr ? b->colors.p : nullptr, ki.p, kc.p);
-  if (st != DLIOM_OK) {
-    ki.release(ctx);
-    kc.release(ctx);
-    dliom_cloud_destroy(kept_cloud);
-    return st;
-  }
-  dliom_cloud_destroy(b->cloud);  // (waits for the device: the gather has read the old arrays)
-  b->intensities.release(ctx);
-  b->colors.release(ctx);
-  b->cloud = kept_cloud;
-  b->intensities = ki;
-  b->colors = kc;
-  if (kept == 0) b->single_color = false;  // RemovePoints leaves empty vectors: an empty batch has no attributes
-  *num_kept = kept;
-  return DLIOM_OK;
-}
-
-int carve_compact(dliom_ctx* ctx, int64_t n, CompactScratch* s, size_t extra_bytes) {
-  size_t tmp = 0;
-  DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, static_cast<const unsigned*>(nullptr), static_cast<unsigned*>(nullptr),
-                                                 static_cast<int>(n), ctx->stream));
-  const size_t per = align256(4 * static_cast<size_t>(n));
-  DLIOM_TRY(ctx->outlier.reserve(3 * per + 256 + align256(tmp) + extra_bytes));
-  char* b = static_cast<char*>(ctx->outlier.p);
-  s->keep = reinterpret_cast<unsigned*>(b);
-  s->inclusive = reinterpret_cast<unsigned*>(b + per);
-  s->index = reinterpret_cast<int*>(b + 2 * per);
-  s->max_sq = reinterpret_cast<unsigned*>(b + 3 * per);
-  s->tmp = b + 3 * per + 256;
-  s->tmp_bytes = tmp;
-  s->extra = b + 3 * per + 256 + align256(tmp);
-  const FillJob fill{s->max_sq, 4, 0u};
-  return fill_multi(ctx, &fill, 1);
-}
-
 }  // namespace dliom
 
 using namespace dliom;
@@ -425,6 +278,27 @@ int dliom_outlier_remover::grow_pool(int64_t want_leaves) {
   leaf_capacity = cap;
   book();
   return DLIOM_OK;
+}
+
+// Pass 3's keep flags of `points` (n > 0) into freshly carved scratch, for the cloud and the batch entry point
+static int flag_by_voxels(dliom_outlier_remover* r, const dliom_cloud* points, CompactScratch* s) {
+  dliom_ctx* ctx = r->ctx;
+  const unsigned n = static_cast<unsigned>(points->n);
+  DLIOM_TRY(carve_compact(ctx, points->n, s));
+  const FillJob fill{r->d_words + kWordFlag, 4, 0u};
+  DLIOM_TRY(fill_multi(ctx, &fill, 1));
+  hipLaunchKernelGGL(outlier_keep_flags_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, points->d_x, points->d_y,
+                     points->d_z, n, r->view(), s->keep, r->d_words, s->max_sq);
+  return hipGetLastError() == hipSuccess ? DLIOM_OK : DLIOM_ERR_HIP;
+}
+
+static int flag_by_range(dliom_ctx* ctx, const dliom_cloud* in, const float origin[3], double min_range, double max_range,
+                         CompactScratch* s) {
+  const unsigned n = static_cast<unsigned>(in->n);
+  DLIOM_TRY(carve_compact(ctx, in->n, s));
+  hipLaunchKernelGGL(range_keep_flags_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, in->d_x, in->d_y, in->d_z, n,
+                     origin[0], origin[1], origin[2], min_range, max_range, s->keep, s->max_sq);
+  return hipGetLastError() == hipSuccess ? DLIOM_OK : DLIOM_ERR_HIP;
 }
 
 extern "C" {
@@ -528,14 +402,8 @@ int dliom_outlier_remover_filter(dliom_outlier_remover* r, const dliom_cloud* po
     r->phase = 3;
     return empty_cloud(ctx, kept);
   }
-  const unsigned n = static_cast<unsigned>(points->n);
   CompactScratch s;
-  DLIOM_TRY(carve_compact(ctx, points->n, &s));
-  const FillJob fill{r->d_words + kWordFlag, 4, 0u};
-  DLIOM_TRY(fill_multi(ctx, &fill, 1));
-  hipLaunchKernelGGL(outlier_keep_flags_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, points->d_x, points->d_y,
-                     points->d_z, n, r->view(), s.keep, r->d_words, s.max_sq);
-  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_TRY(flag_by_voxels(r, points, &s));
   unsigned flag = 0;
   DLIOM_TRY(compact_kept(ctx, points, s, r->d_words + kWordFlag, &flag, kept, kept_index, capacity, num_kept));
   if (flag != 0u) return status_of_flag(flag);  // (non-finite: the only one this pass raises)
@@ -614,12 +482,8 @@ int dliom_cloud_min_max_range_filter(dliom_ctx* ctx, const dliom_cloud* in, cons
   *num_kept = 0;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   if (in->n == 0) return empty_cloud(ctx, out);
-  const unsigned n = static_cast<unsigned>(in->n);
   CompactScratch s;
-  DLIOM_TRY(carve_compact(ctx, in->n, &s));
-  hipLaunchKernelGGL(range_keep_flags_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, in->d_x, in->d_y, in->d_z, n,
-                     origin[0], origin[1], origin[2], min_range, max_range, s.keep, s.max_sq);
-  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_TRY(flag_by_range(ctx, in, origin, min_range, max_range, &s));
   return compact_kept(ctx, in, s, nullptr, nullptr, out, kept_index, capacity, num_kept);
 }
 
@@ -632,15 +496,8 @@ int dliom_outlier_remover_filter_batch(dliom_outlier_remover* r, dliom_points_ba
     return DLIOM_OK;
   }
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  const dliom_cloud* points = batch->cloud;
-  const unsigned n = static_cast<unsigned>(points->n);
   CompactScratch s;
-  DLIOM_TRY(carve_compact(ctx, points->n, &s));
-  const FillJob fill{r->d_words + kWordFlag, 4, 0u};
-  DLIOM_TRY(fill_multi(ctx, &fill, 1));
-  hipLaunchKernelGGL(outlier_keep_flags_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, points->d_x, points->d_y,
-                     points->d_z, n, r->view(), s.keep, r->d_words, s.max_sq);
-  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_TRY(flag_by_voxels(r, batch->cloud, &s));
   unsigned flag = 0;
   int64_t kept = 0;
   DLIOM_TRY(compact_batch(batch, s, r->d_words + kWordFlag, &flag, &kept));
@@ -655,13 +512,8 @@ int dliom_points_batch_min_max_range_filter(dliom_points_batch* batch, double mi
   if (batch->cloud->n == 0) return DLIOM_OK;
   dliom_ctx* ctx = batch->ctx;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  const dliom_cloud* in = batch->cloud;
-  const unsigned n = static_cast<unsigned>(in->n);
   CompactScratch s;
-  DLIOM_TRY(carve_compact(ctx, in->n, &s));
-  hipLaunchKernelGGL(range_keep_flags_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, in->d_x, in->d_y, in->d_z, n,
-                     batch->origin[0], batch->origin[1], batch->origin[2], min_range, max_range, s.keep, s.max_sq);
-  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_TRY(flag_by_range(ctx, batch->cloud, batch->origin, min_range, max_range, &s));
   int64_t kept = 0;
   return compact_batch(batch, s, nullptr, nullptr, &kept);
 }

@@ -2,7 +2,7 @@
 // (DESIGN.md section 3.14): ColoringPointsProcessor, IntensityToColorPointsProcessor, FixedRatioSamplingPointsProcessor
 // over common::FixedRatioSampler, and the per-point loops of PlyWritingPointsProcessor / PcdWritingPointsProcessor as
 // packed records.  The compacting stages that decide by geometry (range filter, outlier removal) live in outlier.hip and
-// the head of the export in assemble.hip; all of them share outlier.hip's scan, scatter and attribute gather.
+// the head of the export in assemble.hip; all of them share compact.hip's scan, scatter and attribute gather.
 //
 // Everything here equals the reference byte for byte: the colour stages are float arithmetic in the reference's order
 // (no contraction, IEEE division), the sampler's decisions are the sequential loop's (proven per call, below), and the
@@ -95,21 +95,6 @@ __global__ __launch_bounds__(kBlock) void sampler_check_kernel(unsigned chunks, 
   }
   bad[c] = wrong;
   if (wrong) atomicAdd(&words[0], 1u);
-}
-
-// the largest squared norm of the kept points (cloud_max_norm's order), for the compacted cloud's bound
-__global__ __launch_bounds__(kBlock) void kept_max_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                          const float* __restrict__ z, const unsigned* __restrict__ keep, unsigned n,
-                                                          unsigned* __restrict__ max_sq) {
-  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-  unsigned word = 0;
-  if (i < n && keep[i] != 0u) {
-    const float sq = x[i] * x[i] + (y[i] * y[i] + z[i] * z[i]);
-    if (sq == sq) word = __float_as_uint(sq);  // bit patterns of non-negative floats keep their order
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) word = max(word, static_cast<unsigned>(__shfl_xor(static_cast<int>(word), off, 64)));
-  if ((threadIdx.x & 63u) == 0u && word != 0u) atomicMax(max_sq, word);
 }
 
 // ---- the writers' records ------------------------------------------------------------------------------------------
@@ -404,8 +389,8 @@ int dliom_points_batch_fixed_ratio_sample(dliom_fixed_ratio_sampler* sampler, dl
                        d_end, d_bad, pass > 0 ? 1 : 0, s.keep);
     hipLaunchKernelGGL(sampler_check_kernel, dim3(blocks_of(chunks)), dim3(kBlock), 0, ctx->stream, chunks, d_start, d_end, d_bad,
                        d_words);
-    hipLaunchKernelGGL(kept_max_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, in->d_x, in->d_y, in->d_z, s.keep, n, s.max_sq);
     DLIOM_HIP_TRY(hipGetLastError());
+    DLIOM_TRY(max_of_kept(ctx, in->d_x, in->d_y, in->d_z, n64, s));
     unsigned wrong = 0;
     // the number of wrong starts rides in the read-back of the kept count; while it is not zero nothing is compacted
     DLIOM_TRY(compact_batch(b, s, d_words, &wrong, &kept));

@@ -686,7 +686,7 @@ int dliom_inserter2d_insert_cloud(dliom_inserter2d* ins, dliom_probability_grid*
     box_y1 = std::max(box_y1, bpy);
   }
 
-  // The export stages' scratch (dliom_ctx::outlier, shared with outlier.hip's compaction): every user's contents live
+  // The export stages' scratch (dliom_ctx::outlier, shared with compact.hip's compaction): every user's contents live
   // only within one call, in stream order, so the ends may sit there until this call's last read-back.
   if (ctx->outlier.reserve(static_cast<size_t>(n) * sizeof(int2)) != DLIOM_OK) {
     restore();

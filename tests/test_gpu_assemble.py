@@ -189,6 +189,84 @@ def test_refusals(dl, ctx, model, tmp_path):
     trajectory.close()
 
 
+def test_stages_share_the_scratch_on_one_context(dl, ctx, model, tmp_path):
+    """The assembler, the range filter and the sampler carve the same scratch of the context, each to its own size: 4097
+    points, then a 65-point batch filtered and sampled (0.55), then 4097 again, then 63 -- across one wavefront, one
+    workgroup and 4096.  Every result is the model's, and the two 4097-point results are equal."""
+    import points_batch_common as pb
+    times, poses = small_trajectory()
+    t_end = int(times[-1])
+
+    def message(n):  # every third point lies outside the trajectory
+        inside = -np.linspace(1000.0, 399_000.0, n)
+        return points(n, np.where(np.arange(n) % 3 == 0, 5000.0, inside), seed=n)
+
+    big, small = message(4097), message(63)
+    pushed, (want_big, want_small) = ac.run_model(model, times, poses, [ac.assemble_op(t_end, MOUNT, big), ac.assemble_op(t_end, MOUNT, small)], tmp_path)
+    assert pushed == 0 and len(want_big["index"]) == 4097 - 1366 and len(want_small["index"]) == 42
+    # the batch: the kept points lie 10 m from the origin, the others 30 m
+    batch_model = pb.build_model(tmp_path)
+    pts, it, col = pb.batch_arrays(65, 65, "both")
+    keep = np.arange(65) % 2 == 0
+    d = np.random.RandomState(65).normal(size=(65, 3)) + 1e-3
+    pts = (d / np.linalg.norm(d, axis=1)[:, None] * np.where(keep, 10.0, 30.0)[:, None]).astype(f32)
+    filtered, (pulses, _, _) = pb.run_model(batch_model, [pb.remove_op(pts, it, col, keep), pb.pulse_op(0.55, 0, 0, 33)], tmp_path)
+    assert len(filtered[0]) == 33 and 0 < int(np.sum(pulses)) < 33
+    sampled, = pb.run_model(batch_model, [pb.remove_op(*filtered, pulses)], tmp_path)
+
+    trajectory = dl.Trajectory(ctx, times, poses)
+    first = trajectory.assemble(t_end, big, MOUNT)
+    ac.assert_equal_bits(*first, want_big)
+    b = dl.PointsBatch(ctx, pts, (0, 0, 0), it, col)
+    b.min_max_range_filter(5.0, 20.0)
+    pb.assert_batch_equals(b, filtered)
+    sampler = dl.FixedRatioSampler(0.55)
+    b.fixed_ratio_sample(sampler)
+    pb.assert_batch_equals(b, sampled)
+    sampler.close()
+    b.close()
+    again = trajectory.assemble(t_end, big, MOUNT)
+    ac.assert_equal_bits(*again, want_big)
+    assert again[0].download().tobytes() == first[0].download().tobytes() and again[1].tobytes() == first[1].tobytes()
+    assert np.array_equal(again[2], first[2])
+    last = trajectory.assemble(t_end, small, MOUNT)
+    ac.assert_equal_bits(*last, want_small)
+    for cloud in (first[0], again[0], last[0]):
+        cloud.close()
+    trajectory.close()
+
+
+def assembler_round_trips(dl, ctx):
+    """-> (read-backs, synchronisations) of one warm 4097-point dliom_cloud_from_sensor_points without a kept_index buffer,
+    and the same with one."""
+    times, poses = small_trajectory()
+    trajectory = dl.Trajectory(ctx, times, poses)
+    xyzt = points(4097, -np.linspace(0.0, 390_000.0, 97))
+    L = dl.load_library()
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    mount, origin, index = np.array(MOUNT), np.zeros(3, dtype=f32), np.zeros(4097, dtype=np.int32)
+    out = []
+    for kept_index in (None, index.ctypes.data_as(ip), None, index.ctypes.data_as(ip)):  # (the first two calls warm up)
+        h, kept = C.c_void_p(), C.c_int64()
+        r0, s0 = ctx.read_backs(), ctx.synchronizations()
+        status = L.dliom_cloud_from_sensor_points(ctx.h, trajectory.h, int(times[-1]), xyzt.ctypes.data_as(fp), 4097,
+                                                  mount.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h),
+                                                  origin.ctypes.data_as(fp), kept_index, 4097, C.byref(kept))
+        out.append((ctx.read_backs() - r0, ctx.synchronizations() - s0))
+        assert status == dl.OK and kept.value == 4097
+        dl.PointCloud(ctx, _handle=h).close()
+    trajectory.close()
+    return out[2], out[3]
+
+
+def test_round_trips_of_a_call(dl, ctx):
+    """One polled read-back a call; the download of kept_index, when asked for, is one stream synchronisation more
+    (DESIGN.md section 3.13), with the compaction shared among the export stages as before it was."""
+    without_index, with_index = assembler_round_trips(dl, ctx)
+    assert without_index == (1, 0)
+    assert with_index == (1, 1)
+
+
 def test_adapter_chain_equals_model(dl, model, tmp_path):
     """transform::TransformInterpolationBuffer and io::AssemblePointsBatch -> MinMaxRangeFiteringPointsProcessor ->
     OutlierRemovingPointsProcessor's marks (tests/cpp/assemble_adapter.cc): the assembled batch is the model's, the chain
