@@ -1010,4 +1010,11 @@ int dliom_cloud_size(const dliom_cloud* cloud, int64_t* n) {
   return DLIOM_OK;
 }
 
+int dliom_cloud_bounds(const dliom_cloud* cloud, float* max_norm, float abs_max[3]) {
+  if (cloud == nullptr || max_norm == nullptr || abs_max == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *max_norm = cloud->max_norm;
+  for (int a = 0; a < 3; ++a) abs_max[a] = cloud->abs_max[a];
+  return DLIOM_OK;
+}
+
 }  // extern "C"

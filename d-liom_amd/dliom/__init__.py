@@ -277,6 +277,7 @@ SYMBOLS = [
     ("dliom_cloud_create", C.c_int, [_vp, _f32p, C.c_int64, C.POINTER(_vp)]),
     ("dliom_cloud_destroy", C.c_int, [_vp]),
     ("dliom_cloud_size", C.c_int, [_vp, _i64p]),
+    ("dliom_cloud_bounds", C.c_int, [_vp, _f32p, _f32p]),
     ("dliom_cloud_voxel_filter", C.c_int, [_vp, _vp, C.c_float, C.POINTER(_vp)]),
     ("dliom_cloud_adaptive_voxel_filter", C.c_int, [_vp, _vp, C.POINTER(AdaptiveVoxelFilterOptions), C.POINTER(_vp)]),
     ("dliom_cloud_adaptive_voxel_filter_pair", C.c_int, [_vp, _vp, C.POINTER(AdaptiveVoxelFilterOptions),
@@ -633,6 +634,12 @@ class Context:
         return out
 
 
+def _cloud_bounds(lib, handle):
+    max_norm, abs_max = C.c_float(), np.zeros(3, dtype=np.float32)
+    _check(lib.dliom_cloud_bounds(handle, C.byref(max_norm), _p(abs_max, _f32p)), "dliom_cloud_bounds")
+    return np.float32(max_norm.value), abs_max
+
+
 class PointCloud:
     """sensor::PointCloud staged in HBM (dliom_cloud)."""
 
@@ -685,6 +692,10 @@ class PointCloud:
                                                         float(max_range), C.byref(h), _p(index, _i32p), self.n,
                                                         C.byref(kept)), "dliom_cloud_min_max_range_filter")
         return PointCloud(self.ctx, _handle=h), index[:kept.value].copy()
+
+    def bounds(self):
+        """dliom_cloud_bounds -> (max_norm np.float32, abs_max float32[3]; a negative component: unknown)."""
+        return _cloud_bounds(self._L, self.h)
 
     def download(self, pose7=None):
         """The points, packed xyz; pose7 (float [t, q]): sensor::TransformPointCloud(cloud, pose) applied on the device."""
@@ -912,11 +923,14 @@ PACK_PLY, PACK_PCD = 0, 1
 class _BorrowedCloud:
     """The points of a PointsBatch as the stages that take a dliom_cloud see them (not owned: no close)."""
 
-    def __init__(self, handle, n):
-        self.h, self.n = handle, n
+    def __init__(self, L, handle, n):
+        self._L, self.h, self.n = L, handle, n
 
     def __len__(self):
         return self.n
+
+    def bounds(self):
+        return _cloud_bounds(self._L, self.h)
 
 
 class PointsBatch:
@@ -981,7 +995,7 @@ class PointsBatch:
         compacting call on this batch."""
         h = _vp()
         _check(self._L.dliom_points_batch_cloud(self.h, C.byref(h)), "dliom_points_batch_cloud")
-        return _BorrowedCloud(h, len(self))
+        return _BorrowedCloud(self._L, h, len(self))
 
     def download(self):
         """-> (points float32 (n, 3), intensities float32 (n,) or None, colors float32 (n, 3) or None)"""

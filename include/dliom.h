@@ -231,6 +231,11 @@ int dliom_inserter_insert_cloud_multi(const dliom_inserter* inserter, int num_ta
 int dliom_cloud_create(dliom_ctx* ctx, const float* points_xyz, int64_t n, dliom_cloud** out);
 int dliom_cloud_destroy(dliom_cloud* cloud);
 int dliom_cloud_size(const dliom_cloud* cloud, int64_t* n);
+/* The bounds the cloud carries, as its producer left them (no device work, no synchronisation): max_norm = max_i |p_i|
+ * (float, x*x + (y*y + z*z), a NaN norm never counts, 0 for an empty cloud) and abs_max = max_i |x_i|, |y_i|, |z_i| per
+ * axis, or a negative value where the producer does not know it (max_norm bounds that axis then).  The matchers'
+ * search windows and the inserters' growth are sized from these. */
+int dliom_cloud_bounds(const dliom_cloud* cloud, float* max_norm, float abs_max[3]);
 
 /* ---- RealTimeCorrelativeScanMatcher3D -------------------------------------
  * proto::RealTimeCorrelativeScanMatcherOptions

@@ -258,3 +258,90 @@ def compare(dl, ctx, exe, voxel_size, transform, ops, directory, floors=1, color
         for x in xs:
             x.close()
     return result, stats, fraction
+
+
+# ---- prescribed runs and column counts (the per-point sums' path edges and the sort's key width) ------------------------
+# points_xray.hip: one lane sums a run of up to 64 points of a column, a wavefront in trips of 64 anything longer; a run goes
+# to the wavefront only when a 65th point follows; the wavefront's loop ends on a trip of fewer than 64.
+RUN_LENGTHS = [1, 2, 63, 64, 65, 127, 128, 129, 192, 193]
+RUN_LAST = [64, 65, 128]  # the variants: the run that gets the highest column slot and so ends the sorted arrays
+RUN_SEED = 1  # chosen on the CPU (tests/test_points_xray_host.py): every run of 64 or more is order-sensitive with it
+COLUMN_COUNTS = [255, 256, 257, 65535, 65536, 65537]
+
+
+def _column_point(column, x):
+    """A point of column `column` (cells y = column % 256 - 128, z = column // 256 - 128) at voxel size 1, identity."""
+    return [x + 0.1, column % 256 - 128 + 0.1, column // 256 - 128 - 0.1]
+
+
+def run_length_batch(seed=RUN_SEED):
+    """One batch whose columns 0..9 receive RUN_LENGTHS[k] points, interleaved by a fixed permutation (only a stable sort
+    keeps a run in batch order), with random colours -> (points, colours, column of every point)."""
+    rng = np.random.RandomState(seed)
+    column = rng.permutation(np.repeat(np.arange(len(RUN_LENGTHS)), RUN_LENGTHS))
+    pts = np.array([_column_point(3 * c, i % 37) for i, c in enumerate(column)], dtype=f32)
+    return pts, rng.uniform(0.0, 1.0, (len(pts), 3)).astype(f32), column
+
+
+def run_length_ops(last, colors="point", seed=RUN_SEED):
+    """Ten one-point inserts, one a column, claim the column slots in a known order (a slot is given out per new column,
+    insert after insert) with the run of `last` points last; then the batch twice: the second time the sums continue from
+    the stored ones.  colors: "point", "constant" (one colour a batch) or "none"."""
+    pts, col, column = run_length_batch(seed)
+    order = [k for k in range(len(RUN_LENGTHS)) if RUN_LENGTHS[k] != last] + [RUN_LENGTHS.index(last)]
+    rng = np.random.RandomState(seed + 1)
+    ops = []
+    for k in order:
+        c = rng.uniform(0.0, 1.0, 3).astype(f32)
+        ops.append(insert([_column_point(3 * k, 50)], None if colors == "none" else c))
+    for _ in range(2):
+        c = rng.uniform(0.0, 1.0, 3).astype(f32)
+        ops.append(insert(pts, col if colors == "point" else (c if colors == "constant" else None)))
+    return ops
+
+
+def run_lengths_of(voxel_size, transform, pts):
+    """The run lengths of a batch, from camera_cells, in the order of the columns' (y, z)."""
+    cells = camera_cells(voxel_size, transform, pts)
+    _, counts = np.unique(cells[:, 1] * 65536 + cells[:, 2], return_counts=True)
+    return counts.tolist()
+
+
+def order_sensitive_runs(colors, column):
+    """For every run of 64 or more points: does the sequential float32 sum of its red values, in batch order, differ from
+    the sum in reverse order AND from a pairwise (tree) sum?"""
+    def pairwise(v):
+        v = list(v)
+        while len(v) > 1:
+            v = [f32(v[i] + v[i + 1]) if i + 1 < len(v) else v[i] for i in range(0, len(v), 2)]
+        return v[0]
+    out = []
+    for k, length in enumerate(RUN_LENGTHS):
+        if length < 64:
+            continue
+        reds = colors[column == k, 0]
+        forward = backward = f32(0)
+        for v in reds:
+            forward = f32(forward + v)
+        for v in reds[::-1]:
+            backward = f32(backward + v)
+        out.append(forward.tobytes() != backward.tobytes() and forward.tobytes() != pairwise(reds).tobytes())
+    return out
+
+
+def column_count_ops(count, colors="point"):
+    """Inserts that leave the aggregator with exactly `count` columns.  A one-point insert gives column 0 slot 0; the next
+    batches (of up to 40 000 points) have one point a column for the columns 1 .. count - 2 and a few repeats; the last batch brings the last column --
+    the highest slot, count - 1 -- as a run of 3 with distinct colours, interleaved with points of column 0 (the slot that
+    count - 1 turns into when count - 1 is a power of two and the sort drops the top key bit) and a few other columns."""
+    rng = np.random.RandomState(count)
+
+    def colours(n):
+        if colors == "none":
+            return None
+        return rng.uniform(0.0, 1.0, (n, 3)).astype(f32) if colors == "point" else rng.uniform(0.0, 1.0, 3).astype(f32)
+    first = [_column_point(c, 0) for c in range(1, count - 1)] + [_column_point(c, 1 + i) for i, c in enumerate((1, 2, 3, 2, 1, count - 2))]
+    n, x = count - 1, 0
+    last = [_column_point(c, i) for i, c in enumerate([n, x, n, x, n, 5, 7, 5])]
+    pieces = [first[i:i + 40000] for i in range(0, len(first), 40000)]  # no batch above 65 537 points
+    return ([insert([_column_point(0, 9)], colours(1))] + [insert(p, colours(len(p))) for p in pieces] + [insert(last, colours(len(last)))])

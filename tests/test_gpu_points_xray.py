@@ -228,3 +228,32 @@ def test_randomised_slice(dl, ctx, model, tmp_path):
     import fuzz_points_xray
     for seed in (1, 2, 3, 4, 5, 6, 7, 8):
         fuzz_points_xray.run_case(dl, ctx, model, seed, str(tmp_path))
+
+
+@pytest.mark.parametrize("colors", ["point", "constant", "none"])
+@pytest.mark.parametrize("last", xc.RUN_LAST)
+def test_prescribed_run_lengths(dl, ctx, model, tmp_path, last, colors):
+    """Runs of exactly 1, 2, 63, 64, 65, 127, 128, 129, 192 and 193 points in one batch, interleaved in batch order, the run
+    of `last` points at the very end of the sorted arrays (j + 64 == n for 64; a trip with count == 0 for 128); the batch a
+    second time on top of the stored sums.  tests/test_points_xray_host.py asserts the run lengths and that every run of
+    64 or more sums to different bits in another order."""
+    ops = xc.run_length_ops(last, colors)
+    assert xc.run_lengths_of(1.0, IDENTITY, ops[-1][2]) == xc.RUN_LENGTHS
+    result, stats, _ = xc.compare(dl, ctx, model, 1.0, IDENTITY, ops, tmp_path, need_honest=False)
+    a = result.aggregations[0]
+    assert a["counts"].tolist() == [2 * k + 1 for k in xc.RUN_LENGTHS] and stats[0]["columns"] == len(xc.RUN_LENGTHS)
+    assert stats[0]["longest_segment"] == max(xc.RUN_LENGTHS)
+
+
+@pytest.mark.parametrize("colors", ["point", "constant", "none"])
+@pytest.mark.parametrize("count", xc.COLUMN_COUNTS)
+def test_prescribed_column_counts(dl, ctx, model, tmp_path, count, colors):
+    """Exactly 2^k - 1, 2^k and 2^k + 1 columns (k = 8, 16): the radix sort's key width steps there.  The highest slot holds
+    a run of 3 interleaved with points of slot 0: a sort that drops the top key bit breaks the run up."""
+    ops = xc.column_count_ops(count, colors)
+    result, stats, _ = xc.compare(dl, ctx, model, 1.0, IDENTITY, ops, tmp_path, need_honest=False)
+    a = result.aggregations[0]
+    assert stats[0]["columns"] == count == len(a["yz"])
+    last = count - 1
+    at = np.flatnonzero((a["yz"][:, 0] == last % 256 - 128) & (a["yz"][:, 1] == last // 256 - 128))
+    assert len(at) == 1 and a["counts"][at[0]] == 3

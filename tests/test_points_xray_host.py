@@ -176,3 +176,45 @@ def test_the_parity_scenes_are_honest(model, tmp_path, colors):
         r = xc.run_model(model, 0.05, xc.TRANSFORMS[name], ops, tmp_path)
         fraction = xc.honest(r, ops, 0.05, xc.TRANSFORMS[name], colored=True)
         print(name, colors, "order-sensitive share of the columns with >= 8 points: %.3f" % fraction)
+
+
+def test_prescribed_runs_are_what_they_claim(model, tmp_path):
+    """The premises of test_gpu_points_xray.py's prescribed runs: the batch's run lengths are the prescribed list; every run
+    of 64 or more is order-sensitive (sequential != reversed, sequential != pairwise; the seed was chosen for this); the
+    batch is interleaved (no run is contiguous in batch order); the three variants differ only in the one-point inserts."""
+    pts, colors, column = xc.run_length_batch()
+    assert xc.run_lengths_of(1.0, IDENTITY, pts) == xc.RUN_LENGTHS and len(pts) == sum(xc.RUN_LENGTHS) <= 65537
+    sensitive = xc.order_sensitive_runs(colors, column)
+    assert len(sensitive) == sum(k >= 64 for k in xc.RUN_LENGTHS) and all(sensitive), sensitive
+    for k, length in enumerate(xc.RUN_LENGTHS):
+        where = np.flatnonzero(column == k)
+        assert len(where) == length and (length < 3 or where[-1] - where[0] + 1 > length)
+    for colors_kind in ("point", "constant", "none"):
+        variants = [xc.run_length_ops(last, colors_kind) for last in xc.RUN_LAST]
+        for last, ops in zip(xc.RUN_LAST, variants):
+            assert len(ops) == 12 and all(len(o[2]) == 1 for o in ops[:10])
+            assert ops[-1][2].tobytes() == pts.tobytes() and ops[-2][2].tobytes() == variants[0][-1][2].tobytes()
+            cells = xc.camera_cells(1.0, IDENTITY, np.concatenate([o[2] for o in ops[:10]]))
+            assert len({tuple(c[1:]) for c in cells}) == 10  # ten columns, claimed one insert at a time
+            last_cell = cells[9, 1:]
+            main = xc.camera_cells(1.0, IDENTITY, pts)
+            assert int(np.sum((main[:, 1] == last_cell[0]) & (main[:, 2] == last_cell[1]))) == last
+            r = xc.run_model(model, 1.0, IDENTITY, ops, tmp_path)
+            assert r.statuses == [0] * 12 and r.aggregations[0]["counts"].tolist() == [2 * k + 1 for k in xc.RUN_LENGTHS]
+
+
+@pytest.mark.parametrize("count", xc.COLUMN_COUNTS)
+def test_prescribed_column_counts_are_what_they_claim(model, tmp_path, count):
+    ops = xc.column_count_ops(count)
+    assert max(len(o[2]) for o in ops) <= 65537
+    r = xc.run_model(model, 1.0, IDENTITY, ops, tmp_path)
+    a = r.aggregations[0]
+    assert r.statuses == [0] * len(ops) and len(a["yz"]) == count
+    # the last batch brings exactly one new column, three times, with three different colours, between points of column 0
+    before = xc.run_model(model, 1.0, IDENTITY, ops[:-1], tmp_path).aggregations[0]
+    assert len(before["yz"]) == count - 1
+    cells = xc.camera_cells(1.0, IDENTITY, ops[-1][2])[:, 1:]
+    new = [i for i, c in enumerate(cells) if not np.any(np.all(before["yz"] == c, axis=1))]
+    assert new == [0, 2, 4] and len({ops[-1][3][i].tobytes() for i in new}) == 3
+    first = xc.camera_cells(1.0, IDENTITY, ops[0][2])[0, 1:]
+    assert np.array_equal(cells[1], first) and np.array_equal(cells[3], first)
