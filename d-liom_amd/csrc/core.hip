@@ -484,6 +484,11 @@ int wait_done(dliom_ctx* ctx, hipStream_t stream, const unsigned* done_word, uns
   return __atomic_load_n(done_word, __ATOMIC_ACQUIRE) == done_seq ? DLIOM_OK : DLIOM_ERR_HIP;
 }
 
+unsigned next_done_seq(dliom_ctx* ctx) {
+  if (++ctx->done_seq == 0u) ++ctx->done_seq;
+  return ctx->done_seq;
+}
+
 int gather_and_wait(dliom_ctx* ctx, const GatherJob* jobs, int num_jobs, void* pinned_dst) {
   if (num_jobs <= 0) return DLIOM_OK;
   if (ctx->done_word == nullptr) {  // no completion word (allocation failed at creation): the plain way
@@ -491,7 +496,7 @@ int gather_and_wait(dliom_ctx* ctx, const GatherJob* jobs, int num_jobs, void* p
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DLIOM_OK;
   }
-  const unsigned seq = ++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq;
+  const unsigned seq = next_done_seq(ctx);
   DLIOM_TRY(gather_to_pinned(ctx, jobs, num_jobs, pinned_dst, ctx->stream, ctx->done_word, seq));
   return wait_done(ctx, ctx->stream, ctx->done_word, seq);
 }

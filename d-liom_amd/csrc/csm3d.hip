@@ -145,7 +145,7 @@ __device__ __forceinline__ double fast_reciprocal(double d) {
 // csm_lm_kernel is bound by instruction issue; the values differ from the reference's separately rounded operations in
 // the last bits, far inside the 1e-9 bar against the oracle's Jets).  Explicit, not `#pragma clang fp contract`: which
 // products a contracting compiler fuses depends on what the function is inlined into, and the one-launch kernel, the
-// evaluation kernel and the grid-barrier kernel must produce the same bits.  The float block in between -- which cell,
+// evaluation kernel and the batch kernel must produce the same bits.  The float block in between -- which cell,
 // which side of its centre: interpolated_grid.h:123-139 -- is the reference's arithmetic to the bit.
 __device__ __forceinline__ double cross_term(double a, double b, double c, double d) { return fma(a, b, -(c * d)); }  // a b - c d
 // interpolated_grid.h:88-102, one axis: (a - b) n^3 2 + (b - a) n^2 3 + a, with c3 = 2 n^3 and c2 = 3 n^2
@@ -269,8 +269,10 @@ __device__ __forceinline__ void csm_point(const CsmPose& a, const CsmCloudArg& c
 // 16, then l ^ 16 with 8, ... -- so that after five steps lane l holds ONE quantity (number l >> 1) summed over half the
 // wave and the sixth step completes it: 32 additions and 32 exchanges instead of 168 and 84, v_permlane32/16_swap and
 // DPP instead of ds_bpermute.  The waves' 4 x 28 results meet in LDS (2 KB, double-buffered: ONE barrier per call) and
-// every thread adds them.  The order of the additions is fixed, and the same in csm_eval_kernel, csm_lm_kernel and
-// csm_lm_grid_kernel: they still produce the same bits (tested).
+// every thread adds them.  The order of the additions is fixed, and the same in csm_eval_kernel and DeviceEval (tested).
+// The accumulation in front of it is written out in both ON PURPOSE: one __forceinline__ helper for it made csm_eval_kernel
+// 1 767 -> 1 731 instructions but csm_lm_kernel<1> 9 088 -> 9 137, <3> 11 742 -> 11 909 and csm_lm_batch_kernel<3>
+// 11 490 -> 11 614 (pointer or array reference alike), and csm_lm_kernel is bound by instruction issue.
 struct Halves {
   unsigned lo, hi;
 };
@@ -557,6 +559,15 @@ __host__ __device__ static void finish_normal(const double* sums28, const double
   out->cost = 0.5 * sumsq;
 }
 
+// The host's wait for a kernel of ctx->stream that ends in the completion word: polls it (wait_done) or, on a context
+// that has none, synchronises the stream -- one of the synchronisations dliom_ctx_synchronizations counts.
+static int wait_word_or_sync(dliom_ctx* ctx, const unsigned* done_word, unsigned seq) {
+  if (done_word != nullptr) return wait_done(ctx, ctx->stream, done_word, seq);
+  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ++ctx->host_syncs;
+  return DLIOM_OK;
+}
+
 // One evaluation at x = [t, q]: device occupied-space sums + host prior residuals.
 static int evaluate(CsmProblem* p, const double x[7], Normal* out) {
   dliom_ctx* ctx = p->ctx;
@@ -570,7 +581,7 @@ static int evaluate(CsmProblem* p, const double x[7], Normal* out) {
   double* host = pinned_at<double>(ctx, kPinCsmSums);
   // ... and a completion word behind them, which the host polls: ten evaluations a match, 5 us of synchronise each
   unsigned* done = p->d_arrivals != nullptr ? ctx->done_word : nullptr;
-  const unsigned seq = done != nullptr ? (++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq) : 0u;
+  const unsigned seq = done != nullptr ? next_done_seq(ctx) : 0u;
   hipLaunchKernelGGL(csm_eval_kernel, dim3(p->num_blocks), dim3(kCsmBlock), 0, ctx->stream, a, kValueToProbabilityScale,
                      kValueToProbabilityOffset, kUnknownProbability, p->d_partials, host, done, seq);
   if (p->num_blocks > 1)
@@ -578,10 +589,7 @@ static int evaluate(CsmProblem* p, const double x[7], Normal* out) {
                        p->num_blocks, host, p->d_arrivals, done, seq);
   ctx->end_span(span);
   DLIOM_HIP_TRY(hipGetLastError());
-  if (done != nullptr)
-    DLIOM_TRY(wait_done(ctx, ctx->stream, done, seq));
-  else
-    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  DLIOM_TRY(wait_word_or_sync(ctx, done, seq));
   ++p->evaluations;
   if (p->nloc == 3)
     finish_normal<3>(host, x, a.pose.plus, p->o->translation_weight, p->o->rotation_weight, p->target_t, p->init_q, out);
@@ -1057,123 +1065,6 @@ extern "C" int dliom_exp_lm_stamps(unsigned long long* out) {
 namespace dliom {
 #endif
 
-// ---- the whole Levenberg-Marquardt loop in ONE launch for LARGE clouds: the same grid as csm_eval_kernel (every
-// workgroup resident), every thread of every workgroup runs the same minimize<> loop on the same numbers, and an
-// evaluation is csm_eval_kernel's accumulation + block reduction, a grid barrier, and csm_final_reduce_kernel's
-// reduction done by every workgroup for itself -- the same additions in the same order, hence the same bits as the
-// per-evaluation loop, without its launch + synchronise round trip per evaluation (ten of them per match: 0.29 ms per
-// 131 072-point match, of which the kernels were 0.17).  The partial sums alternate between two buffers, so one barrier
-// per evaluation is enough.  Barrier: agent-scope release / acquire on one counter (MI355X_MICROARCH.md, "Inter-workgroup
-// visibility"), every spin bounded.
-struct GridSync {
-  unsigned* counter;   // zeroed by the host before the launch
-  unsigned target;     // arrivals expected so far
-  bool timed_out;
-};
-__device__ __forceinline__ void grid_barrier(GridSync& gs) {
-  __syncthreads();  // this workgroup's partial sums are written
-  gs.target += gridDim.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(gs.counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0;
-    while (__hip_atomic_load(gs.counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < gs.target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > (1u << 24)) break;  // ~seconds: a workgroup that never became resident; the match reports an error
-    }
-  }
-  __syncthreads();
-}
-
-template <int NLOC>
-struct DeviceGridEval {
-  const CsmArgs* a;
-  const LmKernelParams* prm;
-  double* part;              // block_reduce28's LDS: [2][4][32]
-  double* tot;               // [kAcc]
-  double* partials;          // 2 x gridDim.x x kAcc
-  GridSync gs;
-  int evaluations = 0;
-  __device__ int operator()(const double x[7], Normal* out) {
-    CsmPose pose;
-    for (int i = 0; i < 3; ++i) pose.t[i] = x[i];
-    for (int i = 0; i < 4; ++i) pose.q[i] = x[3 + i];
-    pose.nloc = NLOC;
-    plus_jacobian(x + 3, NLOC, pose.plus);
-    double acc[kAcc];
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) acc[k] = 0.;
-    const int stride = gridDim.x * blockDim.x;
-    for (int ci = 0; ci < a->num_clouds; ++ci) {
-      const CsmCloudArg& c = a->cloud[ci];
-      for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < c.n; i += stride) {
-        double r, j[6];
-        csm_point(pose, c, i, prm->k_scale, prm->k_offset, prm->k_unknown, &r, j);
-        int idx = 0;
-#pragma unroll
-        for (int p = 0; p < 6; ++p)
-#pragma unroll
-          for (int q = p; q < 6; ++q) acc[idx++] += j[p] * j[q];
-#pragma unroll
-        for (int p = 0; p < 6; ++p) acc[21 + p] += j[p] * r;
-        acc[27] += r * r;
-      }
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double* mine = partials + static_cast<size_t>(evaluations & 1) * gridDim.x * kAcc;
-    {
-      double block_sums[kAcc];
-      block_reduce28(acc, part, evaluations, block_sums);  // csm_eval_kernel's block reduction
-      if (threadIdx.x < kAcc) {
-        double v = block_sums[0];
-#pragma unroll
-        for (int k = 1; k < kAcc; ++k)
-          if (static_cast<int>(threadIdx.x) == k) v = block_sums[k];
-        mine[blockIdx.x * kAcc + threadIdx.x] = v;
-      }
-    }
-    grid_barrier(gs);
-    for (int k = wave; k < kAcc; k += kCsmBlock / 64) {  // csm_final_reduce_kernel's reduction
-      double sk = 0.;
-      for (int b = lane; b < static_cast<int>(gridDim.x); b += 64) sk += mine[b * kAcc + k];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) sk += __shfl_xor(sk, off, 64);
-      if (lane == 0) tot[k] = sk;
-    }
-    __syncthreads();
-    double sums[kAcc];
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) sums[k] = tot[k];
-    finish_normal<NLOC>(sums, x, pose.plus, prm->translation_weight, prm->rotation_weight, prm->target_t, prm->init_q, out);
-    ++evaluations;
-    return DLIOM_OK;
-  }
-};
-
-template <int NLOC>
-__global__ __launch_bounds__(kCsmBlock) void csm_lm_grid_kernel(CsmArgs a, LmKernelParams prm, double* partials,
-                                                                unsigned* counter, LmKernelOut* out) {
-  __shared__ double part[2 * (kCsmBlock / 64) * 32];
-  __shared__ double tot[kAcc];
-  DeviceGridEval<NLOC> ev;
-  ev.a = &a;
-  ev.prm = &prm;
-  ev.part = part;
-  ev.tot = tot;
-  ev.partials = partials;
-  ev.gs = GridSync{counter, 0u, false};
-  double x[7];
-  for (int i = 0; i < 7; ++i) x[i] = prm.x0[i];
-  dliom_csm_summary sum;
-  const int status = minimize<NLOC>(ev, prm.cfg, x, &sum);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    for (int i = 0; i < 7; ++i) out->x[i] = x[i];
-    out->summary = sum;
-    // every workgroup must have taken part in every barrier: the counter tells
-    const unsigned arrived = __hip_atomic_load(counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    out->status = arrived >= ev.gs.target ? status : DLIOM_ERR_HIP;
-  }
-}
-
 static int setup_problem(dliom_ctx* ctx, const dliom_csm_options* o, const double target_t[3],
                          const double init7[7], int k, const dliom_cloud* const* clouds,
                          const dliom_grid* const* grids, CsmProblem* p) {
@@ -1235,17 +1126,34 @@ static LmKernelParams lm_params(const dliom_csm_options* o, const CsmProblem& p,
   return prm;
 }
 
+// What a problem's clouds are refused for before anything is staged -- their number, then cloud after cloud; shared by
+// the single call and the batch.  device[j] != nullptr: cloud j is on the device already, pts[j] and n[j] do not count.
+static int clouds_refusal(int k, const dliom_cloud* const* device, const float* const* pts, const int64_t* n) {
+  if (k <= 0 || k > DLIOM_MAX_CLOUDS) return DLIOM_ERR_WEIGHTS;
+  for (int j = 0; j < k; ++j) {
+    if (device != nullptr && device[j] != nullptr) continue;
+    if (n[j] < 0 || (n[j] > 0 && pts[j] == nullptr)) return DLIOM_ERR_INVALID_ARGUMENT;
+    if (n[j] == 0) return DLIOM_ERR_EMPTY_CLOUD;
+  }
+  return DLIOM_OK;
+}
+
+// Where host clouds of n[0 .. count) points go in ctx->points, one behind the other (stage_cloud's offsets; n[i] <= 0:
+// nothing is staged for i).  Returns the bytes to reserve.
+static size_t staged_layout(const int64_t* n, size_t count, size_t* off) {
+  size_t total = 0;
+  for (size_t i = 0; i < count; ++i) {
+    off[i] = total;
+    if (n[i] > 0) total += align256(staged_cloud_bytes(n[i]));
+  }
+  return total;
+}
+
 static int stage_clouds(dliom_ctx* ctx, int k, const float* const* pts, const int64_t* n,
                         std::vector<dliom_cloud>* staged, std::vector<const dliom_cloud*>* ptrs) {
-  size_t total = 0;
+  DLIOM_TRY(clouds_refusal(k, nullptr, pts, n));
   std::vector<size_t> off(k);
-  for (int i = 0; i < k; ++i) {
-    if (n[i] < 0 || (n[i] > 0 && pts[i] == nullptr)) return DLIOM_ERR_INVALID_ARGUMENT;
-    if (n[i] == 0) return DLIOM_ERR_EMPTY_CLOUD;
-    off[i] = total;
-    total += align256(staged_cloud_bytes(n[i]));
-  }
-  DLIOM_TRY(ctx->points.reserve(total));
+  DLIOM_TRY(ctx->points.reserve(staged_layout(n, static_cast<size_t>(k), off.data())));
   staged->resize(k);
   ptrs->resize(k);
   for (int i = 0; i < k; ++i) {
@@ -1281,7 +1189,7 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* o, const do
     LmKernelParams prm = lm_params(o, p, cfg, x);
     LmKernelOut* host = pinned_at<LmKernelOut>(ctx, kPinLmResult);  // device-visible
     prm.done_word = ctx->done_word;
-    prm.done_seq = ctx->done_word != nullptr ? (++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq) : 0u;
+    prm.done_seq = ctx->done_word != nullptr ? next_done_seq(ctx) : 0u;
     const int span = ctx->begin_span(DLIOM_KERNEL_CSM_EVAL);
     if (p.nloc == 3)
       hipLaunchKernelGGL(csm_lm_kernel<3>, dim3(1), dim3(kCsmBlock), 0, ctx->stream, p.args, prm, host);
@@ -1289,46 +1197,7 @@ int dliom_csm3d_match_cloud(dliom_ctx* ctx, const dliom_csm_options* o, const do
       hipLaunchKernelGGL(csm_lm_kernel<1>, dim3(1), dim3(kCsmBlock), 0, ctx->stream, p.args, prm, host);
     ctx->end_span(span);
     DLIOM_HIP_TRY(hipGetLastError());
-    if (prm.done_word != nullptr) {
-      DLIOM_TRY(wait_done(ctx, ctx->stream, prm.done_word, prm.done_seq));
-    } else {
-      DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      ++ctx->host_syncs;
-    }
-    std::memcpy(out7, host->x, sizeof(x));
-    *sum = host->summary;
-    return host->status;
-  }
-  const int num_cus = ctx->num_cus;
-  // large clouds: the loop in one launch with grid barriers when every workgroup of the evaluation grid is resident at
-  // once (256 threads and 57 KB of LDS each: two per CU)
-  if (ctx->tuning[DLIOM_TUNE_CSM_GRID_SYNC] != 0 && p.num_blocks > 1 && p.num_blocks <= 2 * num_cus) {
-    LmKernelParams prm;
-    prm.cfg = cfg;
-    prm.translation_weight = o->translation_weight;
-    prm.rotation_weight = o->rotation_weight;
-    for (int i = 0; i < 3; ++i) prm.target_t[i] = p.target_t[i];
-    for (int i = 0; i < 4; ++i) prm.init_q[i] = p.init_q[i];
-    for (int i = 0; i < 7; ++i) prm.x0[i] = x[i];
-    prm.k_scale = kValueToProbabilityScale;
-    prm.k_offset = kValueToProbabilityOffset;
-    prm.k_unknown = kUnknownProbability;
-    prm.done_word = nullptr;
-    prm.done_seq = 0u;
-    const size_t part_bytes = align256(2 * static_cast<size_t>(p.num_blocks) * kAcc * sizeof(double));
-    DLIOM_TRY(ctx->partials.reserve(part_bytes + 256));
-    double* partials = ctx->partials.as<double>();
-    unsigned* counter = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->partials.p) + part_bytes);
-    DLIOM_HIP_TRY(hipMemsetAsync(counter, 0, 4, ctx->stream));
-    LmKernelOut* host = pinned_at<LmKernelOut>(ctx, kPinLmResult);  // device-visible
-    const int span = ctx->begin_span(DLIOM_KERNEL_CSM_EVAL);
-    if (p.nloc == 3)
-      hipLaunchKernelGGL(csm_lm_grid_kernel<3>, dim3(p.num_blocks), dim3(kCsmBlock), 0, ctx->stream, p.args, prm, partials, counter, host);
-    else
-      hipLaunchKernelGGL(csm_lm_grid_kernel<1>, dim3(p.num_blocks), dim3(kCsmBlock), 0, ctx->stream, p.args, prm, partials, counter, host);
-    ctx->end_span(span);
-    DLIOM_HIP_TRY(hipGetLastError());
-    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    DLIOM_TRY(wait_word_or_sync(ctx, prm.done_word, prm.done_seq));
     std::memcpy(out7, host->x, sizeof(x));
     *sum = host->summary;
     return host->status;
@@ -1371,18 +1240,15 @@ int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* o, int coun
   constexpr int kChunk = 256;  // problems per launch; bounds the host clouds staged at once
   for (int at = 0; at < count; at += kChunk) {
     const int B = std::min(kChunk, count - at);
-    // host clouds: staged for the whole chunk with one reservation (stage_clouds' layout, problem after problem)
-    size_t total = 0;
-    std::vector<size_t> off(static_cast<size_t>(B) * DLIOM_MAX_CLOUDS, 0);
+    // host clouds: staged for the whole chunk with one reservation, problem after problem
+    std::vector<int64_t> host_n(static_cast<size_t>(B) * DLIOM_MAX_CLOUDS, 0);
+    std::vector<size_t> off(host_n.size());
     for (int b = 0; b < B; ++b) {
       const dliom_csm_problem& q = problems[at + b];
       for (int j = 0; j < std::min(std::max(q.num_clouds, 0), DLIOM_MAX_CLOUDS); ++j)
-        if (q.clouds[j] == nullptr && q.n[j] > 0) {
-          off[b * DLIOM_MAX_CLOUDS + j] = total;
-          total += align256(staged_cloud_bytes(q.n[j]));
-        }
+        if (q.clouds[j] == nullptr) host_n[b * DLIOM_MAX_CLOUDS + j] = q.n[j];
     }
-    DLIOM_TRY(ctx->points.reserve(total));
+    DLIOM_TRY(ctx->points.reserve(staged_layout(host_n.data(), host_n.size(), off.data())));
     std::vector<dliom_cloud> staged(static_cast<size_t>(B) * DLIOM_MAX_CLOUDS);
     std::vector<CsmProblem> prob(B);
     std::vector<int> batched, single;
@@ -1391,17 +1257,14 @@ int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* o, int coun
       const dliom_csm_problem& q = problems[i];
       std::memset(&poses[7 * static_cast<size_t>(i)], 0, 7 * sizeof(double));
       if (summaries != nullptr) std::memset(&summaries[i], 0, sizeof(dliom_csm_summary));
-      // dliom_csm3d_match's refusals, in its order
-      int status = q.num_clouds <= 0 || q.num_clouds > DLIOM_MAX_CLOUDS ? DLIOM_ERR_WEIGHTS : DLIOM_OK;
+      int status = clouds_refusal(q.num_clouds, q.clouds, q.points_xyz, q.n);
       const dliom_cloud* clouds[DLIOM_MAX_CLOUDS] = {};
       for (int j = 0; status == DLIOM_OK && j < q.num_clouds; ++j) {
-        if (q.clouds[j] != nullptr) {
-          clouds[j] = q.clouds[j];
-        } else if (q.n[j] == 0) {
-          status = DLIOM_ERR_EMPTY_CLOUD;
-        } else {
-          status = stage_cloud(ctx, q.points_xyz[j], q.n[j], &staged[b * DLIOM_MAX_CLOUDS + j], off[b * DLIOM_MAX_CLOUDS + j]);
-          clouds[j] = &staged[b * DLIOM_MAX_CLOUDS + j];
+        clouds[j] = q.clouds[j];
+        if (clouds[j] == nullptr) {
+          const size_t slot = static_cast<size_t>(b) * DLIOM_MAX_CLOUDS + j;
+          status = stage_cloud(ctx, q.points_xyz[j], q.n[j], &staged[slot], off[slot]);
+          clouds[j] = &staged[slot];
         }
       }
       if (status == DLIOM_OK)
@@ -1437,7 +1300,7 @@ int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* o, int coun
       DLIOM_HIP_TRY(hipMemcpyAsync(d, h, upload, hipMemcpyHostToDevice, ctx->stream));
       unsigned* arrivals = reinterpret_cast<unsigned*>(d + args_bytes + prm_bytes);
       unsigned* done_word = ctx->done_word != nullptr ? ctx->done_word : reinterpret_cast<unsigned*>(h + args_bytes + prm_bytes);
-      const unsigned seq = ++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq;
+      const unsigned seq = next_done_seq(ctx);
       if (nloc == 3)
         hipLaunchKernelGGL(csm_lm_batch_kernel<3>, dim3(n), dim3(kCsmBlock), 0, ctx->stream, reinterpret_cast<const CsmArgs*>(d),
                            reinterpret_cast<const LmKernelParams*>(d + args_bytes), h_out, arrivals, done_word, seq);
@@ -1445,12 +1308,7 @@ int dliom_csm3d_match_batch(dliom_ctx* ctx, const dliom_csm_options* o, int coun
         hipLaunchKernelGGL(csm_lm_batch_kernel<1>, dim3(n), dim3(kCsmBlock), 0, ctx->stream, reinterpret_cast<const CsmArgs*>(d),
                            reinterpret_cast<const LmKernelParams*>(d + args_bytes), h_out, arrivals, done_word, seq);
       DLIOM_HIP_TRY(hipGetLastError());
-      if (ctx->done_word != nullptr) {
-        DLIOM_TRY(wait_done(ctx, ctx->stream, done_word, seq));
-      } else {
-        DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ++ctx->host_syncs;
-      }
+      DLIOM_TRY(wait_word_or_sync(ctx, ctx->done_word, seq));
       ++st.lm_launches;
       ++st.chunks;
       st.batched += n;

@@ -19,6 +19,7 @@
 // box of the submap's leaves (a max-pool is order independent); cells outside read 0 like
 // HybridGridBase<uint8>::value() of an unset cell.
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -413,6 +414,7 @@ struct Search {
   std::vector<PoseF> scan_poses;
   std::vector<float> rotational_scores;
   int n_hi = 0;
+  int64_t n_lo = 0;  // the batch: points of the low-resolution cloud (lo_cloud is made per chunk)
   int *d_cx = nullptr, *d_cy = nullptr, *d_cz = nullptr;
   const dliom_cloud* lo_cloud = nullptr;
   float min_low_resolution_score_f = 0.f;
@@ -481,7 +483,17 @@ struct Search {
            (static_cast<uint64_t>((o[0] + 8192) & 0x3FFF) << 28) | (static_cast<uint64_t>((o[1] + 8192) & 0x3FFF) << 14) |
            static_cast<uint64_t>((o[2] + 8192) & 0x3FFF);
   }
+  static uint64_t key(int depth, const Candidate& c) { return key(depth, c.scan_index, c.offset); }
 };
+
+// a candidate <-> its record in the device frontier's lists; a float pose -> t, q (w, x, y, z) as floats or doubles
+inline Candidate to_candidate(const FrontierRec& r) { return Candidate{r.scan, {r.ox, r.oy, r.oz}}; }
+inline FrontierRec to_rec(const Candidate& c) { return FrontierRec{c.scan_index, c.offset[0], c.offset[1], c.offset[2], 0}; }
+template <class T>
+inline void pose7(const PoseF& p, T* out) {
+  const T v[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
+  std::memcpy(out, v, sizeof(v));
+}
 
 // Integer sums of `list` at `depth` (device), in list order.
 int device_sums(Search& s, int depth, const std::vector<Candidate>& list, std::vector<int>* sums) {
@@ -540,20 +552,30 @@ inline float to_probability(float value) {  // precomputation_grid_3d.h:31-34
   return kMinProbability + value * ((kMaxProbability - kMinProbability) / 255.f);
 }
 
+// Appends to `missing` those of `list` whose sum at `depth` the cache lacks.
+void append_missing(const Search& s, int depth, const std::vector<Candidate>& list, std::vector<Candidate>* missing) {
+  for (const Candidate& c : list)
+    if (!s.cache.has(Search::key(depth, c))) missing->push_back(c);
+}
+// The sums of `missing` at `depth`: from the device into the cache.
+int fetch_sums(Search& s, int depth, const std::vector<Candidate>& missing) {
+  if (missing.empty()) return DLIOM_OK;
+  std::vector<int> sums;
+  DLIOM_TRY(device_sums(s, depth, missing, &sums));
+  for (size_t i = 0; i < missing.size(); ++i) s.cache.put(Search::key(depth, missing[i]), sums[i]);
+  return DLIOM_OK;
+}
+// ScoreCandidates' float (:407-411) of a candidate whose sum is in the cache.
+float cached_score(const Search& s, int depth, const Candidate& c) {
+  return to_probability(*s.cache.get(Search::key(depth, c)) / static_cast<float>(s.n_hi));
+}
+
 // ScoreCandidates (:394-417) with the sums served from the cache (filled here when missing).
 int score_candidates(Search& s, int depth, std::vector<Candidate>* candidates) {
   std::vector<Candidate> missing;
-  for (const Candidate& c : *candidates)
-    if (!s.cache.has(Search::key(depth, c.scan_index, c.offset))) missing.push_back(c);
-  if (!missing.empty()) {
-    std::vector<int> sums;
-    DLIOM_TRY(device_sums(s, depth, missing, &sums));
-    for (size_t i = 0; i < missing.size(); ++i) s.cache.put(Search::key(depth, missing[i].scan_index, missing[i].offset), sums[i]);
-  }
-  for (Candidate& c : *candidates) {
-    const int sum = *s.cache.get(Search::key(depth, c.scan_index, c.offset));
-    c.score = to_probability(sum / static_cast<float>(s.n_hi));
-  }
+  append_missing(s, depth, *candidates, &missing);
+  DLIOM_TRY(fetch_sums(s, depth, missing));
+  for (Candidate& c : *candidates) c.score = cached_score(s, depth, c);
   std::sort(candidates->begin(), candidates->end(), std::greater<Candidate>());
   return DLIOM_OK;
 }
@@ -586,14 +608,9 @@ int prefetch_children(Search& s, const std::vector<Candidate>& siblings, size_t 
     if (siblings[i].score <= min_score) break;
     std::vector<Candidate> ch;
     children_of(s, siblings[i], candidate_depth, &ch);
-    for (const Candidate& c : ch)
-      if (!s.cache.has(Search::key(candidate_depth - 1, c.scan_index, c.offset))) batch.push_back(c);
+    append_missing(s, candidate_depth - 1, ch, &batch);
   }
-  if (batch.empty()) return DLIOM_OK;
-  std::vector<int> sums;
-  DLIOM_TRY(device_sums(s, candidate_depth - 1, batch, &sums));
-  for (size_t i = 0; i < batch.size(); ++i) s.cache.put(Search::key(candidate_depth - 1, batch[i].scan_index, batch[i].offset), sums[i]);
-  return DLIOM_OK;
+  return fetch_sums(s, candidate_depth - 1, batch);
 }
 
 // Wavefront prefetch: once a first match has raised the bound, every node the recursion can still
@@ -609,17 +626,11 @@ int prefetch_frontier(Search& s, float threshold) {
     for (const Candidate& c : frontier) children_of(s, c, depth, &children);
     if (children.size() > (1u << 18)) break;  // a flat score landscape: stay with on-demand batches
     std::vector<Candidate> missing;
-    for (const Candidate& c : children)
-      if (!s.cache.has(Search::key(depth - 1, c.scan_index, c.offset))) missing.push_back(c);
-    if (!missing.empty()) {
-      std::vector<int> sums;
-      DLIOM_TRY(device_sums(s, depth - 1, missing, &sums));
-      for (size_t i = 0; i < missing.size(); ++i)
-        s.cache.put(Search::key(depth - 1, missing[i].scan_index, missing[i].offset), sums[i]);
-    }
+    append_missing(s, depth - 1, children, &missing);
+    DLIOM_TRY(fetch_sums(s, depth - 1, missing));
     frontier.clear();
     for (Candidate& c : children) {
-      c.score = to_probability(*s.cache.get(Search::key(depth - 1, c.scan_index, c.offset)) / static_cast<float>(s.n_hi));
+      c.score = cached_score(s, depth - 1, c);
       if (c.score > threshold) frontier.push_back(c);
     }
   }
@@ -680,11 +691,7 @@ float take_frontier(Search& s, const int* out, int out_records, int cap) {
   int at = 0;
   for (int depth = max_depth; depth >= 0 && at < out_records; --depth) {
     const int cnt = std::min(std::min(out[depth], cap), out_records - at);
-    for (int i = 0; i < cnt; ++i) {
-      const FrontierRec& r = rec[at + i];
-      const int o[3] = {r.ox, r.oy, r.oz};
-      s.cache.put(Search::key(depth, r.scan, o), r.sum);
-    }
+    for (int i = 0; i < cnt; ++i) s.cache.put(Search::key(depth, to_candidate(rec[at + i])), rec[at + i].sum);
     at += cnt;
   }
   s.scored += at;
@@ -734,7 +741,7 @@ int device_frontier(Search& s, const std::vector<Candidate>& lowest, float min_s
   std::memset(counts, 0, kCountWords * 4);
   counts[max_depth] = static_cast<int>(k);
   FrontierRec* flat = reinterpret_cast<FrontierRec*>(h + frontier_flat_at(1));
-  for (size_t i = 0; i < k; ++i) flat[i] = FrontierRec{lowest[i].scan_index, lowest[i].offset[0], lowest[i].offset[1], lowest[i].offset[2], 0};
+  for (size_t i = 0; i < k; ++i) flat[i] = to_rec(lowest[i]);
   DLIOM_HIP_TRY(hipMemcpyAsync(d, h, frontier_upload_bytes(1, k), hipMemcpyHostToDevice, ctx->stream));
   DLIOM_TRY(enqueue_frontier_chain(ctx, 1, static_cast<int>(k), max_depth, d));
   DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -756,8 +763,8 @@ int low_resolution_score(Search& s, const Candidate& c, float* score) {  // low_
   if (ahead != s.low_sums.end()) {
     sum = ahead->second;  // scored by the batch's chain: the same kernels on the same pose
   } else {
-    const PoseF pose = pose_from_candidate(s, c);
-    const float p7[7] = {pose.t.x, pose.t.y, pose.t.z, pose.q.w, pose.q.x, pose.q.y, pose.q.z};
+    float p7[7];
+    pose7(pose_from_candidate(s, c), p7);
     DLIOM_TRY(sequential_probability_sums(s.ctx, *s.lo_cloud, s.m->lo_grid, p7, 1, &sum));
   }
   *score = sum / static_cast<float>(s.lo_cloud->n);
@@ -850,9 +857,7 @@ int finish_search(Search& s, std::vector<Candidate>* lowest, float min_score, dl
   if (best.score > min_score) {
     r->found = 1;
     r->score = best.score;
-    const PoseF p = pose_from_candidate(s, best);
-    const double out[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
-    std::memcpy(r->pose_estimate, out, sizeof(out));
+    pose7(pose_from_candidate(s, best), r->pose_estimate);
     r->rotational_score = s.rotational_scores[best.scan_index];
     r->low_resolution_score = best.low_resolution_score;
   }
@@ -876,11 +881,7 @@ int run_search(Search& s, const dliom_cloud& hi_cloud, float min_score, dliom_fa
   s.d_cy = s.d_cx + cells;
   s.d_cz = s.d_cy + cells;
   std::vector<float> poses(7 * static_cast<size_t>(num_scans));
-  for (int i = 0; i < num_scans; ++i) {
-    const PoseF& p = s.scan_poses[i];
-    const float v[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
-    std::memcpy(&poses[7 * i], v, sizeof(v));
-  }
+  for (int i = 0; i < num_scans; ++i) pose7(s.scan_poses[i], &poses[7 * static_cast<size_t>(i)]);
   // through the pinned block when they fit: no synchronisation here, the stream orders the kernels behind the copy
   const bool poses_pinned = poses.size() * 4 <= kPinPoses.bytes;
   const float* poses_src = poses.data();
@@ -990,6 +991,22 @@ void setup_search(Search* s, dliom_ctx* ctx, const dliom_fast_csm* m, int kind, 
   }
 }
 
+// What the three single calls share.  `submap_pose` is neither read nor required by MatchWith3DofInitial.
+int match_one(dliom_ctx* ctx, const dliom_fast_csm* m, int kind, const double* pose, const double* submap_pose,
+              const dliom_fast_csm_node_data* data, float min_score, dliom_fast_csm_result* result) {
+  if (ctx == nullptr || m == nullptr || pose == nullptr || result == nullptr ||
+      (submap_pose == nullptr && kind != DLIOM_FAST_CSM_MATCH_WITH_3DOF_INITIAL))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  if (ctx->device != m->ctx->device) return DLIOM_ERR_INVALID_ARGUMENT;  // the pyramid lives on the creating device
+  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  StagedClouds c;
+  DLIOM_TRY(stage(ctx, data, &c));
+  Search s;
+  setup_search(&s, ctx, m, kind, pose, submap_pose, *data, c.hi->max_norm);
+  s.lo_cloud = c.lo;
+  return run_search(s, *c.hi, min_score, result);
+}
+
 // ---- the batch (dliom_fast_csm_match_batch) -------------------------------------------------------------------
 constexpr int kBatchCap = 4096;          // records per list of a batched search (the single call's: 8 192)
 constexpr int kBatchOutRecords = 4096;   // records a batched search packs into its page-locked region
@@ -1001,39 +1018,80 @@ constexpr int kChunkScans = 65535;       //   discrete scans (discretize_batch_k
 
 inline size_t pad64(int64_t n) { return (static_cast<size_t>(n) + 63) & ~static_cast<size_t>(63); }
 
+// What one search takes of a chunk's blocks, each stated once: for the chunking (fast_csm_batch) and the layout below.
+inline size_t num_scans_of(const Search& s) { return s.scan_poses.size(); }
+inline size_t hi_cloud_bytes(const Search& s) { return align256(static_cast<size_t>(s.n_hi) * 12); }  // packed xyz
+inline size_t lo_cloud_bytes(const Search& s) { return 3 * pad64(s.n_lo) * 4; }                       // SoA, zero padded
+inline size_t pool_bytes(const Search& s) { return static_cast<size_t>(s.m->max_depth() + 1) * kBatchCap * sizeof(FrontierRec); }
+inline size_t cell_bytes(const Search& s) { return align256(3 * num_scans_of(s) * static_cast<size_t>(s.n_hi) * 4); }
+
+// One chunk's device block (ctx->batch) and page-locked block (ctx->batch_pinned), in the manner of pinned_layout.h.
+// Device: the upload [frontier args | counts | flat top (frontier_*_at)][scans][hi][lo], then [pools][cells] and the leaves'
+// [rot][trans][list][lsum].  Page-locked: the upload's mirror, then [h_out: out_stride per search][h_leaf: the mirror of
+// rot, trans and list][h_lsum].  Within scans, hi, lo, pools and cells the searches follow one another in chunk order.
+struct ChunkLayout {
+  size_t total_top = 0, total_scans = 0;
+  int deepest = 0, widest = 0;  // the deepest pyramid, the largest high-resolution cloud
+  PinRegion scans, hi, lo, pools, cells, rot, trans, list, lsum, h_out, h_leaf, h_lsum;
+  size_t out_stride, upload_bytes, device_bytes, pinned_bytes;
+};
+ChunkLayout chunk_layout(const int* ids, int S, const std::vector<std::unique_ptr<Search>>& searches,
+                         const std::vector<std::vector<Candidate>>& lowest) {
+  ChunkLayout L;
+  size_t hi = 0, lo = 0, pool = 0, cells = 0;
+  for (int j = 0; j < S; ++j) {
+    const Search& s = *searches[ids[j]];
+    L.total_top += lowest[ids[j]].size();
+    L.total_scans += num_scans_of(s);
+    hi += hi_cloud_bytes(s);
+    lo += lo_cloud_bytes(s);
+    pool += pool_bytes(s);
+    cells += cell_bytes(s);
+    L.deepest = std::max(L.deepest, s.m->max_depth());
+    L.widest = std::max(L.widest, s.n_hi);
+  }
+  const size_t leaves = static_cast<size_t>(S) * kBatchLeavesAhead;
+  L.out_stride = align256((kMaxLevels + 2) * 4 + static_cast<size_t>(kBatchOutRecords) * sizeof(FrontierRec));
+  const auto end = [](PinRegion r) { return r.at + r.bytes; };
+  const PinRegion front{0, align256(frontier_upload_bytes(S, L.total_top))};
+  L.scans = PinRegion{end(front), align256(L.total_scans * sizeof(DiscreteScanArg))};
+  L.hi = PinRegion{end(L.scans), hi};
+  L.lo = PinRegion{end(L.hi), lo};
+  L.upload_bytes = end(L.lo);
+  L.pools = PinRegion{align256(L.upload_bytes), pool};
+  L.cells = PinRegion{end(L.pools), cells};
+  L.rot = PinRegion{end(L.cells), align256(leaves * 16)};
+  L.trans = PinRegion{end(L.rot), align256(leaves * 12)};
+  L.list = PinRegion{end(L.trans), align256(leaves * 4)};
+  L.lsum = PinRegion{end(L.list), align256(leaves * 4)};
+  L.device_bytes = end(L.lsum);
+  L.h_out = PinRegion{align256(L.upload_bytes), S * L.out_stride};
+  L.h_leaf = PinRegion{end(L.h_out), L.lsum.at - L.rot.at};
+  L.h_lsum = PinRegion{end(L.h_leaf), L.lsum.bytes};
+  L.pinned_bytes = end(L.h_lsum);
+#ifdef DLIOM_DEBUG_CHECKS  // make experiments EXP_FLAGS=-DDLIOM_DEBUG_CHECKS; the shipped library has no abort path
+  const auto chained = [&end](std::initializer_list<PinRegion> rs, size_t total) {  // no overlap, the last ends at the total
+    size_t at = 0;
+    for (const PinRegion& r : rs) {
+      if (r.at < at) return false;
+      at = end(r);
+    }
+    return at == total;
+  };
+  assert(chained({front, L.scans, L.hi, L.lo, L.pools, L.cells, L.rot, L.trans, L.list, L.lsum}, L.device_bytes));
+  assert(chained({front, L.scans, L.hi, L.lo, L.h_out, L.h_leaf, L.h_lsum}, L.pinned_bytes));
+#endif
+  return L;
+}
+
 // One chunk: discretisation + frontier chain (one synchronisation), the low-resolution scores of the leaves at or
 // above each search's theta (one more), then each search's recursion in query order.
 int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const int* ids, int S,
                    std::vector<std::unique_ptr<Search>>& searches, std::vector<std::vector<Candidate>>& lowest,
                    dliom_fast_csm_result* results, dliom_batch_stats* st) {
-  // ---- layout: upload [frontier args | counts | flat top][scan args][hi clouds xyz][lo clouds SoA], then device-only
-  // pools and cells; page-locked: the upload's mirror, the output regions, the leaves' poses and their sums
-  size_t total_top = 0, total_scans = 0, hi_bytes = 0, lo_bytes = 0, pool_bytes = 0, cell_bytes = 0;
-  int deepest = 0, widest = 0;
-  for (int j = 0; j < S; ++j) {
-    const Search& s = *searches[ids[j]];
-    const dliom_fast_csm_node_data& d = queries[ids[j]].node_data;
-    total_top += lowest[ids[j]].size();
-    total_scans += s.scan_poses.size();
-    hi_bytes += align256(static_cast<size_t>(d.num_high_resolution_points) * 12);
-    lo_bytes += 3 * pad64(d.num_low_resolution_points) * 4;
-    pool_bytes += static_cast<size_t>(s.m->max_depth() + 1) * kBatchCap * sizeof(FrontierRec);
-    cell_bytes += align256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
-    deepest = std::max(deepest, s.m->max_depth());
-    widest = std::max(widest, s.n_hi);
-  }
-  const size_t front_bytes = align256(frontier_upload_bytes(S, total_top));
-  const size_t scan_at = front_bytes, hi_at = scan_at + align256(total_scans * sizeof(DiscreteScanArg)), lo_at = hi_at + hi_bytes;
-  const size_t upload_bytes = lo_at + lo_bytes;
-  const size_t pool_at = align256(upload_bytes), cells_at = pool_at + pool_bytes;
-  const size_t leaves = static_cast<size_t>(S) * kBatchLeavesAhead;
-  const size_t rot_at = cells_at + cell_bytes, trans_at = rot_at + align256(leaves * 16), list_at = trans_at + align256(leaves * 12),
-               lsum_at = list_at + align256(leaves * 4);
-  DLIOM_TRY(ctx->batch.reserve(lsum_at + align256(leaves * 4)));
-  const size_t out_stride = align256((kMaxLevels + 2) * 4 + static_cast<size_t>(kBatchOutRecords) * sizeof(FrontierRec));
-  const size_t h_out_at = align256(upload_bytes), h_leaf_at = h_out_at + S * out_stride;
-  const size_t h_lsum_at = h_leaf_at + (lsum_at - rot_at);
-  DLIOM_TRY(ctx->reserve_batch_pinned(h_lsum_at + align256(leaves * 4)));
+  const ChunkLayout L = chunk_layout(ids, S, searches, lowest);
+  DLIOM_TRY(ctx->batch.reserve(L.device_bytes));
+  DLIOM_TRY(ctx->reserve_batch_pinned(L.pinned_bytes));
   char* d = static_cast<char*>(ctx->batch.p);
   char* h = static_cast<char*>(ctx->batch_pinned);
 
@@ -1041,38 +1099,37 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
   FrontierArgs* h_args = reinterpret_cast<FrontierArgs*>(h);
   int* h_counts = reinterpret_cast<int*>(h + frontier_counts_at(S));
   FrontierRec* h_flat = reinterpret_cast<FrontierRec*>(h + frontier_flat_at(S));
-  DiscreteScanArg* h_scans = reinterpret_cast<DiscreteScanArg*>(h + scan_at);
+  DiscreteScanArg* h_scans = reinterpret_cast<DiscreteScanArg*>(h + L.scans.at);
   std::memset(h_counts, 0, static_cast<size_t>(S) * kCountWords * 4);
   std::vector<dliom_cloud> lo(S);
-  size_t top = 0, scan = 0, hi_off = 0, lo_off = 0, pool_off = 0, cell_off = 0;
+  struct {
+    size_t top = 0, scan = 0, hi = 0, lo = 0, pool = 0, cells = 0;
+  } at;  // where search j begins in the flat top list, the scan arguments and (bytes) the regions of those names
   for (int j = 0; j < S; ++j) {
     Search& s = *searches[ids[j]];
     const dliom_fast_csm_node_data& nd = queries[ids[j]].node_data;
     const std::vector<Candidate>& low = lowest[ids[j]];
     const int num_scans = static_cast<int>(s.scan_poses.size());
     const size_t cells = static_cast<size_t>(num_scans) * s.n_hi;
-    s.d_cx = reinterpret_cast<int*>(d + cells_at + cell_off);
+    s.d_cx = reinterpret_cast<int*>(d + L.cells.at + at.cells);
     s.d_cy = s.d_cx + cells;
     s.d_cz = s.d_cy + cells;
-    std::memcpy(h + hi_at + hi_off, nd.high_resolution_points, static_cast<size_t>(s.n_hi) * 12);
-    const float* d_pts = reinterpret_cast<const float*>(d + hi_at + hi_off);
-    for (int k = 0; k < num_scans; ++k, ++scan) {
-      DiscreteScanArg& a = h_scans[scan];
-      const PoseF& p = s.scan_poses[k];
-      a.pts = d_pts;
+    std::memcpy(h + L.hi.at + at.hi, nd.high_resolution_points, static_cast<size_t>(s.n_hi) * 12);
+    for (int k = 0; k < num_scans; ++k) {
+      DiscreteScanArg& a = h_scans[at.scan + k];
+      a.pts = reinterpret_cast<const float*>(d + L.hi.at + at.hi);
       a.cx = s.d_cx + static_cast<size_t>(k) * s.n_hi;
       a.cy = s.d_cy + static_cast<size_t>(k) * s.n_hi;
       a.cz = s.d_cz + static_cast<size_t>(k) * s.n_hi;
       a.n = s.n_hi;
       a.resolution = s.m->resolution;
-      const float v[7] = {p.t.x, p.t.y, p.t.z, p.q.w, p.q.x, p.q.y, p.q.z};
-      std::memcpy(a.pose, v, sizeof(v));
+      pose7(s.scan_poses[k], a.pose);
     }
     // the low-resolution cloud, SoA, zero padded (what sequential_probability_sums reads of a dliom_cloud)
     const int64_t n_lo = nd.num_low_resolution_points;
     const size_t pl = pad64(n_lo);
-    float* hx = reinterpret_cast<float*>(h + lo_at + lo_off);
-    std::memset(hx, 0, 3 * pl * 4);
+    float* hx = reinterpret_cast<float*>(h + L.lo.at + at.lo);
+    std::memset(hx, 0, lo_cloud_bytes(s));
     for (int64_t i = 0; i < n_lo; ++i) {
       hx[i] = nd.low_resolution_points[3 * i];
       hx[pl + i] = nd.low_resolution_points[3 * i + 1];
@@ -1083,7 +1140,7 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
     c.device = ctx->device;
     c.n = n_lo;
     c.n_padded = static_cast<int64_t>(pl);
-    c.d_x = reinterpret_cast<float*>(d + lo_at + lo_off);
+    c.d_x = reinterpret_cast<float*>(d + L.lo.at + at.lo);
     c.d_y = c.d_x + pl;
     c.d_z = c.d_y + pl;
     c.max_norm = cloud_max_norm(nd.low_resolution_points, n_lo);
@@ -1091,42 +1148,48 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
     s.lo_cloud = &c;
     // the frontier
     FrontierArgs a = frontier_args(s, queries[ids[j]].min_score);
-    a.pool = reinterpret_cast<FrontierRec*>(d + pool_at + pool_off);
+    a.pool = reinterpret_cast<FrontierRec*>(d + L.pools.at + at.pool);
     a.counts = reinterpret_cast<int*>(d + frontier_counts_at(S)) + static_cast<size_t>(j) * kCountWords;
     a.cap = kBatchCap;
-    a.top_begin = static_cast<int>(top);
+    a.top_begin = static_cast<int>(at.top);
     a.top_count = static_cast<int>(low.size());
-    a.out = reinterpret_cast<int*>(h + h_out_at + j * out_stride);
+    a.out = reinterpret_cast<int*>(h + L.h_out.at + j * L.out_stride);
     a.out_records = kBatchOutRecords;
     std::memcpy(&h_args[j], &a, sizeof(a));
     h_counts[static_cast<size_t>(j) * kCountWords + a.max_depth] = a.top_count;
-    for (const Candidate& cd : low) h_flat[top++] = FrontierRec{cd.scan_index, cd.offset[0], cd.offset[1], cd.offset[2], 0};
-    hi_off += align256(static_cast<size_t>(s.n_hi) * 12);
-    lo_off += 3 * pl * 4;
-    pool_off += static_cast<size_t>(s.m->max_depth() + 1) * kBatchCap * sizeof(FrontierRec);
-    cell_off += align256(3 * cells * 4);
+    for (size_t i = 0; i < low.size(); ++i) h_flat[at.top + i] = to_rec(low[i]);
+    at.top += low.size();
+    at.scan += num_scans_of(s);
+    at.hi += hi_cloud_bytes(s);
+    at.lo += lo_cloud_bytes(s);
+    at.pool += pool_bytes(s);
+    at.cells += cell_bytes(s);
   }
+#ifdef DLIOM_DEBUG_CHECKS  // the searches filled each region exactly
+  assert(at.top == L.total_top && at.scan == L.total_scans && at.hi == L.hi.bytes && at.lo == L.lo.bytes &&
+         at.pool == L.pools.bytes && at.cells == L.cells.bytes);
+#endif
 
   // ---- one upload, the discrete scans, the chain, one synchronisation
-  DLIOM_HIP_TRY(hipMemcpyAsync(d, h, upload_bytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(discretize_batch_kernel, dim3(static_cast<unsigned>((widest + 255) / 256), static_cast<unsigned>(total_scans)),
-                     dim3(256), 0, ctx->stream, reinterpret_cast<const DiscreteScanArg*>(d + scan_at));
-  DLIOM_TRY(enqueue_frontier_chain(ctx, S, static_cast<int>(total_top), deepest, d));
+  DLIOM_HIP_TRY(hipMemcpyAsync(d, h, L.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(discretize_batch_kernel, dim3(static_cast<unsigned>((L.widest + 255) / 256), static_cast<unsigned>(L.total_scans)),
+                     dim3(256), 0, ctx->stream, reinterpret_cast<const DiscreteScanArg*>(d + L.scans.at));
+  DLIOM_TRY(enqueue_frontier_chain(ctx, S, static_cast<int>(L.total_top), L.deepest, d));
   DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   ++ctx->host_syncs;
   ++st->chunks;
   ++st->frontier_chains;
 
   // ---- the leaves at or above theta: their low-resolution sums, ahead of the recursion (one more synchronisation)
-  float4* h_rot = reinterpret_cast<float4*>(h + h_leaf_at);
-  float* h_trans = reinterpret_cast<float*>(h + h_leaf_at + (trans_at - rot_at));
-  unsigned* h_list = reinterpret_cast<unsigned*>(h + h_leaf_at + (list_at - rot_at));
+  float4* h_rot = reinterpret_cast<float4*>(h + L.h_leaf.at);
+  float* h_trans = reinterpret_cast<float*>(h + L.h_leaf.at + (L.trans.at - L.rot.at));
+  unsigned* h_list = reinterpret_cast<unsigned*>(h + L.h_leaf.at + (L.list.at - L.rot.at));
   std::vector<SequentialSumJob> jobs;
   std::vector<std::vector<uint64_t>> leaf_keys(S);
   int first = 0;
   for (int j = 0; j < S; ++j) {
     Search& s = *searches[ids[j]];
-    const int* out = reinterpret_cast<const int*>(h + h_out_at + j * out_stride);
+    const int* out = reinterpret_cast<const int*>(h + L.h_out.at + j * L.out_stride);
     const float theta = take_frontier(s, out, kBatchOutRecords, kBatchCap);
     const float min_score = queries[ids[j]].min_score;
     int at = 0;  // the depth-0 records come last
@@ -1135,11 +1198,7 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
     const FrontierRec* rec = reinterpret_cast<const FrontierRec*>(out + kMaxLevels + 2);
     int k = 0;
     for (int i = at; i < end && k < kBatchLeavesAhead; ++i) {
-      Candidate c;
-      c.scan_index = rec[i].scan;
-      c.offset[0] = rec[i].ox;
-      c.offset[1] = rec[i].oy;
-      c.offset[2] = rec[i].oz;
+      const Candidate c = to_candidate(rec[i]);
       const float score = to_probability(rec[i].sum / static_cast<float>(s.n_hi));
       if (!(score >= theta && score > min_score)) continue;
       const PoseF p = pose_from_candidate(s, c);
@@ -1147,7 +1206,7 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
       h_trans[3 * (first + k)] = p.t.x;
       h_trans[3 * (first + k) + 1] = p.t.y;
       h_trans[3 * (first + k) + 2] = p.t.z;
-      leaf_keys[j].push_back(Search::key(0, c.scan_index, c.offset));
+      leaf_keys[j].push_back(Search::key(0, c));
       ++k;
     }
     for (int i = 0; i < k; ++i) h_list[first + i] = static_cast<unsigned>(i * k + i);
@@ -1155,13 +1214,13 @@ int fast_csm_chunk(dliom_ctx* ctx, const dliom_fast_csm_query* queries, const in
     first += k;
   }
   if (first > 0) {
-    DLIOM_HIP_TRY(hipMemcpyAsync(d + rot_at, h + h_leaf_at, lsum_at - rot_at, hipMemcpyHostToDevice, ctx->stream));
-    float* d_lsum = reinterpret_cast<float*>(d + lsum_at);
+    DLIOM_HIP_TRY(hipMemcpyAsync(d + L.rot.at, h + L.h_leaf.at, L.h_leaf.bytes, hipMemcpyHostToDevice, ctx->stream));
+    float* d_lsum = reinterpret_cast<float*>(d + L.lsum.at);
     DLIOM_TRY(sequential_probability_sums_enqueue(ctx, jobs.data(), static_cast<int>(jobs.size()),
-                                                  reinterpret_cast<const float4*>(d + rot_at),
-                                                  reinterpret_cast<const float*>(d + trans_at),
-                                                  reinterpret_cast<const unsigned*>(d + list_at), d_lsum));
-    float* h_lsum = reinterpret_cast<float*>(h + h_lsum_at);
+                                                  reinterpret_cast<const float4*>(d + L.rot.at),
+                                                  reinterpret_cast<const float*>(d + L.trans.at),
+                                                  reinterpret_cast<const unsigned*>(d + L.list.at), d_lsum));
+    float* h_lsum = reinterpret_cast<float*>(h + L.h_lsum.at);
     DLIOM_HIP_TRY(hipMemcpyAsync(h_lsum, d_lsum, static_cast<size_t>(first) * 4, hipMemcpyDeviceToHost, ctx->stream));
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     ++ctx->host_syncs;
@@ -1201,19 +1260,14 @@ int fast_csm_batch(dliom_ctx* ctx, const dliom_fast_csm_query* queries, int coun
       continue;
     }
     s->n_hi = static_cast<int>(nd.num_high_resolution_points);
+    s->n_lo = nd.num_low_resolution_points;
     statuses[i] = lowest_candidates(*s, &lowest[i]);
     if (statuses[i] != DLIOM_OK) {
       ++st->without_search;
       continue;
     }
     if (!frontier_suits(*s, lowest[i].size(), kBatchCap)) {
-      int status;
-      if (q.kind == DLIOM_FAST_CSM_MATCH)
-        status = dliom_fast_csm_match(ctx, q.matcher, q.pose, q.submap_pose, &nd, q.min_score, r);
-      else if (q.kind == DLIOM_FAST_CSM_MATCH_FULL_SUBMAP)
-        status = dliom_fast_csm_match_full_submap(ctx, q.matcher, q.pose, q.submap_pose, &nd, q.min_score, r);
-      else
-        status = dliom_fast_csm_match_with_3dof_initial(ctx, q.matcher, q.pose, &nd, q.min_score, r);
+      const int status = match_one(ctx, q.matcher, q.kind, q.pose, q.submap_pose, &nd, q.min_score, r);
       if (status != DLIOM_OK && status != DLIOM_ERR_CAPACITY) return status;
       statuses[i] = status;
       lowest[i].clear();
@@ -1229,8 +1283,8 @@ int fast_csm_batch(dliom_ctx* ctx, const dliom_fast_csm_query* queries, int coun
     int scans = 0;
     while (end < batched.size() && end - at < static_cast<size_t>(kChunkSearches)) {
       const Search& s = *searches[batched[end]];
-      const size_t k = lowest[batched[end]].size(), c = align256(3 * s.scan_poses.size() * static_cast<size_t>(s.n_hi) * 4);
-      const int ns = static_cast<int>(s.scan_poses.size());
+      const size_t k = lowest[batched[end]].size(), c = cell_bytes(s);
+      const int ns = static_cast<int>(num_scans_of(s));
       if (end > at && (top + k > kChunkTop || cells + c > kChunkCellBytes || scans + ns > kChunkScans)) break;
       top += k;
       cells += c;
@@ -1358,45 +1412,19 @@ int dliom_fast_csm_level(const dliom_fast_csm* m, int depth, int32_t lo[3], int3
 
 int dliom_fast_csm_match(dliom_ctx* ctx, const dliom_fast_csm* m, const double global_node_pose[7], const double global_submap_pose[7],
                          const dliom_fast_csm_node_data* data, float min_score, dliom_fast_csm_result* result) {
-  if (ctx == nullptr || m == nullptr || global_node_pose == nullptr || global_submap_pose == nullptr || result == nullptr)
-    return DLIOM_ERR_INVALID_ARGUMENT;
-  if (ctx->device != m->ctx->device) return DLIOM_ERR_INVALID_ARGUMENT;  // the pyramid lives on the creating device
-  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  StagedClouds c;
-  DLIOM_TRY(stage(ctx, data, &c));
-  Search s;
-  setup_search(&s, ctx, m, DLIOM_FAST_CSM_MATCH, global_node_pose, global_submap_pose, *data, c.hi->max_norm);
-  s.lo_cloud = c.lo;
-  return run_search(s, *c.hi, min_score, result);
+  return match_one(ctx, m, DLIOM_FAST_CSM_MATCH, global_node_pose, global_submap_pose, data, min_score, result);
 }
 
 int dliom_fast_csm_match_full_submap(dliom_ctx* ctx, const dliom_fast_csm* m, const double global_node_rotation[4],
                                      const double global_submap_rotation[4], const dliom_fast_csm_node_data* data,
                                      float min_score, dliom_fast_csm_result* result) {
-  if (ctx == nullptr || m == nullptr || global_node_rotation == nullptr || global_submap_rotation == nullptr || result == nullptr)
-    return DLIOM_ERR_INVALID_ARGUMENT;
-  if (ctx->device != m->ctx->device) return DLIOM_ERR_INVALID_ARGUMENT;  // the pyramid lives on the creating device
-  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  StagedClouds c;
-  DLIOM_TRY(stage(ctx, data, &c));
-  Search s;
-  setup_search(&s, ctx, m, DLIOM_FAST_CSM_MATCH_FULL_SUBMAP, global_node_rotation, global_submap_rotation, *data, c.hi->max_norm);
-  s.lo_cloud = c.lo;
-  return run_search(s, *c.hi, min_score, result);
+  return match_one(ctx, m, DLIOM_FAST_CSM_MATCH_FULL_SUBMAP, global_node_rotation, global_submap_rotation, data, min_score, result);
 }
 
 int dliom_fast_csm_match_with_3dof_initial(dliom_ctx* ctx, const dliom_fast_csm* m, const double pose_in_submap_guess[7],
                                            const dliom_fast_csm_node_data* data, float min_score,
                                            dliom_fast_csm_result* result) {
-  if (ctx == nullptr || m == nullptr || pose_in_submap_guess == nullptr || result == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
-  if (ctx->device != m->ctx->device) return DLIOM_ERR_INVALID_ARGUMENT;  // the pyramid lives on the creating device
-  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
-  StagedClouds c;
-  DLIOM_TRY(stage(ctx, data, &c));
-  Search s;
-  setup_search(&s, ctx, m, DLIOM_FAST_CSM_MATCH_WITH_3DOF_INITIAL, pose_in_submap_guess, nullptr, *data, c.hi->max_norm);
-  s.lo_cloud = c.lo;
-  return run_search(s, *c.hi, min_score, result);
+  return match_one(ctx, m, DLIOM_FAST_CSM_MATCH_WITH_3DOF_INITIAL, pose_in_submap_guess, nullptr, data, min_score, result);
 }
 
 int dliom_fast_csm_match_batch(dliom_ctx* ctx, const dliom_fast_csm_query* queries, int count, dliom_fast_csm_result* results,

@@ -1307,7 +1307,7 @@ int dliom_inserter_insert_cloud_multi(const dliom_inserter* ins, int num_targets
   // ordered behind them by the stream.  Pass 1 ends its copy of the verdict with a completion word; the call returns
   // when that arrives (the update passes may still be running -- 50 us the caller's next step no longer waits for).
   a.done_word = ctx->done_word;
-  a.done_seq = ctx->done_word != nullptr ? (++ctx->done_seq == 0u ? ++ctx->done_seq : ctx->done_seq) : 0u;
+  a.done_seq = ctx->done_word != nullptr ? next_done_seq(ctx) : 0u;
   account_insertion(&a, grids, num_targets, n, F);
   const int span = ctx->begin_span(DLIOM_KERNEL_INSERT);
   hipLaunchKernelGGL(multi_insert_kernel<0>, grid_dim, block, 0, ctx->stream, a);

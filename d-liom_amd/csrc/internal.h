@@ -115,7 +115,7 @@ struct dliom_ctx {
   bool zero_words_ready = false;  // proven unnecessary on the host (grid.hip: insertion without the extent scan)
   bool box_error_zeroed = false;
   bool force_dense_score = false;  // rerun after the LDS-box kernel flagged an inconsistency
-  int tuning[DLIOM_TUNE_COUNT] = {3, 4096, 0, 0};  // dliom_ctx_set_tuning (defaults: dliom.h)
+  int tuning[DLIOM_TUNE_COUNT] = {3, 4096, 0};  // dliom_ctx_set_tuning (defaults: dliom.h)
   bool last_score_used_box = false;
   int last_score_mapping = -1;     // 3 box, 2 dense mirror, 1 / 0 leaf table kernels
   int last_box_refusal = 0;        // DLIOM_BOX_* of the last score volume (dliom_rtcsm_stats.box_kernel_status)
@@ -347,6 +347,8 @@ int gather_to_pinned(dliom_ctx* ctx, const GatherJob* jobs, int num_jobs, void* 
 // is known to take longer (the histogram of a scan with a floor: 0.4 ms) passes what its last call took (round 4 burnt
 // the 150 us and then synchronised on every such call: `poll_fallbacks: 621` in profiles/r4_hist_bench.json).
 int wait_done(dliom_ctx* ctx, hipStream_t stream, const unsigned* done_word, unsigned done_seq, int max_poll_us = 150);
+// the next value for ctx->done_word on the main stream: never 0, which is what a fresh word holds
+unsigned next_done_seq(dliom_ctx* ctx);
 // gather_to_pinned on ctx->stream + wait_done: the read-back of a few words without a memcpy and without a full synchronise
 int gather_and_wait(dliom_ctx* ctx, const GatherJob* jobs, int num_jobs, void* pinned_dst);
 // 64 device words that are zero and that nobody writes (zeroed on ctx->stream at first use)

@@ -1252,12 +1252,7 @@ enum {
                                          dense kernel" path once; 2 / 3 force the de-skew check's overflow and fix
                                          paths, 4 / 5 the batch assembler's (every point recorded / the device's
                                          rotation also perturbed).  The shipped library contains no fault injection. */
-  DLIOM_TUNE_CSM_GRID_SYNC = 3,       /* CeresScanMatcher3D on large clouds: 1 = the whole loop in one launch with grid
-                                         barriers, 0 = one launch per evaluation (default: measured 0.27 ms against
-                                         0.35 ms per 131 072-point match -- the barrier, the final reduction and the
-                                         LM step repeated by 256 workgroups cost more than the round trips they save;
-                                         both give the same bits) */
-  DLIOM_TUNE_COUNT = 4
+  DLIOM_TUNE_COUNT = 3
 };
 int dliom_ctx_set_tuning(dliom_ctx* ctx, int knob, int value);
 int dliom_ctx_get_tuning(const dliom_ctx* ctx, int knob, int* value);

@@ -384,33 +384,45 @@ def test_csm3d_one_launch_equals_per_evaluation_loop(dl, ctx, orc, monkeypatch, 
     dg_lo.close()
 
 
-@pytest.mark.parametrize("n_hi,n_lo,yaw_only", [(3000, 2500, False), (40000, 40000, False), (65536, 65536, True), (1100, 900, False)])
-def test_csm3d_grid_barrier_loop_equals_per_evaluation_loop(dl, ctx, orc, n_hi, n_lo, yaw_only):
-    """Large clouds: the trust-region loop in ONE launch with grid barriers (csm_lm_grid_kernel) must give the bits of
-    the loop that launches csm_eval_kernel + csm_final_reduce_kernel per evaluation -- same grid, same strided
-    accumulation, same two reductions -- and the same summary."""
-    from dliom import synth
-    og_hi, pts, init, truth = _synthetic_case(orc, 64, 1024, resolution=0.1, max_range=40.0)
+@pytest.fixture(scope="module")
+def multi_workgroup_scene(dl, ctx, orc):
+    """A 64 x 1024 scan against the 0.1 m / 0.45 m submaps, built once for the shapes of the test below."""
+    og_hi, pts, init, _ = _synthetic_case(orc, 64, 1024, resolution=0.1, max_range=40.0)
     og_lo = build_oracle_submap(orc, 0.45, num_scans=6, beams=16, azimuths=256)
     dg_hi, dg_lo = to_device_grid(dl, ctx, og_hi), to_device_grid(dl, ctx, og_lo)
+    yield og_hi, og_lo, dg_hi, dg_lo, pts, init
+    dg_hi.close()
+    dg_lo.close()
+
+
+@pytest.mark.parametrize("n_hi,n_lo,yaw_only", [(300, 300, False), (1100, 900, True), (1100, 900, False), (20000, 13000, False)])
+def test_csm3d_per_evaluation_loop_multi_workgroup(dl, ctx, orc, multi_workgroup_scene, n_hi, n_lo, yaw_only):
+    """The loop that launches csm_eval_kernel on several workgroups + csm_final_reduce_kernel per evaluation (what clouds
+    above DLIOM_TUNE_CSM_ONE_LAUNCH_MAX take): 600 points = 2 workgroups, the smallest case with the final reduction and
+    its last-wave completion word; 2 000 = 4, both parameterisations; 33 000 = 65, where a lane of the final reduction
+    adds a second partial.  The reductions' order is fixed, so two runs give the same bits; against the oracle the bounds
+    are test_csm3d_match_close_to_oracle's."""
+    og_hi, og_lo, dg_hi, dg_lo, pts, init = multi_workgroup_scene
+    assert len(pts) >= n_hi
     rng = np.random.default_rng(n_hi + 3 * n_lo)
-    hi = pts[rng.choice(len(pts), min(n_hi, len(pts)), replace=False)]
-    lo = pts[rng.choice(len(pts), min(n_lo, len(pts)), replace=False)]
-    m = dl.CeresScanMatcher3D(ctx, dict(DEFAULT_CSM, only_optimize_yaw=yaw_only))
-    ctx.set_tuning(dl.TUNE_CSM_ONE_LAUNCH_MAX, 0)  # both runs take the large-cloud paths
+    hi = pts[rng.choice(len(pts), n_hi, replace=False)]
+    lo = pts[rng.choice(len(pts), n_lo, replace=False)]
+    opts = dict(DEFAULT_CSM, only_optimize_yaw=yaw_only)
+    m = dl.CeresScanMatcher3D(ctx, opts)
+    ctx.set_tuning(dl.TUNE_CSM_ONE_LAUNCH_MAX, 0)
     try:
-        ctx.set_tuning(dl.TUNE_CSM_GRID_SYNC, 1)
         pose_a, sum_a = m.Match(init[:3], init, [(hi, dg_hi), (lo, dg_lo)])
-        ctx.set_tuning(dl.TUNE_CSM_GRID_SYNC, 0)
         pose_b, sum_b = m.Match(init[:3], init, [(hi, dg_hi), (lo, dg_lo)])
     finally:
-        ctx.set_tuning(dl.TUNE_CSM_GRID_SYNC, 0)
         ctx.set_tuning(dl.TUNE_CSM_ONE_LAUNCH_MAX, 4096)
     assert np.array_equal(pose_a, pose_b), (pose_a, pose_b)
     assert sum_a == sum_b, (sum_a, sum_b)
     assert sum_a["num_iterations"] >= 2
-    dg_hi.close()
-    dg_lo.close()
+    ref = orc.csm3d_match(opts, init[:3], init, [(hi, og_hi), (lo, og_lo)])
+    dt, da = pose_distance(pose_a, ref["pose"])
+    assert dt <= 1e-6 and da <= 1e-6, (dt, da, sum_a, ref)
+    assert abs(sum_a["final_cost"] - ref["final_cost"]) <= 1e-9 * max(1.0, ref["final_cost"])
+    assert sum_a["num_iterations"] == ref["num_iterations"]
 
 
 def test_csm3d_error_codes(dl, ctx, orc):
