@@ -1255,6 +1255,151 @@ class LocalTrajectoryBuilder3D {
 
 }  // namespace mapping
 
+// ---- pose graph optimisation (mapping/internal/optimization/optimization_problem_3d.h) --------------------------------
+namespace mapping {
+struct SubmapId {  // mapping/id.h
+  int trajectory_id;
+  int submap_index;
+  bool operator<(const SubmapId& o) const { return trajectory_id != o.trajectory_id ? trajectory_id < o.trajectory_id : submap_index < o.submap_index; }
+  bool operator==(const SubmapId& o) const { return trajectory_id == o.trajectory_id && submap_index == o.submap_index; }
+};
+struct NodeId {
+  int trajectory_id;
+  int node_index;
+  bool operator<(const NodeId& o) const { return trajectory_id != o.trajectory_id ? trajectory_id < o.trajectory_id : node_index < o.node_index; }
+  bool operator==(const NodeId& o) const { return trajectory_id == o.trajectory_id && node_index == o.node_index; }
+};
+namespace optimization {
+struct NodeSpec3D {  // optimization_problem_3d.h:44-48
+  int64_t time;
+  transform::Rigid3d local_pose;
+  transform::Rigid3d global_pose;
+};
+struct SubmapSpec3D {  // :50-52
+  transform::Rigid3d global_pose;
+};
+struct OptimizationProblemOptions {  // proto/optimization_problem_options.proto: the fields the fork's Solve reads
+  bool fix_z_in_3d = false;
+  bool use_nonmonotonic_steps = false;
+  int max_num_iterations = 50;
+  int num_threads = 1;
+};
+struct LandmarkNode {};  // pose_graph_interface.h: landmarks are not covered, Solve refuses a non-empty map
+
+// OptimizationProblem3D (optimization_problem_3d.h:54-132, .cc:196-589) over dliom_pose_graph_solve.  MapById is a
+// std::map ordered like it (trajectory, index); Append continues a trajectory's indices.  AddOdometryData's use,
+// AddFixedFramePoseData and landmarks are not part of it (the fork's Solve has those terms commented out or unused).
+class OptimizationProblem3D {
+ public:
+  struct Constraint {  // PoseGraphInterface::Constraint
+    struct Pose {
+      transform::Rigid3d zbar_ij;
+      double translation_weight;
+      double rotation_weight;
+    };
+    SubmapId submap_id;
+    NodeId node_id;
+    Pose pose;
+    enum Tag { INTRA_SUBMAP, INTER_SUBMAP } tag = INTRA_SUBMAP;
+  };
+
+  OptimizationProblem3D(Context* context, const OptimizationProblemOptions& options) : context_(context), options_(options) {}
+  OptimizationProblem3D(const OptimizationProblem3D&) = delete;
+  OptimizationProblem3D& operator=(const OptimizationProblem3D&) = delete;
+
+  void AddImuData(int trajectory_id, const sensor::ImuData& imu_data) { imu_data_[trajectory_id].push_back(imu_data); }  // stored, unused, as in the fork
+  void AddTrajectoryNode(int trajectory_id, const NodeSpec3D& node_data) {
+    node_data_.emplace(NodeId{trajectory_id, NextIndex(node_data_, NodeId{trajectory_id, 0}, &NodeId::node_index)}, node_data);
+  }
+  void InsertTrajectoryNode(const NodeId& node_id, const NodeSpec3D& node_data) {
+    if (!node_data_.emplace(node_id, node_data).second) Check(DLIOM_ERR_INVALID_ARGUMENT, "InsertTrajectoryNode: the id exists");
+  }
+  void TrimTrajectoryNode(const NodeId& node_id) {
+    if (node_data_.erase(node_id) != 1) Check(DLIOM_ERR_INVALID_ARGUMENT, "TrimTrajectoryNode: no such id");
+  }
+  void AddSubmap(int trajectory_id, const transform::Rigid3d& global_submap_pose) {
+    submap_data_.emplace(SubmapId{trajectory_id, NextIndex(submap_data_, SubmapId{trajectory_id, 0}, &SubmapId::submap_index)},
+                         SubmapSpec3D{global_submap_pose});
+  }
+  void InsertSubmap(const SubmapId& submap_id, const transform::Rigid3d& global_submap_pose) {
+    if (!submap_data_.emplace(submap_id, SubmapSpec3D{global_submap_pose}).second) Check(DLIOM_ERR_INVALID_ARGUMENT, "InsertSubmap: the id exists");
+  }
+  void TrimSubmap(const SubmapId& submap_id) {
+    if (submap_data_.erase(submap_id) != 1) Check(DLIOM_ERR_INVALID_ARGUMENT, "TrimSubmap: no such id");
+  }
+  void SetMaxNumIterations(int32_t max_num_iterations) { options_.max_num_iterations = max_num_iterations; }
+
+  // optimization_problem_3d.cc:259-589: ids are compacted to indices in MapById order, the first submap is the
+  // gravity-aligned one, the poses of a frozen trajectory are constant; the solved poses go back into the maps.
+  void Solve(const std::vector<Constraint>& constraints, const std::set<int>& frozen_trajectories,
+             const std::map<std::string, LandmarkNode>& landmark_nodes) {
+    if (node_data_.empty()) return;  // nothing to optimize
+    if (!landmark_nodes.empty()) Check(DLIOM_ERR_INVALID_ARGUMENT, "OptimizationProblem3D::Solve: landmarks are not supported");
+    if (submap_data_.empty()) Check(DLIOM_ERR_INVALID_ARGUMENT, "OptimizationProblem3D::Solve: CHECK(!submap_data_.empty())");
+    std::map<SubmapId, int32_t> submap_index;
+    std::map<NodeId, int32_t> node_index;
+    std::vector<double> submap_poses, node_poses;
+    std::vector<unsigned char> submap_constant, node_constant;
+    for (const auto& id_data : submap_data_) {
+      submap_index.emplace(id_data.first, static_cast<int32_t>(submap_index.size()));
+      const std::array<double, 7> pose = id_data.second.global_pose.ToArray();
+      submap_poses.insert(submap_poses.end(), pose.begin(), pose.end());
+      submap_constant.push_back(frozen_trajectories.count(id_data.first.trajectory_id) != 0);
+    }
+    for (const auto& id_data : node_data_) {
+      node_index.emplace(id_data.first, static_cast<int32_t>(node_index.size()));
+      const std::array<double, 7> pose = id_data.second.global_pose.ToArray();
+      node_poses.insert(node_poses.end(), pose.begin(), pose.end());
+      node_constant.push_back(frozen_trajectories.count(id_data.first.trajectory_id) != 0);
+    }
+    std::vector<dliom_pose_graph_constraint> compact(constraints.size());
+    for (size_t i = 0; i < constraints.size(); ++i) {
+      const auto a = submap_index.find(constraints[i].submap_id);
+      const auto n = node_index.find(constraints[i].node_id);
+      if (a == submap_index.end() || n == node_index.end()) Check(DLIOM_ERR_INVALID_ARGUMENT, "OptimizationProblem3D::Solve: MapById::at");
+      compact[i].submap = a->second;
+      compact[i].node = n->second;
+      const std::array<double, 7> zbar = constraints[i].pose.zbar_ij.ToArray();
+      for (int k = 0; k < 7; ++k) compact[i].zbar[k] = zbar[k];
+      compact[i].translation_weight = constraints[i].pose.translation_weight;
+      compact[i].rotation_weight = constraints[i].pose.rotation_weight;
+    }
+    const dliom_pose_graph_options options = {options_.fix_z_in_3d ? 1 : 0, options_.use_nonmonotonic_steps ? 1 : 0,
+                                              options_.max_num_iterations, options_.num_threads};
+    Check(dliom_pose_graph_solve(context_->get(), &options, static_cast<int>(submap_index.size()), submap_poses.data(),
+                                 submap_constant.data(), 0, static_cast<int>(node_index.size()), node_poses.data(),
+                                 node_constant.data(), static_cast<int64_t>(compact.size()), compact.data(), &summary_),
+          "dliom_pose_graph_solve");
+    size_t at = 0;  // :578-588: store the result
+    for (auto& id_data : submap_data_) id_data.second.global_pose = transform::Rigid3d::FromArray(&submap_poses[7 * at++]);
+    at = 0;
+    for (auto& id_data : node_data_) id_data.second.global_pose = transform::Rigid3d::FromArray(&node_poses[7 * at++]);
+  }
+
+  const std::map<NodeId, NodeSpec3D>& node_data() const { return node_data_; }
+  const std::map<SubmapId, SubmapSpec3D>& submap_data() const { return submap_data_; }
+  const std::map<int, std::vector<sensor::ImuData>>& imu_data() const { return imu_data_; }
+  const dliom_pose_graph_summary& summary() const { return summary_; }  // of the last Solve (ceres::Solver::Summary there)
+
+ private:
+  template <typename Map, typename Id>
+  static int NextIndex(const Map& map, const Id& first_of_trajectory, int Id::*index) {  // MapById::Append
+    auto it = map.lower_bound(Id{first_of_trajectory.trajectory_id + 1, 0});
+    if (it == map.begin()) return 0;
+    --it;
+    return it->first.trajectory_id == first_of_trajectory.trajectory_id ? it->first.*index + 1 : 0;
+  }
+
+  Context* context_;
+  OptimizationProblemOptions options_;
+  std::map<NodeId, NodeSpec3D> node_data_;
+  std::map<SubmapId, SubmapSpec3D> submap_data_;
+  std::map<int, std::vector<sensor::ImuData>> imu_data_;
+  dliom_pose_graph_summary summary_ = {};
+};
+}  // namespace optimization
+}  // namespace mapping
+
 namespace mapping {
 struct Timespan {  // mapping/detect_floors.h:27-30, common::Time as ticks
   int64_t start = 0, end = 0;

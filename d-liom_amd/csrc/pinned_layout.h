@@ -8,6 +8,9 @@
 // Regions that overlap only across time:
 //  * the small read-backs at offset 0 (kPinReadback, kPinCsmSums), kPinLmResult and kPinHistogram are each waited for
 //    and copied out by the call that issued them, before that call stages anything else;
+//  * kPinPoseGraphSums lies inside the bulk regions below (kPinDownload, kPinRtcsmCandidates, kPinFastCsmScores,
+//    kPinFrontierUpload): a pose graph call (pose_graph.hip) is an entry point of its own that runs no match, search or
+//    download, writes the region once an iteration and has copied it out before it launches anything else or returns;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -53,6 +56,10 @@ constexpr PinRegion kPinFrontierUpload{0, 208 * 1024};                // device_
 constexpr PinRegion kPinPoses{208 * 1024, 48 * 1024};                 // the discrete scans' poses (pageable above this)
 constexpr PinRegion kPinFrontierOut{256 * 1024, kPinnedBytes - 256 * 1024 - 8192};  // device_frontier's output
 
+// a pose graph solve (pose_graph.hip): the sums of one trust-region iteration, read back once an iteration; while the
+// call runs nothing else stages in the block
+constexpr PinRegion kPinPoseGraphSums{4096, 256};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -92,6 +99,8 @@ static_assert(pins_disjoint({kPinRtcsmCandidates, kPinBoxTables, kPinSequentialS
 static_assert(pins_disjoint({kPinFrontierUpload, kPinPoses, kPinFrontierOut, kPinSequentialSums}),
               "a single fast-CSM search's regions");
 static_assert(pins_disjoint({kPinCsmSums, kPinLmResult}), "Ceres' regions");
+static_assert(pins_inside({kPinPoseGraphSums}, kPinnedBytes) && pins_disjoint({kPinPoseGraphSums, kPinReadback}),
+              "a pose graph solve's region (apart from the small read-backs of the helpers it may call)");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

@@ -2452,3 +2452,83 @@ def rotational_scan_match(node_histograms, node_angles, scan_histogram, initial_
                                                       _p(_f32(scan_histogram), _f32p), C.c_float(initial_angle),
                                                       _p(a, _f32p), len(a), _p(out, _f32p)), "dliom_rotational_scan_match")
     return out
+
+
+# ---- pose graph optimisation (include/dliom.h "pose graph optimisation") ------------------------------------------------
+ERR_TOO_LARGE = -14
+POSE_GRAPH_MAX_REDUCED_DIMENSION = 8192
+
+
+class PoseGraphOptions(C.Structure):
+    _fields_ = [("fix_z_in_3d", C.c_int), ("use_nonmonotonic_steps", C.c_int), ("max_num_iterations", C.c_int),
+                ("num_threads", C.c_int)]
+
+
+class PoseGraphConstraint(C.Structure):
+    _fields_ = [("submap", C.c_int32), ("node", C.c_int32), ("zbar", C.c_double * 7), ("translation_weight", C.c_double),
+                ("rotation_weight", C.c_double)]
+
+
+class PoseGraphSummary(C.Structure):
+    _fields_ = CsmSummary._fields_ + [("reduced_dimension", C.c_int), ("linear_solver_failures", C.c_int),
+                                      ("linearise_ms", C.c_double), ("eliminate_ms", C.c_double), ("factor_ms", C.c_double),
+                                      ("back_substitute_ms", C.c_double), ("host_ms", C.c_double),
+                                      ("num_recorded_steps", C.c_int), ("steps", C.c_uint8 * 256)]
+
+
+POSE_GRAPH_CONSTRAINT_DTYPE = np.dtype([("submap", "<i4"), ("node", "<i4"), ("zbar", "<f8", 7), ("translation_weight", "<f8"),
+                                        ("rotation_weight", "<f8")])
+assert POSE_GRAPH_CONSTRAINT_DTYPE.itemsize == C.sizeof(PoseGraphConstraint)
+_pgc = C.POINTER(PoseGraphConstraint)
+_PG_GRAPH = [C.c_int, _f64p, _u8p, C.c_int, C.c_int, _f64p, _u8p, C.c_int64, _pgc]
+SYMBOLS += [
+    ("dliom_pose_graph_solve", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [C.POINTER(PoseGraphSummary)]),
+    ("dliom_pose_graph_evaluate", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_f64p, _f64p, _f64p]),
+    ("dliom_pose_graph_step", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [C.c_double, _f64p, _f64p,
+                                                                                       C.POINTER(C.c_int)]),
+]
+
+
+class PoseGraph:
+    """OptimizationProblem3D::Solve on compacted indices.  submap_poses / node_poses: (n, 7) [t, q wxyz]; constraints:
+    a POSE_GRAPH_CONSTRAINT_DTYPE array; *_constant: uint8 flags or None; gravity_aligned_submap: index or -1."""
+
+    def __init__(self, ctx, submap_poses, node_poses, constraints, submap_constant=None, node_constant=None,
+                 gravity_aligned_submap=0, fix_z_in_3d=False, use_nonmonotonic_steps=False, max_num_iterations=10):
+        self.ctx, self._L = ctx, ctx._L
+        self.submaps = _f64(submap_poses).reshape(-1, 7).copy()
+        self.nodes = _f64(node_poses).reshape(-1, 7).copy()
+        self.constraints = np.ascontiguousarray(constraints, dtype=POSE_GRAPH_CONSTRAINT_DTYPE)
+        self.submap_constant = None if submap_constant is None else np.ascontiguousarray(submap_constant, dtype=np.uint8)
+        self.node_constant = None if node_constant is None else np.ascontiguousarray(node_constant, dtype=np.uint8)
+        self.gravity = int(gravity_aligned_submap)
+        self.options = PoseGraphOptions(int(fix_z_in_3d), int(use_nonmonotonic_steps), int(max_num_iterations), 1)
+
+    def _graph(self):
+        u8 = lambda a: None if a is None else _p(a, _u8p)  # noqa: E731
+        return (len(self.submaps), _p(self.submaps, _f64p), u8(self.submap_constant), self.gravity, len(self.nodes),
+                _p(self.nodes, _f64p), u8(self.node_constant), len(self.constraints), _p(self.constraints, _pgc))
+
+    def evaluate(self):
+        """-> (cost, residuals (C, 6), gradient (S + N, 6))"""
+        cost, r = C.c_double(), np.zeros((len(self.constraints), 6))
+        g = np.zeros((len(self.submaps) + len(self.nodes), 6))
+        _check(self._L.dliom_pose_graph_evaluate(self.ctx.h, C.byref(self.options), *self._graph(), C.byref(cost), _p(r, _f64p),
+                                                 _p(g, _f64p)), "dliom_pose_graph_evaluate")
+        return cost.value, r, g
+
+    def step(self, radius=1e4):
+        """-> (delta (S + N, 6), model_cost_change, reduced_dimension)"""
+        d, m, n = np.zeros((len(self.submaps) + len(self.nodes), 6)), C.c_double(), C.c_int()
+        _check(self._L.dliom_pose_graph_step(self.ctx.h, C.byref(self.options), *self._graph(), float(radius), _p(d, _f64p),
+                                             C.byref(m), C.byref(n)), "dliom_pose_graph_step")
+        return d, m.value, n.value
+
+    def solve(self):
+        """Overwrites self.submaps / self.nodes with the best iterate -> the summary as a dict (steps: list of 1 / 0 / 2)."""
+        s = PoseGraphSummary()
+        _check(self._L.dliom_pose_graph_solve(self.ctx.h, C.byref(self.options), *self._graph(), C.byref(s)),
+               "dliom_pose_graph_solve")
+        out = {k: getattr(s, k) for k, _ in PoseGraphSummary._fields_ if k not in ("steps", "num_recorded_steps")}
+        out["steps"] = list(s.steps[:s.num_recorded_steps])
+        return out

@@ -343,3 +343,88 @@ def moving_scan(t_end, num_beams=64, num_azimuths=1024, centers=None):
     rng_ = cast_many(pos, dirs_w, centers)
     back = np.isfinite(rng_)
     return np.concatenate([dirs_s[back] * rng_[back, None], rel_t[back, None]], axis=1).astype(np.float32)
+
+
+# ---- pose graphs (OptimizationProblem3D::Solve) ------------------------------------------------------------------------
+def _quat_mul(a, b):
+    return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                     a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3], a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1]])
+
+
+def _quat_rotate(q, v):
+    qv = np.array([0.0, v[0], v[1], v[2]])
+    return _quat_mul(_quat_mul(q, qv), q * np.array([1.0, -1.0, -1.0, -1.0]))[1:]
+
+
+def _quat_of(rotation_vector):
+    angle = np.linalg.norm(rotation_vector)
+    if angle < 1e-12:
+        return np.array([1.0, 0.0, 0.0, 0.0])
+    return np.concatenate([[np.cos(angle / 2)], np.sin(angle / 2) * np.asarray(rotation_vector) / angle])
+
+
+def pose7_compose(a, b):
+    """a * b of poses [t, q wxyz]."""
+    q = _quat_mul(a[3:], b[3:])
+    return np.concatenate([_quat_rotate(a[3:], b[:3]) + a[:3], q / np.linalg.norm(q)])
+
+
+def pose7_inverse(a):
+    q = a[3:] * np.array([1.0, -1.0, -1.0, -1.0])
+    return np.concatenate([-_quat_rotate(q, a[:3]), q])
+
+
+def pose_graph(num_submaps, num_nodes, loop_groups=0, seed=0, every_nodes_to_find_constraint=3, drift=(0.02, 0.002),
+               noise=(0.01, 0.002), frozen_submaps=0):
+    """A pose graph as PoseGraph3D hands it to OptimizationProblem3D::Solve: `num_nodes` nodes on a closed, climbing loop;
+    submap a starts at node a * num_nodes // (num_submaps - 1), and every node is constrained (INTRA_SUBMAP, weights
+    matcher_*_weight of pose_graph.lua) to the two consecutive submaps it was inserted into; `loop_groups` groups of
+    67 // every_nodes_to_find_constraint INTER_SUBMAP constraints (weights loop_closure_*_weight of basic_config_3d.lua)
+    tie nodes of the last quarter to a submap of the first.  The initial poses carry a random-walk drift
+    (metres, radians a node); the first `frozen_submaps` submaps and their nodes are constant (a frozen trajectory).
+    -> dict(submaps (S, 7), nodes (N, 7), constraints (structured: submap, node, zbar, translation_weight,
+    rotation_weight), submap_constant, node_constant, truth_nodes)."""
+    rng = np.random.RandomState(seed)
+    segments = max(num_submaps - 1, 1)
+    truth = np.zeros((num_nodes, 7))
+    for j in range(num_nodes):
+        a = 2 * np.pi * j / num_nodes
+        truth[j, :3] = [20 * np.cos(a), 20 * np.sin(a), 0.5 * np.sin(2 * a)]
+        truth[j, 3:] = _quat_mul(_quat_of([0, 0, a + np.pi / 2]), _quat_of([0.05 * np.sin(3 * a), 0.04 * np.cos(2 * a), 0]))
+    start = [min(a * num_nodes // segments, num_nodes - 1) for a in range(num_submaps)]
+    truth_submaps = truth[start].copy()
+    # the drifting estimate: a random walk of small relative errors along the trajectory
+    nodes = np.zeros_like(truth)
+    error = np.array([0, 0, 0, 1.0, 0, 0, 0])
+    for j in range(num_nodes):
+        step = np.concatenate([rng.normal(0, drift[0], 3), _quat_of(rng.normal(0, drift[1], 3))])
+        error = pose7_compose(error, step)
+        nodes[j] = pose7_compose(error, truth[j])
+    submaps = nodes[start].copy()
+    rows = []
+
+    def constrain(a, j, tw, rw):
+        z = pose7_compose(pose7_inverse(truth_submaps[a]), truth[j])
+        z = pose7_compose(z, np.concatenate([rng.normal(0, noise[0], 3), _quat_of(rng.normal(0, noise[1], 3))]))
+        rows.append((a, j, z, tw, rw))
+    for j in range(num_nodes):
+        a = min(j * segments // num_nodes, num_submaps - 1)
+        constrain(a, j, 5e2, 1.6e3)
+        if a + 1 < num_submaps and num_submaps > 1:
+            constrain(a + 1, j, 5e2, 1.6e3)
+    per_group = 67 // every_nodes_to_find_constraint
+    for k in range(loop_groups):
+        a = int(rng.randint(0, max(num_submaps // 4, 1)))
+        first = int(rng.randint(3 * num_nodes // 4, max(num_nodes - per_group * every_nodes_to_find_constraint, 3 * num_nodes // 4 + 1)))
+        for i in range(per_group):
+            j = first + i * every_nodes_to_find_constraint
+            if j < num_nodes:
+                constrain(a, j, 1e4, 1e2)
+    constraints = np.zeros(len(rows), dtype=[("submap", "<i4"), ("node", "<i4"), ("zbar", "<f8", 7), ("translation_weight", "<f8"),
+                                             ("rotation_weight", "<f8")])
+    for i, (a, j, z, tw, rw) in enumerate(rows):
+        constraints[i] = (a, j, z, tw, rw)
+    submap_constant = (np.arange(num_submaps) < frozen_submaps).astype(np.uint8)
+    node_constant = np.array([min(j * segments // num_nodes, num_submaps - 1) < frozen_submaps for j in range(num_nodes)], dtype=np.uint8)
+    return dict(submaps=submaps, nodes=nodes, constraints=constraints, submap_constant=submap_constant, node_constant=node_constant,
+                truth_nodes=truth)

@@ -1237,6 +1237,95 @@ int dliom_csm3d_evaluate(dliom_ctx* ctx, const dliom_csm_options* options,
                          const dliom_grid* const* grids, double* cost, double gradient[6],
                          double jtj[36]);
 
+/* ---- pose graph optimisation ------------------------------------------------------------------
+ * OptimizationProblem3D::Solve (mapping/internal/optimization/optimization_problem_3d.cc:259-589) as this fork runs
+ * it: the IMU, odometry and local-SLAM terms are commented out there (:350-489) and the inter-submap loss is
+ * TrivialLoss (:336-338), so the problem is one SpaCostFunction3D a constraint (cost_functions/spa_cost_function_3d.h:
+ * 46-56, cost_helpers_impl.h:57-101, transform/transform.h:59-81) between ONE submap pose and ONE node pose.  Landmarks
+ * (AddLandmarkCostFunctions), fixed-frame poses (:491-548) and the 2D problem are not covered.
+ *
+ * Poses are [tx ty tz qw qx qy qz].  Parameter blocks (:279-330, ceres_pose.cc): a translation block with no
+ * parameterisation, or SubsetParameterization(3, {2}) under fix_z_in_3d; a rotation block with
+ * QuaternionParameterization.  `gravity_aligned_submap` (the first submap in MapById order, or -1 for none) keeps its
+ * translation constant and moves its rotation by ConstantYawQuaternionPlus (mapping/internal/3d/
+ * rotation_parameterization.h:41-62).  submap_constant[i] / node_constant[i] != 0: both blocks constant (a frozen
+ * trajectory, :310-315,325-329).  A NULL constant array means none.
+ *
+ * The solver is ceres::Solve as common/ceres_solver_options.cc:35-42 configures it (Ceres 1.13 defaults otherwise):
+ * trust region, Levenberg-Marquardt, Jacobi scaling, tolerances 1e-6 / 1e-10 / 1e-8.  As in Ceres (its behaviour, not
+ * the tree's) constant blocks, blocks no constraint touches and constraints whose four blocks are all constant leave
+ * the reduced problem; the cost of the latter is added to the summary's costs as a fixed cost.
+ *
+ * The nodes are eliminated (their Hessian is block-diagonal) and the dense reduced system over the submaps is
+ * factorised on the device in FP64.  Its dimension (summary->reduced_dimension: the free tangent columns of the
+ * submaps) is capped at DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION = 8192 (about 1 365 free submaps, 512 MB): beyond it,
+ * or with index arrays beyond 2^31 - 1 entries, DLIOM_ERR_TOO_LARGE.  Scratch is allocated and released inside the
+ * call: dliom_ctx_memory_stats is unchanged by it.  DLIOM_ERR_INVALID_ARGUMENT: NULL pointers, negative counts, a
+ * constraint index or gravity_aligned_submap out of range.  DLIOM_ERR_SOLVER: where Ceres would report FAILURE (a
+ * non-finite input pose or constraint, five invalid steps in a row); the poses are then left as they were.  A
+ * non-finite candidate cost is a rejected step, not an error.  Refusals of the arguments (the three statuses above,
+ * a non-finite input) happen before anything is launched.
+ * Every sum is taken in a fixed order without floating-point atomics: two solves of one input give the same bits. */
+#define DLIOM_ERR_TOO_LARGE (-14)
+#define DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION 8192
+#define DLIOM_POSE_GRAPH_MAX_RECORDED_STEPS 256
+typedef struct dliom_pose_graph_options {
+  int fix_z_in_3d;            /* optimization_problem_options.proto fix_z_in_3d */
+  int use_nonmonotonic_steps; /* common.proto.CeresSolverOptions */
+  int max_num_iterations;     /* ... (SetMaxNumIterations, pose_graph_3d.cc:677-682) */
+  int num_threads;            /* accepted, unused */
+} dliom_pose_graph_options;
+/* OptimizationProblem3D::Constraint (pose_graph_interface.h): zbar = the node's pose in the submap frame. */
+typedef struct dliom_pose_graph_constraint {
+  int32_t submap;
+  int32_t node;
+  double zbar[7];
+  double translation_weight;
+  double rotation_weight;
+} dliom_pose_graph_constraint;
+typedef struct dliom_pose_graph_summary {
+  double initial_cost;
+  double final_cost;
+  int num_successful_steps;
+  int num_unsuccessful_steps;
+  int num_iterations;
+  int num_residual_evaluations;
+  int num_jacobian_evaluations;
+  int termination_type; /* 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE */
+  int reduced_dimension;
+  int linear_solver_failures; /* factorisations that met a non-positive pivot (each an invalid step) */
+  /* milliseconds a stage took, summed over the iterations; filled (and the stages separated by stream
+   * synchronisations) only while the context's profiling is on */
+  double linearise_ms, eliminate_ms, factor_ms, back_substitute_ms, host_ms;
+  /* iterations 1 .. num_recorded_steps: 1 successful, 0 unsuccessful, 2 invalid */
+  int num_recorded_steps;
+  unsigned char steps[DLIOM_POSE_GRAPH_MAX_RECORDED_STEPS];
+} dliom_pose_graph_summary;
+/* void OptimizationProblem3D::Solve(constraints, frozen_trajectories, landmark_nodes) (optimization_problem_3d.cc:
+ * 259-589) on compacted indices: submap_poses7 / node_poses7 are read and, on DLIOM_OK, overwritten with the best
+ * iterate (blocks outside the reduced problem keep their bits). */
+int dliom_pose_graph_solve(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
+                           const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                           double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
+                           const dliom_pose_graph_constraint* constraints, dliom_pose_graph_summary* summary);
+/* Diagnostics in the style of dliom_csm3d_evaluate.  One evaluation at the given poses: *cost = 1/2 sum r^2 of the
+ * reduced problem plus the fixed cost, residuals[6 * c ..] of every constraint (cost_helpers_impl.h:57-101), and the
+ * gradient J^T r in the tangent space: 6 slots a pose, submaps first, [translation | rotation]; a slot outside the
+ * reduced problem (constant, fix_z's z, the gravity-aligned submap's third) holds 0.  Any output may be NULL. */
+int dliom_pose_graph_evaluate(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                              const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                              int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                              int64_t num_constraints, const dliom_pose_graph_constraint* constraints, double* cost,
+                              double* residuals, double* gradient);
+/* The trust-region step of iteration 1 (levenberg_marquardt_strategy.cc with the iteration-0 Jacobi scaling) for the
+ * given radius: delta[6 * (num_submaps + num_nodes)] in the slots of `gradient` above, already multiplied by the column
+ * scaling (what Plus receives), and *model_cost_change.  DLIOM_ERR_SOLVER when the factorisation fails. */
+int dliom_pose_graph_step(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                          const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                          int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                          int64_t num_constraints, const dliom_pose_graph_constraint* constraints, double radius,
+                          double* delta, double* model_cost_change, int* reduced_dimension);
+
 /* Per-context choices a caller may make; none of them changes a result (every kernel variant is parity-tested).  The
  * library never reads the environment (tuning experiments live in `make experiments` builds only). */
 enum {
