@@ -556,6 +556,12 @@ __device__ __forceinline__ void bitonic_sort_keys(unsigned long long* skey, int 
 
 #include "rothist_big.h"
 
+// dynamic LDS of slice_kernel, what the host asks for: [sort keys kMaxSlice u64 | sx | sy | sz | eight arrays of kU16 u16 |
+// kMaxSlice bytes of flags] and 1 KB to spare
+constexpr int kU16 = kMaxSlice + 8;
+constexpr size_t kSliceU16At = static_cast<size_t>(kMaxSlice) * (8 + 12);
+constexpr size_t kSliceLdsBytes = kSliceU16At + 8 * static_cast<size_t>(kU16) * 2 + kMaxSlice + 64 + 1024;
+
 __global__ __launch_bounds__(kThreads) void slice_kernel(const float* __restrict__ rx, const float* __restrict__ ry,
                                                          const float* __restrict__ rz, const short* __restrict__ keys, int n,
                                                          const unsigned* __restrict__ bin_counts, int histogram_size,
@@ -568,10 +574,11 @@ __global__ __launch_bounds__(kThreads) void slice_kernel(const float* __restrict
   float* sz = sy + kMaxSlice;
   // std::sort's order of equal keys (wave_sort_arrangement) and later steps: eight arrays of kMaxSlice + 8 u16
   unsigned short* u16_base = reinterpret_cast<unsigned short*>(sz + kMaxSlice);
-  constexpr int kU16 = kMaxSlice + 8;
+  static_assert((3 * kMaxSlice) * sizeof(float) + kMaxSlice * sizeof(unsigned long long) == kSliceU16At, "where the u16 arrays begin");
   unsigned short* idx_of = u16_base + 7 * kU16;  // arrangement position -> position in the slice
   unsigned char* tied_flags = reinterpret_cast<unsigned char*>(idx_of);  // by position in the slice; dead once idx_of is written
   unsigned char* act_flags = reinterpret_cast<unsigned char*>(u16_base + 8 * kU16);  // [kMaxSlice]; later the chain's marks
+  static_assert(kSliceU16At + 8 * static_cast<size_t>(kU16) * 2 + kMaxSlice <= kSliceLdsBytes, "the carving ends inside what the host asks for");
   static_assert(sizeof(Queue) <= static_cast<size_t>(kU16) * 2, "the queue fits one of the arrays");
   const SortScratch sort_scratch{u16_base, u16_base + kU16, tied_flags, reinterpret_cast<Queue*>(u16_base + 2 * kU16)};
   // std::sort's input and arrangement (the plainly sorted keys stay in skey): arrays 3 .. 6
@@ -1177,13 +1184,16 @@ extern "C" int dliom_exp_rothist_acc_stamps(unsigned long long* out) {
 namespace dliom {
 namespace rothist {
 // dliom_diag_std_sort_order: the slice kernel's sort (plain sort; on ties std::sort's partitions + stable sort) on bare keys
+// dynamic LDS, what the host asks for: slice_kernel's layout without the points
+constexpr size_t kStdSortU16At = static_cast<size_t>(kMaxSlice) * 8;
+constexpr size_t kStdSortLdsBytes = kStdSortU16At + 8 * static_cast<size_t>(kU16) * 2 + kMaxSlice + 64;
 __global__ __launch_bounds__(kThreads) void std_sort_order_kernel(const float* __restrict__ keys, int n, int* __restrict__ order,
                                                                   int* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds_dyn[];
   unsigned long long* skey = lds_dyn;
   unsigned short* u16_base = reinterpret_cast<unsigned short*>(skey + kMaxSlice);
-  constexpr int kU16 = kMaxSlice + 8;
   unsigned short* idx_of = u16_base + 7 * kU16;
+  static_assert(kStdSortU16At + 8 * static_cast<size_t>(kU16) * 2 <= kStdSortLdsBytes, "the carving ends inside what the host asks for");
   unsigned char* tied_flags = reinterpret_cast<unsigned char*>(idx_of);
   const SortScratch sc{u16_base, u16_base + kU16, tied_flags, reinterpret_cast<Queue*>(u16_base + 2 * kU16)};
   int pow2 = 64;
@@ -1255,10 +1265,9 @@ size_t carve_big_arrays(char* base, size_t entries, dliom::rothist::BigArrays* A
   A->spy = reinterpret_cast<float*>(take(e * 4));
   A->val_in = reinterpret_cast<unsigned*>(take(e * 4));
   A->val_out = reinterpret_cast<unsigned*>(take(e * 4));
-  unsigned** u32s[] = {&A->seg_first, &A->seg_last, &A->g, &A->l, &A->tmp_l, &A->tmp_r, &A->cut, &A->tpre, &A->pos_of, &A->sorted_id,
-                       &A->jump_a, &A->jump_b};
+  unsigned** u32s[] = {&A->l, &A->tmp_l, &A->tmp_r, &A->pos_of, &A->sorted_id, &A->jump_a, &A->jump_b};
   for (unsigned** q : u32s) *q = reinterpret_cast<unsigned*>(take(e * 4));
-  unsigned char** u8s[] = {&A->act, &A->fl, &A->tied, &A->dead, &A->mark};
+  unsigned char** u8s[] = {&A->tied, &A->dead, &A->mark};
   for (unsigned char** q : u8s) *q = reinterpret_cast<unsigned char*>(take(e));
   A->valid = reinterpret_cast<unsigned*>(take(256));
   return at;
@@ -1310,7 +1319,7 @@ extern "C" int dliom_diag_std_sort_order(dliom_ctx* ctx, const float* keys, int 
   int* d_order = reinterpret_cast<int*>(d_keys + kMaxSlice);
   int* d_status = d_order + kMaxSlice;
   DLIOM_HIP_TRY(hipMemcpyAsync(d_keys, keys, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, ctx->stream));
-  const size_t lds = static_cast<size_t>(kMaxSlice) * 8 + 8 * static_cast<size_t>(kMaxSlice + 8) * 2 + kMaxSlice + 64;
+  const size_t lds = kStdSortLdsBytes;
   if ((ctx->func_attr_set & kFuncAttrStdSortDiag) == 0u) {
     DLIOM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(std_sort_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       static_cast<int>(lds)));
@@ -1412,7 +1421,7 @@ int enqueue_histogram(dliom_ctx* ctx, hipStream_t stream, dliom::DevBuf& scratch
   const unsigned blocks = static_cast<unsigned>((N + kThreads - 1) / kThreads);
   hipLaunchKernelGGL(prepare_kernel, dim3(blocks), dim3(kThreads), 0, stream, cloud->d_x, cloud->d_y, cloud->d_z, n, q,
                      rotation_wxyz != nullptr ? 1 : 0, rx, ry, rz, keys, bin_counts, flags);
-  const size_t lds = static_cast<size_t>(kMaxSlice) * (8 + 12) + 8 * static_cast<size_t>(kMaxSlice + 8) * 2 + kMaxSlice + 64 + 1024;
+  const size_t lds = kSliceLdsBytes;
   const size_t acc_lds = static_cast<size_t>(kAccCap + 64) * 4;
   if ((ctx->func_attr_set & kFuncAttrHistogram) == 0u) {
     DLIOM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -16,7 +16,14 @@
 // `last_point`): introsort's partition rounds are replayed on the input-order array as in the LDS path, but only on
 // segments that still hold two tied elements -- a segment without ties has a unique sorted order, and the final insertion
 // sort is stable, so all that is needed of the arrangement is where the tied elements are: every group of equal angles
-// is then ordered by arrangement position.
+// is then ordered by arrangement position.  big_sort_order has two variants, chosen by size (LdsReplaySizes::fits): the
+// whole replay in LDS on 32-bit items (rank << 16 | position) for slices up to 15 391 items, and arrays in HBM on 64-bit
+// items (key << 32 | position) above that, which drains batches of segments through wave_sort_arrangement in LDS.  The
+// steps of a round -- tie marking, the depth limit, median-to-first, the cooperative partition, the tied-per-side count
+// with the work list's update, the tie groups' placement -- are written once, as templates on the item type, the stop
+// type and the loads a wave keeps in flight; the two drivers keep what differs: how items are built, where the arrays
+// live, which segment is picked, the hand-over to wave_sort_arrangement.  tests/cpp/big_sort_worklist_model.cc models
+// the drivers' control flow.
 // `last_point` (:70-80) moves to the first live point farther than kMaxDistance from it.  On a floor slice sorted by
 // angle nearly every point is such a jump (13 688 of 14 460), so walking the chain costs one step per point.  Instead:
 // next(i) for EVERY i in parallel, then the nodes on the path 0 -> next(0) -> ... by pointer doubling: marks spread along
@@ -26,15 +33,34 @@
 #ifdef DLIOM_EXPERIMENTS
 __device__ unsigned long long dbg_big[64 * 16];
 #define DLIOM_BSTAMP(k) if (threadIdx.x == 0 && blockIdx.x < 4) dbg_big[(blockIdx.x + 4 * (kernel_id)) * 16 + (k)] = __builtin_readcyclecounter()
+#define DLIOM_SSTAMP(k) if (threadIdx.x == 0 && blockIdx.x < 4) dbg_big[(blockIdx.x + 8) * 16 + (k)] = __builtin_readcyclecounter()
 #else
 #define DLIOM_BSTAMP(k)
+#define DLIOM_SSTAMP(k)  // big_sort_order's phases (tools/hist_stamps.py)
 #endif
 
-// dynamic LDS of big_slice_kernel: the replay's arrays (61 KB) or the exact sums' scratch (50 KB) or the chain's arrays
-// (10 bytes per point) -- one after the other; one workgroup of 1024 threads per CU anyway
-constexpr size_t kBigReplayBytes = static_cast<size_t>(kMaxSlice) * 8 + 2 * static_cast<size_t>(kMaxSlice + 8) * 2 + sizeof(Queue) + kMaxSlice + 64;
+// dynamic LDS of big_slice_kernel and big_sort_order_kernel (kBigLdsBytes; one workgroup of 1024 threads per CU anyway),
+// used for one thing after the other: the LDS variant of the replay (all of it, LdsReplaySizes), or the HBM variant's
+// batch (below, 61 KB), then the exact sums' scratch (50 KB), then the chain's arrays (10 bytes per point).
 constexpr size_t kBigLdsBytes = 150 * 1024;
+// The HBM variant's batch, the layout of wave_sort_arrangement on the small slices' 64-bit items:
+// [items: kMaxSlice u64 | the two pointers' stops: kMaxSlice + 8 u16 each | Queue | tie flags: kMaxSlice + 64 bytes]
+constexpr size_t kBigReplayStopsAt = static_cast<size_t>(kMaxSlice) * 8;
+constexpr size_t kBigReplayQueueAt = kBigReplayStopsAt + 2 * static_cast<size_t>(kMaxSlice + 8) * 2;
+constexpr size_t kBigReplayTiedAt = kBigReplayQueueAt + sizeof(Queue);
+constexpr size_t kBigReplayBytes = kBigReplayTiedAt + kMaxSlice + 64;
+static_assert(kBigReplayQueueAt % 8 == 0, "the queue's uint2 entries are aligned");
 static_assert(kBigReplayBytes <= kBigLdsBytes, "the replay's arrays fit");
+struct BigReplayLds {
+  unsigned long long* items;
+  SortScratch scratch;
+};
+__device__ __forceinline__ BigReplayLds carve_big_replay(unsigned long long* lds) {
+  char* base = reinterpret_cast<char*>(lds);
+  unsigned short* stops = reinterpret_cast<unsigned short*>(base + kBigReplayStopsAt);
+  return BigReplayLds{lds, SortScratch{stops, stops + kMaxSlice + 8, reinterpret_cast<unsigned char*>(base + kBigReplayTiedAt),
+                                       reinterpret_cast<Queue*>(base + kBigReplayQueueAt)}};
+}
 constexpr int kWorkListCap = 256;    // segments of a big slice's replay that still hold ties, before they fit LDS together
 constexpr int kMaxBig = 63;         // big slices per cloud (slice ordinal 63 is the sort's padding key)
 constexpr int kBigKeyBits = 38;     // 32 angle bits + 6 slice bits
@@ -44,13 +70,17 @@ __device__ int dbg_coop_min = 4096;
 #endif
 struct BigArrays {
   // per point of the cloud (n_padded + 64 entries each; slice b works at offset begin_b + b, so that every slice has
-  // room for one sentinel behind its last entry)
+  // room for one sentinel behind its last entry): 79 bytes a point
   float *bx, *by;                  // the slice's points in input order
-  unsigned long long *key_in, *key_out;
-  unsigned *val_in, *val_out;
-  unsigned long long* arr;         // introsort's array: key << 32 | position in the slice
-  unsigned *seg_first, *seg_last, *g, *l, *tmp_l, *tmp_r, *cut, *tpre, *pos_of, *sorted_id, *jump_a, *jump_b;
-  unsigned char *act, *fl, *tied, *dead, *mark;
+  unsigned long long *key_in, *key_out;  // the radix sort's items (slice << 32 | ordered angle bits), in input order and sorted
+  unsigned *val_in, *val_out;            // ... and their positions in the slice
+  unsigned long long* arr;         // introsort's array (HBM variant): key << 32 | position in the slice
+  unsigned *tmp_l, *tmp_r;         // ... the two pointers' stops
+  unsigned* l;                     // ... of a batch in LDS: packed index -> position in the slice
+  unsigned* pos_of;                // ... where a tied element is in the finished arrangement
+  unsigned* sorted_id;             // position in the slice of the j-th element of std::sort's result
+  unsigned *jump_a, *jump_b;       // the chain's next pointers while it does not fit LDS
+  unsigned char *tied, *dead, *mark;  // by position in the slice: key occurs more than once; by sorted position: the chain's
   float *spx, *spy;                // the sorted points
   unsigned* valid;                 // [kMaxBig]: items of slice b handed to the sort
 };
@@ -131,753 +161,310 @@ __device__ __forceinline__ int block_exclusive_max(int v, int identity, int* wav
   return max(before, excl);
 }
 
-__device__ __forceinline__ unsigned key_of(unsigned long long item) { return static_cast<unsigned>(item >> 32); }
-
 // ---- std::sort's order of equal keys on a slice of any size --------------------------------------------------------
-// Thread t owns the positions [lo, hi) in every pass; they are visited four at a time with the loads of all four issued
-// before anything depends on them: a plain loop of load -> use -> store pays the memory latency once per position, and
-// with ~15 positions per thread and a dozen passes per partition round that was 1.3 ms for a floor slice of 14 500
-// returns (round 4's first version).
-template <class Stage1, class Stage2, class Use>
-__device__ __forceinline__ void for_owned4(int lo, int hi, Stage1 stage1, Stage2 stage2, Use use) {
-  for (int p0 = lo; p0 < hi; p0 += 4) {
-    const int q0 = p0, q1 = min(p0 + 1, hi - 1), q2 = min(p0 + 2, hi - 1), q3 = min(p0 + 3, hi - 1);
-    const auto a0 = stage1(q0);
-    const auto a1 = stage1(q1);
-    const auto a2 = stage1(q2);
-    const auto a3 = stage1(q3);
-    const auto b0 = stage2(q0, a0);
-    const auto b1 = stage2(q1, a1);
-    const auto b2 = stage2(q2, a2);
-    const auto b3 = stage2(q3, a3);
-    use(q0, a0, b0);
-    if (p0 + 1 < hi) use(q1, a1, b1);
-    if (p0 + 2 < hi) use(q2, a2, b2);
-    if (p0 + 3 < hi) use(q3, a3, b3);
-  }
-}
-struct U2 {
-  unsigned a, b;
+// introsort's partition rounds, replayed only on segments that still hold two tied elements.  The steps of a round are
+// written once, below, for both variants of big_sort_order: the items (32 bits in LDS, 64 in HBM), the two pointers' stops
+// (16-bit positions in LDS, 32-bit in HBM) and the number of 64-position steps whose loads a wave issues before anything
+// depends on them (kSteps: 1 in LDS, 4 in HBM -- a plain loop of load -> use -> store pays the memory latency once per
+// step) are template parameters.  An item's id (its position in the slice, what tied[] and pos_of[] are indexed by) is
+// read by an accessor the variant chooses: item_id() keeps 16 bits, which is all of a 32-bit item's position and all that
+// wave_sort_arrangement packs, but NOT all of a 64-bit item's, whose whole low word is the position (up to 2^22).
+struct IdLow16 {
+  __device__ __forceinline__ unsigned operator()(unsigned item) const { return item_id(item); }
 };
-struct U4 {
-  unsigned a, b, c, d;
+struct IdLowWord {
+  __device__ __forceinline__ unsigned operator()(unsigned long long item) const { return static_cast<unsigned>(item); }
 };
 
-// in:  sk/sv   the m items sorted by (key, input position): key in the low 32 bits of sk, position in sv (< count)
-//      ik/iv   the same items in input order
-// out: sorted_id[j] = position (in the slice) of the j-th element of std::sort's result
-// Scratch arrays have m + 1 entries.  The partition rounds run on arrays in HBM while more than kMaxSlice elements lie in
-// segments that still hold ties, then in LDS (lds_a / lds_sc: wave_sort_arrangement, the replay of the small slices).  Returns false when
-// the depth limit's heap sort would have to run on a segment too large to do by one thread in global memory (flags |= 4:
-// the host entry point takes the cloud).
-__device__ bool big_sort_order(const unsigned long long* __restrict__ sk, const unsigned* __restrict__ sv,
-                               const unsigned long long* __restrict__ ik, const unsigned* __restrict__ iv, int m, int count,
-                               const BigArrays& A, unsigned off, unsigned* wave_sums, unsigned long long* lds_a,
-                               const SortScratch& lds_sc) {
-#ifdef DLIOM_EXPERIMENTS
-#define DLIOM_SSTAMP(k) if (threadIdx.x == 0 && blockIdx.x < 4) dbg_big[(blockIdx.x + 8) * 16 + (k)] = __builtin_readcyclecounter()
-#else
-#define DLIOM_SSTAMP(k)
-#endif
-  __shared__ int wl_first[kWorkListCap], wl_last[kWorkListCap], wl_depth[kWorkListCap];
-  __shared__ int wl_n, wl_pick, wl_total, wl_overflow, wl_mode;
-  __shared__ int wl_base[kWorkListCap + 1];
-  __shared__ unsigned co_cnt[2][kThreads / 64];
-  __shared__ unsigned co_k, co_tied[2];
-  __shared__ int co_cut;
-  // ---- slices up to ~16 000 points (the floor of a filtered 64- or 128-beam scan): the whole replay in LDS.  An item is
-  //      32 bits there -- the angle's dense RANK among the slice's angles (the radix sort's order gives it; equal angles
-  //      share it, so comparisons come out as on the angles) and the position in the slice, 16 bits each -- and the two
-  //      pointers' stops are 16-bit positions: 9 bytes per point with the tie flags.  (Until this, seven workgroup-wide
-  //      partitions on arrays in HBM at ~9.5 us each -- nine dependent L2 round trips a round -- then a copy into LDS
-  //      for the rest: 150 us of a 10 000-point floor slice's 300.)
-  {
-    const size_t arr_bytes = (static_cast<size_t>(m) + 2) / 2 * 8;               // u32 [m + 1], 8-byte aligned end
-    const size_t stop_bytes = (static_cast<size_t>(m) + 8 + 3) / 4 * 8;          // u16 [m + 8]
-    const size_t tied_bytes = (static_cast<size_t>(count) + 8 + 15) / 16 * 16;   // u8 [count + 8]
-    // the ring of the wave-per-segment stage: the segments of a level are disjoint and have more than 16 elements each
-    const size_t queue_entries = 2 * static_cast<size_t>(m) / 17 + 64;
-    const size_t need = arr_bytes + 2 * stop_bytes + tied_bytes + 16 + queue_entries * sizeof(uint2) + 16;
-    if (need <= kBigLdsBytes && count < 65536 && 2 * stop_bytes >= 2 * static_cast<size_t>(count)) {
-      char* base = reinterpret_cast<char*>(lds_a);
-      unsigned* arr = reinterpret_cast<unsigned*>(base);
-      unsigned short* tl = reinterpret_cast<unsigned short*>(base + arr_bytes);
-      unsigned short* tr = reinterpret_cast<unsigned short*>(base + arr_bytes + stop_bytes);
-      unsigned char* tied = reinterpret_cast<unsigned char*>(base + arr_bytes + 2 * stop_bytes);
-      Queue* queue = reinterpret_cast<Queue*>(base + arr_bytes + 2 * stop_bytes + tied_bytes);
-      unsigned short* rank_by_pos = tl;  // [count], before the partitions need the stops' arrays
-      unsigned* __restrict__ sorted_id = A.sorted_id + off;
-      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-      DLIOM_SSTAMP(0);
-      for (int p = threadIdx.x; p < count + 8; p += kThreads) tied[p] = 0;
-      __syncthreads();
-      int t = 0;
-      for (int j0 = static_cast<int>(threadIdx.x); j0 < m; j0 += 8 * kThreads) {  // (coalesced, eight loads in flight)
-        unsigned ka[8], kb[8], ia[8], ib[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int j = min(j0 + u * kThreads, m - 1), j1 = min(j + 1, m - 1);
-          ka[u] = static_cast<unsigned>(sk[j]);
-          kb[u] = static_cast<unsigned>(sk[j1]);
-          ia[u] = sv[j];
-          ib[u] = sv[j1];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int j = j0 + u * kThreads;
-          if (j + 1 < m && ka[u] == kb[u]) {
-            tied[ia[u]] = 1;
-            tied[ib[u]] = 1;
-            t = 1;
-          }
-        }
-      }
-      const bool any_tie = __syncthreads_or(t) != 0;
-      if (!any_tie) {
-        for (int j = threadIdx.x; j < m; j += kThreads) sorted_id[j] = sv[j];
-        __syncthreads();
-        return true;
-      }
-      DLIOM_SSTAMP(1);
-      // the angles' dense ranks: thread t owns the sorted positions [lo, hi)
-      int lo, hi;
-      owned_range(m, &lo, &hi);
-      {
-        constexpr int kOwnMax = 16;  // (m <= 16 384 here)
-        unsigned kk[kOwnMax + 1], vv[kOwnMax];
-#pragma unroll
-        for (int u = 0; u <= kOwnMax; ++u) kk[u] = static_cast<unsigned>(sk[min(max(lo - 1 + u, 0), m - 1)]);
-#pragma unroll
-        for (int u = 0; u < kOwnMax; ++u) vv[u] = sv[min(lo + u, m - 1)];
-        unsigned mine = 0u;
-#pragma unroll
-        for (int u = 0; u < kOwnMax; ++u)
-          if (lo + u < hi && lo + u > 0 && kk[u + 1] != kk[u]) ++mine;
-        unsigned total;
-        unsigned rank = block_exclusive_scan(mine, wave_sums, &total);
-#pragma unroll
-        for (int u = 0; u < kOwnMax; ++u)
-          if (lo + u < hi) {
-            if (lo + u > 0 && kk[u + 1] != kk[u]) ++rank;
-            rank_by_pos[vv[u]] = static_cast<unsigned short>(rank);
-          }
-      }
-      __syncthreads();
-      for (int q0 = static_cast<int>(threadIdx.x); q0 < m; q0 += 8 * kThreads) {  // std::sort's input: the items in input order
-        unsigned v8[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v8[u] = iv[min(q0 + u * kThreads, m - 1)];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (q0 + u * kThreads < m) arr[q0 + u * kThreads] = (static_cast<unsigned>(rank_by_pos[v8[u]]) << 16) | v8[u];
-      }
-      int depth0 = 0;
-      for (int v = m; v > 1; v >>= 1) ++depth0;
-      depth0 *= 2;
-      if (threadIdx.x == 0) {
-        wl_first[0] = 0;
-        wl_last[0] = m;
-        wl_depth[0] = depth0;
-        wl_n = m > 16 ? 1 : 0;
-        wl_overflow = 0;
-      }
-      queue_init(queue, static_cast<unsigned>(queue_entries));
-      __syncthreads();  // (rank_by_pos is dead: the stops' arrays are free)
-      DLIOM_SSTAMP(2);
-#ifdef DLIOM_EXPERIMENTS
-      int dbg_rounds_lds = 0;
-#endif
-      bool ok = true;
-#ifdef DLIOM_EXPERIMENTS
-      const int kCoopMin = dbg_coop_min;
-#else
-      // larger segments are partitioned by the whole workgroup, smaller ones by a wave each (a workgroup-wide partition
-      // costs ~18 000 cycles whatever the size -- nine barriers --, a wave takes ~30 cycles per element but sixteen of
-      // them work side by side; measured on a 10 462-point floor slice: 239 000 cycles with 1024, 206 000 with 2048,
-      // 175 000 with 4096, 230 000 with 8192)
-      constexpr int kCoopMin = 4096;
-#endif
-      for (int guard = 0; guard < (1 << 16); ++guard) {
-        if (threadIdx.x == 0) {
-          int pick = -1, best = kCoopMin;
-          for (int e = 0; e < wl_n; ++e) {
-            const int len = wl_last[e] - wl_first[e];
-            if (len > best) {
-              best = len;
-              pick = e;
-            }
-          }
-          wl_pick = pick;
-        }
-        __syncthreads();
-        if (wl_pick < 0 || wl_overflow != 0) break;
-#ifdef DLIOM_EXPERIMENTS
-        ++dbg_rounds_lds;
-#endif
-        const int first = wl_first[wl_pick], last = wl_last[wl_pick], depth = wl_depth[wl_pick];
-        if (depth == 0) {  // std::sort's depth limit on a segment that large: its heap sort, sequential -- refused
-          ok = false;
-          break;
-        }
-        // (a) __move_median_to_first(first, first + 1, mid, last - 1)
-        if (threadIdx.x == 0) {
-          const int ia = first + 1, ib = first + (last - first) / 2, ic = last - 1;
-          const unsigned ka = item_key(arr[ia]), kb = item_key(arr[ib]), kc = item_key(arr[ic]);
-          int md;
-          if (ka < kb) {
-            if (kb < kc) md = ib;
-            else if (ka < kc) md = ic;
-            else md = ia;
-          } else if (ka < kc) md = ia;
-          else if (kb < kc) md = ic;
-          else md = ib;
-          const unsigned tmp = arr[first];
-          arr[first] = arr[md];
-          arr[md] = tmp;
-        }
-        __syncthreads();
-        const unsigned pivot = item_key(arr[first]);
-        // (b) the stops of the two pointers, both lists in ascending order of position: wave w takes a contiguous share
-        const int n_in = last - (first + 1);
-        const int per_wave = ((n_in + (kThreads / 64) * 64 - 1) / ((kThreads / 64) * 64)) * 64;
-        const int w_lo = first + 1 + wave * per_wave, w_hi = min(last, w_lo + per_wave);
-        unsigned cl = 0u, cr = 0u;
-        for (int base2 = w_lo; base2 < w_hi; base2 += 64) {
-          const int p = base2 + lane;
-          const bool in = p < w_hi;
-          const unsigned x = in ? item_key(arr[p]) : 0u;
-          cl += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in && !(x < pivot)));
-          cr += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in && !(pivot < x)));
-        }
-        if (lane == 0) {
-          co_cnt[0][wave] = cl;
-          co_cnt[1][wave] = cr;
-        }
-        __syncthreads();
-        unsigned at_l = 0u, at_r = 0u, cnt_l = 0u, cnt_r = 0u;
-        for (int w = 0; w < kThreads / 64; ++w) {
-          if (w < wave) {
-            at_l += co_cnt[0][w];
-            at_r += co_cnt[1][w];
-          }
-          cnt_l += co_cnt[0][w];
-          cnt_r += co_cnt[1][w];
-        }
-        unsigned short* stops_l = tl + first + 1;
-        unsigned short* stops_r = tr + first + 1;
-        for (int base2 = w_lo; base2 < w_hi; base2 += 64) {
-          const int p = base2 + lane;
-          const bool in = p < w_hi;
-          const unsigned x = in ? item_key(arr[p]) : 0u;
-          const bool ge = in && !(x < pivot), le = in && !(pivot < x);
-          const unsigned long long ml = __builtin_amdgcn_ballot_w64(ge), mr = __builtin_amdgcn_ballot_w64(le);
-          if (ge) stops_l[at_l + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(ml >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(ml), 0u))] = static_cast<unsigned short>(p);
-          if (le) stops_r[at_r + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mr >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mr), 0u))] = static_cast<unsigned short>(p);
-          at_l += __builtin_popcountll(ml);
-          at_r += __builtin_popcountll(mr);
-        }
-        if (threadIdx.x == 0) {
-          co_k = min(cnt_l, cnt_r);
-          co_tied[0] = co_tied[1] = 0u;
-        }
-        __syncthreads();
-        // (c) the k-th stop from the left swaps with the k-th from the right while they have not crossed
-        const unsigned lim = min(cnt_l, cnt_r);
-        {
-          unsigned first_invalid = lim;
-          for (unsigned k = threadIdx.x; k < lim; k += kThreads)
-            if (!(stops_l[k] < stops_r[cnt_r - 1u - k])) {
-              first_invalid = k;
-              break;  // (the valid k are a prefix: this thread's later ones are invalid as well)
-            }
-          if (first_invalid < lim) atomicMin(&co_k, first_invalid);
-        }
-        __syncthreads();
-        const unsigned K = co_k;
-        for (unsigned k = threadIdx.x; k < K; k += kThreads) {
-          const unsigned il = stops_l[k], ir = stops_r[cnt_r - 1u - k];
-          const unsigned xl = arr[il], xr = arr[ir];
-          arr[il] = xr;
-          arr[ir] = xl;
-        }
-        if (threadIdx.x == 0) {
-          unsigned c = 0x7fffffffu;  // where the left pointer stops next
-          if (K < cnt_l) c = stops_l[K];
-          if (K > 0u) c = min(c, static_cast<unsigned>(stops_r[cnt_r - K]));
-          co_cut = static_cast<int>(c);
-        }
-        __syncthreads();
-        const int cut = co_cut;
-        // (d) [first, cut) and [cut, last): on the list if they are above the threshold and hold two tied elements
-        {
-          unsigned tl2 = 0u, tr2 = 0u;
-          for (int p = first + static_cast<int>(threadIdx.x); p < last; p += kThreads) {
-            const bool td = tied[item_id(arr[p])] != 0;
-            tl2 += (td && p < cut) ? 1u : 0u;
-            tr2 += (td && p >= cut) ? 1u : 0u;
-          }
-#pragma unroll
-          for (int d = 1; d < 64; d <<= 1) {
-            tl2 += __shfl_xor(tl2, d, 64);
-            tr2 += __shfl_xor(tr2, d, 64);
-          }
-          if (lane == 0) {
-            if (tl2 != 0u) atomicAdd(&co_tied[0], tl2);
-            if (tr2 != 0u) atomicAdd(&co_tied[1], tr2);
-          }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          int n = wl_n;
-          wl_first[wl_pick] = wl_first[n - 1];
-          wl_last[wl_pick] = wl_last[n - 1];
-          wl_depth[wl_pick] = wl_depth[n - 1];
-          --n;
-          const int cf[2] = {first, cut}, cl2[2] = {cut, last};
-          for (int c = 0; c < 2; ++c)
-            if (cl2[c] - cf[c] > 16 && co_tied[c] >= 2u) {
-              if (n < kWorkListCap) {
-                wl_first[n] = cf[c];
-                wl_last[n] = cl2[c];
-                wl_depth[n] = depth - 1;
-                ++n;
-              } else {
-                wl_overflow = 1;
-              }
-            }
-          wl_n = n;
-        }
-        __syncthreads();
-      }
-      if (!ok || wl_overflow != 0) return false;
-      DLIOM_SSTAMP(3);
-#ifdef DLIOM_EXPERIMENTS
-      if (threadIdx.x == 0 && blockIdx.x < 4) dbg_big[(blockIdx.x + 8) * 16 + 15] = static_cast<unsigned long long>(dbg_rounds_lds) | (static_cast<unsigned long long>(wl_n) << 32);
-#endif
-      // what is left: one wave per segment, level by level (wave_sort_arrangement), in place
-      if (static_cast<int>(threadIdx.x) < wl_n) queue_push(queue, wl_first[threadIdx.x], wl_last[threadIdx.x], wl_depth[threadIdx.x]);
-      __syncthreads();
-      {
-        const SortScratch sc{tl, tr, tied, queue};
-        if (!wave_sort_arrangement(arr, sc)) return false;
-      }
-      DLIOM_SSTAMP(4);
-      // where the tied elements are in the arrangement; a group of equal keys ends up in arrangement order (the final
-      // insertion sort is stable)
-      unsigned short* pos_of = tl;  // by position in the slice (the stops' arrays are free again)
-      for (int q = threadIdx.x; q < m; q += kThreads) {
-        const unsigned id = item_id(arr[q]);
-        if (tied[id]) pos_of[id] = static_cast<unsigned short>(q);
-      }
-      __syncthreads();
-      for (int j0 = static_cast<int>(threadIdx.x); j0 < m; j0 += 8 * kThreads) {
-        unsigned id8[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) id8[u] = sv[min(j0 + u * kThreads, m - 1)];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int j = j0 + u * kThreads;
-          if (j >= m) continue;
-          const unsigned id = id8[u];
-          unsigned dst = static_cast<unsigned>(j);
-          if (tied[id]) {
-            const unsigned key = static_cast<unsigned>(sk[j]);
-            int gs = j, ge = j + 1;
-            while (gs > 0 && static_cast<unsigned>(sk[gs - 1]) == key) --gs;
-            while (ge < m && static_cast<unsigned>(sk[ge]) == key) ++ge;
-            const unsigned mine = pos_of[id];
-            unsigned r = 0u;
-            for (int w2 = gs; w2 < ge; ++w2) r += pos_of[sv[w2]] < mine ? 1u : 0u;
-            dst = static_cast<unsigned>(gs) + r;
-          }
-          sorted_id[dst] = id;
-        }
-      }
-      __syncthreads();
-      DLIOM_SSTAMP(5);
-      return true;
-    }
-  }
-  unsigned long long* __restrict__ arr = A.arr + off;
-  unsigned* __restrict__ l = A.l + off;
-  unsigned* __restrict__ tmp_l = A.tmp_l + off;
-  unsigned* __restrict__ tmp_r = A.tmp_r + off;
-  unsigned* __restrict__ pos_of = A.pos_of + off;
-  unsigned* __restrict__ sorted_id = A.sorted_id + off;
-  unsigned char* __restrict__ tied = A.tied + off;
-  int lo, hi;
-  {  // positions in the slice run over [0, count); m <= count of them are items
-    int clo, chi;
-    owned_range(count, &clo, &chi);
-    for (int p = clo; p < chi; ++p) tied[p] = 0;
-  }
-  owned_range(m, &lo, &hi);
-  __syncthreads();
+// What the workgroup shares during the replay: the work list of segments that still hold ties (disjoint, in the
+// coordinates of the array), thread 0's decision for the round, and the counters of the partition in progress.
+struct ReplayShared {
+  int wl_first[kWorkListCap], wl_last[kWorkListCap], wl_depth[kWorkListCap];
+  int wl_n, wl_pick, wl_total, wl_overflow, wl_mode;
+  int wl_base[kWorkListCap + 1];  // the HBM variant's batch in LDS: where its segments begin there
+  unsigned co_cnt[2][kThreads / 64];
+  unsigned co_k, co_tied[2];
+  int co_cut;
+};
+
+// tied[position in the slice] = 1 for every element whose key occurs more than once, from the m items sorted by (key,
+// input position).  The caller has zeroed tied[] (and a barrier); returns, after a barrier, whether there is any.
+__device__ __forceinline__ bool mark_tied(const unsigned long long* __restrict__ sk, const unsigned* __restrict__ sv, int m,
+                                          unsigned char* __restrict__ tied) {
   int t = 0;
   for (int j0 = static_cast<int>(threadIdx.x); j0 < m; j0 += 8 * kThreads) {  // (coalesced, eight loads in flight)
-    unsigned ka[8], kb[8];
+    unsigned ka[8], kb[8], ia[8], ib[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const int j = min(j0 + u * kThreads, m - 1);
+      const int j = min(j0 + u * kThreads, m - 1), j1 = min(j + 1, m - 1);
       ka[u] = static_cast<unsigned>(sk[j]);
-      kb[u] = static_cast<unsigned>(sk[min(j + 1, m - 1)]);
+      kb[u] = static_cast<unsigned>(sk[j1]);
+      ia[u] = sv[j];
+      ib[u] = sv[j1];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int j = j0 + u * kThreads;
       if (j + 1 < m && ka[u] == kb[u]) {
-        tied[sv[j]] = 1;
-        tied[sv[j + 1]] = 1;
+        tied[ia[u]] = 1;
+        tied[ib[u]] = 1;
         t = 1;
       }
     }
   }
-  const bool any_tie = __syncthreads_or(t) != 0;
-#ifdef DLIOM_EXPERIMENTS
-  int dbg_round = 0;
-#endif
-  DLIOM_SSTAMP(0);
-  if (!any_tie) {
-    for (int j = threadIdx.x; j < m; j += kThreads) sorted_id[j] = sv[j];
-    __syncthreads();
-    return true;
-  }
-  for (int p0 = static_cast<int>(threadIdx.x); p0 < m; p0 += 8 * kThreads) {
-    unsigned k8[8], v8[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int p = min(p0 + u * kThreads, m - 1);
-      k8[u] = static_cast<unsigned>(ik[p]);
-      v8[u] = iv[p];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (p0 + u * kThreads < m) arr[p0 + u * kThreads] = (static_cast<unsigned long long>(k8[u]) << 32) | v8[u];
-  }
+  return __syncthreads_or(t) != 0;
+}
+
+// No ties: the sorted order is unique
+__device__ __forceinline__ void plain_sorted_order(const unsigned* __restrict__ sv, int m, unsigned* __restrict__ sorted_id) {
+  for (int j = threadIdx.x; j < m; j += kThreads) sorted_id[j] = sv[j];
+  __syncthreads();
+}
+
+// std::sort's first call: __introsort_loop(first, last, std::__lg(m) * 2) -- depth0 partitions on a path before the heap
+// sort.  All threads; a barrier must follow.
+__device__ __forceinline__ void work_list_start(ReplayShared& sh, int m) {
   int depth0 = 0;
   for (int v = m; v > 1; v >>= 1) ++depth0;
   depth0 *= 2;
-  bool ok = true;
-  // ---- introsort's partitions, only where two tied elements still share a segment.  A work list of such segments
-  //      (disjoint, in HBM coordinates); while they hold more than kMaxSlice elements together the LARGEST one is
-  //      partitioned by the whole workgroup (coop_partition: four coalesced passes), then everything left moves to LDS
-  //      and wave_sort_arrangement finishes it.  (Round 4's first version ran all segments through block-wide rounds over
-  //      thread-owned positions: ~90 us per round for a floor slice of 10 000 returns, four or five rounds.)
   if (threadIdx.x == 0) {
-    wl_first[0] = 0;
-    wl_last[0] = m;
-    wl_depth[0] = depth0;
-    wl_n = m > 16 ? 1 : 0;
-    wl_overflow = 0;
+    sh.wl_first[0] = 0;
+    sh.wl_last[0] = m;
+    sh.wl_depth[0] = depth0;
+    sh.wl_n = m > 16 ? 1 : 0;
+    sh.wl_overflow = 0;
+  }
+}
+
+// (a) __move_median_to_first(first, first + 1, mid, last - 1); returns the pivot's key (after a barrier)
+template <class Item>
+__device__ __forceinline__ unsigned median_to_first(Item* __restrict__ arr, int first, int last) {
+  if (threadIdx.x == 0) {
+    const int ia = first + 1, ib = first + (last - first) / 2, ic = last - 1;
+    const unsigned ka = item_key(arr[ia]), kb = item_key(arr[ib]), kc = item_key(arr[ic]);
+    int md;
+    if (ka < kb) {
+      if (kb < kc) md = ib;
+      else if (ka < kc) md = ic;
+      else md = ia;
+    } else if (ka < kc) md = ia;
+    else if (kb < kc) md = ic;
+    else md = ib;
+    const Item tmp = arr[first];
+    arr[first] = arr[md];
+    arr[md] = tmp;
   }
   __syncthreads();
+  return item_key(arr[first]);
+}
+
+// (b), (c) __unguarded_partition(first + 1, last, first) by the whole workgroup; returns the cut (after a barrier) and
+// leaves co_tied zeroed for (d).  tl / tr: the two pointers' stops, as many entries as arr.
+template <int kSteps, class Item, class Stop>
+__device__ __forceinline__ int coop_partition(Item* __restrict__ arr, Stop* __restrict__ tl, Stop* __restrict__ tr, int first,
+                                              int last, unsigned pivot, ReplayShared& sh) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int guard = 0; guard < (1 << 20); ++guard) {
-    // What next (thread 0 decides, everybody follows): the largest segment is partitioned by the whole workgroup in HBM,
-    // or as many segments as fit LDS together are finished there (wave_sort_arrangement) and leave the list.
-    if (threadIdx.x == 0) {
-      int pick = -1, best = 0, total = 0;
-      for (int e = 0; e < wl_n; ++e) {
-        const int len = wl_last[e] - wl_first[e];
-        total += len;
-        if (len > best) {
-          best = len;
-          pick = e;
-        }
-      }
-      wl_pick = pick;
-      // With a handful of tied pairs the segments that matter halve with every partition: a few workgroup-wide
-      // partitions (~9 us each) until everything left fits LDS at once beat several LDS batches (~40 us each).  With ties
-      // everywhere nothing shrinks: then the segments go through LDS in batches as soon as they are small enough.
-      // A segment at std::sort's depth limit is heap-sorted, which wave_sort_arrangement does (one lane) for what fits LDS:
-      // such a segment goes with a batch however much else is waiting.  (Round 6's soak, 18 865 keys with a fifth of
-      // them tied: a path of lopsided partitions reached the limit on 1 203 elements while 5 000 others waited, the
-      // workgroup-wide branch was chosen for it and refused.)
-      int mode = 0;
-      if (wl_n > 0) {
-        const bool by_workgroup = best > kMaxSlice || (total > kMaxSlice && best > kMaxSlice / 4 && wl_depth[pick] > 0);
-        mode = (by_workgroup && wl_n < kWorkListCap - 2) ? 1 : 2;
-      }
-      if (mode == 2) {  // the batch: entries in list order while they fit; the chosen ones move to the END of the list
-        int at = 0, taken = 0, n = wl_n;
-        for (int e = 0; e < n - taken;) {
-          const int len = wl_last[e] - wl_first[e];
-          if (len <= kMaxSlice && at + len <= kMaxSlice && taken < kWorkListCap) {
-            const int last_free = n - taken - 1;
-            const int f = wl_first[e], l2 = wl_last[e], d = wl_depth[e];
-            wl_first[e] = wl_first[last_free];
-            wl_last[e] = wl_last[last_free];
-            wl_depth[e] = wl_depth[last_free];
-            wl_first[last_free] = f;
-            wl_last[last_free] = l2;
-            wl_depth[last_free] = d;
-            at += len;
-            ++taken;
-          } else {
-            ++e;
-          }
-        }
-        wl_total = taken;  // the batch is the last `taken` entries of the list
-        if (taken == 0) wl_overflow = 1;  // a list full of segments above kMaxSlice: cannot happen below 2^18 elements
-      }
-      wl_mode = mode;
-    }
-    __syncthreads();
-    if (wl_mode == 0 || wl_overflow != 0) break;
-    if (wl_mode == 2) {
-      // ---- a batch in LDS: the chosen segments packed one behind the other; an item's identity there is its packed index
-      const int n_batch = wl_total, e0 = wl_n - n_batch;
-      if (threadIdx.x == 0) {
-        int at = 0;
-        for (int e = 0; e < n_batch; ++e) {
-          wl_base[e] = at;
-          at += wl_last[e0 + e] - wl_first[e0 + e];
-        }
-        wl_base[n_batch] = at;
-      }
-      queue_init(lds_sc.queue);
-      __syncthreads();
-      const int T = wl_base[n_batch];
-      unsigned* __restrict__ cid = l;  // packed index -> position in the slice (the item's low word)
-      for (int c = threadIdx.x; c < T; c += kThreads) {
-        int e = 0;
-        while (c >= wl_base[e + 1]) ++e;
-        const int p = wl_first[e0 + e] + (c - wl_base[e]);
-        const unsigned long long item = arr[p];
-        lds_a[c] = (item & 0xffffffff00000000ull) | static_cast<unsigned>(c);
-        const_cast<unsigned char*>(lds_sc.tied)[c] = tied[static_cast<unsigned>(item)];
-        cid[c] = static_cast<unsigned>(item);
-      }
-      if (static_cast<int>(threadIdx.x) < n_batch)
-        queue_push(lds_sc.queue, wl_base[threadIdx.x], wl_base[threadIdx.x + 1], wl_depth[e0 + threadIdx.x]);
-      __syncthreads();
-      DLIOM_SSTAMP(11);
-      if (!wave_sort_arrangement(lds_a, lds_sc)) ok = false;
-      DLIOM_SSTAMP(12);
-#ifdef DLIOM_EXPERIMENTS
-      if (threadIdx.x == 0 && blockIdx.x < 4) dbg_big[(blockIdx.x + 8) * 16 + 15] = static_cast<unsigned long long>(T) | (static_cast<unsigned long long>(dbg_round) << 32);
-#endif
-      for (int q = threadIdx.x; q < T; q += kThreads) {
-        int e = 0;
-        while (q >= wl_base[e + 1]) ++e;
-        const unsigned long long item = lds_a[q];
-        arr[wl_first[e0 + e] + (q - wl_base[e])] = (item & 0xffffffff00000000ull) | cid[static_cast<unsigned>(item) & 0xffffu];
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) wl_n = e0;
-      __syncthreads();
-      if (!ok) break;
-      continue;
-    }
-#ifdef DLIOM_EXPERIMENTS
-    if (dbg_round < 9) DLIOM_SSTAMP(1 + dbg_round);
-    ++dbg_round;
-#endif
-    const int first = wl_first[wl_pick], last = wl_last[wl_pick], depth = wl_depth[wl_pick];
-    if (depth == 0) {
-      // std::sort's depth limit on a segment that large: its heap sort, sequential in HBM -- refused (the host takes the cloud)
-      ok = false;
-      break;
-    }
-    // (a) __move_median_to_first(first, first + 1, mid, last - 1)
-    if (threadIdx.x == 0) {
-      const int ia = first + 1, ib = first + (last - first) / 2, ic = last - 1;
-      const unsigned ka = key_of(arr[ia]), kb = key_of(arr[ib]), kc = key_of(arr[ic]);
-      int md;
-      if (ka < kb) {
-        if (kb < kc) md = ib;
-        else if (ka < kc) md = ic;
-        else md = ia;
-      } else if (ka < kc) md = ia;
-      else if (kb < kc) md = ic;
-      else md = ib;
-      const unsigned long long tmp = arr[first];
-      arr[first] = arr[md];
-      arr[md] = tmp;
-    }
-    __syncthreads();
-    const unsigned pivot = key_of(arr[first]);
-    // (b) the stops of the two pointers, both lists in ascending order of position: wave w takes a contiguous share of
-    //     (first, last) in steps of 64 positions, four steps' loads in flight
-    const int n_in = last - (first + 1);
-    const int per_wave = ((n_in + (kThreads / 64) * 64 - 1) / ((kThreads / 64) * 64)) * 64;
-    const int w_lo = first + 1 + wave * per_wave, w_hi = min(last, w_lo + per_wave);
-    unsigned cl = 0u, cr = 0u;
-    for (int base = w_lo; base < w_hi; base += 256) {
-      unsigned x[4];
+  // (b) the stops of the two pointers, both lists in ascending order of position: wave w takes a contiguous share of
+  //     (first, last) in steps of 64 positions, kSteps steps' loads in flight
+  const int n_in = last - (first + 1);
+  const int per_wave = ((n_in + (kThreads / 64) * 64 - 1) / ((kThreads / 64) * 64)) * 64;
+  const int w_lo = first + 1 + wave * per_wave, w_hi = min(last, w_lo + per_wave);
+  unsigned cl = 0u, cr = 0u;
+  for (int base = w_lo; base < w_hi; base += 64 * kSteps) {
+    unsigned x[kSteps];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < kSteps; ++u) {
+      const int p = base + 64 * u + lane;
+      x[u] = p < w_hi ? item_key(arr[p]) : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u) {
+      const bool in = base + 64 * u + lane < w_hi;
+      cl += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in && !(x[u] < pivot)));
+      cr += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in && !(pivot < x[u])));
+    }
+  }
+  if (lane == 0) {
+    sh.co_cnt[0][wave] = cl;
+    sh.co_cnt[1][wave] = cr;
+  }
+  __syncthreads();
+  unsigned at_l = 0u, at_r = 0u, cnt_l = 0u, cnt_r = 0u;
+  for (int w = 0; w < kThreads / 64; ++w) {
+    if (w < wave) {
+      at_l += sh.co_cnt[0][w];
+      at_r += sh.co_cnt[1][w];
+    }
+    cnt_l += sh.co_cnt[0][w];
+    cnt_r += sh.co_cnt[1][w];
+  }
+  Stop* __restrict__ stops_l = tl + first + 1;
+  Stop* __restrict__ stops_r = tr + first + 1;
+  for (int base = w_lo; base < w_hi; base += 64 * kSteps) {
+    unsigned x[kSteps];
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u) {
+      const int p = base + 64 * u + lane;
+      x[u] = p < w_hi ? item_key(arr[p]) : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u) {
+      const int p = base + 64 * u + lane;
+      const bool in = p < w_hi;
+      const bool ge = in && !(x[u] < pivot), le = in && !(pivot < x[u]);
+      const unsigned long long ml = __builtin_amdgcn_ballot_w64(ge), mr = __builtin_amdgcn_ballot_w64(le);
+      if (ge) stops_l[at_l + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(ml >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(ml), 0u))] = static_cast<Stop>(p);
+      if (le) stops_r[at_r + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mr >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mr), 0u))] = static_cast<Stop>(p);
+      at_l += __builtin_popcountll(ml);
+      at_r += __builtin_popcountll(mr);
+    }
+  }
+  if (threadIdx.x == 0) {
+    sh.co_k = min(cnt_l, cnt_r);
+    sh.co_tied[0] = sh.co_tied[1] = 0u;
+  }
+  __syncthreads();
+  // (c) the k-th stop from the left swaps with the k-th from the right while they have not crossed: K = the first k
+  //     that does not (the valid k are 0 .. K - 1: positions from the left grow with k, from the right they fall -- once
+  //     a thread has met an invalid k, its later ones are invalid as well)
+  const unsigned lim = min(cnt_l, cnt_r);
+  {
+    unsigned first_invalid = lim;
+    for (unsigned k0 = threadIdx.x; k0 < lim && first_invalid == lim; k0 += kSteps * kThreads) {
+      unsigned a[kSteps], b[kSteps];
+#pragma unroll
+      for (int u = 0; u < kSteps; ++u) {
+        const unsigned k = k0 + u * kThreads;
+        a[u] = k < lim ? stops_l[k] : 0u;
+        b[u] = k < lim ? stops_r[cnt_r - 1u - k] : 1u;
+      }
+#pragma unroll
+      for (int u = 0; u < kSteps; ++u) {
+        const unsigned k = k0 + u * kThreads;
+        if (k < lim && !(a[u] < b[u])) first_invalid = min(first_invalid, k);
+      }
+    }
+    if (first_invalid < lim) atomicMin(&sh.co_k, first_invalid);
+  }
+  __syncthreads();
+  const unsigned K = sh.co_k;
+  for (unsigned k0 = threadIdx.x; k0 < K; k0 += kSteps * kThreads) {
+    unsigned il[kSteps], ir[kSteps];
+    Item xl[kSteps], xr[kSteps];
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u) {
+      const unsigned k = k0 + u * kThreads;
+      il[u] = k < K ? stops_l[k] : 0u;
+      ir[u] = k < K ? stops_r[cnt_r - 1u - k] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u) {
+      xl[u] = arr[il[u]];
+      xr[u] = arr[ir[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < kSteps; ++u)
+      if (k0 + u * kThreads < K) {
+        arr[il[u]] = xr[u];
+        arr[ir[u]] = xl[u];
+      }
+  }
+  if (threadIdx.x == 0) {
+    unsigned c = 0x7fffffffu;  // where the left pointer stops next
+    if (K < cnt_l) c = stops_l[K];
+    if (K > 0u) c = min(c, static_cast<unsigned>(stops_r[cnt_r - K]));
+    sh.co_cut = static_cast<int>(c);
+  }
+  __syncthreads();
+  return sh.co_cut;
+}
+
+// (d) [first, cut) and [cut, last) replace the picked entry of the work list if they are above the insertion sort's
+// threshold and hold two tied elements (co_tied: zeroed by coop_partition).  Returns after a barrier.
+template <int kSteps, class Item, class IdOf>
+__device__ __forceinline__ void replace_by_children(const Item* __restrict__ arr, const unsigned char* __restrict__ tied, IdOf id_of,
+                                                    int first, int cut, int last, int depth, ReplayShared& sh) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  {
+    const int n_all = last - first;
+    const int pw = ((n_all + (kThreads / 64) * 64 - 1) / ((kThreads / 64) * 64)) * 64;
+    const int lo_w = first + wave * pw, hi_w = min(last, lo_w + pw);
+    unsigned tied_l = 0u, tied_r = 0u;
+    for (int base = lo_w; base < hi_w; base += 64 * kSteps) {
+      unsigned id[kSteps];
+#pragma unroll
+      for (int u = 0; u < kSteps; ++u) {
         const int p = base + 64 * u + lane;
-        x[u] = p < w_hi ? key_of(arr[p]) : 0u;
+        id[u] = p < hi_w ? id_of(arr[p]) : 0u;
       }
+      unsigned char td[kSteps];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bool in = base + 64 * u + lane < w_hi;
-        cl += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in && !(x[u] < pivot)));
-        cr += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in && !(pivot < x[u])));
+      for (int u = 0; u < kSteps; ++u) td[u] = base + 64 * u + lane < hi_w ? tied[id[u]] : 0;
+#pragma unroll
+      for (int u = 0; u < kSteps; ++u) {
+        const int p = base + 64 * u + lane;
+        tied_l += __builtin_popcountll(__builtin_amdgcn_ballot_w64(td[u] != 0 && p < cut));
+        tied_r += __builtin_popcountll(__builtin_amdgcn_ballot_w64(td[u] != 0 && p >= cut));
       }
     }
     if (lane == 0) {
-      co_cnt[0][wave] = cl;
-      co_cnt[1][wave] = cr;
+      atomicAdd(&sh.co_tied[0], tied_l);
+      atomicAdd(&sh.co_tied[1], tied_r);
     }
-    __syncthreads();
-    unsigned at_l = 0u, at_r = 0u, cnt_l = 0u, cnt_r = 0u;
-    for (int w = 0; w < kThreads / 64; ++w) {
-      if (w < wave) {
-        at_l += co_cnt[0][w];
-        at_r += co_cnt[1][w];
-      }
-      cnt_l += co_cnt[0][w];
-      cnt_r += co_cnt[1][w];
-    }
-    unsigned* stops_l = tmp_l + first + 1;
-    unsigned* stops_r = tmp_r + first + 1;
-    for (int base = w_lo; base < w_hi; base += 256) {
-      unsigned x[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int p = base + 64 * u + lane;
-        x[u] = p < w_hi ? key_of(arr[p]) : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int p = base + 64 * u + lane;
-        const bool in = p < w_hi;
-        const bool ge = in && !(x[u] < pivot), le = in && !(pivot < x[u]);
-        const unsigned long long ml = __builtin_amdgcn_ballot_w64(ge), mr = __builtin_amdgcn_ballot_w64(le);
-        if (ge) stops_l[at_l + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(ml >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(ml), 0u))] = static_cast<unsigned>(p);
-        if (le) stops_r[at_r + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mr >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mr), 0u))] = static_cast<unsigned>(p);
-        at_l += __builtin_popcountll(ml);
-        at_r += __builtin_popcountll(mr);
-      }
-    }
-    if (threadIdx.x == 0) {
-      co_k = min(cnt_l, cnt_r);
-      co_tied[0] = co_tied[1] = 0u;
-    }
-    __syncthreads();
-    // (c) the k-th stop from the left swaps with the k-th from the right while they have not crossed: K = the first k
-    //     that does not (the valid k are 0 .. K - 1: positions from the left grow with k, from the right they fall)
-    const unsigned lim = min(cnt_l, cnt_r);
-    {
-      unsigned first_invalid = lim;
-      for (unsigned k0 = threadIdx.x; k0 < lim; k0 += 4 * kThreads) {
-        unsigned a4[4], b4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned k = k0 + u * kThreads;
-          a4[u] = k < lim ? stops_l[k] : 0u;
-          b4[u] = k < lim ? stops_r[cnt_r - 1u - k] : 1u;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned k = k0 + u * kThreads;
-          if (k < lim && !(a4[u] < b4[u])) first_invalid = min(first_invalid, k);
-        }
-      }
-      if (first_invalid < lim) atomicMin(&co_k, first_invalid);
-    }
-    __syncthreads();
-    const unsigned K = co_k;
-    for (unsigned k0 = threadIdx.x; k0 < K; k0 += 4 * kThreads) {
-      unsigned il[4], ir[4];
-      unsigned long long xl[4], xr[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const unsigned k = k0 + u * kThreads;
-        il[u] = k < K ? stops_l[k] : 0u;
-        ir[u] = k < K ? stops_r[cnt_r - 1u - k] : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        xl[u] = arr[il[u]];
-        xr[u] = arr[ir[u]];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (k0 + u * kThreads < K) {
-          arr[il[u]] = xr[u];
-          arr[ir[u]] = xl[u];
-        }
-    }
-    if (threadIdx.x == 0) {
-      unsigned c = 0x7fffffffu;  // where the left pointer stops next
-      if (K < cnt_l) c = stops_l[K];
-      if (K > 0u) c = min(c, stops_r[cnt_r - K]);
-      co_cut = static_cast<int>(c);
-    }
-    __syncthreads();
-    const int cut = co_cut;
-    // (d) [first, cut) and [cut, last): on the list if they are above the threshold and hold two tied elements
-    {
-      const int n_all = last - first;
-      const int pw = ((n_all + (kThreads / 64) * 64 - 1) / ((kThreads / 64) * 64)) * 64;
-      const int lo_w = first + wave * pw, hi_w = min(last, lo_w + pw);
-      unsigned tl = 0u, tr = 0u;
-      for (int base = lo_w; base < hi_w; base += 256) {
-        unsigned id4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int p = base + 64 * u + lane;
-          id4[u] = p < hi_w ? static_cast<unsigned>(arr[p]) : 0u;
-        }
-        unsigned char t4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) t4[u] = base + 64 * u + lane < hi_w ? tied[id4[u]] : 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int p = base + 64 * u + lane;
-          tl += __builtin_popcountll(__builtin_amdgcn_ballot_w64(t4[u] != 0 && p < cut));
-          tr += __builtin_popcountll(__builtin_amdgcn_ballot_w64(t4[u] != 0 && p >= cut));
-        }
-      }
-      if (lane == 0) {
-        atomicAdd(&co_tied[0], tl);
-        atomicAdd(&co_tied[1], tr);
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      // replace the entry by its children that still matter
-      int n = wl_n;
-      wl_first[wl_pick] = wl_first[n - 1];
-      wl_last[wl_pick] = wl_last[n - 1];
-      wl_depth[wl_pick] = wl_depth[n - 1];
-      --n;
-      const int cf[2] = {first, cut}, cl2[2] = {cut, last};
-      for (int c = 0; c < 2; ++c)
-        if (cl2[c] - cf[c] > 16 && co_tied[c] >= 2u) {
-          if (n < kWorkListCap) {
-            wl_first[n] = cf[c];
-            wl_last[n] = cl2[c];
-            wl_depth[n] = depth - 1;
-            ++n;
-          } else {
-            wl_overflow = 1;
-          }
-        }
-      wl_n = n;
-    }
-    __syncthreads();
   }
-  if (wl_overflow != 0) ok = false;
-  if (!ok) return false;
-  DLIOM_SSTAMP(13);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int n = sh.wl_n;
+    sh.wl_first[sh.wl_pick] = sh.wl_first[n - 1];
+    sh.wl_last[sh.wl_pick] = sh.wl_last[n - 1];
+    sh.wl_depth[sh.wl_pick] = sh.wl_depth[n - 1];
+    --n;
+    const int cf[2] = {first, cut}, cl[2] = {cut, last};
+    for (int c = 0; c < 2; ++c)
+      if (cl[c] - cf[c] > 16 && sh.co_tied[c] >= 2u) {
+        if (n < kWorkListCap) {
+          sh.wl_first[n] = cf[c];
+          sh.wl_last[n] = cl[c];
+          sh.wl_depth[n] = depth - 1;
+          ++n;
+        } else {
+          sh.wl_overflow = 1;
+        }
+      }
+    sh.wl_n = n;
+  }
+  __syncthreads();
+}
+
+// One workgroup-wide round on the picked entry [first, last) of the work list: (a) - (d)
+template <int kSteps, class Item, class Stop, class IdOf>
+__device__ __forceinline__ void coop_round(Item* __restrict__ arr, Stop* __restrict__ tl, Stop* __restrict__ tr,
+                                           const unsigned char* __restrict__ tied, IdOf id_of, int first, int last, int depth,
+                                           ReplayShared& sh) {
+  const unsigned pivot = median_to_first(arr, first, last);
+  const int cut = coop_partition<kSteps>(arr, tl, tr, first, last, pivot, sh);
+  replace_by_children<kSteps>(arr, tied, id_of, first, cut, last, depth, sh);
+}
+
+// From the finished arrangement to sorted_id: the elements without ties are where the plain sort has them, and a group
+// of equal keys ends up in arrangement order (the final insertion sort is stable).  pos_of: by position in the slice.
+template <class Item, class Pos, class IdOf>
+__device__ __forceinline__ void place_tie_groups(const Item* __restrict__ arr, const unsigned char* __restrict__ tied,
+                                                 Pos* __restrict__ pos_of, IdOf id_of, const unsigned long long* __restrict__ sk,
+                                                 const unsigned* __restrict__ sv, int m, unsigned* __restrict__ sorted_id) {
   // where the tied elements are in the arrangement
   for (int q0 = static_cast<int>(threadIdx.x); q0 < m; q0 += 8 * kThreads) {
     unsigned id8[8];
     unsigned char f8[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) id8[u] = static_cast<unsigned>(arr[min(q0 + u * kThreads, m - 1)]);
+    for (int u = 0; u < 8; ++u) id8[u] = id_of(arr[min(q0 + u * kThreads, m - 1)]);
 #pragma unroll
     for (int u = 0; u < 8; ++u) f8[u] = tied[id8[u]];
 #pragma unroll
     for (int u = 0; u < 8; ++u)
-      if (q0 + u * kThreads < m && f8[u]) pos_of[id8[u]] = static_cast<unsigned>(q0 + u * kThreads);
+      if (q0 + u * kThreads < m && f8[u]) pos_of[id8[u]] = static_cast<Pos>(q0 + u * kThreads);
   }
   __syncthreads();
-  // the final insertion sort is stable: a group of equal keys ends up in arrangement order
   for (int j0 = static_cast<int>(threadIdx.x); j0 < m; j0 += 8 * kThreads) {
     unsigned id8[8];
     unsigned char f8[8];
@@ -890,25 +477,318 @@ __device__ bool big_sort_order(const unsigned long long* __restrict__ sk, const 
       const int j = j0 + u * kThreads;
       if (j >= m) continue;
       const unsigned id = id8[u];
-      {
-        unsigned dst = static_cast<unsigned>(j);
-        if (f8[u]) {
-          const unsigned key = static_cast<unsigned>(sk[j]);
-          int gs = j, ge = j + 1;
-          while (gs > 0 && static_cast<unsigned>(sk[gs - 1]) == key) --gs;
-          while (ge < m && static_cast<unsigned>(sk[ge]) == key) ++ge;
-          const unsigned mine = pos_of[id];
-          unsigned r = 0u;
-          for (int w2 = gs; w2 < ge; ++w2) r += pos_of[sv[w2]] < mine ? 1u : 0u;
-          dst = static_cast<unsigned>(gs) + r;
-        }
-        sorted_id[dst] = id;
+      unsigned dst = static_cast<unsigned>(j);
+      if (f8[u]) {
+        const unsigned key = static_cast<unsigned>(sk[j]);
+        int gs = j, ge = j + 1;
+        while (gs > 0 && static_cast<unsigned>(sk[gs - 1]) == key) --gs;
+        while (ge < m && static_cast<unsigned>(sk[ge]) == key) ++ge;
+        const unsigned mine = pos_of[id];
+        unsigned r = 0u;
+        for (int w2 = gs; w2 < ge; ++w2) r += pos_of[sv[w2]] < mine ? 1u : 0u;
+        dst = static_cast<unsigned>(gs) + r;
       }
+      sorted_id[dst] = id;
     }
   }
   __syncthreads();
+}
+
+// The arrays of the LDS variant for m items of a slice of `count` points, and whether it takes the slice
+struct LdsReplaySizes {
+  size_t arr_bytes, stop_bytes, tied_bytes, queue_entries;
+  __device__ __forceinline__ LdsReplaySizes(int m, int count)
+      : arr_bytes((static_cast<size_t>(m) + 2) / 2 * 8),              // u32 [m + 1], 8-byte aligned end
+        stop_bytes((static_cast<size_t>(m) + 8 + 3) / 4 * 8),         // u16 [m + 8]
+        tied_bytes((static_cast<size_t>(count) + 8 + 15) / 16 * 16),  // u8 [count + 8]
+        // the ring of the wave-per-segment stage: the segments of a level are disjoint and have more than 16 elements each
+        queue_entries(2 * static_cast<size_t>(m) / 17 + 64) {}
+  __device__ __forceinline__ bool fits(int count) const {
+    const size_t need = arr_bytes + 2 * stop_bytes + tied_bytes + 16 + queue_entries * sizeof(uint2) + 16;
+    return need <= kBigLdsBytes && count < 65536 && 2 * stop_bytes >= 2 * static_cast<size_t>(count);
+  }
+};
+
+// ---- slices up to ~15 000 points (the floor of a filtered 64- or 128-beam scan): the whole replay in LDS.  An item is
+//      32 bits there -- the angle's dense RANK among the slice's angles (the radix sort's order gives it; equal angles
+//      share it, so comparisons come out as on the angles) and the position in the slice, 16 bits each -- and the two
+//      pointers' stops are 16-bit positions: 9 bytes per point with the tie flags.  (Until this, seven workgroup-wide
+//      partitions on arrays in HBM at ~9.5 us each -- nine dependent L2 round trips a round -- then a copy into LDS
+//      for the rest: 150 us of a 10 000-point floor slice's 300.)
+__device__ __forceinline__ bool big_sort_order_lds(const unsigned long long* __restrict__ sk, const unsigned* __restrict__ sv,
+                                                   const unsigned* __restrict__ iv, int m, int count, unsigned* __restrict__ sorted_id,
+                                                   unsigned* wave_sums, char* base, const LdsReplaySizes& sz, ReplayShared& sh) {
+  unsigned* arr = reinterpret_cast<unsigned*>(base);
+  unsigned short* tl = reinterpret_cast<unsigned short*>(base + sz.arr_bytes);
+  unsigned short* tr = reinterpret_cast<unsigned short*>(base + sz.arr_bytes + sz.stop_bytes);
+  unsigned char* tied = reinterpret_cast<unsigned char*>(base + sz.arr_bytes + 2 * sz.stop_bytes);
+  Queue* queue = reinterpret_cast<Queue*>(base + sz.arr_bytes + 2 * sz.stop_bytes + sz.tied_bytes);
+  unsigned short* rank_by_pos = tl;  // [count], before the partitions need the stops' arrays
+  DLIOM_SSTAMP(0);
+  for (int p = threadIdx.x; p < count + 8; p += kThreads) tied[p] = 0;
+  __syncthreads();
+  if (!mark_tied(sk, sv, m, tied)) {
+    plain_sorted_order(sv, m, sorted_id);
+    return true;
+  }
+  DLIOM_SSTAMP(1);
+  // the angles' dense ranks: thread t owns the sorted positions [lo, hi)
+  int lo, hi;
+  owned_range(m, &lo, &hi);
+  {
+    constexpr int kOwnMax = 16;  // (m <= 16 384 here)
+    unsigned kk[kOwnMax + 1], vv[kOwnMax];
+#pragma unroll
+    for (int u = 0; u <= kOwnMax; ++u) kk[u] = static_cast<unsigned>(sk[min(max(lo - 1 + u, 0), m - 1)]);
+#pragma unroll
+    for (int u = 0; u < kOwnMax; ++u) vv[u] = sv[min(lo + u, m - 1)];
+    unsigned mine = 0u;
+#pragma unroll
+    for (int u = 0; u < kOwnMax; ++u)
+      if (lo + u < hi && lo + u > 0 && kk[u + 1] != kk[u]) ++mine;
+    unsigned total;
+    unsigned rank = block_exclusive_scan(mine, wave_sums, &total);
+#pragma unroll
+    for (int u = 0; u < kOwnMax; ++u)
+      if (lo + u < hi) {
+        if (lo + u > 0 && kk[u + 1] != kk[u]) ++rank;
+        rank_by_pos[vv[u]] = static_cast<unsigned short>(rank);
+      }
+  }
+  __syncthreads();
+  for (int q0 = static_cast<int>(threadIdx.x); q0 < m; q0 += 8 * kThreads) {  // std::sort's input: the items in input order
+    unsigned v8[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v8[u] = iv[min(q0 + u * kThreads, m - 1)];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (q0 + u * kThreads < m) arr[q0 + u * kThreads] = (static_cast<unsigned>(rank_by_pos[v8[u]]) << 16) | v8[u];
+  }
+  work_list_start(sh, m);
+  queue_init(queue, static_cast<unsigned>(sz.queue_entries));
+  __syncthreads();  // (rank_by_pos is dead: the stops' arrays are free)
+  DLIOM_SSTAMP(2);
+#ifdef DLIOM_EXPERIMENTS
+  int dbg_rounds_lds = 0;
+  const int kCoopMin = dbg_coop_min;
+#else
+  // larger segments are partitioned by the whole workgroup, smaller ones by a wave each (a workgroup-wide partition
+  // costs ~18 000 cycles whatever the size -- nine barriers --, a wave takes ~30 cycles per element but sixteen of
+  // them work side by side; measured on a 10 462-point floor slice: 239 000 cycles with 1024, 206 000 with 2048,
+  // 175 000 with 4096, 230 000 with 8192)
+  constexpr int kCoopMin = 4096;
+#endif
+  for (int guard = 0; guard < (1 << 16); ++guard) {
+    if (threadIdx.x == 0) {
+      int pick = -1, best = kCoopMin;
+      for (int e = 0; e < sh.wl_n; ++e) {
+        const int len = sh.wl_last[e] - sh.wl_first[e];
+        if (len > best) {
+          best = len;
+          pick = e;
+        }
+      }
+      sh.wl_pick = pick;
+    }
+    __syncthreads();
+    if (sh.wl_pick < 0 || sh.wl_overflow != 0) break;
+#ifdef DLIOM_EXPERIMENTS
+    ++dbg_rounds_lds;
+#endif
+    const int first = sh.wl_first[sh.wl_pick], last = sh.wl_last[sh.wl_pick], depth = sh.wl_depth[sh.wl_pick];
+    if (depth == 0) return false;  // std::sort's depth limit on a segment that large: its heap sort, sequential -- refused
+    coop_round<1>(arr, tl, tr, tied, IdLow16{}, first, last, depth, sh);
+  }
+  if (sh.wl_overflow != 0) return false;
+  DLIOM_SSTAMP(3);
+#ifdef DLIOM_EXPERIMENTS
+  if (threadIdx.x == 0 && blockIdx.x < 4) dbg_big[(blockIdx.x + 8) * 16 + 15] = static_cast<unsigned long long>(dbg_rounds_lds) | (static_cast<unsigned long long>(sh.wl_n) << 32);
+#endif
+  // what is left: one wave per segment, level by level (wave_sort_arrangement), in place
+  if (static_cast<int>(threadIdx.x) < sh.wl_n) queue_push(queue, sh.wl_first[threadIdx.x], sh.wl_last[threadIdx.x], sh.wl_depth[threadIdx.x]);
+  __syncthreads();
+  {
+    const SortScratch sc{tl, tr, tied, queue};
+    if (!wave_sort_arrangement(arr, sc)) return false;
+  }
+  DLIOM_SSTAMP(4);
+  place_tie_groups(arr, tied, /*pos_of (the stops' arrays are free again)*/ tl, IdLow16{}, sk, sv, m, sorted_id);
+  DLIOM_SSTAMP(5);
+  return true;
+}
+
+// ---- larger slices: the arrays in HBM (L2 resident), 64-bit items (key << 32 | position in the slice), and a work
+//      list of the segments that still hold ties.  While they hold more than kMaxSlice elements together the LARGEST one
+//      is partitioned by the whole workgroup, then what is left moves to LDS (lds_a / lds_sc) and wave_sort_arrangement
+//      finishes it.  (Round 4's first version ran all segments through block-wide rounds over thread-owned positions:
+//      ~90 us per round for a floor slice of 10 000 returns, four or five rounds.)
+__device__ __forceinline__ bool big_sort_order_hbm(const unsigned long long* __restrict__ sk, const unsigned* __restrict__ sv,
+                                                   const unsigned long long* __restrict__ ik, const unsigned* __restrict__ iv, int m,
+                                                   int count, const BigArrays& A, unsigned off, unsigned long long* lds_a,
+                                                   const SortScratch& lds_sc, ReplayShared& sh) {
+  unsigned long long* __restrict__ arr = A.arr + off;
+  unsigned* __restrict__ l = A.l + off;
+  unsigned* __restrict__ tmp_l = A.tmp_l + off;
+  unsigned* __restrict__ tmp_r = A.tmp_r + off;
+  unsigned* __restrict__ pos_of = A.pos_of + off;
+  unsigned* __restrict__ sorted_id = A.sorted_id + off;
+  unsigned char* __restrict__ tied = A.tied + off;
+  {  // positions in the slice run over [0, count); m <= count of them are items
+    int clo, chi;
+    owned_range(count, &clo, &chi);
+    for (int p = clo; p < chi; ++p) tied[p] = 0;
+  }
+  __syncthreads();
+  const bool any_tie = mark_tied(sk, sv, m, tied);
+#ifdef DLIOM_EXPERIMENTS
+  int dbg_round = 0;
+#endif
+  DLIOM_SSTAMP(0);
+  if (!any_tie) {
+    plain_sorted_order(sv, m, sorted_id);
+    return true;
+  }
+  for (int p0 = static_cast<int>(threadIdx.x); p0 < m; p0 += 8 * kThreads) {  // std::sort's input: the items in input order
+    unsigned k8[8], v8[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int p = min(p0 + u * kThreads, m - 1);
+      k8[u] = static_cast<unsigned>(ik[p]);
+      v8[u] = iv[p];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (p0 + u * kThreads < m) arr[p0 + u * kThreads] = (static_cast<unsigned long long>(k8[u]) << 32) | v8[u];
+  }
+  work_list_start(sh, m);
+  __syncthreads();
+  for (int guard = 0; guard < (1 << 20); ++guard) {
+    // What next (thread 0 decides, everybody follows): the largest segment is partitioned by the whole workgroup in HBM,
+    // or as many segments as fit LDS together are finished there (wave_sort_arrangement) and leave the list.
+    if (threadIdx.x == 0) {
+      int pick = -1, best = 0, total = 0;
+      for (int e = 0; e < sh.wl_n; ++e) {
+        const int len = sh.wl_last[e] - sh.wl_first[e];
+        total += len;
+        if (len > best) {
+          best = len;
+          pick = e;
+        }
+      }
+      sh.wl_pick = pick;
+      // With a handful of tied pairs the segments that matter halve with every partition: a few workgroup-wide
+      // partitions (~9 us each) until everything left fits LDS at once beat several LDS batches (~40 us each).  With ties
+      // everywhere nothing shrinks: then the segments go through LDS in batches as soon as they are small enough.
+      // A segment at std::sort's depth limit is heap-sorted, which wave_sort_arrangement does (one lane) for what fits LDS:
+      // such a segment goes with a batch however much else is waiting.  (Round 6's soak, 18 865 keys with a fifth of
+      // them tied: a path of lopsided partitions reached the limit on 1 203 elements while 5 000 others waited, the
+      // workgroup-wide branch was chosen for it and refused.)
+      int mode = 0;
+      if (sh.wl_n > 0) {
+        const bool by_workgroup = best > kMaxSlice || (total > kMaxSlice && best > kMaxSlice / 4 && sh.wl_depth[pick] > 0);
+        mode = (by_workgroup && sh.wl_n < kWorkListCap - 2) ? 1 : 2;
+      }
+      if (mode == 2) {  // the batch: entries in list order while they fit; the chosen ones move to the END of the list
+        int at = 0, taken = 0, n = sh.wl_n;
+        for (int e = 0; e < n - taken;) {
+          const int len = sh.wl_last[e] - sh.wl_first[e];
+          if (len <= kMaxSlice && at + len <= kMaxSlice && taken < kWorkListCap) {
+            const int last_free = n - taken - 1;
+            const int f = sh.wl_first[e], l2 = sh.wl_last[e], d = sh.wl_depth[e];
+            sh.wl_first[e] = sh.wl_first[last_free];
+            sh.wl_last[e] = sh.wl_last[last_free];
+            sh.wl_depth[e] = sh.wl_depth[last_free];
+            sh.wl_first[last_free] = f;
+            sh.wl_last[last_free] = l2;
+            sh.wl_depth[last_free] = d;
+            at += len;
+            ++taken;
+          } else {
+            ++e;
+          }
+        }
+        sh.wl_total = taken;  // the batch is the last `taken` entries of the list
+        if (taken == 0) sh.wl_overflow = 1;  // a list full of segments above kMaxSlice: cannot happen below 2^18 elements
+      }
+      sh.wl_mode = mode;
+    }
+    __syncthreads();
+    if (sh.wl_mode == 0 || sh.wl_overflow != 0) break;
+    if (sh.wl_mode == 2) {
+      // ---- a batch in LDS: the chosen segments packed one behind the other; an item's identity there is its packed index
+      const int n_batch = sh.wl_total, e0 = sh.wl_n - n_batch;
+      if (threadIdx.x == 0) {
+        int at = 0;
+        for (int e = 0; e < n_batch; ++e) {
+          sh.wl_base[e] = at;
+          at += sh.wl_last[e0 + e] - sh.wl_first[e0 + e];
+        }
+        sh.wl_base[n_batch] = at;
+      }
+      queue_init(lds_sc.queue);
+      __syncthreads();
+      const int T = sh.wl_base[n_batch];
+      unsigned* __restrict__ cid = l;  // packed index -> position in the slice (the item's low word)
+      for (int c = threadIdx.x; c < T; c += kThreads) {
+        int e = 0;
+        while (c >= sh.wl_base[e + 1]) ++e;
+        const int p = sh.wl_first[e0 + e] + (c - sh.wl_base[e]);
+        const unsigned long long item = arr[p];
+        lds_a[c] = (item & 0xffffffff00000000ull) | static_cast<unsigned>(c);
+        const_cast<unsigned char*>(lds_sc.tied)[c] = tied[static_cast<unsigned>(item)];
+        cid[c] = static_cast<unsigned>(item);
+      }
+      if (static_cast<int>(threadIdx.x) < n_batch)
+        queue_push(lds_sc.queue, sh.wl_base[threadIdx.x], sh.wl_base[threadIdx.x + 1], sh.wl_depth[e0 + threadIdx.x]);
+      __syncthreads();
+      DLIOM_SSTAMP(11);
+      const bool ok = wave_sort_arrangement(lds_a, lds_sc);
+      DLIOM_SSTAMP(12);
+#ifdef DLIOM_EXPERIMENTS
+      if (threadIdx.x == 0 && blockIdx.x < 4) dbg_big[(blockIdx.x + 8) * 16 + 15] = static_cast<unsigned long long>(T) | (static_cast<unsigned long long>(dbg_round) << 32);
+#endif
+      for (int q = threadIdx.x; q < T; q += kThreads) {
+        int e = 0;
+        while (q >= sh.wl_base[e + 1]) ++e;
+        const unsigned long long item = lds_a[q];
+        arr[sh.wl_first[e0 + e] + (q - sh.wl_base[e])] = (item & 0xffffffff00000000ull) | cid[item_id(item)];
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) sh.wl_n = e0;
+      __syncthreads();
+      if (!ok) return false;
+      continue;
+    }
+#ifdef DLIOM_EXPERIMENTS
+    if (dbg_round < 9) DLIOM_SSTAMP(1 + dbg_round);
+    ++dbg_round;
+#endif
+    const int first = sh.wl_first[sh.wl_pick], last = sh.wl_last[sh.wl_pick], depth = sh.wl_depth[sh.wl_pick];
+    // std::sort's depth limit on a segment that large: its heap sort, sequential in HBM -- refused (the host takes the cloud)
+    if (depth == 0) return false;
+    coop_round<4>(arr, tmp_l, tmp_r, tied, IdLowWord{}, first, last, depth, sh);
+  }
+  if (sh.wl_overflow != 0) return false;
+  DLIOM_SSTAMP(13);
+  place_tie_groups(arr, tied, pos_of, IdLowWord{}, sk, sv, m, sorted_id);
   DLIOM_SSTAMP(14);
   return true;
+}
+
+// in:  sk/sv   the m items sorted by (key, input position): key in the low 32 bits of sk, position in sv (< count)
+//      ik/iv   the same items in input order
+// out: A.sorted_id[off + j] = position (in the slice) of the j-th element of std::sort's result
+// Scratch arrays have m + 1 entries.  lds: the kernel's dynamic LDS (kBigLdsBytes).  Returns false when the depth limit's
+// heap sort would have to run on a segment too large for wave_sort_arrangement, or a list overflowed (flags |= 4: the
+// host entry point takes the cloud).
+__device__ bool big_sort_order(const unsigned long long* __restrict__ sk, const unsigned* __restrict__ sv,
+                               const unsigned long long* __restrict__ ik, const unsigned* __restrict__ iv, int m, int count,
+                               const BigArrays& A, unsigned off, unsigned* wave_sums, unsigned long long* lds) {
+  __shared__ ReplayShared sh;
+  const LdsReplaySizes sz(m, count);
+  if (sz.fits(count)) return big_sort_order_lds(sk, sv, iv, m, count, A.sorted_id + off, wave_sums, reinterpret_cast<char*>(lds), sz, sh);
+  const BigReplayLds r = carve_big_replay(lds);
+  return big_sort_order_hbm(sk, sv, ik, iv, m, count, A, off, r.items, r.scratch, sh);
 }
 
 // ---- kernel B1: compaction, centroid, items ------------------------------------------------------------------------
@@ -1024,15 +904,8 @@ __global__ __launch_bounds__(kThreads) void big_prepare_kernel(const float* __re
 __global__ __launch_bounds__(kThreads) void big_slice_kernel(const unsigned* __restrict__ bin_counts, int histogram_size,
                                                              float squared_jump, BigArrays A, unsigned char* __restrict__ c_bucket,
                                                              float* __restrict__ c_value, unsigned* __restrict__ flags) {
-  // dynamic LDS: the arrays of the small slices' replay (libstdcxx_sort_arrangement) for the rounds that fit; the exact
-  // sums' scratch lies over them (never in use at the same time)
+  // dynamic LDS (kBigLdsBytes): the replay's arrays; the exact sums' scratch lies over them (never in use at the same time)
   extern __shared__ __attribute__((aligned(16))) unsigned long long big_lds[];
-  unsigned long long* lds_a = big_lds;
-  unsigned short* u16_base = reinterpret_cast<unsigned short*>(lds_a + kMaxSlice);
-  constexpr int kU16 = kMaxSlice + 8;
-  const SortScratch lds_sc{u16_base, u16_base + kU16,
-                           reinterpret_cast<unsigned char*>(u16_base + 2 * kU16) + sizeof(Queue),
-                           reinterpret_cast<Queue*>(u16_base + 2 * kU16)};
   static_assert(sizeof(exact_sum::Scratch<2>) <= kBigLdsBytes, "the exact sums' scratch fits the replay's arrays");
   exact_sum::Scratch<2>& es = *reinterpret_cast<exact_sum::Scratch<2>*>(big_lds);
   __shared__ unsigned wave_sums[kThreads / 64];
@@ -1052,7 +925,7 @@ __global__ __launch_bounds__(kThreads) void big_slice_kernel(const unsigned* __r
   for (int b = 0; b < s.ordinal; ++b) sorted_at += A.valid[b];
   const unsigned long long* sk = A.key_out + sorted_at;
   const unsigned* sv = A.val_out + sorted_at;
-  if (!big_sort_order(sk, sv, A.key_in + off, A.val_in + off, m, static_cast<int>(s.count), A, off, wave_sums, lds_a, lds_sc)) {
+  if (!big_sort_order(sk, sv, A.key_in + off, A.val_in + off, m, static_cast<int>(s.count), A, off, wave_sums, big_lds)) {
     if (threadIdx.x == 0) atomicOr(flags, 4u);
     return;
   }
@@ -1325,14 +1198,8 @@ __global__ __launch_bounds__(kThreads) void big_slice_kernel(const unsigned* __r
 // dliom_diag_std_sort_order for more than kMaxSlice keys: the sorted (key, position) pairs come from the radix sort
 __global__ __launch_bounds__(kThreads) void big_sort_order_kernel(int n, BigArrays A, int* __restrict__ order, int* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long big_lds[];
-  unsigned long long* lds_a = big_lds;
-  unsigned short* u16_base = reinterpret_cast<unsigned short*>(lds_a + kMaxSlice);
-  constexpr int kU16 = kMaxSlice + 8;
-  const SortScratch lds_sc{u16_base, u16_base + kU16,
-                           reinterpret_cast<unsigned char*>(u16_base + 2 * kU16) + sizeof(Queue),
-                           reinterpret_cast<Queue*>(u16_base + 2 * kU16)};
   __shared__ unsigned wave_sums[kThreads / 64];
-  const bool ok = big_sort_order(A.key_out, A.val_out, A.key_in, A.val_in, n, n, A, 0u, wave_sums, lds_a, lds_sc);
+  const bool ok = big_sort_order(A.key_out, A.val_out, A.key_in, A.val_in, n, n, A, 0u, wave_sums, big_lds);
   int lo, hi;
   owned_range(n, &lo, &hi);
   if (ok)

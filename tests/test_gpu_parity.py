@@ -1695,6 +1695,26 @@ def test_device_std_sort_order_above_4096_keys(dl, ctx, orc):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [4097, 15391, 15392, 65535, 65537])
+def test_device_std_sort_order_at_the_lds_hbm_switch(dl, ctx, orc, n):
+    """big_sort_order's two variants run the same steps on different items, and the sizes where one hands over to the other
+    are where a step that reads the wrong item width shows.  With count == m and 150 KB of LDS the LDS variant needs
+    8 ceil((m + 1) / 2) + 16 ceil((m + 8) / 4) + 16 ceil((m + 8) / 16) + 8 (2 m / 17 + 64) + 32 bytes: 153 600 at
+    m = 15 391, the last size it takes, 153 608 at 15 392, the first in HBM.  4097: the first workgroup-wide partition sits
+    just above kCoopMin = 4096.  65 535 and 65 537: either side of the LDS variant's `count < 65536` guard and of a
+    16-bit id -- in HBM an item's id is its whole low word.  Against the real std::sort of this libstdc++: a handful of
+    tied pairs among distinct keys, runs of seven, and ties everywhere."""
+    rng = np.random.RandomState(n)
+    pairs = rng.permutation(n).astype(np.float32)  # distinct (exact below 2^24) ...
+    dup = rng.choice(n, 6, replace=False)
+    pairs[dup[:3]] = pairs[dup[3:]]  # ... but for three tied pairs
+    for kind, keys in enumerate([pairs, (np.arange(n) // 7).astype(np.float32), rng.randint(0, n // 3 + 1, n).astype(np.float32)]):
+        got = dl.diag_std_sort_order(ctx, keys)
+        want = orc.std_sort_order(keys)
+        assert np.array_equal(got, want), (n, kind, int((got != want).sum()))
+
+
+@pytest.mark.gpu
 def test_device_std_sort_order_on_paths_of_lopsided_partitions(dl, ctx, orc):
     """Descending keys in runs of ties make introsort partition lopsidedly: one segment queued per level on many paths,
     1 277 segments in all for 9 716 keys in tied pairs -- more than the 2 m / 17 + 64 the device's segment queue held
