@@ -141,6 +141,25 @@ class FamilyFactory {  // (NewCounterFamily is not used on this path)
 };
 }  // namespace metrics
 
+namespace common {
+// common::optional (common/optional.h), the part the adapters use; T is default-constructible here
+template <typename T>
+class optional {
+ public:
+  optional() : has_value_(false), value_() {}
+  optional(const T& value) : has_value_(true), value_(value) {}  // NOLINT: converting, like the reference's
+  bool has_value() const { return has_value_; }
+  const T& value() const {
+    if (!has_value_) Check(DLIOM_ERR_INVALID_ARGUMENT, "optional::value: CHECK(has_value())");
+    return value_;
+  }
+
+ private:
+  bool has_value_;
+  T value_;
+};
+}  // namespace common
+
 namespace transform {
 struct Vector3d {
   double v[3];
@@ -636,6 +655,10 @@ struct ImuData {
   int64_t time;
   double linear_acceleration[3];
   double angular_velocity[3];
+};
+struct FixedFramePoseData {  // sensor/fixed_frame_pose_data.h:32-35 (GPS): a sample may come without a pose
+  int64_t time;
+  common::optional<transform::Rigid3d> pose;
 };
 struct OdometryData {
   int64_t time;
@@ -1283,12 +1306,76 @@ struct OptimizationProblemOptions {  // proto/optimization_problem_options.proto
   bool use_nonmonotonic_steps = false;
   int max_num_iterations = 50;
   int num_threads = 1;
+  double fixed_frame_pose_translation_weight = 1e1;  // pose_graph.lua:81-82
+  double fixed_frame_pose_rotation_weight = 1e2;
+  // The fork's binary ignores its configurations' huber_scale (it builds TrivialLoss, optimization_problem_3d.cc:
+  // 335-338): 0 is that.  Upstream's behaviour is huber_scale > 0 (basic_config_3d.lua:108 sets 1e2, campus.lua:20
+  // 1e5): HuberLoss on the INTER_SUBMAP constraints.
+  double huber_scale = 0.;
 };
 struct LandmarkNode {};  // pose_graph_interface.h: landmarks are not covered, Solve refuses a non-empty map
+struct TrajectoryData {  // pose_graph_interface.h:76-80; the first two are stored and unused, as in the fork
+  double gravity_constant = 9.8;
+  std::array<double, 4> imu_calibration{{1., 0., 0., 0.}};
+  common::optional<transform::Rigid3d> fixed_frame_origin_in_map;
+};
 
-// OptimizationProblem3D (optimization_problem_3d.h:54-132, .cc:196-589) over dliom_pose_graph_solve.  MapById is a
-// std::map ordered like it (trajectory, index); Append continues a trajectory's indices.  AddOdometryData's use,
-// AddFixedFramePoseData and landmarks are not part of it (the fork's Solve has those terms commented out or unused).
+// The host arithmetic of the fixed-frame terms (optimization_problem_3d.cc:78-102, 491-548), as Eigen does it.
+namespace fixed_frame {
+inline std::array<double, 3> Rotate(const transform::Quaterniond& q, const double v[3]) {  // QuaternionBase::_transformVector
+  const double uv[3] = {2. * (q.y() * v[2] - q.z() * v[1]), 2. * (q.z() * v[0] - q.x() * v[2]), 2. * (q.x() * v[1] - q.y() * v[0])};
+  return {{v[0] + q.w() * uv[0] + (q.y() * uv[2] - q.z() * uv[1]), v[1] + q.w() * uv[1] + (q.z() * uv[0] - q.x() * uv[2]),
+           v[2] + q.w() * uv[2] + (q.x() * uv[1] - q.y() * uv[0])}};
+}
+inline transform::Rigid3d Inverse(const transform::Rigid3d& a) {  // Rigid3::inverse
+  const transform::Quaterniond q{{a.rotation().w(), -a.rotation().x(), -a.rotation().y(), -a.rotation().z()}};
+  const std::array<double, 3> t = Rotate(q, a.translation().v);
+  return transform::Rigid3d(transform::Vector3d{{-t[0], -t[1], -t[2]}}, q);
+}
+inline transform::Rigid3d Multiply(const transform::Rigid3d& a, const transform::Rigid3d& b) {  // operator*(Rigid3, Rigid3)
+  const std::array<double, 3> t = Rotate(a.rotation(), b.translation().v);
+  const transform::Quaterniond &p = a.rotation(), &q = b.rotation();
+  const double w = p.w() * q.w() - p.x() * q.x() - p.y() * q.y() - p.z() * q.z(), x = p.w() * q.x() + p.x() * q.w() + p.y() * q.z() - p.z() * q.y(),
+               y = p.w() * q.y() + p.y() * q.w() + p.z() * q.x() - p.x() * q.z(), z = p.w() * q.z() + p.z() * q.w() + p.x() * q.y() - p.y() * q.x();
+  const double norm = std::sqrt(w * w + x * x + y * y + z * z);
+  return transform::Rigid3d(transform::Vector3d{{t[0] + a.translation().v[0], t[1] + a.translation().v[1], t[2] + a.translation().v[2]}},
+                            transform::Quaterniond{{w / norm, x / norm, y / norm, z / norm}});
+}
+// Rigid3d(translation, AngleAxisd(GetYaw(rotation), UnitZ)) (:529-533, transform.h:43-47)
+inline transform::Rigid3d YawOnly(const transform::Rigid3d& a) {
+  const double unit_x[3] = {1., 0., 0.};
+  const std::array<double, 3> direction = Rotate(a.rotation(), unit_x);
+  const double yaw = std::atan2(direction[1], direction[0]);
+  return transform::Rigid3d(a.translation(), transform::Quaterniond{{std::cos(yaw / 2.), 0., 0., std::sin(yaw / 2.)}});
+}
+// transform::Interpolate (timestamped_transform.cc:23-39) with Eigen's slerp; times in ticks of 100 ns
+inline transform::Rigid3d Interpolate(int64_t start_time, const transform::Rigid3d& start, int64_t end_time, const transform::Rigid3d& end,
+                                      int64_t time) {
+  const double duration = static_cast<double>(end_time - start_time) / 1e7;
+  const double factor = static_cast<double>(time - start_time) / 1e7 / duration;
+  transform::Vector3d origin;
+  for (int k = 0; k < 3; ++k) origin.v[k] = start.translation().v[k] + (end.translation().v[k] - start.translation().v[k]) * factor;
+  const transform::Quaterniond &p = start.rotation(), &q = end.rotation();
+  const double d = p.w() * q.w() + p.x() * q.x() + p.y() * q.y() + p.z() * q.z(), abs_d = std::fabs(d);
+  double scale0 = 1. - factor, scale1 = factor;
+  if (!(abs_d >= 1. - 2.220446049250313e-16)) {
+    const double theta = std::acos(abs_d), sin_theta = std::sin(theta);
+    scale0 = std::sin((1. - factor) * theta) / sin_theta;
+    scale1 = std::sin(factor * theta) / sin_theta;
+  }
+  if (d < 0.) scale1 = -scale1;
+  transform::Quaterniond rotation;
+  for (int k = 0; k < 4; ++k) rotation.wxyz[k] = scale0 * p.wxyz[k] + scale1 * q.wxyz[k];
+  return transform::Rigid3d(origin, rotation);
+}
+}  // namespace fixed_frame
+
+// OptimizationProblem3D (optimization_problem_3d.h:54-132, .cc:196-589) over dliom_pose_graph_solve_terms.  MapById is a
+// std::map ordered like it (trajectory, index); Append continues a trajectory's indices; MapByTime is a std::map by time
+// a trajectory.  The IMU, odometry and local-SLAM terms are commented out in the fork's Solve (:350-489), so that data
+// is stored and unused.  The fixed-frame pose constraints (:491-548) are live code there and are built here; so is the
+// loss the fork left out (options.huber_scale).  Landmarks are not covered: a landmark residual couples two nodes, which
+// breaks the node elimination the device solve rests on; Solve refuses a non-empty landmark_nodes.
 class OptimizationProblem3D {
  public:
   struct Constraint {  // PoseGraphInterface::Constraint
@@ -1308,14 +1395,28 @@ class OptimizationProblem3D {
   OptimizationProblem3D& operator=(const OptimizationProblem3D&) = delete;
 
   void AddImuData(int trajectory_id, const sensor::ImuData& imu_data) { imu_data_[trajectory_id].push_back(imu_data); }  // stored, unused, as in the fork
+  void AddFixedFramePoseData(int trajectory_id, const sensor::FixedFramePoseData& fixed_frame_pose_data) {  // MapByTime::Append
+    std::map<int64_t, sensor::FixedFramePoseData>& trajectory = fixed_frame_pose_data_[trajectory_id];
+    if (!trajectory.empty() && !(fixed_frame_pose_data.time > trajectory.rbegin()->first))
+      Check(DLIOM_ERR_INVALID_ARGUMENT, "AddFixedFramePoseData: CHECK_GT(data.time, the last time)");
+    trajectory.emplace(fixed_frame_pose_data.time, fixed_frame_pose_data);
+  }
+  void SetTrajectoryData(int trajectory_id, const TrajectoryData& trajectory_data) { trajectory_data_[trajectory_id] = trajectory_data; }
   void AddTrajectoryNode(int trajectory_id, const NodeSpec3D& node_data) {
     node_data_.emplace(NodeId{trajectory_id, NextIndex(node_data_, NodeId{trajectory_id, 0}, &NodeId::node_index)}, node_data);
+    trajectory_data_[trajectory_id];
   }
   void InsertTrajectoryNode(const NodeId& node_id, const NodeSpec3D& node_data) {
     if (!node_data_.emplace(node_id, node_data).second) Check(DLIOM_ERR_INVALID_ARGUMENT, "InsertTrajectoryNode: the id exists");
+    trajectory_data_[node_id.trajectory_id];
   }
-  void TrimTrajectoryNode(const NodeId& node_id) {
-    if (node_data_.erase(node_id) != 1) Check(DLIOM_ERR_INVALID_ARGUMENT, "TrimTrajectoryNode: no such id");
+  void TrimTrajectoryNode(const NodeId& node_id) {  // :229-237
+    const auto node_it = node_data_.find(node_id);
+    if (node_it == node_data_.end()) Check(DLIOM_ERR_INVALID_ARGUMENT, "TrimTrajectoryNode: no such id");
+    TrimFixedFramePoseData(node_it);
+    node_data_.erase(node_it);
+    const auto rest = node_data_.lower_bound(NodeId{node_id.trajectory_id, 0});
+    if (rest == node_data_.end() || rest->first.trajectory_id != node_id.trajectory_id) trajectory_data_.erase(node_id.trajectory_id);
   }
   void AddSubmap(int trajectory_id, const transform::Rigid3d& global_submap_pose) {
     submap_data_.emplace(SubmapId{trajectory_id, NextIndex(submap_data_, SubmapId{trajectory_id, 0}, &SubmapId::submap_index)},
@@ -1364,21 +1465,59 @@ class OptimizationProblem3D {
       compact[i].translation_weight = constraints[i].pose.translation_weight;
       compact[i].rotation_weight = constraints[i].pose.rotation_weight;
     }
+    std::vector<unsigned char> inter_submap(constraints.size());
+    for (size_t i = 0; i < constraints.size(); ++i) inter_submap[i] = constraints[i].tag == Constraint::INTER_SUBMAP;
+    // :491-548: one block a trajectory that has fixed-frame data and at least one node that interpolates -- also on a
+    // frozen trajectory, which the fork does not skip here
+    std::vector<int> frame_trajectories;
+    std::vector<double> frame_poses;
+    std::vector<dliom_pose_graph_constraint> frame_constraints;
+    for (const auto& id_data : node_data_) {
+      const int trajectory_id = id_data.first.trajectory_id;
+      if (fixed_frame_pose_data_.count(trajectory_id) == 0) continue;
+      const std::unique_ptr<transform::Rigid3d> fixed_frame_pose = Interpolate(trajectory_id, id_data.second.time);
+      if (fixed_frame_pose == nullptr) continue;
+      if (frame_trajectories.empty() || frame_trajectories.back() != trajectory_id) {
+        const TrajectoryData& trajectory_data = trajectory_data_.at(trajectory_id);
+        const transform::Rigid3d fixed_frame_pose_in_map =
+            trajectory_data.fixed_frame_origin_in_map.has_value()
+                ? trajectory_data.fixed_frame_origin_in_map.value()
+                : fixed_frame::Multiply(id_data.second.global_pose, fixed_frame::Inverse(*fixed_frame_pose));
+        const std::array<double, 7> start = fixed_frame::YawOnly(fixed_frame_pose_in_map).ToArray();
+        frame_trajectories.push_back(trajectory_id);
+        frame_poses.insert(frame_poses.end(), start.begin(), start.end());
+      }
+      dliom_pose_graph_constraint c;
+      c.submap = static_cast<int32_t>(frame_trajectories.size()) - 1;
+      c.node = node_index.at(id_data.first);
+      const std::array<double, 7> zbar = fixed_frame_pose->ToArray();
+      for (int k = 0; k < 7; ++k) c.zbar[k] = zbar[k];
+      c.translation_weight = options_.fixed_frame_pose_translation_weight;
+      c.rotation_weight = options_.fixed_frame_pose_rotation_weight;
+      frame_constraints.push_back(c);
+    }
+    const dliom_pose_graph_terms terms = {static_cast<int>(frame_trajectories.size()), frame_poses.data(),
+                                          static_cast<int64_t>(frame_constraints.size()), frame_constraints.data(),
+                                          options_.huber_scale, inter_submap.data()};
     const dliom_pose_graph_options options = {options_.fix_z_in_3d ? 1 : 0, options_.use_nonmonotonic_steps ? 1 : 0,
                                               options_.max_num_iterations, options_.num_threads};
-    Check(dliom_pose_graph_solve(context_->get(), &options, static_cast<int>(submap_index.size()), submap_poses.data(),
-                                 submap_constant.data(), 0, static_cast<int>(node_index.size()), node_poses.data(),
-                                 node_constant.data(), static_cast<int64_t>(compact.size()), compact.data(), &summary_),
-          "dliom_pose_graph_solve");
+    Check(dliom_pose_graph_solve_terms(context_->get(), &options, static_cast<int>(submap_index.size()), submap_poses.data(),
+                                       submap_constant.data(), 0, static_cast<int>(node_index.size()), node_poses.data(),
+                                       node_constant.data(), static_cast<int64_t>(compact.size()), compact.data(), &terms, &summary_),
+          "dliom_pose_graph_solve_terms");
     size_t at = 0;  // :578-588: store the result
     for (auto& id_data : submap_data_) id_data.second.global_pose = transform::Rigid3d::FromArray(&submap_poses[7 * at++]);
     at = 0;
     for (auto& id_data : node_data_) id_data.second.global_pose = transform::Rigid3d::FromArray(&node_poses[7 * at++]);
+    for (size_t f = 0; f < frame_trajectories.size(); ++f)
+      trajectory_data_.at(frame_trajectories[f]).fixed_frame_origin_in_map = transform::Rigid3d::FromArray(&frame_poses[7 * f]);
   }
 
   const std::map<NodeId, NodeSpec3D>& node_data() const { return node_data_; }
   const std::map<SubmapId, SubmapSpec3D>& submap_data() const { return submap_data_; }
   const std::map<int, std::vector<sensor::ImuData>>& imu_data() const { return imu_data_; }
+  const std::map<int, std::map<int64_t, sensor::FixedFramePoseData>>& fixed_frame_pose_data() const { return fixed_frame_pose_data_; }
+  const std::map<int, TrajectoryData>& trajectory_data() const { return trajectory_data_; }
   const dliom_pose_graph_summary& summary() const { return summary_; }  // of the last Solve (ceres::Solver::Summary there)
 
  private:
@@ -1390,8 +1529,49 @@ class OptimizationProblem3D {
     return it->first.trajectory_id == first_of_trajectory.trajectory_id ? it->first.*index + 1 : 0;
   }
 
+  // :78-102: the fixed-frame pose at `time`, between the samples around it if both have a pose
+  std::unique_ptr<transform::Rigid3d> Interpolate(int trajectory_id, int64_t time) const {
+    const std::map<int64_t, sensor::FixedFramePoseData>& trajectory = fixed_frame_pose_data_.at(trajectory_id);
+    const auto it = trajectory.lower_bound(time);
+    if (it == trajectory.end() || !it->second.pose.has_value()) return nullptr;
+    if (it == trajectory.begin()) {
+      if (it->second.time == time) return std::unique_ptr<transform::Rigid3d>(new transform::Rigid3d(it->second.pose.value()));
+      return nullptr;
+    }
+    const auto prev_it = std::prev(it);
+    if (!prev_it->second.pose.has_value()) return nullptr;
+    return std::unique_ptr<transform::Rigid3d>(new transform::Rigid3d(
+        fixed_frame::Interpolate(prev_it->second.time, prev_it->second.pose.value(), it->second.time, it->second.pose.value(), time)));
+  }
+  // sensor::MapByTime::Trim (map_by_time.h:48-97): the data between the trimmed node's neighbours goes, but for the
+  // first and the last of it, which interpolation with the data outside still needs
+  void TrimFixedFramePoseData(std::map<NodeId, NodeSpec3D>::const_iterator node_it) {
+    const int trajectory_id = node_it->first.trajectory_id;
+    const auto found = fixed_frame_pose_data_.find(trajectory_id);
+    if (found == fixed_frame_pose_data_.end()) return;
+    const bool has_previous = node_it != node_data_.begin() && std::prev(node_it)->first.trajectory_id == trajectory_id;
+    const auto next_it = std::next(node_it);
+    const bool has_next = next_it != node_data_.end() && next_it->first.trajectory_id == trajectory_id;
+    const int64_t gap_start = has_previous ? std::prev(node_it)->second.time : INT64_MIN;
+    const int64_t gap_end = has_next ? next_it->second.time : INT64_MAX;
+    if (!(gap_start < gap_end)) Check(DLIOM_ERR_INVALID_ARGUMENT, "TrimTrajectoryNode: CHECK_LT(gap_start, gap_end)");
+    std::map<int64_t, sensor::FixedFramePoseData>& trajectory = found->second;
+    auto data_it = trajectory.lower_bound(gap_start);
+    auto data_end = trajectory.upper_bound(gap_end);
+    if (data_it == data_end) return;
+    if (has_next) {
+      data_end = std::prev(data_end);
+      if (data_it == data_end) return;
+    }
+    if (has_previous) data_it = std::next(data_it);
+    while (data_it != data_end) data_it = trajectory.erase(data_it);
+    if (trajectory.empty()) fixed_frame_pose_data_.erase(found);
+  }
+
   Context* context_;
   OptimizationProblemOptions options_;
+  std::map<int, std::map<int64_t, sensor::FixedFramePoseData>> fixed_frame_pose_data_;
+  std::map<int, TrajectoryData> trajectory_data_;
   std::map<NodeId, NodeSpec3D> node_data_;
   std::map<SubmapId, SubmapSpec3D> submap_data_;
   std::map<int, std::vector<sensor::ImuData>> imu_data_;

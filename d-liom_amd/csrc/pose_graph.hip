@@ -1,10 +1,13 @@
 // OptimizationProblem3D::Solve on the device (mapping/internal/optimization/optimization_problem_3d.cc:259-589 as this
-// fork runs it: SpaCostFunction3D only, see include/dliom.h "pose graph optimisation").
+// fork runs it: SpaCostFunction3D only, see include/dliom.h "pose graph optimisation"), with the fixed-frame pose
+// constraints (:491-548) and upstream's HuberLoss on the inter-submap constraints (dliom_pose_graph_terms).
 //
-// Every constraint couples one submap pose with one node pose, so with the nodes eliminated (their Hessian is
-// block-diagonal 6x6) a dense system over the submaps' columns is left.  One trust-region iteration is a chain of
-// kernel launches -- stage boundaries are launches, nothing waits on another workgroup -- and ONE polled read-back:
-//   linearise        per constraint: residual and tangent-space Jacobians by forward duals (pg_linearise_kernel);
+// Every constraint couples one kept pose -- a submap or a fixed frame -- with one node pose, so with the nodes eliminated
+// (their Hessian is block-diagonal 6x6) a dense system over the kept blocks' columns is left.  One trust-region iteration
+// is a chain of kernel launches -- stage boundaries are launches, nothing waits on another workgroup -- and ONE polled
+// read-back:
+//   linearise        per constraint: residual and tangent-space Jacobians by forward duals, corrected for the loss
+//                    (pg_linearise_kernel);
 //                    per pose: diagonal block, gradient, column scaling (pg_pose_kernel, pg_pose_values_kernel)
 //   eliminate        per node: V = (H_nn + D^2)^-1 and the constraints' W V (pg_node_kernel); per block pair
 //                    S_ab = [a == b](H_ss + D^2) - sum W V W^T over its sorted list (pg_pairs_kernel); right-hand side
@@ -166,9 +169,15 @@ __device__ inline void spa_residual(const Dual<N> qi[4], const Dual<N> ti[3], co
 // ---- local parameterisations ------------------------------------------------------------------------------------------
 // d Plus / d delta at 0 of the rotation block, 4 x 3 row-major: QuaternionParameterization (ceres/local_parameterization.cc)
 // or, gravity-aligned, the two columns of ConstantYawQuaternionPlus (rotation_parameterization.h:41-62: x (x) [1, d0, d1, 0]
-// to first order; its 1e-6 branch makes the autodiff Jacobian exactly that)
-__device__ inline void plus_jacobian(const double* q, bool gravity_aligned, double* j) {
-  if (gravity_aligned) {
+// to first order; its 1e-6 branch makes the autodiff Jacobian exactly that), or, for a fixed frame, the one column of
+// YawOnlyQuaternionPlus (:27-39: [sqrt(1 - d^2), 0, 0, d] (x) x; the square root's derivative vanishes at 0)
+__device__ inline void plus_jacobian(const double* q, int kind, double* j) {
+  if (kind == pg::kKindYawOnly) {
+    j[0] = -q[3]; j[1] = 0.; j[2] = 0.;
+    j[3] = -q[2]; j[4] = 0.; j[5] = 0.;
+    j[6] = q[1];  j[7] = 0.; j[8] = 0.;
+    j[9] = q[0];  j[10] = 0.; j[11] = 0.;
+  } else if (kind == pg::kKindConstantYaw) {
     j[0] = -q[1]; j[1] = -q[2]; j[2] = 0.;
     j[3] = q[0];  j[4] = -q[3]; j[5] = 0.;
     j[6] = q[3];  j[7] = q[0];  j[8] = 0.;
@@ -187,12 +196,19 @@ __device__ inline void hamilton(const double* z, const double* w, double* zw) { 
   zw[3] = z[0] * w[3] + z[1] * w[2] - z[2] * w[1] + z[3] * w[0];
 }
 // Plus of a pose's blocks on the slots of `mask`; a block outside the problem keeps its bits.
-__device__ inline void pose_plus(const double* x, const double* delta, int mask, bool gravity_aligned, double* out) {
+__device__ inline void pose_plus(const double* x, const double* delta, int mask, int kind, double* out) {
   for (int k = 0; k < 3; ++k) out[k] = (mask >> k) & 1 ? x[k] + delta[k] : x[k];
   for (int k = 3; k < 7; ++k) out[k] = x[k];
   if ((mask & 56) == 0) return;
   double q_delta[4];
-  if (gravity_aligned) {
+  if (kind == pg::kKindYawOnly) {
+    const double clamped = delta[3] > 0.5 ? 0.5 : (delta[3] < -0.5 ? -0.5 : delta[3]);  // common::Clamp
+    q_delta[0] = sqrt(1. - clamped * clamped);
+    q_delta[1] = 0.;
+    q_delta[2] = 0.;
+    q_delta[3] = clamped;
+    hamilton(q_delta, x + 3, out + 3);
+  } else if (kind == pg::kKindConstantYaw) {
     const double norm = sqrt(delta[3] * delta[3] + delta[4] * delta[4]);
     const double sin_over = norm < 1e-6 ? 1. : sin(norm) / norm;
     q_delta[0] = norm < 1e-6 ? 1. : cos(norm);
@@ -213,16 +229,33 @@ __device__ inline void pose_plus(const double* x, const double* delta, int mask,
   }
 }
 
+// ---- the loss ----------------------------------------------------------------------------------------------------------
+// ceres::HuberLoss(a) at s = ||r||^2 (loss_function.cc) with Corrector (corrector.cc) for rho'' <= 0, where it is a pure
+// scaling of residual and Jacobian by sqrt(rho'): returns rho and sets *scaling.  Inside the quadratic region rho = s and
+// the scaling is exactly 1, as under TrivialLoss.
+__device__ inline double huber(double a, double s, double* scaling) {
+  const double b = a * a;
+  *scaling = 1.;
+  if (!(s > b)) return s;
+  const double r = sqrt(s);
+  *scaling = sqrt(fmax(DBL_MIN, a / r));
+  return 2. * a * r - b;
+}
+
 // ---- what the kernels share --------------------------------------------------------------------------------------------
 struct Graph {
-  int num_submaps, num_nodes, num_constraints, num_pairs, gravity_aligned;
+  // kept blocks: the submaps, then the fixed frames; constraints: the submaps', then the fixed frames'
+  int num_kept, num_nodes, num_constraints, num_pairs;
   int n, np;  // reduced dimension and its padded size (the leading dimension of S)
+  double huber_scale;  // 0: TrivialLoss everywhere
   // structure (one packed upload)
   const double* constraint_data;  // 9 a constraint: zbar, translation weight, rotation weight
   const int *constraint_submap, *constraint_node, *mask, *column, *fixed, *pose_start, *pose_constraints;
+  const int* kind;   // per kept block: its rotation's parameterisation (pg::kKind*)
+  const int* lossy;  // per constraint: non-zero = under HuberLoss(huber_scale); null when huber_scale is 0
   const int *pair_a, *pair_b, *pair_start, *pair_c, *pair_c2;
   // state
-  double *x, *candidate;                  // 7 a pose, submaps first
+  double *x, *candidate;                  // 7 a pose: kept blocks, then nodes
   double *scale, *diagonal_block, *gradient;  // 6, 36, 6 a pose (unscaled)
   double *residual, *jacobian;            // 6, 72 a constraint ([6 x 6 submap | 6 x 6 node], unscaled, masked)
   double *cross, *cross_v, *cross_vg;     // 36, 36, 6 a constraint: E = Js^T Jn (scaled), E V, E V g_n
@@ -234,9 +267,17 @@ struct Graph {
   unsigned* flag;                         // non-zero: a non-positive pivot; later stages return at once
 };
 
+__device__ inline int kind_of(const Graph& g, int p) { return p < g.num_kept ? g.kind[p] : pg::kKindQuaternion; }
+// 1/2 rho(s) of constraint c and the corrector's scaling
+__device__ inline double constraint_cost(const Graph& g, int c, double squared, double* scaling) {
+  *scaling = 1.;
+  if (g.huber_scale > 0. && g.lossy[c] != 0) return 0.5 * huber(g.huber_scale, squared, scaling);
+  return 0.5 * squared;
+}
+
 template <int N>
 __device__ inline void evaluate_constraint(const Graph& g, const double* poses, int c, Dual<N> e[6]) {
-  const int a = g.constraint_submap[c], n = g.num_submaps + g.constraint_node[c];
+  const int a = g.constraint_submap[c], n = g.num_kept + g.constraint_node[c];
   const double* xa = poses + 7 * a;
   const double* xn = poses + 7 * n;
   Dual<N> ti[3], qi[4], tj[3], qj[4];
@@ -246,8 +287,8 @@ __device__ inline void evaluate_constraint(const Graph& g, const double* poses, 
     // seeded with the tangent directions: the duals' parts are the tangent-space Jacobian's columns
     const int ma = g.mask[a], mn = g.mask[n];
     double ja[12], jn[12];
-    plus_jacobian(xa + 3, a == g.gravity_aligned, ja);
-    plus_jacobian(xn + 3, false, jn);
+    plus_jacobian(xa + 3, g.kind[a], ja);
+    plus_jacobian(xn + 3, pg::kKindQuaternion, jn);
     for (int k = 0; k < 3; ++k) {
       if ((ma >> k) & 1) ti[k].v[k] = 1.;
       if ((mn >> k) & 1) tj[k].v[6 + k] = 1.;
@@ -267,17 +308,18 @@ __global__ void __launch_bounds__(64) pg_linearise_kernel(Graph g) {
   if (c >= g.num_constraints) return;
   Dual<12> e[6];
   evaluate_constraint<12>(g, g.x, c, e);
-  double squared = 0.;
+  double squared = 0., scaling;
+  for (int k = 0; k < 6; ++k) squared += e[k].a * e[k].a;
+  g.cost[c] = constraint_cost(g, c, squared, &scaling);
+  // the corrected residual and Jacobian (a scaling of exactly 1 leaves the bits alone)
   for (int k = 0; k < 6; ++k) {
-    g.residual[6 * static_cast<int64_t>(c) + k] = e[k].a;
-    squared += e[k].a * e[k].a;
+    g.residual[6 * static_cast<int64_t>(c) + k] = e[k].a * scaling;
     double* row = g.jacobian + 72 * static_cast<int64_t>(c);
     for (int i = 0; i < 6; ++i) {
-      row[k * 6 + i] = e[k].v[i];
-      row[36 + k * 6 + i] = e[k].v[6 + i];
+      row[k * 6 + i] = e[k].v[i] * scaling;
+      row[36 + k * 6 + i] = e[k].v[6 + i] * scaling;
     }
   }
-  g.cost[c] = 0.5 * squared;
 }
 
 // One wavefront a pose: lanes 0..35 the diagonal block J^T J, lanes 36..41 the gradient J^T r, over the pose's
@@ -285,8 +327,8 @@ __global__ void __launch_bounds__(64) pg_linearise_kernel(Graph g) {
 __global__ void __launch_bounds__(256) pg_pose_kernel(Graph g, int set_scale) {
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (p >= g.num_submaps + g.num_nodes || lane >= 42) return;
-  const int side = p < g.num_submaps ? 0 : 36;
+  if (p >= g.num_kept + g.num_nodes || lane >= 42) return;
+  const int side = p < g.num_kept ? 0 : 36;
   const int i = lane < 36 ? lane / 6 : lane - 36, j = lane < 36 ? lane % 6 : 0;
   double sum = 0.;
   for (int at = g.pose_start[p]; at < g.pose_start[p + 1]; ++at) {
@@ -309,12 +351,12 @@ __global__ void __launch_bounds__(256) pg_pose_kernel(Graph g, int set_scale) {
 // Per pose: max |Plus(x, -gradient) - x| and ||x||^2 over the blocks in the problem.
 __global__ void pg_pose_values_kernel(Graph g) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= g.num_submaps + g.num_nodes) return;
+  if (p >= g.num_kept + g.num_nodes) return;
   const int mask = g.mask[p];
   const double* x = g.x + 7 * static_cast<int64_t>(p);
   double negative[6], projected[7];
   for (int k = 0; k < 6; ++k) negative[k] = -g.gradient[6 * static_cast<int64_t>(p) + k];
-  pose_plus(x, negative, mask, p == g.gravity_aligned, projected);
+  pose_plus(x, negative, mask, kind_of(g, p), projected);
   double most = 0., squared = 0.;
   if (mask & 7)
     for (int k = 0; k < 3; ++k) most = fmax(most, fabs(x[k] - projected[k])), squared += x[k] * x[k];
@@ -334,7 +376,7 @@ __device__ inline double lm_diagonal(double scaled_diagonal, double radius) {
 __global__ void __launch_bounds__(64) pg_node_kernel(Graph g, double radius) {
   const int node = blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= g.num_nodes) return;
-  const int p = g.num_submaps + node;
+  const int p = g.num_kept + node;
   const int mask = g.mask[p];
   double v[36], vg[6], sn[6];
   for (int k = 0; k < 36; ++k) v[k] = 0.;
@@ -452,7 +494,7 @@ __global__ void __launch_bounds__(256) pg_zero_lower_kernel(Graph g) {
 __global__ void pg_rhs_kernel(Graph g) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < g.np - g.n) g.s[static_cast<int64_t>(g.n + t) * g.np + g.n + t] = 1.;
-  if (t >= g.num_submaps * 6) return;
+  if (t >= g.num_kept * 6) return;
   const int a = t / 6, i = t % 6;
   const int row = g.column[t];
   if (row < 0) return;
@@ -622,11 +664,11 @@ __global__ void __launch_bounds__(kSmallThreads) pg_small_kernel(Graph g) {
 // the candidate, ||x - candidate||^2 over the blocks in the problem.
 __global__ void pg_step_kernel(Graph g) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= g.num_submaps + g.num_nodes || *g.flag != 0u) return;
+  if (p >= g.num_kept + g.num_nodes || *g.flag != 0u) return;
   const int mask = g.mask[p];
   const double* scale = g.scale + 6 * static_cast<int64_t>(p);
   double y[6];
-  if (p < g.num_submaps) {
+  if (p < g.num_kept) {
     for (int k = 0; k < 6; ++k) y[k] = g.column[p * 6 + k] >= 0 ? g.rhs[g.column[p * 6 + k]] : 0.;
   } else {
     double w[6];
@@ -642,7 +684,7 @@ __global__ void pg_step_kernel(Graph g) {
         for (int k = 0; k < 6; ++k) w[k] += e[i * 6 + k] * ys;
       }
     }
-    const double* v = g.v + 36 * static_cast<int64_t>(p - g.num_submaps);
+    const double* v = g.v + 36 * static_cast<int64_t>(p - g.num_kept);
     for (int i = 0; i < 6; ++i) {
       double t = 0.;
       for (int k = 0; k < 6; ++k) t += v[i * 6 + k] * w[k];
@@ -657,7 +699,7 @@ __global__ void pg_step_kernel(Graph g) {
     g.delta[6 * static_cast<int64_t>(p) + k] = delta[k];
   }
   const double* x = g.x + 7 * static_cast<int64_t>(p);
-  pose_plus(x, delta, mask, p == g.gravity_aligned, out);
+  pose_plus(x, delta, mask, kind_of(g, p), out);
   double squared = 0.;
   for (int k = 0; k < 7; ++k) {
     g.candidate[7 * static_cast<int64_t>(p) + k] = out[k];
@@ -670,7 +712,7 @@ __global__ void __launch_bounds__(256) pg_candidate_kernel(Graph g) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= g.num_constraints || *g.flag != 0u) return;
   const double* da = g.delta + 6 * static_cast<int64_t>(g.constraint_submap[c]);
-  const double* dn = g.delta + 6 * static_cast<int64_t>(g.num_submaps + g.constraint_node[c]);
+  const double* dn = g.delta + 6 * static_cast<int64_t>(g.num_kept + g.constraint_node[c]);
   const double* jac = g.jacobian + 72 * static_cast<int64_t>(c);
   double model = 0.;
   for (int k = 0; k < 6; ++k) {
@@ -682,9 +724,9 @@ __global__ void __launch_bounds__(256) pg_candidate_kernel(Graph g) {
   g.model[c] = model;
   Dual<0> e[6];
   evaluate_constraint<0>(g, g.candidate, c, e);
-  double squared = 0.;
+  double squared = 0., scaling;
   for (int k = 0; k < 6; ++k) squared += e[k].a * e[k].a;
-  g.candidate_cost[c] = 0.5 * squared;
+  g.candidate_cost[c] = constraint_cost(g, c, squared, &scaling);
 }
 
 // The sums of an iteration in a fixed order (thread t takes elements t, t + 1024, ...; then a tree), into the
@@ -703,7 +745,7 @@ __device__ inline double block_sum(double mine, double* scratch, bool maximum) {
 __global__ void __launch_bounds__(kSmallThreads) pg_reduce_kernel(Graph g, int with_step, double* out, unsigned* done_word, unsigned done_seq) {
   __shared__ double scratch[kSmallThreads];
   const int tid = threadIdx.x;
-  const int poses = g.num_submaps + g.num_nodes;
+  const int poses = g.num_kept + g.num_nodes;
   const bool step = with_step != 0 && *g.flag == 0u;
   double cost = 0., fixed = 0., most = 0., x_squared = 0., model = 0., candidate = 0., step_squared = 0.;
   for (int c = tid; c < g.num_constraints; c += kSmallThreads) {
@@ -773,50 +815,69 @@ bool all_finite(const double* v, int64_t n) {
 int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, const double* submap_poses7,
             const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes, const double* node_poses7,
             const unsigned char* node_constant, int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
-            Solver* solver) {
+            const dliom_pose_graph_terms* terms, Solver* solver) {
+  static const dliom_pose_graph_terms kNoTerms = {0, nullptr, 0, nullptr, 0., nullptr};
+  if (terms == nullptr) terms = &kNoTerms;
+  const int num_frames = terms->num_fixed_frames;
+  const int64_t num_frame_constraints = terms->num_fixed_frame_constraints;
+  const dliom_pose_graph_constraint* frame_constraints = terms->fixed_frame_constraints;
+  if (num_frames < 0 || num_frame_constraints < 0 || (num_frames > 0 && terms->fixed_frame_poses7 == nullptr) ||
+      (num_frame_constraints > 0 && frame_constraints == nullptr) || !(terms->huber_scale >= 0.) || !std::isfinite(terms->huber_scale))
+    return DLIOM_ERR_INVALID_ARGUMENT;
   if (ctx == nullptr || options == nullptr || num_submaps < 0 || num_nodes < 0 || num_constraints < 0 ||
       (num_submaps > 0 && submap_poses7 == nullptr) || (num_nodes > 0 && node_poses7 == nullptr) ||
       (num_constraints > 0 && constraints == nullptr) || gravity_aligned_submap < -1 || gravity_aligned_submap >= num_submaps)
     return DLIOM_ERR_INVALID_ARGUMENT;
-  if (static_cast<int64_t>(num_submaps) + num_nodes > INT32_MAX / 72) return DLIOM_ERR_TOO_LARGE;
+  if (static_cast<int64_t>(num_submaps) + num_frames + num_nodes > INT32_MAX / 72) return DLIOM_ERR_TOO_LARGE;
   solver->ctx = ctx;
   pg::Structure& s = solver->structure;
   constexpr int64_t stride = sizeof(dliom_pose_graph_constraint) / sizeof(int32_t);
   static_assert(sizeof(dliom_pose_graph_constraint) % sizeof(int32_t) == 0, "the constraints are read with an int32 stride");
   const int32_t* first = reinterpret_cast<const int32_t*>(constraints);
-  const int status = pg::build_structure(num_submaps, submap_constant, gravity_aligned_submap, num_nodes, node_constant,
-                                         num_constraints, first, first + 1, stride, options->fix_z_in_3d != 0,
-                                         DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION, &s);
+  const int32_t* frame_first = reinterpret_cast<const int32_t*>(frame_constraints);
+  const int status = pg::build_structure_terms(num_submaps, submap_constant, gravity_aligned_submap, num_frames, num_nodes,
+                                               node_constant, num_constraints, first, first + 1, stride, num_frame_constraints,
+                                               frame_first, frame_first + 1, stride, options->fix_z_in_3d != 0,
+                                               DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION, &s);
   if (status == pg::kStructureBadIndex) return DLIOM_ERR_INVALID_ARGUMENT;
   if (status == pg::kStructureTooLarge) return DLIOM_ERR_TOO_LARGE;
   if (!all_finite(submap_poses7, 7 * static_cast<int64_t>(num_submaps)) || !all_finite(node_poses7, 7 * static_cast<int64_t>(num_nodes)))
     return DLIOM_ERR_SOLVER;
-  for (int64_t c = 0; c < num_constraints; ++c)
-    if (!all_finite(constraints[c].zbar, 7) || !std::isfinite(constraints[c].translation_weight) || !std::isfinite(constraints[c].rotation_weight))
+  if (!all_finite(terms->fixed_frame_poses7, 7 * static_cast<int64_t>(num_frames))) return DLIOM_ERR_SOLVER;
+  // residual block c: the constraints, then the fixed frames'
+  const int64_t C = num_constraints + num_frame_constraints;
+  auto block = [&](int64_t c) -> const dliom_pose_graph_constraint& {
+    return c < num_constraints ? constraints[c] : frame_constraints[c - num_constraints];
+  };
+  for (int64_t c = 0; c < C; ++c)
+    if (!all_finite(block(c).zbar, 7) || !std::isfinite(block(c).translation_weight) || !std::isfinite(block(c).rotation_weight))
       return DLIOM_ERR_SOLVER;
+  // fixed-frame constraints never carry a loss (optimization_problem_3d.cc:541-546)
+  const bool with_loss = terms->huber_scale > 0. && terms->inter_submap != nullptr;
 
   Graph& g = solver->g;
-  const int64_t poses = static_cast<int64_t>(num_submaps) + num_nodes, C = num_constraints;
-  g.num_submaps = num_submaps;
+  const int64_t kept = static_cast<int64_t>(num_submaps) + num_frames, poses = kept + num_nodes;
+  g.num_kept = static_cast<int>(kept);
+  g.huber_scale = with_loss ? terms->huber_scale : 0.;
   g.num_nodes = num_nodes;
   g.num_constraints = static_cast<int>(C);
   g.num_pairs = static_cast<int>(s.pair_a.size());
-  g.gravity_aligned = gravity_aligned_submap;
   g.n = s.reduced_dimension;
   g.np = std::max(kPanel, (g.n + kPanel - 1) / kPanel * kPanel);
   // one host buffer, one copy: [constraint data | poses | int arrays] (a vector of doubles; the ints ride in its tail)
-  const size_t num_ints = 2 * static_cast<size_t>(C) + s.mask.size() + s.column.size() + s.fixed.size() + s.pose_start.size() +
+  const size_t num_ints = (with_loss ? 3 : 2) * static_cast<size_t>(C) + s.kind.size() + s.mask.size() + s.column.size() + s.fixed.size() + s.pose_start.size() +
                           s.pose_constraints.size() + s.pair_a.size() + s.pair_b.size() + s.pair_start.size() + s.pair_c.size() +
                           s.pair_c2.size() + 1;
   const size_t upload_doubles = static_cast<size_t>(9 * C + 7 * poses);
   std::vector<double> host(upload_doubles + (num_ints + 1) / 2);
   for (int64_t c = 0; c < C; ++c) {
-    std::memcpy(&host[9 * c], constraints[c].zbar, 7 * sizeof(double));
-    host[9 * c + 7] = constraints[c].translation_weight;
-    host[9 * c + 8] = constraints[c].rotation_weight;
+    std::memcpy(&host[9 * c], block(c).zbar, 7 * sizeof(double));
+    host[9 * c + 7] = block(c).translation_weight;
+    host[9 * c + 8] = block(c).rotation_weight;
   }
   if (num_submaps > 0) std::memcpy(&host[9 * C], submap_poses7, sizeof(double) * 7 * num_submaps);
-  if (num_nodes > 0) std::memcpy(&host[9 * C + 7 * static_cast<int64_t>(num_submaps)], node_poses7, sizeof(double) * 7 * num_nodes);
+  if (num_frames > 0) std::memcpy(&host[9 * C + 7 * static_cast<int64_t>(num_submaps)], terms->fixed_frame_poses7, sizeof(double) * 7 * num_frames);
+  if (num_nodes > 0) std::memcpy(&host[9 * C + 7 * kept], node_poses7, sizeof(double) * 7 * num_nodes);
   int32_t* host_ints = reinterpret_cast<int32_t*>(host.data() + upload_doubles);
   size_t ints_used = 0;
   auto append = [&](const std::vector<int32_t>& v) {
@@ -826,9 +887,13 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
     return at;
   };
   const size_t at_submap = ints_used;
-  for (int64_t c = 0; c < C; ++c) host_ints[ints_used++] = constraints[c].submap;
+  for (int64_t c = 0; c < C; ++c) host_ints[ints_used++] = c < num_constraints ? block(c).submap : num_submaps + block(c).submap;
   const size_t at_node = ints_used;
-  for (int64_t c = 0; c < C; ++c) host_ints[ints_used++] = constraints[c].node;
+  for (int64_t c = 0; c < C; ++c) host_ints[ints_used++] = block(c).node;
+  const size_t at_lossy = ints_used;
+  if (with_loss)
+    for (int64_t c = 0; c < C; ++c) host_ints[ints_used++] = c < num_constraints && terms->inter_submap[c] != 0 ? 1 : 0;
+  const size_t at_kind = append(s.kind);
   const size_t at_mask = append(s.mask), at_column = append(s.column), at_fixed = append(s.fixed), at_start = append(s.pose_start),
                at_list = append(s.pose_constraints), at_a = append(s.pair_a), at_b = append(s.pair_b),
                at_pair_start = append(s.pair_start), at_c = append(s.pair_c), at_c2 = append(s.pair_c2);
@@ -883,6 +948,8 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   g.s = d + o_s;
   g.constraint_submap = ints + at_submap;
   g.constraint_node = ints + at_node;
+  g.kind = ints + at_kind;
+  g.lossy = with_loss ? ints + at_lossy : nullptr;
   g.mask = ints + at_mask;
   g.column = ints + at_column;
   g.fixed = ints + at_fixed;
@@ -900,7 +967,7 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
 int enqueue_linearise(Solver* solver, bool set_scale) {
   const Graph& g = solver->g;
   hipStream_t stream = solver->ctx->stream;
-  const int poses = g.num_submaps + g.num_nodes;
+  const int poses = g.num_kept + g.num_nodes;
   DLIOM_TRY(solver->begin_stage());
   if (g.num_constraints > 0) hipLaunchKernelGGL(pg_linearise_kernel, dim3(blocks_of(g.num_constraints, 64)), dim3(64), 0, stream, g);
   if (poses > 0) {
@@ -914,14 +981,14 @@ int enqueue_linearise(Solver* solver, bool set_scale) {
 int enqueue_step(Solver* solver, double radius) {
   const Graph& g = solver->g;
   hipStream_t stream = solver->ctx->stream;
-  const int poses = g.num_submaps + g.num_nodes;
+  const int poses = g.num_kept + g.num_nodes;
   DLIOM_TRY(solver->begin_stage());
   DLIOM_HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(unsigned), stream));
   DLIOM_HIP_TRY(hipMemsetAsync(g.rhs, 0, static_cast<size_t>(g.np) * sizeof(double), stream));
   hipLaunchKernelGGL(pg_zero_lower_kernel, dim3(g.np / kPanel, g.np / kPanel), dim3(256), 0, stream, g);
   if (g.num_nodes > 0) hipLaunchKernelGGL(pg_node_kernel, dim3(blocks_of(g.num_nodes, 64)), dim3(64), 0, stream, g, radius);
   if (g.num_pairs > 0) hipLaunchKernelGGL(pg_pairs_kernel, dim3(blocks_of(g.num_pairs, 4)), dim3(256), 0, stream, g, radius);
-  hipLaunchKernelGGL(pg_rhs_kernel, dim3(blocks_of(std::max(g.num_submaps * 6, g.np), 256)), dim3(256), 0, stream, g);
+  hipLaunchKernelGGL(pg_rhs_kernel, dim3(blocks_of(std::max(g.num_kept * 6, g.np), 256)), dim3(256), 0, stream, g);
   DLIOM_HIP_TRY(hipGetLastError());
   DLIOM_TRY(solver->end_stage(1));
   DLIOM_TRY(solver->begin_stage());
@@ -967,6 +1034,17 @@ int read_sums(Solver* solver, bool with_step, double sums[kSums]) {
   return DLIOM_OK;
 }
 
+// `width` doubles a pose from the device's order (submaps, fixed frames, nodes) into the caller's three arrays; enqueued.
+int copy_poses_out(Solver* solver, const double* device, int width, int num_submaps, int num_nodes, double* submaps, double* nodes,
+                   double* frames) {
+  hipStream_t stream = solver->ctx->stream;
+  const size_t S = static_cast<size_t>(num_submaps), K = static_cast<size_t>(solver->g.num_kept), bytes = sizeof(double) * width;
+  if (S > 0) DLIOM_HIP_TRY(hipMemcpyAsync(submaps, device, bytes * S, hipMemcpyDeviceToHost, stream));
+  if (K > S) DLIOM_HIP_TRY(hipMemcpyAsync(frames, device + width * S, bytes * (K - S), hipMemcpyDeviceToHost, stream));
+  if (num_nodes > 0) DLIOM_HIP_TRY(hipMemcpyAsync(nodes, device + width * K, bytes * num_nodes, hipMemcpyDeviceToHost, stream));
+  return DLIOM_OK;
+}
+
 }  // namespace
 }  // namespace dliom
 
@@ -974,37 +1052,45 @@ using namespace dliom;
 
 extern "C" {
 
+int dliom_pose_graph_evaluate_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                    const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                    int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                    int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                    const dliom_pose_graph_terms* terms, double* cost, double* residuals, double* gradient) {
+  Solver solver;
+  DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
+                    node_constant, num_constraints, constraints, terms, &solver));
+  DLIOM_TRY(enqueue_linearise(&solver, true));
+  double sums[kSums];
+  DLIOM_TRY(read_sums(&solver, false, sums));
+  if (cost != nullptr) *cost = sums[kSumCost] + sums[kSumFixedCost];
+  if (residuals != nullptr && solver.g.num_constraints > 0)
+    DLIOM_HIP_TRY(hipMemcpyAsync(residuals, solver.g.residual, sizeof(double) * 6 * solver.g.num_constraints, hipMemcpyDeviceToHost, ctx->stream));
+  if (gradient != nullptr) DLIOM_TRY(copy_poses_out(&solver, solver.g.gradient, 6, num_submaps, num_nodes, gradient, gradient + 6 * static_cast<size_t>(num_submaps),
+                                                    gradient + 6 * (static_cast<size_t>(num_submaps) + num_nodes)));
+  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ++ctx->host_syncs;
+  return DLIOM_OK;
+}
 int dliom_pose_graph_evaluate(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
                               const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
                               int num_nodes, const double* node_poses7, const unsigned char* node_constant,
                               int64_t num_constraints, const dliom_pose_graph_constraint* constraints, double* cost,
                               double* residuals, double* gradient) {
-  Solver solver;
-  DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
-                    node_constant, num_constraints, constraints, &solver));
-  DLIOM_TRY(enqueue_linearise(&solver, true));
-  double sums[kSums];
-  DLIOM_TRY(read_sums(&solver, false, sums));
-  if (cost != nullptr) *cost = sums[kSumCost] + sums[kSumFixedCost];
-  const size_t poses = static_cast<size_t>(num_submaps) + num_nodes;
-  if (residuals != nullptr && num_constraints > 0)
-    DLIOM_HIP_TRY(hipMemcpyAsync(residuals, solver.g.residual, sizeof(double) * 6 * num_constraints, hipMemcpyDeviceToHost, ctx->stream));
-  if (gradient != nullptr && poses > 0)
-    DLIOM_HIP_TRY(hipMemcpyAsync(gradient, solver.g.gradient, sizeof(double) * 6 * poses, hipMemcpyDeviceToHost, ctx->stream));
-  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  ++ctx->host_syncs;
-  return DLIOM_OK;
+  return dliom_pose_graph_evaluate_terms(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes,
+                                         node_poses7, node_constant, num_constraints, constraints, nullptr, cost, residuals, gradient);
 }
 
-int dliom_pose_graph_step(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
-                          const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
-                          int num_nodes, const double* node_poses7, const unsigned char* node_constant,
-                          int64_t num_constraints, const dliom_pose_graph_constraint* constraints, double radius,
-                          double* delta, double* model_cost_change, int* reduced_dimension) {
+int dliom_pose_graph_step_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                const dliom_pose_graph_terms* terms, double radius, double* delta, double* model_cost_change,
+                                int* reduced_dimension) {
   if (!(radius > 0.)) return DLIOM_ERR_INVALID_ARGUMENT;
   Solver solver;
   DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
-                    node_constant, num_constraints, constraints, &solver));
+                    node_constant, num_constraints, constraints, terms, &solver));
   if (reduced_dimension != nullptr) *reduced_dimension = solver.g.n;
   DLIOM_TRY(enqueue_linearise(&solver, true));
   DLIOM_TRY(enqueue_step(&solver, radius));
@@ -1012,29 +1098,38 @@ int dliom_pose_graph_step(dliom_ctx* ctx, const dliom_pose_graph_options* option
   DLIOM_TRY(read_sums(&solver, true, sums));
   if (sums[kSumFlag] != 0.) return DLIOM_ERR_SOLVER;
   if (model_cost_change != nullptr) *model_cost_change = -sums[kSumModel];
-  const size_t poses = static_cast<size_t>(num_submaps) + num_nodes;
-  if (delta != nullptr && poses > 0)
-    DLIOM_HIP_TRY(hipMemcpyAsync(delta, solver.g.delta, sizeof(double) * 6 * poses, hipMemcpyDeviceToHost, ctx->stream));
+  if (delta != nullptr) DLIOM_TRY(copy_poses_out(&solver, solver.g.delta, 6, num_submaps, num_nodes, delta, delta + 6 * static_cast<size_t>(num_submaps),
+                                                 delta + 6 * (static_cast<size_t>(num_submaps) + num_nodes)));
   DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   ++ctx->host_syncs;
   return DLIOM_OK;
 }
+int dliom_pose_graph_step(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                          const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                          int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                          int64_t num_constraints, const dliom_pose_graph_constraint* constraints, double radius,
+                          double* delta, double* model_cost_change, int* reduced_dimension) {
+  return dliom_pose_graph_step_terms(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes,
+                                     node_poses7, node_constant, num_constraints, constraints, nullptr, radius, delta,
+                                     model_cost_change, reduced_dimension);
+}
 
 // trust_region_minimizer.cc of Ceres 1.13 (Init / IterationZero / the loop), with levenberg_marquardt_strategy.cc's
 // radius rules and trust_region_step_evaluator.cc, for this configuration: third-party behaviour, restated.
-int dliom_pose_graph_solve(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
-                           const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
-                           double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
-                           const dliom_pose_graph_constraint* constraints, dliom_pose_graph_summary* summary) {
+int dliom_pose_graph_solve_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
+                                 const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                                 double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
+                                 const dliom_pose_graph_constraint* constraints, const dliom_pose_graph_terms* terms,
+                                 dliom_pose_graph_summary* summary) {
   if (summary == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
   const auto started = std::chrono::steady_clock::now();
   Solver solver;
   DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
-                    node_constant, num_constraints, constraints, &solver));
+                    node_constant, num_constraints, constraints, terms, &solver));
   std::memset(summary, 0, sizeof(*summary));
   summary->reduced_dimension = solver.g.n;
   Graph& g = solver.g;
-  const size_t pose_bytes = sizeof(double) * 7 * (static_cast<size_t>(num_submaps) + num_nodes);
+  const size_t pose_bytes = sizeof(double) * 7 * (static_cast<size_t>(g.num_kept) + num_nodes);
   double* best = solver.best;
 
   // the 1.13 defaults that common/ceres_solver_options.cc:35-42 leaves alone
@@ -1200,11 +1295,8 @@ int dliom_pose_graph_solve(dliom_ctx* ctx, const dliom_pose_graph_options* optio
     status = DLIOM_ERR_SOLVER;
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   } else {
-    if (num_submaps > 0)
-      DLIOM_HIP_TRY(hipMemcpyAsync(submap_poses7, best, sizeof(double) * 7 * num_submaps, hipMemcpyDeviceToHost, ctx->stream));
-    if (num_nodes > 0)
-      DLIOM_HIP_TRY(hipMemcpyAsync(node_poses7, best + 7 * static_cast<size_t>(num_submaps), sizeof(double) * 7 * num_nodes,
-                                   hipMemcpyDeviceToHost, ctx->stream));
+    DLIOM_TRY(copy_poses_out(&solver, best, 7, num_submaps, num_nodes, submap_poses7, node_poses7,
+                             terms != nullptr ? terms->fixed_frame_poses7 : nullptr));
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
   ++ctx->host_syncs;
@@ -1217,6 +1309,13 @@ int dliom_pose_graph_solve(dliom_ctx* ctx, const dliom_pose_graph_options* optio
     summary->host_ms = total - (solver.stage_ms[0] + solver.stage_ms[1] + solver.stage_ms[2] + solver.stage_ms[3]);
   }
   return status;
+}
+int dliom_pose_graph_solve(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
+                           const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                           double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
+                           const dliom_pose_graph_constraint* constraints, dliom_pose_graph_summary* summary) {
+  return dliom_pose_graph_solve_terms(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes,
+                                      node_poses7, node_constant, num_constraints, constraints, nullptr, summary);
 }
 
 }  // extern "C"

@@ -20,47 +20,80 @@ constexpr int kStructureOk = 0, kStructureBadIndex = 1, kStructureTooLarge = 2;
 constexpr unsigned kTranslationBits = 7u, kRotationBits = 56u;
 
 struct Structure {
-  int num_submaps = 0, num_nodes = 0;
-  int64_t num_constraints = 0;
-  int reduced_dimension = 0;          // columns of the submaps' system
-  std::vector<int32_t> mask;          // per pose (submaps, then nodes): the slots that are columns
-  std::vector<int32_t> column;        // 6 per submap: the slot's column in the reduced system, or -1
+  int num_submaps = 0, num_fixed_frames = 0, num_nodes = 0;
+  int64_t num_constraints = 0;        // residual blocks: the constraints, then the fixed-frame constraints
+  int reduced_dimension = 0;          // columns of the kept blocks' system
+  std::vector<int32_t> kind;          // per kept block (submaps, then fixed frames): kKind*
+  std::vector<int32_t> mask;          // per pose (submaps, fixed frames, then nodes): the slots that are columns
+  std::vector<int32_t> column;        // 6 per kept block: the slot's column in the reduced system, or -1
   std::vector<int32_t> fixed;         // per constraint: 1 = all four blocks constant
-  std::vector<int32_t> pose_start;    // CSR over poses (num_submaps + num_nodes + 1) ...
+  std::vector<int32_t> pose_start;    // CSR over poses (their count + 1) ...
   std::vector<int32_t> pose_constraints;  // ... of the constraints that stay, in input order
   // block pairs (a >= b, both with columns) in (a, b) order, every (a, a) among them; their (c, c') pairs -- c on a,
   // c' on b, both on one eliminated node -- in (node, c, c') order
   std::vector<int32_t> pair_a, pair_b, pair_start, pair_c, pair_c2;
 };
 
-// submap / node: the constraints' indices (stride in int32 words).  *_constant may be null.
-inline int build_structure(int num_submaps, const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
-                           const unsigned char* node_constant, int64_t num_constraints, const int32_t* submap,
-                           const int32_t* node, int64_t stride, bool fix_z, int max_reduced_dimension, Structure* out) {
+// Parameterisation of a kept block's rotation (rotation_parameterization.h): QuaternionParameterization, the gravity-
+// aligned submap's ConstantYawQuaternionPlus (two columns), a fixed frame's YawOnlyQuaternionPlus (one column, slot 3).
+constexpr int kKindQuaternion = 0, kKindConstantYaw = 1, kKindYawOnly = 2;
+// a fixed frame: the translation has no parameterisation (three columns even under fix_z), the yaw is slot 3
+constexpr int kFixedFrameMask = 15;
+
+// The kept side is the submaps followed by the fixed frames; the residual blocks are the constraints followed by the
+// fixed-frame constraints (frame / frame_node: their indices, frame_stride in int32 words), and that is the input order
+// of every list below.  A fixed frame is never constant.  submap / node: the constraints' indices (stride in int32
+// words).  *_constant may be null.
+inline int build_structure_terms(int num_submaps, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                 int num_fixed_frames, int num_nodes, const unsigned char* node_constant,
+                                 int64_t num_submap_constraints, const int32_t* submap_index, const int32_t* submap_node,
+                                 int64_t stride, int64_t num_frame_constraints, const int32_t* frame, const int32_t* frame_node,
+                                 int64_t frame_stride, bool fix_z, int max_reduced_dimension, Structure* out) {
   Structure& s = *out;
   s = Structure();
   s.num_submaps = num_submaps;
+  s.num_fixed_frames = num_fixed_frames;
   s.num_nodes = num_nodes;
+  if (num_submap_constraints > INT32_MAX / 2 || num_frame_constraints > INT32_MAX / 2 - num_submap_constraints) return kStructureTooLarge;
+  const int64_t num_constraints = num_submap_constraints + num_frame_constraints;
   s.num_constraints = num_constraints;
-  if (num_constraints > INT32_MAX / 2) return kStructureTooLarge;
-  for (int64_t c = 0; c < num_constraints; ++c) {
-    const int32_t a = submap[c * stride], n = node[c * stride];
+  for (int64_t c = 0; c < num_submap_constraints; ++c) {
+    const int32_t a = submap_index[c * stride], n = submap_node[c * stride];
     if (a < 0 || a >= num_submaps || n < 0 || n >= num_nodes) return kStructureBadIndex;
   }
-  const int num_poses = num_submaps + num_nodes;
+  for (int64_t c = 0; c < num_frame_constraints; ++c) {
+    const int32_t f = frame[c * frame_stride], n = frame_node[c * frame_stride];
+    if (f < 0 || f >= num_fixed_frames || n < 0 || n >= num_nodes) return kStructureBadIndex;
+  }
+  // from here on the kept blocks take the submaps' place: kept index and node of residual block c
+  const int num_kept = num_submaps + num_fixed_frames;
+  auto kept = [&](int64_t c) -> int32_t {
+    return c < num_submap_constraints ? submap_index[c * stride] : num_submaps + frame[(c - num_submap_constraints) * frame_stride];
+  };
+  auto node = [&](int64_t c) -> int32_t {
+    return c < num_submap_constraints ? submap_node[c * stride] : frame_node[(c - num_submap_constraints) * frame_stride];
+  };
+  const int num_poses = num_kept + num_nodes;
+  s.kind.assign(num_kept, kKindQuaternion);
+  if (gravity_aligned_submap >= 0 && gravity_aligned_submap < num_submaps) s.kind[gravity_aligned_submap] = kKindConstantYaw;
+  for (int f = 0; f < num_fixed_frames; ++f) s.kind[num_submaps + f] = kKindYawOnly;
   const unsigned translation = fix_z ? 3u : 7u;
   s.mask.assign(num_poses, 0);
   for (int p = 0; p < num_poses; ++p) {
+    if (p >= num_submaps && p < num_kept) {
+      s.mask[p] = kFixedFrameMask;
+      continue;
+    }
     const bool is_submap = p < num_submaps;
     const unsigned char* constant = is_submap ? submap_constant : node_constant;
-    if (constant != nullptr && constant[is_submap ? p : p - num_submaps] != 0) continue;
+    if (constant != nullptr && constant[is_submap ? p : p - num_kept] != 0) continue;
     s.mask[p] = is_submap && p == gravity_aligned_submap ? 24 : static_cast<int32_t>(translation | kRotationBits);
   }
   // constraints that stay, and the poses they use
   s.fixed.assign(num_constraints, 0);
   std::vector<int32_t> degree(num_poses + 1, 0);
   for (int64_t c = 0; c < num_constraints; ++c) {
-    const int a = submap[c * stride], n = num_submaps + node[c * stride];
+    const int a = kept(c), n = num_kept + node(c);
     if (s.mask[a] == 0 && s.mask[n] == 0) {
       s.fixed[c] = 1;
       continue;
@@ -77,12 +110,12 @@ inline int build_structure(int num_submaps, const unsigned char* submap_constant
   std::vector<int32_t> fill(s.pose_start.begin(), s.pose_start.end() - 1);
   for (int64_t c = 0; c < num_constraints; ++c) {
     if (s.fixed[c]) continue;
-    s.pose_constraints[fill[submap[c * stride]]++] = static_cast<int32_t>(c);
-    s.pose_constraints[fill[num_submaps + node[c * stride]]++] = static_cast<int32_t>(c);
+    s.pose_constraints[fill[kept(c)]++] = static_cast<int32_t>(c);
+    s.pose_constraints[fill[num_kept + node(c)]++] = static_cast<int32_t>(c);
   }
-  s.column.assign(static_cast<size_t>(num_submaps) * 6, -1);
+  s.column.assign(static_cast<size_t>(num_kept) * 6, -1);
   int64_t columns = 0;
-  for (int a = 0; a < num_submaps; ++a)
+  for (int a = 0; a < num_kept; ++a)
     for (int i = 0; i < 6; ++i)
       if ((s.mask[a] >> i) & 1) s.column[a * 6 + i] = static_cast<int32_t>(columns++);
   s.reduced_dimension = static_cast<int>(columns);
@@ -92,18 +125,18 @@ inline int build_structure(int num_submaps, const unsigned char* submap_constant
     int32_t a, b, n, c, c2;
   };
   std::vector<Triple> triples;
-  for (int a = 0; a < num_submaps; ++a)
+  for (int a = 0; a < num_kept; ++a)
     if (s.mask[a] != 0) triples.push_back(Triple{a, a, -1, -1, -1});  // every diagonal block exists
   for (int n = 0; n < num_nodes; ++n) {
-    const int p = num_submaps + n;
+    const int p = num_kept + n;
     if (s.mask[p] == 0) continue;
     for (int i = s.pose_start[p]; i < s.pose_start[p + 1]; ++i) {
       const int32_t c = s.pose_constraints[i];
-      const int32_t a = submap[c * stride];
+      const int32_t a = kept(c);
       if (s.mask[a] == 0) continue;
       for (int j = s.pose_start[p]; j < s.pose_start[p + 1]; ++j) {
         const int32_t c2 = s.pose_constraints[j];
-        const int32_t b = submap[c2 * stride];
+        const int32_t b = kept(c2);
         if (s.mask[b] == 0 || b > a) continue;
         if (triples.size() >= static_cast<size_t>(INT32_MAX / 2)) return kStructureTooLarge;
         triples.push_back(Triple{a, b, n, c, c2});
@@ -130,6 +163,14 @@ inline int build_structure(int num_submaps, const unsigned char* submap_constant
   }
   s.pair_start.push_back(static_cast<int32_t>(s.pair_c.size()));
   return kStructureOk;
+}
+
+// The graph without fixed frames.
+inline int build_structure(int num_submaps, const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                           const unsigned char* node_constant, int64_t num_constraints, const int32_t* submap,
+                           const int32_t* node, int64_t stride, bool fix_z, int max_reduced_dimension, Structure* out) {
+  return build_structure_terms(num_submaps, submap_constant, gravity_aligned_submap, 0, num_nodes, node_constant, num_constraints,
+                               submap, node, stride, 0, nullptr, nullptr, 1, fix_z, max_reduced_dimension, out);
 }
 
 }  // namespace pose_graph

@@ -2481,20 +2481,38 @@ POSE_GRAPH_CONSTRAINT_DTYPE = np.dtype([("submap", "<i4"), ("node", "<i4"), ("zb
 assert POSE_GRAPH_CONSTRAINT_DTYPE.itemsize == C.sizeof(PoseGraphConstraint)
 _pgc = C.POINTER(PoseGraphConstraint)
 _PG_GRAPH = [C.c_int, _f64p, _u8p, C.c_int, C.c_int, _f64p, _u8p, C.c_int64, _pgc]
+
+
+class PoseGraphTerms(C.Structure):
+    _fields_ = [("num_fixed_frames", C.c_int), ("fixed_frame_poses7", _f64p), ("num_fixed_frame_constraints", C.c_int64),
+                ("fixed_frame_constraints", _pgc), ("huber_scale", C.c_double), ("inter_submap", _u8p)]
+
+
+_pgt = C.POINTER(PoseGraphTerms)
 SYMBOLS += [
     ("dliom_pose_graph_solve", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [C.POINTER(PoseGraphSummary)]),
     ("dliom_pose_graph_evaluate", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_f64p, _f64p, _f64p]),
     ("dliom_pose_graph_step", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [C.c_double, _f64p, _f64p,
                                                                                        C.POINTER(C.c_int)]),
+    ("dliom_pose_graph_solve_terms", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_pgt, C.POINTER(PoseGraphSummary)]),
+    ("dliom_pose_graph_evaluate_terms", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_pgt, _f64p, _f64p, _f64p]),
+    ("dliom_pose_graph_step_terms", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_pgt, C.c_double, _f64p, _f64p,
+                                                                                             C.POINTER(C.c_int)]),
 ]
 
 
 class PoseGraph:
     """OptimizationProblem3D::Solve on compacted indices.  submap_poses / node_poses: (n, 7) [t, q wxyz]; constraints:
-    a POSE_GRAPH_CONSTRAINT_DTYPE array; *_constant: uint8 flags or None; gravity_aligned_submap: index or -1."""
+    a POSE_GRAPH_CONSTRAINT_DTYPE array; *_constant: uint8 flags or None; gravity_aligned_submap: index or -1.
+
+    The further terms (dliom_pose_graph_terms): fixed_frame_poses (F, 7), fixed_frame_constraints (their `submap` is the
+    fixed frame's index), huber_scale and inter_submap (uint8 flags a constraint, or None).  entry: "plain" calls
+    dliom_pose_graph_*, "null" the *_terms entry points with a NULL struct, "terms" those with the struct; None picks
+    "plain" when there is no further term and "terms" otherwise."""
 
     def __init__(self, ctx, submap_poses, node_poses, constraints, submap_constant=None, node_constant=None,
-                 gravity_aligned_submap=0, fix_z_in_3d=False, use_nonmonotonic_steps=False, max_num_iterations=10):
+                 gravity_aligned_submap=0, fix_z_in_3d=False, use_nonmonotonic_steps=False, max_num_iterations=10,
+                 fixed_frame_poses=None, fixed_frame_constraints=None, huber_scale=0.0, inter_submap=None, entry=None):
         self.ctx, self._L = ctx, ctx._L
         self.submaps = _f64(submap_poses).reshape(-1, 7).copy()
         self.nodes = _f64(node_poses).reshape(-1, 7).copy()
@@ -2503,32 +2521,59 @@ class PoseGraph:
         self.node_constant = None if node_constant is None else np.ascontiguousarray(node_constant, dtype=np.uint8)
         self.gravity = int(gravity_aligned_submap)
         self.options = PoseGraphOptions(int(fix_z_in_3d), int(use_nonmonotonic_steps), int(max_num_iterations), 1)
+        self.fixed_frames = _f64(np.zeros((0, 7)) if fixed_frame_poses is None else fixed_frame_poses).reshape(-1, 7).copy()
+        self.fixed_frame_constraints = np.ascontiguousarray(
+            np.zeros(0, POSE_GRAPH_CONSTRAINT_DTYPE) if fixed_frame_constraints is None else fixed_frame_constraints,
+            dtype=POSE_GRAPH_CONSTRAINT_DTYPE)
+        self.huber_scale = float(huber_scale)
+        self.inter_submap = None if inter_submap is None else np.ascontiguousarray(inter_submap, dtype=np.uint8)
+        if self.inter_submap is not None and len(self.inter_submap) != len(self.constraints):
+            raise ValueError("inter_submap: one flag a constraint")
+        plain = len(self.fixed_frames) == 0 and len(self.fixed_frame_constraints) == 0 and self.huber_scale == 0.0
+        self.entry = ("plain" if plain else "terms") if entry is None else entry
+        if self.entry not in ("plain", "null", "terms") or (self.entry != "terms" and not plain):
+            raise ValueError("entry %r cannot carry the further terms" % (self.entry,))
 
     def _graph(self):
         u8 = lambda a: None if a is None else _p(a, _u8p)  # noqa: E731
         return (len(self.submaps), _p(self.submaps, _f64p), u8(self.submap_constant), self.gravity, len(self.nodes),
                 _p(self.nodes, _f64p), u8(self.node_constant), len(self.constraints), _p(self.constraints, _pgc))
 
+    def _call(self, name, *rest):
+        """dliom_pose_graph_<name> or its _terms form, by self.entry; rest: the arguments behind the graph."""
+        if self.entry == "plain":
+            status = getattr(self._L, "dliom_pose_graph_" + name)(self.ctx.h, C.byref(self.options), *self._graph(), *rest)
+        else:
+            terms = None
+            if self.entry == "terms":
+                terms = C.byref(PoseGraphTerms(
+                    len(self.fixed_frames), _p(self.fixed_frames, _f64p) if len(self.fixed_frames) else None,
+                    len(self.fixed_frame_constraints),
+                    _p(self.fixed_frame_constraints, _pgc) if len(self.fixed_frame_constraints) else None, self.huber_scale,
+                    None if self.inter_submap is None else _p(self.inter_submap, _u8p)))
+            status = getattr(self._L, "dliom_pose_graph_%s_terms" % name)(self.ctx.h, C.byref(self.options), *self._graph(), terms,
+                                                                          *rest)
+        _check(status, "dliom_pose_graph_" + name)
+
     def evaluate(self):
-        """-> (cost, residuals (C, 6), gradient (S + N, 6))"""
-        cost, r = C.c_double(), np.zeros((len(self.constraints), 6))
-        g = np.zeros((len(self.submaps) + len(self.nodes), 6))
-        _check(self._L.dliom_pose_graph_evaluate(self.ctx.h, C.byref(self.options), *self._graph(), C.byref(cost), _p(r, _f64p),
-                                                 _p(g, _f64p)), "dliom_pose_graph_evaluate")
+        """-> (cost, residuals (C + CF, 6), gradient (S + N + F, 6)): the constraints and then the fixed frames'; the submaps,
+        the nodes and then the fixed frames"""
+        cost, r = C.c_double(), np.zeros((len(self.constraints) + len(self.fixed_frame_constraints), 6))
+        g = np.zeros((len(self.submaps) + len(self.nodes) + len(self.fixed_frames), 6))
+        self._call("evaluate", C.byref(cost), _p(r, _f64p), _p(g, _f64p))
         return cost.value, r, g
 
     def step(self, radius=1e4):
-        """-> (delta (S + N, 6), model_cost_change, reduced_dimension)"""
-        d, m, n = np.zeros((len(self.submaps) + len(self.nodes), 6)), C.c_double(), C.c_int()
-        _check(self._L.dliom_pose_graph_step(self.ctx.h, C.byref(self.options), *self._graph(), float(radius), _p(d, _f64p),
-                                             C.byref(m), C.byref(n)), "dliom_pose_graph_step")
+        """-> (delta (S + N + F, 6), model_cost_change, reduced_dimension)"""
+        d, m, n = np.zeros((len(self.submaps) + len(self.nodes) + len(self.fixed_frames), 6)), C.c_double(), C.c_int()
+        self._call("step", float(radius), _p(d, _f64p), C.byref(m), C.byref(n))
         return d, m.value, n.value
 
     def solve(self):
-        """Overwrites self.submaps / self.nodes with the best iterate -> the summary as a dict (steps: list of 1 / 0 / 2)."""
+        """Overwrites self.submaps / self.nodes / self.fixed_frames with the best iterate -> the summary as a dict (steps:
+        list of 1 / 0 / 2)."""
         s = PoseGraphSummary()
-        _check(self._L.dliom_pose_graph_solve(self.ctx.h, C.byref(self.options), *self._graph(), C.byref(s)),
-               "dliom_pose_graph_solve")
+        self._call("solve", C.byref(s))
         out = {k: getattr(s, k) for k, _ in PoseGraphSummary._fields_ if k not in ("steps", "num_recorded_steps")}
         out["steps"] = list(s.steps[:s.num_recorded_steps])
         return out

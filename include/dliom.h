@@ -1241,8 +1241,11 @@ int dliom_csm3d_evaluate(dliom_ctx* ctx, const dliom_csm_options* options,
  * OptimizationProblem3D::Solve (mapping/internal/optimization/optimization_problem_3d.cc:259-589) as this fork runs
  * it: the IMU, odometry and local-SLAM terms are commented out there (:350-489) and the inter-submap loss is
  * TrivialLoss (:336-338), so the problem is one SpaCostFunction3D a constraint (cost_functions/spa_cost_function_3d.h:
- * 46-56, cost_helpers_impl.h:57-101, transform/transform.h:59-81) between ONE submap pose and ONE node pose.  Landmarks
- * (AddLandmarkCostFunctions), fixed-frame poses (:491-548) and the 2D problem are not covered.
+ * 46-56, cost_helpers_impl.h:57-101, transform/transform.h:59-81) between ONE submap pose and ONE node pose.  The
+ * *_terms entry points below add the fixed-frame pose constraints (:491-548, live code in the fork) and upstream's
+ * HuberLoss on the inter-submap constraints.  Landmarks (AddLandmarkCostFunctions) are not covered: a landmark residual
+ * couples two nodes, so the nodes' Hessian would no longer be block-diagonal and every node a landmark touches would
+ * have to move into the dense reduced system.  The 2D problem is not covered either.
  *
  * Poses are [tx ty tz qw qx qy qz].  Parameter blocks (:279-330, ceres_pose.cc): a translation block with no
  * parameterisation, or SubsetParameterization(3, {2}) under fix_z_in_3d; a rotation block with
@@ -1325,6 +1328,58 @@ int dliom_pose_graph_step(dliom_ctx* ctx, const dliom_pose_graph_options* option
                           int num_nodes, const double* node_poses7, const unsigned char* node_constant,
                           int64_t num_constraints, const dliom_pose_graph_constraint* constraints, double radius,
                           double* delta, double* model_cost_change, int* reduced_dimension);
+
+/* Further terms of OptimizationProblem3D::Solve.  A NULL pointer to this struct, and a struct of 0 fixed frames and
+ * huber_scale 0, are the entry points above, bit for bit (those are calls of the ones below with NULL).
+ *
+ * Fixed frames (optimization_problem_3d.cc:491-548): one block a trajectory with fixed-frame pose data (GPS).  Its
+ * translation has NO parameterisation -- three columns even under fix_z_in_3d -- and its rotation moves by
+ * AutoDiffLocalParameterization<YawOnlyQuaternionPlus, 4, 1> (rotation_parameterization.h:27-39): one column, tangent
+ * slot 3, Plus = [sqrt(1 - d^2), 0, 0, d] (x) q with d = clamp(delta, -0.5, 0.5).  That is applied to whatever rotation
+ * is given; starting the block yaw-only is the caller's business (:529-533).  A fixed frame is never constant, also
+ * on a frozen trajectory (the fork does not skip those in this loop).  A fixed-frame constraint is a
+ * dliom_pose_graph_constraint whose .submap is the fixed frame's index: the same SpaCostFunction3D with the fixed frame
+ * in the submap's place, never under a loss (:541-546).  The fixed frames' columns follow the submaps' in the reduced
+ * system, four a frame, and count against DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION.  Residual blocks are ordered
+ * constraints first, then fixed-frame constraints.
+ *
+ * Loss: huber_scale == 0 is the fork's TrivialLoss; > 0 puts ceres::HuberLoss(huber_scale) (upstream :335-338,
+ * optimization_problem_options.proto huber_scale) on the constraints c with inter_submap[c] != 0 (Constraint::tag ==
+ * INTER_SUBMAP; NULL: none).  Ceres 1.13 restated: s = ||r||^2 of the block, b = huber_scale^2; for s > b the block's
+ * cost is 1/2 (2 a sqrt(s) - b) and residual and Jacobian are scaled by sqrt(rho') with rho' = max(DBL_MIN, a / sqrt(s))
+ * (Corrector with rho'' <= 0).  Costs, residuals and gradients reported below are the corrected ones, as
+ * Problem::Evaluate reports them.
+ *
+ * Beyond the refusals above: DLIOM_ERR_INVALID_ARGUMENT for a negative count, a positive count with a NULL array, a
+ * fixed-frame or node index out of range, a negative or non-finite huber_scale; DLIOM_ERR_SOLVER for a non-finite
+ * fixed-frame pose or constraint; all before anything is launched. */
+typedef struct dliom_pose_graph_terms {
+  int num_fixed_frames;
+  double* fixed_frame_poses7; /* the start value; solve overwrites it with the best iterate on DLIOM_OK */
+  int64_t num_fixed_frame_constraints;
+  const dliom_pose_graph_constraint* fixed_frame_constraints;
+  double huber_scale;
+  const unsigned char* inter_submap; /* num_constraints flags, or NULL */
+} dliom_pose_graph_terms;
+int dliom_pose_graph_solve_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
+                                 const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                                 double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
+                                 const dliom_pose_graph_constraint* constraints, const dliom_pose_graph_terms* terms,
+                                 dliom_pose_graph_summary* summary);
+/* residuals: 6 a residual block, the constraints and then the fixed-frame constraints; gradient: 6 slots a pose, the
+ * submaps, the nodes and then the fixed frames (slots 0..2 the translation, slot 3 the yaw, 4 and 5 hold 0). */
+int dliom_pose_graph_evaluate_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                    const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                    int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                    int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                    const dliom_pose_graph_terms* terms, double* cost, double* residuals, double* gradient);
+/* delta: in the slots of `gradient` above. */
+int dliom_pose_graph_step_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                const dliom_pose_graph_terms* terms, double radius, double* delta, double* model_cost_change,
+                                int* reduced_dimension);
 
 /* Per-context choices a caller may make; none of them changes a result (every kernel variant is parity-tested).  The
  * library never reads the environment (tuning experiments live in `make experiments` builds only). */

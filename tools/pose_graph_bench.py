@@ -1,7 +1,10 @@
 """dliom_pose_graph_solve against the CPU model (tests/cpp/pose_graph_model.cc, one thread -- this repository's model,
 NOT Ceres) on graphs of S submaps with M nodes a submap: milliseconds a Solve and an iteration, the stage split of the
 summary (a second, profiled run: the stages are then separated by synchronisations), polled read-backs.
-usage: python tools/pose_graph_bench.py [--sizes 3x100,40x100,360x100] [--repeats 3]"""
+--terms adds the further terms of dliom_pose_graph_solve_terms to each graph: two fixed frames, one constraining every
+fifth node of the first half and one every fifth of the second, and HuberLoss(1e3) on the loop closures, one more of
+which is 5 m wrong; the model is then tests/cpp/pose_graph_terms_model.cc.
+usage: python tools/pose_graph_bench.py [--sizes 3x100,40x100,360x100] [--repeats 3] [--terms]"""
 import argparse
 import ctypes as C
 import json
@@ -22,15 +25,27 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="3x100,40x100,360x100")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--terms", action="store_true")
     args = ap.parse_args()
     L = dl.load_library()
     ctx = dl.Context(0)
     d = tempfile.mkdtemp()
-    exe = pc.build_model(d)
+    if args.terms:
+        import pose_graph_terms_common as tc
+    exe = tc.build_model(d) if args.terms else pc.build_model(d)
     for size in args.sizes.split(","):
         s, m = (int(v) for v in size.split("x"))
-        g = pc.synthetic(s, m * s, max(1, s // 10), seed=s, max_iterations=10)  # S * M nodes in all
-        model = pc.model_solve(exe, g, d)
+        if args.terms:
+            g, truth, inter = tc.synthetic(s, m * s, max(1, s // 10), seed=s, max_iterations=10)
+            g, inter = tc.false_closure(g, inter, truth, 5.0, submap=1, node=len(g.nodes) // 2, seed=s)
+            half = len(g.nodes) // 2
+            frames = [dict(origin=tc._yaw_pose([1.0, 2.0, 0.0], -0.4), nodes=list(range(0, half, 5))),
+                      dict(origin=tc._yaw_pose([0.0, -3.0, 0.5], 2.0), nodes=list(range(half, len(g.nodes), 5)))]
+            g = tc.with_fixed_frames(g, truth, frames, seed=s, huber_scale=tc.LOSS_HUBER_SCALE, inter_submap=inter)
+            model = tc.model_solve(exe, g, d)
+        else:
+            g = pc.synthetic(s, m * s, max(1, s // 10), seed=s, max_iterations=10)  # S * M nodes in all
+            model = pc.model_solve(exe, g, d)
         n0 = C.c_int64()
         L.dliom_ctx_read_backs(ctx.h, C.byref(n0))
         times = []
@@ -46,7 +61,7 @@ def main():
         L.dliom_ctx_set_profiling(ctx.h, 0)
         iterations = max(summary["num_iterations"] - 1, 1)
         print(json.dumps(dict(
-            submaps=s, nodes=len(g.nodes), constraints=len(g.constraints), reduced_dimension=summary["reduced_dimension"],
+            submaps=s, nodes=len(g.nodes), constraints=len(g.constraints), terms=args.terms, reduced_dimension=summary["reduced_dimension"],
             iterations=summary["num_iterations"], same_steps_as_model=summary["steps"] == model["steps"],
             device_ms_per_solve=min(times), device_ms_first_solve=times[0], device_ms_per_iteration=min(times) / iterations,
             read_backs_per_solve=(n1.value - n0.value) / args.repeats,
