@@ -15,6 +15,7 @@
 //   dliom::io::PointsBatch / PointsProcessor                  io/points_batch.h:36-73, io/points_processor.h:29-52
 //   dliom::io::MinMaxRangeFiteringPointsProcessor             io/min_max_range_filtering_points_processor.h:30-53
 //   dliom::io::OutlierRemovingPointsProcessor                 io/outlier_removing_points_processor.h:29-82
+//   dliom::mapping::constraints::SubmapFeatureMatcher         mapping/internal/constraints/constraint_builder_3d.cc:459-529
 //
 // The value types below are layout-compatible stand-ins for Eigen::Vector3f / transform::Rigid3d
 // so that this header builds without Eigen; inside cartographer the same adapters are
@@ -1578,6 +1579,89 @@ class OptimizationProblem3D {
   dliom_pose_graph_summary summary_ = {};
 };
 }  // namespace optimization
+}  // namespace mapping
+
+// ---- submap feature matching (mapping/internal/constraints/constraint_builder_3d.cc:459-529) ----------------------------
+namespace transform {
+// transform::Embed3D(Rigid2d(translation, Rotation2D(theta))) (transform/transform.h): (x, y, 0) and a turn about z
+inline Rigid3d Embed3D(double x, double y, double theta) {
+  return Rigid3d(Vector3d{{x, y, 0.0}}, Quaterniond{{std::cos(0.5 * theta), 0.0, 0.0, std::sin(0.5 * theta)}});
+}
+}  // namespace transform
+namespace mapping {
+namespace constraints {
+struct KeyPoint {  // cv::KeyPoint::pt, pixels
+  float x, y;
+};
+static_assert(sizeof(KeyPoint) == 8, "packed xy like cv::Point2f");
+struct FeatureMatchOptions {  // proto/constraint_builder_options.proto, the fields :485-513 read; seed: dliom.h
+  double good_match_ratio_of_distance;
+  int minimum_good_match_num;
+  double ransac_thresh_of_2d_transform_estimate;
+  double scale_estimated_tolerance;
+  uint64_t seed = 0;
+};
+// The second half of ExtractFeaturesForSubmap: the submaps' key points and descriptors (what surf_detector_ produced, a
+// continuous CV_32F cv::Mat's rows) stay on the device; AddSubmap returns the new submap's `matched_submaps`, the
+// submap_to_submap_2D of the constraint queries.  Parity unpinned against OpenCV (dliom.h).
+class SubmapFeatureMatcher {
+ public:
+  SubmapFeatureMatcher(Context* context, int descriptor_size) {
+    Check(dliom_feature_index_create(context->get(), descriptor_size, &index_), "dliom_feature_index_create");
+  }
+  ~SubmapFeatureMatcher() { dliom_feature_index_destroy(index_); }
+  SubmapFeatureMatcher(const SubmapFeatureMatcher&) = delete;
+  SubmapFeatureMatcher& operator=(const SubmapFeatureMatcher&) = delete;
+
+  // descriptors: key_points.size() rows of descriptor_size floats.  Matches against every stored submap but those of the
+  // same trajectory within two submap indices (:470-473); a submap that was never added has no features and is not
+  // matched (:467).  `results`, when given, receives every searched submap's dliom_submap_match.
+  std::map<SubmapId, transform::Rigid3d> AddSubmap(const SubmapId& submap_id, const std::vector<KeyPoint>& key_points,
+                                                   const float* descriptors, double ox, double oy, double resolution,
+                                                   const FeatureMatchOptions& options,
+                                                   std::map<SubmapId, dliom_submap_match>* results = nullptr) {
+    std::vector<SubmapId> searched;
+    std::vector<int64_t> keys;
+    for (const SubmapId& id : stored_) {
+      if (id.trajectory_id == submap_id.trajectory_id && std::abs(submap_id.submap_index - id.submap_index) <= 2) continue;
+      searched.push_back(id);
+      keys.push_back(Key(id));
+    }
+    Check(dliom_feature_index_add(index_, Key(submap_id), descriptors, key_points.empty() ? nullptr : &key_points[0].x,
+                                  static_cast<int32_t>(key_points.size()), ox, oy, resolution),
+          "dliom_feature_index_add");
+    stored_.insert(submap_id);
+    const dliom_feature_match_options o{options.good_match_ratio_of_distance, options.minimum_good_match_num, 0,
+                                        options.ransac_thresh_of_2d_transform_estimate, options.scale_estimated_tolerance,
+                                        options.seed};
+    std::vector<dliom_submap_match> matches(searched.size());
+    Check(dliom_feature_index_match(index_, Key(submap_id), keys.data(), static_cast<int>(keys.size()), &o, matches.data(),
+                                    &stats_),
+          "dliom_feature_index_match");
+    std::map<SubmapId, transform::Rigid3d> matched_submaps;
+    for (size_t k = 0; k < searched.size(); ++k) {
+      if (results != nullptr) (*results)[searched[k]] = matches[k];
+      if (matches[k].status == DLIOM_FEATURE_MATCHED)
+        matched_submaps.insert({searched[k], transform::Embed3D(matches[k].tx, matches[k].ty, matches[k].theta)});
+    }
+    return matched_submaps;
+  }
+  // ConstraintBuilder3D::DeleteScanMatcher: the submap's features leave the device
+  void DeleteSubmap(const SubmapId& submap_id) {
+    if (stored_.erase(submap_id) != 0) Check(dliom_feature_index_remove(index_, Key(submap_id)), "dliom_feature_index_remove");
+  }
+  const dliom_feature_match_stats& stats() const { return stats_; }  // of the last AddSubmap
+
+ private:
+  static int64_t Key(const SubmapId& id) {
+    return static_cast<int64_t>((static_cast<uint64_t>(static_cast<uint32_t>(id.trajectory_id)) << 32) |
+                                static_cast<uint32_t>(id.submap_index));
+  }
+  dliom_feature_index* index_ = nullptr;
+  std::set<SubmapId> stored_;
+  dliom_feature_match_stats stats_ = {};
+};
+}  // namespace constraints
 }  // namespace mapping
 
 namespace mapping {

@@ -274,7 +274,7 @@ struct dliom_points_batch {
 namespace dliom {
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remembered per context, not per thread or process
 enum : unsigned { kFuncAttrScoreBox = 1u, kFuncAttrHistogram = 2u, kFuncAttrStdSortDiag = 4u, kFuncAttrHistogramBig = 8u,
-                  kFuncAttrScoreBoxW3 = 16u, kFuncAttrScoreBoxWide = 32u };
+                  kFuncAttrScoreBoxW3 = 16u, kFuncAttrScoreBoxWide = 32u, kFuncAttrFeatureRansac = 64u };
 // Coordinate of the padding points of the Morton-ordered arrays: far outside any grid extent.
 constexpr int kCostChunk = 32;  // points per chunk of dliom_cloud::d_chunk_order (= the box score kernel's chunk)
 constexpr int kCostChunkBig = 64;  // ... of d_chunk_order_big (the big-box variants' chunk)

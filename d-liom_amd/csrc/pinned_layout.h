@@ -11,6 +11,8 @@
 //  * kPinPoseGraphSums lies inside the bulk regions below (kPinDownload, kPinRtcsmCandidates, kPinFastCsmScores,
 //    kPinFrontierUpload): a pose graph call (pose_graph.hip) is an entry point of its own that runs no match, search or
 //    download, writes the region once an iteration and has copied it out before it launches anything else or returns;
+//  * kPinFeaturePairs and kPinFeatureResults belong to a feature match (feature_match.hip), likewise an entry point of its
+//    own: it fills the first before its launches and has copied the second out before it returns;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -60,6 +62,11 @@ constexpr PinRegion kPinFrontierOut{256 * 1024, kPinnedBytes - 256 * 1024 - 8192
 // call runs nothing else stages in the block
 constexpr PinRegion kPinPoseGraphSums{4096, 256};
 
+// a feature match (feature_match.hip), an entry point of its own like the pose graph's: the pair table it uploads
+// (32 bytes a train set) and the one read-back of the call (48 bytes a train set), DLIOM_FEATURE_MAX_TRAIN_SETS of each
+constexpr PinRegion kPinFeaturePairs{0, 8192 * 32};
+constexpr PinRegion kPinFeatureResults{8192 * 32, 8192 * 48};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -101,6 +108,9 @@ static_assert(pins_disjoint({kPinFrontierUpload, kPinPoses, kPinFrontierOut, kPi
 static_assert(pins_disjoint({kPinCsmSums, kPinLmResult}), "Ceres' regions");
 static_assert(pins_inside({kPinPoseGraphSums}, kPinnedBytes) && pins_disjoint({kPinPoseGraphSums, kPinReadback}),
               "a pose graph solve's region (apart from the small read-backs of the helpers it may call)");
+static_assert(pins_inside({kPinFeaturePairs, kPinFeatureResults}, kPinnedBytes) &&
+                  pins_disjoint({kPinFeaturePairs, kPinFeatureResults}),
+              "a feature match's regions");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

@@ -2577,3 +2577,130 @@ class PoseGraph:
         out = {k: getattr(s, k) for k, _ in PoseGraphSummary._fields_ if k not in ("steps", "num_recorded_steps")}
         out["steps"] = list(s.steps[:s.num_recorded_steps])
         return out
+
+
+# ---- submap feature matching (include/dliom.h "submap feature matching") ---------------------------------------------------
+FEATURE_RANSAC_HYPOTHESES, FEATURE_MAX_GOOD, FEATURE_TRAIN_CHUNK, FEATURE_MAX_TRAIN_SETS = 2000, 4096, 64, 8192
+FEATURE_MATCHED, FEATURE_TOO_FEW_KEYPOINTS, FEATURE_TOO_FEW_GOOD_MATCHES, FEATURE_NO_MODEL, FEATURE_SCALE_REJECTED = range(5)
+
+
+class FeatureMatchOptions(C.Structure):
+    _fields_ = [("good_match_ratio_of_distance", C.c_double), ("minimum_good_match_num", C.c_int), ("reserved", C.c_int),
+                ("ransac_threshold", C.c_double), ("scale_estimated_tolerance", C.c_double), ("seed", C.c_uint64)]
+
+
+class SubmapMatch(C.Structure):
+    _fields_ = [("key", C.c_int64), ("status", C.c_int), ("good_matches", C.c_int), ("inliers", C.c_int),
+                ("hypothesis", C.c_int)] + [(f, C.c_double) for f in ("a", "b", "tx", "ty", "scale", "theta")]
+
+
+class FeatureMatchStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("pairs", "matched", "too_few_keypoints", "too_few_good_matches", "no_model",
+                                         "scale_rejected", "over_capacity", "ransac_pairs", "read_backs")] + \
+               [(f, C.c_double) for f in ("knn_ms", "good_ms", "ransac_ms")]
+
+
+class FeatureRansacResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("inliers", C.c_int), ("hypothesis", C.c_int), ("num_hypotheses", C.c_int)] + \
+               [(f, C.c_double) for f in ("a", "b", "tx", "ty", "scale", "theta")]
+
+
+class FeatureIndexMemory(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("sets", "keypoints", "descriptor_bytes", "keypoint_bytes", "scratch_bytes")]
+
+
+SUBMAP_MATCH_DTYPE = np.dtype([("key", "<i8"), ("status", "<i4"), ("good_matches", "<i4"), ("inliers", "<i4"),
+                               ("hypothesis", "<i4"), ("a", "<f8"), ("b", "<f8"), ("tx", "<f8"), ("ty", "<f8"),
+                               ("scale", "<f8"), ("theta", "<f8")])
+assert SUBMAP_MATCH_DTYPE.itemsize == C.sizeof(SubmapMatch)
+SYMBOLS += [
+    ("dliom_feature_index_create", C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    ("dliom_feature_index_destroy", None, [_vp]),
+    ("dliom_feature_index_size", C.c_int, [_vp, _i64p]),
+    ("dliom_feature_index_memory_stats", C.c_int, [_vp, C.POINTER(FeatureIndexMemory)]),
+    ("dliom_feature_index_add", C.c_int, [_vp, C.c_int64, _f32p, _f32p, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    ("dliom_feature_index_remove", C.c_int, [_vp, C.c_int64]),
+    ("dliom_feature_index_match", C.c_int, [_vp, C.c_int64, _i64p, C.c_int, C.POINTER(FeatureMatchOptions),
+                                            C.POINTER(SubmapMatch), C.POINTER(FeatureMatchStats)]),
+    ("dliom_feature_index_knn", C.c_int, [_vp, C.c_int64, C.c_int64, _i32p, _i32p, _f32p, _f32p]),
+    ("dliom_feature_ransac", C.c_int, [_vp, _f32p, _f32p, C.c_int, C.c_double, C.c_uint64, C.POINTER(FeatureRansacResult),
+                                       _u8p]),
+]
+
+
+def feature_match_options(good_match_ratio_of_distance, minimum_good_match_num, ransac_threshold, scale_estimated_tolerance,
+                          seed=0):
+    return FeatureMatchOptions(float(good_match_ratio_of_distance), int(minimum_good_match_num), 0, float(ransac_threshold),
+                               float(scale_estimated_tolerance), int(seed))
+
+
+class FeatureIndex:
+    """The key points and descriptors of the finished submaps in HBM (dliom_feature_index) and the second half of
+    ConstraintBuilder3D::ExtractFeaturesForSubmap on them.  Parity unpinned against OpenCV (dliom.h)."""
+
+    def __init__(self, ctx, descriptor_size):
+        self.ctx, self._L = ctx, ctx._L
+        h = _vp()
+        _check(self._L.dliom_feature_index_create(ctx.h, int(descriptor_size), C.byref(h)), "dliom_feature_index_create")
+        self.h, self.descriptor_size = h, int(descriptor_size)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_feature_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        n = C.c_int64()
+        _check(self._L.dliom_feature_index_size(self.h, C.byref(n)), "dliom_feature_index_size")
+        return int(n.value)
+
+    def memory_stats(self):
+        m = FeatureIndexMemory()
+        _check(self._L.dliom_feature_index_memory_stats(self.h, C.byref(m)), "dliom_feature_index_memory_stats")
+        return {k: getattr(m, k) for k, _ in FeatureIndexMemory._fields_}
+
+    def add(self, key, descriptors, keypoints_xy, ox, oy, resolution):
+        d = _f32(descriptors).reshape(-1, self.descriptor_size)
+        k = _f32(keypoints_xy).reshape(-1, 2)
+        if len(d) != len(k):
+            raise ValueError("one descriptor a key point")
+        _check(self._L.dliom_feature_index_add(self.h, int(key), _p(d, _f32p), _p(k, _f32p), len(d), float(ox), float(oy),
+                                               float(resolution)), "dliom_feature_index_add")
+
+    def remove(self, key):
+        _check(self._L.dliom_feature_index_remove(self.h, int(key)), "dliom_feature_index_remove")
+
+    def match(self, query_key, train_keys, options):
+        """-> (results: a SUBMAP_MATCH_DTYPE array, one a train key; stats: dict)"""
+        keys = np.ascontiguousarray(train_keys, dtype=np.int64)
+        results = np.zeros(len(keys), dtype=SUBMAP_MATCH_DTYPE)
+        stats = FeatureMatchStats()
+        _check(self._L.dliom_feature_index_match(self.h, int(query_key), _p(keys, _i64p), len(keys), C.byref(options),
+                                                 _p(results, C.POINTER(SubmapMatch)), C.byref(stats)),
+               "dliom_feature_index_match")
+        return results, {k: getattr(stats, k) for k, _ in FeatureMatchStats._fields_}
+
+    def knn(self, query_key, train_key, num_queries):
+        """-> (j0, j1, d0, d1) of the query set's num_queries key points"""
+        j0, j1 = np.zeros(num_queries, np.int32), np.zeros(num_queries, np.int32)
+        d0, d1 = np.zeros(num_queries, np.float32), np.zeros(num_queries, np.float32)
+        _check(self._L.dliom_feature_index_knn(self.h, int(query_key), int(train_key), _p(j0, _i32p), _p(j1, _i32p),
+                                               _p(d0, _f32p), _p(d1, _f32p)), "dliom_feature_index_knn")
+        return j0, j1, d0, d1
+
+
+def feature_ransac(ctx, from_xy, to_xy, threshold, seed=0):
+    """dliom_feature_ransac -> (dict of the result's fields, inlier mask (M,) uint8)"""
+    p, q = _f32(from_xy).reshape(-1, 2), _f32(to_xy).reshape(-1, 2)
+    if len(p) != len(q):
+        raise ValueError("one `to` point a `from` point")
+    r, mask = FeatureRansacResult(), np.zeros(len(p), np.uint8)
+    _check(ctx._L.dliom_feature_ransac(ctx.h, _p(p, _f32p), _p(q, _f32p), len(p), float(threshold), int(seed), C.byref(r),
+                                       _p(mask, _u8p)), "dliom_feature_ransac")
+    return {k: getattr(r, k) for k, _ in FeatureRansacResult._fields_}, mask

@@ -1381,6 +1381,132 @@ int dliom_pose_graph_step_terms(dliom_ctx* ctx, const dliom_pose_graph_options* 
                                 const dliom_pose_graph_terms* terms, double radius, double* delta, double* model_cost_change,
                                 int* reduced_dimension);
 
+/* ---- submap feature matching -------------------------------------------------------------------
+ * The second half of ConstraintBuilder3D::ExtractFeaturesForSubmap (mapping/internal/constraints/
+ * constraint_builder_3d.cc:459-529): which earlier submaps a finished submap is matched against (`matched_submaps`),
+ * from the key points and descriptors the caller's SURF produced.  PARITY UNPINNED AGAINST OPENCV: the reference's
+ * matcher is FLANN (randomised, approximate) and estimateAffinePartial2D draws from OpenCV's RNG, so its result cannot
+ * be pinned.  What is pinned, bit for bit against a CPU model (tests/cpp/feature_match_model.cc), is this definition:
+ *
+ * Nearest neighbours.  Descriptors have D floats, D a multiple of 4, 4 <= D <= 128.  s(i, j) is a float accumulated in
+ * dimension order d = 0 .. D-1 from 0.0f: diff = q[d] - t[d]; s = fmaf(diff, diff, s).  The nearest neighbour j0 of
+ * query i is the j with the least s, ties to the lowest j; the second nearest j1 is the same rule over j != j0.
+ * d0 = sqrtf(s(i, j0)), d1 = sqrtf(s(i, j1)), correctly rounded.  A pair of sets is matched only if both hold >= 2 key
+ * points (:476-477), else DLIOM_FEATURE_TOO_FEW_KEYPOINTS.
+ *
+ * Good matches (:485-491).  Match i is good iff (double)d0 < r * (double)d1, r = good_match_ratio_of_distance; good
+ * matches keep query order.  Fewer than minimum_good_match_num: DLIOM_FEATURE_TOO_FEW_GOOD_MATCHES (:493).  More than
+ * DLIOM_FEATURE_MAX_GOOD: DLIOM_ERR_CAPACITY as that pair's status.
+ *
+ * Points (:494-504), floats as in cv::Point2f: from.x = (float)ox_q + (float)((double)kp_q[i].x * resolution_q),
+ * to.x = (float)ox_t + (float)((double)kp_t[j0].x * resolution_q), likewise y.  Both sides take the QUERY set's
+ * resolution, as the reference does.  Everything below is double arithmetic on these floats, every operation rounded
+ * on its own (no contraction), in the order written.
+ *
+ * Hypotheses, our statement of estimateAffinePartial2D(from, to, inliers, RANSAC, threshold).  With M good matches and
+ * H = DLIOM_FEATURE_RANSAC_HYPOTHESES: if M (M - 1) / 2 <= H (M <= 63) the hypotheses are all pairs i < j in
+ * lexicographic order; otherwise there are H, and hypothesis h draws
+ *     z = seed + h;  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31;                       (splitmix64, 64-bit wrap-around)
+ *     i = (uint32)z % M;  j = (uint32)(z >> 32) % (M - 1);  j += (j >= i);
+ * Every hypothesis is evaluated (no adaptive stop).  M < 2 has none.  With p = from, P = to:
+ *     dx = p_j.x - p_i.x;  dy = p_j.y - p_i.y;  ex = P_j.x - P_i.x;  ey = P_j.y - P_i.y;
+ *     den = dx * dx + dy * dy;                          den == 0: degenerate, the hypothesis scores -1
+ *     a = (dx * ex + dy * ey) / den;  b = (dx * ey - dy * ex) / den;
+ *     tx = P_i.x - (a * p_i.x - b * p_i.y);  ty = P_i.y - (b * p_i.x + a * p_i.y);
+ * Match k is an inlier iff, with rx = ((a * p_k.x - b * p_k.y) + tx) - P_k.x and ry = ((b * p_k.x + a * p_k.y) + ty)
+ * - P_k.y, rx * rx + ry * ry <= threshold * threshold.  The best hypothesis has the most inliers, ties to the lowest h;
+ * all degenerate (or none): DLIOM_FEATURE_NO_MODEL.
+ *
+ * Refit over the best hypothesis's n inliers, the closed-form least-squares similarity (what OpenCV's LM refinement
+ * converges to); every sum sequential in match order from 0.0:
+ *     mpx = (sum p.x) / n, mpy, mPx, mPy likewise;  per inlier dcx = p.x - mpx, dcy = p.y - mpy, ecx = P.x - mPx, ecy = P.y - mPy;
+ *     sdd += dcx * dcx + dcy * dcy;  sde += dcx * ecx + dcy * ecy;  sx += dcx * ecy - dcy * ecx;
+ *     sdd == 0: the hypothesis's own (a, b, tx, ty) stand; else a = sde / sdd;  b = sx / sdd;
+ *     tx = mPx - (a * mpx - b * mpy);  ty = mPy - (b * mpx + a * mpy).
+ * On the host: scale = sqrt(a * a + b * b); |scale - 1| > scale_estimated_tolerance: DLIOM_FEATURE_SCALE_REJECTED
+ * (:510-514); else DLIOM_FEATURE_MATCHED with theta = atan2(b, a) (:516-517) and the translation (tx, ty) (:519-525).
+ *
+ * No floating-point atomics anywhere: two calls on one input give the same bytes.  Malformed input fails the whole
+ * call with DLIOM_ERR_INVALID_ARGUMENT before anything runs. */
+#define DLIOM_FEATURE_RANSAC_HYPOTHESES 2000 /* OpenCV's default iteration cap */
+#define DLIOM_FEATURE_MAX_GOOD 4096          /* good matches a pair (the RANSAC kernel keeps a pair's points in LDS) */
+#define DLIOM_FEATURE_TRAIN_CHUNK 64         /* train descriptors staged in LDS at a time (feature_knn_kernel) */
+#define DLIOM_FEATURE_MAX_TRAIN_SETS 8192    /* train keys of one dliom_feature_index_match call (the page-locked block) */
+#define DLIOM_FEATURE_MAX_KEYPOINTS (1 << 20) /* key points of one set */
+enum {
+  DLIOM_FEATURE_MATCHED = 0,
+  DLIOM_FEATURE_TOO_FEW_KEYPOINTS = 1,
+  DLIOM_FEATURE_TOO_FEW_GOOD_MATCHES = 2,
+  DLIOM_FEATURE_NO_MODEL = 3,
+  DLIOM_FEATURE_SCALE_REJECTED = 4
+};
+typedef struct dliom_feature_index dliom_feature_index;
+typedef struct dliom_feature_match_options {
+  double good_match_ratio_of_distance;  /* constraint_builder_options.proto, as the fork reads them (:485-513) */
+  int minimum_good_match_num;
+  int reserved;                         /* 0 */
+  double ransac_threshold;              /* ransac_thresh_of_2d_transform_estimate */
+  double scale_estimated_tolerance;
+  uint64_t seed;
+} dliom_feature_match_options;
+typedef struct dliom_submap_match {
+  int64_t key;      /* the train key */
+  int status;       /* DLIOM_FEATURE_*, or DLIOM_ERR_CAPACITY for this pair alone */
+  int good_matches; /* 0 under TOO_FEW_KEYPOINTS */
+  int inliers;      /* of the best hypothesis; 0 where no hypothesis was evaluated */
+  int hypothesis;   /* its index h, -1 where there is none */
+  double a, b, tx, ty; /* [a -b tx; b a ty]: query frame -> train frame; 0 where there is no model */
+  double scale, theta;
+} dliom_submap_match;
+typedef struct dliom_feature_match_stats {
+  int64_t pairs, matched, too_few_keypoints, too_few_good_matches, no_model, scale_rejected, over_capacity;
+  int64_t ransac_pairs; /* pairs whose hypotheses were evaluated */
+  int64_t read_backs;   /* polled read-backs of the call: 1, or 0 when no pair reached the device */
+  /* milliseconds of the three kernels; filled (the call then synchronises the stream) only while the context's
+   * profiling is on */
+  double knn_ms, good_ms, ransac_ms;
+} dliom_feature_match_stats;
+typedef struct dliom_feature_ransac_result {
+  int status;         /* DLIOM_FEATURE_MATCHED or DLIOM_FEATURE_NO_MODEL (no scale gate here: `scale` is reported) */
+  int inliers;
+  int hypothesis;
+  int num_hypotheses; /* M (M - 1) / 2 or DLIOM_FEATURE_RANSAC_HYPOTHESES */
+  double a, b, tx, ty, scale, theta;
+} dliom_feature_ransac_result;
+typedef struct dliom_feature_index_memory {
+  int64_t sets, keypoints, descriptor_bytes, keypoint_bytes, scratch_bytes;
+} dliom_feature_index_memory;
+/* The descriptors and key points of all stored sets stay in HBM.  One thread at a time per index, like its context;
+ * destroy the index before the context. */
+int dliom_feature_index_create(dliom_ctx* ctx, int descriptor_size, dliom_feature_index** index);
+void dliom_feature_index_destroy(dliom_feature_index* index);
+int dliom_feature_index_size(const dliom_feature_index* index, int64_t* num_sets);
+int dliom_feature_index_memory_stats(const dliom_feature_index* index, dliom_feature_index_memory* out);
+/* descriptors: count x descriptor_size floats; keypoints_xy: count x 2 floats (cv::KeyPoint::pt, pixels); ox, oy: the
+ * image's corner as ProjectToCvMat returns it; resolution: metres a pixel.  Refuses (DLIOM_ERR_INVALID_ARGUMENT) a
+ * duplicate key, a non-finite value, count < 0 or > DLIOM_FEATURE_MAX_KEYPOINTS.  count 0 or 1 is stored and later
+ * yields DLIOM_FEATURE_TOO_FEW_KEYPOINTS. */
+int dliom_feature_index_add(dliom_feature_index* index, int64_t key, const float* descriptors, const float* keypoints_xy,
+                            int32_t count, double ox, double oy, double resolution);
+/* DeleteScanMatcher: an unknown key is DLIOM_ERR_INVALID_ARGUMENT. */
+int dliom_feature_index_remove(dliom_feature_index* index, int64_t key);
+/* The stored set `query_key` against each of train_keys[0 .. count): results[k] belongs to train_keys[k].  Three
+ * launches and one polled read-back for the whole list.  An unknown key, count < 0, NULL options / results, a
+ * non-finite or negative option: DLIOM_ERR_INVALID_ARGUMENT; count > DLIOM_FEATURE_MAX_TRAIN_SETS: DLIOM_ERR_TOO_LARGE;
+ * all before anything runs.  stats may be NULL. */
+int dliom_feature_index_match(dliom_feature_index* index, int64_t query_key, const int64_t* train_keys, int count,
+                              const dliom_feature_match_options* options, dliom_submap_match* results,
+                              dliom_feature_match_stats* stats);
+/* Diagnostics for the tests, both on the device.  The two nearest neighbours of every key point of `query_key` in
+ * `train_key` (both sets >= 2 key points, else DLIOM_ERR_INVALID_ARGUMENT): four arrays of the query's count. */
+int dliom_feature_index_knn(dliom_feature_index* index, int64_t query_key, int64_t train_key, int32_t* j0, int32_t* j1,
+                            float* d0, float* d1);
+/* The hypotheses and the refit on M given matches (2 <= M <= DLIOM_FEATURE_MAX_GOOD; x y interleaved);
+ * inlier_mask: M bytes of the best hypothesis's inliers (zeros under NO_MODEL), may be NULL. */
+int dliom_feature_ransac(dliom_ctx* ctx, const float* from_xy, const float* to_xy, int num_matches, double threshold,
+                         uint64_t seed, dliom_feature_ransac_result* result, unsigned char* inlier_mask);
+
 /* Per-context choices a caller may make; none of them changes a result (every kernel variant is parity-tested).  The
  * library never reads the environment (tuning experiments live in `make experiments` builds only). */
 enum {
