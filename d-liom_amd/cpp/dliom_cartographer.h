@@ -1620,16 +1620,53 @@ class SubmapFeatureMatcher {
                                                    const float* descriptors, double ox, double oy, double resolution,
                                                    const FeatureMatchOptions& options,
                                                    std::map<SubmapId, dliom_submap_match>* results = nullptr) {
-    std::vector<SubmapId> searched;
-    std::vector<int64_t> keys;
-    for (const SubmapId& id : stored_) {
-      if (id.trajectory_id == submap_id.trajectory_id && std::abs(submap_id.submap_index - id.submap_index) <= 2) continue;
-      searched.push_back(id);
-      keys.push_back(Key(id));
-    }
+    const std::vector<SubmapId> searched = Searched(submap_id);
     Check(dliom_feature_index_add(index_, Key(submap_id), descriptors, key_points.empty() ? nullptr : &key_points[0].x,
                                   static_cast<int32_t>(key_points.size()), ox, oy, resolution),
           "dliom_feature_index_add");
+    return MatchStored(submap_id, searched, options, results);
+  }
+  // The whole of ExtractFeaturesForSubmap (:436-532) from the finished submap's high resolution grid: ProjectToCvMat,
+  // cv::threshold, cv::erode and SURF (dliom.h "submap image features") run on the device and the features go straight
+  // into the index (dliom_feature_index_add_from_grid); the matcher must have descriptor size 64 and the grid's context.
+  // Replaces :442-458 and the overload above at the call site.  Parity unpinned against OpenCV (dliom.h).
+  std::map<SubmapId, transform::Rigid3d> AddSubmap(const SubmapId& submap_id, const HybridGrid& high_resolution_hybrid_grid,
+                                                   const transform::Rigid3d& global_submap_pose,
+                                                   const dliom_surf_options& surf_options, const FeatureMatchOptions& options,
+                                                   std::map<SubmapId, dliom_submap_match>* results = nullptr) {
+    const std::vector<SubmapId> searched = Searched(submap_id);
+    const std::array<double, 7> pose = global_submap_pose.ToArray();
+    Check(dliom_feature_index_add_from_grid(index_, Key(submap_id), high_resolution_hybrid_grid.get(), pose.data(), &surf_options,
+                                            nullptr, nullptr, nullptr, nullptr),
+          "dliom_feature_index_add_from_grid");
+    return MatchStored(submap_id, searched, options, results);
+  }
+  // ConstraintBuilder3D::DeleteScanMatcher: the submap's features leave the device
+  void DeleteSubmap(const SubmapId& submap_id) {
+    if (stored_.erase(submap_id) != 0) Check(dliom_feature_index_remove(index_, Key(submap_id)), "dliom_feature_index_remove");
+  }
+  const dliom_feature_match_stats& stats() const { return stats_; }  // of the last AddSubmap
+
+ private:
+  static int64_t Key(const SubmapId& id) {
+    return static_cast<int64_t>((static_cast<uint64_t>(static_cast<uint32_t>(id.trajectory_id)) << 32) |
+                                static_cast<uint32_t>(id.submap_index));
+  }
+  // every stored submap but those of the same trajectory within two submap indices (:470-473)
+  std::vector<SubmapId> Searched(const SubmapId& submap_id) const {
+    std::vector<SubmapId> searched;
+    for (const SubmapId& id : stored_) {
+      if (id.trajectory_id == submap_id.trajectory_id && std::abs(submap_id.submap_index - id.submap_index) <= 2) continue;
+      searched.push_back(id);
+    }
+    return searched;
+  }
+  // the submap's set is in the index: record it and match it against `searched`
+  std::map<SubmapId, transform::Rigid3d> MatchStored(const SubmapId& submap_id, const std::vector<SubmapId>& searched,
+                                                     const FeatureMatchOptions& options,
+                                                     std::map<SubmapId, dliom_submap_match>* results) {
+    std::vector<int64_t> keys;
+    for (const SubmapId& id : searched) keys.push_back(Key(id));
     stored_.insert(submap_id);
     const dliom_feature_match_options o{options.good_match_ratio_of_distance, options.minimum_good_match_num, 0,
                                         options.ransac_thresh_of_2d_transform_estimate, options.scale_estimated_tolerance,
@@ -1645,17 +1682,6 @@ class SubmapFeatureMatcher {
         matched_submaps.insert({searched[k], transform::Embed3D(matches[k].tx, matches[k].ty, matches[k].theta)});
     }
     return matched_submaps;
-  }
-  // ConstraintBuilder3D::DeleteScanMatcher: the submap's features leave the device
-  void DeleteSubmap(const SubmapId& submap_id) {
-    if (stored_.erase(submap_id) != 0) Check(dliom_feature_index_remove(index_, Key(submap_id)), "dliom_feature_index_remove");
-  }
-  const dliom_feature_match_stats& stats() const { return stats_; }  // of the last AddSubmap
-
- private:
-  static int64_t Key(const SubmapId& id) {
-    return static_cast<int64_t>((static_cast<uint64_t>(static_cast<uint32_t>(id.trajectory_id)) << 32) |
-                                static_cast<uint32_t>(id.submap_index));
   }
   dliom_feature_index* index_ = nullptr;
   std::set<SubmapId> stored_;

@@ -355,6 +355,12 @@ int launch_ransac(dliom_ctx* ctx, const float4* points, int stride, const int* c
   return DLIOM_OK;
 }
 
+// a stored set's key points from the records of dliom_surf_detect_and_compute: (x, y) of each
+__global__ __launch_bounds__(256) void feature_keypoints_xy_kernel(const float* __restrict__ records, int n, float2* __restrict__ xy) {
+  const int k = static_cast<int>(blockIdx.x) * 256 + threadIdx.x;
+  if (k < n) xy[k] = make_float2(records[DLIOM_SURF_KEYPOINT_FLOATS * k], records[DLIOM_SURF_KEYPOINT_FLOATS * k + 1]);
+}
+
 bool all_finite(const float* v, size_t n) {
   for (size_t i = 0; i < n; ++i)
     if (!std::isfinite(v[i])) return false;
@@ -465,6 +471,52 @@ int dliom_feature_index_add(dliom_feature_index* index, int64_t key, const float
   }
   index->sets.emplace(key, s);
   index->keypoints += count;
+  return DLIOM_OK;
+}
+
+int dliom_feature_index_add_from_grid(dliom_feature_index* index, int64_t key, const dliom_grid* grid,
+                                      const double transform7[7], const dliom_surf_options* options, int32_t* count, double* ox,
+                                      double* oy, double* resolution) {
+  if (index == nullptr || grid == nullptr || transform7 == nullptr || grid->ctx != index->ctx ||
+      index->D != DLIOM_SURF_DESCRIPTOR_SIZE || index->sets.count(key) != 0)
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  DLIOM_TRY(dliom::surf_check_options(options));
+  dliom_ctx* ctx = index->ctx;
+  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  const uint8_t* image = nullptr;
+  int32_t width = 0, height = 0;
+  FeatureSet s;
+  DLIOM_TRY(dliom::project_to_image_on_device(grid, transform7, &image, &width, &height, &s.ox, &s.oy, &s.resolution));
+  const float *records = nullptr, *descriptors = nullptr;
+  if (image != nullptr)
+    DLIOM_TRY(dliom::surf_features_on_device(ctx, image, width, height, *options, &records, &descriptors, &s.count));
+  if (s.count > 0) {
+    const size_t n = static_cast<size_t>(s.count);
+    DLIOM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.descriptors), n * index->D * sizeof(float)));
+    if (hipMalloc(reinterpret_cast<void**>(&s.keypoints), n * 2 * sizeof(float)) != hipSuccess) {
+      (void)hipFree(s.descriptors);
+      return DLIOM_ERR_HIP;
+    }
+    hipError_t e = hipMemcpyAsync(s.descriptors, descriptors, n * index->D * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(dliom::feature_keypoints_xy_kernel, dim3(dliom::blocks_of(s.count, 256)), dim3(256), 0, ctx->stream, records,
+                         s.count, reinterpret_cast<float2*>(s.keypoints));
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the scratch the set was copied from is free again
+    if (e != hipSuccess) {
+      dliom::set_last_error("dliom_feature_index_add_from_grid copy", e, __FILE__, __LINE__);
+      (void)hipFree(s.descriptors);
+      (void)hipFree(s.keypoints);
+      return DLIOM_ERR_HIP;
+    }
+  }
+  index->sets.emplace(key, s);
+  index->keypoints += s.count;
+  if (count != nullptr) *count = s.count;
+  if (ox != nullptr) *ox = s.ox;
+  if (oy != nullptr) *oy = s.oy;
+  if (resolution != nullptr) *resolution = s.resolution;
   return DLIOM_OK;
 }
 

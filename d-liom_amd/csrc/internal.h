@@ -132,6 +132,9 @@ struct dliom_ctx {
   dliom::DevBuf batch;
   // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
   dliom::DevBuf xray_leaves, xray_cells;
+  // the submap image features (surf.hip): what is sized by the image and the candidates; what is sized by the key points
+  dliom::DevBuf surf, surf_out;
+  bool surf_tables_ready = false;  // `surf` holds the Gaussian tables: cleared whenever reserve() made a new allocation
   // the export stages (compact.hip): keep flags, their scan and the survivors' indices; the voxel list of a table dump
   dliom::DevBuf outlier;
   void* batch_pinned = nullptr;
@@ -318,6 +321,17 @@ int compact_equal_arrays_enqueue(dliom_ctx* ctx, const Soa& in, const unsigned c
                                  float* oy, float* oz, const unsigned* n_dev, const unsigned** d_total);
 int needed_bits_for_cell_range(int min_index, int max_index);
 // sizes and offsets inside the scratch buffers are multiples of 256 bytes
+// xray.hip: dliom_grid_project_to_image with the picture left in HBM (*image: ctx->xray_cells, valid until the context's
+// next projection; nullptr under an empty projection).  Nothing is waited for after the kernels.
+int project_to_image_on_device(const dliom_grid* grid, const double transform7[7], const uint8_t** image, int32_t* width,
+                               int32_t* height, double* ox, double* oy, double* resolution);
+// surf.hip: steps 1-8 of dliom.h "submap image features" on an image in HBM.  *keypoints (count x 7 floats) and
+// *descriptors (count x 64) lie in ctx->surf_out until the context's next such call; the stream has been waited for.
+// More than DLIOM_SURF_MAX_KEYPOINTS candidates: DLIOM_ERR_CAPACITY with *count = their number.
+int surf_features_on_device(dliom_ctx* ctx, const uint8_t* image, int width, int height, const dliom_surf_options& options,
+                            const float** keypoints, const float** descriptors, int* count);
+int surf_check_options(const dliom_surf_options* options);  // DLIOM_OK or DLIOM_ERR_INVALID_ARGUMENT
+
 constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
 // workgroups of `threads` that cover n items
 constexpr unsigned blocks_of(int64_t n, int threads) { return static_cast<unsigned>((n + threads - 1) / threads); }

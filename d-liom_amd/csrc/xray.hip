@@ -284,7 +284,10 @@ struct XrayResult {
 };
 
 // Runs the projection; out == nullptr or capacity too small: sizes only.  2 bytes per pixel (texture) or 1 (image).
-int run_xray(const dliom_grid* g, const XrayTransform& T, bool texture, uint8_t* out, int64_t capacity, XrayResult* r) {
+// device_out != nullptr: the picture stays in HBM (ctx->xray_cells, valid until the next projection on the context);
+// out and capacity are then not used and nothing is copied or waited for after the kernels.
+int run_xray(const dliom_grid* g, const XrayTransform& T, bool texture, uint8_t* out, int64_t capacity, XrayResult* r,
+             const uint8_t** device_out = nullptr) {
   dliom_ctx* ctx = g->ctx;
   const int64_t S = std::min<int64_t>(g->used_upper, g->capacity) - 1;  // candidate slots 1 .. S; the count is on the device
   if (S <= 0 || g->d_pool == nullptr) return DLIOM_OK;
@@ -337,8 +340,10 @@ int run_xray(const dliom_grid* g, const XrayTransform& T, bool texture, uint8_t*
   r->height = texture ? sx : sy;
   const int64_t pixels = sx * sy;
   if (pixels > DLIOM_XRAY_MAX_PIXELS) return DLIOM_ERR_CAPACITY;
-  if (out == nullptr) return DLIOM_OK;
-  if (capacity < bpp * pixels) return DLIOM_ERR_CAPACITY;
+  if (device_out == nullptr) {
+    if (out == nullptr) return DLIOM_OK;
+    if (capacity < bpp * pixels) return DLIOM_ERR_CAPACITY;
+  }
 
   // ---- phase 2: occupied cells in iterator order, stable sort by pixel, one thread per pixel -----------------------
   int end_bit = 1;
@@ -373,6 +378,10 @@ int run_xray(const dliom_grid* g, const XrayTransform& T, bool texture, uint8_t*
     hipLaunchKernelGGL(xray_image_kernel, dim3(blocks_of(pixels, 256)), dim3(256), 0, st, a, gain);
   }
   DLIOM_HIP_TRY(hipGetLastError());
+  if (device_out != nullptr) {
+    *device_out = img;
+    return DLIOM_OK;
+  }
   DLIOM_HIP_TRY(hipMemcpyAsync(out, img, static_cast<size_t>(bpp * pixels), hipMemcpyDeviceToHost, st));
   DLIOM_HIP_TRY(hipStreamSynchronize(st));
   ++ctx->host_syncs;
@@ -386,7 +395,50 @@ PoseD pose_from7(const double* p) {
   return r;
 }
 
+// ProjectToCvMat (submap_3d.cc:391-463) behind dliom_grid_project_to_image; device_image != nullptr: see run_xray
+int project_to_image(const dliom_grid* grid, const double transform7[7], uint8_t* image, int64_t capacity,
+                     const uint8_t** device_image, int32_t* width, int32_t* height, double* ox, double* oy, double* resolution) {
+  const PoseD g = pose_from7(transform7);
+  // yaw = GetYaw(transform) (transform.h:43-52): atan2 of the rotated unit x, in double
+  const double ux[3] = {1.0, 0.0, 0.0};
+  double dir[3];
+  qrot_d(g.q, ux, dir);
+  const double yaw = std::atan2(dir[1], dir[0]);
+  // Embed3D(Rigid2d::Rotation(-yaw)) (transform.h:110-115): AngleAxisd(-yaw, UnitZ) -> quaternion, then cast<float>
+  const double ha = 0.5 * -yaw, sh = std::sin(ha);
+  const QF yaw_q{static_cast<float>(std::cos(ha)), static_cast<float>(sh * 0.0), static_cast<float>(sh * 0.0),
+                 static_cast<float>(sh * 1.0)};
+  // Rigid3d::Rotation(transform.rotation()).cast<float>(), composed: Rigid3f product (rigid_transform.h:206-212)
+  const QF rot_q{static_cast<float>(g.q[0]), static_cast<float>(g.q[1]), static_cast<float>(g.q[2]), static_cast<float>(g.q[3])};
+  const QF q = qnormalized(qmul(yaw_q, rot_q));
+  const F3 t = add3(qrot(yaw_q, F3{0.f, 0.f, 0.f}), F3{0.f, 0.f, 0.f});
+  XrayTransform T;
+  T.q = Quat4{q.w, q.x, q.y, q.z};
+  T.t[0] = t.x;
+  T.t[1] = t.y;
+  T.t[2] = t.z;
+  const double res = grid->resolution;  // `double& resolution` in ProjectToCvMat
+  T.resolution = grid->resolution;
+  T.inv_resolution = static_cast<float>(1.f / res);  // double division, stored to float (submap_3d.cc:399)
+  T.threshold = obstructed_threshold();
+  XrayResult r;
+  const int s = run_xray(grid, T, false, image, capacity, &r, device_image);
+  *width = static_cast<int32_t>(r.width);
+  *height = static_cast<int32_t>(r.height);
+  *resolution = res;
+  *ox = r.min_x * res;  // int * double (submap_3d.cc:422-423)
+  *oy = r.min_y * res;
+  return s;
+}
+
 }  // namespace
+
+int project_to_image_on_device(const dliom_grid* grid, const double transform7[7], const uint8_t** image, int32_t* width,
+                               int32_t* height, double* ox, double* oy, double* resolution) {
+  *image = nullptr;  // stays so under an empty projection
+  return project_to_image(grid, transform7, nullptr, 0, image, width, height, ox, oy, resolution);
+}
+
 }  // namespace dliom
 
 using namespace dliom;
@@ -432,37 +484,7 @@ int dliom_grid_project_to_image(const dliom_grid* grid, const double transform7[
   if (grid == nullptr || transform7 == nullptr || width == nullptr || height == nullptr || ox == nullptr || oy == nullptr ||
       resolution == nullptr || capacity < 0)
     return DLIOM_ERR_INVALID_ARGUMENT;
-  const PoseD g = pose_from7(transform7);
-  // yaw = GetYaw(transform) (transform.h:43-52): atan2 of the rotated unit x, in double
-  const double ux[3] = {1.0, 0.0, 0.0};
-  double dir[3];
-  qrot_d(g.q, ux, dir);
-  const double yaw = std::atan2(dir[1], dir[0]);
-  // Embed3D(Rigid2d::Rotation(-yaw)) (transform.h:110-115): AngleAxisd(-yaw, UnitZ) -> quaternion, then cast<float>
-  const double ha = 0.5 * -yaw, sh = std::sin(ha);
-  const QF yaw_q{static_cast<float>(std::cos(ha)), static_cast<float>(sh * 0.0), static_cast<float>(sh * 0.0),
-                 static_cast<float>(sh * 1.0)};
-  // Rigid3d::Rotation(transform.rotation()).cast<float>(), composed: Rigid3f product (rigid_transform.h:206-212)
-  const QF rot_q{static_cast<float>(g.q[0]), static_cast<float>(g.q[1]), static_cast<float>(g.q[2]), static_cast<float>(g.q[3])};
-  const QF q = qnormalized(qmul(yaw_q, rot_q));
-  const F3 t = add3(qrot(yaw_q, F3{0.f, 0.f, 0.f}), F3{0.f, 0.f, 0.f});
-  XrayTransform T;
-  T.q = Quat4{q.w, q.x, q.y, q.z};
-  T.t[0] = t.x;
-  T.t[1] = t.y;
-  T.t[2] = t.z;
-  const double res = grid->resolution;  // `double& resolution` in ProjectToCvMat
-  T.resolution = grid->resolution;
-  T.inv_resolution = static_cast<float>(1.f / res);  // double division, stored to float (submap_3d.cc:399)
-  T.threshold = obstructed_threshold();
-  XrayResult r;
-  const int s = run_xray(grid, T, false, image, capacity, &r);
-  *width = static_cast<int32_t>(r.width);
-  *height = static_cast<int32_t>(r.height);
-  *resolution = res;
-  *ox = r.min_x * res;  // int * double (submap_3d.cc:422-423)
-  *oy = r.min_y * res;
-  return s;
+  return project_to_image(grid, transform7, image, capacity, nullptr, width, height, ox, oy, resolution);
 }
 
 }  // extern "C"

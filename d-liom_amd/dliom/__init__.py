@@ -2673,6 +2673,16 @@ class FeatureIndex:
         _check(self._L.dliom_feature_index_add(self.h, int(key), _p(d, _f32p), _p(k, _f32p), len(d), float(ox), float(oy),
                                                float(resolution)), "dliom_feature_index_add")
 
+    def add_from_grid(self, key, grid, pose, options):
+        """dliom_feature_index_add_from_grid: project, binarise, erode, detect, describe and store, all in HBM (options:
+        surf_options()) -> (count, ox, oy, resolution)"""
+        p = _f64(pose)
+        n, ox, oy, res = C.c_int32(), C.c_double(), C.c_double(), C.c_double()
+        _check(self._L.dliom_feature_index_add_from_grid(self.h, int(key), grid.h, _p(p, _f64p), C.byref(options), C.byref(n),
+                                                         C.byref(ox), C.byref(oy), C.byref(res)),
+               "dliom_feature_index_add_from_grid")
+        return int(n.value), ox.value, oy.value, res.value
+
     def remove(self, key):
         _check(self._L.dliom_feature_index_remove(self.h, int(key)), "dliom_feature_index_remove")
 
@@ -2704,3 +2714,73 @@ def feature_ransac(ctx, from_xy, to_xy, threshold, seed=0):
     _check(ctx._L.dliom_feature_ransac(ctx.h, _p(p, _f32p), _p(q, _f32p), len(p), float(threshold), int(seed), C.byref(r),
                                        _p(mask, _u8p)), "dliom_feature_ransac")
     return {k: getattr(r, k) for k, _ in FeatureRansacResult._fields_}, mask
+
+
+# ---- submap image features (dliom.h "submap image features") ------------------------------------------------------------
+class SurfOptions(C.Structure):
+    _fields_ = [("binary_threshold", C.c_int), ("structure_element_size", C.c_int), ("hessian_threshold", C.c_double),
+                ("n_octaves", C.c_int), ("n_octave_layers", C.c_int), ("extended", C.c_int), ("upright", C.c_int)]
+
+
+SURF_MAX_PIXELS, SURF_MAX_KEYPOINTS, SURF_MAX_STRUCTURE_ELEMENT = 1 << 23, 65536, 33
+SURF_DESCRIPTOR_SIZE, SURF_KEYPOINT_FLOATS = 64, 7
+SYMBOLS += [
+    ("dliom_surf_default_options", SurfOptions, []),
+    ("dliom_image_binarize_erode", C.c_int, [_vp, _u8p, C.c_int32, C.c_int32, C.POINTER(SurfOptions), _u8p]),
+    ("dliom_surf_layer", C.c_int, [_vp, _u8p, C.c_int32, C.c_int32, C.c_int, C.c_int, _f32p, _f32p, _i32p, _i32p]),
+    ("dliom_surf_detect_and_compute", C.c_int, [_vp, _u8p, C.c_int32, C.c_int32, C.POINTER(SurfOptions), _f32p, _f32p,
+                                                C.c_int32, _i32p]),
+    ("dliom_feature_index_add_from_grid", C.c_int, [_vp, C.c_int64, _vp, _f64p, C.POINTER(SurfOptions), _i32p, _f64p, _f64p,
+                                                    _f64p]),
+]
+
+
+def surf_options(binary_threshold=200, structure_element_size=3, hessian_threshold=400.0, n_octaves=4, n_octave_layers=3,
+                 extended=0, upright=0):
+    """dliom_surf_options; the defaults are dliom_surf_default_options()'s (pose_graph.lua:27-28, constraint_builder_3d.h:206)"""
+    return SurfOptions(int(binary_threshold), int(structure_element_size), float(hessian_threshold), int(n_octaves),
+                       int(n_octave_layers), int(extended), int(upright))
+
+
+def _image(image):
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    if img.ndim != 2:
+        raise ValueError("an image is (height, width) bytes")
+    return img
+
+
+def image_binarize_erode(ctx, image, options):
+    """dliom_image_binarize_erode -> the eroded image (height, width) uint8"""
+    img = _image(image)
+    out = np.zeros_like(img)
+    _check(ctx._L.dliom_image_binarize_erode(ctx.h, _p(img, _u8p), img.shape[1], img.shape[0], C.byref(options), _p(out, _u8p)),
+           "dliom_image_binarize_erode")
+    return out
+
+
+def surf_layer(ctx, image, octave, layer):
+    """dliom_surf_layer -> (det, trace), each (rows, cols) float32"""
+    img = _image(image)
+    rows, cols = C.c_int32(), C.c_int32()
+    args = (ctx.h, _p(img, _u8p), img.shape[1], img.shape[0], int(octave), int(layer))
+    _check(ctx._L.dliom_surf_layer(*args, None, None, C.byref(rows), C.byref(cols)), "dliom_surf_layer")
+    det, trace = np.zeros((rows.value, cols.value), np.float32), np.zeros((rows.value, cols.value), np.float32)
+    if det.size:
+        _check(ctx._L.dliom_surf_layer(*args, _p(det, _f32p), _p(trace, _f32p), C.byref(rows), C.byref(cols)), "dliom_surf_layer")
+    return det, trace
+
+
+def surf_detect_and_compute(ctx, image, options, capacity=None):
+    """dliom_surf_detect_and_compute -> (keypoints (n, 7) float32: x, y, size, angle, response, octave, laplacian sign;
+    descriptors (n, 64) float32).  capacity None: the size query first."""
+    img = _image(image)
+    n = C.c_int32()
+    args = (ctx.h, _p(img, _u8p), img.shape[1], img.shape[0], C.byref(options))
+    if capacity is None:
+        _check(ctx._L.dliom_surf_detect_and_compute(*args, None, None, 0, C.byref(n)), "dliom_surf_detect_and_compute")
+        capacity = n.value
+    kp = np.zeros((capacity, SURF_KEYPOINT_FLOATS), np.float32)
+    desc = np.zeros((capacity, SURF_DESCRIPTOR_SIZE), np.float32)
+    _check(ctx._L.dliom_surf_detect_and_compute(*args, _p(kp, _f32p), _p(desc, _f32p), capacity, C.byref(n)),
+           "dliom_surf_detect_and_compute")
+    return kp[:n.value], desc[:n.value]

@@ -1507,6 +1507,150 @@ int dliom_feature_index_knn(dliom_feature_index* index, int64_t query_key, int64
 int dliom_feature_ransac(dliom_ctx* ctx, const float* from_xy, const float* to_xy, int num_matches, double threshold,
                          uint64_t seed, dliom_feature_ransac_result* result, unsigned char* inlier_mask);
 
+/* ---- submap image features ----------------------------------------------------------------------
+ * The first half of ConstraintBuilder3D::ExtractFeaturesForSubmap (constraint_builder_3d.cc:451-458): cv::threshold,
+ * cv::erode and SURF::detectAndCompute on the image dliom_grid_project_to_image makes, so that loop detection runs from
+ * a grid in HBM to `matched_submaps` without the image or the features leaving the device.
+ * PARITY UNPINNED AGAINST OPENCV: OpenCV (and its non-free xfeatures2d) is neither in the reference tree nor a
+ * dependency here, so its result cannot be pinned.  What is pinned, bit for bit against a CPU model (tests/cpp/surf_model.cc), is this definition:
+ * SURF as OpenCV parametrises it (hessianThreshold 400, constraint_builder_3d.h:206; 4 octaves, 3 layers an octave, 64
+ * dimensions, oriented).
+ *
+ * Arithmetic.  Every float operation is rounded on its own (no contraction), in the order written, parentheses first
+ * and otherwise left to right.  round() is round-half-to-even (cvRound, rintf).  No transcendental function runs on
+ * the device: the two Gaussian tables are made on the host when the library is loaded, with the C library's exp().
+ * W, H: the image's width and height; pixels are bytes, row-major.
+ *
+ * (1) Binarise and erode (:451-455).  b(x, y) = 255 if pixel > binary_threshold else 0.  With k =
+ * structure_element_size (1 <= k <= DLIOM_SURF_MAX_STRUCTURE_ELEMENT) and a = k / 2, e(x, y) = min of b(x + dx - a,
+ * y + dy - a) over 0 <= dx, dy < k, positions outside the image taking no part.  k = 1 is the identity.  The projected
+ * image's empty pixels are 224, above the reference's threshold of 200, hence white: that is the reference.
+ *
+ * (2) Integral image.  S is (H + 1) x (W + 1) 32-bit integers, S(x, y) = sum of e over [0, x) x [0, y); exact, so any
+ * summation order gives it.  W * H > DLIOM_SURF_MAX_PIXELS (2^23; 2^23 * 255 < 2^31) is DLIOM_ERR_TOO_LARGE.  The sum
+ * over a box with corners (x1, y1), (x2, y2) is S(x1, y1) + S(x2, y2) - S(x1, y2) - S(x2, y1) modulo 2^32, as an int.
+ *
+ * (3) Layers.  Octave o < n_octaves, layer l in [0, n_octave_layers + 1]: size = (9 + 6 l) << o, step = 1 << o.  A
+ * template (DLIOM_SURF_TEMPLATE_*: rows of {x1, y1, x2, y2, weight} on a 9 x 9 pattern) is resized with ratio =
+ * (float)size / 9.0f: every corner c becomes round(ratio * (float)c), and the box weight w = (float)weight /
+ * (float)((x2 - x1) * (y2 - y1)) of the resized corners.  A template's response at (x0, y0) is r = 0.0f; r = r +
+ * (float)(box sum at the corners shifted by (x0, y0)) * w, box after box in the table's order.  The layer's arrays det
+ * and trace have H / step rows and W / step columns and hold 0.0f where there is no sample.  If size <= H and size <=
+ * W the samples are i < 1 + (H - size) / step, j < 1 + (W - size) / step, taken at (x0, y0) = (j step, i step) and
+ * stored at row i + m, column j + m, m = (size / 2) / step:
+ *     det = dxx * dyy - (0.81f * dxy) * dxy;   trace = dxx + dyy.
+ *
+ * (4) Maxima, in the layers l = 1 .. n_octave_layers.  With margin = (size_{l+1} / 2) / step + 1, an array position
+ * (i, j) with margin <= i < rows - margin, margin <= j < cols - margin is a candidate iff v = det_l(i, j) >
+ * (float)hessian_threshold and v > each of its 26 neighbours N(s, r, c) = det_{l+s}(i + r, j + c).  Refinement, in
+ * float:
+ *     bx = -((N(0,0,1) - N(0,0,-1)) * 0.5f);  by = -((N(0,1,0) - N(0,-1,0)) * 0.5f);  bs = -((N(1,0,0) - N(-1,0,0)) * 0.5f);
+ *     axx = (N(0,0,-1) - 2.0f * v) + N(0,0,1);  ayy = (N(0,-1,0) - 2.0f * v) + N(0,1,0);  ass = (N(-1,0,0) - 2.0f * v) + N(1,0,0);
+ *     axy = (((N(0,1,1) - N(0,1,-1)) - N(0,-1,1)) + N(0,-1,-1)) * 0.25f;
+ *     axs = (((N(1,0,1) - N(1,0,-1)) - N(-1,0,1)) + N(-1,0,-1)) * 0.25f;
+ *     ays = (((N(1,1,0) - N(1,-1,0)) - N(-1,1,0)) + N(-1,-1,0)) * 0.25f;
+ * then Cramer's rule in double on a = axx, b = axy, c = axs, d = ayy, e = ays, f = ass, p = bx, q = by, r = bs:
+ *     c00 = d * f - e * e;  c01 = b * f - c * e;  c02 = b * e - c * d;  D = (a * c00 - b * c01) + c * c02;
+ *     qfer = q * f - e * r;  qedr = q * e - d * r;  brqc = b * r - q * c;
+ *     x0 = ((p * c00 - b * qfer) + c * qedr) / D;  x1 = ((a * qfer - p * c01) + c * brqc) / D;
+ *     x2 = ((a * (d * r - q * e) - b * brqc) + p * c02) / D;
+ * The candidate is kept iff D != 0 and, with (t0, t1, t2) = (float)(x0, x1, x2), not all t are 0 and every |t| <= 1.
+ *     x = ((float)(step (j - m)) + (float)(size - 1) * 0.5f) + t0 * (float)step,   y likewise from i and t1,
+ *     size = (float)round((float)size_l + t2 * (float)(size_l - size_{l-1})),
+ *     response = v,  laplacian sign = (trace_l(i, j) > 0) - (trace_l(i, j) < 0),  angle = -1 until step 6.
+ *
+ * (5) Order.  By response descending; ties to the lowest generation index (o << 25 | l << 23 | i cols + j), which is
+ * unique.  More than DLIOM_SURF_MAX_KEYPOINTS kept candidates: DLIOM_ERR_CAPACITY.
+ *
+ * (6) Orientation.  s = size * 1.2f / 9.0f; side = 2 round(2.0f * s).  H + 1 < side or W + 1 < side: the key point is
+ * dropped.  The wavelets DLIOM_SURF_WAVELET_X / _Y (on a 4 x 4 pattern) are resized to `side` as in (3).  g = the
+ * Gaussian table of 13 entries, sigma 2.5: t_n = exp(-(x_n * x_n) / (2.0 * sigma * sigma)) with x_n = n - (N - 1) * 0.5
+ * in double, g_n = (float)(t_n / (t_0 + t_1 + ...)) summed in index order.  For i = -6 .. 6 (outer) and j = -6 .. 6
+ * with i i + j j <= 36, the DLIOM_SURF_ORI_SAMPLES offsets:
+ *     px = round((x + (float)i * s) - (float)(side - 1) / 2.0f);  py = round((y + (float)j * s) - (float)(side - 1) / 2.0f);
+ * the sample is skipped unless 0 <= px < W + 1 - side and 0 <= py < H + 1 - side; else X = (response of wavelet X at
+ * (px, py)) * (g[i + 6] * g[j + 6]), Y likewise, and A = round(fastAtan2(Y, X)).  No sample: dropped.  fastAtan2(y, x),
+ * degrees, with p1, p3, p5, p7 = 0.9997878412794807f, -0.3258083974640975f, 0.1555786518463281f,
+ * -0.04432655554792128f, each times (float)(180 / pi):
+ *     c = min(|x|, |y|) / (max(|x|, |y|) + (float)DBL_EPSILON);  c2 = c * c;  a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+ *     |x| < |y|: a = 90.0f - a;  then x < 0: a = 180.0f - a;  then y < 0: a = 360.0f - a.
+ * Windows w = 0, 5, .., 355: sumx, sumy start at 0.0f and take, sequentially in sample order, the X and Y of every
+ * sample with d = |A - w| < 30 or d > 330.  The best window has the greatest sumx * sumx + sumy * sumy above 0, ties to
+ * the lowest w; with n = sqrtf(bestx * bestx + besty * besty), n == 0 (also: no window above 0): dropped.
+ * angle = fastAtan2(-besty, bestx); the descriptor's frame is cos = bestx / n, sin = besty / n.
+ *
+ * (7) Descriptor.  w = (int)(21.0f * s); off = -((float)(w - 1) / 2.0f); sx = (x + off * cos) + off * sin; sy = (y -
+ * off * sin) + off * cos.  Window pixel (i, j), 0 <= i, j < w, is e at (round((sx + (float)i * sin) + (float)j * cos),
+ * round((sy + (float)i * cos) - (float)j * sin)), each coordinate clamped to the image.  The 21 x 21 patch, exact in
+ * integers: with ov(k, p) = min(21 k + 21, w (p + 1)) - max(21 k, w p) where positive, patch(pi, pj) = (2 sum + w w) /
+ * (2 w w), sum = the sum over (ki, kj) of ov(ki, pi) ov(kj, pj) window(ki, kj).  h = the Gaussian table of 20 entries,
+ * sigma 3.3.  For 0 <= i, j < 20:
+ *     DX(i, j) = (float)(patch(i, j+1) - patch(i, j) + patch(i+1, j+1) - patch(i+1, j)) * (h[i] * h[j]);
+ *     DY(i, j) = (float)(patch(i+1, j) - patch(i, j) + patch(i+1, j+1) - patch(i, j+1)) * (h[i] * h[j]).
+ * Sub-region (a, b), 0 <= a, b < 4, holds rows 5a .. 5a+4 and columns 5b .. 5b+4; its four sums of DX, DY, |DX|, |DY|
+ * start at 0.0f and run in row-major order; they are values 4 (4a + b) .. + 3 of the descriptor.  q = 0.0f; q = q +
+ * v * v over the 64 values in order; every value is then multiplied by 1.0f / (sqrtf(q) + (float)DBL_EPSILON).
+ *
+ * (8) Dropped key points leave the list; the order of the rest is kept.
+ *
+ * (9) Options.  extended and upright are reserved: 0.  n_octaves in [1, 4], n_octave_layers in [1, 3],
+ * hessian_threshold finite and >= 0, binary_threshold in [0, 255], structure_element_size as in (1); anything else is
+ * DLIOM_ERR_INVALID_ARGUMENT.
+ *
+ * No floating-point atomics anywhere: two calls on one input give the same bytes. */
+#define DLIOM_SURF_MAX_PIXELS (1 << 23)
+#define DLIOM_SURF_MAX_KEYPOINTS 65536
+#define DLIOM_SURF_MAX_STRUCTURE_ELEMENT 33
+#define DLIOM_SURF_DESCRIPTOR_SIZE 64
+#define DLIOM_SURF_KEYPOINT_FLOATS 7 /* x, y, size, angle, response, octave, laplacian sign */
+#define DLIOM_SURF_SIZE0 9
+#define DLIOM_SURF_SIZE_INCREMENT 6
+#define DLIOM_SURF_ORI_RADIUS 6
+#define DLIOM_SURF_ORI_SAMPLES 113 /* offsets with i i + j j <= 36 */
+#define DLIOM_SURF_ORI_SIGMA 2.5
+#define DLIOM_SURF_PATCH 20
+#define DLIOM_SURF_DESCRIPTOR_SIGMA 3.3
+#define DLIOM_SURF_TEMPLATE_DXX {{0, 2, 3, 7, 1}, {3, 2, 6, 7, -2}, {6, 2, 9, 7, 1}}
+#define DLIOM_SURF_TEMPLATE_DYY {{2, 0, 7, 3, 1}, {2, 3, 7, 6, -2}, {2, 6, 7, 9, 1}}
+#define DLIOM_SURF_TEMPLATE_DXY {{1, 1, 4, 4, 1}, {5, 1, 8, 4, -1}, {1, 5, 4, 8, -1}, {5, 5, 8, 8, 1}}
+#define DLIOM_SURF_WAVELET_X {{0, 0, 2, 4, -1}, {2, 0, 4, 4, 1}}
+#define DLIOM_SURF_WAVELET_Y {{0, 0, 4, 2, 1}, {0, 2, 4, 4, -1}}
+typedef struct dliom_surf_options {
+  int binary_threshold;       /* cv_binary_threshold (pose_graph.lua:27: 200) */
+  int structure_element_size; /* cv_structure_element_size (pose_graph.lua:28: 3) */
+  double hessian_threshold;   /* 400 */
+  int n_octaves, n_octave_layers, extended, upright; /* 4, 3, 0, 0 */
+} dliom_surf_options;
+dliom_surf_options dliom_surf_default_options(void);
+/* Step 1 alone: host bytes in and out (width * height each).  width or height 0 is DLIOM_OK and writes nothing. */
+int dliom_image_binarize_erode(dliom_ctx* ctx, const uint8_t* image, int32_t width, int32_t height,
+                               const dliom_surf_options* options, uint8_t* out);
+/* Diagnostic for the tests: steps 2 and 3 for one layer on an image taken as it is (no step 1).  octave in [0, 3],
+ * layer in [0, 4].  *rows, *cols: the arrays' size; det and trace (rows * cols floats each) may both be NULL for the
+ * size alone. */
+int dliom_surf_layer(dliom_ctx* ctx, const uint8_t* image, int32_t width, int32_t height, int octave, int layer, float* det,
+                     float* trace, int32_t* rows, int32_t* cols);
+/* Steps 1-8 on a caller's image.  keypoints: DLIOM_SURF_KEYPOINT_FLOATS floats a key point; descriptors:
+ * DLIOM_SURF_DESCRIPTOR_SIZE floats a key point; capacity: key points the buffers hold.  *count = the key points
+ * found; keypoints == NULL and descriptors == NULL asks for the count alone; *count > capacity is DLIOM_ERR_CAPACITY
+ * (nothing written).  More than DLIOM_SURF_MAX_KEYPOINTS candidates (step 5) is DLIOM_ERR_CAPACITY whatever the
+ * capacity, with *count = the candidates. */
+int dliom_surf_detect_and_compute(dliom_ctx* ctx, const uint8_t* image, int32_t width, int32_t height,
+                                  const dliom_surf_options* options, float* keypoints, float* descriptors, int32_t capacity,
+                                  int32_t* count);
+/* ExtractFeaturesForSubmap's first half into the index: project `grid` (dliom_grid_project_to_image), then steps 1-8,
+ * and store the set under `key` with the key points' (x, y) -- neither the image nor the features leave HBM.  The
+ * stored set equals dliom_grid_project_to_image -> dliom_surf_detect_and_compute -> dliom_feature_index_add bit for
+ * bit.  The index must have descriptor size 64 and share the grid's context.  An empty projection (0 x 0) or an image
+ * too small for any layer stores an empty set (later DLIOM_FEATURE_TOO_FEW_KEYPOINTS, as :476-483).  count, ox, oy,
+ * resolution (each may be NULL): the set's size and the image's corner and metres a pixel.  DLIOM_ERR_CAPACITY: a
+ * projection above DLIOM_XRAY_MAX_PIXELS, or more than DLIOM_SURF_MAX_KEYPOINTS candidates; DLIOM_ERR_TOO_LARGE: an image
+ * above DLIOM_SURF_MAX_PIXELS; DLIOM_ERR_INVALID_ARGUMENT: a NULL argument, a duplicate key, another descriptor size or
+ * context, refused options.  On every error nothing is stored and count, ox, oy, resolution are not written. */
+int dliom_feature_index_add_from_grid(dliom_feature_index* index, int64_t key, const dliom_grid* grid,
+                                      const double transform7[7], const dliom_surf_options* options, int32_t* count, double* ox,
+                                      double* oy, double* resolution);
+
 /* Per-context choices a caller may make; none of them changes a result (every kernel variant is parity-tested).  The
  * library never reads the environment (tuning experiments live in `make experiments` builds only). */
 enum {
