@@ -1313,8 +1313,21 @@ struct OptimizationProblemOptions {  // proto/optimization_problem_options.proto
   // 335-338): 0 is that.  Upstream's behaviour is huber_scale > 0 (basic_config_3d.lua:108 sets 1e2, campus.lua:20
   // 1e5): HuberLoss on the INTER_SUBMAP constraints.
   double huber_scale = 0.;
+  // Landmarks are opt-in: false keeps the refusal of a non-empty landmark_nodes that callers of the earlier adapter
+  // rely on; true adds AddLandmarkCostFunctions (optimization_problem_3d.cc:124-186).
+  bool use_landmarks = false;
 };
-struct LandmarkNode {};  // pose_graph_interface.h: landmarks are not covered, Solve refuses a non-empty map
+struct LandmarkNode {  // pose_graph_interface.h:57-67; times in ticks of 100 ns
+  struct LandmarkObservation {
+    int trajectory_id;
+    int64_t time;
+    transform::Rigid3d landmark_to_tracking_transform;
+    double translation_weight;
+    double rotation_weight;
+  };
+  std::vector<LandmarkObservation> landmark_observations;
+  common::optional<transform::Rigid3d> global_landmark_pose;
+};
 struct TrajectoryData {  // pose_graph_interface.h:76-80; the first two are stored and unused, as in the fork
   double gravity_constant = 9.8;
   std::array<double, 4> imu_calibration{{1., 0., 0., 0.}};
@@ -1371,12 +1384,12 @@ inline transform::Rigid3d Interpolate(int64_t start_time, const transform::Rigid
 }
 }  // namespace fixed_frame
 
-// OptimizationProblem3D (optimization_problem_3d.h:54-132, .cc:196-589) over dliom_pose_graph_solve_terms.  MapById is a
+// OptimizationProblem3D (optimization_problem_3d.h:54-132, .cc:196-589) over dliom_pose_graph_solve_landmarks.  MapById is a
 // std::map ordered like it (trajectory, index); Append continues a trajectory's indices; MapByTime is a std::map by time
 // a trajectory.  The IMU, odometry and local-SLAM terms are commented out in the fork's Solve (:350-489), so that data
 // is stored and unused.  The fixed-frame pose constraints (:491-548) are live code there and are built here; so is the
-// loss the fork left out (options.huber_scale).  Landmarks are not covered: a landmark residual couples two nodes, which
-// breaks the node elimination the device solve rests on; Solve refuses a non-empty landmark_nodes.
+// loss the fork left out (options.huber_scale).  Landmarks (:124-186) are built with options.use_landmarks; without it
+// Solve refuses a non-empty landmark_nodes.
 class OptimizationProblem3D {
  public:
   struct Constraint {  // PoseGraphInterface::Constraint
@@ -1436,7 +1449,8 @@ class OptimizationProblem3D {
   void Solve(const std::vector<Constraint>& constraints, const std::set<int>& frozen_trajectories,
              const std::map<std::string, LandmarkNode>& landmark_nodes) {
     if (node_data_.empty()) return;  // nothing to optimize
-    if (!landmark_nodes.empty()) Check(DLIOM_ERR_INVALID_ARGUMENT, "OptimizationProblem3D::Solve: landmarks are not supported");
+    if (!landmark_nodes.empty() && !options_.use_landmarks)
+      Check(DLIOM_ERR_INVALID_ARGUMENT, "OptimizationProblem3D::Solve: landmarks are not supported");
     if (submap_data_.empty()) Check(DLIOM_ERR_INVALID_ARGUMENT, "OptimizationProblem3D::Solve: CHECK(!submap_data_.empty())");
     std::map<SubmapId, int32_t> submap_index;
     std::map<NodeId, int32_t> node_index;
@@ -1497,21 +1511,100 @@ class OptimizationProblem3D {
       c.rotation_weight = options_.fixed_frame_pose_rotation_weight;
       frame_constraints.push_back(c);
     }
+    LandmarkBlocks blocks = CompactLandmarks(frozen_trajectories, landmark_nodes);
+    const std::vector<std::string>& landmark_ids = blocks.ids;
+    std::vector<double>& landmark_poses = blocks.poses;
+    const std::vector<unsigned char>& landmark_constant = blocks.constant;
+    const std::vector<dliom_pose_graph_landmark_observation>& observations = blocks.observations;
+    const dliom_pose_graph_landmarks landmarks = {static_cast<int>(landmark_ids.size()), landmark_poses.data(), landmark_constant.data(),
+                                                  static_cast<int64_t>(observations.size()), observations.data()};
     const dliom_pose_graph_terms terms = {static_cast<int>(frame_trajectories.size()), frame_poses.data(),
                                           static_cast<int64_t>(frame_constraints.size()), frame_constraints.data(),
                                           options_.huber_scale, inter_submap.data()};
     const dliom_pose_graph_options options = {options_.fix_z_in_3d ? 1 : 0, options_.use_nonmonotonic_steps ? 1 : 0,
                                               options_.max_num_iterations, options_.num_threads};
-    Check(dliom_pose_graph_solve_terms(context_->get(), &options, static_cast<int>(submap_index.size()), submap_poses.data(),
-                                       submap_constant.data(), 0, static_cast<int>(node_index.size()), node_poses.data(),
-                                       node_constant.data(), static_cast<int64_t>(compact.size()), compact.data(), &terms, &summary_),
-          "dliom_pose_graph_solve_terms");
+    Check(dliom_pose_graph_solve_landmarks(context_->get(), &options, static_cast<int>(submap_index.size()), submap_poses.data(),
+                                           submap_constant.data(), 0, static_cast<int>(node_index.size()), node_poses.data(),
+                                           node_constant.data(), static_cast<int64_t>(compact.size()), compact.data(), &terms,
+                                           &landmarks, &summary_),
+          "dliom_pose_graph_solve_landmarks");
     size_t at = 0;  // :578-588: store the result
     for (auto& id_data : submap_data_) id_data.second.global_pose = transform::Rigid3d::FromArray(&submap_poses[7 * at++]);
     at = 0;
     for (auto& id_data : node_data_) id_data.second.global_pose = transform::Rigid3d::FromArray(&node_poses[7 * at++]);
     for (size_t f = 0; f < frame_trajectories.size(); ++f)
       trajectory_data_.at(frame_trajectories[f]).fixed_frame_origin_in_map = transform::Rigid3d::FromArray(&frame_poses[7 * f]);
+    for (size_t l = 0; l < landmark_ids.size(); ++l) landmark_data_[landmark_ids[l]] = transform::Rigid3d::FromArray(&landmark_poses[7 * l]);
+  }
+
+  // :124-186 AddLandmarkCostFunctions on the host: the landmarks that are used, their start values and constant flags,
+  // and the observations that have a node before and a node after them, on node indices in MapById order.  Touches no
+  // device.
+  struct LandmarkBlocks {
+    std::vector<std::string> ids;
+    std::vector<double> poses;  // 7 a landmark
+    std::vector<unsigned char> constant;
+    std::vector<dliom_pose_graph_landmark_observation> observations;
+  };
+  LandmarkBlocks CompactLandmarks(const std::set<int>& frozen_trajectories, const std::map<std::string, LandmarkNode>& landmark_nodes) const {
+    LandmarkBlocks blocks;
+    std::vector<std::string>& landmark_ids = blocks.ids;
+    std::vector<double>& landmark_poses = blocks.poses;
+    std::vector<unsigned char>& landmark_constant = blocks.constant;
+    std::vector<dliom_pose_graph_landmark_observation>& observations = blocks.observations;
+    std::map<NodeId, int32_t> node_index;
+    std::vector<double> node_poses;
+    for (const auto& id_data : node_data_) {
+      node_index.emplace(id_data.first, static_cast<int32_t>(node_index.size()));
+      const std::array<double, 7> pose = id_data.second.global_pose.ToArray();
+      node_poses.insert(node_poses.end(), pose.begin(), pose.end());
+    }
+    const bool freeze_landmarks = !frozen_trajectories.empty();  // :169-174 with :343-345
+    for (const auto& landmark_node : landmark_nodes) {
+      // landmarks that were not optimized for localization are not used (:131-134)
+      if (!landmark_node.second.global_landmark_pose.has_value() && freeze_landmarks) continue;
+      bool added = false;
+      for (const LandmarkNode::LandmarkObservation& observation : landmark_node.second.landmark_observations) {
+        const auto begin_of_trajectory = node_data_.lower_bound(NodeId{observation.trajectory_id, 0});
+        const auto end_of_trajectory = node_data_.lower_bound(NodeId{observation.trajectory_id + 1, 0});
+        if (begin_of_trajectory == end_of_trajectory) continue;  // no node at all (the reference dereferences end() here)
+        if (observation.time < begin_of_trajectory->second.time) continue;  // made before the trajectory was created
+        auto next = begin_of_trajectory;  // MapById::lower_bound(trajectory, time): the first node not before the observation
+        while (next != end_of_trajectory && next->second.time < observation.time) ++next;
+        if (next == end_of_trajectory) continue;  // the next node has not been added yet
+        if (next == begin_of_trajectory) next = std::next(next);
+        if (next == end_of_trajectory) continue;  // a trajectory of one node has no pair (the reference dereferences end())
+        const auto prev = std::prev(next);
+        dliom_pose_graph_landmark_observation o = {};
+        o.landmark = static_cast<int32_t>(landmark_ids.size()) - (added ? 1 : 0);
+        o.prev_node = node_index.at(prev->first);
+        o.next_node = node_index.at(next->first);
+        // common::ToSeconds of both differences (landmark_cost_function_3d.h:85-87)
+        o.interpolation_parameter = (static_cast<double>(observation.time - prev->second.time) / 1e7) /
+                                    (static_cast<double>(next->second.time - prev->second.time) / 1e7);
+        const std::array<double, 7> z = observation.landmark_to_tracking_transform.ToArray();
+        for (int k = 0; k < 7; ++k) o.landmark_to_tracking7[k] = z[k];
+        o.translation_weight = observation.translation_weight;
+        o.rotation_weight = observation.rotation_weight;
+        if (!added) {  // the block's start value: the stored pose, or the first used observation's (:158-168)
+          std::array<double, 7> start;
+          if (landmark_node.second.global_landmark_pose.has_value()) {
+            start = landmark_node.second.global_landmark_pose.value().ToArray();
+          } else {
+            Check(dliom_pose_graph_initial_landmark_pose(&node_poses[7 * static_cast<size_t>(o.prev_node)],
+                                                         &node_poses[7 * static_cast<size_t>(o.next_node)], o.interpolation_parameter,
+                                                         o.landmark_to_tracking7, start.data()),
+                  "dliom_pose_graph_initial_landmark_pose");
+          }
+          landmark_ids.push_back(landmark_node.first);
+          landmark_poses.insert(landmark_poses.end(), start.begin(), start.end());
+          landmark_constant.push_back(freeze_landmarks ? 1 : 0);
+          added = true;
+        }
+        observations.push_back(o);
+      }
+    }
+    return blocks;
   }
 
   const std::map<NodeId, NodeSpec3D>& node_data() const { return node_data_; }
@@ -1519,6 +1612,7 @@ class OptimizationProblem3D {
   const std::map<int, std::vector<sensor::ImuData>>& imu_data() const { return imu_data_; }
   const std::map<int, std::map<int64_t, sensor::FixedFramePoseData>>& fixed_frame_pose_data() const { return fixed_frame_pose_data_; }
   const std::map<int, TrajectoryData>& trajectory_data() const { return trajectory_data_; }
+  const std::map<std::string, transform::Rigid3d>& landmark_data() const { return landmark_data_; }
   const dliom_pose_graph_summary& summary() const { return summary_; }  // of the last Solve (ceres::Solver::Summary there)
 
  private:
@@ -1576,6 +1670,7 @@ class OptimizationProblem3D {
   std::map<NodeId, NodeSpec3D> node_data_;
   std::map<SubmapId, SubmapSpec3D> submap_data_;
   std::map<int, std::vector<sensor::ImuData>> imu_data_;
+  std::map<std::string, transform::Rigid3d> landmark_data_;
   dliom_pose_graph_summary summary_ = {};
 };
 }  // namespace optimization

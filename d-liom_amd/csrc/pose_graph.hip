@@ -19,12 +19,19 @@
 // The trust-region loop itself (Ceres 1.13 trust_region_minimizer.cc, levenberg_marquardt_strategy.cc,
 // trust_region_step_evaluator.cc -- third-party behaviour, restated for this configuration) runs on the host.
 // No floating-point atomics: every accumulation is a segmented sum in the order pose_graph_structure.h fixes.
+//
+// Landmark observations (LandmarkCostFunction3D, dliom_pose_graph_landmarks) couple two nodes and a landmark.  Those
+// nodes ("promoted") and the landmarks join the kept blocks; a residual block between kept blocks only -- a constraint of
+// a promoted node, an observation -- never enters the node elimination: it adds J_a^T J_b to S_ab directly
+// (pg_pairs_kernel, after the pair's elimination terms) and its J^T r reaches the right-hand side through the pose's
+// gradient.  An observation is linearised per (observation, block) with six dual parts (pg_observation_linearise_kernel).
 #include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "host_math.h"
 #include "internal.h"
 #include "pose_graph_structure.h"
 
@@ -120,6 +127,14 @@ __device__ inline Dual<N> dual_sin(const Dual<N>& f) {
   for (int i = 0; i < N; ++i) r.v[i] = c * f.v[i];
   return r;
 }
+template <int N>
+__device__ inline Dual<N> dual_acos(const Dual<N>& f) {
+  Dual<N> r;
+  r.a = acos(f.a);
+  const double scale = -1.0 / sqrt(1.0 - f.a * f.a);
+  for (int i = 0; i < N; ++i) r.v[i] = scale * f.v[i];
+  return r;
+}
 
 // a * b of Eigen::Quaternion (w x y z)
 template <int N>
@@ -164,6 +179,27 @@ __device__ inline void spa_residual(const Dual<N> qi[4], const Dual<N> ti[3], co
     e[k] = (constant<N>(zbar[k]) - h[k]) * translation_weight;
     e[3 + k] = (scale * product[1 + k]) * rotation_weight;
   }
+}
+
+// InterpolateNodes3D (cost_helpers_impl.h:103-153): SlerpQuaternions as written there -- the dot product in its order, the
+// linear scales from |cos theta| >= 1 - 1e-5 on, next_scale negated for cos theta < 0, no renormalisation -- and the
+// translation prev + t (next - prev).
+template <int N>
+__device__ inline void interpolate_nodes(const Dual<N> prev_q[4], const Dual<N> prev_t[3], const Dual<N> next_q[4],
+                                         const Dual<N> next_t[3], double t, Dual<N> q[4], Dual<N> translation[3]) {
+  using D = Dual<N>;
+  const D cos_theta = prev_q[0] * next_q[0] + prev_q[1] * next_q[1] + prev_q[2] * next_q[2] + prev_q[3] * next_q[3];
+  const D abs_cos_theta = cos_theta.a < 0. ? -cos_theta : cos_theta;
+  D prev_scale = constant<N>(1. - t), next_scale = constant<N>(t);
+  if (abs_cos_theta.a < 1. - 1e-5) {
+    const D theta = dual_acos(abs_cos_theta);
+    const D sin_theta = dual_sin(theta);
+    prev_scale = dual_sin(theta * (1. - t)) / sin_theta;
+    next_scale = dual_sin(theta * t) / sin_theta;
+  }
+  if (cos_theta.a < 0.) next_scale = -next_scale;
+  for (int k = 0; k < 4; ++k) q[k] = prev_scale * prev_q[k] + next_scale * next_q[k];
+  for (int k = 0; k < 3; ++k) translation[k] = prev_t[k] + (next_t[k] - prev_t[k]) * t;
 }
 
 // ---- local parameterisations ------------------------------------------------------------------------------------------
@@ -265,9 +301,22 @@ struct Graph {
   double *model, *cost, *candidate_cost;  // a constraint
   double *step_squared, *x_squared, *gradient_max;  // a pose
   unsigned* flag;                         // non-zero: a non-positive pivot; later stages return at once
+  // Landmarks: the poses are the kept blocks, the nodes, then the landmarks; `column` then has 6 entries a pose.  The
+  // observations' Jacobian blocks (three 6 x 6 an observation: prev, next, landmark), residuals, costs and models lie
+  // behind the constraints' in `jacobian`, `residual`, `cost`, `model` and `candidate_cost`.
+  int num_landmarks, num_observations;
+  const double* observation_data;  // 10 an observation: landmark_to_tracking, the two weights, t
+  const int *observation_pose;     // 3 an observation: the poses of prev, next and the landmark
+  const int *observation_fixed, *node_promoted;  // node_promoted is null without landmarks
+  const int *pose_observation_start, *pose_observations, *pair_direct_start, *pair_direct_a, *pair_direct_b;
 };
 
 __device__ inline int kind_of(const Graph& g, int p) { return p < g.num_kept ? g.kind[p] : pg::kKindQuaternion; }
+__device__ inline int pose_count(const Graph& g) { return g.num_kept + g.num_nodes + g.num_landmarks; }
+// a block of the reduced system: a submap, a fixed frame, a promoted node or a landmark
+__device__ inline bool is_kept(const Graph& g, int p) {
+  return p < g.num_kept || (g.node_promoted != nullptr && (p >= g.num_kept + g.num_nodes || g.node_promoted[p - g.num_kept] != 0));
+}
 // 1/2 rho(s) of constraint c and the corrector's scaling
 __device__ inline double constraint_cost(const Graph& g, int c, double squared, double* scaling) {
   *scaling = 1.;
@@ -322,12 +371,61 @@ __global__ void __launch_bounds__(64) pg_linearise_kernel(Graph g) {
   }
 }
 
+// LandmarkCostFunction3D (landmark_cost_function_3d.h:55-75): SpaCostFunction3D's error between the interpolated node pose
+// (start) and the landmark (end).  N == 6: seeded with the tangent directions of block `seeded` (0 prev, 1 next, 2 the
+// landmark), so that the duals' parts are that block's tangent-space Jacobian; the scalar parts do not depend on it.
+template <int N>
+__device__ inline void evaluate_observation(const Graph& g, const double* poses, int o, int seeded, Dual<N> e[6]) {
+  Dual<N> t[3][3], q[3][4];
+  for (int block = 0; block < 3; ++block) {
+    const int p = g.observation_pose[3 * o + block];
+    const double* x = poses + 7 * static_cast<int64_t>(p);
+    for (int k = 0; k < 3; ++k) t[block][k] = constant<N>(x[k]);
+    for (int k = 0; k < 4; ++k) q[block][k] = constant<N>(x[3 + k]);
+    if constexpr (N == 6) {
+      if (block != seeded) continue;
+      const int mask = g.mask[p];
+      double j[12];
+      plus_jacobian(x + 3, pg::kKindQuaternion, j);
+      for (int k = 0; k < 3; ++k)
+        if ((mask >> k) & 1) t[block][k].v[k] = 1.;
+      for (int k = 0; k < 4; ++k)
+        for (int col = 0; col < 3; ++col)
+          if ((mask >> (3 + col)) & 1) q[block][k].v[3 + col] = j[k * 3 + col];
+    }
+  }
+  const double* data = g.observation_data + 10 * static_cast<int64_t>(o);
+  Dual<N> interpolated_q[4], interpolated_t[3];
+  interpolate_nodes<N>(q[0], t[0], q[1], t[1], data[9], interpolated_q, interpolated_t);
+  spa_residual<N>(interpolated_q, interpolated_t, q[2], t[2], data, data[7], data[8], e);
+}
+
+// One thread an (observation, block): the block's 6 x 6 Jacobian; the prev block's thread also writes the residual and the
+// cost (no loss on an observation).
+__global__ void __launch_bounds__(64) pg_observation_linearise_kernel(Graph g) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 3 * g.num_observations) return;
+  const int o = t / 3, block = t % 3;
+  Dual<6> e[6];
+  evaluate_observation<6>(g, g.x, o, block, e);
+  double* jac = g.jacobian + 72 * static_cast<int64_t>(g.num_constraints) + 36 * static_cast<int64_t>(t);
+  for (int k = 0; k < 6; ++k)
+    for (int i = 0; i < 6; ++i) jac[k * 6 + i] = e[k].v[i];
+  if (block != 0) return;
+  double squared = 0.;
+  for (int k = 0; k < 6; ++k) {
+    squared += e[k].a * e[k].a;
+    g.residual[6 * (static_cast<int64_t>(g.num_constraints) + o) + k] = e[k].a;
+  }
+  g.cost[g.num_constraints + o] = 0.5 * squared;
+}
+
 // One wavefront a pose: lanes 0..35 the diagonal block J^T J, lanes 36..41 the gradient J^T r, over the pose's
 // constraints in their fixed order.  set_scale: the iteration-0 column scaling 1 / (1 + ||J_col||).
 __global__ void __launch_bounds__(256) pg_pose_kernel(Graph g, int set_scale) {
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (p >= g.num_kept + g.num_nodes || lane >= 42) return;
+  if (p >= pose_count(g) || lane >= 42) return;
   const int side = p < g.num_kept ? 0 : 36;
   const int i = lane < 36 ? lane / 6 : lane - 36, j = lane < 36 ? lane % 6 : 0;
   double sum = 0.;
@@ -338,6 +436,18 @@ __global__ void __launch_bounds__(256) pg_pose_kernel(Graph g, int set_scale) {
       for (int k = 0; k < 6; ++k) sum += jac[k * 6 + i] * jac[k * 6 + j];
     } else {
       for (int k = 0; k < 6; ++k) sum += jac[k * 6 + i] * g.residual[6 * c + k];
+    }
+  }
+  if (g.num_observations > 0) {  // the observations follow the constraints in the residual blocks' order
+    for (int at = g.pose_observation_start[p]; at < g.pose_observation_start[p + 1]; ++at) {
+      const int64_t entry = g.pose_observations[at];
+      const double* jac = g.jacobian + 72 * static_cast<int64_t>(g.num_constraints) + 36 * entry;
+      const double* residual = g.residual + 6 * (g.num_constraints + entry / 3);
+      if (lane < 36) {
+        for (int k = 0; k < 6; ++k) sum += jac[k * 6 + i] * jac[k * 6 + j];
+      } else {
+        for (int k = 0; k < 6; ++k) sum += jac[k * 6 + i] * residual[k];
+      }
     }
   }
   if (lane < 36) {
@@ -351,7 +461,7 @@ __global__ void __launch_bounds__(256) pg_pose_kernel(Graph g, int set_scale) {
 // Per pose: max |Plus(x, -gradient) - x| and ||x||^2 over the blocks in the problem.
 __global__ void pg_pose_values_kernel(Graph g) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= g.num_kept + g.num_nodes) return;
+  if (p >= pose_count(g)) return;
   const int mask = g.mask[p];
   const double* x = g.x + 7 * static_cast<int64_t>(p);
   double negative[6], projected[7];
@@ -377,6 +487,15 @@ __global__ void __launch_bounds__(64) pg_node_kernel(Graph g, double radius) {
   const int node = blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= g.num_nodes) return;
   const int p = g.num_kept + node;
+  if (g.node_promoted != nullptr && g.node_promoted[node] != 0) {
+    // a kept block: nothing of it is eliminated, and its constraints' elimination terms read as zero
+    for (int at = g.pose_start[p]; at < g.pose_start[p + 1]; ++at) {
+      const int64_t c = g.pose_constraints[at];
+      for (int k = 0; k < 36; ++k) g.cross[36 * c + k] = 0., g.cross_v[36 * c + k] = 0.;
+      for (int k = 0; k < 6; ++k) g.cross_vg[6 * c + k] = 0.;
+    }
+    return;
+  }
   const int mask = g.mask[p];
   double v[36], vg[6], sn[6];
   for (int k = 0; k < 36; ++k) v[k] = 0.;
@@ -479,7 +598,17 @@ __global__ void __launch_bounds__(256) pg_pairs_kernel(Graph g, double radius) {
     value = scale[i] * scale[j] * g.diagonal_block[36 * static_cast<int64_t>(a) + lane];
     if (i == j) value += lm_diagonal(value, radius);
   }
-  g.s[static_cast<int64_t>(row) * g.np + col] = value - sum;
+  value -= sum;
+  if (g.pair_direct_start != nullptr) {
+    double direct = 0.;
+    for (int at = g.pair_direct_start[pair]; at < g.pair_direct_start[pair + 1]; ++at) {
+      const double* ja = g.jacobian + 36 * static_cast<int64_t>(g.pair_direct_a[at]) + i;
+      const double* jb = g.jacobian + 36 * static_cast<int64_t>(g.pair_direct_b[at]) + j;
+      for (int k = 0; k < 6; ++k) direct += ja[k * 6] * jb[k * 6];
+    }
+    value += g.scale[6 * static_cast<int64_t>(a) + i] * g.scale[6 * static_cast<int64_t>(b) + j] * direct;
+  }
+  g.s[static_cast<int64_t>(row) * g.np + col] = value;
 }
 
 // Zeroes the lower triangle of S (its diagonal tiles whole) in kPanel x kPanel tiles, grid (tiles, tiles): block pairs that
@@ -494,7 +623,7 @@ __global__ void __launch_bounds__(256) pg_zero_lower_kernel(Graph g) {
 __global__ void pg_rhs_kernel(Graph g) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < g.np - g.n) g.s[static_cast<int64_t>(g.n + t) * g.np + g.n + t] = 1.;
-  if (t >= g.num_kept * 6) return;
+  if (t >= (g.node_promoted != nullptr ? pose_count(g) : g.num_kept) * 6) return;
   const int a = t / 6, i = t % 6;
   const int row = g.column[t];
   if (row < 0) return;
@@ -664,11 +793,11 @@ __global__ void __launch_bounds__(kSmallThreads) pg_small_kernel(Graph g) {
 // the candidate, ||x - candidate||^2 over the blocks in the problem.
 __global__ void pg_step_kernel(Graph g) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= g.num_kept + g.num_nodes || *g.flag != 0u) return;
+  if (p >= pose_count(g) || *g.flag != 0u) return;
   const int mask = g.mask[p];
   const double* scale = g.scale + 6 * static_cast<int64_t>(p);
   double y[6];
-  if (p < g.num_kept) {
+  if (is_kept(g, p)) {
     for (int k = 0; k < 6; ++k) y[k] = g.column[p * 6 + k] >= 0 ? g.rhs[g.column[p * 6 + k]] : 0.;
   } else {
     double w[6];
@@ -729,6 +858,29 @@ __global__ void __launch_bounds__(256) pg_candidate_kernel(Graph g) {
   g.candidate_cost[c] = constraint_cost(g, c, squared, &scaling);
 }
 
+// Per observation: the same over its three blocks.
+__global__ void __launch_bounds__(256) pg_observation_candidate_kernel(Graph g) {
+  const int o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= g.num_observations || *g.flag != 0u) return;
+  const double* jac = g.jacobian + 72 * static_cast<int64_t>(g.num_constraints) + 108 * static_cast<int64_t>(o);
+  const double* residual = g.residual + 6 * (static_cast<int64_t>(g.num_constraints) + o);
+  double model = 0.;
+  for (int k = 0; k < 6; ++k) {
+    double jy = 0.;
+    for (int block = 0; block < 3; ++block) {
+      const double* d = g.delta + 6 * static_cast<int64_t>(g.observation_pose[3 * o + block]);
+      for (int i = 0; i < 6; ++i) jy += jac[36 * block + k * 6 + i] * d[i];
+    }
+    model += jy * (residual[k] + jy / 2.0);
+  }
+  g.model[g.num_constraints + o] = model;
+  Dual<0> e[6];
+  evaluate_observation<0>(g, g.candidate, o, 0, e);
+  double squared = 0.;
+  for (int k = 0; k < 6; ++k) squared += e[k].a * e[k].a;
+  g.candidate_cost[g.num_constraints + o] = 0.5 * squared;
+}
+
 // The sums of an iteration in a fixed order (thread t takes elements t, t + 1024, ...; then a tree), into the
 // page-locked block, and the completion word behind them.
 __device__ inline double block_sum(double mine, double* scratch, bool maximum) {
@@ -745,11 +897,11 @@ __device__ inline double block_sum(double mine, double* scratch, bool maximum) {
 __global__ void __launch_bounds__(kSmallThreads) pg_reduce_kernel(Graph g, int with_step, double* out, unsigned* done_word, unsigned done_seq) {
   __shared__ double scratch[kSmallThreads];
   const int tid = threadIdx.x;
-  const int poses = g.num_kept + g.num_nodes;
+  const int poses = pose_count(g);
   const bool step = with_step != 0 && *g.flag == 0u;
   double cost = 0., fixed = 0., most = 0., x_squared = 0., model = 0., candidate = 0., step_squared = 0.;
-  for (int c = tid; c < g.num_constraints; c += kSmallThreads) {
-    if (g.fixed[c]) {
+  for (int c = tid; c < g.num_constraints + g.num_observations; c += kSmallThreads) {
+    if (c < g.num_constraints ? g.fixed[c] : g.observation_fixed[c - g.num_constraints]) {
       fixed += g.cost[c];
     } else {
       cost += g.cost[c];
@@ -815,9 +967,18 @@ bool all_finite(const double* v, int64_t n) {
 int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, const double* submap_poses7,
             const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes, const double* node_poses7,
             const unsigned char* node_constant, int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
-            const dliom_pose_graph_terms* terms, Solver* solver) {
+            const dliom_pose_graph_terms* terms, const dliom_pose_graph_landmarks* landmarks, Solver* solver) {
   static const dliom_pose_graph_terms kNoTerms = {0, nullptr, 0, nullptr, 0., nullptr};
+  static const dliom_pose_graph_landmarks kNoLandmarks = {0, nullptr, nullptr, 0, nullptr};
   if (terms == nullptr) terms = &kNoTerms;
+  if (landmarks == nullptr) landmarks = &kNoLandmarks;
+  const int num_landmarks = landmarks->num_landmarks;
+  const int64_t num_observations = landmarks->num_observations;
+  const dliom_pose_graph_landmark_observation* observations = landmarks->observations;
+  if (num_landmarks < 0 || num_observations < 0 || (num_landmarks > 0 && landmarks->landmark_poses7 == nullptr) ||
+      (num_observations > 0 && observations == nullptr))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  const bool with_landmarks = num_landmarks > 0 || num_observations > 0;
   const int num_frames = terms->num_fixed_frames;
   const int64_t num_frame_constraints = terms->num_fixed_frame_constraints;
   const dliom_pose_graph_constraint* frame_constraints = terms->fixed_frame_constraints;
@@ -828,22 +989,32 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
       (num_submaps > 0 && submap_poses7 == nullptr) || (num_nodes > 0 && node_poses7 == nullptr) ||
       (num_constraints > 0 && constraints == nullptr) || gravity_aligned_submap < -1 || gravity_aligned_submap >= num_submaps)
     return DLIOM_ERR_INVALID_ARGUMENT;
-  if (static_cast<int64_t>(num_submaps) + num_frames + num_nodes > INT32_MAX / 72) return DLIOM_ERR_TOO_LARGE;
+  if (static_cast<int64_t>(num_submaps) + num_frames + num_nodes + num_landmarks > INT32_MAX / 72) return DLIOM_ERR_TOO_LARGE;
   solver->ctx = ctx;
   pg::Structure& s = solver->structure;
   constexpr int64_t stride = sizeof(dliom_pose_graph_constraint) / sizeof(int32_t);
   static_assert(sizeof(dliom_pose_graph_constraint) % sizeof(int32_t) == 0, "the constraints are read with an int32 stride");
   const int32_t* first = reinterpret_cast<const int32_t*>(constraints);
   const int32_t* frame_first = reinterpret_cast<const int32_t*>(frame_constraints);
-  const int status = pg::build_structure_terms(num_submaps, submap_constant, gravity_aligned_submap, num_frames, num_nodes,
-                                               node_constant, num_constraints, first, first + 1, stride, num_frame_constraints,
-                                               frame_first, frame_first + 1, stride, options->fix_z_in_3d != 0,
-                                               DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION, &s);
+  constexpr int64_t observation_stride = sizeof(dliom_pose_graph_landmark_observation) / sizeof(int32_t);
+  static_assert(sizeof(dliom_pose_graph_landmark_observation) % sizeof(int32_t) == 0, "the observations are read with an int32 stride");
+  const int32_t* observation_first = reinterpret_cast<const int32_t*>(observations);
+  const int status = pg::build_structure_landmarks(num_submaps, submap_constant, gravity_aligned_submap, num_frames, num_nodes,
+                                                   node_constant, num_constraints, first, first + 1, stride, num_frame_constraints,
+                                                   frame_first, frame_first + 1, stride, num_landmarks, landmarks->landmark_constant,
+                                                   num_observations, observation_first, observation_first + 1, observation_first + 2,
+                                                   observation_stride, options->fix_z_in_3d != 0,
+                                                   DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION, &s);
   if (status == pg::kStructureBadIndex) return DLIOM_ERR_INVALID_ARGUMENT;
   if (status == pg::kStructureTooLarge) return DLIOM_ERR_TOO_LARGE;
   if (!all_finite(submap_poses7, 7 * static_cast<int64_t>(num_submaps)) || !all_finite(node_poses7, 7 * static_cast<int64_t>(num_nodes)))
     return DLIOM_ERR_SOLVER;
   if (!all_finite(terms->fixed_frame_poses7, 7 * static_cast<int64_t>(num_frames))) return DLIOM_ERR_SOLVER;
+  if (!all_finite(landmarks->landmark_poses7, 7 * static_cast<int64_t>(num_landmarks))) return DLIOM_ERR_SOLVER;
+  for (int64_t o = 0; o < num_observations; ++o)
+    if (!std::isfinite(observations[o].interpolation_parameter) || !all_finite(observations[o].landmark_to_tracking7, 7) ||
+        !std::isfinite(observations[o].translation_weight) || !std::isfinite(observations[o].rotation_weight))
+      return DLIOM_ERR_SOLVER;
   // residual block c: the constraints, then the fixed frames'
   const int64_t C = num_constraints + num_frame_constraints;
   auto block = [&](int64_t c) -> const dliom_pose_graph_constraint& {
@@ -856,8 +1027,11 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   const bool with_loss = terms->huber_scale > 0. && terms->inter_submap != nullptr;
 
   Graph& g = solver->g;
-  const int64_t kept = static_cast<int64_t>(num_submaps) + num_frames, poses = kept + num_nodes;
+  const int64_t kept = static_cast<int64_t>(num_submaps) + num_frames, poses = kept + num_nodes + num_landmarks;
+  const int64_t O = num_observations;
   g.num_kept = static_cast<int>(kept);
+  g.num_landmarks = num_landmarks;
+  g.num_observations = static_cast<int>(O);
   g.huber_scale = with_loss ? terms->huber_scale : 0.;
   g.num_nodes = num_nodes;
   g.num_constraints = static_cast<int>(C);
@@ -865,10 +1039,14 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   g.n = s.reduced_dimension;
   g.np = std::max(kPanel, (g.n + kPanel - 1) / kPanel * kPanel);
   // one host buffer, one copy: [constraint data | poses | int arrays] (a vector of doubles; the ints ride in its tail)
-  const size_t num_ints = (with_loss ? 3 : 2) * static_cast<size_t>(C) + s.kind.size() + s.mask.size() + s.column.size() + s.fixed.size() + s.pose_start.size() +
+  // with landmarks `column` covers every pose
+  const std::vector<int32_t>& column = with_landmarks ? s.pose_column : s.column;
+  const size_t num_ints = (with_loss ? 3 : 2) * static_cast<size_t>(C) + s.kind.size() + s.mask.size() + column.size() + s.fixed.size() + s.pose_start.size() +
                           s.pose_constraints.size() + s.pair_a.size() + s.pair_b.size() + s.pair_start.size() + s.pair_c.size() +
-                          s.pair_c2.size() + 1;
-  const size_t upload_doubles = static_cast<size_t>(9 * C + 7 * poses);
+                          s.pair_c2.size() + 1 + 3 * static_cast<size_t>(O) + s.observation_fixed.size() + s.node_promoted.size() +
+                          s.pose_observation_start.size() + s.pose_observations.size() + s.pair_direct_start.size() +
+                          s.pair_direct_a.size() + s.pair_direct_b.size();
+  const size_t upload_doubles = static_cast<size_t>(9 * C + 7 * poses + 10 * O);
   std::vector<double> host(upload_doubles + (num_ints + 1) / 2);
   for (int64_t c = 0; c < C; ++c) {
     std::memcpy(&host[9 * c], block(c).zbar, 7 * sizeof(double));
@@ -878,6 +1056,14 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   if (num_submaps > 0) std::memcpy(&host[9 * C], submap_poses7, sizeof(double) * 7 * num_submaps);
   if (num_frames > 0) std::memcpy(&host[9 * C + 7 * static_cast<int64_t>(num_submaps)], terms->fixed_frame_poses7, sizeof(double) * 7 * num_frames);
   if (num_nodes > 0) std::memcpy(&host[9 * C + 7 * kept], node_poses7, sizeof(double) * 7 * num_nodes);
+  if (num_landmarks > 0) std::memcpy(&host[9 * C + 7 * (kept + num_nodes)], landmarks->landmark_poses7, sizeof(double) * 7 * num_landmarks);
+  for (int64_t o = 0; o < O; ++o) {
+    double* data = &host[9 * C + 7 * poses + 10 * o];
+    std::memcpy(data, observations[o].landmark_to_tracking7, 7 * sizeof(double));
+    data[7] = observations[o].translation_weight;
+    data[8] = observations[o].rotation_weight;
+    data[9] = observations[o].interpolation_parameter;
+  }
   int32_t* host_ints = reinterpret_cast<int32_t*>(host.data() + upload_doubles);
   size_t ints_used = 0;
   auto append = [&](const std::vector<int32_t>& v) {
@@ -894,10 +1080,19 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   if (with_loss)
     for (int64_t c = 0; c < C; ++c) host_ints[ints_used++] = c < num_constraints && terms->inter_submap[c] != 0 ? 1 : 0;
   const size_t at_kind = append(s.kind);
-  const size_t at_mask = append(s.mask), at_column = append(s.column), at_fixed = append(s.fixed), at_start = append(s.pose_start),
+  const size_t at_mask = append(s.mask), at_column = append(column), at_fixed = append(s.fixed), at_start = append(s.pose_start),
                at_list = append(s.pose_constraints), at_a = append(s.pair_a), at_b = append(s.pair_b),
                at_pair_start = append(s.pair_start), at_c = append(s.pair_c), at_c2 = append(s.pair_c2);
   host_ints[ints_used++] = 0;
+  const size_t at_observation_pose = ints_used;
+  for (int64_t o = 0; o < O; ++o) {
+    host_ints[ints_used++] = static_cast<int32_t>(kept) + observations[o].prev_node;
+    host_ints[ints_used++] = static_cast<int32_t>(kept) + observations[o].next_node;
+    host_ints[ints_used++] = static_cast<int32_t>(kept) + num_nodes + observations[o].landmark;
+  }
+  const size_t at_observation_fixed = append(s.observation_fixed), at_promoted = append(s.node_promoted),
+               at_observation_start = append(s.pose_observation_start), at_observation_list = append(s.pose_observations),
+               at_direct_start = append(s.pair_direct_start), at_direct_a = append(s.pair_direct_a), at_direct_b = append(s.pair_direct_b);
 
   // the device block: doubles, then the ints
   int64_t doubles = 0;
@@ -908,10 +1103,10 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   };
   const int64_t np = g.np;
   const int64_t o_upload = take(static_cast<int64_t>(host.size())), o_candidate = take(7 * poses), o_scale = take(6 * poses),
-                o_block = take(36 * poses), o_gradient = take(6 * poses), o_residual = take(6 * C), o_jacobian = take(72 * C),
+                o_block = take(36 * poses), o_gradient = take(6 * poses), o_residual = take(6 * (C + O)), o_jacobian = take(72 * C + 108 * O),
                 o_cross = take(36 * C), o_cross_v = take(36 * C), o_cross_vg = take(6 * C), o_v = take(36 * static_cast<int64_t>(num_nodes)),
                 o_vg = take(6 * static_cast<int64_t>(num_nodes)), o_rhs = take(np), o_step = take(6 * poses), o_delta = take(6 * poses),
-                o_model = take(C), o_cost = take(C), o_candidate_cost = take(C), o_step_squared = take(poses),
+                o_model = take(C + O), o_cost = take(C + O), o_candidate_cost = take(C + O), o_step_squared = take(poses),
                 o_x_squared = take(poses), o_gradient_max = take(poses), o_flag = take(32), o_best = take(7 * poses), o_s = take(np * np);
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   DLIOM_HIP_TRY(hipMalloc(&solver->device, static_cast<size_t>(doubles) * sizeof(double)));
@@ -960,6 +1155,15 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   g.pair_start = ints + at_pair_start;
   g.pair_c = ints + at_c;
   g.pair_c2 = ints + at_c2;
+  g.observation_data = d + o_upload + 9 * C + 7 * poses;
+  g.observation_pose = ints + at_observation_pose;
+  g.observation_fixed = ints + at_observation_fixed;
+  g.node_promoted = with_landmarks ? ints + at_promoted : nullptr;
+  g.pose_observation_start = ints + at_observation_start;
+  g.pose_observations = ints + at_observation_list;
+  g.pair_direct_start = with_landmarks ? ints + at_direct_start : nullptr;
+  g.pair_direct_a = ints + at_direct_a;
+  g.pair_direct_b = ints + at_direct_b;
   solver->best = d + o_best;
   return DLIOM_OK;
 }
@@ -967,9 +1171,11 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
 int enqueue_linearise(Solver* solver, bool set_scale) {
   const Graph& g = solver->g;
   hipStream_t stream = solver->ctx->stream;
-  const int poses = g.num_kept + g.num_nodes;
+  const int poses = g.num_kept + g.num_nodes + g.num_landmarks;
   DLIOM_TRY(solver->begin_stage());
   if (g.num_constraints > 0) hipLaunchKernelGGL(pg_linearise_kernel, dim3(blocks_of(g.num_constraints, 64)), dim3(64), 0, stream, g);
+  if (g.num_observations > 0)
+    hipLaunchKernelGGL(pg_observation_linearise_kernel, dim3(blocks_of(3 * g.num_observations, 64)), dim3(64), 0, stream, g);
   if (poses > 0) {
     hipLaunchKernelGGL(pg_pose_kernel, dim3(blocks_of(poses, 4)), dim3(256), 0, stream, g, set_scale ? 1 : 0);
     hipLaunchKernelGGL(pg_pose_values_kernel, dim3(blocks_of(poses, 256)), dim3(256), 0, stream, g);
@@ -981,14 +1187,14 @@ int enqueue_linearise(Solver* solver, bool set_scale) {
 int enqueue_step(Solver* solver, double radius) {
   const Graph& g = solver->g;
   hipStream_t stream = solver->ctx->stream;
-  const int poses = g.num_kept + g.num_nodes;
+  const int poses = g.num_kept + g.num_nodes + g.num_landmarks;
   DLIOM_TRY(solver->begin_stage());
   DLIOM_HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(unsigned), stream));
   DLIOM_HIP_TRY(hipMemsetAsync(g.rhs, 0, static_cast<size_t>(g.np) * sizeof(double), stream));
   hipLaunchKernelGGL(pg_zero_lower_kernel, dim3(g.np / kPanel, g.np / kPanel), dim3(256), 0, stream, g);
   if (g.num_nodes > 0) hipLaunchKernelGGL(pg_node_kernel, dim3(blocks_of(g.num_nodes, 64)), dim3(64), 0, stream, g, radius);
   if (g.num_pairs > 0) hipLaunchKernelGGL(pg_pairs_kernel, dim3(blocks_of(g.num_pairs, 4)), dim3(256), 0, stream, g, radius);
-  hipLaunchKernelGGL(pg_rhs_kernel, dim3(blocks_of(std::max(g.num_kept * 6, g.np), 256)), dim3(256), 0, stream, g);
+  hipLaunchKernelGGL(pg_rhs_kernel, dim3(blocks_of(std::max((g.node_promoted != nullptr ? poses : g.num_kept) * 6, g.np), 256)), dim3(256), 0, stream, g);
   DLIOM_HIP_TRY(hipGetLastError());
   DLIOM_TRY(solver->end_stage(1));
   DLIOM_TRY(solver->begin_stage());
@@ -1010,6 +1216,8 @@ int enqueue_step(Solver* solver, double radius) {
   DLIOM_TRY(solver->begin_stage());
   if (poses > 0) hipLaunchKernelGGL(pg_step_kernel, dim3(blocks_of(poses, 256)), dim3(256), 0, stream, g);
   if (g.num_constraints > 0) hipLaunchKernelGGL(pg_candidate_kernel, dim3(blocks_of(g.num_constraints, 256)), dim3(256), 0, stream, g);
+  if (g.num_observations > 0)
+    hipLaunchKernelGGL(pg_observation_candidate_kernel, dim3(blocks_of(g.num_observations, 256)), dim3(256), 0, stream, g);
   DLIOM_HIP_TRY(hipGetLastError());
   return solver->end_stage(3);
 }
@@ -1034,14 +1242,17 @@ int read_sums(Solver* solver, bool with_step, double sums[kSums]) {
   return DLIOM_OK;
 }
 
-// `width` doubles a pose from the device's order (submaps, fixed frames, nodes) into the caller's three arrays; enqueued.
+// `width` doubles a pose from the device's order (submaps, fixed frames, nodes, landmarks) into the caller's four arrays;
+// enqueued.
 int copy_poses_out(Solver* solver, const double* device, int width, int num_submaps, int num_nodes, double* submaps, double* nodes,
-                   double* frames) {
+                   double* frames, double* landmarks) {
   hipStream_t stream = solver->ctx->stream;
   const size_t S = static_cast<size_t>(num_submaps), K = static_cast<size_t>(solver->g.num_kept), bytes = sizeof(double) * width;
   if (S > 0) DLIOM_HIP_TRY(hipMemcpyAsync(submaps, device, bytes * S, hipMemcpyDeviceToHost, stream));
   if (K > S) DLIOM_HIP_TRY(hipMemcpyAsync(frames, device + width * S, bytes * (K - S), hipMemcpyDeviceToHost, stream));
   if (num_nodes > 0) DLIOM_HIP_TRY(hipMemcpyAsync(nodes, device + width * K, bytes * num_nodes, hipMemcpyDeviceToHost, stream));
+  if (solver->g.num_landmarks > 0)
+    DLIOM_HIP_TRY(hipMemcpyAsync(landmarks, device + width * (K + num_nodes), bytes * solver->g.num_landmarks, hipMemcpyDeviceToHost, stream));
   return DLIOM_OK;
 }
 
@@ -1052,25 +1263,37 @@ using namespace dliom;
 
 extern "C" {
 
+int dliom_pose_graph_evaluate_landmarks(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                        const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                        int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                        int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                        const dliom_pose_graph_terms* terms, const dliom_pose_graph_landmarks* landmarks, double* cost,
+                                        double* residuals, double* gradient) {
+  Solver solver;
+  DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
+                    node_constant, num_constraints, constraints, terms, landmarks, &solver));
+  DLIOM_TRY(enqueue_linearise(&solver, true));
+  double sums[kSums];
+  DLIOM_TRY(read_sums(&solver, false, sums));
+  if (cost != nullptr) *cost = sums[kSumCost] + sums[kSumFixedCost];
+  const size_t blocks = static_cast<size_t>(solver.g.num_constraints) + solver.g.num_observations;
+  if (residuals != nullptr && blocks > 0)
+    DLIOM_HIP_TRY(hipMemcpyAsync(residuals, solver.g.residual, sizeof(double) * 6 * blocks, hipMemcpyDeviceToHost, ctx->stream));
+  const size_t before_frames = static_cast<size_t>(num_submaps) + num_nodes, before_landmarks = static_cast<size_t>(solver.g.num_kept) + num_nodes;
+  if (gradient != nullptr) DLIOM_TRY(copy_poses_out(&solver, solver.g.gradient, 6, num_submaps, num_nodes, gradient, gradient + 6 * static_cast<size_t>(num_submaps),
+                                                    gradient + 6 * before_frames, gradient + 6 * before_landmarks));
+  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ++ctx->host_syncs;
+  return DLIOM_OK;
+}
 int dliom_pose_graph_evaluate_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
                                     const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
                                     int num_nodes, const double* node_poses7, const unsigned char* node_constant,
                                     int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
                                     const dliom_pose_graph_terms* terms, double* cost, double* residuals, double* gradient) {
-  Solver solver;
-  DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
-                    node_constant, num_constraints, constraints, terms, &solver));
-  DLIOM_TRY(enqueue_linearise(&solver, true));
-  double sums[kSums];
-  DLIOM_TRY(read_sums(&solver, false, sums));
-  if (cost != nullptr) *cost = sums[kSumCost] + sums[kSumFixedCost];
-  if (residuals != nullptr && solver.g.num_constraints > 0)
-    DLIOM_HIP_TRY(hipMemcpyAsync(residuals, solver.g.residual, sizeof(double) * 6 * solver.g.num_constraints, hipMemcpyDeviceToHost, ctx->stream));
-  if (gradient != nullptr) DLIOM_TRY(copy_poses_out(&solver, solver.g.gradient, 6, num_submaps, num_nodes, gradient, gradient + 6 * static_cast<size_t>(num_submaps),
-                                                    gradient + 6 * (static_cast<size_t>(num_submaps) + num_nodes)));
-  DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  ++ctx->host_syncs;
-  return DLIOM_OK;
+  return dliom_pose_graph_evaluate_landmarks(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap,
+                                             num_nodes, node_poses7, node_constant, num_constraints, constraints, terms, nullptr, cost,
+                                             residuals, gradient);
 }
 int dliom_pose_graph_evaluate(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
                               const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
@@ -1081,16 +1304,16 @@ int dliom_pose_graph_evaluate(dliom_ctx* ctx, const dliom_pose_graph_options* op
                                          node_poses7, node_constant, num_constraints, constraints, nullptr, cost, residuals, gradient);
 }
 
-int dliom_pose_graph_step_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
-                                const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
-                                int num_nodes, const double* node_poses7, const unsigned char* node_constant,
-                                int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
-                                const dliom_pose_graph_terms* terms, double radius, double* delta, double* model_cost_change,
-                                int* reduced_dimension) {
+int dliom_pose_graph_step_landmarks(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                    const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                    int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                    int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                    const dliom_pose_graph_terms* terms, const dliom_pose_graph_landmarks* landmarks, double radius,
+                                    double* delta, double* model_cost_change, int* reduced_dimension) {
   if (!(radius > 0.)) return DLIOM_ERR_INVALID_ARGUMENT;
   Solver solver;
   DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
-                    node_constant, num_constraints, constraints, terms, &solver));
+                    node_constant, num_constraints, constraints, terms, landmarks, &solver));
   if (reduced_dimension != nullptr) *reduced_dimension = solver.g.n;
   DLIOM_TRY(enqueue_linearise(&solver, true));
   DLIOM_TRY(enqueue_step(&solver, radius));
@@ -1098,11 +1321,22 @@ int dliom_pose_graph_step_terms(dliom_ctx* ctx, const dliom_pose_graph_options* 
   DLIOM_TRY(read_sums(&solver, true, sums));
   if (sums[kSumFlag] != 0.) return DLIOM_ERR_SOLVER;
   if (model_cost_change != nullptr) *model_cost_change = -sums[kSumModel];
+  const size_t before_frames = static_cast<size_t>(num_submaps) + num_nodes, before_landmarks = static_cast<size_t>(solver.g.num_kept) + num_nodes;
   if (delta != nullptr) DLIOM_TRY(copy_poses_out(&solver, solver.g.delta, 6, num_submaps, num_nodes, delta, delta + 6 * static_cast<size_t>(num_submaps),
-                                                 delta + 6 * (static_cast<size_t>(num_submaps) + num_nodes)));
+                                                 delta + 6 * before_frames, delta + 6 * before_landmarks));
   DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   ++ctx->host_syncs;
   return DLIOM_OK;
+}
+int dliom_pose_graph_step_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                const dliom_pose_graph_terms* terms, double radius, double* delta, double* model_cost_change,
+                                int* reduced_dimension) {
+  return dliom_pose_graph_step_landmarks(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes,
+                                         node_poses7, node_constant, num_constraints, constraints, terms, nullptr, radius, delta,
+                                         model_cost_change, reduced_dimension);
 }
 int dliom_pose_graph_step(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
                           const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
@@ -1116,20 +1350,20 @@ int dliom_pose_graph_step(dliom_ctx* ctx, const dliom_pose_graph_options* option
 
 // trust_region_minimizer.cc of Ceres 1.13 (Init / IterationZero / the loop), with levenberg_marquardt_strategy.cc's
 // radius rules and trust_region_step_evaluator.cc, for this configuration: third-party behaviour, restated.
-int dliom_pose_graph_solve_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
-                                 const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
-                                 double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
-                                 const dliom_pose_graph_constraint* constraints, const dliom_pose_graph_terms* terms,
-                                 dliom_pose_graph_summary* summary) {
+int dliom_pose_graph_solve_landmarks(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
+                                     const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                                     double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
+                                     const dliom_pose_graph_constraint* constraints, const dliom_pose_graph_terms* terms,
+                                     const dliom_pose_graph_landmarks* landmarks, dliom_pose_graph_summary* summary) {
   if (summary == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
   const auto started = std::chrono::steady_clock::now();
   Solver solver;
   DLIOM_TRY(prepare(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes, node_poses7,
-                    node_constant, num_constraints, constraints, terms, &solver));
+                    node_constant, num_constraints, constraints, terms, landmarks, &solver));
   std::memset(summary, 0, sizeof(*summary));
   summary->reduced_dimension = solver.g.n;
   Graph& g = solver.g;
-  const size_t pose_bytes = sizeof(double) * 7 * (static_cast<size_t>(g.num_kept) + num_nodes);
+  const size_t pose_bytes = sizeof(double) * 7 * (static_cast<size_t>(g.num_kept) + num_nodes + g.num_landmarks);
   double* best = solver.best;
 
   // the 1.13 defaults that common/ceres_solver_options.cc:35-42 leaves alone
@@ -1296,7 +1530,8 @@ int dliom_pose_graph_solve_terms(dliom_ctx* ctx, const dliom_pose_graph_options*
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   } else {
     DLIOM_TRY(copy_poses_out(&solver, best, 7, num_submaps, num_nodes, submap_poses7, node_poses7,
-                             terms != nullptr ? terms->fixed_frame_poses7 : nullptr));
+                             terms != nullptr ? terms->fixed_frame_poses7 : nullptr,
+                             landmarks != nullptr ? landmarks->landmark_poses7 : nullptr));
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
   ++ctx->host_syncs;
@@ -1309,6 +1544,39 @@ int dliom_pose_graph_solve_terms(dliom_ctx* ctx, const dliom_pose_graph_options*
     summary->host_ms = total - (solver.stage_ms[0] + solver.stage_ms[1] + solver.stage_ms[2] + solver.stage_ms[3]);
   }
   return status;
+}
+int dliom_pose_graph_solve_terms(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
+                                 const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                                 double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
+                                 const dliom_pose_graph_constraint* constraints, const dliom_pose_graph_terms* terms,
+                                 dliom_pose_graph_summary* summary) {
+  return dliom_pose_graph_solve_landmarks(ctx, options, num_submaps, submap_poses7, submap_constant, gravity_aligned_submap, num_nodes,
+                                          node_poses7, node_constant, num_constraints, constraints, terms, nullptr, summary);
+}
+// GetInitialLandmarkPose (optimization_problem_3d.cc:106-122): Rigid3d::FromArrays(InterpolateNodes3D(...)) *
+// landmark_to_tracking, on the host in double.
+int dliom_pose_graph_initial_landmark_pose(const double* prev_pose7, const double* next_pose7, double t,
+                                           const double* landmark_to_tracking7, double* out7) {
+  if (prev_pose7 == nullptr || next_pose7 == nullptr || landmark_to_tracking7 == nullptr || out7 == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  const double* start = prev_pose7 + 3;
+  const double* end = next_pose7 + 3;
+  const double cos_theta = start[0] * end[0] + start[1] * end[1] + start[2] * end[2] + start[3] * end[3];
+  const double abs_cos_theta = std::fabs(cos_theta);
+  double prev_scale = 1. - t, next_scale = t;
+  if (abs_cos_theta < 1. - 1e-5) {
+    const double theta = std::acos(abs_cos_theta);
+    const double sin_theta = std::sin(theta);
+    prev_scale = std::sin((1. - t) * theta) / sin_theta;
+    next_scale = std::sin(t * theta) / sin_theta;
+  }
+  if (cos_theta < 0.) next_scale = -next_scale;
+  PoseD interpolated, observed;
+  for (int k = 0; k < 4; ++k) interpolated.q[k] = prev_scale * start[k] + next_scale * end[k], observed.q[k] = landmark_to_tracking7[3 + k];
+  for (int k = 0; k < 3; ++k) interpolated.t[k] = prev_pose7[k] + t * (next_pose7[k] - prev_pose7[k]), observed.t[k] = landmark_to_tracking7[k];
+  const PoseD pose = pose_mul(interpolated, observed);
+  for (int k = 0; k < 3; ++k) out7[k] = pose.t[k];
+  for (int k = 0; k < 4; ++k) out7[3 + k] = pose.q[k];
+  return DLIOM_OK;
 }
 int dliom_pose_graph_solve(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
                            const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,

@@ -2489,6 +2489,37 @@ class PoseGraphTerms(C.Structure):
 
 
 _pgt = C.POINTER(PoseGraphTerms)
+
+
+class PoseGraphLandmarkObservation(C.Structure):
+    _fields_ = [("landmark", C.c_int32), ("prev_node", C.c_int32), ("next_node", C.c_int32),
+                ("interpolation_parameter", C.c_double), ("landmark_to_tracking7", C.c_double * 7),
+                ("translation_weight", C.c_double), ("rotation_weight", C.c_double)]
+
+
+POSE_GRAPH_LANDMARK_OBSERVATION_DTYPE = np.dtype(
+    {"names": ["landmark", "prev_node", "next_node", "interpolation_parameter", "landmark_to_tracking", "translation_weight",
+               "rotation_weight"],
+     "formats": ["<i4", "<i4", "<i4", "<f8", ("<f8", 7), "<f8", "<f8"], "offsets": [0, 4, 8, 16, 24, 80, 88], "itemsize": 96})
+assert POSE_GRAPH_LANDMARK_OBSERVATION_DTYPE.itemsize == C.sizeof(PoseGraphLandmarkObservation)
+assert all(POSE_GRAPH_LANDMARK_OBSERVATION_DTYPE.fields[n][1] == getattr(PoseGraphLandmarkObservation, f).offset
+           for n, (f, _) in zip(POSE_GRAPH_LANDMARK_OBSERVATION_DTYPE.names, PoseGraphLandmarkObservation._fields_))
+_pglo = C.POINTER(PoseGraphLandmarkObservation)
+
+
+class PoseGraphLandmarks(C.Structure):
+    _fields_ = [("num_landmarks", C.c_int), ("landmark_poses7", _f64p), ("landmark_constant", _u8p),
+                ("num_observations", C.c_int64), ("observations", _pglo)]
+
+
+_pgl = C.POINTER(PoseGraphLandmarks)
+SYMBOLS += [
+    ("dliom_pose_graph_solve_landmarks", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_pgt, _pgl, C.POINTER(PoseGraphSummary)]),
+    ("dliom_pose_graph_evaluate_landmarks", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_pgt, _pgl, _f64p, _f64p, _f64p]),
+    ("dliom_pose_graph_step_landmarks", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_pgt, _pgl, C.c_double, _f64p, _f64p,
+                                                                                                 C.POINTER(C.c_int)]),
+    ("dliom_pose_graph_initial_landmark_pose", C.c_int, [_f64p, _f64p, C.c_double, _f64p, _f64p]),
+]
 SYMBOLS += [
     ("dliom_pose_graph_solve", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [C.POINTER(PoseGraphSummary)]),
     ("dliom_pose_graph_evaluate", C.c_int, [_vp, C.POINTER(PoseGraphOptions)] + _PG_GRAPH + [_f64p, _f64p, _f64p]),
@@ -2501,6 +2532,15 @@ SYMBOLS += [
 ]
 
 
+def initial_landmark_pose(prev_pose, next_pose, t, landmark_to_tracking):
+    """GetInitialLandmarkPose (dliom_pose_graph_initial_landmark_pose): a landmark's start value from an observation."""
+    prev_pose, next_pose, z, out = _f64(prev_pose).copy(), _f64(next_pose).copy(), _f64(landmark_to_tracking).copy(), np.zeros(7)
+    _check(load_library().dliom_pose_graph_initial_landmark_pose(_p(prev_pose, _f64p), _p(next_pose, _f64p), float(t),
+                                                                _p(z, _f64p), _p(out, _f64p)),
+           "dliom_pose_graph_initial_landmark_pose")
+    return out
+
+
 class PoseGraph:
     """OptimizationProblem3D::Solve on compacted indices.  submap_poses / node_poses: (n, 7) [t, q wxyz]; constraints:
     a POSE_GRAPH_CONSTRAINT_DTYPE array; *_constant: uint8 flags or None; gravity_aligned_submap: index or -1.
@@ -2508,12 +2548,25 @@ class PoseGraph:
     The further terms (dliom_pose_graph_terms): fixed_frame_poses (F, 7), fixed_frame_constraints (their `submap` is the
     fixed frame's index), huber_scale and inter_submap (uint8 flags a constraint, or None).  entry: "plain" calls
     dliom_pose_graph_*, "null" the *_terms entry points with a NULL struct, "terms" those with the struct; None picks
-    "plain" when there is no further term and "terms" otherwise."""
+    "plain" when there is no further term and "terms" otherwise.
+
+    Landmarks (dliom_pose_graph_landmarks): landmarks (L, 7) start values, landmark_constant (uint8 flags or None) and
+    landmark_observations (a POSE_GRAPH_LANDMARK_OBSERVATION_DTYPE array).  With any of them the entry is "landmarks" (the
+    *_landmarks entry points with both structs); "landmarks_null" and "landmarks_empty" call those with a NULL / an empty
+    landmark struct and NULL terms, and carry no further term."""
 
     def __init__(self, ctx, submap_poses, node_poses, constraints, submap_constant=None, node_constant=None,
                  gravity_aligned_submap=0, fix_z_in_3d=False, use_nonmonotonic_steps=False, max_num_iterations=10,
-                 fixed_frame_poses=None, fixed_frame_constraints=None, huber_scale=0.0, inter_submap=None, entry=None):
+                 fixed_frame_poses=None, fixed_frame_constraints=None, huber_scale=0.0, inter_submap=None, entry=None,
+                 landmarks=None, landmark_constant=None, landmark_observations=None):
         self.ctx, self._L = ctx, ctx._L
+        self.landmarks = _f64(np.zeros((0, 7)) if landmarks is None else landmarks).reshape(-1, 7).copy()
+        self.landmark_constant = None if landmark_constant is None else np.ascontiguousarray(landmark_constant, dtype=np.uint8)
+        self.landmark_observations = np.ascontiguousarray(
+            np.zeros(0, POSE_GRAPH_LANDMARK_OBSERVATION_DTYPE) if landmark_observations is None else landmark_observations,
+            dtype=POSE_GRAPH_LANDMARK_OBSERVATION_DTYPE)
+        if self.landmark_constant is not None and len(self.landmark_constant) != len(self.landmarks):
+            raise ValueError("landmark_constant: one flag a landmark")
         self.submaps = _f64(submap_poses).reshape(-1, 7).copy()
         self.nodes = _f64(node_poses).reshape(-1, 7).copy()
         self.constraints = np.ascontiguousarray(constraints, dtype=POSE_GRAPH_CONSTRAINT_DTYPE)
@@ -2530,8 +2583,10 @@ class PoseGraph:
         if self.inter_submap is not None and len(self.inter_submap) != len(self.constraints):
             raise ValueError("inter_submap: one flag a constraint")
         plain = len(self.fixed_frames) == 0 and len(self.fixed_frame_constraints) == 0 and self.huber_scale == 0.0
-        self.entry = ("plain" if plain else "terms") if entry is None else entry
-        if self.entry not in ("plain", "null", "terms") or (self.entry != "terms" and not plain):
+        with_landmarks = len(self.landmarks) > 0 or len(self.landmark_observations) > 0
+        self.entry = ("landmarks" if with_landmarks else "plain" if plain else "terms") if entry is None else entry
+        if self.entry not in ("plain", "null", "terms", "landmarks", "landmarks_null", "landmarks_empty") or \
+                (self.entry not in ("terms", "landmarks") and not plain) or (self.entry != "landmarks" and with_landmarks):
             raise ValueError("entry %r cannot carry the further terms" % (self.entry,))
 
     def _graph(self):
@@ -2545,32 +2600,45 @@ class PoseGraph:
             status = getattr(self._L, "dliom_pose_graph_" + name)(self.ctx.h, C.byref(self.options), *self._graph(), *rest)
         else:
             terms = None
-            if self.entry == "terms":
+            if self.entry in ("terms", "landmarks"):
                 terms = C.byref(PoseGraphTerms(
                     len(self.fixed_frames), _p(self.fixed_frames, _f64p) if len(self.fixed_frames) else None,
                     len(self.fixed_frame_constraints),
                     _p(self.fixed_frame_constraints, _pgc) if len(self.fixed_frame_constraints) else None, self.huber_scale,
                     None if self.inter_submap is None else _p(self.inter_submap, _u8p)))
-            status = getattr(self._L, "dliom_pose_graph_%s_terms" % name)(self.ctx.h, C.byref(self.options), *self._graph(), terms,
-                                                                          *rest)
+            if self.entry.startswith("landmarks"):
+                landmarks = None
+                if self.entry != "landmarks_null":
+                    landmarks = C.byref(PoseGraphLandmarks(
+                        len(self.landmarks), _p(self.landmarks, _f64p) if len(self.landmarks) else None,
+                        None if self.landmark_constant is None else _p(self.landmark_constant, _u8p),
+                        len(self.landmark_observations),
+                        _p(self.landmark_observations, _pglo) if len(self.landmark_observations) else None))
+                status = getattr(self._L, "dliom_pose_graph_%s_landmarks" % name)(self.ctx.h, C.byref(self.options), *self._graph(),
+                                                                                  terms, landmarks, *rest)
+            else:
+                status = getattr(self._L, "dliom_pose_graph_%s_terms" % name)(self.ctx.h, C.byref(self.options), *self._graph(),
+                                                                              terms, *rest)
         _check(status, "dliom_pose_graph_" + name)
 
     def evaluate(self):
-        """-> (cost, residuals (C + CF, 6), gradient (S + N + F, 6)): the constraints and then the fixed frames'; the submaps,
-        the nodes and then the fixed frames"""
-        cost, r = C.c_double(), np.zeros((len(self.constraints) + len(self.fixed_frame_constraints), 6))
-        g = np.zeros((len(self.submaps) + len(self.nodes) + len(self.fixed_frames), 6))
+        """-> (cost, residuals (C + CF + O, 6), gradient (S + N + F + L, 6)): the constraints, the fixed frames' and then the
+        observations; the submaps, the nodes, the fixed frames and then the landmarks"""
+        cost = C.c_double()
+        r = np.zeros((len(self.constraints) + len(self.fixed_frame_constraints) + len(self.landmark_observations), 6))
+        g = np.zeros((len(self.submaps) + len(self.nodes) + len(self.fixed_frames) + len(self.landmarks), 6))
         self._call("evaluate", C.byref(cost), _p(r, _f64p), _p(g, _f64p))
         return cost.value, r, g
 
     def step(self, radius=1e4):
-        """-> (delta (S + N + F, 6), model_cost_change, reduced_dimension)"""
-        d, m, n = np.zeros((len(self.submaps) + len(self.nodes) + len(self.fixed_frames), 6)), C.c_double(), C.c_int()
+        """-> (delta (S + N + F + L, 6), model_cost_change, reduced_dimension)"""
+        d = np.zeros((len(self.submaps) + len(self.nodes) + len(self.fixed_frames) + len(self.landmarks), 6))
+        m, n = C.c_double(), C.c_int()
         self._call("step", float(radius), _p(d, _f64p), C.byref(m), C.byref(n))
         return d, m.value, n.value
 
     def solve(self):
-        """Overwrites self.submaps / self.nodes / self.fixed_frames with the best iterate -> the summary as a dict (steps:
+        """Overwrites self.submaps / self.nodes / self.fixed_frames / self.landmarks with the best iterate -> the summary as a dict (steps:
         list of 1 / 0 / 2)."""
         s = PoseGraphSummary()
         self._call("solve", C.byref(s))

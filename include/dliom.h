@@ -1243,9 +1243,8 @@ int dliom_csm3d_evaluate(dliom_ctx* ctx, const dliom_csm_options* options,
  * TrivialLoss (:336-338), so the problem is one SpaCostFunction3D a constraint (cost_functions/spa_cost_function_3d.h:
  * 46-56, cost_helpers_impl.h:57-101, transform/transform.h:59-81) between ONE submap pose and ONE node pose.  The
  * *_terms entry points below add the fixed-frame pose constraints (:491-548, live code in the fork) and upstream's
- * HuberLoss on the inter-submap constraints.  Landmarks (AddLandmarkCostFunctions) are not covered: a landmark residual
- * couples two nodes, so the nodes' Hessian would no longer be block-diagonal and every node a landmark touches would
- * have to move into the dense reduced system.  The 2D problem is not covered either.
+ * HuberLoss on the inter-submap constraints, the *_landmarks entry points further the landmark observations
+ * (AddLandmarkCostFunctions, :124-186).  The 2D problem is not covered.
  *
  * Poses are [tx ty tz qw qx qy qz].  Parameter blocks (:279-330, ceres_pose.cc): a translation block with no
  * parameterisation, or SubsetParameterization(3, {2}) under fix_z_in_3d; a rotation block with
@@ -1380,6 +1379,78 @@ int dliom_pose_graph_step_terms(dliom_ctx* ctx, const dliom_pose_graph_options* 
                                 int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
                                 const dliom_pose_graph_terms* terms, double radius, double* delta, double* model_cost_change,
                                 int* reduced_dimension);
+
+/* Landmark observations (optimization_problem_3d.cc:124-186, cost_functions/landmark_cost_function_3d.h).  A NULL pointer
+ * to dliom_pose_graph_landmarks, and a struct of 0 landmarks and 0 observations, are the *_terms entry points, bit for
+ * bit (those are calls of the ones below with NULL).
+ *
+ * Every used observation of a landmark is one residual block without a loss over six parameter blocks -- rotation and
+ * translation of the node before the observation (prev), of the node after it (next) and of the landmark:
+ *   e = ScaleError(ComputeUnscaledError(landmark_to_tracking, slerp(prev.q, next.q, t), prev.p + t (next.p - prev.p),
+ *                                       landmark.q, landmark.p), translation_weight, rotation_weight)
+ * (cost_helpers_impl.h:57-153) with t = (observation.time - prev.time) / (next.time - prev.time), which the caller
+ * computes (interpolation_parameter).
+ *   SlerpQuaternions is restated exactly: cos_theta = p0 n0 + p1 n1 + p2 n2 + p3 n3 in that order; for
+ *   |cos_theta| < 1 - 1e-5, theta = acos(|cos_theta|), prev_scale = sin((1 - t) theta) / sin(theta), next_scale =
+ *   sin(t theta) / sin(theta); otherwise the linear scales 1 - t and t; next_scale changes sign when cos_theta < 0; the
+ *   result prev_scale p + next_scale n is NOT renormalised.
+ *   The landmark block is CeresPose(start, nullptr, QuaternionParameterization): its translation has NO
+ *   parameterisation -- three columns also under fix_z_in_3d, as for a fixed frame -- and its rotation moves by
+ *   QuaternionParameterization.  The nodes keep theirs: a node drops its z column under fix_z_in_3d.
+ *   landmark_constant[l] != 0: both blocks of landmark l are constant (NULL: none).  The reference sets this for every
+ *   landmark when frozen_trajectories is non-empty (:169-174) and then skips the landmarks that have no
+ *   global_landmark_pose (:131-134); both rules, like finding prev and next (:137-154), are the caller's business.
+ *   Ceres' removal rules extend unchanged: a constant block, or a block no remaining residual block uses, leaves the
+ *   problem; an observation whose six blocks are all constant contributes only to the fixed cost.
+ *   Residual block order, which is the input order of every segmented sum: the constraints, the fixed-frame
+ *   constraints, then the observations in input order.
+ *
+ * A landmark residual couples two nodes, so those nodes cannot stay in the block-diagonal elimination: every
+ * non-constant node that a remaining observation names is "promoted" into the dense reduced system, six columns (five
+ * under fix_z_in_3d), and so is every non-constant landmark, six columns.  The columns are ordered submaps, fixed
+ * frames, promoted nodes, landmarks, and all count against DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION (so at most about
+ * 1 365 promoted nodes and landmarks together with no submap free).  Landmarks are kept, not eliminated.
+ *
+ * Beyond the refusals above, all before anything is launched: DLIOM_ERR_INVALID_ARGUMENT for a negative count, a
+ * positive count with a NULL array, a landmark or node index out of range, prev_node == next_node;
+ * DLIOM_ERR_SOLVER for a non-finite interpolation_parameter, landmark pose, weight or transform. */
+typedef struct dliom_pose_graph_landmark_observation {
+  int32_t landmark, prev_node, next_node; /* prev_node != next_node */
+  double interpolation_parameter;         /* t, finite */
+  double landmark_to_tracking7[7];
+  double translation_weight, rotation_weight;
+} dliom_pose_graph_landmark_observation;
+typedef struct dliom_pose_graph_landmarks {
+  int num_landmarks;
+  double* landmark_poses7;                /* start values; solve overwrites them with the best iterate on DLIOM_OK */
+  const unsigned char* landmark_constant; /* or NULL */
+  int64_t num_observations;
+  const dliom_pose_graph_landmark_observation* observations;
+} dliom_pose_graph_landmarks;
+int dliom_pose_graph_solve_landmarks(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps, double* submap_poses7,
+                                     const unsigned char* submap_constant, int gravity_aligned_submap, int num_nodes,
+                                     double* node_poses7, const unsigned char* node_constant, int64_t num_constraints,
+                                     const dliom_pose_graph_constraint* constraints, const dliom_pose_graph_terms* terms,
+                                     const dliom_pose_graph_landmarks* landmarks, dliom_pose_graph_summary* summary);
+/* residuals: 6 a residual block -- the constraints, the fixed-frame constraints, then the observations; gradient: 6
+ * slots a pose -- the submaps, the nodes, the fixed frames, then the landmarks. */
+int dliom_pose_graph_evaluate_landmarks(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                        const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                        int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                        int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                        const dliom_pose_graph_terms* terms, const dliom_pose_graph_landmarks* landmarks, double* cost,
+                                        double* residuals, double* gradient);
+/* delta: in the slots of `gradient` above. */
+int dliom_pose_graph_step_landmarks(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_submaps,
+                                    const double* submap_poses7, const unsigned char* submap_constant, int gravity_aligned_submap,
+                                    int num_nodes, const double* node_poses7, const unsigned char* node_constant,
+                                    int64_t num_constraints, const dliom_pose_graph_constraint* constraints,
+                                    const dliom_pose_graph_terms* terms, const dliom_pose_graph_landmarks* landmarks, double radius,
+                                    double* delta, double* model_cost_change, int* reduced_dimension);
+/* GetInitialLandmarkPose (optimization_problem_3d.cc:106-122) on the host in double: the pose interpolated between prev
+ * and next at t, times landmark_to_tracking -- a landmark's start value from its first used observation.  No context. */
+int dliom_pose_graph_initial_landmark_pose(const double* prev_pose7, const double* next_pose7, double t,
+                                           const double* landmark_to_tracking7, double* out7);
 
 /* ---- submap feature matching -------------------------------------------------------------------
  * The second half of ConstraintBuilder3D::ExtractFeaturesForSubmap (mapping/internal/constraints/
