@@ -26,6 +26,7 @@
 //          strictly greater score in generation order wins.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -37,6 +38,7 @@
 #include "device_common.h"
 #include "host_math.h"
 #include "probability_values.h"
+#include "rtcsm_candidates.h"
 #include "score_box.h"
 
 namespace dliom {
@@ -492,83 +494,6 @@ __global__ void probe_cells_kernel(Quat4 q, float tx, float ty, float tz, const 
 }
 
 // ---------------------------------------------------------------------------------- host side
-struct Candidates {
-  dliom_rtcsm_window w;
-  PoseF init;
-  std::vector<QF> rot;        // candidate rotation  normalized(init.q * q_r)
-  std::vector<QF> rot_raw;    // q_r (transform rotation)
-  std::vector<float> r_angle; // GetAngle(transform) per rotation
-  std::vector<F3> trans;      // candidate translation init.q * t_j + init.t
-  std::vector<float> t_norm;  // ||t_j||
-};
-
-// rtcsm_3d.cc:58-70
-static void compute_window(const dliom_rtcsm_options& o, float resolution, float cloud_max_norm_value,
-                           dliom_rtcsm_window* w) {
-  w->linear_window_size = static_cast<int>(std::lround(o.linear_search_window / resolution));
-  float max_scan_range = 3.f * resolution;
-  max_scan_range = std::max(cloud_max_norm_value, max_scan_range);
-  const float kSafetyMargin = 1.f - 1e-3f;
-  const float res2 = resolution * (resolution * 1.f);
-  const float range2 = max_scan_range * (max_scan_range * 1.f);
-  w->angular_step_size = kSafetyMargin * std::acos(1.f - res2 / (2.f * range2));
-  w->angular_window_size =
-      static_cast<int>(std::lround(o.angular_search_window / w->angular_step_size));
-  w->max_scan_range = max_scan_range;
-  const int64_t tl = 2 * static_cast<int64_t>(w->linear_window_size) + 1;
-  const int64_t ta = 2 * static_cast<int64_t>(w->angular_window_size) + 1;
-  w->num_translations = tl * tl * tl;
-  w->num_rotations = ta * ta * ta;
-  w->num_candidates = w->num_translations * w->num_rotations;
-}
-
-static void generate_candidates(const dliom_rtcsm_options& o, float resolution, float max_norm,
-                                const double init7[7], Candidates* c) {
-  compute_window(o, resolution, max_norm, &c->w);
-  c->init.t = F3{static_cast<float>(init7[0]), static_cast<float>(init7[1]), static_cast<float>(init7[2])};
-  c->init.q = QF{static_cast<float>(init7[3]), static_cast<float>(init7[4]),
-                 static_cast<float>(init7[5]), static_cast<float>(init7[6])};
-  const int L = c->w.linear_window_size, A = c->w.angular_window_size;
-  const float step = c->w.angular_step_size;
-  // The transform rotations q_r and their angles depend on the window only: cached per thread
-  // across matches (sin/cos/atan2 per rotation are the expensive part of this function).
-  struct RotCache {
-    int A = -1;
-    float step = 0.f;
-    std::vector<QF> rot_raw;
-    std::vector<float> r_angle;
-  };
-  static thread_local RotCache cache;
-  if (cache.A != A || cache.step != step) {
-    cache.A = A;
-    cache.step = step;
-    cache.rot_raw.clear();
-    cache.r_angle.clear();
-    cache.rot_raw.reserve(c->w.num_rotations);
-    cache.r_angle.reserve(c->w.num_rotations);
-    for (int rz = -A; rz <= A; ++rz)
-      for (int ry = -A; ry <= A; ++ry)
-        for (int rx = -A; rx <= A; ++rx) {
-          const QF q = angle_axis_to_quaternion(F3{rx * step, ry * step, rz * step});
-          cache.rot_raw.push_back(q);
-          cache.r_angle.push_back(rotation_angle(q));
-        }
-  }
-  c->rot_raw = cache.rot_raw;
-  c->r_angle = cache.r_angle;
-  c->rot.resize(cache.rot_raw.size());
-  for (size_t i = 0; i < cache.rot_raw.size(); ++i) c->rot[i] = qnormalized(qmul(c->init.q, cache.rot_raw[i]));
-  c->trans.clear();
-  c->t_norm.clear();
-  for (int z = -L; z <= L; ++z)
-    for (int y = -L; y <= L; ++y)
-      for (int x = -L; x <= L; ++x) {
-        const F3 t{x * resolution, y * resolution, z * resolution};
-        c->t_norm.push_back(norm3(t));
-        c->trans.push_back(add3(qrot(c->init.q, t), c->init.t));
-      }
-}
-
 // Device copies of the candidate tables inside ctx->cand.
 struct DeviceCandidates {
   float4* rot;
@@ -579,6 +504,36 @@ struct DeviceCandidates {
   const float4* rot_src;  // where a kernel that runs BEFORE the pending copy (PrepArgs) finds the rotations: the pinned
                           // staging copy while the upload is pending, `rot` itself otherwise
 };
+
+// State of a (possibly sharded) match between its phases; lives in dliom_ctx::rtcsm_state.
+struct RtcsmState {
+  dliom_rtcsm_options o;
+  Candidates c;
+  DeviceCandidates d;
+  dliom_cloud cloud;
+  const dliom_grid* grid = nullptr;
+  int r_first = 0, r_last = 0;
+  unsigned long long* d_sums = nullptr;
+  float* d_hi = nullptr;
+  unsigned* d_list = nullptr;
+  unsigned* d_ctrs = nullptr;
+  float best_score = -1.f;
+  int64_t best_c = -1;
+  bool active = false;
+  double init7[7] = {0, 0, 0, 1, 0, 0, 0};
+  int shard = 0, num_shards = 1;
+  bool used_box = false;
+  // host tables that do not fit their page-locked staging region are built here (capacity kept from match to match)
+  std::vector<char> host_tables, host_box_tables;
+};
+
+static RtcsmState* state_of(dliom_ctx* ctx) {
+  if (ctx->rtcsm_state == nullptr) {
+    ctx->rtcsm_state = new RtcsmState;
+    ctx->rtcsm_state_free = [](void* p) { delete static_cast<RtcsmState*>(p); };
+  }
+  return static_cast<RtcsmState*>(ctx->rtcsm_state);
+}
 
 // ---- pending copies / fills of a match (device_common.h: PrepArgs) --------------------------------------------------
 static bool prep_add(PrepArgs* prep, void* dst, const void* src, size_t bytes, unsigned value) {
@@ -608,62 +563,63 @@ static int prep_flush(dliom_ctx* ctx, PrepArgs* prep) {
 // prep != null: the H2D copy becomes a pending job (the staged tables stay in the pinned block until the kernel that
 // carries the jobs has run -- every entry point that gets here synchronises the stream before it returns).
 static int upload_candidates(dliom_ctx* ctx, const Candidates& c, DeviceCandidates* d, PrepArgs* prep = nullptr) {
-  const size_t R = c.rot.size(), T = c.trans.size();
-  const size_t Tpad = T;
-  const size_t bytes_rot = align256(R * 16);
-  const size_t bytes_trans = align256(Tpad * 12);
-  const size_t bytes_tn = align256(T * 4);
-  const size_t bytes_ra = align256(R * 4);
-  const size_t bytes_t4 = align256(T * 16);
-  const size_t total = bytes_rot + bytes_trans + bytes_tn + bytes_ra + bytes_t4;
-  DLIOM_TRY(ctx->cand.reserve(total));
-  std::vector<char> host(total, 0);
-  float* hr = reinterpret_cast<float*>(host.data());
-  for (size_t i = 0; i < R; ++i) {
-    hr[4 * i] = c.rot[i].w;
-    hr[4 * i + 1] = c.rot[i].x;
-    hr[4 * i + 2] = c.rot[i].y;
-    hr[4 * i + 3] = c.rot[i].z;
-  }
-  float* ht = reinterpret_cast<float*>(host.data() + bytes_rot);
-  for (size_t i = 0; i < Tpad; ++i) {
-    const F3& t = c.trans[std::min(i, T - 1)];  // padding repeats the last translation (unused)
-    ht[3 * i] = t.x;
-    ht[3 * i + 1] = t.y;
-    ht[3 * i + 2] = t.z;
-  }
-  std::memcpy(host.data() + bytes_rot + bytes_trans, c.t_norm.data(), T * 4);
-  std::memcpy(host.data() + bytes_rot + bytes_trans + bytes_tn, c.r_angle.data(), R * 4);
-  float* h4 = reinterpret_cast<float*>(host.data() + bytes_rot + bytes_trans + bytes_tn + bytes_ra);
-  for (size_t i = 0; i < T; ++i) {
-    h4[4 * i] = c.trans[i].x;
-    h4[4 * i + 1] = c.trans[i].y;
-    h4[4 * i + 2] = c.trans[i].z;
-    h4[4 * i + 3] = 0.f;
-  }
+  const CandidateTableLayout l = candidate_table_layout(c.num_rotations(), c.trans.size());
+  DLIOM_TRY(ctx->cand.reserve(l.total));
   char* base = static_cast<char*>(ctx->cand.p);
   d->rot_src = reinterpret_cast<const float4*>(base);
-  if (total <= kPinRtcsmCandidates.bytes) {  // (the match's other regions: pinned_layout.h)
-    // Pinned staging: truly asynchronous.
-    void* staged = pinned_at(ctx, kPinRtcsmCandidates);
-    std::memcpy(staged, host.data(), total);
-    if (prep_add(prep, base, staged, total, 0u))
-      d->rot_src = static_cast<const float4*>(staged);
+  if (l.total <= kPinRtcsmCandidates.bytes) {  // (the match's other regions: pinned_layout.h)
+    // Pinned staging, written in place: truly asynchronous.
+    char* staged = pinned_at<char>(ctx, kPinRtcsmCandidates);
+    fill_candidate_tables(c, l, staged);
+    if (prep_add(prep, base, staged, l.total, 0u))
+      d->rot_src = reinterpret_cast<const float4*>(staged);
     else
-      DLIOM_HIP_TRY(hipMemcpyAsync(base, staged, total, hipMemcpyHostToDevice, ctx->stream));
+      DLIOM_HIP_TRY(hipMemcpyAsync(base, staged, l.total, hipMemcpyHostToDevice, ctx->stream));
   } else {
-    DLIOM_HIP_TRY(hipMemcpyAsync(base, host.data(), total, hipMemcpyHostToDevice, ctx->stream));
-    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `host` dies at scope exit
+    std::vector<char>& host = state_of(ctx)->host_tables;
+    host.resize(l.total);
+    fill_candidate_tables(c, l, host.data());
+    DLIOM_HIP_TRY(hipMemcpyAsync(base, host.data(), l.total, hipMemcpyHostToDevice, ctx->stream));
+    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `host` is the next match's as well
   }
-  d->rot = reinterpret_cast<float4*>(base);
-  d->trans = reinterpret_cast<float*>(base + bytes_rot);
-  d->t_norm = reinterpret_cast<float*>(base + bytes_rot + bytes_trans);
-  d->r_angle = reinterpret_cast<float*>(base + bytes_rot + bytes_trans + bytes_tn);
-  d->trans4 = reinterpret_cast<float4*>(base + bytes_rot + bytes_trans + bytes_tn + bytes_ra);
+  d->rot = reinterpret_cast<float4*>(base + l.rot);
+  d->trans = reinterpret_cast<float*>(base + l.trans);
+  d->t_norm = reinterpret_cast<float*>(base + l.t_norm);
+  d->r_angle = reinterpret_cast<float*>(base + l.r_angle);
+  d->trans4 = reinterpret_cast<float4*>(base + l.trans4);
   return DLIOM_OK;
 }
 
 static int env_int(const char* name, int fallback) { return tuning_int(name, fallback); }  // experiments builds only
+
+#ifdef DLIOM_EXPERIMENTS
+// Host time of a match from match_begin()'s entry to its first launch, and to the laps on the way (DLIOM_HOST_PREP_TIMING=1:
+// one line on stderr when the library is unloaded; tools/critical_path.py reads it).  Laps: 0 candidates generated,
+// 1 tables staged, 2 mirror and Morton copies ensured, 3 box tables built, 4 span opened, 5 = the total.
+struct HostPrepClock {
+  static constexpr int kLaps = 6;
+  std::chrono::steady_clock::time_point t0;
+  std::vector<float> us[kLaps];
+  void start() { t0 = std::chrono::steady_clock::now(); }
+  void lap(int k) { us[k].push_back(std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t0).count()); }
+  void stop() { lap(kLaps - 1); }
+  ~HostPrepClock() {
+    std::vector<float>& total = us[kLaps - 1];
+    if (total.empty() || env_int("DLIOM_HOST_PREP_TIMING", 0) == 0) return;
+    double sum = 0.0;
+    for (float v : total) sum += v;
+    for (std::vector<float>& v : us) std::sort(v.begin(), v.end());
+    std::fprintf(stderr, "rtcsm host prep: matches %zu mean_us %.2f median_us %.2f min_us %.2f lap_medians_us", total.size(),
+                 sum / total.size(), total[total.size() / 2], total.front());
+    for (const std::vector<float>& v : us) std::fprintf(stderr, " %.2f", v.empty() ? 0.f : v[v.size() / 2]);
+    std::fprintf(stderr, "\n");
+  }
+};
+static HostPrepClock g_host_prep;
+#define DLIOM_PREP_LAP(k) g_host_prep.lap(k)
+#else
+#define DLIOM_PREP_LAP(k) ((void)0)
+#endif
 
 // LDS-box score kernel (score_box.h): builds the per-pass constants in double and launches it.
 // Returns DLIOM_ERR_CAPACITY when the search does not suit the kernel (the caller then uses the dense
@@ -710,8 +666,36 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   // (the reference's own float rounding of r + t and of the quotient, 2 |q| 2^-24): the band widens with it, nothing
   // breaks -- any cell DynamicGrid can address (|q| < 8192 + range) is fine.
   if (!std::isfinite(qmax) || qmax > 16500.0) return (ctx->last_box_refusal = DLIOM_BOX_REFUSED_RANGE, DLIOM_ERR_CAPACITY);
-  std::vector<Pass> pass(static_cast<size_t>(passes));
-  std::vector<float> tau(static_cast<size_t>(passes) * TC * 4, 0.f);
+  // ---- waves per workgroup, rotation blocks (what the tables' sizes depend on)
+  const int rot_groups_all = (r_last - r_first + 63) / 64;
+  static const int forced_nw = env_int("DLIOM_BOX_NW", 0);  // tuning knob
+  const int nw = forced_nw >= 1 && forced_nw <= kWaves
+                     ? std::min(forced_nw, rot_groups_all)
+                     : std::min(rot_groups_all, kWaves);  // four waves = one per SIMD: measured 2-3 % faster than three even
+                                                          // when that leaves idle waves in the last rotation block
+  const int rot_blocks = (rot_groups_all + nw - 1) / nw;
+  // ---- host tables [tau | passes | groups | bitmaps], built where they are staged: in the pinned block when they fit
+  // (a few KB), else in the match state's own buffer.  A refusal below leaves them half written: nobody reads them then.
+  const size_t tau_count = static_cast<size_t>(passes) * TC * 4, bitmap_count = static_cast<size_t>(passes) * kBitmapWords;
+  const size_t tau_bytes = align256(tau_count * 4);
+  const size_t pass_only_bytes = align256(static_cast<size_t>(passes) * sizeof(Pass));
+  const size_t group_bytes = align256(static_cast<size_t>(rot_blocks) * sizeof(Group));
+  const size_t bitmap_bytes = align256(bitmap_count * 4);
+  const size_t pass_bytes = pass_only_bytes + group_bytes + bitmap_bytes;  // [passes | groups | bitmaps]
+  const bool tables_staged = tau_bytes + pass_bytes <= kPinBoxTables.bytes;
+  char* h = nullptr;
+  if (tables_staged) {
+    h = pinned_at<char>(ctx, kPinBoxTables);
+  } else {
+    std::vector<char>& host = state_of(ctx)->host_box_tables;
+    host.resize(tau_bytes + pass_bytes);
+    h = host.data();
+  }
+  float* const tau = reinterpret_cast<float*>(h);
+  Pass* const pass = reinterpret_cast<Pass*>(h + tau_bytes);
+  unsigned* const bitmap = reinterpret_cast<unsigned*>(h + tau_bytes + pass_only_bytes + group_bytes);
+  std::memset(tau, 0, tau_count * 4);
+  std::memset(pass, 0, static_cast<size_t>(passes) * sizeof(Pass));
   double taumax = 0.0;
   for (int tp = 0; tp < passes; ++tp) {  // pass centres first: taumax enters the band
     const int j0 = tp * TC, tc = std::min(TC, T - j0);
@@ -764,12 +748,12 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   }
   // ---- band bitmap: fractions phi of a scaled coordinate for which SOME translation of the pass gives
   // frac16(fl(phi + tau_j)) <= thr, i.e. frac(phi + tau_j) in [-u/2, (thr + 1/2) u]; one u of margin each side
-  std::vector<unsigned> bitmap(static_cast<size_t>(passes) * kBitmapWords, 0u);
+  std::memset(bitmap, 0, bitmap_count * 4);
   const unsigned thr_units = static_cast<unsigned>(s_units + B);
   for (int tp = 0; tp < passes; ++tp) {
     const Pass& ps = pass[static_cast<size_t>(tp)];
     for (int a = 0; a < 3; ++a) {
-      unsigned* words = bitmap.data() + static_cast<size_t>(tp) * kBitmapWords + static_cast<size_t>(a) * (kBuckets / 32);
+      unsigned* words = bitmap + static_cast<size_t>(tp) * kBitmapWords + static_cast<size_t>(a) * (kBuckets / 32);
       for (int jj = 0; jj < ps.tc; ++jj) {
         const double tv = static_cast<double>(tau[(static_cast<size_t>(tp) * TC + jj) * 4 + a]);
         const double af = tv - std::floor(tv);
@@ -791,14 +775,6 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
     if (dim > kMaxDim || dim * dim * (dim * 0.25) > cells) return (ctx->last_box_refusal = DLIOM_BOX_REFUSED_WINDOW, DLIOM_ERR_CAPACITY);
   }
   // ---- spread of every wave's 64 rotations around its centre lane (window only: q_init cancels)
-  const int rot_groups_all = (r_last - r_first + 63) / 64;
-  // waves per workgroup
-  static const int forced_nw = env_int("DLIOM_BOX_NW", 0);  // tuning knob
-  const int nw = forced_nw >= 1 && forced_nw <= kWaves
-                     ? std::min(forced_nw, rot_groups_all)
-                     : std::min(rot_groups_all, kWaves);  // four waves = one per SIMD: measured 2-3 % faster than three even
-                                                          // when that leaves idle waves in the last rotation block
-  const int rot_blocks = (rot_groups_all + nw - 1) / nw;
   if (TC * sizeof(float4) + kBitmapWords * 4 + 16 + static_cast<size_t>(nw) * kListWords * 4 + static_cast<size_t>(cells) * 2 >
       160 * 1024)
     return (ctx->last_box_refusal = DLIOM_BOX_REFUSED_LDS, DLIOM_ERR_CAPACITY);  // LDS budget (checked again where the launch is sized)
@@ -826,36 +802,13 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
       gr.c_lane = 0;
       continue;
     }
-    auto qd = [&](int r, double q[4]) {
-      const QF& f = c.rot_raw[static_cast<size_t>(r)];
-      const double nn = std::sqrt(double(f.w) * f.w + double(f.x) * f.x + double(f.y) * f.y + double(f.z) * f.z);
-      q[0] = f.w / nn; q[1] = f.x / nn; q[2] = f.y / nn; q[3] = f.z / nn;
-    };
-    double qc[4];
-    qd(r0 + gr.c_lane, qc);
-    double lo3[3] = {1e300, 1e300, 1e300}, hi3[3] = {-1e300, -1e300, -1e300}, th = 0.0;
-    for (int l = 0; l < cnt; ++l) {
-      double q[4];
-      qd(r0 + l, q);
-      // d = conj(qc) * q
-      const double a0 = qc[0], a1 = -qc[1], a2 = -qc[2], a3 = -qc[3];
-      double dq[4] = {a0 * q[0] - a1 * q[1] - a2 * q[2] - a3 * q[3], a0 * q[1] + a1 * q[0] + a2 * q[3] - a3 * q[2],
-                      a0 * q[2] - a1 * q[3] + a2 * q[0] + a3 * q[1], a0 * q[3] + a1 * q[2] - a2 * q[1] + a3 * q[0]};
-      if (dq[0] < 0) for (double& v : dq) v = -v;
-      const double vn = std::sqrt(dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]);
-      const double ang = 2.0 * std::atan2(vn, dq[0]);
-      const double k = vn > 1e-300 ? ang / vn : 2.0;
-      const double dv[3] = {k * dq[1], k * dq[2], k * dq[3]};
-      th = std::max(th, ang);
-      for (int a = 0; a < 3; ++a) {
-        lo3[a] = std::min(lo3[a], dv[a]);
-        hi3[a] = std::max(hi3[a], dv[a]);
-      }
-    }
+    RotationSpread sp;  // of the block's rotations around its centre lane (rtcsm_candidates.h)
+    rotation_spread(c, r0, cnt, &sp);
+    const double th = sp.max_angle;
     if (th > 0.3) return (ctx->last_box_refusal = DLIOM_BOX_REFUSED_WINDOW, DLIOM_ERR_CAPACITY);  // the second-order bound below assumes small relative rotations
     for (int a = 0; a < 3; ++a) {
-      gr.dc[a] = static_cast<float>(0.5 * (lo3[a] + hi3[a]));
-      gr.hd[a] = static_cast<float>(0.5 * (hi3[a] - lo3[a]) * 1.0001 + 1e-7);
+      gr.dc[a] = static_cast<float>(0.5 * (sp.lo[a] + sp.hi[a]));
+      gr.hd[a] = static_cast<float>(0.5 * (sp.hi[a] - sp.lo[a]) * 1.0001 + 1e-7);
     }
     gr.theta2 = static_cast<float>(0.51 * th * th * 1.01 + 1e-9);
   }
@@ -864,40 +817,27 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   gcache.r_first = r_first;
   gcache.r_last = r_last;
   gcache.nw = nw;
+  DLIOM_PREP_LAP(3);
   // every refusal (DLIOM_ERR_CAPACITY) is behind us: the launch below is what DLIOM_KERNEL_RTCSM_SCORE times
   struct SpanGuard {
     dliom_ctx* c;
     int span;
     ~SpanGuard() { c->end_span(span); }
   } span_guard{ctx, ctx->begin_span(DLIOM_KERNEL_RTCSM_SCORE)};
+  DLIOM_PREP_LAP(4);
   // ---- device tables (after the candidate tables inside ctx->cand would alias uploads in flight: own buffer)
-  const size_t tau_bytes = align256(tau.size() * 4);
-  const size_t pass_only_bytes = align256(pass.size() * sizeof(Pass));
-  const size_t group_bytes = align256(groups.size() * sizeof(Group));
-  const size_t bitmap_bytes = align256(bitmap.size() * 4);
-  const size_t pass_bytes = pass_only_bytes + group_bytes + bitmap_bytes;  // [passes | groups | bitmaps]
   DLIOM_TRY(ctx->box_tables.reserve(tau_bytes + pass_bytes));
   char* base = static_cast<char*>(ctx->box_tables.p);
   const Group* group_src = reinterpret_cast<const Group*>(base + tau_bytes + pass_only_bytes);  // for the pre-pass (below)
-  // small (a few KB): staged through the pinned block when it fits, else a synchronous copy
-  if (tau_bytes + pass_bytes <= kPinBoxTables.bytes) {
-    char* h = pinned_at<char>(ctx, kPinBoxTables);
-    std::memcpy(h, tau.data(), tau.size() * 4);
-    std::memcpy(h + tau_bytes, pass.data(), pass.size() * sizeof(Pass));
-    std::memcpy(h + tau_bytes + pass_only_bytes, groups.data(), groups.size() * sizeof(Group));
-    std::memcpy(h + tau_bytes + pass_only_bytes + group_bytes, bitmap.data(), bitmap.size() * 4);
+  std::memcpy(h + tau_bytes + pass_only_bytes, groups.data(), groups.size() * sizeof(Group));
+  if (tables_staged) {
     if (prep_add(prep, base, h, tau_bytes + pass_bytes, 0u))  // rides in the pre-pass, which reads its groups from the staging copy
       group_src = reinterpret_cast<const Group*>(h + tau_bytes + pass_only_bytes);
     else
       DLIOM_HIP_TRY(hipMemcpyAsync(base, h, tau_bytes + pass_bytes, hipMemcpyHostToDevice, ctx->stream));
   } else {
-    DLIOM_HIP_TRY(hipMemcpyAsync(base, tau.data(), tau.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    DLIOM_HIP_TRY(hipMemcpyAsync(base + tau_bytes, pass.data(), pass.size() * sizeof(Pass), hipMemcpyHostToDevice, ctx->stream));
-    DLIOM_HIP_TRY(hipMemcpyAsync(base + tau_bytes + pass_only_bytes, groups.data(), groups.size() * sizeof(Group),
-                                 hipMemcpyHostToDevice, ctx->stream));
-    DLIOM_HIP_TRY(hipMemcpyAsync(base + tau_bytes + pass_only_bytes + group_bytes, bitmap.data(), bitmap.size() * 4,
-                                 hipMemcpyHostToDevice, ctx->stream));
-    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    DLIOM_HIP_TRY(hipMemcpyAsync(base, h, tau_bytes + pass_bytes, hipMemcpyHostToDevice, ctx->stream));
+    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // pageable: the buffer is the next match's as well
   }
   Params p;
   p.tau = reinterpret_cast<const float4*>(base);
@@ -967,6 +907,9 @@ static int launch_score_box(dliom_ctx* ctx, const dliom_cloud& cloud, const Grid
   p.ext_stride = static_cast<int>(cloud.n_padded);
   DLIOM_TRY(ctx->box_extents.reserve(static_cast<size_t>(rot_blocks) * 6 * static_cast<size_t>(cloud.n_padded) * 4));
   p.ext = ctx->box_extents.as<float>();
+#ifdef DLIOM_EXPERIMENTS
+  g_host_prep.stop();
+#endif
   {
     // the pre-pass is the first kernel of the match: one more row of workgroups carries the pending copies and fills
     PrepArgs none;
@@ -1137,6 +1080,7 @@ static int run_score_volume(dliom_ctx* ctx, const dliom_cloud& cloud, const dlio
   PrepArgs prep;
   prep.n = 0;
   DLIOM_TRY(upload_candidates(ctx, c, d, &prep));
+  DLIOM_PREP_LAP(1);
   const int64_t C = c.w.num_candidates;
   DLIOM_TRY(ctx->sums.reserve(static_cast<size_t>(C) * 8));
   *d_sums = ctx->sums.as<unsigned long long>();
@@ -1178,6 +1122,7 @@ static int run_score_volume(dliom_ctx* ctx, const dliom_cloud& cloud, const dlio
   if (windowed && mapping == 2) mapping = 1;
   const GridView g = grid->view();
   DLIOM_TRY(ensure_morton(ctx, &cloud));
+  DLIOM_PREP_LAP(2);
   if (g.log2_leaves > 10 && mapping >= 1) {  // bits = 8: only the point-per-lane kernel has 64-bit table indices
     if (mapping == 3) ctx->last_box_refusal = DLIOM_BOX_REFUSED_NO_MIRROR;
     mapping = 0;
@@ -1243,26 +1188,6 @@ static const LutModel& lut_model() {
   return m;
 }
 
-// State of a (possibly sharded) match between its phases; lives in dliom_ctx::rtcsm_state.
-struct RtcsmState {
-  dliom_rtcsm_options o;
-  Candidates c;
-  DeviceCandidates d;
-  dliom_cloud cloud;
-  const dliom_grid* grid = nullptr;
-  int r_first = 0, r_last = 0;
-  unsigned long long* d_sums = nullptr;
-  float* d_hi = nullptr;
-  unsigned* d_list = nullptr;
-  unsigned* d_ctrs = nullptr;
-  float best_score = -1.f;
-  int64_t best_c = -1;
-  bool active = false;
-  double init7[7] = {0, 0, 0, 1, 0, 0, 0};
-  int shard = 0, num_shards = 1;
-  bool used_box = false;
-};
-
 // The LDS-box kernel checks its own fast index against the reference's arithmetic wherever the two could differ; an
 // exact cell more than one cell away from the fast one contradicts the error budget of score_box.h ("cannot
 // happen").  If it ever does, the kernel sets box_error[0] (sticky, dliom_rtcsm3d_box_error) and box_error[1]: the
@@ -1277,20 +1202,15 @@ static int box_overflowed(dliom_ctx* ctx, unsigned err1, bool* overflow) {
   return DLIOM_OK;
 }
 
-static RtcsmState* state_of(dliom_ctx* ctx) {
-  if (ctx->rtcsm_state == nullptr) {
-    ctx->rtcsm_state = new RtcsmState;
-    ctx->rtcsm_state_free = [](void* p) { delete static_cast<RtcsmState*>(p); };
-  }
-  return static_cast<RtcsmState*>(ctx->rtcsm_state);
-}
-
 // Phase 1: score volume + score bounds for the rotations [shard * R / num_shards, ...).
 // local_best_lo_bits (optional) receives this shard's best lower bound (float bits) -- the
 // quantity that is max-all-reduced when the window is sharded across GPUs.
 static int match_begin(dliom_ctx* ctx, const dliom_rtcsm_options* o, const double init7[7],
                        const dliom_cloud& cloud, const dliom_grid* grid, int shard, int num_shards,
                        unsigned* local_best_lo_bits) {
+#ifdef DLIOM_EXPERIMENTS
+  g_host_prep.start();
+#endif
   if (cloud.n <= 0) return DLIOM_ERR_EMPTY_CLOUD;
   if (cloud.n > (1 << 27) || num_shards < 1 || shard < 0 || shard >= num_shards)
     return DLIOM_ERR_INVALID_ARGUMENT;
@@ -1305,6 +1225,7 @@ static int match_begin(dliom_ctx* ctx, const dliom_rtcsm_options* o, const doubl
   st->used_box = false;
   Candidates& c = st->c;
   generate_candidates(*o, grid->resolution, cloud.max_norm, init7, &c);
+  DLIOM_PREP_LAP(0);
   const int64_t C = c.w.num_candidates;
   const int R = static_cast<int>(c.w.num_rotations), T = static_cast<int>(c.w.num_translations);
   if (C <= 0 || C > (int64_t{1} << 31)) return DLIOM_ERR_INVALID_ARGUMENT;
@@ -1504,10 +1425,11 @@ static int match_decode(dliom_ctx* ctx, uint64_t best_packed, double out7[7], fl
   out7[0] = c.trans[j].x;
   out7[1] = c.trans[j].y;
   out7[2] = c.trans[j].z;
-  out7[3] = c.rot[r].w;
-  out7[4] = c.rot[r].x;
-  out7[5] = c.rot[r].y;
-  out7[6] = c.rot[r].z;
+  const QF q = c.rot(static_cast<size_t>(r));  // the table's entry, bit for bit (rtcsm_candidates.h)
+  out7[3] = q.w;
+  out7[4] = q.x;
+  out7[5] = q.y;
+  out7[6] = q.z;
   *out_score = score;
   ctx->last_rtcsm.best_index = best_c;
   return DLIOM_OK;
