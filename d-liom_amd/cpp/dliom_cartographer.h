@@ -16,6 +16,7 @@
 //   dliom::io::MinMaxRangeFiteringPointsProcessor             io/min_max_range_filtering_points_processor.h:30-53
 //   dliom::io::OutlierRemovingPointsProcessor                 io/outlier_removing_points_processor.h:29-82
 //   dliom::mapping::constraints::SubmapFeatureMatcher         mapping/internal/constraints/constraint_builder_3d.cc:459-529
+//   dliom::io::SubmapSlice / FillSubmapSlice / PaintSubmapSlices  io/submap_painter.h:30-94 (+ CreateOccupancyGrid)
 //
 // The value types below are layout-compatible stand-ins for Eigen::Vector3f / transform::Rigid3d
 // so that this header builds without Eigen; inside cartographer the same adapters are
@@ -2774,6 +2775,140 @@ class XRayPointsProcessor : public PointsProcessor {
   ImageSink sink_;
   std::vector<dliom_points_xray*> aggregations_;
 };
+
+// ---- io/submap_painter.{h,cc}: the map of all submaps -------------------------------------------------------------------
+// A slice's texture lives in HBM (dliom_submap_slice) where the reference keeps a cairo surface; PaintSubmapSlices
+// composites the slices on the device in std::map order (dliom.h "painting submap slices into one map") and returns
+// pixels, not a cairo surface: cairo's trajectory drawing and PNG stay with the caller.
+struct PaintSubmapSlicesResult {  // submap_painter.h:30-38
+  std::vector<uint32_t> pixels;   // height x width, alpha << 24 | red << 16 | green << 8 | blue (CAIRO_FORMAT_ARGB32)
+  int width = 0;
+  int height = 0;
+  std::array<float, 2> origin{{0.f, 0.f}};  // top left pixel of `pixels` in map frame
+};
+
+struct SubmapSlice {  // submap_painter.h:40-57
+  // Texture data.
+  int width = 0;
+  int height = 0;
+  int version = 0;
+  double resolution = 0.;
+  transform::Rigid3d slice_pose;
+  std::shared_ptr<dliom_submap_slice> surface;  // the texture, on the device; null: PaintSubmapSlices stops there (.cc:38)
+  // Metadata.
+  transform::Rigid3d pose;  // set it after an optimisation as the reference does: the next paint uses it, no texel moves
+  int metadata_version = -1;
+};
+
+struct SubmapTexturePixels {  // SubmapTexture::Pixels, submap_painter.h:60-63
+  std::vector<char> intensity;
+  std::vector<char> alpha;
+};
+
+// UnpackTextureData (submap_painter.cc:140-156) without its gunzip step: `cells` are the uncompressed bytes
+inline SubmapTexturePixels UnpackTextureData(const std::string& cells, int width, int height) {
+  SubmapTexturePixels pixels;
+  const size_t num_pixels = static_cast<size_t>(width) * height;
+  if (cells.size() != 2 * num_pixels) Check(DLIOM_ERR_INVALID_ARGUMENT, "UnpackTextureData: CHECK_EQ(cells.size(), 2 * num_pixels)");
+  for (size_t i = 0; i < num_pixels; ++i) {
+    pixels.intensity.push_back(cells[2 * i]);
+    pixels.alpha.push_back(cells[2 * i + 1]);
+  }
+  return pixels;
+}
+
+namespace internal {
+inline void AdoptSlice(dliom_submap_slice* handle, SubmapSlice* submap_slice) {
+  submap_slice->surface = std::shared_ptr<dliom_submap_slice>(handle, [](dliom_submap_slice* s) { dliom_submap_slice_destroy(s); });
+  dliom_submap_slice_description d;
+  Check(dliom_submap_slice_info(handle, &d), "dliom_submap_slice_info");
+  submap_slice->width = d.width;
+  submap_slice->height = d.height;
+  submap_slice->resolution = d.resolution;
+  submap_slice->slice_pose = transform::Rigid3d::FromArray(d.slice_pose7);
+  submap_slice->pose = transform::Rigid3d::FromArray(d.pose7);
+}
+}  // namespace internal
+
+// FillSubmapSlice (submap_painter.cc:110-138) for a 3D submap on the device: textures(0), the high resolution grid's, made
+// by the X-ray kernels and kept in HBM.  2D submaps are not covered.
+inline void FillSubmapSlice(const transform::Rigid3d& global_submap_pose, const mapping::Submap3D& submap,
+                            SubmapSlice* const submap_slice) {
+  const std::array<double, 7> pose = global_submap_pose.ToArray();
+  dliom_submap_slice* handle = nullptr;
+  Check(dliom_submap_slice_create_from_grid(submap.high_resolution_hybrid_grid(), pose.data(), &handle),
+        "dliom_submap_slice_create_from_grid");
+  internal::AdoptSlice(handle, submap_slice);
+  submap_slice->version = submap.num_range_data();
+}
+// ... and for a texture that arrived as bytes (a SubmapQuery response, cells uncompressed): uploaded once
+inline void FillSubmapSlice(Context* context, const transform::Rigid3d& global_submap_pose, const mapping::SubmapTexture& texture,
+                            SubmapSlice* const submap_slice) {
+  const std::array<double, 7> pose = global_submap_pose.ToArray(), slice_pose = texture.slice_pose.ToArray();
+  if (texture.cells.size() != 2 * static_cast<size_t>(texture.width) * texture.height)
+    Check(DLIOM_ERR_INVALID_ARGUMENT, "FillSubmapSlice: CHECK_EQ(cells.size(), 2 * num_pixels)");
+  dliom_submap_slice* handle = nullptr;
+  Check(dliom_submap_slice_create(context->get(), reinterpret_cast<const uint8_t*>(texture.cells.data()), texture.width,
+                                  texture.height, texture.resolution, slice_pose.data(), pose.data(), &handle),
+        "dliom_submap_slice_create");
+  internal::AdoptSlice(handle, submap_slice);
+}
+
+namespace internal {
+// the handles in std::map order up to the first slice without a texture, their poses brought up to date
+inline std::vector<const dliom_submap_slice*> SliceHandles(const std::map<mapping::SubmapId, SubmapSlice>& submaps) {
+  std::vector<const dliom_submap_slice*> handles;
+  for (const auto& pair : submaps) {
+    if (pair.second.surface == nullptr) break;
+    const std::array<double, 7> pose = pair.second.pose.ToArray();
+    Check(dliom_submap_slice_set_pose(pair.second.surface.get(), pose.data()), "dliom_submap_slice_set_pose");
+    handles.push_back(pair.second.surface.get());
+  }
+  return handles;
+}
+}  // namespace internal
+
+// PaintSubmapSlices (submap_painter.cc:62-108)
+inline PaintSubmapSlicesResult PaintSubmapSlices(const std::map<mapping::SubmapId, SubmapSlice>& submaps, const double resolution) {
+  const std::vector<const dliom_submap_slice*> handles = internal::SliceHandles(submaps);
+  PaintSubmapSlicesResult r;
+  int32_t w = 0, h = 0;
+  const int64_t n = static_cast<int64_t>(handles.size());
+  Check(dliom_submap_slices_paint(nullptr, handles.data(), n, resolution, nullptr, 0, &w, &h, r.origin.data()),
+        "dliom_submap_slices_paint");
+  r.pixels.resize(static_cast<size_t>(w) * h);
+  Check(dliom_submap_slices_paint(nullptr, handles.data(), n, resolution, r.pixels.data(), static_cast<int64_t>(r.pixels.size()), &w,
+                                  &h, r.origin.data()), "dliom_submap_slices_paint");
+  r.width = w;
+  r.height = h;
+  return r;
+}
+
+// nav_msgs::OccupancyGrid's info and data (cartographer_ros msg_conversion.cc:321-368) as a plain struct: header.stamp,
+// frame_id and map_load_time stay with the caller; origin orientation is the identity
+struct OccupancyGrid {
+  double resolution = 0.;
+  int width = 0;
+  int height = 0;
+  std::array<double, 3> origin_position{{0., 0., 0.}};
+  std::vector<int8_t> data;
+};
+// PaintSubmapSlices + CreateOccupancyGridMsg in one call: painted and converted on the device, one byte a cell comes back
+inline OccupancyGrid CreateOccupancyGrid(const std::map<mapping::SubmapId, SubmapSlice>& submaps, const double resolution) {
+  const std::vector<const dliom_submap_slice*> handles = internal::SliceHandles(submaps);
+  OccupancyGrid g;
+  g.resolution = resolution;
+  int32_t w = 0, h = 0;
+  const int64_t n = static_cast<int64_t>(handles.size());
+  Check(dliom_submap_slices_occupancy(nullptr, handles.data(), n, resolution, nullptr, 0, &w, &h, nullptr, g.origin_position.data()),
+        "dliom_submap_slices_occupancy");
+  g.data.resize(static_cast<size_t>(w) * h);
+  Check(dliom_submap_slices_occupancy(nullptr, handles.data(), n, resolution, g.data.data(), static_cast<int64_t>(g.data.size()), &w,
+                                      &h, nullptr, g.origin_position.data()), "dliom_submap_slices_occupancy");
+  g.width = w;
+  g.height = h;
+  return g;
+}
 
 }  // namespace io
 }  // namespace dliom

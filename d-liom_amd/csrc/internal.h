@@ -134,6 +134,9 @@ struct dliom_ctx {
   dliom::DevBuf xray_leaves, xray_cells;
   // the submap image features (surf.hip): what is sized by the image and the candidates; what is sized by the key points
   dliom::DevBuf surf, surf_out;
+  // the submap painter (submap_painter.hip): slice records, tile lists and the painted map of one paint
+  dliom::DevBuf painter;
+  int64_t painter_launches = 0, painter_pairs = 0, painter_texels_uploaded = 0;  // dliom_ctx_submap_painter_stats
   bool surf_tables_ready = false;  // `surf` holds the Gaussian tables: cleared whenever reserve() made a new allocation
   // the export stages (compact.hip): keep flags, their scan and the survivors' indices; the voxel list of a table dump
   dliom::DevBuf outlier;
@@ -330,6 +333,10 @@ int project_to_image_on_device(const dliom_grid* grid, const double transform7[7
 // More than DLIOM_SURF_MAX_KEYPOINTS candidates: DLIOM_ERR_CAPACITY with *count = their number.
 int surf_features_on_device(dliom_ctx* ctx, const uint8_t* image, int width, int height, const dliom_surf_options& options,
                             const float** keypoints, const float** descriptors, int* count);
+// xray.hip: dliom_grid_xray_texture with the cells left in HBM (*cells: ctx->xray_cells, valid until the context's next
+// projection; nullptr under an empty projection).  Nothing is waited for after the kernels.
+int xray_texture_on_device(const dliom_grid* grid, const double global_submap_pose7[7], const uint8_t** cells, int32_t* width,
+                           int32_t* height, double* resolution, double slice_pose7[7]);
 int surf_check_options(const dliom_surf_options* options);  // DLIOM_OK or DLIOM_ERR_INVALID_ARGUMENT
 
 constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }

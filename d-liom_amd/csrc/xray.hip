@@ -431,7 +431,41 @@ int project_to_image(const dliom_grid* grid, const double transform7[7], uint8_t
   return s;
 }
 
+// AddToTextureProto (submap_3d.cc:53-177) behind dliom_grid_xray_texture; device_cells != nullptr: see run_xray
+int xray_texture(const dliom_grid* grid, const double global_submap_pose7[7], uint8_t* cells, int64_t capacity,
+                 const uint8_t** device_cells, int32_t* width, int32_t* height, double* resolution, double slice_pose7[7]) {
+  const PoseD g = pose_from7(global_submap_pose7);
+  XrayTransform T;
+  T.q = Quat4{static_cast<float>(g.q[0]), static_cast<float>(g.q[1]), static_cast<float>(g.q[2]), static_cast<float>(g.q[3])};
+  for (int i = 0; i < 3; ++i) T.t[i] = static_cast<float>(g.t[i]);  // global_submap_pose.cast<float>()
+  T.resolution = grid->resolution;
+  T.inv_resolution = 1.f / grid->resolution;  // submap_3d.cc:85
+  T.threshold = obstructed_threshold();
+  XrayResult r;
+  const int s = run_xray(grid, T, true, cells, capacity, &r, device_cells);
+  *width = static_cast<int32_t>(r.width);
+  *height = static_cast<int32_t>(r.height);
+  *resolution = grid->resolution;
+  // global_submap_pose.inverse() * Translation(max_x * res, max_y * res, t.z): float products widened (submap_3d.cc:173-176)
+  PoseD slice;
+  slice.t[0] = static_cast<double>(static_cast<float>(r.max_x) * grid->resolution);
+  slice.t[1] = static_cast<double>(static_cast<float>(r.max_y) * grid->resolution);
+  slice.t[2] = g.t[2];
+  slice.q[0] = 1.0;
+  slice.q[1] = slice.q[2] = slice.q[3] = 0.0;
+  const PoseD sp = pose_mul(pose_inverse(g), slice);
+  for (int i = 0; i < 3; ++i) slice_pose7[i] = sp.t[i];
+  for (int i = 0; i < 4; ++i) slice_pose7[3 + i] = sp.q[i];
+  return s;
+}
+
 }  // namespace
+
+int xray_texture_on_device(const dliom_grid* grid, const double global_submap_pose7[7], const uint8_t** cells, int32_t* width,
+                           int32_t* height, double* resolution, double slice_pose7[7]) {
+  *cells = nullptr;  // stays so under an empty projection
+  return xray_texture(grid, global_submap_pose7, nullptr, 0, cells, width, height, resolution, slice_pose7);
+}
 
 int project_to_image_on_device(const dliom_grid* grid, const double transform7[7], const uint8_t** image, int32_t* width,
                                int32_t* height, double* ox, double* oy, double* resolution) {
@@ -454,29 +488,7 @@ int dliom_grid_xray_texture(const dliom_grid* grid, const double global_submap_p
   if (grid == nullptr || global_submap_pose7 == nullptr || width == nullptr || height == nullptr || resolution == nullptr ||
       slice_pose7 == nullptr || capacity < 0)
     return DLIOM_ERR_INVALID_ARGUMENT;
-  const PoseD g = pose_from7(global_submap_pose7);
-  XrayTransform T;
-  T.q = Quat4{static_cast<float>(g.q[0]), static_cast<float>(g.q[1]), static_cast<float>(g.q[2]), static_cast<float>(g.q[3])};
-  for (int i = 0; i < 3; ++i) T.t[i] = static_cast<float>(g.t[i]);  // global_submap_pose.cast<float>()
-  T.resolution = grid->resolution;
-  T.inv_resolution = 1.f / grid->resolution;  // submap_3d.cc:85
-  T.threshold = obstructed_threshold();
-  XrayResult r;
-  const int s = run_xray(grid, T, true, cells, capacity, &r);
-  *width = static_cast<int32_t>(r.width);
-  *height = static_cast<int32_t>(r.height);
-  *resolution = grid->resolution;
-  // global_submap_pose.inverse() * Translation(max_x * res, max_y * res, t.z): float products widened (submap_3d.cc:173-176)
-  PoseD slice;
-  slice.t[0] = static_cast<double>(static_cast<float>(r.max_x) * grid->resolution);
-  slice.t[1] = static_cast<double>(static_cast<float>(r.max_y) * grid->resolution);
-  slice.t[2] = g.t[2];
-  slice.q[0] = 1.0;
-  slice.q[1] = slice.q[2] = slice.q[3] = 0.0;
-  const PoseD sp = pose_mul(pose_inverse(g), slice);
-  for (int i = 0; i < 3; ++i) slice_pose7[i] = sp.t[i];
-  for (int i = 0; i < 4; ++i) slice_pose7[3 + i] = sp.q[i];
-  return s;
+  return xray_texture(grid, global_submap_pose7, cells, capacity, nullptr, width, height, resolution, slice_pose7);
 }
 
 int dliom_grid_project_to_image(const dliom_grid* grid, const double transform7[7], uint8_t* image, int64_t capacity,

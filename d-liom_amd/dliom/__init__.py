@@ -2852,3 +2852,128 @@ def surf_detect_and_compute(ctx, image, options, capacity=None):
     _check(ctx._L.dliom_surf_detect_and_compute(*args, _p(kp, _f32p), _p(desc, _f32p), capacity, C.byref(n)),
            "dliom_surf_detect_and_compute")
     return kp[:n.value], desc[:n.value]
+
+
+# ---- painting submap slices into one map (dliom.h "painting submap slices into one map") -------------------------------
+class SubmapSliceDescription(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("resolution", C.c_double), ("slice_pose7", C.c_double * 7),
+                ("pose7", C.c_double * 7)]
+
+
+class SubmapPainterStats(C.Structure):
+    _fields_ = [("launches", C.c_int64), ("texels_uploaded", C.c_int64), ("tile_slice_pairs", C.c_int64)]
+
+
+SUBMAP_PAINTER_TILE, SUBMAP_PAINTER_MAX_PAIRS = 16, 1 << 30
+_i8p = C.POINTER(C.c_int8)
+_slicep = C.POINTER(SubmapSliceDescription)
+SYMBOLS += [
+    ("dliom_submap_slice_create", C.c_int, [_vp, _u8p, C.c_int32, C.c_int32, C.c_double, _f64p, _f64p, C.POINTER(_vp)]),
+    ("dliom_submap_slice_create_from_grid", C.c_int, [_vp, _f64p, C.POINTER(_vp)]),
+    ("dliom_submap_slice_set_pose", C.c_int, [_vp, _f64p]),
+    ("dliom_submap_slice_info", C.c_int, [_vp, _slicep]),
+    ("dliom_submap_slice_destroy", C.c_int, [_vp]),
+    ("dliom_submap_slices_layout", C.c_int, [_slicep, C.c_int64, C.c_double, _i32p, _i32p, _f32p, _i64p]),
+    ("dliom_submap_occupancy_table", C.c_int, [_i8p]),
+    ("dliom_submap_slices_paint", C.c_int, [_vp, C.POINTER(_vp), C.c_int64, C.c_double, _u32p, C.c_int64, _i32p, _i32p, _f32p]),
+    ("dliom_submap_slices_occupancy", C.c_int, [_vp, C.POINTER(_vp), C.c_int64, C.c_double, _i8p, C.c_int64, _i32p, _i32p,
+                                                _f32p, _f64p]),
+    ("dliom_ctx_submap_painter_stats", C.c_int, [_vp, C.POINTER(SubmapPainterStats)]),
+]
+
+
+def submap_slice_description(width, height, resolution, slice_pose, pose):
+    return SubmapSliceDescription(int(width), int(height), float(resolution), (C.c_double * 7)(*_pose7(slice_pose)),
+                                  (C.c_double * 7)(*_pose7(pose)))
+
+
+def submap_slices_layout(descriptions, resolution):
+    """dliom_submap_slices_layout (host only) -> (status, width, height, origin float32[2], fixed int64 (n, 6): A B E C D G);
+    the status is returned, not raised: the sizes are filled under ERR_CAPACITY too."""
+    n = len(descriptions)
+    arr = (SubmapSliceDescription * max(n, 1))(*descriptions)
+    w, h = C.c_int32(), C.c_int32()
+    origin, fixed = np.zeros(2, np.float32), np.zeros((n, 6), np.int64)
+    status = load_library().dliom_submap_slices_layout(arr if n else None, n, float(resolution), C.byref(w), C.byref(h),
+                                                       _p(origin, _f32p), _p(fixed, _i64p))
+    return status, w.value, h.value, origin, fixed
+
+
+def submap_occupancy_table():
+    out = np.zeros(256, np.int8)
+    _check(load_library().dliom_submap_occupancy_table(_p(out, _i8p)), "dliom_submap_occupancy_table")
+    return out
+
+
+class SubmapSlice:
+    """io::SubmapSlice with its texture in HBM (dliom_submap_slice).  SubmapSlice(ctx, cells, resolution, slice_pose, pose)
+    uploads (height, width, 2) uint8 (intensity, alpha); SubmapSlice.from_grid(grid, global_submap_pose) is FillSubmapSlice."""
+
+    def __init__(self, ctx, cells, resolution, slice_pose, pose, _handle=None):
+        self._L = ctx._L
+        self.ctx = ctx
+        if _handle is not None:
+            self.h = _handle
+            return
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        if cells.ndim != 3 or cells.shape[2] != 2:
+            raise ValueError("cells are (height, width, 2) bytes: intensity, alpha")
+        h = _vp()
+        _check(self._L.dliom_submap_slice_create(ctx.h, _p(cells, _u8p) if cells.size else None, cells.shape[1], cells.shape[0],
+                                                 float(resolution), _p(_pose7(slice_pose), _f64p), _p(_pose7(pose), _f64p),
+                                                 C.byref(h)), "dliom_submap_slice_create")
+        self.h = h
+
+    @classmethod
+    def from_grid(cls, grid, global_submap_pose):
+        h = _vp()
+        _check(grid._L.dliom_submap_slice_create_from_grid(grid.h, _p(_pose7(global_submap_pose), _f64p), C.byref(h)),
+               "dliom_submap_slice_create_from_grid")
+        return cls(grid.ctx, None, 0.0, None, None, _handle=h)
+
+    def set_pose(self, pose):
+        _check(self._L.dliom_submap_slice_set_pose(self.h, _p(_pose7(pose), _f64p)), "dliom_submap_slice_set_pose")
+
+    def info(self):
+        d = SubmapSliceDescription()
+        _check(self._L.dliom_submap_slice_info(self.h, C.byref(d)), "dliom_submap_slice_info")
+        return d
+
+    def close(self):
+        if self.h is not None:
+            self._L.dliom_submap_slice_destroy(self.h)
+            self.h = None
+
+
+def _slice_handles(slices):
+    return (_vp * max(len(slices), 1))(*[s.h for s in slices])
+
+
+def paint_submap_slices(ctx, slices, resolution):
+    """io::PaintSubmapSlices on the device -> (pixels (height, width) uint32 ARGB, origin float32[2])"""
+    hs, n = _slice_handles(slices), len(slices)
+    w, h, origin = C.c_int32(), C.c_int32(), np.zeros(2, np.float32)
+    _check(ctx._L.dliom_submap_slices_paint(ctx.h, hs, n, float(resolution), None, 0, C.byref(w), C.byref(h), _p(origin, _f32p)),
+           "dliom_submap_slices_paint")
+    pixels = np.zeros((h.value, w.value), np.uint32)
+    _check(ctx._L.dliom_submap_slices_paint(ctx.h, hs, n, float(resolution), _p(pixels, _u32p), pixels.size, C.byref(w),
+                                            C.byref(h), _p(origin, _f32p)), "dliom_submap_slices_paint")
+    return pixels, origin
+
+
+def submap_slices_occupancy(ctx, slices, resolution):
+    """PaintSubmapSlices + CreateOccupancyGridMsg's cells -> (data (height, width) int8, origin_xy float64[2])"""
+    hs, n = _slice_handles(slices), len(slices)
+    w, h, origin_xy = C.c_int32(), C.c_int32(), np.zeros(2, np.float64)
+    _check(ctx._L.dliom_submap_slices_occupancy(ctx.h, hs, n, float(resolution), None, 0, C.byref(w), C.byref(h), None,
+                                                _p(origin_xy, _f64p)), "dliom_submap_slices_occupancy")
+    data = np.zeros((h.value, w.value), np.int8)
+    _check(ctx._L.dliom_submap_slices_occupancy(ctx.h, hs, n, float(resolution), _p(data, _i8p), data.size, C.byref(w),
+                                                C.byref(h), None, _p(origin_xy, _f64p)), "dliom_submap_slices_occupancy")
+    return data, origin_xy
+
+
+def submap_painter_stats(ctx):
+    s = SubmapPainterStats()
+    _check(ctx._L.dliom_ctx_submap_painter_stats(ctx.h, C.byref(s)), "dliom_ctx_submap_painter_stats")
+    return {k: getattr(s, k) for k, _ in SubmapPainterStats._fields_}

@@ -1722,6 +1722,108 @@ int dliom_feature_index_add_from_grid(dliom_feature_index* index, int64_t key, c
                                       const double transform7[7], const dliom_surf_options* options, int32_t* count, double* ox,
                                       double* oy, double* resolution);
 
+/* ---- painting submap slices into one map (io/submap_painter.cc:30-108, cartographer_ros msg_conversion.cc:321-368) ----
+ * io::PaintSubmapSlices draws every submap's X-ray texture into one ARGB32 image with cairo, and CreateOccupancyGridMsg
+ * turns that image into the /map occupancy grid.  Here the textures stay in HBM (dliom_submap_slice) and one gather
+ * kernel composites them: every output pixel is produced by one thread, samples every slice that can reach it once, in
+ * the order given, and is written once.  cairo is not a dependency, so the problem is stated here, once; the device
+ * equals a CPU model of this statement (tests/submap_painter_common.py) bit for bit, and the statement is checked against
+ * the system's cairo where there is one (tests/test_submap_painter_host.py).  The sampling below is pixman's bilinear
+ * filter, which is what cairo's default CAIRO_FILTER_GOOD uses whenever the map's resolution is no coarser than the
+ * slices' (0.05 m against 0.10 m, the occupancy grid node's default with 3D submaps): there the statement gives what the
+ * reference shows, up to cairo's own 16.16 rounding of the matrix (a few levels in red and green).  For a map coarser than
+ * a slice cairo >= 1.14 switches to a box-convolution filter: the statement stays bilinear, parity unpinned against cairo.
+ * cairo's trajectory drawing and PNG output stay out of scope: parity unpinned against cairo there too, nothing is built.
+ *
+ * The statement.  Integer or ordered double arithmetic throughout (-ffp-contract=off), no transcendental function.
+ *  Texel      a slice is height x width (intensity, alpha) byte pairs as dliom_grid_xray_texture emits them; the texel is
+ *             alpha << 24 | intensity << 16 | observed << 8 with observed = (intensity == 0 && alpha == 0) ? 0 : 255
+ *             (DrawTexture, submap_painter.cc:158-177).  A fetch outside the slice is 0.
+ *  Matrices   doubles.  P = pose * slice_pose (the Rigid3d product: t = pose.q * slice_pose.t + pose.t, q = normalized
+ *             quaternion product); with q = (w, x, y, z) of P and tx = 2x, ty = 2y, tz = 2z:
+ *               r00 = 1 - (ty*y + tz*z), r01 = ty*x - tz*w, r10 = ty*x + tz*w, r11 = 1 - (tx*x + tz*z)
+ *             m = (xx, yx, xy, yy, x0, y0) = (r10, r00, -r11, -r01, P.t[0], -P.t[1]) in cairo's convention
+ *             x' = xx*x + xy*y + x0, y' = yx*x + yy*y + y0.  With k = 1. / resolution and s = the slice's resolution the
+ *             slice's matrix Scale(s), then m, then Scale(k) -- cairo_matrix_multiply with its zero terms dropped -- is
+ *               L = ((m.xx*k)*s, (m.yx*k)*s, (m.xy*k)*s, (m.yy*k)*s, m.x0*k, m.y0*k)
+ *  Layout     the corners (0,0), (w,0), (0,h), (w,h) of every slice through L, (xx*x + xy*y) + x0 and (yx*x + yy*y) + y0,
+ *             each rounded to float; min and max over all slices in float; per axis size = int(ceil(max - min)) + 10 with
+ *             the difference in float, origin = -min + 5.f in float (kPaddingPixel = 5).  A slice with w == 0 or h == 0
+ *             contributes its corners like any other (one point when both are 0) and paints nothing.
+ *  Inverse    F = L with x0 + origin[0], y0 + origin[1] (double sums).  det = F.xx*F.yy - F.yx*F.xy and
+ *               ixx = F.yy/det, ixy = -F.xy/det, ix0 = (F.xy*F.y0 - F.yy*F.x0)/det
+ *               iyx = -F.yx/det, iyy = F.xx/det, iy0 = (F.yx*F.x0 - F.xx*F.y0)/det
+ *             A, B, E = rint(ixx * 2^32), rint(ixy * 2^32), rint(ix0 * 2^32) as int64 (round half to even), C, D, G
+ *             likewise from the second row: 32.32 fixed point.
+ *  Bound      refused with DLIOM_ERR_TOO_LARGE unless all six are finite, |ixx|, |ixy|, |iyx|, |iyy| <= 2^10 (texels a
+ *             pixel) and |ixx|*width + |ixy|*height + |ix0| + 1 < 2^29, likewise the second row (doubles, in this order).
+ *             Then |A x + B y + E + ((A + B) >> 1) - 2^31| < 2^61 + 2^33 for every pixel 0 <= x < width, 0 <= y < height
+ *             -- the sum of the magnitudes is below 2^29 texels = 2^61, each rint moves a term by at most x/2, y/2 or 1/2
+ *             units with x, y < 2^23 (width * height <= 2^26 and both >= 10) -- so U and V fit an int64 with room and
+ *             x1, y1 fit an int32.
+ *  Sample     pixel (x, y): U = A*x + B*y + E + ((A + B) >> 1) - 2^31 (arithmetic shifts; the pixel's centre in texel
+ *             centres), V likewise from C, D, G.  x1 = U >> 32, dx = ((U >> 25) & 127) << 1, y1 and dy likewise (pixman's
+ *             seven-bit weights).  w_br = dx*dy, w_tr = (dx << 8) - w_br, w_bl = (dy << 8) - w_br,
+ *             w_tl = 65536 - (dx << 8) - (dy << 8) + w_br; tl, tr, bl, br = the texels at (x1, y1), (x1 + 1, y1),
+ *             (x1, y1 + 1), (x1 + 1, y1 + 1); each of the four channels is (tl*w_tl + tr*w_tr + bl*w_bl + br*w_br) >> 16.
+ *  Composite  the map starts as 0xFF800000; slices are painted in the order given; per channel
+ *             d = min(255, s + MUL8(d, 255 - s_alpha)), MUL8(a, b): t = a*b + 128; ((t >> 8) + t) >> 8.  The saturation
+ *             matters: the texel is not premultiplied, intensity can exceed alpha.
+ *  Grid       occupancy row r is image row height - 1 - r; value = -1 if the green byte is 0, else table[red] with
+ *             table[c] = lround((1. - c / 255.) * 100.) in double (dliom_submap_occupancy_table).
+ *             origin_xy[0] = -double(origin[0]) * resolution; origin_xy[1] = double(float(-height) + origin[1]) *
+ *             resolution: the sum in float, as C++ evaluates the reference's int + float.
+ *
+ * Sizes: pixels / data == NULL is a size query (DLIOM_OK, sizes and origin filled); capacity counts pixels (cells); a
+ * buffer smaller than the map fills the sizes and returns DLIOM_ERR_CAPACITY; more than DLIOM_XRAY_MAX_PIXELS pixels fills
+ * the sizes and returns DLIOM_ERR_CAPACITY whatever the buffer.  DLIOM_ERR_INVALID_ARGUMENT: no slices, a NULL pointer,
+ * a resolution or pose entry that is not finite, a resolution <= 0, a negative slice size, slices of another context.
+ * DLIOM_ERR_TOO_LARGE: the bound above, a corner that is not finite as float, a size beyond int32, a slice of more than
+ * DLIOM_XRAY_MAX_PIXELS texels, more than DLIOM_SUBMAP_PAINTER_MAX_SLICES slices or more than
+ * DLIOM_SUBMAP_PAINTER_MAX_PAIRS (tile, slice) pairs in one paint. */
+#define DLIOM_SUBMAP_PAINTER_TILE 16                       /* the paint kernel's workgroup covers 16 x 16 pixels */
+#define DLIOM_SUBMAP_PAINTER_MAX_PAIRS (INT64_C(1) << 30)  /* 4 bytes each in the tile lists */
+#define DLIOM_SUBMAP_PAINTER_MAX_SLICES (1 << 24)
+typedef struct dliom_submap_slice dliom_submap_slice;
+typedef struct dliom_submap_slice_description {
+  int32_t width, height; /* texels */
+  double resolution;     /* metres a texel */
+  double slice_pose7[7]; /* SubmapSlice::slice_pose */
+  double pose7[7];       /* SubmapSlice::pose, the submap's global pose */
+} dliom_submap_slice_description;
+typedef struct dliom_submap_painter_stats {
+  int64_t launches;         /* kernel launches of the context's last paint: the same whatever the number of slices */
+  int64_t texels_uploaded;  /* host -> device texels of dliom_submap_slice_create since the context was created */
+  int64_t tile_slice_pairs; /* (tile, slice) pairs the last paint's lists held */
+} dliom_submap_painter_stats;
+/* Uploads height * width (intensity, alpha) byte pairs once; they stay in HBM until the slice is destroyed.  cells may be
+ * NULL when width * height == 0. */
+int dliom_submap_slice_create(dliom_ctx* ctx, const uint8_t* cells, int32_t width, int32_t height, double resolution,
+                              const double slice_pose7[7], const double pose7[7], dliom_submap_slice** out);
+/* FillSubmapSlice for a device grid: dliom_grid_xray_texture's kernels, the texture kept on the device (only the
+ * bounding-box read-back that sizes it remains).  pose = global_submap_pose; the slice is on the grid's context. */
+int dliom_submap_slice_create_from_grid(const dliom_grid* grid, const double global_submap_pose7[7], dliom_submap_slice** out);
+/* The slice's new global pose after an optimisation.  Host only: no texture data moves. */
+int dliom_submap_slice_set_pose(dliom_submap_slice* slice, const double pose7[7]);
+int dliom_submap_slice_info(const dliom_submap_slice* slice, dliom_submap_slice_description* out);
+int dliom_submap_slice_destroy(dliom_submap_slice* slice);
+/* Layout and Inverse of the statement on the host, from plain descriptions: no device, no context.  fixed6 (may be NULL):
+ * A, B, E, C, D, G per slice, n * 6 values; written only when the call returns DLIOM_OK. */
+int dliom_submap_slices_layout(const dliom_submap_slice_description* slices, int64_t n, double resolution, int32_t* width,
+                               int32_t* height, float origin2f[2], int64_t* fixed6);
+int dliom_submap_occupancy_table(int8_t table256[256]);
+/* PaintSubmapSlices: pixels = height * width words alpha << 24 | red << 16 | green << 8 | blue, row-major
+ * (CAIRO_FORMAT_ARGB32 on a little-endian host).  Runs on the context's stream and synchronises it.  ctx == NULL stands
+ * for the context the slices were created on (they must all share one). */
+int dliom_submap_slices_paint(dliom_ctx* ctx, const dliom_submap_slice* const* slices, int64_t n, double resolution,
+                              uint32_t* pixels, int64_t capacity, int32_t* width, int32_t* height, float origin2f[2]);
+/* PaintSubmapSlices + CreateOccupancyGridMsg's data and origin: painted and converted on the device, one byte a cell
+ * comes back.  origin2f may be NULL. */
+int dliom_submap_slices_occupancy(dliom_ctx* ctx, const dliom_submap_slice* const* slices, int64_t n, double resolution,
+                                  int8_t* data, int64_t capacity, int32_t* width, int32_t* height, float origin2f[2],
+                                  double origin_xy[2]);
+int dliom_ctx_submap_painter_stats(const dliom_ctx* ctx, dliom_submap_painter_stats* out);
+
 /* Per-context choices a caller may make; none of them changes a result (every kernel variant is parity-tested).  The
  * library never reads the environment (tuning experiments live in `make experiments` builds only). */
 enum {
