@@ -17,6 +17,8 @@
 //   dliom::io::OutlierRemovingPointsProcessor                 io/outlier_removing_points_processor.h:29-82
 //   dliom::mapping::constraints::SubmapFeatureMatcher         mapping/internal/constraints/constraint_builder_3d.cc:459-529
 //   dliom::io::SubmapSlice / FillSubmapSlice / PaintSubmapSlices  io/submap_painter.h:30-94 (+ CreateOccupancyGrid)
+//   dliom::sensor::CompressedPointCloud                       sensor/compressed_point_cloud.h:36-95
+//   dliom::mapping::ToProto / FromProto(TrajectoryNode::Data) mapping/trajectory_node.h:39-69 (+ ToProto over a span of nodes)
 //
 // The value types below are layout-compatible stand-ins for Eigen::Vector3f / transform::Rigid3d
 // so that this header builds without Eigen; inside cartographer the same adapters are
@@ -2911,6 +2913,147 @@ inline OccupancyGrid CreateOccupancyGrid(const std::map<mapping::SubmapId, Subma
 }
 
 }  // namespace io
+
+// ---- sensor::CompressedPointCloud and mapping::ToProto / FromProto(TrajectoryNode::Data) on device clouds
+// (sensor/compressed_point_cloud.h:36-95, mapping/trajectory_node.h:39-69, .cc:27-69; dliom.h "compressed point clouds").
+// Protos travel as their serialized bytes (std::string): inside cartographer, ParseFromString / SerializeAsString on the
+// generated classes are the glue.
+namespace sensor {
+class CompressedPointCloud {
+ public:
+  CompressedPointCloud() {}
+  // Compresses a cloud in HBM (what LocalTrajectoryBuilder3D::matched_clouds hands out)
+  CompressedPointCloud(Context* context, const dliom_cloud* cloud) {
+    int64_t words = 0;
+    int64_t points = 0;
+    Check(dliom_cloud_size(cloud, &points), "dliom_cloud_size");
+    Check(dliom_cloud_compress(context->get(), cloud, nullptr, 0, &words), "CompressedPointCloud: a point beyond the 23-bit range");
+    point_data_.resize(static_cast<size_t>(words));
+    Check(dliom_cloud_compress(context->get(), cloud, point_data_.data(), words, &words), "dliom_cloud_compress");
+    num_points_ = static_cast<int32_t>(points);
+  }
+  CompressedPointCloud(Context* context, const PointCloud& point_cloud)
+      : CompressedPointCloud(context, io::internal::DeviceCloud(context, point_cloud).cloud) {}
+  // CompressedPointCloud(const proto::CompressedPointCloud&), from the serialized message (host only)
+  static CompressedPointCloud FromProto(const std::string& bytes) {
+    CompressedPointCloud c;
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(bytes.data());
+    int64_t words = 0;
+    Check(dliom_compressed_point_cloud_from_proto(b, static_cast<int64_t>(bytes.size()), &c.num_points_, nullptr, 0, &words),
+          "dliom_compressed_point_cloud_from_proto");
+    c.point_data_.resize(static_cast<size_t>(words));
+    Check(dliom_compressed_point_cloud_from_proto(b, static_cast<int64_t>(bytes.size()), &c.num_points_, c.point_data_.data(), words,
+                                                  &words), "dliom_compressed_point_cloud_from_proto");
+    return c;
+  }
+  bool empty() const { return num_points_ == 0; }
+  size_t size() const { return static_cast<size_t>(num_points_); }
+  const std::vector<int32_t>& point_data() const { return point_data_; }
+  bool operator==(const CompressedPointCloud& other) const {
+    return num_points_ == other.num_points_ && point_data_ == other.point_data_;
+  }
+  // Decompress() into HBM: the caller's cloud; a malformed stream fails the CHECK the reference lacks (its TODO)
+  std::shared_ptr<io::internal::DeviceCloud> DecompressOnDevice(Context* context) const {
+    dliom_cloud* cloud = nullptr;
+    Check(dliom_cloud_decompress(context->get(), num_points_, point_data_.data(), static_cast<int64_t>(point_data_.size()), &cloud),
+          "dliom_cloud_decompress");
+    return std::make_shared<io::internal::DeviceCloud>(context, cloud);
+  }
+  PointCloud Decompress(Context* context) const {
+    const std::shared_ptr<io::internal::DeviceCloud> cloud = DecompressOnDevice(context);
+    PointCloud points(size());
+    if (!points.empty()) Check(dliom_cloud_download(cloud->cloud, &points[0].x), "dliom_cloud_download");
+    return points;
+  }
+  // ToProto().SerializeAsString() (host only: frames the words)
+  std::string ToProto() const {
+    int64_t size = 0;
+    const int64_t words = static_cast<int64_t>(point_data_.size());
+    Check(dliom_compressed_point_cloud_to_proto(num_points_, point_data_.data(), words, nullptr, 0, &size),
+          "dliom_compressed_point_cloud_to_proto");
+    std::string bytes(static_cast<size_t>(size), '\0');
+    Check(dliom_compressed_point_cloud_to_proto(num_points_, point_data_.data(), words, reinterpret_cast<uint8_t*>(&bytes[0]), size, &size),
+          "dliom_compressed_point_cloud_to_proto");
+    return bytes;
+  }
+
+ private:
+  int32_t num_points_ = 0;
+  std::vector<int32_t> point_data_;
+};
+}  // namespace sensor
+
+namespace mapping {
+struct TrajectoryNode {
+  // TrajectoryNode::Data with its clouds in HBM (null: the empty cloud); time in ticks of 100 ns (common::ToUniversal)
+  struct Data {
+    int64_t time = 0;
+    transform::Quaterniond gravity_alignment{{1, 0, 0, 0}};
+    std::shared_ptr<io::internal::DeviceCloud> filtered_gravity_aligned_point_cloud;
+    std::shared_ptr<io::internal::DeviceCloud> high_resolution_point_cloud;
+    std::shared_ptr<io::internal::DeviceCloud> low_resolution_point_cloud;
+    std::vector<float> rotational_scan_matcher_histogram;
+    transform::Rigid3d local_pose;
+  };
+};
+
+// mapping::ToProto over a span of nodes, serialized: every cloud of every node is compressed in ONE device batch -- what
+// a SerializeState loop calls instead of a ToProto a node.
+inline std::vector<std::string> ToProto(Context* context, const TrajectoryNode::Data* const* nodes, size_t count) {
+  std::vector<dliom_trajectory_node_data> in(count);
+  for (size_t i = 0; i < count; ++i) {
+    const TrajectoryNode::Data& d = *nodes[i];
+    dliom_trajectory_node_data& n = in[i];
+    n.timestamp = d.time;
+    std::memcpy(n.gravity_alignment_wxyz, d.gravity_alignment.wxyz, sizeof n.gravity_alignment_wxyz);
+    n.filtered_gravity_aligned = d.filtered_gravity_aligned_point_cloud ? d.filtered_gravity_aligned_point_cloud->cloud : nullptr;
+    n.high_resolution = d.high_resolution_point_cloud ? d.high_resolution_point_cloud->cloud : nullptr;
+    n.low_resolution = d.low_resolution_point_cloud ? d.low_resolution_point_cloud->cloud : nullptr;
+    n.histogram = d.rotational_scan_matcher_histogram.data();
+    n.histogram_size = static_cast<int>(d.rotational_scan_matcher_histogram.size());
+    const std::array<double, 7> pose = d.local_pose.ToArray();
+    std::memcpy(n.local_pose7, pose.data(), sizeof n.local_pose7);
+  }
+  std::vector<int64_t> offsets(count + 1, 0);
+  int refused = -1;
+  Check(dliom_trajectory_nodes_data_to_proto(context->get(), in.data(), static_cast<int>(count), nullptr, 0, offsets.data(), &refused),
+        "mapping::ToProto(TrajectoryNode::Data): a point beyond the 23-bit range");
+  std::vector<uint8_t> bytes(static_cast<size_t>(offsets[count]) + 1);
+  Check(dliom_trajectory_nodes_data_to_proto(context->get(), in.data(), static_cast<int>(count), bytes.data(), offsets[count],
+                                             offsets.data(), &refused), "dliom_trajectory_nodes_data_to_proto");
+  std::vector<std::string> protos(count);
+  for (size_t i = 0; i < count; ++i) protos[i].assign(reinterpret_cast<const char*>(bytes.data()) + offsets[i], static_cast<size_t>(offsets[i + 1] - offsets[i]));
+  return protos;
+}
+inline std::string ToProto(Context* context, const TrajectoryNode::Data& constant_data) {
+  const TrajectoryNode::Data* node = &constant_data;
+  return ToProto(context, &node, 1)[0];
+}
+inline TrajectoryNode::Data FromProto(Context* context, const std::string& proto) {
+  TrajectoryNode::Data d;
+  dliom_cloud* clouds[3] = {nullptr, nullptr, nullptr};
+  double gravity[4], pose[7];
+  int histogram_size = 0;
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(proto.data());
+  const int64_t size = static_cast<int64_t>(proto.size());
+  d.rotational_scan_matcher_histogram.resize(256);
+  int status = dliom_trajectory_node_data_from_proto(context->get(), b, size, &d.time, gravity, &clouds[0], &clouds[1], &clouds[2],
+                                                     d.rotational_scan_matcher_histogram.data(), 256, &histogram_size, pose);
+  if (status == DLIOM_ERR_CAPACITY) {
+    d.rotational_scan_matcher_histogram.resize(static_cast<size_t>(histogram_size));
+    status = dliom_trajectory_node_data_from_proto(context->get(), b, size, &d.time, gravity, &clouds[0], &clouds[1], &clouds[2],
+                                                   d.rotational_scan_matcher_histogram.data(), histogram_size, &histogram_size, pose);
+  }
+  Check(status, "dliom_trajectory_node_data_from_proto");
+  d.rotational_scan_matcher_histogram.resize(static_cast<size_t>(histogram_size));
+  d.gravity_alignment = transform::Quaterniond{{gravity[0], gravity[1], gravity[2], gravity[3]}};
+  d.filtered_gravity_aligned_point_cloud = std::make_shared<io::internal::DeviceCloud>(context, clouds[0]);
+  d.high_resolution_point_cloud = std::make_shared<io::internal::DeviceCloud>(context, clouds[1]);
+  d.low_resolution_point_cloud = std::make_shared<io::internal::DeviceCloud>(context, clouds[2]);
+  d.local_pose = transform::Rigid3d::FromArray(pose);
+  return d;
+}
+}  // namespace mapping
 }  // namespace dliom
 
 #endif  // DLIOM_CPP_DLIOM_CARTOGRAPHER_H_

@@ -798,6 +798,8 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
   ctx->surf.release();
   ctx->surf_out.release();
   ctx->painter.release();
+  ctx->compress.release();
+  ctx->compress_out.release();
   ctx->outlier.release();
   if (ctx->batch_pinned != nullptr) (void)hipHostFree(ctx->batch_pinned);
   ctx->aux_scratch.release();
@@ -844,7 +846,8 @@ int dliom_ctx_memory_stats(const dliom_ctx* ctx, dliom_memory_stats* out) {
   const dliom::DevBuf* bufs[] = {&ctx->points, &ctx->cand, &ctx->sums, &ctx->bounds, &ctx->rescore, &ctx->partials, &ctx->misc,
                                  &ctx->sort_tmp, &ctx->voxel, &ctx->box_tables, &ctx->box_counters, &ctx->box_extents,
                                  &ctx->csm_arrivals, &ctx->box_error, &ctx->deskew_flags, &ctx->zero_words, &ctx->aux_scratch,
-                                 &ctx->xray_leaves, &ctx->xray_cells, &ctx->outlier, &ctx->surf, &ctx->surf_out, &ctx->painter};
+                                 &ctx->xray_leaves, &ctx->xray_cells, &ctx->outlier, &ctx->surf, &ctx->surf_out, &ctx->painter,
+                                 &ctx->compress, &ctx->compress_out};
   for (const dliom::DevBuf* b : bufs) out->scratch_bytes += static_cast<int64_t>(b->cap);
   return DLIOM_OK;
 }

@@ -16,35 +16,14 @@
 
 #include "../../include/dliom.h"
 #include "probability_values.h"
+#include "proto_wire.h"
+
+using namespace dliom::wire;
 
 namespace {
 
-void put_varint(std::vector<uint8_t>* out, uint64_t v) {
-  while (v >= 0x80) {
-    out->push_back(static_cast<uint8_t>(v) | 0x80);
-    v >>= 7;
-  }
-  out->push_back(static_cast<uint8_t>(v));
-}
 inline uint32_t zigzag(int32_t n) { return (static_cast<uint32_t>(n) << 1) ^ static_cast<uint32_t>(n >> 31); }
 inline int32_t unzigzag(uint32_t n) { return static_cast<int32_t>((n >> 1) ^ (~(n & 1) + 1)); }
-
-void put_packed(std::vector<uint8_t>* out, int field, const std::vector<uint8_t>& payload) {
-  if (payload.empty()) return;  // proto3: empty repeated fields are not emitted
-  put_varint(out, static_cast<uint64_t>(field) << 3 | 2);
-  put_varint(out, payload.size());
-  out->insert(out->end(), payload.begin(), payload.end());
-}
-
-bool get_varint(const uint8_t*& p, const uint8_t* end, uint64_t* v) {
-  *v = 0;
-  for (int shift = 0; shift < 64 && p < end; shift += 7) {
-    const uint8_t b = *p++;
-    *v |= static_cast<uint64_t>(b & 0x7F) << shift;
-    if ((b & 0x80) == 0) return true;
-  }
-  return false;
-}
 
 // probability_values.h: the round trip the proto constructor applies to every value, SetProbability(index,
 // ValueToProbability(uint16(value))).  The probability comes out of the table, so it is never a NaN, whatever the bytes.
@@ -188,69 +167,14 @@ extern "C" int dliom_grid_from_proto(dliom_ctx* ctx, const uint8_t* buffer, int6
 
 
 // ---- mapping::proto::Submap3D around two serialized grids (mapping/proto/submap.proto, transform/proto/transform.proto)
-namespace {
-void put_double_field(std::vector<uint8_t>* out, int field, double v) {
-  if (v == 0.0) return;  // proto3 implicit presence, as the C++ runtime decides it (x != 0)
-  put_varint(out, static_cast<uint64_t>(field) << 3 | 1);
-  uint64_t bits;
-  std::memcpy(&bits, &v, 8);
-  for (int i = 0; i < 8; ++i) out->push_back(static_cast<uint8_t>(bits >> (8 * i)));
-}
-void put_message(std::vector<uint8_t>* out, int field, const std::vector<uint8_t>& payload) {
-  put_varint(out, static_cast<uint64_t>(field) << 3 | 2);  // a present sub-message is emitted even when empty
-  put_varint(out, payload.size());
-  out->insert(out->end(), payload.begin(), payload.end());
-}
-void put_bytes(std::vector<uint8_t>* out, int field, const uint8_t* p, int64_t n) {
-  put_varint(out, static_cast<uint64_t>(field) << 3 | 2);
-  put_varint(out, static_cast<uint64_t>(n));
-  out->insert(out->end(), p, p + n);
-}
-bool skip_field(const uint8_t*& p, const uint8_t* end, unsigned wire) {
-  uint64_t v;
-  switch (wire) {
-    case 0: return get_varint(p, end, &v);
-    case 1: if (end - p < 8) return false; p += 8; return true;
-    case 2: if (!get_varint(p, end, &v) || static_cast<uint64_t>(end - p) < v) return false; p += v; return true;
-    case 5: if (end - p < 4) return false; p += 4; return true;
-    default: return false;
-  }
-}
-// doubles of a Vector3d / Quaterniond message into dst[field - 1]
-bool parse_doubles(const uint8_t* p, const uint8_t* end, double* dst, int max_field) {
-  while (p < end) {
-    uint64_t tag;
-    if (!get_varint(p, end, &tag)) return false;
-    const unsigned wire = static_cast<unsigned>(tag & 7), field = static_cast<unsigned>(tag >> 3);
-    if (wire == 1 && field >= 1 && field <= static_cast<unsigned>(max_field)) {
-      if (end - p < 8) return false;
-      uint64_t bits = 0;
-      for (int i = 0; i < 8; ++i) bits |= static_cast<uint64_t>(p[i]) << (8 * i);
-      std::memcpy(&dst[field - 1], &bits, 8);
-      p += 8;
-    } else if (!skip_field(p, end, wire)) {
-      return false;
-    }
-  }
-  return true;
-}
-}  // namespace
-
 extern "C" int dliom_submap3d_to_proto(const double local_pose7[7], int32_t num_range_data, int finished,
                                        const uint8_t* hi, int64_t hi_size, const uint8_t* lo, int64_t lo_size,
                                        int wrap_in_submap, uint8_t* buffer, int64_t capacity, int64_t* size) {
   if (local_pose7 == nullptr || size == nullptr || capacity < 0 || (hi != nullptr && hi_size < 0) ||
       (lo != nullptr && lo_size < 0))
     return DLIOM_ERR_INVALID_ARGUMENT;
-  std::vector<uint8_t> translation, rotation, pose, msg;
-  for (int i = 0; i < 3; ++i) put_double_field(&translation, i + 1, local_pose7[i]);  // Vector3d x, y, z
-  put_double_field(&rotation, 1, local_pose7[4]);                                      // Quaterniond x, y, z, w
-  put_double_field(&rotation, 2, local_pose7[5]);
-  put_double_field(&rotation, 3, local_pose7[6]);
-  put_double_field(&rotation, 4, local_pose7[3]);
-  put_message(&pose, 1, translation);  // transform::ToProto(Rigid3d) sets both sub-messages
-  put_message(&pose, 2, rotation);
-  put_message(&msg, 1, pose);
+  std::vector<uint8_t> msg;
+  put_rigid3d(&msg, 1, local_pose7);
   if (num_range_data != 0) {
     put_varint(&msg, 2u << 3 | 0);
     put_varint(&msg, static_cast<uint64_t>(static_cast<int64_t>(num_range_data)));  // int32: sign-extended to 64 bits
@@ -319,20 +243,7 @@ extern "C" int dliom_submap3d_from_proto(const uint8_t* buffer, int64_t size, in
         *lo_offset = p - buffer;
         *lo_size = static_cast<int64_t>(len);
       } else {  // Rigid3d: 1 translation, 2 rotation
-        const uint8_t* r = p;
-        const uint8_t* rend = p + len;
-        while (r < rend) {
-          uint64_t rtag, rlen;
-          if (!get_varint(r, rend, &rtag)) return DLIOM_ERR_INVALID_ARGUMENT;
-          if ((rtag & 7) == 2 && ((rtag >> 3) == 1 || (rtag >> 3) == 2)) {
-            if (!get_varint(r, rend, &rlen) || static_cast<uint64_t>(rend - r) < rlen) return DLIOM_ERR_INVALID_ARGUMENT;
-            const bool ok = (rtag >> 3) == 1 ? parse_doubles(r, r + rlen, t, 3) : parse_doubles(r, r + rlen, q, 4);
-            if (!ok) return DLIOM_ERR_INVALID_ARGUMENT;
-            r += rlen;
-          } else if (!skip_field(r, rend, static_cast<unsigned>(rtag & 7))) {
-            return DLIOM_ERR_INVALID_ARGUMENT;
-          }
-        }
+        if (!parse_rigid3d(p, p + len, t, q)) return DLIOM_ERR_INVALID_ARGUMENT;
       }
       p += len;
     } else if (wire == 0 && (field == 2 || field == 3)) {

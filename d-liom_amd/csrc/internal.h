@@ -137,6 +137,9 @@ struct dliom_ctx {
   // the submap painter (submap_painter.hip): slice records, tile lists and the painted map of one paint
   dliom::DevBuf painter;
   int64_t painter_launches = 0, painter_pairs = 0, painter_texels_uploaded = 0;  // dliom_ctx_submap_painter_stats
+  // the node clouds' compression (compressed_cloud.hip): keys, sort buffers, scans and the word streams of one batch; the
+  // varint bytes of its field-3 payloads, sized by the byte count the batch's read-back brought
+  dliom::DevBuf compress, compress_out;
   bool surf_tables_ready = false;  // `surf` holds the Gaussian tables: cleared whenever reserve() made a new allocation
   // the export stages (compact.hip): keep flags, their scan and the survivors' indices; the voxel list of a table dump
   dliom::DevBuf outlier;

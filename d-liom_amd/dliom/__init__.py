@@ -1697,6 +1697,204 @@ def submap3d_from_proto(data, wrapped=False):
     return pose, n.value, bool(fin.value), hi, low
 
 
+# ---- compressed point clouds and trajectory node data (dliom.h "compressed point clouds") ----
+_u8p = C.POINTER(C.c_uint8)
+
+
+class TrajectoryNodeData(C.Structure):
+    _fields_ = [("timestamp", C.c_int64), ("gravity_alignment_wxyz", C.c_double * 4), ("filtered_gravity_aligned", _vp),
+                ("high_resolution", _vp), ("low_resolution", _vp), ("histogram", _f32p), ("histogram_size", C.c_int),
+                ("local_pose7", C.c_double * 7)]
+
+
+SYMBOLS += [
+    ("dliom_trajectory_nodes_data_to_proto", C.c_int, [_vp, C.POINTER(TrajectoryNodeData), C.c_int, _u8p, C.c_int64, _i64p,
+                                                       C.POINTER(C.c_int)]),
+    ("dliom_clouds_compress", C.c_int, [_vp, C.POINTER(_vp), C.c_int, _i32p, C.c_int64, _i64p, C.POINTER(C.c_int)]),
+    ("dliom_cloud_compress", C.c_int, [_vp, _vp, _i32p, C.c_int64, _i64p]),
+    ("dliom_clouds_compress_to_proto", C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u8p, C.c_int64, _i64p, C.POINTER(C.c_int)]),
+    ("dliom_cloud_decompress", C.c_int, [_vp, C.c_int32, _i32p, C.c_int64, C.POINTER(_vp)]),
+    ("dliom_cloud_from_compressed_proto", C.c_int, [_vp, _u8p, C.c_int64, C.POINTER(_vp)]),
+    ("dliom_compressed_point_cloud_to_proto", C.c_int, [C.c_int32, _i32p, C.c_int64, _u8p, C.c_int64, _i64p]),
+    ("dliom_compressed_point_cloud_from_proto", C.c_int, [_u8p, C.c_int64, C.POINTER(C.c_int32), _i32p, C.c_int64, _i64p]),
+    ("dliom_compressed_point_cloud_check", C.c_int, [C.c_int32, _i32p, C.c_int64]),
+    ("dliom_trajectory_node_data_to_proto", C.c_int, [_vp, C.c_int64, _f64p, _vp, _vp, _vp, _f32p, C.c_int, _f64p, _u8p,
+                                                      C.c_int64, _i64p]),
+    ("dliom_trajectory_node_data_from_proto", C.c_int, [_vp, _u8p, C.c_int64, _i64p, _f64p, C.POINTER(_vp), C.POINTER(_vp),
+                                                        C.POINTER(_vp), _f32p, C.c_int, C.POINTER(C.c_int), _f64p]),
+]
+
+
+class CloudRefused(DliomError):
+    """A batch refused by Compress's bound check: first_refused is the lowest offending cloud's index."""
+
+    def __init__(self, status, where, first_refused):
+        super().__init__(status, where)
+        self.first_refused = first_refused
+
+
+def _bytes_in(data):
+    return (C.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) if len(data) else b"\0")
+
+
+def _cloud_handles(clouds):
+    return (_vp * max(len(clouds), 1))(*[None if c is None else c.h for c in clouds])
+
+
+def _compress_call(fn, name, ctx, clouds, dtype):
+    """Query-then-fill of a batched compression -> (flat output, offsets[k + 1])."""
+    k, handles = len(clouds), _cloud_handles(clouds)
+    offsets, refused = np.zeros(k + 1, dtype=np.int64), C.c_int(-1)
+
+    def call(out, capacity):
+        s = fn(ctx.h, handles, k, out, capacity, _p(offsets, _i64p), C.byref(refused))
+        if s == ERR_GRID_EXTENT and refused.value >= 0:
+            raise CloudRefused(s, name, refused.value)
+        _check(s, name)
+    call(None, 0)
+    out = np.zeros(max(int(offsets[k]), 1), dtype=dtype)
+    call(_p(out, C.POINTER(C.c_int32 if dtype == np.int32 else C.c_uint8)), int(offsets[k]))
+    return out[:int(offsets[k])], offsets
+
+
+def compress_point_clouds(ctx, clouds):
+    """sensor::CompressedPointCloud(cloud) for every PointCloud of the list (None: the empty cloud), one batch on the
+    device -> [(num_points, int32 point_data)]."""
+    out, off = _compress_call(ctx._L.dliom_clouds_compress, "dliom_clouds_compress", ctx, clouds, np.int32)
+    return [(0 if c is None else len(c), out[off[i]:off[i + 1]].copy()) for i, c in enumerate(clouds)]
+
+
+def compress_point_clouds_to_proto(ctx, clouds):
+    """The serialized sensor::proto::CompressedPointCloud of every cloud of the list, one batch -> [bytes]."""
+    out, off = _compress_call(ctx._L.dliom_clouds_compress_to_proto, "dliom_clouds_compress_to_proto", ctx, clouds, np.uint8)
+    return [out[off[i]:off[i + 1]].tobytes() for i in range(len(clouds))]
+
+
+def compress_point_cloud(ctx, cloud):
+    """(num_points, int32 point_data) of one PointCloud: the batch of one (dliom_cloud_compress)."""
+    n = C.c_int64()
+    try:
+        _check(ctx._L.dliom_cloud_compress(ctx.h, cloud.h, None, 0, C.byref(n)), "dliom_cloud_compress")
+    except DliomError as e:
+        if e.status == ERR_GRID_EXTENT:
+            raise CloudRefused(e.status, "dliom_cloud_compress", 0)
+        raise
+    out = np.zeros(max(n.value, 1), dtype=np.int32)
+    _check(ctx._L.dliom_cloud_compress(ctx.h, cloud.h, _p(out, _i32p), n.value, C.byref(n)), "dliom_cloud_compress")
+    return len(cloud), out[:n.value]
+
+
+def _words(point_data):
+    return np.ascontiguousarray(point_data, dtype=np.int32).reshape(-1)
+
+
+def decompress_point_cloud(ctx, num_points, point_data):
+    """CompressedPointCloud::Decompress on the device -> PointCloud; a malformed stream is refused."""
+    w, h = _words(point_data), _vp()
+    _check(ctx._L.dliom_cloud_decompress(ctx.h, int(num_points), _p(w, _i32p), len(w), C.byref(h)), "dliom_cloud_decompress")
+    return PointCloud(ctx, _handle=h)
+
+
+def point_cloud_from_compressed_proto(ctx, data):
+    """A serialized sensor::proto::CompressedPointCloud -> PointCloud on the device."""
+    h = _vp()
+    _check(ctx._L.dliom_cloud_from_compressed_proto(ctx.h, _bytes_in(data), len(data), C.byref(h)),
+           "dliom_cloud_from_compressed_proto")
+    return PointCloud(ctx, _handle=h)
+
+
+def compressed_point_cloud_to_proto(num_points, point_data):
+    """Serialized sensor::proto::CompressedPointCloud around words the caller holds (host only)."""
+    L, w, n = load_library(), _words(point_data), C.c_int64()
+    args = (int(num_points), _p(w, _i32p), len(w))
+    _check(L.dliom_compressed_point_cloud_to_proto(*args, None, 0, C.byref(n)), "dliom_compressed_point_cloud_to_proto")
+    out = (C.c_uint8 * max(n.value, 1))()
+    _check(L.dliom_compressed_point_cloud_to_proto(*args, out, n.value, C.byref(n)), "dliom_compressed_point_cloud_to_proto")
+    return bytes(out[:n.value])
+
+
+def compressed_point_cloud_from_proto(data):
+    """(num_points, int32 point_data) of a serialized sensor::proto::CompressedPointCloud (host only, not validated)."""
+    L, b, n, num = load_library(), _bytes_in(data), C.c_int64(), C.c_int32()
+    _check(L.dliom_compressed_point_cloud_from_proto(b, len(data), C.byref(num), None, 0, C.byref(n)),
+           "dliom_compressed_point_cloud_from_proto")
+    out = np.zeros(max(n.value, 1), dtype=np.int32)
+    _check(L.dliom_compressed_point_cloud_from_proto(b, len(data), C.byref(num), _p(out, _i32p), n.value, C.byref(n)),
+           "dliom_compressed_point_cloud_from_proto")
+    return num.value, out[:n.value]
+
+
+def compressed_point_cloud_check(num_points, point_data):
+    """True for a stream Decompress accepts (host only): counts > 0 that sum to num_points, no truncation, no trailing
+    words, every point word in [0, 2^30)."""
+    w = _words(point_data)
+    s = load_library().dliom_compressed_point_cloud_check(int(num_points), _p(w, _i32p), len(w))
+    if s not in (OK, ERR_INVALID_ARGUMENT):
+        _check(s, "dliom_compressed_point_cloud_check")
+    return s == OK
+
+
+def trajectory_nodes_data_to_proto(ctx, nodes):
+    """The serialized mapping::proto::TrajectoryNodeData of every node of the list -- dicts with timestamp,
+    gravity_alignment (w, x, y, z), filtered_gravity_aligned, high_resolution, low_resolution (PointClouds on `ctx` or
+    None: empty), histogram, local_pose -- all clouds compressed as one batch -> [bytes]."""
+    count = len(nodes)
+    structs, keep = (TrajectoryNodeData * max(count, 1))(), []
+    for s, node in zip(structs, nodes):
+        hist = _f32(node["histogram"]).reshape(-1)
+        keep.append(hist)
+        s.timestamp = int(node["timestamp"])
+        s.gravity_alignment_wxyz[:] = [float(v) for v in node["gravity_alignment"]]
+        for name in ("filtered_gravity_aligned", "high_resolution", "low_resolution"):
+            setattr(s, name, None if node.get(name) is None else node[name].h)
+        s.histogram, s.histogram_size = _p(hist, _f32p), len(hist)
+        s.local_pose7[:] = list(_pose7(node["local_pose"]))
+    offsets, refused = np.zeros(count + 1, dtype=np.int64), C.c_int(-1)
+    where = "dliom_trajectory_nodes_data_to_proto"
+
+    def call(out, capacity):
+        st = ctx._L.dliom_trajectory_nodes_data_to_proto(ctx.h, structs, count, out, capacity, _p(offsets, _i64p), C.byref(refused))
+        if st == ERR_GRID_EXTENT and refused.value >= 0:
+            raise CloudRefused(st, where, refused.value)
+        _check(st, where)
+    call(None, 0)
+    out = (C.c_uint8 * max(int(offsets[count]), 1))()
+    call(out, int(offsets[count]))
+    blob = bytes(out)
+    return [blob[offsets[i]:offsets[i + 1]] for i in range(count)]
+
+
+def trajectory_node_data_to_proto(ctx, timestamp, gravity_alignment_wxyz, filtered_gravity_aligned, high_resolution,
+                                  low_resolution, histogram, local_pose7):
+    """Serialized mapping::proto::TrajectoryNodeData (mapping::ToProto(TrajectoryNode::Data)); the clouds are PointClouds
+    on `ctx` or None (empty), compressed as one batch."""
+    g, pose, hist = _f64(gravity_alignment_wxyz), _pose7(local_pose7), _f32(histogram).reshape(-1)
+    h = [None if c is None else c.h for c in (filtered_gravity_aligned, high_resolution, low_resolution)]
+    n = C.c_int64()
+    args = (ctx.h, int(timestamp), _p(g, _f64p), h[0], h[1], h[2], _p(hist, _f32p), len(hist), _p(pose, _f64p))
+    where = "dliom_trajectory_node_data_to_proto"
+    _check(ctx._L.dliom_trajectory_node_data_to_proto(*args, None, 0, C.byref(n)), where)
+    out = (C.c_uint8 * max(n.value, 1))()
+    _check(ctx._L.dliom_trajectory_node_data_to_proto(*args, out, n.value, C.byref(n)), where)
+    return bytes(out[:n.value])
+
+
+def trajectory_node_data_from_proto(ctx, data, histogram_capacity=1024):
+    """mapping::FromProto(TrajectoryNodeData) -> dict(timestamp, gravity_alignment (w, x, y, z), filtered_gravity_aligned,
+    high_resolution, low_resolution (PointClouds on the device), histogram, local_pose (x, y, z, qw, qx, qy, qz))."""
+    g, pose, hist = np.zeros(4), np.zeros(7), np.zeros(max(histogram_capacity, 1), dtype=np.float32)
+    t, hn, h = C.c_int64(), C.c_int(), [_vp(), _vp(), _vp()]
+    s = ctx._L.dliom_trajectory_node_data_from_proto(ctx.h, _bytes_in(data), len(data), C.byref(t), _p(g, _f64p), C.byref(h[0]),
+                                                     C.byref(h[1]), C.byref(h[2]), _p(hist, _f32p), histogram_capacity,
+                                                     C.byref(hn), _p(pose, _f64p))
+    if s == ERR_CAPACITY and hn.value > histogram_capacity:
+        return trajectory_node_data_from_proto(ctx, data, hn.value)
+    _check(s, "dliom_trajectory_node_data_from_proto")
+    clouds = [PointCloud(ctx, _handle=x) for x in h]
+    return dict(timestamp=t.value, gravity_alignment=g, filtered_gravity_aligned=clouds[0], high_resolution=clouds[1],
+                low_resolution=clouds[2], histogram=hist[:hn.value].copy(), local_pose=pose)
+
+
 XRAY_MAX_PIXELS = 1 << 26  # DLIOM_XRAY_MAX_PIXELS
 
 

@@ -145,6 +145,95 @@ int dliom_submap3d_to_proto(const double local_pose7[7], int32_t num_range_data,
 int dliom_submap3d_from_proto(const uint8_t* buffer, int64_t size, int wrapped_in_submap, double local_pose7[7],
                               int32_t* num_range_data, int* finished, int64_t* high_offset, int64_t* high_size,
                               int64_t* low_offset, int64_t* low_size);
+/* ---- compressed point clouds and trajectory node data (sensor/compressed_point_cloud.cc:99-146, mapping/
+ * trajectory_node.cc:27-69): the other half of a saved pose graph, from the clouds in HBM ----
+ * kPrecision = 0.001f, 10 bits per coordinate inside a block, 23 bits per direction.
+ *
+ * Compress(cloud), N points in input order:
+ *  1 Bound    every coordinate p of every point: |p| / 0.001f < 8388608.f, a float division and a float comparison, so
+ *             NaN and +-inf fail it.  (The reference CHECKs max(|x|, |y|, |z|), :113, and aborts; here the cloud is
+ *             refused, see below.)  The largest float that passes is 8388.607421875, which rounds to 8388607: no
+ *             accepted float reaches 2^23, so Grow()'s CHECK_LE(new_bits, 8) cannot fire for an accepted cloud.
+ *  2 Round    per axis q = lround(p / 0.001f) -- GetCellIndex's float division, then round half away from zero --
+ *             block = q >> 10 (arithmetic: negative q round down, block in [-8192, 8191]) and off = q & 1023.
+ *  3 Blocks   in HybridGridBase's iterator order (hybrid_grid.h:181-231, 306-374).  With X = block_x + 8192 in
+ *             [0, 16384), Y and Z likewise, blocks are ordered lexicographically by the nine fields
+ *               Z >> 6, Y >> 6, X >> 6,   (Z >> 3) & 7, (Y >> 3) & 7, (X >> 3) & 7,   Z & 7, Y & 7, X & 7
+ *             -- 42 bits, z-major at each of the three levels; the order does not depend on how far the DynamicGrid
+ *             had grown, since Grow() shifts every meta cell by the same amount.
+ *  4 Inside   a block the points keep their input order; duplicates stay duplicates.
+ *  5 Stream   point_data, int32: per block in that order `count, block_x, block_y, block_z`, then a word a point,
+ *             (((off_z << 10) + off_y) << 10) + off_x.  B blocks: 4 B + N words, at most 5 N.  num_points = N.  The
+ *             empty cloud has the empty stream.
+ * Decompress(num_points, point_data): ReadNextPoint's walk (:79-97); every coordinate is
+ * float(int32((block << 10) + off)) * 0.001f, one conversion and one float multiply ((block << 10) + off in 32-bit
+ * two's complement).  The reference does not validate (TODO, :153); here DLIOM_ERR_INVALID_ARGUMENT, and nothing read
+ * past the buffer, for: a block count <= 0, a stream that ends inside a header or inside a block, counts that do not
+ * sum to num_points, trailing words, a point word outside [0, 2^30), num_points < 0.
+ *
+ * Wire format (proto3).  sensor::proto::CompressedPointCloud: field 1 num_points, an int32 varint, omitted when 0;
+ * field 3 point_data, packed int32 varints (a negative word is sign-extended to 64 bits: 10 bytes), omitted when empty.
+ * mapping::proto::TrajectoryNodeData: 1 timestamp (int64 varint); 2 gravity_alignment (Quaterniond: x, y, z, w as doubles
+ * 1-4); 3, 4, 5 the filtered gravity-aligned, high and low resolution clouds, each always present as a sub-message, even
+ * when empty; 6 rotational_scan_matcher_histogram (packed float, every element); 7 local_pose (Rigid3d: 1 translation,
+ * 2 rotation, both always present).  Scalars that compare equal to zero are omitted (v == 0.0, so -0.0 is omitted as
+ * well, where the C++ runtime compares bits).  Parsers accept the packed and the unpacked form of a repeated field,
+ * skip unknown fields and take the last occurrence of a sub-message.
+ *
+ * The device path is the batched one (K clouds of one context: keys, a stable sort over the key bits in use, emission,
+ * varint packing); a single cloud is a batch of one.  A NULL cloud is the empty cloud.  Sizes come back in one
+ * read-back a call, not one a cloud.  Query-then-fill as dliom_grid_to_proto: an output pointer of NULL is a size
+ * query (offsets filled); a capacity below offsets[k] fills the offsets and returns DLIOM_ERR_CAPACITY.  5 * the
+ * batch's points words always suffice.  A cloud that fails the bound check refuses the whole call with
+ * DLIOM_ERR_GRID_EXTENT (the blocks are a HybridGridBase): *first_refused is the lowest such cloud's index (-1
+ * otherwise) and neither the data nor the offsets are written.  More than 2^26 points or 2^20 clouds a batch:
+ * DLIOM_ERR_TOO_LARGE.
+ *   clouds_compress           cloud c's stream is point_data[word_offsets[c], word_offsets[c + 1]); capacity in words
+ *   cloud_compress            k = 1: *size words
+ *   clouds_compress_to_proto  K complete CompressedPointCloud messages, cloud c's at bytes[byte_offsets[c], [c + 1])
+ *   cloud_decompress          a device cloud like every other (bounds kept: max_norm and the per-axis maxima)
+ *   compressed_point_cloud_to_proto / _from_proto   host only: frames / parses words the caller holds (*n words;
+ *                             point_data NULL queries *n); from_proto does not validate the stream
+ *   compressed_point_cloud_check     host only: DLIOM_OK for a stream Decompress accepts, else DLIOM_ERR_INVALID_ARGUMENT
+ *   trajectory_nodes_data_to_proto   `count` nodes, all their clouds (NULL: empty) compressed as one batch -- what a
+ *                             SerializeState loop calls; node i's message is bytes[byte_offsets[i], [i + 1]);
+ *                             *first_refused is the node's index; histogram_size >= 0
+ *   trajectory_node_data_to_proto    count = 1: *size bytes
+ *   trajectory_node_data_from_proto  three new device clouds (the caller's to destroy; absent: empty), *histogram_size
+ *                             floats (DLIOM_ERR_CAPACITY with the size if histogram_capacity is too small), poses as
+ *                             (w, x, y, z) and (x, y, z, qw, qx, qy, qz), absent fields zero */
+int dliom_clouds_compress(dliom_ctx* ctx, const dliom_cloud* const* clouds, int k, int32_t* point_data, int64_t capacity,
+                          int64_t* word_offsets, int* first_refused);
+int dliom_cloud_compress(dliom_ctx* ctx, const dliom_cloud* cloud, int32_t* point_data, int64_t capacity, int64_t* size);
+int dliom_clouds_compress_to_proto(dliom_ctx* ctx, const dliom_cloud* const* clouds, int k, uint8_t* bytes, int64_t capacity,
+                                   int64_t* byte_offsets, int* first_refused);
+int dliom_cloud_decompress(dliom_ctx* ctx, int32_t num_points, const int32_t* point_data, int64_t n, dliom_cloud** out);
+int dliom_cloud_from_compressed_proto(dliom_ctx* ctx, const uint8_t* bytes, int64_t size, dliom_cloud** out);
+int dliom_compressed_point_cloud_to_proto(int32_t num_points, const int32_t* point_data, int64_t n, uint8_t* buffer,
+                                          int64_t capacity, int64_t* size);
+int dliom_compressed_point_cloud_from_proto(const uint8_t* bytes, int64_t size, int32_t* num_points, int32_t* point_data,
+                                            int64_t capacity, int64_t* n);
+int dliom_compressed_point_cloud_check(int32_t num_points, const int32_t* point_data, int64_t n);
+typedef struct {
+  int64_t timestamp;                /* common::ToUniversal(time) */
+  double gravity_alignment_wxyz[4];
+  const dliom_cloud* filtered_gravity_aligned; /* each may be NULL: the empty cloud */
+  const dliom_cloud* high_resolution;
+  const dliom_cloud* low_resolution;
+  const float* histogram;           /* rotational_scan_matcher_histogram */
+  int histogram_size;
+  double local_pose7[7];            /* x, y, z, qw, qx, qy, qz */
+} dliom_trajectory_node_data;
+int dliom_trajectory_nodes_data_to_proto(dliom_ctx* ctx, const dliom_trajectory_node_data* nodes, int count, uint8_t* bytes,
+                                         int64_t capacity, int64_t* byte_offsets, int* first_refused);
+int dliom_trajectory_node_data_to_proto(dliom_ctx* ctx, int64_t timestamp, const double gravity_alignment_wxyz[4],
+                                        const dliom_cloud* filtered_gravity_aligned, const dliom_cloud* high_resolution,
+                                        const dliom_cloud* low_resolution, const float* histogram, int histogram_size,
+                                        const double local_pose7[7], uint8_t* buffer, int64_t capacity, int64_t* size);
+int dliom_trajectory_node_data_from_proto(dliom_ctx* ctx, const uint8_t* bytes, int64_t size, int64_t* timestamp,
+                                          double gravity_alignment_wxyz[4], dliom_cloud** filtered_gravity_aligned,
+                                          dliom_cloud** high_resolution, dliom_cloud** low_resolution, float* histogram,
+                                          int histogram_capacity, int* histogram_size, double local_pose7[7]);
 /* ---- X-ray projections of a grid (mapping/3d/submap_3d.cc), computed on the device from the leaf pool ----
  * Both reproduce the reference's float arithmetic byte for byte: the cells with ValueToProbability(v) >= 0.501 in
  * HybridGrid::Iterator order, each cell centre index * resolution transformed in float and rounded with
