@@ -679,6 +679,94 @@ struct TimedPointCloudOriginData {
   std::vector<RangeMeasurement> ranges;
 };
 }  // namespace sensor
+
+// ---- sensor_msgs/PointCloud2, decoded on the device (dliom.h "PointCloud2 messages decoded on the device") ----------------
+// The message as plain data, shaped like the ROS type: a caller with ROS copies nothing but the header fields (data may be
+// moved or swapped in).  Parity of the decoding is unpinned against PCL: dliom.h states it.
+namespace sensor_msgs {
+struct PointField {
+  std::string name;
+  uint32_t offset = 0;
+  uint8_t datatype = 0;  // INT8 = 1 ... FLOAT64 = 8
+  uint32_t count = 1;
+};
+struct PointCloud2 {
+  struct {
+    struct {
+      uint32_t sec = 0, nsec = 0;
+    } stamp;
+    std::string frame_id;
+  } header;
+  uint32_t height = 0, width = 0;
+  std::vector<PointField> fields;
+  bool is_bigendian = false;
+  uint32_t point_step = 0, row_step = 0;
+  std::vector<uint8_t> data;
+};
+}  // namespace sensor_msgs
+namespace sensor {
+// A decoded message in HBM: packed (x, y, z, t) and, from the export modes, one intensity a point.
+class TimedCloudOnDevice {
+ public:
+  // mode: DLIOM_POINT_CLOUD2_*; sensor_to_tracking null: the points stay in the sensor frame (the export's way)
+  TimedCloudOnDevice(Context* context, const sensor_msgs::PointCloud2& msg, int mode, const transform::Rigid3d* sensor_to_tracking)
+      : context_(context) {
+    std::vector<dliom_point_field> fields(msg.fields.size());
+    for (size_t k = 0; k < fields.size(); ++k)
+      fields[k] = dliom_point_field{msg.fields[k].name.c_str(), msg.fields[k].offset, msg.fields[k].datatype, msg.fields[k].count};
+    dliom_point_cloud2 m{};
+    m.height = msg.height;
+    m.width = msg.width;
+    m.point_step = msg.point_step;
+    m.row_step = msg.row_step;
+    m.is_bigendian = msg.is_bigendian ? 1u : 0u;
+    m.num_fields = static_cast<int32_t>(fields.size());
+    m.fields = fields.data();
+    m.data = msg.data.data();
+    m.data_size = msg.data.size();
+    m.stamp_sec = msg.header.stamp.sec;
+    m.stamp_nsec = msg.header.stamp.nsec;
+    std::array<double, 7> mount{};
+    if (sensor_to_tracking != nullptr) mount = sensor_to_tracking->ToArray();
+    float origin[3];
+    Check(dliom_point_cloud2_decode(context->get(), &m, mode, sensor_to_tracking != nullptr ? mount.data() : nullptr, &cloud_, &time_,
+                                    origin),
+          "dliom_point_cloud2_decode");
+    origin_ = Vector3f(origin[0], origin[1], origin[2]);
+  }
+  ~TimedCloudOnDevice() { dliom_timed_cloud_destroy(cloud_); }
+  TimedCloudOnDevice(const TimedCloudOnDevice&) = delete;
+  TimedCloudOnDevice& operator=(const TimedCloudOnDevice&) = delete;
+  const dliom_timed_cloud* get() const { return cloud_; }
+  Context* context() const { return context_; }
+  int64_t time() const { return time_; }  // the stamp HandleRangefinder gets: the last point's
+  const Vector3f& origin() const { return origin_; }
+  size_t size() const {
+    int64_t n = 0;
+    Check(dliom_timed_cloud_size(cloud_, &n), "dliom_timed_cloud_size");
+    return static_cast<size_t>(n);
+  }
+  // t of the last kept point, without a download (0 for an empty cloud)
+  float back_time() const {
+    float front = 0.f, back = 0.f;
+    Check(dliom_timed_cloud_front_back_time(cloud_, &front, &back), "dliom_timed_cloud_front_back_time");
+    return back;
+  }
+  // what the general host paths go on with
+  TimedPointCloudData Download() const {
+    TimedPointCloudData data{time_, origin_, TimedPointCloud(size())};
+    static_assert(sizeof(TimedPoint) == 16, "packed x, y, z, t");
+    Check(dliom_timed_cloud_download(cloud_, data.ranges.empty() ? nullptr : &data.ranges[0].x, nullptr), "dliom_timed_cloud_download");
+    return data;
+  }
+
+ private:
+  Context* context_;
+  dliom_timed_cloud* cloud_ = nullptr;
+  int64_t time_ = 0;
+  Vector3f origin_;
+};
+}  // namespace sensor
 namespace mapping {
 
 // Host logic restated from mapping/internal/3d/range_data_synchronizer.cc:29-130: the prior lidar's cloud is passed
@@ -1090,6 +1178,31 @@ class LocalTrajectoryBuilder3D {
     return AddAccumulatedRangeData(sync.time, current_pose, origin_in_tracking, cloud);
   }
 
+  // The single-sensor path above on a message decoded on the device (SensorBridge::HandlePointCloud2Message): the ranges are
+  // in HBM already, in the tracking frame, and stay there; the two checks on them read what the decode brought back.
+  // Several sensors, manual de-skew and accumulation stay on the general host path: they download the cloud and go on as
+  // before (the synchronizer merges and sorts on the host).
+  std::unique_ptr<MatchingResult> AddRangeData(const std::string& sensor_id, const sensor::TimedCloudOnDevice& ranges) {
+    if (!(synchronizer_.SingleSensor(sensor_id) && !options_.enable_manual_descrew && options_.num_accumulated_range_data == 1))
+      return AddRangeData(sensor_id, ranges.Download());
+    if (ranges.size() == 0 || !imu_initialized_ || !have_prediction_) return nullptr;
+    if (ranges.back_time() > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
+    DLIOM_ADAPTER_STAGE(0);
+    double prev[7], vel[3], bias[6], predicted[7], pvel[3];
+    Check(dliom_imu_window_state(window_, 0, prev, vel, bias), "dliom_imu_window_state");
+    Check(dliom_imu_window_predict(window_, predicted, pvel), "dliom_imu_window_predict");
+    accumulation_started_ = std::chrono::steady_clock::now();
+    const float origin[3] = {ranges.origin().x, ranges.origin().y, ranges.origin().z};
+    dliom_cloud* cloud = nullptr;
+    float origin_in_tracking[3], current_pose[7];
+    Check(dliom_add_range_data_timed_cloud(context_->get(), prev, predicted, options_.scan_period, ranges.get(), origin,
+                                           options_.min_range, options_.max_range, options_.voxel_filter_size, &cloud,
+                                           origin_in_tracking, current_pose),
+          "AddRangeData (de-skew, filters, tracking frame)");
+    DLIOM_ADAPTER_STAGE(1);
+    return AddAccumulatedRangeData(ranges.time(), current_pose, origin_in_tracking, cloud);
+  }
+
   const ActiveSubmaps3D& active_submaps() const { return active_submaps_; }
   // local_trajectory_builder_3d.h:113, .cc:624-649: the same five metrics under the same family names, labels and bucket
   // boundaries; they are process-wide like the reference's file-scope statics and observe nothing until this is called
@@ -1281,6 +1394,35 @@ class LocalTrajectoryBuilder3D {
 };
 
 }  // namespace mapping
+
+// ---- cartographer_ros/sensor_bridge.cc:176-240, 286-299: a PointCloud2 message into the local trajectory builder ---------
+// HandlePointCloud2Message's per-point code -- the gather of the sensor's fields, the finite test, the times re-based to
+// the last point, the stamp moved there -- and HandleRangefinder's change into the tracking frame run on the device in one
+// pass over the message's bytes, and the result feeds LocalTrajectoryBuilder3D::AddRangeData without coming back.  tf is the
+// caller's: sensor_to_tracking is what tf_bridge_.LookupToTracking(time, frame_id) returned (a null lookup drops the
+// message before this is called).  LaserScan and MultiEchoLaserScan messages are not handled here.
+class SensorBridge {
+ public:
+  SensorBridge(Context* context, mapping::LocalTrajectoryBuilder3D* trajectory_builder)
+      : context_(context), trajectory_builder_(trajectory_builder) {}
+  // sensor_type: "ouster", "velodyne", "robosense"; anything else is a pcl::PointXYZI cloud without point times
+  static int ModeOf(const std::string& sensor_type) {
+    return sensor_type == "ouster"      ? DLIOM_POINT_CLOUD2_SLAM_OUSTER
+           : sensor_type == "velodyne"  ? DLIOM_POINT_CLOUD2_SLAM_VELODYNE
+           : sensor_type == "robosense" ? DLIOM_POINT_CLOUD2_SLAM_ROBOSENSE
+                                        : DLIOM_POINT_CLOUD2_SLAM_OTHER;
+  }
+  std::unique_ptr<mapping::LocalTrajectoryBuilder3D::MatchingResult> HandlePointCloud2Message(
+      const std::string& sensor_id, const sensor_msgs::PointCloud2& msg, const std::string& sensor_type,
+      const transform::Rigid3d& sensor_to_tracking) {
+    const sensor::TimedCloudOnDevice ranges(context_, msg, ModeOf(sensor_type), &sensor_to_tracking);
+    return trajectory_builder_->AddRangeData(sensor_id, ranges);
+  }
+
+ private:
+  Context* context_;
+  mapping::LocalTrajectoryBuilder3D* trajectory_builder_;
+};
 
 // ---- pose graph optimisation (mapping/internal/optimization/optimization_problem_3d.h) --------------------------------
 namespace mapping {
@@ -2132,6 +2274,31 @@ inline std::unique_ptr<PointsBatch> AssemblePointsBatch(OnDevice, const transfor
   std::unique_ptr<PointsBatch> batch(new PointsBatch);
   batch->start_time = cloud_time;
   batch->frame_id = frame_id;
+  float origin[3];
+  Check(dliom_points_batch_origin(made, origin), "dliom_points_batch_origin");
+  batch->origin = sensor::Vector3f(origin[0], origin[1], origin[2]);
+  batch->device_batch = std::make_shared<internal::DeviceBatch>(context, made, true);
+  return batch;
+}
+
+// HandleMessage (assets_writer.cc:119-160) from the message itself: ToPointCloudWithIntensities, or with rslidar
+// ToPointCloudWithIntensitiesRsLiDAR (msg_conversion.cc:185-226), decoded on the device in the sensor frame and assembled
+// there -- points and intensities are uploaded once, as the message's bytes, and never visit the host.  Null when no point's
+// time lies on the trajectory.
+inline std::unique_ptr<PointsBatch> HandleMessage(const sensor_msgs::PointCloud2& message, bool rslidar,
+                                                  const transform::TransformInterpolationBuffer& buffer,
+                                                  const transform::Rigid3d& sensor_to_tracking, Context* context = nullptr) {
+  if (context == nullptr) context = buffer.context();
+  const sensor::TimedCloudOnDevice decoded(context, message, rslidar ? DLIOM_POINT_CLOUD2_EXPORT_RSLIDAR : DLIOM_POINT_CLOUD2_EXPORT,
+                                           nullptr);
+  const std::array<double, 7> mount = sensor_to_tracking.ToArray();
+  dliom_points_batch* made = nullptr;
+  Check(dliom_points_batch_from_timed_cloud(context->get(), buffer.trajectory(), decoded.time(), decoded.get(), mount.data(), &made),
+        "dliom_points_batch_from_timed_cloud");
+  if (made == nullptr) return nullptr;
+  std::unique_ptr<PointsBatch> batch(new PointsBatch);
+  batch->start_time = decoded.time();
+  batch->frame_id = message.header.frame_id;
   float origin[3];
   Check(dliom_points_batch_origin(made, origin), "dliom_points_batch_origin");
   batch->origin = sensor::Vector3f(origin[0], origin[1], origin[2]);

@@ -444,13 +444,15 @@ int dliom_trajectory_lookup(const dliom_trajectory* t, int64_t time, int* has, d
 
 // intensities (host, n floats, may be null): uploaded once beside the points; the kept ones are gathered by the indices the
 // scatter leaves in scratch into *kept_intensities (an empty block of the caller's; left empty when nothing is kept).
+// device_points: both are in HBM already (internal.h); the points the check records are fetched from there.
 int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt,
-                                       int64_t n, const double sensor_to_tracking[7], dliom_cloud** out, float origin[3],
-                                       int32_t* kept_index, int64_t capacity, int64_t* num_kept, const float* intensities,
-                                       AttrBlock* kept_intensities) {
+                                       const DevicePoints* device_points, int64_t n, const double sensor_to_tracking[7],
+                                       dliom_cloud** out, float origin[3], int32_t* kept_index, int64_t capacity, int64_t* num_kept,
+                                       const float* intensities, AttrBlock* kept_intensities) {
+  const bool on_device = device_points != nullptr;
   if (ctx == nullptr || traj == nullptr || traj->ctx != ctx || sensor_to_tracking == nullptr || out == nullptr || origin == nullptr ||
-      num_kept == nullptr || n < 0 || n > INT32_MAX || capacity < 0 || (n > 0 && points_xyzt == nullptr) ||
-      !pose_is_finite(sensor_to_tracking))
+      num_kept == nullptr || n < 0 || n > INT32_MAX || capacity < 0 || (n > 0 && !on_device && points_xyzt == nullptr) ||
+      (n > 0 && on_device && device_points->xyzt == nullptr) || !pose_is_finite(sensor_to_tracking))
     return DLIOM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   *num_kept = 0;
@@ -468,21 +470,27 @@ int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, i
   if (ctx->tuning[DLIOM_TUNE_RESERVED_TEST_HOOK] >= 4) a.wide = 1;
   if (ctx->tuning[DLIOM_TUNE_RESERVED_TEST_HOOK] == 5) a.perturb = 1;
 #endif
-  // behind the compaction's scratch: words | raw points | x | y | z | intensities
+  // behind the compaction's scratch: words | raw points | x | y | z | intensities (raw points, intensities: host input only)
   const unsigned un = static_cast<unsigned>(n);
-  const size_t per = align256(4 * static_cast<size_t>(n)), raw = align256(16 * static_cast<size_t>(n)), wb = align256(4 * kWords);
+  const size_t per = align256(4 * static_cast<size_t>(n)), raw = on_device ? 0 : align256(16 * static_cast<size_t>(n)),
+               wb = align256(4 * kWords);
   CompactScratch s;
   DLIOM_TRY(carve_compact(ctx, n, &s, wb + raw + 3 * per + (intensities != nullptr ? per : 0), 4 * kHeadWords));
   char* base = static_cast<char*>(s.extra);
   unsigned* words = reinterpret_cast<unsigned*>(base);
-  const float4* d_points = reinterpret_cast<const float4*>(base + wb);
+  const float4* d_points = on_device ? device_points->xyzt : reinterpret_cast<const float4*>(base + wb);
   float* x = reinterpret_cast<float*>(base + wb + raw);
   float* y = reinterpret_cast<float*>(base + wb + raw + per);
   float* z = reinterpret_cast<float*>(base + wb + raw + 2 * per);
-  float* d_intensities = reinterpret_cast<float*>(base + wb + raw + 3 * per);
-  DLIOM_HIP_TRY(hipMemcpyAsync(base + wb, points_xyzt, 16 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-  if (intensities != nullptr)
-    DLIOM_HIP_TRY(hipMemcpyAsync(d_intensities, intensities, 4 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+  const float* d_intensities = on_device ? device_points->intensities : nullptr;
+  if (!on_device) {
+    DLIOM_HIP_TRY(hipMemcpyAsync(base + wb, points_xyzt, 16 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+    if (intensities != nullptr) {
+      float* staged = reinterpret_cast<float*>(base + wb + raw + 3 * per);
+      DLIOM_HIP_TRY(hipMemcpyAsync(staged, intensities, 4 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+      d_intensities = staged;
+    }
+  }
   hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, ctx->stream, a, d_points, un, x, y, z, s.keep, words, s.max_sq, 0);
   DLIOM_HIP_TRY(hipGetLastError());
   DLIOM_TRY(scan_kept(ctx, n, s));
@@ -507,6 +515,14 @@ int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, i
     std::memcpy(h.sq, a.sq, sizeof a.sq);
     h.st_max = a.st_max;
     std::vector<unsigned> fixes;
+    std::vector<float> fetched;  // a decoded message's points, for the recorded ones' times (rare: one more synchronise)
+    if (on_device) {
+      fetched.resize(4 * static_cast<size_t>(n));
+      DLIOM_HIP_TRY(hipMemcpyAsync(fetched.data(), d_points, 16 * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
+      DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+      ++ctx->host_syncs;
+      points_xyzt = fetched.data();
+    }
     if (recorded <= static_cast<unsigned>(kRing)) {
       check_records(h, points_xyzt, n, head.data() + kHeadWords, recorded, &fixes);
       ctx->assemble_recomputed += recorded;
@@ -550,7 +566,7 @@ int dliom::assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, i
   }
   // ---- the cloud: the kept points in input order, and their intensities by the indices the scatter leaves in scratch
   DLIOM_TRY(emit_kept(ctx, x, y, z, n, s, kept, max_sq, out, kept_index));
-  if (intensities != nullptr) {
+  if (d_intensities != nullptr) {
     int st = kept_intensities->alloc(ctx, static_cast<size_t>(kept));
     if (st == DLIOM_OK) st = gather_batch_attributes(ctx, s.index, kept, d_intensities, nullptr, kept_intensities->p, nullptr);
     if (st != DLIOM_OK) {
@@ -569,21 +585,21 @@ extern "C" {
 int dliom_cloud_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt, int64_t n,
                                    const double sensor_to_tracking[7], dliom_cloud** out, float origin[3], int32_t* kept_index,
                                    int64_t capacity, int64_t* num_kept) {
-  return assemble_from_sensor_points(ctx, traj, cloud_time, points_xyzt, n, sensor_to_tracking, out, origin, kept_index, capacity,
-                                     num_kept, nullptr, nullptr);
+  return assemble_from_sensor_points(ctx, traj, cloud_time, points_xyzt, nullptr, n, sensor_to_tracking, out, origin, kept_index,
+                                     capacity, num_kept, nullptr, nullptr);
 }
 
-int dliom_points_batch_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt,
-                                          const float* intensities, int64_t n, const double sensor_to_tracking[7],
-                                          dliom_points_batch** out) {
+// the batch of either input: the points and intensities from the host, or a decoded message's in HBM
+static int batch_from_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt, const float* intensities,
+                             const DevicePoints* device_points, int64_t n, const double sensor_to_tracking[7], dliom_points_batch** out) {
   if (out == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   dliom_cloud* cloud = nullptr;
   float origin[3] = {0.f, 0.f, 0.f};
   int64_t kept = 0;
   AttrBlock kept_intensities;
-  DLIOM_TRY(assemble_from_sensor_points(ctx, traj, cloud_time, points_xyzt, n, sensor_to_tracking, &cloud, origin, nullptr, 0, &kept,
-                                        intensities, &kept_intensities));
+  DLIOM_TRY(assemble_from_sensor_points(ctx, traj, cloud_time, points_xyzt, device_points, n, sensor_to_tracking, &cloud, origin, nullptr,
+                                        0, &kept, intensities, &kept_intensities));
   if (cloud == nullptr) return DLIOM_OK;  // nothing kept: the reference returns nullptr
   dliom_points_batch* b = new dliom_points_batch;
   b->ctx = ctx;
@@ -592,6 +608,22 @@ int dliom_points_batch_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj
   b->intensities = kept_intensities;
   *out = b;
   return DLIOM_OK;
+}
+
+int dliom_points_batch_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt,
+                                          const float* intensities, int64_t n, const double sensor_to_tracking[7],
+                                          dliom_points_batch** out) {
+  return batch_from_points(ctx, traj, cloud_time, points_xyzt, intensities, nullptr, n, sensor_to_tracking, out);
+}
+
+int dliom_points_batch_from_timed_cloud(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const dliom_timed_cloud* points,
+                                        const double sensor_to_tracking[7], dliom_points_batch** out) {
+  if (ctx == nullptr || out == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  DevicePoints d{nullptr, nullptr};
+  int64_t n = 0;
+  DLIOM_TRY(timed_cloud_view(points, ctx, &n, &d.xyzt, &d.intensities, nullptr));
+  return batch_from_points(ctx, traj, cloud_time, nullptr, nullptr, &d, n, sensor_to_tracking, out);
 }
 
 int dliom_assemble_check_stats(const dliom_ctx* ctx, int64_t* recorded, int64_t* recomputed, int64_t* fixed, int64_t* ring_overflows) {

@@ -414,9 +414,19 @@ int gather_batch_attributes(dliom_ctx* ctx, const int* d_index, int64_t kept, co
 int compact_batch(dliom_points_batch* batch, const CompactScratch& s, const unsigned* flag_word, unsigned* flag, int64_t* num_kept);
 // assemble.hip: dliom_cloud_from_sensor_points with the kept points' intensities (host, n floats, may be null) gathered on
 // the device into *kept_intensities (left empty when there are none or nothing is kept)
-int assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt, int64_t n,
-                                const double sensor_to_tracking[7], dliom_cloud** out, float origin[3], int32_t* kept_index,
+// device_points (null: none): the points are in HBM already (a decoded message) -- packed xyzt and one intensity a point
+// (device, may be null); points_xyzt and intensities are null then and nothing is uploaded
+struct DevicePoints {
+  const float4* xyzt;
+  const float* intensities;
+};
+int assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t cloud_time, const float* points_xyzt, const DevicePoints* device_points,
+                                int64_t n, const double sensor_to_tracking[7], dliom_cloud** out, float origin[3], int32_t* kept_index,
                                 int64_t capacity, int64_t* num_kept, const float* intensities, AttrBlock* kept_intensities);
+// point_cloud2.hip: what the consumers take of a decoded message (refused unless it is this context's).  *d_intensities
+// (may be null: not asked for) is null for an object without; *front_t (may be null) the first point's t.
+int timed_cloud_view(const dliom_timed_cloud* cloud, const dliom_ctx* ctx, int64_t* n, const float4** d_xyzt, const float** d_intensities,
+                     float* front_t);
 // sequential_sums.hip: the reference's sequential `score += probability` float sums, bit-identical.
 // Launches the kernels for `count` candidates whose indices are in d_list (c -> translation c / R, rotation c % R):
 // method 0 = one lane replays the loop, 1 = element scan, 2 = chunk scan.  Methods 1 and 2 need the 15-bit values of a

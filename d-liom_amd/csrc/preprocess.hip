@@ -494,9 +494,11 @@ namespace dliom {
 
 // AddRangeData up to the accumulation (:393-472): VoxelFilter(0.5 size) on the timed hits, per-hit de-skew + range
 // gate, the returns compacted in hit order into ctx->misc (x | y | z with stride *stride).  origin_index (one float
-// per range, may be null) and origins (num_origins x 3) are the RangeDataSynchronizer's origin table.
+// per range, may be null) and origins (num_origins x 3) are the RangeDataSynchronizer's origin table.  d_ranges (null: none):
+// the ranges are in HBM already (a decoded message, point_cloud2.hip), ranges_xyzt is null and front_time is the first one's t.
 static int add_range_data_stage_a(dliom_ctx* ctx, const double prev_pose[7], const double predicted_pose[7],
-                                  double scan_period, const float* ranges_xyzt, const float* origin_index, int64_t n,
+                                  double scan_period, const float* ranges_xyzt, const float4* d_ranges, float front_time,
+                                  const float* origin_index, int64_t n,
                                   const float* origins, int num_origins, float min_range, float max_range,
                                   float voxel_filter_size, float current_pose[7], const float** returns,
                                   size_t* stride, int64_t* num_returns) {
@@ -520,15 +522,18 @@ static int add_range_data_stage_a(dliom_ctx* ctx, const double prev_pose[7], con
   unsigned* d_flags = nullptr;  // [last hit's pose | record counter | records]: persistent, read back with the compaction's counts
   DLIOM_TRY(deskew_flag_buffer(ctx, &d_flags));
   const int threads = 256;
-  DLIOM_HIP_TRY(hipMemcpyAsync(base + off_raw, ranges_xyzt, 16 * nn, hipMemcpyHostToDevice, ctx->stream));
+  if (d_ranges == nullptr) {
+    DLIOM_HIP_TRY(hipMemcpyAsync(base + off_raw, ranges_xyzt, 16 * nn, hipMemcpyHostToDevice, ctx->stream));
+    d_ranges = reinterpret_cast<const float4*>(base + off_raw);
+    front_time = ranges_xyzt[3];
+  }
   hipLaunchKernelGGL(split_xyzt_kernel, dim3(static_cast<unsigned>((n + threads - 1) / threads)), dim3(threads), 0,
-                     ctx->stream, reinterpret_cast<const float4*>(base + off_raw), static_cast<int>(n), b, b + nn,
-                     b + 2 * nn, b + 3 * nn);
+                     ctx->stream, d_ranges, static_cast<int>(n), b, b + nn, b + 2 * nn, b + 3 * nn);
   // hits = VoxelFilter(0.5f * voxel_filter_size).Filter(ranges): the time rides along
   const bool multi = origin_index != nullptr && num_origins > 1;
   DeskewArgs a;
   // the first range always survives the filter, so hits.front() is ranges.front()
-  DLIOM_TRY(make_deskew_args(prev_pose, predicted_pose, scan_period, origins, min_range, max_range, ranges_xyzt[3], &a));
+  DLIOM_TRY(make_deskew_args(prev_pose, predicted_pose, scan_period, origins, min_range, max_range, front_time, &a));
   deskew_test_hook(ctx, &a);
   for (int k = 0; k < std::min(num_origins, 4); ++k)
     for (int i = 0; i < 3; ++i) a.origins[k][i] = origins[3 * k + i];
@@ -716,7 +721,32 @@ extern "C" int dliom_add_range_data(dliom_ctx* ctx, const double prev_pose[7], c
   const float* e = nullptr;
   size_t stride = 0;
   int64_t n2 = 0;
-  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, nullptr, n, origin, 1,
+  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, nullptr, 0.f, nullptr, n, origin, 1,
+                                   min_range, max_range, voxel_filter_size, current_pose, &e, &stride, &n2));
+  return add_range_data_stage_b(ctx, e, e + stride, e + 2 * stride, n2, voxel_filter_size, current_pose,
+                                returns_in_tracking, origin_in_tracking);
+}
+
+// dliom_add_range_data on a decoded message (point_cloud2.hip): the same two stages, the upload left out
+extern "C" int dliom_add_range_data_timed_cloud(dliom_ctx* ctx, const double prev_pose[7], const double predicted_pose[7],
+                                                double scan_period, const dliom_timed_cloud* ranges, const float origin[3],
+                                                float min_range, float max_range, float voxel_filter_size,
+                                                dliom_cloud** returns_in_tracking, float origin_in_tracking[3],
+                                                float current_pose[7]) {
+  if (ctx == nullptr || prev_pose == nullptr || predicted_pose == nullptr || origin == nullptr || returns_in_tracking == nullptr ||
+      origin_in_tracking == nullptr || current_pose == nullptr || !(scan_period > 0.) || !(voxel_filter_size > 0.f))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  *returns_in_tracking = nullptr;
+  int64_t n = 0;
+  const float4* d_ranges = nullptr;
+  float front_time = 0.f;
+  DLIOM_TRY(timed_cloud_view(ranges, ctx, &n, &d_ranges, nullptr, &front_time));
+  if (n == 0) return DLIOM_ERR_EMPTY_CLOUD;
+  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  const float* e = nullptr;
+  size_t stride = 0;
+  int64_t n2 = 0;
+  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, nullptr, d_ranges, front_time, nullptr, n, origin, 1,
                                    min_range, max_range, voxel_filter_size, current_pose, &e, &stride, &n2));
   return add_range_data_stage_b(ctx, e, e + stride, e + 2 * stride, n2, voxel_filter_size, current_pose,
                                 returns_in_tracking, origin_in_tracking);
@@ -763,7 +793,7 @@ extern "C" int dliom_range_accumulator_add(dliom_range_accumulator* a, const dou
   const float* e = nullptr;
   size_t stride = 0;
   int64_t n2 = 0;
-  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, origin_index, n, origins,
+  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, nullptr, 0.f, origin_index, n, origins,
                                    num_origins, min_range, max_range, voxel_filter_size, current_pose, &e, &stride, &n2));
   const size_t need = static_cast<size_t>(a->count + n2);
   if (need > a->cap) {  // grow, keeping what is there

@@ -3175,3 +3175,124 @@ def submap_painter_stats(ctx):
     s = SubmapPainterStats()
     _check(ctx._L.dliom_ctx_submap_painter_stats(ctx.h, C.byref(s)), "dliom_ctx_submap_painter_stats")
     return {k: getattr(s, k) for k, _ in SubmapPainterStats._fields_}
+
+
+# ---- PointCloud2 messages decoded on the device (dliom.h "PointCloud2 messages decoded on the device") ----------------
+POINT_FIELD_INT8, POINT_FIELD_UINT8, POINT_FIELD_INT16, POINT_FIELD_UINT16 = 1, 2, 3, 4
+POINT_FIELD_INT32, POINT_FIELD_UINT32, POINT_FIELD_FLOAT32, POINT_FIELD_FLOAT64 = 5, 6, 7, 8
+POINT_CLOUD2_SLAM_OUSTER, POINT_CLOUD2_SLAM_VELODYNE, POINT_CLOUD2_SLAM_ROBOSENSE, POINT_CLOUD2_SLAM_OTHER = 0, 1, 2, 3
+POINT_CLOUD2_EXPORT, POINT_CLOUD2_EXPORT_RSLIDAR = 4, 5
+
+
+class PointField(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint32), ("count", C.c_uint32)]
+
+
+class PointCloud2Struct(C.Structure):
+    _fields_ = [("height", C.c_uint32), ("width", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
+                ("is_bigendian", C.c_uint32), ("num_fields", C.c_int32), ("fields", C.POINTER(PointField)),
+                ("data", C.c_void_p), ("data_size", C.c_uint64), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32)]
+
+
+_pc2p = C.POINTER(PointCloud2Struct)
+SYMBOLS += [
+    ("dliom_point_cloud2_check", C.c_int, [_pc2p, C.c_int, _i64p, _f64p]),
+    ("dliom_point_cloud2_decode", C.c_int, [_vp, _pc2p, C.c_int, _f64p, C.POINTER(_vp), _i64p, _f32p]),
+    ("dliom_timed_cloud_destroy", C.c_int, [_vp]),
+    ("dliom_timed_cloud_size", C.c_int, [_vp, _i64p]),
+    ("dliom_timed_cloud_has_intensities", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("dliom_timed_cloud_front_back_time", C.c_int, [_vp, _f32p, _f32p]),
+    ("dliom_timed_cloud_download", C.c_int, [_vp, _f32p, _f32p]),
+    ("dliom_add_range_data_timed_cloud", C.c_int, [_vp, _f64p, _f64p, C.c_double, _vp, _f32p, C.c_float, C.c_float, C.c_float,
+                                                   C.POINTER(_vp), _f32p, _f32p]),
+    ("dliom_points_batch_from_timed_cloud", C.c_int, [_vp, _vp, C.c_int64, _vp, _f64p, C.POINTER(_vp)]),
+]
+
+
+class PointCloud2:
+    """sensor_msgs/PointCloud2 as the library takes it: fields is a list of (name, offset, datatype, count); data any
+    uint8 array (a view at any byte offset will do: nothing needs to be aligned), kept alive by this object."""
+
+    def __init__(self, height, width, point_step, row_step, fields, data, stamp_sec=0, stamp_nsec=0, is_bigendian=0,
+                 data_size=None):
+        self.data = np.asarray(data, dtype=np.uint8)
+        if self.data.ndim != 1 or (self.data.size > 1 and self.data.strides[0] != 1):
+            raise ValueError("data is a one-dimensional run of bytes")
+        self.fields = [(str(name), int(offset), int(datatype), int(count)) for name, offset, datatype, count in fields]
+        self._table = (PointField * max(len(self.fields), 1))(*[PointField(name.encode(), offset, datatype, count)
+                                                                 for name, offset, datatype, count in self.fields])
+        self.struct = PointCloud2Struct(int(height), int(width), int(point_step), int(row_step), int(is_bigendian), len(self.fields),
+                                        self._table if self.fields else None, self.data.ctypes.data if self.data.size else None,
+                                        self.data.size if data_size is None else int(data_size), int(stamp_sec), int(stamp_nsec))
+
+    def check(self, mode):
+        """dliom_point_cloud2_check (host only) -> (status, time, rel_time_last); the status is returned, not raised."""
+        time, rel = C.c_int64(), C.c_double()
+        status = load_library().dliom_point_cloud2_check(C.byref(self.struct), int(mode), C.byref(time), C.byref(rel))
+        return status, time.value, rel.value
+
+    def decode(self, ctx, mode, sensor_to_tracking=None):
+        """dliom_point_cloud2_decode -> (TimedCloud, time, origin float32[3])"""
+        h, time, origin = _vp(), C.c_int64(), np.zeros(3, np.float32)
+        _check(ctx._L.dliom_point_cloud2_decode(ctx.h, C.byref(self.struct), int(mode),
+                                                None if sensor_to_tracking is None else _p(_f64(sensor_to_tracking), _f64p),
+                                                C.byref(h), C.byref(time), _p(origin, _f32p)), "dliom_point_cloud2_decode")
+        return TimedCloud(ctx, h), time.value, origin
+
+
+class TimedCloud:
+    """A decoded message in HBM (dliom_timed_cloud): packed (x, y, z, t) and, in the export modes, one intensity a point."""
+
+    def __init__(self, ctx, handle):
+        self._L, self.ctx, self.h = ctx._L, ctx, handle
+
+    def __len__(self):
+        n = C.c_int64()
+        _check(self._L.dliom_timed_cloud_size(self.h, C.byref(n)), "dliom_timed_cloud_size")
+        return int(n.value)
+
+    @property
+    def has_intensities(self):
+        v = C.c_int()
+        _check(self._L.dliom_timed_cloud_has_intensities(self.h, C.byref(v)), "dliom_timed_cloud_has_intensities")
+        return bool(v.value)
+
+    def front_back_time(self):
+        t = np.zeros(2, np.float32)
+        _check(self._L.dliom_timed_cloud_front_back_time(self.h, _p(t[:1], _f32p), _p(t[1:], _f32p)),
+               "dliom_timed_cloud_front_back_time")
+        return t[0], t[1]
+
+    def download(self):
+        """-> (xyzt float32 (n, 4), intensities float32 (n,) or None)"""
+        n = len(self)
+        xyzt = np.zeros((n, 4), np.float32)
+        it = np.zeros(n, np.float32) if self.has_intensities else None
+        _check(self._L.dliom_timed_cloud_download(self.h, _p(xyzt, _f32p), None if it is None else _p(it, _f32p)),
+               "dliom_timed_cloud_download")
+        return xyzt, it
+
+    def add_range_data(self, prev_pose, predicted_pose, scan_period, origin, min_range, max_range, voxel_filter_size):
+        """dliom_add_range_data_timed_cloud: add_range_data() with the ranges taken from this object.
+        Returns (PointCloud returns_in_tracking, origin_in_tracking, current_pose)."""
+        h = _vp()
+        o = np.zeros(3, dtype=np.float32)
+        cur = np.zeros(7, dtype=np.float32)
+        _check(self._L.dliom_add_range_data_timed_cloud(self.ctx.h, _p(_f64(prev_pose), _f64p), _p(_f64(predicted_pose), _f64p),
+                                                        scan_period, self.h, _p(_f32(origin), _f32p), C.c_float(min_range),
+                                                        C.c_float(max_range), C.c_float(voxel_filter_size), C.byref(h),
+                                                        _p(o, _f32p), _p(cur, _f32p)), "dliom_add_range_data_timed_cloud")
+        return PointCloud(self.ctx, _handle=h), o, cur
+
+    def to_points_batch(self, trajectory, cloud_time, sensor_to_tracking):
+        """dliom_points_batch_from_timed_cloud -> PointsBatch, or None when no point is kept."""
+        h = _vp()
+        _check(self._L.dliom_points_batch_from_timed_cloud(self.ctx.h, trajectory.h, int(cloud_time), self.h,
+                                                           _p(_f64(sensor_to_tracking), _f64p), C.byref(h)),
+               "dliom_points_batch_from_timed_cloud")
+        return PointsBatch(self.ctx, _handle=h) if h else None
+
+    def close(self):
+        if self.h is not None:
+            self._L.dliom_timed_cloud_destroy(self.h)
+            self.h = None

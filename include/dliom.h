@@ -1957,6 +1957,118 @@ int dliom_ctx_voxel_filter_reruns(const dliom_ctx* ctx, int64_t* count);
 int dliom_host_register(dliom_ctx* ctx, void* buffer, size_t bytes);
 int dliom_host_unregister(dliom_ctx* ctx, void* buffer);
 
+/* ---- PointCloud2 messages decoded on the device (cartographer_ros/sensor_bridge.cc:176-240, 286-299 and
+ * msg_conversion.cc:185-226) ----
+ * The per-point code in front of both pipelines: SensorBridge::HandlePointCloud2Message's four sensor branches with
+ * HandleRangefinder's change of frame, and the export's ToPointCloudWithIntensities / ...RsLiDAR.  PCL and ROS are not
+ * part of the reference tree this library is checked against, so this section is PARITY UNPINNED AGAINST PCL: the
+ * statement below defines the result, and the device equals a CPU model of the statement bit for bit
+ * (tests/point_cloud2_common.py, tests/cpp/point_cloud2_model.cc).
+ *
+ * The message is sensor_msgs/PointCloud2 as a plain struct.  Point i lies at
+ *     data + (i / width) * row_step + (i % width) * point_step,      n = height * width points,
+ * and a field of the table is `count` values of `datatype` (ROS's codes) at `offset` inside the point's record.
+ * Fields are matched by name, the first of that name, as pcl::fromROSMsg does; nothing needs to be aligned.
+ *
+ * Modes, and where each takes the point time t and the intensity from (x, y, z: FLOAT32, count 1, in every mode):
+ *   SLAM_OUSTER    (sensor_bridge.cc:183-194)  field "t", UINT32 [ns]
+ *       rel_time_last = double(float(t_last) * 1e-9f)     the uint32 rounds to the nearest float, then a float product
+ *       t_i = float(double(float(t_i) * 1e-9f) - rel_time_last)         the product is never fused with the subtraction
+ *   SLAM_VELODYNE  (:195-208)  field "time", FLOAT32 [s]
+ *       rel_time_last = double(time_last),   t_i = float(double(time_i) - rel_time_last)
+ *   SLAM_ROBOSENSE (:209-225)  field "timestamp", FLOAT64 [s]
+ *       t_i = float(timestamp_i - timestamp_last), subtracted in double
+ *   SLAM_OTHER     (:226-235)  t = 0
+ *   EXPORT         (msg_conversion.cc:187-210)  t = 0; intensity = the FLOAT32 field "intensity", or 1.0f for every point
+ *                  when no field has that name
+ *   EXPORT_RSLIDAR (:214-226)  t = 0; intensity = float(the UINT8 field "intensity")
+ * `last` is the message's last point, whether or not it is kept.  The four SLAM modes drop a point when any of x, y, z
+ * is NaN or +-Inf and keep the message's order; the export modes keep every point.
+ *
+ * *time = FromRos(stamp) = (stamp_sec + 719162 * 86400) * 10^7 + (stamp_nsec + 50) / 100, and for Ouster and Velodyne
+ * plus FromSeconds(rel_time_last) = int64(rel_time_last * 1e7), truncated.
+ *
+ * Frame change (HandleRangefinder): with sensor_to_tracking = [tx, ty, tz, qw, qx, qy, qz] given, every kept point becomes
+ * sensor_to_tracking.cast<float>() * p in float (Eigen's _transformVector order; the quaternion is cast as it is, not
+ * normalised), t untouched, and origin = the cast translation.  NULL: the points stay in the sensor frame and origin is
+ * zero -- the export applies its transform later, in the assembler.  (A non-finite coordinate an export mode keeps is a
+ * copy of the message's bits only without a frame change: what arithmetic makes of a NaN or an infinity is a NaN whose
+ * sign and payload are the machine's.)
+ *
+ * Refused with DLIOM_ERR_INVALID_ARGUMENT before anything touches a device (the host-only _check below answers the same):
+ *   is_bigendian != 0;  a datatype outside 1 .. 8;  a field with offset + size * count > point_step;
+ *   a required field that is missing, has another datatype or count != 1;  in the export modes an "intensity" field of
+ *   another datatype or count (PCL would leave the point's default there: refused here instead of guessed);
+ *   width * point_step > row_step;  height * row_step > data_size;  n >= 2^27;
+ *   n == 0 in the three timed modes (the reference calls back() on an empty vector);
+ *   a rel_time_last (Robosense: timestamp_last) that is not finite, or whose ticks do not fit an int64.
+ * Found on the device and refused from the call's ONE read-back, leaving no object: a kept point whose t is not finite or
+ * has |t * 1e7| >= 2^63 (the assembler's own rule for its input).
+ *
+ * A dliom_timed_cloud holds the kept points as packed (x, y, z, t) in HBM and, in the export modes, one intensity a
+ * point, in a block of the cloud pool (handed back by _destroy after a whole-device synchronise, like a cloud's).  The
+ * message's bytes are uploaded once -- from a buffer registered with dliom_host_register without a staging copy -- and
+ * one pass gathers the fields, tests, computes t, changes the frame and compacts; the result never comes back unless
+ * _download asks.  *out is an empty object, not NULL, when nothing is kept.  The message is free when the call returns. */
+enum {
+  DLIOM_POINT_FIELD_INT8 = 1,
+  DLIOM_POINT_FIELD_UINT8 = 2,
+  DLIOM_POINT_FIELD_INT16 = 3,
+  DLIOM_POINT_FIELD_UINT16 = 4,
+  DLIOM_POINT_FIELD_INT32 = 5,
+  DLIOM_POINT_FIELD_UINT32 = 6,
+  DLIOM_POINT_FIELD_FLOAT32 = 7,
+  DLIOM_POINT_FIELD_FLOAT64 = 8
+};
+typedef struct {
+  const char* name;
+  uint32_t offset;
+  uint32_t datatype; /* DLIOM_POINT_FIELD_* */
+  uint32_t count;
+} dliom_point_field;
+typedef struct {
+  uint32_t height, width, point_step, row_step;
+  uint32_t is_bigendian;
+  int32_t num_fields;
+  const dliom_point_field* fields;
+  const uint8_t* data;
+  uint64_t data_size;
+  uint32_t stamp_sec, stamp_nsec; /* header.stamp */
+} dliom_point_cloud2;
+typedef enum {
+  DLIOM_POINT_CLOUD2_SLAM_OUSTER = 0,
+  DLIOM_POINT_CLOUD2_SLAM_VELODYNE = 1,
+  DLIOM_POINT_CLOUD2_SLAM_ROBOSENSE = 2,
+  DLIOM_POINT_CLOUD2_SLAM_OTHER = 3,
+  DLIOM_POINT_CLOUD2_EXPORT = 4,
+  DLIOM_POINT_CLOUD2_EXPORT_RSLIDAR = 5
+} dliom_point_cloud2_mode;
+typedef struct dliom_timed_cloud dliom_timed_cloud;
+/* Host only, no context: the refusals above; *time (may be NULL) and *rel_time_last (may be NULL; 0 in the untimed modes)
+ * as the decode would return and use them. */
+int dliom_point_cloud2_check(const dliom_point_cloud2* message, int mode, int64_t* time, double* rel_time_last);
+int dliom_point_cloud2_decode(dliom_ctx* ctx, const dliom_point_cloud2* message, int mode, const double sensor_to_tracking[7],
+                              dliom_timed_cloud** out, int64_t* time, float origin[3]);
+int dliom_timed_cloud_destroy(dliom_timed_cloud* cloud);
+int dliom_timed_cloud_size(const dliom_timed_cloud* cloud, int64_t* n);
+int dliom_timed_cloud_has_intensities(const dliom_timed_cloud* cloud, int* has);
+/* t of the first and of the last kept point, known on the host from the decode's read-back (both 0 for an empty object):
+ * what HandleLaserScan's and AddRangeData's checks on the message need without a download. */
+int dliom_timed_cloud_front_back_time(const dliom_timed_cloud* cloud, float* front, float* back);
+/* xyzt: 4 n floats, intensities: n floats; either may be NULL.  Intensities the object does not have are refused. */
+int dliom_timed_cloud_download(const dliom_timed_cloud* cloud, float* xyzt, float* intensities);
+/* dliom_add_range_data with ranges_xyzt replaced by a decoded message: the raw points and the first range's time come
+ * from the object, which stays the caller's; everything else, every result and the read-back count are that call's. */
+int dliom_add_range_data_timed_cloud(dliom_ctx* ctx, const double prev_pose[7], const double predicted_pose[7],
+                                     double scan_period, const dliom_timed_cloud* ranges, const float origin[3],
+                                     float min_range, float max_range, float voxel_filter_size,
+                                     dliom_cloud** returns_in_tracking, float origin_in_tracking[3], float current_pose[7]);
+/* dliom_points_batch_from_sensor_points with points_xyzt and intensities replaced by a decoded message (an object
+ * without intensities gives a batch without).  The points the exactness check records are fetched from the object. */
+int dliom_points_batch_from_timed_cloud(dliom_ctx* ctx, dliom_trajectory* trajectory, int64_t cloud_time,
+                                        const dliom_timed_cloud* points, const double sensor_to_tracking[7],
+                                        dliom_points_batch** out);
+
 /* Kernel timing (HIP events on the context's stream). */
 enum {
   DLIOM_KERNEL_RTCSM_SCORE = 0, /* score-volume kernel (dominant) */
