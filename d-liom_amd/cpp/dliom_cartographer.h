@@ -710,7 +710,7 @@ class TimedCloudOnDevice {
  public:
   // mode: DLIOM_POINT_CLOUD2_*; sensor_to_tracking null: the points stay in the sensor frame (the export's way)
   TimedCloudOnDevice(Context* context, const sensor_msgs::PointCloud2& msg, int mode, const transform::Rigid3d* sensor_to_tracking)
-      : context_(context) {
+      : context_(context), column_times_(mode != DLIOM_POINT_CLOUD2_SLAM_VELODYNE && mode != DLIOM_POINT_CLOUD2_SLAM_ROBOSENSE) {
     std::vector<dliom_point_field> fields(msg.fields.size());
     for (size_t k = 0; k < fields.size(); ++k)
       fields[k] = dliom_point_field{msg.fields[k].name.c_str(), msg.fields[k].offset, msg.fields[k].datatype, msg.fields[k].count};
@@ -734,9 +734,22 @@ class TimedCloudOnDevice {
           "dliom_point_cloud2_decode");
     origin_ = Vector3f(origin[0], origin[1], origin[2]);
   }
-  ~TimedCloudOnDevice() { dliom_timed_cloud_destroy(cloud_); }
+  // takes over an object the library made (dliom_timed_cloud_stamp, dliom_timed_clouds_merge)
+  TimedCloudOnDevice(Context* context, dliom_timed_cloud* adopted, int64_t time, const Vector3f& origin, bool column_times)
+      : context_(context), cloud_(adopted), time_(time), origin_(origin), column_times_(column_times) {}
+  ~TimedCloudOnDevice() {
+    if (cloud_ != nullptr) dliom_timed_cloud_destroy(cloud_);
+  }
   TimedCloudOnDevice(const TimedCloudOnDevice&) = delete;
   TimedCloudOnDevice& operator=(const TimedCloudOnDevice&) = delete;
+  // (moved from: an object without a cloud, good for nothing but its destructor)
+  TimedCloudOnDevice(TimedCloudOnDevice&& other)
+      : context_(other.context_), cloud_(other.cloud_), time_(other.time_), origin_(other.origin_), column_times_(other.column_times_) {
+    other.cloud_ = nullptr;
+  }
+  // true: many points share a time -- an Ouster's one time a column (64 or 128 points), a cloud without point times.
+  // A merge of such a cloud replays std::sort's partitions on every run of equal times (RangeDataSynchronizer).
+  bool column_times() const { return column_times_; }
   const dliom_timed_cloud* get() const { return cloud_; }
   Context* context() const { return context_; }
   int64_t time() const { return time_; }  // the stamp HandleRangefinder gets: the last point's
@@ -752,12 +765,29 @@ class TimedCloudOnDevice {
     Check(dliom_timed_cloud_front_back_time(cloud_, &front, &back), "dliom_timed_cloud_front_back_time");
     return back;
   }
+  float front_time() const {
+    float front = 0.f, back = 0.f;
+    Check(dliom_timed_cloud_front_back_time(cloud_, &front, &back), "dliom_timed_cloud_front_back_time");
+    return front;
+  }
+  // StampRangeData on the device: a new object with this one's stamp and origin
+  std::shared_ptr<const TimedCloudOnDevice> Stamped(double scan_period) const {
+    dliom_timed_cloud* stamped = nullptr;
+    Check(dliom_timed_cloud_stamp(context_->get(), cloud_, scan_period, &stamped), "dliom_timed_cloud_stamp");
+    return std::make_shared<const TimedCloudOnDevice>(context_, stamped, time_, origin_, false);
+  }
   // what the general host paths go on with
   TimedPointCloudData Download() const {
     TimedPointCloudData data{time_, origin_, TimedPointCloud(size())};
     static_assert(sizeof(TimedPoint) == 16, "packed x, y, z, t");
+    ++Downloads();
     Check(dliom_timed_cloud_download(cloud_, data.ranges.empty() ? nullptr : &data.ranges[0].x, nullptr), "dliom_timed_cloud_download");
     return data;
+  }
+  // Download() calls of this process so far: what a caller who set up a device-only path checks it against
+  static std::atomic<int64_t>& Downloads() {
+    static std::atomic<int64_t> count(0);
+    return count;
   }
 
  private:
@@ -765,6 +795,7 @@ class TimedCloudOnDevice {
   dliom_timed_cloud* cloud_ = nullptr;
   int64_t time_ = 0;
   Vector3f origin_;
+  bool column_times_ = false;
 };
 }  // namespace sensor
 namespace mapping {
@@ -780,7 +811,73 @@ class RangeDataSynchronizer {
 
   // true: `sensor_id` is the only expected range sensor (no secondary cloud can be pending)
   bool SingleSensor(const std::string& sensor_id) const {
-    return expected_sensor_ids_.size() == 1 && sensor_id == prior_sensor_id_ && secondary_cloud_.empty();
+    return expected_sensor_ids_.size() == 1 && sensor_id == prior_sensor_id_ && secondary_cloud_.empty() &&
+           secondary_on_device_.empty();
+  }
+  // The same on decoded messages that stay in HBM (dliom.h "Two range sensors' clouds merged on the device"): the
+  // decisions below are the host overload's, taken from the stamps and first times the objects carry; stamping and the
+  // merge are the library's.  The pending secondary clouds are kept as device objects, so one synchronizer is fed either
+  // through this overload or through the host one, not both.
+  struct OnDevice {
+    int64_t time = 0;
+    std::vector<sensor::Vector3f> origins;
+    std::shared_ptr<const sensor::TimedCloudOnDevice> ranges;  // null: nothing yet (a secondary cloud was queued)
+    // this scan was merged by the host overload from downloads and `host` holds the result: the device merge refused it
+    // (DLIOM_ERR_CAPACITY: device_refused), or it was not asked (max_column_time_points)
+    bool merged_on_host = false, device_refused = false;
+    sensor::TimedPointCloudOriginData host;
+  };
+  // max_column_time_points: where the prior cloud or the pending one has column times (TimedCloudOnDevice::column_times),
+  // primary + secondary points above which the merge is left to the host overload (< 0: never)
+  OnDevice AddRangeData(const std::string& sensor_id, const std::shared_ptr<const sensor::TimedCloudOnDevice>& data, bool descrew,
+                        int64_t max_column_time_points = -1) {
+    if (expected_sensor_ids_.count(sensor_id) == 0)
+      Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_NE(expected_sensor_ids_.count(sensor_id), 0)");
+    OnDevice result;
+    const std::shared_ptr<const sensor::TimedCloudOnDevice> cloud = descrew ? data->Stamped(0.1) : data;
+    if (sensor_id != prior_sensor_id_) {
+      secondary_on_device_.push_back(cloud);
+      return result;
+    }
+    const double current_end = Seconds(cloud->time());
+    const double current_start = cloud->size() == 0 ? current_end : current_end + cloud->front_time();
+    while (!secondary_on_device_.empty() && Seconds(secondary_on_device_.front()->time()) < current_start)
+      secondary_on_device_.pop_front();
+    result.time = cloud->time();
+    if (secondary_on_device_.empty() || secondary_on_device_.front()->size() == 0 ||
+        Seconds(secondary_on_device_.front()->time()) + secondary_on_device_.front()->front_time() > current_end) {
+      result.origins.assign(1, cloud->origin());
+      result.ranges = cloud;
+      return result;
+    }
+    const sensor::TimedCloudOnDevice& sec = *secondary_on_device_.front();
+    dliom_timed_cloud* merged = nullptr;
+    int status = DLIOM_ERR_CAPACITY;
+    const bool ask = max_column_time_points < 0 || !(data->column_times() || sec.column_times()) ||
+                     static_cast<int64_t>(data->size() + sec.size()) <= max_column_time_points;
+    if (ask)
+      status = dliom_timed_clouds_merge(data->context()->get(), data->get(), descrew ? cloud->get() : nullptr, cloud->time(), sec.get(),
+                                        sec.time(), &merged);
+    if (status == DLIOM_ERR_CAPACITY) {
+      result.device_refused = ask;
+      // this scan the host's way: the pending cloud (stamped already) and the prior one come down, the host overload merges
+      secondary_cloud_.assign(1, sec.Download());
+      try {
+        result.host = AddRangeData(sensor_id, data->Download(), descrew);
+      } catch (...) {
+        secondary_cloud_.clear();
+        throw;
+      }
+      secondary_cloud_.clear();
+      result.merged_on_host = true;
+      return result;
+    }
+    Check(status, "dliom_timed_clouds_merge (CHECK(i_start != -1) range_data_synchronizer.cc:84)");
+    result.origins.push_back(cloud->origin());
+    result.origins.push_back(sec.origin());
+    result.ranges = std::make_shared<const sensor::TimedCloudOnDevice>(data->context(), merged, cloud->time(), cloud->origin(),
+                                                                       data->column_times() || sec.column_times());
+    return result;
   }
   sensor::TimedPointCloudOriginData AddRangeData(const std::string& sensor_id, const sensor::TimedPointCloudData& data,
                                                  bool descrew) {
@@ -854,6 +951,7 @@ class RangeDataSynchronizer {
   std::set<std::string> expected_sensor_ids_;
   std::string prior_sensor_id_;
   std::deque<sensor::TimedPointCloudData> secondary_cloud_;
+  std::deque<std::shared_ptr<const sensor::TimedCloudOnDevice>> secondary_on_device_;
 };
 
 // proto::LocalTrajectoryBuilderOptions3D: the front end's options plus the AddRangeData / IMU fields
@@ -1136,8 +1234,12 @@ class LocalTrajectoryBuilder3D {
       DLIOM_ADAPTER_STAGE(1);
       return AddAccumulatedRangeData(unsynchronized.time, current_pose, origin_in_tracking, cloud);
     }
-    const sensor::TimedPointCloudOriginData sync =
-        synchronizer_.AddRangeData(sensor_id, unsynchronized, options_.enable_manual_descrew);
+    return AddSynchronizedRangeData(synchronizer_.AddRangeData(sensor_id, unsynchronized, options_.enable_manual_descrew));
+  }
+
+ private:
+  // the general host path behind the synchronizer: pack, upload, de-skew + accumulate
+  std::unique_ptr<MatchingResult> AddSynchronizedRangeData(const sensor::TimedPointCloudOriginData& sync) {
     if (sync.ranges.empty() || !imu_initialized_ || !have_prediction_) return nullptr;
     if (sync.ranges.back().point_time.t > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
     // prev_state_ and predicted_states_.back() (.cc:424-427)
@@ -1178,13 +1280,79 @@ class LocalTrajectoryBuilder3D {
     return AddAccumulatedRangeData(sync.time, current_pose, origin_in_tracking, cloud);
   }
 
+ public:
   // The single-sensor path above on a message decoded on the device (SensorBridge::HandlePointCloud2Message): the ranges are
   // in HBM already, in the tracking frame, and stay there; the two checks on them read what the decode brought back.
-  // Several sensors, manual de-skew and accumulation stay on the general host path: they download the cloud and go on as
-  // before (the synchronizer merges and sorts on the host).
+  // Several sensors, manual de-skew and accumulation need an object they may keep (a secondary lidar's cloud waits for the
+  // prior one's): from a caller who keeps his, they download the cloud and go on through the host synchronizer;
+  // the overload below takes the object over and stays on the device.
   std::unique_ptr<MatchingResult> AddRangeData(const std::string& sensor_id, const sensor::TimedCloudOnDevice& ranges) {
-    if (!(synchronizer_.SingleSensor(sensor_id) && !options_.enable_manual_descrew && options_.num_accumulated_range_data == 1))
-      return AddRangeData(sensor_id, ranges.Download());
+    if (!FastPath(sensor_id)) return AddRangeData(sensor_id, ranges.Download());
+    return AddSingleSensorRangeData(ranges);
+  }
+  // ... on an object handed over.  Several sensors, manual de-skew or accumulation: the synchronizer's device overload
+  // (stamp, merge and std::sort's order on the device) and the accumulator's device input, without a download.  A merge the
+  // device refuses (DLIOM_ERR_CAPACITY: an arrangement of equal times the sort's replay does not take) goes the host's way
+  // for that scan and is counted (merge_host_fallbacks()); so does, counted apart (merges_left_to_host()), a merge of
+  // clouds with column times above kMaxColumnTimePointsOnDevice.
+  std::unique_ptr<MatchingResult> AddRangeData(const std::string& sensor_id, sensor::TimedCloudOnDevice&& ranges) {
+    if (FastPath(sensor_id)) return AddSingleSensorRangeData(ranges);
+    const RangeDataSynchronizer::OnDevice sync =
+        synchronizer_.AddRangeData(sensor_id, std::make_shared<const sensor::TimedCloudOnDevice>(std::move(ranges)),
+                                   options_.enable_manual_descrew, kMaxColumnTimePointsOnDevice);
+    if (sync.merged_on_host) {
+      ++(sync.device_refused ? merge_host_fallbacks_ : merges_left_to_host_);
+      return AddSynchronizedRangeData(sync.host);
+    }
+    if (sync.origins.size() > 1) ++device_merges_;
+    if (sync.ranges == nullptr || sync.ranges->size() == 0 || !imu_initialized_ || !have_prediction_) return nullptr;
+    if (sync.ranges->back_time() > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
+    double prev[7], vel[3], bias[6], predicted[7], pvel[3];
+    Check(dliom_imu_window_state(window_, 0, prev, vel, bias), "dliom_imu_window_state");
+    Check(dliom_imu_window_predict(window_, predicted, pvel), "dliom_imu_window_predict");
+    std::vector<float> origins(3 * sync.origins.size());
+    for (size_t k = 0; k < sync.origins.size(); ++k) {
+      origins[3 * k] = sync.origins[k].x;
+      origins[3 * k + 1] = sync.origins[k].y;
+      origins[3 * k + 2] = sync.origins[k].z;
+    }
+    float current_pose[7];
+    int accumulated = 0;
+    if (!accumulating_) {
+      accumulation_started_ = std::chrono::steady_clock::now();
+      accumulating_ = true;
+    }
+    Check(dliom_range_accumulator_add_timed_cloud(accumulator_, prev, predicted, options_.scan_period, sync.ranges->get(), origins.data(),
+                                                  static_cast<int>(sync.origins.size()), options_.min_range, options_.max_range,
+                                                  options_.voxel_filter_size, current_pose, &accumulated),
+          "AddRangeData (de-skew + accumulate)");
+    if (accumulated < options_.num_accumulated_range_data) return nullptr;
+    accumulating_ = false;
+    dliom_cloud* cloud = nullptr;
+    float origin_in_tracking[3];
+    Check(dliom_range_accumulator_finish(accumulator_, options_.voxel_filter_size, &cloud, origin_in_tracking),
+          "AddRangeData (voxel filter + tracking frame)");
+    return AddAccumulatedRangeData(sync.time, current_pose, origin_in_tracking, cloud);
+  }
+  // scans whose merge the device refused and the host synchronizer served
+  int64_t merge_host_fallbacks() const { return merge_host_fallbacks_; }
+  // scans the synchronizer merged with a secondary lidar's on the device
+  int64_t device_merges() const { return device_merges_; }
+  // scans with column times (an Ouster's, a cloud without point times) whose merge was left to the host synchronizer
+  int64_t merges_left_to_host() const { return merges_left_to_host_; }
+  // Primary + secondary points up to which clouds with column times are merged on the device.  0: never -- the replay of
+  // std::sort's partitions on runs of equal times is one workgroup's work and lost to download + host std::sort + upload
+  // at every size measured, 0.25 ms against 0.19 ms at 768 merged points, 13.4 ms against 2.0 ms at 98 304 (64 x 1024 +
+  // half of a second one) and 77.9 ms against 16.9 ms at 393 216 (profiles/range_sync_bench.json, DESIGN.md section
+  // 3.21).  Clouds with distinct times (Velodyne, Robosense) are not limited: 0.41 ms against 4.2 ms and 0.94 ms against
+  // 25.7 ms at the same sizes.
+  static constexpr int64_t kMaxColumnTimePointsOnDevice = 0;
+
+ private:
+  bool FastPath(const std::string& sensor_id) const {
+    return synchronizer_.SingleSensor(sensor_id) && !options_.enable_manual_descrew && options_.num_accumulated_range_data == 1;
+  }
+  std::unique_ptr<MatchingResult> AddSingleSensorRangeData(const sensor::TimedCloudOnDevice& ranges) {
     if (ranges.size() == 0 || !imu_initialized_ || !have_prediction_) return nullptr;
     if (ranges.back_time() > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
     DLIOM_ADAPTER_STAGE(0);
@@ -1203,6 +1371,7 @@ class LocalTrajectoryBuilder3D {
     return AddAccumulatedRangeData(ranges.time(), current_pose, origin_in_tracking, cloud);
   }
 
+ public:
   const ActiveSubmaps3D& active_submaps() const { return active_submaps_; }
   // local_trajectory_builder_3d.h:113, .cc:624-649: the same five metrics under the same family names, labels and bucket
   // boundaries; they are process-wide like the reference's file-scope statics and observe nothing until this is called
@@ -1385,6 +1554,7 @@ class LocalTrajectoryBuilder3D {
   bool accumulating_ = false;  // num_accumulated_ > 0
   std::chrono::steady_clock::time_point accumulation_started_ = std::chrono::steady_clock::now();
   int64_t histogram_host_fallbacks_ = 0;
+  int64_t merge_host_fallbacks_ = 0, merges_left_to_host_ = 0, device_merges_ = 0;
 
  public:
   // ComputeHistogram calls that the device entry point refused and the host one served
@@ -1415,8 +1585,8 @@ class SensorBridge {
   std::unique_ptr<mapping::LocalTrajectoryBuilder3D::MatchingResult> HandlePointCloud2Message(
       const std::string& sensor_id, const sensor_msgs::PointCloud2& msg, const std::string& sensor_type,
       const transform::Rigid3d& sensor_to_tracking) {
-    const sensor::TimedCloudOnDevice ranges(context_, msg, ModeOf(sensor_type), &sensor_to_tracking);
-    return trajectory_builder_->AddRangeData(sensor_id, ranges);
+    sensor::TimedCloudOnDevice ranges(context_, msg, ModeOf(sensor_type), &sensor_to_tracking);
+    return trajectory_builder_->AddRangeData(sensor_id, std::move(ranges));
   }
 
  private:

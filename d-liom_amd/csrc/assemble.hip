@@ -623,6 +623,9 @@ int dliom_points_batch_from_timed_cloud(dliom_ctx* ctx, dliom_trajectory* traj, 
   DevicePoints d{nullptr, nullptr};
   int64_t n = 0;
   DLIOM_TRY(timed_cloud_view(points, ctx, &n, &d.xyzt, &d.intensities, nullptr));
+  bool has_origin_index = false;
+  DLIOM_TRY(timed_cloud_origin_index(points, &has_origin_index, nullptr));
+  if (has_origin_index) return DLIOM_ERR_INVALID_ARGUMENT;  // two sensors' merged ranges: not a message's points
   return batch_from_points(ctx, traj, cloud_time, nullptr, nullptr, &d, n, sensor_to_tracking, out);
 }
 

@@ -427,6 +427,13 @@ int assemble_from_sensor_points(dliom_ctx* ctx, dliom_trajectory* traj, int64_t 
 // (may be null: not asked for) is null for an object without; *front_t (may be null) the first point's t.
 int timed_cloud_view(const dliom_timed_cloud* cloud, const dliom_ctx* ctx, int64_t* n, const float4** d_xyzt, const float** d_intensities,
                      float* front_t);
+// ... and of the origin-index channel a merge's result has (range_sync.hip): *has, and *d_origin_index (may be null: not
+// asked for), which is null for an object without the channel or without points
+int timed_cloud_origin_index(const dliom_timed_cloud* cloud, bool* has, const float** d_origin_index);
+// rotational_histogram.hip: the device stages of dliom_diag_std_sort_order on n keys (1 .. 2^22) that are in HBM already,
+// outside ctx->misc, which the stages work in: the radix sort's buffers, *d_order (n indices) and *d_status (0, or 1: the
+// replay refuses) lie there afterwards.  Enqueued on ctx->stream; no upload, no download, no synchronisation.
+int std_sort_order_enqueue(dliom_ctx* ctx, const float* d_keys, int n, const int** d_order, const int** d_status);
 // sequential_sums.hip: the reference's sequential `score += probability` float sums, bit-identical.
 // Launches the kernels for `count` candidates whose indices are in d_list (c -> translation c / R, rotation c % R):
 // method 0 = one lane replays the loop, 1 = element scan, 2 = chunk scan.  Methods 1 and 2 need the 15-bit values of a

@@ -14,18 +14,7 @@
 
 #include "device_common.h"
 #include "point_cloud2_layout.h"
-
-struct dliom_timed_cloud {
-  dliom_ctx* ctx = nullptr;
-  int device = 0;
-  int64_t n = 0;
-  void* base = nullptr;  // a block of the cloud pool: xyzt | intensities (null: the empty object)
-  size_t base_bytes = 0;
-  float4* d_xyzt = nullptr;
-  float* d_intensities = nullptr;  // null: none (the SLAM modes)
-  bool has_intensities = false;    // "one a point", also of an empty object made by an export mode
-  float front_t = 0.f, back_t = 0.f;
-};
+#include "timed_cloud.h"
 
 namespace dliom {
 namespace {
@@ -281,6 +270,21 @@ int dliom_timed_cloud_has_intensities(const dliom_timed_cloud* cloud, int* has) 
   return DLIOM_OK;
 }
 
+int dliom_timed_cloud_has_origin_index(const dliom_timed_cloud* cloud, int* has) {
+  if (cloud == nullptr || has == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *has = cloud->has_origin_index ? 1 : 0;
+  return DLIOM_OK;
+}
+
+int dliom_timed_cloud_download_origin_index(const dliom_timed_cloud* cloud, float* origin_index) {
+  if (cloud == nullptr || origin_index == nullptr || !cloud->has_origin_index) return DLIOM_ERR_INVALID_ARGUMENT;
+  if (cloud->n == 0) return DLIOM_OK;
+  DLIOM_HIP_TRY(hipSetDevice(cloud->device));
+  DLIOM_HIP_TRY(hipStreamSynchronize(cloud->ctx->stream));
+  DLIOM_HIP_TRY(hipMemcpy(origin_index, cloud->d_origin_index, 4 * static_cast<size_t>(cloud->n), hipMemcpyDeviceToHost));
+  return DLIOM_OK;
+}
+
 int dliom_timed_cloud_front_back_time(const dliom_timed_cloud* cloud, float* front, float* back) {
   if (cloud == nullptr || front == nullptr || back == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
   *front = cloud->front_t;
@@ -310,6 +314,12 @@ int timed_cloud_view(const dliom_timed_cloud* cloud, const dliom_ctx* ctx, int64
   *d_xyzt = cloud->d_xyzt;
   if (d_intensities != nullptr) *d_intensities = cloud->n > 0 ? cloud->d_intensities : nullptr;
   if (front_t != nullptr) *front_t = cloud->front_t;
+  return DLIOM_OK;
+}
+int timed_cloud_origin_index(const dliom_timed_cloud* cloud, bool* has, const float** d_origin_index) {
+  if (cloud == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *has = cloud->has_origin_index;
+  if (d_origin_index != nullptr) *d_origin_index = cloud->n > 0 ? cloud->d_origin_index : nullptr;
   return DLIOM_OK;
 }
 }  // namespace dliom

@@ -495,10 +495,11 @@ namespace dliom {
 // AddRangeData up to the accumulation (:393-472): VoxelFilter(0.5 size) on the timed hits, per-hit de-skew + range
 // gate, the returns compacted in hit order into ctx->misc (x | y | z with stride *stride).  origin_index (one float
 // per range, may be null) and origins (num_origins x 3) are the RangeDataSynchronizer's origin table.  d_ranges (null: none):
-// the ranges are in HBM already (a decoded message, point_cloud2.hip), ranges_xyzt is null and front_time is the first one's t.
+// the ranges are in HBM already (a decoded message, point_cloud2.hip), ranges_xyzt is null and front_time is the first one's t;
+// d_origin_index (null: none) is then the origin index in HBM (a merge's result, range_sync.hip) and origin_index is null.
 static int add_range_data_stage_a(dliom_ctx* ctx, const double prev_pose[7], const double predicted_pose[7],
                                   double scan_period, const float* ranges_xyzt, const float4* d_ranges, float front_time,
-                                  const float* origin_index, int64_t n,
+                                  const float* origin_index, const float* d_origin_index, int64_t n,
                                   const float* origins, int num_origins, float min_range, float max_range,
                                   float voxel_filter_size, float current_pose[7], const float** returns,
                                   size_t* stride, int64_t* num_returns) {
@@ -530,7 +531,7 @@ static int add_range_data_stage_a(dliom_ctx* ctx, const double prev_pose[7], con
   hipLaunchKernelGGL(split_xyzt_kernel, dim3(static_cast<unsigned>((n + threads - 1) / threads)), dim3(threads), 0,
                      ctx->stream, d_ranges, static_cast<int>(n), b, b + nn, b + 2 * nn, b + 3 * nn);
   // hits = VoxelFilter(0.5f * voxel_filter_size).Filter(ranges): the time rides along
-  const bool multi = origin_index != nullptr && num_origins > 1;
+  const bool multi = (origin_index != nullptr || d_origin_index != nullptr) && num_origins > 1;
   DeskewArgs a;
   // the first range always survives the filter, so hits.front() is ranges.front()
   DLIOM_TRY(make_deskew_args(prev_pose, predicted_pose, scan_period, origins, min_range, max_range, front_time, &a));
@@ -574,9 +575,12 @@ static int add_range_data_stage_a(dliom_ctx* ctx, const double prev_pose[7], con
     DLIOM_TRY(voxel_filter_arrays(ctx, Soa{b, b + nn, b + 2 * nn, b + 3 * nn, n}, 0.5f * voxel_filter_size, c, c + nn,
                                   c + 2 * nn, c + 3 * nn, &n1));
     if (multi) {  // the same filter once more with the origin index as the passenger: same survivors, same order
-      DLIOM_HIP_TRY(hipMemcpyAsync(oi_in, origin_index, 4 * nn, hipMemcpyHostToDevice, ctx->stream));
+      if (d_origin_index == nullptr) {
+        DLIOM_HIP_TRY(hipMemcpyAsync(oi_in, origin_index, 4 * nn, hipMemcpyHostToDevice, ctx->stream));
+        d_origin_index = oi_in;
+      }
       int64_t n1b = 0;
-      DLIOM_TRY(voxel_filter_arrays(ctx, Soa{b, b + nn, b + 2 * nn, oi_in, n}, 0.5f * voxel_filter_size, d, d + nn,
+      DLIOM_TRY(voxel_filter_arrays(ctx, Soa{b, b + nn, b + 2 * nn, d_origin_index, n}, 0.5f * voxel_filter_size, d, d + nn,
                                     d + 2 * nn, oi_f, &n1b));
       if (n1b != n1) return DLIOM_ERR_INVALID_ARGUMENT;
     }
@@ -721,7 +725,7 @@ extern "C" int dliom_add_range_data(dliom_ctx* ctx, const double prev_pose[7], c
   const float* e = nullptr;
   size_t stride = 0;
   int64_t n2 = 0;
-  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, nullptr, 0.f, nullptr, n, origin, 1,
+  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, nullptr, 0.f, nullptr, nullptr, n, origin, 1,
                                    min_range, max_range, voxel_filter_size, current_pose, &e, &stride, &n2));
   return add_range_data_stage_b(ctx, e, e + stride, e + 2 * stride, n2, voxel_filter_size, current_pose,
                                 returns_in_tracking, origin_in_tracking);
@@ -741,12 +745,15 @@ extern "C" int dliom_add_range_data_timed_cloud(dliom_ctx* ctx, const double pre
   const float4* d_ranges = nullptr;
   float front_time = 0.f;
   DLIOM_TRY(timed_cloud_view(ranges, ctx, &n, &d_ranges, nullptr, &front_time));
+  bool has_origin_index = false;
+  DLIOM_TRY(timed_cloud_origin_index(ranges, &has_origin_index, nullptr));
+  if (has_origin_index) return DLIOM_ERR_INVALID_ARGUMENT;  // two sensors' ranges: dliom_range_accumulator_add_timed_cloud
   if (n == 0) return DLIOM_ERR_EMPTY_CLOUD;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   const float* e = nullptr;
   size_t stride = 0;
   int64_t n2 = 0;
-  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, nullptr, d_ranges, front_time, nullptr, n, origin, 1,
+  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, nullptr, d_ranges, front_time, nullptr, nullptr, n, origin, 1,
                                    min_range, max_range, voxel_filter_size, current_pose, &e, &stride, &n2));
   return add_range_data_stage_b(ctx, e, e + stride, e + 2 * stride, n2, voxel_filter_size, current_pose,
                                 returns_in_tracking, origin_in_tracking);
@@ -777,15 +784,13 @@ extern "C" int dliom_range_accumulator_destroy(dliom_range_accumulator* a) {
   return DLIOM_OK;
 }
 
-extern "C" int dliom_range_accumulator_add(dliom_range_accumulator* a, const double prev_pose[7],
-                                           const double predicted_pose[7], double scan_period, const float* ranges_xyzt,
-                                           const float* origin_index, int64_t n, const float* origins, int num_origins,
-                                           float min_range, float max_range, float voxel_filter_size,
-                                           float current_pose[7], int* num_accumulated) {
-  if (a == nullptr || prev_pose == nullptr || predicted_pose == nullptr || origins == nullptr || num_origins < 1 ||
-      num_origins > 4 || n < 0 || current_pose == nullptr || (n > 0 && ranges_xyzt == nullptr) || !(scan_period > 0.) ||
-      !(voxel_filter_size > 0.f))
-    return DLIOM_ERR_INVALID_ARGUMENT;
+// one AddRangeData call up to the accumulation, the ranges and the origin index from the host (ranges_xyzt, origin_index)
+// or in HBM already (d_ranges with front_time, d_origin_index)
+static int range_accumulator_add(dliom_range_accumulator* a, const double prev_pose[7], const double predicted_pose[7],
+                                 double scan_period, const float* ranges_xyzt, const float* origin_index, const float4* d_ranges,
+                                 float front_time, const float* d_origin_index, int64_t n, const float* origins, int num_origins,
+                                 float min_range, float max_range, float voxel_filter_size, float current_pose[7],
+                                 int* num_accumulated) {
   if (n == 0) return DLIOM_ERR_EMPTY_CLOUD;
   if (n > (1 << 30)) return DLIOM_ERR_INVALID_ARGUMENT;
   dliom_ctx* ctx = a->ctx;
@@ -793,8 +798,9 @@ extern "C" int dliom_range_accumulator_add(dliom_range_accumulator* a, const dou
   const float* e = nullptr;
   size_t stride = 0;
   int64_t n2 = 0;
-  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, nullptr, 0.f, origin_index, n, origins,
-                                   num_origins, min_range, max_range, voxel_filter_size, current_pose, &e, &stride, &n2));
+  DLIOM_TRY(add_range_data_stage_a(ctx, prev_pose, predicted_pose, scan_period, ranges_xyzt, d_ranges, front_time, origin_index,
+                                   d_origin_index, n, origins, num_origins, min_range, max_range, voxel_filter_size, current_pose, &e,
+                                   &stride, &n2));
   const size_t need = static_cast<size_t>(a->count + n2);
   if (need > a->cap) {  // grow, keeping what is there
     const size_t new_cap = std::max<size_t>(need * 2, 4096);
@@ -820,6 +826,39 @@ extern "C" int dliom_range_accumulator_add(dliom_range_accumulator* a, const dou
   std::memcpy(a->current_pose, current_pose, sizeof a->current_pose);
   if (num_accumulated != nullptr) *num_accumulated = a->num_accumulated;
   return DLIOM_OK;
+}
+
+extern "C" int dliom_range_accumulator_add(dliom_range_accumulator* a, const double prev_pose[7],
+                                           const double predicted_pose[7], double scan_period, const float* ranges_xyzt,
+                                           const float* origin_index, int64_t n, const float* origins, int num_origins,
+                                           float min_range, float max_range, float voxel_filter_size,
+                                           float current_pose[7], int* num_accumulated) {
+  if (a == nullptr || prev_pose == nullptr || predicted_pose == nullptr || origins == nullptr || num_origins < 1 ||
+      num_origins > 4 || n < 0 || current_pose == nullptr || (n > 0 && ranges_xyzt == nullptr) || !(scan_period > 0.) ||
+      !(voxel_filter_size > 0.f))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  return range_accumulator_add(a, prev_pose, predicted_pose, scan_period, ranges_xyzt, origin_index, nullptr, 0.f, nullptr, n, origins,
+                               num_origins, min_range, max_range, voxel_filter_size, current_pose, num_accumulated);
+}
+
+// dliom_range_accumulator_add on a device object (a decoded message, or range_sync.hip's merge with its origin index)
+extern "C" int dliom_range_accumulator_add_timed_cloud(dliom_range_accumulator* a, const double prev_pose[7],
+                                                       const double predicted_pose[7], double scan_period,
+                                                       const dliom_timed_cloud* ranges, const float* origins, int num_origins,
+                                                       float min_range, float max_range, float voxel_filter_size,
+                                                       float current_pose[7], int* num_accumulated) {
+  if (a == nullptr || prev_pose == nullptr || predicted_pose == nullptr || origins == nullptr || num_origins < 1 ||
+      num_origins > 4 || current_pose == nullptr || !(scan_period > 0.) || !(voxel_filter_size > 0.f))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  int64_t n = 0;
+  const float4* d_ranges = nullptr;
+  const float* d_origin_index = nullptr;
+  float front_time = 0.f;
+  bool has_origin_index = false;
+  DLIOM_TRY(timed_cloud_view(ranges, a->ctx, &n, &d_ranges, nullptr, &front_time));
+  DLIOM_TRY(timed_cloud_origin_index(ranges, &has_origin_index, &d_origin_index));
+  return range_accumulator_add(a, prev_pose, predicted_pose, scan_period, nullptr, nullptr, d_ranges, front_time, d_origin_index, n,
+                               origins, num_origins, min_range, max_range, voxel_filter_size, current_pose, num_accumulated);
 }
 
 extern "C" int dliom_range_accumulator_finish(dliom_range_accumulator* a, float voxel_filter_size,

@@ -1274,11 +1274,13 @@ size_t carve_big_arrays(char* base, size_t entries, dliom::rothist::BigArrays* A
 }
 }  // namespace
 
-extern "C" int dliom_diag_std_sort_order(dliom_ctx* ctx, const float* keys, int n, int32_t* order) {
+// The device stages of the sort order on keys that are in HBM already (internal.h): nothing is uploaded, read back or waited
+// for.  Works in ctx->misc, where *d_order (n indices) and *d_status (0, or 1: the replay refuses -- the work-list cap, the
+// heap-sort fallback of a large segment) point afterwards; d_keys must lie elsewhere.
+namespace dliom {
+int std_sort_order_enqueue(dliom_ctx* ctx, const float* d_keys, int n, const int** d_order_out, const int** d_status_out) {
   using namespace rothist;
-  if (ctx == nullptr || (n > 0 && (keys == nullptr || order == nullptr)) || n < 0 || n > (1 << 22)) return DLIOM_ERR_INVALID_ARGUMENT;
-  if (n == 0) return DLIOM_OK;
-  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx == nullptr || d_keys == nullptr || n <= 0 || n > (1 << 22)) return DLIOM_ERR_INVALID_ARGUMENT;
   if (n > kMaxSlice) {
     // the path of slices above kMaxSlice (rothist_big.h): radix sort + the order of equal keys from introsort's partitions
     BigArrays A;
@@ -1286,16 +1288,13 @@ extern "C" int dliom_diag_std_sort_order(dliom_ctx* ctx, const float* keys, int 
     const size_t big_bytes = carve_big_arrays(nullptr, entries, &A);
     size_t temp_bytes = 0;
     DLIOM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, A.key_in, A.key_out, A.val_in, A.val_out, n, 0, 32, ctx->stream));
-    const size_t keys_at = align256(big_bytes);
-    const size_t order_at = keys_at + align256(static_cast<size_t>(n) * 4);
+    const size_t order_at = align256(big_bytes);
     const size_t temp_at = order_at + align256(static_cast<size_t>(n) * 4 + 256);
     DLIOM_TRY(ctx->misc.reserve(temp_at + temp_bytes + 256));
     char* base = static_cast<char*>(ctx->misc.p);
     carve_big_arrays(base, entries, &A);
-    float* d_keys = reinterpret_cast<float*>(base + keys_at);
     int* d_order = reinterpret_cast<int*>(base + order_at);
     int* d_status = d_order + n;
-    DLIOM_HIP_TRY(hipMemcpyAsync(d_keys, keys, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(big_sort_items_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_keys, n, A.key_in, A.val_in);
     DLIOM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(base + temp_at, temp_bytes, A.key_in, A.key_out, A.val_in, A.val_out, n, 0, 32,
                                                      ctx->stream));
@@ -1308,17 +1307,13 @@ extern "C" int dliom_diag_std_sort_order(dliom_ctx* ctx, const float* keys, int 
     }
     hipLaunchKernelGGL(big_sort_order_kernel, dim3(1), dim3(kThreads), kBigLdsBytes, ctx->stream, n, A, d_order, d_status);
     DLIOM_HIP_TRY(hipGetLastError());
-    int status = 0;
-    DLIOM_HIP_TRY(hipMemcpyAsync(order, d_order, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DLIOM_HIP_TRY(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return status == 0 ? DLIOM_OK : DLIOM_ERR_CAPACITY;
+    *d_order_out = d_order;
+    *d_status_out = d_status;
+    return DLIOM_OK;
   }
-  DLIOM_TRY(ctx->misc.reserve(static_cast<size_t>(kMaxSlice) * 8 + 256));
-  float* d_keys = ctx->misc.as<float>();
-  int* d_order = reinterpret_cast<int*>(d_keys + kMaxSlice);
+  DLIOM_TRY(ctx->misc.reserve(static_cast<size_t>(kMaxSlice) * 4 + 256));
+  int* d_order = ctx->misc.as<int>();
   int* d_status = d_order + kMaxSlice;
-  DLIOM_HIP_TRY(hipMemcpyAsync(d_keys, keys, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, ctx->stream));
   const size_t lds = kStdSortLdsBytes;
   if ((ctx->func_attr_set & kFuncAttrStdSortDiag) == 0u) {
     DLIOM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(std_sort_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1327,6 +1322,22 @@ extern "C" int dliom_diag_std_sort_order(dliom_ctx* ctx, const float* keys, int 
   }
   hipLaunchKernelGGL(std_sort_order_kernel, dim3(1), dim3(kThreads), lds, ctx->stream, d_keys, n, d_order, d_status);
   DLIOM_HIP_TRY(hipGetLastError());
+  *d_order_out = d_order;
+  *d_status_out = d_status;
+  return DLIOM_OK;
+}
+}  // namespace dliom
+
+// upload, the device stages above, download (the keys wait in the export stages' scratch: the stages work in ctx->misc)
+extern "C" int dliom_diag_std_sort_order(dliom_ctx* ctx, const float* keys, int n, int32_t* order) {
+  if (ctx == nullptr || (n > 0 && (keys == nullptr || order == nullptr)) || n < 0 || n > (1 << 22)) return DLIOM_ERR_INVALID_ARGUMENT;
+  if (n == 0) return DLIOM_OK;
+  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  DLIOM_TRY(ctx->outlier.reserve(static_cast<size_t>(n) * 4));
+  float* d_keys = ctx->outlier.as<float>();
+  DLIOM_HIP_TRY(hipMemcpyAsync(d_keys, keys, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, ctx->stream));
+  const int *d_order = nullptr, *d_status = nullptr;
+  DLIOM_TRY(std_sort_order_enqueue(ctx, d_keys, n, &d_order, &d_status));
   int status = 0;
   DLIOM_HIP_TRY(hipMemcpyAsync(order, d_order, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, ctx->stream));
   DLIOM_HIP_TRY(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));

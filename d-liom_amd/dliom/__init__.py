@@ -2474,6 +2474,19 @@ class RangeDataAccumulator:
                "dliom_range_accumulator_add")
         return cur, k.value
 
+    def add_timed_cloud(self, prev_pose, predicted_pose, scan_period, ranges, min_range, max_range, voxel_filter_size,
+                        origins=((0.0, 0.0, 0.0),)):
+        """dliom_range_accumulator_add_timed_cloud: add() with the ranges and the origin index taken from a TimedCloud."""
+        og = _f32(origins).reshape(-1, 3)
+        cur = np.zeros(7, dtype=np.float32)
+        k = C.c_int()
+        _check(self._L.dliom_range_accumulator_add_timed_cloud(self.h, _p(_f64(prev_pose), _f64p), _p(_f64(predicted_pose), _f64p),
+                                                               float(scan_period), ranges.h, _p(og, _f32p), len(og),
+                                                               C.c_float(min_range), C.c_float(max_range),
+                                                               C.c_float(voxel_filter_size), _p(cur, _f32p), C.byref(k)),
+               "dliom_range_accumulator_add_timed_cloud")
+        return cur, k.value
+
     def finish(self, voxel_filter_size):
         h = _vp()
         org = np.zeros(3, dtype=np.float32)
@@ -3206,6 +3219,13 @@ SYMBOLS += [
     ("dliom_add_range_data_timed_cloud", C.c_int, [_vp, _f64p, _f64p, C.c_double, _vp, _f32p, C.c_float, C.c_float, C.c_float,
                                                    C.POINTER(_vp), _f32p, _f32p]),
     ("dliom_points_batch_from_timed_cloud", C.c_int, [_vp, _vp, C.c_int64, _vp, _f64p, C.POINTER(_vp)]),
+    # two range sensors' clouds merged on the device (range_sync.hip)
+    ("dliom_timed_cloud_has_origin_index", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("dliom_timed_cloud_download_origin_index", C.c_int, [_vp, _f32p]),
+    ("dliom_timed_cloud_stamp", C.c_int, [_vp, _vp, C.c_double, C.POINTER(_vp)]),
+    ("dliom_timed_clouds_merge", C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(_vp)]),
+    ("dliom_range_accumulator_add_timed_cloud", C.c_int, [_vp, _f64p, _f64p, C.c_double, _vp, _f32p, C.c_int, C.c_float, C.c_float,
+                                                          C.c_float, _f32p, C.POINTER(C.c_int)]),
 ]
 
 
@@ -3292,7 +3312,36 @@ class TimedCloud:
                "dliom_points_batch_from_timed_cloud")
         return PointsBatch(self.ctx, _handle=h) if h else None
 
+    @property
+    def has_origin_index(self):
+        v = C.c_int()
+        _check(self._L.dliom_timed_cloud_has_origin_index(self.h, C.byref(v)), "dliom_timed_cloud_has_origin_index")
+        return bool(v.value)
+
+    def download_origin_index(self):
+        """-> float32 (n,): the origin index of every point of a merge's result"""
+        oi = np.zeros(len(self), np.float32)
+        _check(self._L.dliom_timed_cloud_download_origin_index(self.h, _p(oi, _f32p)), "dliom_timed_cloud_download_origin_index")
+        return oi
+
+    def stamp(self, scan_period):
+        """dliom_timed_cloud_stamp (StampRangeData) -> TimedCloud"""
+        h = _vp()
+        _check(self._L.dliom_timed_cloud_stamp(self.ctx.h, self.h, float(scan_period), C.byref(h)), "dliom_timed_cloud_stamp")
+        return TimedCloud(self.ctx, h)
+
     def close(self):
         if self.h is not None:
             self._L.dliom_timed_cloud_destroy(self.h)
             self.h = None
+
+
+def merge_timed_clouds(ctx, primary, primary_time, secondary, secondary_time, primary_for_times=None):
+    """dliom_timed_clouds_merge: the prior lidar's cloud with the overlapping part of the secondary's merged in, in
+    std::sort's order of the times -> TimedCloud with the origin-index channel.  primary_for_times: the stamped copy of
+    `primary` under manual de-skew."""
+    h = _vp()
+    _check(ctx._L.dliom_timed_clouds_merge(ctx.h, primary.h, None if primary_for_times is None else primary_for_times.h,
+                                           int(primary_time), secondary.h, int(secondary_time), C.byref(h)),
+           "dliom_timed_clouds_merge")
+    return TimedCloud(ctx, h)

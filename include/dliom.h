@@ -2069,6 +2069,58 @@ int dliom_points_batch_from_timed_cloud(dliom_ctx* ctx, dliom_trajectory* trajec
                                         const dliom_timed_cloud* points, const double sensor_to_tracking[7],
                                         dliom_points_batch** out);
 
+/* ---- Two range sensors' clouds merged on the device (mapping/internal/3d/range_data_synchronizer.cc:29-130) ----
+ * The RangeDataSynchronizer's per-point work on decoded messages, so that a second lidar, manual de-skew and accumulation
+ * keep the ranges in HBM.  Which cloud is pending, when one is dropped as too old, "the secondary lidar may be too fast" and
+ * the pass-through stay the caller's (cpp/dliom_cartographer.h): they need only stamps and first times, which the objects
+ * carry.  The statement below defines the result; the device equals a CPU model of it (tests/range_sync_common.py) and the
+ * adapter's host class bit for bit, in the same point order.
+ *
+ * Seconds(time) = double((time - 719162 * 86400 * 10^7) * 100) * 1e-9: common::ToSecondsStamp of universal-time ticks,
+ * the subtraction and the product in int64.
+ *
+ * _stamp: StampRangeData (:115-130).  n < 2: a copy.  Otherwise
+ *       t_i = float(-scan_period + double(i) * (scan_period / double(n - 1)))    the product is never fused with the sum
+ *   and the last point's t = 0; x, y, z are copied.  First and last t are known on the host without a read-back.
+ *
+ * _merge: the branch at :69-111.  `primary` is the prior lidar's cloud, stamped primary_time; `primary_for_times` its
+ * stamped copy under manual de-skew (same size) and NULL otherwise; `secondary` the pending cloud of the other lidar.
+ *   current_end   = Seconds(primary_time)
+ *   current_start = current_end + double(t of the first point of primary_for_times, or of primary when that is NULL),
+ *                   current_end for an empty primary
+ *   st            = Seconds(secondary_time)
+ *   i_start       = the first i with current_start <= st + double(t_i) <= current_end, both bounds inclusive
+ *   i_end + 1     = the first i > i_start with st + double(t_i) > current_end, or the secondary's size if there is none
+ * The merged array is every point of `primary` as it is -- under manual de-skew with its UNSTAMPED t, as :94 takes them --
+ * with origin index 0, then the secondary's points i_start .. i_end with origin index 1 and
+ *       t = float((double(t_i) + st) - current_end),
+ * and the result is that array in the order libstdc++'s std::sort leaves it in when it compares by t alone: where times
+ * are equal (an Ouster column holds 64 or 128 of them) the order is what introsort's partitions make of it, and it decides
+ * which point of a voxel AddRangeData's first filter keeps.  *out holds the points and the origin-index channel, one float
+ * a point; its first and last t are known on the host.
+ * Refused, leaving no object and the context usable: no i_start (the reference's CHECK at :84; also an empty secondary)
+ * with DLIOM_ERR_INVALID_ARGUMENT; an arrangement of equal times the sort's replay refuses (dliom_diag_std_sort_order: its
+ * work-list cap, the heap-sort fallback of a large segment) or more than 2^22 merged points with DLIOM_ERR_CAPACITY --
+ * the caller then merges that scan on the host.  Inputs must be this context's and carry neither intensities nor the
+ * origin-index channel.  Two read-backs a merge: the overlap's bounds, then the sort's status with the first and last t.
+ *
+ * An object with the channel is input to dliom_range_accumulator_add_timed_cloud only: dliom_add_range_data_timed_cloud
+ * and dliom_points_batch_from_timed_cloud refuse it with DLIOM_ERR_INVALID_ARGUMENT. */
+int dliom_timed_cloud_has_origin_index(const dliom_timed_cloud* cloud, int* has);
+/* origin_index: n floats.  An object without the channel is refused. */
+int dliom_timed_cloud_download_origin_index(const dliom_timed_cloud* cloud, float* origin_index);
+int dliom_timed_cloud_stamp(dliom_ctx* ctx, const dliom_timed_cloud* in, double scan_period, dliom_timed_cloud** out);
+int dliom_timed_clouds_merge(dliom_ctx* ctx, const dliom_timed_cloud* primary, const dliom_timed_cloud* primary_for_times,
+                             int64_t primary_time, const dliom_timed_cloud* secondary, int64_t secondary_time,
+                             dliom_timed_cloud** out);
+/* dliom_range_accumulator_add with ranges_xyzt, origin_index and n taken from a device object -- a decoded message
+ * (origin index 0 throughout) or a merge's result; `origins` stays the caller's table.  Results, read-back count and
+ * refusals are those of the host-input call. */
+int dliom_range_accumulator_add_timed_cloud(dliom_range_accumulator* accumulator, const double prev_pose[7],
+                                            const double predicted_pose[7], double scan_period, const dliom_timed_cloud* ranges,
+                                            const float* origins, int num_origins, float min_range, float max_range,
+                                            float voxel_filter_size, float current_pose[7], int* num_accumulated);
+
 /* Kernel timing (HIP events on the context's stream). */
 enum {
   DLIOM_KERNEL_RTCSM_SCORE = 0, /* score-volume kernel (dominant) */
