@@ -999,12 +999,19 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   constexpr int64_t observation_stride = sizeof(dliom_pose_graph_landmark_observation) / sizeof(int32_t);
   static_assert(sizeof(dliom_pose_graph_landmark_observation) % sizeof(int32_t) == 0, "the observations are read with an int32 stride");
   const int32_t* observation_first = reinterpret_cast<const int32_t*>(observations);
-  const int status = pg::build_structure_landmarks(num_submaps, submap_constant, gravity_aligned_submap, num_frames, num_nodes,
-                                                   node_constant, num_constraints, first, first + 1, stride, num_frame_constraints,
-                                                   frame_first, frame_first + 1, stride, num_landmarks, landmarks->landmark_constant,
-                                                   num_observations, observation_first, observation_first + 1, observation_first + 2,
-                                                   observation_stride, options->fix_z_in_3d != 0,
-                                                   DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION, &s);
+  pg::Indices in;
+  in.num_submaps = num_submaps, in.submap_constant = submap_constant, in.gravity_aligned_submap = gravity_aligned_submap;
+  in.num_fixed_frames = num_frames;
+  in.num_nodes = num_nodes, in.node_constant = node_constant;
+  in.num_constraints = num_constraints, in.constraint_submap = first, in.constraint_node = first + 1, in.constraint_stride = stride;
+  in.num_frame_constraints = num_frame_constraints, in.frame_constraint_frame = frame_first, in.frame_constraint_node = frame_first + 1;
+  in.frame_constraint_stride = stride;
+  in.num_landmarks = num_landmarks, in.landmark_constant = landmarks->landmark_constant;
+  in.num_observations = num_observations, in.observation_landmark = observation_first, in.observation_prev = observation_first + 1;
+  in.observation_next = observation_first + 2, in.observation_stride = observation_stride;
+  in.fix_z = options->fix_z_in_3d != 0;
+  in.max_reduced_dimension = DLIOM_POSE_GRAPH_MAX_REDUCED_DIMENSION;
+  const int status = pg::build_structure(in, &s);
   if (status == pg::kStructureBadIndex) return DLIOM_ERR_INVALID_ARGUMENT;
   if (status == pg::kStructureTooLarge) return DLIOM_ERR_TOO_LARGE;
   if (!all_finite(submap_poses7, 7 * static_cast<int64_t>(num_submaps)) || !all_finite(node_poses7, 7 * static_cast<int64_t>(num_nodes)))
@@ -1039,13 +1046,16 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   g.n = s.reduced_dimension;
   g.np = std::max(kPanel, (g.n + kPanel - 1) / kPanel * kPanel);
   // one host buffer, one copy: [constraint data | poses | int arrays] (a vector of doubles; the ints ride in its tail)
-  // with landmarks `column` covers every pose
-  const std::vector<int32_t>& column = with_landmarks ? s.pose_column : s.column;
-  const size_t num_ints = (with_loss ? 3 : 2) * static_cast<size_t>(C) + s.kind.size() + s.mask.size() + column.size() + s.fixed.size() + s.pose_start.size() +
+  // Without landmarks and observations the device sees the columns of the submaps and the fixed frames only, and none
+  // of the observations' and the direct terms' lists: node_promoted and pair_direct_start stay null, and the kernels
+  // branch on that.
+  const size_t num_columns = 6 * static_cast<size_t>(with_landmarks ? poses : kept);
+  size_t num_ints = (with_loss ? 3 : 2) * static_cast<size_t>(C) + s.kind.size() + s.mask.size() + num_columns + s.fixed.size() + s.pose_start.size() +
                           s.pose_constraints.size() + s.pair_a.size() + s.pair_b.size() + s.pair_start.size() + s.pair_c.size() +
-                          s.pair_c2.size() + 1 + 3 * static_cast<size_t>(O) + s.observation_fixed.size() + s.node_promoted.size() +
-                          s.pose_observation_start.size() + s.pose_observations.size() + s.pair_direct_start.size() +
-                          s.pair_direct_a.size() + s.pair_direct_b.size();
+                          s.pair_c2.size() + 1 + 3 * static_cast<size_t>(O);
+  if (with_landmarks)
+    num_ints += s.observation_fixed.size() + s.node_promoted.size() + s.pose_observation_start.size() + s.pose_observations.size() +
+                s.pair_direct_start.size() + s.pair_direct_a.size() + s.pair_direct_b.size();
   const size_t upload_doubles = static_cast<size_t>(9 * C + 7 * poses + 10 * O);
   std::vector<double> host(upload_doubles + (num_ints + 1) / 2);
   for (int64_t c = 0; c < C; ++c) {
@@ -1066,10 +1076,10 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   }
   int32_t* host_ints = reinterpret_cast<int32_t*>(host.data() + upload_doubles);
   size_t ints_used = 0;
-  auto append = [&](const std::vector<int32_t>& v) {
-    const size_t at = ints_used;
-    if (!v.empty()) std::memcpy(host_ints + at, v.data(), v.size() * sizeof(int32_t));
-    ints_used += v.size();
+  auto append = [&](const std::vector<int32_t>& v, size_t at_most = SIZE_MAX) {
+    const size_t at = ints_used, count = std::min(v.size(), at_most);
+    if (count > 0) std::memcpy(host_ints + at, v.data(), count * sizeof(int32_t));
+    ints_used += count;
     return at;
   };
   const size_t at_submap = ints_used;
@@ -1080,7 +1090,7 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
   if (with_loss)
     for (int64_t c = 0; c < C; ++c) host_ints[ints_used++] = c < num_constraints && terms->inter_submap[c] != 0 ? 1 : 0;
   const size_t at_kind = append(s.kind);
-  const size_t at_mask = append(s.mask), at_column = append(column), at_fixed = append(s.fixed), at_start = append(s.pose_start),
+  const size_t at_mask = append(s.mask), at_column = append(s.column, num_columns), at_fixed = append(s.fixed), at_start = append(s.pose_start),
                at_list = append(s.pose_constraints), at_a = append(s.pair_a), at_b = append(s.pair_b),
                at_pair_start = append(s.pair_start), at_c = append(s.pair_c), at_c2 = append(s.pair_c2);
   host_ints[ints_used++] = 0;
@@ -1090,9 +1100,12 @@ int prepare(dliom_ctx* ctx, const dliom_pose_graph_options* options, int num_sub
     host_ints[ints_used++] = static_cast<int32_t>(kept) + observations[o].next_node;
     host_ints[ints_used++] = static_cast<int32_t>(kept) + num_nodes + observations[o].landmark;
   }
-  const size_t at_observation_fixed = append(s.observation_fixed), at_promoted = append(s.node_promoted),
-               at_observation_start = append(s.pose_observation_start), at_observation_list = append(s.pose_observations),
-               at_direct_start = append(s.pair_direct_start), at_direct_a = append(s.pair_direct_a), at_direct_b = append(s.pair_direct_b);
+  const size_t landmark_ints = with_landmarks ? SIZE_MAX : 0;
+  const size_t at_observation_fixed = append(s.observation_fixed, landmark_ints), at_promoted = append(s.node_promoted, landmark_ints),
+               at_observation_start = append(s.pose_observation_start, landmark_ints),
+               at_observation_list = append(s.pose_observations, landmark_ints),
+               at_direct_start = append(s.pair_direct_start, landmark_ints), at_direct_a = append(s.pair_direct_a, landmark_ints),
+               at_direct_b = append(s.pair_direct_b, landmark_ints);
 
   // the device block: doubles, then the ints
   int64_t doubles = 0;

@@ -1,18 +1,38 @@
 // CPU model of the pose graph solve (test infrastructure, NOT product code): OptimizationProblem3D::Solve of the
-// reference's fork (mapping/internal/optimization/optimization_problem_3d.cc:259-589: SpaCostFunction3D only) on the
-// oracle's restatement of Ceres 1.13 (oracle/src/om_jet.h, om_ceres.h, included unmodified).
+// reference's fork (mapping/internal/optimization/optimization_problem_3d.cc:124-186 and :259-589, upstream's :335-338)
+// on the oracle's restatement of Ceres 1.13 (oracle/src/om_jet.h, om_ceres.h, included unmodified).
 //   * residual: the functor of cost_functions/cost_helpers_impl.h:57-101 with transform/transform.h:59-81 on Jet<14>
 //     (submap rotation 0..3, submap translation 4..6, node rotation 7..10, node translation 11..13, the order of
-//     SpaCostFunction3D's parameter blocks); sqrt / atan2 / sin of a Jet are added here (ceres/jet.h);
-//   * local parameterisations: QuaternionParameterization, SubsetParameterization(3, {2}) under fix_z, the autodiff
-//     Jacobian of ConstantYawQuaternionPlus (rotation_parameterization.h:41-62) for the gravity-aligned submap;
+//     SpaCostFunction3D's parameter blocks); sqrt / atan2 / sin / acos / abs of a Jet are added here (ceres/jet.h);
+//   * local parameterisations, a kind per submap and fixed frame: QuaternionParameterization, SubsetParameterization(3,
+//     {2}) under fix_z, the autodiff Jacobian of ConstantYawQuaternionPlus (rotation_parameterization.h:41-62) for the
+//     gravity-aligned submap, YawOnlyQuaternionPlus for a fixed frame (:27-39: one column, slot 3, the step clamped to
+//     +-0.5);
+//   * fixed-frame blocks behind the submaps (translation without a parameterisation: mask 15 also under fix_z; never
+//     constant) and their constraints behind the constraints, the same SpaCostFunction3D;
+//   * ceres::HuberLoss and Corrector (Ceres 1.13 loss_function.cc, corrector.cc, residual_block.cc -- third-party
+//     behaviour, restated) in the residual block's evaluation: after the tangent-space Jacobian is formed, s = ||r||^2,
+//     the Jacobian and then the residual scaled by sqrt(rho'), the block's cost 1/2 rho;
+//   * landmark blocks behind the nodes (translation without a parameterisation: six columns also under fix_z;
+//     QuaternionParameterization) and one LandmarkCostFunction3D a used observation behind the other residual blocks,
+//     without a loss.  The functor has the reference's shape (landmark_cost_function_3d.h:55-75 on cost_helpers_impl.h:
+//     57-153) and runs on Jets over its 21 parameters;
 //   * what leaves the reduced problem (Ceres' Program::RemoveFixedBlocks, third-party behaviour restated): constant
 //     blocks, blocks no remaining residual uses, residuals whose blocks are all constant (-> fixed cost);
+//   * the promoted layout: a non-constant node that a remaining observation names is a kept block.  The columns are the
+//     submaps', the fixed frames', the promoted nodes', the landmarks', then the eliminated nodes'.  A residual block
+//     between kept blocks only (a constraint of a promoted node, an observation) adds its J^T J to the reduced system
+//     directly (eliminated normal equations) or joins the kept blocks' dense problem as six rows (structured QR);
 //   * minimiser: om_ceres.h's Solve generalised to many blocks, with its LevenbergMarquardtStrategy and
 //     TrustRegionStepEvaluator; three linear solvers: the strategy's own dense QR of [J; D] (solver 0), normal
 //     equations with the nodes eliminated (solver 1), and the Householder QR of [J; D] with the nodes' columns first and
 //     the operations on structural zeros left out (solver 2: no J^T J, no Cholesky; affordable on every case).
+// Zero fixed frames, landmarks and observations and a zero huber_scale are ordinary values.  Honesty margins of a solve:
+// loss_margin, the least |s - b| / b over the tagged constraints at every evaluated point; clamp_margin, the least
+// ||delta| - 0.5| / 0.5 over every yaw step; slerp_margin, the least distance of |cos theta| from 1 - 1e-5 and of
+// cos theta from 0 over every evaluated observation; each 1e300 where its term is absent.
 // usage: pose_graph_model <in> <out> | pose_graph_model --reduces-noise <out-problem>
+#include <cfloat>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -49,6 +69,18 @@ Jet<N> sin(const Jet<N>& f) {
   return r;
 }
 template <int N>
+Jet<N> acos(const Jet<N>& f) {
+  Jet<N> r;
+  r.a = std::acos(f.a);
+  const double tmp = -1.0 / std::sqrt(1.0 - f.a * f.a);
+  for (int i = 0; i < N; ++i) r.v[i] = tmp * f.v[i];
+  return r;
+}
+template <int N>
+Jet<N> abs(const Jet<N>& f) {
+  return f.a < 0.0 ? -f : f;
+}
+template <int N>
 bool operator<(const Jet<N>& f, double s) {
   return f.a < s;
 }
@@ -59,6 +91,8 @@ using oracle::ceres_like::DenseMatrix;
 using oracle::ceres_like::LevenbergMarquardtStrategy;
 using oracle::ceres_like::Options;
 using oracle::ceres_like::TrustRegionStepEvaluator;
+using std::abs;
+using std::acos;
 using std::atan2;
 using std::sin;
 using std::sqrt;
@@ -72,6 +106,11 @@ double Make<double>(double v) {
 template <>
 oracle::Jet<14> Make<oracle::Jet<14>>(double v) {
   return oracle::Jet<14>(v);
+}
+
+template <>
+oracle::Jet<21> Make<oracle::Jet<21>>(double v) {
+  return oracle::Jet<21>(v);
 }
 
 template <typename T>
@@ -129,6 +168,48 @@ void SpaResidual(const double zbar[7], double translation_weight, double rotatio
   }
 }
 
+// SlerpQuaternions and InterpolateNodes3D (cost_helpers_impl.h:103-153); *cos_theta_out: the scalar part, for the margin
+template <typename T>
+void InterpolateNodes3D(const T* prev_rotation, const T* prev_translation, const T* next_rotation, const T* next_translation,
+                        double factor, T rotation[4], T translation[3], double* cos_theta_out) {
+  const T* start = prev_rotation;
+  const T* end = next_rotation;
+  const T cos_theta = start[0] * end[0] + start[1] * end[1] + start[2] * end[2] + start[3] * end[3];
+  *cos_theta_out = oracle::ScalarPart(cos_theta);
+  const T abs_cos_theta = abs(cos_theta);
+  T prev_scale = Make<T>(1. - factor);
+  T next_scale = Make<T>(factor);
+  if (abs_cos_theta < 1. - 1e-5) {
+    const T theta = acos(abs_cos_theta);
+    const T sin_theta = sin(theta);
+    prev_scale = sin((1. - factor) * theta) / sin_theta;
+    next_scale = sin(factor * theta) / sin_theta;
+  }
+  if (cos_theta < 0.) next_scale = -next_scale;
+  for (int k = 0; k < 4; ++k) rotation[k] = prev_scale * start[k] + next_scale * end[k];
+  for (int k = 0; k < 3; ++k) translation[k] = prev_translation[k] + factor * (next_translation[k] - prev_translation[k]);
+}
+// LandmarkCostFunction3D::operator() (landmark_cost_function_3d.h:55-75): ComputeUnscaledError's start is the interpolated
+// pose, its end the landmark
+template <typename T>
+void LandmarkResidual(const double landmark_to_tracking[7], double translation_weight, double rotation_weight, double factor,
+                      const T* prev_rotation, const T* prev_translation, const T* next_rotation, const T* next_translation,
+                      const T* landmark_rotation, const T* landmark_translation, T* e, double* cos_theta) {
+  T rotation[4], translation[3];
+  InterpolateNodes3D(prev_rotation, prev_translation, next_rotation, next_translation, factor, rotation, translation, cos_theta);
+  SpaResidual<T>(landmark_to_tracking, translation_weight, rotation_weight, rotation, translation, landmark_rotation,
+                 landmark_translation, e);
+}
+
+struct Observation {
+  int32_t landmark, prev_node, next_node;
+  int32_t pad;
+  double interpolation_parameter;
+  double landmark_to_tracking[7];
+  double translation_weight, rotation_weight;
+};
+static_assert(sizeof(Observation) == 96, "the layout of dliom_pose_graph_landmark_observation");
+
 struct Constraint {
   int32_t submap, node;
   double zbar[7];
@@ -137,8 +218,23 @@ struct Constraint {
 static_assert(sizeof(Constraint) == 80, "the layout of dliom_pose_graph_constraint");
 
 struct Graph {
-  int S = 0, N = 0, gravity = -1, fix_z = 0;
-  std::vector<double> x;  // 7 a pose [t, q], submaps first
+  int S = 0, N = 0, gravity = -1, fix_z = 0;  // S: the submaps and then the fixed frames
+  int L = 0;                                  // landmarks: poses S + N ..
+  std::vector<Observation> observations;      // residual blocks constraints.size() ..
+  std::vector<char> observation_fixed, promoted;  // promoted: per node
+  mutable double slerp_margin = 1e300;
+  int P() const { return S + N + L; }
+  bool Kept(int p) const { return p < S || p >= S + N || promoted[p - S]; }
+  int ObservedPose(const Observation& o, int which) const { return which == 2 ? S + N + o.landmark : S + (which == 0 ? o.prev_node : o.next_node); }
+  void SlerpMargin(double cos_theta) const {
+    slerp_margin = std::min(slerp_margin, std::min(std::fabs(std::fabs(cos_theta) - (1. - 1e-5)), std::fabs(cos_theta)));
+  }
+  int submaps = 0;                            // how many of the kept blocks are submaps
+  double huber_scale = 0;
+  std::vector<char> lossy;                    // per constraint (the fixed frames' follow the submaps', submap = kept index)
+  mutable double loss_margin = 1e300, clamp_margin = 1e300;
+  int clamped_steps = 0;                      // yaw steps beyond +-0.5
+  std::vector<double> x;  // 7 a pose [t, q], kept blocks first
   std::vector<int32_t> constant;
   std::vector<Constraint> constraints;
   // derived
@@ -147,13 +243,26 @@ struct Graph {
   std::vector<char> fixed;
   std::vector<int> rows;      // the constraints that stay
   int num_eff = 0;
+  enum { kQuaternion = 0, kConstantYaw = 1, kYawOnly = 2 };
+  int Kind(int p) const { return p == gravity ? kConstantYaw : (p >= submaps && p < S ? kYawOnly : kQuaternion); }
+  // 1/2 rho(s) of constraint c and the corrector's scaling sqrt(rho') (rho'' <= 0: a pure scaling)
+  double Loss(int c, double s, double* scaling) const {
+    *scaling = 1.;
+    if (!(huber_scale > 0.) || !lossy[c]) return 0.5 * s;
+    const double b = huber_scale * huber_scale;
+    loss_margin = std::min(loss_margin, std::fabs(s - b) / b);
+    if (s <= b) return 0.5 * s;
+    const double r = std::sqrt(s);
+    *scaling = std::sqrt(std::max(DBL_MIN, huber_scale / r));
+    return 0.5 * (2. * huber_scale * r - b);
+  }
 
   void Derive() {
-    const int P = S + N;
+    const int P = S + N + L;
     mask.assign(P, 0);
     for (int p = 0; p < P; ++p) {
       if (constant[p]) continue;
-      mask[p] = p == gravity ? 24 : ((fix_z ? 3 : 7) | 56);
+      mask[p] = p == gravity ? 24 : (p >= submaps && p < S ? 15 : p >= S + N ? 63 : ((fix_z ? 3 : 7) | 56));
     }
     std::vector<int> used(P, 0);
     fixed.assign(constraints.size(), 0);
@@ -167,19 +276,41 @@ struct Graph {
       used[a] = used[n] = 1;
       rows.push_back(static_cast<int>(c));
     }
+    observation_fixed.assign(observations.size(), 0);
+    promoted.assign(N, 0);
+    for (size_t o = 0; o < observations.size(); ++o) {
+      const int p[3] = {ObservedPose(observations[o], 0), ObservedPose(observations[o], 1), ObservedPose(observations[o], 2)};
+      if (mask[p[0]] == 0 && mask[p[1]] == 0 && mask[p[2]] == 0) {
+        observation_fixed[o] = 1;
+        continue;
+      }
+      for (int which = 0; which < 3; ++which) {
+        used[p[which]] = 1;
+        if (which < 2 && mask[p[which]] != 0) promoted[p[which] - S] = 1;
+      }
+    }
     column.assign(static_cast<size_t>(P) * 6, -1);
     num_eff = 0;
-    for (int p = 0; p < P; ++p) {
-      if (!used[p]) mask[p] = 0;
-      for (int i = 0; i < 6; ++i)
-        if ((mask[p] >> i) & 1) column[p * 6 + i] = num_eff++;
-    }
+    for (int pass = 0; pass < 2; ++pass)  // the kept blocks' columns, then the eliminated nodes'
+      for (int p = 0; p < P; ++p) {
+        if (Kept(p) != (pass == 0)) continue;
+        if (!used[p]) mask[p] = 0;
+        for (int i = 0; i < 6; ++i)
+          if ((mask[p] >> i) & 1) column[p * 6 + i] = num_eff++;
+      }
   }
 };
 
 // d Plus / d delta at 0, 4 x 3 row-major (third column unused for the gravity-aligned submap)
-void PlusJacobian(const double* q, bool gravity_aligned, double* j) {
-  if (gravity_aligned) {
+void PlusJacobian(const double* q, int kind, double* j) {
+  if (kind == Graph::kYawOnly) {
+    // AutoDiffLocalParameterization<YawOnlyQuaternionPlus, 4, 1> at delta = 0: d sqrt(1 - d^2) = 0, so the column is
+    // [0 0 0 1] (x) q
+    const double e3[4] = {0, 0, 0, 1};
+    double c[4];
+    oracle::ceres_like::QuaternionProductD(e3, q, c);
+    for (int k = 0; k < 4; ++k) j[k * 3] = c[k], j[k * 3 + 1] = 0., j[k * 3 + 2] = 0.;
+  } else if (kind == Graph::kConstantYaw) {
     // AutoDiffLocalParameterization<ConstantYawQuaternionPlus, 4, 2> at delta = 0: the 1e-6 branch makes q_delta =
     // [1, d0, d1, 0], so the columns are q (x) [0 1 0 0] and q (x) [0 0 1 0]
     const double e1[4] = {0, 1, 0, 0}, e2[4] = {0, 0, 1, 0};
@@ -191,11 +322,15 @@ void PlusJacobian(const double* q, bool gravity_aligned, double* j) {
     oracle::ceres_like::QuaternionParameterization().ComputeJacobian(q, j);
   }
 }
-void PosePlus(const double* x, const double* delta, int mask, bool gravity_aligned, double* out) {
+void PosePlus(const double* x, const double* delta, int mask, int kind, double* out) {
   for (int k = 0; k < 3; ++k) out[k] = (mask >> k) & 1 ? x[k] + delta[k] : x[k];
   for (int k = 3; k < 7; ++k) out[k] = x[k];
   if ((mask & 56) == 0) return;
-  if (gravity_aligned) {
+  if (kind == Graph::kYawOnly) {
+    const double clamped = delta[3] > 0.5 ? 0.5 : (delta[3] < -0.5 ? -0.5 : delta[3]);  // common::Clamp
+    const double q_delta[4] = {std::sqrt(1. - clamped * clamped), 0., 0., clamped};
+    oracle::ceres_like::QuaternionProductD(q_delta, x + 3, out + 3);
+  } else if (kind == Graph::kConstantYaw) {
     const double norm = std::sqrt(delta[3] * delta[3] + delta[4] * delta[4]);
     const double sin_over = norm < 1e-6 ? 1. : std::sin(norm) / norm;
     const double q_delta[4] = {norm < 1e-6 ? 1. : std::cos(norm), sin_over * delta[3], sin_over * delta[4], 0.};
@@ -205,9 +340,11 @@ void PosePlus(const double* x, const double* delta, int mask, bool gravity_align
   }
 }
 
-struct RowBlock {  // one constraint's 6 rows in the tangent space, on the slots of its two poses
-  int c;
-  double r[6], js[36], jn[36];
+struct RowBlock {  // one residual block's 6 rows in the tangent space, on the slots of its poses
+  int c;            // constraints, then observations
+  int num, pose[3];  // a constraint: the kept block and the node; an observation: prev, next, the landmark
+  double r[6], j[3][36];
+  bool direct;      // between kept blocks only: never in the elimination
 };
 struct Linearisation {
   double cost = 0, fixed_cost = 0;
@@ -234,6 +371,19 @@ bool Cost(const Graph& g, const std::vector<double>& x, double* cost) {
     Residual(g, x, c, e);
     if (!Finite6(e)) return false;
     for (int k = 0; k < 6; ++k) sq += e[k] * e[k];
+    double scaling;
+    *cost += g.Loss(c, sq, &scaling);
+  }
+  for (size_t o = 0; o < g.observations.size(); ++o) {
+    if (g.observation_fixed[o]) continue;
+    const Observation& k = g.observations[o];
+    const double *a = &x[7 * g.ObservedPose(k, 0)], *b = &x[7 * g.ObservedPose(k, 1)], *l = &x[7 * g.ObservedPose(k, 2)];
+    double e[6], sq = 0, cos_theta;
+    LandmarkResidual<double>(k.landmark_to_tracking, k.translation_weight, k.rotation_weight, k.interpolation_parameter, a + 3, a,
+                             b + 3, b, l + 3, l, e, &cos_theta);
+    g.SlerpMargin(cos_theta);
+    if (!Finite6(e)) return false;
+    for (int i = 0; i < 6; ++i) sq += e[i] * e[i];
     *cost += 0.5 * sq;
   }
   return true;
@@ -242,7 +392,7 @@ bool Linearise(const Graph& g, const std::vector<double>& x, Linearisation* out)
   using J = oracle::Jet<14>;
   out->cost = out->fixed_cost = 0;
   out->blocks.clear();
-  out->all_residuals.assign(g.constraints.size() * 6, 0.);
+  out->all_residuals.assign((g.constraints.size() + g.observations.size()) * 6, 0.);
   for (size_t c = 0; c < g.constraints.size(); ++c) {
     const Constraint& k = g.constraints[c];
     const int pa = k.submap, pn = g.S + k.node;
@@ -254,17 +404,22 @@ bool Linearise(const Graph& g, const std::vector<double>& x, Linearisation* out)
     SpaResidual<J>(k.zbar, k.translation_weight, k.rotation_weight, qi, ti, qj, tj, e);
     RowBlock b;
     b.c = static_cast<int>(c);
+    b.num = 2, b.pose[0] = pa, b.pose[1] = pn, b.pose[2] = -1;
+    b.direct = g.promoted[k.node] != 0;
     double sq = 0;
-    for (int i = 0; i < 6; ++i) b.r[i] = e[i].a, sq += e[i].a * e[i].a, out->all_residuals[6 * c + i] = e[i].a;
+    for (int i = 0; i < 6; ++i) b.r[i] = e[i].a, sq += e[i].a * e[i].a;
     if (!Finite6(b.r)) return false;
+    double scaling;
+    const double cost = g.Loss(static_cast<int>(c), sq, &scaling);
+    for (int i = 0; i < 6; ++i) out->all_residuals[6 * c + i] = e[i].a * scaling;
     if (g.fixed[c]) {
-      out->fixed_cost += 0.5 * sq;
+      out->fixed_cost += cost;
       continue;
     }
-    out->cost += 0.5 * sq;
+    out->cost += cost;
     double ja[12], jn[12];
-    PlusJacobian(a + 3, pa == g.gravity, ja);
-    PlusJacobian(n + 3, false, jn);
+    PlusJacobian(a + 3, g.Kind(pa), ja);
+    PlusJacobian(n + 3, Graph::kQuaternion, jn);
     for (int row = 0; row < 6; ++row)
       for (int slot = 0; slot < 6; ++slot) {
         double vs = 0, vn = 0;
@@ -274,9 +429,56 @@ bool Linearise(const Graph& g, const std::vector<double>& x, Linearisation* out)
         } else {
           for (int q = 0; q < 4; ++q) vs += e[row].v[q] * ja[q * 3 + slot - 3], vn += e[row].v[7 + q] * jn[q * 3 + slot - 3];
         }
-        b.js[row * 6 + slot] = (g.mask[pa] >> slot) & 1 ? vs : 0.;
-        b.jn[row * 6 + slot] = (g.mask[pn] >> slot) & 1 ? vn : 0.;
+        b.j[0][row * 6 + slot] = (g.mask[pa] >> slot) & 1 ? vs : 0.;
+        b.j[1][row * 6 + slot] = (g.mask[pn] >> slot) & 1 ? vn : 0.;
       }
+    // Corrector: the Jacobian first, then the residual
+    for (int k = 0; k < 36; ++k) b.j[0][k] *= scaling, b.j[1][k] *= scaling;
+    for (int k = 0; k < 6; ++k) b.r[k] *= scaling;
+    out->blocks.push_back(b);
+  }
+  using J21 = oracle::Jet<21>;
+  for (size_t o = 0; o < g.observations.size(); ++o) {
+    const Observation& k = g.observations[o];
+    // parameter order of the AutoDiffCostFunction: per pose rotation (4), translation (3)
+    J21 q[3][4], t[3][3], e[6];
+    RowBlock b;
+    b.c = static_cast<int>(g.constraints.size() + o);
+    b.num = 3;
+    b.direct = true;
+    for (int which = 0; which < 3; ++which) {
+      b.pose[which] = g.ObservedPose(k, which);
+      const double* p = &x[7 * b.pose[which]];
+      for (int i = 0; i < 4; ++i) q[which][i] = J21(p[3 + i], 7 * which + i);
+      for (int i = 0; i < 3; ++i) t[which][i] = J21(p[i], 7 * which + 4 + i);
+    }
+    double cos_theta;
+    LandmarkResidual<J21>(k.landmark_to_tracking, k.translation_weight, k.rotation_weight, k.interpolation_parameter, q[0], t[0], q[1],
+                          t[1], q[2], t[2], e, &cos_theta);
+    g.SlerpMargin(cos_theta);
+    double sq = 0;
+    for (int i = 0; i < 6; ++i) b.r[i] = e[i].a, sq += e[i].a * e[i].a;
+    if (!Finite6(b.r)) return false;
+    for (int i = 0; i < 6; ++i) out->all_residuals[6 * b.c + i] = e[i].a;
+    if (g.observation_fixed[o]) {
+      out->fixed_cost += 0.5 * sq;
+      continue;
+    }
+    out->cost += 0.5 * sq;
+    for (int which = 0; which < 3; ++which) {
+      double jq[12];
+      PlusJacobian(&x[7 * b.pose[which] + 3], Graph::kQuaternion, jq);
+      for (int row = 0; row < 6; ++row)
+        for (int slot = 0; slot < 6; ++slot) {
+          double v = 0;
+          if (slot < 3) {
+            v = e[row].v[7 * which + 4 + slot];
+          } else {
+            for (int i = 0; i < 4; ++i) v += e[row].v[7 * which + i] * jq[i * 3 + slot - 3];
+          }
+          b.j[which][row * 6 + slot] = (g.mask[b.pose[which]] >> slot) & 1 ? v : 0.;
+        }
+    }
     out->blocks.push_back(b);
   }
   return true;
@@ -289,14 +491,13 @@ void Dense(const Graph& g, const Linearisation& lin, const std::vector<double>& 
   r->assign(lin.blocks.size() * 6, 0.);
   for (size_t b = 0; b < lin.blocks.size(); ++b) {
     const RowBlock& k = lin.blocks[b];
-    const int pa = g.constraints[k.c].submap, pn = g.S + g.constraints[k.c].node;
     for (int row = 0; row < 6; ++row) {
       (*r)[b * 6 + row] = k.r[row];
-      for (int slot = 0; slot < 6; ++slot) {
-        const int ca = g.column[pa * 6 + slot], cn = g.column[pn * 6 + slot];
-        if (ca >= 0) (*jac)(static_cast<int>(b) * 6 + row, ca) = k.js[row * 6 + slot] * scale[ca];
-        if (cn >= 0) (*jac)(static_cast<int>(b) * 6 + row, cn) = k.jn[row * 6 + slot] * scale[cn];
-      }
+      for (int slot = 0; slot < 6; ++slot)
+        for (int which = 0; which < k.num; ++which) {
+          const int col = g.column[k.pose[which] * 6 + slot];
+          if (col >= 0) (*jac)(static_cast<int>(b) * 6 + row, col) = k.j[which][row * 6 + slot] * scale[col];
+        }
     }
   }
 }
@@ -334,20 +535,37 @@ bool EliminatedStep(const Graph& g, const Linearisation& lin, const std::vector<
                     double max_diagonal, std::vector<double>* step) {
   const int n_all = g.num_eff;
   int ns = 0;  // the submaps' columns come first
-  for (int p = 0; p < g.S; ++p)
-    for (int i = 0; i < 6; ++i) ns += g.column[p * 6 + i] >= 0;
+  for (int p = 0; p < g.P(); ++p)
+    for (int i = 0; i < 6; ++i) ns += g.Kept(p) && g.column[p * 6 + i] >= 0;
   std::vector<double> diagonal(n_all, 0.), gradient(n_all, 0.);
   std::vector<double> S(static_cast<size_t>(ns) * ns, 0.), rhs(ns, 0.);
   std::vector<double> hnn(static_cast<size_t>(g.N) * 36, 0.);
   std::vector<std::vector<int>> of_node(g.N);
-  auto scaled = [&](const RowBlock& k, bool node, int row, int slot) {
-    const int p = node ? g.S + g.constraints[k.c].node : g.constraints[k.c].submap;
-    const int col = g.column[p * 6 + slot];
-    return col < 0 ? 0. : (node ? k.jn : k.js)[row * 6 + slot] * scale[col];
+  auto scaled_at = [&](const RowBlock& k, int which, int row, int slot) {
+    const int col = g.column[k.pose[which] * 6 + slot];
+    return col < 0 ? 0. : k.j[which][row * 6 + slot] * scale[col];
   };
+  auto scaled = [&](const RowBlock& k, bool node, int row, int slot) { return scaled_at(k, node ? 1 : 0, row, slot); };
   for (size_t b = 0; b < lin.blocks.size(); ++b) {
     const RowBlock& k = lin.blocks[b];
-    const int pa = g.constraints[k.c].submap, node = g.constraints[k.c].node;
+    if (k.direct) {  // J^T J and J^T r of a block between kept blocks, straight into the reduced system
+      for (int x = 0; x < k.num; ++x)
+        for (int i = 0; i < 6; ++i) {
+          const int ci = g.column[k.pose[x] * 6 + i];
+          if (ci < 0) continue;
+          for (int row = 0; row < 6; ++row) gradient[ci] += scaled_at(k, x, row, i) * k.r[row];
+          for (int y = 0; y < k.num; ++y)
+            for (int j = 0; j < 6; ++j) {
+              const int cj = g.column[k.pose[y] * 6 + j];
+              if (cj < 0) continue;
+              double t = 0;
+              for (int row = 0; row < 6; ++row) t += scaled_at(k, x, row, i) * scaled_at(k, y, row, j);
+              S[static_cast<size_t>(ci) * ns + cj] += t;
+            }
+        }
+      continue;
+    }
+    const int pa = k.pose[0], node = (k.pose[1] - g.S);
     of_node[node].push_back(static_cast<int>(b));
     for (int i = 0; i < 6; ++i) {
       const int ci = g.column[pa * 6 + i], cn = g.column[(g.S + node) * 6 + i];
@@ -367,7 +585,7 @@ bool EliminatedStep(const Graph& g, const Linearisation& lin, const std::vector<
   for (int c = 0; c < ns; ++c) diagonal[c] = S[static_cast<size_t>(c) * ns + c];
   for (int node = 0; node < g.N; ++node)
     for (int i = 0; i < 6; ++i)
-      if (g.column[(g.S + node) * 6 + i] >= 0) diagonal[g.column[(g.S + node) * 6 + i]] = hnn[static_cast<size_t>(node) * 36 + i * 7];
+      if (!g.promoted[node] && g.column[(g.S + node) * 6 + i] >= 0) diagonal[g.column[(g.S + node) * 6 + i]] = hnn[static_cast<size_t>(node) * 36 + i * 7];
   for (int c = 0; c < n_all; ++c) diagonal[c] = std::min(std::max(diagonal[c], min_diagonal), max_diagonal) / radius;
   for (int c = 0; c < ns; ++c) S[static_cast<size_t>(c) * ns + c] += diagonal[c], rhs[c] = -gradient[c];
   std::vector<double> V(static_cast<size_t>(g.N) * 36, 0.);
@@ -406,7 +624,7 @@ bool EliminatedStep(const Graph& g, const Linearisation& lin, const std::vector<
           for (int q = 0; q < 6; ++q) t += w1[i * 6 + q] * V[static_cast<size_t>(node) * 36 + q * 6 + j];
           w1v[i * 6 + j] = t;
         }
-      const int pa = g.constraints[k1.c].submap;
+      const int pa = k1.pose[0];
       for (int i = 0; i < 6; ++i) {
         const int ci = g.column[pa * 6 + i];
         if (ci < 0) continue;
@@ -414,7 +632,7 @@ bool EliminatedStep(const Graph& g, const Linearisation& lin, const std::vector<
       }
       for (int b2 : of_node[node]) {
         const RowBlock& k2 = lin.blocks[b2];
-        const int pb = g.constraints[k2.c].submap;
+        const int pb = k2.pose[0];
         for (int i = 0; i < 6; ++i) {
           const int ci = g.column[pa * 6 + i];
           if (ci < 0) continue;
@@ -442,7 +660,7 @@ bool EliminatedStep(const Graph& g, const Linearisation& lin, const std::vector<
     for (int j = 0; j < 6; ++j) w[j] = g.column[(g.S + node) * 6 + j] >= 0 ? gradient[g.column[(g.S + node) * 6 + j]] : 0.;
     for (int b : of_node[node]) {
       const RowBlock& k = lin.blocks[b];
-      const int pa = g.constraints[k.c].submap;
+      const int pa = k.pose[0];
       for (int i = 0; i < 6; ++i) {
         const int ci = g.column[pa * 6 + i];
         if (ci < 0) continue;
@@ -506,25 +724,24 @@ bool SparseQrStep(const Graph& g, const Linearisation& lin, const std::vector<do
                   double max_diagonal, std::vector<double>* step) {
   const int n_all = g.num_eff;
   int ns = 0;
-  for (int p = 0; p < g.S; ++p)
-    for (int i = 0; i < 6; ++i) ns += g.column[p * 6 + i] >= 0;
+  for (int p = 0; p < g.P(); ++p)
+    for (int i = 0; i < 6; ++i) ns += g.Kept(p) && g.column[p * 6 + i] >= 0;
   std::vector<double> diagonal(n_all, 0.);
   std::vector<std::vector<int>> of_node(g.N);
-  auto scaled = [&](const RowBlock& k, bool node, int row, int slot) {
-    const int p = node ? g.S + g.constraints[k.c].node : g.constraints[k.c].submap;
-    const int col = g.column[p * 6 + slot];
-    return col < 0 ? 0. : (node ? k.jn : k.js)[row * 6 + slot] * scale[col];
+  auto scaled_at = [&](const RowBlock& k, int which, int row, int slot) {
+    const int col = g.column[k.pose[which] * 6 + slot];
+    return col < 0 ? 0. : k.j[which][row * 6 + slot] * scale[col];
   };
+  auto scaled = [&](const RowBlock& k, bool node, int row, int slot) { return scaled_at(k, node ? 1 : 0, row, slot); };
   for (size_t b = 0; b < lin.blocks.size(); ++b) {
     const RowBlock& k = lin.blocks[b];
-    of_node[g.constraints[k.c].node].push_back(static_cast<int>(b));
-    for (int slot = 0; slot < 6; ++slot) {
-      const int ca = g.column[g.constraints[k.c].submap * 6 + slot], cn = g.column[(g.S + g.constraints[k.c].node) * 6 + slot];
-      for (int row = 0; row < 6; ++row) {
-        if (ca >= 0) diagonal[ca] += scaled(k, false, row, slot) * scaled(k, false, row, slot);
-        if (cn >= 0) diagonal[cn] += scaled(k, true, row, slot) * scaled(k, true, row, slot);
+    if (!k.direct) of_node[(k.pose[1] - g.S)].push_back(static_cast<int>(b));
+    for (int which = 0; which < k.num; ++which)
+      for (int slot = 0; slot < 6; ++slot) {
+        const int col = g.column[k.pose[which] * 6 + slot];
+        if (col < 0) continue;
+        for (int row = 0; row < 6; ++row) diagonal[col] += scaled_at(k, which, row, slot) * scaled_at(k, which, row, slot);
       }
-    }
   }
   std::vector<double> lm(n_all);
   for (int c = 0; c < n_all; ++c) lm[c] = std::sqrt(std::min(std::max(diagonal[c], min_diagonal), max_diagonal) / radius);
@@ -543,7 +760,7 @@ bool SparseQrStep(const Graph& g, const Linearisation& lin, const std::vector<do
       if (g.column[(g.S + node) * 6 + i] >= 0) f.node_cols.push_back(i);
     f.m = static_cast<int>(f.node_cols.size());
     for (int b : of_node[node]) {
-      const int pa = g.constraints[lin.blocks[b].c].submap;
+      const int pa = lin.blocks[b].pose[0];
       for (int i = 0; i < 6; ++i) {
         const int c = g.column[pa * 6 + i];
         if (c >= 0 && std::find(f.submap_cols.begin(), f.submap_cols.end(), c) == f.submap_cols.end()) f.submap_cols.push_back(c);
@@ -556,7 +773,7 @@ bool SparseQrStep(const Graph& g, const Linearisation& lin, const std::vector<do
     int row0 = 0;
     for (int b : of_node[node]) {
       const RowBlock& k = lin.blocks[b];
-      const int pa = g.constraints[k.c].submap;
+      const int pa = k.pose[0];
       for (int row = 0; row < 6; ++row) {
         for (int j = 0; j < f.m; ++j) at(row0 + row, j) = scaled(k, true, row, f.node_cols[j]);
         for (int i = 0; i < 6; ++i) {
@@ -578,6 +795,18 @@ bool SparseQrStep(const Graph& g, const Linearisation& lin, const std::vector<do
       std::vector<double> dense(ns + 1, 0.);
       for (int j = 0; j < f.q; ++j) dense[f.submap_cols[j]] = at(i, f.m + j);
       dense[ns] = at(i, cols - 1);
+      reduced_rows.push_back(dense);
+    }
+  }
+  // a block between kept blocks only: its six rows as they are
+  for (const RowBlock& k : lin.blocks) {
+    if (!k.direct) continue;
+    for (int row = 0; row < 6; ++row) {
+      std::vector<double> dense(ns + 1, 0.);
+      for (int which = 0; which < k.num; ++which)
+        for (int slot = 0; slot < 6; ++slot)
+          if (g.column[k.pose[which] * 6 + slot] >= 0) dense[g.column[k.pose[which] * 6 + slot]] = scaled_at(k, which, row, slot);
+      dense[ns] = k.r[row];
       reduced_rows.push_back(dense);
     }
   }
@@ -636,7 +865,7 @@ struct State {
 };
 double ReducedNorm(const Graph& g, const std::vector<double>& x) {
   double s = 0;
-  for (int p = 0; p < g.S + g.N; ++p) {
+  for (int p = 0; p < g.P(); ++p) {
     if (g.mask[p] & 7)
       for (int k = 0; k < 3; ++k) s += x[7 * p + k] * x[7 * p + k];
     if (g.mask[p] & 56)
@@ -645,7 +874,7 @@ double ReducedNorm(const Graph& g, const std::vector<double>& x) {
   return std::sqrt(s);
 }
 void SlotsFromColumns(const Graph& g, const std::vector<double>& v, std::vector<double>* slots) {
-  slots->assign(static_cast<size_t>(g.S + g.N) * 6, 0.);
+  slots->assign(static_cast<size_t>(g.P()) * 6, 0.);
   for (size_t i = 0; i < slots->size(); ++i)
     if (g.column[i] >= 0) (*slots)[i] = v[g.column[i]];
 }
@@ -653,22 +882,20 @@ void PlusAll(const Graph& g, const std::vector<double>& x, const std::vector<dou
   std::vector<double> slots;
   SlotsFromColumns(g, delta_columns, &slots);
   out->resize(x.size());
-  for (int p = 0; p < g.S + g.N; ++p) PosePlus(&x[7 * p], &slots[6 * p], g.mask[p], p == g.gravity, &(*out)[7 * p]);
+  for (int p = 0; p < g.P(); ++p) PosePlus(&x[7 * p], &slots[6 * p], g.mask[p], g.Kind(p), &(*out)[7 * p]);
 }
 bool EvaluateGradientAndJacobian(const Graph& g, const std::vector<double>& x, bool first, State* s) {
   if (!Linearise(g, x, &s->lin)) return false;
   s->gradient.assign(g.num_eff, 0.);
   std::vector<double> squared(g.num_eff, 0.);
-  for (const RowBlock& k : s->lin.blocks) {
-    const int pa = g.constraints[k.c].submap, pn = g.S + g.constraints[k.c].node;
-    for (int slot = 0; slot < 6; ++slot) {
-      const int ca = g.column[pa * 6 + slot], cn = g.column[pn * 6 + slot];
-      for (int row = 0; row < 6; ++row) {
-        if (ca >= 0) s->gradient[ca] += k.js[row * 6 + slot] * k.r[row], squared[ca] += k.js[row * 6 + slot] * k.js[row * 6 + slot];
-        if (cn >= 0) s->gradient[cn] += k.jn[row * 6 + slot] * k.r[row], squared[cn] += k.jn[row * 6 + slot] * k.jn[row * 6 + slot];
+  for (const RowBlock& k : s->lin.blocks)
+    for (int which = 0; which < k.num; ++which)
+      for (int slot = 0; slot < 6; ++slot) {
+        const int col = g.column[k.pose[which] * 6 + slot];
+        if (col < 0) continue;
+        const double* j = k.j[which];
+        for (int row = 0; row < 6; ++row) s->gradient[col] += j[row * 6 + slot] * k.r[row], squared[col] += j[row * 6 + slot] * j[row * 6 + slot];
       }
-    }
-  }
   if (first) {
     s->scale.assign(g.num_eff, 1.);
     for (int c = 0; c < g.num_eff; ++c) s->scale[c] = 1.0 / (1.0 + std::sqrt(squared[c]));
@@ -677,7 +904,7 @@ bool EvaluateGradientAndJacobian(const Graph& g, const std::vector<double>& x, b
   for (int c = 0; c < g.num_eff; ++c) negative[c] = -s->gradient[c];
   PlusAll(g, x, negative, &projected);
   s->gradient_max_norm = 0;
-  for (int p = 0; p < g.S + g.N; ++p)
+  for (int p = 0; p < g.P(); ++p)
     for (int k = 0; k < 7; ++k)
       if ((k < 3 ? g.mask[p] & 7 : g.mask[p] & 56) != 0)
         s->gradient_max_norm = std::max(s->gradient_max_norm, std::fabs(x[7 * p + k] - projected[7 * p + k]));
@@ -705,11 +932,13 @@ bool ComputeStep(const Graph& g, const State& s, int solver, const Options& o, L
   SlotsFromColumns(g, s.scale, &scales);
   double dot = 0;
   for (const RowBlock& k : s.lin.blocks) {
-    const int pa = g.constraints[k.c].submap, pn = g.S + g.constraints[k.c].node;
     for (int row = 0; row < 6; ++row) {
       double m = 0;
-      for (int slot = 0; slot < 6; ++slot)
-        m += k.js[row * 6 + slot] * scales[pa * 6 + slot] * slots[pa * 6 + slot] + k.jn[row * 6 + slot] * scales[pn * 6 + slot] * slots[pn * 6 + slot];
+      for (int slot = 0; slot < 6; ++slot) {
+        double t = k.j[0][row * 6 + slot] * scales[k.pose[0] * 6 + slot] * slots[k.pose[0] * 6 + slot];
+        for (int which = 1; which < k.num; ++which) t += k.j[which][row * 6 + slot] * scales[k.pose[which] * 6 + slot] * slots[k.pose[which] * 6 + slot];
+        m += t;
+      }
       dot += m * (k.r[row] + m / 2.0);
     }
   }
@@ -775,10 +1004,16 @@ void Solve(const Options& options, int solver, Graph* g, Result* out) {
     }
     num_consecutive_invalid_steps = 0;
     for (int c = 0; c < g->num_eff; ++c) delta[c] = step[c] * s.scale[c];
+    for (int p = g->submaps; p < g->S; ++p)
+      if (g->column[p * 6 + 3] >= 0) {
+        const double yaw_step = std::fabs(delta[g->column[p * 6 + 3]]);
+        g->clamp_margin = std::min(g->clamp_margin, std::fabs(yaw_step - 0.5) / 0.5);
+        g->clamped_steps += yaw_step > 0.5;
+      }
     PlusAll(*g, x, delta, &candidate_x);
     if (!Cost(*g, candidate_x, &candidate_cost)) candidate_cost = std::numeric_limits<double>::max();
     double step_norm = 0;
-    for (int p = 0; p < g->S + g->N; ++p)
+    for (int p = 0; p < g->P(); ++p)
       for (int k = 0; k < 7; ++k)
         if ((k < 3 ? g->mask[p] & 7 : g->mask[p] & 56) != 0) step_norm += (x[7 * p + k] - candidate_x[7 * p + k]) * (x[7 * p + k] - candidate_x[7 * p + k]);
     step_norm = std::sqrt(step_norm);
@@ -928,25 +1163,53 @@ int ReducesNoise(const char* path) {
 
 }  // namespace
 
-// in: int32 S N C gravity fix_z nonmonotonic max_iterations mode solver; double radius; poses; int32 constant[S + N];
-// constraints.  mode 0 solve, 1 evaluate, 2 step.
+// in: int32 S N C gravity fix_z nonmonotonic max_iterations mode solver F CF L O; double radius, huber_scale; poses
+// (submaps, fixed frames, nodes); int32 constant[S + N]; constraints; fixed-frame constraints (.submap = the frame); int32
+// inter_submap[C]; landmark poses; int32 landmark_constant[L]; observations (dliom_pose_graph_landmark_observation).
+// mode 0 solve, 1 evaluate, 2 step.  out: the poses (7 a pose) and the slots (6 a pose) in the order submaps, fixed frames,
+// nodes, landmarks and the residuals (6 a residual block) in the order constraints, fixed-frame constraints, observations.
+//   solve: int32 termination, iterations, successful, unsuccessful, columns, steps, rises, clamped_steps; double
+//     initial_cost, final_cost, quality_margin, tolerance_margin, seconds; int32 step[steps]; the poses; double
+//     loss_margin, clamp_margin, slerp_margin
+//   evaluate: int32 failed, columns; double cost; the residuals; the gradient's slots
+//   step: int32 failed, columns; double model_cost_change; the step's slots; int32 blocks, and a remaining residual block
+//     its int32 index, 6 residuals and its 6 x 6 Jacobian blocks (two, an observation's three); the scale's slots
 int main(int argc, char** argv) {
   if (argc == 3 && std::strcmp(argv[1], "--reduces-noise") == 0) return ReducesNoise(argv[2]);
   if (argc != 3) return 2;
   FILE* f = fopen(argv[1], "rb");
   if (f == nullptr) return 2;
-  int32_t head[9];
-  double radius;
+  int32_t head[13];
+  double reals[2];
   Graph g;
-  if (fread(head, 4, 9, f) != 9 || fread(&radius, 8, 1, f) != 1) return 2;
-  g.S = head[0], g.N = head[1], g.gravity = head[3], g.fix_z = head[4];
-  g.x.resize(7 * static_cast<size_t>(g.S + g.N));
-  g.constant.resize(g.S + g.N);
-  g.constraints.resize(head[2]);
-  if (fread(g.x.data(), 8, g.x.size(), f) != g.x.size() || fread(g.constant.data(), 4, g.constant.size(), f) != g.constant.size() ||
-      fread(g.constraints.data(), sizeof(Constraint), g.constraints.size(), f) != g.constraints.size())
+  if (fread(head, 4, 13, f) != 13 || fread(reals, 8, 2, f) != 2) return 2;
+  const double radius = reals[0];
+  const int F = head[9], CF = head[10], C = head[2];
+  g.submaps = head[0], g.S = head[0] + F, g.N = head[1], g.gravity = head[3], g.fix_z = head[4];
+  g.huber_scale = reals[1];
+  g.L = head[11];
+  const int O = head[12];
+  g.x.resize(7 * static_cast<size_t>(g.S + g.N + g.L));
+  const size_t before_landmarks = 7 * static_cast<size_t>(g.S + g.N);
+  std::vector<int32_t> landmark_constant(g.L);
+  g.observations.resize(O);
+  std::vector<int32_t> constant(g.submaps + g.N), inter_submap(C);
+  g.constraints.resize(C + CF);
+  if (fread(g.x.data(), 8, before_landmarks, f) != before_landmarks || fread(constant.data(), 4, constant.size(), f) != constant.size() ||
+      fread(g.constraints.data(), sizeof(Constraint), g.constraints.size(), f) != g.constraints.size() ||
+      fread(inter_submap.data(), 4, inter_submap.size(), f) != inter_submap.size() ||
+      fread(g.x.data() + before_landmarks, 8, 7 * static_cast<size_t>(g.L), f) != 7 * static_cast<size_t>(g.L) ||
+      fread(landmark_constant.data(), 4, landmark_constant.size(), f) != landmark_constant.size() ||
+      fread(g.observations.data(), sizeof(Observation), g.observations.size(), f) != g.observations.size())
     return 2;
   fclose(f);
+  g.constant.assign(g.S + g.N + g.L, 0);  // a fixed frame is never constant
+  for (int l = 0; l < g.L; ++l) g.constant[g.S + g.N + l] = landmark_constant[l];
+  for (int p = 0; p < g.submaps; ++p) g.constant[p] = constant[p];
+  for (int p = 0; p < g.N; ++p) g.constant[g.S + p] = constant[g.submaps + p];
+  g.lossy.assign(C + CF, 0);
+  for (int c = 0; c < C; ++c) g.lossy[c] = inter_submap[c] != 0;
+  for (int c = C; c < C + CF; ++c) g.constraints[c].submap += g.submaps;
   g.Derive();
   Options options;
   options.use_nonmonotonic_steps = head[5] != 0;
@@ -958,13 +1221,15 @@ int main(int argc, char** argv) {
   if (mode == 0) {
     Result r;
     Solve(options, solver, &g, &r);
-    const int32_t ints[8] = {r.termination, r.iterations, r.successful, r.unsuccessful, g.num_eff, static_cast<int32_t>(r.steps.size()), r.rises, 0};
+    const int32_t ints[8] = {r.termination, r.iterations, r.successful, r.unsuccessful, g.num_eff, static_cast<int32_t>(r.steps.size()), r.rises, g.clamped_steps};
     fwrite(ints, 4, 8, o);
     const double d[5] = {r.initial_cost, r.final_cost, r.quality_margin, r.tolerance_margin, r.seconds};
     put_d(d, 5);
     std::vector<int32_t> steps(r.steps.begin(), r.steps.end());
     fwrite(steps.data(), 4, steps.size(), o);
     put_d(g.x.data(), g.x.size());
+    const double margins[3] = {g.loss_margin, g.clamp_margin, g.slerp_margin};
+    put_d(margins, 3);
   } else {
     State s;
     s.g = &g;
@@ -1000,8 +1265,7 @@ int main(int argc, char** argv) {
       for (const RowBlock& k : s.lin.blocks) {
         fwrite(&k.c, 4, 1, o);
         put_d(k.r, 6);
-        put_d(k.js, 36);
-        put_d(k.jn, 36);
+        for (int which = 0; which < k.num; ++which) put_d(k.j[which], 36);
       }
       SlotsFromColumns(g, s.scale, &slots);
       put_d(slots.data(), slots.size());

@@ -1,5 +1,7 @@
-"""Shared by tests/test_pose_graph_host.py, tests/test_gpu_pose_graph.py and tools/pose_graph_bench.py: builds and runs
-the CPU model (tests/cpp/pose_graph_model.cc), makes the graphs and holds the fixed case list."""
+"""Shared by tests/test_pose_graph*_host.py, tests/test_gpu_pose_graph*.py and tools/pose_graph_bench.py: builds and runs
+the CPU model (tests/cpp/pose_graph_model.cc) on any of the graph classes, makes the graphs without further terms and holds
+their fixed case list.  The graphs with fixed frames and the loss are pose_graph_terms_common's, those with landmarks
+pose_graph_landmarks_common's."""
 import os
 import struct
 import subprocess
@@ -22,6 +24,21 @@ def build_model(directory):
     exe = os.path.join(str(directory), "pose_graph_model")
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, MODEL_SRC])
     return exe
+
+
+def build_structure_check(directory):
+    """tests/cpp/pose_graph_structure_check.cc as a stand-alone program under sanitisers; it reads the model's input."""
+    exe = os.path.join(str(directory), "pose_graph_structure_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+                           "-Werror", "-o", exe, os.path.join(ROOT, "tests", "cpp", "pose_graph_structure_check.cc")])
+    return exe
+
+
+def structure_check_fields(line):
+    """One "<path> ok columns 14 pairs 3 ..." line of the structure check -> dict(columns=14, pairs=3, ...)."""
+    words = line.split()
+    assert words[1] == "ok", line
+    return {key: int(value) for key, value in zip(words[2::2], words[3::2])}
 
 
 class Graph:
@@ -49,11 +66,37 @@ class Graph:
                             self.gravity, self.fix_z, self.nonmonotonic, self.max_iterations)
 
 
+def _terms(graph):
+    """The further terms of any of the graph classes (this module's Graph, pose_graph_terms_common's, pose_graph_landmarks_
+    common's), an absent one empty -> (frames, frame_constraints, huber_scale, inter_submap, landmarks, landmark_constant,
+    observations)."""
+    frames, landmarks = getattr(graph, "frames", np.zeros((0, 7))), getattr(graph, "landmarks", np.zeros((0, 7)))
+    return (frames, getattr(graph, "frame_constraints", np.zeros(0, CONSTRAINT)), getattr(graph, "huber_scale", 0.0),
+            getattr(graph, "inter_submap", np.zeros(len(graph.constraints), np.uint8)), landmarks,
+            getattr(graph, "landmark_constant", np.zeros(len(landmarks), np.uint8)), getattr(graph, "observations", np.zeros(0, np.uint8)))
+
+
 def _write(graph, path, mode, solver, radius):
+    """The model's input (tests/cpp/pose_graph_model.cc, above its main)."""
+    frames, frame_constraints, huber_scale, inter_submap, landmarks, landmark_constant, observations = _terms(graph)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<13i", len(graph.submaps), len(graph.nodes), len(graph.constraints), graph.gravity, int(graph.fix_z),
+                            int(graph.nonmonotonic), graph.max_iterations, mode, solver, len(frames), len(frame_constraints),
+                            len(landmarks), len(observations)))
+        f.write(struct.pack("<2d", radius, huber_scale))
+        f.write(graph.submaps.tobytes() + frames.tobytes() + graph.nodes.tobytes())
+        f.write(np.concatenate([graph.submap_constant, graph.node_constant]).astype("<i4").tobytes())
+        f.write(graph.constraints.tobytes() + frame_constraints.tobytes())
+        f.write(inter_submap.astype("<i4").tobytes())
+        f.write(landmarks.tobytes() + landmark_constant.astype("<i4").tobytes() + observations.tobytes())
+
+
+def write_adapter_graph(graph, path):
+    """The head of the adapter programs' input (tests/cpp/pose_graph*_adapter.cc): the graph without further terms."""
     with open(path, "wb") as f:
         f.write(struct.pack("<9i", len(graph.submaps), len(graph.nodes), len(graph.constraints), graph.gravity, int(graph.fix_z),
-                            int(graph.nonmonotonic), graph.max_iterations, mode, solver))
-        f.write(struct.pack("<d", radius))
+                            int(graph.nonmonotonic), graph.max_iterations, 0, 0))
+        f.write(struct.pack("<d", 1e4))
         f.write(graph.submaps.tobytes() + graph.nodes.tobytes())
         f.write(np.concatenate([graph.submap_constant, graph.node_constant]).astype("<i4").tobytes())
         f.write(graph.constraints.tobytes())
@@ -66,48 +109,77 @@ def _run(exe, graph, directory, mode, solver, radius=1e4):
     return open(dst, "rb").read()
 
 
+def _split(graph, rows):
+    """rows in the model's order (submaps, fixed frames, nodes, landmarks) -> (submaps, nodes, frames, landmarks), the order
+    in which the device reports them"""
+    s, f, n = len(graph.submaps), len(_terms(graph)[0]), len(graph.nodes)
+    return rows[:s].copy(), rows[s + f:s + f + n].copy(), rows[s:s + f].copy(), rows[s + f + n:].copy()
+
+
 def model_solve(exe, graph, directory, solver=ELIMINATED):
-    """-> dict(termination, iterations, successful, unsuccessful, columns, steps, initial_cost, final_cost, quality_margin,
-    tolerance_margin, seconds, submaps, nodes)"""
+    """-> dict(termination, iterations, successful, unsuccessful, columns, steps, rises, initial_cost, final_cost,
+    quality_margin, tolerance_margin, seconds, submaps, nodes, frames, landmarks, loss_margin, clamp_margin, clamped_steps,
+    slerp_margin).  Of an absent term the margins are 1e300, slerp_margin inf, and clamped_steps is 0."""
     data = _run(exe, graph, directory, 0, solver)
-    termination, iterations, successful, unsuccessful, columns, num_steps, rises, _ = struct.unpack_from("<8i", data, 0)
+    termination, iterations, successful, unsuccessful, columns, num_steps, rises, clamped = struct.unpack_from("<8i", data, 0)
     initial, final, quality, tolerance, seconds = struct.unpack_from("<5d", data, 32)
     steps = list(struct.unpack_from("<%di" % num_steps, data, 72))
-    poses = np.frombuffer(data, dtype=np.float64, offset=72 + 4 * num_steps).reshape(-1, 7)
-    assert len(poses) == len(graph.submaps) + len(graph.nodes)
+    at = 72 + 4 * num_steps
+    poses = np.frombuffer(data, dtype=np.float64, count=(len(data) - at - 24) // 8, offset=at).reshape(-1, 7)
+    submaps, nodes, frames, landmarks = _split(graph, poses)
+    assert (len(submaps), len(nodes), len(landmarks)) == (len(graph.submaps), len(graph.nodes), len(_terms(graph)[4]))
+    loss_margin, clamp_margin, slerp_margin = struct.unpack_from("<3d", data, len(data) - 24)
+    if len(landmarks) + len(_terms(graph)[6]) == 0:
+        assert slerp_margin == 1e300
+        slerp_margin = np.inf
     return dict(termination=termination, iterations=iterations, successful=successful, unsuccessful=unsuccessful,
                 columns=columns, steps=steps, rises=rises, initial_cost=initial, final_cost=final, quality_margin=quality,
-                tolerance_margin=tolerance, seconds=seconds, submaps=poses[:len(graph.submaps)].copy(),
-                nodes=poses[len(graph.submaps):].copy())
+                tolerance_margin=tolerance, seconds=seconds, submaps=submaps, nodes=nodes, frames=frames, landmarks=landmarks,
+                loss_margin=loss_margin, clamp_margin=clamp_margin, clamped_steps=clamped, slerp_margin=slerp_margin)
+
+
+def _counts(graph):
+    """-> (constraints and fixed-frame constraints, observations, poses)"""
+    frames, frame_constraints, _, _, landmarks, _, observations = _terms(graph)
+    return (len(graph.constraints) + len(frame_constraints), len(observations),
+            len(graph.submaps) + len(frames) + len(graph.nodes) + len(landmarks))
 
 
 def model_evaluate(exe, graph, directory):
-    """-> (cost, residuals (C, 6), gradient (S + N, 6), columns)"""
+    """-> (cost, residuals (C + CF + O, 6), gradient (S + N + F + L, 6) -- submaps, nodes, fixed frames, landmarks, as the
+    device reports it --, columns)"""
     data = _run(exe, graph, directory, 1, 0)
     failed, columns = struct.unpack_from("<2i", data, 0)
     assert failed == 0
     cost = struct.unpack_from("<d", data, 8)[0]
-    c, p = len(graph.constraints), len(graph.submaps) + len(graph.nodes)
-    r = np.frombuffer(data, dtype=np.float64, count=6 * c, offset=16).reshape(c, 6).copy()
-    g = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16 + 48 * c).reshape(p, 6).copy()
-    return cost, r, g, columns
+    c, o, p = _counts(graph)
+    r = np.frombuffer(data, dtype=np.float64, count=6 * (c + o), offset=16).reshape(c + o, 6).copy()
+    g = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16 + 48 * (c + o)).reshape(p, 6)
+    assert len(data) == 16 + 48 * (c + o + p)
+    return cost, r, np.concatenate(_split(graph, g)), columns
 
 
 def model_step(exe, graph, directory, solver, radius=1e4):
-    """-> dict(delta (S + N, 6), model_cost_change, columns, blocks: (constraint, r (6), js (6, 6), jn (6, 6)) arrays on the
-    unscaled tangent slots, scale (S + N, 6))"""
+    """-> dict(delta (S + N + F + L, 6) in the device's order, model_cost_change, columns, blocks: the remaining constraints'
+    and fixed-frame constraints' (c, r (6), js (6, 6), jn (6, 6)) arrays on the unscaled tangent slots, scale like delta)"""
     data = _run(exe, graph, directory, 2, solver, radius)
     failed, columns = struct.unpack_from("<2i", data, 0)
     assert failed == 0
     change = struct.unpack_from("<d", data, 8)[0]
-    p = len(graph.submaps) + len(graph.nodes)
-    delta = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16).reshape(p, 6).copy()
+    c, _, p = _counts(graph)
+    delta = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16).reshape(p, 6)
     at = 16 + 48 * p
+    block = np.dtype([("c", "<i4"), ("r", "<f8", 6), ("js", "<f8", (6, 6)), ("jn", "<f8", (6, 6))])
     blocks = struct.unpack_from("<i", data, at)[0]
-    rec = np.frombuffer(data, dtype=np.dtype([("c", "<i4"), ("r", "<f8", 6), ("js", "<f8", (6, 6)), ("jn", "<f8", (6, 6))]),
-                        count=blocks, offset=at + 4)
-    scale = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=at + 4 + rec.nbytes).reshape(p, 6).copy()
-    return dict(delta=delta, model_cost_change=change, columns=columns, blocks=rec, scale=scale)
+    # the constraints' blocks come first; an observation's (c past the constraints) has a third 6 x 6 block
+    two = 0
+    while two < blocks and struct.unpack_from("<i", data, at + 4 + two * block.itemsize)[0] < c:
+        two += 1
+    rec = np.frombuffer(data, dtype=block, count=two, offset=at + 4)
+    scale = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=at + 4 + rec.nbytes + (blocks - two) * (block.itemsize + 288)).reshape(p, 6)
+    assert len(data) == at + 4 + rec.nbytes + (blocks - two) * (block.itemsize + 288) + 48 * p
+    return dict(delta=np.concatenate(_split(graph, delta)), model_cost_change=change, columns=columns, blocks=rec,
+                scale=np.concatenate(_split(graph, scale)))
 
 
 def reduces_noise(exe, directory):

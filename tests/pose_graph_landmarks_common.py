@@ -1,10 +1,9 @@
 """Shared by tests/test_pose_graph_landmarks_host.py, tests/test_gpu_pose_graph_landmarks.py and tools/pose_graph_bench.py:
-builds and runs the CPU model with landmark observations (tests/cpp/pose_graph_landmarks_model.cc), restates the
-reference's interpolation and GetInitialLandmarkPose, makes the graphs and holds their fixed case list.  The graphs
-without landmarks are pose_graph_terms_common's."""
+restates the reference's interpolation and GetInitialLandmarkPose, makes the graphs with landmark observations and holds
+their fixed case list.  The graphs without landmarks are pose_graph_terms_common's, the CPU model's harness is
+pose_graph_common's."""
 import os
 import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -14,17 +13,10 @@ import pose_graph_common as pc  # noqa: E402
 import pose_graph_terms_common as tc  # noqa: E402
 from pose_graph_common import synth  # noqa: E402
 
-MODEL_SRC = os.path.join(pc.ROOT, "tests", "cpp", "pose_graph_landmarks_model.cc")
 OBSERVATION = np.dtype({"names": ["landmark", "prev_node", "next_node", "interpolation_parameter", "landmark_to_tracking",
                                   "translation_weight", "rotation_weight"],
                         "formats": ["<i4", "<i4", "<i4", "<f8", ("<f8", 7), "<f8", "<f8"], "offsets": [0, 4, 8, 16, 24, 80, 88],
                         "itemsize": 96})
-
-
-def build_model(directory):
-    exe = os.path.join(str(directory), "pose_graph_landmarks_model")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, MODEL_SRC])
-    return exe
 
 
 class Graph(tc.Graph):
@@ -47,83 +39,6 @@ class Graph(tc.Graph):
                             inter_submap=self.inter_submap if self.inter_submap.any() else None, entry=entry,
                             landmarks=self.landmarks, landmark_constant=self.landmark_constant if self.landmark_constant.any() else None,
                             landmark_observations=self.observations)
-
-
-def _write(graph, path, mode, solver, radius):
-    with open(path, "wb") as f:
-        f.write(struct.pack("<13i", len(graph.submaps), len(graph.nodes), len(graph.constraints), graph.gravity, int(graph.fix_z),
-                            int(graph.nonmonotonic), graph.max_iterations, mode, solver, len(graph.frames),
-                            len(graph.frame_constraints), len(graph.landmarks), len(graph.observations)))
-        f.write(struct.pack("<2d", radius, graph.huber_scale))
-        f.write(graph.submaps.tobytes() + graph.frames.tobytes() + graph.nodes.tobytes())
-        f.write(np.concatenate([graph.submap_constant, graph.node_constant]).astype("<i4").tobytes())
-        f.write(graph.constraints.tobytes() + graph.frame_constraints.tobytes())
-        f.write(graph.inter_submap.astype("<i4").tobytes())
-        f.write(graph.landmarks.tobytes() + graph.landmark_constant.astype("<i4").tobytes() + graph.observations.tobytes())
-
-
-def _run(exe, graph, directory, mode, solver, radius=1e4):
-    if not isinstance(graph, Graph):
-        graph = Graph(graph)
-    src, dst = os.path.join(str(directory), "pgl_in.bin"), os.path.join(str(directory), "pgl_out.bin")
-    _write(graph, src, mode, solver, radius)
-    subprocess.check_call([exe, src, dst])
-    return graph, open(dst, "rb").read()
-
-
-def _split(graph, rows):
-    """rows in the model's order (submaps, fixed frames, nodes, landmarks) -> (submaps, nodes, frames, landmarks)"""
-    s, f, n = len(graph.submaps), len(graph.frames), len(graph.nodes)
-    return rows[:s].copy(), rows[s + f:s + f + n].copy(), rows[s:s + f].copy(), rows[s + f + n:].copy()
-
-
-def model_solve(exe, graph, directory, solver=pc.ELIMINATED):
-    """pose_graph_terms_common.model_solve's dict and: landmarks, slerp_margin (inf without landmarks); raw: the output's
-    bytes without the seconds (pose_graph_terms_model.cc's output of a graph without landmarks)."""
-    graph, data = _run(exe, graph, directory, 0, solver)
-    termination, iterations, successful, unsuccessful, columns, num_steps, rises, clamped = struct.unpack_from("<8i", data, 0)
-    initial, final, quality, tolerance, seconds = struct.unpack_from("<5d", data, 32)
-    steps = list(struct.unpack_from("<%di" % num_steps, data, 72))
-    count = len(graph.submaps) + len(graph.frames) + len(graph.nodes) + len(graph.landmarks)
-    poses = np.frombuffer(data, dtype=np.float64, count=7 * count, offset=72 + 4 * num_steps).reshape(-1, 7)
-    at = 72 + 4 * num_steps + 56 * count
-    loss_margin, clamp_margin = struct.unpack_from("<2d", data, at)
-    slerp_margin = np.inf
-    if len(graph.landmarks) + len(graph.observations) > 0:
-        slerp_margin = struct.unpack_from("<d", data, at + 16)[0]
-        at += 8
-    assert len(data) == at + 16
-    submaps, nodes, frames, landmarks = _split(graph, poses)
-    return dict(termination=termination, iterations=iterations, successful=successful, unsuccessful=unsuccessful,
-                columns=columns, steps=steps, rises=rises, initial_cost=initial, final_cost=final, quality_margin=quality,
-                tolerance_margin=tolerance, seconds=seconds, submaps=submaps, nodes=nodes, frames=frames, landmarks=landmarks,
-                loss_margin=loss_margin, clamp_margin=clamp_margin, clamped_steps=clamped, slerp_margin=slerp_margin,
-                raw=data[:64] + data[72:])
-
-
-def model_evaluate(exe, graph, directory):
-    """-> (cost, residuals (C + CF + O, 6), gradient (S + N + F + L, 6) -- submaps, nodes, fixed frames, landmarks, as the
-    device reports it --, columns, raw)"""
-    graph, data = _run(exe, graph, directory, 1, 0)
-    failed, columns = struct.unpack_from("<2i", data, 0)
-    assert failed == 0
-    cost = struct.unpack_from("<d", data, 8)[0]
-    c = len(graph.constraints) + len(graph.frame_constraints) + len(graph.observations)
-    p = len(graph.submaps) + len(graph.frames) + len(graph.nodes) + len(graph.landmarks)
-    r = np.frombuffer(data, dtype=np.float64, count=6 * c, offset=16).reshape(c, 6).copy()
-    g = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16 + 48 * c).reshape(p, 6)
-    return cost, r, np.concatenate(_split(graph, g)), columns, data
-
-
-def model_step(exe, graph, directory, solver, radius=1e4):
-    """-> dict(delta (S + N + F + L, 6) in the device's order, model_cost_change, columns, raw)"""
-    graph, data = _run(exe, graph, directory, 2, solver, radius)
-    failed, columns = struct.unpack_from("<2i", data, 0)
-    assert failed == 0
-    change = struct.unpack_from("<d", data, 8)[0]
-    p = len(graph.submaps) + len(graph.frames) + len(graph.nodes) + len(graph.landmarks)
-    delta = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16).reshape(p, 6)
-    return dict(delta=np.concatenate(_split(graph, delta)), model_cost_change=change, columns=columns, raw=data)
 
 
 # ---- the reference's host arithmetic, restated -------------------------------------------------------------------------------
@@ -409,7 +324,7 @@ def adapter_case():
 
 
 def adapter_write(path, base, spec, frozen, extra):
-    pc._write(base, path, 0, 0, 1e4)
+    pc.write_adapter_graph(base, path)
     with open(path, "ab") as f:
         f.write(struct.pack("<3i", frozen, int(extra), len(spec)))
         for landmark in spec:

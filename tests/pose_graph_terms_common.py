@@ -1,10 +1,7 @@
-"""Shared by tests/test_pose_graph_terms_host.py, tests/test_gpu_pose_graph_terms.py and tools/pose_graph_bench.py: builds
-and runs the CPU model with the further terms (tests/cpp/pose_graph_terms_model.cc: fixed-frame pose constraints and the
-Huber loss), makes the graphs and holds their fixed case list.  The graphs without a further term are
-pose_graph_common's."""
+"""Shared by tests/test_pose_graph_terms_host.py, tests/test_gpu_pose_graph_terms.py and tools/pose_graph_bench.py: makes
+the graphs with the further terms (fixed-frame pose constraints and the Huber loss) and holds their fixed case list.  The
+graphs without a further term and the CPU model's harness are pose_graph_common's."""
 import os
-import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -13,14 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pose_graph_common as pc  # noqa: E402
 from pose_graph_common import synth  # noqa: E402
 
-MODEL_SRC = os.path.join(pc.ROOT, "tests", "cpp", "pose_graph_terms_model.cc")
 CONSTRAINT = pc.CONSTRAINT
-
-
-def build_model(directory):
-    exe = os.path.join(str(directory), "pose_graph_terms_model")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, MODEL_SRC])
-    return exe
 
 
 class Graph(pc.Graph):
@@ -44,75 +34,6 @@ class Graph(pc.Graph):
                             self.gravity, self.fix_z, self.nonmonotonic, self.max_iterations, fixed_frame_poses=self.frames,
                             fixed_frame_constraints=self.frame_constraints, huber_scale=self.huber_scale,
                             inter_submap=self.inter_submap if self.inter_submap.any() else None, entry=entry)
-
-
-def _write(graph, path, mode, solver, radius):
-    with open(path, "wb") as f:
-        f.write(struct.pack("<11i", len(graph.submaps), len(graph.nodes), len(graph.constraints), graph.gravity, int(graph.fix_z),
-                            int(graph.nonmonotonic), graph.max_iterations, mode, solver, len(graph.frames),
-                            len(graph.frame_constraints)))
-        f.write(struct.pack("<2d", radius, graph.huber_scale))
-        f.write(graph.submaps.tobytes() + graph.frames.tobytes() + graph.nodes.tobytes())
-        f.write(np.concatenate([graph.submap_constant, graph.node_constant]).astype("<i4").tobytes())
-        f.write(graph.constraints.tobytes() + graph.frame_constraints.tobytes())
-        f.write(graph.inter_submap.astype("<i4").tobytes())
-
-
-def _run(exe, graph, directory, mode, solver, radius=1e4):
-    if not isinstance(graph, Graph):
-        graph = Graph(graph)
-    src, dst = os.path.join(str(directory), "pgt_in.bin"), os.path.join(str(directory), "pgt_out.bin")
-    _write(graph, src, mode, solver, radius)
-    subprocess.check_call([exe, src, dst])
-    return graph, open(dst, "rb").read()
-
-
-def _split(graph, rows):
-    """rows in the model's order (submaps, fixed frames, nodes) -> (submaps, nodes, frames)"""
-    s, f = len(graph.submaps), len(graph.frames)
-    return rows[:s].copy(), rows[s + f:].copy(), rows[s:s + f].copy()
-
-
-def model_solve(exe, graph, directory, solver=pc.ELIMINATED):
-    """pose_graph_common.model_solve's dict and: frames, loss_margin, clamp_margin, clamped_steps; raw: the output's bytes without the
-    seconds and the two margins (pose_graph_model.cc's output of a graph without a further term)."""
-    graph, data = _run(exe, graph, directory, 0, solver)
-    termination, iterations, successful, unsuccessful, columns, num_steps, rises, clamped = struct.unpack_from("<8i", data, 0)
-    initial, final, quality, tolerance, seconds = struct.unpack_from("<5d", data, 32)
-    steps = list(struct.unpack_from("<%di" % num_steps, data, 72))
-    count = len(graph.submaps) + len(graph.frames) + len(graph.nodes)
-    poses = np.frombuffer(data, dtype=np.float64, count=7 * count, offset=72 + 4 * num_steps).reshape(-1, 7)
-    loss_margin, clamp_margin = struct.unpack_from("<2d", data, 72 + 4 * num_steps + 56 * count)
-    assert len(data) == 72 + 4 * num_steps + 56 * count + 16
-    submaps, nodes, frames = _split(graph, poses)
-    return dict(termination=termination, iterations=iterations, successful=successful, unsuccessful=unsuccessful,
-                columns=columns, steps=steps, rises=rises, initial_cost=initial, final_cost=final, quality_margin=quality,
-                tolerance_margin=tolerance, seconds=seconds, submaps=submaps, nodes=nodes, frames=frames,
-                loss_margin=loss_margin, clamp_margin=clamp_margin, clamped_steps=clamped, raw=data[:64] + data[72:-16])
-
-
-def model_evaluate(exe, graph, directory):
-    """-> (cost, residuals (C + CF, 6), gradient (S + N + F, 6) -- submaps, nodes, fixed frames, as the device reports
-    it --, columns)"""
-    graph, data = _run(exe, graph, directory, 1, 0)
-    failed, columns = struct.unpack_from("<2i", data, 0)
-    assert failed == 0
-    cost = struct.unpack_from("<d", data, 8)[0]
-    c, p = len(graph.constraints) + len(graph.frame_constraints), len(graph.submaps) + len(graph.frames) + len(graph.nodes)
-    r = np.frombuffer(data, dtype=np.float64, count=6 * c, offset=16).reshape(c, 6).copy()
-    g = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16 + 48 * c).reshape(p, 6)
-    return cost, r, np.concatenate(_split(graph, g)), columns
-
-
-def model_step(exe, graph, directory, solver, radius=1e4):
-    """-> dict(delta (S + N + F, 6) in the device's order, model_cost_change, columns, raw)"""
-    graph, data = _run(exe, graph, directory, 2, solver, radius)
-    failed, columns = struct.unpack_from("<2i", data, 0)
-    assert failed == 0
-    change = struct.unpack_from("<d", data, 8)[0]
-    p = len(graph.submaps) + len(graph.frames) + len(graph.nodes)
-    delta = np.frombuffer(data, dtype=np.float64, count=6 * p, offset=16).reshape(p, 6)
-    return dict(delta=np.concatenate(_split(graph, delta)), model_cost_change=change, columns=columns, raw=data)
 
 
 # ---- graphs with the further terms ------------------------------------------------------------------------------------------

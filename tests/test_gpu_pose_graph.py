@@ -243,7 +243,7 @@ def test_adapter(dl, ctx, model, tmp_path, frozen):
                            "-Wl,-rpath," + os.path.dirname(dl.LIB_PATH)])
     g = pc.synthetic(7, 41, 1, seed=9, fix_z=frozen is not None, nonmonotonic=True, max_iterations=12)
     src, dst = str(tmp_path / "graph.bin"), str(tmp_path / "adapter.bin")
-    pc._write(g, src, 0, 0, 1e4)
+    pc.write_adapter_graph(g, src)
     subprocess.check_call([exe, src, dst] + ([] if frozen is None else [str(frozen)]))
     data = open(dst, "rb").read()
     S, N = len(g.submaps), len(g.nodes)

@@ -1,6 +1,6 @@
 """GPU tests of the pose graph solve's landmark observations (include/dliom.h dliom_pose_graph_landmarks:
 LandmarkCostFunction3D, promoted nodes and landmarks in the dense reduced system) against the CPU model (tests/cpp/
-pose_graph_landmarks_model.cc).  The bars are those of tests/test_gpu_pose_graph_terms.py: `evaluate` 1e-9 relative; `step`
+pose_graph_model.cc).  The bars are those of tests/test_gpu_pose_graph_terms.py: `evaluate` 1e-9 relative; `step`
 within 10 x the difference between the model's own two linear solvers on the same case; `solve` with equal termination,
 iteration counts and accept / reject sequences, poses within 1e-6 m and 1e-6 rad -- the landmarks' included -- and costs
 within 1e-9 relative."""
@@ -36,8 +36,8 @@ def ctx(dl):
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    d = tmp_path_factory.mktemp("pose_graph_landmarks_model")
-    return lc.build_model(d), d
+    d = tmp_path_factory.mktemp("pose_graph_model")
+    return pc.build_model(d), d
 
 
 def relative(got, want):
@@ -70,7 +70,7 @@ def test_evaluate(dl, ctx, model, fix_z):
     under a free landmark."""
     exe, d = model
     g = lc.evaluate_graph(fix_z)
-    cost, residuals, gradient, _, _ = lc.model_evaluate(exe, g, d)
+    cost, residuals, gradient, _ = pc.model_evaluate(exe, g, d)
     got_cost, got_residuals, got_gradient = g.device(dl, ctx).evaluate()
     print("cost", abs(got_cost - cost) / cost, "residuals", relative(got_residuals, residuals), "gradient", relative(got_gradient, gradient))
     assert abs(got_cost - cost) <= 1e-9 * cost
@@ -92,7 +92,7 @@ def test_step(dl, ctx, model, name):
     exe, d = model
     pairs, landmarks, fix_z, dimension = lc.STEP_CASES[name]
     g = lc.boundary_graph(pairs, landmarks, fix_z)
-    qr, eliminated = lc.model_step(exe, g, d, pc.SPARSE_QR), lc.model_step(exe, g, d, pc.ELIMINATED)
+    qr, eliminated = pc.model_step(exe, g, d, pc.SPARSE_QR), pc.model_step(exe, g, d, pc.ELIMINATED)
     cpu = relative(eliminated["delta"], qr["delta"])
     delta, change, got_dimension = g.device(dl, ctx).step(1e4)
     got = relative(delta, qr["delta"])
@@ -109,7 +109,7 @@ def test_step(dl, ctx, model, name):
 
 def solve_both(dl, ctx, exe, d, g):
     p = g.device(dl, ctx)
-    return lc.model_solve(exe, g, d), p, p.solve()
+    return pc.model_solve(exe, g, d), p, p.solve()
 
 
 def assert_equal_solves(name, g, want, p, summary):
@@ -185,7 +185,7 @@ def test_entry_points_are_bit_identical(dl, ctx, model, name):
     """The old entry point, the new one with NULL and the new one with an empty struct (s44: 260 columns, the blocked
     factorisation)."""
     exe, d = model
-    g = lc.Graph(pc.CASES[name](pc.build_model(d), d))
+    g = lc.Graph(pc.CASES[name](exe, d))
     results = []
     for entry in ("plain", "landmarks_null", "landmarks_empty"):
         p = g.device(dl, ctx, entry=entry)

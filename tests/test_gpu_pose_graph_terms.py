@@ -1,5 +1,5 @@
 """GPU tests of the pose graph solve's further terms (include/dliom.h dliom_pose_graph_terms: fixed-frame pose constraints
-and the Huber loss) against the CPU model (tests/cpp/pose_graph_terms_model.cc).  The bars are those of
+and the Huber loss) against the CPU model (tests/cpp/pose_graph_model.cc).  The bars are those of
 tests/test_gpu_pose_graph.py: `evaluate` 1e-9 relative; `step` within 10 x the difference between the model's own two
 linear solvers on the same case; `solve` with equal termination, iteration counts and accept / reject sequences and poses
 within 1e-6 m and 1e-6 rad, the fixed frames' included."""
@@ -39,8 +39,8 @@ def ctx(dl):
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    d = tmp_path_factory.mktemp("pose_graph_terms_model")
-    return tc.build_model(d), d
+    d = tmp_path_factory.mktemp("pose_graph_model")
+    return pc.build_model(d), d
 
 
 def relative(got, want):
@@ -54,7 +54,7 @@ def test_evaluate(dl, ctx, model, fix_z, huber_scale):
     exe, d = model
     g = tc.evaluate_graph(fix_z, huber_scale)
     assert len(g.submaps) <= 8 and len(g.nodes) == 200 and len(g.frames) == 2
-    cost, residuals, gradient, _ = tc.model_evaluate(exe, g, d)
+    cost, residuals, gradient, _ = pc.model_evaluate(exe, g, d)
     got_cost, got_residuals, got_gradient = g.device(dl, ctx).evaluate()
     print("cost", abs(got_cost - cost) / cost, "residuals", relative(got_residuals, residuals), "gradient", relative(got_gradient, gradient))
     assert abs(got_cost - cost) <= 1e-9 * cost
@@ -74,7 +74,7 @@ def test_step_at_the_one_workgroup_boundary(dl, ctx, model, name):
     exe, d = model
     submaps, frames, fix_z, dimension = BOUNDARY[name]
     g = tc.boundary_graph(submaps, frames, fix_z)
-    qr, eliminated = tc.model_step(exe, g, d, pc.SPARSE_QR), tc.model_step(exe, g, d, pc.ELIMINATED)
+    qr, eliminated = pc.model_step(exe, g, d, pc.SPARSE_QR), pc.model_step(exe, g, d, pc.ELIMINATED)
     cpu = relative(eliminated["delta"], qr["delta"])
     delta, change, got_dimension = g.device(dl, ctx).step(1e4)
     got = relative(delta, qr["delta"])
@@ -89,7 +89,7 @@ def test_step_at_the_one_workgroup_boundary(dl, ctx, model, name):
 
 def solve_both(dl, ctx, exe, d, g):
     p = g.device(dl, ctx)
-    return tc.model_solve(exe, g, d), p, p.solve()
+    return pc.model_solve(exe, g, d), p, p.solve()
 
 
 def assert_equal_solves(name, g, want, p, summary):
@@ -166,7 +166,7 @@ def test_entry_points_are_bit_identical(dl, ctx, model, name):
     """The old entry point, the new one with NULL and the new one with an empty struct (s44: 260 columns, the blocked
     factorisation)."""
     exe, d = model
-    g = tc.Graph(pc.CASES[name](pc.build_model(d), d))
+    g = tc.Graph(pc.CASES[name](exe, d))
     results = []
     for entry in ("plain", "null", "terms"):
         p = g.device(dl, ctx, entry=entry)
@@ -337,7 +337,7 @@ def test_adapter(dl, ctx, tmp_path):
     samples = [[(t, None if (trajectory, k) == (0, 3) else sample(trajectory, t)) for k, t in enumerate(times[trajectory])]
                for trajectory in range(2)]
     src, dst = str(tmp_path / "graph.bin"), str(tmp_path / "adapter.bin")
-    pc._write(g, src, 0, 0, 1e4)
+    pc.write_adapter_graph(g, src)
     with open(src, "ab") as f:
         f.write(inter.astype("<i4").tobytes() + struct.pack("<d", huber_scale))
         for trajectory in range(2):

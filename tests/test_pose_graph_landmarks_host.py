@@ -1,8 +1,7 @@
-"""The pose graph solve's landmark observations without a GPU: the CPU model with LandmarkCostFunction3D (tests/cpp/
-pose_graph_landmarks_model.cc) against the model without it, against the reference's own known answer, against hand
-computations and an independent minimiser; the honesty of the parity cases; the host helper
-dliom_pose_graph_initial_landmark_pose; and the host structure builder with promoted nodes (build_structure_landmarks of
-d-liom_amd/csrc/pose_graph_structure.h) under sanitisers, as a stand-alone program."""
+"""The pose graph solve's landmark observations without a GPU: the CPU model (tests/cpp/pose_graph_model.cc) on graphs
+with LandmarkCostFunction3D against the reference's own known answer, against hand computations and an independent
+minimiser; the honesty of the parity cases; the host helper dliom_pose_graph_initial_landmark_pose; and the host
+structure builder (d-liom_amd/csrc/pose_graph_structure.h) on promoted nodes under sanitisers, as a stand-alone program."""
 import os
 import subprocess
 import sys
@@ -21,34 +20,19 @@ from test_pose_graph_host import numpy_residual  # noqa: E402
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    d = tmp_path_factory.mktemp("pose_graph_landmarks_model")
-    return lc.build_model(d), tc.build_model(d), d
-
-
-@pytest.mark.parametrize("name", list(tc.CASES))
-def test_the_model_is_a_superset(model, name):
-    """Without landmarks the model writes pose_graph_terms_model.cc's bytes: a solve with either linear solver (all but the
-    seconds it took), an evaluation and a step."""
-    exe, old, d = model
-    g = tc.CASES[name](old, d)
-    for solver in (pc.ELIMINATED, pc.SPARSE_QR):
-        want = tc._run(old, g, d, 0, solver)[1]
-        got = lc.model_solve(exe, g, d, solver)
-        assert got["raw"] == want[:64] + want[72:], solver
-        assert got["slerp_margin"] == np.inf
-    assert lc._run(exe, g, d, 1, 0)[1] == tc._run(old, g, d, 1, 0)[1]
-    assert lc._run(exe, g, d, 2, pc.SPARSE_QR)[1] == tc._run(old, g, d, 2, pc.SPARSE_QR)[1]
+    d = tmp_path_factory.mktemp("pose_graph_model")
+    return pc.build_model(d), d
 
 
 def test_the_references_known_answer(model):
     """landmark_cost_function_3d_test.cc's SmokeTest: residuals (1, 0, 0, 0, 0, 0) exactly."""
-    exe, _, d = model
+    exe, d = model
     identity = [1.0, 0.0, 0.0, 0.0]
     nodes = np.array([[0.0, 0.0, 0.0] + identity, [2.0, 2.0, 2.0] + identity])
     base = pc.Graph(np.zeros((0, 7)), nodes, np.zeros(0, pc.CONSTRAINT), gravity=-1)
     rows = [(0, 0, 1, 0.5, np.array([1.0, 1.0, 1.0] + identity), 1.0, 2.0)]
     g = lc.Graph(base, np.array([[1.0, 2.0, 2.0] + identity]), None, lc.rows_to_observations(rows))
-    cost, residuals, gradient, _, _ = lc.model_evaluate(exe, g, d)
+    cost, residuals, gradient, _ = pc.model_evaluate(exe, g, d)
     assert residuals.tolist() == [[1.0, 0.0, 0.0, 0.0, 0.0, 0.0]] and cost == 0.5
     assert lc.landmark_residual(g.observations[0], nodes[0], nodes[1], g.landmarks[0]).tolist() == [1.0, 0.0, 0.0, 0.0, 0.0, 0.0]
     # d e0 / d (prev.x, next.x, landmark.x) = (1 - t, t, -1), times e0 = 1
@@ -69,11 +53,11 @@ def _promoted(g):
 def test_the_evaluate_case_holds_every_branch(model):
     """tests/test_gpu_pose_graph_landmarks.py::test_evaluate's graph by construction, the model's residuals against the
     hand-written ones, and the zero pattern of its gradient."""
-    exe, _, d = model
+    exe, d = model
     for fix_z in (False, True):
         g = lc.evaluate_graph(fix_z)
         assert (len(g.submaps), len(g.nodes), len(g.landmarks), len(g.observations)) == (4, 40, 3, 14)
-        cost, residuals, gradient, _, _ = lc.model_evaluate(exe, g, d)
+        cost, residuals, gradient, _ = pc.model_evaluate(exe, g, d)
         C, S, N = len(g.constraints), len(g.submaps), len(g.nodes)
         cosines = [lc.slerp_scales(g.nodes[o["prev_node"], 3:], g.nodes[o["next_node"], 3:], 0.5)[2] for o in g.observations]
         assert abs(cosines[0]) >= 1 - 1e-5                                   # the linear branch
@@ -142,11 +126,11 @@ def test_independent_minimum(model):
     """The model's final cost against scipy.optimize.least_squares on hand-written residuals; the bar of
     tests/test_pose_graph_host.py::test_independent_minimum: Ceres stops early (function tolerance 1e-6), so the model may
     not undercut the converged minimum and lies within 1e-4 of it."""
-    exe, _, d = model
+    exe, d = model
     g = small_graph(81)
     u = Unknowns(g)
     for solver in (pc.ELIMINATED, pc.SPARSE_QR):
-        got = lc.model_solve(exe, g, d, solver)
+        got = pc.model_solve(exe, g, d, solver)
         if solver == pc.ELIMINATED:
             sol = least_squares(lambda p: u.blocks(p).reshape(-1), np.zeros(u.size), method="trf", xtol=1e-14, ftol=1e-14, gtol=1e-12, max_nfev=400)
             cost_min = 0.5 * (sol.fun ** 2).sum()
@@ -161,9 +145,9 @@ def test_independent_minimum(model):
 def test_gradient_by_central_differences(model):
     """The model's J^T r, slot by slot -- promoted nodes and landmarks among them --, against central differences of the
     hand-written 1/2 sum r^2."""
-    exe, _, d = model
+    exe, d = model
     g = small_graph(82)
-    cost, residuals, gradient, columns, _ = lc.model_evaluate(exe, g, d)
+    cost, residuals, gradient, columns = pc.model_evaluate(exe, g, d)
     u = Unknowns(g)
     assert columns == u.size and abs(cost - u.cost(np.zeros(u.size))) <= 1e-9 * cost
     want = np.concatenate([gradient[0, 3:5], gradient[1:].reshape(-1)])  # no fixed frame: submaps, nodes, landmarks
@@ -184,10 +168,10 @@ def test_parity_cases_are_honest(model, name):
     """tests/test_pose_graph_terms_host.py::test_parity_cases_are_honest with one more margin: no observation's |cos theta|
     within 1e-6 of 1 - 1e-5, and no cos theta within 1e-6 of 0, at any evaluated point; for the eliminated normal equations
     with the promoted layout and the structured QR, within 1e-8 of each other and with equal step sequences."""
-    exe, _, d = model
+    exe, d = model
     g = lc.CASES[name](exe, d)
-    a = lc.model_solve(exe, g, d, pc.ELIMINATED)
-    b = lc.model_solve(exe, g, d, pc.SPARSE_QR)
+    a = pc.model_solve(exe, g, d, pc.ELIMINATED)
+    b = pc.model_solve(exe, g, d, pc.SPARSE_QR)
     difference = max(np.abs(a[key] - b[key]).max(initial=0.0) for key in ("nodes", "submaps", "frames", "landmarks"))
     print(name, a["termination"], a["iterations"], a["steps"], a["quality_margin"], a["tolerance_margin"], a["loss_margin"],
           a["clamp_margin"], a["slerp_margin"], "solvers differ by", difference)
@@ -204,18 +188,18 @@ def test_parity_cases_are_honest(model, name):
 def test_the_step_cases_are_honest(model):
     """The step cases' two linear solvers agree (their difference is the bar of the device's step test) and the evaluated
     point is away from the slerp's branch points."""
-    exe, _, d = model
+    exe, d = model
     for name, (pairs, landmarks, fix_z, _) in lc.STEP_CASES.items():
         g = lc.boundary_graph(pairs, landmarks, fix_z)
-        a, b = lc.model_step(exe, g, d, pc.SPARSE_QR), lc.model_step(exe, g, d, pc.ELIMINATED)
+        a, b = pc.model_step(exe, g, d, pc.SPARSE_QR), pc.model_step(exe, g, d, pc.ELIMINATED)
         difference = np.abs(a["delta"] - b["delta"]).max()
-        margin = lc.model_solve(exe, lc.Graph(g, g.landmarks, g.landmark_constant, g.observations, max_iterations=0), d)["slerp_margin"]
+        margin = pc.model_solve(exe, lc.Graph(g, g.landmarks, g.landmark_constant, g.observations, max_iterations=0), d)["slerp_margin"]
         print(name, "solvers differ by", difference, "of", np.abs(a["delta"]).max(), "slerp margin", margin)
         assert difference <= 1e-8 and margin > 1e-6
 
 
 def test_the_cases_cover_what_they_name(model):
-    exe, _, d = model
+    exe, d = model
     g = lc.CASES["s3_n30_initial_landmark_pose"](exe, d)
     first = g.observations[np.flatnonzero(g.observations["landmark"] == 1)[0]]
     want = lc.initial_landmark_pose(g.nodes[first["prev_node"]], g.nodes[first["next_node"]], first["interpolation_parameter"],
@@ -225,14 +209,14 @@ def test_the_cases_cover_what_they_name(model):
     assert np.abs(lc.landmark_residual(first, g.nodes[first["prev_node"]], g.nodes[first["next_node"]], want)).max() < 1e-9
     g = lc.CASES["s4_n40_frozen_landmarks"](exe, d)
     assert g.landmark_constant.all() and g.node_constant.any() and not g.node_constant.all()
-    solved = lc.model_solve(exe, g, d)
+    solved = pc.model_solve(exe, g, d)
     assert solved["landmarks"].tobytes() == g.landmarks.tobytes()
     assert solved["nodes"][g.node_constant != 0].tobytes() == g.nodes[g.node_constant != 0].tobytes()
     g = lc.CASES["s6_n120_landmarks_frames_loss"](exe, d)
     assert len(g.frames) > 0 and g.huber_scale > 0 and g.inter_submap.any() and len(g.observations) > 0
     # one landmark closes the loop, on the model (the device's run is tests/test_gpu_pose_graph_landmarks.py's)
     with_it, without, truth = lc.loop_pair()
-    errors = [tc.node_error(truth, lc.model_solve(exe, graph, d)["nodes"]) for graph in (with_it, without)]
+    errors = [tc.node_error(truth, pc.model_solve(exe, graph, d)["nodes"]) for graph in (with_it, without)]
     print("node errors with and without the landmark", errors)
     assert errors[0] < errors[1]
 
@@ -260,15 +244,13 @@ def test_initial_landmark_pose_helper():
 
 
 def test_structure_builder_under_sanitizers(model, tmp_path):
-    """tests/cpp/pose_graph_landmarks_structure_check.cc, a stand-alone program built with -fsanitize=address,undefined: the
-    case lists, promotion and columns under fix_z, a landmark that only constant nodes see, an observation with all six
-    blocks constant, the column cap, bad indices, and build_structure_terms' structure without landmarks."""
-    exe, old, d = model
-    check = str(tmp_path / "pose_graph_landmarks_structure_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
-                           "-Werror", "-o", check, os.path.join(pc.ROOT, "tests", "cpp", "pose_graph_landmarks_structure_check.cc")])
+    """tests/cpp/pose_graph_structure_check.cc, a stand-alone program built with -fsanitize=address,undefined: the case
+    lists with and without landmarks, promotion and columns under fix_z, a landmark that only constant nodes see, an
+    observation with all six blocks constant, the column cap and bad indices."""
+    exe, d = model
+    check = pc.build_structure_check(tmp_path)
     graphs = [make(exe, d) for make in lc.CASES.values()]
-    without = [lc.Graph(make(old, d)) for make in tc.CASES.values()] + [lc.Graph(pc.branches_graph(True))]
+    without = [lc.Graph(make(exe, d)) for make in tc.CASES.values()] + [lc.Graph(pc.branches_graph(True))]
     named = [lc.evaluate_graph(False), lc.evaluate_graph(True)] + [lc.boundary_graph(*k[:3]) for k in lc.STEP_CASES.values()]
     base, truth, _ = tc.synthetic(3, 12, 0, seed=1)
     constant_nodes = np.zeros(12, np.uint8)
@@ -281,13 +263,12 @@ def test_structure_builder_under_sanitizers(model, tmp_path):
     paths = []
     for i, g in enumerate(graphs + without + named):
         paths.append(str(tmp_path / ("graph%d.bin" % i)))
-        lc._write(g, paths[-1], 0, 0, 1e4)
+        pc._write(g, paths[-1], 0, 0, 1e4)
     out = subprocess.check_output([check] + paths).decode().splitlines()
     print("\n".join(out))
     assert len(out) == len(paths) and all(" ok columns " in line for line in out)
-    assert all(line.endswith("same-as-terms") for line in out[len(graphs):len(graphs) + len(without)])
-    fields = [line.split() for line in out[len(graphs) + len(without):]]
-    columns, direct, promoted = [int(f[3]) for f in fields], [int(f[9]) for f in fields], [int(f[11]) for f in fields]
+    fields = [pc.structure_check_fields(line) for line in out[len(graphs) + len(without):]]
+    columns, direct, promoted = [f["columns"] for f in fields], [f["direct"] for f in fields], [f["promoted"] for f in fields]
     # the evaluate graph: three free submaps, 18 promoted nodes, two free landmarks
     assert columns[:2] == [18 + 18 * 6 + 12, 15 + 18 * 5 + 12] and promoted[:2] == [18, 18]
     assert columns[2:5] == [k[3] for k in lc.STEP_CASES.values()] and promoted[2:5] == [44, 40, 10]
@@ -299,15 +280,15 @@ def test_structure_builder_under_sanitizers(model, tmp_path):
     nodes = np.tile(base.nodes[:1], (many, 1))
     rows = [(0, i, i + 1, 0.5, base.nodes[0], 1.0, 1.0) for i in range(0, many, 2)]
     big = lc.Graph(pc.Graph(base.submaps[:0], nodes, base.constraints[:0], gravity=-1), one.landmarks[:1], [1], lc.rows_to_observations(rows))
-    lc._write(big, paths[0], 0, 0, 1e4)
+    pc._write(big, paths[0], 0, 0, 1e4)
     assert subprocess.check_output([check, paths[0]]).decode().split()[-2:] == ["status", "2"]
     big.observations = big.observations[:-1]                                                 # 1 364 promoted nodes fit
-    lc._write(big, paths[0], 0, 0, 1e4)
+    pc._write(big, paths[0], 0, 0, 1e4)
     assert subprocess.check_output([check, paths[0]]).decode().split()[1:4] == ["ok", "columns", str(6 * 1364)]
     for key, index, value in (("landmark", 0, 2), ("landmark", 1, -1), ("prev_node", 0, 12), ("next_node", 1, -1), ("next_node", 0, 4)):
         bad = lc.Graph(frozen_pair, one.landmarks, None, one.observations.copy())
         bad.observations[key][index] = value
-        lc._write(bad, paths[0], 0, 0, 1e4)
+        pc._write(bad, paths[0], 0, 0, 1e4)
         assert subprocess.check_output([check, paths[0]]).decode().split()[-2:] == ["status", "1"], (key, index, value)
 
 

@@ -3,11 +3,10 @@ NOT Ceres) on graphs of S submaps with M nodes a submap: milliseconds a Solve an
 summary (a second, profiled run: the stages are then separated by synchronisations), polled read-backs.
 --terms adds the further terms of dliom_pose_graph_solve_terms to each graph: two fixed frames, one constraining every
 fifth node of the first half and one every fifth of the second, and HuberLoss(1e3) on the loop closures, one more of
-which is 5 m wrong; the model is then tests/cpp/pose_graph_terms_model.cc.
+which is 5 m wrong.
 --landmarks adds 8 landmarks to each graph, seen in turn from every 10th node (dliom_pose_graph_solve_landmarks: two
 promoted nodes a sighting, so 360x100 with its 7 200 promoted nodes is past the column cap and reported as refused); the
-model is then tests/cpp/pose_graph_landmarks_model.cc, run only up to 1 024 columns (its dense reduced system takes
-minutes beyond).
+model is then run only up to 1 024 columns (its dense reduced system takes minutes beyond).
 usage: python tools/pose_graph_bench.py [--sizes 3x100,40x100,360x100] [--repeats 3] [--terms | --landmarks]"""
 import argparse
 import ctypes as C
@@ -39,7 +38,7 @@ def main():
         import pose_graph_terms_common as tc
     if args.landmarks:
         import pose_graph_landmarks_common as lc
-    exe = lc.build_model(d) if args.landmarks else tc.build_model(d) if args.terms else pc.build_model(d)
+    exe = pc.build_model(d)
     for size in args.sizes.split(","):
         s, m = (int(v) for v in size.split("x"))
         if args.landmarks:
@@ -51,7 +50,7 @@ def main():
                 print(json.dumps(dict(submaps=s, nodes=len(g.nodes), landmarks=len(g.landmarks), observations=len(g.observations),
                                       refused=e.status, too_large=e.status == dl.ERR_TOO_LARGE)))
                 continue
-            model = lc.model_solve(exe, g, d) if columns <= 1024 else None
+            model = pc.model_solve(exe, g, d) if columns <= 1024 else None
         elif args.terms:
             g, truth, inter = tc.synthetic(s, m * s, max(1, s // 10), seed=s, max_iterations=10)
             g, inter = tc.false_closure(g, inter, truth, 5.0, submap=1, node=len(g.nodes) // 2, seed=s)
@@ -59,7 +58,7 @@ def main():
             frames = [dict(origin=tc._yaw_pose([1.0, 2.0, 0.0], -0.4), nodes=list(range(0, half, 5))),
                       dict(origin=tc._yaw_pose([0.0, -3.0, 0.5], 2.0), nodes=list(range(half, len(g.nodes), 5)))]
             g = tc.with_fixed_frames(g, truth, frames, seed=s, huber_scale=tc.LOSS_HUBER_SCALE, inter_submap=inter)
-            model = tc.model_solve(exe, g, d)
+            model = pc.model_solve(exe, g, d)
         else:
             g = pc.synthetic(s, m * s, max(1, s // 10), seed=s, max_iterations=10)  # S * M nodes in all
             model = pc.model_solve(exe, g, d)
