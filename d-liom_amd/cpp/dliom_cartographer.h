@@ -18,6 +18,7 @@
 //   dliom::mapping::constraints::SubmapFeatureMatcher         mapping/internal/constraints/constraint_builder_3d.cc:459-529
 //   dliom::io::SubmapSlice / FillSubmapSlice / PaintSubmapSlices  io/submap_painter.h:30-94 (+ CreateOccupancyGrid)
 //   dliom::sensor::CompressedPointCloud                       sensor/compressed_point_cloud.h:36-95
+//   dliom::registration::IterativeClosestPoint                pcl::IterativeClosestPoint as gen_ground_truth_by_ndt_match.cc:190-205 runs it
 //   dliom::mapping::ToProto / FromProto(TrajectoryNode::Data) mapping/trajectory_node.h:39-69 (+ ToProto over a span of nodes)
 //
 // The value types below are layout-compatible stand-ins for Eigen::Vector3f / transform::Rigid3d
@@ -38,6 +39,7 @@
 #include <chrono>
 #include <deque>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <set>
@@ -3391,6 +3393,146 @@ inline TrajectoryNode::Data FromProto(Context* context, const std::string& proto
   return d;
 }
 }  // namespace mapping
+// pcl::IterativeClosestPoint<PointXYZ, PointXYZ> as gen_ground_truth_by_ndt_match.cc:190-205 and
+// LocalTrajectoryBuilder3D::MatchByICP (local_trajectory_builder_3d.cc:937-967) use it, with PCL's method names, on the
+// device (dliom.h "scan alignment by ICP": exact nearest neighbours, a fixed-order least-squares solve).  Parity unpinned
+// against PCL (dliom.h).  Points with a non-finite coordinate take no part, so removeNaNFromPointCloud (:97) is not needed.
+namespace registration {
+struct Matrix4f {  // Eigen::Matrix4f's element access; row-major storage
+  float m[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+  static Matrix4f Identity() { return Matrix4f(); }
+  float& operator()(int row, int col) { return m[4 * row + col]; }
+  float operator()(int row, int col) const { return m[4 * row + col]; }
+};
+class IterativeClosestPoint {
+ public:
+  explicit IterativeClosestPoint(Context* context) : context_(context) {
+    Check(dliom_icp_default_options(&options_), "dliom_icp_default_options");
+    // PCL's own defaults where the tool sets nothing else: 10 iterations, no bound, both epsilons 0
+    options_.max_correspondence_distance = std::sqrt(std::numeric_limits<double>::max());
+    options_.maximum_iterations = 10;
+    options_.transformation_epsilon = 0.0;
+    options_.euclidean_fitness_epsilon = 0.0;
+  }
+  ~IterativeClosestPoint() { Reset(); }
+  IterativeClosestPoint(const IterativeClosestPoint&) = delete;
+  IterativeClosestPoint& operator=(const IterativeClosestPoint&) = delete;
+
+  void setMaxCorrespondenceDistance(double distance) { options_.max_correspondence_distance = distance; }
+  void setMaximumIterations(int iterations) { options_.maximum_iterations = iterations; }
+  void setTransformationEpsilon(double epsilon) { options_.transformation_epsilon = epsilon; }
+  void setEuclideanFitnessEpsilon(double epsilon) { options_.euclidean_fitness_epsilon = epsilon; }
+  // the tool asks for none (:196); outlier rejection by RANSAC is not built
+  void setRANSACIterations(int iterations) {
+    if (iterations != 0) Check(DLIOM_ERR_INVALID_ARGUMENT, "IterativeClosestPoint::setRANSACIterations: only 0");
+  }
+  void setInputSource(const sensor::PointCloud* cloud) { source_ = cloud; }
+  // builds the nearest-neighbour index of the target, as PCL builds its kd-tree here
+  void setInputTarget(const sensor::PointCloud* cloud) {
+    if (cloud == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "IterativeClosestPoint::setInputTarget");
+    Reset();
+    dliom_cloud* target = nullptr;
+    Check(dliom_cloud_create(context_->get(), cloud->empty() ? nullptr : &(*cloud)[0].x, static_cast<int64_t>(cloud->size()), &target),
+          "dliom_cloud_create");
+    const int status = dliom_nn_index_create(context_->get(), target, nullptr, &index_);
+    dliom_cloud_destroy(target);
+    Check(status, "dliom_nn_index_create");
+  }
+  // output (may be null): the source under the final transformation
+  void align(sensor::PointCloud* output, const Matrix4f& guess = Matrix4f::Identity()) {
+    if (source_ == nullptr || index_ == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "IterativeClosestPoint::align: no input");
+    dliom_cloud* source = nullptr;
+    Check(dliom_cloud_create(context_->get(), source_->empty() ? nullptr : &(*source_)[0].x, static_cast<int64_t>(source_->size()),
+                             &source),
+          "dliom_cloud_create");
+    double guess16[16];
+    for (int k = 0; k < 16; ++k) guess16[k] = static_cast<double>(guess.m[k]);
+    dliom_cloud* aligned = nullptr;
+    const int status = dliom_icp_align(index_, source, guess16, &options_, &result_, output != nullptr ? &aligned : nullptr);
+    dliom_cloud_destroy(source);
+    Check(status, "dliom_icp_align");
+    if (output != nullptr) {
+      output->resize(source_->size());
+      const int download = output->empty() ? DLIOM_OK : dliom_cloud_download(aligned, &(*output)[0].x);
+      dliom_cloud_destroy(aligned);
+      Check(download, "dliom_cloud_download");
+    }
+  }
+  bool hasConverged() const { return result_.converged != 0; }
+  double getFitnessScore() const { return result_.fitness_score; }
+  Matrix4f getFinalTransformation() const {
+    Matrix4f out;
+    for (int k = 0; k < 16; ++k) out.m[k] = static_cast<float>(result_.transform[k]);
+    return out;
+  }
+  const dliom_icp_result& result() const { return result_; }  // of the last align, with its reason and counts
+  const dliom_icp_options& options() const { return options_; }
+
+  // gen_ground_truth_by_ndt_match.cc:192-196
+  static std::unique_ptr<IterativeClosestPoint> GroundTruthIcp(Context* context) { return Preset(context, 30.0); }
+  // local_trajectory_builder_3d.cc:942-946
+  static std::unique_ptr<IterativeClosestPoint> MatchByIcp(Context* context) { return Preset(context, 3.0); }
+
+ private:
+  static std::unique_ptr<IterativeClosestPoint> Preset(Context* context, double distance) {
+    std::unique_ptr<IterativeClosestPoint> icp(new IterativeClosestPoint(context));
+    icp->setMaxCorrespondenceDistance(distance);
+    icp->setMaximumIterations(100);
+    icp->setTransformationEpsilon(1e-6);
+    icp->setEuclideanFitnessEpsilon(1e-6);
+    icp->setRANSACIterations(0);
+    return icp;
+  }
+  void Reset() {
+    dliom_nn_index_destroy(index_);
+    index_ = nullptr;
+  }
+  Context* context_;
+  dliom_icp_options options_;
+  dliom_icp_result result_ = {};
+  const sensor::PointCloud* source_ = nullptr;
+  dliom_nn_index* index_ = nullptr;
+};
+
+// The revisit node of gen_ground_truth_by_ndt_match.cc:158-167: among the nodes at least 60 s from node `from`, the one
+// whose position is nearest to it; the first least distance wins.  -1: there is none (the tool would fall back on node 0
+// unasked).  timestamps_ns: one a pose, nanoseconds.
+inline int FindRevisitNode(const std::vector<transform::Rigid3d>& poses, const std::vector<int64_t>& timestamps_ns, size_t from) {
+  if (from >= poses.size() || timestamps_ns.size() != poses.size()) Check(DLIOM_ERR_INVALID_ARGUMENT, "FindRevisitNode");
+  int found = -1;
+  double least = std::numeric_limits<double>::max();
+  for (size_t k = 0; k < poses.size(); ++k) {
+    if (k == from) continue;
+    const int64_t apart = timestamps_ns[k] - timestamps_ns[from];
+    if (static_cast<double>(apart < 0 ? -apart : apart) * 1e-9 < 60.) continue;
+    const transform::Vector3d &a = poses[from].translation(), &b = poses[k].translation();
+    const double dx = a.v[0] - b.v[0], dy = a.v[1] - b.v[1], dz = a.v[2] - b.v[2];
+    const double distance = std::sqrt(dx * dx + dy * dy + dz * dz);
+    if (distance < least) {
+      least = distance;
+      found = static_cast<int>(k);
+    }
+  }
+  return found;
+}
+
+// One line of the tool's ground-truth file (:256-260) as an ostream with its default format writes it: the two stamps, the
+// alignment error (a double), the three rows of (R | t) as floats, the norm of the translation's difference to the
+// pose-graph's estimate (a float), each followed by a blank but the last, which a newline follows.
+inline std::string FormatGroundTruthLine(int64_t stamp_from, int64_t stamp_to, double align_error, const Matrix4f& transformation,
+                                         float difference_norm) {
+  char text[64];
+  std::snprintf(text, sizeof(text), "%lld %lld %g ", static_cast<long long>(stamp_from), static_cast<long long>(stamp_to), align_error);
+  std::string line(text);
+  for (int row = 0; row < 3; ++row)
+    for (int col = 0; col < 4; ++col) {
+      std::snprintf(text, sizeof(text), "%g ", static_cast<double>(transformation(row, col)));
+      line += text;
+    }
+  std::snprintf(text, sizeof(text), "%g\n", static_cast<double>(difference_norm));
+  return line + text;
+}
+}  // namespace registration
 }  // namespace dliom
 
 #endif  // DLIOM_CPP_DLIOM_CARTOGRAPHER_H_

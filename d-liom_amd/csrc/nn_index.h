@@ -1,0 +1,54 @@
+// The exact 3-D nearest-neighbour index (nn_index.hip) as icp.hip sees it: dliom.h "scan alignment by ICP".
+#ifndef DLIOM_CSRC_NN_INDEX_H_
+#define DLIOM_CSRC_NN_INDEX_H_
+
+#include "internal.h"
+
+namespace dliom {
+
+constexpr int kNnShells = DLIOM_NN_MAX_SHELLS;
+
+// Device view of an index, passed by value to the kernels.
+struct NnGridView {
+  const float4* sorted;   // the finite target points by cell: x, y, z and the point's index in the cloud (as bits)
+  const float4* by_index; // every target point in the cloud's order: x, y, z (what a correspondence's sums read)
+  const int* cell_start;  // cells + 1 entries: cell c holds sorted[cell_start[c] .. cell_start[c + 1])
+  int n_finite;
+  int dims[3];
+  float lo[3], hi[3];     // the finite points' bounding box
+  float inv;              // cells a metre
+  double edge;            // 1 / inv, rounded once (0 under the one-cell grid): the stop rule of nn_shell_kernel
+};
+
+// Words of an index's counter block
+enum : int { kNnListCount = 0, kNnByGrid = 1, kNnByBruteForce = 2, kNnNonFinite = 3, kNnCounterWords = 4 };
+
+// One search, only enqueued on the context's stream.  px/py/pz: n query points in HBM; j (-1: none) and d2 (+inf: none):
+// n entries each; key: n 64-bit words and list: n ints of scratch; counters: kNnCounterWords ints of which [kNnListCount]
+// is zero on entry.  The caller zeroes [kNnListCount] behind the search.
+struct NnSearch {
+  const float *px, *py, *pz;
+  int n;
+  int* j;
+  float* d2;
+  unsigned long long* key;  // 8-byte aligned
+  int* list;
+  int* counters;
+};
+int nn_search_enqueue(dliom_nn_index* index, const NnSearch& s, double max_distance_squared, int search);
+NnGridView nn_view(const dliom_nn_index* index);
+dliom_ctx* nn_ctx(const dliom_nn_index* index);
+DevBuf* nn_scratch(dliom_nn_index* index);  // grow-only, free between the index's calls
+int* nn_poll_us(dliom_nn_index* index);
+
+// p = (float)(((r00*x + r01*y) + r02*z) + t0) ... in double from float points, m: 12 doubles (3 rows of r0 r1 r2 t);
+// in place is fine.
+struct Rigid12 {
+  double m[12];
+};
+int nn_transform_enqueue(dliom_ctx* ctx, const float* x, const float* y, const float* z, int n, const Rigid12& m, float* ox,
+                         float* oy, float* oz);
+
+}  // namespace dliom
+
+#endif  // DLIOM_CSRC_NN_INDEX_H_

@@ -13,6 +13,9 @@
 //    download, writes the region once an iteration and has copied it out before it launches anything else or returns;
 //  * kPinFeaturePairs and kPinFeatureResults belong to a feature match (feature_match.hip), likewise an entry point of its
 //    own: it fills the first before its launches and has copied the second out before it returns;
+//  * kPinIcpSums belongs to an alignment or a step of icp.hip, entry points of their own: one read-back an iteration (the
+//    sums of the tree reduction), copied out before the next launch.  The index's creation (nn_index.hip) reads its
+//    bounding box through kPinReadback, in a call of its own;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -67,6 +70,9 @@ constexpr PinRegion kPinPoseGraphSums{4096, 256};
 constexpr PinRegion kPinFeaturePairs{0, 8192 * 32};
 constexpr PinRegion kPinFeatureResults{8192 * 32, 8192 * 48};
 
+// an ICP alignment (icp.hip): the sixteen sums, the count and the search counters of one iteration
+constexpr PinRegion kPinIcpSums{4096, 256};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -111,6 +117,8 @@ static_assert(pins_inside({kPinPoseGraphSums}, kPinnedBytes) && pins_disjoint({k
 static_assert(pins_inside({kPinFeaturePairs, kPinFeatureResults}, kPinnedBytes) &&
                   pins_disjoint({kPinFeaturePairs, kPinFeatureResults}),
               "a feature match's regions");
+static_assert(pins_inside({kPinIcpSums}, kPinnedBytes) && pins_disjoint({kPinIcpSums, kPinReadback}),
+              "an ICP alignment's region (apart from the small read-backs of the helpers it may call)");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

@@ -3345,3 +3345,168 @@ def merge_timed_clouds(ctx, primary, primary_time, secondary, secondary_time, pr
                                            int(primary_time), secondary.h, int(secondary_time), C.byref(h)),
            "dliom_timed_clouds_merge")
     return TimedCloud(ctx, h)
+
+
+# ---- scan alignment by ICP, exact nearest neighbours (include/dliom.h "scan alignment by ICP") ---------------------------
+NN_MAX_SHELLS, NN_MAX_CELLS_PER_AXIS, NN_MAX_CELLS, NN_MAX_POINTS = 3, 1024, 1 << 22, 1 << 24
+ICP_JACOBI_SWEEPS, ICP_TREE_MIN_LEAVES = 12, 2048
+NN_AUTO, NN_BRUTE_FORCE = 0, 1
+ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
+
+
+class NnIndexOptions(C.Structure):
+    _fields_ = [("cell_edge", C.c_double), ("search", C.c_int), ("reserved", C.c_int)]
+
+
+class NnQueryStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("queries", "non_finite", "settled_by_grid", "settled_by_brute_force", "read_backs")] + \
+               [("search_ms", C.c_double)]
+
+
+class NnIndexMemory(C.Structure):
+    _fields_ = [("points", C.c_int64), ("finite_points", C.c_int64), ("cells", C.c_int64), ("dims", C.c_int64 * 3),
+                ("index_bytes", C.c_int64), ("scratch_bytes", C.c_int64), ("cell_edge", C.c_double)]
+
+
+class IcpOptions(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("max_correspondence_distance", "transformation_epsilon", "euclidean_fitness_epsilon",
+                                          "rotation_epsilon", "relative_mse_epsilon")] + \
+               [(f, C.c_int) for f in ("maximum_iterations", "min_correspondences", "search", "reserved")]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("converged", "reason", "iterations", "correspondences")] + \
+               [("transform", C.c_double * 16), ("mse", C.c_double), ("fitness_score", C.c_double)] + \
+               [(f, C.c_int64) for f in ("fitness_count", "read_backs", "settled_by_grid", "settled_by_brute_force")] + \
+               [(f, C.c_double) for f in ("search_ms", "reduce_ms", "solve_ms", "transform_ms")]
+
+
+SYMBOLS += [
+    ("dliom_nn_index_create", C.c_int, [_vp, _vp, C.POINTER(NnIndexOptions), C.POINTER(_vp)]),
+    ("dliom_nn_index_destroy", None, [_vp]),
+    ("dliom_nn_index_memory_stats", C.c_int, [_vp, C.POINTER(NnIndexMemory)]),
+    ("dliom_nn_index_query", C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_int, _i32p, _f32p, C.POINTER(NnQueryStats)]),
+    ("dliom_icp_default_options", C.c_int, [C.POINTER(IcpOptions)]),
+    ("dliom_icp_align", C.c_int, [_vp, _vp, _f64p, C.POINTER(IcpOptions), C.POINTER(IcpResult), C.POINTER(_vp)]),
+    ("dliom_icp_step", C.c_int, [_vp, _vp, C.POINTER(IcpOptions), _i32p, _f32p, _f64p, _i64p, _f64p, _f64p]),
+]
+
+
+def _as_cloud(ctx, points):
+    """(cloud, made here) of a PointCloud or an (n, 3) array"""
+    if isinstance(points, PointCloud):
+        return points, False
+    return PointCloud(ctx, points), True
+
+
+def icp_options(**overrides):
+    """dliom_icp_default_options (the ground-truth tool's values) with fields replaced"""
+    o = IcpOptions()
+    _check(load_library().dliom_icp_default_options(C.byref(o)), "dliom_icp_default_options")
+    for k, v in overrides.items():
+        if k not in dict(IcpOptions._fields_):
+            raise TypeError("no ICP option " + k)
+        setattr(o, k, v)
+    return o
+
+
+def ground_truth_icp_options():
+    """gen_ground_truth_by_ndt_match.cc:192-196"""
+    return icp_options()
+
+
+def match_by_icp_options():
+    """LocalTrajectoryBuilder3D::MatchByICP, local_trajectory_builder_3d.cc:942-946: the same with 3 m"""
+    return icp_options(max_correspondence_distance=3.0)
+
+
+class NnIndex:
+    """Exact nearest neighbours of 3-D points in HBM (dliom_nn_index): a cell grid over the target and a brute-force
+    scan that give the same (j, d2) bits (dliom.h)."""
+
+    def __init__(self, ctx, target, cell_edge=0.0, search=NN_AUTO):
+        self.ctx, self._L = ctx, ctx._L
+        cloud, mine = _as_cloud(ctx, target)
+        h, o = _vp(), NnIndexOptions(float(cell_edge), int(search), 0)
+        try:
+            _check(self._L.dliom_nn_index_create(ctx.h, cloud.h, C.byref(o), C.byref(h)), "dliom_nn_index_create")
+        finally:
+            if mine:
+                cloud.close()
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_nn_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def memory_stats(self):
+        m = NnIndexMemory()
+        _check(self._L.dliom_nn_index_memory_stats(self.h, C.byref(m)), "dliom_nn_index_memory_stats")
+        return {k: (list(getattr(m, k)) if k == "dims" else getattr(m, k)) for k, _ in NnIndexMemory._fields_}
+
+    def query(self, queries, max_distance=np.inf, transform=None, search=NN_AUTO):
+        """-> (j int32 (-1: none), d2 float32 (+inf: none), stats dict)"""
+        cloud, mine = _as_cloud(self.ctx, queries)
+        try:
+            j, d2, st = np.zeros(max(cloud.n, 1), np.int32), np.zeros(max(cloud.n, 1), np.float32), NnQueryStats()
+            t = None if transform is None else _f64(transform).reshape(16)
+            _check(self._L.dliom_nn_index_query(self.h, cloud.h, None if t is None else _p(t, _f64p), float(max_distance),
+                                                int(search), _p(j, _i32p), _p(d2, _f32p), C.byref(st)), "dliom_nn_index_query")
+            return j[:cloud.n], d2[:cloud.n], {k: getattr(st, k) for k, _ in NnQueryStats._fields_}
+        finally:
+            if mine:
+                cloud.close()
+
+
+def _icp_result(r):
+    out = {k: getattr(r, k) for k, _ in IcpResult._fields_ if k != "transform"}
+    out["transform"] = np.array(r.transform, dtype=np.float64).reshape(4, 4)
+    return out
+
+
+class Icp:
+    """pcl::IterativeClosestPoint as the ground-truth tool runs it, on an NnIndex of the target (dliom_icp_align).
+    Parity unpinned against PCL (dliom.h)."""
+
+    def __init__(self, index, options=None):
+        self.index, self._L = index, index._L
+        self.options = options if options is not None else icp_options()
+
+    def align(self, source, guess=None, want_aligned=False):
+        """-> result dict (transform: 4x4 float64), and the aligned points (n, 3) float32 if asked for"""
+        cloud, mine = _as_cloud(self.index.ctx, source)
+        try:
+            g = _f64(np.eye(4) if guess is None else guess).reshape(16)
+            r, h = IcpResult(), _vp()
+            _check(self._L.dliom_icp_align(self.index.h, cloud.h, _p(g, _f64p), C.byref(self.options), C.byref(r),
+                                           C.byref(h) if want_aligned else None), "dliom_icp_align")
+            if not want_aligned:
+                return _icp_result(r)
+            aligned = PointCloud(self.index.ctx, _handle=h)
+            try:
+                return _icp_result(r), aligned.download()
+            finally:
+                aligned.close()
+        finally:
+            if mine:
+                cloud.close()
+
+    def step(self, points):
+        """dliom_icp_step -> dict(j, d2, sums (16,), n, R (3, 3), t (3,))"""
+        cloud, mine = _as_cloud(self.index.ctx, points)
+        try:
+            j, d2 = np.zeros(max(cloud.n, 1), np.int32), np.zeros(max(cloud.n, 1), np.float32)
+            sums, R, t, n = np.zeros(16), np.zeros(9), np.zeros(3), C.c_int64()
+            _check(self._L.dliom_icp_step(self.index.h, cloud.h, C.byref(self.options), _p(j, _i32p), _p(d2, _f32p),
+                                          _p(sums, _f64p), C.byref(n), _p(R, _f64p), _p(t, _f64p)), "dliom_icp_step")
+            return {"j": j[:cloud.n], "d2": d2[:cloud.n], "sums": sums, "n": int(n.value), "R": R.reshape(3, 3), "t": t}
+        finally:
+            if mine:
+                cloud.close()

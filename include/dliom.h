@@ -2121,6 +2121,152 @@ int dliom_range_accumulator_add_timed_cloud(dliom_range_accumulator* accumulator
                                             const float* origins, int num_origins, float min_range, float max_range,
                                             float voxel_filter_size, float current_pose[7], int* num_accumulated);
 
+/* ---- scan alignment by ICP, exact nearest neighbours ------------------------------------------------
+ * gen_ground_truth_by_ndt_match.cc's default method (`icp`, :62): pcl::IterativeClosestPoint on two raw scans (:190-205:
+ * 30 m correspondence distance, 100 iterations, both epsilons 1e-6, no RANSAC); LocalTrajectoryBuilder3D::MatchByICP
+ * (local_trajectory_builder_3d.cc:937-967) carries the same settings with 3 m.  PARITY UNPINNED AGAINST PCL: PCL is
+ * neither in the reference tree nor a dependency here.  What is pinned, bit for bit against a CPU model
+ * (tests/icp_common.py), is this definition, our reading of PCL 1.8's IterativeClosestPoint, TransformationEstimationSVD
+ * and DefaultConvergenceCriteria; where it differs from PCL, this text governs.
+ *
+ * Arithmetic.  Every operation is rounded on its own (no contraction), in the order written, parentheses first and
+ * otherwise left to right.
+ *
+ * Points.  Source and target are clouds of float xyz (dliom_cloud); indices are those of the clouds as given.  A target point
+ * with a non-finite coordinate is never a neighbour; a source point with a non-finite coordinate never has a
+ * correspondence.
+ *
+ * Nearest neighbour.  For query p and target t_j, in float: dx = p.x - t.x, dy, dz likewise; d2 = (dx*dx + dy*dy) + dz*dz.
+ * The neighbour is the j with the least d2 among the finite targets, ties (a d2 that overflowed to +inf included) to
+ * the lowest j.  A correspondence exists iff (double)d2 <= D * D in double, D = the correspondence distance, inclusive;
+ * D = +inf is "no bound".  The search is EXACT: the cell grid and the brute-force scan give the same (j, d2) bits, for
+ * every cell edge.
+ *
+ * Start.  T = guess (double 4x4, row-major, rigid); p_i = (float)(((r00*x + r01*y) + r02*z) + t0) and so on, in double
+ * from the float source point.
+ *
+ * Iteration k = 1, 2, ...  Correspondences of the current p_i: n of them.  n < min_correspondences: stop, not converged,
+ * DLIOM_ICP_NO_CORRESPONDENCES, T and p_i stay, `iterations` = k - 1.  Else sixteen sums in double from the float values
+ * of p_i and q_i = t_j(i): Sp (3), Sq (3), Spq[a][b] = sum p_a * q_b (9, the RAW moments, one pass; the products are
+ * exact in double) and Sd = sum (double)d2.  Every sum runs over the SOURCE INDEX with +0.0 where there is no
+ * correspondence, in one fixed tree: pad to max(2048, the next power of two) leaves with +0.0, then add adjacent pairs
+ * level by level -- a function of the index alone.  (Leaves beyond the next power of two change nothing but a root of
+ * -0.0.)
+ * Solve: cp = Sp / n, cq = Sq / n, H[a][b] = Spq[a][b] - (Sp[a] * Sq[b]) / n.  Horn's matrix
+ *     N = [ Hxx+Hyy+Hzz  Hyz-Hzy      Hzx-Hxz      Hxy-Hyx
+ *           .            Hxx-Hyy-Hzz  Hxy+Hyx      Hzx+Hxz
+ *           .            .            (Hyy-Hxx)-Hzz  Hyz+Hzy
+ *           .            .            .            (Hzz-Hxx)-Hyy ]  (symmetric),
+ * its eigenvectors by DLIOM_ICP_JACOBI_SWEEPS cyclic Jacobi sweeps over (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), each
+ * rotation (skipped when a_pq == 0): theta = (a_qq - a_pp) / (2 * a_pq); tt = (theta >= 0 ? 1 : -1) / (|theta| +
+ * sqrt(theta * theta + 1)); c = 1 / sqrt(tt * tt + 1); s = tt * c; a_pp -= tt * a_pq; a_qq += tt * a_pq; a_pq = 0; for
+ * r != p, q: (a_rp, a_rq) = (c * a_rp - s * a_rq, s * a_rp + c * a_rq); for every r: (v_rp, v_rq) likewise.  The
+ * quaternion (w, x, y, z) is the column of V with the greatest diagonal entry (ties to the lowest column), divided by
+ * its norm sqrt(((w*w + x*x) + y*y) + z*z); R is its rotation matrix, R00 = 1 - 2 * (y*y + z*z), R01 = 2 * (x*y - z*w),
+ * R02 = 2 * (x*z + y*w), R10 = 2 * (x*y + z*w), R11 = 1 - 2 * (x*x + z*z), R12 = 2 * (y*z - x*w), R20 = 2 * (x*z - y*w),
+ * R21 = 2 * (y*z + x*w), R22 = 1 - 2 * (x*x + y*y); t_a = cq_a - ((R_a0 * cp_0 + R_a1 * cp_1) + R_a2 * cp_2).  Only IEEE
+ * double + - * / sqrt, a fixed count, on the host.  A degenerate H (collinear pairs: the greatest eigenvalue repeated)
+ * has no rule of its own: the procedure's output is a proper rotation that attains the least squares, one of several.
+ * Then p_i <- (float)(R p_i + t) in the order of Start, T <- M T with M = [R t; 0 0 0 1] (each entry ((m0*t0 + m1*t1) +
+ * m2*t2), the translation column + m3), mse_k = Sd / n.
+ *
+ * Convergence, tested in this order after iteration k (mse_0 = +inf):
+ *   1. k >= maximum_iterations: DLIOM_ICP_ITERATIONS, reported as converged like PCL does (so 0 runs one iteration);
+ *   2. 0.5 * (((R00 + R11) + R22) - 1) >= 1 - rotation_epsilon and (tx*tx + ty*ty) + tz*tz <= transformation_epsilon:
+ *      DLIOM_ICP_TRANSFORM;
+ *   3. |mse_k - mse_{k-1}| < euclidean_fitness_epsilon: DLIOM_ICP_ABS_MSE;
+ *   4. |mse_k - mse_{k-1}| / mse_{k-1} < relative_mse_epsilon: DLIOM_ICP_REL_MSE.
+ * After the first iteration 3 compares +inf and 4 compares inf / inf = NaN: both false, as is 0 / 0 in 4.
+ *
+ * Fitness score (getFitnessScore()): one more search on the final p_i without a distance bound; the mean of d2 over
+ * the source points that have a neighbour, by the same tree; the count is reported.
+ *
+ * No floating-point atomics anywhere: two calls on one input give the same bytes.  Malformed input fails with
+ * DLIOM_ERR_INVALID_ARGUMENT before anything runs: NULLs, a non-finite or negative option (the correspondence distance
+ * alone may be +inf), maximum_iterations < 0, min_correspondences < 3, a guess with a non-finite entry, a last row other
+ * than 0 0 0 1 or |R^T R - I| > 1e-6 in any entry or det R <= 0, clouds of another context, and an EMPTY target cloud.
+ * A target whose points are all non-finite is accepted: no query has a neighbour, an alignment ends with
+ * DLIOM_ICP_NO_CORRESPONDENCES. */
+#define DLIOM_NN_MAX_SHELLS 3        /* shells of cells walked around a query's cell before the brute-force scan takes it */
+#define DLIOM_NN_MAX_CELLS_PER_AXIS 1024
+#define DLIOM_NN_MAX_CELLS (1 << 22)
+#define DLIOM_NN_MAX_POINTS (1 << 24) /* of a target and of a query cloud */
+#define DLIOM_ICP_JACOBI_SWEEPS 12
+#define DLIOM_ICP_TREE_MIN_LEAVES 2048
+enum { DLIOM_NN_AUTO = 0, DLIOM_NN_BRUTE_FORCE = 1 };
+enum {
+  DLIOM_ICP_NOT_CONVERGED = 0,
+  DLIOM_ICP_ITERATIONS = 1,
+  DLIOM_ICP_TRANSFORM = 2,
+  DLIOM_ICP_ABS_MSE = 3,
+  DLIOM_ICP_REL_MSE = 4,
+  DLIOM_ICP_NO_CORRESPONDENCES = 5
+};
+typedef struct dliom_nn_index dliom_nn_index;
+typedef struct dliom_nn_index_options {
+  double cell_edge; /* metres; 0: automatic (half the edge that puts one point a cell into the bounding box).  Grown until
+                       the grid fits DLIOM_NN_MAX_CELLS_PER_AXIS and DLIOM_NN_MAX_CELLS.  Results never depend on it. */
+  int search;       /* DLIOM_NN_*: what DLIOM_NN_AUTO means for this index's queries */
+  int reserved;     /* 0 */
+} dliom_nn_index_options;
+typedef struct dliom_nn_query_stats {
+  int64_t queries, non_finite;       /* non_finite: queries without a search */
+  int64_t settled_by_grid;           /* by the shell walk */
+  int64_t settled_by_brute_force;    /* by the brute-force scan */
+  int64_t read_backs;
+  double search_ms;                  /* filled only while the context's profiling is on */
+} dliom_nn_query_stats;
+typedef struct dliom_nn_index_memory {
+  int64_t points, finite_points, cells, dims[3], index_bytes, scratch_bytes;
+  double cell_edge; /* the edge in use */
+} dliom_nn_index_memory;
+typedef struct dliom_icp_options {
+  double max_correspondence_distance;
+  double transformation_epsilon;     /* on the squared translation */
+  double euclidean_fitness_epsilon;
+  double rotation_epsilon;           /* 1 - PCL's cosine 0.99999 */
+  double relative_mse_epsilon;
+  int maximum_iterations;
+  int min_correspondences;
+  int search;                        /* DLIOM_NN_* */
+  int reserved;                      /* 0 */
+} dliom_icp_options;
+typedef struct dliom_icp_result {
+  int converged, reason, iterations; /* reason: DLIOM_ICP_* */
+  int correspondences;               /* of the last search of the loop */
+  double transform[16];              /* T, row-major */
+  double mse;                        /* of the last completed iteration; +inf if there is none */
+  double fitness_score;              /* NaN when fitness_count is 0 */
+  int64_t fitness_count;
+  int64_t read_backs;                /* polled read-backs of the call: one an iteration's sums, one for the fitness score */
+  int64_t settled_by_grid, settled_by_brute_force; /* over every search of the call */
+  /* milliseconds of the stages over all iterations (solve_ms: host time of solve and decision); filled (the call then
+   * synchronises the stream) only while the context's profiling is on */
+  double search_ms, reduce_ms, solve_ms, transform_ms;
+} dliom_icp_result;
+/* Builds the cell grid over the finite points of `target` (one polled read-back: the bounding box).  The index keeps its
+ * own copy of the points: the cloud may be destroyed.  One thread at a time per index, like its context; destroy the
+ * index before the context.  options may be NULL (automatic edge, DLIOM_NN_AUTO). */
+int dliom_nn_index_create(dliom_ctx* ctx, const dliom_cloud* target, const dliom_nn_index_options* options,
+                          dliom_nn_index** index);
+void dliom_nn_index_destroy(dliom_nn_index* index);
+int dliom_nn_index_memory_stats(const dliom_nn_index* index, dliom_nn_index_memory* out);
+/* The neighbour of every point of `queries` (transformed by transform16 as in Start when it is not NULL) within
+ * max_distance (+inf: no bound): j_out[i] = -1 and d2_out[i] = +inf where there is none.  search: DLIOM_NN_AUTO (the
+ * index's own choice) or DLIOM_NN_BRUTE_FORCE.  stats may be NULL. */
+int dliom_nn_index_query(dliom_nn_index* index, const dliom_cloud* queries, const double* transform16, double max_distance,
+                         int search, int32_t* j_out, float* d2_out, dliom_nn_query_stats* stats);
+/* The tool's values (gen_ground_truth_by_ndt_match.cc:192-196): 30 m, 100 iterations, both epsilons 1e-6. */
+int dliom_icp_default_options(dliom_icp_options* options);
+/* Aligns `source` to the index's target from guess16.  aligned (may be NULL): the final p_i as a cloud of the context. */
+int dliom_icp_align(dliom_nn_index* index, const dliom_cloud* source, const double* guess16, const dliom_icp_options* options,
+                    dliom_icp_result* result, dliom_cloud** aligned);
+/* Diagnostic: one iteration from the given points (no guess): their correspondences (j, d2 as dliom_nn_index_query
+ * gives them), the sixteen sums (Sp, Sq, Spq row-major, Sd), n, and R (row-major), t -- the identity when
+ * n < min_correspondences. */
+int dliom_icp_step(dliom_nn_index* index, const dliom_cloud* points, const dliom_icp_options* options, int32_t* j_out,
+                   float* d2_out, double* sums16, int64_t* correspondences, double* rotation9, double* translation3);
+
 /* Kernel timing (HIP events on the context's stream). */
 enum {
   DLIOM_KERNEL_RTCSM_SCORE = 0, /* score-volume kernel (dominant) */
