@@ -3532,6 +3532,169 @@ inline std::string FormatGroundTruthLine(int64_t stamp_from, int64_t stamp_to, d
   std::snprintf(text, sizeof(text), "%g\n", static_cast<double>(difference_norm));
   return line + text;
 }
+
+// pcl::ApproximateVoxelGrid<PointXYZ> as PCL 1.8.0 runs it (MatchByNDT filters both clouds with it at 0.2 m), on the HOST:
+// it is sequential by construction -- the output depends on the stream order -- and a device version is open.
+// The statement: inv = 1.0f / leaf; a point's voxel is (floor(x * inv), floor(y * inv), floor(z * inv)) in float, cast to
+// int; its slot is (ix * 7171 + iy * 3079 + iz * 4231) & 511 in int arithmetic (wrapping).  A slot that holds another voxel
+// is flushed to the output first (centroid = float sums / (float)count, the sums taken in stream order) and starts anew;
+// at the end the occupied slots are flushed in slot order.  xyz only; the points are taken to be finite.
+class ApproximateVoxelGrid {
+ public:
+  void setLeafSize(float x, float y, float z) {
+    if (!(x > 0.f) || y != x || z != x) Check(DLIOM_ERR_INVALID_ARGUMENT, "ApproximateVoxelGrid::setLeafSize: one positive edge");
+    leaf_ = x;
+  }
+  void setInputCloud(const sensor::PointCloud* cloud) { input_ = cloud; }
+  void filter(sensor::PointCloud* output) const {
+    if (input_ == nullptr || output == nullptr || output == input_) Check(DLIOM_ERR_INVALID_ARGUMENT, "ApproximateVoxelGrid::filter");
+    struct Slot {
+      int ix, iy, iz, count;
+      float sx, sy, sz;
+    };
+    std::vector<Slot> slots(512, Slot{0, 0, 0, 0, 0.f, 0.f, 0.f});
+    const auto flush = [output](const Slot& s) {
+      const float n = static_cast<float>(s.count);
+      output->push_back(sensor::Vector3f(s.sx / n, s.sy / n, s.sz / n));
+    };
+    output->clear();
+    const float inv = 1.0f / leaf_;
+    for (const sensor::Vector3f& p : *input_) {
+      const int ix = static_cast<int>(std::floor(p.x * inv)), iy = static_cast<int>(std::floor(p.y * inv)),
+                iz = static_cast<int>(std::floor(p.z * inv));
+      const unsigned hash = static_cast<unsigned>(ix) * 7171u + static_cast<unsigned>(iy) * 3079u + static_cast<unsigned>(iz) * 4231u;
+      Slot& s = slots[hash & 511u];
+      if (s.count != 0 && (s.ix != ix || s.iy != iy || s.iz != iz)) {
+        flush(s);
+        s.count = 0;
+      }
+      if (s.count == 0) s = Slot{ix, iy, iz, 0, 0.f, 0.f, 0.f};
+      s.sx += p.x;
+      s.sy += p.y;
+      s.sz += p.z;
+      ++s.count;
+    }
+    for (const Slot& s : slots)
+      if (s.count != 0) flush(s);
+  }
+
+ private:
+  float leaf_ = 0.2f;
+  const sensor::PointCloud* input_ = nullptr;
+};
+
+// pcl::NormalDistributionsTransform<PointXYZ, PointXYZ> as gen_ground_truth_by_ndt_match.cc:142-145,211-222 and
+// LocalTrajectoryBuilder3D::MatchByNDT (local_trajectory_builder_3d.cc:969-1008) use it, with PCL's method names, on the
+// device (dliom.h "scan alignment by NDT").  Parity unpinned against PCL (dliom.h).
+class NormalDistributionsTransform {
+ public:
+  explicit NormalDistributionsTransform(Context* context) : context_(context) {
+    Check(dliom_ndt_default_options(&options_), "dliom_ndt_default_options");
+  }
+  ~NormalDistributionsTransform() { Reset(); }
+  NormalDistributionsTransform(const NormalDistributionsTransform&) = delete;
+  NormalDistributionsTransform& operator=(const NormalDistributionsTransform&) = delete;
+
+  void setTransformationEpsilon(double epsilon) { options_.transformation_epsilon = epsilon; }
+  void setStepSize(double step) { options_.step_size = step; }
+  void setMaximumIterations(int iterations) { options_.maximum_iterations = iterations; }
+  void setOulierRatio(double ratio) { options_.outlier_ratio = ratio; }  // PCL's own spelling
+  void setStepMode(int mode) { options_.step_mode = mode; }              // DLIOM_NDT_STEP_*
+  // call before setInputTarget, which builds the cells (PCL rebuilds them here)
+  void setResolution(float resolution) {
+    if (target_ != nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "NormalDistributionsTransform::setResolution after setInputTarget");
+    options_.resolution = static_cast<double>(resolution);
+  }
+  void setInputSource(const sensor::PointCloud* cloud) { source_ = cloud; }
+  // builds the target's cells and, for getFitnessScore(), its nearest-neighbour index
+  void setInputTarget(const sensor::PointCloud* cloud, bool want_fitness_score = true) {
+    if (cloud == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "NormalDistributionsTransform::setInputTarget");
+    Reset();
+    dliom_cloud* target = nullptr;
+    Check(dliom_cloud_create(context_->get(), cloud->empty() ? nullptr : &(*cloud)[0].x, static_cast<int64_t>(cloud->size()), &target),
+          "dliom_cloud_create");
+    int status = dliom_ndt_target_create(context_->get(), target, &options_, &target_);
+    if (status == DLIOM_OK && want_fitness_score) status = dliom_nn_index_create(context_->get(), target, nullptr, &index_);
+    dliom_cloud_destroy(target);
+    if (status != DLIOM_OK) Reset();
+    Check(status, "dliom_ndt_target_create");
+  }
+  // output (may be null): the source under the final transformation
+  void align(sensor::PointCloud* output, const Matrix4f& guess = Matrix4f::Identity()) {
+    if (source_ == nullptr || target_ == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "NormalDistributionsTransform::align: no input");
+    dliom_cloud* source = nullptr;
+    Check(dliom_cloud_create(context_->get(), source_->empty() ? nullptr : &(*source_)[0].x, static_cast<int64_t>(source_->size()),
+                             &source),
+          "dliom_cloud_create");
+    double guess16[16];
+    for (int k = 0; k < 16; ++k) guess16[k] = static_cast<double>(guess.m[k]);
+    dliom_cloud* aligned = nullptr;
+    const int status = dliom_ndt_align(target_, source, guess16, &options_, index_, &result_, output != nullptr ? &aligned : nullptr);
+    dliom_cloud_destroy(source);
+    Check(status, "dliom_ndt_align");
+    if (output != nullptr) {
+      output->resize(source_->size());
+      const int download = output->empty() ? DLIOM_OK : dliom_cloud_download(aligned, &(*output)[0].x);
+      dliom_cloud_destroy(aligned);
+      Check(download, "dliom_cloud_download");
+    }
+  }
+  bool hasConverged() const { return result_.converged != 0; }
+  double getFitnessScore() const { return result_.fitness_score; }
+  double getTransformationProbability() const { return result_.transformation_probability; }
+  int getFinalNumIteration() const { return result_.iterations; }
+  Matrix4f getFinalTransformation() const {
+    Matrix4f out;
+    for (int k = 0; k < 16; ++k) out.m[k] = static_cast<float>(result_.transform[k]);
+    return out;
+  }
+  const dliom_ndt_result& result() const { return result_; }
+  const dliom_ndt_options& options() const { return options_; }
+
+  // gen_ground_truth_by_ndt_match.cc:142-145 and local_trajectory_builder_3d.cc:981-984: epsilon 0.01, step 0.1, resolution
+  // 1.0, 35 iterations -- the library's defaults
+  static std::unique_ptr<NormalDistributionsTransform> GroundTruthNdt(Context* context) {
+    return std::unique_ptr<NormalDistributionsTransform>(new NormalDistributionsTransform(context));
+  }
+
+ private:
+  void Reset() {
+    dliom_ndt_target_destroy(target_);
+    dliom_nn_index_destroy(index_);
+    target_ = nullptr;
+    index_ = nullptr;
+  }
+  Context* context_;
+  dliom_ndt_options options_;
+  dliom_ndt_result result_ = {};
+  const sensor::PointCloud* source_ = nullptr;
+  dliom_ndt_target* target_ = nullptr;
+  dliom_nn_index* index_ = nullptr;
+};
+
+// LocalTrajectoryBuilder3D::MatchByNDT (local_trajectory_builder_3d.cc:969-1008): both clouds through ApproximateVoxelGrid
+// at 0.2 m, NDT of the filtered current scan against the filtered previous one from init_guess; -> the final
+// transformation's rotation (row-major) and translation, as floats like the reference's Matrix4f.  The target is rebuilt
+// for every pair.
+inline void MatchByNDT(Context* context, const sensor::PointCloud& pre_scan, const sensor::PointCloud& cur_scan, const Matrix4f& init_guess,
+                       float rotation9[9], float translation3[3]) {
+  sensor::PointCloud pre_filtered, cur_filtered;
+  ApproximateVoxelGrid filter;
+  filter.setLeafSize(0.2f, 0.2f, 0.2f);
+  filter.setInputCloud(&pre_scan);
+  filter.filter(&pre_filtered);
+  filter.setInputCloud(&cur_scan);
+  filter.filter(&cur_filtered);
+  NormalDistributionsTransform ndt(context);
+  ndt.setInputSource(&cur_filtered);
+  ndt.setInputTarget(&pre_filtered, false);
+  ndt.align(nullptr, init_guess);
+  const Matrix4f t = ndt.getFinalTransformation();
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) rotation9[3 * r + c] = t(r, c);
+    translation3[r] = t(r, 3);
+  }
+}
 }  // namespace registration
 }  // namespace dliom
 

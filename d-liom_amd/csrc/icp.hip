@@ -3,12 +3,11 @@
 // is stated once, in the header; the kernels and the host solve below follow it operation for operation.
 //
 // An iteration is: search (nn_index.hip), tree reduction, solve and decision, transform.
-//   icp_reduce_kernel  one workgroup per 2048 consecutive source indices: a lane sums the sixteen quantities of 8
-//                      adjacent leaves pairwise, the workgroup its 256 lanes pairwise through LDS -- the subtree of the
-//                      header's fixed tree over those 2048 leaves, whatever the launch geometry
-//   icp_finish_kernel  one workgroup: the tree over the workgroups' partial sums (padded with +0.0 to a power of two),
-//                      then the sums, the count and the search counters into the page-locked block (kPinIcpSums) and the
-//                      completion word that wait_done() polls
+//   tree_reduce_kernel (tree_reduce.h)  the header's fixed tree over 2048 consecutive source indices a workgroup, sixteen
+//                      quantities a leaf (IcpLeaves::leaf), whatever the launch geometry
+//   icp_finish_kernel  one workgroup: the tree over the workgroups' partial sums (tree_finish), then the sums, the count
+//                      and the search counters into the page-locked block (kPinIcpSums) and the completion word that
+//                      wait_done() polls
 //   the solve          on the host, in double (nothing in the compiler's documents says that double division and sqrt
 //                      are correctly rounded on the device): one polled read-back an iteration, counted in the result
 //   nn_transform_kernel (nn_index.hip)  p <- (float)(R p + t)
@@ -21,14 +20,12 @@
 
 #include "device_common.h"
 #include "nn_index.h"
+#include "tree_reduce.h"
 
 namespace dliom {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kLeavesPerLane = 8;
-constexpr int kLeavesPerBlock = kThreads * kLeavesPerLane;
-static_assert(kLeavesPerBlock == DLIOM_ICP_TREE_MIN_LEAVES, "the tree's least size is one workgroup's subtree");
+constexpr int kThreads = kTreeThreads;
 constexpr int kSums = 16;  // Sp (3), Sq (3), Spq (9, row-major), Sd
 
 struct IcpLeaves {
@@ -37,6 +34,23 @@ struct IcpLeaves {
   const float* d2;
   const float4* by_index;
   int n;
+  __device__ __forceinline__ void leaf(int i, double v[kSums], int* count) const {
+    const bool has = i < n && j[i] >= 0;
+    if (has) {
+      const double p[3] = {px[i], py[i], pz[i]};
+      const float4 t = by_index[j[i]];
+      const double q[3] = {t.x, t.y, t.z};
+      for (int a = 0; a < 3; ++a) {
+        v[a] = p[a];
+        v[3 + a] = q[a];
+        for (int b = 0; b < 3; ++b) v[6 + 3 * a + b] = p[a] * q[b];
+      }
+      v[15] = static_cast<double>(d2[i]);
+    } else {
+      for (int k = 0; k < kSums; ++k) v[k] = 0.0;
+    }
+    *count = has ? 1 : 0;
+  }
 };
 
 struct IcpReadback {  // kPinIcpSums
@@ -47,72 +61,11 @@ struct IcpReadback {  // kPinIcpSums
 };
 static_assert(sizeof(IcpReadback) <= kPinIcpSums.bytes, "the read-back fits its region");
 
-// The subtree over the W leaves from `first` (W a power of two): left half + right half
-template <int W>
-__device__ __forceinline__ void subtree(const IcpLeaves& L, int first, double v[kSums], int* count) {
-  if constexpr (W == 1) {
-    const bool has = first < L.n && L.j[first] >= 0;
-    if (has) {
-      const double p[3] = {L.px[first], L.py[first], L.pz[first]};
-      const float4 t = L.by_index[L.j[first]];
-      const double q[3] = {t.x, t.y, t.z};
-      for (int a = 0; a < 3; ++a) {
-        v[a] = p[a];
-        v[3 + a] = q[a];
-        for (int b = 0; b < 3; ++b) v[6 + 3 * a + b] = p[a] * q[b];
-      }
-      v[15] = static_cast<double>(L.d2[first]);
-    } else {
-      for (int k = 0; k < kSums; ++k) v[k] = 0.0;
-    }
-    *count = has ? 1 : 0;
-  } else {
-    double r[kSums];
-    int c = 0;
-    subtree<W / 2>(L, first, v, count);
-    subtree<W / 2>(L, first + W / 2, r, &c);
-    for (int k = 0; k < kSums; ++k) v[k] = v[k] + r[k];
-    *count += c;
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void icp_reduce_kernel(IcpLeaves L, double* __restrict__ partials, int* __restrict__ counts) {
-  __shared__ double lds[kThreads * kSums];
-  __shared__ int lds_count[kThreads];
-  double v[kSums];
-  int count = 0;
-  subtree<kLeavesPerLane>(L, (static_cast<int>(blockIdx.x) * kThreads + threadIdx.x) * kLeavesPerLane, v, &count);
-  for (int k = 0; k < kSums; ++k) lds[threadIdx.x * kSums + k] = v[k];
-  lds_count[threadIdx.x] = count;
-  for (int w = 1; w < kThreads; w <<= 1) {  // adjacent pairs, level by level
-    __syncthreads();
-    const int pairs = kThreads / (2 * w);
-    for (int e = threadIdx.x; e < pairs * kSums; e += kThreads) {
-      const int left = (e / kSums) * 2 * w, k = e % kSums;
-      lds[left * kSums + k] = lds[left * kSums + k] + lds[(left + w) * kSums + k];
-    }
-    if (static_cast<int>(threadIdx.x) < pairs) lds_count[threadIdx.x * 2 * w] += lds_count[threadIdx.x * 2 * w + w];
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) partials[static_cast<size_t>(blockIdx.x) * kSums + threadIdx.x] = lds[threadIdx.x];
-  if (threadIdx.x == 0) counts[blockIdx.x] = lds_count[0];
-}
-
 // partials: room for P2 >= P entries, P2 a power of two
 __global__ __launch_bounds__(kThreads) void icp_finish_kernel(double* partials, const int* __restrict__ counts, int P, int P2,
                                                               int* counters, const unsigned* max_sq, IcpReadback* out,
                                                               unsigned* done_word, unsigned done_seq) {
-  for (int e = P * kSums + threadIdx.x; e < P2 * kSums; e += kThreads) partials[e] = 0.0;
-  for (int w = 1; w < P2; w <<= 1) {
-    __syncthreads();
-    const int pairs = P2 / (2 * w);
-    for (int e = threadIdx.x; e < pairs * kSums; e += kThreads) {
-      const size_t left = static_cast<size_t>(e / kSums) * 2 * w;
-      const int k = e % kSums;
-      partials[left * kSums + k] = partials[left * kSums + k] + partials[(left + w) * kSums + k];
-    }
-  }
-  __syncthreads();
+  tree_finish<kSums>(partials, P, P2);
   if (threadIdx.x < kSums) out->sums[threadIdx.x] = partials[threadIdx.x];
   if (threadIdx.x == 0) {
     long long n = 0;
@@ -284,9 +237,7 @@ int icp_carve(dliom_nn_index* index, int n, IcpWork* w) {
   w->index = index;
   w->ctx = nn_ctx(index);
   w->n = n;
-  w->P = static_cast<int>(blocks_of(std::max(n, 1), kLeavesPerBlock));
-  w->P2 = 1;
-  while (w->P2 < w->P) w->P2 <<= 1;
+  tree_geometry(n, &w->P, &w->P2);
   const size_t per = align256(4 * static_cast<size_t>(std::max(n, 1)));
   const size_t partial_bytes = align256(static_cast<size_t>(w->P2) * kSums * sizeof(double));
   DevBuf* scratch = nn_scratch(index);
@@ -320,7 +271,7 @@ int icp_search_and_sum(IcpWork* w, double max_d2, int search, IcpReadback* out) 
   DLIOM_TRY(w->mark());
   const NnGridView g = nn_view(w->index);
   const IcpLeaves L{w->search.px, w->search.py, w->search.pz, w->search.j, w->search.d2, g.by_index, w->n};
-  hipLaunchKernelGGL(icp_reduce_kernel, dim3(static_cast<unsigned>(w->P)), dim3(kThreads), 0, ctx->stream, L, w->partials, w->counts);
+  hipLaunchKernelGGL((tree_reduce_kernel<kSums, IcpLeaves>), dim3(static_cast<unsigned>(w->P)), dim3(kThreads), 0, ctx->stream, L, w->partials, w->counts);
   DLIOM_HIP_TRY(hipGetLastError());
   IcpReadback* const host = pinned_at<IcpReadback>(ctx, kPinIcpSums);
   const unsigned seq = next_done_seq(ctx);
@@ -338,6 +289,23 @@ int icp_search_and_sum(IcpWork* w, double max_d2, int search, IcpReadback* out) 
 }
 
 }  // namespace
+
+// nn_index.h: the fitness score of n points in HBM (ndt.hip's final points): one search without a bound, one read-back
+int icp_fitness_of(dliom_nn_index* index, const float* x, const float* y, const float* z, int n, double* score, long long* count) {
+  IcpWork w;
+  DLIOM_TRY(icp_carve(index, n, &w));
+  if (n > 0) {
+    DLIOM_HIP_TRY(hipMemcpyAsync(w.px, x, 4 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, w.ctx->stream));
+    DLIOM_HIP_TRY(hipMemcpyAsync(w.py, y, 4 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, w.ctx->stream));
+    DLIOM_HIP_TRY(hipMemcpyAsync(w.pz, z, 4 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, w.ctx->stream));
+  }
+  IcpReadback rb;
+  DLIOM_TRY(icp_search_and_sum(&w, std::numeric_limits<double>::infinity(), DLIOM_NN_AUTO, &rb));
+  *count = rb.n;
+  *score = rb.n > 0 ? rb.sums[15] / static_cast<double>(rb.n) : std::numeric_limits<double>::quiet_NaN();
+  return DLIOM_OK;
+}
+
 }  // namespace dliom
 
 extern "C" {

@@ -1,0 +1,1037 @@
+// Scan alignment by NDT (dliom.h "scan alignment by NDT"): pcl::NormalDistributionsTransform as
+// LocalTrajectoryBuilder3D::MatchByNDT and gen_ground_truth_by_ndt_match.cc's `--method ndt` run it.  The definition is
+// stated once, in the header; the kernels and the host steps below follow it operation for operation.
+//
+// The target (dliom_ndt_target_create):
+//   ndt_key_kernel      a lane a target point: its 63-bit cell key (z high, x low), or the skip key
+//   hipcub radix sort   stable, by key: a cell's points come out in ascending point index
+//   ndt_head_kernel     segment heads; their inclusive sum numbers the cells; ndt_bounds_kernel writes each cell's first
+//                       position and key
+//   ndt_cell_sums_kernel  a workgroup a cell: n and the nine sums in the header's fixed tree -- 256 leaves at a time
+//                       through LDS, longer cells in aligned chunks of 256 whose partial sums meet in a binary counter
+//                       (the same tree, whatever the cell's length)
+//   the per-cell step   on the host, in double (division and sqrt, as ICP's solve): mean, covariance, Jacobi, icov; the
+//                       valid cells' keys, means and icov go back up once, sorted by key
+// An evaluation (the hot path):
+//   ndt_eval_kernel<G, H>  a lane a source point: transform, nine binary searches (a row of three x-neighbours is
+//                       contiguous in key order), the 7 / 21 / 28 values in registers in the header's order, then one
+//                       store a value into the leaf arrays in HBM (224 B a point at most)
+//   tree_reduce_kernel (tree_reduce.h) and ndt_finish_kernel  ICP's fixed tree over the source index; the sums and the
+//                       pair count into the page-locked block (kPinNdtSums) and the completion word: one polled read-back
+// The pseudo-inverse, the step length and every decision run on the host between evaluations.
+#include <hipcub/hipcub.hpp>
+
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "device_common.h"
+#include "nn_index.h"
+#include "tree_reduce.h"
+
+struct dliom_ndt_target {
+  dliom_ctx* ctx = nullptr;
+  double resolution = 0.0;
+  int min_points = 0;
+  int64_t n_points = 0, n_kept = 0, n_valid = 0;
+  std::vector<dliom_ndt_cell> cells;  // every cell, in key order
+  dliom::DevBuf table;                // the valid cells: keys (8 B each), then mean and icov (72 B each)
+  size_t cell_data_at = 0;
+  dliom::DevBuf scratch;              // an evaluation's leaves, partial sums and counts
+  int poll_us = 150;
+  int64_t build_read_backs = 0;
+  double build_ms = 0.0;
+};
+
+namespace dliom {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kHalf = DLIOM_NDT_MAX_CELL_INDEX;
+constexpr unsigned long long kSkipKey = ~0ull;
+constexpr int kCellDoubles = 9;  // mean (3), icov 00 01 02 11 12 22
+
+__host__ __device__ inline unsigned long long ndt_key(int ix, int iy, int iz) {
+  return (static_cast<unsigned long long>(iz + kHalf) << 42) | (static_cast<unsigned long long>(iy + kHalf) << 21) |
+         static_cast<unsigned long long>(ix + kHalf);
+}
+
+// ---- the target --------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void ndt_key_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                           const float* __restrict__ z, int n, float inv,
+                                                           unsigned long long* __restrict__ keys, int* __restrict__ index) {
+  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const float f[3] = {floorf(x[i] * inv), floorf(y[i] * inv), floorf(z[i] * inv)};
+  bool ok = isfinite(x[i]) && isfinite(y[i]) && isfinite(z[i]);
+  for (int a = 0; a < 3; ++a) ok = ok && f[a] >= -static_cast<float>(kHalf) && f[a] < static_cast<float>(kHalf);
+  keys[i] = ok ? ndt_key(static_cast<int>(f[0]), static_cast<int>(f[1]), static_cast<int>(f[2])) : kSkipKey;
+  index[i] = i;
+}
+
+// head[i] = 1 where a cell starts; *kept (n on entry) = the first position that holds the skip key
+__global__ __launch_bounds__(kThreads) void ndt_head_kernel(const unsigned long long* __restrict__ keys, int n,
+                                                            unsigned* __restrict__ head, unsigned* __restrict__ kept) {
+  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long k = keys[i];
+  const bool first = i == 0 || keys[i - 1] != k;
+  head[i] = first && k != kSkipKey ? 1u : 0u;
+  if (first && k == kSkipKey) *kept = static_cast<unsigned>(i);
+}
+
+// cell_first: cells + 1 entries
+__global__ __launch_bounds__(kThreads) void ndt_bounds_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ head,
+                                                              const unsigned* __restrict__ inclusive, int n, int cells, int kept,
+                                                              int* __restrict__ cell_first, unsigned long long* __restrict__ cell_key) {
+  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i == 0) cell_first[cells] = kept;
+  if (i >= n || head[i] == 0u) return;
+  const int c = static_cast<int>(inclusive[i]) - 1;
+  if (c < 0 || c >= cells) return;
+  cell_first[c] = i;
+  cell_key[c] = keys[i];
+}
+
+// sums: cells x 9 (S 0..2, Q 00 01 02 11 12 22)
+__global__ __launch_bounds__(kThreads) void ndt_cell_sums_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                                 const float* __restrict__ z, const int* __restrict__ sorted_index,
+                                                                 const int* __restrict__ cell_first, double* __restrict__ sums) {
+  __shared__ double lds[kThreads * 9];
+  __shared__ double stack[17 * 9];  // the binary counter of the chunks' partial sums: level l holds 2^l chunks
+  const int c = static_cast<int>(blockIdx.x);
+  const int first = cell_first[c], m = cell_first[c + 1] - first;
+  int m2 = 1;
+  while (m2 < m) m2 <<= 1;
+  const int width = m2 < kThreads ? m2 : kThreads;  // leaves of a chunk
+  const int chunks = m2 / width;
+  for (int chunk = 0; chunk < chunks; ++chunk) {
+    const int at = chunk * width + static_cast<int>(threadIdx.x);
+    double v[9];
+    if (static_cast<int>(threadIdx.x) < width && at < m) {
+      const int j = sorted_index[first + at];
+      const double p[3] = {x[j], y[j], z[j]};
+      v[0] = p[0];
+      v[1] = p[1];
+      v[2] = p[2];
+      v[3] = p[0] * p[0];
+      v[4] = p[0] * p[1];
+      v[5] = p[0] * p[2];
+      v[6] = p[1] * p[1];
+      v[7] = p[1] * p[2];
+      v[8] = p[2] * p[2];
+    } else {
+      for (int k = 0; k < 9; ++k) v[k] = 0.0;
+    }
+    __syncthreads();  // the previous chunk's root has been taken
+    for (int k = 0; k < 9; ++k) lds[threadIdx.x * 9 + k] = v[k];
+    for (int w = 1; w < width; w <<= 1) {
+      __syncthreads();
+      const int pairs = width / (2 * w);
+      for (int e = threadIdx.x; e < pairs * 9; e += kThreads) {
+        const int left = (e / 9) * 2 * w, k = e % 9;
+        lds[left * 9 + k] = lds[left * 9 + k] + lds[(left + w) * 9 + k];
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {  // lane k carries sum k through the counter
+      double carry = lds[threadIdx.x];
+      int level = 0;
+      while ((chunk >> level) & 1) {
+        carry = stack[level * 9 + threadIdx.x] + carry;
+        ++level;
+      }
+      stack[level * 9 + threadIdx.x] = carry;
+      if (chunk == chunks - 1) sums[static_cast<size_t>(c) * 9 + threadIdx.x] = carry;
+    }
+  }
+}
+
+// ---- the evaluation ------------------------------------------------------------------------------------------------------
+struct NdtTable {
+  const unsigned long long* keys;  // the valid cells, ascending
+  const double* cell;              // 9 doubles each
+  int cells;
+  float inv, r2;
+  double d1, d2;
+};
+
+// T(p) and the coefficient rows of the header's point derivatives
+struct NdtPose {
+  double R[9], t[3];
+  double J[3][3][3];  // [angle][component][coefficient]; J[0][0] is not used (the component is +0.0)
+  double H[6][3][3];  // 33 34 35 44 45 55; [0..2][0] are not used
+};
+
+__device__ __forceinline__ double ndt_exp(double u) {
+  if (u < -708.0) return 0.0;
+  if (u != u) return u;
+  if (u > 708.0) return __longlong_as_double(0x7ff0000000000000ll);
+  const double k = rint(u * 0x1.71547652b82fep+0);
+  const double r = (u - k * 0x1.62e42fee00000p-1) - k * 0x1.a39ef35793c76p-33;
+  constexpr double c[14] = {1.0,
+                            1.0,
+                            1.0 / 2.0,
+                            1.0 / 6.0,
+                            1.0 / 24.0,
+                            1.0 / 120.0,
+                            1.0 / 720.0,
+                            1.0 / 5040.0,
+                            1.0 / 40320.0,
+                            1.0 / 362880.0,
+                            1.0 / 3628800.0,
+                            1.0 / 39916800.0,
+                            1.0 / 479001600.0,
+                            1.0 / 6227020800.0};
+  double p = c[13];
+#pragma unroll
+  for (int n = 12; n >= 0; --n) p = p * r + c[n];
+  return p * __longlong_as_double(static_cast<long long>(static_cast<int>(k) + 1023) << 52);
+}
+
+__device__ __forceinline__ double dot3(const double a[3], double x0, double x1, double x2) { return (a[0] * x0 + a[1] * x1) + a[2] * x2; }
+
+constexpr int ndt_sums(bool G, bool H) { return (G ? 7 : 0) + (H ? 21 : 0); }
+
+// leaves: S arrays of n; pairs: n
+template <bool G, bool H>
+__global__ __launch_bounds__(kThreads) void ndt_eval_kernel(NdtTable T, NdtPose P, const float* __restrict__ sx, const float* __restrict__ sy,
+                                                            const float* __restrict__ sz, int n, double* __restrict__ leaves,
+                                                            int* __restrict__ pairs) {
+  constexpr int S = ndt_sums(G, H);
+  constexpr int kH0 = G ? 7 : 0;
+  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n) return;
+  double acc[S];
+#pragma unroll
+  for (int k = 0; k < S; ++k) acc[k] = 0.0;
+  int count = 0;
+  const double x0 = sx[i], x1 = sy[i], x2 = sz[i];
+  const float q[3] = {static_cast<float>(((P.R[0] * x0 + P.R[1] * x1) + P.R[2] * x2) + P.t[0]),
+                      static_cast<float>(((P.R[3] * x0 + P.R[4] * x1) + P.R[5] * x2) + P.t[1]),
+                      static_cast<float>(((P.R[6] * x0 + P.R[7] * x1) + P.R[8] * x2) + P.t[2])};
+  const float f[3] = {floorf(q[0] * T.inv), floorf(q[1] * T.inv), floorf(q[2] * T.inv)};
+  bool live = isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) live = live && f[a] >= -static_cast<float>(kHalf + 1) && f[a] <= static_cast<float>(kHalf);
+  if (live && T.cells > 0) {
+    const int ix = static_cast<int>(f[0]), iy = static_cast<int>(f[1]), iz = static_cast<int>(f[2]);
+    // the point's derivative vectors
+    double Jv[3][3], Hv[6][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) Jv[a][r] = (a == 0 && r == 0) ? 0.0 : dot3(P.J[a][r], x0, x1, x2);
+    if constexpr (H) {
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) Hv[a][r] = (a < 3 && r == 0) ? 0.0 : dot3(P.H[a][r], x0, x1, x2);
+    }
+    const int xlo = max(ix - 1, -kHalf), xhi = min(ix + 1, kHalf - 1);
+    for (int dz = -1; dz <= 1; ++dz) {
+      const int cz = iz + dz;
+      if (cz < -kHalf || cz >= kHalf) continue;
+      for (int dy = -1; dy <= 1; ++dy) {
+        const int cy = iy + dy;
+        if (cy < -kHalf || cy >= kHalf || xlo > xhi) continue;
+        const unsigned long long klo = ndt_key(xlo, cy, cz), khi = ndt_key(xhi, cy, cz);
+        int lo = 0, hi = T.cells;  // the first cell with key >= klo
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (T.keys[mid] < klo)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        for (int c = lo; c < T.cells && T.keys[c] <= khi; ++c) {
+          const double* cell = T.cell + static_cast<size_t>(c) * kCellDoubles;
+          const double mean[3] = {cell[0], cell[1], cell[2]};
+          const float dx = q[0] - static_cast<float>(mean[0]), dy2 = q[1] - static_cast<float>(mean[1]),
+                      dz2 = q[2] - static_cast<float>(mean[2]);
+          if (!((dx * dx + dy2 * dy2) + dz2 * dz2 <= T.r2)) continue;
+          ++count;
+          const double ic[3][3] = {{cell[3], cell[4], cell[5]}, {cell[4], cell[6], cell[7]}, {cell[5], cell[7], cell[8]}};
+          const double xt[3] = {static_cast<double>(q[0]) - mean[0], static_cast<double>(q[1]) - mean[1],
+                                static_cast<double>(q[2]) - mean[2]};
+          double w[3];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) w[r] = dot3(ic[r], xt[0], xt[1], xt[2]);
+          const double qq = (xt[0] * w[0] + xt[1] * w[1]) + xt[2] * w[2];
+          const double e = ndt_exp(-(T.d2 * qq) * 0.5);
+          double fe = T.d2 * e;
+          if (fe > 1.0 || fe < 0.0 || fe != fe) continue;
+          if constexpr (G) acc[0] += -T.d1 * e;
+          fe = fe * T.d1;
+          double cJ[6][3], u[6];
+#pragma unroll
+          for (int a = 0; a < 6; ++a) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) cJ[a][r] = a < 3 ? ic[r][a] : dot3(ic[r], Jv[a - 3][0], Jv[a - 3][1], Jv[a - 3][2]);
+            u[a] = (xt[0] * cJ[a][0] + xt[1] * cJ[a][1]) + xt[2] * cJ[a][2];
+            if constexpr (G) acc[1 + a] += u[a] * fe;
+          }
+          if constexpr (H) {
+            int slot = kH0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+              for (int b = a; b < 6; ++b) {
+                double h = 0.0;
+                if (a >= 3) {  // b >= a
+                  const int which = a == 3 ? b - 3 : (a == 4 ? b - 1 : 5);
+                  double v[3];
+#pragma unroll
+                  for (int r = 0; r < 3; ++r) v[r] = dot3(ic[r], Hv[which][0], Hv[which][1], Hv[which][2]);
+                  h = (xt[0] * v[0] + xt[1] * v[1]) + xt[2] * v[2];
+                }
+                const double k = b < 3 ? cJ[a][b] : (Jv[b - 3][0] * cJ[a][0] + Jv[b - 3][1] * cJ[a][1]) + Jv[b - 3][2] * cJ[a][2];
+                acc[slot] += fe * ((((-T.d2) * u[a]) * u[b] + h) + k);
+                ++slot;
+              }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < S; ++k) leaves[static_cast<size_t>(k) * n + i] = acc[k];
+  pairs[i] = count;
+}
+
+template <int S>
+struct NdtLeaves {
+  const double* v;
+  const int* pairs;
+  int n;
+  __device__ __forceinline__ void leaf(int i, double out[S], int* count) const {
+    if (i < n) {
+      for (int k = 0; k < S; ++k) out[k] = v[static_cast<size_t>(k) * n + i];
+      *count = pairs[i];
+    } else {
+      for (int k = 0; k < S; ++k) out[k] = 0.0;
+      *count = 0;
+    }
+  }
+};
+
+struct NdtReadback {  // kPinNdtSums
+  double sums[28];
+  long long pairs;
+};
+static_assert(sizeof(NdtReadback) <= kPinNdtSums.bytes, "the read-back fits its region");
+
+template <int S>
+__global__ __launch_bounds__(kTreeThreads) void ndt_finish_kernel(double* partials, const int* __restrict__ counts, int P, int P2,
+                                                                  NdtReadback* out, unsigned* done_word, unsigned done_seq) {
+  tree_finish<S>(partials, P, P2);
+  if (threadIdx.x < S) out->sums[threadIdx.x] = partials[threadIdx.x];
+  if (threadIdx.x == 0) {
+    long long n = 0;
+    for (int b = 0; b < P; ++b) n += counts[b];
+    out->pairs = n;
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence_system();
+    *reinterpret_cast<volatile unsigned*>(done_word) = done_seq;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void ndt_max_norm_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                                const float* __restrict__ z, int n, unsigned* max_sq) {
+  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
+  note_kept(i < n ? norm_word(x[i], y[i], z[i]) : 0u, max_sq);
+}
+
+// ---- host steps ----------------------------------------------------------------------------------------------------------
+// Cyclic Jacobi with ICP's rotation rule on a symmetric N x N; the eigenvalues are left on A's diagonal
+template <int N>
+void jacobi(double A[N][N], double V[N][N], int sweeps) {
+  for (int r = 0; r < N; ++r)
+    for (int c = 0; c < N; ++c) V[r][c] = r == c ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < sweeps; ++sweep)
+    for (int p = 0; p < N - 1; ++p)
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(tt * tt + 1.0);
+        const double s = tt * c;
+        A[p][p] = A[p][p] - tt * apq;
+        A[q][q] = A[q][q] + tt * apq;
+        A[p][q] = A[q][p] = 0.0;
+        for (int r = 0; r < N; ++r) {
+          if (r != p && r != q) {
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = A[p][r] = c * arp - s * arq;
+            A[r][q] = A[q][r] = s * arp + c * arq;
+          }
+          const double vrp = V[r][p], vrq = V[r][q];
+          V[r][p] = c * vrp - s * vrq;
+          V[r][q] = s * vrp + c * vrq;
+        }
+      }
+}
+
+// dliom.h, target cells: mean, covariance, eigen-decomposition, icov, validity
+void ndt_finish_cell(const double S[9], int min_points, dliom_ndt_cell* cell) {
+  const double dn = static_cast<double>(cell->n);
+  for (int a = 0; a < 3; ++a) cell->mean[a] = S[a] / dn;
+  for (double& v : cell->icov) v = 0.0;
+  cell->valid = 0;
+  if (cell->n < min_points) return;
+  const int at[3][3] = {{3, 4, 5}, {4, 6, 7}, {5, 7, 8}};
+  double C[3][3], V[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b)
+      C[a][b] = C[b][a] = ((S[at[a][b]] - 2.0 * (S[a] * cell->mean[b])) / dn + cell->mean[a] * cell->mean[b]) * ((dn - 1.0) / dn);
+  jacobi<3>(C, V, DLIOM_NDT_JACOBI_SWEEPS);
+  int order[3] = {0, 1, 2};
+  for (int a = 1; a < 3; ++a)  // stable insertion sort
+    for (int b = a; b > 0 && C[order[b]][order[b]] < C[order[b - 1]][order[b - 1]]; --b) std::swap(order[b], order[b - 1]);
+  double l[3] = {C[order[0]][order[0]], C[order[1]][order[1]], C[order[2]][order[2]]};
+  if (!(l[0] >= 0.0 && l[1] >= 0.0 && l[2] > 0.0)) return;
+  const double least = 0.01 * l[2];
+  if (l[0] < least) l[0] = least;
+  if (l[1] < least) l[1] = least;
+  double icov[6];
+  int k = 0;
+  bool finite = true;
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b) {
+      icov[k] = ((V[a][order[0]] * V[b][order[0]]) / l[0] + (V[a][order[1]] * V[b][order[1]]) / l[1]) +
+                (V[a][order[2]] * V[b][order[2]]) / l[2];
+      finite = finite && std::isfinite(icov[k]);
+      ++k;
+    }
+  if (!finite) return;
+  std::memcpy(cell->icov, icov, sizeof(icov));
+  cell->valid = 1;
+}
+
+void ndt_pose(const double p[6], NdtPose* P) {
+  const double sa = std::sin(p[3]), ca = std::cos(p[3]), sb = std::sin(p[4]), cb = std::cos(p[4]), sc = std::sin(p[5]),
+               cc = std::cos(p[5]);
+  std::memset(P, 0, sizeof(*P));
+  const double R[9] = {cb * cc, -(cb * sc), sb, ca * sc + sa * sb * cc, ca * cc - sa * sb * sc, -(sa * cb),
+                       sa * sc - ca * sb * cc, sa * cc + ca * sb * sc, ca * cb};
+  std::memcpy(P->R, R, sizeof(R));
+  for (int a = 0; a < 3; ++a) P->t[a] = p[a];
+  auto set = [](double row[3], double k0, double k1, double k2) {
+    row[0] = k0;
+    row[1] = k1;
+    row[2] = k2;
+  };
+  set(P->J[0][1], -(sa * sc) + ca * sb * cc, -(sa * cc) - ca * sb * sc, -(ca * cb));
+  set(P->J[0][2], ca * sc + sa * sb * cc, ca * cc - sa * sb * sc, -(sa * cb));
+  set(P->J[1][0], -(sb * cc), sb * sc, cb);
+  set(P->J[1][1], sa * cb * cc, -(sa * cb * sc), sa * sb);
+  set(P->J[1][2], -(ca * cb * cc), ca * cb * sc, -(ca * sb));
+  set(P->J[2][0], -(cb * sc), -(cb * cc), 0.0);
+  set(P->J[2][1], ca * cc - sa * sb * sc, -(ca * sc) - sa * sb * cc, 0.0);
+  set(P->J[2][2], sa * cc + ca * sb * sc, -(sa * sc) + ca * sb * cc, 0.0);
+  set(P->H[0][1], -(ca * sc) - sa * sb * cc, -(ca * cc) + sa * sb * sc, sa * cb);
+  set(P->H[0][2], -(sa * sc) + ca * sb * cc, -(sa * cc) - ca * sb * sc, -(ca * cb));
+  set(P->H[1][1], ca * cb * cc, -(ca * cb * sc), ca * sb);
+  set(P->H[1][2], sa * cb * cc, -(sa * cb * sc), sa * sb);
+  set(P->H[2][1], -(sa * cc) - ca * sb * sc, sa * sc - ca * sb * cc, 0.0);
+  set(P->H[2][2], ca * cc - sa * sb * sc, -(ca * sc) - sa * sb * cc, 0.0);
+  set(P->H[3][0], -(cb * cc), cb * sc, -sb);
+  set(P->H[3][1], -(sa * sb * cc), sa * sb * sc, sa * cb);
+  set(P->H[3][2], ca * sb * cc, -(ca * sb * sc), -(ca * cb));
+  set(P->H[4][0], sb * sc, sb * cc, 0.0);
+  set(P->H[4][1], -(sa * cb * sc), -(sa * cb * cc), 0.0);
+  set(P->H[4][2], ca * cb * sc, ca * cb * cc, 0.0);
+  set(P->H[5][0], -(cb * cc), cb * sc, 0.0);
+  set(P->H[5][1], -(ca * sc) - sa * sb * cc, -(ca * cc) + sa * sb * sc, 0.0);
+  set(P->H[5][2], -(sa * sc) + ca * sb * cc, -(sa * cc) - ca * sb * sc, 0.0);
+}
+
+struct NdtConstants {
+  double d1, d2;
+};
+NdtConstants ndt_constants(const dliom_ndt_options& o) {
+  const double c1 = 10.0 * (1.0 - o.outlier_ratio);
+  const double c2 = o.outlier_ratio / ((o.resolution * o.resolution) * o.resolution);
+  const double d3 = -std::log(c2);
+  const double d1 = -std::log(c1 + c2) - d3;
+  const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
+  return NdtConstants{d1, d2};
+}
+
+bool ndt_options_ok(const dliom_ndt_options* o) {
+  if (o == nullptr) return false;
+  if (!std::isfinite(o->resolution) || o->resolution <= 0.0 || !std::isfinite(o->step_size) || o->step_size <= 0.0) return false;
+  if (!(o->outlier_ratio > 0.0 && o->outlier_ratio < 1.0)) return false;
+  if (!std::isfinite(o->transformation_epsilon) || o->transformation_epsilon < 0.0) return false;
+  return o->maximum_iterations >= 0 && o->min_points_per_voxel >= 3 && o->reserved == 0 &&
+         (o->step_mode == DLIOM_NDT_STEP_CLAMPED || o->step_mode == DLIOM_NDT_STEP_MORE_THUENTE);
+}
+
+// dliom.h (ICP): finite, last row 0 0 0 1, |R^T R - I| <= 1e-6 in every entry, det R > 0
+bool ndt_guess_ok(const double* g) {
+  if (g == nullptr) return false;
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(g[k])) return false;
+  if (g[12] != 0.0 || g[13] != 0.0 || g[14] != 0.0 || g[15] != 1.0) return false;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double dot = g[a] * g[b] + g[4 + a] * g[4 + b] + g[8 + a] * g[8 + b];
+      if (!(std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-6)) return false;
+    }
+  const double det = g[0] * (g[5] * g[10] - g[6] * g[9]) - g[1] * (g[4] * g[10] - g[6] * g[8]) + g[2] * (g[4] * g[9] - g[5] * g[8]);
+  return det > 0.0;
+}
+
+struct NdtSums {
+  double score = 0.0, g[6] = {}, H[6][6] = {};
+  long long pairs = 0;
+};
+
+// One evaluation's work on the stream and its read-back.  Events (while timed): before | after the evaluation kernel |
+// after the reduction.
+struct NdtRun {
+  dliom_ndt_target* target;
+  const dliom_cloud* source;
+  NdtConstants k;
+  bool timed = false;
+  std::vector<hipEvent_t> events;
+  int64_t read_backs = 0, with_hessian = 0, without_hessian = 0;
+  ~NdtRun() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  }
+  int mark() {
+    if (!timed) return DLIOM_OK;
+    hipEvent_t e = nullptr;
+    DLIOM_HIP_TRY(hipEventCreate(&e));
+    events.push_back(e);
+    DLIOM_HIP_TRY(hipEventRecord(e, target->ctx->stream));
+    return DLIOM_OK;
+  }
+  template <bool G, bool H>
+  int run(const NdtPose& P, NdtSums* out);
+  int evaluate(const double p[6], int what, NdtSums* out) {
+    NdtPose P;
+    ndt_pose(p, &P);
+    if (what == DLIOM_NDT_EVAL_GRADIENT) {
+      ++without_hessian;
+      return run<true, false>(P, out);
+    }
+    ++with_hessian;
+    return what == DLIOM_NDT_EVAL_ALL ? run<true, true>(P, out) : run<false, true>(P, out);
+  }
+};
+
+template <bool G, bool H>
+int NdtRun::run(const NdtPose& P, NdtSums* out) {
+  constexpr int S = ndt_sums(G, H);
+  dliom_ndt_target* const t = target;
+  dliom_ctx* const ctx = t->ctx;
+  const int n = static_cast<int>(source->n);
+  int blocks = 0, P2 = 1;
+  tree_geometry(n, &blocks, &P2);
+  const size_t leaf_bytes = align256(static_cast<size_t>(S) * std::max(n, 1) * sizeof(double));
+  const size_t pair_bytes = align256(4 * static_cast<size_t>(std::max(n, 1)));
+  const size_t partial_bytes = align256(static_cast<size_t>(P2) * S * sizeof(double));
+  DLIOM_TRY(t->scratch.reserve(leaf_bytes + pair_bytes + partial_bytes + align256(4 * static_cast<size_t>(P2))));
+  char* const base = t->scratch.as<char>();
+  double* const leaves = reinterpret_cast<double*>(base);
+  int* const pairs = reinterpret_cast<int*>(base + leaf_bytes);
+  double* const partials = reinterpret_cast<double*>(base + leaf_bytes + pair_bytes);
+  int* const counts = reinterpret_cast<int*>(base + leaf_bytes + pair_bytes + partial_bytes);
+  const float res = static_cast<float>(t->resolution);
+  const NdtTable table{t->table.as<unsigned long long>(),
+                       reinterpret_cast<const double*>(t->table.as<char>() + t->cell_data_at),
+                       static_cast<int>(t->n_valid),
+                       1.0f / res,
+                       res * res,
+                       k.d1,
+                       k.d2};
+  DLIOM_TRY(mark());
+  if (n > 0) {
+    hipLaunchKernelGGL((ndt_eval_kernel<G, H>), dim3(blocks_of(n, kThreads)), dim3(kThreads), 0, ctx->stream, table, P, source->d_x,
+                       source->d_y, source->d_z, n, leaves, pairs);
+    DLIOM_HIP_TRY(hipGetLastError());
+  }
+  DLIOM_TRY(mark());
+  const NdtLeaves<S> L{leaves, pairs, n};
+  hipLaunchKernelGGL((tree_reduce_kernel<S, NdtLeaves<S>>), dim3(static_cast<unsigned>(blocks)), dim3(kTreeThreads), 0, ctx->stream, L,
+                     partials, counts);
+  DLIOM_HIP_TRY(hipGetLastError());
+  NdtReadback* const host = pinned_at<NdtReadback>(ctx, kPinNdtSums);
+  const unsigned seq = next_done_seq(ctx);
+  const auto enqueued_at = std::chrono::steady_clock::now();
+  hipLaunchKernelGGL((ndt_finish_kernel<S>), dim3(1), dim3(kTreeThreads), 0, ctx->stream, partials, counts, blocks, P2, host,
+                     ctx->done_word, seq);
+  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_TRY(mark());
+  DLIOM_TRY(wait_done(ctx, ctx->stream, ctx->done_word, seq, t->poll_us));
+  const auto took = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - enqueued_at).count();
+  t->poll_us = static_cast<int>(std::min<long long>(std::max<long long>(2 * took, 150), 100000));
+  ++read_backs;
+  const NdtReadback rb = *host;
+  int at = 0;
+  if (G) {
+    out->score = rb.sums[0];
+    for (int a = 0; a < 6; ++a) out->g[a] = rb.sums[1 + a];
+    at = 7;
+  }
+  if (H)
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b) out->H[a][b] = out->H[b][a] = rb.sums[at++];
+  out->pairs = rb.pairs;
+  return DLIOM_OK;
+}
+
+// delta = -pinv(H) g (dliom.h, Alignment 1)
+void ndt_newton_step(const NdtSums& s, double delta[6]) {
+  double A[6][6], V[6][6];
+  std::memcpy(A, s.H, sizeof(A));
+  jacobi<6>(A, V, DLIOM_NDT_PINV_SWEEPS);
+  double largest = 0.0;
+  for (int k = 0; k < 6; ++k)
+    if (std::fabs(A[k][k]) > largest) largest = std::fabs(A[k][k]);
+  const double floor_ = 6.0 * 0x1p-52 * largest;
+  double z[6];
+  for (int k = 0; k < 6; ++k) {
+    double y = 0.0;
+    for (int r = 0; r < 6; ++r) y = y + V[r][k] * s.g[r];
+    z[k] = std::fabs(A[k][k]) > floor_ ? y / A[k][k] : 0.0;
+  }
+  for (int r = 0; r < 6; ++r) {
+    double v = 0.0;
+    for (int k = 0; k < 6; ++k) v = v + V[r][k] * z[k];
+    delta[r] = -v;
+  }
+}
+
+inline double min_of(double a, double b) { return b < a ? b : a; }
+inline double max_of(double a, double b) { return a < b ? b : a; }
+
+double mt_trial(double a_l, double f_l, double g_l, double a_u, double f_u, double g_u, double a_t, double f_t, double g_t) {
+  if (f_t > f_l) {
+    const double z = (3.0 * (f_t - f_l) / (a_t - a_l) - g_t) - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * ((w - g_l) - z) / ((g_t - g_l) + 2.0 * w);
+    const double a_q = a_l - 0.5 * (a_l - a_t) * g_l / (g_l - (f_l - f_t) / (a_l - a_t));
+    return std::fabs(a_c - a_l) < std::fabs(a_q - a_l) ? a_c : 0.5 * (a_q + a_c);
+  }
+  if (g_t * g_l < 0.0) {
+    const double z = (3.0 * (f_t - f_l) / (a_t - a_l) - g_t) - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * ((w - g_l) - z) / ((g_t - g_l) + 2.0 * w);
+    const double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
+    return std::fabs(a_c - a_t) >= std::fabs(a_s - a_t) ? a_c : a_s;
+  }
+  if (std::fabs(g_t) <= std::fabs(g_l)) {
+    const double z = (3.0 * (f_t - f_l) / (a_t - a_l) - g_t) - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * ((w - g_l) - z) / ((g_t - g_l) + 2.0 * w);
+    const double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
+    const double next = std::fabs(a_c - a_t) < std::fabs(a_s - a_t) ? a_c : a_s;
+    return a_t > a_l ? min_of(a_t + 0.66 * (a_u - a_t), next) : max_of(a_t + 0.66 * (a_u - a_t), next);
+  }
+  const double z = (3.0 * (f_t - f_u) / (a_t - a_u) - g_t) - g_u;
+  const double w = std::sqrt(z * z - g_t * g_u);
+  return a_u + (a_t - a_u) * ((w - g_u) - z) / ((g_t - g_u) + 2.0 * w);
+}
+
+// -> converged
+bool mt_update(double* a_l, double* f_l, double* g_l, double* a_u, double* f_u, double* g_u, double a_t, double f_t, double g_t) {
+  if (f_t > *f_l) {
+    *a_u = a_t;
+    *f_u = f_t;
+    *g_u = g_t;
+    return false;
+  }
+  if (g_t * (*a_l - a_t) > 0.0) {
+    *a_l = a_t;
+    *f_l = f_t;
+    *g_l = g_t;
+    return false;
+  }
+  if (g_t * (*a_l - a_t) < 0.0) {
+    *a_u = *a_l;
+    *f_u = *f_l;
+    *g_u = *g_l;
+    *a_l = a_t;
+    *f_l = f_t;
+    *g_l = g_t;
+    return false;
+  }
+  return true;
+}
+
+double dot6(const double a[6], const double b[6]) {
+  double v = 0.0;
+  for (int r = 0; r < 6; ++r) v = v + a[r] * b[r];
+  return v;
+}
+
+// dliom.h, Step length.  sums: in, those at p; out, those of the step's last evaluation.  dir may come back negated.
+int ndt_step_length(NdtRun* run, const double p[6], double dir[6], double step_init, const dliom_ndt_options& o, NdtSums* sums,
+                    double* a_out) {
+  const double step_max = o.step_size, step_min = o.transformation_epsilon / 2.0;
+  const double phi0 = -sums->score;
+  double dphi0 = -dot6(sums->g, dir);
+  *a_out = 0.0;
+  if (dphi0 == 0.0) return DLIOM_OK;
+  if (dphi0 > 0.0) {
+    dphi0 = -dphi0;
+    for (int r = 0; r < 6; ++r) dir[r] = -dir[r];
+  }
+  double a_t = max_of(min_of(step_init, step_max), step_min);
+  double x[6];
+  for (int r = 0; r < 6; ++r) x[r] = p[r] + dir[r] * a_t;
+  DLIOM_TRY(run->evaluate(x, DLIOM_NDT_EVAL_ALL, sums));
+  *a_out = a_t;
+  if (o.step_mode == DLIOM_NDT_STEP_CLAMPED) return DLIOM_OK;
+  const double mu = 1e-4, nu = 0.9;
+  double a_l = 0.0, a_u = 0.0, f_l = 0.0, f_u = 0.0, g_l = dphi0 - mu * dphi0, g_u = dphi0 - mu * dphi0;
+  bool open = true, interval_converged = false;
+  double phi_t = -sums->score, dphi_t = -dot6(sums->g, dir);
+  double psi_t = (phi_t - phi0) - (mu * dphi0) * a_t, dpsi_t = dphi_t - mu * dphi0;
+  int trials = 0;
+  while (!interval_converged && trials < 10 && !(psi_t <= 0.0 && dphi_t <= -nu * dphi0)) {
+    a_t = open ? mt_trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, dpsi_t) : mt_trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, dphi_t);
+    a_t = max_of(min_of(a_t, step_max), step_min);
+    for (int r = 0; r < 6; ++r) x[r] = p[r] + dir[r] * a_t;
+    DLIOM_TRY(run->evaluate(x, DLIOM_NDT_EVAL_GRADIENT, sums));
+    phi_t = -sums->score;
+    dphi_t = -dot6(sums->g, dir);
+    psi_t = (phi_t - phi0) - (mu * dphi0) * a_t;
+    dpsi_t = dphi_t - mu * dphi0;
+    if (open && psi_t <= 0.0 && dpsi_t >= 0.0) {
+      open = false;
+      f_l = (f_l + phi0) - (mu * dphi0) * a_l;
+      g_l = g_l + mu * dphi0;
+      f_u = (f_u + phi0) - (mu * dphi0) * a_u;
+      g_u = g_u + mu * dphi0;
+    }
+    interval_converged = open ? mt_update(&a_l, &f_l, &g_l, &a_u, &f_u, &g_u, a_t, psi_t, dpsi_t)
+                              : mt_update(&a_l, &f_l, &g_l, &a_u, &f_u, &g_u, a_t, phi_t, dphi_t);
+    ++trials;
+  }
+  if (trials > 0) DLIOM_TRY(run->evaluate(x, DLIOM_NDT_EVAL_HESSIAN, sums));
+  *a_out = a_t;
+  return DLIOM_OK;
+}
+
+void ndt_pose_of_guess(const double* g, double p[6]) {
+  p[0] = g[3];
+  p[1] = g[7];
+  p[2] = g[11];
+  p[3] = std::atan2(-g[6], g[10]);
+  p[4] = std::atan2(g[2], std::sqrt(g[0] * g[0] + g[1] * g[1]));
+  p[5] = std::atan2(-g[4 * 0 + 1], g[0]);
+}
+
+bool ndt_call_ok(const dliom_ndt_target* target, const dliom_cloud* source, const dliom_ndt_options* options) {
+  if (target == nullptr || source == nullptr || !ndt_options_ok(options)) return false;
+  if (source->ctx != target->ctx || source->n < 0 || source->n > DLIOM_NN_MAX_POINTS || target->ctx->done_word == nullptr) return false;
+  return options->resolution == target->resolution;
+}
+
+}  // namespace
+}  // namespace dliom
+
+extern "C" {
+
+int dliom_ndt_default_options(dliom_ndt_options* options) {
+  if (options == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *options = dliom_ndt_options{1.0, 0.1, 0.01, 0.55, 35, 6, DLIOM_NDT_STEP_CLAMPED, 0};
+  return DLIOM_OK;
+}
+
+int dliom_ndt_target_create(dliom_ctx* ctx, const dliom_cloud* target, const dliom_ndt_options* options, dliom_ndt_target** out) {
+  using namespace dliom;
+  if (out != nullptr) *out = nullptr;
+  if (ctx == nullptr || target == nullptr || out == nullptr || !ndt_options_ok(options) || target->ctx != ctx || target->n <= 0 ||
+      target->n > DLIOM_NN_MAX_POINTS || ctx->done_word == nullptr)
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  const auto started = std::chrono::steady_clock::now();
+  const int n = static_cast<int>(target->n);
+  struct Work {  // released on every way out
+    DevBuf a, b;
+    ~Work() {
+      a.release();
+      b.release();
+    }
+  } work;
+  size_t sort_bytes = 0, scan_bytes = 0;
+  DLIOM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, static_cast<const unsigned long long*>(nullptr),
+                                                   static_cast<unsigned long long*>(nullptr), static_cast<const int*>(nullptr),
+                                                   static_cast<int*>(nullptr), n, 0, 64, ctx->stream));
+  DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, static_cast<const unsigned*>(nullptr), static_cast<unsigned*>(nullptr), n,
+                                                 ctx->stream));
+  const size_t per8 = align256(8 * static_cast<size_t>(n)), per4 = align256(4 * static_cast<size_t>(n));
+  const size_t tmp_bytes = align256(std::max(sort_bytes, scan_bytes));
+  DLIOM_TRY(work.a.reserve(2 * per8 + 4 * per4 + 256 + tmp_bytes));
+  char* const a = work.a.as<char>();
+  auto* const keys_in = reinterpret_cast<unsigned long long*>(a);
+  auto* const keys = reinterpret_cast<unsigned long long*>(a + per8);
+  int* const index_in = reinterpret_cast<int*>(a + 2 * per8);
+  int* const sorted_index = reinterpret_cast<int*>(a + 2 * per8 + per4);
+  unsigned* const head = reinterpret_cast<unsigned*>(a + 2 * per8 + 2 * per4);
+  unsigned* const inclusive = reinterpret_cast<unsigned*>(a + 2 * per8 + 3 * per4);
+  unsigned* const kept_word = reinterpret_cast<unsigned*>(a + 2 * per8 + 4 * per4);
+  void* const tmp = a + 2 * per8 + 4 * per4 + 256;
+  const FillJob fill{kept_word, 4, static_cast<unsigned>(n)};
+  DLIOM_TRY(fill_multi(ctx, &fill, 1));
+  const float inv = 1.0f / static_cast<float>(options->resolution);
+  const dim3 grid(blocks_of(n, kThreads)), block(kThreads);
+  hipLaunchKernelGGL(ndt_key_kernel, grid, block, 0, ctx->stream, target->d_x, target->d_y, target->d_z, n, inv, keys_in, index_in);
+  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, keys_in, keys, index_in, sorted_index, n, 0, 64, ctx->stream));
+  hipLaunchKernelGGL(ndt_head_kernel, grid, block, 0, ctx->stream, keys, n, head, kept_word);
+  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, scan_bytes, head, inclusive, n, ctx->stream));
+  const GatherJob jobs[2] = {{inclusive + (n - 1), 1}, {kept_word, 1}};
+  unsigned* const words = pinned_at<unsigned>(ctx, kPinReadback);
+  DLIOM_TRY(gather_and_wait(ctx, jobs, 2, words));
+  const int cells = static_cast<int>(words[0]), kept = static_cast<int>(words[1]);
+  if (cells < 0 || cells > n || kept < 0 || kept > n) return DLIOM_ERR_INTERNAL;
+  auto t = std::make_unique<dliom_ndt_target>();
+  t->ctx = ctx;
+  t->resolution = options->resolution;
+  t->min_points = options->min_points_per_voxel;
+  t->n_points = n;
+  t->n_kept = kept;
+  t->build_read_backs = 1;
+  std::vector<unsigned long long> valid_keys;
+  std::vector<double> valid_data;
+  if (cells > 0) {
+    const size_t first_bytes = align256(4 * (static_cast<size_t>(cells) + 1)), key_bytes = align256(8 * static_cast<size_t>(cells));
+    DLIOM_TRY(work.b.reserve(first_bytes + key_bytes + 72 * static_cast<size_t>(cells)));
+    char* const b = work.b.as<char>();
+    int* const cell_first = reinterpret_cast<int*>(b);
+    auto* const cell_key = reinterpret_cast<unsigned long long*>(b + first_bytes);
+    double* const sums = reinterpret_cast<double*>(b + first_bytes + key_bytes);
+    hipLaunchKernelGGL(ndt_bounds_kernel, grid, block, 0, ctx->stream, keys, head, inclusive, n, cells, kept, cell_first, cell_key);
+    DLIOM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ndt_cell_sums_kernel, dim3(static_cast<unsigned>(cells)), block, 0, ctx->stream, target->d_x, target->d_y,
+                       target->d_z, sorted_index, cell_first, sums);
+    DLIOM_HIP_TRY(hipGetLastError());
+    std::vector<int> h_first(static_cast<size_t>(cells) + 1);
+    std::vector<unsigned long long> h_key(cells);
+    std::vector<double> h_sums(static_cast<size_t>(cells) * 9);
+    DLIOM_HIP_TRY(hipMemcpyAsync(h_first.data(), cell_first, 4 * h_first.size(), hipMemcpyDeviceToHost, ctx->stream));
+    DLIOM_HIP_TRY(hipMemcpyAsync(h_key.data(), cell_key, 8 * h_key.size(), hipMemcpyDeviceToHost, ctx->stream));
+    DLIOM_HIP_TRY(hipMemcpyAsync(h_sums.data(), sums, 8 * h_sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ++ctx->host_syncs;
+    ++t->build_read_backs;
+    t->cells.resize(cells);
+    for (int c = 0; c < cells; ++c) {
+      dliom_ndt_cell& cell = t->cells[c];
+      cell.index[0] = static_cast<int>(h_key[c] & 0x1fffffu) - kHalf;
+      cell.index[1] = static_cast<int>((h_key[c] >> 21) & 0x1fffffu) - kHalf;
+      cell.index[2] = static_cast<int>((h_key[c] >> 42) & 0x1fffffu) - kHalf;
+      cell.n = h_first[c + 1] - h_first[c];
+      ndt_finish_cell(&h_sums[static_cast<size_t>(c) * 9], t->min_points, &cell);
+      if (cell.valid != 0) {
+        valid_keys.push_back(h_key[c]);
+        valid_data.insert(valid_data.end(), cell.mean, cell.mean + 3);
+        valid_data.insert(valid_data.end(), cell.icov, cell.icov + 6);
+      }
+    }
+  }
+  t->n_valid = static_cast<int64_t>(valid_keys.size());
+  t->cell_data_at = align256(8 * std::max<size_t>(valid_keys.size(), 1));
+  DLIOM_TRY(t->table.reserve(t->cell_data_at + 72 * std::max<size_t>(valid_keys.size(), 1)));
+  int status = DLIOM_OK;
+  if (!valid_keys.empty()) {
+    if (hipMemcpyAsync(t->table.p, valid_keys.data(), 8 * valid_keys.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(t->table.as<char>() + t->cell_data_at, valid_data.data(), 8 * valid_data.size(), hipMemcpyHostToDevice,
+                       ctx->stream) != hipSuccess)
+      status = DLIOM_ERR_HIP;
+  }
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) status = DLIOM_ERR_HIP;  // the host vectors and the work buffers are free again
+  ++ctx->host_syncs;
+  if (status != DLIOM_OK) {
+    t->table.release();
+    return status;
+  }
+  if (ctx->profiling) t->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count();
+  *out = t.release();
+  return DLIOM_OK;
+}
+
+void dliom_ndt_target_destroy(dliom_ndt_target* target) {
+  if (target == nullptr) return;
+  (void)hipSetDevice(target->ctx->device);
+  (void)hipStreamSynchronize(target->ctx->stream);
+  target->table.release();
+  target->scratch.release();
+  delete target;
+}
+
+int dliom_ndt_target_memory_stats(const dliom_ndt_target* target, dliom_ndt_target_memory* out) {
+  if (target == nullptr || out == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *out = dliom_ndt_target_memory{target->n_points,
+                                 target->n_kept,
+                                 static_cast<int64_t>(target->cells.size()),
+                                 target->n_valid,
+                                 static_cast<int64_t>(target->table.cap),
+                                 static_cast<int64_t>(target->scratch.cap),
+                                 target->build_read_backs,
+                                 target->build_ms};
+  return DLIOM_OK;
+}
+
+int dliom_ndt_target_cells(const dliom_ndt_target* target, dliom_ndt_cell* cells, int64_t capacity, int64_t* count) {
+  if (target == nullptr || count == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *count = static_cast<int64_t>(target->cells.size());
+  if (cells == nullptr) return DLIOM_OK;
+  if (capacity < *count) return DLIOM_ERR_CAPACITY;
+  if (*count > 0) std::memcpy(cells, target->cells.data(), sizeof(dliom_ndt_cell) * target->cells.size());
+  return DLIOM_OK;
+}
+
+int dliom_ndt_evaluate(dliom_ndt_target* target, const dliom_cloud* source, const double* p6, const dliom_ndt_options* options,
+                       int what, double* score, double* gradient6, double* hessian36, int64_t* pairs) {
+  using namespace dliom;
+  if (!ndt_call_ok(target, source, options) || p6 == nullptr || score == nullptr || gradient6 == nullptr || hessian36 == nullptr ||
+      pairs == nullptr || what < DLIOM_NDT_EVAL_GRADIENT || what > DLIOM_NDT_EVAL_HESSIAN)
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  DLIOM_HIP_TRY(hipSetDevice(target->ctx->device));
+  NdtRun run{target, source, ndt_constants(*options)};
+  NdtSums sums;
+  DLIOM_TRY(run.evaluate(p6, what, &sums));
+  *score = sums.score;
+  std::memcpy(gradient6, sums.g, sizeof(sums.g));
+  std::memcpy(hessian36, sums.H, sizeof(sums.H));
+  *pairs = sums.pairs;
+  return DLIOM_OK;
+}
+
+int dliom_ndt_align(dliom_ndt_target* target, const dliom_cloud* source, const double* guess16, const dliom_ndt_options* options,
+                    dliom_nn_index* fitness_index, dliom_ndt_result* result, dliom_cloud** aligned) {
+  using namespace dliom;
+  if (aligned != nullptr) *aligned = nullptr;
+  if (!ndt_call_ok(target, source, options) || result == nullptr || !ndt_guess_ok(guess16) ||
+      (fitness_index != nullptr && nn_ctx(fitness_index) != target->ctx))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  dliom_ctx* const ctx = target->ctx;
+  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  const int n = static_cast<int>(source->n);
+  dliom_ndt_result res = {};
+  res.fitness_score = std::numeric_limits<double>::quiet_NaN();
+  NdtRun run{target, source, ndt_constants(*options)};
+  run.timed = ctx->profiling;
+  const auto started = std::chrono::steady_clock::now();
+  double p[6];
+  ndt_pose_of_guess(guess16, p);
+  NdtSums sums;
+  DLIOM_TRY(run.evaluate(p, DLIOM_NDT_EVAL_ALL, &sums));
+  for (int it = 0;; ++it) {
+    double delta[6], dir[6];
+    ndt_newton_step(sums, delta);
+    const double s = std::sqrt(dot6(delta, delta));
+    if (s == 0.0 || s != s) {
+      res.converged = s == s ? 1 : 0;
+      res.reason = DLIOM_NDT_ZERO_STEP;
+      res.iterations = it;
+      break;
+    }
+    for (int r = 0; r < 6; ++r) dir[r] = delta[r] / s;
+    double a = 0.0;
+    DLIOM_TRY(ndt_step_length(&run, p, dir, s, *options, &sums, &a));
+    for (int r = 0; r < 6; ++r) p[r] = p[r] + dir[r] * a;
+    if (it > options->maximum_iterations || (it > 0 && std::fabs(a) < options->transformation_epsilon)) {
+      res.converged = 1;
+      res.reason = it > options->maximum_iterations ? DLIOM_NDT_ITERATIONS : DLIOM_NDT_EPSILON;
+      res.iterations = it + 1;
+      break;
+    }
+  }
+  const double loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count();
+  std::memcpy(res.p, p, sizeof(p));
+  NdtPose P;
+  ndt_pose(p, &P);
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) res.transform[4 * a + b] = P.R[3 * a + b];
+    res.transform[4 * a + 3] = P.t[a];
+  }
+  res.transform[15] = 1.0;
+  res.score = sums.score;
+  res.transformation_probability = sums.score / static_cast<double>(n);
+  res.pairs = sums.pairs;
+  res.evaluations_with_hessian = run.with_hessian;
+  res.evaluations_without_hessian = run.without_hessian;
+  res.read_backs = run.read_backs;
+  if (!run.events.empty()) {
+    DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t e = 0; e + 2 < run.events.size(); e += 3) {
+      float ms[2] = {0.f, 0.f};
+      DLIOM_HIP_TRY(hipEventElapsedTime(&ms[0], run.events[e], run.events[e + 1]));
+      DLIOM_HIP_TRY(hipEventElapsedTime(&ms[1], run.events[e + 1], run.events[e + 2]));
+      res.evaluate_ms += ms[0];
+      res.reduce_ms += ms[1];
+    }
+    res.host_ms = std::max(0.0, loop_ms - res.evaluate_ms - res.reduce_ms);
+  }
+  // the final points: the fitness score and the aligned cloud
+  if (fitness_index != nullptr || aligned != nullptr) {
+    float *x, *y, *z;
+    dliom_cloud* cloud = nullptr;
+    DLIOM_TRY(alloc_device_cloud(ctx, n, &cloud, &x, &y, &z));
+    Rigid12 m;
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) m.m[4 * a + b] = P.R[3 * a + b];
+      m.m[4 * a + 3] = P.t[a];
+    }
+    int st = DLIOM_OK;
+    unsigned* max_sq = nullptr;
+    if (n > 0) st = nn_transform_enqueue(ctx, source->d_x, source->d_y, source->d_z, n, m, x, y, z);
+    if (st == DLIOM_OK && fitness_index != nullptr) {
+      long long count = 0;
+      st = icp_fitness_of(fitness_index, x, y, z, n, &res.fitness_score, &count);
+      res.fitness_count = count;
+      ++res.read_backs;
+    }
+    if (st == DLIOM_OK && aligned != nullptr) {
+      unsigned word = 0;
+      if (n > 0) {
+        st = target->scratch.reserve(256);
+        if (st == DLIOM_OK) {
+          max_sq = target->scratch.as<unsigned>();
+          const FillJob fill{max_sq, 4, 0u};
+          st = fill_multi(ctx, &fill, 1);
+        }
+        if (st == DLIOM_OK) {
+          hipLaunchKernelGGL(ndt_max_norm_kernel, dim3(blocks_of(n, kThreads)), dim3(kThreads), 0, ctx->stream, x, y, z, n, max_sq);
+          if (hipGetLastError() != hipSuccess) st = DLIOM_ERR_HIP;
+        }
+        if (st == DLIOM_OK) {
+          const GatherJob job{max_sq, 1};
+          unsigned* const words = pinned_at<unsigned>(ctx, kPinReadback);
+          st = gather_and_wait(ctx, &job, 1, words);
+          word = words[0];
+          ++res.read_backs;
+        }
+      }
+      float max_norm_sq;
+      std::memcpy(&max_norm_sq, &word, 4);
+      if (st == DLIOM_OK) st = finish_device_cloud(ctx, cloud, std::sqrt(max_norm_sq));
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == DLIOM_OK) st = DLIOM_ERR_HIP;
+    ++ctx->host_syncs;
+    if (st != DLIOM_OK || aligned == nullptr) {
+      dliom_cloud_destroy(cloud);
+      if (st != DLIOM_OK) return st;
+    } else {
+      *aligned = cloud;
+    }
+  }
+  *result = res;
+  return DLIOM_OK;
+}
+
+}  // extern "C"

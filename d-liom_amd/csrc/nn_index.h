@@ -49,6 +49,10 @@ struct Rigid12 {
 int nn_transform_enqueue(dliom_ctx* ctx, const float* x, const float* y, const float* z, int n, const Rigid12& m, float* ox,
                          float* oy, float* oz);
 
+// icp.hip: dliom.h's fitness score of n points in HBM (n <= DLIOM_NN_MAX_POINTS) against the index's target: the mean of
+// d2 without a bound by the fixed tree (NaN when *count is 0); one polled read-back
+int icp_fitness_of(dliom_nn_index* index, const float* x, const float* y, const float* z, int n, double* score, long long* count);
+
 }  // namespace dliom
 
 #endif  // DLIOM_CSRC_NN_INDEX_H_

@@ -16,6 +16,9 @@
 //  * kPinIcpSums belongs to an alignment or a step of icp.hip, entry points of their own: one read-back an iteration (the
 //    sums of the tree reduction), copied out before the next launch.  The index's creation (nn_index.hip) reads its
 //    bounding box through kPinReadback, in a call of its own;
+//  * kPinNdtSums belongs to an alignment or an evaluation of ndt.hip, entry points of their own: one read-back an
+//    evaluation, copied out before the next launch.  The fitness score at an alignment's end is ICP's (kPinIcpSums); the
+//    target's creation and the aligned cloud's norm read a few words through kPinReadback;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -73,6 +76,9 @@ constexpr PinRegion kPinFeatureResults{8192 * 32, 8192 * 48};
 // an ICP alignment (icp.hip): the sixteen sums, the count and the search counters of one iteration
 constexpr PinRegion kPinIcpSums{4096, 256};
 
+// an NDT evaluation (ndt.hip): up to 28 sums and the pair count
+constexpr PinRegion kPinNdtSums{4096 + 256, 256};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -119,6 +125,8 @@ static_assert(pins_inside({kPinFeaturePairs, kPinFeatureResults}, kPinnedBytes) 
               "a feature match's regions");
 static_assert(pins_inside({kPinIcpSums}, kPinnedBytes) && pins_disjoint({kPinIcpSums, kPinReadback}),
               "an ICP alignment's region (apart from the small read-backs of the helpers it may call)");
+static_assert(pins_inside({kPinNdtSums}, kPinnedBytes) && pins_disjoint({kPinNdtSums, kPinIcpSums, kPinReadback}),
+              "an NDT alignment's regions (its fitness score is ICP's)");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

@@ -3510,3 +3510,149 @@ class Icp:
         finally:
             if mine:
                 cloud.close()
+
+
+# ---- scan alignment by NDT (include/dliom.h "scan alignment by NDT") -----------------------------------------------------
+NDT_JACOBI_SWEEPS, NDT_PINV_SWEEPS, NDT_MAX_CELL_INDEX = 8, 12, 1 << 20
+NDT_STEP_CLAMPED, NDT_STEP_MORE_THUENTE = 0, 1
+NDT_NOT_CONVERGED, NDT_ITERATIONS, NDT_EPSILON, NDT_ZERO_STEP = range(4)
+NDT_EVAL_GRADIENT, NDT_EVAL_ALL, NDT_EVAL_HESSIAN = range(3)
+
+
+class NdtOptions(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("resolution", "step_size", "transformation_epsilon", "outlier_ratio")] + \
+               [(f, C.c_int) for f in ("maximum_iterations", "min_points_per_voxel", "step_mode", "reserved")]
+
+
+class NdtCell(C.Structure):
+    _fields_ = [("index", C.c_int32 * 3), ("valid", C.c_int32), ("n", C.c_int64), ("mean", C.c_double * 3),
+                ("icov", C.c_double * 6)]
+
+
+class NdtTargetMemory(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("points", "kept_points", "cells", "valid_cells", "target_bytes", "scratch_bytes",
+                                         "read_backs")] + [("build_ms", C.c_double)]
+
+
+class NdtResult(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("converged", "reason", "iterations", "reserved")] + \
+               [(f, C.c_int64) for f in ("evaluations_with_hessian", "evaluations_without_hessian")] + \
+               [("p", C.c_double * 6), ("transform", C.c_double * 16), ("score", C.c_double),
+                ("transformation_probability", C.c_double), ("fitness_score", C.c_double)] + \
+               [(f, C.c_int64) for f in ("fitness_count", "pairs", "read_backs")] + \
+               [(f, C.c_double) for f in ("evaluate_ms", "reduce_ms", "host_ms")]
+
+
+SYMBOLS += [
+    ("dliom_ndt_default_options", C.c_int, [C.POINTER(NdtOptions)]),
+    ("dliom_ndt_target_create", C.c_int, [_vp, _vp, C.POINTER(NdtOptions), C.POINTER(_vp)]),
+    ("dliom_ndt_target_destroy", None, [_vp]),
+    ("dliom_ndt_target_memory_stats", C.c_int, [_vp, C.POINTER(NdtTargetMemory)]),
+    ("dliom_ndt_target_cells", C.c_int, [_vp, C.POINTER(NdtCell), C.c_int64, _i64p]),
+    ("dliom_ndt_evaluate", C.c_int, [_vp, _vp, _f64p, C.POINTER(NdtOptions), C.c_int, _f64p, _f64p, _f64p, _i64p]),
+    ("dliom_ndt_align", C.c_int, [_vp, _vp, _f64p, C.POINTER(NdtOptions), _vp, C.POINTER(NdtResult), C.POINTER(_vp)]),
+]
+
+
+def ndt_options(**overrides):
+    """dliom_ndt_default_options (the ground-truth tool's and MatchByNDT's values) with fields replaced"""
+    o = NdtOptions()
+    _check(load_library().dliom_ndt_default_options(C.byref(o)), "dliom_ndt_default_options")
+    for k, v in overrides.items():
+        if k not in dict(NdtOptions._fields_):
+            raise TypeError("no NDT option " + k)
+        setattr(o, k, v)
+    return o
+
+
+class NdtTarget:
+    """The target's cells in HBM (dliom_ndt_target): pcl::VoxelGridCovariance as dliom.h states it."""
+
+    def __init__(self, ctx, target, options=None):
+        self.ctx, self._L = ctx, ctx._L
+        self.options = options if options is not None else ndt_options()
+        cloud, mine = _as_cloud(ctx, target)
+        h = _vp()
+        try:
+            _check(self._L.dliom_ndt_target_create(ctx.h, cloud.h, C.byref(self.options), C.byref(h)), "dliom_ndt_target_create")
+        finally:
+            if mine:
+                cloud.close()
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_ndt_target_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def memory_stats(self):
+        m = NdtTargetMemory()
+        _check(self._L.dliom_ndt_target_memory_stats(self.h, C.byref(m)), "dliom_ndt_target_memory_stats")
+        return {k: getattr(m, k) for k, _ in NdtTargetMemory._fields_}
+
+    def cells(self):
+        """-> dict(index (m, 3) int32, n (m,) int64, valid (m,) bool, mean (m, 3), icov (m, 6)), in key order (z, y, x)"""
+        count = C.c_int64()
+        _check(self._L.dliom_ndt_target_cells(self.h, None, 0, C.byref(count)), "dliom_ndt_target_cells")
+        m = int(count.value)
+        buf = (NdtCell * max(m, 1))()
+        _check(self._L.dliom_ndt_target_cells(self.h, buf, m, C.byref(count)), "dliom_ndt_target_cells")
+        a = np.frombuffer(buf, dtype=np.dtype([("index", np.int32, 3), ("valid", np.int32), ("n", np.int64),
+                                               ("mean", np.float64, 3), ("icov", np.float64, 6)]))[:m]
+        return {"index": a["index"].copy(), "n": a["n"].copy(), "valid": a["valid"] != 0, "mean": a["mean"].copy(),
+                "icov": a["icov"].copy()}
+
+
+def _ndt_result(r):
+    out = {k: getattr(r, k) for k, _ in NdtResult._fields_ if k not in ("transform", "p", "reserved")}
+    out["p"] = np.array(r.p, dtype=np.float64)
+    out["transform"] = np.array(r.transform, dtype=np.float64).reshape(4, 4)
+    return out
+
+
+class Ndt:
+    """pcl::NormalDistributionsTransform as the ground-truth tool and MatchByNDT run it, on an NdtTarget
+    (dliom_ndt_align).  Parity unpinned against PCL (dliom.h)."""
+
+    def __init__(self, target, options=None, fitness_index=None):
+        self.target, self._L = target, target._L
+        self.options = options if options is not None else target.options
+        self.fitness_index = fitness_index
+
+    def align(self, source, guess=None, want_aligned=False):
+        """-> result dict (p: (6,), transform: 4x4 float64), and the aligned points (n, 3) float32 if asked for"""
+        cloud, mine = _as_cloud(self.target.ctx, source)
+        try:
+            g = _f64(np.eye(4) if guess is None else guess).reshape(16)
+            r, h = NdtResult(), _vp()
+            _check(self._L.dliom_ndt_align(self.target.h, cloud.h, _p(g, _f64p), C.byref(self.options),
+                                           None if self.fitness_index is None else self.fitness_index.h, C.byref(r),
+                                           C.byref(h) if want_aligned else None), "dliom_ndt_align")
+            if not want_aligned:
+                return _ndt_result(r)
+            aligned = PointCloud(self.target.ctx, _handle=h)
+            try:
+                return _ndt_result(r), aligned.download()
+            finally:
+                aligned.close()
+        finally:
+            if mine:
+                cloud.close()
+
+    def evaluate(self, source, p6, what=NDT_EVAL_ALL):
+        """dliom_ndt_evaluate -> dict(score, gradient (6,), hessian (6, 6), pairs)"""
+        cloud, mine = _as_cloud(self.target.ctx, source)
+        try:
+            p, score, g, H, pairs = _f64(p6).reshape(6), C.c_double(), np.zeros(6), np.zeros(36), C.c_int64()
+            _check(self._L.dliom_ndt_evaluate(self.target.h, cloud.h, _p(p, _f64p), C.byref(self.options), int(what),
+                                              C.byref(score), _p(g, _f64p), _p(H, _f64p), C.byref(pairs)), "dliom_ndt_evaluate")
+            return {"score": score.value, "gradient": g, "hessian": H.reshape(6, 6), "pairs": int(pairs.value)}
+        finally:
+            if mine:
+                cloud.close()

@@ -2267,6 +2267,189 @@ int dliom_icp_align(dliom_nn_index* index, const dliom_cloud* source, const doub
 int dliom_icp_step(dliom_nn_index* index, const dliom_cloud* points, const dliom_icp_options* options, int32_t* j_out,
                    float* d2_out, double* sums16, int64_t* correspondences, double* rotation9, double* translation3);
 
+/* ---- scan alignment by NDT ------------------------------------------------------------------------------
+ * pcl::NormalDistributionsTransform as the reference runs it: LocalTrajectoryBuilder3D::MatchByNDT
+ * (local_trajectory_builder_3d.cc:969-1008: epsilon 0.01, step 0.1, resolution 1.0, 35 iterations, on clouds filtered by
+ * pcl::ApproximateVoxelGrid at 0.2 m) and gen_ground_truth_by_ndt_match.cc's `--method ndt` (:211-222, the same four
+ * values, on raw scans).  PARITY UNPINNED AGAINST PCL, for the reason given in the ICP section.  What is pinned, bit for bit
+ * against a CPU model (tests/ndt_common.py), is this definition, our reading of PCL 1.8.0's VoxelGridCovariance and
+ * NormalDistributionsTransform; where it differs from PCL, this text governs.  Arithmetic is double unless said otherwise,
+ * every operation rounded on its own, in the order written, parentheses first and otherwise left to right.  min(a, b) is
+ * (b < a ? b : a) and max(a, b) is (a < b ? b : a).
+ *
+ * TARGET CELLS.  inv = 1.0f / (float)resolution.  The cell of a target point is (floor(x*inv), floor(y*inv), floor(z*inv))
+ * in float.  A point with a non-finite coordinate, or with a cell index outside [-2^20, 2^20) on any axis, is skipped.
+ * Cells are kept sparsely (sorted 63-bit keys, z high, x low): there is no dense box.  For each cell n, S_a = sum x_a (3) and
+ * Q_ab = sum x_a * x_b for a <= b (6; float * float is exact in double), each over the cell's points in ascending point
+ * index in one fixed tree: pad to the next power of two with +0.0, then add adjacent pairs level by level.
+ * Per cell, on the host: mean_a = S_a / n; for a <= b, mirrored,
+ *     C_ab = ((Q_ab - 2 * (S_a * mean_b)) / n + mean_a * mean_b) * ((n - 1.0) / n).
+ * Eigen-decomposition of C by DLIOM_NDT_JACOBI_SWEEPS cyclic Jacobi sweeps over (0,1) (0,2) (1,2) with ICP's rotation
+ * rule; eigenvalues l0 <= l1 <= l2 by a stable sort of the diagonal (ties keep column order), v_k the matching columns.
+ * The cell is VALID iff n >= min_points_per_voxel, l0 >= 0, l1 >= 0, l2 > 0 and every entry of icov is finite, where
+ * l0 and l1 are first raised to 0.01 * l2 if below it and, for a <= b, mirrored,
+ *     icov_ab = ((v_a0*v_b0)/l0 + (v_a1*v_b1)/l1) + (v_a2*v_b2)/l2.
+ * (The test on n comes first: a cell with n < min_points_per_voxel has no C.)  An invalid cell is never a neighbour; PCL
+ * leaves such a leaf in its kd-tree with stale values.
+ *
+ * NEIGHBOURS of a query q (float xyz).  q without a finite coordinate, or whose cell index lies outside [-2^20 - 1, 2^20]
+ * on an axis, has none.  Candidates: the valid cells whose index differs from q's by at most 1 on every axis, visited z
+ * outermost, x fastest, each from -1.  A candidate is a neighbour iff, in float with m = (float)mean, dx = q.x - m.x and so
+ * on, (dx*dx + dy*dy) + dz*dz <= r2, r2 = (float)resolution * (float)resolution, inclusive.  This stands for PCL's FLANN
+ * radius search over the centroids.
+ *
+ * CONSTANTS (host libm log and exp), o = outlier_ratio: c1 = 10 * (1 - o); c2 = o / ((resolution * resolution) *
+ * resolution); d3 = -log(c2); d1 = -log(c1 + c2) - d3; d2 = -2 * log((-log(c1 * exp(-0.5) + c2) - d3) / d1).
+ *
+ * POSE.  p = (tx, ty, tz, a, b, c), T(p) = [R t], R = Rx(a) Ry(b) Rz(c); sa, ca, sb, cb, sc, cc from host libm (no
+ * small-angle shortcut).  A product of three factors is (u*v)*w.  Rows of R:
+ *     (cb*cc, -cb*sc, sb)   (ca*sc + sa*sb*cc, ca*cc - sa*sb*sc, -sa*cb)   (sa*sc - ca*sb*cc, sa*cc + ca*sb*sc, ca*cb).
+ * From a guess (checked as ICP checks it): t = its last column, a = atan2(-R12, R22), b = atan2(R02, sqrt(R00*R00 +
+ * R01*R01)), c = atan2(-R01, R00): Eigen's eulerAngles(0,1,2) rotation, not its branch.  A transformed point is
+ * x' = (float)(((r0*x + r1*y) + r2*z) + t) row by row, as in ICP's Start; x below is the (double) source point itself.
+ *
+ * POINT DERIVATIVES.  J_0..2 are the unit vectors; J_3 = d(Rx)/da, J_4 = d(Rx)/db, J_5 = d(Rx)/dc; H_ij = d2(Rx)/dp_i dp_j
+ * (zero unless i, j >= 3).  Each component is a row of coefficients k dotted with x as (k0*x0 + k1*x1) + k2*x2; a
+ * component not listed is +0.0.  The rows (Magnusson 2009, eq. 6.19 and 6.21):
+ *   J_3: [1] (-sa*sc + ca*sb*cc, -sa*cc - ca*sb*sc, -ca*cb)   [2] (ca*sc + sa*sb*cc, ca*cc - sa*sb*sc, -sa*cb)
+ *   J_4: [0] (-sb*cc, sb*sc, cb)   [1] (sa*cb*cc, -sa*cb*sc, sa*sb)   [2] (-ca*cb*cc, ca*cb*sc, -ca*sb)
+ *   J_5: [0] (-cb*sc, -cb*cc, 0)   [1] (ca*cc - sa*sb*sc, -ca*sc - sa*sb*cc, 0)   [2] (sa*cc + ca*sb*sc, -sa*sc + ca*sb*cc, 0)
+ *   H_33: [1] (-ca*sc - sa*sb*cc, -ca*cc + sa*sb*sc, sa*cb)   [2] (-sa*sc + ca*sb*cc, -sa*cc - ca*sb*sc, -ca*cb)
+ *   H_34: [1] (ca*cb*cc, -ca*cb*sc, ca*sb)   [2] (sa*cb*cc, -sa*cb*sc, sa*sb)
+ *   H_35: [1] (-sa*cc - ca*sb*sc, sa*sc - ca*sb*cc, 0)   [2] (ca*cc - sa*sb*sc, -ca*sc - sa*sb*cc, 0)
+ *   H_44: [0] (-cb*cc, cb*sc, -sb)   [1] (-sa*sb*cc, sa*sb*sc, sa*cb)   [2] (ca*sb*cc, -ca*sb*sc, -ca*cb)
+ *   H_45: [0] (sb*sc, sb*cc, 0)   [1] (-sa*cb*sc, -sa*cb*cc, 0)   [2] (ca*cb*sc, ca*cb*cc, 0)
+ *   H_55: [0] (-cb*cc, cb*sc, 0)   [1] (-ca*sc - sa*sb*cc, -ca*cc + sa*sb*sc, 0)   [2] (-sa*sc + ca*sb*cc, -sa*cc - ca*sb*sc, 0)
+ * Negation is exact, so a signed two-term entry has one value whatever the order of its terms.  The host computes the
+ * 8 + 15 rows once an evaluation.
+ *
+ * EVALUATION at p.  For every source point i and every neighbour cell of x'_i in the order above, xt = (double)x' - mean:
+ *   w_r = (icov_r0*xt0 + icov_r1*xt1) + icov_r2*xt2;  q = (xt0*w0 + xt1*w1) + xt2*w2;  e = E(-(d2 * q) * 0.5);
+ *   f = d2 * e;  if f > 1, f < 0 or f is NaN the cell adds nothing (it is still counted as a pair).  Otherwise
+ *   score += -d1 * e;  f = f * d1;  with cJ_i = icov J_i (rows as w; for i < 3 this is column i of icov) and
+ *   u_i = (xt0*cJ_i0 + xt1*cJ_i1) + xt2*cJ_i2:
+ *   g_i += u_i * f;
+ *   H_ij += f * ((((-d2) * u_i) * u_j + h_ij) + k_ij) for i <= j, mirrored, where h_ij = xt . (icov H_ij) (rows as w, dot as
+ *   q; +0.0 unless i, j >= 3) and k_ij = (J_j0*cJ_i0 + J_j1*cJ_i1) + J_j2*cJ_i2 (for j < 3 this is cJ_ij).
+ * A point's 28 values (score, g 0..5, H 00 01 .. 05 11 12 .. 55) start at +0.0 and are summed over its cells in that order;
+ * the 28 sums over the source index run in ICP's fixed tree (DLIOM_ICP_TREE_MIN_LEAVES), with +0.0 for a point without
+ * neighbours.  The count of (point, neighbour cell) pairs is reported.  An evaluation may leave out the Hessian, or
+ * compute the Hessian alone; what it computes has the same bits.
+ * E(u): +0.0 for u < -708; u itself for a NaN; +inf for u > 708; otherwise k = the nearest integer to
+ * u * 0x1.71547652b82fep+0 (ties to even), r = (u - k * 0x1.62e42fee00000p-1) - k * 0x1.a39ef35793c76p-33, Horner's rule
+ * p = p * r + c_n from p = c_13 down to c_0, c_n = 1/n! rounded to double, and the result is p * 2^k (exact).  Within
+ * 1.14 ulp of the correctly rounded exponential on [-708, 0] (measured on a CPU, 800 000 arguments).
+ *
+ * ALIGNMENT.  Evaluate at the guess's p (with the Hessian).  Then, from it = 0:
+ *   1. delta = -pinv(H) g: DLIOM_NDT_PINV_SWEEPS cyclic Jacobi sweeps on the symmetric 6x6 (pairs (0,1) (0,2) .. (4,5), ICP's
+ *      rule) give l_k and V; y_k = sum_r V_rk * g_r; z_k = y_k / l_k if |l_k| > 6 * 2^-52 * max|l|, else +0.0;
+ *      delta_r = -(sum_k V_rk * z_k); the sums left to right from +0.0.  It stands for PCL's JacobiSVD solve.
+ *   2. s = sqrt of the sum of delta_r^2 (left to right).  s == 0 or NaN: stop, DLIOM_NDT_ZERO_STEP, converged iff s == s;
+ *      `iterations` = it.
+ *   3. dir = delta / s; a = step_length (below); p_r <- p_r + dir_r * a (the point of the step's last evaluation).
+ *   4. Stop, converged, iff it > maximum_iterations (DLIOM_NDT_ITERATIONS) or (it > 0 and |a| < transformation_epsilon)
+ *      (DLIOM_NDT_EPSILON); `iterations` = it + 1.
+ *   5. it += 1.
+ * transformation_probability = score / N, N = every source point; score, g, H are those of the last evaluation.
+ *
+ * STEP LENGTH (computeStepLengthMT), step_max = step_size, step_min = transformation_epsilon / 2.
+ *   phi0 = -score; dphi0 = -(g . dir) (left to right).  dphi0 == 0: return 0 (nothing is evaluated).  dphi0 > 0: negate
+ *   dphi0 and dir (the caller's too).  a_t = max(min(s, step_max), step_min).  Evaluate at p + dir*a_t with the Hessian.
+ *   DLIOM_NDT_STEP_CLAMPED: return a_t.  This is PCL 1.8.0, whose interval test `(step_max - step_min) > 0` makes the
+ *   search loop unreachable.
+ *   DLIOM_NDT_STEP_MORE_THUENTE (as later PCL): mu = 1e-4, nu = 0.9; a_l = a_u = 0; f_l = f_u = 0 (psi(0));
+ *   g_l = g_u = dphi0 - mu * dphi0; open = true; phi_t = -score, dphi_t = -(g . dir), psi_t = (phi_t - phi0) - (mu * dphi0) * a_t,
+ *   dpsi_t = dphi_t - mu * dphi0.  While fewer than 10 trials ran, the interval has not converged and not (psi_t <= 0 and
+ *   dphi_t <= -nu * dphi0): a_t = trial(..., psi_t, dpsi_t) if open else trial(..., phi_t, dphi_t); a_t = max(min(a_t,
+ *   step_max), step_min); evaluate at p + dir*a_t WITHOUT the Hessian; phi_t, dphi_t, psi_t, dpsi_t anew; if open and
+ *   psi_t <= 0 and dpsi_t >= 0: open = false, f_l = (f_l + phi0) - (mu * dphi0) * a_l, g_l = g_l + mu * dphi0, likewise u;
+ *   then the interval update with (psi_t, dpsi_t) if open, else (phi_t, dphi_t).  If any trial ran, one Hessian-only
+ *   evaluation at the final point.
+ *   trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t): z = (3 * (f_t - f_l) / (a_t - a_l) - g_t) - g_l; w = sqrt(z*z - g_t*g_l);
+ *   a_c = a_l + (a_t - a_l) * ((w - g_l) - z) / ((g_t - g_l) + 2 * w).
+ *     1. f_t > f_l: a_q = a_l - 0.5 * (a_l - a_t) * g_l / (g_l - (f_l - f_t) / (a_l - a_t)); a_c if |a_c - a_l| < |a_q - a_l|,
+ *        else 0.5 * (a_q + a_c).
+ *     2. else g_t * g_l < 0: a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l; a_c if |a_c - a_t| >= |a_s - a_t|, else a_s.
+ *     3. else |g_t| <= |g_l|: a_s as in 2; n = a_c if |a_c - a_t| < |a_s - a_t| else a_s; min(a_t + 0.66 * (a_u - a_t), n) if
+ *        a_t > a_l, else the max of the two.
+ *     4. else: z = (3 * (f_t - f_u) / (a_t - a_u) - g_t) - g_u; w = sqrt(z*z - g_t*g_u);
+ *        a_u + (a_t - a_u) * ((w - g_u) - z) / ((g_t - g_u) + 2 * w).
+ *   Interval update: 1. f_t > f_l: u <- t.  2. else g_t * (a_l - a_t) > 0: l <- t.  3. else g_t * (a_l - a_t) < 0: u <- l, then
+ *   l <- t.  4. else: converged.
+ *
+ * FITNESS SCORE (the tool's getFitnessScore()): with a dliom_nn_index of the target, ICP's: one search on the final
+ * x'_i without a bound, the mean of d2 by the same tree; NaN and count 0 without an index.
+ *
+ * No floating-point atomics anywhere: two calls on one input give the same bytes.  Malformed input fails with
+ * DLIOM_ERR_INVALID_ARGUMENT before anything runs: NULLs, clouds (or an index) of another context, a non-finite or
+ * non-positive resolution or step size, an outlier ratio outside (0, 1), a negative or non-finite epsilon, a negative
+ * maximum_iterations, min_points_per_voxel < 3, an unknown step mode, options whose resolution is not the target's, a bad
+ * guess, an empty target.  A target without a valid cell is accepted: every evaluation is all zeros and the alignment ends
+ * with DLIOM_NDT_ZERO_STEP. */
+#define DLIOM_NDT_JACOBI_SWEEPS 8    /* 3x3, per cell */
+#define DLIOM_NDT_PINV_SWEEPS 12     /* 6x6, per iteration */
+#define DLIOM_NDT_MAX_CELL_INDEX (1 << 20)
+enum { DLIOM_NDT_STEP_CLAMPED = 0, DLIOM_NDT_STEP_MORE_THUENTE = 1 };
+enum { DLIOM_NDT_NOT_CONVERGED = 0, DLIOM_NDT_ITERATIONS = 1, DLIOM_NDT_EPSILON = 2, DLIOM_NDT_ZERO_STEP = 3 };
+enum { DLIOM_NDT_EVAL_GRADIENT = 0, DLIOM_NDT_EVAL_ALL = 1, DLIOM_NDT_EVAL_HESSIAN = 2 };
+typedef struct dliom_ndt_target dliom_ndt_target;
+typedef struct dliom_ndt_options {
+  double resolution;             /* metres a cell */
+  double step_size;              /* step_max */
+  double transformation_epsilon;
+  double outlier_ratio;
+  int maximum_iterations;
+  int min_points_per_voxel;
+  int step_mode;                 /* DLIOM_NDT_STEP_* */
+  int reserved;                  /* 0 */
+} dliom_ndt_options;
+typedef struct dliom_ndt_cell {
+  int32_t index[3];
+  int32_t valid;
+  int64_t n;
+  double mean[3];
+  double icov[6];                /* 00 01 02 11 12 22; zeros for an invalid cell */
+} dliom_ndt_cell;
+typedef struct dliom_ndt_target_memory {
+  int64_t points, kept_points, cells, valid_cells, target_bytes, scratch_bytes;
+  int64_t read_backs;            /* of the build */
+  double build_ms;               /* keys, sort, sums, the host step and the upload; filled only under profiling */
+} dliom_ndt_target_memory;
+typedef struct dliom_ndt_result {
+  int converged, reason, iterations; /* reason: DLIOM_NDT_* */
+  int reserved;
+  int64_t evaluations_with_hessian, evaluations_without_hessian; /* a Hessian-only evaluation counts as with */
+  double p[6];
+  double transform[16];              /* T(p), row-major */
+  double score, transformation_probability;
+  double fitness_score;              /* NaN when fitness_count is 0 */
+  int64_t fitness_count;
+  int64_t pairs;                     /* (point, neighbour cell) pairs of the last evaluation */
+  int64_t read_backs;                /* one an evaluation, one for the fitness score */
+  /* milliseconds over all evaluations (host_ms: pseudo-inverse, step length and decisions); filled (the call then
+   * synchronises the stream) only while the context's profiling is on */
+  double evaluate_ms, reduce_ms, host_ms;
+} dliom_ndt_result;
+/* The tool's and the front end's values: resolution 1.0, step 0.1, epsilon 0.01, 35 iterations; PCL's 0.55 and 6;
+ * DLIOM_NDT_STEP_CLAMPED. */
+int dliom_ndt_default_options(dliom_ndt_options* options);
+/* Builds the cells of `target` (resolution and min_points_per_voxel of `options`): two round trips (the cell count, then
+ * the sums) and one upload.  The cloud may be destroyed afterwards.  One thread at a time per target, like its context;
+ * destroy the target before the context. */
+int dliom_ndt_target_create(dliom_ctx* ctx, const dliom_cloud* target, const dliom_ndt_options* options, dliom_ndt_target** out);
+void dliom_ndt_target_destroy(dliom_ndt_target* target);
+int dliom_ndt_target_memory_stats(const dliom_ndt_target* target, dliom_ndt_target_memory* out);
+/* Diagnostic: every cell in key order (z, then y, then x).  cells == NULL: only *count.  capacity < *count: DLIOM_ERR_CAPACITY. */
+int dliom_ndt_target_cells(const dliom_ndt_target* target, dliom_ndt_cell* cells, int64_t capacity, int64_t* count);
+/* Diagnostic: one evaluation at p6.  what: DLIOM_NDT_EVAL_*; what is not computed comes back as zeros.  hessian36 is
+ * row-major and mirrored. */
+int dliom_ndt_evaluate(dliom_ndt_target* target, const dliom_cloud* source, const double* p6, const dliom_ndt_options* options,
+                       int what, double* score, double* gradient6, double* hessian36, int64_t* pairs);
+/* Aligns `source` to the target from guess16.  fitness_index (may be NULL): an index of the target's cloud on the same
+ * context.  aligned (may be NULL): the final x'_i as a cloud of the context. */
+int dliom_ndt_align(dliom_ndt_target* target, const dliom_cloud* source, const double* guess16, const dliom_ndt_options* options,
+                    dliom_nn_index* fitness_index, dliom_ndt_result* result, dliom_cloud** aligned);
+
 /* Kernel timing (HIP events on the context's stream). */
 enum {
   DLIOM_KERNEL_RTCSM_SCORE = 0, /* score-volume kernel (dominant) */
