@@ -976,6 +976,14 @@ struct LocalTrajectoryBuilderOptions3D {
   double scan_period = 0.1;
   bool enable_manual_descrew = false;    // eable_mannually_discrew_
   int rotational_histogram_size = 120;   // trajectory_builder_3d.lua: rotational_histogram_size
+  // The initialisation (.cc:164-176, 203-330, 372-381).  false, the default: the state comes from SetInitialState() and
+  // everything before it is dropped.  true: the builder initialises itself from its first messages as the reference does
+  // -- InitilizeByNDT if enable_ndt_initialization, else InitializeStatic -- and every call returns nullptr until then.
+  bool internal_initialization = false;
+  bool enable_ndt_initialization = false;
+  int frames_for_dynamic_initialization = 7;
+  int frames_for_static_initialization = 7;
+  transform::Rigid3d transform_lb;       // AlignWithWorld's T_lb (identity)
 };
 
 // proto::SubmapQuery::Response (mapping/proto/submap_visualization.proto) as plain structs.  `cells` is the texture's
@@ -1137,9 +1145,10 @@ class ActiveSubmaps3D {
   dliom_front_end* fe_ = nullptr;
 };
 
-// LocalTrajectoryBuilder3D (mapping/internal/3d/local_trajectory_builder_3d.h:83-111), steady state: the state after
-// the reference's IMU-lidar initialisation (InitializeStatic / InitilizeByNDT: PCL + VINS alignment, start-up only,
-// out of scope -- SURVEY 8c) is supplied through SetInitialState().  AddOdometryData is accepted and ignored like in
+// LocalTrajectoryBuilder3D (mapping/internal/3d/local_trajectory_builder_3d.h:83-111).  By default the state after the
+// reference's IMU-lidar initialisation is supplied through SetInitialState() and everything before it is dropped; with
+// options.internal_initialization the builder is fed from its first message and initialises itself as the reference does
+// (InitializeStatic, or InitilizeByNDT with AlignWithWorld: DESIGN 3.24).  AddOdometryData is accepted and ignored like in
 // the reference's D-LIOM path, whose extrapolator is never created (.cc:324-333).
 class LocalTrajectoryBuilder3D {
  public:
@@ -1175,8 +1184,20 @@ class LocalTrajectoryBuilder3D {
     if (imu.graph_reset_every >= 2 && !options.keep_imu_window_size) imu.window_size = 0;
     Check(dliom_imu_window_create(&imu, &window_), "dliom_imu_window_create");
     Check(dliom_range_accumulator_create(context->get(), &accumulator_), "dliom_range_accumulator_create");
+    if (options.internal_initialization && options.enable_ndt_initialization) {
+      if (options.frames_for_dynamic_initialization < 1 || options.frames_for_dynamic_initialization + 1 > DLIOM_INIT_MAX_FRAMES)
+        Check(DLIOM_ERR_INVALID_ARGUMENT, "frames_for_dynamic_initialization");
+      const double zero[3] = {0., 0., 0.};
+      const dliom_imu_noise noise{imu.acc_noise, imu.gyr_noise, imu.acc_bias_noise, imu.gyr_bias_noise};
+      Check(dliom_imu_integrator_create(zero, zero, &noise, &init_integrator_), "dliom_imu_integrator_create");
+      dliom_ndt_options ndt;
+      Check(dliom_ndt_default_options(&ndt), "dliom_ndt_default_options");  // .cc:252-259: 0.01, 0.1, 1.0, 35
+      Check(dliom_ndt_scan_matcher_create(context->get(), &ndt, 0.2f, &init_matcher_), "dliom_ndt_scan_matcher_create");
+    }
   }
   ~LocalTrajectoryBuilder3D() {
+    if (init_integrator_ != nullptr) dliom_imu_integrator_destroy(init_integrator_);
+    dliom_ndt_scan_matcher_destroy(init_matcher_);
     dliom_range_accumulator_destroy(accumulator_);
     dliom_imu_window_destroy(window_);
   }
@@ -1199,9 +1220,32 @@ class LocalTrajectoryBuilder3D {
     last_imu_time_ = -1;
     imu_initialized_ = true;
     have_prediction_ = false;
+    const std::array<double, 7> p = pose.ToArray();
+    for (int k = 0; k < 7; ++k) initial_state_[k] = p[k];
+    for (int k = 0; k < 3; ++k) initial_state_[7 + k] = velocity.v[k];
+    for (int k = 0; k < 6; ++k) initial_state_[10 + k] = bias6[k];
   }
+  // The state the last SetInitialState() took (what InitializeIMU starts from): pose7, velocity3, bias6.  false before it.
+  bool InitialState(double state16[16]) const {
+    if (!imu_initialized_) return false;
+    for (int k = 0; k < 16; ++k) state16[k] = initial_state_[k];
+    return true;
+  }
+  // InitilizeByNDT's frames held (buffered_scan_count_) and the AlignWithWorld calls that failed and started over
+  int initialization_frames() const { return static_cast<int>(init_frames_.size()); }
+  int64_t initialization_failures() const { return initialization_failures_; }
   void AddImuData(const sensor::ImuData& imu) {
-    if (!imu_initialized_) return;  // the reference buffers it for its initialisation
+    if (!imu_initialized_) {  // .cc:165-176; without internal_initialization the data is dropped
+      if (!options_.internal_initialization) return;
+      if (init_integrator_ != nullptr) {
+        const double dt = last_imu_time_ini_ < 0 ? 1.0 / 500.0 : static_cast<double>(imu.time - last_imu_time_ini_) * 1e-7;
+        last_imu_time_ini_ = imu.time;
+        Check(dliom_imu_integrator_push_back(init_integrator_, dt, imu.linear_acceleration, imu.angular_velocity), "AddImuData (initialisation)");
+      } else {
+        init_imu_buffer_.push_back(imu);
+      }
+      return;
+    }
     const double dt = last_imu_time_ < 0 ? 1.0 / 500.0 : static_cast<double>(imu.time - last_imu_time_) * 1e-7;  // .cc:183-185
     last_imu_time_ = imu.time;
     if (!(dt > 0)) return;
@@ -1218,6 +1262,8 @@ class LocalTrajectoryBuilder3D {
     // ranges, the packed staging vector: ~3 MB of host traffic and two reallocating push_back loops per 64 x 1024 scan)
     // were a quarter of the adapter's time per scan (round 6, tools/wref_cpp.cc).
     if (synchronizer_.SingleSensor(sensor_id) && !options_.enable_manual_descrew && options_.num_accumulated_range_data == 1) {
+      if (!unsynchronized.ranges.empty() && !imu_initialized_)
+        return Initialize(unsynchronized.time, [&] { return UploadPoints(&unsynchronized.ranges[0].x, 4, unsynchronized.ranges.size()); });
       if (unsynchronized.ranges.empty() || !imu_initialized_ || !have_prediction_) return nullptr;
       if (unsynchronized.ranges.back().t > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
       static_assert(sizeof(sensor::TimedPoint) == 16, "packed x, y, z, t");
@@ -1242,6 +1288,13 @@ class LocalTrajectoryBuilder3D {
  private:
   // the general host path behind the synchronizer: pack, upload, de-skew + accumulate
   std::unique_ptr<MatchingResult> AddSynchronizedRangeData(const sensor::TimedPointCloudOriginData& sync) {
+    if (!sync.ranges.empty() && !imu_initialized_) {
+      static_assert(sizeof(sensor::TimedPointCloudOriginData::RangeMeasurement) % sizeof(float) == 0, "a stride in floats");
+      return Initialize(sync.time, [&] {
+        return UploadPoints(&sync.ranges[0].point_time.x, sizeof(sensor::TimedPointCloudOriginData::RangeMeasurement) / sizeof(float),
+                            sync.ranges.size());
+      });
+    }
     if (sync.ranges.empty() || !imu_initialized_ || !have_prediction_) return nullptr;
     if (sync.ranges.back().point_time.t > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
     // prev_state_ and predicted_states_.back() (.cc:424-427)
@@ -1307,6 +1360,8 @@ class LocalTrajectoryBuilder3D {
       return AddSynchronizedRangeData(sync.host);
     }
     if (sync.origins.size() > 1) ++device_merges_;
+    if (sync.ranges != nullptr && sync.ranges->size() != 0 && !imu_initialized_)
+      return Initialize(sync.time, [&] { return DevicePoints(*sync.ranges); });
     if (sync.ranges == nullptr || sync.ranges->size() == 0 || !imu_initialized_ || !have_prediction_) return nullptr;
     if (sync.ranges->back_time() > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
     double prev[7], vel[3], bias[6], predicted[7], pvel[3];
@@ -1355,6 +1410,7 @@ class LocalTrajectoryBuilder3D {
     return synchronizer_.SingleSensor(sensor_id) && !options_.enable_manual_descrew && options_.num_accumulated_range_data == 1;
   }
   std::unique_ptr<MatchingResult> AddSingleSensorRangeData(const sensor::TimedCloudOnDevice& ranges) {
+    if (ranges.size() != 0 && !imu_initialized_) return Initialize(ranges.time(), [&] { return DevicePoints(ranges); });
     if (ranges.size() == 0 || !imu_initialized_ || !have_prediction_) return nullptr;
     if (ranges.back_time() > 0.1f) Check(DLIOM_ERR_INVALID_ARGUMENT, "CHECK_LE(ranges.back().point_time[3], 0.1f)");
     DLIOM_ADAPTER_STAGE(0);
@@ -1542,6 +1598,177 @@ class LocalTrajectoryBuilder3D {
     const float cx = qy * uvz - qz * uvy, cy = qz * uvx - qx * uvz, cz = qx * uvy - qy * uvx;
     return sensor::Vector3f{((x + w * uvx) + cx) + p7[0], ((y + w * uvy) + cy) + p7[1], ((z + w * uvz) + cz) + p7[2]};
   }
+
+  // ---- the reference's initialisation (.cc:372-381): every scan before the state is known ends here; nullptr, always ----
+  template <class MakeCloud>
+  std::unique_ptr<MatchingResult> Initialize(int64_t time, MakeCloud&& make_cloud) {
+    if (!options_.internal_initialization) return nullptr;  // dropped: the state comes from SetInitialState()
+    if (options_.enable_ndt_initialization) {
+      InitilizeByNDT(time, make_cloud);
+    } else if (accumulated_frame_num_++ > options_.frames_for_static_initialization) {
+      InitializeStatic();
+    }
+    return nullptr;
+  }
+  // cvtPointCloud: the xyz of the scan as a cloud of the context (owned by the caller)
+  dliom_cloud* UploadPoints(const float* first_x, size_t stride_floats, size_t n) {
+    std::vector<float> xyz(3 * n);
+    for (size_t i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) xyz[3 * i + a] = first_x[stride_floats * i + a];
+    dliom_cloud* cloud = nullptr;
+    Check(dliom_cloud_create(context_->get(), xyz.data(), static_cast<int64_t>(n), &cloud), "dliom_cloud_create");
+    return cloud;
+  }
+  dliom_cloud* DevicePoints(const sensor::TimedCloudOnDevice& ranges) {
+    dliom_cloud* cloud = nullptr;
+    Check(dliom_timed_cloud_points(context_->get(), ranges.get(), &cloud), "dliom_timed_cloud_points");
+    return cloud;
+  }
+  // InitializeStatic (.cc:203-229) on the buffered IMU samples; without one the scan is only counted
+  void InitializeStatic() {
+    if (init_imu_buffer_.empty()) return;
+    std::vector<double> acc(3 * init_imu_buffer_.size()), gyr(3 * init_imu_buffer_.size());
+    for (size_t i = 0; i < init_imu_buffer_.size(); ++i)
+      for (int a = 0; a < 3; ++a) {
+        acc[3 * i + a] = init_imu_buffer_[i].linear_acceleration[a];
+        gyr[3 * i + a] = init_imu_buffer_[i].angular_velocity[a];
+      }
+    double R[9], bias[6], P[3], V[3];
+    Check(dliom_imu_static_initialization(static_cast<int64_t>(init_imu_buffer_.size()), acc.data(), gyr.data(), options_.imu.gravity, R,
+                                          bias, bias + 3, P, V),
+          "dliom_imu_static_initialization");
+    init_imu_buffer_.clear();
+    SetInitialState(transform::Rigid3d(transform::Vector3d{{P[0], P[1], P[2]}}, QuaternionOfMatrix(R)), transform::Vector3d{{V[0], V[1], V[2]}},
+                    bias);
+  }
+  // InitilizeByNDT (.cc:231-330), including what looks odd: a frame's translation is the pair's own t, not an accumulated
+  // one.  The guess and the velocity are float arithmetic, as the reference's Matrix4f / Vector3f: init_q = (float)deltaQ,
+  // init_R its matrix by toRotationMatrix's formula in float, dt = (float)(seconds between the scans),
+  // init_t = linear_velocity * dt, linear_velocity = t / dt.
+  template <class MakeCloud>
+  void InitilizeByNDT(int64_t time, MakeCloud&& make_cloud) {
+    const double zero[3] = {0., 0., 0.};
+    const dliom_imu_noise noise{options_.imu.acc_noise, options_.imu.gyr_noise, options_.imu.acc_bias_noise, options_.imu.gyr_bias_noise};
+    struct Scan {  // destroyed on every way out
+      dliom_cloud* cloud;
+      ~Scan() { dliom_cloud_destroy(cloud); }
+    };
+    if (init_frames_.empty()) {
+      if (last_imu_time_ini_ < 0) return;  // still no IMU sample
+      const Scan scan{make_cloud()};
+      Check(dliom_ndt_scan_matcher_match(init_matcher_, scan.cloud, nullptr, nullptr), "MatchByNDT (first scan)");
+      last_scan_time_ = time;
+      linear_velocity_[0] = linear_velocity_[1] = linear_velocity_[2] = 0.f;
+      dliom_init_frame first = {};
+      first.pose[3] = 1.0;  // the identity, no preintegration
+      init_frames_.push_back(first);
+      Check(dliom_imu_integrator_reset(init_integrator_, zero, zero, &noise), "resetIntegration");
+      return;
+    }
+    const float dt = static_cast<float>(static_cast<double>(time - last_scan_time_) * 1e-7);
+    dliom_imu_preintegration running;
+    Check(dliom_imu_integrator_get(init_integrator_, &running), "dliom_imu_integrator_get");
+    const float w = static_cast<float>(running.delta_q[0]), x = static_cast<float>(running.delta_q[1]),
+                y = static_cast<float>(running.delta_q[2]), z = static_cast<float>(running.delta_q[3]);
+    const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
+                tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    const float guess[16] = {1.f - (tyy + tzz), txy - twz, txz + twy, linear_velocity_[0] * dt,
+                             txy + twz, 1.f - (txx + tzz), tyz - twx, linear_velocity_[1] * dt,
+                             txz - twy, tyz + twx, 1.f - (txx + tyy), linear_velocity_[2] * dt,
+                             0.f, 0.f, 0.f, 1.f};
+    double guess16[16];
+    for (int k = 0; k < 16; ++k) guess16[k] = static_cast<double>(guess[k]);
+    dliom_ndt_result result = {};
+    {
+      const Scan scan{make_cloud()};
+      Check(dliom_ndt_scan_matcher_match(init_matcher_, scan.cloud, guess16, &result), "MatchByNDT");
+    }
+    float R[9], t[3];  // MatchByNDT's Matrix3f and Vector3f
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) R[3 * r + c] = static_cast<float>(result.transform[4 * r + c]);
+      t[r] = static_cast<float>(result.transform[4 * r + 3]);
+    }
+    // Rigid3d(t, Quaterniond(R_previous_frame * R))
+    const dliom_init_frame& previous = init_frames_.back();
+    double Rp[9], Rf[9];
+    MatrixOfQuaternion(&previous.pose[3], Rp);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c)
+        Rf[3 * r + c] = (Rp[3 * r] * static_cast<double>(R[c]) + Rp[3 * r + 1] * static_cast<double>(R[3 + c])) +
+                        Rp[3 * r + 2] * static_cast<double>(R[6 + c]);
+    const transform::Quaterniond q = QuaternionOfMatrix(Rf);
+    dliom_init_frame frame = {};
+    for (int a = 0; a < 3; ++a) {
+      frame.pose[a] = static_cast<double>(t[a]);
+      frame.delta_p[a] = running.delta_p[a];
+      frame.delta_v[a] = running.delta_v[a];
+      linear_velocity_[a] = t[a] / dt;
+    }
+    for (int a = 0; a < 4; ++a) frame.pose[3 + a] = q.wxyz[a];
+    frame.has_preintegration = 1;
+    frame.sum_dt = running.sum_dt;
+    init_frames_.push_back(frame);
+    Check(dliom_imu_integrator_reset(init_integrator_, zero, zero, &noise), "resetIntegration");
+    last_scan_time_ = time;
+    const int frames = options_.frames_for_dynamic_initialization + 1;
+    if (static_cast<int>(init_frames_.size()) != frames) return;
+    std::vector<double> P(3 * frames), Rs(9 * frames), V(3 * frames);
+    double g_laser[3], Rw[9], excitation = 0.;
+    int outcome = -1;
+    const std::array<double, 7> lb = options_.transform_lb.ToArray();
+    Check(dliom_imu_lidar_align_with_world(init_frames_.data(), frames, lb.data(), options_.imu.gravity, P.data(), Rs.data(), V.data(),
+                                           g_laser, Rw, &excitation, &outcome),
+          "AlignWithWorld");
+    if (outcome != DLIOM_INIT_OK) {  // re-initialisation: one frame, the last scan stays the matcher's
+      ++initialization_failures_;
+      init_frames_.resize(1);
+      return;
+    }
+    const int last = frames - 1;
+    const double bias[6] = {0., 0., 0., 0., 0., 0.};
+    SetInitialState(transform::Rigid3d(transform::Vector3d{{P[3 * last], P[3 * last + 1], P[3 * last + 2]}}, QuaternionOfMatrix(&Rs[9 * last])),
+                    transform::Vector3d{{V[3 * last], V[3 * last + 1], V[3 * last + 2]}}, bias);
+  }
+  // Eigen's Quaternion::toRotationMatrix and Quaterniond(Matrix3d), operation for operation (row-major matrices)
+  static void MatrixOfQuaternion(const double wxyz[4], double R[9]) {
+    const double w = wxyz[0], x = wxyz[1], y = wxyz[2], z = wxyz[3];
+    const double tx = 2. * x, ty = 2. * y, tz = 2. * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
+                 tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    const double m[9] = {1. - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1. - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1. - (txx + tyy)};
+    for (int k = 0; k < 9; ++k) R[k] = m[k];
+  }
+  static transform::Quaterniond QuaternionOfMatrix(const double m[9]) {
+    transform::Quaterniond q{{1., 0., 0., 0.}};
+    double t = (m[0] + m[4]) + m[8];
+    if (t > 0.) {
+      t = std::sqrt(t + 1.0);
+      q.wxyz[0] = 0.5 * t;
+      t = 0.5 / t;
+      q.wxyz[1] = (m[7] - m[5]) * t;
+      q.wxyz[2] = (m[2] - m[6]) * t;
+      q.wxyz[3] = (m[3] - m[1]) * t;
+    } else {
+      int i = 0;
+      if (m[4] > m[0]) i = 1;
+      if (m[8] > m[4 * i]) i = 2;
+      const int j = (i + 1) % 3, k = (j + 1) % 3;
+      t = std::sqrt(((m[4 * i] - m[4 * j]) - m[4 * k]) + 1.0);
+      q.wxyz[1 + i] = 0.5 * t;
+      t = 0.5 / t;
+      q.wxyz[0] = (m[3 * k + j] - m[3 * j + k]) * t;
+      q.wxyz[1 + j] = (m[3 * j + i] + m[3 * i + j]) * t;
+      q.wxyz[1 + k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+    return q;
+  }
+  std::vector<dliom_init_frame> init_frames_;  // all_laser_transforms_[0 .. buffered_scan_count_)
+  dliom_imu_integrator* init_integrator_ = nullptr;
+  dliom_ndt_scan_matcher* init_matcher_ = nullptr;  // holds last_scan_
+  std::vector<sensor::ImuData> init_imu_buffer_;
+  int64_t last_imu_time_ini_ = -1, last_scan_time_ = 0, initialization_failures_ = 0;
+  float linear_velocity_[3] = {0.f, 0.f, 0.f};
+  int accumulated_frame_num_ = 0;
+  double initial_state_[16] = {};
 
   Context* context_;
   LocalTrajectoryBuilderOptions3D options_;
@@ -3534,11 +3761,9 @@ inline std::string FormatGroundTruthLine(int64_t stamp_from, int64_t stamp_to, d
 }
 
 // pcl::ApproximateVoxelGrid<PointXYZ> as PCL 1.8.0 runs it (MatchByNDT filters both clouds with it at 0.2 m), on the HOST:
-// it is sequential by construction -- the output depends on the stream order -- and a device version is open.
-// The statement: inv = 1.0f / leaf; a point's voxel is (floor(x * inv), floor(y * inv), floor(z * inv)) in float, cast to
-// int; its slot is (ix * 7171 + iy * 3079 + iz * 4231) & 511 in int arithmetic (wrapping).  A slot that holds another voxel
-// is flushed to the output first (centroid = float sums / (float)count, the sums taken in stream order) and starts anew;
-// at the end the occupied slots are flushed in slot order.  xyz only; the points are taken to be finite.
+// the sequential loop of the definition in dliom.h ("the approximate voxel grid"), which
+// dliom_cloud_approximate_voxel_filter replays on the device, bit for bit; this class is the cross-check of that call
+// (tests/cpp/approx_voxel_adapter.cc).  xyz only; the points are taken to be finite.
 class ApproximateVoxelGrid {
  public:
   void setLeafSize(float x, float y, float z) {
@@ -3695,6 +3920,40 @@ inline void MatchByNDT(Context* context, const sensor::PointCloud& pre_scan, con
     translation3[r] = t(r, 3);
   }
 }
+
+// MatchByNDT over a stream of scans, as InitilizeByNDT calls it (local_trajectory_builder_3d.cc:231-330): every scan is
+// filtered once, on the device, and aligned to its predecessor, whose cells stay there (dliom_ndt_scan_matcher).  For every
+// pair the rotation and translation are, bit for bit, MatchByNDT's above for the same two raw scans and guess.
+class NdtScanMatcher {
+ public:
+  explicit NdtScanMatcher(Context* context, float leaf = 0.2f) {
+    dliom_ndt_options options;
+    Check(dliom_ndt_default_options(&options), "dliom_ndt_default_options");
+    Check(dliom_ndt_scan_matcher_create(context->get(), &options, leaf, &matcher_), "dliom_ndt_scan_matcher_create");
+  }
+  ~NdtScanMatcher() { dliom_ndt_scan_matcher_destroy(matcher_); }
+  NdtScanMatcher(const NdtScanMatcher&) = delete;
+  NdtScanMatcher& operator=(const NdtScanMatcher&) = delete;
+  // -> false for the first scan (nothing is written), true for every later one.  `scan`: a cloud of the matcher's context
+  // (dliom_cloud_create of a host cloud; dliom_timed_cloud_points of a decoded, stamped or merged one)
+  bool Match(const dliom_cloud* scan, const Matrix4f& init_guess, float rotation9[9], float translation3[3]) {
+    double guess16[16];
+    for (int k = 0; k < 16; ++k) guess16[k] = static_cast<double>(init_guess.m[k]);
+    dliom_ndt_result result = {};
+    int had_target = 0;
+    Check(dliom_ndt_scan_matcher_has_target(matcher_, &had_target), "dliom_ndt_scan_matcher_has_target");
+    Check(dliom_ndt_scan_matcher_match(matcher_, scan, guess16, &result), "dliom_ndt_scan_matcher_match");
+    if (had_target == 0) return false;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) rotation9[3 * r + c] = static_cast<float>(result.transform[4 * r + c]);
+      translation3[r] = static_cast<float>(result.transform[4 * r + 3]);
+    }
+    return true;
+  }
+
+ private:
+  dliom_ndt_scan_matcher* matcher_ = nullptr;
+};
 }  // namespace registration
 }  // namespace dliom
 

@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "../../include/dliom.h"
+#include "sym_solve.h"
 
 namespace {
 
@@ -449,30 +450,7 @@ struct GFrame {   // Rigid3dWithPreintegrator: a pose and the preintegration tha
   double dt;      // deltaTij()
   V3 dP, dV;      // deltaPij(), deltaVij()
 };
-bool solve_sym(const double* A, const double* b, int n, double* x) {  // A.ldlt().solve(b), n <= 3
-  double M[3][4];
-  for (int i = 0; i < n; ++i) {
-    for (int j = 0; j < n; ++j) M[i][j] = A[i * n + j];
-    M[i][n] = b[i];
-  }
-  for (int c = 0; c < n; ++c) {
-    int piv = c;
-    for (int r = c + 1; r < n; ++r)
-      if (std::fabs(M[r][c]) > std::fabs(M[piv][c])) piv = r;
-    if (!(std::fabs(M[piv][c]) > 0.0)) return false;
-    for (int j = 0; j <= n; ++j) std::swap(M[c][j], M[piv][j]);
-    for (int r = c + 1; r < n; ++r) {
-      const double f = M[r][c] / M[c][c];
-      for (int j = c; j <= n; ++j) M[r][j] -= f * M[c][j];
-    }
-  }
-  for (int i = n - 1; i >= 0; --i) {
-    double v = M[i][n];
-    for (int j = i + 1; j < n; ++j) v -= M[i][j] * x[j];
-    x[i] = v / M[i][i];
-  }
-  return true;
-}
+using dliom::solve_sym;  // A.ldlt().solve(b): sym_solve.h, shared with imu_lidar_init.cc
 // ApproximateGravity (:20-97): [R_i^T dt^2/2; R_i^T dt] g = [dP_j + R_i^T R_j tlb - tlb - R_i^T (T_j - T_i) + dt V_i;
 // dV_j + V_i - R_i^T R_j V_{i+1}], normal equations over the consecutive pairs, x 1000, solved; |g| within 0.5 of g_norm.
 // frame_j's OWN preintegration is paired with the poses of frames i and j, as the reference does.

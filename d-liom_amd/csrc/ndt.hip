@@ -19,6 +19,8 @@
 //   tree_reduce_kernel (tree_reduce.h) and ndt_finish_kernel  ICP's fixed tree over the source index; the sums and the
 //                       pair count into the page-locked block (kPinNdtSums) and the completion word: one polled read-back
 // The pseudo-inverse, the step length and every decision run on the host between evaluations.
+// A stream of scans (dliom_ndt_scan_matcher, MatchByNDT as InitilizeByNDT calls it): each scan through the approximate
+// voxel grid (approx_voxel.hip) once, aligned to the cells its predecessor left, then its own cells built and kept.
 #include <hipcub/hipcub.hpp>
 
 #include <chrono>
@@ -43,6 +45,13 @@ struct dliom_ndt_target {
   int poll_us = 150;
   int64_t build_read_backs = 0;
   double build_ms = 0.0;
+};
+
+struct dliom_ndt_scan_matcher {
+  dliom_ctx* ctx;
+  dliom_ndt_options options;
+  float leaf;
+  dliom_ndt_target* target;  // the previous scan's cells (null before the first scan)
 };
 
 namespace dliom {
@@ -1031,6 +1040,46 @@ int dliom_ndt_align(dliom_ndt_target* target, const dliom_cloud* source, const d
     }
   }
   *result = res;
+  return DLIOM_OK;
+}
+
+// ---- MatchByNDT over a stream of scans: the previous scan's cells stay on the device -----------------------------------------
+int dliom_ndt_scan_matcher_create(dliom_ctx* ctx, const dliom_ndt_options* options, float leaf, dliom_ndt_scan_matcher** out) {
+  if (out != nullptr) *out = nullptr;
+  if (ctx == nullptr || out == nullptr || !dliom::ndt_options_ok(options) || !(leaf > 0.f)) return DLIOM_ERR_INVALID_ARGUMENT;
+  *out = new dliom_ndt_scan_matcher{ctx, *options, leaf, nullptr};
+  return DLIOM_OK;
+}
+
+void dliom_ndt_scan_matcher_destroy(dliom_ndt_scan_matcher* matcher) {
+  if (matcher == nullptr) return;
+  dliom_ndt_target_destroy(matcher->target);
+  delete matcher;
+}
+
+int dliom_ndt_scan_matcher_has_target(const dliom_ndt_scan_matcher* matcher, int* has_target) {
+  if (matcher == nullptr || has_target == nullptr) return DLIOM_ERR_INVALID_ARGUMENT;
+  *has_target = matcher->target != nullptr ? 1 : 0;
+  return DLIOM_OK;
+}
+
+int dliom_ndt_scan_matcher_match(dliom_ndt_scan_matcher* matcher, const dliom_cloud* scan, const double* guess16,
+                                 dliom_ndt_result* result) {
+  if (matcher == nullptr || scan == nullptr || scan->ctx != matcher->ctx) return DLIOM_ERR_INVALID_ARGUMENT;
+  const bool first = matcher->target == nullptr;
+  if (!first && (guess16 == nullptr || result == nullptr)) return DLIOM_ERR_INVALID_ARGUMENT;
+  dliom_cloud* filtered = nullptr;
+  DLIOM_TRY(dliom_cloud_approximate_voxel_filter(matcher->ctx, scan, matcher->leaf, &filtered));
+  dliom_ndt_result res = {};
+  int st = DLIOM_OK;
+  if (!first) st = dliom_ndt_align(matcher->target, filtered, guess16, &matcher->options, nullptr, &res, nullptr);
+  dliom_ndt_target* cells = nullptr;
+  if (st == DLIOM_OK) st = dliom_ndt_target_create(matcher->ctx, filtered, &matcher->options, &cells);
+  dliom_cloud_destroy(filtered);
+  if (st != DLIOM_OK) return st;  // the matcher is as it was
+  dliom_ndt_target_destroy(matcher->target);
+  matcher->target = cells;
+  if (!first) *result = res;
   return DLIOM_OK;
 }
 

@@ -305,6 +305,53 @@ int dliom_timed_cloud_download(const dliom_timed_cloud* cloud, float* xyzt, floa
 
 }  // extern "C"
 
+namespace dliom {
+// cvtPointCloud: a timed cloud's xyz as they stand, and the largest squared norm for the cloud's bound
+__global__ __launch_bounds__(256) void timed_points_kernel(const float4* __restrict__ xyzt, int n, float* __restrict__ x,
+                                                           float* __restrict__ y, float* __restrict__ z, unsigned* max_sq) {
+  const int i = static_cast<int>(blockIdx.x) * 256 + threadIdx.x;
+  unsigned word = 0u;
+  if (i < n) {
+    const float4 p = xyzt[i];
+    x[i] = p.x;
+    y[i] = p.y;
+    z[i] = p.z;
+    word = norm_word(p.x, p.y, p.z);
+  }
+  note_kept(word, max_sq);
+}
+}  // namespace dliom
+
+extern "C" int dliom_timed_cloud_points(dliom_ctx* ctx, const dliom_timed_cloud* in, dliom_cloud** out) {
+  if (out != nullptr) *out = nullptr;
+  if (ctx == nullptr || in == nullptr || out == nullptr || in->ctx != ctx || in->n < 0 || in->n > (int64_t{1} << 30))
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  DLIOM_HIP_TRY(hipSetDevice(ctx->device));
+  if (in->n == 0) return empty_cloud(ctx, out);
+  const int n = static_cast<int>(in->n);
+  DLIOM_TRY(ctx->misc.reserve(256));
+  unsigned* const max_sq = ctx->misc.as<unsigned>();
+  const FillJob fill{max_sq, 4, 0u};
+  DLIOM_TRY(fill_multi(ctx, &fill, 1));
+  float *x, *y, *z;
+  DLIOM_TRY(alloc_device_cloud(ctx, n, out, &x, &y, &z));
+  hipLaunchKernelGGL(timed_points_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, in->d_xyzt, n, x, y, z, max_sq);
+  int st = hipGetLastError() == hipSuccess ? DLIOM_OK : DLIOM_ERR_HIP;
+  unsigned* const host = pinned_at<unsigned>(ctx, kPinReadback);
+  const GatherJob job{max_sq, 1};
+  if (st == DLIOM_OK) st = gather_and_wait(ctx, &job, 1, host);
+  float sq = 0.f;
+  if (st == DLIOM_OK) {
+    std::memcpy(&sq, host, 4);
+    st = finish_device_cloud(ctx, *out, std::sqrt(sq));  // sqrt is monotone: the max of the norms
+  }
+  if (st != DLIOM_OK) {
+    dliom_cloud_destroy(*out);
+    *out = nullptr;
+  }
+  return st;
+}
+
 // what the consumers (preprocess.hip, assemble.hip) take of an object
 namespace dliom {
 int timed_cloud_view(const dliom_timed_cloud* cloud, const dliom_ctx* ctx, int64_t* n, const float4** d_xyzt, const float** d_intensities,

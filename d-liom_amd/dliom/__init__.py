@@ -3656,3 +3656,152 @@ class Ndt:
         finally:
             if mine:
                 cloud.close()
+
+
+# ---- the approximate voxel grid and MatchByNDT over a stream of scans (include/dliom.h) ------------------------------------
+SYMBOLS += [
+    ("dliom_cloud_approximate_voxel_filter", C.c_int, [_vp, _vp, C.c_float, C.POINTER(_vp)]),
+    ("dliom_timed_cloud_points", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    ("dliom_ndt_scan_matcher_create", C.c_int, [_vp, C.POINTER(NdtOptions), C.c_float, C.POINTER(_vp)]),
+    ("dliom_ndt_scan_matcher_destroy", None, [_vp]),
+    ("dliom_ndt_scan_matcher_match", C.c_int, [_vp, _vp, _f64p, C.POINTER(NdtResult)]),
+    ("dliom_ndt_scan_matcher_has_target", C.c_int, [_vp, C.POINTER(C.c_int)]),
+]
+
+
+def approximate_voxel_filter(ctx, points, leaf):
+    """pcl::ApproximateVoxelGrid as PCL 1.8.0 runs it, on the device (dliom_cloud_approximate_voxel_filter) -> a new
+    PointCloud: the sequential loop's centroids, bit for bit and in its order"""
+    cloud, mine = _as_cloud(ctx, points)
+    try:
+        h = _vp()
+        _check(ctx._L.dliom_cloud_approximate_voxel_filter(ctx.h, cloud.h, C.c_float(leaf), C.byref(h)),
+               "dliom_cloud_approximate_voxel_filter")
+        return PointCloud(ctx, _handle=h)
+    finally:
+        if mine:
+            cloud.close()
+
+
+def timed_cloud_points(ctx, timed_cloud):
+    """cvtPointCloud: a TimedCloud's xyz as a PointCloud, copied on the device (dliom_timed_cloud_points)"""
+    h = _vp()
+    _check(ctx._L.dliom_timed_cloud_points(ctx.h, timed_cloud.h, C.byref(h)), "dliom_timed_cloud_points")
+    return PointCloud(ctx, _handle=h)
+
+
+class NdtScanMatcher:
+    """MatchByNDT as InitilizeByNDT calls it (dliom_ndt_scan_matcher): every scan is filtered once and aligned to its
+    predecessor, whose cells stay in HBM."""
+
+    def __init__(self, ctx, options=None, leaf=0.2):
+        self.ctx, self._L = ctx, ctx._L
+        self.options = options if options is not None else ndt_options()
+        h = _vp()
+        _check(self._L.dliom_ndt_scan_matcher_create(ctx.h, C.byref(self.options), C.c_float(leaf), C.byref(h)),
+               "dliom_ndt_scan_matcher_create")
+        self.h = h
+        self.num_scans = 0  # the scans taken (a failed match takes none): a count for the caller, not what match() decides by
+
+    @property
+    def has_target(self):
+        v = C.c_int()
+        _check(self._L.dliom_ndt_scan_matcher_has_target(self.h, C.byref(v)), "dliom_ndt_scan_matcher_has_target")
+        return v.value != 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_ndt_scan_matcher_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def match(self, scan, guess=None):
+        """-> None for the first scan, else the result dict of Ndt.align for (previous scan, this scan, guess)"""
+        cloud, mine = _as_cloud(self.ctx, scan)
+        try:
+            first = not self.has_target
+            g = _f64(np.eye(4) if guess is None else guess).reshape(16)
+            r = NdtResult()
+            _check(self._L.dliom_ndt_scan_matcher_match(self.h, cloud.h, None if first else _p(g, _f64p),
+                                                        None if first else C.byref(r)), "dliom_ndt_scan_matcher_match")
+            self.num_scans += 1
+            return None if first else _ndt_result(r)
+        finally:
+            if mine:
+                cloud.close()
+
+
+# ---- IMU-LiDAR initialisation (include/dliom.h "IMU-LiDAR initialisation") -------------------------------------------------
+SYMBOLS += [
+    ("dliom_imu_static_initialization", C.c_int, [C.c_int64, _f64p, _f64p, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p]),
+]
+
+
+def imu_static_initialization(acc, gyr, gravity_norm):
+    """InitializeStatic (dliom_imu_static_initialization) on n accelerometer and gyroscope samples (n, 3)
+    -> dict(R (3, 3) IMU frame to world, ba, bg, P, V)"""
+    a, g = _f64(acc).reshape(-1, 3), _f64(gyr).reshape(-1, 3)
+    if len(a) != len(g):
+        raise ValueError("one gyroscope sample an accelerometer sample")
+    R, ba, bg, P, V = np.zeros(9), np.zeros(3), np.zeros(3), np.zeros(3), np.zeros(3)
+    _check(load_library().dliom_imu_static_initialization(len(a), _p(a, _f64p), _p(g, _f64p), float(gravity_norm), _p(R, _f64p),
+                                                          _p(ba, _f64p), _p(bg, _f64p), _p(P, _f64p), _p(V, _f64p)),
+           "dliom_imu_static_initialization")
+    return {"R": R.reshape(3, 3), "ba": ba, "bg": bg, "P": P, "V": V}
+
+
+INIT_OK, INIT_NO_EXCITATION, INIT_TOO_FEW_FRAMES, INIT_GRAVITY_NORM, INIT_SINGULAR = range(5)
+INIT_MAX_FRAMES = 64
+
+
+class InitFrame(C.Structure):
+    _fields_ = [("pose", C.c_double * 7), ("has_preintegration", C.c_int), ("reserved", C.c_int), ("sum_dt", C.c_double),
+                ("delta_p", C.c_double * 3), ("delta_v", C.c_double * 3)]
+
+
+SYMBOLS += [
+    ("dliom_imu_lidar_initialization", C.c_int, [C.POINTER(InitFrame), C.c_int, _f64p, C.c_double, _f64p, _f64p, C.POINTER(C.c_int)]),
+    ("dliom_imu_lidar_align_with_world", C.c_int, [C.POINTER(InitFrame), C.c_int, _f64p, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p,
+                                                   _f64p, C.POINTER(C.c_int)]),
+]
+
+
+def _init_frames(frames):
+    """frames: (pose7, preintegration or None), the preintegration a dict with sum_dt, delta_p, delta_v (ImuIntegrator.get)"""
+    out = (InitFrame * max(len(frames), 1))()
+    for f, (pose, pre) in zip(out, frames):
+        f.pose[:] = [float(v) for v in pose]
+        f.has_preintegration = 0 if pre is None else 1
+        if pre is not None:
+            f.sum_dt = float(pre["sum_dt"])
+            f.delta_p[:] = [float(v) for v in pre["delta_p"]]
+            f.delta_v[:] = [float(v) for v in pre["delta_v"]]
+    return out
+
+
+def imu_lidar_initialization(frames, transform_lb, gravity_norm):
+    """Initializer::Initialization (dliom_imu_lidar_initialization) -> dict(outcome INIT_*, velocities (n, 3) each in its own
+    frame, gravity (3,) in the first laser frame)"""
+    n = len(frames)
+    V, g, outcome = np.zeros(3 * max(n, 1)), np.zeros(3), C.c_int(-1)
+    _check(load_library().dliom_imu_lidar_initialization(_init_frames(frames), n, _p(_f64(transform_lb), _f64p), float(gravity_norm),
+                                                         _p(V, _f64p), _p(g, _f64p), C.byref(outcome)), "dliom_imu_lidar_initialization")
+    return {"outcome": outcome.value, "velocities": V[:3 * n].reshape(n, 3), "gravity": g}
+
+
+def imu_lidar_align_with_world(frames, transform_lb, gravity_norm):
+    """AlignWithWorld (dliom_imu_lidar_align_with_world) -> dict(outcome INIT_*, excitation, P (n, 3), R (n, 3, 3), V (n, 3) in
+    the world frame, gravity_in_laser, world_rotation (3, 3))"""
+    n = len(frames)
+    P, R, V, g, Rw = np.zeros(3 * max(n, 1)), np.zeros(9 * max(n, 1)), np.zeros(3 * max(n, 1)), np.zeros(3), np.zeros(9)
+    excitation, outcome = np.zeros(1), C.c_int(-1)
+    _check(load_library().dliom_imu_lidar_align_with_world(_init_frames(frames), n, _p(_f64(transform_lb), _f64p), float(gravity_norm),
+                                                           _p(P, _f64p), _p(R, _f64p), _p(V, _f64p), _p(g, _f64p), _p(Rw, _f64p),
+                                                           _p(excitation, _f64p), C.byref(outcome)), "dliom_imu_lidar_align_with_world")
+    return {"outcome": outcome.value, "excitation": float(excitation[0]), "P": P[:3 * n].reshape(n, 3), "R": R[:9 * n].reshape(n, 3, 3),
+            "V": V[:3 * n].reshape(n, 3), "gravity_in_laser": g, "world_rotation": Rw.reshape(3, 3)}

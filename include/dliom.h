@@ -599,6 +599,19 @@ int dliom_cloud_adaptive_voxel_filter_pair(dliom_ctx* ctx, const dliom_cloud* in
                                            const dliom_adaptive_voxel_filter_options* first,
                                            const dliom_adaptive_voxel_filter_options* second, dliom_cloud** out_first,
                                            dliom_cloud** out_second);
+/* The approximate voxel grid: pcl::ApproximateVoxelGrid<PointXYZ> as PCL 1.8.0 runs it, on a device-resident cloud
+ * (LocalTrajectoryBuilder3D::MatchByNDT, local_trajectory_builder_3d.cc:969-1008, filters both of its clouds with it at
+ * 0.2 m).  THE DEFINITION, float arithmetic, every operation rounded on its own:
+ *   inv = 1.0f / leaf.  A point's voxel is (floor(x * inv), floor(y * inv), floor(z * inv)) in float, cast to int; its slot
+ *   is (ix * 7171 + iy * 3079 + iz * 4231) & 511 in wrapping 32-bit arithmetic.  The points are taken in input order into a
+ *   table of 512 slots.  A slot that holds another voxel is flushed to the output first (centroid = float sums / (float)count,
+ *   the sums taken from +0.0 in input order) and starts anew; at the end the occupied slots are flushed in slot order.
+ * *out is a new cloud that equals that loop bit for bit, in values and in order (the adapter's host class
+ * registration::ApproximateVoxelGrid is the loop itself).  The output depends on the input order, but only within a slot:
+ * the device replays the 512 slots as independent streams.  xyz only.  An empty input gives an empty cloud.
+ * DLIOM_ERR_INVALID_ARGUMENT: NULLs, a cloud of another context, leaf <= 0 or NaN, a non-finite coordinate, a floor(p * inv)
+ * outside [-2^31, 2^31) (the cast is undefined there).  One read-back a call. */
+int dliom_cloud_approximate_voxel_filter(dliom_ctx* ctx, const dliom_cloud* in, float leaf, dliom_cloud** out);
 /* The points of a cloud in input order, packed xyz (room for dliom_cloud_size points). */
 int dliom_cloud_download(const dliom_cloud* cloud, float* points_xyz);
 /* ... moved by a float pose [tx, ty, tz, qw, qx, qy, qz]: sensor::TransformPointCloud(cloud, pose) (sensor/point_cloud.cc:25-33,
@@ -1184,6 +1197,89 @@ int dliom_imu_integrator_evaluate(const dliom_imu_integrator* integrator, const 
                                   const double state_j[16], const double gravity[3], double residuals[15]);
 int dliom_imu_integrator_predict(const dliom_imu_integrator* integrator, const double state_i[16],
                                  const double gravity[3], double state_j[16]);
+
+/* ---- IMU-LiDAR initialisation (host) ----------------------------------------------------------------
+ * The state the steady-state path starts from.  Double arithmetic, every operation rounded on its own, in the order
+ * written, parentheses first and otherwise left to right; u . v = (u0*v0 + u1*v1) + u2*v2; u x v = (u1*v2 - u2*v1,
+ * u2*v0 - u0*v2, u0*v1 - u1*v0); n(v) = v / sqrt(v . v), component by component.
+ *
+ * FROM TWO VECTORS (Eigen's Quaternion::FromTwoVectors, general branch, operation for operation): v0 = n(a), v1 = n(b),
+ * c = v1 . v0.  For c >= -1 + 1e-12: axis = v0 x v1, s = sqrt((1 + c) * 2), invs = 1 / s, q = (w = s * 0.5, axis * invs).
+ * NEARLY OPPOSITE (c < -1 + 1e-12), PARITY UNPINNED AGAINST EIGEN, which takes an SVD there: q = (0, n(v0 x e_k)), half
+ * a turn, e_k the coordinate axis on which |v0| is least (ties: the lowest k).
+ * The rotation matrix of q is Eigen's toRotationMatrix: tx = 2*x, ty = 2*y, tz = 2*z, twx = tx*w, twy = ty*w, twz = tz*w,
+ * txx = tx*x, txy = ty*x, txz = tz*x, tyy = ty*y, tyz = tz*y, tzz = tz*z; rows (1 - (tyy + tzz), txy - twz, txz + twy),
+ * (txy + twz, 1 - (txx + tzz), tyz - twx), (txz - twy, tyz + twx, 1 - (txx + tyy)).
+ *
+ * dliom_imu_static_initialization: LocalTrajectoryBuilder3D::InitializeStatic (local_trajectory_builder_3d.cc:203-229) for
+ * a platform at rest.  acc and gyr hold n samples (x, y, z each).  The sums run from +0.0 in sample order; acc_mean and
+ * gyro_mean are the sums / (double)n.  g_vec = (0, 0, -gravity_norm).  R = the matrix of FROM TWO VECTORS (acc_mean,
+ * -g_vec): IMU frame to world, row-major in rotation9.  ba = R^T g_vec + acc_mean, a component
+ * ((R0a*g0 + R1a*g1) + R2a*g2) + acc_mean_a; bg = gyro_mean; position = velocity = 0.
+ * DLIOM_ERR_INVALID_ARGUMENT: NULLs, n <= 0, a non-finite sample, a non-finite or non-positive gravity_norm, an
+ * acc_mean without a direction. */
+int dliom_imu_static_initialization(int64_t n, const double* acc, const double* gyr, double gravity_norm, double rotation9[9],
+                                    double ba[3], double bg[3], double position[3], double velocity[3]);
+/* dliom_imu_lidar_initialization: Initializer::Initialization (initialization/imu_lidar_initializer.cc:50-229) on N frames
+ * (F + 1 of them in the caller's terms).  A frame is a pose T_li of the laser in the first laser frame
+ * [tx, ty, tz, qw, qx, qy, qz] and the preintegration that was running when it was stored (sum_dt, delta_p, delta_v of
+ * dliom_imu_integrator_get); frame 0 may carry none, and its own is never read.  R_i is the rotation matrix of the frame's
+ * quaternion as it stands (FROM TWO VECTORS above), T_i its translation, tlb the translation of transform_lb, whose
+ * rotation the reference reads and does not use.  A pair is (i, j = i + 1) with a preintegration on j; pairs without are
+ * skipped.  dt = sum_dt of j.  THE SOLVER is the library's own (Gaussian elimination with partial pivoting by rows, back
+ * substitution left to right), PARITY UNPINNED AGAINST EIGEN's pivoted LDLT; it is pinned against numpy.linalg.solve within
+ * 64 * cond(A) * 2^-52 * |x| a solve (tests/test_imu_lidar_init_host.py).
+ *   ApproximateGravity (:50-124).  N < 7: DLIOM_INIT_TOO_FEW_FRAMES.  Unknowns: the frames' velocities in their own frames
+ *   (3 N), then g (3).  A pair's 6 x 9 block M over (V_i, V_j, g) and its right-hand side r:
+ *     rows 0-2: (-dt I | 0 | R_i^T * (dt*dt/2)),   r = ((delta_p + (R_i^T R_j) tlb) - tlb) - R_i^T (T_j - T_i)
+ *     rows 3-5: (-I | R_i^T R_j | R_i^T * dt),     r = delta_v
+ *   M^T M and M^T r (sums over the six rows in row order) are added at the columns of V_i, V_j and g.  Then A and b are
+ *   multiplied by 1000 and solved; g = the last three unknowns.  | |g| - gravity_norm | < 1.0, else DLIOM_INIT_GRAVITY_NORM.
+ *   TangentBasis (:36-48): a = n(g0); tmp = (0, 0, 1), or (1, 0, 0) if a == (0, 0, 1) exactly; b = n(tmp - a * (a . tmp)),
+ *   c = a x b.
+ *   RefineGravity (:126-211).  g0 = n(g) * gravity_norm.  Unknowns: the velocities (3 N), then (d0, d1).  A and b are zeroed
+ *   ONCE, before four passes, and NOT between them: every pass adds its blocks to the already scaled system of the pass
+ *   before.  That is what the reference's binary does.  A pass: (lx, ly) = TangentBasis(g0); a pair's 6 x 8 block with
+ *   L = [lx ly]:
+ *     rows 0-2: (-dt I | 0 | (R_i^T L) * (dt*dt/2)),  r = (((delta_p + (R_i^T R_j) tlb) - tlb) - (R_i^T g0) * (dt*dt/2)) - R_i^T (T_j - T_i)
+ *     rows 3-5: (-I | R_i^T R_j | (R_i^T L) * dt),    r = delta_v - (R_i^T g0) * dt
+ *   added as above; A and b times 1000; solved; g0 = n(g0 + (lx * d0 + ly * d1)) * gravity_norm.
+ *   After the four passes gravity = g0 and velocities = the last solve's first 3 N unknowns (each in its own frame);
+ *   | |g| - gravity_norm | < 0.2, else DLIOM_INIT_GRAVITY_NORM.  A system without a pivot: DLIOM_INIT_SINGULAR.
+ * *outcome is a DLIOM_INIT_* value; the call returns DLIOM_OK whenever its arguments were well formed.
+ *
+ * dliom_imu_lidar_align_with_world: LocalTrajectoryBuilder3D::AlignWithWorld (local_trajectory_builder_3d.cc:1010-1086), in
+ * its order, F = num_frames - 1:
+ *   1. Excitation.  Over the F later frames (those without a preintegration skipped): t = delta_v / sum_dt; sum from ZERO
+ *      (the reference leaves sum_g uninitialised); mean = sum * 1.0 / F; var = the sum of (t - mean) . (t - mean);
+ *      *excitation = sqrt(var / F).  Below 0.25: DLIOM_INIT_NO_EXCITATION.
+ *   2. The call above; its outcome if it is not DLIOM_INIT_OK.  gravity_in_laser is its g.
+ *   3. Per frame: T_li * transform_lb: P_i = R_li t_lb + T_i; R_i = the matrix of (q_li q_lb) / |q_li q_lb| (Hamilton
+ *      product, each component's four terms left to right); V_i = R_i V_i.
+ *   4. g_base = -g; world_rotation9 = the matrix of FROM TWO VECTORS (n(g_base), (0, 0, -1)); P_i, R_i and V_i are turned by
+ *      it from the left.
+ * positions and velocities hold 3, rotations 9 doubles a frame (row-major); they are written only under DLIOM_INIT_OK.
+ * DLIOM_ERR_INVALID_ARGUMENT for both calls: NULLs, fewer than 1 (align: 2) or more than DLIOM_INIT_MAX_FRAMES frames,
+ * non-finite input, a preintegration with sum_dt <= 0, a non-positive gravity_norm. */
+#define DLIOM_INIT_MAX_FRAMES 64
+enum {
+  DLIOM_INIT_OK = 0,
+  DLIOM_INIT_NO_EXCITATION = 1,
+  DLIOM_INIT_TOO_FEW_FRAMES = 2,
+  DLIOM_INIT_GRAVITY_NORM = 3,
+  DLIOM_INIT_SINGULAR = 4
+};
+typedef struct dliom_init_frame {
+  double pose[7];
+  int has_preintegration;
+  int reserved;              /* 0 */
+  double sum_dt, delta_p[3], delta_v[3];
+} dliom_init_frame;
+int dliom_imu_lidar_initialization(const dliom_init_frame* frames, int num_frames, const double transform_lb[7],
+                                   double gravity_norm, double* velocities, double gravity[3], int* outcome);
+int dliom_imu_lidar_align_with_world(const dliom_init_frame* frames, int num_frames, const double transform_lb[7],
+                                     double gravity_norm, double* positions, double* rotations, double* velocities,
+                                     double gravity_in_laser[3], double world_rotation9[9], double* excitation, int* outcome);
 
 /* ---- LocalTrajectoryBuilder3D::WindowOptimize: IMU-preintegration cost in the optimisation ----------
  * (host; PARITY UNPINNED: GTSAM 4.0.2 is not in the reference tree and the reference has no
@@ -2113,6 +2209,10 @@ int dliom_timed_cloud_stamp(dliom_ctx* ctx, const dliom_timed_cloud* in, double 
 int dliom_timed_clouds_merge(dliom_ctx* ctx, const dliom_timed_cloud* primary, const dliom_timed_cloud* primary_for_times,
                              int64_t primary_time, const dliom_timed_cloud* secondary, int64_t secondary_time,
                              dliom_timed_cloud** out);
+/* cvtPointCloud (local_trajectory_builder_3d.cc): the xyz of a device object -- a decoded message, a stamped cloud or a
+ * merge's result -- as a cloud of the context, in the object's order: a device copy, no de-skew, no filter.  The times and
+ * the other channels are left behind.  One read-back (the cloud's bound). */
+int dliom_timed_cloud_points(dliom_ctx* ctx, const dliom_timed_cloud* in, dliom_cloud** out);
 /* dliom_range_accumulator_add with ranges_xyzt, origin_index and n taken from a device object -- a decoded message
  * (origin index 0 throughout) or a merge's result; `origins` stays the caller's table.  Results, read-back count and
  * refusals are those of the host-input call. */
@@ -2449,6 +2549,22 @@ int dliom_ndt_evaluate(dliom_ndt_target* target, const dliom_cloud* source, cons
  * context.  aligned (may be NULL): the final x'_i as a cloud of the context. */
 int dliom_ndt_align(dliom_ndt_target* target, const dliom_cloud* source, const double* guess16, const dliom_ndt_options* options,
                     dliom_nn_index* fitness_index, dliom_ndt_result* result, dliom_cloud** aligned);
+/* LocalTrajectoryBuilder3D::MatchByNDT (local_trajectory_builder_3d.cc:969-1008) as InitilizeByNDT (:231-330, the
+ * reference's spelling) calls it: every scan is aligned to its predecessor, so the matcher keeps the previous scan's cells
+ * on the device.  The first match only filters the scan (the approximate voxel grid above, at `leaf`: the reference's
+ * 0.2 m), builds its cells and keeps them; guess16 and result may be NULL and nothing is written to result.  Every later
+ * match filters the new scan ONCE, aligns it to the kept cells from guess16 as dliom_ndt_align does without a fitness
+ * index, builds the new scan's cells and makes them the kept ones.  *result is, bit for bit, what the composition filter
+ * (previous) -> dliom_ndt_target_create, filter (scan) -> dliom_ndt_align gives for the two raw scans and the guess.  A call
+ * that fails leaves the matcher as it was.  The scan may be destroyed afterwards.  One thread at a time per matcher, like
+ * its context; destroy the matcher before the context. */
+typedef struct dliom_ndt_scan_matcher dliom_ndt_scan_matcher;
+int dliom_ndt_scan_matcher_create(dliom_ctx* ctx, const dliom_ndt_options* options, float leaf, dliom_ndt_scan_matcher** out);
+void dliom_ndt_scan_matcher_destroy(dliom_ndt_scan_matcher* matcher);
+int dliom_ndt_scan_matcher_match(dliom_ndt_scan_matcher* matcher, const dliom_cloud* scan, const double* guess16,
+                                 dliom_ndt_result* result);
+/* *has_target: 1 once a match has succeeded (the matcher holds a scan's cells and the next match writes a result), else 0. */
+int dliom_ndt_scan_matcher_has_target(const dliom_ndt_scan_matcher* matcher, int* has_target);
 
 /* Kernel timing (HIP events on the context's stream). */
 enum {
