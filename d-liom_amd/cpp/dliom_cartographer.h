@@ -3760,6 +3760,145 @@ inline std::string FormatGroundTruthLine(int64_t stamp_from, int64_t stamp_to, d
   return line + text;
 }
 
+// Many alignments in one call (dliom_icp_align_batch): the pairs of the tool's loop over a trajectory's constraints.
+struct AlignmentPair {
+  const sensor::PointCloud* source = nullptr;
+  const sensor::PointCloud* target = nullptr;
+  Matrix4f guess;
+};
+// What IterativeClosestPoint with `icp_options` gives pair by pair (setInputSource, setInputTarget, align(guess), result()),
+// bit for bit.  ONE index is built per distinct target pointer and one cloud uploaded per distinct source pointer, however
+// many pairs name them.  limits: NULL = the defaults.  aligned (may be null): every pair's source under its final
+// transformation.  stats (may be null): the call's.
+inline std::vector<dliom_icp_result> AlignPairs(Context* context, const dliom_icp_options& icp_options,
+                                                const std::vector<AlignmentPair>& pairs, const dliom_icp_batch_limits* limits = nullptr,
+                                                std::vector<sensor::PointCloud>* aligned = nullptr,
+                                                dliom_icp_batch_stats* stats = nullptr) {
+  struct Owned {  // destroyed on every way out, the indices before nothing else depends on them
+    std::map<const sensor::PointCloud*, dliom_nn_index*> indices;
+    std::map<const sensor::PointCloud*, dliom_cloud*> sources;
+    std::vector<dliom_cloud*> outputs;
+    ~Owned() {
+      for (auto& e : indices) dliom_nn_index_destroy(e.second);
+      for (auto& e : sources) dliom_cloud_destroy(e.second);
+      for (dliom_cloud* c : outputs) dliom_cloud_destroy(c);
+    }
+  } owned;
+  const auto upload = [context](const sensor::PointCloud* cloud) {
+    dliom_cloud* out = nullptr;
+    Check(dliom_cloud_create(context->get(), cloud->empty() ? nullptr : &(*cloud)[0].x, static_cast<int64_t>(cloud->size()), &out),
+          "dliom_cloud_create");
+    return out;
+  };
+  std::vector<dliom_icp_pair> table(pairs.size());
+  for (size_t i = 0; i < pairs.size(); ++i) {
+    const AlignmentPair& p = pairs[i];
+    if (p.source == nullptr || p.target == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "AlignPairs: a pair without a cloud");
+    if (owned.indices.find(p.target) == owned.indices.end()) {
+      dliom_cloud* target = upload(p.target);
+      dliom_nn_index* index = nullptr;
+      const int status = dliom_nn_index_create(context->get(), target, nullptr, &index);
+      dliom_cloud_destroy(target);
+      Check(status, "dliom_nn_index_create");
+      owned.indices[p.target] = index;
+    }
+    if (owned.sources.find(p.source) == owned.sources.end()) owned.sources[p.source] = upload(p.source);
+    table[i].index = owned.indices[p.target];
+    table[i].source = owned.sources[p.source];
+    for (int k = 0; k < 16; ++k) table[i].guess[k] = static_cast<double>(p.guess.m[k]);
+  }
+  std::vector<dliom_icp_result> results(pairs.size());
+  if (aligned != nullptr) owned.outputs.assign(pairs.size(), nullptr);
+  Check(dliom_icp_align_batch(context->get(), table.data(), static_cast<int>(table.size()), &icp_options, limits, results.data(),
+                              aligned != nullptr ? owned.outputs.data() : nullptr, stats),
+        "dliom_icp_align_batch");
+  if (aligned != nullptr) {
+    aligned->assign(pairs.size(), sensor::PointCloud());
+    for (size_t i = 0; i < pairs.size(); ++i) {
+      (*aligned)[i].resize(pairs[i].source->size());
+      if (!(*aligned)[i].empty()) Check(dliom_cloud_download(owned.outputs[i], &(*aligned)[i][0].x), "dliom_cloud_download");
+    }
+  }
+  return results;
+}
+
+// gen_ground_truth_by_ndt_match.cc:182-185: gt = (poses[to].inverse() * poses[from]).cast<float>() as a 4x4, the rotation by
+// toRotationMatrix's formula in float.
+inline Matrix4f GroundTruthGuess(const transform::Rigid3d& to, const transform::Rigid3d& from) {
+  namespace ff = mapping::optimization::fixed_frame;
+  const transform::Rigid3f ig(ff::Multiply(ff::Inverse(to), from));
+  const float w = ig.wxyz[0], x = ig.wxyz[1], y = ig.wxyz[2], z = ig.wxyz[3];
+  const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
+              tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  Matrix4f gt;
+  const float R[9] = {1.f - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.f - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1.f - (txx + tyy)};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) gt(r, c) = R[3 * r + c];
+    gt(r, 3) = ig.t[r];
+  }
+  return gt;
+}
+// The line's last field (:202, :259): the norm of the translation of gt^-1 * trans.  The RIGID inverse in float, in this
+// order: d = t_trans - t_gt per axis, v_c = (R_gt[0][c] * d_0 + R_gt[1][c] * d_1) + R_gt[2][c] * d_2, sqrt((v_0*v_0 + v_1*v_1) +
+// v_2*v_2).  UNPINNED against Eigen's general 4x4 inverse, which the tool calls: the two agree to float rounding, not in bits.
+inline float GroundTruthDifferenceNorm(const Matrix4f& gt, const Matrix4f& trans) {
+  const float d[3] = {trans(0, 3) - gt(0, 3), trans(1, 3) - gt(1, 3), trans(2, 3) - gt(2, 3)};
+  float v[3];
+  for (int c = 0; c < 3; ++c) v[c] = (gt(0, c) * d[0] + gt(1, c) * d[1]) + gt(2, c) * d[2];
+  return std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+}
+
+// The tool's loop (gen_ground_truth_by_ndt_match.cc:151-261) for --method icp over the constraints whose `from` nodes are
+// given (the caller has dropped the intra-submap ones, :153): the text of the tool's file for them, in order.
+// poses, timestamps_ns: one a node; stamps_in_bag (sorted) and clouds: one a scan of the bag.  A `from` node without a
+// revisit node (FindRevisitNode: -1) is skipped; so is a pair with a stamp past the bag's last (:173-180) and a pair whose
+// alignment does not converge (:205).  Alignments run batch_size pairs a call, with the GroundTruthIcp preset; the text is
+// byte-equal to the loop through IterativeClosestPoint::GroundTruthIcp one pair at a time, whatever batch_size is.
+inline std::string GenerateGroundTruthIcp(Context* context, const std::vector<transform::Rigid3d>& poses,
+                                          const std::vector<int64_t>& timestamps_ns, const std::vector<int64_t>& stamps_in_bag,
+                                          const std::vector<sensor::PointCloud>& clouds, const std::vector<size_t>& from_nodes,
+                                          size_t batch_size) {
+  if (batch_size < 1 || clouds.size() != stamps_in_bag.size() || timestamps_ns.size() != poses.size())
+    Check(DLIOM_ERR_INVALID_ARGUMENT, "GenerateGroundTruthIcp");
+  struct Wanted {
+    int64_t stamp_from, stamp_to;
+    Matrix4f gt;
+  };
+  std::vector<Wanted> wanted;
+  std::vector<AlignmentPair> pairs;
+  for (const size_t from : from_nodes) {
+    const int to = FindRevisitNode(poses, timestamps_ns, from);
+    if (to < 0) continue;
+    const int64_t stamp_to = timestamps_ns[static_cast<size_t>(to)], stamp_from = timestamps_ns[from];
+    const auto it_to = std::lower_bound(stamps_in_bag.begin(), stamps_in_bag.end(), stamp_to);
+    const auto it_from = std::lower_bound(stamps_in_bag.begin(), stamps_in_bag.end(), stamp_from);
+    if (it_to == stamps_in_bag.end() || it_from == stamps_in_bag.end()) continue;
+    Wanted w{stamp_from, stamp_to, GroundTruthGuess(poses[static_cast<size_t>(to)], poses[from])};
+    AlignmentPair p;
+    p.source = &clouds[static_cast<size_t>(it_from - stamps_in_bag.begin())];
+    p.target = &clouds[static_cast<size_t>(it_to - stamps_in_bag.begin())];
+    p.guess = w.gt;
+    wanted.push_back(w);
+    pairs.push_back(p);
+  }
+  const dliom_icp_options options = IterativeClosestPoint::GroundTruthIcp(context)->options();
+  std::string text;
+  for (size_t first = 0; first < pairs.size(); first += batch_size) {
+    const size_t end = std::min(pairs.size(), first + batch_size);
+    const std::vector<AlignmentPair> group(pairs.begin() + static_cast<std::ptrdiff_t>(first), pairs.begin() + static_cast<std::ptrdiff_t>(end));
+    const std::vector<dliom_icp_result> results = AlignPairs(context, options, group);
+    for (size_t i = first; i < end; ++i) {
+      const dliom_icp_result& r = results[i - first];
+      if (r.converged == 0) continue;
+      Matrix4f trans;
+      for (int k = 0; k < 16; ++k) trans.m[k] = static_cast<float>(r.transform[k]);
+      text += FormatGroundTruthLine(wanted[i].stamp_from, wanted[i].stamp_to, r.fitness_score, trans,
+                                    GroundTruthDifferenceNorm(wanted[i].gt, trans));
+    }
+  }
+  return text;
+}
+
 // pcl::ApproximateVoxelGrid<PointXYZ> as PCL 1.8.0 runs it (MatchByNDT filters both clouds with it at 0.2 m), on the HOST:
 // the sequential loop of the definition in dliom.h ("the approximate voxel grid"), which
 // dliom_cloud_approximate_voxel_filter replays on the device, bit for bit; this class is the cross-check of that call

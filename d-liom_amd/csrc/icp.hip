@@ -19,62 +19,18 @@
 #include <vector>
 
 #include "device_common.h"
-#include "nn_index.h"
-#include "tree_reduce.h"
+#include "icp_internal.h"
 
 namespace dliom {
 namespace {
 
 constexpr int kThreads = kTreeThreads;
-constexpr int kSums = 16;  // Sp (3), Sq (3), Spq (9, row-major), Sd
-
-struct IcpLeaves {
-  const float *px, *py, *pz;
-  const int* j;
-  const float* d2;
-  const float4* by_index;
-  int n;
-  __device__ __forceinline__ void leaf(int i, double v[kSums], int* count) const {
-    const bool has = i < n && j[i] >= 0;
-    if (has) {
-      const double p[3] = {px[i], py[i], pz[i]};
-      const float4 t = by_index[j[i]];
-      const double q[3] = {t.x, t.y, t.z};
-      for (int a = 0; a < 3; ++a) {
-        v[a] = p[a];
-        v[3 + a] = q[a];
-        for (int b = 0; b < 3; ++b) v[6 + 3 * a + b] = p[a] * q[b];
-      }
-      v[15] = static_cast<double>(d2[i]);
-    } else {
-      for (int k = 0; k < kSums; ++k) v[k] = 0.0;
-    }
-    *count = has ? 1 : 0;
-  }
-};
-
-struct IcpReadback {  // kPinIcpSums
-  double sums[kSums];
-  long long n;
-  int counters[kNnCounterWords];
-  unsigned max_sq, pad;
-};
 static_assert(sizeof(IcpReadback) <= kPinIcpSums.bytes, "the read-back fits its region");
 
-// partials: room for P2 >= P entries, P2 a power of two
 __global__ __launch_bounds__(kThreads) void icp_finish_kernel(double* partials, const int* __restrict__ counts, int P, int P2,
                                                               int* counters, const unsigned* max_sq, IcpReadback* out,
                                                               unsigned* done_word, unsigned done_seq) {
-  tree_finish<kSums>(partials, P, P2);
-  if (threadIdx.x < kSums) out->sums[threadIdx.x] = partials[threadIdx.x];
-  if (threadIdx.x == 0) {
-    long long n = 0;
-    for (int b = 0; b < P; ++b) n += counts[b];
-    out->n = n;
-    for (int k = 0; k < kNnCounterWords; ++k) out->counters[k] = counters[k];
-    counters[kNnListCount] = 0;  // the next search's list starts empty
-    out->max_sq = max_sq != nullptr ? *max_sq : 0u;
-  }
+  icp_finish_body(partials, counts, P, P2, counters, max_sq, out);
   __threadfence_system();
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -89,8 +45,11 @@ __global__ __launch_bounds__(kThreads) void icp_max_norm_kernel(const float* __r
   note_kept(i < n ? norm_word(x[i], y[i], z[i]) : 0u, max_sq);
 }
 
-// ---- the solve (dliom.h, Solve): IEEE double + - * / sqrt, a fixed count
-void icp_solve(const double S[kSums], long long n, double R[9], double t[3]) {
+}  // namespace
+
+// ---- the solve (dliom.h, Solve): IEEE double + - * / sqrt, a fixed count.  (These, the checks and icp_iterate are
+// icp_internal.h's: icp_batch.hip runs the same ones per pair.)
+void icp_solve(const double S[kIcpSums], long long n, double R[9], double t[3]) {
   const double dn = static_cast<double>(n);
   double cp[3], cq[3], H[3][3];
   for (int a = 0; a < 3; ++a) {
@@ -206,6 +165,52 @@ bool icp_guess_ok(const double* g) {
   return det > 0.0;
 }
 
+// dliom.h, Iteration and Convergence: iteration k of an alignment from the sums of its search.  false: fewer than
+// min_correspondences (the loop ends, T and the points stay).  Else T and the result are brought up to date, (R, t) is
+// what the points are to be moved by, and *ends says whether a criterion of Convergence held.
+bool icp_iterate(const dliom_icp_options* options, const double sums[kIcpSums], long long n, int k, double* previous_mse,
+                 dliom_icp_result* res, double R[9], double t[3], bool* ends) {
+  res->correspondences = static_cast<int>(n);
+  if (n < options->min_correspondences) {
+    res->converged = 0;
+    res->reason = DLIOM_ICP_NO_CORRESPONDENCES;
+    return false;
+  }
+  icp_solve(sums, n, R, t);
+  icp_compose(R, t, res->transform);
+  const double mse = sums[15] / static_cast<double>(n);
+  res->mse = mse;
+  res->iterations = k;
+  const double cosine = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+  const double translation_sq = (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
+  const double change = std::fabs(mse - *previous_mse);
+  int reason = DLIOM_ICP_NOT_CONVERGED;
+  if (k >= options->maximum_iterations)
+    reason = DLIOM_ICP_ITERATIONS;
+  else if (cosine >= 1.0 - options->rotation_epsilon && translation_sq <= options->transformation_epsilon)
+    reason = DLIOM_ICP_TRANSFORM;
+  else if (change < options->euclidean_fitness_epsilon)
+    reason = DLIOM_ICP_ABS_MSE;
+  else if (change / *previous_mse < options->relative_mse_epsilon)
+    reason = DLIOM_ICP_REL_MSE;
+  *previous_mse = mse;
+  *ends = reason != DLIOM_ICP_NOT_CONVERGED;
+  if (*ends) {
+    res->converged = 1;
+    res->reason = reason;
+  }
+  return true;
+}
+
+size_t icp_work_bytes(int64_t n) {
+  int P = 1, P2 = 1;
+  tree_geometry(static_cast<int>(n), &P, &P2);
+  const size_t per = align256(4 * static_cast<size_t>(std::max<int64_t>(n, 1)));
+  return 8 * per + align256(static_cast<size_t>(P2) * kIcpSums * sizeof(double)) + align256(4 * static_cast<size_t>(P2));
+}
+
+namespace {
+
 // The device arrays of one alignment or step, carved from the index's scratch
 struct IcpWork {
   dliom_nn_index* index = nullptr;
@@ -239,9 +244,9 @@ int icp_carve(dliom_nn_index* index, int n, IcpWork* w) {
   w->n = n;
   tree_geometry(n, &w->P, &w->P2);
   const size_t per = align256(4 * static_cast<size_t>(std::max(n, 1)));
-  const size_t partial_bytes = align256(static_cast<size_t>(w->P2) * kSums * sizeof(double));
+  const size_t partial_bytes = align256(static_cast<size_t>(w->P2) * kIcpSums * sizeof(double));
   DevBuf* scratch = nn_scratch(index);
-  DLIOM_TRY(scratch->reserve(256 + 8 * per + partial_bytes + align256(4 * static_cast<size_t>(w->P2))));
+  DLIOM_TRY(scratch->reserve(256 + icp_work_bytes(n)));
   char* const base = scratch->as<char>();
   w->counters = reinterpret_cast<int*>(base);
   w->max_sq = reinterpret_cast<unsigned*>(base + 64);
@@ -271,7 +276,7 @@ int icp_search_and_sum(IcpWork* w, double max_d2, int search, IcpReadback* out) 
   DLIOM_TRY(w->mark());
   const NnGridView g = nn_view(w->index);
   const IcpLeaves L{w->search.px, w->search.py, w->search.pz, w->search.j, w->search.d2, g.by_index, w->n};
-  hipLaunchKernelGGL((tree_reduce_kernel<kSums, IcpLeaves>), dim3(static_cast<unsigned>(w->P)), dim3(kThreads), 0, ctx->stream, L, w->partials, w->counts);
+  hipLaunchKernelGGL((tree_reduce_kernel<kIcpSums, IcpLeaves>), dim3(static_cast<unsigned>(w->P)), dim3(kThreads), 0, ctx->stream, L, w->partials, w->counts);
   DLIOM_HIP_TRY(hipGetLastError());
   IcpReadback* const host = pinned_at<IcpReadback>(ctx, kPinIcpSums);
   const unsigned seq = next_done_seq(ctx);
@@ -344,45 +349,21 @@ int dliom_icp_align(dliom_nn_index* index, const dliom_cloud* source, const doub
   for (int k = 1;; ++k) {
     DLIOM_TRY(icp_search_and_sum(&w, max_d2, options->search, &rb));
     ++res.read_backs;
-    res.correspondences = static_cast<int>(rb.n);
-    if (rb.n < options->min_correspondences) {
-      res.converged = 0;
-      res.reason = DLIOM_ICP_NO_CORRESPONDENCES;
+    const auto solve_from = std::chrono::steady_clock::now();
+    double R[9], t[3];
+    bool ends = false;
+    if (!icp_iterate(options, rb.sums, rb.n, k, &previous_mse, &res, R, t, &ends)) {
       if (w.timed) {  // keeps the events in fives
         DLIOM_TRY(w.mark());
         DLIOM_TRY(w.mark());
       }
       break;
     }
-    const auto solve_from = std::chrono::steady_clock::now();
-    double R[9], t[3];
-    icp_solve(rb.sums, rb.n, R, t);
-    icp_compose(R, t, res.transform);
-    const double mse = rb.sums[15] / static_cast<double>(rb.n);
-    res.mse = mse;
-    res.iterations = k;
-    const double cosine = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-    const double translation_sq = (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
-    const double change = std::fabs(mse - previous_mse);
-    int reason = DLIOM_ICP_NOT_CONVERGED;
-    if (k >= options->maximum_iterations)
-      reason = DLIOM_ICP_ITERATIONS;
-    else if (cosine >= 1.0 - options->rotation_epsilon && translation_sq <= options->transformation_epsilon)
-      reason = DLIOM_ICP_TRANSFORM;
-    else if (change < options->euclidean_fitness_epsilon)
-      reason = DLIOM_ICP_ABS_MSE;
-    else if (change / previous_mse < options->relative_mse_epsilon)
-      reason = DLIOM_ICP_REL_MSE;
-    previous_mse = mse;
     w.solve_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - solve_from).count();
     DLIOM_TRY(w.mark());
     DLIOM_TRY(nn_transform_enqueue(ctx, w.px, w.py, w.pz, n, rigid_of(R, t), w.px, w.py, w.pz));
     DLIOM_TRY(w.mark());
-    if (reason != DLIOM_ICP_NOT_CONVERGED) {
-      res.converged = 1;
-      res.reason = reason;
-      break;
-    }
+    if (ends) break;
   }
   // the fitness score: one more search without a bound (and the aligned cloud's norm bound in the same read-back)
   const size_t loop_events = w.events.size();

@@ -130,6 +130,9 @@ struct dliom_ctx {
   // the batched loop-closure calls (dliom_fast_csm_match_batch, dliom_csm3d_match_batch): device scratch and a
   // page-locked block of their own, reserved by the first batch that needs them (contexts that never batch hold neither)
   dliom::DevBuf batch;
+  // a batched ICP alignment (icp_batch.hip): the descriptor table and every pair's arrays of the chunk in flight; the
+  // scratch belongs to the call, not to an index, since pairs share indices.  Reserved by the first such call
+  dliom::DevBuf icp_batch;
   // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
   dliom::DevBuf xray_leaves, xray_cells;
   // the submap image features (surf.hip): what is sized by the image and the candidates; what is sized by the key points

@@ -15,6 +15,10 @@
 //                      integer atomicMin, whose result no order of arrival can change
 //   nn_resolve_kernel  a listed query's key -> (j, d2) under the distance bound
 //   nn_transform_kernel  p = (float)(R p + t) in double
+// The shell walk, the scan, the resolve and the transform are each ONE __device__ body over (view, search, bound,
+// workgroup index).  nn_*_kernel runs it for the one search of its arguments; nn_*_batch_kernel for the searches of a table
+// in HBM (nn_index.h NnBatchItem), with the pair as a grid dimension.  What is proven of a body -- the stop rule, the tie
+// rule -- holds for both.
 //
 // Every loop's bound is known before it starts: the shells by DLIOM_NN_MAX_SHELLS, the rows of a shell by its width, a
 // row's points by the index's size; the brute-force kernel by the index's size.  No kernel waits on another workgroup.
@@ -187,8 +191,8 @@ __device__ __forceinline__ void write_result(const NnSearch& s, int i, const Bes
 // rounding cannot go below that float.  So every unseen target's COMPUTED d2 is above the threshold: under (b) it is
 // strictly worse than the best seen one (no tie to lose), under (c) it is beyond the correspondence distance like every
 // other unseen one, and the best seen target decides.
-__global__ __launch_bounds__(kThreads) void nn_shell_kernel(NnGridView g, NnSearch s, double max_d2) {
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
+__device__ __forceinline__ void nn_shell_body(const NnGridView& g, const NnSearch& s, double max_d2, int block) {
+  const int i = block * kThreads + threadIdx.x;
   const int lane = threadIdx.x & 63;
   bool searched = false, settled = false, non_finite = false;
   if (i < s.n) {
@@ -252,14 +256,19 @@ __global__ __launch_bounds__(kThreads) void nn_shell_kernel(NnGridView g, NnSear
   }
 }
 
+__global__ __launch_bounds__(kThreads) void nn_shell_kernel(NnGridView g, NnSearch s, double max_d2) {
+  nn_shell_body(g, s, max_d2, static_cast<int>(blockIdx.x));
+}
+
 // listed: the queries list[0 .. counters[kNnListCount]); else every query (keys preset to ~0).  Workgroup (x, y) takes
-// the tiles x, x + gridDim.x, ... of 256 queries against the points [y * segment, (y + 1) * segment): both loops' bounds are
+// the tiles x, x + blocks, ... of 256 queries against the points [y * segment, (y + 1) * segment): both loops' bounds are
 // the same for the whole workgroup and known on entry.  key = d2's bits << 32 | j orders like (d2, j): d2 >= +0.
-__global__ __launch_bounds__(kThreads) void nn_brute_kernel(NnGridView g, NnSearch s, bool listed, int segment) {
+__device__ __forceinline__ void nn_brute_body(const NnGridView& g, const NnSearch& s, bool listed, int segment, int block,
+                                              int blocks, int segment_index) {
   __shared__ float4 tile[kTile];
   const int total = listed ? s.counters[kNnListCount] : s.n;
-  const int first = static_cast<int>(blockIdx.y) * segment, last = min(first + segment, g.n_finite);
-  for (int q0 = static_cast<int>(blockIdx.x) * kThreads; q0 < total; q0 += static_cast<int>(gridDim.x) * kThreads) {
+  const int first = segment_index * segment, last = min(first + segment, g.n_finite);
+  for (int q0 = block * kThreads; q0 < total; q0 += blocks * kThreads) {
     const int k = q0 + threadIdx.x;
     const int i = k < total ? (listed ? s.list[k] : k) : -1;
     float px = 0.f, py = 0.f, pz = 0.f;
@@ -286,10 +295,14 @@ __global__ __launch_bounds__(kThreads) void nn_brute_kernel(NnGridView g, NnSear
   }
 }
 
-__global__ __launch_bounds__(kThreads) void nn_resolve_kernel(NnSearch s, double max_d2, bool listed) {
+__global__ __launch_bounds__(kThreads) void nn_brute_kernel(NnGridView g, NnSearch s, bool listed, int segment) {
+  nn_brute_body(g, s, listed, segment, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), static_cast<int>(blockIdx.y));
+}
+
+__device__ __forceinline__ void nn_resolve_body(const NnSearch& s, double max_d2, bool listed, int block) {
   const int total = listed ? s.counters[kNnListCount] : s.n;
-  const int k = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  if (static_cast<int>(blockIdx.x) * kThreads >= total) return;  // the whole workgroup
+  const int k = block * kThreads + threadIdx.x;
+  if (block * kThreads >= total) return;  // the whole workgroup
   const int i = k < total ? (listed ? s.list[k] : k) : -1;
   bool live = false;
   if (i >= 0) {
@@ -310,10 +323,14 @@ __global__ __launch_bounds__(kThreads) void nn_resolve_kernel(NnSearch s, double
   }
 }
 
-__global__ __launch_bounds__(kThreads) void nn_transform_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                                const float* __restrict__ z, int n, Rigid12 m, float* ox, float* oy,
-                                                                float* oz) {
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void nn_resolve_kernel(NnSearch s, double max_d2, bool listed) {
+  nn_resolve_body(s, max_d2, listed, static_cast<int>(blockIdx.x));
+}
+
+// x/y/z may be ox/oy/oz: a lane reads its point before it writes it
+__device__ __forceinline__ void nn_transform_body(const float* x, const float* y, const float* z, int n, const Rigid12& m, float* ox,
+                                                  float* oy, float* oz, int block) {
+  const int i = block * kThreads + threadIdx.x;
   if (i < n) {
     const double px = x[i], py = y[i], pz = z[i];
     const float rx = static_cast<float>(((m.m[0] * px + m.m[1] * py) + m.m[2] * pz) + m.m[3]);
@@ -323,6 +340,58 @@ __global__ __launch_bounds__(kThreads) void nn_transform_kernel(const float* __r
     oy[i] = ry;
     oz[i] = rz;
   }
+}
+
+__global__ __launch_bounds__(kThreads) void nn_transform_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                                const float* __restrict__ z, int n, Rigid12 m, float* ox, float* oy,
+                                                                float* oz) {
+  nn_transform_body(x, y, z, n, m, ox, oy, oz, static_cast<int>(blockIdx.x));
+}
+
+// ---- the same bodies over a table of searches: blockIdx.y (z for the scan, whose y is the segment) is the pair.  A
+// workgroup outside its pair's extent -- queries, segments -- leaves as a whole before any barrier or ballot.
+__device__ __forceinline__ const NnBatchItem& nn_item(const char* table, size_t stride, unsigned pair) {
+  return *reinterpret_cast<const NnBatchItem*>(table + stride * pair);
+}
+
+__global__ __launch_bounds__(kThreads) void nn_transform_batch_kernel(const char* __restrict__ table, size_t stride) {
+  const NnBatchItem& d = nn_item(table, stride, blockIdx.y);
+  const int block = static_cast<int>(blockIdx.x);
+  if (d.transform == 0 || block * kThreads >= d.search.n) return;
+  const Rigid12 m = d.m;
+  nn_transform_body(d.sx, d.sy, d.sz, d.search.n, m, d.ox, d.oy, d.oz, block);
+}
+
+// a pair that searches by brute force has no walk: its keys are preset here, where nn_search_enqueue has a memset
+__global__ __launch_bounds__(kThreads) void nn_shell_batch_kernel(const char* __restrict__ table, size_t stride) {
+  const NnBatchItem& d = nn_item(table, stride, blockIdx.y);
+  const int block = static_cast<int>(blockIdx.x);
+  if (block * kThreads >= d.search.n) return;
+  const NnSearch s = d.search;
+  if (d.brute != 0) {
+    const int i = block * kThreads + threadIdx.x;
+    if (i < s.n) s.key[i] = ~0ull;
+    return;
+  }
+  const NnGridView g = d.view;
+  nn_shell_body(g, s, d.max_d2, block);
+}
+
+__global__ __launch_bounds__(kThreads) void nn_brute_batch_kernel(const char* __restrict__ table, size_t stride) {
+  const NnBatchItem& d = nn_item(table, stride, blockIdx.z);
+  const int block = static_cast<int>(blockIdx.x);
+  if (static_cast<int>(blockIdx.y) >= d.segments || block * kThreads >= d.search.n) return;
+  const NnGridView g = d.view;
+  const NnSearch s = d.search;
+  nn_brute_body(g, s, d.brute == 0, d.segment, block, static_cast<int>(gridDim.x), static_cast<int>(blockIdx.y));
+}
+
+__global__ __launch_bounds__(kThreads) void nn_resolve_batch_kernel(const char* __restrict__ table, size_t stride) {
+  const NnBatchItem& d = nn_item(table, stride, blockIdx.y);
+  const int block = static_cast<int>(blockIdx.x);
+  if (block * kThreads >= d.search.n) return;
+  const NnSearch s = d.search;
+  nn_resolve_body(s, d.max_d2, d.brute == 0, block);
 }
 
 // The grid over a box of `extent` metres an axis for n points: edge0 (0: half the edge that puts a point a cell into the
@@ -389,24 +458,64 @@ dliom_ctx* nn_ctx(const dliom_nn_index* index) { return index->ctx; }
 DevBuf* nn_scratch(dliom_nn_index* index) { return &index->scratch; }
 int* nn_poll_us(dliom_nn_index* index) { return &index->poll_us; }
 
+// segments of about kBruteSegment (kListedSegment) points, at most 256 of them
+void nn_batch_item(const dliom_nn_index* index, int search, NnBatchItem* item) {
+  item->view = nn_view(index);
+  const bool brute = search == DLIOM_NN_BRUTE_FORCE || (search == DLIOM_NN_AUTO && index->search == DLIOM_NN_BRUTE_FORCE);
+  item->brute = brute ? 1 : 0;
+  const int wanted = brute ? kBruteSegment : kListedSegment;
+  item->segments = std::max(1, std::min(256, (item->view.n_finite + wanted - 1) / wanted));
+  item->segment = std::max(1, (item->view.n_finite + item->segments - 1) / item->segments);
+}
+
 int nn_search_enqueue(dliom_nn_index* index, const NnSearch& s, double max_d2, int search) {
   if (s.n <= 0) return DLIOM_OK;
   hipStream_t stream = index->ctx->stream;
-  const NnGridView g = nn_view(index);
+  NnBatchItem geometry;
+  nn_batch_item(index, search, &geometry);
+  const NnGridView g = geometry.view;
   const dim3 grid(blocks_of(s.n, kThreads)), block(kThreads);
-  const bool brute = search == DLIOM_NN_BRUTE_FORCE || (search == DLIOM_NN_AUTO && index->search == DLIOM_NN_BRUTE_FORCE);
+  const bool brute = geometry.brute != 0;
   if (brute)
     DLIOM_HIP_TRY(hipMemsetAsync(s.key, 0xFF, sizeof(unsigned long long) * static_cast<size_t>(s.n), stream));
   else
     hipLaunchKernelGGL(nn_shell_kernel, grid, block, 0, stream, g, s, max_d2);
-  // segments of about kBruteSegment (kListedSegment) points, at most 256 of them; tiles of queries strided over at most
-  // 128 workgroups
-  const int wanted = brute ? kBruteSegment : kListedSegment;
-  const int segments = std::max(1, std::min(256, (g.n_finite + wanted - 1) / wanted));
-  const int segment = std::max(1, (g.n_finite + segments - 1) / segments);
-  const dim3 brute_grid(std::min(grid.x, 128u), static_cast<unsigned>(segments));
-  hipLaunchKernelGGL(nn_brute_kernel, brute_grid, block, 0, stream, g, s, !brute, segment);
+  // tiles of queries strided over at most 128 workgroups
+  const dim3 brute_grid(std::min(grid.x, 128u), static_cast<unsigned>(geometry.segments));
+  hipLaunchKernelGGL(nn_brute_kernel, brute_grid, block, 0, stream, g, s, !brute, geometry.segment);
   hipLaunchKernelGGL(nn_resolve_kernel, grid, block, 0, stream, s, max_d2, !brute);
+  DLIOM_HIP_TRY(hipGetLastError());
+  return DLIOM_OK;
+}
+
+// Launches sized by the largest pair of the table; a key cannot be lost to the stride of the tiles (an atomicMin's result
+// does not depend on which workgroup brought a segment's best).  A launch holds at most 2^30 lanes: a table of many large
+// pairs goes in runs of pairs, one behind the other.
+int nn_batch_pairs_per_launch(int max_n) { return std::max(1, (1 << 22) / static_cast<int>(blocks_of(std::max(max_n, 1), kThreads))); }
+
+int nn_search_batch_enqueue(dliom_ctx* ctx, const void* table, size_t stride, int count, int max_n, int max_segments) {
+  if (count <= 0 || max_n <= 0) return DLIOM_OK;
+  const unsigned blocks = blocks_of(max_n, kThreads);
+  const dim3 block(kThreads);
+  const int run = nn_batch_pairs_per_launch(max_n);
+  for (int first = 0; first < count; first += run) {
+    const char* const t = static_cast<const char*>(table) + stride * static_cast<size_t>(first);
+    const unsigned pairs = static_cast<unsigned>(std::min(run, count - first));
+    hipLaunchKernelGGL(nn_shell_batch_kernel, dim3(blocks, pairs), block, 0, ctx->stream, t, stride);
+    hipLaunchKernelGGL(nn_brute_batch_kernel, dim3(std::min(blocks, 128u), static_cast<unsigned>(std::max(max_segments, 1)), pairs),
+                       block, 0, ctx->stream, t, stride);
+    hipLaunchKernelGGL(nn_resolve_batch_kernel, dim3(blocks, pairs), block, 0, ctx->stream, t, stride);
+  }
+  DLIOM_HIP_TRY(hipGetLastError());
+  return DLIOM_OK;
+}
+
+int nn_transform_batch_enqueue(dliom_ctx* ctx, const void* table, size_t stride, int count, int max_n) {
+  if (count <= 0 || max_n <= 0) return DLIOM_OK;
+  const int run = nn_batch_pairs_per_launch(max_n);
+  for (int first = 0; first < count; first += run)
+    hipLaunchKernelGGL(nn_transform_batch_kernel, dim3(blocks_of(max_n, kThreads), static_cast<unsigned>(std::min(run, count - first))),
+                       dim3(kThreads), 0, ctx->stream, static_cast<const char*>(table) + stride * static_cast<size_t>(first), stride);
   DLIOM_HIP_TRY(hipGetLastError());
   return DLIOM_OK;
 }

@@ -16,6 +16,9 @@
 //  * kPinIcpSums belongs to an alignment or a step of icp.hip, entry points of their own: one read-back an iteration (the
 //    sums of the tree reduction), copied out before the next launch.  The index's creation (nn_index.hip) reads its
 //    bounding box through kPinReadback, in a call of its own;
+//  * kPinIcpBatchReadback and kPinIcpBatchTable belong to a batched alignment (icp_batch.hip), an entry point of its own
+//    that runs no single alignment: every lock-step round it fills the table with the descriptors of the pairs in flight
+//    before its launches and has copied the pairs' read-back slots out before it writes the table again or returns;
 //  * kPinNdtSums belongs to an alignment or an evaluation of ndt.hip, entry points of their own: one read-back an
 //    evaluation, copied out before the next launch.  The fitness score at an alignment's end is ICP's (kPinIcpSums); the
 //    target's creation and the aligned cloud's norm read a few words through kPinReadback;
@@ -76,6 +79,12 @@ constexpr PinRegion kPinFeatureResults{8192 * 32, 8192 * 48};
 // an ICP alignment (icp.hip): the sixteen sums, the count and the search counters of one iteration
 constexpr PinRegion kPinIcpSums{4096, 256};
 
+// a batched ICP alignment (icp_batch.hip): a read-back slot (icp_internal.h IcpReadback) for every pair that may be in
+// flight (DLIOM_ICP_BATCH_MAX_PAIRS), and the round's upload, a descriptor for each of them
+constexpr size_t kPinIcpBatchPairs = 256, kPinIcpBatchSlotBytes = 160, kPinIcpBatchEntryBytes = 384;
+constexpr PinRegion kPinIcpBatchReadback{8192, kPinIcpBatchPairs * kPinIcpBatchSlotBytes};
+constexpr PinRegion kPinIcpBatchTable{65536, kPinIcpBatchPairs * kPinIcpBatchEntryBytes};
+
 // an NDT evaluation (ndt.hip): up to 28 sums and the pair count
 constexpr PinRegion kPinNdtSums{4096 + 256, 256};
 
@@ -125,6 +134,9 @@ static_assert(pins_inside({kPinFeaturePairs, kPinFeatureResults}, kPinnedBytes) 
               "a feature match's regions");
 static_assert(pins_inside({kPinIcpSums}, kPinnedBytes) && pins_disjoint({kPinIcpSums, kPinReadback}),
               "an ICP alignment's region (apart from the small read-backs of the helpers it may call)");
+static_assert(pins_inside({kPinIcpBatchReadback, kPinIcpBatchTable}, kPinnedBytes) &&
+                  pins_disjoint({kPinIcpBatchReadback, kPinIcpBatchTable, kPinReadback, kPinIcpSums, kPinNdtSums}),
+              "a batched ICP alignment's regions");
 static_assert(pins_inside({kPinNdtSums}, kPinnedBytes) && pins_disjoint({kPinNdtSums, kPinIcpSums, kPinReadback}),
               "an NDT alignment's regions (its fitness score is ICP's)");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");

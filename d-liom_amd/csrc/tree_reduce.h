@@ -3,6 +3,7 @@
 // the leaf index, +0.0 beyond the last leaf, adjacent pairs added level by level -- a function of the index alone.
 //   tree_reduce_kernel<S, Leaves>  one workgroup per 2048 consecutive leaves: a lane sums 8 adjacent leaves pairwise, the
 //                                  workgroup its 256 lanes pairwise through LDS -- the subtree over those 2048 leaves
+//                                  (tree_reduce_block, the body, is also what a batched reduction runs per pair)
 //   tree_finish<S>                 inside a one-workgroup kernel: the tree over the workgroups' partial sums, padded with
 //                                  +0.0 to a power of two; the root is left in partials[0 .. S)
 // Leaves: a struct passed by value with  __device__ void leaf(int i, double v[S], int* count) const  (all +0.0 and 0 for
@@ -34,13 +35,15 @@ __device__ __forceinline__ void tree_subtree(const Leaves& L, int first, double 
   }
 }
 
+// One workgroup's subtree: the 2048 leaves from block * 2048, into partials[block * S ..) and counts[block].  Called by every
+// lane of a kTreeThreads workgroup (tree_reduce_kernel; icp_batch.hip's kernel, where the block is one of a pair's)
 template <int S, class Leaves>
-__global__ __launch_bounds__(kTreeThreads) void tree_reduce_kernel(Leaves L, double* __restrict__ partials, int* __restrict__ counts) {
+__device__ __forceinline__ void tree_reduce_block(const Leaves& L, int block, double* __restrict__ partials, int* __restrict__ counts) {
   __shared__ double lds[kTreeThreads * S];
   __shared__ int lds_count[kTreeThreads];
   double v[S];
   int count = 0;
-  tree_subtree<S, kTreeLeavesPerLane>(L, (static_cast<int>(blockIdx.x) * kTreeThreads + threadIdx.x) * kTreeLeavesPerLane, v, &count);
+  tree_subtree<S, kTreeLeavesPerLane>(L, (block * kTreeThreads + static_cast<int>(threadIdx.x)) * kTreeLeavesPerLane, v, &count);
   for (int k = 0; k < S; ++k) lds[threadIdx.x * S + k] = v[k];
   lds_count[threadIdx.x] = count;
   for (int w = 1; w < kTreeThreads; w <<= 1) {  // adjacent pairs, level by level
@@ -53,8 +56,13 @@ __global__ __launch_bounds__(kTreeThreads) void tree_reduce_kernel(Leaves L, dou
     if (static_cast<int>(threadIdx.x) < pairs) lds_count[threadIdx.x * 2 * w] += lds_count[threadIdx.x * 2 * w + w];
   }
   __syncthreads();
-  if (threadIdx.x < S) partials[static_cast<size_t>(blockIdx.x) * S + threadIdx.x] = lds[threadIdx.x];
-  if (threadIdx.x == 0) counts[blockIdx.x] = lds_count[0];
+  if (threadIdx.x < S) partials[static_cast<size_t>(block) * S + threadIdx.x] = lds[threadIdx.x];
+  if (threadIdx.x == 0) counts[block] = lds_count[0];
+}
+
+template <int S, class Leaves>
+__global__ __launch_bounds__(kTreeThreads) void tree_reduce_kernel(Leaves L, double* __restrict__ partials, int* __restrict__ counts) {
+  tree_reduce_block<S, Leaves>(L, static_cast<int>(blockIdx.x), partials, counts);
 }
 
 // partials: room for P2 >= P entries of S, P2 a power of two; called by every lane of a kTreeThreads workgroup

@@ -3512,6 +3512,93 @@ class Icp:
                 cloud.close()
 
 
+# many pairs in one call (dliom_icp_align_batch): the ground-truth tool's loop over a trajectory's constraints
+ICP_BATCH_MAX_PAIRS = 256
+
+
+class IcpPair(C.Structure):
+    _fields_ = [("index", _vp), ("source", _vp), ("guess", C.c_double * 16)]
+
+
+class IcpBatchLimits(C.Structure):
+    _fields_ = [("max_pairs_in_flight", C.c_int), ("reserved", C.c_int), ("max_scratch_bytes", C.c_int64)]
+
+
+class IcpBatchStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("pairs", "chunks", "steps", "read_backs", "synchronizations", "pair_searches",
+                                         "max_in_flight")] + \
+               [(f, C.c_double) for f in ("search_ms", "reduce_ms", "solve_ms", "transform_ms")]
+
+
+SYMBOLS += [
+    ("dliom_icp_batch_default_limits", C.c_int, [C.POINTER(IcpBatchLimits)]),
+    ("dliom_icp_batch_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("dliom_icp_align_batch", C.c_int, [_vp, C.POINTER(IcpPair), C.c_int, C.POINTER(IcpOptions), C.POINTER(IcpBatchLimits),
+                                        C.POINTER(IcpResult), C.POINTER(_vp), C.POINTER(IcpBatchStats)]),
+]
+
+
+def icp_batch_default_limits(**overrides):
+    """dliom_icp_batch_default_limits, with fields replaced"""
+    lim = IcpBatchLimits()
+    _check(load_library().dliom_icp_batch_default_limits(C.byref(lim)), "dliom_icp_batch_default_limits")
+    for k, v in overrides.items():
+        if k not in dict(IcpBatchLimits._fields_):
+            raise TypeError("no ICP batch limit " + k)
+        setattr(lim, k, v)
+    return lim
+
+
+def icp_batch_scratch_bytes(n):
+    """the device scratch one pair in flight with n source points reserves (host only)"""
+    return int(load_library().dliom_icp_batch_scratch_bytes(int(n)))
+
+
+def icp_align_batch(ctx, pairs, options=None, limits=None, want_aligned=False):
+    """dliom_icp_align_batch.  pairs: a list of (NnIndex, PointCloud or (n, 3) array, guess 4x4 or None).  -> (results,
+    stats) or (results, stats, clouds): results as Icp.align gives them, pair by pair and bit for bit; stats a dict; clouds
+    the aligned points, (n, 3) float32 each."""
+    L = ctx._L
+    options = options if options is not None else icp_options()
+    count = len(pairs)
+    table, made = (IcpPair * max(count, 1))(), []
+    handles = (_vp * max(count, 1))()
+    try:
+        uploaded = {}  # one upload for an array that several pairs name
+        for i, (index, source, guess) in enumerate(pairs):
+            if isinstance(source, PointCloud):
+                cloud = source
+            elif id(source) in uploaded:
+                cloud = uploaded[id(source)]
+            else:
+                cloud = uploaded[id(source)] = PointCloud(ctx, source)
+                made.append(cloud)
+            table[i].index, table[i].source = index.h, cloud.h
+            table[i].guess[:] = list(_f64(np.eye(4) if guess is None else guess).reshape(16))
+        results, stats = (IcpResult * max(count, 1))(), IcpBatchStats()
+        _check(L.dliom_icp_align_batch(ctx.h, table, count, C.byref(options), None if limits is None else C.byref(limits),
+                                       results, handles if want_aligned else None, C.byref(stats)), "dliom_icp_align_batch")
+        out = [_icp_result(results[i]) for i in range(count)]
+        st = {k: getattr(stats, k) for k, _ in IcpBatchStats._fields_}
+        if not want_aligned:
+            return out, st
+        clouds = []
+        for i in range(count):
+            aligned = PointCloud(ctx, _handle=_vp(handles[i]))
+            handles[i] = None
+            try:
+                clouds.append(aligned.download())
+            finally:
+                aligned.close()
+        return out, st, clouds
+    finally:
+        for i in range(count):
+            if want_aligned and handles[i]:
+                L.dliom_cloud_destroy(_vp(handles[i]))
+        for cloud in made:
+            cloud.close()
+
+
 # ---- scan alignment by NDT (include/dliom.h "scan alignment by NDT") -----------------------------------------------------
 NDT_JACOBI_SWEEPS, NDT_PINV_SWEEPS, NDT_MAX_CELL_INDEX = 8, 12, 1 << 20
 NDT_STEP_CLAMPED, NDT_STEP_MORE_THUENTE = 0, 1

@@ -2367,6 +2367,53 @@ int dliom_icp_align(dliom_nn_index* index, const dliom_cloud* source, const doub
 int dliom_icp_step(dliom_nn_index* index, const dliom_cloud* points, const dliom_icp_options* options, int32_t* j_out,
                    float* d2_out, double* sums16, int64_t* correspondences, double* rotation9, double* translation3);
 
+/* Many pairs in one call: gen_ground_truth_by_ndt_match.cc:151-261 aligns the two scans of EVERY inter-submap constraint of
+ * a trajectory, hundreds to thousands of independent alignments.  All pairs of a chunk advance in lock step: a step is one
+ * search of every pair still in flight, in ONE launch chain with ONE polled read-back, whatever the number of pairs.
+ *
+ * Results.  results[i] is what dliom_icp_align(pairs[i].index, pairs[i].source, pairs[i].guess, options, ...) returns, bit
+ * for bit, in converged, reason, iterations, correspondences, transform, mse, fitness_score, fitness_count, read_backs (the
+ * searches the pair took part in), settled_by_grid and settled_by_brute_force (from a counter block of the pair's own,
+ * zeroed at its start).  The four *_ms fields of a result are 0; the stages' times are in the statistics.  aligned[i] is the
+ * single call's cloud, norm bound included.  Results never depend on the limits or on the order of the pairs.
+ *
+ * Schedule.  Chunks are consecutive runs of pairs in input order.  A chunk closes when it holds max_pairs_in_flight pairs,
+ * or when adding the next pair's dliom_icp_batch_scratch_bytes(n) would take the chunk's sum above max_scratch_bytes; it
+ * always holds at least one pair.  Chunks are not refilled: a chunk takes as many steps as the pair of it with the most
+ * searches, `steps` is the sum over the chunks, and read_backs == steps.
+ *
+ * Refusals, all before anything runs (DLIOM_ERR_INVALID_ARGUMENT): a NULL context or options; NULL pairs or results
+ * with count > 0; count < 0; options that dliom_icp_align refuses; limits outside their ranges; a pair with a NULL index
+ * or source, with an index or a cloud of another context, or with a guess that dliom_icp_align refuses.  count == 0
+ * succeeds and launches nothing.  A HIP or allocation failure fails the whole call and leaves no cloud behind (every
+ * aligned[i] is NULL).  There is no per-pair status: the single call has no refusal of a pair that passes these checks. */
+#define DLIOM_ICP_BATCH_MAX_PAIRS 256
+typedef struct dliom_icp_pair {
+  dliom_nn_index* index;        /* the target; any number of pairs may name one index */
+  const dliom_cloud* source;    /* any number of pairs may name one cloud */
+  double guess[16];             /* as dliom_icp_align's guess16 */
+} dliom_icp_pair;
+typedef struct dliom_icp_batch_limits {
+  int max_pairs_in_flight;      /* 1 .. DLIOM_ICP_BATCH_MAX_PAIRS; default 64 */
+  int reserved;                 /* 0 */
+  int64_t max_scratch_bytes;    /* > 0; default 1 GiB */
+} dliom_icp_batch_limits;       /* NULL = the defaults, which dliom_icp_batch_default_limits() returns */
+typedef struct dliom_icp_batch_stats {
+  int64_t pairs, chunks, steps; /* steps: lock-step rounds (one search of every pair still in flight) */
+  int64_t read_backs;           /* polled read-backs of the call == steps */
+  int64_t synchronizations;     /* stream synchronisations of the call: one a chunk when `aligned` is given (its clouds are
+                                   copied out of the chunk's scratch), one for the stages' times while profiling is on */
+  int64_t pair_searches;        /* sum over pairs of the searches they took part in == sum of results[i].read_backs */
+  int64_t max_in_flight;        /* the largest chunk */
+  double search_ms, reduce_ms, solve_ms, transform_ms;  /* only while the context's profiling is on */
+} dliom_icp_batch_stats;
+int dliom_icp_batch_default_limits(dliom_icp_batch_limits* limits);
+/* Host only: the device scratch that one pair in flight with source_points points reserves (0 for a negative count). */
+int64_t dliom_icp_batch_scratch_bytes(int64_t source_points);
+int dliom_icp_align_batch(dliom_ctx* ctx, const dliom_icp_pair* pairs, int count, const dliom_icp_options* options,
+                          const dliom_icp_batch_limits* limits, dliom_icp_result* results,
+                          dliom_cloud** aligned /* NULL, or count entries */, dliom_icp_batch_stats* stats /* may be NULL */);
+
 /* ---- scan alignment by NDT ------------------------------------------------------------------------------
  * pcl::NormalDistributionsTransform as the reference runs it: LocalTrajectoryBuilder3D::MatchByNDT
  * (local_trajectory_builder_3d.cc:969-1008: epsilon 0.01, step 0.1, resolution 1.0, 35 iterations, on clouds filtered by
