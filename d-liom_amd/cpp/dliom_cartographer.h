@@ -3848,6 +3848,34 @@ inline float GroundTruthDifferenceNorm(const Matrix4f& gt, const Matrix4f& trans
   return std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
 }
 
+// The pair-collection half of the loop (:151-185), which the two methods share: for every `from` node that has a revisit node
+// and whose two stamps lie within the bag, the stamps, the pose-graph's estimate gt and the pair (source: the `from` scan,
+// target: the revisit node's, guess: gt), in order.
+struct GroundTruthWanted {
+  int64_t stamp_from, stamp_to;
+  Matrix4f gt;
+};
+inline void CollectGroundTruthPairs(const std::vector<transform::Rigid3d>& poses, const std::vector<int64_t>& timestamps_ns,
+                                    const std::vector<int64_t>& stamps_in_bag, const std::vector<sensor::PointCloud>& clouds,
+                                    const std::vector<size_t>& from_nodes, std::vector<GroundTruthWanted>* wanted,
+                                    std::vector<AlignmentPair>* pairs) {
+  for (const size_t from : from_nodes) {
+    const int to = FindRevisitNode(poses, timestamps_ns, from);
+    if (to < 0) continue;
+    const int64_t stamp_to = timestamps_ns[static_cast<size_t>(to)], stamp_from = timestamps_ns[from];
+    const auto it_to = std::lower_bound(stamps_in_bag.begin(), stamps_in_bag.end(), stamp_to);
+    const auto it_from = std::lower_bound(stamps_in_bag.begin(), stamps_in_bag.end(), stamp_from);
+    if (it_to == stamps_in_bag.end() || it_from == stamps_in_bag.end()) continue;
+    GroundTruthWanted w{stamp_from, stamp_to, GroundTruthGuess(poses[static_cast<size_t>(to)], poses[from])};
+    AlignmentPair p;
+    p.source = &clouds[static_cast<size_t>(it_from - stamps_in_bag.begin())];
+    p.target = &clouds[static_cast<size_t>(it_to - stamps_in_bag.begin())];
+    p.guess = w.gt;
+    wanted->push_back(w);
+    pairs->push_back(p);
+  }
+}
+
 // The tool's loop (gen_ground_truth_by_ndt_match.cc:151-261) for --method icp over the constraints whose `from` nodes are
 // given (the caller has dropped the intra-submap ones, :153): the text of the tool's file for them, in order.
 // poses, timestamps_ns: one a node; stamps_in_bag (sorted) and clouds: one a scan of the bag.  A `from` node without a
@@ -3860,27 +3888,9 @@ inline std::string GenerateGroundTruthIcp(Context* context, const std::vector<tr
                                           size_t batch_size) {
   if (batch_size < 1 || clouds.size() != stamps_in_bag.size() || timestamps_ns.size() != poses.size())
     Check(DLIOM_ERR_INVALID_ARGUMENT, "GenerateGroundTruthIcp");
-  struct Wanted {
-    int64_t stamp_from, stamp_to;
-    Matrix4f gt;
-  };
-  std::vector<Wanted> wanted;
+  std::vector<GroundTruthWanted> wanted;
   std::vector<AlignmentPair> pairs;
-  for (const size_t from : from_nodes) {
-    const int to = FindRevisitNode(poses, timestamps_ns, from);
-    if (to < 0) continue;
-    const int64_t stamp_to = timestamps_ns[static_cast<size_t>(to)], stamp_from = timestamps_ns[from];
-    const auto it_to = std::lower_bound(stamps_in_bag.begin(), stamps_in_bag.end(), stamp_to);
-    const auto it_from = std::lower_bound(stamps_in_bag.begin(), stamps_in_bag.end(), stamp_from);
-    if (it_to == stamps_in_bag.end() || it_from == stamps_in_bag.end()) continue;
-    Wanted w{stamp_from, stamp_to, GroundTruthGuess(poses[static_cast<size_t>(to)], poses[from])};
-    AlignmentPair p;
-    p.source = &clouds[static_cast<size_t>(it_from - stamps_in_bag.begin())];
-    p.target = &clouds[static_cast<size_t>(it_to - stamps_in_bag.begin())];
-    p.guess = w.gt;
-    wanted.push_back(w);
-    pairs.push_back(p);
-  }
+  CollectGroundTruthPairs(poses, timestamps_ns, stamps_in_bag, clouds, from_nodes, &wanted, &pairs);
   const dliom_icp_options options = IterativeClosestPoint::GroundTruthIcp(context)->options();
   std::string text;
   for (size_t first = 0; first < pairs.size(); first += batch_size) {
@@ -4035,6 +4045,104 @@ class NormalDistributionsTransform {
   dliom_ndt_target* target_ = nullptr;
   dliom_nn_index* index_ = nullptr;
 };
+
+// Many NDT alignments in one call (dliom_ndt_align_batch): the pairs of the tool's loop under --method ndt.  What
+// NormalDistributionsTransform with `ndt_options` gives pair by pair (setInputSource, setInputTarget(target, with_fitness),
+// align(guess), result()), bit for bit but for read_backs (dliom.h).  ONE dliom_ndt_target is built per distinct target
+// pointer -- and with with_fitness ONE nearest-neighbour index for getFitnessScore() -- and one cloud uploaded per distinct
+// source pointer, however many pairs name them; everything is destroyed on every way out.  limits: NULL = the defaults.
+// aligned (may be null): every pair's source under its final transformation.  stats (may be null): the call's.
+inline std::vector<dliom_ndt_result> AlignPairsNdt(Context* context, const dliom_ndt_options& ndt_options,
+                                                   const std::vector<AlignmentPair>& pairs, bool with_fitness = true,
+                                                   const dliom_ndt_batch_limits* limits = nullptr,
+                                                   std::vector<sensor::PointCloud>* aligned = nullptr,
+                                                   dliom_ndt_batch_stats* stats = nullptr) {
+  struct Owned {  // destroyed on every way out, the targets and indices before nothing else depends on them
+    std::map<const sensor::PointCloud*, dliom_ndt_target*> targets;
+    std::map<const sensor::PointCloud*, dliom_nn_index*> indices;
+    std::map<const sensor::PointCloud*, dliom_cloud*> sources;
+    std::vector<dliom_cloud*> outputs;
+    ~Owned() {
+      for (auto& e : targets) dliom_ndt_target_destroy(e.second);
+      for (auto& e : indices) dliom_nn_index_destroy(e.second);
+      for (auto& e : sources) dliom_cloud_destroy(e.second);
+      for (dliom_cloud* c : outputs) dliom_cloud_destroy(c);
+    }
+  } owned;
+  const auto upload = [context](const sensor::PointCloud* cloud) {
+    dliom_cloud* out = nullptr;
+    Check(dliom_cloud_create(context->get(), cloud->empty() ? nullptr : &(*cloud)[0].x, static_cast<int64_t>(cloud->size()), &out),
+          "dliom_cloud_create");
+    return out;
+  };
+  std::vector<dliom_ndt_pair> table(pairs.size());
+  for (size_t i = 0; i < pairs.size(); ++i) {
+    const AlignmentPair& p = pairs[i];
+    if (p.source == nullptr || p.target == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "AlignPairsNdt: a pair without a cloud");
+    if (owned.targets.find(p.target) == owned.targets.end()) {
+      dliom_cloud* cloud = upload(p.target);
+      dliom_ndt_target* target = nullptr;
+      dliom_nn_index* index = nullptr;
+      int status = dliom_ndt_target_create(context->get(), cloud, &ndt_options, &target);
+      if (status == DLIOM_OK) owned.targets[p.target] = target;
+      if (status == DLIOM_OK && with_fitness) {
+        status = dliom_nn_index_create(context->get(), cloud, nullptr, &index);
+        if (status == DLIOM_OK) owned.indices[p.target] = index;
+      }
+      dliom_cloud_destroy(cloud);
+      Check(status, "dliom_ndt_target_create");
+    }
+    if (owned.sources.find(p.source) == owned.sources.end()) owned.sources[p.source] = upload(p.source);
+    table[i].target = owned.targets[p.target];
+    table[i].source = owned.sources[p.source];
+    table[i].fitness_index = with_fitness ? owned.indices[p.target] : nullptr;
+    for (int k = 0; k < 16; ++k) table[i].guess[k] = static_cast<double>(p.guess.m[k]);
+  }
+  std::vector<dliom_ndt_result> results(pairs.size());
+  if (aligned != nullptr) owned.outputs.assign(pairs.size(), nullptr);
+  Check(dliom_ndt_align_batch(context->get(), table.data(), static_cast<int>(table.size()), &ndt_options, limits, results.data(),
+                              aligned != nullptr ? owned.outputs.data() : nullptr, stats),
+        "dliom_ndt_align_batch");
+  if (aligned != nullptr) {
+    aligned->assign(pairs.size(), sensor::PointCloud());
+    for (size_t i = 0; i < pairs.size(); ++i) {
+      (*aligned)[i].resize(pairs[i].source->size());
+      if (!(*aligned)[i].empty()) Check(dliom_cloud_download(owned.outputs[i], &(*aligned)[i][0].x), "dliom_cloud_download");
+    }
+  }
+  return results;
+}
+
+// The tool's loop (gen_ground_truth_by_ndt_match.cc:151-261) for --method ndt (:211-222), GenerateGroundTruthIcp's other
+// half: the same pairs (CollectGroundTruthPairs), aligned batch_size pairs a call with the GroundTruthNdt preset on the raw
+// clouds, getFitnessScore() as the alignment error, a pair that does not converge dropped (:218).  The text is byte-equal
+// to the loop through NormalDistributionsTransform::GroundTruthNdt one pair at a time, whatever batch_size is.
+inline std::string GenerateGroundTruthNdt(Context* context, const std::vector<transform::Rigid3d>& poses,
+                                          const std::vector<int64_t>& timestamps_ns, const std::vector<int64_t>& stamps_in_bag,
+                                          const std::vector<sensor::PointCloud>& clouds, const std::vector<size_t>& from_nodes,
+                                          size_t batch_size) {
+  if (batch_size < 1 || clouds.size() != stamps_in_bag.size() || timestamps_ns.size() != poses.size())
+    Check(DLIOM_ERR_INVALID_ARGUMENT, "GenerateGroundTruthNdt");
+  std::vector<GroundTruthWanted> wanted;
+  std::vector<AlignmentPair> pairs;
+  CollectGroundTruthPairs(poses, timestamps_ns, stamps_in_bag, clouds, from_nodes, &wanted, &pairs);
+  const dliom_ndt_options options = NormalDistributionsTransform::GroundTruthNdt(context)->options();
+  std::string text;
+  for (size_t first = 0; first < pairs.size(); first += batch_size) {
+    const size_t end = std::min(pairs.size(), first + batch_size);
+    const std::vector<AlignmentPair> group(pairs.begin() + static_cast<std::ptrdiff_t>(first), pairs.begin() + static_cast<std::ptrdiff_t>(end));
+    const std::vector<dliom_ndt_result> results = AlignPairsNdt(context, options, group, true);
+    for (size_t i = first; i < end; ++i) {
+      const dliom_ndt_result& r = results[i - first];
+      if (r.converged == 0) continue;
+      Matrix4f trans;
+      for (int k = 0; k < 16; ++k) trans.m[k] = static_cast<float>(r.transform[k]);
+      text += FormatGroundTruthLine(wanted[i].stamp_from, wanted[i].stamp_to, r.fitness_score, trans,
+                                    GroundTruthDifferenceNorm(wanted[i].gt, trans));
+    }
+  }
+  return text;
+}
 
 // LocalTrajectoryBuilder3D::MatchByNDT (local_trajectory_builder_3d.cc:969-1008): both clouds through ApproximateVoxelGrid
 // at 0.2 m, NDT of the filtered current scan against the filtered previous one from init_guess; -> the final

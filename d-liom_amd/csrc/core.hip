@@ -794,6 +794,7 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
   ctx->csm_arrivals.release();
   ctx->batch.release();
   ctx->icp_batch.release();
+  ctx->ndt_batch.release();
   ctx->xray_leaves.release();
   ctx->xray_cells.release();
   ctx->surf.release();

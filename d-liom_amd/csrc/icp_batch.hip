@@ -30,50 +30,24 @@ constexpr size_t kEntryBytes = kPinIcpBatchEntryBytes;
 // what dliom_icp_batch_scratch_bytes counts in front of a pair's arrays: its descriptor (rounded up) and its counters
 constexpr size_t kEntryShare = 512, kCounterBytes = 256;
 
-struct IcpBatchEntry {
-  NnBatchItem nn;
-  double* partials;
-  int* counts;
-  int P, P2;
-  unsigned* max_sq;
-  int want_norm;  // this is the pair's fitness step and its cloud is wanted
-  int slot;       // of kPinIcpBatchReadback
-};
 static_assert(sizeof(IcpBatchEntry) <= kEntryBytes && kEntryBytes % 8 == 0 && kEntryBytes <= kEntryShare, "a descriptor fits its place");
 
-__device__ __forceinline__ const IcpBatchEntry& entry_of(const char* table, unsigned pair) {
-  return *reinterpret_cast<const IcpBatchEntry*>(table + kEntryBytes * pair);
-}
-
+// the bodies are icp_internal.h's: ndt_batch.hip runs them in its pairs' final rounds
 __global__ __launch_bounds__(kThreads) void icp_batch_max_norm_kernel(const char* __restrict__ table) {
-  const IcpBatchEntry& d = entry_of(table, blockIdx.y);
-  const int n = d.nn.search.n;
-  if (d.want_norm == 0 || static_cast<int>(blockIdx.x) * kThreads >= n) return;
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  note_kept(i < n ? norm_word(d.nn.search.px[i], d.nn.search.py[i], d.nn.search.pz[i]) : 0u, d.max_sq);
+  icp_batch_max_norm_body(icp_batch_entry(table, kEntryBytes, blockIdx.y), static_cast<int>(blockIdx.x));
 }
 
 __global__ __launch_bounds__(kThreads) void icp_batch_reduce_kernel(const char* __restrict__ table) {
-  const IcpBatchEntry& d = entry_of(table, blockIdx.y);
-  const int block = static_cast<int>(blockIdx.x);
-  if (block >= d.P) return;
-  const IcpLeaves L{d.nn.search.px, d.nn.search.py, d.nn.search.pz, d.nn.search.j, d.nn.search.d2, d.nn.view.by_index, d.nn.search.n};
-  tree_reduce_block<kIcpSums, IcpLeaves>(L, block, d.partials, d.counts);
+  icp_batch_reduce_body(icp_batch_entry(table, kEntryBytes, blockIdx.y), static_cast<int>(blockIdx.x));
 }
 
 __global__ __launch_bounds__(kThreads) void icp_batch_finish_kernel(const char* __restrict__ table, IcpReadback* slots) {
-  const IcpBatchEntry& d = entry_of(table, blockIdx.x);
-  icp_finish_body(d.partials, d.counts, d.P, d.P2, d.nn.search.counters, d.max_sq, slots + d.slot);
-  __threadfence_system();  // the slot is in the host's memory before this workgroup ends
+  const IcpBatchEntry& d = icp_batch_entry(table, kEntryBytes, blockIdx.x);
+  icp_batch_finish_body(d, slots + d.slot);
 }
 
 // Runs behind the finish kernel on the stream: every slot has been written and fenced when the word goes out.
-__global__ void icp_batch_done_kernel(unsigned* done_word, unsigned done_seq) {
-  if (threadIdx.x == 0) {
-    __threadfence_system();
-    *reinterpret_cast<volatile unsigned*>(done_word) = done_seq;
-  }
-}
+__global__ void icp_batch_done_kernel(unsigned* done_word, unsigned done_seq) { batch_done_body(done_word, done_seq); }
 
 size_t pair_scratch_bytes(int64_t n) { return kEntryShare + kCounterBytes + icp_work_bytes(n); }
 

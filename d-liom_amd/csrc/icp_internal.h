@@ -4,6 +4,7 @@
 #ifndef DLIOM_CSRC_ICP_INTERNAL_H_
 #define DLIOM_CSRC_ICP_INTERNAL_H_
 
+#include "device_common.h"
 #include "nn_index.h"
 #include "tree_reduce.h"
 
@@ -59,6 +60,50 @@ __device__ __forceinline__ void icp_finish_body(double* partials, const int* __r
     for (int k = 0; k < kNnCounterWords; ++k) out->counters[k] = counters[k];
     counters[kNnListCount] = 0;  // the next search's list starts empty
     out->max_sq = max_sq != nullptr ? *max_sq : 0u;
+  }
+}
+
+// ---- many pairs in lock step (icp_batch.hip; the final rounds of ndt_batch.hip): a pair's descriptor in the round's table
+// and the bodies of the kernels that take the pair as a grid dimension.  A workgroup outside its pair's extent leaves as
+// a whole before any barrier.
+struct IcpBatchEntry {
+  NnBatchItem nn;
+  double* partials;
+  int* counts;
+  int P, P2;
+  unsigned* max_sq;
+  int want_norm;  // this is the pair's fitness step and its cloud is wanted
+  int slot;       // of the round's read-back slots
+};
+
+__device__ __forceinline__ const IcpBatchEntry& icp_batch_entry(const char* table, size_t stride, unsigned pair) {
+  return *reinterpret_cast<const IcpBatchEntry*>(table + stride * pair);
+}
+
+__device__ __forceinline__ void icp_batch_max_norm_body(const IcpBatchEntry& d, int block) {
+  const int n = d.nn.search.n;
+  if (d.want_norm == 0 || block * kTreeThreads >= n) return;
+  const int i = block * kTreeThreads + static_cast<int>(threadIdx.x);
+  note_kept(i < n ? norm_word(d.nn.search.px[i], d.nn.search.py[i], d.nn.search.pz[i]) : 0u, d.max_sq);
+}
+
+__device__ __forceinline__ void icp_batch_reduce_body(const IcpBatchEntry& d, int block) {
+  if (block >= d.P) return;
+  const IcpLeaves L{d.nn.search.px, d.nn.search.py, d.nn.search.pz, d.nn.search.j, d.nn.search.d2, d.nn.view.by_index, d.nn.search.n};
+  tree_reduce_block<kIcpSums, IcpLeaves>(L, block, d.partials, d.counts);
+}
+
+// a workgroup a pair: tree_finish over that pair's partial sums, into the pair's read-back slot (page-locked)
+__device__ __forceinline__ void icp_batch_finish_body(const IcpBatchEntry& d, IcpReadback* out) {
+  icp_finish_body(d.partials, d.counts, d.P, d.P2, d.nn.search.counters, d.max_sq, out);
+  __threadfence_system();  // the slot is in the host's memory before this workgroup ends
+}
+
+// one completion word behind everything on the stream
+__device__ __forceinline__ void batch_done_body(unsigned* done_word, unsigned done_seq) {
+  if (threadIdx.x == 0) {
+    __threadfence_system();
+    *reinterpret_cast<volatile unsigned*>(done_word) = done_seq;
   }
 }
 

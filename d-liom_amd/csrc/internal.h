@@ -133,6 +133,8 @@ struct dliom_ctx {
   // a batched ICP alignment (icp_batch.hip): the descriptor table and every pair's arrays of the chunk in flight; the
   // scratch belongs to the call, not to an index, since pairs share indices.  Reserved by the first such call
   dliom::DevBuf icp_batch;
+  // a batched NDT alignment (ndt_batch.hip): likewise, carved per pair as dliom_ndt_batch_scratch_bytes says
+  dliom::DevBuf ndt_batch;
   // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
   dliom::DevBuf xray_leaves, xray_cells;
   // the submap image features (surf.hip): what is sized by the image and the candidates; what is sized by the key points

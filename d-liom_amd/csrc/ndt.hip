@@ -18,7 +18,9 @@
 //                       store a value into the leaf arrays in HBM (224 B a point at most)
 //   tree_reduce_kernel (tree_reduce.h) and ndt_finish_kernel  ICP's fixed tree over the source index; the sums and the
 //                       pair count into the page-locked block (kPinNdtSums) and the completion word: one polled read-back
-// The pseudo-inverse, the step length and every decision run on the host between evaluations.
+// The pseudo-inverse, the step length and every decision run on the host between evaluations: NdtAlignment, a state machine
+// that takes an evaluation's sums and gives the next evaluation to run.  dliom_ndt_align drives one of it and blocks on
+// every evaluation; ndt_batch.hip drives one per pair, a round at a time.  The kernels' bodies are ndt_internal.h's.
 // A stream of scans (dliom_ndt_scan_matcher, MatchByNDT as InitilizeByNDT calls it): each scan through the approximate
 // voxel grid (approx_voxel.hip) once, aligned to the cells its predecessor left, then its own cells built and kept.
 #include <hipcub/hipcub.hpp>
@@ -29,23 +31,7 @@
 #include <limits>
 #include <vector>
 
-#include "device_common.h"
-#include "nn_index.h"
-#include "tree_reduce.h"
-
-struct dliom_ndt_target {
-  dliom_ctx* ctx = nullptr;
-  double resolution = 0.0;
-  int min_points = 0;
-  int64_t n_points = 0, n_kept = 0, n_valid = 0;
-  std::vector<dliom_ndt_cell> cells;  // every cell, in key order
-  dliom::DevBuf table;                // the valid cells: keys (8 B each), then mean and icov (72 B each)
-  size_t cell_data_at = 0;
-  dliom::DevBuf scratch;              // an evaluation's leaves, partial sums and counts
-  int poll_us = 150;
-  int64_t build_read_backs = 0;
-  double build_ms = 0.0;
-};
+#include "ndt_internal.h"
 
 struct dliom_ndt_scan_matcher {
   dliom_ctx* ctx;
@@ -57,15 +43,9 @@ struct dliom_ndt_scan_matcher {
 namespace dliom {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kHalf = DLIOM_NDT_MAX_CELL_INDEX;
+constexpr int kThreads = kNdtThreads;
+constexpr int kHalf = kNdtHalf;
 constexpr unsigned long long kSkipKey = ~0ull;
-constexpr int kCellDoubles = 9;  // mean (3), icov 00 01 02 11 12 22
-
-__host__ __device__ inline unsigned long long ndt_key(int ix, int iy, int iz) {
-  return (static_cast<unsigned long long>(iz + kHalf) << 42) | (static_cast<unsigned long long>(iy + kHalf) << 21) |
-         static_cast<unsigned long long>(ix + kHalf);
-}
 
 // ---- the target --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void ndt_key_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -158,190 +138,18 @@ __global__ __launch_bounds__(kThreads) void ndt_cell_sums_kernel(const float* __
   }
 }
 
-// ---- the evaluation ------------------------------------------------------------------------------------------------------
-struct NdtTable {
-  const unsigned long long* keys;  // the valid cells, ascending
-  const double* cell;              // 9 doubles each
-  int cells;
-  float inv, r2;
-  double d1, d2;
-};
-
-// T(p) and the coefficient rows of the header's point derivatives
-struct NdtPose {
-  double R[9], t[3];
-  double J[3][3][3];  // [angle][component][coefficient]; J[0][0] is not used (the component is +0.0)
-  double H[6][3][3];  // 33 34 35 44 45 55; [0..2][0] are not used
-};
-
-__device__ __forceinline__ double ndt_exp(double u) {
-  if (u < -708.0) return 0.0;
-  if (u != u) return u;
-  if (u > 708.0) return __longlong_as_double(0x7ff0000000000000ll);
-  const double k = rint(u * 0x1.71547652b82fep+0);
-  const double r = (u - k * 0x1.62e42fee00000p-1) - k * 0x1.a39ef35793c76p-33;
-  constexpr double c[14] = {1.0,
-                            1.0,
-                            1.0 / 2.0,
-                            1.0 / 6.0,
-                            1.0 / 24.0,
-                            1.0 / 120.0,
-                            1.0 / 720.0,
-                            1.0 / 5040.0,
-                            1.0 / 40320.0,
-                            1.0 / 362880.0,
-                            1.0 / 3628800.0,
-                            1.0 / 39916800.0,
-                            1.0 / 479001600.0,
-                            1.0 / 6227020800.0};
-  double p = c[13];
-#pragma unroll
-  for (int n = 12; n >= 0; --n) p = p * r + c[n];
-  return p * __longlong_as_double(static_cast<long long>(static_cast<int>(k) + 1023) << 52);
-}
-
-__device__ __forceinline__ double dot3(const double a[3], double x0, double x1, double x2) { return (a[0] * x0 + a[1] * x1) + a[2] * x2; }
-
-constexpr int ndt_sums(bool G, bool H) { return (G ? 7 : 0) + (H ? 21 : 0); }
-
-// leaves: S arrays of n; pairs: n
+// ---- the evaluation (ndt_internal.h: the table, the pose's rows, the body, the leaves and the read-back) --------------------
 template <bool G, bool H>
 __global__ __launch_bounds__(kThreads) void ndt_eval_kernel(NdtTable T, NdtPose P, const float* __restrict__ sx, const float* __restrict__ sy,
                                                             const float* __restrict__ sz, int n, double* __restrict__ leaves,
                                                             int* __restrict__ pairs) {
-  constexpr int S = ndt_sums(G, H);
-  constexpr int kH0 = G ? 7 : 0;
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  if (i >= n) return;
-  double acc[S];
-#pragma unroll
-  for (int k = 0; k < S; ++k) acc[k] = 0.0;
-  int count = 0;
-  const double x0 = sx[i], x1 = sy[i], x2 = sz[i];
-  const float q[3] = {static_cast<float>(((P.R[0] * x0 + P.R[1] * x1) + P.R[2] * x2) + P.t[0]),
-                      static_cast<float>(((P.R[3] * x0 + P.R[4] * x1) + P.R[5] * x2) + P.t[1]),
-                      static_cast<float>(((P.R[6] * x0 + P.R[7] * x1) + P.R[8] * x2) + P.t[2])};
-  const float f[3] = {floorf(q[0] * T.inv), floorf(q[1] * T.inv), floorf(q[2] * T.inv)};
-  bool live = isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) live = live && f[a] >= -static_cast<float>(kHalf + 1) && f[a] <= static_cast<float>(kHalf);
-  if (live && T.cells > 0) {
-    const int ix = static_cast<int>(f[0]), iy = static_cast<int>(f[1]), iz = static_cast<int>(f[2]);
-    // the point's derivative vectors
-    double Jv[3][3], Hv[6][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int r = 0; r < 3; ++r) Jv[a][r] = (a == 0 && r == 0) ? 0.0 : dot3(P.J[a][r], x0, x1, x2);
-    if constexpr (H) {
-#pragma unroll
-      for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int r = 0; r < 3; ++r) Hv[a][r] = (a < 3 && r == 0) ? 0.0 : dot3(P.H[a][r], x0, x1, x2);
-    }
-    const int xlo = max(ix - 1, -kHalf), xhi = min(ix + 1, kHalf - 1);
-    for (int dz = -1; dz <= 1; ++dz) {
-      const int cz = iz + dz;
-      if (cz < -kHalf || cz >= kHalf) continue;
-      for (int dy = -1; dy <= 1; ++dy) {
-        const int cy = iy + dy;
-        if (cy < -kHalf || cy >= kHalf || xlo > xhi) continue;
-        const unsigned long long klo = ndt_key(xlo, cy, cz), khi = ndt_key(xhi, cy, cz);
-        int lo = 0, hi = T.cells;  // the first cell with key >= klo
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (T.keys[mid] < klo)
-            lo = mid + 1;
-          else
-            hi = mid;
-        }
-        for (int c = lo; c < T.cells && T.keys[c] <= khi; ++c) {
-          const double* cell = T.cell + static_cast<size_t>(c) * kCellDoubles;
-          const double mean[3] = {cell[0], cell[1], cell[2]};
-          const float dx = q[0] - static_cast<float>(mean[0]), dy2 = q[1] - static_cast<float>(mean[1]),
-                      dz2 = q[2] - static_cast<float>(mean[2]);
-          if (!((dx * dx + dy2 * dy2) + dz2 * dz2 <= T.r2)) continue;
-          ++count;
-          const double ic[3][3] = {{cell[3], cell[4], cell[5]}, {cell[4], cell[6], cell[7]}, {cell[5], cell[7], cell[8]}};
-          const double xt[3] = {static_cast<double>(q[0]) - mean[0], static_cast<double>(q[1]) - mean[1],
-                                static_cast<double>(q[2]) - mean[2]};
-          double w[3];
-#pragma unroll
-          for (int r = 0; r < 3; ++r) w[r] = dot3(ic[r], xt[0], xt[1], xt[2]);
-          const double qq = (xt[0] * w[0] + xt[1] * w[1]) + xt[2] * w[2];
-          const double e = ndt_exp(-(T.d2 * qq) * 0.5);
-          double fe = T.d2 * e;
-          if (fe > 1.0 || fe < 0.0 || fe != fe) continue;
-          if constexpr (G) acc[0] += -T.d1 * e;
-          fe = fe * T.d1;
-          double cJ[6][3], u[6];
-#pragma unroll
-          for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r) cJ[a][r] = a < 3 ? ic[r][a] : dot3(ic[r], Jv[a - 3][0], Jv[a - 3][1], Jv[a - 3][2]);
-            u[a] = (xt[0] * cJ[a][0] + xt[1] * cJ[a][1]) + xt[2] * cJ[a][2];
-            if constexpr (G) acc[1 + a] += u[a] * fe;
-          }
-          if constexpr (H) {
-            int slot = kH0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-              for (int b = a; b < 6; ++b) {
-                double h = 0.0;
-                if (a >= 3) {  // b >= a
-                  const int which = a == 3 ? b - 3 : (a == 4 ? b - 1 : 5);
-                  double v[3];
-#pragma unroll
-                  for (int r = 0; r < 3; ++r) v[r] = dot3(ic[r], Hv[which][0], Hv[which][1], Hv[which][2]);
-                  h = (xt[0] * v[0] + xt[1] * v[1]) + xt[2] * v[2];
-                }
-                const double k = b < 3 ? cJ[a][b] : (Jv[b - 3][0] * cJ[a][0] + Jv[b - 3][1] * cJ[a][1]) + Jv[b - 3][2] * cJ[a][2];
-                acc[slot] += fe * ((((-T.d2) * u[a]) * u[b] + h) + k);
-                ++slot;
-              }
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < S; ++k) leaves[static_cast<size_t>(k) * n + i] = acc[k];
-  pairs[i] = count;
+  ndt_eval_body<G, H>(T, P, sx, sy, sz, n, leaves, pairs, static_cast<int>(blockIdx.x));
 }
-
-template <int S>
-struct NdtLeaves {
-  const double* v;
-  const int* pairs;
-  int n;
-  __device__ __forceinline__ void leaf(int i, double out[S], int* count) const {
-    if (i < n) {
-      for (int k = 0; k < S; ++k) out[k] = v[static_cast<size_t>(k) * n + i];
-      *count = pairs[i];
-    } else {
-      for (int k = 0; k < S; ++k) out[k] = 0.0;
-      *count = 0;
-    }
-  }
-};
-
-struct NdtReadback {  // kPinNdtSums
-  double sums[28];
-  long long pairs;
-};
-static_assert(sizeof(NdtReadback) <= kPinNdtSums.bytes, "the read-back fits its region");
 
 template <int S>
 __global__ __launch_bounds__(kTreeThreads) void ndt_finish_kernel(double* partials, const int* __restrict__ counts, int P, int P2,
                                                                   NdtReadback* out, unsigned* done_word, unsigned done_seq) {
-  tree_finish<S>(partials, P, P2);
-  if (threadIdx.x < S) out->sums[threadIdx.x] = partials[threadIdx.x];
-  if (threadIdx.x == 0) {
-    long long n = 0;
-    for (int b = 0; b < P; ++b) n += counts[b];
-    out->pairs = n;
-  }
+  ndt_finish_body<S>(partials, counts, P, P2, out);
   __threadfence_system();
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -423,6 +231,8 @@ void ndt_finish_cell(const double S[9], int min_points, dliom_ndt_cell* cell) {
   cell->valid = 1;
 }
 
+}  // namespace
+
 void ndt_pose(const double p[6], NdtPose* P) {
   const double sa = std::sin(p[3]), ca = std::cos(p[3]), sb = std::sin(p[4]), cb = std::cos(p[4]), sc = std::sin(p[5]),
                cc = std::cos(p[5]);
@@ -461,9 +271,6 @@ void ndt_pose(const double p[6], NdtPose* P) {
   set(P->H[5][2], -(sa * sc) + ca * sb * cc, -(sa * cc) - ca * sb * sc, 0.0);
 }
 
-struct NdtConstants {
-  double d1, d2;
-};
 NdtConstants ndt_constants(const dliom_ndt_options& o) {
   const double c1 = 10.0 * (1.0 - o.outlier_ratio);
   const double c2 = o.outlier_ratio / ((o.resolution * o.resolution) * o.resolution);
@@ -497,104 +304,28 @@ bool ndt_guess_ok(const double* g) {
   return det > 0.0;
 }
 
-struct NdtSums {
-  double score = 0.0, g[6] = {}, H[6][6] = {};
-  long long pairs = 0;
-};
-
-// One evaluation's work on the stream and its read-back.  Events (while timed): before | after the evaluation kernel |
-// after the reduction.
-struct NdtRun {
-  dliom_ndt_target* target;
-  const dliom_cloud* source;
-  NdtConstants k;
-  bool timed = false;
-  std::vector<hipEvent_t> events;
-  int64_t read_backs = 0, with_hessian = 0, without_hessian = 0;
-  ~NdtRun() {
-    for (hipEvent_t e : events) (void)hipEventDestroy(e);
-  }
-  int mark() {
-    if (!timed) return DLIOM_OK;
-    hipEvent_t e = nullptr;
-    DLIOM_HIP_TRY(hipEventCreate(&e));
-    events.push_back(e);
-    DLIOM_HIP_TRY(hipEventRecord(e, target->ctx->stream));
-    return DLIOM_OK;
-  }
-  template <bool G, bool H>
-  int run(const NdtPose& P, NdtSums* out);
-  int evaluate(const double p[6], int what, NdtSums* out) {
-    NdtPose P;
-    ndt_pose(p, &P);
-    if (what == DLIOM_NDT_EVAL_GRADIENT) {
-      ++without_hessian;
-      return run<true, false>(P, out);
-    }
-    ++with_hessian;
-    return what == DLIOM_NDT_EVAL_ALL ? run<true, true>(P, out) : run<false, true>(P, out);
-  }
-};
-
-template <bool G, bool H>
-int NdtRun::run(const NdtPose& P, NdtSums* out) {
-  constexpr int S = ndt_sums(G, H);
-  dliom_ndt_target* const t = target;
-  dliom_ctx* const ctx = t->ctx;
-  const int n = static_cast<int>(source->n);
-  int blocks = 0, P2 = 1;
-  tree_geometry(n, &blocks, &P2);
-  const size_t leaf_bytes = align256(static_cast<size_t>(S) * std::max(n, 1) * sizeof(double));
-  const size_t pair_bytes = align256(4 * static_cast<size_t>(std::max(n, 1)));
-  const size_t partial_bytes = align256(static_cast<size_t>(P2) * S * sizeof(double));
-  DLIOM_TRY(t->scratch.reserve(leaf_bytes + pair_bytes + partial_bytes + align256(4 * static_cast<size_t>(P2))));
-  char* const base = t->scratch.as<char>();
-  double* const leaves = reinterpret_cast<double*>(base);
-  int* const pairs = reinterpret_cast<int*>(base + leaf_bytes);
-  double* const partials = reinterpret_cast<double*>(base + leaf_bytes + pair_bytes);
-  int* const counts = reinterpret_cast<int*>(base + leaf_bytes + pair_bytes + partial_bytes);
+NdtTable ndt_table_of(const dliom_ndt_target* t, const NdtConstants& k) {
   const float res = static_cast<float>(t->resolution);
-  const NdtTable table{t->table.as<unsigned long long>(),
-                       reinterpret_cast<const double*>(t->table.as<char>() + t->cell_data_at),
-                       static_cast<int>(t->n_valid),
-                       1.0f / res,
-                       res * res,
-                       k.d1,
-                       k.d2};
-  DLIOM_TRY(mark());
-  if (n > 0) {
-    hipLaunchKernelGGL((ndt_eval_kernel<G, H>), dim3(blocks_of(n, kThreads)), dim3(kThreads), 0, ctx->stream, table, P, source->d_x,
-                       source->d_y, source->d_z, n, leaves, pairs);
-    DLIOM_HIP_TRY(hipGetLastError());
-  }
-  DLIOM_TRY(mark());
-  const NdtLeaves<S> L{leaves, pairs, n};
-  hipLaunchKernelGGL((tree_reduce_kernel<S, NdtLeaves<S>>), dim3(static_cast<unsigned>(blocks)), dim3(kTreeThreads), 0, ctx->stream, L,
-                     partials, counts);
-  DLIOM_HIP_TRY(hipGetLastError());
-  NdtReadback* const host = pinned_at<NdtReadback>(ctx, kPinNdtSums);
-  const unsigned seq = next_done_seq(ctx);
-  const auto enqueued_at = std::chrono::steady_clock::now();
-  hipLaunchKernelGGL((ndt_finish_kernel<S>), dim3(1), dim3(kTreeThreads), 0, ctx->stream, partials, counts, blocks, P2, host,
-                     ctx->done_word, seq);
-  DLIOM_HIP_TRY(hipGetLastError());
-  DLIOM_TRY(mark());
-  DLIOM_TRY(wait_done(ctx, ctx->stream, ctx->done_word, seq, t->poll_us));
-  const auto took = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - enqueued_at).count();
-  t->poll_us = static_cast<int>(std::min<long long>(std::max<long long>(2 * took, 150), 100000));
-  ++read_backs;
-  const NdtReadback rb = *host;
+  return NdtTable{t->table.as<unsigned long long>(),
+                  reinterpret_cast<const double*>(t->table.as<char>() + t->cell_data_at),
+                  static_cast<int>(t->n_valid),
+                  1.0f / res,
+                  res * res,
+                  k.d1,
+                  k.d2};
+}
+
+void ndt_unpack(const NdtReadback& rb, int what, NdtSums* out) {
   int at = 0;
-  if (G) {
+  if (what != DLIOM_NDT_EVAL_HESSIAN) {
     out->score = rb.sums[0];
     for (int a = 0; a < 6; ++a) out->g[a] = rb.sums[1 + a];
     at = 7;
   }
-  if (H)
+  if (what != DLIOM_NDT_EVAL_GRADIENT)
     for (int a = 0; a < 6; ++a)
       for (int b = a; b < 6; ++b) out->H[a][b] = out->H[b][a] = rb.sums[at++];
   out->pairs = rb.pairs;
-  return DLIOM_OK;
 }
 
 // delta = -pinv(H) g (dliom.h, Alignment 1)
@@ -617,6 +348,90 @@ void ndt_newton_step(const NdtSums& s, double delta[6]) {
     for (int k = 0; k < 6; ++k) v = v + V[r][k] * z[k];
     delta[r] = -v;
   }
+}
+
+namespace {
+
+// One evaluation's work on the stream and its read-back.  Events (while timed): before | after the evaluation kernel |
+// after the reduction.
+struct NdtRun {
+  dliom_ndt_target* target;
+  const dliom_cloud* source;
+  NdtConstants k;
+  bool timed = false;
+  std::vector<hipEvent_t> events;
+  int64_t read_backs = 0;
+  ~NdtRun() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  }
+  int mark() {
+    if (!timed) return DLIOM_OK;
+    hipEvent_t e = nullptr;
+    DLIOM_HIP_TRY(hipEventCreate(&e));
+    events.push_back(e);
+    DLIOM_HIP_TRY(hipEventRecord(e, target->ctx->stream));
+    return DLIOM_OK;
+  }
+  template <bool G, bool H>
+  int run(const NdtPose& P, NdtReadback* out);
+  // *out keeps what this kind of evaluation does not compute
+  int evaluate(const double p[6], int what, NdtSums* out) {
+    NdtPose P;
+    ndt_pose(p, &P);
+    NdtReadback rb;
+    if (what == DLIOM_NDT_EVAL_GRADIENT)
+      DLIOM_TRY((run<true, false>(P, &rb)));
+    else if (what == DLIOM_NDT_EVAL_ALL)
+      DLIOM_TRY((run<true, true>(P, &rb)));
+    else
+      DLIOM_TRY((run<false, true>(P, &rb)));
+    ndt_unpack(rb, what, out);
+    return DLIOM_OK;
+  }
+};
+
+template <bool G, bool H>
+int NdtRun::run(const NdtPose& P, NdtReadback* out) {
+  constexpr int S = ndt_sums(G, H);
+  dliom_ndt_target* const t = target;
+  dliom_ctx* const ctx = t->ctx;
+  const int n = static_cast<int>(source->n);
+  int blocks = 0, P2 = 1;
+  tree_geometry(n, &blocks, &P2);
+  const size_t leaf_bytes = align256(static_cast<size_t>(S) * std::max(n, 1) * sizeof(double));
+  const size_t pair_bytes = align256(4 * static_cast<size_t>(std::max(n, 1)));
+  const size_t partial_bytes = align256(static_cast<size_t>(P2) * S * sizeof(double));
+  DLIOM_TRY(t->scratch.reserve(leaf_bytes + pair_bytes + partial_bytes + align256(4 * static_cast<size_t>(P2))));
+  char* const base = t->scratch.as<char>();
+  double* const leaves = reinterpret_cast<double*>(base);
+  int* const pairs = reinterpret_cast<int*>(base + leaf_bytes);
+  double* const partials = reinterpret_cast<double*>(base + leaf_bytes + pair_bytes);
+  int* const counts = reinterpret_cast<int*>(base + leaf_bytes + pair_bytes + partial_bytes);
+  const NdtTable table = ndt_table_of(t, k);
+  DLIOM_TRY(mark());
+  if (n > 0) {
+    hipLaunchKernelGGL((ndt_eval_kernel<G, H>), dim3(blocks_of(n, kThreads)), dim3(kThreads), 0, ctx->stream, table, P, source->d_x,
+                       source->d_y, source->d_z, n, leaves, pairs);
+    DLIOM_HIP_TRY(hipGetLastError());
+  }
+  DLIOM_TRY(mark());
+  const NdtLeaves<S> L{leaves, pairs, n};
+  hipLaunchKernelGGL((tree_reduce_kernel<S, NdtLeaves<S>>), dim3(static_cast<unsigned>(blocks)), dim3(kTreeThreads), 0, ctx->stream, L,
+                     partials, counts);
+  DLIOM_HIP_TRY(hipGetLastError());
+  NdtReadback* const host = pinned_at<NdtReadback>(ctx, kPinNdtSums);
+  const unsigned seq = next_done_seq(ctx);
+  const auto enqueued_at = std::chrono::steady_clock::now();
+  hipLaunchKernelGGL((ndt_finish_kernel<S>), dim3(1), dim3(kTreeThreads), 0, ctx->stream, partials, counts, blocks, P2, host,
+                     ctx->done_word, seq);
+  DLIOM_HIP_TRY(hipGetLastError());
+  DLIOM_TRY(mark());
+  DLIOM_TRY(wait_done(ctx, ctx->stream, ctx->done_word, seq, t->poll_us));
+  const auto took = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - enqueued_at).count();
+  t->poll_us = static_cast<int>(std::min<long long>(std::max<long long>(2 * took, 150), 100000));
+  ++read_backs;
+  *out = *host;
+  return DLIOM_OK;
 }
 
 inline double min_of(double a, double b) { return b < a ? b : a; }
@@ -682,55 +497,6 @@ double dot6(const double a[6], const double b[6]) {
   return v;
 }
 
-// dliom.h, Step length.  sums: in, those at p; out, those of the step's last evaluation.  dir may come back negated.
-int ndt_step_length(NdtRun* run, const double p[6], double dir[6], double step_init, const dliom_ndt_options& o, NdtSums* sums,
-                    double* a_out) {
-  const double step_max = o.step_size, step_min = o.transformation_epsilon / 2.0;
-  const double phi0 = -sums->score;
-  double dphi0 = -dot6(sums->g, dir);
-  *a_out = 0.0;
-  if (dphi0 == 0.0) return DLIOM_OK;
-  if (dphi0 > 0.0) {
-    dphi0 = -dphi0;
-    for (int r = 0; r < 6; ++r) dir[r] = -dir[r];
-  }
-  double a_t = max_of(min_of(step_init, step_max), step_min);
-  double x[6];
-  for (int r = 0; r < 6; ++r) x[r] = p[r] + dir[r] * a_t;
-  DLIOM_TRY(run->evaluate(x, DLIOM_NDT_EVAL_ALL, sums));
-  *a_out = a_t;
-  if (o.step_mode == DLIOM_NDT_STEP_CLAMPED) return DLIOM_OK;
-  const double mu = 1e-4, nu = 0.9;
-  double a_l = 0.0, a_u = 0.0, f_l = 0.0, f_u = 0.0, g_l = dphi0 - mu * dphi0, g_u = dphi0 - mu * dphi0;
-  bool open = true, interval_converged = false;
-  double phi_t = -sums->score, dphi_t = -dot6(sums->g, dir);
-  double psi_t = (phi_t - phi0) - (mu * dphi0) * a_t, dpsi_t = dphi_t - mu * dphi0;
-  int trials = 0;
-  while (!interval_converged && trials < 10 && !(psi_t <= 0.0 && dphi_t <= -nu * dphi0)) {
-    a_t = open ? mt_trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, dpsi_t) : mt_trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, dphi_t);
-    a_t = max_of(min_of(a_t, step_max), step_min);
-    for (int r = 0; r < 6; ++r) x[r] = p[r] + dir[r] * a_t;
-    DLIOM_TRY(run->evaluate(x, DLIOM_NDT_EVAL_GRADIENT, sums));
-    phi_t = -sums->score;
-    dphi_t = -dot6(sums->g, dir);
-    psi_t = (phi_t - phi0) - (mu * dphi0) * a_t;
-    dpsi_t = dphi_t - mu * dphi0;
-    if (open && psi_t <= 0.0 && dpsi_t >= 0.0) {
-      open = false;
-      f_l = (f_l + phi0) - (mu * dphi0) * a_l;
-      g_l = g_l + mu * dphi0;
-      f_u = (f_u + phi0) - (mu * dphi0) * a_u;
-      g_u = g_u + mu * dphi0;
-    }
-    interval_converged = open ? mt_update(&a_l, &f_l, &g_l, &a_u, &f_u, &g_u, a_t, psi_t, dpsi_t)
-                              : mt_update(&a_l, &f_l, &g_l, &a_u, &f_u, &g_u, a_t, phi_t, dphi_t);
-    ++trials;
-  }
-  if (trials > 0) DLIOM_TRY(run->evaluate(x, DLIOM_NDT_EVAL_HESSIAN, sums));
-  *a_out = a_t;
-  return DLIOM_OK;
-}
-
 void ndt_pose_of_guess(const double* g, double p[6]) {
   p[0] = g[3];
   p[1] = g[7];
@@ -747,6 +513,159 @@ bool ndt_call_ok(const dliom_ndt_target* target, const dliom_cloud* source, cons
 }
 
 }  // namespace
+
+// ---- dliom.h's ALIGNMENT and STEP LENGTH, between evaluations (ndt_internal.h) ----------------------------------------------
+void NdtAlignment::ask(int what, NdtRequest* next) {
+  if (what == DLIOM_NDT_EVAL_GRADIENT)
+    ++without_hessian_;
+  else
+    ++with_hessian_;
+  next->what = what;
+}
+
+void NdtAlignment::start(const dliom_ndt_options& options, const double guess16[16], NdtRequest* first) {
+  *this = NdtAlignment();
+  o_ = options;
+  ndt_pose_of_guess(guess16, p_);
+  std::memcpy(first->p, p_, sizeof(p_));
+  ask(DLIOM_NDT_EVAL_ALL, first);
+  phase_ = kGuess;
+}
+
+bool NdtAlignment::advance(const NdtSums& sums, NdtRequest* next) {
+  const double mu = 1e-4;
+  sums_ = sums;
+  switch (phase_) {
+    case kGuess:
+      return begin_iteration(next);
+    case kFirstTrial:  // the clamped first trial's evaluation, with the Hessian
+      if (o_.step_mode == DLIOM_NDT_STEP_CLAMPED) return end_step(a_t_, next);
+      a_l_ = a_u_ = f_l_ = f_u_ = 0.0;
+      g_l_ = g_u_ = dphi0_ - mu * dphi0_;
+      open_ = true;
+      interval_converged_ = false;
+      phi_t_ = -sums_.score;
+      dphi_t_ = -dot6(sums_.g, dir_);
+      psi_t_ = (phi_t_ - phi0_) - (mu * dphi0_) * a_t_;
+      dpsi_t_ = dphi_t_ - mu * dphi0_;
+      trials_ = 0;
+      return more_trials(next);
+    case kTrial:  // a trial's evaluation, without the Hessian
+      phi_t_ = -sums_.score;
+      dphi_t_ = -dot6(sums_.g, dir_);
+      psi_t_ = (phi_t_ - phi0_) - (mu * dphi0_) * a_t_;
+      dpsi_t_ = dphi_t_ - mu * dphi0_;
+      if (open_ && psi_t_ <= 0.0 && dpsi_t_ >= 0.0) {
+        open_ = false;
+        f_l_ = (f_l_ + phi0_) - (mu * dphi0_) * a_l_;
+        g_l_ = g_l_ + mu * dphi0_;
+        f_u_ = (f_u_ + phi0_) - (mu * dphi0_) * a_u_;
+        g_u_ = g_u_ + mu * dphi0_;
+      }
+      interval_converged_ = open_ ? mt_update(&a_l_, &f_l_, &g_l_, &a_u_, &f_u_, &g_u_, a_t_, psi_t_, dpsi_t_)
+                                  : mt_update(&a_l_, &f_l_, &g_l_, &a_u_, &f_u_, &g_u_, a_t_, phi_t_, dphi_t_);
+      ++trials_;
+      return more_trials(next);
+    case kHessianOnly:
+      return end_step(a_t_, next);
+    case kDone:
+      break;
+  }
+  return false;
+}
+
+// Alignment 1 to 3, up to the step's first evaluation
+bool NdtAlignment::begin_iteration(NdtRequest* next) {
+  for (;;) {
+    double delta[6];
+    ndt_newton_step(sums_, delta);
+    const double s = std::sqrt(dot6(delta, delta));
+    if (s == 0.0 || s != s) {
+      converged_ = s == s ? 1 : 0;
+      reason_ = DLIOM_NDT_ZERO_STEP;
+      iterations_ = it_;
+      phase_ = kDone;
+      return false;
+    }
+    for (int r = 0; r < 6; ++r) dir_[r] = delta[r] / s;
+    const double step_max = o_.step_size, step_min = o_.transformation_epsilon / 2.0;
+    phi0_ = -sums_.score;
+    dphi0_ = -dot6(sums_.g, dir_);
+    if (dphi0_ == 0.0) {  // a step of length 0: nothing is evaluated
+      if (moved_and_done(0.0)) return false;
+      continue;
+    }
+    if (dphi0_ > 0.0) {
+      dphi0_ = -dphi0_;
+      for (int r = 0; r < 6; ++r) dir_[r] = -dir_[r];
+    }
+    a_t_ = max_of(min_of(s, step_max), step_min);
+    for (int r = 0; r < 6; ++r) x_[r] = p_[r] + dir_[r] * a_t_;
+    std::memcpy(next->p, x_, sizeof(x_));
+    ask(DLIOM_NDT_EVAL_ALL, next);
+    phase_ = kFirstTrial;
+    return true;
+  }
+}
+
+// the More-Thuente loop's test and the next trial; behind the loop the Hessian-only evaluation, if any trial ran
+bool NdtAlignment::more_trials(NdtRequest* next) {
+  const double nu = 0.9;
+  const double step_max = o_.step_size, step_min = o_.transformation_epsilon / 2.0;
+  if (!interval_converged_ && trials_ < 10 && !(psi_t_ <= 0.0 && dphi_t_ <= -nu * dphi0_)) {
+    a_t_ = open_ ? mt_trial(a_l_, f_l_, g_l_, a_u_, f_u_, g_u_, a_t_, psi_t_, dpsi_t_)
+                 : mt_trial(a_l_, f_l_, g_l_, a_u_, f_u_, g_u_, a_t_, phi_t_, dphi_t_);
+    a_t_ = max_of(min_of(a_t_, step_max), step_min);
+    for (int r = 0; r < 6; ++r) x_[r] = p_[r] + dir_[r] * a_t_;
+    std::memcpy(next->p, x_, sizeof(x_));
+    ask(DLIOM_NDT_EVAL_GRADIENT, next);
+    phase_ = kTrial;
+    return true;
+  }
+  if (trials_ > 0) {
+    std::memcpy(next->p, x_, sizeof(x_));
+    ask(DLIOM_NDT_EVAL_HESSIAN, next);
+    phase_ = kHessianOnly;
+    return true;
+  }
+  return end_step(a_t_, next);
+}
+
+// Alignment 3 (the move) to 5
+bool NdtAlignment::end_step(double a, NdtRequest* next) { return moved_and_done(a) ? false : begin_iteration(next); }
+
+bool NdtAlignment::moved_and_done(double a) {
+  for (int r = 0; r < 6; ++r) p_[r] = p_[r] + dir_[r] * a;
+  if (it_ > o_.maximum_iterations || (it_ > 0 && std::fabs(a) < o_.transformation_epsilon)) {
+    converged_ = 1;
+    reason_ = it_ > o_.maximum_iterations ? DLIOM_NDT_ITERATIONS : DLIOM_NDT_EPSILON;
+    iterations_ = it_ + 1;
+    phase_ = kDone;
+    return true;
+  }
+  ++it_;
+  return false;
+}
+
+void NdtAlignment::finish(int64_t n, dliom_ndt_result* res, NdtPose* P) const {
+  res->converged = converged_;
+  res->reason = reason_;
+  res->iterations = iterations_;
+  std::memcpy(res->p, p_, sizeof(p_));
+  ndt_pose(p_, P);
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) res->transform[4 * a + b] = P->R[3 * a + b];
+    res->transform[4 * a + 3] = P->t[a];
+  }
+  res->transform[12] = res->transform[13] = res->transform[14] = 0.0;
+  res->transform[15] = 1.0;
+  res->score = sums_.score;
+  res->transformation_probability = sums_.score / static_cast<double>(n);
+  res->pairs = sums_.pairs;
+  res->evaluations_with_hessian = with_hessian_;
+  res->evaluations_without_hessian = without_hessian_;
+}
+
 }  // namespace dliom
 
 extern "C" {
@@ -935,45 +854,16 @@ int dliom_ndt_align(dliom_ndt_target* target, const dliom_cloud* source, const d
   NdtRun run{target, source, ndt_constants(*options)};
   run.timed = ctx->profiling;
   const auto started = std::chrono::steady_clock::now();
-  double p[6];
-  ndt_pose_of_guess(guess16, p);
+  NdtAlignment machine;
+  NdtRequest request;
   NdtSums sums;
-  DLIOM_TRY(run.evaluate(p, DLIOM_NDT_EVAL_ALL, &sums));
-  for (int it = 0;; ++it) {
-    double delta[6], dir[6];
-    ndt_newton_step(sums, delta);
-    const double s = std::sqrt(dot6(delta, delta));
-    if (s == 0.0 || s != s) {
-      res.converged = s == s ? 1 : 0;
-      res.reason = DLIOM_NDT_ZERO_STEP;
-      res.iterations = it;
-      break;
-    }
-    for (int r = 0; r < 6; ++r) dir[r] = delta[r] / s;
-    double a = 0.0;
-    DLIOM_TRY(ndt_step_length(&run, p, dir, s, *options, &sums, &a));
-    for (int r = 0; r < 6; ++r) p[r] = p[r] + dir[r] * a;
-    if (it > options->maximum_iterations || (it > 0 && std::fabs(a) < options->transformation_epsilon)) {
-      res.converged = 1;
-      res.reason = it > options->maximum_iterations ? DLIOM_NDT_ITERATIONS : DLIOM_NDT_EPSILON;
-      res.iterations = it + 1;
-      break;
-    }
-  }
+  machine.start(*options, guess16, &request);
+  do {
+    DLIOM_TRY(run.evaluate(request.p, request.what, &sums));
+  } while (machine.advance(sums, &request));
   const double loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count();
-  std::memcpy(res.p, p, sizeof(p));
   NdtPose P;
-  ndt_pose(p, &P);
-  for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 3; ++b) res.transform[4 * a + b] = P.R[3 * a + b];
-    res.transform[4 * a + 3] = P.t[a];
-  }
-  res.transform[15] = 1.0;
-  res.score = sums.score;
-  res.transformation_probability = sums.score / static_cast<double>(n);
-  res.pairs = sums.pairs;
-  res.evaluations_with_hessian = run.with_hessian;
-  res.evaluations_without_hessian = run.without_hessian;
+  machine.finish(n, &res, &P);
   res.read_backs = run.read_backs;
   if (!run.events.empty()) {
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -22,6 +22,10 @@
 //  * kPinNdtSums belongs to an alignment or an evaluation of ndt.hip, entry points of their own: one read-back an
 //    evaluation, copied out before the next launch.  The fitness score at an alignment's end is ICP's (kPinIcpSums); the
 //    target's creation and the aligned cloud's norm read a few words through kPinReadback;
+//  * kPinNdtBatchReadback and kPinNdtBatchTable belong to a batched NDT alignment (ndt_batch.hip), an entry point of its own
+//    that runs no single alignment and no batched ICP alignment (whose regions it lies over): every lock-step round it
+//    fills the table with the descriptors of the pairs in flight before its launches and has copied the pairs' read-back
+//    slots out before it writes the table again or returns;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -88,6 +92,13 @@ constexpr PinRegion kPinIcpBatchTable{65536, kPinIcpBatchPairs * kPinIcpBatchEnt
 // an NDT evaluation (ndt.hip): up to 28 sums and the pair count
 constexpr PinRegion kPinNdtSums{4096 + 256, 256};
 
+// a batched NDT alignment (ndt_batch.hip): a read-back slot for every pair that may be in flight
+// (DLIOM_NDT_BATCH_MAX_PAIRS) -- an evaluation's NdtReadback or a final round's IcpReadback -- and the round's upload, a
+// descriptor for each of them (the table, the pose's rows, the arrays; in a final round the search's item)
+constexpr size_t kPinNdtBatchPairs = 256, kPinNdtBatchSlotBytes = 256, kPinNdtBatchEntryBytes = 1024;
+constexpr PinRegion kPinNdtBatchReadback{8192, kPinNdtBatchPairs * kPinNdtBatchSlotBytes};
+constexpr PinRegion kPinNdtBatchTable{131072, kPinNdtBatchPairs * kPinNdtBatchEntryBytes};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -139,6 +150,9 @@ static_assert(pins_inside({kPinIcpBatchReadback, kPinIcpBatchTable}, kPinnedByte
               "a batched ICP alignment's regions");
 static_assert(pins_inside({kPinNdtSums}, kPinnedBytes) && pins_disjoint({kPinNdtSums, kPinIcpSums, kPinReadback}),
               "an NDT alignment's regions (its fitness score is ICP's)");
+static_assert(pins_inside({kPinNdtBatchReadback, kPinNdtBatchTable}, kPinnedBytes) &&
+                  pins_disjoint({kPinNdtBatchReadback, kPinNdtBatchTable, kPinReadback, kPinIcpSums, kPinNdtSums}),
+              "a batched NDT alignment's regions");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

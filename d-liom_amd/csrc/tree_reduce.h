@@ -36,7 +36,7 @@ __device__ __forceinline__ void tree_subtree(const Leaves& L, int first, double 
 }
 
 // One workgroup's subtree: the 2048 leaves from block * 2048, into partials[block * S ..) and counts[block].  Called by every
-// lane of a kTreeThreads workgroup (tree_reduce_kernel; icp_batch.hip's kernel, where the block is one of a pair's)
+// lane of a kTreeThreads workgroup (tree_reduce_kernel; icp_batch.hip's and ndt_batch.hip's kernels, where the block is one of a pair's)
 template <int S, class Leaves>
 __device__ __forceinline__ void tree_reduce_block(const Leaves& L, int block, double* __restrict__ partials, int* __restrict__ counts) {
   __shared__ double lds[kTreeThreads * S];

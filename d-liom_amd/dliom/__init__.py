@@ -3745,6 +3745,98 @@ class Ndt:
                 cloud.close()
 
 
+# many pairs in one call (dliom_ndt_align_batch): the ground-truth tool's loop under `--method ndt`
+NDT_BATCH_MAX_PAIRS, NDT_BATCH_DEFAULT_POINTS = 256, 64 * 1024
+
+
+class NdtPair(C.Structure):
+    _fields_ = [("target", _vp), ("source", _vp), ("fitness_index", _vp), ("guess", C.c_double * 16)]
+
+
+class NdtBatchLimits(C.Structure):
+    _fields_ = [("max_pairs_in_flight", C.c_int), ("reserved", C.c_int), ("max_scratch_bytes", C.c_int64)]
+
+
+class NdtBatchStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("pairs", "chunks", "steps", "read_backs", "synchronizations", "max_in_flight",
+                                         "pair_evaluations", "pair_searches")] + \
+               [("evaluation_launches", C.c_int64 * 3), ("mixed_steps", C.c_int64)] + \
+               [(f, C.c_double) for f in ("evaluate_ms", "reduce_ms", "fitness_ms", "host_ms")]
+
+
+SYMBOLS += [
+    ("dliom_ndt_batch_default_limits", C.c_int, [C.POINTER(NdtBatchLimits)]),
+    ("dliom_ndt_batch_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("dliom_ndt_align_batch", C.c_int, [_vp, C.POINTER(NdtPair), C.c_int, C.POINTER(NdtOptions), C.POINTER(NdtBatchLimits),
+                                        C.POINTER(NdtResult), C.POINTER(_vp), C.POINTER(NdtBatchStats)]),
+]
+
+
+def ndt_batch_default_limits(**overrides):
+    """dliom_ndt_batch_default_limits, with fields replaced"""
+    lim = NdtBatchLimits()
+    _check(load_library().dliom_ndt_batch_default_limits(C.byref(lim)), "dliom_ndt_batch_default_limits")
+    for k, v in overrides.items():
+        if k not in dict(NdtBatchLimits._fields_):
+            raise TypeError("no NDT batch limit " + k)
+        setattr(lim, k, v)
+    return lim
+
+
+def ndt_batch_scratch_bytes(n):
+    """the device scratch one pair in flight with n source points reserves (host only)"""
+    return int(load_library().dliom_ndt_batch_scratch_bytes(int(n)))
+
+
+def ndt_align_batch(ctx, pairs, options=None, limits=None, want_aligned=False):
+    """dliom_ndt_align_batch.  pairs: a list of (NdtTarget, PointCloud or (n, 3) array, guess 4x4 or None[, NnIndex or
+    None]).  -> (results, stats) or (results, stats, clouds): results as Ndt.align gives them, pair by pair and bit for bit
+    (read_backs: the pair's rounds); stats a dict (evaluation_launches: a list by NDT_EVAL_*); clouds the aligned points,
+    (n, 3) float32 each."""
+    L = ctx._L
+    options = options if options is not None else ndt_options()
+    count = len(pairs)
+    table, made = (NdtPair * max(count, 1))(), []
+    handles = (_vp * max(count, 1))()
+    try:
+        uploaded = {}  # one upload for an array that several pairs name
+        for i, pair in enumerate(pairs):
+            target, source, guess = pair[:3]
+            index = pair[3] if len(pair) > 3 else None
+            if isinstance(source, PointCloud):
+                cloud = source
+            elif id(source) in uploaded:
+                cloud = uploaded[id(source)]
+            else:
+                cloud = uploaded[id(source)] = PointCloud(ctx, source)
+                made.append(cloud)
+            table[i].target, table[i].source = target.h, cloud.h
+            table[i].fitness_index = None if index is None else index.h
+            table[i].guess[:] = list(_f64(np.eye(4) if guess is None else guess).reshape(16))
+        results, stats = (NdtResult * max(count, 1))(), NdtBatchStats()
+        _check(L.dliom_ndt_align_batch(ctx.h, table, count, C.byref(options), None if limits is None else C.byref(limits),
+                                       results, handles if want_aligned else None, C.byref(stats)), "dliom_ndt_align_batch")
+        out = [_ndt_result(results[i]) for i in range(count)]
+        st = {k: (list(getattr(stats, k)) if k == "evaluation_launches" else getattr(stats, k)) for k, _ in NdtBatchStats._fields_}
+        if not want_aligned:
+            return out, st
+        clouds = []
+        for i in range(count):
+            aligned = PointCloud(ctx, _handle=_vp(handles[i]))
+            handles[i] = None
+            try:
+                clouds.append(aligned.download())
+            finally:
+                aligned.close()
+        return out, st, clouds
+    finally:
+        for i in range(count):
+            if want_aligned and handles[i]:
+                L.dliom_cloud_destroy(_vp(handles[i]))
+        for cloud in made:
+            cloud.close()
+
+
 # ---- the approximate voxel grid and MatchByNDT over a stream of scans (include/dliom.h) ------------------------------------
 SYMBOLS += [
     ("dliom_cloud_approximate_voxel_filter", C.c_int, [_vp, _vp, C.c_float, C.POINTER(_vp)]),

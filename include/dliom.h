@@ -2613,6 +2613,75 @@ int dliom_ndt_scan_matcher_match(dliom_ndt_scan_matcher* matcher, const dliom_cl
 /* *has_target: 1 once a match has succeeded (the matcher holds a scan's cells and the next match writes a result), else 0. */
 int dliom_ndt_scan_matcher_has_target(const dliom_ndt_scan_matcher* matcher, int* has_target);
 
+/* Many pairs in one call: the `--method ndt` half of the loop of gen_ground_truth_by_ndt_match.cc:151-261 (:211-222), as
+ * dliom_icp_align_batch is its `--method icp` half.  All pairs of a chunk advance in lock step: a round is the next
+ * evaluation of every pair still aligning -- at most one launch per kind of evaluation (DLIOM_NDT_EVAL_*) present among
+ * them -- and the FINAL ROUND of every pair whose alignment ended in the round before (the final points, the fitness
+ * search when the pair has an index, the aligned cloud's norm bound when the clouds are wanted), in ONE launch chain with
+ * ONE polled read-back, whatever the number of pairs.  The host decisions between the rounds are those of ALIGNMENT and
+ * STEP LENGTH above, pair by pair.
+ *
+ * Options.  One `options` serves the call; its resolution must be every target's, as dliom_ndt_align demands.  Either step
+ * mode.
+ *
+ * Results.  results[i] is what dliom_ndt_align(pairs[i].target, pairs[i].source, pairs[i].guess, options,
+ * pairs[i].fitness_index, ...) returns, bit for bit, in converged, reason, iterations, both evaluation counts, p,
+ * transform, score, transformation_probability, fitness_score, fitness_count and pairs.  read_backs of a result is the
+ * number of rounds the pair took part in: its evaluations, plus one final round if it has a fitness index or the clouds
+ * are wanted.  The batch reads the aligned cloud's norm bound back in the final round's slot, where the single call
+ * spends a read-back of its own on it, so this field is ONE LESS than the single call's for a pair that has a fitness
+ * index, a non-empty source and a wanted cloud; it is one more for a pair with an empty source, no index and a wanted
+ * cloud (the single call reads nothing back for it), and equal otherwise.  The three *_ms fields of a result are 0; the stages'
+ * times are in the statistics.  aligned[i] is the single call's cloud, norm bound included.  Results never depend on the
+ * limits, on the order of the pairs, or on which other pairs share a chunk.
+ *
+ * Schedule.  Chunks are consecutive runs of pairs in input order.  A chunk closes when it holds max_pairs_in_flight pairs,
+ * or when adding the next pair's dliom_ndt_batch_scratch_bytes(n) would take the chunk's sum above max_scratch_bytes; it
+ * always holds at least one pair.  Chunks are not refilled: a chunk takes as many rounds as the pair of it with the most
+ * rounds, `steps` is the sum over the chunks, and read_backs == steps.  The default scratch budget holds
+ * max_pairs_in_flight = 64 pairs of DLIOM_NDT_BATCH_DEFAULT_POINTS source points: 64 *
+ * dliom_ndt_batch_scratch_bytes(65536) = 1 091 354 624 bytes (the leaves of an evaluation alone are 28 doubles a point).
+ *
+ * Refusals, all before anything runs (DLIOM_ERR_INVALID_ARGUMENT): a NULL context or options; NULL pairs or results
+ * with count > 0; count < 0; options that dliom_ndt_align refuses; limits outside their ranges; a pair with a NULL target
+ * or source, with a target, a cloud or an index of another context, with a guess that dliom_ndt_align refuses, or with
+ * a target whose resolution is not the options'.  count == 0 succeeds and launches nothing.  A HIP or allocation failure
+ * fails the whole call and leaves no cloud behind (every aligned[i] is NULL).  There is no per-pair status. */
+#define DLIOM_NDT_BATCH_MAX_PAIRS 256
+#define DLIOM_NDT_BATCH_DEFAULT_POINTS (64 * 1024)
+typedef struct dliom_ndt_pair {
+  dliom_ndt_target* target;        /* any number of pairs may name one target */
+  const dliom_cloud* source;       /* any number of pairs may name one cloud */
+  dliom_nn_index* fitness_index;   /* may be NULL, as in dliom_ndt_align */
+  double guess[16];                /* as dliom_ndt_align's guess16 */
+} dliom_ndt_pair;
+typedef struct dliom_ndt_batch_limits {
+  int max_pairs_in_flight;         /* 1 .. DLIOM_NDT_BATCH_MAX_PAIRS; default 64 */
+  int reserved;                    /* 0 */
+  int64_t max_scratch_bytes;       /* > 0; default 64 * dliom_ndt_batch_scratch_bytes(DLIOM_NDT_BATCH_DEFAULT_POINTS) */
+} dliom_ndt_batch_limits;          /* NULL = the defaults, which dliom_ndt_batch_default_limits() returns */
+typedef struct dliom_ndt_batch_stats {
+  int64_t pairs, chunks, steps;    /* steps: lock-step rounds */
+  int64_t read_backs;              /* polled read-backs of the call == steps */
+  int64_t synchronizations;        /* stream synchronisations of the call: one a chunk when `aligned` is given (its clouds are
+                                      copied out of the chunk's scratch), one for the stages' times while profiling is on */
+  int64_t max_in_flight;           /* the largest chunk */
+  int64_t pair_evaluations;        /* sum over the results of both evaluation counts */
+  int64_t pair_searches;           /* final rounds, summed over the pairs */
+  int64_t evaluation_launches[3];  /* by DLIOM_NDT_EVAL_* kind: one a round in which a pair with a non-empty source
+                                      evaluates that kind (a kind's list goes in several launches only beyond 2^22 workgroups) */
+  int64_t mixed_steps;             /* rounds that launched more than one kind of evaluation, or an evaluation beside a
+                                      final round */
+  double evaluate_ms, reduce_ms, fitness_ms, host_ms;  /* upload and evaluations | their reductions | the final rounds'
+                                      chain | the host's decisions and tables; only while the context's profiling is on */
+} dliom_ndt_batch_stats;
+int dliom_ndt_batch_default_limits(dliom_ndt_batch_limits* limits);
+/* Host only: the device scratch that one pair in flight with source_points points reserves (0 for a negative count). */
+int64_t dliom_ndt_batch_scratch_bytes(int64_t source_points);
+int dliom_ndt_align_batch(dliom_ctx* ctx, const dliom_ndt_pair* pairs, int count, const dliom_ndt_options* options,
+                          const dliom_ndt_batch_limits* limits, dliom_ndt_result* results,
+                          dliom_cloud** aligned /* NULL, or count entries */, dliom_ndt_batch_stats* stats /* may be NULL */);
+
 /* Kernel timing (HIP events on the context's stream). */
 enum {
   DLIOM_KERNEL_RTCSM_SCORE = 0, /* score-volume kernel (dominant) */
