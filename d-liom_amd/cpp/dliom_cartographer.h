@@ -4046,11 +4046,28 @@ class NormalDistributionsTransform {
   dliom_nn_index* index_ = nullptr;
 };
 
+// Many NDT targets in one call (dliom_ndt_target_create_batch): what NormalDistributionsTransform::setInputTarget builds
+// cloud by cloud with `ndt_options`, cell for cell and bit for bit, in one device chain a chunk.  clouds: clouds of the
+// context, none empty; a cloud may be named more than once.  -> a target a cloud, the caller's to destroy
+// (dliom_ndt_target_destroy), each on its own.  limits: NULL = the defaults.  stats (may be null): the call's.
+inline std::vector<dliom_ndt_target*> BuildNdtTargets(Context* context, const dliom_ndt_options& ndt_options,
+                                                      const std::vector<const dliom_cloud*>& clouds,
+                                                      const dliom_ndt_target_batch_limits* limits = nullptr,
+                                                      dliom_ndt_target_batch_stats* stats = nullptr) {
+  std::vector<dliom_ndt_target*> targets(clouds.size(), nullptr);
+  dliom_ndt_target* none = nullptr;
+  Check(dliom_ndt_target_create_batch(context->get(), clouds.data(), static_cast<int>(clouds.size()), &ndt_options, limits,
+                                      targets.empty() ? &none : targets.data(), stats),
+        "dliom_ndt_target_create_batch");
+  return targets;
+}
+
 // Many NDT alignments in one call (dliom_ndt_align_batch): the pairs of the tool's loop under --method ndt.  What
 // NormalDistributionsTransform with `ndt_options` gives pair by pair (setInputSource, setInputTarget(target, with_fitness),
 // align(guess), result()), bit for bit but for read_backs (dliom.h).  ONE dliom_ndt_target is built per distinct target
-// pointer -- and with with_fitness ONE nearest-neighbour index for getFitnessScore() -- and one cloud uploaded per distinct
-// source pointer, however many pairs name them; everything is destroyed on every way out.  limits: NULL = the defaults.
+// pointer, all of them in ONE call (BuildNdtTargets) -- and with with_fitness ONE nearest-neighbour index for
+// getFitnessScore() -- and one cloud uploaded per distinct source pointer, however many pairs name them; everything is
+// destroyed on every way out.  limits: NULL = the defaults.
 // aligned (may be null): every pair's source under its final transformation.  stats (may be null): the call's.
 inline std::vector<dliom_ndt_result> AlignPairsNdt(Context* context, const dliom_ndt_options& ndt_options,
                                                    const std::vector<AlignmentPair>& pairs, bool with_fitness = true,
@@ -4061,11 +4078,12 @@ inline std::vector<dliom_ndt_result> AlignPairsNdt(Context* context, const dliom
     std::map<const sensor::PointCloud*, dliom_ndt_target*> targets;
     std::map<const sensor::PointCloud*, dliom_nn_index*> indices;
     std::map<const sensor::PointCloud*, dliom_cloud*> sources;
-    std::vector<dliom_cloud*> outputs;
+    std::vector<dliom_cloud*> target_clouds, outputs;
     ~Owned() {
       for (auto& e : targets) dliom_ndt_target_destroy(e.second);
       for (auto& e : indices) dliom_nn_index_destroy(e.second);
       for (auto& e : sources) dliom_cloud_destroy(e.second);
+      for (dliom_cloud* c : target_clouds) dliom_cloud_destroy(c);
       for (dliom_cloud* c : outputs) dliom_cloud_destroy(c);
     }
   } owned;
@@ -4075,23 +4093,33 @@ inline std::vector<dliom_ndt_result> AlignPairsNdt(Context* context, const dliom
           "dliom_cloud_create");
     return out;
   };
+  // the distinct target clouds, in the order of their first mention: uploaded, their cells built in one call, then their indices
+  std::vector<const sensor::PointCloud*> distinct;
+  for (const AlignmentPair& p : pairs) {
+    if (p.source == nullptr || p.target == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "AlignPairsNdt: a pair without a cloud");
+    if (std::find(distinct.begin(), distinct.end(), p.target) == distinct.end()) distinct.push_back(p.target);
+  }
+  for (const sensor::PointCloud* cloud : distinct) {
+    owned.target_clouds.push_back(nullptr);
+    owned.target_clouds.back() = upload(cloud);
+  }
+  {
+    const std::vector<const dliom_cloud*> clouds(owned.target_clouds.begin(), owned.target_clouds.end());
+    const std::vector<dliom_ndt_target*> built = BuildNdtTargets(context, ndt_options, clouds);
+    for (size_t k = 0; k < distinct.size(); ++k) owned.targets[distinct[k]] = built[k];
+  }
+  for (size_t k = 0; with_fitness && k < distinct.size(); ++k) {
+    dliom_nn_index* index = nullptr;
+    Check(dliom_nn_index_create(context->get(), owned.target_clouds[k], nullptr, &index), "dliom_nn_index_create");
+    owned.indices[distinct[k]] = index;
+  }
+  for (dliom_cloud*& c : owned.target_clouds) {  // as before: a target's cloud is gone before the sources are uploaded
+    dliom_cloud_destroy(c);
+    c = nullptr;
+  }
   std::vector<dliom_ndt_pair> table(pairs.size());
   for (size_t i = 0; i < pairs.size(); ++i) {
     const AlignmentPair& p = pairs[i];
-    if (p.source == nullptr || p.target == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "AlignPairsNdt: a pair without a cloud");
-    if (owned.targets.find(p.target) == owned.targets.end()) {
-      dliom_cloud* cloud = upload(p.target);
-      dliom_ndt_target* target = nullptr;
-      dliom_nn_index* index = nullptr;
-      int status = dliom_ndt_target_create(context->get(), cloud, &ndt_options, &target);
-      if (status == DLIOM_OK) owned.targets[p.target] = target;
-      if (status == DLIOM_OK && with_fitness) {
-        status = dliom_nn_index_create(context->get(), cloud, nullptr, &index);
-        if (status == DLIOM_OK) owned.indices[p.target] = index;
-      }
-      dliom_cloud_destroy(cloud);
-      Check(status, "dliom_ndt_target_create");
-    }
     if (owned.sources.find(p.source) == owned.sources.end()) owned.sources[p.source] = upload(p.source);
     table[i].target = owned.targets[p.target];
     table[i].source = owned.sources[p.source];

@@ -135,6 +135,8 @@ struct dliom_ctx {
   dliom::DevBuf icp_batch;
   // a batched NDT alignment (ndt_batch.hip): likewise, carved per pair as dliom_ndt_batch_scratch_bytes says
   dliom::DevBuf ndt_batch;
+  // a batched NDT target build (ndt_target_batch.hip): the sort's arrays, the scan and the cells' sums of the chunk in flight
+  dliom::DevBuf ndt_target_batch;
   // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
   dliom::DevBuf xray_leaves, xray_cells;
   // the submap image features (surf.hip): what is sized by the image and the candidates; what is sized by the key points

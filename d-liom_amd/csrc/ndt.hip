@@ -45,97 +45,36 @@ namespace {
 
 constexpr int kThreads = kNdtThreads;
 constexpr int kHalf = kNdtHalf;
-constexpr unsigned long long kSkipKey = ~0ull;
 
-// ---- the target --------------------------------------------------------------------------------------------------------------
+// ---- the target (ndt_internal.h: the bodies, which a chunk of ndt_target_batch.hip runs too) ---------------------------------
 __global__ __launch_bounds__(kThreads) void ndt_key_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                            const float* __restrict__ z, int n, float inv,
                                                            unsigned long long* __restrict__ keys, int* __restrict__ index) {
   const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
   if (i >= n) return;
-  const float f[3] = {floorf(x[i] * inv), floorf(y[i] * inv), floorf(z[i] * inv)};
-  bool ok = isfinite(x[i]) && isfinite(y[i]) && isfinite(z[i]);
-  for (int a = 0; a < 3; ++a) ok = ok && f[a] >= -static_cast<float>(kHalf) && f[a] < static_cast<float>(kHalf);
-  keys[i] = ok ? ndt_key(static_cast<int>(f[0]), static_cast<int>(f[1]), static_cast<int>(f[2])) : kSkipKey;
+  keys[i] = ndt_key_body(x, y, z, i, inv);
   index[i] = i;
 }
 
-// head[i] = 1 where a cell starts; *kept (n on entry) = the first position that holds the skip key
 __global__ __launch_bounds__(kThreads) void ndt_head_kernel(const unsigned long long* __restrict__ keys, int n,
                                                             unsigned* __restrict__ head, unsigned* __restrict__ kept) {
   const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long k = keys[i];
-  const bool first = i == 0 || keys[i - 1] != k;
-  head[i] = first && k != kSkipKey ? 1u : 0u;
-  if (first && k == kSkipKey) *kept = static_cast<unsigned>(i);
+  if (i < n) ndt_head_body(keys, i, head, kept);
 }
 
-// cell_first: cells + 1 entries
 __global__ __launch_bounds__(kThreads) void ndt_bounds_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ head,
                                                               const unsigned* __restrict__ inclusive, int n, int cells, int kept,
                                                               int* __restrict__ cell_first, unsigned long long* __restrict__ cell_key) {
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  if (i == 0) cell_first[cells] = kept;
-  if (i >= n || head[i] == 0u) return;
-  const int c = static_cast<int>(inclusive[i]) - 1;
-  if (c < 0 || c >= cells) return;
-  cell_first[c] = i;
-  cell_key[c] = keys[i];
+  ndt_bounds_body(keys, head, inclusive, 0u, static_cast<int>(blockIdx.x) * kThreads + threadIdx.x, n, cells, kept, cell_first, cell_key);
 }
 
-// sums: cells x 9 (S 0..2, Q 00 01 02 11 12 22)
+// sums: cells x 9
 __global__ __launch_bounds__(kThreads) void ndt_cell_sums_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                  const float* __restrict__ z, const int* __restrict__ sorted_index,
                                                                  const int* __restrict__ cell_first, double* __restrict__ sums) {
-  __shared__ double lds[kThreads * 9];
-  __shared__ double stack[17 * 9];  // the binary counter of the chunks' partial sums: level l holds 2^l chunks
   const int c = static_cast<int>(blockIdx.x);
-  const int first = cell_first[c], m = cell_first[c + 1] - first;
-  int m2 = 1;
-  while (m2 < m) m2 <<= 1;
-  const int width = m2 < kThreads ? m2 : kThreads;  // leaves of a chunk
-  const int chunks = m2 / width;
-  for (int chunk = 0; chunk < chunks; ++chunk) {
-    const int at = chunk * width + static_cast<int>(threadIdx.x);
-    double v[9];
-    if (static_cast<int>(threadIdx.x) < width && at < m) {
-      const int j = sorted_index[first + at];
-      const double p[3] = {x[j], y[j], z[j]};
-      v[0] = p[0];
-      v[1] = p[1];
-      v[2] = p[2];
-      v[3] = p[0] * p[0];
-      v[4] = p[0] * p[1];
-      v[5] = p[0] * p[2];
-      v[6] = p[1] * p[1];
-      v[7] = p[1] * p[2];
-      v[8] = p[2] * p[2];
-    } else {
-      for (int k = 0; k < 9; ++k) v[k] = 0.0;
-    }
-    __syncthreads();  // the previous chunk's root has been taken
-    for (int k = 0; k < 9; ++k) lds[threadIdx.x * 9 + k] = v[k];
-    for (int w = 1; w < width; w <<= 1) {
-      __syncthreads();
-      const int pairs = width / (2 * w);
-      for (int e = threadIdx.x; e < pairs * 9; e += kThreads) {
-        const int left = (e / 9) * 2 * w, k = e % 9;
-        lds[left * 9 + k] = lds[left * 9 + k] + lds[(left + w) * 9 + k];
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {  // lane k carries sum k through the counter
-      double carry = lds[threadIdx.x];
-      int level = 0;
-      while ((chunk >> level) & 1) {
-        carry = stack[level * 9 + threadIdx.x] + carry;
-        ++level;
-      }
-      stack[level * 9 + threadIdx.x] = carry;
-      if (chunk == chunks - 1) sums[static_cast<size_t>(c) * 9 + threadIdx.x] = carry;
-    }
-  }
+  const int first = cell_first[c];
+  ndt_cell_sums_body(x, y, z, sorted_index, first, cell_first[c + 1] - first, sums + static_cast<size_t>(c) * 9);
 }
 
 // ---- the evaluation (ndt_internal.h: the table, the pose's rows, the body, the leaves and the read-back) --------------------
@@ -313,6 +252,37 @@ NdtTable ndt_table_of(const dliom_ndt_target* t, const NdtConstants& k) {
                   res * res,
                   k.d1,
                   k.d2};
+}
+
+void ndt_finish_cells(dliom_ndt_target* t, int cells, const int* first, const unsigned long long* key, const double* sums,
+                      NdtValidCells* valid) {
+  t->cells.resize(cells);
+  for (int c = 0; c < cells; ++c) {
+    dliom_ndt_cell& cell = t->cells[c];
+    cell.index[0] = static_cast<int>(key[c] & 0x1fffffu) - kHalf;
+    cell.index[1] = static_cast<int>((key[c] >> 21) & 0x1fffffu) - kHalf;
+    cell.index[2] = static_cast<int>((key[c] >> 42) & 0x1fffffu) - kHalf;
+    cell.n = first[c + 1] - first[c];
+    ndt_finish_cell(&sums[static_cast<size_t>(c) * 9], t->min_points, &cell);
+    if (cell.valid != 0) {
+      valid->keys.push_back(key[c]);
+      valid->data.insert(valid->data.end(), cell.mean, cell.mean + 3);
+      valid->data.insert(valid->data.end(), cell.icov, cell.icov + 6);
+    }
+  }
+}
+
+int ndt_table_upload_enqueue(dliom_ndt_target* t, const NdtValidCells& valid) {
+  t->n_valid = static_cast<int64_t>(valid.keys.size());
+  t->cell_data_at = align256(8 * std::max<size_t>(valid.keys.size(), 1));
+  DLIOM_TRY(t->table.reserve(t->cell_data_at + 72 * std::max<size_t>(valid.keys.size(), 1)));
+  if (valid.keys.empty()) return DLIOM_OK;
+  hipStream_t stream = t->ctx->stream;
+  if (hipMemcpyAsync(t->table.p, valid.keys.data(), 8 * valid.keys.size(), hipMemcpyHostToDevice, stream) != hipSuccess ||
+      hipMemcpyAsync(t->table.as<char>() + t->cell_data_at, valid.data.data(), 8 * valid.data.size(), hipMemcpyHostToDevice, stream) !=
+          hipSuccess)
+    return DLIOM_ERR_HIP;
+  return DLIOM_OK;
 }
 
 void ndt_unpack(const NdtReadback& rb, int what, NdtSums* out) {
@@ -732,8 +702,7 @@ int dliom_ndt_target_create(dliom_ctx* ctx, const dliom_cloud* target, const dli
   t->n_points = n;
   t->n_kept = kept;
   t->build_read_backs = 1;
-  std::vector<unsigned long long> valid_keys;
-  std::vector<double> valid_data;
+  NdtValidCells valid;
   if (cells > 0) {
     const size_t first_bytes = align256(4 * (static_cast<size_t>(cells) + 1)), key_bytes = align256(8 * static_cast<size_t>(cells));
     DLIOM_TRY(work.b.reserve(first_bytes + key_bytes + 72 * static_cast<size_t>(cells)));
@@ -755,31 +724,9 @@ int dliom_ndt_target_create(dliom_ctx* ctx, const dliom_cloud* target, const dli
     DLIOM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     ++ctx->host_syncs;
     ++t->build_read_backs;
-    t->cells.resize(cells);
-    for (int c = 0; c < cells; ++c) {
-      dliom_ndt_cell& cell = t->cells[c];
-      cell.index[0] = static_cast<int>(h_key[c] & 0x1fffffu) - kHalf;
-      cell.index[1] = static_cast<int>((h_key[c] >> 21) & 0x1fffffu) - kHalf;
-      cell.index[2] = static_cast<int>((h_key[c] >> 42) & 0x1fffffu) - kHalf;
-      cell.n = h_first[c + 1] - h_first[c];
-      ndt_finish_cell(&h_sums[static_cast<size_t>(c) * 9], t->min_points, &cell);
-      if (cell.valid != 0) {
-        valid_keys.push_back(h_key[c]);
-        valid_data.insert(valid_data.end(), cell.mean, cell.mean + 3);
-        valid_data.insert(valid_data.end(), cell.icov, cell.icov + 6);
-      }
-    }
+    ndt_finish_cells(t.get(), cells, h_first.data(), h_key.data(), h_sums.data(), &valid);
   }
-  t->n_valid = static_cast<int64_t>(valid_keys.size());
-  t->cell_data_at = align256(8 * std::max<size_t>(valid_keys.size(), 1));
-  DLIOM_TRY(t->table.reserve(t->cell_data_at + 72 * std::max<size_t>(valid_keys.size(), 1)));
-  int status = DLIOM_OK;
-  if (!valid_keys.empty()) {
-    if (hipMemcpyAsync(t->table.p, valid_keys.data(), 8 * valid_keys.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(t->table.as<char>() + t->cell_data_at, valid_data.data(), 8 * valid_data.size(), hipMemcpyHostToDevice,
-                       ctx->stream) != hipSuccess)
-      status = DLIOM_ERR_HIP;
-  }
+  int status = ndt_table_upload_enqueue(t.get(), valid);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) status = DLIOM_ERR_HIP;  // the host vectors and the work buffers are free again
   ++ctx->host_syncs;
   if (status != DLIOM_OK) {

@@ -37,6 +37,95 @@ __host__ __device__ inline unsigned long long ndt_key(int ix, int iy, int iz) {
          static_cast<unsigned long long>(ix + kNdtHalf);
 }
 
+// ---- the target's build: the bodies that dliom_ndt_target_create's kernels (ndt.hip) and a chunk of
+// dliom_ndt_target_create_batch (ndt_target_batch.hip) both run.  Every pointer is the TARGET'S OWN: its coordinates, and
+// its run of the sorted keys, indices, heads and scan, so that positions count from the target's first one.
+constexpr unsigned long long kNdtSkipKey = ~0ull;
+
+// point i's 63-bit cell key (z high, x low), or the skip key
+__device__ __forceinline__ unsigned long long ndt_key_body(const float* __restrict__ x, const float* __restrict__ y,
+                                                           const float* __restrict__ z, int i, float inv) {
+  const float f[3] = {floorf(x[i] * inv), floorf(y[i] * inv), floorf(z[i] * inv)};
+  bool ok = isfinite(x[i]) && isfinite(y[i]) && isfinite(z[i]);
+  for (int a = 0; a < 3; ++a) ok = ok && f[a] >= -static_cast<float>(kNdtHalf) && f[a] < static_cast<float>(kNdtHalf);
+  return ok ? ndt_key(static_cast<int>(f[0]), static_cast<int>(f[1]), static_cast<int>(f[2])) : kNdtSkipKey;
+}
+
+// head[i] = 1 where a cell starts; *kept (n on entry) = the first position that holds the skip key.  Position 0 starts a
+// cell whatever lies in front of the target's run.
+__device__ __forceinline__ void ndt_head_body(const unsigned long long* __restrict__ keys, int i, unsigned* __restrict__ head,
+                                              unsigned* __restrict__ kept) {
+  const unsigned long long k = keys[i];
+  const bool first = i == 0 || keys[i - 1] != k;
+  head[i] = first && k != kNdtSkipKey ? 1u : 0u;
+  if (first && k == kNdtSkipKey) *kept = static_cast<unsigned>(i);
+}
+
+// cell_first: cells + 1 entries.  before: the scan's value in front of the target's run (0 for a run that starts the scan).
+__device__ __forceinline__ void ndt_bounds_body(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ head,
+                                                const unsigned* __restrict__ inclusive, unsigned before, int i, int n, int cells,
+                                                int kept, int* __restrict__ cell_first, unsigned long long* __restrict__ cell_key) {
+  if (i == 0) cell_first[cells] = kept;
+  if (i >= n || head[i] == 0u) return;
+  const int c = static_cast<int>(inclusive[i] - before) - 1;
+  if (c < 0 || c >= cells) return;
+  cell_first[c] = i;
+  cell_key[c] = keys[i];
+}
+
+// Called by every lane of a kNdtThreads workgroup: the nine sums (S 0..2, Q 00 01 02 11 12 22) of the cell that holds the
+// m sorted positions from `first`, in the header's fixed tree -- 256 leaves at a time through LDS, longer cells in aligned
+// chunks of 256 whose partial sums meet in a binary counter (the same tree, whatever the cell's length).
+__device__ __forceinline__ void ndt_cell_sums_body(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                                                   const int* __restrict__ sorted_index, int first, int m, double* __restrict__ sums) {
+  __shared__ double lds[kNdtThreads * 9];
+  __shared__ double stack[17 * 9];  // the binary counter of the chunks' partial sums: level l holds 2^l chunks
+  int m2 = 1;
+  while (m2 < m) m2 <<= 1;
+  const int width = m2 < kNdtThreads ? m2 : kNdtThreads;  // leaves of a chunk
+  const int chunks = m2 / width;
+  for (int chunk = 0; chunk < chunks; ++chunk) {
+    const int at = chunk * width + static_cast<int>(threadIdx.x);
+    double v[9];
+    if (static_cast<int>(threadIdx.x) < width && at < m) {
+      const int j = sorted_index[first + at];
+      const double p[3] = {x[j], y[j], z[j]};
+      v[0] = p[0];
+      v[1] = p[1];
+      v[2] = p[2];
+      v[3] = p[0] * p[0];
+      v[4] = p[0] * p[1];
+      v[5] = p[0] * p[2];
+      v[6] = p[1] * p[1];
+      v[7] = p[1] * p[2];
+      v[8] = p[2] * p[2];
+    } else {
+      for (int k = 0; k < 9; ++k) v[k] = 0.0;
+    }
+    __syncthreads();  // the previous chunk's root has been taken
+    for (int k = 0; k < 9; ++k) lds[threadIdx.x * 9 + k] = v[k];
+    for (int w = 1; w < width; w <<= 1) {
+      __syncthreads();
+      const int pairs = width / (2 * w);
+      for (int e = threadIdx.x; e < pairs * 9; e += kNdtThreads) {
+        const int left = (e / 9) * 2 * w, k = e % 9;
+        lds[left * 9 + k] = lds[left * 9 + k] + lds[(left + w) * 9 + k];
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {  // lane k carries sum k through the counter
+      double carry = lds[threadIdx.x];
+      int level = 0;
+      while ((chunk >> level) & 1) {
+        carry = stack[level * 9 + threadIdx.x] + carry;
+        ++level;
+      }
+      stack[level * 9 + threadIdx.x] = carry;
+      if (chunk == chunks - 1) sums[threadIdx.x] = carry;
+    }
+  }
+}
+
 struct NdtTable {
   const unsigned long long* keys;  // the valid cells, ascending
   const double* cell;              // 9 doubles each
@@ -235,6 +324,18 @@ bool ndt_options_ok(const dliom_ndt_options* o);
 bool ndt_guess_ok(const double* g);
 void ndt_pose(const double p[6], NdtPose* P);
 NdtTable ndt_table_of(const dliom_ndt_target* t, const NdtConstants& k);
+
+// The build's host step (dliom.h, target cells), a cell at a time in double: fills t->cells from the cells' first positions
+// (cells + 1 entries), keys and sums (9 a cell) as they were read back, and gathers the valid cells' keys and data.
+struct NdtValidCells {
+  std::vector<unsigned long long> keys;
+  std::vector<double> data;  // kNdtCellDoubles a cell
+};
+void ndt_finish_cells(dliom_ndt_target* t, int cells, const int* first, const unsigned long long* key, const double* sums,
+                      NdtValidCells* valid);
+// Allocates t->table for the valid cells and enqueues their copies on the context's stream; `valid` stays as it is until
+// the stream has been waited for.
+int ndt_table_upload_enqueue(dliom_ndt_target* t, const NdtValidCells& valid);
 
 // What the host keeps of an alignment's evaluations: an evaluation writes only what it computed, the rest stays
 struct NdtSums {

@@ -26,6 +26,10 @@
 //    that runs no single alignment and no batched ICP alignment (whose regions it lies over): every lock-step round it
 //    fills the table with the descriptors of the pairs in flight before its launches and has copied the pairs' read-back
 //    slots out before it writes the table again or returns;
+//  * kPinNdtTargetBatchTable belongs to a batched NDT target build (ndt_target_batch.hip), an entry point of its own: a
+//    chunk fills it with its targets' descriptors before its launches; its one small read-back (a cell count and a kept
+//    count a target) goes through kPinReadback and is copied out before the chunk stages anything else.  The cells' first
+//    positions, keys and sums are too many for this block: they go to the call's own host memory;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -99,6 +103,11 @@ constexpr size_t kPinNdtBatchPairs = 256, kPinNdtBatchSlotBytes = 256, kPinNdtBa
 constexpr PinRegion kPinNdtBatchReadback{8192, kPinNdtBatchPairs * kPinNdtBatchSlotBytes};
 constexpr PinRegion kPinNdtBatchTable{131072, kPinNdtBatchPairs * kPinNdtBatchEntryBytes};
 
+// a batched NDT target build (ndt_target_batch.hip): the chunk's upload, a descriptor for every target that may be in
+// flight (DLIOM_NDT_TARGET_BATCH_MAX_TARGETS); its counts' read-back, two words a target, is kPinReadback
+constexpr size_t kPinNdtTargetBatchTargets = 256, kPinNdtTargetBatchEntryBytes = 32;
+constexpr PinRegion kPinNdtTargetBatchTable{8192, kPinNdtTargetBatchTargets * kPinNdtTargetBatchEntryBytes};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -153,6 +162,9 @@ static_assert(pins_inside({kPinNdtSums}, kPinnedBytes) && pins_disjoint({kPinNdt
 static_assert(pins_inside({kPinNdtBatchReadback, kPinNdtBatchTable}, kPinnedBytes) &&
                   pins_disjoint({kPinNdtBatchReadback, kPinNdtBatchTable, kPinReadback, kPinIcpSums, kPinNdtSums}),
               "a batched NDT alignment's regions");
+static_assert(pins_inside({kPinNdtTargetBatchTable}, kPinnedBytes) && pins_disjoint({kPinNdtTargetBatchTable, kPinReadback}) &&
+                  2 * 4 * kPinNdtTargetBatchTargets <= kPinReadback.bytes,
+              "a batched NDT target build's regions");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

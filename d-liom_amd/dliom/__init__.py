@@ -3667,6 +3667,13 @@ class NdtTarget:
                 cloud.close()
         self.h = h
 
+    @classmethod
+    def _adopt(cls, ctx, options, handle):
+        """a target that a batched build made (ndt_targets_batch)"""
+        t = cls.__new__(cls)
+        t.ctx, t._L, t.options, t.h = ctx, ctx._L, options, handle
+        return t
+
     def close(self):
         if getattr(self, "h", None):
             self._L.dliom_ndt_target_destroy(self.h)
@@ -3833,6 +3840,67 @@ def ndt_align_batch(ctx, pairs, options=None, limits=None, want_aligned=False):
         for i in range(count):
             if want_aligned and handles[i]:
                 L.dliom_cloud_destroy(_vp(handles[i]))
+        for cloud in made:
+            cloud.close()
+
+
+# many targets in one call (dliom_ndt_target_create_batch): the K distinct target scans of that loop in one device chain a chunk
+NDT_TARGET_BATCH_MAX_TARGETS = 256
+
+
+class NdtTargetBatchLimits(C.Structure):
+    _fields_ = [("max_targets_in_flight", C.c_int), ("reserved", C.c_int), ("max_points_in_flight", C.c_int64)]
+
+
+class NdtTargetBatchStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("targets", "chunks", "points", "kept_points", "cells", "valid_cells", "read_backs",
+                                         "synchronizations", "max_in_flight", "scratch_bytes")] + \
+               [(f, C.c_double) for f in ("sort_ms", "sums_ms", "host_ms", "upload_ms")]
+
+
+SYMBOLS += [
+    ("dliom_ndt_target_batch_default_limits", C.c_int, [C.POINTER(NdtTargetBatchLimits)]),
+    ("dliom_ndt_target_create_batch", C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(NdtOptions),
+                                                C.POINTER(NdtTargetBatchLimits), C.POINTER(_vp), C.POINTER(NdtTargetBatchStats)]),
+]
+
+
+def ndt_target_batch_default_limits(**overrides):
+    """dliom_ndt_target_batch_default_limits, with fields replaced"""
+    lim = NdtTargetBatchLimits()
+    _check(load_library().dliom_ndt_target_batch_default_limits(C.byref(lim)), "dliom_ndt_target_batch_default_limits")
+    for k, v in overrides.items():
+        if k not in dict(NdtTargetBatchLimits._fields_):
+            raise TypeError("no NDT target batch limit " + k)
+        setattr(lim, k, v)
+    return lim
+
+
+def ndt_targets_batch(ctx, clouds, options=None, limits=None):
+    """dliom_ndt_target_create_batch.  clouds: a list of PointClouds or (n, 3) arrays, as NdtTarget takes them (an array
+    that is named several times is uploaded once).  -> (targets, stats): an NdtTarget a cloud, cell for cell and bit for
+    bit what NdtTarget(ctx, cloud, options) builds, each closed on its own; stats a dict."""
+    L = ctx._L
+    options = options if options is not None else ndt_options()
+    count = len(clouds)
+    table, handles, made = (_vp * max(count, 1))(), (_vp * max(count, 1))(), []
+    try:
+        uploaded = {}
+        for i, source in enumerate(clouds):
+            if isinstance(source, PointCloud):
+                cloud = source
+            elif id(source) in uploaded:
+                cloud = uploaded[id(source)]
+            else:
+                cloud = uploaded[id(source)] = PointCloud(ctx, source)
+                made.append(cloud)
+            table[i] = cloud.h
+        stats = NdtTargetBatchStats()
+        _check(L.dliom_ndt_target_create_batch(ctx.h, table, count, C.byref(options), None if limits is None else C.byref(limits),
+                                               handles, C.byref(stats)), "dliom_ndt_target_create_batch")
+        targets = [NdtTarget._adopt(ctx, options, _vp(handles[i])) for i in range(count)]
+        return targets, {k: getattr(stats, k) for k, _ in NdtTargetBatchStats._fields_}
+    finally:
         for cloud in made:
             cloud.close()
 

@@ -2682,6 +2682,60 @@ int dliom_ndt_align_batch(dliom_ctx* ctx, const dliom_ndt_pair* pairs, int count
                           const dliom_ndt_batch_limits* limits, dliom_ndt_result* results,
                           dliom_cloud** aligned /* NULL, or count entries */, dliom_ndt_batch_stats* stats /* may be NULL */);
 
+/* Many targets in one call: the other half of that loop, which builds the cells of every distinct target scan before it
+ * aligns (gen_ground_truth_by_ndt_match.cc:211-222, setInputTarget).  The clouds of a chunk are treated as ONE
+ * concatenation of positions and go through ONE launch chain, whatever their number: the keys, one stable radix sort by
+ * key over the whole chunk and one by the target's slot (so that the order is slot, key, ascending point index: within
+ * every target dliom_ndt_target_create's), one scan that numbers the chunk's cells, and one launch of the cells' sums, a
+ * workgroup a cell over the chunk's total.  The per-cell step (mean, covariance, Jacobi, icov) runs on the host, in
+ * double, as in the single build.
+ *
+ * Results.  out[i] is a dliom_ndt_target like any other: destroyed on its own with dliom_ndt_target_destroy, in any order
+ * and before or after its cloud, and usable with dliom_ndt_align, dliom_ndt_evaluate and dliom_ndt_align_batch.  Every cell
+ * is, bit for bit, what dliom_ndt_target_create(ctx, clouds[i], options, ...) builds (dliom_ndt_target_cells: index, n,
+ * valid, mean, icov), dliom_ndt_target_memory_stats gives the single build's points, kept_points, cells, valid_cells and
+ * target_bytes, and the device table of the valid cells is byte-equal to the single build's.  A batch-built target's
+ * read_backs is ITS CHUNK'S (2, or 1 for a chunk without any cell) and its build_ms is 0: the stages' times are in the
+ * statistics.  A cloud may be named more than once; each mention gets a target of its own.  Results never depend on the
+ * limits, on the order of the clouds, or on which other clouds share a chunk.
+ *
+ * Schedule.  Chunks are consecutive runs of clouds in input order.  A chunk closes when it holds max_targets_in_flight
+ * clouds, or when adding the next cloud would take the chunk's point sum above max_points_in_flight; it always holds at
+ * least one cloud (a cloud is at most DLIOM_NN_MAX_POINTS points, so positions in a chunk fit an int).  A chunk with at
+ * least one cell costs TWO polled read-backs -- every target's cell count and kept count, then the first positions, keys
+ * and sums of all its cells -- and a chunk without any cell one; read_backs is the sum over the chunks.  Every chunk takes
+ * one upload of its targets' descriptors, the copies of its targets' tables and ONE stream synchronisation at its end
+ * (synchronizations == chunks).  The work space is one block on the context, sized before the chain starts for the worst
+ * case that every point is a cell of its own: about 108 bytes a point of the largest chunk (scratch_bytes), kept until
+ * the context is destroyed.
+ *
+ * Refusals, all before anything runs (DLIOM_ERR_INVALID_ARGUMENT, no read-back or synchronisation counted on the context):
+ * a NULL context, options or out; NULL clouds with count > 0; count < 0; options that dliom_ndt_target_create refuses;
+ * limits outside their ranges or reserved != 0; a NULL cloud, a cloud of another context, an empty cloud.  count == 0
+ * succeeds and launches nothing.  A HIP or allocation failure fails the whole call, destroys what was built and leaves
+ * every out[i] NULL.  There is no per-target status. */
+#define DLIOM_NDT_TARGET_BATCH_MAX_TARGETS 256
+typedef struct dliom_ndt_target_batch_limits {
+  int max_targets_in_flight;       /* 1 .. DLIOM_NDT_TARGET_BATCH_MAX_TARGETS; default 64 */
+  int reserved;                    /* 0 */
+  int64_t max_points_in_flight;    /* 1 .. 2^30; default 64 * DLIOM_NDT_BATCH_DEFAULT_POINTS */
+} dliom_ndt_target_batch_limits;   /* NULL = the defaults, which dliom_ndt_target_batch_default_limits() returns */
+typedef struct dliom_ndt_target_batch_stats {
+  int64_t targets, chunks;
+  int64_t points, kept_points, cells, valid_cells; /* summed over the targets */
+  int64_t read_backs;              /* polled read-backs of the call: 2 a chunk with a cell, 1 a chunk without */
+  int64_t synchronizations;        /* stream synchronisations of the call: one a chunk */
+  int64_t max_in_flight;           /* the largest chunk, in targets */
+  int64_t scratch_bytes;           /* the largest chunk's device work space */
+  double sort_ms, sums_ms, host_ms, upload_ms; /* keys, both sorts, heads, scan and the first read-back | bounds, the cells'
+                                      sums and the second read-back | the per-cell step | the tables' allocations, copies and
+                                      the synchronisation; on the host's clock, only while the context's profiling is on */
+} dliom_ndt_target_batch_stats;
+int dliom_ndt_target_batch_default_limits(dliom_ndt_target_batch_limits* limits);
+int dliom_ndt_target_create_batch(dliom_ctx* ctx, const dliom_cloud* const* clouds, int count, const dliom_ndt_options* options,
+                                  const dliom_ndt_target_batch_limits* limits, dliom_ndt_target** out /* count entries */,
+                                  dliom_ndt_target_batch_stats* stats /* may be NULL */);
+
 /* Kernel timing (HIP events on the context's stream). */
 enum {
   DLIOM_KERNEL_RTCSM_SCORE = 0, /* score-volume kernel (dominant) */
