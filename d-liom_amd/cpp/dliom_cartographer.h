@@ -3766,21 +3766,44 @@ struct AlignmentPair {
   const sensor::PointCloud* target = nullptr;
   Matrix4f guess;
 };
+// Many nearest-neighbour indices in one call (dliom_nn_index_create_batch): what setInputTarget's dliom_nn_index_create
+// builds cloud by cloud -- every query answered with the same bits -- in one device chain a chunk.  clouds: clouds of the
+// context, none empty; a cloud may be named more than once.  options: NULL = the defaults, as setInputTarget passes.  -> an
+// index a cloud, the caller's to destroy (dliom_nn_index_destroy), each on its own.  limits: NULL = the defaults.  stats
+// (may be null): the call's.
+inline std::vector<dliom_nn_index*> BuildNnIndices(Context* context, const std::vector<const dliom_cloud*>& clouds,
+                                                   const dliom_nn_index_options* options = nullptr,
+                                                   const dliom_nn_index_batch_limits* limits = nullptr,
+                                                   dliom_nn_index_batch_stats* stats = nullptr) {
+  std::vector<dliom_nn_index*> indices(clouds.size(), nullptr);
+  dliom_nn_index* none = nullptr;
+  Check(dliom_nn_index_create_batch(context->get(), clouds.data(), static_cast<int>(clouds.size()), options, limits,
+                                    indices.empty() ? &none : indices.data(), stats),
+        "dliom_nn_index_create_batch");
+  return indices;
+}
+// How AlignPairs, AlignPairsNdt and the two generators build the indices of their distinct targets: one dliom_nn_index_create
+// a target (one read-back each), or all of them in ONE dliom_nn_index_create_batch (one read-back a chunk).  The results are
+// the same bits either way.
+enum class IndexBuild { kOneByOne, kBatched };
+
 // What IterativeClosestPoint with `icp_options` gives pair by pair (setInputSource, setInputTarget, align(guess), result()),
 // bit for bit.  ONE index is built per distinct target pointer and one cloud uploaded per distinct source pointer, however
 // many pairs name them.  limits: NULL = the defaults.  aligned (may be null): every pair's source under its final
-// transformation.  stats (may be null): the call's.
+// transformation.  stats (may be null): the call's.  build: kBatched uploads the distinct target clouds in the order of
+// their first mention and builds all their indices in one call.
 inline std::vector<dliom_icp_result> AlignPairs(Context* context, const dliom_icp_options& icp_options,
                                                 const std::vector<AlignmentPair>& pairs, const dliom_icp_batch_limits* limits = nullptr,
                                                 std::vector<sensor::PointCloud>* aligned = nullptr,
-                                                dliom_icp_batch_stats* stats = nullptr) {
+                                                dliom_icp_batch_stats* stats = nullptr, IndexBuild build = IndexBuild::kOneByOne) {
   struct Owned {  // destroyed on every way out, the indices before nothing else depends on them
     std::map<const sensor::PointCloud*, dliom_nn_index*> indices;
     std::map<const sensor::PointCloud*, dliom_cloud*> sources;
-    std::vector<dliom_cloud*> outputs;
+    std::vector<dliom_cloud*> target_clouds, outputs;
     ~Owned() {
       for (auto& e : indices) dliom_nn_index_destroy(e.second);
       for (auto& e : sources) dliom_cloud_destroy(e.second);
+      for (dliom_cloud* c : target_clouds) dliom_cloud_destroy(c);
       for (dliom_cloud* c : outputs) dliom_cloud_destroy(c);
     }
   } owned;
@@ -3790,6 +3813,24 @@ inline std::vector<dliom_icp_result> AlignPairs(Context* context, const dliom_ic
           "dliom_cloud_create");
     return out;
   };
+  if (build == IndexBuild::kBatched) {
+    std::vector<const sensor::PointCloud*> distinct;
+    for (const AlignmentPair& p : pairs) {
+      if (p.source == nullptr || p.target == nullptr) Check(DLIOM_ERR_INVALID_ARGUMENT, "AlignPairs: a pair without a cloud");
+      if (std::find(distinct.begin(), distinct.end(), p.target) == distinct.end()) distinct.push_back(p.target);
+    }
+    for (const sensor::PointCloud* cloud : distinct) {
+      owned.target_clouds.push_back(nullptr);
+      owned.target_clouds.back() = upload(cloud);
+    }
+    const std::vector<const dliom_cloud*> clouds(owned.target_clouds.begin(), owned.target_clouds.end());
+    const std::vector<dliom_nn_index*> built = BuildNnIndices(context, clouds);
+    for (size_t k = 0; k < distinct.size(); ++k) owned.indices[distinct[k]] = built[k];
+    for (dliom_cloud*& c : owned.target_clouds) {  // as one by one: a target's cloud is gone before the sources are uploaded
+      dliom_cloud_destroy(c);
+      c = nullptr;
+    }
+  }
   std::vector<dliom_icp_pair> table(pairs.size());
   for (size_t i = 0; i < pairs.size(); ++i) {
     const AlignmentPair& p = pairs[i];
@@ -3881,11 +3922,11 @@ inline void CollectGroundTruthPairs(const std::vector<transform::Rigid3d>& poses
 // poses, timestamps_ns: one a node; stamps_in_bag (sorted) and clouds: one a scan of the bag.  A `from` node without a
 // revisit node (FindRevisitNode: -1) is skipped; so is a pair with a stamp past the bag's last (:173-180) and a pair whose
 // alignment does not converge (:205).  Alignments run batch_size pairs a call, with the GroundTruthIcp preset; the text is
-// byte-equal to the loop through IterativeClosestPoint::GroundTruthIcp one pair at a time, whatever batch_size is.
+// byte-equal to the loop through IterativeClosestPoint::GroundTruthIcp one pair at a time, whatever batch_size and build are.
 inline std::string GenerateGroundTruthIcp(Context* context, const std::vector<transform::Rigid3d>& poses,
                                           const std::vector<int64_t>& timestamps_ns, const std::vector<int64_t>& stamps_in_bag,
                                           const std::vector<sensor::PointCloud>& clouds, const std::vector<size_t>& from_nodes,
-                                          size_t batch_size) {
+                                          size_t batch_size, IndexBuild build = IndexBuild::kOneByOne) {
   if (batch_size < 1 || clouds.size() != stamps_in_bag.size() || timestamps_ns.size() != poses.size())
     Check(DLIOM_ERR_INVALID_ARGUMENT, "GenerateGroundTruthIcp");
   std::vector<GroundTruthWanted> wanted;
@@ -3896,7 +3937,7 @@ inline std::string GenerateGroundTruthIcp(Context* context, const std::vector<tr
   for (size_t first = 0; first < pairs.size(); first += batch_size) {
     const size_t end = std::min(pairs.size(), first + batch_size);
     const std::vector<AlignmentPair> group(pairs.begin() + static_cast<std::ptrdiff_t>(first), pairs.begin() + static_cast<std::ptrdiff_t>(end));
-    const std::vector<dliom_icp_result> results = AlignPairs(context, options, group);
+    const std::vector<dliom_icp_result> results = AlignPairs(context, options, group, nullptr, nullptr, nullptr, build);
     for (size_t i = first; i < end; ++i) {
       const dliom_icp_result& r = results[i - first];
       if (r.converged == 0) continue;
@@ -4068,12 +4109,13 @@ inline std::vector<dliom_ndt_target*> BuildNdtTargets(Context* context, const dl
 // pointer, all of them in ONE call (BuildNdtTargets) -- and with with_fitness ONE nearest-neighbour index for
 // getFitnessScore() -- and one cloud uploaded per distinct source pointer, however many pairs name them; everything is
 // destroyed on every way out.  limits: NULL = the defaults.
-// aligned (may be null): every pair's source under its final transformation.  stats (may be null): the call's.
+// aligned (may be null): every pair's source under its final transformation.  stats (may be null): the call's.  build:
+// kBatched builds the fitness indices in ONE call too (BuildNnIndices).
 inline std::vector<dliom_ndt_result> AlignPairsNdt(Context* context, const dliom_ndt_options& ndt_options,
                                                    const std::vector<AlignmentPair>& pairs, bool with_fitness = true,
                                                    const dliom_ndt_batch_limits* limits = nullptr,
                                                    std::vector<sensor::PointCloud>* aligned = nullptr,
-                                                   dliom_ndt_batch_stats* stats = nullptr) {
+                                                   dliom_ndt_batch_stats* stats = nullptr, IndexBuild build = IndexBuild::kOneByOne) {
   struct Owned {  // destroyed on every way out, the targets and indices before nothing else depends on them
     std::map<const sensor::PointCloud*, dliom_ndt_target*> targets;
     std::map<const sensor::PointCloud*, dliom_nn_index*> indices;
@@ -4108,7 +4150,12 @@ inline std::vector<dliom_ndt_result> AlignPairsNdt(Context* context, const dliom
     const std::vector<dliom_ndt_target*> built = BuildNdtTargets(context, ndt_options, clouds);
     for (size_t k = 0; k < distinct.size(); ++k) owned.targets[distinct[k]] = built[k];
   }
-  for (size_t k = 0; with_fitness && k < distinct.size(); ++k) {
+  if (with_fitness && build == IndexBuild::kBatched) {
+    const std::vector<const dliom_cloud*> clouds(owned.target_clouds.begin(), owned.target_clouds.end());
+    const std::vector<dliom_nn_index*> built = BuildNnIndices(context, clouds);
+    for (size_t k = 0; k < distinct.size(); ++k) owned.indices[distinct[k]] = built[k];
+  }
+  for (size_t k = 0; with_fitness && build == IndexBuild::kOneByOne && k < distinct.size(); ++k) {
     dliom_nn_index* index = nullptr;
     Check(dliom_nn_index_create(context->get(), owned.target_clouds[k], nullptr, &index), "dliom_nn_index_create");
     owned.indices[distinct[k]] = index;
@@ -4144,11 +4191,11 @@ inline std::vector<dliom_ndt_result> AlignPairsNdt(Context* context, const dliom
 // The tool's loop (gen_ground_truth_by_ndt_match.cc:151-261) for --method ndt (:211-222), GenerateGroundTruthIcp's other
 // half: the same pairs (CollectGroundTruthPairs), aligned batch_size pairs a call with the GroundTruthNdt preset on the raw
 // clouds, getFitnessScore() as the alignment error, a pair that does not converge dropped (:218).  The text is byte-equal
-// to the loop through NormalDistributionsTransform::GroundTruthNdt one pair at a time, whatever batch_size is.
+// to the loop through NormalDistributionsTransform::GroundTruthNdt one pair at a time, whatever batch_size and build are.
 inline std::string GenerateGroundTruthNdt(Context* context, const std::vector<transform::Rigid3d>& poses,
                                           const std::vector<int64_t>& timestamps_ns, const std::vector<int64_t>& stamps_in_bag,
                                           const std::vector<sensor::PointCloud>& clouds, const std::vector<size_t>& from_nodes,
-                                          size_t batch_size) {
+                                          size_t batch_size, IndexBuild build = IndexBuild::kOneByOne) {
   if (batch_size < 1 || clouds.size() != stamps_in_bag.size() || timestamps_ns.size() != poses.size())
     Check(DLIOM_ERR_INVALID_ARGUMENT, "GenerateGroundTruthNdt");
   std::vector<GroundTruthWanted> wanted;
@@ -4159,7 +4206,7 @@ inline std::string GenerateGroundTruthNdt(Context* context, const std::vector<tr
   for (size_t first = 0; first < pairs.size(); first += batch_size) {
     const size_t end = std::min(pairs.size(), first + batch_size);
     const std::vector<AlignmentPair> group(pairs.begin() + static_cast<std::ptrdiff_t>(first), pairs.begin() + static_cast<std::ptrdiff_t>(end));
-    const std::vector<dliom_ndt_result> results = AlignPairsNdt(context, options, group, true);
+    const std::vector<dliom_ndt_result> results = AlignPairsNdt(context, options, group, true, nullptr, nullptr, nullptr, build);
     for (size_t i = first; i < end; ++i) {
       const dliom_ndt_result& r = results[i - first];
       if (r.converged == 0) continue;

@@ -796,6 +796,7 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
   ctx->icp_batch.release();
   ctx->ndt_batch.release();
   ctx->ndt_target_batch.release();
+  ctx->nn_index_batch.release();
   ctx->xray_leaves.release();
   ctx->xray_cells.release();
   ctx->surf.release();

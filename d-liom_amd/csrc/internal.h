@@ -137,6 +137,9 @@ struct dliom_ctx {
   dliom::DevBuf ndt_batch;
   // a batched NDT target build (ndt_target_batch.hip): the sort's arrays, the scan and the cells' sums of the chunk in flight
   dliom::DevBuf ndt_target_batch;
+  // a batched index build (nn_index_batch.hip): the chunk's descriptors and box words, then its points' cells and the
+  // counting sort's populations, cursors and scan
+  dliom::DevBuf nn_index_batch;
   // the X-ray projections (xray.hip): per-leaf arrays, then per-cell arrays and the image; reserved on first use
   dliom::DevBuf xray_leaves, xray_cells;
   // the submap image features (surf.hip): what is sized by the image and the candidates; what is sized by the key points

@@ -18,7 +18,8 @@
 // The shell walk, the scan, the resolve and the transform are each ONE __device__ body over (view, search, bound,
 // workgroup index).  nn_*_kernel runs it for the one search of its arguments; nn_*_batch_kernel for the searches of a table
 // in HBM (nn_index.h NnBatchItem), with the pair as a grid dimension.  What is proven of a body -- the stop rule, the tie
-// rule -- holds for both.
+// rule -- holds for both.  The three build kernels' bodies, the index and the host's choice of its grid are in
+// nn_index_internal.h: many indices are built in one call by nn_index_batch.hip.
 //
 // Every loop's bound is known before it starts: the shells by DLIOM_NN_MAX_SHELLS, the rows of a shell by its width, a
 // row's points by the index's size; the brute-force kernel by the index's size.  No kernel waits on another workgroup.
@@ -28,108 +29,30 @@
 #include <cmath>
 #include <cstring>
 
-#include "device_common.h"
-#include "nn_index.h"
-
-struct dliom_nn_index {
-  dliom_ctx* ctx = nullptr;
-  int64_t n_target = 0, n_finite = 0;
-  int dims[3] = {1, 1, 1};
-  float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};
-  float inv = 0.f;
-  double edge = 0.0;
-  int search = DLIOM_NN_AUTO;
-  dliom::DevBuf sorted, by_index, cell_start;
-  dliom::DevBuf scratch;  // of the call that runs
-  int poll_us = 150;      // poll window of a read-back's completion word: twice what the previous one took
-};
+#include "nn_index_internal.h"
 
 namespace dliom {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kNnThreads;
 constexpr int kTile = 1024;  // target points staged in LDS at a time (16 KiB)
 // Target points a workgroup of nn_brute_kernel scans for its queries.  Every query: 4 tiles (many workgroups a SIMD hide
 // the LDS latency).  Listed queries are few -- often a handful, one wave a SIMD -- and wait for the longest segment: a
 // quarter tile, i.e. as many segments as the grid's second dimension is allowed (256), more atomics and a shorter tail.
 constexpr int kBruteSegment = 4 * kTile, kListedSegment = kTile / 4;
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  const float inf = __int_as_float(0x7f800000);
-  return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;  // false for NaN
-}
-
-// bit patterns that order like the floats they come from
-__device__ __forceinline__ unsigned ordered_word(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float float_of_ordered_word(unsigned w) {
-  const unsigned u = (w & 0x80000000u) ? (w & 0x7fffffffu) : ~w;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
+// The three build kernels run the bodies of nn_index_internal.h, which a batched build (nn_index_batch.hip) runs too.
 // words: [min x y z, unused | max x y z, finite count]
 __global__ __launch_bounds__(kThreads) void nn_box_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                           const float* __restrict__ z, int n, unsigned* __restrict__ words) {
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
-  bool ok = false;
-  if (i < n) {
-    const float p[3] = {x[i], y[i], z[i]};
-    ok = finite3(p[0], p[1], p[2]);
-    if (ok)
-      for (int a = 0; a < 3; ++a) lo[a] = hi[a] = ordered_word(p[a]);
-  }
-  const unsigned long long votes = __ballot(ok);
-  if (votes == 0ull) return;  // the whole wave
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = min(lo[a], static_cast<unsigned>(__shfl_xor(static_cast<int>(lo[a]), off, 64)));
-      hi[a] = max(hi[a], static_cast<unsigned>(__shfl_xor(static_cast<int>(hi[a]), off, 64)));
-    }
-  if ((threadIdx.x & 63u) == 0u) {
-    for (int a = 0; a < 3; ++a) {
-      atomicMin(words + a, lo[a]);
-      atomicMax(words + 4 + a, hi[a]);
-    }
-    atomicAdd(words + 7, static_cast<unsigned>(__popcll(votes)));
-  }
-}
-
-// The cell of a coordinate inside [lo, hi].  Monotone in x: the rounded subtraction, the rounded product with inv >= 0,
-// floorf and the clamps all are -- what the stop rule of nn_shell_kernel stands on.  (A NaN product, inf * 0 under the
-// one-cell grid of an unbounded box, is cell 0: fmaxf returns its other argument.)
-__device__ __forceinline__ int nn_cell(float x, float lo, float inv, int dim, float* u_out = nullptr) {
-  const float u = (x - lo) * inv;
-  if (u_out != nullptr) *u_out = u;
-  return static_cast<int>(fminf(fmaxf(floorf(u), 0.f), static_cast<float>(dim - 1)));
-}
-
-__device__ __forceinline__ int nn_cell_index(const NnGridView& g, float x, float y, float z) {
-  const int cx = nn_cell(x, g.lo[0], g.inv, g.dims[0]);
-  const int cy = nn_cell(y, g.lo[1], g.inv, g.dims[1]);
-  const int cz = nn_cell(z, g.lo[2], g.inv, g.dims[2]);
-  return (cz * g.dims[1] + cy) * g.dims[0] + cx;
+  nn_box_body(x, y, z, n, words, words + 4, static_cast<int>(blockIdx.x));
 }
 
 __global__ __launch_bounds__(kThreads) void nn_count_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                            const float* __restrict__ z, int n, NnGridView g,
+                                                            const float* __restrict__ z, int n, NnCells g,
                                                             int* __restrict__ cell_of_point, int* __restrict__ counts,
                                                             float4* __restrict__ by_index) {
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const float px = x[i], py = y[i], pz = z[i];
-  by_index[i] = make_float4(px, py, pz, 0.f);
-  int c = -1;
-  if (finite3(px, py, pz)) {
-    c = nn_cell_index(g, px, py, pz);
-    atomicAdd(counts + c, 1);
-  }
-  cell_of_point[i] = c;
+  nn_count_body(x, y, z, n, g, cell_of_point, counts, by_index, static_cast<int>(blockIdx.x));
 }
 
 __global__ __launch_bounds__(kThreads) void nn_scatter_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -137,12 +60,7 @@ __global__ __launch_bounds__(kThreads) void nn_scatter_kernel(const float* __res
                                                               const int* __restrict__ cell_of_point,
                                                               const int* __restrict__ cell_start, int* __restrict__ cursor,
                                                               float4* __restrict__ sorted) {
-  const int i = static_cast<int>(blockIdx.x) * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const int c = cell_of_point[i];
-  if (c < 0) return;
-  const int at = cell_start[c] + atomicAdd(cursor + c, 1);  // < cell_start[c + 1]: the cursor counts what nn_count_kernel counted
-  sorted[at] = make_float4(x[i], y[i], z[i], __int_as_float(i));
+  nn_scatter_body(x, y, z, n, cell_of_point, cell_start, 0, cursor, sorted, static_cast<int>(blockIdx.x));
 }
 
 struct Best {
@@ -394,49 +312,6 @@ __global__ __launch_bounds__(kThreads) void nn_resolve_batch_kernel(const char* 
   nn_resolve_body(s, d.max_d2, d.brute == 0, block);
 }
 
-// The grid over a box of `extent` metres an axis for n points: edge0 (0: half the edge that puts a point a cell into the
-// box's volume, area or length, whichever it has -- a scan's points lie on surfaces and crowd near the sensor, so most
-// cells are empty, and an empty cell costs the walk nothing: a shell's row is one range of slots), grown by 26 % a step
-// until the grid fits.  A box whose extent is not finite, or a
-// single point, is one cell with inv = 0.
-void nn_choose_grid(const double extent[3], int64_t n, double edge0, int dims[3], float* inv, double* edge) {
-  dims[0] = dims[1] = dims[2] = 1;
-  *inv = 0.f;
-  *edge = 0.0;
-  double product = 1.0;
-  int axes = 0;
-  for (int a = 0; a < 3; ++a) {
-    if (!std::isfinite(extent[a])) return;
-    if (extent[a] > 0.0) {
-      product *= extent[a];
-      ++axes;
-    }
-  }
-  if (axes == 0 || !std::isfinite(product)) return;
-  double e = edge0 > 0.0 ? edge0 : 0.5 * std::pow(product / static_cast<double>(std::max<int64_t>(n, 1)), 1.0 / axes);
-  if (!(e >= 1e-6)) e = 1e-6;
-  for (int step = 0; step < 400; ++step, e *= 1.26) {
-    const float f = static_cast<float>(1.0 / e);
-    if (!(f > 0.f) || !std::isfinite(f)) continue;
-    double cells = 1.0;
-    bool fits = true;
-    int d[3];
-    for (int a = 0; a < 3; ++a) {
-      const double along = std::floor(extent[a] * static_cast<double>(f)) + 1.0;
-      fits = fits && along <= DLIOM_NN_MAX_CELLS_PER_AXIS;
-      d[a] = fits ? static_cast<int>(along) : 1;
-      cells *= along;
-    }
-    if (!fits || cells > DLIOM_NN_MAX_CELLS) continue;
-    dims[0] = d[0];
-    dims[1] = d[1];
-    dims[2] = d[2];
-    *inv = f;
-    *edge = 1.0 / static_cast<double>(f);
-    return;
-  }
-}
-
 }  // namespace
 
 NnGridView nn_view(const dliom_nn_index* index) {
@@ -539,13 +414,7 @@ int dliom_nn_index_create(dliom_ctx* ctx, const dliom_cloud* target, const dliom
   if (target->n < 1 || target->n > DLIOM_NN_MAX_POINTS) return DLIOM_ERR_INVALID_ARGUMENT;
   double edge0 = 0.0;
   int search = DLIOM_NN_AUTO;
-  if (options != nullptr) {
-    if (!std::isfinite(options->cell_edge) || options->cell_edge < 0.0 || options->reserved != 0 ||
-        (options->search != DLIOM_NN_AUTO && options->search != DLIOM_NN_BRUTE_FORCE))
-      return DLIOM_ERR_INVALID_ARGUMENT;
-    edge0 = options->cell_edge;
-    search = options->search;
-  }
+  if (!nn_index_options_ok(options, &edge0, &search)) return DLIOM_ERR_INVALID_ARGUMENT;
   DLIOM_HIP_TRY(hipSetDevice(ctx->device));
   const int n = static_cast<int>(target->n);
   struct Guard {  // a failure on the way frees what was made
@@ -569,15 +438,7 @@ int dliom_nn_index_create(dliom_ctx* ctx, const dliom_cloud* target, const dliom
   unsigned* const host = pinned_at<unsigned>(ctx, kPinReadback);
   const GatherJob job{words, 8};
   DLIOM_TRY(gather_and_wait(ctx, &job, 1, host));
-  f->n_finite = host[7];
-  double extent[3] = {0.0, 0.0, 0.0};
-  if (f->n_finite > 0)
-    for (int a = 0; a < 3; ++a) {
-      f->lo[a] = float_of_ordered_word(host[a]);
-      f->hi[a] = float_of_ordered_word(host[4 + a]);
-      extent[a] = static_cast<double>(f->hi[a]) - static_cast<double>(f->lo[a]);
-    }
-  nn_choose_grid(extent, f->n_finite, edge0, f->dims, &f->inv, &f->edge);
+  nn_set_grid(f, host, host + 4, edge0);
   const size_t cells = static_cast<size_t>(f->dims[0]) * f->dims[1] * f->dims[2];
   // counting sort by cell: populations, their exclusive sum (cells + 1 entries: the last is the total), scatter
   size_t tmp = 0;
@@ -596,7 +457,7 @@ int dliom_nn_index_create(dliom_ctx* ctx, const dliom_cloud* target, const dliom
   int* const counts = work.as<int>();
   int* const cursor = reinterpret_cast<int*>(work.as<char>() + per);
   DLIOM_HIP_TRY(hipMemsetAsync(work.p, 0, 2 * per, ctx->stream));
-  const NnGridView g = nn_view(f);
+  const NnCells g = nn_cells_of(f);
   hipLaunchKernelGGL(nn_count_kernel, grid, block, 0, ctx->stream, target->d_x, target->d_y, target->d_z, n, g, cell_of_point, counts,
                      f->by_index.as<float4>());
   DLIOM_HIP_TRY(hipGetLastError());
@@ -616,6 +477,8 @@ void dliom_nn_index_destroy(dliom_nn_index* index) {
   if (index == nullptr) return;
   (void)hipSetDevice(index->ctx->device);
   (void)hipStreamSynchronize(index->ctx->stream);
+  if (index->slab.p != nullptr) index->sorted = index->by_index = index->cell_start = dliom::DevBuf{};  // views into the slab
+  index->slab.release();
   index->sorted.release();
   index->by_index.release();
   index->cell_start.release();

@@ -30,6 +30,11 @@
 //    chunk fills it with its targets' descriptors before its launches; its one small read-back (a cell count and a kept
 //    count a target) goes through kPinReadback and is copied out before the chunk stages anything else.  The cells' first
 //    positions, keys and sums are too many for this block: they go to the call's own host memory;
+//  * kPinNnIndexBatchTable and kPinNnIndexBatchBoxes belong to a batched index build (nn_index_batch.hip), an entry point
+//    of its own that runs no single build: a chunk fills the table with its clouds' descriptors before the boxes' launch,
+//    reads every cloud's eight box words back through the second region (8 words x 256 clouds are more than kPinReadback
+//    holds), and only then writes the table again, with the grids' views, before the sort's launches.  The chunk's stream
+//    synchronisation frees both for the next chunk;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -108,6 +113,12 @@ constexpr PinRegion kPinNdtBatchTable{131072, kPinNdtBatchPairs * kPinNdtBatchEn
 constexpr size_t kPinNdtTargetBatchTargets = 256, kPinNdtTargetBatchEntryBytes = 32;
 constexpr PinRegion kPinNdtTargetBatchTable{8192, kPinNdtTargetBatchTargets * kPinNdtTargetBatchEntryBytes};
 
+// a batched index build (nn_index_batch.hip): the chunk's uploads, a descriptor for every cloud that may be in flight
+// (DLIOM_NN_INDEX_BATCH_MAX_INDICES), and the boxes' read-back: the clouds' four low words, then their four high words
+constexpr size_t kPinNnIndexBatchIndices = 256, kPinNnIndexBatchEntryBytes = 128, kPinNnIndexBatchBoxWords = 8;
+constexpr PinRegion kPinNnIndexBatchTable{8192, kPinNnIndexBatchIndices * kPinNnIndexBatchEntryBytes};
+constexpr PinRegion kPinNnIndexBatchBoxes{65536, kPinNnIndexBatchIndices * kPinNnIndexBatchBoxWords * 4};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -165,6 +176,10 @@ static_assert(pins_inside({kPinNdtBatchReadback, kPinNdtBatchTable}, kPinnedByte
 static_assert(pins_inside({kPinNdtTargetBatchTable}, kPinnedBytes) && pins_disjoint({kPinNdtTargetBatchTable, kPinReadback}) &&
                   2 * 4 * kPinNdtTargetBatchTargets <= kPinReadback.bytes,
               "a batched NDT target build's regions");
+static_assert(pins_inside({kPinNnIndexBatchTable, kPinNnIndexBatchBoxes}, kPinnedBytes) &&
+                  pins_disjoint({kPinNnIndexBatchTable, kPinNnIndexBatchBoxes, kPinReadback}) &&
+                  kPinNnIndexBatchBoxWords * 4 * kPinNnIndexBatchIndices > kPinReadback.bytes,
+              "a batched index build's regions (its boxes would not fit the small read-backs')");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

@@ -3435,6 +3435,13 @@ class NnIndex:
                 cloud.close()
         self.h = h
 
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        """an index that a batched build made (nn_indices_batch)"""
+        index = cls.__new__(cls)
+        index.ctx, index._L, index.h = ctx, ctx._L, handle
+        return index
+
     def close(self):
         if getattr(self, "h", None):
             self._L.dliom_nn_index_destroy(self.h)
@@ -3463,6 +3470,68 @@ class NnIndex:
         finally:
             if mine:
                 cloud.close()
+
+
+# many indices in one call (dliom_nn_index_create_batch): the K distinct target scans of the ground-truth tool's loop in
+# one device chain a chunk
+NN_INDEX_BATCH_MAX_INDICES = 256
+
+
+class NnIndexBatchLimits(C.Structure):
+    _fields_ = [("max_indices_in_flight", C.c_int), ("reserved", C.c_int), ("max_points_in_flight", C.c_int64),
+                ("max_cells_in_flight", C.c_int64)]
+
+
+class NnIndexBatchStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("indices", "chunks", "cell_runs", "points", "finite_points", "cells", "read_backs",
+                                         "synchronizations", "max_in_flight", "scratch_bytes")] + \
+               [(f, C.c_double) for f in ("box_ms", "sort_ms", "alloc_ms")]
+
+
+SYMBOLS += [
+    ("dliom_nn_index_batch_default_limits", C.c_int, [C.POINTER(NnIndexBatchLimits)]),
+    ("dliom_nn_index_create_batch", C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(NnIndexOptions),
+                                              C.POINTER(NnIndexBatchLimits), C.POINTER(_vp), C.POINTER(NnIndexBatchStats)]),
+]
+
+
+def nn_index_batch_default_limits(**overrides):
+    """dliom_nn_index_batch_default_limits, with fields replaced"""
+    lim = NnIndexBatchLimits()
+    _check(load_library().dliom_nn_index_batch_default_limits(C.byref(lim)), "dliom_nn_index_batch_default_limits")
+    for k, v in overrides.items():
+        if k not in dict(NnIndexBatchLimits._fields_):
+            raise TypeError("no index batch limit " + k)
+        setattr(lim, k, v)
+    return lim
+
+
+def nn_indices_batch(ctx, clouds, cell_edge=0.0, search=NN_AUTO, limits=None):
+    """dliom_nn_index_create_batch.  clouds: a list of PointClouds or (n, 3) arrays, as NnIndex takes them (an array that
+    is named several times is uploaded once).  -> (indices, stats): an NnIndex a cloud that answers every query bit for
+    bit as NnIndex(ctx, cloud, cell_edge, search) does, each closed on its own; stats a dict."""
+    L = ctx._L
+    count = len(clouds)
+    table, handles, made = (_vp * max(count, 1))(), (_vp * max(count, 1))(), []
+    try:
+        uploaded = {}
+        for i, source in enumerate(clouds):
+            if isinstance(source, PointCloud):
+                cloud = source
+            elif id(source) in uploaded:
+                cloud = uploaded[id(source)]
+            else:
+                cloud = uploaded[id(source)] = PointCloud(ctx, source)
+                made.append(cloud)
+            table[i] = cloud.h
+        o, stats = NnIndexOptions(float(cell_edge), int(search), 0), NnIndexBatchStats()
+        _check(L.dliom_nn_index_create_batch(ctx.h, table, count, C.byref(o), None if limits is None else C.byref(limits),
+                                             handles, C.byref(stats)), "dliom_nn_index_create_batch")
+        indices = [NnIndex._adopt(ctx, _vp(handles[i])) for i in range(count)]
+        return indices, {k: getattr(stats, k) for k, _ in NnIndexBatchStats._fields_}
+    finally:
+        for cloud in made:
+            cloud.close()
 
 
 def _icp_result(r):

@@ -2356,6 +2356,69 @@ int dliom_nn_index_memory_stats(const dliom_nn_index* index, dliom_nn_index_memo
  * index's own choice) or DLIOM_NN_BRUTE_FORCE.  stats may be NULL. */
 int dliom_nn_index_query(dliom_nn_index* index, const dliom_cloud* queries, const double* transform16, double max_distance,
                          int search, int32_t* j_out, float* d2_out, dliom_nn_query_stats* stats);
+
+/* Many indices in one call: the tool's other per-target build (gen_ground_truth_by_ndt_match.cc:199-200, setInputTarget of
+ * every distinct ICP target, and :219, the index behind an NDT pair's getFitnessScore()).  The clouds of a chunk go through
+ * ONE launch chain, whatever their number, with the cloud's slot as a grid dimension: the bounding boxes, one read-back,
+ * and the counting sort by cell with ONE scan over the concatenation of many indices' cell arrays.  Every kernel runs the
+ * body that dliom_nn_index_create's kernel runs, on the cloud's own points with the cloud's own grid.
+ *
+ * Results.  out[i] is a dliom_nn_index like any other: destroyed on its own with dliom_nn_index_destroy, in any order and
+ * before or after its cloud, and usable with dliom_nn_index_query, dliom_icp_align, dliom_icp_step, dliom_icp_align_batch
+ * and as a fitness_index of dliom_ndt_align and dliom_ndt_align_batch.  dliom_nn_index_memory_stats gives the single build's
+ * points, finite_points, cells, dims, cell_edge and index_bytes (not scratch_bytes: a batch-built index has no scratch
+ * until its first call).  Every query gives, bit for bit, what it gives on the index that dliom_nn_index_create(ctx,
+ * clouds[i], options, ...) builds: j, d2, settled_by_grid, settled_by_brute_force and non_finite.  The order of the points
+ * inside a cell is unspecified, as the single build's is; no result depends on it.  A cloud may be named more than once;
+ * each mention gets an index of its own.  Results never depend on the limits, on the order of the clouds, or on which
+ * other clouds share a chunk.
+ *
+ * Schedule.  Chunks are consecutive runs of clouds in input order.  A chunk closes when it holds max_indices_in_flight
+ * clouds, or when adding the next cloud would take the chunk's point sum above max_points_in_flight; it always holds at
+ * least one cloud.  A chunk costs one upload of its clouds' descriptors, one launch of the bounding boxes and ONE polled
+ * read-back: eight words a cloud, the ordered box words and the finite count.  The host then chooses every grid as the
+ * single build does, makes ONE device allocation an index (by_index | cell_start | sorted: all three sizes are known by
+ * then) and uploads the descriptors again, with the grids and the arrays.  The chunk's indices then go through the
+ * counting sort in CELL RUNS: consecutive indices whose cells + 1 sum to at most max_cells_in_flight, at least one index a
+ * run (an index has at most DLIOM_NN_MAX_CELLS cells, so a run's positions fit an int).  A cell run is one memset, one
+ * launch that counts, ONE exclusive sum over the concatenation of the run's cell arrays, and one launch that scatters and
+ * writes each index's own cell_start, the scan's value minus its value at the index's first cell.  Runs add launches,
+ * never read-backs.  (A launch holds at most 2^30 lanes; a chunk of very many very long clouds splits its launches by
+ * slots.)  ONE stream synchronisation ends a chunk: after it the descriptor table is free for the next chunk and the
+ * clouds are the caller's again.  read_backs == synchronizations == chunks, and cell_runs is the sum over the chunks.  The
+ * work space is one growable block on the context, kept until the context is destroyed: the descriptors and the box words
+ * before the read-back; the descriptors, a cell a point (4 bytes) and the populations, cursors and scan of the largest
+ * cell run after it, sized exactly (scratch_bytes: the larger of the two over the chunks).
+ *
+ * Refusals, all before anything runs (DLIOM_ERR_INVALID_ARGUMENT, no read-back or synchronisation counted on the context):
+ * a NULL context or out; NULL clouds with count > 0; count < 0; options that dliom_nn_index_create refuses (NULL: the
+ * defaults, one set for all); limits outside their ranges or reserved != 0; a NULL cloud, a cloud of another context, an
+ * empty cloud, a cloud above DLIOM_NN_MAX_POINTS.  count == 0 succeeds and launches nothing.  A HIP or allocation failure
+ * fails the whole call, destroys what was built and leaves every out[i] NULL.  There is no per-index status. */
+#define DLIOM_NN_INDEX_BATCH_MAX_INDICES 256
+typedef struct dliom_nn_index_batch_limits {
+  int max_indices_in_flight;      /* 1 .. DLIOM_NN_INDEX_BATCH_MAX_INDICES; default 64 */
+  int reserved;                   /* 0 */
+  int64_t max_points_in_flight;   /* 1 .. 2^30; default 64 * DLIOM_NDT_BATCH_DEFAULT_POINTS */
+  int64_t max_cells_in_flight;    /* 1 .. 2^30; default 2^26 */
+} dliom_nn_index_batch_limits;    /* NULL = the defaults, which dliom_nn_index_batch_default_limits() returns */
+typedef struct dliom_nn_index_batch_stats {
+  int64_t indices, chunks, cell_runs;
+  int64_t points, finite_points, cells;   /* summed over the indices */
+  int64_t read_backs;             /* polled read-backs of the call: one a chunk */
+  int64_t synchronizations;       /* stream synchronisations of the call: one a chunk */
+  int64_t max_in_flight;          /* the largest chunk, in indices */
+  int64_t scratch_bytes;          /* the largest chunk's device work space */
+  double box_ms, sort_ms, alloc_ms; /* descriptors, boxes and the read-back | the second upload, the cell runs and the
+                                     synchronisation | the grids' choice and the allocations; on the host's clock, only
+                                     while the context's profiling is on */
+} dliom_nn_index_batch_stats;
+int dliom_nn_index_batch_default_limits(dliom_nn_index_batch_limits* limits);
+int dliom_nn_index_create_batch(dliom_ctx* ctx, const dliom_cloud* const* clouds, int count,
+                                const dliom_nn_index_options* options /* may be NULL, one for all */,
+                                const dliom_nn_index_batch_limits* limits, dliom_nn_index** out /* count entries */,
+                                dliom_nn_index_batch_stats* stats /* may be NULL */);
+
 /* The tool's values (gen_ground_truth_by_ndt_match.cc:192-196): 30 m, 100 iterations, both epsilons 1e-6. */
 int dliom_icp_default_options(dliom_icp_options* options);
 /* Aligns `source` to the index's target from guess16.  aligned (may be NULL): the final p_i as a cloud of the context. */
