@@ -44,6 +44,7 @@
 #include <memory>
 #include <set>
 #include <string>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -3131,6 +3132,105 @@ class PcdWritingPointsProcessor : public PointsProcessor {
   internal::RecordWriter writer_;
   int64_t num_points_ = 0;
   bool has_colors_ = false;
+};
+
+// io/xyz_writing_points_processor.{h,cc}: "write_xyz".  The reference formats one point at a time through a
+// std::ostringstream; here the batch's text is made on the device (dliom.h "XYZ text of export batches": the same bytes)
+// and written with one Write.  The buffer holds DLIOM_XYZ_MAX_RECORD bytes a point, which one call never refuses.
+class XyzWriterPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "write_xyz";
+  XyzWriterPointsProcessor(std::unique_ptr<FileWriter> file_writer, PointsProcessor* next, Context* context = nullptr)
+      : next_(next), context_(context != nullptr ? context : Context::ForThisThread()), file_writer_(std::move(file_writer)) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:50-55
+    const int64_t n = internal::BatchSize(context_, *batch);
+    if (n > 0) {
+      internal::DeviceBatch* d = internal::EnsureOnDevice(context_, batch.get());
+      text_.resize(static_cast<size_t>(n) * DLIOM_XYZ_MAX_RECORD);
+      int64_t bytes = 0;
+      Check(dliom_points_batch_pack_xyz(d->batch, text_.data(), static_cast<int64_t>(text_.size()), &bytes),
+            "dliom_points_batch_pack_xyz");
+      internal::DeviceBatch::DownloadedBytes() += bytes;
+      if (!file_writer_->Write(reinterpret_cast<const char*>(text_.data()), static_cast<size_t>(bytes))) Fail("Write");
+    }
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override {  // .cc:37-48
+    if (!file_writer_->Close()) Fail("Close");  // "Closing XYZ file failed."
+    return internal::FlushLastStage(next_, "XYZ generation must be configured to occur after any stages that require multiple "
+                                           "passes.");
+  }
+
+ private:
+  static void Fail(const char* what) {
+    std::fprintf(stderr, "Check failed: file_writer->%s\n", what);
+    std::abort();
+  }
+  PointsProcessor* const next_;
+  Context* const context_;
+  std::unique_ptr<FileWriter> file_writer_;
+  std::vector<uint8_t> text_;
+};
+
+// io/counting_points_processor.{h,cc}: "dump_num_points".  A batch in HBM is asked for its size; nothing is downloaded.
+class CountingPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "dump_num_points";
+  explicit CountingPointsProcessor(PointsProcessor* next, Context* context = nullptr)
+      : next_(next), context_(context != nullptr ? context : Context::ForThisThread()) {}
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:37-40
+    num_points_ += internal::BatchSize(context_, *batch);
+    next_->Process(std::move(batch));
+  }
+  FlushResult Flush() override {  // .cc:42-55
+    switch (next_->Flush()) {
+      case FlushResult::kFinished:
+        std::fprintf(stderr, "Processed %lld and finishing.\n", static_cast<long long>(num_points_));
+        return FlushResult::kFinished;
+      case FlushResult::kRestartStream:
+        std::fprintf(stderr, "Processed %lld and restarting stream.\n", static_cast<long long>(num_points_));
+        num_points_ = 0;
+        return FlushResult::kRestartStream;
+    }
+    std::abort();  // LOG(FATAL)
+  }
+  int64_t num_points() const { return num_points_; }  // (not in the reference, which only logs it)
+
+ private:
+  PointsProcessor* const next_;
+  Context* const context_;
+  int64_t num_points_ = 0;
+};
+
+// io/frame_id_filtering_points_processor.{h,cc}: "frame_id_filter".  Whole batches are passed on or dropped by their
+// frame_id; the points, wherever they are, are not touched.
+class FrameIdFilteringPointsProcessor : public PointsProcessor {
+ public:
+  constexpr static const char* kConfigurationFileActionName = "frame_id_filter";
+  FrameIdFilteringPointsProcessor(const std::unordered_set<std::string>& keep_frame_ids,
+                                  const std::unordered_set<std::string>& drop_frame_ids, PointsProcessor* next)
+      : keep_frame_ids_(keep_frame_ids), drop_frame_ids_(drop_frame_ids), next_(next) {
+    if (keep_frame_ids.empty() == drop_frame_ids.empty()) {  // CHECK_NE (.cc:52-54)
+      std::fprintf(stderr, "Check failed: You have to specify exactly one of the `keep_frames` property or the `drop_frames` "
+                           "property, but not both at the same time.\n");
+      std::abort();
+    }
+  }
+
+  void Process(std::unique_ptr<PointsBatch> batch) override {  // .cc:57-63
+    if ((!keep_frame_ids_.empty() && keep_frame_ids_.count(batch->frame_id)) ||
+        (!drop_frame_ids_.empty() && !drop_frame_ids_.count(batch->frame_id))) {
+      next_->Process(std::move(batch));
+    }
+  }
+  FlushResult Flush() override { return next_->Flush(); }  // .cc:65-67
+
+ private:
+  const std::unordered_set<std::string> keep_frame_ids_;
+  const std::unordered_set<std::string> drop_frame_ids_;
+  PointsProcessor* const next_;
 };
 
 // io/coloring_points_processor.{h,cc}: "color_points".  On a batch in HBM the colour is set there; on host vectors it

@@ -697,6 +697,10 @@ class PointCloud:
         """dliom_cloud_bounds -> (max_norm np.float32, abs_max float32[3]; a negative component: unknown)."""
         return _cloud_bounds(self._L, self.h)
 
+    def pack_xyz(self, capacity=None, fill=0):
+        """PointsBatch.pack_xyz of the cloud's points (dliom_cloud_pack_xyz)."""
+        return _pack_xyz(self._L.dliom_cloud_pack_xyz, self.h, capacity, fill)
+
     def download(self, pose7=None):
         """The points, packed xyz; pose7 (float [t, q]): sensor::TransformPointCloud(cloud, pose) applied on the device."""
         out = np.zeros((self.n, 3), dtype=np.float32)
@@ -1044,6 +1048,15 @@ class PointsBatch:
                                                _p(out, C.POINTER(C.c_uint8)), len(out), C.byref(n)), "dliom_points_batch_pack")
         return out, int(n.value)
 
+    def pack_xyz_size(self):
+        """The size of the batch's XYZ text in bytes (one read-back)."""
+        return _pack_xyz_size(self._L.dliom_points_batch_pack_xyz, self.h)
+
+    def pack_xyz(self, capacity=None, fill=0):
+        """The XYZ writer's text ("x y z\\n" a point, every float as '%.6g') -> uint8 array of `capacity` bytes (default:
+        exactly the size) pre-filled with `fill`, and the number of bytes written."""
+        return _pack_xyz(self._L.dliom_points_batch_pack_xyz, self.h, capacity, fill)
+
     def close(self):
         if getattr(self, "h", None):
             self._L.dliom_points_batch_destroy(self.h)
@@ -1099,6 +1112,36 @@ def ply_header(with_colors, with_intensities, num_points):
 def pcd_header(with_colors, num_points):
     """WriteBinaryPcdHeader (io/pcd_writing_points_processor.cc:35-57) -> bytes."""
     return _text(lambda b, c, n: load_library().dliom_pcd_header(int(with_colors), int(num_points), b, c, n))
+
+
+SYMBOLS += [
+    ("dliom_float_text", C.c_int, [C.c_float, C.c_char_p, _i32p]),
+    ("dliom_points_batch_pack_xyz", C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_int64, _i64p]),
+    ("dliom_cloud_pack_xyz", C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_int64, _i64p]),
+]
+XYZ_MAX_RECORD = 39  # DLIOM_XYZ_MAX_RECORD: "-1.17549e-38" three times, two spaces, one newline
+
+
+def float_text(value):
+    """What `std::ostream << std::setprecision(6) << float` writes for np.float32(value) -> bytes (dliom_float_text; host)."""
+    buffer = C.create_string_buffer(16)
+    n = C.c_int32()
+    _check(load_library().dliom_float_text(C.c_float(np.float32(value)), buffer, C.byref(n)), "dliom_float_text")
+    return buffer.raw[:n.value]
+
+
+def _pack_xyz_size(entry, handle):
+    n = C.c_int64()
+    _check(entry(handle, None, 0, C.byref(n)), "pack_xyz")
+    return int(n.value)
+
+
+def _pack_xyz(entry, handle, capacity, fill):
+    size = _pack_xyz_size(entry, handle) if capacity is None else int(capacity)
+    out = np.full(size, fill, dtype=np.uint8)
+    n = C.c_int64()
+    _check(entry(handle, _p(out, C.POINTER(C.c_uint8)), len(out), C.byref(n)), "pack_xyz")
+    return out, int(n.value)
 
 
 KERNEL_PG_HITS, KERNEL_PG_RAYS, KERNEL_PG_CLEAR = 6, 7, 8

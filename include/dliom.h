@@ -867,6 +867,40 @@ int dliom_points_batch_pack(const dliom_points_batch* batch, int format, int wit
 int dliom_ply_header(int with_colors, int with_intensities, int64_t num_points, char* buffer, int64_t capacity, int64_t* length);
 int dliom_pcd_header(int with_colors, int64_t num_points, char* buffer, int64_t capacity, int64_t* length);
 
+/* ---- XYZ text of export batches (the pipeline action "write_xyz"; io/xyz_writing_points_processor.cc:13-20) ----
+ * Text of a float.  What `std::ostream << std::setprecision(6) << float` writes under glibc / libstdc++, which is
+ * printf("%.6g") of the value promoted to double; at most 12 characters ("-0.000123456", "-1.17549e-38").
+ *   zero       "0", and "-0" with the sign bit set
+ *   infinity   "inf", "-inf"
+ *   NaN        "nan", and "-nan" with the sign bit set (the payload does not show)
+ *   otherwise  an optional '-', then the six significant decimal digits D (10^5 <= D < 10^6) and the decimal exponent X
+ *              of the float's EXACT value v: D = v / 10^(X - 5) rounded to the nearest integer, a tie to the even one --
+ *              so 1000.125f is "1000.12", 1.015625f "1.01562", 100000.5f "100000" and 100001.5f "100002".  A D that
+ *              rounds up to 10^6 is 10^5 with X one larger (999999.5f is "1e+06").
+ *              -4 <= X < 6: fixed notation, the decimal point behind digit X (in front of -X - 1 zeros and "0." for
+ *              X < 0), trailing zeros of the fraction and a bare '.' removed ("100", "0.0001", "2.5").
+ *              else: d[.ddddd]e+XX or e-XX, trailing zeros and a bare '.' removed, two exponent digits ("1e+06",
+ *              "1.17549e-38"; |X| <= 45).
+ * The device and dliom_float_text run ONE integer-only formatter (csrc/float_text.h): no floating-point rounding decides
+ * a digit, and the device's bytes equal the host's for every bit pattern.  No locale: the point is '.'.
+ *
+ * Record of a point.  x, ' ', y, ' ', z, '\n': 6 to DLIOM_XYZ_MAX_RECORD bytes.  Intensities and colours are ignored, as
+ * the reference ignores them, and nothing about the batch changes.
+ *
+ * dliom_points_batch_pack_xyz / dliom_cloud_pack_xyz follow dliom_points_batch_pack's conventions: *num_bytes is always
+ * the exact size of the text; bytes NULL: the size only (one read-back); capacity < *num_bytes: DLIOM_ERR_CAPACITY and
+ * nothing written; else exactly *num_bytes bytes are written (two host synchronisations: the size, then the download).
+ * An empty batch gives DLIOM_OK and 0 bytes without touching the device.  capacity >= DLIOM_XYZ_MAX_RECORD * n NEVER
+ * returns DLIOM_ERR_CAPACITY: a caller that brings such a buffer needs one call only.  Byte offsets into the text are
+ * 64-bit on the host and on the device, so no size a batch can have (n <= 2^31 - 1) wraps; the scratch holds
+ * min(capacity, DLIOM_XYZ_MAX_RECORD * n) bytes of text, and a batch too large for the device's memory fails with
+ * DLIOM_ERR_HIP.  NULL batch / cloud / num_bytes and a negative capacity: DLIOM_ERR_INVALID_ARGUMENT. */
+#define DLIOM_XYZ_MAX_RECORD 39
+/* Host only.  buffer takes the characters (no terminator), *length their number (<= 12).  NULL: refused. */
+int dliom_float_text(float value, char buffer[16], int32_t* length);
+int dliom_points_batch_pack_xyz(const dliom_points_batch* batch, uint8_t* bytes, int64_t capacity, int64_t* num_bytes);
+int dliom_cloud_pack_xyz(const dliom_cloud* cloud, uint8_t* bytes, int64_t capacity, int64_t* num_bytes);
+
 /* ---- 2D probability grid of the export pipeline (the actions "write_probability_grid" and "write_ros_map") ----
  * io::ProbabilityGridPointsProcessor (io/probability_grid_points_processor.{h,cc}) and
  * cartographer_ros::RosMapWritingPointsProcessor (ros_map_writing_points_processor.cc:52-94, ros_map.cc:21-47) insert
