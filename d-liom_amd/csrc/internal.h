@@ -173,6 +173,7 @@ struct dliom_ctx {
   bool hist_expect_big = true;  // the previous cloud had height slices above 4096 points (rotational_histogram.hip)
   int hist_poll_us = 150;       // poll window of the histogram's completion word: twice what the previous histogram took
   std::chrono::steady_clock::time_point hist_enqueued_at;  // ... measured from its enqueue
+  int match_poll_us = 150;      // poll window of an RTCSM3D match's read-back: twice what the previous match's wait took
   // the big slices' kernels (one workgroup per slice, a few hundred microseconds) run on a stream of their own beside the
   // small slices' kernel (256 workgroups): created with the first histogram that needs them
   hipStream_t hist_big_stream = nullptr;
@@ -446,12 +447,24 @@ int timed_cloud_origin_index(const dliom_timed_cloud* cloud, bool* has, const fl
 int std_sort_order_enqueue(dliom_ctx* ctx, const float* d_keys, int n, const int** d_order, const int** d_status);
 // sequential_sums.hip: the reference's sequential `score += probability` float sums, bit-identical.
 // Launches the kernels for `count` candidates whose indices are in d_list (c -> translation c / R, rotation c % R):
-// method 0 = one lane replays the loop, 1 = element scan, 2 = chunk scan.  Methods 1 and 2 need the 15-bit values of a
-// candidate in LDS (n <= 65536) and fall back to method 0 beyond.  `scratch` receives values / chunk sums / chunk
+// method 0 = one lane replays the loop, 1 = element scan, 2 = chunk scan.  Methods 1 and 2 handle n <= 65536 (the values of a
+// candidate in LDS, a chunk per thread) and fall back to method 0 beyond.  `scratch` receives values / chunk sums / chunk
 // functions; d_count != nullptr: the kernels read the live candidate count on the device.
+// `readback` (null: none, the sums stay on the device): the last kernel's blocks write the sums' read-back themselves --
+// block k its list word and its sum, the last block to arrive (blocks beyond *d_count arrive too) the count pair, the
+// error word and the completion word, which the caller polls (wait_done); no gather launch behind the sums.
+struct SumReadback {
+  unsigned* dst = nullptr;             // page-locked: [ctrs[0], ctrs[1] | list[slots] | sums[slots] | error word]
+  const unsigned* ctrs = nullptr;      // device: the pair in front, ctrs[1] the live count
+  const unsigned* err_word = nullptr;  // device, may be null: the word behind the sums is left alone then
+  unsigned* arrivals = nullptr;        // device, zero on entry; the last block leaves it zero again
+  unsigned* done_word = nullptr;       // page-locked completion word
+  unsigned done_seq = 0;
+  unsigned slots = 0;                  // >= count
+};
 int launch_sequential_sums(dliom_ctx* ctx, int method, const GridView& gv, const dliom_cloud& cloud, const float4* d_rot,
                            int R, const float* d_trans, const unsigned* d_list, const unsigned* d_count, unsigned count,
-                           DevBuf* scratch, float* d_ksums);
+                           DevBuf* scratch, float* d_ksums, const SumReadback* readback = nullptr);
 // The method the library itself uses for a cloud of num_points: the serial replay up to 1 024 points, else the chunk scan
 int sequential_sum_method(int64_t num_points);
 // The sums under k explicit float poses (x, y, z, qw, qx, qy, qz), read back into `sums`

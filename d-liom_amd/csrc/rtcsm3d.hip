@@ -25,6 +25,7 @@
 //   host   score = sum / N * exp(-(|t| wt + angle wr)^2) as the reference computes it; first
 //          strictly greater score in generation order wins.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +39,7 @@
 #include "device_common.h"
 #include "host_math.h"
 #include "probability_values.h"
+#include "rtcsm_bounds.h"
 #include "rtcsm_candidates.h"
 #include "score_box.h"
 
@@ -384,35 +386,8 @@ struct BoundParams {
   int n_pad;       // padding points, each of which added exactly 1 to every sum
   int R, T;
   int r_first, r_last;  // rotations owned by this shard
+  SeqSumBoundTable err;  // seq_sum_error_bound(n, U) per binade of U (rtcsm_bounds.h), filled on the host for this n
 };
-
-// Upper bound of the accumulated rounding error of the reference's sequential float sum.
-// Each addition is off by at most half an ulp of its result (round to nearest) and the partial
-// sums s_m are monotone, so the error after m additions is <= m 2^-24 s_m; with every addend
-// <= 0.9000001 this gives s_m <= 0.9000001 m / (1 - m 2^-24) <= 0.93 m for m <= 2^19.  Together
-// with s_m <= U (the final sum's upper bound) the (i+1)-th result is <= min(0.93 (i+1), U).
-__device__ double seq_sum_error_bound(int n, double U) {
-  double err = 0.0;
-  long long i = 0;  // indices [0, i) are already accounted for
-  // binade k: results in [2^k, 2^(k+1)) have ulp 2^(k-23).  Index i (the (i+1)-th addition) has
-  // its result bounded by B_i = min(0.93 (i+1), U).
-  for (int k = -4; k < 64 && i < n; ++k) {
-    const double top = ldexp(1.0, k + 1);
-    long long last;  // indices [i, last) are charged this binade's ulp
-    if (U < top) {
-      last = n;  // the cap keeps every remaining result below `top`
-    } else {
-      // 0.93 (idx+1) < top  <=>  idx + 1 < top / 0.93 ; one index fewer guards the division's rounding
-      last = static_cast<long long>(floor(top / 0.93)) - 1;
-      if (last > n) last = n;
-    }
-    if (last > i) {
-      err += 0.5 * ldexp(1.0, k - 23) * static_cast<double>(last - i);
-      i = last;
-    }
-  }
-  return err;
-}
 
 __device__ __forceinline__ float next_up(float f) { return __uint_as_float(__float_as_uint(f) + 1u); }
 __device__ __forceinline__ float next_down(float f) {
@@ -435,7 +410,7 @@ __global__ void rtcsm_bounds_kernel(const unsigned long long* __restrict__ sums,
   const double slack = p.delta * p.n + 1e-9 * mid;
   double sum_lo = mid - slack, sum_hi = mid + slack;
   const double U = sum_hi * (1.0 + 1.0 / 32.0);
-  const double e = seq_sum_error_bound(p.n, U);
+  const double e = p.err.err[seq_sum_bound_index(U)];  // = seq_sum_error_bound(p.n, U), which sees U's binade alone
   if (sum_hi + e > U || p.n > (1 << 19)) {  // bound not applicable: keep the candidate
     flo = 0.f;
     fhi = 3.0e38f;
@@ -1238,8 +1213,8 @@ static int match_begin(dliom_ctx* ctx, const dliom_rtcsm_options* o, const doubl
   float* d_lo = reinterpret_cast<float*>(bb);
   st->d_hi = reinterpret_cast<float*>(bb + bytes_f);
   st->d_list = reinterpret_cast<unsigned*>(bb + 2 * bytes_f);
-  st->d_ctrs = reinterpret_cast<unsigned*>(bb + 3 * bytes_f);  // [0] best_lo bits, [1] count
-  const FillJob zero_ctrs{st->d_ctrs, 8, 0u};
+  st->d_ctrs = reinterpret_cast<unsigned*>(bb + 3 * bytes_f);  // [0] best_lo bits, [1] count, [2] arrivals of the read-back
+  const FillJob zero_ctrs{st->d_ctrs, 12, 0u};
   if (st->r_last <= st->r_first) DLIOM_TRY(fill_multi(ctx, &zero_ctrs, 1));
   if (st->r_last > st->r_first) {
     int64_t pad_processed = 0;
@@ -1259,6 +1234,7 @@ static int match_begin(dliom_ctx* ctx, const dliom_rtcsm_options* o, const doubl
     bp.T = T;
     bp.r_first = st->r_first;
     bp.r_last = st->r_last;
+    fill_seq_sum_bound_table(bp.n, &bp.err);
     const unsigned cblocks = static_cast<unsigned>((C + 255) / 256);
     const int span = ctx->begin_span(DLIOM_KERNEL_RTCSM_SELECT);
     hipLaunchKernelGGL(rtcsm_bounds_kernel, dim3(cblocks), dim3(256), 0, ctx->stream, st->d_sums,
@@ -1326,22 +1302,41 @@ static int match_finish(dliom_ctx* ctx, const unsigned* global_best_lo_bits, uin
     unsigned* h_ctrs = pinned_at<unsigned>(ctx, kPinMatchReadback);
     unsigned* h_list = h_ctrs + 2;
     float* h_sums = reinterpret_cast<float*>(h_ctrs + 2 + kSpecK);
-    auto rescore = [&](unsigned count, const unsigned* d_count, size_t list_offset) -> int {
+    auto rescore = [&](unsigned count, const unsigned* d_count, size_t list_offset, const SumReadback* readback) -> int {
       DLIOM_TRY(ctx->rescore.reserve(align256(static_cast<size_t>(count) * 4)));
       const int span = ctx->begin_span(DLIOM_KERNEL_RTCSM_RESCORE);
       const int s = launch_sequential_sums(ctx, sequential_sum_method(cloud.n), st->grid->view(), cloud, st->d.rot, R, st->d.trans,
-                                           st->d_list + list_offset, d_count, count, &ctx->misc, ctx->rescore.as<float>());
+                                           st->d_list + list_offset, d_count, count, &ctx->misc, ctx->rescore.as<float>(), readback);
       ctx->end_span(span);
       return s;
     };
-    DLIOM_TRY(rescore(kSpecK, st->d_ctrs + 1, 0));
-    // one read-back dispatch: [count pair | list | sums | box overflow word]
+    // the read-back [count pair | list | sums | box overflow word] is written by the last rescoring kernel itself
+    // (SumReadback, sequential_sums.hip): no gather launch behind it.  The chain in front of the completion word is the
+    // whole match, so the word is polled for twice as long as the previous match's wait took (150 us .. 4 ms).
     unsigned* h_err = h_ctrs + 2 + 2 * kSpecK;
     *h_err = 0u;
     const bool want_err = st->used_box && global_best_lo_bits == nullptr;
-    const GatherJob back[4] = {{st->d_ctrs, 2}, {st->d_list, kSpecK}, {ctx->rescore.p, kSpecK},
-                               {static_cast<char*>(ctx->box_error.p) + 4, 1}};
-    DLIOM_TRY(gather_and_wait(ctx, back, want_err ? 4 : 3, h_ctrs));
+    if (ctx->done_word != nullptr) {
+      SumReadback rb;
+      rb.dst = h_ctrs;
+      rb.ctrs = st->d_ctrs;
+      rb.err_word = want_err ? reinterpret_cast<const unsigned*>(static_cast<char*>(ctx->box_error.p) + 4) : nullptr;
+      rb.arrivals = st->d_ctrs + 2;
+      rb.done_word = ctx->done_word;
+      rb.done_seq = next_done_seq(ctx);
+      rb.slots = kSpecK;
+      DLIOM_TRY(rescore(kSpecK, st->d_ctrs + 1, 0, &rb));
+      const auto t0 = std::chrono::steady_clock::now();
+      const int s = wait_done(ctx, ctx->stream, ctx->done_word, rb.done_seq, ctx->match_poll_us);
+      const double took_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+      ctx->match_poll_us = static_cast<int>(std::min(4000.0, std::max(150.0, 2.0 * took_us)));
+      DLIOM_TRY(s);
+    } else {  // no completion word (allocation failed at creation): a gather and a synchronise
+      DLIOM_TRY(rescore(kSpecK, st->d_ctrs + 1, 0, nullptr));
+      const GatherJob back[4] = {{st->d_ctrs, 2}, {st->d_list, kSpecK}, {ctx->rescore.p, kSpecK},
+                                 {static_cast<char*>(ctx->box_error.p) + 4, 1}};
+      DLIOM_TRY(gather_and_wait(ctx, back, want_err ? 4 : 3, h_ctrs));
+    }
     {
       bool overflow = false;
       DLIOM_TRY(box_overflowed(ctx, *h_err, &overflow));
@@ -1363,7 +1358,7 @@ static int match_finish(dliom_ctx* ctx, const unsigned* global_best_lo_bits, uin
     ksums.assign(h_sums, h_sums + first);
     if (K > kSpecK) {  // the rest, exactly sized
       const unsigned rest = K - kSpecK;
-      DLIOM_TRY(rescore(rest, nullptr, kSpecK));
+      DLIOM_TRY(rescore(rest, nullptr, kSpecK, nullptr));
       list.resize(K);
       ksums.resize(K);
       DLIOM_HIP_TRY(hipMemcpyAsync(list.data() + kSpecK, st->d_list + kSpecK, static_cast<size_t>(rest) * 4,

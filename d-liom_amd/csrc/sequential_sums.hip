@@ -8,6 +8,21 @@
 //   1  element scan, binade by binade (rtcsm_rescore_values_kernel + rtcsm_rescore_scan_kernel)
 //   2  chunk functions + binade-wise scan (... + rtcsm_rescore_chunk_fns_kernel + rtcsm_rescore_chunk_scan_kernel)
 // The kernels keep the rtcsm_rescore_ names they had in rtcsm3d.hip: committed kernel statistics refer to them.
+//
+// Method 2's scan kernel walks the sum binade by binade on TWO levels, all of it on wave 0 and without a block barrier:
+// a chunk is 64 additions with a ParityFn per binade the sum can be in while it crosses the chunk (ChunkFns, at most two),
+// a super-chunk is 64 consecutive chunks (4 096 additions) whose ParityFn for a binade is the composition of its chunks'
+// functions in chunk order -- defined only where all 64 chunks carry one (at most two binades again; wave w builds
+// super-chunk w with one wave scan per binade, behind the kernel's first barrier).  Composition is associative, so a pass
+// that skips whole super-chunks (lane <-> super-chunk), opens the one that halts it lane <-> chunk and the crossing chunk
+// lane <-> element ends in the same (m, e, i0) as one that composes the chunks one by one.  Whatever the one-wave walk does
+// not handle -- a chunk without a function for the binade in front of the crossing, i.e. a violated bound -- is left
+// with its exact state to the block's pass (sixteen waves, chunk per thread; sh_force_serial opens such chunks element
+// by element), which is also what methods 0 and 1 are compared with.
+//
+// A client that wants the sums on the host (the real-time matcher) passes a SumReadback: the blocks of the last kernel
+// then write their own list word and sum into the page-locked block, and the last block to arrive -- blocks beyond the
+// live count arrive too -- adds the count pair, the box overflow word and the completion word.  Nobody waits for anybody.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -16,6 +31,27 @@
 #include "probability_values.h"
 
 namespace dliom {
+
+// One thread of every block of a sum's last kernel: its own list word and sum into the read-back block (has_sum: the block
+// is below the live count), then the arrival; the last one adds what no block owns and releases the host.  The counter is
+// re-armed for the next launch, as csm_final_reduce_kernel does.
+__device__ __forceinline__ void publish_sum(const SumReadback& rb, const unsigned* __restrict__ list, bool has_sum, float sum) {
+  if (rb.dst == nullptr) return;
+  const unsigned k = blockIdx.x;
+  if (has_sum && k < rb.slots) {
+    rb.dst[2u + k] = list[k];
+    rb.dst[2u + rb.slots + k] = __float_as_uint(sum);
+  }
+  __threadfence_system();
+  if (atomicAdd(rb.arrivals, 1u) == gridDim.x - 1u) {
+    *rb.arrivals = 0u;
+    rb.dst[0] = rb.ctrs[0];
+    rb.dst[1] = rb.ctrs[1];
+    if (rb.err_word != nullptr) rb.dst[2u + 2u * rb.slots] = *rb.err_word;
+    __threadfence_system();
+    *reinterpret_cast<volatile unsigned*>(rb.done_word) = rb.done_seq;
+  }
+}
 
 // ---------------------------------------------------------------------------------- kernel C
 // One workgroup per surviving candidate.  Waves 1-3 turn tiles of points (INPUT order) into
@@ -28,9 +64,12 @@ __global__ __launch_bounds__(256) void rtcsm_rescore_kernel(
     GridView g, const float* __restrict__ px, const float* __restrict__ py,
     const float* __restrict__ pz, int n, const float4* __restrict__ rot, int R,
     const float* __restrict__ trans, const unsigned* __restrict__ list, const unsigned* __restrict__ count,
-    float k_scale, float k_offset, float k_unknown, float* __restrict__ sums) {
+    float k_scale, float k_offset, float k_unknown, float* __restrict__ sums, SumReadback rb) {
   __shared__ float4 tile[2][kChainTile / 4];
-  if (count != nullptr && blockIdx.x >= *count) return;
+  if (count != nullptr && blockIdx.x >= *count) {
+    if (threadIdx.x == 0) publish_sum(rb, list, false, 0.f);
+    return;
+  }
   const unsigned c = list[blockIdx.x];
   const int j = static_cast<int>(c / static_cast<unsigned>(R));
   const int r = static_cast<int>(c % static_cast<unsigned>(R));
@@ -73,7 +112,10 @@ __global__ __launch_bounds__(256) void rtcsm_rescore_kernel(
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) sums[blockIdx.x] = s;
+  if (threadIdx.x == 0) {
+    sums[blockIdx.x] = s;
+    publish_sum(rb, list, true, s);
+  }
 }
 
 // Parallel, bit-exact evaluation of the SAME sequential float sum (one workgroup of 1024 threads
@@ -394,33 +436,55 @@ __device__ __forceinline__ PFn2 lane_of(const PFn2& f, int l) {  // l uniform
 }
 __device__ __forceinline__ unsigned apply2(const PFn2& f, unsigned parity) { return (parity ? f.b : f.a) & 0x7FFFFFFFu; }
 
-// Round 5 form: thread t <-> chunk t for the whole kernel (its ChunkFns are loaded ONCE, beside the copy of the values
-// into LDS, instead of a dependent 32-byte global load per pass), the first 256 additions replayed by wave 0 out of
-// registers with v_readlane (one thread chasing 256 dependent LDS reads was a fifth of the kernel), the partial chunk a
-// pass resumes in and the chunk the sum leaves the binade in opened by the WAVE that owns them (no hand-over through
-// LDS), three barriers a pass.  Same arithmetic, same result bits as before (test_sequential_sum_kernels_bit_exact
-// compares it with the element scan and the serial replay).
+// Thread t <-> chunk t for the whole kernel: its ChunkFns are loaded ONCE, into registers for the block's passes and into
+// LDS for wave 0's walk (the file's header: chunks, super-chunks, elements).  The first 256 additions are replayed by
+// wave 0 out of registers with v_readlane.  The block's pass -- the fallback -- opens the partial chunk it resumes in and
+// the chunk the sum leaves the binade in by the WAVE that owns them, three barriers a pass.  Same arithmetic, same
+// result bits on either path (test_sequential_sum_kernels_bit_exact and tests/test_sequential_sum_walk.py compare them
+// with the element scan and the serial replay).
 __global__ __launch_bounds__(kScanThreads) void rtcsm_rescore_chunk_scan_kernel(
     const unsigned short* __restrict__ values, int n, int n_stride, float k_scale, float k_offset, float k_unknown,
-    const unsigned* __restrict__ count, const ChunkFns* __restrict__ fns, int num_chunks, float* __restrict__ sums) {
-  extern __shared__ unsigned short lds_value[];  // n_stride grid values (15 bit), input order
-  if (count != nullptr && blockIdx.x >= *count) return;
+    const unsigned* __restrict__ count, const ChunkFns* __restrict__ fns, int num_chunks, float* __restrict__ sums,
+    const unsigned* __restrict__ list, SumReadback rb) {
+  if (count != nullptr && blockIdx.x >= *count) {
+    if (threadIdx.x == 0) publish_sum(rb, list, false, 0.f);
+    return;
+  }
   __shared__ PFn2 wave_total[kScanThreads / 64];
   __shared__ unsigned sh_m, sh_e, sh_i0, sh_cross_t, sh_total, sh_mismatch_t, sh_force_serial;
-  constexpr int kEarlyChunks = 128;            // the functions of the first chunks, for wave 0's own passes (below)
-  __shared__ ChunkFns early_fns[kEarlyChunks];
+  // every chunk's functions for wave 0's walk: {e0's PFn2, e1's PFn2} and e0 | e1 << 8 (0xFF: absent; a binade is < 32)
+  __shared__ uint4 lds_fn[kScanThreads];
+  __shared__ unsigned lds_fn_e[kScanThreads];
+  // super-chunk w = the 64 chunks of wave w: its function for the (at most two) binades that ALL of its chunks carry
+  __shared__ unsigned super_e[kScanThreads / 64][2];
+  __shared__ PFn2 super_fn[kScanThreads / 64][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const ChunkFns none{0xFFFFFFFFu, 0u, 0u, 0u, 0xFFFFFFFFu, 0u, 0u, 0u};
   const ChunkFns cf = tid < num_chunks ? fns[static_cast<size_t>(blockIdx.x) * num_chunks + tid] : none;  // in flight during the copy
-  if (tid < kEarlyChunks) early_fns[tid] = cf;
+  // The values stay in global memory: the walk opens two or three chunks a pass, and reading those 128 bytes from L2
+  // is cheaper than copying up to 128 KB into LDS first (measured at 65 536 points: 25.4 -> 23.2 us a survivor).
+  const unsigned short* __restrict__ vals = values + static_cast<size_t>(blockIdx.x) * n_stride;
   {
-    const uint4* src = reinterpret_cast<const uint4*>(values + static_cast<size_t>(blockIdx.x) * n_stride);
-    uint4* dst = reinterpret_cast<uint4*>(lds_value);
-    for (int i = tid; i < n_stride / 8; i += kScanThreads) dst[i] = src[i];
+    const PFn2 cf0{cf.s00 | ((cf.pp0 & 1u) << 31), cf.s01 | ((cf.pp0 >> 1) << 31)};
+    const PFn2 cf1{cf.s10 | ((cf.pp1 & 1u) << 31), cf.s11 | ((cf.pp1 >> 1) << 31)};
+    lds_fn[tid] = make_uint4(cf0.a, cf0.b, cf1.a, cf1.b);
+    lds_fn_e[tid] = (cf.e0 & 0xFFu) | ((cf.e1 & 0xFFu) << 8);
+    // a binade that all 64 chunks carry is one of the first chunk's two (all sixteen waves are whole here: the scans are DPP)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const unsigned E = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(k == 0 ? cf.e0 : cf.e1), 0));
+      const bool has0 = cf.e0 == E, has = E != 0xFFFFFFFFu && (has0 || cf.e1 == E);
+      const PFn2 total = lane_of(wave_inclusive_scan2(has ? (has0 ? cf0 : cf1) : pfn2_identity()), 63);
+      const bool all = __ballot(has) == ~0ull;
+      if (lane == 0) {
+        super_e[wave][k] = all ? E : 0xFFFFFFFFu;
+        super_fn[wave][k] = total;
+      }
+    }
   }
   __syncthreads();
   auto prob = [&](unsigned v) { return v == 0u ? k_unknown : static_cast<float>(static_cast<int>(v)) * k_scale + k_offset; };
-  auto fixed = [&](unsigned i) { return fixed_of_value(lds_value[i], k_scale, k_offset, k_unknown); };
+  auto fixed = [&](unsigned i) { return fixed_of_value(vals[i], k_scale, k_offset, k_unknown); };
   const int n0 = min(n, kSerialPrefix);
   if (wave == 0) {
     float s = 0.f;
@@ -428,20 +492,22 @@ __global__ __launch_bounds__(kScanThreads) void rtcsm_rescore_chunk_scan_kernel(
       // element k * 64 + l sits in lane l's register k: the 256 sequential additions read them with v_readlane
       float pv[kSerialPrefix / 64];
 #pragma unroll
-      for (int k = 0; k < kSerialPrefix / 64; ++k) pv[k] = prob(lds_value[k * 64 + lane]);
+      for (int k = 0; k < kSerialPrefix / 64; ++k) pv[k] = prob(vals[k * 64 + lane]);
 #pragma unroll
       for (int k = 0; k < kSerialPrefix / 64; ++k)
 #pragma unroll
         for (int l = 0; l < 64; ++l) s += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pv[k]), l));
     } else {
-      for (int i = 0; i < n0; ++i) s += prob(lds_value[i]);
+      for (int i = 0; i < n0; ++i) s += prob(vals[i]);
     }
-    // ---- the first binades by wave 0 ALONE (round 5).  The sum doubles from binade to binade, so the early passes
-    // cover a few dozen chunks each -- and used to cost what the late ones cost, three barriers of sixteen waves (4.4 us
-    // a pass, nine passes).  While a pass's window fits 64 chunks (lane l <-> chunk c0 + l, functions out of LDS) it
-    // needs no other wave: the same steps as the block's pass below on wave-uniform state, no barrier.  Anything
-    // unusual (a chunk without a function for this binade in front of the crossing, a window beyond the early chunks)
-    // leaves the pass to the block.
+    // ---- every binade by wave 0 ALONE.  The sum doubles from binade to binade, so the early passes cover a few dozen
+    // chunks each and the last ones tens of thousands of additions -- and a block pass costs three barriers of sixteen
+    // waves and a serial compose over the wave totals whatever its window (4.4 us a pass).  One step of the loop below
+    // opens up to 64 chunks from the one the walk resumes in (lane l <-> chunk c0 + l, functions out of LDS), up to the
+    // window's end or, if that is further, up to the next super-chunk boundary; from a boundary it skips whole
+    // super-chunks (lane s <-> super-chunk s) up to the first that crosses, has no function for the binade or is cut by
+    // the window's end, which the next step opens.  Every step leaves an exact (m, e, i0) further on, so a pass is a few
+    // steps of wave-uniform state.  A chunk without a function in front of the crossing leaves the pass to the block.
     const unsigned b0 = __float_as_uint(s);
     unsigned m = (b0 & 0x7FFFFFu) | 0x800000u, e = (b0 >> 23) - 123u, i0 = static_cast<unsigned>(n0);
     const PFn2 idw = pfn2_identity();
@@ -451,19 +517,22 @@ __global__ __launch_bounds__(kScanThreads) void rtcsm_rescore_chunk_scan_kernel(
       const unsigned c0 = i0 / kChunk;
       const unsigned i_lim = min(static_cast<unsigned>(n), ((i0 + window + kChunk - 1u) / kChunk) * kChunk);
       const unsigned last_chunk = (i_lim - 1u) / kChunk;
-      if (last_chunk - c0 >= 64u || last_chunk >= static_cast<unsigned>(kEarlyChunks)) break;  // the block's job
+      // chunks [c0, cend) in this step: the window's rest if 64 lanes reach it, else up to the super-chunk boundary
+      const unsigned cend = last_chunk - c0 < 64u ? last_chunk + 1u : ((c0 >> 6) + 1u) << 6;
       const unsigned c = c0 + static_cast<unsigned>(lane);
       const unsigned begin = max(i0, c * kChunk), end = min(i_lim, (c + 1u) * kChunk);
-      const bool in_window = begin < end;
+      const bool in_window = c < cend;  // <= last_chunk < num_chunks
+      const bool resume_partial = (i0 & (kChunk - 1u)) != 0u;
       PFn2 f = idw;
       bool mismatch = false;
-      if (in_window && lane != 0) {
-        const ChunkFns cw = early_fns[c];
-        if (cw.e0 == e) f = PFn2{cw.s00 | ((cw.pp0 & 1u) << 31), cw.s01 | ((cw.pp0 >> 1) << 31)};
-        else if (cw.e1 == e) f = PFn2{cw.s10 | ((cw.pp1 & 1u) << 31), cw.s11 | ((cw.pp1 >> 1) << 31)};
+      if (in_window && !(resume_partial && lane == 0)) {
+        const unsigned ce = lds_fn_e[c];
+        const uint4 cw = lds_fn[c];
+        if ((ce & 0xFFu) == e) f = PFn2{cw.x, cw.y};
+        else if ((ce >> 8) == e) f = PFn2{cw.z, cw.w};
         else mismatch = true;
       }
-      {  // the chunk the walk resumes in is partial: lane per element
+      if (resume_partial) {  // the chunk the walk resumes in is partial: lane per element
         const unsigned he = min(i_lim, (c0 + 1u) * kChunk);
         const unsigned i = i0 + static_cast<unsigned>(lane);
         const PFn2 h = wave_inclusive_scan2(i < he ? pack_fn(element_fn(fixed(i), e)) : idw);
@@ -479,9 +548,35 @@ __global__ __launch_bounds__(kScanThreads) void rtcsm_rescore_chunk_scan_kernel(
       const int cross_l = cross_mask != 0ull ? __ffsll(static_cast<long long>(cross_mask)) - 1 : 64;
       const int mism_l = mism_mask != 0ull ? __ffsll(static_cast<long long>(mism_mask)) - 1 : 64;
       if (mism_l < cross_l || (cross_l == 64 && mism_l != 64)) break;  // the block's pass knows how to open such chunks
-      if (cross_l == 64) {  // the cloud ended inside this binade
+      if (cross_l == 64) {  // no crossing in these chunks (lanes behind cend are the identity)
         m = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(mt_end), 63));
-        i0 = i_lim;
+        i0 = min(i_lim, cend * kChunk);
+        if (i0 >= i_lim) continue;  // the cloud ended inside this binade
+        // at a super-chunk boundary with window left: skip whole super-chunks.  One that the window's end cuts, one without
+        // a function for this binade and one the sum leaves the binade in halt the skip; the next step opens it.
+        const unsigned s_first = cend >> 6, s_last = last_chunk >> 6;
+        const bool whole_last = (last_chunk & 63u) == 63u;
+        const unsigned sc = static_cast<unsigned>(lane);
+        const bool active = sc >= s_first && sc <= s_last;  // s_last < kScanThreads / 64
+        PFn2 g = idw;
+        bool stop = active;
+        if (active && (sc < s_last || whole_last)) {
+          if (super_e[sc][0] == e) {
+            g = super_fn[sc][0];
+            stop = false;
+          } else if (super_e[sc][1] == e) {
+            g = super_fn[sc][1];
+            stop = false;
+          }
+        }
+        const PFn2 ginc = wave_inclusive_scan2(g);
+        const PFn2 gexc = wave_shift_right1(ginc);
+        const unsigned gp = m & 1u;
+        const unsigned g_start = m + apply2(gexc, gp), g_end = m + apply2(ginc, gp);
+        const unsigned long long halt_mask = __ballot(active && (stop || g_end >= (1u << 24)));
+        const int halt = halt_mask != 0ull ? __ffsll(static_cast<long long>(halt_mask)) - 1 : static_cast<int>(s_last) + 1;
+        m = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(g_start), halt));  // lane s_last + 1: the identity
+        i0 = min(i_lim, static_cast<unsigned>(halt) * (64u * kChunk));
         continue;
       }
       const unsigned cb = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(begin), cross_l));
@@ -612,7 +707,11 @@ __global__ __launch_bounds__(kScanThreads) void rtcsm_rescore_chunk_scan_kernel(
     }
     __syncthreads();  // (3) the next pass's state
   }
-  if (tid == 0) sums[blockIdx.x] = __uint_as_float(((sh_e + 123u) << 23) | (sh_m & 0x7FFFFFu));
+  if (tid == 0) {
+    const float sum = __uint_as_float(((sh_e + 123u) << 23) | (sh_m & 0x7FFFFFu));
+    sums[blockIdx.x] = sum;
+    publish_sum(rb, list, true, sum);
+  }
 }
 
 // ---------------------------------------------------------------------------------- host side
@@ -636,14 +735,16 @@ static ScratchLayout scratch_layout(size_t count, int n) {
 
 int launch_sequential_sums(dliom_ctx* ctx, int method, const GridView& gv, const dliom_cloud& cloud, const float4* d_rot,
                            int R, const float* d_trans, const unsigned* d_list, const unsigned* d_count, unsigned count,
-                           DevBuf* scratch, float* d_ksums) {
+                           DevBuf* scratch, float* d_ksums, const SumReadback* readback) {
+  const SumReadback rb = readback != nullptr ? *readback : SumReadback{};
   const float k_scale = kValueToProbabilityScale, k_offset = kValueToProbabilityOffset, k_unknown = kUnknownProbability;
   const int n = static_cast<int>(cloud.n);
   const int n_stride = (n + 7) & ~7;
   const size_t scan_lds = static_cast<size_t>(n_stride) * 2;
+  // method 1 holds a candidate's values in LDS and method 2 a chunk per thread: 65 536 points at most for either
   if (method == 0 || scan_lds > 128 * 1024 || count > 65535) {
     hipLaunchKernelGGL(rtcsm_rescore_kernel, dim3(count), dim3(256), 0, ctx->stream, gv, cloud.d_x, cloud.d_y, cloud.d_z, n,
-                       d_rot, R, d_trans, d_list, d_count, k_scale, k_offset, k_unknown, d_ksums);
+                       d_rot, R, d_trans, d_list, d_count, k_scale, k_offset, k_unknown, d_ksums, rb);
     DLIOM_HIP_TRY(hipGetLastError());
     return DLIOM_OK;
   }
@@ -660,8 +761,8 @@ int launch_sequential_sums(dliom_ctx* ctx, int method, const GridView& gv, const
   if (method == 2) {
     hipLaunchKernelGGL(rtcsm_rescore_chunk_fns_kernel, dim3((num_chunks + 3) / 4, count), dim3(256), 0, ctx->stream, d_values,
                        n, n_stride, k_scale, k_offset, k_unknown, d_count, d_chunk_sums, num_chunks, d_fns);
-    hipLaunchKernelGGL(rtcsm_rescore_chunk_scan_kernel, dim3(count), dim3(kScanThreads), scan_lds, ctx->stream, d_values, n,
-                       n_stride, k_scale, k_offset, k_unknown, d_count, d_fns, num_chunks, d_ksums);
+    hipLaunchKernelGGL(rtcsm_rescore_chunk_scan_kernel, dim3(count), dim3(kScanThreads), 0, ctx->stream, d_values, n,
+                       n_stride, k_scale, k_offset, k_unknown, d_count, d_fns, num_chunks, d_ksums, d_list, rb);
   } else {
     hipLaunchKernelGGL(rtcsm_rescore_scan_kernel, dim3(count), dim3(kScanThreads), scan_lds, ctx->stream, d_values, n, n_stride,
                        k_scale, k_offset, k_unknown, d_count, d_ksums);
