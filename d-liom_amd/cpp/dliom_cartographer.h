@@ -263,6 +263,240 @@ class Context {
   dliom_ctx* ctx_ = nullptr;
 };
 
+// The scans the D-LIOM fork keeps for its map cloud and its range-data file (cartographer_ros/map_builder_bridge.cc:591-607
+// range_data_local_all_), kept in HBM where the scan matcher left them (dliom.h "node clouds kept in HBM"), and the fork's
+// three per-point loops over them as batched device calls.  The static Host* members are the reference's loops, one
+// thread: the cross-check of the device calls and the baseline of tools/node_clouds_bench.py.
+namespace cartographer_ros {
+class NodeCloudCache {
+ public:
+  // msg.data of several PointCloud2 messages back to back: node nodes[i]'s is data[offsets[i], offsets[i + 1])
+  struct CloudData {
+    std::vector<uint8_t> data;
+    std::vector<int64_t> offsets{0};
+    std::vector<int64_t> nodes;
+  };
+  explicit NodeCloudCache(Context* context) : context_(context) {
+    Check(dliom_node_clouds_create(context->get(), &clouds_), "dliom_node_clouds_create");
+  }
+  ~NodeCloudCache() { dliom_node_clouds_destroy(clouds_); }
+  NodeCloudCache(const NodeCloudCache&) = delete;
+  NodeCloudCache& operator=(const NodeCloudCache&) = delete;
+  dliom_node_clouds* get() const { return clouds_; }
+  int64_t size() const { return static_cast<int64_t>(order_.size()); }
+
+  // MapBuilderBridge::OnLocalSlamResult with the scan still on the device: `returns` in the tracking frame and
+  // pose_to_local = opt_pose.cast<float>() (TransformRangeData on the way in), or already local and pose_to_local null.
+  // One kernel, nothing waited for.  Returns the node's index in the cache.
+  int64_t OnLocalSlamResult(int trajectory_id, int64_t time, const transform::Rigid3d& local_pose, const dliom_cloud* returns,
+                            const float* pose_to_local, const sensor::Vector3f& origin_in_local, const dliom_cloud* misses = nullptr) {
+    dliom_node_cloud_info info;
+    info.timestamp = time;
+    info.trajectory_id = trajectory_id;
+    info.node_index = 0;  // SerializeRangeData never sets it
+    const std::array<double, 7> pose = local_pose.ToArray();
+    std::copy(pose.begin(), pose.end(), info.local_pose7);
+    info.origin_in_local[0] = origin_in_local.x;
+    info.origin_in_local[1] = origin_in_local.y;
+    info.origin_in_local[2] = origin_in_local.z;
+    int64_t index = -1;
+    Check(dliom_node_clouds_add(clouds_, &info, returns, misses, pose_to_local, &index), "NodeCloudCache::OnLocalSlamResult");
+    by_trajectory_[trajectory_id].push_back(index);
+    order_.push_back(info);
+    return index;
+  }
+  // ... with the scan on the host, as the reference's callback receives it (two uploads)
+  int64_t OnLocalSlamResult(int trajectory_id, int64_t time, const transform::Rigid3d& local_pose,
+                            const sensor::RangeData& range_data_in_local) {
+    dliom_cloud *returns = nullptr, *misses = nullptr;
+    const sensor::PointCloud &r = range_data_in_local.returns, &m = range_data_in_local.misses;
+    Check(dliom_cloud_create(context_->get(), r.empty() ? nullptr : &r[0].x, static_cast<int64_t>(r.size()), &returns), "dliom_cloud_create");
+    Check(dliom_cloud_create(context_->get(), m.empty() ? nullptr : &m[0].x, static_cast<int64_t>(m.size()), &misses), "dliom_cloud_create");
+    const int64_t index = OnLocalSlamResult(trajectory_id, time, local_pose, returns, nullptr, range_data_in_local.origin, misses);
+    Check(dliom_ctx_synchronize(context_->get()), "dliom_ctx_synchronize");  // the kernel reads the two clouds
+    dliom_cloud_destroy(returns);
+    dliom_cloud_destroy(misses);
+    return index;
+  }
+
+  // MapBuilderBridge::SerializeRangeData's loop (:177-195): write(data, size) once a NodeRangeData message, trajectories in
+  // map order, a trajectory's nodes in insertion order.  The header and the framing stay with the caller's writer.
+  template <class WriteProto>
+  void SerializeRangeData(WriteProto&& write) const {
+    const std::vector<int64_t> nodes = NodesInMapOrder();
+    ForRuns(nodes, [&](int64_t first, int64_t count) {
+      std::vector<int64_t> offsets(static_cast<size_t>(count) + 1);
+      int64_t capacity = 0;  // the bound that needs no size query: one pass over the points, not two
+      for (int64_t i = first; i < first + count; ++i) {
+        int64_t returns = 0, misses = 0;
+        Check(dliom_node_clouds_info(clouds_, i, nullptr, &returns, &misses), "dliom_node_clouds_info");
+        capacity += DLIOM_NODE_RANGE_MAX_HEADER + DLIOM_NODE_RANGE_MAX_RECORD * (returns + misses);
+      }
+      std::vector<uint8_t> bytes(static_cast<size_t>(capacity));
+      Check(dliom_node_clouds_to_proto(clouds_, first, count, nullptr, bytes.data(), capacity, offsets.data(), nullptr), "SerializeRangeData");
+      for (int64_t i = 0; i < count; ++i) write(bytes.data() + offsets[i], static_cast<size_t>(offsets[i + 1] - offsets[i]));
+    });
+  }
+  // msg.data of the nodes [first, first + count) under num_poses float poses (shared, or node-major per node)
+  CloudData ToPointCloud2Data(int64_t first, int64_t count, const float* poses7, int num_poses, bool per_node) const {
+    CloudData out;
+    Append(first, count, poses7, num_poses, per_node, &out);
+    return out;
+  }
+  // Node::PublishFullMapCloud's loop (node.cc:334-351): every kept scan under local_to_map.cast<float>()
+  CloudData FullMapCloud(const transform::Rigid3d& local_to_map) const {
+    const std::array<float, 7> pose = transform::Rigid3f(local_to_map).ToArray();
+    CloudData out;
+    ForRuns(NodesInMapOrder(), [&](int64_t first, int64_t count) { Append(first, count, pose.data(), 1, false, &out); });
+    return out;
+  }
+  // pb_range_data_to_ros_cloud's loop (:153-186): global_pose * (local_pose.inverse() * p), both in float, for every kept
+  // scan whose timestamp node_table holds; the others are skipped (:157)
+  CloudData GlobalClouds(const std::map<int64_t, transform::Rigid3d>& node_table) const {
+    CloudData out;
+    std::vector<float> poses;
+    int64_t first = 0;
+    auto flush = [&](int64_t end) {
+      if (!poses.empty()) Append(first, end - first, poses.data(), 2, true, &out);
+      poses.clear();
+    };
+    for (int64_t i = 0; i < size(); ++i) {
+      const auto found = node_table.find(order_[static_cast<size_t>(i)].timestamp);
+      if (found == node_table.end()) {
+        flush(i);
+        continue;
+      }
+      if (poses.empty()) first = i;
+      const std::array<float, 7> local = transform::Rigid3f(transform::Rigid3d::FromArray(order_[static_cast<size_t>(i)].local_pose7)).ToArray();
+      const std::array<float, 7> global = transform::Rigid3f(found->second).ToArray();
+      float inverse[7];
+      Check(dliom_rigid3f_inverse(local.data(), inverse), "dliom_rigid3f_inverse");
+      poses.insert(poses.end(), inverse, inverse + 7);
+      poses.insert(poses.end(), global.begin(), global.end());
+    }
+    flush(size());
+    return out;
+  }
+  std::vector<int64_t> NodesInMapOrder() const {
+    std::vector<int64_t> nodes;
+    for (const auto& trajectory : by_trajectory_) nodes.insert(nodes.end(), trajectory.second.begin(), trajectory.second.end());
+    return nodes;
+  }
+
+  // ---- the reference's loops on the host, one thread ----
+  // Rigid3f * Vector3f in Eigen's operation order
+  static sensor::Vector3f HostTransform(const float p7[7], const sensor::Vector3f& p) {
+    const float w = p7[3], qx = p7[4], qy = p7[5], qz = p7[6];
+    float uvx = qy * p.z - qz * p.y, uvy = qz * p.x - qx * p.z, uvz = qx * p.y - qy * p.x;
+    uvx += uvx;
+    uvy += uvy;
+    uvz += uvz;
+    const float cx = qy * uvz - qz * uvy, cy = qz * uvx - qx * uvz, cz = qx * uvy - qy * uvx;
+    return sensor::Vector3f(((p.x + w * uvx) + cx) + p7[0], ((p.y + w * uvy) + cy) + p7[1], ((p.z + w * uvz) + cz) + p7[2]);
+  }
+  // the stream.next() loop: x, y, z, kPointCloudComponentFourMagic of every return, moved by the poses in turn
+  static void HostPointCloud2Data(const sensor::PointCloud& returns, const float* poses7, int num_poses, std::vector<uint8_t>* data) {
+    const size_t at = data->size();
+    data->resize(at + 16 * returns.size());
+    uint8_t* out = data->data() + at;
+    for (const sensor::Vector3f& point : returns) {
+      sensor::Vector3f p = point;
+      for (int k = 0; k < num_poses; ++k) p = HostTransform(poses7 + 7 * k, p);
+      const float record[4] = {p.x, p.y, p.z, 1.0f};
+      std::memcpy(out, record, 16);
+      out += 16;
+    }
+  }
+  // sensor::ToProto(RangeData) and the message around it, serialised (implicit presence: v == 0 is not written)
+  static void HostNodeRangeData(int trajectory_id, int64_t time, const transform::Rigid3d& local_pose, const sensor::RangeData& range_data,
+                                std::vector<uint8_t>* out) {
+    auto varint = [](std::vector<uint8_t>* o, uint64_t v) {
+      for (; v >= 0x80; v >>= 7) o->push_back(static_cast<uint8_t>(v) | 0x80);
+      o->push_back(static_cast<uint8_t>(v));
+    };
+    auto scalar = [](std::vector<uint8_t>* o, int field, int wire, const void* v, size_t n) {
+      o->push_back(static_cast<uint8_t>(field << 3 | wire));
+      const uint8_t* b = static_cast<const uint8_t*>(v);
+      o->insert(o->end(), b, b + n);
+    };
+    auto message = [&](std::vector<uint8_t>* o, int field, const std::vector<uint8_t>& payload) {
+      o->push_back(static_cast<uint8_t>(field << 3 | 2));
+      varint(o, payload.size());
+      o->insert(o->end(), payload.begin(), payload.end());
+    };
+    auto vector3f = [&](std::vector<uint8_t>* o, int field, const sensor::Vector3f& p) {
+      uint8_t record[17];
+      size_t n = 2;
+      const float v[3] = {p.x, p.y, p.z};
+      for (int i = 0; i < 3; ++i) {
+        if (v[i] == 0.f) continue;
+        record[n] = static_cast<uint8_t>((i + 1) << 3 | 5);
+        std::memcpy(record + n + 1, &v[i], 4);
+        n += 5;
+      }
+      record[0] = static_cast<uint8_t>(field << 3 | 2);
+      record[1] = static_cast<uint8_t>(n - 2);
+      o->insert(o->end(), record, record + n);
+    };
+    if (time != 0) {
+      out->push_back(1 << 3);
+      varint(out, static_cast<uint64_t>(time));
+    }
+    if (trajectory_id != 0) {
+      out->push_back(2 << 3);
+      varint(out, static_cast<uint64_t>(static_cast<int64_t>(trajectory_id)));
+    }
+    std::vector<uint8_t> translation, rotation, pose, range;
+    const std::array<double, 7> p = local_pose.ToArray();
+    for (int i = 0; i < 3; ++i)
+      if (p[i] != 0.0) scalar(&translation, i + 1, 1, &p[i], 8);
+    const double xyzw[4] = {p[4], p[5], p[6], p[3]};
+    for (int i = 0; i < 4; ++i)
+      if (xyzw[i] != 0.0) scalar(&rotation, i + 1, 1, &xyzw[i], 8);
+    message(&pose, 1, translation);
+    message(&pose, 2, rotation);
+    message(out, 4, pose);
+    range.reserve(19 + 17 * (range_data.returns.size() + range_data.misses.size()));
+    vector3f(&range, 1, range_data.origin);
+    for (const sensor::Vector3f& point : range_data.returns) vector3f(&range, 2, point);
+    for (const sensor::Vector3f& point : range_data.misses) vector3f(&range, 3, point);
+    message(out, 5, range);
+  }
+
+ private:
+  // maximal runs of consecutive cache indices, in the order given: a single trajectory is one run, one batched call
+  template <class F>
+  static void ForRuns(const std::vector<int64_t>& nodes, F&& f) {
+    for (size_t a = 0; a < nodes.size();) {
+      size_t b = a + 1;
+      while (b < nodes.size() && nodes[b] == nodes[b - 1] + 1) ++b;
+      f(nodes[a], static_cast<int64_t>(b - a));
+      a = b;
+    }
+  }
+  void Append(int64_t first, int64_t count, const float* poses7, int num_poses, bool per_node, CloudData* out) const {
+    dliom_node_clouds_transform t;
+    t.num_poses = num_poses;
+    t.per_node = per_node ? 1 : 0;
+    t.poses7 = poses7;
+    std::vector<int64_t> offsets(static_cast<size_t>(count) + 1);
+    Check(dliom_node_clouds_pack_point_cloud2(clouds_, first, count, &t, nullptr, nullptr, 0, offsets.data(), nullptr), "ToPointCloud2Data (sizes)");
+    const size_t at = out->data.size();
+    out->data.resize(at + static_cast<size_t>(offsets[count]));
+    Check(dliom_node_clouds_pack_point_cloud2(clouds_, first, count, &t, nullptr, out->data.data() + at, offsets[count], offsets.data(), nullptr),
+          "ToPointCloud2Data");
+    for (int64_t i = 0; i < count; ++i) {
+      out->nodes.push_back(first + i);
+      out->offsets.push_back(static_cast<int64_t>(at) + offsets[i + 1]);
+    }
+  }
+  Context* context_;
+  dliom_node_clouds* clouds_ = nullptr;
+  std::map<int, std::vector<int64_t>> by_trajectory_;
+  std::vector<dliom_node_cloud_info> order_;  // the nodes' infos, by cache index
+};
+}  // namespace cartographer_ros
+
 namespace mapping {
 
 class HybridGrid {
@@ -1171,7 +1405,16 @@ class LocalTrajectoryBuilder3D {
     transform::Rigid3d local_pose;
     sensor::RangeData range_data_in_local;
     std::unique_ptr<const InsertionResult> insertion_result;  // nullptr if dropped by the motion filter
+    // the scan's index in the cache given to SetNodeCloudCache (-1: none): range_data_in_local's returns were kept there
+    // straight from the device cloud, the bits of the host vector above
+    int64_t node_cloud_index = -1;
   };
+  // MapBuilderBridge::OnLocalSlamResult's keeping of every scan (-save_range_data, the map cloud), without the host vector's
+  // round trip: each matched scan is added to `cache` (null: none, the default) by one kernel that nothing waits for.
+  void SetNodeCloudCache(cartographer_ros::NodeCloudCache* cache, int trajectory_id) {
+    node_cloud_cache_ = cache;
+    node_cloud_trajectory_id_ = trajectory_id;
+  }
 
   LocalTrajectoryBuilder3D(Context* context, const LocalTrajectoryBuilderOptions3D& options,
                            const std::vector<std::string>& expected_range_sensor_ids)
@@ -1459,6 +1702,8 @@ class LocalTrajectoryBuilder3D {
   }
 
  private:
+  cartographer_ros::NodeCloudCache* node_cloud_cache_ = nullptr;
+  int node_cloud_trajectory_id_ = 0;
   struct Metrics {  // kLocalSlamLatencyMetric ... kScanMatcherResidualAngleMetric (.cc:36-41)
     metrics::Gauge* latency = metrics::Gauge::Null();
     metrics::Histogram* rtcsm_score = metrics::Histogram::Null();
@@ -1513,6 +1758,9 @@ class LocalTrajectoryBuilder3D {
     result->range_data_in_local.origin = TransformPoint(pf, origin[0], origin[1], origin[2]);
     result->range_data_in_local.returns.resize(static_cast<size_t>(n));
     static_assert(sizeof(sensor::Vector3f) == 12, "packed xyz");
+    if (node_cloud_cache_ != nullptr)
+      result->node_cloud_index = node_cloud_cache_->OnLocalSlamResult(node_cloud_trajectory_id_, time, result->local_pose, cloud, pf,
+                                                                      result->range_data_in_local.origin);
     DLIOM_ADAPTER_STAGE(4);
     // ComputeHistogram (.cc:605-610) reads the same filtered cloud as the insertion and writes nothing the insertion
     // reads: its kernels are started first, on the context's auxiliary stream, and run beside the insertion's

@@ -50,6 +50,13 @@ inline void put_double_field(std::vector<uint8_t>* out, int field, double v) {
   std::memcpy(&bits, &v, 8);
   for (int i = 0; i < 8; ++i) out->push_back(static_cast<uint8_t>(bits >> (8 * i)));
 }
+inline void put_float_field(std::vector<uint8_t>* out, int field, float v) {
+  if (v == 0.f) return;  // the same rule in float: -0.0 is dropped, NaN is written
+  put_varint(out, static_cast<uint64_t>(field) << 3 | 5);
+  uint32_t bits;
+  std::memcpy(&bits, &v, 4);
+  for (int i = 0; i < 4; ++i) out->push_back(static_cast<uint8_t>(bits >> (8 * i)));
+}
 inline void put_message(std::vector<uint8_t>* out, int field, const std::vector<uint8_t>& payload) {
   put_varint(out, static_cast<uint64_t>(field) << 3 | 2);  // a present sub-message is emitted even when empty
   put_varint(out, payload.size());
@@ -100,6 +107,31 @@ inline void put_rigid3d(std::vector<uint8_t>* out, int field, const double pose7
   put_message(&pose, 1, translation);
   put_message(&pose, 2, rotation);
   put_message(out, field, pose);
+}
+// transform::proto::Vector3f of (x, y, z): 0 to 15 payload bytes, always emitted (every caller has set the sub-message)
+inline void put_vector3f(std::vector<uint8_t>* out, int field, const float xyz[3]) {
+  std::vector<uint8_t> payload;
+  for (int i = 0; i < 3; ++i) put_float_field(&payload, i + 1, xyz[i]);
+  put_message(out, field, payload);
+}
+// floats of a Vector3f message into dst[field - 1]; absent fields keep what dst holds
+inline bool parse_floats(const uint8_t* p, const uint8_t* end, float* dst, int max_field) {
+  while (p < end) {
+    uint64_t tag;
+    if (!get_varint(p, end, &tag) || (tag >> 3) == 0) return false;
+    const unsigned wire = static_cast<unsigned>(tag & 7);
+    const uint64_t field = tag >> 3;
+    if (wire == 5 && field >= 1 && field <= static_cast<uint64_t>(max_field)) {
+      if (end - p < 4) return false;
+      uint32_t bits = 0;
+      for (int i = 0; i < 4; ++i) bits |= static_cast<uint32_t>(p[i]) << (8 * i);
+      std::memcpy(&dst[field - 1], &bits, 4);
+      p += 4;
+    } else if (!skip_field(p, end, wire)) {
+      return false;
+    }
+  }
+  return true;
 }
 // ... and back: translation into t (x, y, z), rotation into q (x, y, z, w); absent fields keep what t and q hold
 inline bool parse_rigid3d(const uint8_t* r, const uint8_t* rend, double t[3], double q[4]) {

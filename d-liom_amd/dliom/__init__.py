@@ -4164,3 +4164,203 @@ def imu_lidar_align_with_world(frames, transform_lb, gravity_norm):
                                                            _p(excitation, _f64p), C.byref(outcome)), "dliom_imu_lidar_align_with_world")
     return {"outcome": outcome.value, "excitation": float(excitation[0]), "P": P[:3 * n].reshape(n, 3), "R": R[:9 * n].reshape(n, 3, 3),
             "V": V[:3 * n].reshape(n, 3), "gravity_in_laser": g, "world_rotation": Rw.reshape(3, 3)}
+
+
+# ---- node clouds kept in HBM (include/dliom.h "node clouds kept in HBM") ---------------------------------------------------
+class NodeCloudInfo(C.Structure):
+    _fields_ = [("timestamp", C.c_int64), ("trajectory_id", C.c_int32), ("node_index", C.c_int32), ("local_pose7", C.c_double * 7),
+                ("origin_in_local", C.c_float * 3)]
+
+    def as_dict(self):
+        return {"timestamp": int(self.timestamp), "trajectory_id": int(self.trajectory_id), "node_index": int(self.node_index),
+                "local_pose7": np.array(self.local_pose7[:], dtype=np.float64),
+                "origin_in_local": np.array(self.origin_in_local[:], dtype=np.float32)}
+
+
+class NodeCloudsMemory(C.Structure):
+    _fields_ = [("slabs", C.c_int64), ("bytes_used", C.c_int64), ("bytes_reserved", C.c_int64), ("table_bytes", C.c_int64),
+                ("scratch_bytes", C.c_int64)]
+
+
+class NodeCloudsTransform(C.Structure):
+    _fields_ = [("num_poses", C.c_int), ("per_node", C.c_int), ("poses7", _f32p)]
+
+
+class NodeCloudsLimits(C.Structure):
+    _fields_ = [("max_points_per_chunk", C.c_int64)]
+
+
+class NodeCloudsStats(C.Structure):
+    _fields_ = [("chunks", C.c_int), ("launches", C.c_int), ("readbacks", C.c_int), ("points", C.c_int64), ("bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+NODE_RANGE_MAX_RECORD = 17  # DLIOM_NODE_RANGE_MAX_RECORD: tag, length, three tagged floats
+SYMBOLS += [
+    ("dliom_node_clouds_create", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("dliom_node_clouds_create_sized", C.c_int, [_vp, C.c_int64, C.POINTER(_vp)]),
+    ("dliom_node_clouds_destroy", C.c_int, [_vp]),
+    ("dliom_node_clouds_clear", C.c_int, [_vp]),
+    ("dliom_node_clouds_add", C.c_int, [_vp, C.POINTER(NodeCloudInfo), _vp, _vp, _f32p, _i64p]),
+    ("dliom_node_clouds_size", C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    ("dliom_node_clouds_info", C.c_int, [_vp, C.c_int64, C.POINTER(NodeCloudInfo), _i64p, _i64p]),
+    ("dliom_node_clouds_memory_stats", C.c_int, [_vp, C.POINTER(NodeCloudsMemory)]),
+    ("dliom_node_clouds_download", C.c_int, [_vp, C.c_int64, _f32p, _f32p]),
+    ("dliom_node_clouds_pack_point_cloud2", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(NodeCloudsTransform), C.POINTER(NodeCloudsLimits),
+                                                      _u8p, C.c_int64, _i64p, C.POINTER(NodeCloudsStats)]),
+    ("dliom_cloud_pack_point_cloud2", C.c_int, [_vp, _f32p, _u8p, C.c_int64, _i64p]),
+    ("dliom_rigid3f_inverse", C.c_int, [_f32p, _f32p]),
+    ("dliom_node_clouds_to_proto", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(NodeCloudsLimits), _u8p, C.c_int64, _i64p,
+                                             C.POINTER(NodeCloudsStats)]),
+    ("dliom_node_range_data_check", C.c_int, [_u8p, C.c_int64, C.POINTER(NodeCloudInfo), _i64p, _i64p]),
+    ("dliom_node_range_data_from_proto", C.c_int, [_vp, _u8p, C.c_int64, C.POINTER(NodeCloudInfo), C.POINTER(_vp), C.POINTER(_vp)]),
+]
+
+
+def rigid3f_inverse(pose7):
+    """Rigid3f::inverse of a float pose [t, q] (dliom_rigid3f_inverse; host) -> float32[7]."""
+    out = np.zeros(7, dtype=np.float32)
+    _check(load_library().dliom_rigid3f_inverse(_p(_f32(pose7).reshape(7), _f32p), _p(out, _f32p)), "dliom_rigid3f_inverse")
+    return out
+
+
+def _node_cloud_info(timestamp=0, trajectory_id=0, node_index=0, local_pose7=(0, 0, 0, 1, 0, 0, 0), origin_in_local=(0, 0, 0)):
+    info = NodeCloudInfo()
+    info.timestamp, info.trajectory_id, info.node_index = int(timestamp), int(trajectory_id), int(node_index)
+    info.local_pose7[:] = [float(v) for v in local_pose7]
+    info.origin_in_local[:] = [float(np.float32(v)) for v in origin_in_local]
+    return info
+
+
+def _cloud_pack_point_cloud2(self, pose7=None, capacity=None, fill=0):
+    """msg.data of ToPointCloud2Message(TransformPointCloud(cloud, pose7)): x, y, z, 1.0f a point (dliom_cloud_pack_point_cloud2)
+    -> (uint8 array of `capacity` bytes, default the exact size; the size)."""
+    pose = None if pose7 is None else _p(_f32(pose7).reshape(7), _f32p)
+    out = np.full(16 * self.n if capacity is None else int(capacity), fill, dtype=np.uint8)
+    n = C.c_int64()
+    _check(self._L.dliom_cloud_pack_point_cloud2(self.h, pose, _p(out, _u8p), len(out), C.byref(n)), "dliom_cloud_pack_point_cloud2")
+    return out, int(n.value)
+
+
+PointCloud.pack_point_cloud2 = _cloud_pack_point_cloud2
+
+
+class NodeClouds:
+    """Every scan's range_data_in_local kept in HBM (dliom_node_clouds): MapBuilderBridge's range_data_local_all_."""
+
+    def __init__(self, ctx, slab_floats=0):
+        self._L = ctx._L
+        self.ctx = ctx
+        h = _vp()
+        _check(self._L.dliom_node_clouds_create_sized(ctx.h, int(slab_floats), C.byref(h)), "dliom_node_clouds_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dliom_node_clouds_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.size()[0]
+
+    def clear(self):
+        _check(self._L.dliom_node_clouds_clear(self.h), "dliom_node_clouds_clear")
+
+    def add(self, returns, misses=None, pose_to_local=None, **info):
+        """Keeps a scan (PointCloud objects of this context; pose_to_local: a float pose applied on the way in) -> its index.
+        info: timestamp, trajectory_id, node_index, local_pose7, origin_in_local."""
+        index = C.c_int64(-1)
+        pose = None if pose_to_local is None else _p(_f32(pose_to_local).reshape(7), _f32p)
+        _check(self._L.dliom_node_clouds_add(self.h, C.byref(_node_cloud_info(**info)), returns.h, None if misses is None else misses.h,
+                                             pose, C.byref(index)), "dliom_node_clouds_add")
+        return int(index.value)
+
+    def size(self):
+        """(nodes, returns, misses)"""
+        v = [C.c_int64() for _ in range(3)]
+        _check(self._L.dliom_node_clouds_size(self.h, *[C.byref(x) for x in v]), "dliom_node_clouds_size")
+        return tuple(int(x.value) for x in v)
+
+    def info(self, index):
+        """dict of the node's info, with num_returns and num_misses"""
+        info, r, m = NodeCloudInfo(), C.c_int64(), C.c_int64()
+        _check(self._L.dliom_node_clouds_info(self.h, int(index), C.byref(info), C.byref(r), C.byref(m)), "dliom_node_clouds_info")
+        return dict(info.as_dict(), num_returns=int(r.value), num_misses=int(m.value))
+
+    def memory_stats(self):
+        m = NodeCloudsMemory()
+        _check(self._L.dliom_node_clouds_memory_stats(self.h, C.byref(m)), "dliom_node_clouds_memory_stats")
+        return {name: int(getattr(m, name)) for name, _ in m._fields_}
+
+    def download(self, index):
+        """(returns (n, 3), misses (m, 3)) of a node as kept"""
+        i = self.info(index)
+        r, m = np.zeros((i["num_returns"], 3), dtype=np.float32), np.zeros((i["num_misses"], 3), dtype=np.float32)
+        _check(self._L.dliom_node_clouds_download(self.h, int(index), _p(r, _f32p), _p(m, _f32p)), "dliom_node_clouds_download")
+        return r, m
+
+    def _range(self, first, count):
+        first = int(first)
+        return first, (len(self) - first if count is None else int(count))
+
+    def _batched(self, call, count, capacity, fill):
+        """query-then-fill of a batched call -> (uint8 bytes, int64 offsets (count + 1), stats dict, status)"""
+        offsets, stats = np.zeros(count + 1, dtype=np.int64), NodeCloudsStats()
+        if capacity is None:
+            _check(call(None, 0, _p(offsets, _i64p), C.byref(stats)), "node clouds size query")
+            capacity = int(offsets[count])
+        out = np.full(int(capacity), fill, dtype=np.uint8)
+        status = call(_p(out, _u8p), len(out), _p(offsets, _i64p), C.byref(stats))
+        if status not in (OK, ERR_CAPACITY):
+            _check(status, "node clouds batched call")
+        return out, offsets, stats.as_dict(), status
+
+    def pack_point_cloud2(self, first=0, count=None, poses=None, per_node=False, max_points_per_chunk=0, capacity=None, fill=0):
+        """msg.data of the nodes [first, first + count): x, y, z, 1.0f a return (dliom_node_clouds_pack_point_cloud2).
+        poses: None, or float poses [t, q] -- (7,) or (2, 7) shared by all nodes, (count, 7) or (count, 2, 7) with per_node.
+        -> (bytes, offsets, stats, status OK or ERR_CAPACITY)"""
+        first, count = self._range(first, count)
+        t = NodeCloudsTransform(0, 0, None)
+        if poses is not None:
+            p = _f32(poses)
+            num = p.size // 7 // max(count, 1) if per_node else p.size // 7
+            if num not in (1, 2) or p.size != 7 * num * (count if per_node else 1):
+                raise ValueError("one or two poses, for all nodes or for each")
+            t = NodeCloudsTransform(num, 1 if per_node else 0, _p(p, _f32p))
+        limits = NodeCloudsLimits(int(max_points_per_chunk))
+        return self._batched(lambda b, c, o, s: self._L.dliom_node_clouds_pack_point_cloud2(
+            self.h, first, count, C.byref(t), C.byref(limits), b, c, o, s), count, capacity, fill)
+
+    def to_proto(self, first=0, count=None, max_points_per_chunk=0, capacity=None, fill=0):
+        """The nodes' mapping::proto::NodeRangeData messages back to back (dliom_node_clouds_to_proto)
+        -> (bytes, offsets, stats, status OK or ERR_CAPACITY)"""
+        first, count = self._range(first, count)
+        limits = NodeCloudsLimits(int(max_points_per_chunk))
+        return self._batched(lambda b, c, o, s: self._L.dliom_node_clouds_to_proto(self.h, first, count, C.byref(limits), b, c, o, s),
+                             count, capacity, fill)
+
+
+def node_range_data_from_proto(ctx, data):
+    """A NodeRangeData message (bytes) -> (info dict, returns PointCloud, misses PointCloud) (dliom_node_range_data_from_proto)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info, r, m = NodeCloudInfo(), _vp(), _vp()
+    _check(ctx._L.dliom_node_range_data_from_proto(ctx.h, _p(buf, _u8p) if len(buf) else None, len(buf), C.byref(info), C.byref(r), C.byref(m)),
+           "dliom_node_range_data_from_proto")
+    return info.as_dict(), PointCloud(ctx, _handle=r), PointCloud(ctx, _handle=m)
+
+
+def node_range_data_check(data):
+    """The host parse of a NodeRangeData message alone -> (info dict, num_returns, num_misses); DliomError if malformed."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info, r, m = NodeCloudInfo(), C.c_int64(), C.c_int64()
+    _check(load_library().dliom_node_range_data_check(_p(buf, _u8p) if len(buf) else None, len(buf), C.byref(info), C.byref(r), C.byref(m)),
+           "dliom_node_range_data_check")
+    return info.as_dict(), int(r.value), int(m.value)

@@ -234,6 +234,94 @@ int dliom_trajectory_node_data_from_proto(dliom_ctx* ctx, const uint8_t* bytes, 
                                           double gravity_alignment_wxyz[4], dliom_cloud** filtered_gravity_aligned,
                                           dliom_cloud** high_resolution, dliom_cloud** low_resolution, float* histogram,
                                           int histogram_capacity, int* histogram_size, double local_pose7[7]);
+/* ---- node clouds kept in HBM: map cloud messages and NodeRangeData (cartographer_ros/map_builder_bridge.cc:170-201,
+ * 591-607, node.cc:203-220, 318-354, pb_range_data_to_ros_cloud_main.cc:153-186, msg_conversion.cc:159-171) ----
+ * A cache keeps every scan's range_data_in_local (returns, misses) where the scan matcher left it.  Points are stored
+ * SoA in pooled slabs; a node never straddles a slab and growth never moves an earlier node.  The descriptor table
+ * (slab pointers, counts, prefix sums) lives on the host and is mirrored to the device by the first batched call that
+ * needs it.  add is one kernel on the context's stream and waits for nothing: with pose_to_local the float pose is
+ * applied on the way in (sensor::TransformPointCloud: rotation * p + translation in Eigen's operation order, as
+ * dliom_cloud_download_transformed), to returns and misses alike; info->origin_in_local is kept as given.  The clouds
+ * must be the cache's context's.  create_sized: floats a slab (<= 0: the default, 2^24); a node that needs more gets a
+ * slab of its own.
+ *
+ * PointCloud2 data.  A record is the moved return and the float 1.0: x, y, z, 1.0f, 16 bytes, little endian; misses are
+ * not part of it.  Poses are float (tx, ty, tz, qw, qx, qy, qz); two poses are applied one after the other, each
+ * rounded as the reference rounds between them.  Node first + i's data is bytes[byte_offsets[i], byte_offsets[i + 1]),
+ * 16 * its returns: the sizes are known on the host, so a chunk (whole nodes, at least one, up to
+ * max_points_per_chunk returns) is one launch and one download, whatever the number of its nodes.
+ *
+ * mapping::proto::NodeRangeData (proto3).  1 timestamp (int64 varint), 2 trajectory_id, 3 node_index (int32 varints: a
+ * negative value is sign-extended to ten bytes), each omitted when 0; 4 local_pose (Rigid3d: 1 translation, 2 rotation,
+ * always present); 5 range_data_in_local (sensor::proto::RangeData, always present): 1 origin, always present, then
+ * every return as a field 2 and every miss as a field 3, each a transform::proto::Vector3f sub-message: x, y, z as
+ * fixed32 fields 1 to 3, a coordinate written unless v == 0 (so -0.0 is dropped and NaN is written, the rule of the
+ * doubles above).  A point's record -- tag, length, payload -- is 2 to DLIOM_NODE_RANGE_MAX_RECORD bytes and lies at
+ * any byte offset.  A chunk: one launch leaves the bytes of every tile of 256 records, one scan, ONE polled read-back
+ * of the nodes' payload sizes (the host needs them for the two enclosing length varints and makes the headers), one
+ * launch that writes headers and records, one download.  Framing (pbstream, gzip, SerializationHeader) is the caller's.
+ * from_proto is a host parse and one upload a cloud: any field order, unknown fields skipped, absent fields zero,
+ * repeated sub-messages merged as protobuf merges them; truncated or malformed input: DLIOM_ERR_INVALID_ARGUMENT.
+ *
+ * Conventions of dliom_trajectory_nodes_data_to_proto: byte_offsets (count + 1) are always filled; bytes NULL is a size
+ * query; a capacity below byte_offsets[count] returns DLIOM_ERR_CAPACITY and nothing is written past capacity.  stats
+ * (may be NULL): chunks, kernel launches (a scan counts as one), polled read-backs, points and bytes of the call.
+ * DLIOM_ERR_INVALID_ARGUMENT: NULLs, a range outside the cache, num_poses outside 0..2, a cloud of another context. */
+typedef struct dliom_node_clouds dliom_node_clouds;
+typedef struct {
+  int64_t timestamp;        /* common::ToUniversal(time) */
+  int32_t trajectory_id;
+  int32_t node_index;       /* SerializeRangeData never sets it: 0 there */
+  double local_pose7[7];    /* x y z qw qx qy qz */
+  float origin_in_local[3];
+} dliom_node_cloud_info;
+typedef struct {
+  int64_t slabs, bytes_used, bytes_reserved; /* the point slabs */
+  int64_t table_bytes;                       /* the descriptor table's device mirror */
+  int64_t scratch_bytes;                     /* the batched calls' work buffers */
+} dliom_node_clouds_memory;
+typedef struct {
+  int num_poses;        /* 0: the kept points as they are; 1: pose * p; 2: second * (first * p), two separate float transforms */
+  int per_node;         /* 0: the same num_poses poses for every node; 1: num_poses poses per node, node-major */
+  const float* poses7;  /* tx ty tz qw qx qy qz each */
+} dliom_node_clouds_transform;
+typedef struct { int64_t max_points_per_chunk; } dliom_node_clouds_limits;   /* <= 0: the default, 2^22 */
+typedef struct { int chunks, launches, readbacks; int64_t points, bytes; } dliom_node_clouds_stats;
+#define DLIOM_NODE_RANGE_MAX_RECORD 17
+/* a message's bytes in front of its records never exceed this: a capacity of DLIOM_NODE_RANGE_MAX_HEADER a node and
+ * DLIOM_NODE_RANGE_MAX_RECORD a point (returns and misses) NEVER returns DLIOM_ERR_CAPACITY -- one call, no size query */
+#define DLIOM_NODE_RANGE_MAX_HEADER 192
+int dliom_node_clouds_create(dliom_ctx* ctx, dliom_node_clouds** out);
+int dliom_node_clouds_create_sized(dliom_ctx* ctx, int64_t slab_floats, dliom_node_clouds** out);
+int dliom_node_clouds_destroy(dliom_node_clouds* clouds);
+int dliom_node_clouds_clear(dliom_node_clouds* clouds);  /* forgets the nodes, keeps the first slab */
+int dliom_node_clouds_add(dliom_node_clouds* clouds, const dliom_node_cloud_info* info, const dliom_cloud* returns,
+                          const dliom_cloud* misses /* NULL: none */, const float pose_to_local[7] /* NULL: none */,
+                          int64_t* index /* may be NULL */);
+int dliom_node_clouds_size(const dliom_node_clouds* clouds, int64_t* nodes, int64_t* returns, int64_t* misses);
+int dliom_node_clouds_info(const dliom_node_clouds* clouds, int64_t index, dliom_node_cloud_info* info, int64_t* num_returns,
+                           int64_t* num_misses);
+int dliom_node_clouds_memory_stats(const dliom_node_clouds* clouds, dliom_node_clouds_memory* memory);
+/* packed xyz of one node (either pointer may be NULL); waits for the stream */
+int dliom_node_clouds_download(const dliom_node_clouds* clouds, int64_t index, float* returns_xyz, float* misses_xyz);
+int dliom_node_clouds_pack_point_cloud2(dliom_node_clouds* clouds, int64_t first, int64_t count,
+                                        const dliom_node_clouds_transform* transform /* NULL: num_poses 0 */,
+                                        const dliom_node_clouds_limits* limits /* NULL: defaults */, uint8_t* bytes,
+                                        int64_t capacity, int64_t* byte_offsets /* count + 1 */, dliom_node_clouds_stats* stats);
+/* the same records of one device cloud: *num_bytes = 16 n always; bytes NULL: the size only */
+int dliom_cloud_pack_point_cloud2(const dliom_cloud* cloud, const float pose[7] /* or NULL */, uint8_t* bytes, int64_t capacity,
+                                  int64_t* num_bytes);
+/* host: Rigid3f::inverse (rigid_transform.h:167-171) in float: the conjugate, then -(conjugate * translation) */
+int dliom_rigid3f_inverse(const float pose[7], float inverse[7]);
+int dliom_node_clouds_to_proto(dliom_node_clouds* clouds, int64_t first, int64_t count, const dliom_node_clouds_limits* limits,
+                               uint8_t* bytes, int64_t capacity, int64_t* byte_offsets /* count + 1 */,
+                               dliom_node_clouds_stats* stats);
+/* host only: the parse alone -- DLIOM_OK for a message from_proto accepts; info and the counts may be NULL */
+int dliom_node_range_data_check(const uint8_t* bytes, int64_t size, dliom_node_cloud_info* info, int64_t* num_returns,
+                                int64_t* num_misses);
+/* two new device clouds, the caller's to destroy */
+int dliom_node_range_data_from_proto(dliom_ctx* ctx, const uint8_t* bytes, int64_t size, dliom_node_cloud_info* info,
+                                     dliom_cloud** returns, dliom_cloud** misses);
 /* ---- X-ray projections of a grid (mapping/3d/submap_3d.cc), computed on the device from the leaf pool ----
  * Both reproduce the reference's float arithmetic byte for byte: the cells with ValueToProbability(v) >= 0.501 in
  * HybridGrid::Iterator order, each cell centre index * resolution transformed in float and rounded with
