@@ -165,7 +165,20 @@ class optional {
   bool has_value_;
   T value_;
 };
+// common::FastGzipString (common/port.h:46-53) for what is small and on the host, such as a SerializationHeader: one
+// member of dliom.h "gzip on the device" (dliom_gzip_host).  FastGunzipString, or any inflater, reads it; the bytes are
+// not zlib's.
+inline void FastGzipString(const std::string& uncompressed, std::string* compressed) {
+  compressed->assign(static_cast<size_t>(dliom_gzip_bound(static_cast<int64_t>(uncompressed.size()))), '\0');
+  int64_t size = 0;
+  Check(dliom_gzip_host(reinterpret_cast<const uint8_t*>(uncompressed.data()), static_cast<int64_t>(uncompressed.size()),
+                        reinterpret_cast<uint8_t*>(&(*compressed)[0]), static_cast<int64_t>(compressed->size()), &size), "FastGzipString");
+  compressed->resize(static_cast<size_t>(size));
+}
 }  // namespace common
+
+// asks an adapter method for bytes that left the device gzipped (opt-in: the methods without it keep their behaviour)
+enum GzipTag { kGzipped };
 
 namespace transform {
 struct Vector3d {
@@ -334,6 +347,26 @@ class NodeCloudCache {
       }
       std::vector<uint8_t> bytes(static_cast<size_t>(capacity));
       Check(dliom_node_clouds_to_proto(clouds_, first, count, nullptr, bytes.data(), capacity, offsets.data(), nullptr), "SerializeRangeData");
+      for (int64_t i = 0; i < count; ++i) write(bytes.data() + offsets[i], static_cast<size_t>(offsets[i + 1] - offsets[i]));
+    });
+  }
+  // ... with ProtoStreamWriter::WriteProto's framing (proto_stream.cc:50-57) done on the device: write(data, size) once a
+  // node with the 8-byte little-endian compressed size and the gzip member behind it -- the bytes WriteProto puts into the
+  // file for that message.  The messages never reach the host uncompressed.  Opt-in.
+  template <class WriteRecord>
+  void SerializeRangeDataFramed(WriteRecord&& write) const {
+    const std::vector<int64_t> nodes = NodesInMapOrder();
+    ForRuns(nodes, [&](int64_t first, int64_t count) {
+      std::vector<int64_t> offsets(static_cast<size_t>(count) + 1);
+      int64_t capacity = 0;  // the bound that never fails
+      for (int64_t i = first; i < first + count; ++i) {
+        int64_t returns = 0, misses = 0;
+        Check(dliom_node_clouds_info(clouds_, i, nullptr, &returns, &misses), "dliom_node_clouds_info");
+        capacity += 8 + dliom_gzip_bound(DLIOM_NODE_RANGE_MAX_HEADER + DLIOM_NODE_RANGE_MAX_RECORD * (returns + misses));
+      }
+      std::vector<uint8_t> bytes(static_cast<size_t>(capacity));
+      Check(dliom_node_clouds_to_pbstream(clouds_, first, count, nullptr, bytes.data(), capacity, offsets.data(), nullptr, nullptr),
+            "SerializeRangeDataFramed");
       for (int64_t i = 0; i < count; ++i) write(bytes.data() + offsets[i], static_cast<size_t>(offsets[i + 1] - offsets[i]));
     });
   }
@@ -1252,6 +1285,24 @@ inline SubmapTexture XrayTexture(const dliom_grid* grid, const transform::Rigid3
   return t;
 }
 
+// AddToTextureProto with its gzip step on the device (dliom_grid_xray_texture_gzip): `cells` is what the proto field takes.
+inline SubmapTexture XrayTextureGzipped(const dliom_grid* grid, const transform::Rigid3d& global_submap_pose) {
+  const std::array<double, 7> pose = global_submap_pose.ToArray();
+  SubmapTexture t;
+  int32_t w = 0, h = 0;
+  int64_t size = 0;
+  double slice[7];
+  Check(dliom_grid_xray_texture_gzip(grid, pose.data(), nullptr, 0, &size, &w, &h, &t.resolution, slice, nullptr), "dliom_grid_xray_texture_gzip");
+  t.cells.resize(static_cast<size_t>(size));
+  Check(dliom_grid_xray_texture_gzip(grid, pose.data(), reinterpret_cast<uint8_t*>(&t.cells[0]), size, &size, &w, &h, &t.resolution, slice,
+                                     nullptr), "dliom_grid_xray_texture_gzip");
+  t.cells.resize(static_cast<size_t>(size));
+  t.width = w;
+  t.height = h;
+  t.slice_pose = transform::Rigid3d::FromArray(slice);
+  return t;
+}
+
 // ProjectToCvMat's image (D-LIOM mapping/3d/submap_3d.cc:381-443) without OpenCV: `data` is rows x cols CV_8UC1,
 // row-major -- cv::Mat(rows, cols, CV_8UC1, data.data()) wraps it.  Pixel values are the reference's, reduced modulo 256
 // (empty pixels 224); an empty projection is 0 x 0.
@@ -1306,6 +1357,14 @@ class Submap3D {
     r.submap_version = num_range_data_;
     r.textures.push_back(XrayTexture(hi_, global_submap_pose));
     r.textures.push_back(XrayTexture(lo_, global_submap_pose));
+    return r;
+  }
+  // ... with the textures' cells gzipped on the device, ready for the proto (dliom::kGzipped); opt-in
+  SubmapQueryResponse ToResponseProto(const transform::Rigid3d& global_submap_pose, GzipTag) const {
+    SubmapQueryResponse r;
+    r.submap_version = num_range_data_;
+    r.textures.push_back(XrayTextureGzipped(hi_, global_submap_pose));
+    r.textures.push_back(XrayTextureGzipped(lo_, global_submap_pose));
     return r;
   }
 

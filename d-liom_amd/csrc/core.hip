@@ -804,6 +804,8 @@ int dliom_ctx_destroy(dliom_ctx* ctx) {
   ctx->painter.release();
   ctx->compress.release();
   ctx->compress_out.release();
+  ctx->gzip_in.release();
+  ctx->gzip.release();
   ctx->outlier.release();
   if (ctx->batch_pinned != nullptr) (void)hipHostFree(ctx->batch_pinned);
   ctx->aux_scratch.release();

@@ -150,6 +150,8 @@ struct dliom_ctx {
   // the node clouds' compression (compressed_cloud.hip): keys, sort buffers, scans and the word streams of one batch; the
   // varint bytes of its field-3 payloads, sized by the byte count the batch's read-back brought
   dliom::DevBuf compress, compress_out;
+  // gzip on the device (gzip.hip): the bytes a host-pointer entry point uploads; a launch chain's tables, slots and output
+  dliom::DevBuf gzip_in, gzip;
   bool surf_tables_ready = false;  // `surf` holds the Gaussian tables: cleared whenever reserve() made a new allocation
   // the export stages (compact.hip): keep flags, their scan and the survivors' indices; the voxel list of a table dump
   dliom::DevBuf outlier;
@@ -351,6 +353,12 @@ int surf_features_on_device(dliom_ctx* ctx, const uint8_t* image, int width, int
 // projection; nullptr under an empty projection).  Nothing is waited for after the kernels.
 int xray_texture_on_device(const dliom_grid* grid, const double global_submap_pose7[7], const uint8_t** cells, int32_t* width,
                            int32_t* height, double* resolution, double slice_pose7[7]);
+// gzip.hip: the segments [offsets[s], offsets[s + 1]) of `d_in` (device) as gzip members back to back in `out` (host), each
+// behind its 8-byte little-endian size if size_prefix; out_offsets (k + 1) always filled.  The offsets are taken as checked
+// (ascending, no segment above DLIOM_GZIP_MAX_SEGMENT).  DLIOM_ERR_CAPACITY: nothing written past capacity.  The stream has
+// been waited for; `d_in` may lie in any buffer but ctx->gzip.
+int gzip_on_device(dliom_ctx* ctx, const uint8_t* d_in, const int64_t* offsets, int64_t k, bool size_prefix, uint8_t* out, int64_t capacity,
+                   int64_t* out_offsets, dliom_gzip_stats* stats);
 int surf_check_options(const dliom_surf_options* options);  // DLIOM_OK or DLIOM_ERR_INVALID_ARGUMENT
 
 constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }

@@ -487,16 +487,28 @@ size_t proto_scratch_bytes(dliom_ctx* ctx, int64_t tiles, int64_t k, long long i
   return at_out + (with_bytes ? align256(kMaxHeader * static_cast<size_t>(k) + kMaxRecord * static_cast<size_t>(items)) : 0);
 }
 
+// where a chunk's messages go instead of the host: through gzip.hip, a framed record each (dliom_node_clouds_to_pbstream)
+struct GzipSink {
+  uint8_t* out;
+  int64_t capacity;
+  int64_t* offsets;  // count + 1, of the records
+  dliom_gzip_stats* stats;
+  int64_t nodes_done = 0;
+  bool fits = true;
+};
+
+// sink != nullptr: `bytes` and `capacity` are not used, byte_offsets are still the messages' (uncompressed) offsets
 int protos_of_nodes(dliom_node_clouds* nc, int64_t first, int64_t count, const dliom_node_clouds_limits* limits, uint8_t* bytes,
-                    int64_t capacity, int64_t* byte_offsets, dliom_node_clouds_stats* stats, bool* fits) {
+                    int64_t capacity, int64_t* byte_offsets, dliom_node_clouds_stats* stats, bool* fits, GzipSink* sink = nullptr) {
   dliom_ctx* ctx = nc->ctx;
+  const bool want_bytes = bytes != nullptr || sink != nullptr;
   DLIOM_TRY(mirror_table(nc));
   const auto chunks = plan_chunks(nc->item_prefix, first, count, chunk_limit(limits));
   size_t most = 0;
   for (const auto& ch : chunks) {
     int st;
     most = std::max(most, proto_scratch_bytes(ctx, nc->tile_prefix[ch.second] - nc->tile_prefix[ch.first], ch.second - ch.first,
-                                              nc->item_prefix[ch.second] - nc->item_prefix[ch.first], bytes != nullptr, nullptr, nullptr, &st));
+                                              nc->item_prefix[ch.second] - nc->item_prefix[ch.first], want_bytes, nullptr, nullptr, &st));
     DLIOM_TRY(st);
   }
   DLIOM_TRY(nc->work.reserve(most));
@@ -510,7 +522,7 @@ int protos_of_nodes(dliom_node_clouds* nc, int64_t first, int64_t count, const d
     const long long tiles = nc->tile_prefix[b] - nc->tile_prefix[a], items = nc->item_prefix[b] - nc->item_prefix[a];
     ProtoScratch s;
     int st;
-    proto_scratch_bytes(ctx, tiles, k, items, bytes != nullptr, &s, nc->work.as<char>(), &st);
+    proto_scratch_bytes(ctx, tiles, k, items, want_bytes, &s, nc->work.as<char>(), &st);
     DLIOM_TRY(st);
     const unsigned long long* sizes = nullptr;
     if (tiles > 0) {
@@ -556,16 +568,32 @@ int protos_of_nodes(dliom_node_clouds* nc, int64_t first, int64_t count, const d
     }
     byte_offsets[b - first] = at + chunk_bytes;
     if (stats != nullptr) ++stats->chunks;
-    if (bytes != nullptr && *fits && at + chunk_bytes > capacity) *fits = false;  // the sizes of the rest are still owed
-    if (bytes != nullptr && *fits && chunk_bytes > 0) {
+    if (sink == nullptr && bytes != nullptr && *fits && at + chunk_bytes > capacity) *fits = false;  // the sizes of the rest are still owed
+    if (want_bytes && *fits && chunk_bytes > 0) {
       if (up.size() > s.upload_room) return DLIOM_ERR_INTERNAL;
       DLIOM_HIP_TRY(hipMemcpyAsync(s.node_out, up.data(), up.size(), hipMemcpyHostToDevice, ctx->stream));
       hipLaunchKernelGGL(range_emit_kernel, dim3(static_cast<unsigned>(tiles) + blocks_of(k, kTile / 64)), dim3(kTile), 0, ctx->stream, nc->d_desc(),
                          nc->d_tile_prefix(), a, b, static_cast<unsigned>(tiles), s.inclusive, s.node_out,
                          reinterpret_cast<const unsigned char*>(s.node_out + k), s.out);
       if (!launched()) return DLIOM_ERR_HIP;
-      DLIOM_HIP_TRY(hipMemcpyAsync(bytes + at, s.out, static_cast<size_t>(chunk_bytes), hipMemcpyDeviceToHost, ctx->stream));
       if (stats != nullptr) ++stats->launches;
+      if (sink == nullptr) {
+        DLIOM_HIP_TRY(hipMemcpyAsync(bytes + at, s.out, static_cast<size_t>(chunk_bytes), hipMemcpyDeviceToHost, ctx->stream));
+      } else {
+        // the chunk's messages as segments of s.out; the records behind those of the chunks before (a chunk that does not
+        // fit, and every chunk behind it, still runs: the records' sizes are owed, their bytes are not)
+        std::vector<int64_t> segments(k + 1u);
+        for (unsigned c = 0; c <= k; ++c) segments[c] = byte_offsets[a - first + c] - at;
+        int64_t* record = sink->offsets + sink->nodes_done;
+        const int64_t gz_at = sink->nodes_done == 0 ? 0 : record[0];
+        const int64_t room = sink->fits ? sink->capacity - gz_at : 0;
+        const int st = gzip_on_device(ctx, s.out, segments.data(), k, true, sink->out + (sink->fits ? gz_at : 0), room, record, sink->stats);
+        if (st == DLIOM_ERR_CAPACITY) sink->fits = false;
+        else if (st != DLIOM_OK) return st;
+        for (unsigned c = 1; c <= k; ++c) record[c] += gz_at;
+        record[0] = gz_at;
+        sink->nodes_done += k;
+      }
     }
     at += chunk_bytes;
   }
@@ -853,6 +881,27 @@ int dliom_node_clouds_to_proto(dliom_node_clouds* nc, int64_t first, int64_t cou
     stats->bytes = byte_offsets[count];
   }
   return fits ? DLIOM_OK : DLIOM_ERR_CAPACITY;
+}
+
+int dliom_node_clouds_to_pbstream(dliom_node_clouds* nc, int64_t first, int64_t count, const dliom_node_clouds_limits* limits, uint8_t* bytes,
+                                  int64_t capacity, int64_t* byte_offsets, dliom_node_clouds_stats* stats, dliom_gzip_stats* gzip_stats) {
+  if (bytes == nullptr || byte_offsets == nullptr || capacity < 0) return DLIOM_ERR_INVALID_ARGUMENT;
+  DLIOM_TRY(check_range(nc, first, count));
+  clear_stats(stats);
+  if (gzip_stats != nullptr) *gzip_stats = dliom_gzip_stats{0, 0, 0, 0};
+  byte_offsets[0] = 0;
+  if (count == 0) return DLIOM_OK;
+  DLIOM_HIP_TRY(hipSetDevice(nc->ctx->device));
+  std::vector<int64_t> message_offsets(static_cast<size_t>(count) + 1);
+  GzipSink sink{bytes, capacity, byte_offsets, gzip_stats};
+  bool fits = true;
+  const int st = finish(nc->ctx, protos_of_nodes(nc, first, count, limits, nullptr, 0, message_offsets.data(), stats, &fits, &sink));
+  if (st != DLIOM_OK) return st;
+  if (stats != nullptr) {
+    stats->points = nc->item_prefix[first + count] - nc->item_prefix[first];
+    stats->bytes = byte_offsets[count];
+  }
+  return sink.fits ? DLIOM_OK : DLIOM_ERR_CAPACITY;
 }
 
 int dliom_node_range_data_check(const uint8_t* bytes, int64_t size, dliom_node_cloud_info* info, int64_t* num_returns, int64_t* num_misses) {

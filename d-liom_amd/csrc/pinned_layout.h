@@ -35,6 +35,9 @@
 //    reads every cloud's eight box words back through the second region (8 words x 256 clouds are more than kPinReadback
 //    holds), and only then writes the table again, with the grids' views, before the sort's launches.  The chunk's stream
 //    synchronisation frees both for the next chunk;
+//  * kPinGzipSizes belongs to a launch chain of gzip.hip, which the entry points that compress (dliom_gzip and its kin, the
+//    gzipped texture, the framed node records) run only after their own read-backs are copied out: the chain's one
+//    read-back, copied out before the chain's download is issued;
 //  * the bulk regions from offset 0 (kPinRtcsmCandidates, kPinFastCsmScores, kPinDownload, kPinFrontierUpload) belong
 //    to different entry points, except in a fast-CSM search: there device_frontier synchronises and copies its output
 //    (kPinFrontierOut) into the score cache before the recursion's device_sums (kPinFastCsmScores) first runs.  The
@@ -119,6 +122,9 @@ constexpr size_t kPinNnIndexBatchIndices = 256, kPinNnIndexBatchEntryBytes = 128
 constexpr PinRegion kPinNnIndexBatchTable{8192, kPinNnIndexBatchIndices * kPinNnIndexBatchEntryBytes};
 constexpr PinRegion kPinNnIndexBatchBoxes{65536, kPinNnIndexBatchIndices * kPinNnIndexBatchBoxWords * 4};
 
+// a launch chain of gzip.hip: [chunks in stored form | the k + 1 offsets of its segments' members], 64 bits each
+constexpr PinRegion kPinGzipSizes{0, 65536};
+
 // the auxiliary block: the histogram of dliom_cloud_rotational_histogram_begin / _finish and its completion word
 constexpr size_t kAuxPinnedBytes = 4096;
 constexpr PinRegion kAuxHistogram{0, 4032};
@@ -180,6 +186,7 @@ static_assert(pins_inside({kPinNnIndexBatchTable, kPinNnIndexBatchBoxes}, kPinne
                   pins_disjoint({kPinNnIndexBatchTable, kPinNnIndexBatchBoxes, kPinReadback}) &&
                   kPinNnIndexBatchBoxWords * 4 * kPinNnIndexBatchIndices > kPinReadback.bytes,
               "a batched index build's regions (its boxes would not fit the small read-backs')");
+static_assert(pins_inside({kPinGzipSizes}, kPinnedBytes) && kPinGzipSizes.bytes / 8 > 2, "a gzip launch chain's region");
 static_assert(pins_disjoint({kAuxHistogram, kAuxDoneWord}), "the auxiliary block's regions");
 
 }  // namespace dliom

@@ -491,6 +491,28 @@ int dliom_grid_xray_texture(const dliom_grid* grid, const double global_submap_p
   return xray_texture(grid, global_submap_pose7, cells, capacity, nullptr, width, height, resolution, slice_pose7);
 }
 
+int dliom_grid_xray_texture_gzip(const dliom_grid* grid, const double global_submap_pose7[7], uint8_t* cells_gz, int64_t capacity,
+                                 int64_t* cells_gz_size, int32_t* width, int32_t* height, double* resolution, double slice_pose7[7],
+                                 dliom_gzip_stats* gzip_stats) {
+  if (grid == nullptr || global_submap_pose7 == nullptr || cells_gz_size == nullptr || width == nullptr || height == nullptr ||
+      resolution == nullptr || slice_pose7 == nullptr || capacity < 0)
+    return DLIOM_ERR_INVALID_ARGUMENT;
+  if (gzip_stats != nullptr) *gzip_stats = dliom_gzip_stats{0, 0, 0, 0};
+  if (cells_gz == nullptr) {
+    DLIOM_TRY(xray_texture(grid, global_submap_pose7, nullptr, 0, nullptr, width, height, resolution, slice_pose7));
+    *cells_gz_size = dliom_gzip_bound(int64_t{2} * *width * *height);
+    return DLIOM_OK;
+  }
+  const uint8_t* cells = nullptr;
+  DLIOM_TRY(xray_texture(grid, global_submap_pose7, nullptr, 0, &cells, width, height, resolution, slice_pose7));
+  const int64_t offsets[2] = {0, int64_t{2} * *width * *height};
+  int64_t out_offsets[2] = {0, 0};
+  DLIOM_HIP_TRY(hipSetDevice(grid->ctx->device));  // (an empty grid's projection returns before it touches the device)
+  const int st = gzip_on_device(grid->ctx, cells, offsets, 1, false, cells_gz, capacity, out_offsets, gzip_stats);
+  if (st == DLIOM_OK || st == DLIOM_ERR_CAPACITY) *cells_gz_size = out_offsets[1];
+  return st;
+}
+
 int dliom_grid_project_to_image(const dliom_grid* grid, const double transform7[7], uint8_t* image, int64_t capacity,
                                 int32_t* width, int32_t* height, double* ox, double* oy, double* resolution) {
   if (grid == nullptr || transform7 == nullptr || width == nullptr || height == nullptr || ox == nullptr || oy == nullptr ||

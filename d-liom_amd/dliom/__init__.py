@@ -4364,3 +4364,114 @@ def node_range_data_check(data):
     _check(load_library().dliom_node_range_data_check(_p(buf, _u8p) if len(buf) else None, len(buf), C.byref(info), C.byref(r), C.byref(m)),
            "dliom_node_range_data_check")
     return info.as_dict(), int(r.value), int(m.value)
+
+
+# ---- gzip on the device (dliom.h "gzip on the device"; csrc/gzip.hip, csrc/gzip_host.cc) ----
+GZIP_CHUNK = 4096  # DLIOM_GZIP_CHUNK
+ERR_TOO_LARGE = -14
+
+
+class GzipStats(C.Structure):
+    _fields_ = [("chunks", C.c_int64), ("chunks_stored", C.c_int64), ("read_backs", C.c_int64), ("bytes_downloaded", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+SYMBOLS += [
+    ("dliom_gzip_bound", C.c_int64, [C.c_int64]),
+    ("dliom_gzip_host", C.c_int, [_u8p, C.c_int64, _u8p, C.c_int64, _i64p]),
+    ("dliom_gzip", C.c_int, [_vp, _u8p, C.c_int64, _u8p, C.c_int64, _i64p, C.POINTER(GzipStats)]),
+    ("dliom_gzip_segments", C.c_int, [_vp, _u8p, _i64p, C.c_int64, _u8p, C.c_int64, _i64p, C.POINTER(GzipStats)]),
+    ("dliom_grid_xray_texture_gzip", C.c_int, [_vp, _f64p, _u8p, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, C.POINTER(GzipStats)]),
+    ("dliom_node_clouds_to_pbstream", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(NodeCloudsLimits), _u8p, C.c_int64, _i64p,
+                                                C.POINTER(NodeCloudsStats), C.POINTER(GzipStats)]),
+]
+
+
+def gzip_bound(n):
+    """dliom_gzip_bound: 18 + n + 5 * max(1, ceil(n / 4096)); a buffer of that size is never too small."""
+    return int(load_library().dliom_gzip_bound(int(n)))
+
+
+def _gzip_input(data):
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    return buf, (_p(buf, _u8p) if buf.size else None)
+
+
+def gzip_host(data, capacity=None):
+    """One gzip member of `data` by the statement of dliom.h "gzip on the device", on one host thread (dliom_gzip_host)
+    -> bytes.  capacity: the output buffer's size (default the bound); too small raises DliomError(ERR_CAPACITY)."""
+    buf, ptr = _gzip_input(data)
+    out = np.zeros(gzip_bound(buf.size) if capacity is None else int(capacity), dtype=np.uint8)
+    size = C.c_int64()
+    _check(load_library().dliom_gzip_host(ptr, buf.size, _p(out, _u8p), out.size, C.byref(size)), "dliom_gzip_host")
+    return out[:size.value].tobytes()
+
+
+def gzip(ctx, data, capacity=None, with_stats=False):
+    """One gzip member of `data`, compressed on the device (dliom_gzip): upload, one launch chain, one polled read-back, one
+    download of exactly the compressed bytes -> bytes, or (bytes, stats dict)."""
+    buf, ptr = _gzip_input(data)
+    out = np.zeros(gzip_bound(buf.size) if capacity is None else int(capacity), dtype=np.uint8)
+    size, stats = C.c_int64(), GzipStats()
+    _check(ctx._L.dliom_gzip(ctx.h, ptr, buf.size, _p(out, _u8p), out.size, C.byref(size), C.byref(stats)), "dliom_gzip")
+    member = out[:size.value].tobytes()
+    return (member, stats.as_dict()) if with_stats else member
+
+
+def gzip_segments(ctx, data, offsets, capacity=None, with_stats=False):
+    """K gzip members in one launch chain (dliom_gzip_segments): segment s is data[offsets[s]:offsets[s + 1]]
+    -> list of K bytes objects, or (list, stats dict)."""
+    buf, ptr = _gzip_input(data)
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    k = off.size - 1
+    if k < 0 or (k >= 0 and off.size and (off[0] < 0 or off[-1] > buf.size)):
+        raise ValueError("offsets must hold k + 1 entries inside the data")
+    if capacity is None:
+        capacity = sum(gzip_bound(int(off[s + 1] - off[s])) for s in range(k) if off[s + 1] >= off[s])
+    out = np.zeros(max(int(capacity), 1), dtype=np.uint8)
+    out_off, stats = np.zeros(k + 1, dtype=np.int64), GzipStats()
+    _check(ctx._L.dliom_gzip_segments(ctx.h, ptr, _p(off, _i64p), k, _p(out, _u8p), int(capacity), _p(out_off, _i64p), C.byref(stats)),
+           "dliom_gzip_segments")
+    members = [out[out_off[s]:out_off[s + 1]].tobytes() for s in range(k)]
+    return (members, stats.as_dict()) if with_stats else members
+
+
+def grid_xray_texture_gzip(grid, pose, with_stats=False):
+    """grid_xray_texture with `cells` leaving HBM as one gzip member, ready for the proto field (dliom_grid_xray_texture_gzip)
+    -> (width, height, resolution, slice_pose7, cells_gz bytes), with the gzip stats dict behind them if with_stats."""
+    p = _pose7(pose)
+    w, h, res, size, stats = C.c_int32(), C.c_int32(), C.c_double(), C.c_int64(), GzipStats()
+    slice_pose = np.zeros(7, dtype=np.float64)
+    L = grid._L
+    _check(L.dliom_grid_xray_texture_gzip(grid.h, _p(p, _f64p), None, 0, C.byref(size), C.byref(w), C.byref(h), C.byref(res),
+                                          _p(slice_pose, _f64p), None), "dliom_grid_xray_texture_gzip")
+    out = np.zeros(size.value, dtype=np.uint8)
+    _check(L.dliom_grid_xray_texture_gzip(grid.h, _p(p, _f64p), _p(out, _u8p), out.size, C.byref(size), C.byref(w), C.byref(h),
+                                          C.byref(res), _p(slice_pose, _f64p), C.byref(stats)), "dliom_grid_xray_texture_gzip")
+    result = (w.value, h.value, res.value, slice_pose, out[:size.value].tobytes())
+    return result + (stats.as_dict(),) if with_stats else result
+
+
+def _node_clouds_to_pbstream(self, first=0, count=None, max_points_per_chunk=0, capacity=None, fill=0):
+    """The nodes' NodeRangeData messages as ProtoStreamWriter::WriteProto writes them: the 8-byte little-endian size of the
+    gzip member, then the member, a record a node (dliom_node_clouds_to_pbstream).  capacity: default the bound that never
+    fails -> (bytes, offsets (count + 1), stats, gzip stats, status OK or ERR_CAPACITY)"""
+    first, count = self._range(first, count)
+    if capacity is None:
+        capacity = 0
+        for i in range(first, first + count):
+            info = self.info(i)
+            capacity += 8 + gzip_bound(192 + NODE_RANGE_MAX_RECORD * (info["num_returns"] + info["num_misses"]))
+    limits = NodeCloudsLimits(int(max_points_per_chunk))
+    out = np.full(max(int(capacity), 1), fill, dtype=np.uint8)
+    offsets, stats, gz = np.zeros(count + 1, dtype=np.int64), NodeCloudsStats(), GzipStats()
+    status = self._L.dliom_node_clouds_to_pbstream(self.h, first, count, C.byref(limits), _p(out, _u8p), int(capacity), _p(offsets, _i64p),
+                                                   C.byref(stats), C.byref(gz))
+    if status not in (OK, ERR_CAPACITY):
+        _check(status, "dliom_node_clouds_to_pbstream")
+    return out, offsets, stats.as_dict(), gz.as_dict(), status
+
+
+NodeClouds.to_pbstream = _node_clouds_to_pbstream

@@ -322,6 +322,47 @@ int dliom_node_range_data_check(const uint8_t* bytes, int64_t size, dliom_node_c
 /* two new device clouds, the caller's to destroy */
 int dliom_node_range_data_from_proto(dliom_ctx* ctx, const uint8_t* bytes, int64_t size, dliom_node_cloud_info* info,
                                      dliom_cloud** returns, dliom_cloud** misses);
+/* ---- gzip on the device (common::FastGzipString's place: submap_3d.cc:172, proto_stream.cc:50-57) ----
+ * The last byte transformation before the wire, where the bytes already are.  zlib's stream cannot be reproduced in
+ * parallel and no consumer needs it -- both readers only inflate -- so the encoder is stated here, the device equals
+ * the host model of this statement (dliom_gzip_host) bit for bit, and zlib pins it as a decoder: the compressed bytes
+ * are PARITY UNPINNED AGAINST ZLIB.  Output depends on every rule below.
+ *  Member   1f 8b 08 00 00 00 00 00 04 03, the deflate stream, CRC-32 of the input and n mod 2^32, little-endian.
+ *  Chunks   the input is cut into chunks of DLIOM_GZIP_CHUNK bytes, the last may be shorter, empty input is one empty
+ *           chunk.  Chunks are independent: no match reaches before its chunk's first byte.  Every chunk's encoding
+ *           starts and ends on a byte boundary.  The last chunk carries BFINAL = 1 on its last block.
+ *  Tokens   of a chunk b[0, len), greedy, no lazy step, no distance penalty.  At position i <= len - 3 the candidate is
+ *           the greatest j < i in the chunk with b[j, j + 3) == b[i, i + 3), taken over all positions, not only token
+ *           starts.  L is the common prefix of b[j, ..) and b[i, ..), capped at min(258, len - i); overlap is allowed.
+ *           L >= 3: emit (length L, distance i - j) and continue at i + L; otherwise literal b[i] and continue at i + 1.
+ *  Fixed    one BTYPE = 01 block (RFC 1951's fixed codes, length 258 as code 285), then an empty stored block: 3 header
+ *           bits, zero padding to the byte, 00 00 ff ff.  An empty chunk has only the stored block.
+ *  Stored   one stored block holding the chunk, len + 5 bytes; used exactly when that is strictly smaller than the fixed form.
+ *  Bound    dliom_gzip_bound(n) = 18 + n + 5 * max(1, ceil(n / 4096)); a buffer of that size is never too small.
+ * The device calls run one launch chain for up to 8190 segments (chunk kernel, scan, sizes, gather), ONE polled read-back
+ * of the members' offsets and one download of exactly the compressed bytes; they wait for the stream.
+ * Refusals: NULL arguments, negative sizes, descending offsets DLIOM_ERR_INVALID_ARGUMENT; a capacity below what is needed
+ * DLIOM_ERR_CAPACITY with the sizes filled and nothing written past capacity; a segment above DLIOM_GZIP_MAX_SEGMENT bytes
+ * DLIOM_ERR_TOO_LARGE. */
+#define DLIOM_GZIP_CHUNK 4096
+#define DLIOM_GZIP_MAX_SEGMENT INT64_C(2147483647)
+typedef struct { int64_t chunks, chunks_stored, read_backs, bytes_downloaded; } dliom_gzip_stats;
+int64_t dliom_gzip_bound(int64_t n);  /* host; -1 for n < 0 */
+/* host, one thread: the statement itself.  *size is filled whenever the arguments are valid */
+int dliom_gzip_host(const uint8_t* bytes, int64_t n, uint8_t* out, int64_t capacity, int64_t* size);
+/* upload, compress, download; stats may be NULL */
+int dliom_gzip(dliom_ctx* ctx, const uint8_t* bytes, int64_t n, uint8_t* out, int64_t capacity, int64_t* size, dliom_gzip_stats* stats);
+/* k members back to back: segment s is bytes[offsets[s], offsets[s + 1]), its member out[out_offsets[s], out_offsets[s + 1]) */
+int dliom_gzip_segments(dliom_ctx* ctx, const uint8_t* bytes, const int64_t* offsets /* k + 1 */, int64_t k, uint8_t* out,
+                        int64_t capacity, int64_t* out_offsets /* k + 1 */, dliom_gzip_stats* stats);
+/* dliom_node_clouds_to_proto with every message leaving HBM as ProtoStreamWriter::WriteProto writes it: the 8-byte
+ * little-endian size of the gzip member, then the member; record i is bytes[byte_offsets[i], byte_offsets[i + 1]).  Chunked
+ * by the same limits; a chunk's messages never reach the host uncompressed.  bytes must not be NULL (the sizes are known
+ * only after the work); a capacity of 8 + dliom_gzip_bound(DLIOM_NODE_RANGE_MAX_HEADER + DLIOM_NODE_RANGE_MAX_RECORD *
+ * points) a node never returns DLIOM_ERR_CAPACITY.  gzip_stats may be NULL. */
+int dliom_node_clouds_to_pbstream(dliom_node_clouds* clouds, int64_t first, int64_t count, const dliom_node_clouds_limits* limits,
+                                  uint8_t* bytes, int64_t capacity, int64_t* byte_offsets /* count + 1 */,
+                                  dliom_node_clouds_stats* stats, dliom_gzip_stats* gzip_stats);
 /* ---- X-ray projections of a grid (mapping/3d/submap_3d.cc), computed on the device from the leaf pool ----
  * Both reproduce the reference's float arithmetic byte for byte: the cells with ValueToProbability(v) >= 0.501 in
  * HybridGrid::Iterator order, each cell centre index * resolution transformed in float and rounded with
@@ -344,6 +385,13 @@ int dliom_node_range_data_from_proto(dliom_ctx* ctx, const uint8_t* bytes, int64
  * Poses are (tx, ty, tz, qw, qx, qy, qz); the cell transform is global_submap_pose.cast<float>(). */
 int dliom_grid_xray_texture(const dliom_grid* grid, const double global_submap_pose7[7], uint8_t* cells, int64_t capacity,
                             int32_t* width, int32_t* height, double* resolution, double slice_pose7[7]);
+/* ... with the gzip step (submap_3d.cc:172): `cells` leaves HBM as ONE gzip member of dliom.h "gzip on the device", ready
+ * for the proto field, and never reaches the host uncompressed.  *cells_gz_size: the member's bytes; cells_gz NULL: the
+ * sizes and *cells_gz_size = dliom_gzip_bound(2 * width * height), a capacity that never fails (the projection's first
+ * phase runs, nothing is compressed).  An empty projection is the member of empty input.  gzip_stats may be NULL. */
+int dliom_grid_xray_texture_gzip(const dliom_grid* grid, const double global_submap_pose7[7], uint8_t* cells_gz, int64_t capacity,
+                                 int64_t* cells_gz_size, int32_t* width, int32_t* height, double* resolution, double slice_pose7[7],
+                                 dliom_gzip_stats* gzip_stats);
 /* D-LIOM's ProjectToCvMat (submap_3d.cc:381-443): the gravity-aligned, yaw-free top-down CV_8UC1 image for loop
  * detection.  The cells are rotated by Embed3D(Rigid2d::Rotation(-GetYaw(T))).cast<float>() *
  * Rigid3d::Rotation(T.rotation()).cast<float>() (no translation; transform.h:43-52, 110-115).
