@@ -114,6 +114,46 @@ def model(data, count=None):
     return out + struct.pack("<II", zlib.crc32(data), len(data) & 0xffffffff)
 
 
+def model_cached(data, memo, count=None):
+    """model(data, count), a chunk's form looked up in the dictionary `memo` under (chunk, final): for inputs of thousands
+    of chunks out of a few distinct ones (big_segment)"""
+    data = bytes(data)
+    chunks = [data[i:i + CHUNK] for i in range(0, len(data), CHUNK)] or [b""]
+    parts = [HEADER]
+    for k, chunk in enumerate(chunks):
+        key = (chunk, k + 1 == len(chunks))
+        if key not in memo:
+            memo[key] = chunk_form(*key)
+        form, stored = memo[key]
+        if count is not None:
+            count["chunks"] = count.get("chunks", 0) + 1
+            count["chunks_stored"] = count.get("chunks_stored", 0) + (1 if stored else 0)
+        parts.append(form)
+    parts.append(struct.pack("<II", zlib.crc32(data), len(data) & 0xffffffff))
+    return b"".join(parts)
+
+
+_chunk_kinds = None
+
+
+def chunk_kinds():
+    """six chunks of 4096 bytes: random bytes (stored form), zeros, random over 3 symbols, random over 2 symbols, b"ab"
+    repeated, all byte values x 16"""
+    global _chunk_kinds
+    if _chunk_kinds is None:
+        rng = random.Random(4096)
+        _chunk_kinds = [rng.randbytes(CHUNK), bytes(CHUNK), bytes(rng.randrange(3) for _ in range(CHUNK)),
+                        bytes(rng.randrange(2) for _ in range(CHUNK)), b"ab" * (CHUNK // 2), bytes(range(256)) * 16]
+        assert all(len(c) == CHUNK for c in _chunk_kinds)
+    return list(_chunk_kinds)
+
+
+def big_segment(n, seed):
+    """n bytes: the chunks of chunk_kinds() in a seeded random order, cut to n"""
+    kinds, rng = chunk_kinds(), random.Random(seed)
+    return b"".join(kinds[rng.randrange(len(kinds))] for _ in range(-(-n // CHUNK)))[:n]
+
+
 def _with_match(length=None, distance=None):
     """bytes whose greedy parse holds a match of that length, or of that distance: random filler, a random pattern, filler,
     the pattern again, then a byte that ends the match (checked by the host test with token_lengths / token_distances)"""
